@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """bench.py -- queries/s of the MI355X RaBitQ engine at recall@10 >= 0.95 on the BASELINE.json
-workload (configs[2]: 100M x 128 synthetic, 4096 lists, nprobe 64, one GPU), with the scan kernel's
-roofline figures and the CPU baseline (oracle port of the reference's AVX2 path) in the same line.
+workload (configs[2]: 100M x 128 synthetic, 4096 lists, nprobe 64, one GPU).
 
 A "step" is one pass of the hot path (rotate -> coarse rank -> per-list query quantise -> binary
 scan -> rerank -> ordered replay) over one batch of synthetic queries that are already resident
@@ -9,7 +8,15 @@ in HBM.  N > 1: one process per GPU (torch.distributed / RCCL); every rank index
 100M-vector shard under the shared centroid set, answers the same batch against its shard, and
 the per-shard top-k are merged with one all-gather per batch (rabitq_amd/sharding.py).
 
+A plain run builds the index, warms up, times --steps steps and prints one JSON line (the roofline
+figures in it come from the timed steps' own counters).  --full adds everything else, in the same
+process and the same line: ground truth and recall, the per-kernel breakdown, two batches in flight,
+small batches, single queries, the host-pointer entry, the batch sweep, the CPU baseline (oracle port
+of the reference's AVX2 path) and the secondary configurations.  --dump-outputs DIR writes what the
+last timed step returned as DIR/<name>.npy (seeded inputs: two builds compare output for output).
+
     python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full
 """
 import argparse
 import json
@@ -77,7 +84,7 @@ def main():
                          "without torch binds); torch = the same step assembled from the per-call entries and "
                          "torch.distributed collectives (also the in-process fallback if the C-ABI step fails in warm-up)")
     ap.add_argument("--secondary", action=argparse.BooleanOptionalAction, default=True,
-                    help="one-GPU runs also measure, in the same process and into the same JSON line (`secondary`), the hard "
+                    help="--full one-GPU runs also measure, in the same process and into the same JSON line (`secondary`), the hard "
                          "distribution and BASELINE configs[3] (100M x 768); --no-secondary skips them")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="engine option for this run (rq_set_option; e.g. stage_growth=16, rerank_shadow=0): experiments only, "
@@ -98,6 +105,13 @@ def main():
     ap.add_argument("--pipeline", type=int, default=1,
                     help="batches kept in flight in the timed loop (rq_query_batch_device_begin/_end); 1 = one blocking "
                          "call per step (default: per-kernel times are then clean); see --two-in-flight")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: ground truth and recall (--gt-queries), "
+                         "the per-kernel breakdown, --two-in-flight, --small-batch, the single-query loop, the host-pointer entry, "
+                         "--batch-sweep, the CPU baseline and the --secondary configurations.  Off: build, warm up, time the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned as DIR/distances.npy (float32), "
+                         "DIR/ids.npy (float64) and DIR/counts.npy (float32)")
     args = ap.parse_args()
     explicit_workload = (args.vectors is not None or args.dim != 128 or args.distribution != "easy" or args.emulate_world > 1 or
                          args.batch is not None)
@@ -148,9 +162,9 @@ def main():
         _ix.set_option(name, int(val))
 
     ctx = {"world": world, "rank": rank, "dev": dev}
-    line = run_workload(args, ctx, extras=True)
+    line = run_workload(args, ctx, extras=args.full, dump_dir=args.dump_outputs)
     # ---- the configurations only the builder had run so far, measured in the SAME process into the SAME line ------------
-    if world == 1 and not args.sharded_path and args.secondary and not explicit_workload:
+    if world == 1 and args.full and not args.sharded_path and args.secondary and not explicit_workload:
         import copy
         sec = {}
         for name, over in (("hard_distribution_100Mx128", {"distribution": "hard"}),
@@ -170,7 +184,7 @@ def main():
                 traceback.print_exc()
                 sec[name] = {"error": f"{type(e).__name__}: {e}"}
         line["secondary"] = sec
-    if world == 8 and args.secondary and not explicit_workload:
+    if world == 8 and args.full and args.secondary and not explicit_workload:
         # BASELINE configs[4] (1B x 128 over 8 GPUs; k is not given there: 32 768 = 4096 per GPU) next to the
         # 100M-per-GPU point of the scaling curve: 125M vectors per GPU, same lists / batch, same process group
         import copy
@@ -191,9 +205,10 @@ def main():
         dist.destroy_process_group()
 
 
-def run_workload(args, ctx, extras=True):
+def run_workload(args, ctx, extras=True, dump_dir=None):
     """Build the index of one workload, run the timed steps, return the bench line (a dict).  extras: the small-batch /
-    single-query / two-in-flight / CPU-baseline legs of the headline run."""
+    single-query / two-in-flight / CPU-baseline legs of the headline run.  args.full: ground truth and the per-kernel
+    breakdown step.  dump_dir: where the last timed step's results go (dump_outputs)."""
     import torch
     import torch.distributed as dist
     import rabitq_amd
@@ -256,7 +271,7 @@ def run_workload(args, ctx, extras=True):
     # a whole: 100M x 768 would not fit beside its own cluster-ordered copy) ------------------------------------
     # Ground truth in f64 on purpose: the f32 GEMM form |q|^2 - 2 q.x + |x|^2 cancels catastrophically here (neighbour
     # distances differ by ~0.1 under norms of ~160) and an f32 library GEMM gave a wrong ground truth.
-    ngt = min(args.gt_queries, B)
+    ngt = min(args.gt_queries, B) if args.full else 0
     qg = queries[:ngt].double()
     best_d = torch.full((ngt, topk), float("inf"), device=dev, dtype=torch.float64)
     best_i = torch.full((ngt, topk), -1, device=dev, dtype=torch.int64)
@@ -289,7 +304,7 @@ def run_workload(args, ctx, extras=True):
     gt = best_i.cpu().numpy()
     del best_d, best_i, qg, qn
     torch.cuda.empty_cache()     # the engine sizes the HBM tier of the raw vectors by what is free now
-    log(f"pass 1 (rotate, assign, quantise) + ground truth done ({time.time() - t0:.1f}s)")
+    log(f"pass 1 (rotate, assign, quantise){' + ground truth' if ngt else ''} done ({time.time() - t0:.1f}s)")
     tb = time.perf_counter()
     builder.order()
     build_s += time.perf_counter() - tb
@@ -482,9 +497,11 @@ def run_workload(args, ctx, extras=True):
     fence()
     rabitq_amd.metrics_reset()
     t1 = time.perf_counter()
-    run_steps(args.steps, True, rotate=True)
+    res = run_steps(args.steps, True, rotate=True)
     fence()
     elapsed = time.perf_counter() - t1
+    if dump_dir is not None and rank == 0:   # (before any later leg re-uses the output buffers)
+        dump_outputs(dump_dir, *(t.cpu().numpy() for t in res))
     qsel[0] = 0
     # the same loop with two batches in flight: one batch's HBM-bound stages overlap the other's compute-bound scan
     overlap = None
@@ -500,16 +517,18 @@ def run_workload(args, ctx, extras=True):
                    "note": "rq_query_batch_device_begin/_end; per-kernel times are not clean in this mode, so the headline "
                            "`value` and the roofline figures are taken with one batch at a time"}
     # per-kernel-group breakdown from ONE extra, untimed step (an event pair per group costs ~10 us of stream time each)
-    rqi.set_profiling(1)
-    extra_prof.clear()
-    qsel[0] = 0
-    res = step()   # (set 0: also the batch whose first `ngt` queries have a ground truth)
-    fence()
-    breakdown = {}
-    for pr in [rqi.last_profile()] + extra_prof:   # a multi-GPU step is two engine calls
-        for key, v in pr.items():
-            if key.startswith("ms_"):
-                breakdown[key[3:]] = round(breakdown.get(key[3:], 0.0) + v, 3)
+    breakdown = None
+    if args.full:
+        rqi.set_profiling(1)
+        extra_prof.clear()
+        qsel[0] = 0
+        res = step()   # (set 0: also the batch whose first `ngt` queries have a ground truth)
+        fence()
+        breakdown = {}
+        for pr in [rqi.last_profile()] + extra_prof:   # a multi-GPU step is two engine calls
+            for key, v in pr.items():
+                if key.startswith("ms_"):
+                    breakdown[key[3:]] = round(breakdown.get(key[3:], 0.0) + v, 3)
     # share of the matrix-core scan's 32x32 sub-tile steps that were flagged by the integer gate and took the exact f32 path
     # (always-on counters of the timed steps)
     ep = {"matrix_exact_steps": prof.get("matrix_exact_steps", 0), "matrix_subtile_steps": prof.get("matrix_subtile_steps", 0)}
@@ -524,7 +543,7 @@ def run_workload(args, ctx, extras=True):
     # ---- recall@topk on the ground-truth subset ------------------------------------------------------
     rd, ri, rn = res
     ri = ri.cpu().numpy()
-    recall = float(np.mean([len(set(ri[q, :topk].tolist()) & set(gt[q].tolist())) / topk for q in range(ngt)]))
+    recall = float(np.mean([len(set(ri[q, :topk].tolist()) & set(gt[q].tolist())) / topk for q in range(ngt)])) if ngt else None
     m = rabitq_amd.metrics()
 
     # ---- roofline of the dominant kernel ----------------------------------------------------------------
@@ -673,7 +692,7 @@ def run_workload(args, ctx, extras=True):
                        "distribution": args.distribution if not hard else
                        f"hard: centre std = {args.hard_centre_ratio} x sigma (overlapping clusters), Zipf({args.zipf}) list sizes, "
                        f"centroids trained by rq_kmeans_device"},
-            "recall_at_10": round(recall, 4), "recall_queries": ngt, "build_seconds": round(build_s, 2), "build": build_info,
+            "recall_at_10": None if recall is None else round(recall, 4), "recall_queries": ngt, "build_seconds": round(build_s, 2), "build": build_info,
             "rough_per_query": m["rough"] / max(m["query"], 1), "precise_per_query": m["precise"] / max(m["query"], 1),
             "kernel_ms_per_step": breakdown, "scan_ms_per_step_timed": round(prof["ms_scan"] / args.steps, 3),
             "rerank_candidates_per_query": prof["rerank_candidates"] / (B * args.steps),
@@ -709,6 +728,26 @@ def run_workload(args, ctx, extras=True):
     del outs, out_d, out_i, out_n, queries, query_sets, res, rd, rn
     torch.cuda.empty_cache()
     return line
+
+
+def dump_outputs(out_dir, dist, ids, counts, limit_bytes=60_000_000):
+    """What a caller of the timed path receives from one step: distances (float32), ids (float64, exact for every 32-bit
+    id) and per-query result counts (float32).  Slots at or past a query's count hold no result: +inf / -1.  Past
+    `limit_bytes` in all (a batch over many GPUs), a fixed seeded sample of the queries, their row numbers in rows.npy."""
+    topk = dist.shape[1]
+    valid = np.arange(topk)[None, :] < counts[:, None]
+    arrays = {"distances": np.where(valid, dist, np.inf).astype(np.float32),
+              "ids": np.where(valid, ids, -1).astype(np.float64),
+              "counts": counts.astype(np.float32)}
+    per_row = sum(a[0].nbytes for a in arrays.values())
+    if len(counts) * per_row > limit_bytes:
+        rows = np.sort(np.random.default_rng(0).choice(len(counts), limit_bytes // (per_row + 8), replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {out_dir}: " + ", ".join(f"{name}{list(a.shape)}" for name, a in arrays.items()))
 
 
 def batch_sweep(idx, centres, qweights, sigma, dev, d, nprobe, topk, sizes):

@@ -6,6 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 TAG=$1; shift
 K=$PWD/gpurun_out/kt_$TAG; rm -rf $K
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $K -- python3 bench.py --steps 3 --warmup 3 --no-cpu-baseline --no-two-in-flight --no-secondary --small-batch 0 --gt-queries 100 "$@" \
+    --full \
     > gpurun_out/tl_$TAG.json 2> gpurun_out/tl_$TAG.log || { tail -5 gpurun_out/tl_$TAG.log; exit 1; }
 python3 - "$K" > gpurun_out/tl_$TAG.txt <<'PY'
 import csv, glob, sys

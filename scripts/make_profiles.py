@@ -28,7 +28,7 @@ shutil.copy(stats, os.path.join(OUT, f"{ROUND}_kernel_stats_full.csv"))
 ours = [r for r in rows if not any(t in r["Name"] for t in ("at::native", "Cijk_", "__amd_rocclr", "at::cuda", "rocprim", "hipcub"))]
 with open(os.path.join(OUT, f"{ROUND}_kernel_stats.csv"), "w") as f:
     bcfg = json.load(open(newest("bench_final.json")))["config"]
-    f.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-two-in-flight --no-secondary --no-batch-sweep --small-batch 0\n")
+    f.write("# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-two-in-flight --no-secondary --no-batch-sweep --small-batch 0\n")
     f.write(f"# ({bcfg['workload']}: 2 warm-up + 3 timed + 1 breakdown query batches -- every scan_mfma_kernel launch in this table is a\n")
     f.write("#  full-batch launch, every launch alone on the device --, 68 single queries, one streamed 100M build); engine kernels only,\n")
     f.write("#  torch data-generation / ground-truth kernels are in the _full file\n")
@@ -74,7 +74,7 @@ traffic = {
     "config": {"vectors": bench["config"]["n_per_gpu"], "dim": bench["config"]["dim"], "lists": bench["config"]["lists_total"] // bench["n_gpus"],
                "nprobe": bench["config"]["nprobe"], "batch": bench["config"]["batch"],
                "distribution": "hard" if str(bench["config"].get("distribution", "easy")).startswith("hard") else "easy"},
-    "source": "rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-two-in-flight --gt-queries 10 "
+    "source": "rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-two-in-flight --gt-queries 10 "
               f"--small-batch 0 ({bench['config']['workload']})",
     "correction": "gfx950: FETCH_SIZE reports 1/2 of wide coalesced reads (MI355X_MICROARCH.md, HBM section) -> x2",
     "dominant_launch": {"kernel": launches[-1]["kernel"] + " (final stage: stream positions past the first list)",
