@@ -77,8 +77,8 @@ typedef struct {
  * scan's step counters in rq_profile_t are always filled, new option "scan_gate", "coarse_impl" = 3 is back with a new meaning,
  * rq_profile_t.reserved became coarse_fallback_rows, .reserved2 matrix_additive_launches; later in revision 4, additions only: "coarse_impl" = 4,
  * "coarse_tiled_from", "rerank_shadow" = 2 -- the new default; 0.5.0: option "split_rows", rq_info_t.split_rows appended, RQ_ARR_BASE
- * refused for split rows as for tiers).  A host checks rq_abi_version() ==
- * RQ_ABI_VERSION once after loading the library. */
+ * refused for split rows as for tiers; 0.6.0: filtered queries -- rq_filter_* and rq_query_batch*_filtered, additions only).
+ * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
 const char *rq_version(void);
@@ -202,6 +202,34 @@ rq_status rq_query_batch_device_begin(const rq_index *idx, const float *d_querie
                                       float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n,
                                       rq_ticket **out_ticket);
 rq_status rq_query_batch_device_end(rq_ticket *ticket);
+
+/* ---- filtered queries: answer from a subset of the index (an allow-list of vector ids) ------------------------ */
+/* A filter is a set of admitted ids: the original row ids that map_ids holds (global ids on a shard carved by rq_shard_index).
+ * A filtered query returns exactly what the unfiltered query returns on the SUB-INDEX: the same dim, rotation, centroids and
+ * k, every list keeping only its admitted rows in their stored order (lists may become empty) -- what rq_from_arrays builds from
+ * the arrays with the other rows removed.  "Exactly" covers the ids (heap-internal order for the heap ranker, ascending for the
+ * heuristic one), the distance bits, out_n, the status (RQ_ERR_EMPTY where the heuristic ranker of the sub-index finds nothing)
+ * and the counters: rough counts the admitted rows of the probed lists only, precise is the sub-index's, query goes up by nq.
+ * The reference has no counterpart (its README lists insert / update / delete as missing; on an immutable IVF index a query-time
+ * allow-list is how deletion is done).
+ *
+ * allow_bits: bit (id & 31) of word id >> 5 set = id admitted; ids >= nbits are not admitted (nbits <= 2^32; allow_bits may be
+ * NULL when nbits == 0: nothing is admitted).  Host or device memory (bits_on_device).  The filter is made once -- one pass over
+ * map_ids into a position bitmap (n / 8 bytes) and per-list admitted counts --, belongs to `idx` (used with another index:
+ * RQ_ERR_INVALID), is read-only once made, may be used by concurrent queries, and must be freed before its index. */
+typedef struct rq_filter rq_filter;
+rq_status rq_filter_create(const rq_index *idx, const uint32_t *allow_bits, uint64_t nbits, int bits_on_device,
+                           rq_filter **out);
+rq_status rq_filter_rows(const rq_filter *f, uint64_t *out_admitted); /* rows of the index the filter admits */
+void rq_filter_free(rq_filter *f);
+/* rq_query_batch / rq_query_batch_device with a filter (filter == NULL: the unfiltered call).  Batches of <= 64 queries take the
+ * staged launches, not the small-batch path (option "small_batch"), when filtered. */
+rq_status rq_query_batch_filtered(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq,
+                                  uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank, float *out_dist,
+                                  uint32_t *out_id, uint32_t *out_n);
+rq_status rq_query_batch_device_filtered(const rq_index *idx, const rq_filter *filter, const float *d_queries,
+                                         uint32_t nq, uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank,
+                                         float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n);
 
 /* ---- sharded deployments (one index shard per GPU / process) ----------------------------------- */
 /* The coarse ranking of src/rabitq.rs:283-297 restricted to lists [list_lo, list_hi): the `probe`

@@ -16,6 +16,10 @@ struct QueryParams {
     // sum of the survivors instead of nq x the worst query)
     bool seg_final = false;
     bool ext_lists = false;  // the probe lists come from the caller: no coarse ranking in the pass (and no nq x k distance matrix)
+    // Filtered pass (rq_query_batch*_filtered): only the filter's rows can survive the scan, the pairs whose list admits nothing
+    // are settled before the quantisation, and the rough counter counts admitted rows.  Every pass of the call carries it (overlapped
+    // passes, overflow re-runs, arena repeats).
+    const rq_filter *filter = nullptr;
 };
 
 #define RQ_DEFAULT_CAP 4096u
@@ -52,7 +56,7 @@ static rq_status ws_prepare(const rq_index *idx, Workspace &ws, const QueryParam
     RQC(ws.runs.ensure(nq * qp.cap));
     // second run directory, through which long directories (> 512 runs) are ordered: only once the index has shown
     // that it produces them (or with enlarged buffers); until then a stray long directory is bitonic-sorted in place
-    ws.use_runs_tmp = qp.cap > RQ_DEFAULT_CAP || qp.seg_final || idx->big_dirs_hint.load() > 0;
+    ws.use_runs_tmp = qp.cap > RQ_DEFAULT_CAP || qp.seg_final || hints_of(idx, qp.filter).big_dirs.load() > 0;
     if (ws.use_runs_tmp) RQC(ws.runs_tmp.ensure(nq * qp.cap));
     RQC(ws.surv_cnt.ensure(nq));
     RQC(ws.heap_len.ensure(nq));
@@ -88,7 +92,7 @@ static rq_status finish_pass(const rq_index *idx, Workspace &ws, PassResult *res
     res->precise = ws.h_totals[1];
     res->overflowed = ws.h_totals[2];
     res->max_need = ws.h_totals[4];
-    if (rq_large_batch(nq)) const_cast<rq_index *>(idx)->big_dirs_hint.store((uint32_t)ws.h_totals[7]);
+    if (rq_large_batch(nq)) hints_of(idx, ws.pend_filter).big_dirs.store((uint32_t)ws.h_totals[7]);
     // The additive gate is a looser test than the rank-5 threshold it replaces: an index / workload on which it sends more than
     // 3 % of the sub-tile steps down the exact path (each costs ~10 plain steps) goes back to the bf16 threshold MFMA for good
     // (results do not depend on the choice; option scan_gate pins it)
@@ -105,7 +109,7 @@ static rq_status finish_pass(const rq_index *idx, Workspace &ws, PassResult *res
         prof_acc->ms_rerank += ms[PF_RERANK], prof_acc->ms_sort += ms[PF_SORT];
         if (!ws.pend_matrix_ranges.empty()) {  // pairs scored by those launches: per query, its stream length clipped to the range
             std::vector<unsigned long long> len(nq);
-            HIPC(hipMemcpy(len.data(), ws.rough_cnt.p, (size_t)nq * 8, hipMemcpyDeviceToHost));
+            HIPC(hipMemcpy(len.data(), ws.pend_filter ? ws.stream_len.p : ws.rough_cnt.p, (size_t)nq * 8, hipMemcpyDeviceToHost));
             for (const StreamRange &r : ws.pend_matrix_ranges)
                 for (uint32_t b = 0; b < nq; ++b)
                     prof_acc->matrix_pairs += std::min<unsigned long long>(len[b], r.s_hi) - std::min<unsigned long long>(len[b], r.s_lo);
@@ -159,6 +163,11 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
     const uint32_t npairs = nq * nprobe;
     bool listed = false;  // sharded pass: the pairs whose list has members here are listed (ws.live_list, nlive of them)
     uint32_t nlive = 0;
+    const rq_filter *filt = qp.filter;
+    ws.pend_filter = filt;
+    // shortest list of the pass: a filtered pass settles the pairs whose list admits nothing as empty ones, so no slot bound can be
+    // derived from stream positions (as on a shard)
+    const uint32_t min_len = filt ? 0u : idx->min_list_len;
     hipStream_t st = ws.stream;
     ws.pend_prefiltered = false;
     Prof &pf = ws.prof;
@@ -231,7 +240,8 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
 
     // ---- small batches: few, fat launches (kernels_small.h) -------------------------------------------------------
     const bool sb_w = W == 1 || W == 2 || W == 4 || W == 8 || W == 12 || W == 16;
-    bool small = g_small_batch.load() == 0 && nq <= RQ_SB_MAX_NQ && !ext_cluster && !d_row_map && !qp.thr_init && sb_w &&
+    // (filtered passes take the staged launches: the small-batch kernels have no filtered form yet)
+    bool small = g_small_batch.load() == 0 && nq <= RQ_SB_MAX_NQ && !ext_cluster && !d_row_map && !qp.thr_init && !filt && sb_w &&
                  k <= RQ_SB_MAX_K && nprobe <= 64 && topk <= RQ_SB_MAX_TOPK && qp.cap <= 4 * RQ_DEFAULT_CAP;
     bool sb_results_done = false;   // results and totals were written by the small-batch kernels (heap ranker)
     bool sb_fused_finish = false;   // the final stage ends in sb_finish_kernel
@@ -354,22 +364,25 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
         // The 4-bit operand (64 of a pair's ~210 bytes at dim 128) is read by the VALU scans only, and a VALU stage that ends at stream
         // position s_hi cannot reach probe slot s_hi / (shortest list) or beyond: the matrix-core stages' pairs are written without it.
         uint32_t qn_slots = nprobe;
-        if (qn && q6 && !ext_cluster && idx->min_list_len > 0) {
+        if (qn && q6 && !ext_cluster && min_len > 0) {
             uint32_t reach = 0;
             for (const Stage &sg : stages)
                 if (!stage_on_matrix(sg))
-                    reach = std::max<uint32_t>(reach, sg.s_hi == 0xFFFFFFFFu ? nprobe : (uint32_t)std::min<uint64_t>(nprobe, (uint64_t)(sg.s_hi - 1) / idx->min_list_len + 1));
+                    reach = std::max<uint32_t>(reach, sg.s_hi == 0xFFFFFFFFu ? nprobe : (uint32_t)std::min<uint64_t>(nprobe, (uint64_t)(sg.s_hi - 1) / min_len + 1));
             qn_slots = reach;
         }
         // an index most of whose lists are empty (a shard of a multi-GPU deployment: the probe lists name the lists of every shard):
         // the pairs with nothing to scan are settled by one thread each, the quantisation runs over the listed others
-        listed = idx->nonempty_lists * 2 < k && npairs >= 65536 && g_pair_split.load() != 0 &&
+        // -- and a filtered pass, whose pairs with nothing admitted are settled the same way (a filter correlated with the clustering: a
+        // tenant, a region, leaves most probed lists empty)
+        listed = (filt || (idx->nonempty_lists * 2 < k && npairs >= 65536)) && g_pair_split.load() != 0 &&
                  (dim == 64 || dim == 128 || dim == 256 || dim == 512 || dim == 768 || dim == 1024);
         if (listed) {
             RQC(ws.live_list.ensure((size_t)npairs + 1));
             HIPC(hipMemsetAsync(ws.live_list.p + npairs, 0, 4, st));
-            pair_split_kernel<<<ceil_div(npairs, 4096), 1024, 0, st>>>(idx->offsets.p, probe_cluster, probe_dist, npairs, nprobe, k, ws.scal.p,
-                                                                       ws.live_list.p, ws.live_list.p + npairs);
+            // (filtered: the split reads list lengths from the sub-index's offsets -- a list that admits nothing is an empty one)
+            pair_split_kernel<<<ceil_div(npairs, 4096), 1024, 0, st>>>(filt ? filt->sub_off.p : idx->offsets.p, probe_cluster, probe_dist, npairs,
+                                                                       nprobe, k, ws.scal.p, ws.live_list.p, ws.live_list.p + npairs);
             // the launches over the listed pairs are sized by their number: one small copy and a wait (tens of microseconds against
             // the milliseconds that 7 of 8 idle lane groups cost)
             // (into the workspace's pinned block, not a pageable stack word; the wait is the price of sizing the launches below by the
@@ -406,7 +419,12 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
                                                              scan_is_fused(W) ? nullptr : ws.planes.p,   // only the generic-W scan reads bit planes
                                                              qn, q6, nullptr, k, 1u);
     }
-    pair_prefix_kernel<<<ceil_div(nq, 4), 256, 0, st>>>(ws.scal.p, nq, nprobe, ws.rough_cnt.p);
+    if (filt) {  // (the rough counter: the admitted rows of the probed lists; the stream lengths go to stream_len)
+        RQC(ws.stream_len.ensure(nq));
+        pair_prefix_filtered_kernel<<<ceil_div(nq, 4), 256, 0, st>>>(ws.scal.p, nq, nprobe, ws.rough_cnt.p, probe_cluster, filt->sub_off.p, k,
+                                                                     ws.stream_len.p);
+    } else
+        pair_prefix_kernel<<<ceil_div(nq, 4), 256, 0, st>>>(ws.scal.p, nq, nprobe, ws.rough_cnt.p);
     if (rq_large_batch(nq)) {  // large batch: rerank queries of the same nearest list back to back (cache locality of the row gather)
         HIPC(hipMemsetAsync(ws.q_hist.p, 0, (size_t)(k + 2) * 4, st));
         order_count_kernel<<<ceil_div(nq, 256), 256, 0, st>>>(probe_cluster, nprobe, nq, k, ws.q_hist.p);
@@ -428,7 +446,7 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
     ws.pend_seg_slots = 0;
     ws.pend_additive = false, ws.pend_matrix_stages = 0;
     // persistent blocks of the long-directory ordering: sized by how many such directories recent passes produced
-    const uint32_t big_hint = idx->big_dirs_hint.load();
+    const uint32_t big_hint = hints_of(idx, filt).big_dirs.load();
     const uint32_t mid_blocks = big_hint == 0 ? 64u : std::min(4096u, std::max(256u, big_hint / 4));
     const uint32_t tile = scan_tile(W);
     const uint64_t avg_len = std::max<uint64_t>(1, idx->n / std::max<uint32_t>(idx->nonempty_lists, 1));
@@ -453,7 +471,8 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
         // (an arena stage, below: a stage that can exceed the uniform survivor capacity; its scan instantiation has its own tile)
         const bool arena_stage = qp.seg_final && span > qp.cap && scan_is_fused(W) && rq_large_batch(nq);
         const int gate_opt = g_scan_gate.load();
-        const bool additive = use_mfma && !arena_stage && scan_has_additive(W) && idx->list_uref.p != nullptr && gate_opt != 1 &&
+        // (filtered stages run the bf16 threshold form: the filtered instantiations exist for that gate only)
+        const bool additive = use_mfma && !arena_stage && !filt && scan_has_additive(W) && idx->list_uref.p != nullptr && gate_opt != 1 &&
                               (gate_opt == 2 || !idx->additive_loose.load());
         pf.begin(PF_GROUP);
         ScanArgs a{};
@@ -463,8 +482,8 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
         // slots of every query need to be looked at in the early stages (not derivable when lists may be empty,
         // e.g. a shard that does not own every probed list)
         uint32_t slot_hi = nprobe;
-        if (cluster_major && idx->min_list_len > 0 && !ext_cluster && sg.s_hi != 0xFFFFFFFFu)
-            slot_hi = (uint32_t)std::min<uint64_t>(nprobe, (uint64_t)(sg.s_hi - 1) / idx->min_list_len + 1);
+        if (cluster_major && min_len > 0 && !ext_cluster && sg.s_hi != 0xFFFFFFFFu)
+            slot_hi = (uint32_t)std::min<uint64_t>(nprobe, (uint64_t)(sg.s_hi - 1) / min_len + 1);
         const uint32_t stage_pairs = nq * slot_hi;
         bool ranked = false;
         if (cluster_major) {
@@ -530,6 +549,8 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
         sp.surv_cnt = ws.surv_cnt.p;
         sp.stat = ws.stat.p;  // 64 x {sub-tile steps, exact-path steps} of the matrix-core scan
         sp.list_uref = idx->list_uref.p, sp.grp_vref = ws.grp_vref.p;
+        sp.arena = arena_stage, sp.filtered = filt != nullptr;
+        a.x = filt ? filt->extra.p : nullptr;  // (an arena stage points it at its own ScanExtra below, the filter's bitmap included)
         a.cap = qp.cap;
         a.dbg = (uint32_t)g_scan_dbg.load();
         const uint32_t stage_tile = use_mfma ? scan_mfma_tile(W, arena_stage, additive) : tile;
@@ -566,7 +587,7 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
         if (arena_stage) {
             // capacity: what earlier batches needed (+ headroom), at least half the uniform buffers' worth; a shard holds
             // 1 / RQ_ARENA_SHARDS of it
-            uint64_t want = std::max<uint64_t>(idx->arena_hint.load(), (uint64_t)nq * qp.cap / 2);
+            uint64_t want = std::max<uint64_t>(hints_of(idx, filt).arena.load(), (uint64_t)nq * qp.cap / 2);
             unsigned long long total_slots = 0;
             uint32_t arena_rsub = 0;
             bool arena_retried = false;
@@ -588,7 +609,7 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
                 HIPC(hipMemsetAsync(ws.arena_fail.p, 0xFF, RQ_ARENA_SHARDS * 4, st));
                 ScanExtra hx{};
                 RQC(ws.arena_places.ensure(want));
-                hx.arena_places = ws.arena_places.p, hx.reserved = nullptr;
+                hx.arena_places = ws.arena_places.p, hx.allow = filt ? filt->pos_bits.p : nullptr;
                 hx.arena_recs = ws.arena_recs.p, hx.arena_runs = reinterpret_cast<uint4 *>(ws.arena_runs.p), hx.arena_cur = ws.arena_cur.p;
                 hx.arena_fail = ws.arena_fail.p;
                 {  // seven eighths of the arena in shards, the rest as the common area (what a full shard turns away: few, heavy blocks)
@@ -630,9 +651,10 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
             }
             ws.arena_failed = false;
             {  // remember what this stage needed
-                uint64_t cur = idx->arena_hint.load();
+                std::atomic<uint64_t> &arena_hint = hints_of(idx, filt).arena;
+                uint64_t cur = arena_hint.load();
                 const uint64_t learnt = std::max<uint64_t>(total_slots + total_slots * 3 / 5, arena_retried ? std::min<uint64_t>(want, 0xFFFF0000ull) : 0ull);
-                while (cur < learnt && !const_cast<rq_index *>(idx)->arena_hint.compare_exchange_weak(cur, learnt)) {}
+                while (cur < learnt && !arena_hint.compare_exchange_weak(cur, learnt)) {}
             }
             if (total_slots > ws.surv.count || total_slots > ws.runs.count || total_slots > ws.runs_tmp.count) {
                 const uint64_t grow = total_slots + total_slots / 8;
@@ -818,8 +840,8 @@ static rq_status validate_query(const rq_index *idx, const float *d_q, uint32_t 
 // batches overflowed the default capacity (cap_hint) used to size EVERY query of a pass for the worst one (learnt capacity
 // 32 768: 100 GB for a 65 536-query pass of the hard benchmark distribution); large batches now keep the default
 // capacity for the stages that cannot exceed it and give every other stage per-query segments.
-static uint32_t pass_capacity(const rq_index *idx, uint32_t remaining, bool seeded, bool *seg) {
-    const uint32_t hint = idx->cap_hint.load();
+static uint32_t pass_capacity(const rq_index *idx, uint32_t remaining, bool seeded, bool *seg, const rq_filter *filter = nullptr) {
+    const uint32_t hint = hints_of(idx, filter).cap.load();
     const int opt = g_seg_opt.load();
     *seg = !seeded && rq_large_batch(remaining) && scan_is_fused(idx->W) && (opt >= 2 || (opt == 1 && hint > RQ_DEFAULT_CAP));
     if (*seg) return RQ_DEFAULT_CAP;  // stages that cannot exceed it stay uniform, the others are segmented
@@ -828,13 +850,14 @@ static uint32_t pass_capacity(const rq_index *idx, uint32_t remaining, bool seed
 
 // queries per pass: survivor / run buffers are 32 B per slot per query (keep one pass under ~24 GiB) and
 // (query, list) pairs per pass <= 2^22 (bounds the per-pair buffers and every launch size)
-static uint32_t pass_queries(const rq_index *idx, uint32_t remaining, uint32_t probe, uint32_t cap0, bool seg, bool ext_lists = false) {
+static uint32_t pass_queries(const rq_index *idx, uint32_t remaining, uint32_t probe, uint32_t cap0, bool seg, bool ext_lists = false,
+                             const rq_filter *filter = nullptr) {
     // survivor records + run directory: 32 B per slot per query, 48 B when the pass also keeps the second directory buffer
     // (ws_prepare: capacities beyond the default, segmented passes, long directories); the budget is a third of the HBM that
     // was free once the index was resident (at least 4 GiB: an index that fills the HBM -- 100M x 768 -- still answers a
     // 32 768-query batch in ONE pass; split in two, every block of the matrix-core scan paid its start-up twice: a third
     // of that launch at dim 768)
-    const uint64_t slot_bytes = cap0 > RQ_DEFAULT_CAP || seg || idx->big_dirs_hint.load() > 0 ? 48 : 32;
+    const uint64_t slot_bytes = cap0 > RQ_DEFAULT_CAP || seg || hints_of(idx, filter).big_dirs.load() > 0 ? 48 : 32;
     // Probe lists supplied by the caller = a shard of a multi-GPU deployment: most of a query's probed lists live on other ranks
     // (empty here: skipped before any per-pair work), and the step's batch grows with the number of ranks so that a list still
     // meets as many queries as on one GPU -- cut into passes of 65 536 queries, each pass of an 8-GPU step would bring a list
@@ -859,8 +882,9 @@ static rq_status after_pass(rq_index *idx, Workspace *ws, const QueryParams &qp,
         // query (a loose threshold after an unlucky nearest list) must not shrink the passes of all later batches; beyond
         // the bound the outliers are simply re-run below with the capacity they asked for
         uint32_t want = pow2_ceil((uint32_t)std::min<uint64_t>(pr.max_need + pr.max_need / 4, RQ_MAX_CAP_HINT));
-        uint32_t cur = idx->cap_hint.load();
-        while (cur < want && !idx->cap_hint.compare_exchange_weak(cur, want)) {}
+        std::atomic<uint32_t> &cap_hint = hints_of(idx, qp.filter).cap;
+        uint32_t cur = cap_hint.load();
+        while (cur < want && !cap_hint.compare_exchange_weak(cur, want)) {}
     }
     if (!pr.overflowed) return RQ_OK;
     uint32_t cap = qp.cap, hcap = qp.hcap;
@@ -898,6 +922,7 @@ static rq_status after_pass(rq_index *idx, Workspace *ws, const QueryParams &qp,
             uint32_t m = (uint32_t)std::min<size_t>(chunk, over_rows.size() - o);
             QueryParams rq{m, len, probe, topk, heuristic, ncap, nhcap};
             rq.thr_init = qp.thr_init;  // indexed through the row map
+            rq.filter = qp.filter;
             RQC(ws_prepare(idx, rws, rq));
             RQC(sub_q.ensure((uint64_t)m * len));
             RQC(sub_rows.ensure(m));
@@ -960,8 +985,10 @@ static rq_status conclude_query(uint32_t nq, bool heuristic, const uint32_t *d_o
 static rq_status query_device(rq_index *idx, const float *d_q, uint32_t nq, uint32_t len, uint32_t probe,
                               uint32_t topk, bool heuristic, float *d_out_dist, uint32_t *d_out_id,
                               uint32_t *d_out_n, const uint32_t *ext_cluster = nullptr,
-                              const float *ext_dist = nullptr, Workspace *use_ws = nullptr, const float *ext_thr = nullptr) {
+                              const float *ext_dist = nullptr, Workspace *use_ws = nullptr, const float *ext_thr = nullptr,
+                              const rq_filter *filter = nullptr) {
     RQC(validate_query(idx, d_q, len, probe, topk, d_out_dist, d_out_id, d_out_n));
+    if (filter && filter->idx != idx) return fail(RQ_ERR_INVALID, "the filter was made for another index");
     if (nq == 0) return RQ_OK;
     rq_profile_t prof;
     memset(&prof, 0, sizeof prof);
@@ -981,8 +1008,8 @@ static rq_status query_device(rq_index *idx, const float *d_q, uint32_t nq, uint
     // queries 33.9 -> 32.6 ms per call).  Results are those of the passes run one after the other.
     if (!use_ws && !ext_cluster && !ext_thr && g_pass_overlap.load()) {
         bool seg0 = false;
-        const uint32_t cap_first = pass_capacity(idx, nq, false, &seg0);
-        const uint32_t first_nq = pass_queries(idx, nq, probe, cap_first, seg0);
+        const uint32_t cap_first = pass_capacity(idx, nq, false, &seg0, filter);
+        const uint32_t first_nq = pass_queries(idx, nq, probe, cap_first, seg0, false, filter);
         // (only with room for a second workspace: an index that fills the HBM -- configs[3] -- runs its passes one after the other;
         // rough size of a pass's buffers: survivor records + directories, per-pair records and operands, distances, ranker state)
         bool room = false;
@@ -1029,12 +1056,13 @@ static rq_status query_device(rq_index *idx, const float *d_q, uint32_t nq, uint
             for (uint32_t q0 = 0, step_nq = 0; q0 < nq; q0 += step_nq, slot ^= 1u) {
                 rq_status st = finish(fl[slot]);  // the pass before the previous one
                 bool seg = false;
-                const uint32_t cap0 = pass_capacity(idx, nq - q0, false, &seg);
-                step_nq = pass_queries(idx, nq - q0, probe, cap0, seg);
+                const uint32_t cap0 = pass_capacity(idx, nq - q0, false, &seg, filter);
+                step_nq = pass_queries(idx, nq - q0, probe, cap0, seg, false, filter);
                 Flight &f = fl[slot];
                 if (st == RQ_OK) {
-                    f.qp = QueryParams{step_nq, len, probe, topk, heuristic, cap0, std::max(cap0, std::max(RQ_DEFAULT_CAP, idx->cap_hint.load()))};
+                    f.qp = QueryParams{step_nq, len, probe, topk, heuristic, cap0, std::max(cap0, std::max(RQ_DEFAULT_CAP, hints_of(idx, filter).cap.load()))};
                     f.qp.seg_final = seg && rq_large_batch(step_nq);
+                    f.qp.filter = filter;
                     f.q0 = q0;
                     f.ws = ws_acquire(idx);
                     st = ws_prepare(idx, *f.ws, f.qp);
@@ -1073,12 +1101,13 @@ static rq_status query_device(rq_index *idx, const float *d_q, uint32_t nq, uint
     }
     for (uint32_t q0 = 0, step_nq = 0; q0 < nq; q0 += step_nq) {
         bool seg = false;
-        const uint32_t cap0 = pass_capacity(idx, nq - q0, ext_thr != nullptr, &seg);
-        step_nq = pass_queries(idx, nq - q0, probe, cap0, seg, ext_cluster != nullptr);
-        QueryParams qp{step_nq, len, probe, topk, heuristic, cap0, std::max(cap0, std::max(RQ_DEFAULT_CAP, idx->cap_hint.load()))};
+        const uint32_t cap0 = pass_capacity(idx, nq - q0, ext_thr != nullptr, &seg, filter);
+        step_nq = pass_queries(idx, nq - q0, probe, cap0, seg, ext_cluster != nullptr, filter);
+        QueryParams qp{step_nq, len, probe, topk, heuristic, cap0, std::max(cap0, std::max(RQ_DEFAULT_CAP, hints_of(idx, filter).cap.load()))};
         qp.seg_final = seg && rq_large_batch(step_nq);
         qp.thr_init = ext_thr ? ext_thr + q0 : nullptr;
         qp.ext_lists = ext_cluster != nullptr;
+        qp.filter = filter;
         RQC(ws_prepare(idx, *ws, qp));
         PassResult pr;
         const float *q_at = d_q + (uint64_t)q0 * len;

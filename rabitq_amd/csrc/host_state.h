@@ -195,6 +195,8 @@ struct Workspace {
     DevBuf<uint32_t> qnib;
     DevBuf<uint32_t> qf6;
     DevBuf<unsigned long long> rough_cnt, totals, surv_cnt, stat;
+    DevBuf<unsigned long long> stream_len;  // filtered passes: per query, the stream's length (rough_cnt holds the admitted rows)
+    const struct rq_filter *pend_filter = nullptr;  // the pending pass's filter (its stream lengths are in stream_len; its hints)
     DevBuf<float4> grp_vref;  // additive gate: per list, centre and half-range of v' over the stage's pairs (group_vrange_kernel)
     bool pend_additive = false;  // the pass ran a matrix-core stage with the additive gate (finish_pass reads its flag rate)
     uint32_t pend_matrix_stages = 0;  // matrix-core stages of the pass
@@ -269,6 +271,36 @@ struct rq_index {
     std::mutex tt_mu;
     std::map<uint32_t, std::unique_ptr<DevBuf<uint4>>> tile_tables;
 };
+
+// A query-time allow-list (rq_filter_create), in the index's own terms: one bit per cluster-order position and the admitted rows
+// of every list.  Made once, read-only afterwards (concurrent queries share it).
+struct rq_filter {
+    const rq_index *idx = nullptr;  // the index it was made for (another index is refused)
+    DevBuf<uint32_t> pos_bits;      // bit pos of word pos >> 5 = the row at position pos is admitted
+    DevBuf<uint32_t> sub_off;       // k + 1: list offsets of the sub-index (admitted rows of list c = sub_off[c + 1] - sub_off[c])
+    DevBuf<ScanExtra> extra;        // what the filtered scans read through ScanArgs::x outside arena stages: only `allow` is set
+    uint64_t rows = 0;              // admitted rows of the whole index
+    // what its passes learnt about their survivor buffers (as rq_index::cap_hint / arena_hint / big_dirs_hint): a filter whose rows
+    // are far from the queries lets many more candidates through than the unfiltered query, and must not resize the index's
+    // unfiltered passes -- nor they its
+    std::atomic<uint32_t> cap_hint{0};
+    std::atomic<uint64_t> arena_hint{0};
+    std::atomic<uint32_t> big_dirs_hint{0};
+};
+// The learnt survivor-buffer hints a pass reads and updates: the index's own, or the filter's on a filtered pass.
+struct PassHints {
+    std::atomic<uint32_t> &cap;
+    std::atomic<uint64_t> &arena;
+    std::atomic<uint32_t> &big_dirs;
+};
+static PassHints hints_of(const rq_index *idx, const rq_filter *f) {
+    if (f) {
+        rq_filter *m = const_cast<rq_filter *>(f);
+        return PassHints{m->cap_hint, m->arena_hint, m->big_dirs_hint};
+    }
+    rq_index *m = const_cast<rq_index *>(idx);
+    return PassHints{m->cap_hint, m->arena_hint, m->big_dirs_hint};
+}
 
 // ------------------------------------------------------------------------------------------------
 // small init kernels
@@ -523,29 +555,40 @@ static void launch_scan_chunks(const ScanArgs &a, F &&launch) {
 }
 
 #define SCAN_ARGS p.codes, p.factors, p.offsets, p.grp_start, p.recs, p.surv, p.runs, p.surv_cnt, p.tile_table, a
-template <bool ARENA>
+template <bool ARENA, bool FILT>
 static void launch_scan_t(const ScanPtrs &p, const ScanArgs &args, uint32_t W, hipStream_t st) {
     launch_scan_chunks(args, [&](const ScanArgs &a, dim3 g) {
         const dim3 b(256);
+#define RQ_SCAN_K(WW, CPL)                                                                        \
+    do {                                                                                          \
+        if constexpr (FILT) scan_kernel<WW, CPL, ARENA, true><<<g, b, 0, st>>>(SCAN_ARGS);         \
+        else scan_kernel<WW, CPL, ARENA><<<g, b, 0, st>>>(SCAN_ARGS);                             \
+    } while (0)
         switch (W) {
-            case 1: scan_kernel<1, 2, ARENA><<<g, b, 0, st>>>(SCAN_ARGS); break;
-            case 2: scan_kernel<2, 2, ARENA><<<g, b, 0, st>>>(SCAN_ARGS); break;
-            case 3: scan_kernel<3, 2, ARENA><<<g, b, 0, st>>>(SCAN_ARGS); break;
-            case 4: scan_kernel<4, 2, ARENA><<<g, b, 0, st>>>(SCAN_ARGS); break;
-            case 6: scan_kernel<6, 2, ARENA><<<g, b, 0, st>>>(SCAN_ARGS); break;
-            case 8: scan_kernel<8, 2, ARENA><<<g, b, 0, st>>>(SCAN_ARGS); break;
-            case 12: scan_kernel<12, 1, ARENA><<<g, b, 0, st>>>(SCAN_ARGS); break;
-            case 16: scan_kernel<16, 1, ARENA><<<g, b, 0, st>>>(SCAN_ARGS); break;
-            default:
-                if constexpr (!ARENA) scan_generic_kernel<<<g, b, 0, st>>>(SCAN_ARGS, W);  // (arena stages exist for the fused dims only)
+            case 1: RQ_SCAN_K(1, 2); break;
+            case 2: RQ_SCAN_K(2, 2); break;
+            case 3: RQ_SCAN_K(3, 2); break;
+            case 4: RQ_SCAN_K(4, 2); break;
+            case 6: RQ_SCAN_K(6, 2); break;
+            case 8: RQ_SCAN_K(8, 2); break;
+            case 12: RQ_SCAN_K(12, 1); break;
+            case 16: RQ_SCAN_K(16, 1); break;
+            default:  // (arena stages exist for the fused dims only)
+                if constexpr (!ARENA && FILT) scan_generic_filtered_kernel<<<g, b, 0, st>>>(SCAN_ARGS, W);
+                else if constexpr (!ARENA) scan_generic_kernel<<<g, b, 0, st>>>(SCAN_ARGS, W);
                 break;
         }
+#undef RQ_SCAN_K
     });
 }
-// args.x != nullptr: the arena instantiations (the stage appends to the shared arena, ScanExtra)
+// p.arena: the arena instantiations (the stage appends to the shared arena, ScanExtra); p.filtered: the filtered ones (args.x
+// holds the filter's position bitmap, together with the arena's fields in an arena stage)
 static void launch_scan(const ScanPtrs &p, const ScanArgs &args, uint32_t W, hipStream_t st) {
-    if (args.x) launch_scan_t<true>(p, args, W, st);
-    else launch_scan_t<false>(p, args, W, st);
+    if (p.filtered) {
+        if (p.arena) launch_scan_t<true, true>(p, args, W, st);
+        else launch_scan_t<false, true>(p, args, W, st);
+    } else if (p.arena) launch_scan_t<true, false>(p, args, W, st);
+    else launch_scan_t<false, false>(p, args, W, st);
 }
 // scan implementation: 0 = auto (matrix cores when many queries share each list, VALU otherwise),
 // 1 = VALU (v_dot8_u32_u4) only, 2 = matrix cores wherever the kernel exists (test hook)
@@ -583,9 +626,9 @@ static size_t scan_mfma_ring_bytes(uint32_t W, bool arena = false) {  // scan_mf
     const uint64_t slots = W <= 2 ? 4ull : (W >= 16 ? 5ull : 3ull);
     return slots * (32 * (12 * W + 2) + RQ_REC_TAIL * 32) * 4;
 }
-template <int W, int NT, bool ARENA, bool ADD = false>
+template <int W, int NT, bool ARENA, bool ADD = false, bool FILT = false>
 static void launch_scan_mfma_t(const ScanPtrs &p, const ScanArgs &a, dim3 g, hipStream_t st) {
-    scan_mfma_kernel<W, NT, ARENA, ADD><<<g, dim3(64 * scan_mfma_waves<W, ARENA>()), scan_mfma_ring_bytes(W, ARENA), st>>>(p.codes, p.factors, p.offsets, p.grp_start, p.grp_cnt,
+    scan_mfma_kernel<W, NT, ARENA, ADD, FILT><<<g, dim3(64 * scan_mfma_waves<W, ARENA>()), scan_mfma_ring_bytes(W, ARENA), st>>>(p.codes, p.factors, p.offsets, p.grp_start, p.grp_cnt,
                                                                                     p.recs, p.surv, p.runs, p.surv_cnt, p.stat, p.tile_table, p.list_uref, p.grp_vref, a);
 }
 // the additive-gate instantiations (dim 64 / 128, uniform survivor buffers)
@@ -599,25 +642,28 @@ static void launch_scan_mfma_add(const ScanPtrs &p, const ScanArgs &args, uint32
         }
     });
 }
-// callers check scan_has_mfma(W) first; args.x != nullptr: the arena instantiations
-template <bool ARENA>
+// callers check scan_has_mfma(W) first; p.arena: the arena instantiations, p.filtered: the filtered ones (bf16 gate)
+template <bool ARENA, bool FILT = false>
 static void launch_scan_mfma_a(const ScanPtrs &p, const ScanArgs &args, uint32_t W, hipStream_t st) {
     launch_scan_chunks(args, [&](const ScanArgs &a, dim3 g) {
         switch (W) {
-            case 1: launch_scan_mfma_t<1, 4, ARENA>(p, a, g, st); break;
-            case 2: launch_scan_mfma_t<2, RQ_NT_W2, ARENA>(p, a, g, st); break;
-            case 3: launch_scan_mfma_t<3, 4, ARENA>(p, a, g, st); break;
-            case 4: launch_scan_mfma_t<4, 2, ARENA>(p, a, g, st); break;
-            case 6: launch_scan_mfma_t<6, 2, ARENA>(p, a, g, st); break;
-            case 8: launch_scan_mfma_t<8, 2, ARENA>(p, a, g, st); break;
-            case 12: launch_scan_mfma_t<12, RQ_NT_W12, ARENA>(p, a, g, st); break;
-            case 16: launch_scan_mfma_t<16, 2, ARENA>(p, a, g, st); break;
+            case 1: launch_scan_mfma_t<1, 4, ARENA, false, FILT>(p, a, g, st); break;
+            case 2: launch_scan_mfma_t<2, RQ_NT_W2, ARENA, false, FILT>(p, a, g, st); break;
+            case 3: launch_scan_mfma_t<3, 4, ARENA, false, FILT>(p, a, g, st); break;
+            case 4: launch_scan_mfma_t<4, 2, ARENA, false, FILT>(p, a, g, st); break;
+            case 6: launch_scan_mfma_t<6, 2, ARENA, false, FILT>(p, a, g, st); break;
+            case 8: launch_scan_mfma_t<8, 2, ARENA, false, FILT>(p, a, g, st); break;
+            case 12: launch_scan_mfma_t<12, RQ_NT_W12, ARENA, false, FILT>(p, a, g, st); break;
+            case 16: launch_scan_mfma_t<16, 2, ARENA, false, FILT>(p, a, g, st); break;
             default: break;
         }
     });
 }
 static void launch_scan_mfma(const ScanPtrs &p, const ScanArgs &args, uint32_t W, hipStream_t st, bool additive = false) {
-    if (args.x) launch_scan_mfma_a<true>(p, args, W, st);
+    if (p.filtered) {  // (filtered stages never take the additive gate: run_pass)
+        if (p.arena) launch_scan_mfma_a<true, true>(p, args, W, st);
+        else launch_scan_mfma_a<false, true>(p, args, W, st);
+    } else if (p.arena) launch_scan_mfma_a<true>(p, args, W, st);
     else if (additive) launch_scan_mfma_add(p, args, W, st);
     else launch_scan_mfma_a<false>(p, args, W, st);
 }
@@ -663,7 +709,14 @@ static hipError_t set_scan_mfma_attr() {
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)scan_mfma_ring_bytes(W));
         if (e != hipSuccess) return e;
     }
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(scan_mfma_kernel<W, NT, true>),
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(scan_mfma_kernel<W, NT, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)scan_mfma_ring_bytes(W));
+    if (e != hipSuccess) return e;
+    // the filtered instantiations (bf16 gate, uniform and arena), with the same ring
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(scan_mfma_kernel<W, NT, false, false, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)scan_mfma_ring_bytes(W));
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(scan_mfma_kernel<W, NT, true, false, true>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)scan_mfma_ring_bytes(W));
 }
 static rq_status ensure_kernel_attributes() {

@@ -8,7 +8,9 @@
         unsigned long long *, unsigned long long *, const uint4 *, const float4 *, const float4 *, const ScanArgs
 #define RQ_INST(W, NT)                                                                                                               \
     template __global__ void scan_mfma_kernel<W, NT, false, false>(RQ_MFMA_PARAMS);                                                  \
-    template __global__ void scan_mfma_kernel<W, NT, true, false>(RQ_MFMA_PARAMS);
+    template __global__ void scan_mfma_kernel<W, NT, true, false>(RQ_MFMA_PARAMS);                                                   \
+    template __global__ void scan_mfma_kernel<W, NT, false, false, true>(RQ_MFMA_PARAMS);                                            \
+    template __global__ void scan_mfma_kernel<W, NT, true, false, true>(RQ_MFMA_PARAMS);
 RQ_INST(1, 4)
 RQ_INST(2, RQ_NT_W2)
 RQ_INST(3, 4)

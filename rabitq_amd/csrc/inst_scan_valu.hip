@@ -5,7 +5,9 @@
 
 #define RQ_INST(W, CPL)                                                                                                              \
     template __global__ void scan_kernel<W, CPL, false>(SCAN_PARAMS);                                                                \
-    template __global__ void scan_kernel<W, CPL, true>(SCAN_PARAMS);
+    template __global__ void scan_kernel<W, CPL, true>(SCAN_PARAMS);                                                                 \
+    template __global__ void scan_kernel<W, CPL, false, true>(SCAN_PARAMS);                                                          \
+    template __global__ void scan_kernel<W, CPL, true, true>(SCAN_PARAMS);
 RQ_INST(1, 2)
 RQ_INST(2, 2)
 RQ_INST(3, 2)

@@ -1215,10 +1215,15 @@ __global__ __launch_bounds__(256) void prep_small_listed_kernel(const float *__r
 // candidates: lists nearest-first, members in stored order) and the stream length, which is also
 // what the reference adds to METRICS.rough for this query (src/rerank.rs:105).
 // one wave, query row b: 64 slots per step, exclusive scan by shuffles, carry across steps
+// Filtered passes (sub_off != nullptr): the stream keeps the index's positions, but the reference on the sub-index counts only the
+// admitted rows of the probed lists (pair_cluster / sub_off: the probe lists and the sub-index's list offsets).
 __device__ __forceinline__ void pair_prefix_row(PairScalars *__restrict__ scal, uint32_t b, uint32_t nprobe,
-                                                unsigned long long *__restrict__ rough_count) {
+                                                unsigned long long *__restrict__ rough_count,
+                                                const uint32_t *__restrict__ pair_cluster = nullptr,
+                                                const uint32_t *__restrict__ sub_off = nullptr, uint32_t nlists = 0,
+                                                unsigned long long *__restrict__ stream_len = nullptr) {
     const uint32_t lane = threadIdx.x & 63;
-    unsigned long long carry = 0;
+    unsigned long long carry = 0, admitted = 0;
     for (uint32_t s0 = 0; s0 < nprobe; s0 += 64) {
         const uint32_t s = s0 + lane;
         PairScalars *ps = scal + (uint64_t)b * nprobe + s;
@@ -1232,13 +1237,70 @@ __device__ __forceinline__ void pair_prefix_row(PairScalars *__restrict__ scal, 
         const unsigned long long begin = carry + incl - len;
         if (s < nprobe) ps->stream_begin = begin > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)begin;
         carry += __shfl(incl, 63, 64);
+        if (sub_off) {
+            const uint32_t c = s < nprobe && len ? pair_cluster[(uint64_t)b * nprobe + s] : 0xFFFFFFFFu;
+            unsigned long long ad = c < nlists ? sub_off[c + 1] - sub_off[c] : 0ull;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) ad += __shfl_xor(ad, o, 64);
+            admitted += ad;
+        }
     }
-    if (lane == 0) rough_count[b] = carry;
+    if (lane == 0) rough_count[b] = sub_off ? admitted : carry;
+    if (lane == 0 && stream_len) stream_len[b] = carry;  // (filtered passes: the stream's length, for the profile's matrix_pairs)
 }
 __global__ __launch_bounds__(256) void pair_prefix_kernel(PairScalars *__restrict__ scal, uint32_t nq, uint32_t nprobe,
                                                           unsigned long long *__restrict__ rough_count) {
     const uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b < nq) pair_prefix_row(scal, b, nprobe, rough_count);
+}
+__global__ __launch_bounds__(256) void pair_prefix_filtered_kernel(PairScalars *__restrict__ scal, uint32_t nq, uint32_t nprobe,
+                                                                   unsigned long long *__restrict__ rough_count,
+                                                                   const uint32_t *__restrict__ pair_cluster,
+                                                                   const uint32_t *__restrict__ sub_off, uint32_t nlists,
+                                                                   unsigned long long *__restrict__ stream_len) {
+    const uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b < nq) pair_prefix_row(scal, b, nprobe, rough_count, pair_cluster, sub_off, nlists, stream_len);
+}
+
+// ---- filters (rq_filter_create) ----------------------------------------------------------------------------------------------
+// Position bitmap: bit pos of word pos >> 5 = allow[map_ids[pos]] (ids >= nbits are not admitted).  One wave covers 64 positions:
+// its bits come from ONE ballot and leave in two plain 32-bit stores.  Words past the last position are written as zero.
+__global__ __launch_bounds__(256) void filter_positions_kernel(const uint32_t *__restrict__ map_ids, uint64_t n,
+                                                               const uint32_t *__restrict__ allow_ids, uint64_t nbits,
+                                                               uint32_t *__restrict__ pos_bits, uint64_t nwords) {
+    const uint64_t pos = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63;
+    bool in = false;
+    if (pos < n) {
+        const uint32_t id = map_ids[pos];
+        in = (uint64_t)id < nbits && ((allow_ids[id >> 5] >> (id & 31u)) & 1u);
+    }
+    const uint64_t m = __ballot(in);
+    const uint64_t w = (pos - lane) >> 5;  // first of the wave's two words
+    if (lane < 2 && w + lane < nwords) pos_bits[w + lane] = (uint32_t)(m >> (32 * lane));
+}
+// Admitted rows per list: one block per list, one word of the bitmap per lane and step (the list's first and last word masked to
+// its range).
+__global__ __launch_bounds__(256) void filter_lists_kernel(const uint32_t *__restrict__ pos_bits, const uint32_t *__restrict__ offsets,
+                                                           uint32_t *__restrict__ list_adm) {
+    __shared__ uint32_t s_cnt;
+    const uint32_t c = blockIdx.x;
+    const uint32_t b = offsets[c], e = offsets[c + 1];
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    uint32_t cnt = 0;
+    if (e > b) {
+        for (uint32_t w = (b >> 5) + threadIdx.x; w <= ((e - 1) >> 5); w += 256) {
+            uint32_t bits = pos_bits[w];
+            const uint32_t w0 = w << 5;
+            if (w0 < b) bits &= ~0u << (b - w0);                    // positions before the list
+            if (e - w0 < 32) bits &= (1u << (e - w0)) - 1u;         // positions after it
+            cnt += (uint32_t)__popc(bits);
+        }
+    }
+    if (cnt) atomicAdd(&s_cnt, cnt);
+    __syncthreads();
+    if (threadIdx.x == 0) list_adm[c] = s_cnt;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1592,8 +1654,10 @@ __global__ __launch_bounds__(256) void group_vrange_kernel(const uint32_t *__res
 }
 
 
-// generic-W fallback (dim/64 not in the templated set): code words re-read per query (L1-resident)
-__global__ __launch_bounds__(256) void scan_generic_kernel(SCAN_PARAMS, uint32_t W) {
+// generic-W fallback (dim/64 not in the templated set): code words re-read per query (L1-resident).  FILT: the filtered form
+// (scan_generic_filtered_kernel; a.x holds the filter's position bitmap)
+template <bool FILT>
+__device__ __forceinline__ void scan_generic_body(SCAN_PARAMS, uint32_t W) {
     const uint32_t STRIDE = 8 * W + RQ_REC_TAIL;
     const uint32_t gl = blockIdx.x / a.tiles_per_group;
     const uint32_t g = a.group_base + gl;
@@ -1618,6 +1682,11 @@ __global__ __launch_bounds__(256) void scan_generic_kernel(SCAN_PARAMS, uint32_t
     const uint32_t pos = list_begin + (local < list_len ? local : 0);
     const uint32_t *cp = codes + (uint64_t)pos * (2 * W);
     const float4 fac = factors[pos];
+    bool adm = true;
+    if constexpr (FILT) {  // the lane's admission bit (once per block); a tile that admits nothing has nothing to scan
+        adm = rq_admitted(load_scan_extra(a.x).allow, pos) != 0u;
+        if (!__syncthreads_or(adm)) return;
+    }
     for (uint32_t i = pb; i < pe; ++i, rec += STRIDE) {
         const uint32_t *pl = rec;  // the 4 bit planes (AND-popcount form)
         const uint32_t *t = rec + 8 * W;
@@ -1637,7 +1706,7 @@ __global__ __launch_bounds__(256) void scan_generic_kernel(SCAN_PARAMS, uint32_t
         const uint32_t rb = hi_p > P0 ? (hi_p - P0 < 64 ? hi_p - P0 : 64) : 0;
         const uint64_t below_b = rb >= 64 ? ~0ull : ((1ull << rb) - 1ull);
         const uint64_t below_a = ra >= 64 ? ~0ull : ((1ull << ra) - 1ull);
-        uint64_t m = __ballot(rough < __builtin_bit_cast(float, t[RQ_REC_THR])) & below_b & ~below_a;
+        uint64_t m = __ballot(rough < __builtin_bit_cast(float, t[RQ_REC_THR]) && adm) & below_b & ~below_a;
         if (m) {
             const uint32_t b = t[RQ_REC_ROW], slot = t[RQ_REC_SLOT];
             const bool pass = (m >> lane) & 1ull;
@@ -1662,6 +1731,12 @@ __global__ __launch_bounds__(256) void scan_generic_kernel(SCAN_PARAMS, uint32_t
             }
         }
     }
+}
+__global__ __launch_bounds__(256) void scan_generic_kernel(SCAN_PARAMS, uint32_t W) {
+    scan_generic_body<false>(codes, factors, offsets, grp_start, recs, surv, runs, surv_cnt, tile_table, a, W);
+}
+__global__ __launch_bounds__(256) void scan_generic_filtered_kernel(SCAN_PARAMS, uint32_t W) {
+    scan_generic_body<true>(codes, factors, offsets, grp_start, recs, surv, runs, surv_cnt, tile_table, a, W);
 }
 
 // Dense variant for the per-stage test entry rq_scan: rough distance of every member of one list

@@ -91,7 +91,7 @@ struct ScanArgs {   // scalars only; pointers are explicit __restrict__ kernel p
 struct ScanExtra {
     uint2 *arena_places;        // per run descriptor: {first record, directory slot} of the run INSIDE its query's segment -- the value the
                                 // scan's per-query count returned, so that the scatter pass needs no reservation of its own
-    const uint32_t *reserved;
+    const uint32_t *allow;      // filtered instantiations only: the filter's position bitmap (bit pos of word pos >> 5 = admitted)
     SurvRec *arena_recs;        // nullptr: records go straight to the query's segment
     uint4 *arena_runs;          // {pos, slot | cnt << 16, query, record offset in the arena}
     unsigned long long *arena_cur;  // RQ_ARENA_SHARDS cursors, [SHARDS] overflow flag, [SHARDS + 1] (host), [SHARDS + 2] cursor of the common area
@@ -117,7 +117,7 @@ __device__ __forceinline__ ScanExtra load_scan_extra(const ScanExtra *xp) {
     auto ptr = [&](int i) { return ((unsigned long long)v[i + 1] << 32) | v[i]; };
     ScanExtra e;
     e.arena_places = reinterpret_cast<uint2 *>(ptr(0));
-    e.reserved = reinterpret_cast<const uint32_t *>(ptr(2));
+    e.allow = reinterpret_cast<const uint32_t *>(ptr(2));
     e.arena_recs = reinterpret_cast<SurvRec *>(ptr(4));
     e.arena_runs = reinterpret_cast<uint4 *>(ptr(6));
     e.arena_cur = reinterpret_cast<unsigned long long *>(ptr(8));
@@ -143,6 +143,13 @@ __device__ __forceinline__ bool arena_reserve(const ScanExtra &a, uint32_t nrec,
     *reinterpret_cast<unsigned int *>(a.arena_cur + RQ_ARENA_SHARDS) = 1u;
     return false;
 }
+// Filtered queries (rq_filter): a candidate whose bit is clear in the filter's position bitmap is never admitted as a survivor,
+// which for the result is the same as removing it from its list.  The filtered instantiations of the
+// scans read the bitmap pointer from the ScanExtra (a.x; one scalar load at block start) -- the unfiltered ones are the same code
+// as before the filter existed, with the same argument block.
+__device__ __forceinline__ uint32_t rq_admitted(const uint32_t *__restrict__ allow, uint32_t pos) {
+    return (allow[pos >> 5] >> (pos & 31u)) & 1u;
+}
 // (the scans record either into the uniform buffers or, in their ARENA instantiations, into the arena: segments are what
 // the scatter pass and the consumers see)
 __device__ __forceinline__ QSeg scan_seg(const ScanArgs &a) { return QSeg{nullptr, nullptr, a.cap}; }
@@ -160,6 +167,8 @@ struct ScanPtrs {   // host-side bundle only
     const uint4 *tile_table;      // {list, first position of the tile in the list, list begin, list length} (use_table)
     const float4 *list_uref;      // additive gate: U0 per list (index)
     const float4 *grp_vref;       // additive gate: V0, DV per list (stage; group_vrange_kernel)
+    bool arena;                   // the stage appends to the survivor arena (ScanArgs::x: its ScanExtra)
+    bool filtered;                // filtered instantiations (ScanArgs::x: a ScanExtra whose `allow` is the filter's bitmap)
 };
 #define SCAN_PARAMS                                                                                  \
     const uint32_t *__restrict__ codes, const float4 *__restrict__ factors,                          \

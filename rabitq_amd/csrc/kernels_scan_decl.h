@@ -5,7 +5,8 @@
 #pragma once
 
 // ---- VALU scan (kernels_scan_valu.h) ----
-template <int W, int CPL, bool ARENA = false>
+// FILT: the form for filtered queries (a.x holds the filter's position bitmap, ScanExtra::allow)
+template <int W, int CPL, bool ARENA = false, bool FILT = false>
 __global__ __launch_bounds__(256) void scan_kernel(SCAN_PARAMS);
 
 // ---- matrix-core scan (kernels_scan_mfma.h) ----
@@ -67,7 +68,8 @@ constexpr uint32_t scan_mfma_ring_slots() {
 }
 template <int W, bool ARENA, bool ADD>
 constexpr uint32_t scan_mfma_img_dwords() { return rq_img_dwords(12 * W, ADD); }
-template <int W, int NT, bool ARENA = false, bool ADD = false>
+// FILT: the form for filtered queries (bf16 gate only; a.x holds the filter's position bitmap, ScanExtra::allow)
+template <int W, int NT, bool ARENA = false, bool ADD = false, bool FILT = false>
 __global__ __launch_bounds__((64 * scan_mfma_waves<W, ARENA>()), scan_mfma_blocks_per_cu<W>() /* = waves per SIMD: hipcc's second bound counts waves per execution unit */) void scan_mfma_kernel(const uint32_t *__restrict__ codes,
                                                            const float4 *__restrict__ factors,
                                                            const uint32_t *__restrict__ offsets,

@@ -67,7 +67,9 @@ __device__ __forceinline__ uint32_t lds_addr(const void *p) {
 // (exact threshold: < 1e-5), each of which is then decided by the exact f32 expression exactly as before.
 // The candidate operand of this form is fp4 (e2m1: a code bit is 1.0 = 0b0010; same MFMA rate as fp6 x fp6, 4 instead of 6
 // registers per 32 dimensions), which pays for the 16 registers of C.
-template <int W, int NT, bool ARENA, bool ADD>
+// FILT: the filtered form (bf16 gate only) -- the exact path admits a candidate only if its bit in the filter's position bitmap
+// is set; a sub-tile the gate does not flag has no survivors anyway, so the hot loop is untouched.
+template <int W, int NT, bool ARENA, bool ADD, bool FILT>
 __global__ __launch_bounds__((64 * scan_mfma_waves<W, ARENA>()), scan_mfma_blocks_per_cu<W>() /* = waves per SIMD: hipcc's second bound counts waves per execution unit */) void scan_mfma_kernel(const uint32_t *__restrict__ codes,
                                                            const float4 *__restrict__ factors,
                                                            const uint32_t *__restrict__ offsets,
@@ -84,6 +86,7 @@ __global__ __launch_bounds__((64 * scan_mfma_waves<W, ARENA>()), scan_mfma_block
     // (an ADD + ARENA instantiation was built and measured in round 4: on the hard distribution -- overlapping clusters, hub lists with
     // wide v' ranges -- the additive bound flags 95 % of the steps, 45 -> 131 ms per step: the arena stages keep the bf16 threshold)
     static_assert(!(ADD && ARENA), "the additive gate is built for the uniform survivor buffers only");
+    static_assert(!(ADD && FILT), "filtered stages run the bf16 threshold form");
     constexpr uint32_t OPDW = 12 * W;            // operand dwords per record: dim fp6 fields
     constexpr uint32_t OPLD = rq_img_opld(OPDW, ADD);  // row stride (dwords) of the operand image: conflict-free ds_read_b64 (ADD at dim 128: ds_read_b128)
     constexpr uint32_t IMG_OP = 32 * OPLD;       // a query tile image: 32 operand rows ...
@@ -143,6 +146,15 @@ __global__ __launch_bounds__((64 * scan_mfma_waves<W, ARENA>()), scan_mfma_block
         fac0[t] = factors[pos];
 #pragma unroll
         for (int m = 0; m < W; ++m) craw[t][m] = cp[2 * m + h];
+    }
+    // filtered form: the lane's admission bits, one per sub-tile (read once per block); a tile that admits nothing has nothing to
+    // scan (block-uniform: before the first query tile is requested)
+    uint32_t adm = 0;
+    if constexpr (FILT) {
+        const uint32_t *allow = load_scan_extra(a.x).allow;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) adm |= rq_admitted(allow, list_begin + (lpos[t] < list_len ? lpos[t] : 0)) << t;
+        if (!__syncthreads_or(adm)) return;
     }
     float4 u0r = {0, 0, 0, 0}, v0r = {0, 0, 0, 0}, dvr = {0, 0, 0, 0};
     if constexpr (ADD) u0r = list_uref[g], v0r = grp_vref[2 * g], dvr = grp_vref[2 * g + 1];
@@ -527,6 +539,7 @@ __global__ __launch_bounds__((64 * scan_mfma_waves<W, ARENA>()), scan_mfma_block
                 bool pass = rg < __builtin_bit_cast(float, tb.y);  // src/rerank.rs:84
                 // a real query, and a list position inside its stage range
                 pass = pass && row < nvalid && lpos[t] >= tb.z && lpos[t] < tb.w;
+                if constexpr (FILT) pass = pass && ((adm >> t) & 1u);  // (a filtered-out candidate never survives)
                 const uint64_t m = __ballot(pass);
                 if (m == 0) continue;
 #ifdef RQ_DEV_ABLATIONS
@@ -659,5 +672,3 @@ __global__ __launch_bounds__((64 * scan_mfma_waves<W, ARENA>()), scan_mfma_block
         if (n_flag) atomicAdd(stat + 2 * (blockIdx.x & 63u) + 1, (unsigned long long)n_flag);
     }
 }
-
-

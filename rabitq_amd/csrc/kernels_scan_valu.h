@@ -7,7 +7,8 @@
 // expands its candidates' code bits to nibbles ONCE per block (amortised over every query of the
 // group) and the per-query work is 8W chained v_dot8_u32_u4 (8 dimensions each, u32 accumulate,
 // query operand in an SGPR) instead of 8W v_and + 8W v_bcnt + adds.
-template <int W, int CPL, bool ARENA>
+// FILT: the filtered form -- a candidate whose bit in the filter's position bitmap is clear never survives.
+template <int W, int CPL, bool ARENA, bool FILT>
 __global__ __launch_bounds__(256) void scan_kernel(SCAN_PARAMS) {
     constexpr uint32_t STRIDE = 8 * W + RQ_REC_TAIL;
     uint32_t g, first, list_begin = 0, list_len = 0;
@@ -69,6 +70,15 @@ __global__ __launch_bounds__(256) void scan_kernel(SCAN_PARAMS) {
             for (int kq = 0; kq < 4; ++kq) xn[c][4 * j + kq] = spread8(code[j] >> (8 * kq));
         fac[c] = factors[pos[c]];
     }
+    // filtered form: the lane's admission bits, one per candidate (read once per block, not per pair); a tile that admits nothing
+    // has nothing to scan
+    uint32_t adm = 0;
+    if constexpr (FILT) {
+        const uint32_t *allow = load_scan_extra(a.x).allow;
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) adm |= rq_admitted(allow, pos[c]) << c;
+        if (!__syncthreads_or(adm)) return;
+    }
 
     // one (query, list) pair of the group against this block's candidates; qn = the query's 8W operand dwords,
     // t = the record's tail (both wave-uniform: a pointer the compiler turns into scalar loads, or SGPR tuples)
@@ -110,7 +120,8 @@ __global__ __launch_bounds__(256) void scan_kernel(SCAN_PARAMS) {
         if (lo_p <= first && first + 256 * CPL <= hi_p) {  // whole tile inside the stage (the common case)
 #pragma unroll
             for (int c = 0; c < CPL; ++c) {
-                m[c] = __ballot(rough[c] < thr);  // src/rerank.rs:84 gate
+                if constexpr (FILT) m[c] = __ballot(rough[c] < thr && ((adm >> c) & 1u));  // (a filtered-out candidate never survives)
+                else m[c] = __ballot(rough[c] < thr);  // src/rerank.rs:84 gate
                 total += (uint32_t)__popcll(m[c]);
             }
         } else {  // boundary tile: lanes of this wave hold positions P0 .. P0+63, the in-stage ones are a bit range
@@ -121,7 +132,8 @@ __global__ __launch_bounds__(256) void scan_kernel(SCAN_PARAMS) {
                 const uint32_t rb = hi_p > P0 ? (hi_p - P0 < 64 ? hi_p - P0 : 64) : 0;
                 const uint64_t below_b = rb >= 64 ? ~0ull : ((1ull << rb) - 1ull);
                 const uint64_t below_a = ra >= 64 ? ~0ull : ((1ull << ra) - 1ull);
-                m[c] = __ballot(rough[c] < thr) & below_b & ~below_a;
+                if constexpr (FILT) m[c] = __ballot(rough[c] < thr && ((adm >> c) & 1u)) & below_b & ~below_a;
+                else m[c] = __ballot(rough[c] < thr) & below_b & ~below_a;
                 total += (uint32_t)__popcll(m[c]);
             }
         }
@@ -261,4 +273,3 @@ __global__ __launch_bounds__(256) void scan_kernel(SCAN_PARAMS) {
         for (uint32_t i = pb; i < pe; ++i, rec += STRIDE) score_pair(rec, rec + 8 * W);
     }
 }
-

@@ -40,7 +40,7 @@
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-const char *rq_version(void) { return "rabitq_hip 0.5.0 (gfx950, abi 4)"; }
+const char *rq_version(void) { return "rabitq_hip 0.6.0 (gfx950, abi 4)"; }
 uint32_t rq_abi_version(void) { return RQ_ABI_VERSION; }
 const char *rq_last_error(void) { return g_err.c_str(); }
 
@@ -524,6 +524,13 @@ rq_status rq_query_batch_device(const rq_index *idx, const float *d_queries, uin
                         d_out_id, d_out_n);
 }
 
+rq_status rq_query_batch_device_filtered(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq,
+                                         uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank, float *d_out_dist,
+                                         uint32_t *d_out_id, uint32_t *d_out_n) {
+    return query_device(const_cast<rq_index *>(idx), d_queries, nq, len, probe, topk, heuristic_rank != 0, d_out_dist,
+                        d_out_id, d_out_n, nullptr, nullptr, nullptr, nullptr, filter);
+}
+
 rq_status rq_query_batch_device_begin(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t len,
                                       uint32_t probe, uint32_t topk, int heuristic_rank, float *d_out_dist,
                                       uint32_t *d_out_id, uint32_t *d_out_n, rq_ticket **out_ticket) {
@@ -567,10 +574,11 @@ struct HostStaging {
 static thread_local HostStaging g_staging;
 #define RQ_ZERO_COPY_BYTES (1u << 20)
 
-rq_status rq_query_batch(const rq_index *idx, const float *queries, uint32_t nq, uint32_t len, uint32_t probe,
-                         uint32_t topk, int heuristic_rank, float *out_dist, uint32_t *out_id, uint32_t *out_n) {
+static rq_status query_batch_host(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len,
+                                  uint32_t probe, uint32_t topk, int heuristic_rank, float *out_dist, uint32_t *out_id, uint32_t *out_n) {
     RQC(ensure_device());
     if (!idx || !queries || !out_dist || !out_id || !out_n) return fail(RQ_ERR_INVALID, "null argument");
+    if (filter && filter->idx != idx) return fail(RQ_ERR_INVALID, "the filter was made for another index");
     if (nq == 0) return RQ_OK;
     if (topk == 0) return fail(RQ_ERR_UNSUPPORTED, "topk must be in [1, 2048]");
     const size_t qb = ((size_t)nq * len * 4 + 255) & ~(size_t)255, ob = ((size_t)nq * topk * 4 + 255) & ~(size_t)255;
@@ -584,7 +592,8 @@ rq_status rq_query_batch(const rq_index *idx, const float *queries, uint32_t nq,
         char *h = static_cast<char *>(pin), *d = static_cast<char *>(dev);
         memcpy(h, queries, (size_t)nq * len * 4);
         rq_status s = query_device(const_cast<rq_index *>(idx), (const float *)d, nq, len, probe, topk, heuristic_rank != 0,
-                                   (float *)(d + qb), (uint32_t *)(d + qb + ob), (uint32_t *)(d + qb + 2 * ob));
+                                   (float *)(d + qb), (uint32_t *)(d + qb + ob), (uint32_t *)(d + qb + 2 * ob), nullptr, nullptr, nullptr,
+                                   nullptr, filter);
         if (s != RQ_OK && s != RQ_ERR_EMPTY) return s;
         memcpy(out_dist, h + qb, (size_t)nq * topk * 4);
         memcpy(out_id, h + qb + ob, (size_t)nq * topk * 4);
@@ -598,13 +607,77 @@ rq_status rq_query_batch(const rq_index *idx, const float *queries, uint32_t nq,
     RQC(g_staging.get(3, (uint64_t)nq * 4, &dn));
     HIPC(hipMemcpy(dq, queries, (uint64_t)nq * len * 4, hipMemcpyHostToDevice));
     rq_status s = query_device(const_cast<rq_index *>(idx), (const float *)dq, nq, len, probe, topk, heuristic_rank != 0,
-                               (float *)dd, (uint32_t *)di, (uint32_t *)dn);
+                               (float *)dd, (uint32_t *)di, (uint32_t *)dn, nullptr, nullptr, nullptr, nullptr, filter);
     if (s != RQ_OK && s != RQ_ERR_EMPTY) return s;
     HIPC(hipMemcpy(out_dist, dd, (uint64_t)nq * topk * 4, hipMemcpyDeviceToHost));
     HIPC(hipMemcpy(out_id, di, (uint64_t)nq * topk * 4, hipMemcpyDeviceToHost));
     HIPC(hipMemcpy(out_n, dn, nq * 4, hipMemcpyDeviceToHost));
     return s;
 }
+
+rq_status rq_query_batch(const rq_index *idx, const float *queries, uint32_t nq, uint32_t len, uint32_t probe,
+                         uint32_t topk, int heuristic_rank, float *out_dist, uint32_t *out_id, uint32_t *out_n) {
+    return query_batch_host(idx, nullptr, queries, nq, len, probe, topk, heuristic_rank, out_dist, out_id, out_n);
+}
+rq_status rq_query_batch_filtered(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len,
+                                  uint32_t probe, uint32_t topk, int heuristic_rank, float *out_dist, uint32_t *out_id,
+                                  uint32_t *out_n) {
+    return query_batch_host(idx, filter, queries, nq, len, probe, topk, heuristic_rank, out_dist, out_id, out_n);
+}
+
+// ---- filters: the allow-list in the index's terms (position bitmap + admitted rows per list), made once ----
+rq_status rq_filter_create(const rq_index *idx, const uint32_t *allow_bits, uint64_t nbits, int bits_on_device, rq_filter **out) {
+    if (!out) return fail(RQ_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!idx) return fail(RQ_ERR_INVALID, "null index");
+    if (nbits > (1ull << 32)) return fail(RQ_ERR_INVALID, "nbits > 2^32 (ids are u32)");
+    if (!allow_bits && nbits > 0) return fail(RQ_ERR_INVALID, "null bitmap with nbits > 0");
+    RQC(ensure_device());
+    std::unique_ptr<rq_filter> f(new rq_filter());
+    f->idx = idx;
+    const uint64_t n = idx->n, nwords = (n + 63) / 64 * 2 + 2;  // (whole 64-position waves, and never empty)
+    const uint64_t in_words = (nbits + 31) / 32;
+    DevBuf<uint32_t> staged;  // the caller's bitmap in device memory (host bitmaps are copied)
+    const uint32_t *d_allow = allow_bits;
+    if (!bits_on_device || nbits == 0) {
+        RQC(staged.alloc(std::max<uint64_t>(in_words, 1)));
+        HIPC(hipMemset(staged.p, 0, std::max<uint64_t>(in_words, 1) * 4));
+        if (in_words) HIPC(hipMemcpy(staged.p, allow_bits, in_words * 4, hipMemcpyHostToDevice));
+        d_allow = staged.p;
+    }
+    RQC(f->pos_bits.alloc(nwords));
+    RQC(f->sub_off.alloc((size_t)idx->k + 1));
+    RQC(f->extra.alloc(1));
+    DevBuf<uint32_t> counts;
+    RQC(counts.alloc(std::max<uint32_t>(idx->k, 1)));
+    hipStream_t st = nullptr;
+    HIPC(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    struct StreamGuard {
+        hipStream_t s;
+        ~StreamGuard() { (void)hipStreamDestroy(s); }
+    } sg{st};
+    HIPC(hipMemsetAsync(f->pos_bits.p, 0, nwords * 4, st));
+    if (n) filter_positions_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(idx->map_ids.p, n, d_allow, nbits, f->pos_bits.p, nwords);
+    if (idx->k) filter_lists_kernel<<<idx->k, 256, 0, st>>>(f->pos_bits.p, idx->offsets.p, counts.p);
+    std::vector<uint32_t> h_cnt(idx->k), h_off((size_t)idx->k + 1, 0);
+    if (idx->k) HIPC(hipMemcpyAsync(h_cnt.data(), counts.p, (size_t)idx->k * 4, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    HIPC(hipGetLastError());
+    for (uint32_t c = 0; c < idx->k; ++c) h_off[c + 1] = h_off[c] + h_cnt[c];  // the sub-index's offsets (<= n < 2^32)
+    HIPC(hipMemcpy(f->sub_off.p, h_off.data(), h_off.size() * 4, hipMemcpyHostToDevice));
+    ScanExtra hx{};
+    hx.allow = f->pos_bits.p;
+    HIPC(hipMemcpy(f->extra.p, &hx, sizeof hx, hipMemcpyHostToDevice));
+    f->rows = h_off[idx->k];
+    *out = f.release();
+    return RQ_OK;
+}
+rq_status rq_filter_rows(const rq_filter *f, uint64_t *out_admitted) {
+    if (!f || !out_admitted) return fail(RQ_ERR_INVALID, "null argument");
+    *out_admitted = f->rows;
+    return RQ_OK;
+}
+void rq_filter_free(rq_filter *f) { delete f; }
 
 rq_status rq_query(const rq_index *idx, const float *query, uint32_t len, uint32_t probe, uint32_t topk,
                    int heuristic_rank, float *out_dist, uint32_t *out_id, uint32_t *out_n) {

@@ -24,6 +24,67 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def pack_filter_bits(ids=None, mask=None, nbits=None):
+    """An allow-list as the bitmap rq_filter_create reads -> (words u32, nbits): bit (id & 31) of word id >> 5 set = id admitted.
+    `ids`: admitted ids (any order, repeats allowed; ids >= nbits are dropped -- the library never admits them); nbits defaults to
+    max(ids) + 1.  `mask`: a boolean mask over ids (nbits = its length).  Exactly one of the two."""
+    if (ids is None) == (mask is None):
+        raise ValueError("give exactly one of ids / mask")
+    if mask is not None:
+        m = np.ascontiguousarray(mask, dtype=bool).reshape(-1)
+        nb = m.size
+    else:
+        a = np.asarray(ids).reshape(-1)
+        if a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < 0):
+            raise ValueError("ids must be non-negative integers")
+        a = a.astype(np.uint64, copy=False)
+        nb = int(a.max()) + 1 if nbits is None and a.size else int(nbits or 0)
+        m = np.zeros(nb, dtype=bool)
+        m[a[a < nb].astype(np.int64)] = True
+    if nbits is not None and mask is not None and int(nbits) != nb:
+        raise ValueError("nbits must equal the mask's length")
+    if nb > (1 << 32):
+        raise ValueError("ids are u32: nbits <= 2^32")
+    nwords = (nb + 31) // 32
+    packed = np.packbits(m, bitorder="little")
+    buf = np.zeros(nwords * 4, dtype=np.uint8)
+    buf[:packed.size] = packed
+    return buf.view(np.uint32), nb
+
+
+class Filter:
+    """A query-time allow-list of one index (rq_filter_create): made once, passed as `filter=` to the query methods.  Holds a
+    reference to its index, so the index outlives it."""
+
+    def __init__(self, index: "RaBitQ", handle):
+        self.index = index
+        self._h = handle
+        rows = C.c_uint64()
+        check(lib().rq_filter_rows(self._h, C.byref(rows)))
+        self.rows = int(rows.value)   # rows of the index the filter admits
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().rq_filter_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _fh(filter):
+    return filter._h if filter is not None else None
+
+
 class RaBitQ:
     """Device-resident RaBitQ index.  Construct with `from_path`, `build`, `load_from_dir` or
     `from_arrays`; query with `query` (one vector, like the crate) or `query_batch`."""
@@ -162,19 +223,38 @@ class RaBitQ:
         check(lib().rq_get_device_ptr(self._h, which, C.byref(p), C.byref(nbytes)))
         return p.value, nbytes.value
 
+    # ---- filters: answer from a subset of the index --------------------------------------------
+    def make_filter(self, ids=None, mask=None) -> Filter:
+        """A filter admitting the original ids `ids` (an id array) or those where `mask` (a boolean mask over ids) is set;
+        packed on the host (pack_filter_bits), turned into the index's terms on the device once."""
+        words, nbits = pack_filter_bits(ids=ids, mask=mask)
+        h = C.c_void_p()
+        check(lib().rq_filter_create(self._h, _addr(words), nbits, 0, C.byref(h)))
+        return Filter(self, h)
+
+    def make_filter_device(self, bits_ptr: int, nbits: int) -> Filter:
+        """A filter from an id bitmap already in device memory (bit (id & 31) of u32 word id >> 5)."""
+        h = C.c_void_p()
+        check(lib().rq_filter_create(self._h, C.c_void_p(bits_ptr), nbits, 1, C.byref(h)))
+        return Filter(self, h)
+
     # ---- RaBitQ::query (src/rabitq.rs:268) ------------------------------------------------------
-    def query(self, query, probe: int, topk: int, heuristic_rank: bool = False):
+    def query(self, query, probe: int, topk: int, heuristic_rank: bool = False, filter: Filter = None):
         """-> list of (distance, original id), at most topk, in the reference's (unspecified,
-        heap-internal) order."""
+        heap-internal) order.  filter: only its rows can be returned (the filtered batch entry with one query)."""
         q = _f32(query).reshape(-1)
         d = np.empty(max(topk, 1), dtype=np.float32)
         ids = np.empty(max(topk, 1), dtype=np.uint32)
         n = C.c_uint32()
-        check(lib().rq_query(self._h, _addr(q), q.size, probe, topk, int(heuristic_rank), _addr(d), _addr(ids),
-                             C.cast(C.byref(n), C.c_void_p)))
+        if filter is None:
+            check(lib().rq_query(self._h, _addr(q), q.size, probe, topk, int(heuristic_rank), _addr(d), _addr(ids),
+                                 C.cast(C.byref(n), C.c_void_p)))
+        else:
+            check(lib().rq_query_batch_filtered(self._h, _fh(filter), _addr(q), 1, q.size, probe, topk, int(heuristic_rank),
+                                                _addr(d), _addr(ids), C.cast(C.byref(n), C.c_void_p)))
         return [(float(d[i]), int(ids[i])) for i in range(n.value)]
 
-    def query_batch(self, queries, probe: int, topk: int, heuristic_rank: bool = False):
+    def query_batch(self, queries, probe: int, topk: int, heuristic_rank: bool = False, filter: Filter = None):
         """B queries at once -> (dist B x topk f32, ids B x topk u32, counts B u32)."""
         q = _f32(queries)
         if q.ndim != 2:
@@ -183,17 +263,26 @@ class RaBitQ:
         d = np.full((B, max(topk, 1)), np.nan, dtype=np.float32)
         ids = np.full((B, max(topk, 1)), 0xFFFFFFFF, dtype=np.uint32)
         cnt = np.zeros(B, dtype=np.uint32)
-        st = lib().rq_query_batch(self._h, _addr(q), B, q.shape[1], probe, topk, int(heuristic_rank), _addr(d),
-                                  _addr(ids), _addr(cnt))
+        if filter is None:
+            st = lib().rq_query_batch(self._h, _addr(q), B, q.shape[1], probe, topk, int(heuristic_rank), _addr(d),
+                                      _addr(ids), _addr(cnt))
+        else:
+            st = lib().rq_query_batch_filtered(self._h, _fh(filter), _addr(q), B, q.shape[1], probe, topk, int(heuristic_rank),
+                                               _addr(d), _addr(ids), _addr(cnt))
         if st != _lib.RQ_ERR_EMPTY:
             check(st)
         return d, ids, cnt
 
     def query_batch_device(self, q_ptr: int, nq: int, length: int, probe: int, topk: int, out_dist_ptr: int,
-                           out_id_ptr: int, out_n_ptr: int, heuristic_rank: bool = False):
+                           out_id_ptr: int, out_n_ptr: int, heuristic_rank: bool = False, filter: Filter = None):
         """Queries and outputs already in device memory (raw addresses)."""
-        check(lib().rq_query_batch_device(self._h, C.c_void_p(q_ptr), nq, length, probe, topk, int(heuristic_rank),
-                                          C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr), C.c_void_p(out_n_ptr)))
+        if filter is None:
+            check(lib().rq_query_batch_device(self._h, C.c_void_p(q_ptr), nq, length, probe, topk, int(heuristic_rank),
+                                              C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr), C.c_void_p(out_n_ptr)))
+        else:
+            check(lib().rq_query_batch_device_filtered(self._h, _fh(filter), C.c_void_p(q_ptr), nq, length, probe, topk,
+                                                       int(heuristic_rank), C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr),
+                                                       C.c_void_p(out_n_ptr)))
 
     def query_batch_device_begin(self, q_ptr: int, nq: int, length: int, probe: int, topk: int, out_dist_ptr: int,
                                  out_id_ptr: int, out_n_ptr: int, heuristic_rank: bool = False):
