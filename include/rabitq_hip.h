@@ -77,7 +77,9 @@ typedef struct {
  * scan's step counters in rq_profile_t are always filled, new option "scan_gate", "coarse_impl" = 3 is back with a new meaning,
  * rq_profile_t.reserved became coarse_fallback_rows, .reserved2 matrix_additive_launches; later in revision 4, additions only: "coarse_impl" = 4,
  * "coarse_tiled_from", "rerank_shadow" = 2 -- the new default; 0.5.0: option "split_rows", rq_info_t.split_rows appended, RQ_ARR_BASE
- * refused for split rows as for tiers; 0.6.0: filtered queries -- rq_filter_* and rq_query_batch*_filtered, additions only).
+ * refused for split rows as for tiers; 0.6.0: filtered queries -- rq_filter_* and rq_query_batch*_filtered, additions only;
+ * 0.7.0: in-place mutation -- rq_add / rq_remove / rq_last_mutate_stats, additions only; a filter made before a mutation of its
+ * index is refused).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -210,8 +212,9 @@ rq_status rq_query_batch_device_end(rq_ticket *ticket);
  * the arrays with the other rows removed.  "Exactly" covers the ids (heap-internal order for the heap ranker, ascending for the
  * heuristic one), the distance bits, out_n, the status (RQ_ERR_EMPTY where the heuristic ranker of the sub-index finds nothing)
  * and the counters: rough counts the admitted rows of the probed lists only, precise is the sub-index's, query goes up by nq.
- * The reference has no counterpart (its README lists insert / update / delete as missing; on an immutable IVF index a query-time
- * allow-list is how deletion is done).
+ * The reference has no counterpart (its README lists insert / update / delete as missing).  A filter answers "which rows may be
+ * returned" per query; rq_remove below takes rows out of the lists for good.  A filter describes the layout it was made on: after
+ * rq_add / rq_remove on its index the filtered queries refuse it (RQ_ERR_INVALID) -- make it again.
  *
  * allow_bits: bit (id & 31) of word id >> 5 set = id admitted; ids >= nbits are not admitted (nbits <= 2^32; allow_bits may be
  * NULL when nbits == 0: nothing is admitted).  Host or device memory (bits_on_device).  The filter is made once -- one pass over
@@ -230,6 +233,45 @@ rq_status rq_query_batch_filtered(const rq_index *idx, const rq_filter *filter, 
 rq_status rq_query_batch_device_filtered(const rq_index *idx, const rq_filter *filter, const float *d_queries,
                                          uint32_t nq, uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank,
                                          float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n);
+
+/* ---- in-place mutation: add and remove rows ------------------------------------------------------------------------ */
+/* After any sequence of rq_add / rq_remove the index equals, bit for bit, the index rq_build produces from its live rows S in
+ * ascending id order (same centroids and rotation) with every map_ids entry j replaced by the j-th smallest id of S: every array
+ * rq_get_array returns, rq_info's n / max_list_len, rq_dump_dir's files and the results and counters of every query.  Each call is
+ * one relayout into fresh arrays (the old and the new arrays coexist for its duration: RQ_ERR_OOM when they do not fit), moved into
+ * the index only when everything has succeeded: on any error the index is unchanged.  The first mutation of an index (and the
+ * first after a load) also derives a 4-byte key per stored row, kept with the index from then on.
+ * Refused with RQ_ERR_UNSUPPORTED, index untouched: tiered indexes, split-row indexes, shards made by rq_shard_index.  Refused with
+ * RQ_ERR_INVALID: an index with a rq_query_batch_device_begin ticket whose _end has not run.  No query may run on the index while
+ * it is mutated (the caller serialises, as Rust's &mut self does).  Workspaces and tile tables of the old layout are released.
+ *
+ * rq_add: insert m rows (m x d f32, row-major; host or device memory per rows_on_device).  d must pad to the index's dim
+ * (ceil64(d) == dim), else RQ_ERR_DIM_MISMATCH.  ids: NULL = the next ids, first = 1 + the largest id the index holds (0 if
+ * empty), returned in *out_first_id (RQ_ERR_UNSUPPORTED if the last would pass 2^32 - 1); else m explicit u32 ids in the same
+ * memory as the rows, each absent from the index and unique in the batch (else RQ_ERR_INVALID; *out_first_id = the smallest).
+ * Removing and then adding an id with a new vector is an update (two relayouts).  m == 0 changes nothing.
+ * rq_remove: remove the ids set in the bitmap (the rq_filter_create format: bit (id & 31) of word id >> 5, nbits <= 2^32, host or
+ * device memory per bits_on_device); ids that are not in the index are ignored; *out_removed = rows removed (0: nothing changed).
+ * Precondition of rq_add: every list of the index is in the build's order -- strictly ascending by (distance of the row to the
+ * list's centroid, as the build computes it; then id).  Indexes made by rq_build* and rq_add, and their dumps, are; an index given
+ * to rq_from_arrays / rq_load_dir may not be (for example one whose map_ids were remapped to other ids).  The order is checked on
+ * the first mutation of an index (with its keys); where it does not hold, rq_add returns RQ_ERR_UNSUPPORTED with the index
+ * untouched, and rq_remove still works (it keeps the order the lists have).  Indexes of dim > 4096 are refused (RQ_ERR_UNSUPPORTED).
+ * rq_last_mutate_stats: the calling thread's last rq_add / rq_remove, by phase (wall ms; every phase ends in a device
+ * synchronisation): keys = deriving the key cache and checking the order (0 when cached), assign = pass 1 + per-list sort of the
+ * new rows, alloc = the new layout's arrays, merge, gather, derive = finish_index and the shadow / pass budget decided again after
+ * the old layout is freed, free = releasing the old layout; total = the whole call; gather_bytes = what the gather reads + writes. */
+typedef struct {
+    uint32_t struct_size; /* set to sizeof(rq_mutate_stats_t) before the call */
+    uint32_t reserved0;
+    float ms_keys, ms_assign, ms_alloc, ms_merge, ms_gather, ms_derive, ms_free, ms_total;
+    uint64_t rows_before, rows_after;
+    uint64_t gather_bytes;
+} rq_mutate_stats_t;
+rq_status rq_add(rq_index *idx, const float *rows, uint64_t m, uint32_t d, const uint32_t *ids, int rows_on_device,
+                 uint32_t *out_first_id);
+rq_status rq_remove(rq_index *idx, const uint32_t *id_bits, uint64_t nbits, int bits_on_device, uint64_t *out_removed);
+rq_status rq_last_mutate_stats(rq_mutate_stats_t *out);
 
 /* ---- sharded deployments (one index shard per GPU / process) ----------------------------------- */
 /* The coarse ranking of src/rabitq.rs:283-297 restricted to lists [list_lo, list_hi): the `probe`

@@ -357,6 +357,23 @@ struct rq_builder {
 };
 #define RQ_BUILD_CHUNK (1ull << 20)
 
+// pass-1 state of a builder whose index already holds its shape (n, dim, k, W) and the rotated centroids (centroids, cent_t)
+static rq_status builder_alloc_pass1(rq_builder *b) {
+    rq_index *idx = b->idx.get();
+    const uint64_t n = idx->n;
+    const uint32_t dim = idx->dim;
+    RQC(b->label.alloc(n));
+    RQC(b->mind.alloc(n));
+    RQC(b->codes_tmp.alloc(n * idx->W));
+    RQC(b->factors_tmp.alloc(n));
+    const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(n, 1), RQ_BUILD_CHUNK);
+    if (b->d != dim) RQC(b->xpad.alloc(chunk * dim));
+    RQC(b->xrot.alloc(chunk * dim));
+    if (assign_has_mfma(idx->W) && g_assign_impl.load() != 1) RQC(assign_aux_init(idx, b->assign_aux, chunk));
+    for (auto &e : b->ev) HIPC(hipEventCreate(&e));
+    return RQ_OK;
+}
+
 static rq_status builder_create(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
                                 uint64_t seed, uint64_t max_device_base_bytes, rq_builder **out) {
     RQC(ensure_device());
@@ -391,16 +408,7 @@ static rq_status builder_create(uint64_t n, uint32_t d, const float *d_centroids
     transpose_kernel<<<dim3(ceil_div(dim, 32), ceil_div(k, 32)), dim3(32, 8)>>>(idx->centroids.p, idx->cent_t.p, k, dim);
     HIPC(hipDeviceSynchronize());
     HIPC(hipGetLastError());
-
-    RQC(b->label.alloc(n));
-    RQC(b->mind.alloc(n));
-    RQC(b->codes_tmp.alloc(n * idx->W));
-    RQC(b->factors_tmp.alloc(n));
-    const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(n, 1), RQ_BUILD_CHUNK);
-    if (d != dim) RQC(b->xpad.alloc(chunk * dim));
-    RQC(b->xrot.alloc(chunk * dim));
-    if (assign_has_mfma(idx->W) && g_assign_impl.load() != 1) RQC(assign_aux_init(idx, b->assign_aux, chunk));
-    for (auto &e : b->ev) HIPC(hipEventCreate(&e));
+    RQC(builder_alloc_pass1(b.get()));
     *out = b.release();
     return RQ_OK;
 }
@@ -466,7 +474,7 @@ static rq_status builder_order(rq_builder *b) {
     const uint32_t g256 = (uint32_t)std::min<uint64_t>(ceil_div(std::max<uint64_t>(n, 1), 256), 1u << 22);
     if (n) label_hist_kernel<<<ceil_div(n, 256), 256>>>(b->label.p, n, cnt.p);
     group_scan_kernel<<<1, 1024>>>(cnt.p, k, idx->offsets.p, 0u, nullptr, 0u);  // also zeroes cnt -> cursor
-    if (n) label_scatter_kernel<<<ceil_div(n, 256), 256>>>(b->label.p, b->mind.p, n, 0, idx->offsets.p, cnt.p, keys.p);
+    if (n) label_scatter_kernel<<<ceil_div(n, 256), 256>>>(b->label.p, b->mind.p, n, 0, idx->offsets.p, cnt.p, keys.p, nullptr);
     list_sort_kernel<<<k, 1024>>>(keys.p, idx->offsets.p);
     HIPC(hipDeviceSynchronize());
     HIPC(hipGetLastError());

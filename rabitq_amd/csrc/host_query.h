@@ -989,6 +989,8 @@ static rq_status query_device(rq_index *idx, const float *d_q, uint32_t nq, uint
                               const rq_filter *filter = nullptr) {
     RQC(validate_query(idx, d_q, len, probe, topk, d_out_dist, d_out_id, d_out_n));
     if (filter && filter->idx != idx) return fail(RQ_ERR_INVALID, "the filter was made for another index");
+    if (filter && filter->generation != idx->generation)
+        return fail(RQ_ERR_INVALID, "the filter was made before the index was last mutated (rq_add / rq_remove): make it again");
     if (nq == 0) return RQ_OK;
     rq_profile_t prof;
     memset(&prof, 0, sizeof prof);
@@ -1165,11 +1167,18 @@ static rq_status query_device_begin(rq_index *idx, const float *d_q, uint32_t nq
     std::unique_ptr<rq_ticket> t(new rq_ticket());
     t->idx = idx;
     memset(&t->prof, 0, sizeof t->prof);
+    struct Open {  // counted while the ticket is outstanding (rq_add / rq_remove refuse to relayout under it)
+        rq_index *i;
+        bool keep = false;
+        explicit Open(rq_index *x) : i(x) { i->open_tickets.fetch_add(1); }
+        ~Open() { if (!keep) i->open_tickets.fetch_sub(1); }
+    } open(idx);
     bool seg = false;
     const uint32_t cap0 = pass_capacity(idx, nq, false, &seg);
     if (nq == 0 || pass_queries(idx, nq, probe, cap0, seg) < nq) {  // nothing to overlap / several passes: synchronous
         t->status = query_device(idx, d_q, nq, len, probe, topk, heuristic, d_out_dist, d_out_id, d_out_n);
         t->done = true;
+        open.keep = true;
         *out = t.release();
         return RQ_OK;
     }
@@ -1197,6 +1206,7 @@ static rq_status query_device_begin(rq_index *idx, const float *d_q, uint32_t nq
         ws_release(idx, t->ws);
         return st;
     }
+    open.keep = true;
     *out = t.release();
     return RQ_OK;
 }
@@ -1204,6 +1214,7 @@ static rq_status query_device_begin(rq_index *idx, const float *d_q, uint32_t nq
 static rq_status query_device_end(rq_ticket *tk) {
     if (!tk) return fail(RQ_ERR_INVALID, "null ticket");
     std::unique_ptr<rq_ticket> t(tk);
+    t->idx->open_tickets.fetch_sub(1);
     if (t->done) return t->status;
     struct Rel {
         rq_index *i;

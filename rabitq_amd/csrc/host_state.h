@@ -270,12 +270,20 @@ struct rq_index {
     std::vector<uint32_t> h_offsets;
     std::mutex tt_mu;
     std::map<uint32_t, std::unique_ptr<DevBuf<uint4>>> tile_tables;
+    // in-place mutation (host_mutate.h)
+    DevBuf<uint32_t> row_key;     // per position: ord32_biased(distance to its list's centroid), the high word of the build's order key (derived, not dumped)
+    bool row_key_valid = false;   // computed on the first mutation (again after a load); moved along by every relayout
+    bool row_order_ok = true;     // every list strictly ascending by row_key << 32 | id (checked with the keys; rq_add needs it)
+    bool is_shard = false;        // made by rq_shard_index: added ids would collide with other ranks' ids, so it is never mutated
+    uint64_t generation = 0;      // bumped by every relayout; a filter made for an older generation is refused
+    std::atomic<int> open_tickets{0};  // rq_query_batch_device_begin tickets whose _end has not run
 };
 
 // A query-time allow-list (rq_filter_create), in the index's own terms: one bit per cluster-order position and the admitted rows
 // of every list.  Made once, read-only afterwards (concurrent queries share it).
 struct rq_filter {
     const rq_index *idx = nullptr;  // the index it was made for (another index is refused)
+    uint64_t generation = 0;        // idx->generation when it was made (a relayout since then: refused)
     DevBuf<uint32_t> pos_bits;      // bit pos of word pos >> 5 = the row at position pos is admitted
     DevBuf<uint32_t> sub_off;       // k + 1: list offsets of the sub-index (admitted rows of list c = sub_off[c + 1] - sub_off[c])
     DevBuf<ScanExtra> extra;        // what the filtered scans read through ScanArgs::x outside arena stages: only `allow` is set

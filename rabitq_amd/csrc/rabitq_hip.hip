@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <charconv>
+#include <chrono>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -34,13 +35,14 @@
 #include "host_state.h"
 #include "host_query.h"
 #include "host_build.h"
+#include "host_mutate.h"
 
 // ------------------------------------------------------------------------------------------------
 // extern "C"
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-const char *rq_version(void) { return "rabitq_hip 0.6.0 (gfx950, abi 4)"; }
+const char *rq_version(void) { return "rabitq_hip 0.7.0 (gfx950, abi 4)"; }
 uint32_t rq_abi_version(void) { return RQ_ABI_VERSION; }
 const char *rq_last_error(void) { return g_err.c_str(); }
 
@@ -635,6 +637,7 @@ rq_status rq_filter_create(const rq_index *idx, const uint32_t *allow_bits, uint
     RQC(ensure_device());
     std::unique_ptr<rq_filter> f(new rq_filter());
     f->idx = idx;
+    f->generation = idx->generation;
     const uint64_t n = idx->n, nwords = (n + 63) / 64 * 2 + 2;  // (whole 64-position waves, and never empty)
     const uint64_t in_words = (nbits + 31) / 32;
     DevBuf<uint32_t> staged;  // the caller's bitmap in device memory (host bitmaps are copied)
@@ -678,6 +681,27 @@ rq_status rq_filter_rows(const rq_filter *f, uint64_t *out_admitted) {
     return RQ_OK;
 }
 void rq_filter_free(rq_filter *f) { delete f; }
+
+// ---- in-place mutation (host_mutate.h): the index afterwards equals a fresh build of its live rows, bit for bit ----
+static rq_status mutate_done(const rq_index *idx, rq_status s, std::chrono::steady_clock::time_point t0) {
+    if (s != RQ_OK) (void)hipGetLastError();  // (a failed hipMalloc's sticky error must not fail the next call)
+    if (idx) g_mutate_stats.rows_after = idx->n;
+    g_mutate_stats.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return s;
+}
+rq_status rq_add(rq_index *idx, const float *rows, uint64_t m, uint32_t d, const uint32_t *ids, int rows_on_device,
+                 uint32_t *out_first_id) {
+    const auto t0 = std::chrono::steady_clock::now();
+    return mutate_done(idx, index_add(idx, rows, m, d, ids, rows_on_device, out_first_id), t0);
+}
+rq_status rq_remove(rq_index *idx, const uint32_t *id_bits, uint64_t nbits, int bits_on_device, uint64_t *out_removed) {
+    const auto t0 = std::chrono::steady_clock::now();
+    return mutate_done(idx, index_remove(idx, id_bits, nbits, bits_on_device, out_removed), t0);
+}
+rq_status rq_last_mutate_stats(rq_mutate_stats_t *out) {
+    if (!out) return fail(RQ_ERR_INVALID, "null argument");
+    return copy_out_sized(out, g_mutate_stats);
+}
 
 rq_status rq_query(const rq_index *idx, const float *query, uint32_t len, uint32_t probe, uint32_t topk,
                    int heuristic_rank, float *out_dist, uint32_t *out_id, uint32_t *out_n) {

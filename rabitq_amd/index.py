@@ -91,6 +91,9 @@ class RaBitQ:
 
     def __init__(self, handle):
         self._h = handle
+        self._refresh()
+
+    def _refresh(self):
         info = Info()
         check(lib().rq_info(self._h, C.byref(info)))
         self.dim, self.k, self.n, self.max_list_len = int(info.dim), int(info.k), int(info.n), int(info.max_list_len)
@@ -237,6 +240,71 @@ class RaBitQ:
         h = C.c_void_p()
         check(lib().rq_filter_create(self._h, C.c_void_p(bits_ptr), nbits, 1, C.byref(h)))
         return Filter(self, h)
+
+    # ---- in-place mutation: the index afterwards equals a fresh build of its live rows -------------
+    def _rows(self, vectors):
+        v = np.asarray(vectors)
+        if v.dtype.kind not in "fiu":
+            raise TypeError(f"vectors must be real numbers, not {v.dtype}")
+        if v.ndim != 2:
+            raise ValueError(f"vectors must be 2-D (m x d), not {v.ndim}-D")
+        if v.shape[1] == 0 or (v.shape[1] + 63) // 64 * 64 != self.dim:
+            raise _lib.RabitqError(-2, f"row length {v.shape[1]} does not pad to index dim {self.dim}")
+        return _f32(v)
+
+    @staticmethod
+    def _ids(ids, m):
+        a = np.asarray(ids)
+        if a.dtype.kind not in "iu":
+            raise TypeError(f"ids must be integers, not {a.dtype}")
+        if a.ndim != 1 or a.size != m:
+            raise ValueError(f"ids must be 1-D with one id per row ({m}), not shape {a.shape}")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise ValueError("ids are u32: 0 <= id < 2^32")
+        return np.ascontiguousarray(a, dtype=np.uint32)
+
+    def add(self, vectors, ids=None) -> np.ndarray:
+        """Insert rows (m x d, d padding to dim) -> the u32 ids they got: `ids` (absent from the index, unique), or by default
+        the next ids after the largest the index holds.  One relayout (include/rabitq_hip.h: rq_add); filters made before it
+        are refused afterwards."""
+        rows = self._rows(vectors)
+        m = rows.shape[0]
+        idv = self._ids(ids, m) if ids is not None else None
+        first = C.c_uint32()
+        check(lib().rq_add(self._h, _addr(rows), m, rows.shape[1], _addr(idv), 0, C.byref(first)))
+        self._refresh()
+        return idv.copy() if idv is not None else np.arange(m, dtype=np.uint64).astype(np.uint32) + np.uint32(first.value)
+
+    def add_device(self, rows_ptr: int, m: int, d: int, ids_ptr: int = None) -> int:
+        """rq_add on device-resident rows (raw HIP device addresses, as build_device takes); ids_ptr: m u32 ids on the device,
+        None = the next ids.  -> the first id given (default ids: ids first .. first + m - 1)."""
+        first = C.c_uint32()
+        check(lib().rq_add(self._h, C.c_void_p(rows_ptr), m, d, C.c_void_p(ids_ptr or 0), 1, C.byref(first)))
+        self._refresh()
+        return int(first.value)
+
+    def remove(self, ids=None, mask=None) -> int:
+        """Remove the ids `ids` (an id array) or those where `mask` (a boolean mask over ids) is set; ids not in the index are
+        ignored.  -> rows removed.  One relayout (rq_remove) unless nothing matched."""
+        if ids is not None:
+            a = np.asarray(ids)
+            if a.size and a.dtype.kind not in "iu":
+                raise TypeError(f"ids must be integers, not {a.dtype}")
+        words, nbits = pack_filter_bits(ids=ids, mask=mask)
+        removed = C.c_uint64()
+        check(lib().rq_remove(self._h, _addr(words), nbits, 0, C.byref(removed)))
+        self._refresh()
+        return int(removed.value)
+
+    def update(self, ids, vectors) -> None:
+        """Give the ids `ids` the rows `vectors` (ids not in the index are inserted): remove followed by add with those ids --
+        two relayouts, not one."""
+        rows = self._rows(vectors)
+        idv = self._ids(ids, rows.shape[0])
+        if np.unique(idv).size != idv.size:
+            raise ValueError("ids must be unique")
+        self.remove(ids=idv)
+        self.add(rows, idv)
 
     # ---- RaBitQ::query (src/rabitq.rs:268) ------------------------------------------------------
     def query(self, query, probe: int, topk: int, heuristic_rank: bool = False, filter: Filter = None):
@@ -416,6 +484,13 @@ def last_profile() -> dict:
     p = ProfileT()
     check(lib().rq_last_profile(C.byref(p)))
     return {name: getattr(p, name) for name, _ in ProfileT._fields_ if name != "struct_size"}
+
+
+def last_mutate_stats() -> dict:
+    """The calling thread's last add / remove by phase (include/rabitq_hip.h: rq_last_mutate_stats)."""
+    st = _lib.MutateStatsT()
+    check(lib().rq_last_mutate_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _lib.MutateStatsT._fields_ if name not in ("struct_size", "reserved0")}
 
 
 def calculate_recall(truth, res, topk: int) -> float:
