@@ -476,6 +476,10 @@ rq_status rq_set_profiling(int level);
  * 256, 512, 768, 1024}), 1 = never (test hook).  Identical results.
  * "dense_dir": test hook, 1 (default) = the VALU stages of large batches write their survivor runs into a directory
  * indexed by stream position (nothing to sort), 0 = runs are appended and the directory is sorted.
+ * "prep_placement": 1 (default) = a pass whose only matrix-core stage is the final one groups that stage before the query
+ * quantisation, which then writes the fp6 operand rows straight into the stage's tile images (large stages placed by rank; not
+ * filtered, shard-like, arena, seeded or re-run passes), 0 = the pair-major operand and the copying fill everywhere.  Read once
+ * per pass.  Identical results.
  * "group_rank": test hook, placement of a cluster-major stage's (query, list) pairs: 0 = one atomic per pair,
  * 1 = automatic (default: per-block LDS histograms for big stages), 2 = histograms whenever they fit.
  * "assign_impl": nearest-list assignment of builds from now on: 0 (default) = bf16 matrix-core pre-filter + exact-order

@@ -246,6 +246,8 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
     bool sb_results_done = false;   // results and totals were written by the small-batch kernels (heap ranker)
     bool sb_fused_finish = false;   // the final stage ends in sb_finish_kernel
     bool sb_filled = false;         // the final stage's pair-major records were written by sb_query_kernel
+    bool placed = false;            // the final stage was placed before the quantisation, its operand rows were written in place (below)
+    bool fin_additive = false;      // ... and the gate its images were laid out for
     if (small) {
         // the early stages run inside one block per query: the first one takes what would be two (16 x topk candidates
         // under threshold f32::MAX cost one gather round), and the in-block part ends after 64 K candidates at the latest
@@ -356,6 +358,51 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
         // of it through anyway): one stage of launches less for ~1 % more exact distances
         stages = build_stages((uint64_t)std::max<uint32_t>(topk, 1) * (rq_large_batch(nq) ? growth : 1), growth, ~0ull);
     }
+    // Final stage placed ahead of the quantisation (option prep_placement, snapshot for the whole pass).  Its grouping depends on the
+    // probe lists, the list lengths and the stage boundaries only, all known here: the stream positions come from the index's offsets,
+    // the places from group_rank_kernel / group_scan_kernel, and the quantisation then writes every pair's fp6 operand row and the
+    // threshold-free part of its tail straight into the stage's tile images -- no pair-major copy of the operand, no copy pass, and
+    // the tails are completed (with the lists' v' ranges on the way) by stage_tail_kernel once the early stages have set the
+    // thresholds.  The images live in a buffer of their own: the early stages' records go through ws.recs in between.
+    // Passes that keep the older kernels: filtered, listed (shard-like), arena (seg_final), seeded and re-run passes, caller-supplied
+    // probe lists, a final stage placed by atomics (small stages), dimensions without a lane-group quantisation kernel.
+    const bool prep_dim = dim == 64 || dim == 128 || dim == 256 || dim == 512 || dim == 768 || dim == 1024;
+    const bool will_list = (filt || (idx->nonempty_lists * 2 < k && npairs >= 65536)) && g_pair_split.load() != 0 && prep_dim;
+    if (g_prep_placement.load() != 0 && !filt && !ext_cluster && !d_row_map && !qp.thr_init && !qp.seg_final && !will_list && prep_dim &&
+        scan_is_fused(W) && k <= 32768 && !stages.empty() && stages.back().s_hi == 0xFFFFFFFFu && stage_on_matrix(stages.back())) {
+        placed = true;
+        for (size_t i = 0; i + 1 < stages.size(); ++i) placed = placed && !stage_on_matrix(stages[i]);
+        const int rank_opt = g_group_rank.load();  // (the stage loop's rule for a stage of npairs work items)
+        placed = placed && (rank_opt == 2 || (rank_opt == 1 && npairs >= 16 * RQ_RANK_ITEMS && npairs / RQ_RANK_ITEMS >= k / 256));
+        const int gate_opt = g_scan_gate.load();
+        fin_additive = scan_has_additive(W) && idx->list_uref.p != nullptr && gate_opt != 1 && (gate_opt == 2 || !idx->additive_loose.load());
+    }
+    if (placed) {
+        const Stage &fin = stages.back();
+        const uint32_t nblk = ceil_div(npairs, RQ_RANK_ITEMS);
+        RQC(ws.img_final.ensure(((size_t)npairs + 32ull * k + 32) * (12ull * W + 2 + RQ_REC_TAIL)));  // (as ws.recs)
+        RQC(ws.pair_begin.ensure(npairs));
+        RQC(ws.fin_rank.ensure(npairs));
+        RQC(ws.fin_rank_base.ensure((size_t)nblk * k));
+        RQC(ws.fin_grp_cnt.ensure(k + 4));
+        RQC(ws.fin_grp_start.ensure(k + 1));
+        if (fin_additive) RQC(ws.grp_vref.ensure(2 * (size_t)k));
+        pf.begin(PF_GROUP);
+        {  // every word the pass wants zeroed, in one launch
+            ClearSpans cs{};
+            cs.p[0] = reinterpret_cast<uint32_t *>(ws.totals.p), cs.n[0] = 16;   // the pass's totals [0..7]
+            cs.p[1] = reinterpret_cast<uint32_t *>(ws.stat.p), cs.n[1] = 512;    // the matrix-core scan's step counters (+ developer hooks)
+            cs.p[2] = ws.big_list.p + nq, cs.n[2] = 3;
+            cs.p[3] = ws.fin_grp_cnt.p, cs.n[3] = k + 4;
+            if (rq_large_batch(nq)) cs.p[4] = ws.q_hist.p, cs.n[4] = k + 2;
+            clear_words_kernel<<<std::max(2u, ceil_div(k + 4, 256)), 256, 0, st>>>(cs);
+        }
+        pair_prefix_lens_kernel<<<ceil_div(nq, 4), 256, 0, st>>>(idx->offsets.p, probe_cluster, k, nq, nprobe, ws.rough_cnt.p, ws.pair_begin.p, ws.scal.p);
+        group_rank_kernel<<<nblk, 1024, (size_t)k * 4, st>>>(nullptr, probe_cluster, npairs, nprobe, nprobe, fin.s_lo, fin.s_hi, k, ws.fin_grp_cnt.p,
+                                                            ws.fin_rank.p, ws.fin_rank_base.p, ws.pair_begin.p, idx->offsets.p);
+        group_scan_kernel<<<1, 1024, 0, st>>>(ws.fin_grp_cnt.p, k, ws.fin_grp_start.p, 1u | 2u | (fin_additive ? 4u : 0u), ws.img_final.p, 12 * W);
+        pf.end();
+    }
     // 3. per-pair query quantisation (:304-317)
     pf.begin(PF_PREP);
     {
@@ -394,9 +441,17 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
             HIPC(hipStreamSynchronize(st));
             nlive = (uint32_t)*h_live;
         }
+        PrepPlace pl{};
+        if (placed) {
+            pl.stream_begin = ws.pair_begin.p, pl.rank = ws.fin_rank.p, pl.blk_base = ws.fin_rank_base.p, pl.grp_start = ws.fin_grp_start.p;
+            pl.img = ws.img_final.p, pl.s_lo = stages.back().s_lo, pl.s_hi = stages.back().s_hi, pl.tile_images = fin_additive ? 2u : 1u;
+        }
 #define RQ_PREP_SMALL(LP, R, PPB, PP)                                                                              \
     do {                                                                                                           \
-        if (listed)                                                                                                \
+        if (placed)                                                                                                \
+            prep_small_placed_kernel<LP, R, PP><<<ceil_div(npairs, (PPB) * (PP)), 256, 0, st>>>(ws.y.p, idx->centroids.p, idx->offsets.p, probe_cluster, \
+                                                                    probe_dist, npairs, nprobe, ws.scal.p, qn, k, idx->nonempty_lists * 2 < k ? 2u : 1u, qn_slots, pl); \
+        else if (listed)                                                                                           \
             prep_small_listed_kernel<LP, R, PP><<<std::max(1u, ceil_div(nlive, (PPB) * (PP))), 256, 0, st>>>(ws.y.p, idx->centroids.p, idx->offsets.p, probe_cluster, \
                                                                     probe_dist, ws.live_list.p, nlive, nprobe, ws.scal.p, qn, q6, k); \
         else                                                                                                       \
@@ -423,10 +478,10 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
         RQC(ws.stream_len.ensure(nq));
         pair_prefix_filtered_kernel<<<ceil_div(nq, 4), 256, 0, st>>>(ws.scal.p, nq, nprobe, ws.rough_cnt.p, probe_cluster, filt->sub_off.p, k,
                                                                      ws.stream_len.p);
-    } else
+    } else if (!placed)  // (placed: the stream positions were needed ahead of the quantisation, which has copied them into the scalars)
         pair_prefix_kernel<<<ceil_div(nq, 4), 256, 0, st>>>(ws.scal.p, nq, nprobe, ws.rough_cnt.p);
     if (rq_large_batch(nq)) {  // large batch: rerank queries of the same nearest list back to back (cache locality of the row gather)
-        HIPC(hipMemsetAsync(ws.q_hist.p, 0, (size_t)(k + 2) * 4, st));
+        if (!placed) HIPC(hipMemsetAsync(ws.q_hist.p, 0, (size_t)(k + 2) * 4, st));
         order_count_kernel<<<ceil_div(nq, 256), 256, 0, st>>>(probe_cluster, nprobe, nq, k, ws.q_hist.p);
         group_scan_kernel<<<1, 1024, 0, st>>>(ws.q_hist.p, k + 1, ws.q_start.p, 0u, nullptr, 0u);  // also zeroes the histogram: cursor
         order_scatter_kernel<<<ceil_div(nq, 256), 256, 0, st>>>(probe_cluster, nprobe, nq, k, ws.q_start.p, ws.q_hist.p,
@@ -435,9 +490,11 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
     }
     // 4. ranker state (rerank.rs:70-77, :129-139) and per-query counters
     init_state_kernel<<<ceil_div(nq, 256), 256, 0, st>>>(rs, ws.surv_cnt.p, nq, qp.thr_init, d_row_map);
-    HIPC(hipMemsetAsync(ws.totals.p, 0, 8 * sizeof(unsigned long long), st));
-    HIPC(hipMemsetAsync(ws.big_list.p + nq, 0, 12, st));
-    HIPC(hipMemsetAsync(ws.stat.p, 0, 256 * sizeof(unsigned long long), st));  // the matrix-core scan's step counters (+ developer hooks)
+    if (!placed) {  // (placed: cleared by the pass's one clearing launch)
+        HIPC(hipMemsetAsync(ws.totals.p, 0, 8 * sizeof(unsigned long long), st));
+        HIPC(hipMemsetAsync(ws.big_list.p + nq, 0, 12, st));
+        HIPC(hipMemsetAsync(ws.stat.p, 0, 256 * sizeof(unsigned long long), st));  // the matrix-core scan's step counters (+ developer hooks)
+    }
     pf.end();
 
     // 5. stages: planned above
@@ -472,8 +529,12 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
         const bool arena_stage = qp.seg_final && span > qp.cap && scan_is_fused(W) && rq_large_batch(nq);
         const int gate_opt = g_scan_gate.load();
         // (filtered stages run the bf16 threshold form: the filtered instantiations exist for that gate only)
-        const bool additive = use_mfma && !arena_stage && !filt && scan_has_additive(W) && idx->list_uref.p != nullptr && gate_opt != 1 &&
-                              (gate_opt == 2 || !idx->additive_loose.load());
+        const bool placed_stage = placed && stage_no + 1 == stages.size();  // its images were laid out before the quantisation, for the gate chosen there
+        if (placed_stage && (g_scan_dbg.load() & 16384))  // developer hook: the pass's stage list
+            fprintf(stderr, "[rabitq_hip] stage %u: placed ahead of the quantisation (%s gate)\n", stage_no, fin_additive ? "additive" : "bf16");
+        const bool additive = placed_stage ? fin_additive
+                                           : use_mfma && !arena_stage && !filt && scan_has_additive(W) && idx->list_uref.p != nullptr && gate_opt != 1 &&
+                                                 (gate_opt == 2 || !idx->additive_loose.load());
         pf.begin(PF_GROUP);
         ScanArgs a{};
         ScanPtrs sp{};
@@ -486,7 +547,14 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
             slot_hi = (uint32_t)std::min<uint64_t>(nprobe, (uint64_t)(sg.s_hi - 1) / min_len + 1);
         const uint32_t stage_pairs = nq * slot_hi;
         bool ranked = false;
-        if (cluster_major) {
+        if (placed_stage) {
+            // grouped and filled already, but for what hangs on the thresholds: the tails' threshold part and, additive gate, C_q and
+            // the lists' v' ranges
+            stage_tail_kernel<<<k, 256, 0, st>>>(ws.img_final.p, ws.fin_grp_start.p, ws.fin_grp_cnt.p, ws.thr.p, 12 * W, idx->fstats,
+                                                 additive ? 2u : 1u, idx->list_uref.p, ws.grp_vref.p);
+            if (additive) ws.pend_additive = true;
+            a.ngroups = k;
+        } else if (cluster_major) {
             HIPC(hipMemsetAsync(ws.grp_cnt.p, 0, (size_t)((k + 4) & ~3u) * 4, st));  // 16-byte multiple: one fill kernel
             // big stages: places inside the groups come out of the counting pass (LDS histogram per block)
             const int rank_opt = g_group_rank.load();  // 0 never, 1 auto, 2 whenever the histogram fits LDS (tests)
@@ -509,7 +577,7 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
         // pack the stage's work records (query operand + scalars + current threshold + local range)
         const uint32_t *operand = fp6_records ? ws.qf6.p
                                               : (scan_is_fused(W) ? ws.qnib.p : reinterpret_cast<const uint32_t *>(ws.planes.p));
-        if (!(sb_filled && !cluster_major)) {  // (the small-batch kernel has written a pair-major final stage's records already)
+        if (!(sb_filled && !cluster_major) && !placed_stage) {  // (the small-batch kernel has written a pair-major final stage's records already)
             // a sharded pass visits only the listed pairs when the stage's work items ARE the pairs (every slot can be in the stage)
             const bool fill_listed = listed && ranked && cluster_major && slot_hi == nprobe;
             const uint32_t fill_items = fill_listed ? nlive : stage_pairs;
@@ -532,7 +600,7 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
                                                                     ws.rank_base.p, k, idx->list_uref.p, fill_listed ? ws.live_list.p : nullptr);
             }
         }
-        if (additive) {  // the stage's v' ranges per list (the candidates' side of the additive bound is built from them in the scan)
+        if (additive && !placed_stage) {  // the stage's v' ranges per list (the candidates' side of the additive bound is built from them in the scan)
             RQC(ws.grp_vref.ensure(2 * (size_t)k));
             group_vrange_kernel<<<k, 256, 0, st>>>(ws.recs.p, ws.grp_start.p, ws.grp_cnt.p, 12 * W, ws.grp_vref.p);
             ws.pend_additive = true;
@@ -540,10 +608,10 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
         pf.end();
         sp.codes = reinterpret_cast<const uint32_t *>(idx->codes.p);
         sp.factors = idx->factors.p;
-        sp.grp_start = ws.grp_start.p;
-        sp.grp_cnt = ws.grp_cnt.p;
+        sp.grp_start = placed_stage ? ws.fin_grp_start.p : ws.grp_start.p;
+        sp.grp_cnt = placed_stage ? ws.fin_grp_cnt.p : ws.grp_cnt.p;
         sp.offsets = idx->offsets.p;
-        sp.recs = ws.recs.p;
+        sp.recs = placed_stage ? ws.img_final.p : ws.recs.p;
         sp.surv = ws.surv.p;
         sp.runs = ws.runs.p;
         sp.surv_cnt = ws.surv_cnt.p;

@@ -187,6 +187,9 @@ struct Workspace {
     DevBuf<uint32_t> live_list;                 // sharded passes: the (query, list) pairs whose list has members here, + their count
     DevBuf<uint32_t> coarse_redo;               // pre-filtered coarse ranking over more than 8192 lists: rows left to the block-per-query selection
     DevBuf<uint32_t> pair_rank, rank_base;      // group_rank_kernel: places of a big stage's pairs inside their groups
+    // final stage placed ahead of the quantisation (option prep_placement): its tile images, the pairs' stream positions, and its own
+    // grouping (ws.recs / pair_rank / rank_base / grp_cnt / grp_start serve the early stages in between)
+    DevBuf<uint32_t> img_final, pair_begin, fin_rank, fin_rank_base, fin_grp_cnt, fin_grp_start;
     DevBuf<uint32_t> probe_cluster, recs, grp_cnt, grp_start, heap_len, heap_id, precise, need,
         nsurv, nshadow, win_count, arr_len, row_map, big_list;
     DevBuf<int32_t> heap_key;
@@ -610,6 +613,7 @@ static bool rq_large_batch(uint32_t nq) { return nq >= (uint32_t)g_large_from.lo
 static std::atomic<int> g_cluster_major_div{32};  // a VALU stage goes list-major once its (query, list) pairs reach k / this
 static std::atomic<int> g_stage_settle_pct{100};  // developer knob: where a large batch's early (VALU) stages end and the final (matrix-core) stage begins, in percent of the average list length
 static std::atomic<int> g_scan_tile_table{1};  // 0 = plain (list x tile) grids everywhere (test / measurement hook)
+static std::atomic<int> g_prep_placement{1};  // 1 = the final matrix-core stage is placed before the quantisation, which writes its operand rows in place (where it applies); 0 = pair-major operand + stage_fill_kernel everywhere
 static std::atomic<int> g_group_rank{1};  // group_rank_kernel for cluster-major stages: 0 never, 1 big stages, 2 always
 static std::atomic<int> g_shared_thr{1};  // rq_query_batch_sharded_device: thresholds shared between the shards (0 never, 1 world > 1, 2 always)
 static std::atomic<int> g_sb_span{2560};  // developer knob: stream positions a query's block scans itself at most (small-batch path)

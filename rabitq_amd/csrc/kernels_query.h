@@ -1001,7 +1001,45 @@ __global__ __launch_bounds__(256) void prep_kernel(const float *__restrict__ y,
 // are half a qnib dword, its four fp6 fields 24 bits of the 6-dword image of its 32-dimension block.
 // Writes the fused scan's operands only (no bit planes); arithmetic identical to prep_kernel.
 // The pairs p0, p0 + 64/LP, ... (PP of them) of one lane group; p0 already includes the group's index lane / LP.
-template <int LP, int R, int PP>
+// does list [begin, begin+len) of the candidate stream intersect the stage [s_lo, s_hi) ?
+__device__ __forceinline__ bool stream_in_stage(uint32_t begin, uint32_t len, uint32_t s_lo, uint32_t s_hi) {
+    const uint64_t b = begin, e = b + len;
+    return len != 0 && b < s_hi && e > s_lo;
+}
+#define RQ_RANK_ITEMS 32768u  // work items per block of group_rank_kernel
+// The twelve tail dwords of a stage record that do not depend on the query's threshold (t[RQ_REC_THR] is left alone).
+__device__ __forceinline__ void stage_tail_static(const PairScalars &ps, bool in, uint32_t slot, uint32_t s_lo, uint32_t s_hi,
+                                                  uint32_t *__restrict__ t) {
+    uint32_t lo = 0, hi = 0;
+    if (in) {
+        lo = s_lo > ps.stream_begin ? s_lo - ps.stream_begin : 0u;
+        hi = s_hi - ps.stream_begin;  // in-stage => stream_begin < s_hi
+        hi = hi < ps.list_len ? hi : ps.list_len;
+    }
+    t[RQ_REC_LOWER] = __builtin_bit_cast(uint32_t, ps.lower);
+    t[RQ_REC_DELTA] = __builtin_bit_cast(uint32_t, ps.delta);
+    t[RQ_REC_SUMQ] = __builtin_bit_cast(uint32_t, ps.sumq);
+    t[RQ_REC_YCD] = __builtin_bit_cast(uint32_t, ps.ycd);
+    t[RQ_REC_YCD_SQRT] = __builtin_bit_cast(uint32_t, ps.ycd_sqrt);
+    t[RQ_REC_LO] = lo;
+    t[RQ_REC_HI] = hi;
+    t[RQ_REC_ROW] = ps.row;
+    t[RQ_REC_SLOT] = slot;
+    t[RQ_REC_LIST_BEGIN] = ps.list_begin;
+    t[RQ_REC_LIST_LEN] = ps.list_len;
+}
+// Placement of the pass's final (matrix-core) stage, decided BEFORE the quantisation (run_pass, option prep_placement): stream
+// positions from the list lengths (pair_prefix_lens_kernel), places inside the lists' groups from group_rank_kernel /
+// group_scan_kernel.  The quantisation then writes a pair's fp6 operand row and the threshold-free part of its tail straight
+// into the stage's tile image (the place stage_fill_item computes: grp_start[c] + blk_base[block][c] + rank), and
+// stage_tail_kernel adds the threshold's part once the early stages have run.  Work item = pair (every slot can be in the stage).
+struct PrepPlace {
+    const uint32_t *stream_begin;                 // per pair
+    const uint32_t *rank, *blk_base, *grp_start;  // rank ~0u: the pair is not in the stage
+    uint32_t *img;                                // the final stage's tile images
+    uint32_t s_lo, s_hi, tile_images;             // tile_images: 1 = bf16 threshold form, 2 = additive form
+};
+template <int LP, int R, int PP, bool PLACE = false>
 __device__ __forceinline__ void prep_small_pairs(const float *__restrict__ y, const float *__restrict__ centroids,
                                                  const uint32_t *__restrict__ offsets,
                                                  const uint32_t *__restrict__ pair_cluster,
@@ -1010,7 +1048,8 @@ __device__ __forceinline__ void prep_small_pairs(const float *__restrict__ y, co
                                                  uint32_t *__restrict__ qnib, uint32_t *__restrict__ qf6,
                                                  uint32_t nlists, uint32_t skip_empty, uint32_t p0,
                                                  const uint32_t *__restrict__ live_list = nullptr /* compacted pair ids (pair_split_kernel): p0 indexes it */,
-                                                 uint32_t qn_slots = 0xFFFFFFFFu /* the 4-bit operand is written for probe slots below this only */) {
+                                                 uint32_t qn_slots = 0xFFFFFFFFu /* the 4-bit operand is written for probe slots below this only */,
+                                                 const PrepPlace &pl = PrepPlace{} /* PLACE: qf6 is not used */) {
     // dim = 4 * LP * R: LP lanes per pair, each owning 4 consecutive dimensions in each of R rounds of 4*LP
     // dimensions (R > 1 only with LP = 64: dim 512, 768, 1024).  Every lane group handles PP pairs: the kernel is a
     // chain of dependent gathers (probe list -> centroid row, list bounds), so the loads of all PP pairs are issued
@@ -1022,6 +1061,7 @@ __device__ __forceinline__ void prep_small_pairs(const float *__restrict__ y, co
     float ycd_in[PP];
     bool live[PP];
     uint32_t pid[PP];  // the pair each of the PP rounds works on
+    uint32_t sbeg[PP], place[PP];  // PLACE: stream position of the pair's list; its place in the final stage (~0u: not in it)
 #pragma unroll
     for (int pp = 0; pp < PP; ++pp) {
         const uint32_t pi = p0 + pp * PPW;
@@ -1030,6 +1070,11 @@ __device__ __forceinline__ void prep_small_pairs(const float *__restrict__ y, co
         const uint32_t p = pid[pp];
         cl[pp] = live[pp] ? pair_cluster[p] : 0xFFFFFFFFu;
         ycd_in[pp] = live[pp] ? pair_ycd[p] : 0.0f;
+        sbeg[pp] = 0u, place[pp] = ~0u;
+        if constexpr (PLACE) {
+            sbeg[pp] = live[pp] ? pl.stream_begin[p] : 0u;
+            place[pp] = live[pp] ? pl.rank[p] : ~0u;
+        }
     }
     float4 cv[PP][R], yv[PP][R];
 #pragma unroll
@@ -1038,6 +1083,10 @@ __device__ __forceinline__ void prep_small_pairs(const float *__restrict__ y, co
         const bool in = live[pp] && c < nlists;
         lb[pp] = in ? offsets[c] : 0u;
         ll[pp] = in ? offsets[c + 1] - lb[pp] : 0u;
+        if constexpr (PLACE) {
+            if (in && place[pp] != ~0u) place[pp] += pl.grp_start[c] + pl.blk_base[(uint64_t)(p / RQ_RANK_ITEMS) * nlists + c];
+            else place[pp] = ~0u;
+        }
         const uint32_t row = live[pp] ? p / pairs_per_row : 0u;
         // skip_empty == 2 (an index with many empty lists: a shard of a multi-GPU deployment, where 7 of 8 probed lists live on
         // other ranks): the query and centroid rows of a pair are only fetched once its list is known to have members -- one more
@@ -1062,10 +1111,23 @@ __device__ __forceinline__ void prep_small_pairs(const float *__restrict__ y, co
             if (sub == 0) {
                 PairScalars s;
                 s.lower = 0.0f, s.delta = 0.0f, s.sumq = 0.0f, s.ycd = ycd_in[pp], s.ycd_sqrt = 0.0f;
-                s.row = row, s.list_begin = 0, s.list_len = 0, s.stream_begin = 0, s.pad = 0;
+                s.row = row, s.list_begin = 0, s.list_len = 0, s.stream_begin = sbeg[pp], s.pad = 0;
                 scal[p] = s;
             }
             continue;
+        }
+        // where the fp6 operand row goes: the pair-major buffer, or (PLACE) the pair's row of the final stage's tile image
+        uint32_t *q6row = qf6 ? qf6 + (uint64_t)p * 12 * W : nullptr;
+        uint32_t *tail_dst = nullptr;
+        if constexpr (PLACE) {
+            q6row = nullptr;
+            if (place[pp] != ~0u) {
+                const bool additive = pl.tile_images == 2;
+                const uint32_t opld = rq_img_opld(12 * W, additive), at = place[pp];
+                uint32_t *base = pl.img + (uint64_t)(at >> 5) * rq_img_dwords(12 * W, additive);
+                q6row = base + (at & 31u) * opld;
+                tail_dst = base + 32 * opld + (at & 31u) * (additive ? RQ_RECA_TAIL : RQ_REC_TAIL);
+            }
         }
         float r[R][4];
         float mn = 3.402823466e+38f, mx = -3.402823466e+38f;
@@ -1108,9 +1170,9 @@ __device__ __forceinline__ void prep_small_pairs(const float *__restrict__ y, co
             {  // qf6: group t = dsub % 8 of a 32-dimension block holds stream bits [24t, 24t+24) of its 6 dwords
                 const uint32_t nxt = __shfl_down(f24, 1, LP);
                 const uint32_t t = dsub & 7, sh = 8 * (t & 3);
-                if (qf6 && (t & 3) != 3) {
+                if (q6row && (t & 3) != 3) {
                     const uint32_t w = dsub >> 4, h = (dsub >> 3) & 1;
-                    qf6[(uint64_t)p * 12 * W + h * 6 * W + 6 * w + 3 * (t >> 2) + (t & 3)] = (f24 >> sh) | (nxt << (24 - sh));
+                    q6row[h * 6 * W + 6 * w + 3 * (t >> 2) + (t & 3)] = (f24 >> sh) | (nxt << (24 - sh));
                 }
             }
         }
@@ -1126,9 +1188,18 @@ __device__ __forceinline__ void prep_small_pairs(const float *__restrict__ y, co
             s.row = row;
             s.list_begin = lb[pp];
             s.list_len = ll[pp];
-            s.stream_begin = 0;  // filled by pair_prefix_kernel
+            s.stream_begin = sbeg[pp];  // PLACE: known already; else filled by pair_prefix_kernel
             s.pad = 0;
             scal[p] = s;
+            if constexpr (PLACE) {
+                if (tail_dst) {  // the tail but for the threshold's part (stage_tail_kernel), 16-byte aligned in both image layouts
+                    uint32_t t[12];
+                    stage_tail_static(s, true, p - row * pairs_per_row, pl.s_lo, pl.s_hi, t);
+                    t[RQ_REC_THR] = 0u;
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) reinterpret_cast<uint4 *>(tail_dst)[i] = make_uint4(t[4 * i], t[4 * i + 1], t[4 * i + 2], t[4 * i + 3]);
+                }
+            }
         }
     }
 }
@@ -1146,6 +1217,22 @@ __global__ __launch_bounds__(256) void prep_small_kernel(const float *__restrict
     const uint32_t p0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * (PPW * PP) + (threadIdx.x & 63) / LP;
     prep_small_pairs<LP, R, PP>(y, centroids, offsets, pair_cluster, pair_ycd, npairs, pairs_per_row, scal, qnib, qf6, nlists,
                                 skip_empty, p0, nullptr, qn_slots);
+}
+
+// The same quantisation with the final stage placed ahead of it (PrepPlace): no pair-major fp6 buffer
+template <int LP, int R, int PP>
+__global__ __launch_bounds__(256) void prep_small_placed_kernel(const float *__restrict__ y,
+                                                                const float *__restrict__ centroids,
+                                                                const uint32_t *__restrict__ offsets,
+                                                                const uint32_t *__restrict__ pair_cluster,
+                                                                const float *__restrict__ pair_ycd, uint32_t npairs,
+                                                                uint32_t pairs_per_row, PairScalars *__restrict__ scal,
+                                                                uint32_t *__restrict__ qnib, uint32_t nlists,
+                                                                uint32_t skip_empty, uint32_t qn_slots, const PrepPlace pl) {
+    constexpr uint32_t PPW = 64 / LP;
+    const uint32_t p0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * (PPW * PP) + (threadIdx.x & 63) / LP;
+    prep_small_pairs<LP, R, PP, true>(y, centroids, offsets, pair_cluster, pair_ycd, npairs, pairs_per_row, scal, qnib, nullptr, nlists,
+                                      skip_empty, p0, nullptr, qn_slots, pl);
 }
 
 // Sharded passes (a rank of a multi-GPU deployment: most probed lists live on other ranks, i.e. are empty here): one THREAD
@@ -1221,13 +1308,20 @@ __device__ __forceinline__ void pair_prefix_row(PairScalars *__restrict__ scal, 
                                                 unsigned long long *__restrict__ rough_count,
                                                 const uint32_t *__restrict__ pair_cluster = nullptr,
                                                 const uint32_t *__restrict__ sub_off = nullptr, uint32_t nlists = 0,
-                                                unsigned long long *__restrict__ stream_len = nullptr) {
+                                                unsigned long long *__restrict__ stream_len = nullptr,
+                                                const uint32_t *__restrict__ offsets = nullptr /* ahead of the quantisation: list lengths from here (with pair_cluster, nlists) */,
+                                                uint32_t *__restrict__ begin_out = nullptr /* ... and the positions go here, per pair */) {
     const uint32_t lane = threadIdx.x & 63;
     unsigned long long carry = 0, admitted = 0;
     for (uint32_t s0 = 0; s0 < nprobe; s0 += 64) {
         const uint32_t s = s0 + lane;
         PairScalars *ps = scal + (uint64_t)b * nprobe + s;
-        const unsigned long long len = s < nprobe ? ps->list_len : 0;
+        unsigned long long len = 0;
+        if (offsets) {
+            const uint32_t c = s < nprobe ? pair_cluster[(uint64_t)b * nprobe + s] : 0xFFFFFFFFu;
+            len = c < nlists ? offsets[c + 1] - offsets[c] : 0u;
+        } else
+            len = s < nprobe ? ps->list_len : 0;
         unsigned long long incl = len;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -1235,7 +1329,7 @@ __device__ __forceinline__ void pair_prefix_row(PairScalars *__restrict__ scal, 
             if ((int)lane >= o) incl += up;
         }
         const unsigned long long begin = carry + incl - len;
-        if (s < nprobe) ps->stream_begin = begin > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)begin;
+        if (s < nprobe) *(begin_out ? begin_out + (uint64_t)b * nprobe + s : &ps->stream_begin) = begin > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)begin;
         carry += __shfl(incl, 63, 64);
         if (sub_off) {
             const uint32_t c = s < nprobe && len ? pair_cluster[(uint64_t)b * nprobe + s] : 0xFFFFFFFFu;
@@ -1252,6 +1346,14 @@ __global__ __launch_bounds__(256) void pair_prefix_kernel(PairScalars *__restric
                                                           unsigned long long *__restrict__ rough_count) {
     const uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b < nq) pair_prefix_row(scal, b, nprobe, rough_count);
+}
+// ahead of the quantisation (PrepPlace): lengths from the index's offsets, positions into an array of their own
+__global__ __launch_bounds__(256) void pair_prefix_lens_kernel(const uint32_t *__restrict__ offsets, const uint32_t *__restrict__ pair_cluster,
+                                                               uint32_t nlists, uint32_t nq, uint32_t nprobe,
+                                                               unsigned long long *__restrict__ rough_count, uint32_t *__restrict__ begin_out,
+                                                               PairScalars *__restrict__ scal /* not touched */) {
+    const uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b < nq) pair_prefix_row(scal, b, nprobe, rough_count, pair_cluster, nullptr, nlists, nullptr, offsets, begin_out);
 }
 __global__ __launch_bounds__(256) void pair_prefix_filtered_kernel(PairScalars *__restrict__ scal, uint32_t nq, uint32_t nprobe,
                                                                    unsigned long long *__restrict__ rough_count,
@@ -1308,10 +1410,8 @@ __global__ __launch_bounds__(256) void filter_lists_kernel(const uint32_t *__res
 // pair-major: one group per pair.  cluster-major: pairs bucketed by list so that a list is read
 // from HBM once and scored against every query probing it.
 // ------------------------------------------------------------------------------------------------
-// does list [begin, begin+len) of the candidate stream intersect the stage [s_lo, s_hi) ?
 __device__ __forceinline__ bool pair_in_stage(const PairScalars &ps, uint32_t s_lo, uint32_t s_hi) {
-    const uint64_t b = ps.stream_begin, e = b + ps.list_len;
-    return ps.list_len != 0 && b < s_hi && e > s_lo;
+    return stream_in_stage(ps.stream_begin, ps.list_len, s_lo, s_hi);
 }
 
 // `count` = nq * slot_hi work items: only the first slot_hi slots of every query can be in the stage
@@ -1332,12 +1432,14 @@ __global__ void group_count_kernel(const PairScalars *__restrict__ scal,
 //   rank[i]           place of item i among its block's pairs of the same list (~0u: not in the stage)
 //   blk_base[blk][c]  first place of block blk's pairs in list c's group
 // Dynamic LDS: k counters.
-#define RQ_RANK_ITEMS 32768u
+// begins / offsets (ahead of the quantisation, PrepPlace): the stream positions and list lengths come from there, not from scal.
 __global__ __launch_bounds__(1024) void group_rank_kernel(const PairScalars *__restrict__ scal,
                                                           const uint32_t *__restrict__ probe_cluster, uint32_t count,
                                                           uint32_t nprobe, uint32_t slot_hi, uint32_t s_lo, uint32_t s_hi,
                                                           uint32_t k, uint32_t *__restrict__ grp_cnt,
-                                                          uint32_t *__restrict__ rank, uint32_t *__restrict__ blk_base) {
+                                                          uint32_t *__restrict__ rank, uint32_t *__restrict__ blk_base,
+                                                          const uint32_t *__restrict__ begins = nullptr,
+                                                          const uint32_t *__restrict__ offsets = nullptr) {
     extern __shared__ uint32_t rank_hist[];
     for (uint32_t c = threadIdx.x; c < k; c += 1024) rank_hist[c] = 0;
     __syncthreads();
@@ -1347,7 +1449,11 @@ __global__ __launch_bounds__(1024) void group_rank_kernel(const PairScalars *__r
         if (i >= count) break;
         const uint32_t b = i / slot_hi, p = b * nprobe + (i - b * slot_hi);
         uint32_t r = ~0u;
-        if (pair_in_stage(scal[p], s_lo, s_hi)) r = atomicAdd(&rank_hist[probe_cluster[p]], 1u);
+        if (begins) {
+            const uint32_t c = probe_cluster[p];
+            if (c < k && stream_in_stage(begins[p], offsets[c + 1] - offsets[c], s_lo, s_hi)) r = atomicAdd(&rank_hist[c], 1u);
+        } else if (pair_in_stage(scal[p], s_lo, s_hi))
+            r = atomicAdd(&rank_hist[probe_cluster[p]], 1u);
         rank[i] = r;
     }
     __syncthreads();
@@ -1419,6 +1525,66 @@ __device__ __forceinline__ uint32_t bf16_rne(float x) {
 }
 __device__ __forceinline__ float bf16_to_f32(uint32_t b) { return __builtin_bit_cast(float, b << 16); }
 
+// The threshold's part of a matrix-core stage record (comment in stage_fill_item): v'_q, the bound qb of the terms' magnitudes,
+// whether the integer form is safe, and the bf16 form's margin.  Shared by stage_fill_item and stage_tail_kernel.
+struct StageGate {
+    float v[4], qb, margin;
+    bool safe;
+};
+__device__ __forceinline__ StageGate stage_gate(float lower, float delta, float sumq, float ycd, float ycd_sqrt, float th,
+                                                const FactorStats &fs) {
+    StageGate g;
+    const float inv2d = 0.5f / delta;
+    g.v[0] = (th - ycd) * inv2d, g.v[1] = -inv2d, g.v[2] = -lower * inv2d, g.v[3] = ycd_sqrt * inv2d;
+    g.qb = (fabsf(th - ycd) + fs.cds_max + fabsf(lower) * fs.ppc_absmax + ycd_sqrt * fs.eb_max) *
+           fs.invfip_absmax * fabsf(inv2d);
+    g.safe = delta > 0.0f && g.qb + sumq < 524288.0f;  // also false for NaN / inf
+    g.margin = 2.0f + g.qb * (1.0f / 8192.0f) + (g.qb + sumq) * (1.0f / 262144.0f);
+    return g;
+}
+// additive form: the row's accumulator start value C_q (u0: the list's reference U0)
+__device__ __forceinline__ float stage_gate_cq(const StageGate &g, float sumq, const float4 u0) {
+    float bq = u0.x * g.v[0];
+    bq += u0.y * g.v[1];
+    bq += u0.w * g.v[3];
+    bq += 0.5f * sumq;
+    const float margin_a = 2.0f + g.qb * (1.0f / 8192.0f) + (g.qb + sumq) * (1.0f / 65536.0f);
+    float cq = -0.5f * (bq - margin_a);
+    if (!g.safe || !(fabsf(cq) < 1.0e37f)) cq = __builtin_inff();  // always flagged: the exact path decides
+    return cq;
+}
+// bf16 threshold form: the eight dwords at RQ_REC_V0
+__device__ __forceinline__ void stage_gate_bf16(const StageGate &g, float sumq, uint32_t *__restrict__ t8) {
+    const float v4 = -0.5f * (0.5f * sumq - g.margin);
+    uint32_t vh[4], vl[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float x = -0.5f * g.v[i];
+        vh[i] = bf16_rne(x);
+        vl[i] = bf16_rne(x - bf16_to_f32(vh[i]));
+    }
+    uint32_t c0 = bf16_rne(v4);
+    const float r1 = v4 - bf16_to_f32(c0);
+    uint32_t c1 = bf16_rne(r1);
+    uint32_t c2 = bf16_rne(r1 - bf16_to_f32(c1));
+    if (!g.safe) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) vh[i] = 0, vl[i] = 0;
+        c0 = 0x7F80u, c1 = 0, c2 = 0;  // +inf * 1: -S* = +inf
+    }
+    // A operand of the threshold MFMA, element e of lane half h = slot 8h + e:
+    //   vh0 vh0 vl0 vh1 vh1 vl1 c0 c1 | vh2 vh2 vl2 vh3 vh3 vl3 c2 0     against the candidate side's
+    //   uh0 ul0 uh0 uh1 ul1 uh1  1  1 | uh2 ul2 uh2 uh3 ul3 uh3  1 0
+    t8[0] = vh[0] | (vh[0] << 16);
+    t8[1] = vl[0] | (vh[1] << 16);
+    t8[2] = vh[1] | (vl[1] << 16);
+    t8[3] = c0 | (c1 << 16);
+    t8[4] = vh[2] | (vh[2] << 16);
+    t8[5] = vl[2] | (vh[3] << 16);
+    t8[6] = vh[3] | (vl[3] << 16);
+    t8[7] = c2;
+}
+
 // work item wi = (query, slot < slot_hi), handled by the 16 lanes threadIdx.x & ~15 .. | 15; thr_b: the query's threshold
 template <int LPP = 16 /* lanes per work item: 16, or 8 for the additive tile images (16-byte aligned operand rows) */>
 __device__ __forceinline__ void stage_fill_item(const PairScalars *__restrict__ scal,
@@ -1482,24 +1648,8 @@ __device__ __forceinline__ void stage_fill_item(const PairScalars *__restrict__ 
     }
     {  // the tail: computed by every lane of the pair (they would idle otherwise), stored 16 bytes per lane by lanes 0..4
         uint32_t t[RQ_REC_TAIL];
-        uint32_t lo = 0, hi = 0;
-        if (in) {
-            lo = s_lo > ps.stream_begin ? s_lo - ps.stream_begin : 0u;
-            hi = s_hi - ps.stream_begin;  // in-stage => stream_begin < s_hi
-            hi = hi < ps.list_len ? hi : ps.list_len;
-        }
-        t[RQ_REC_LOWER] = __builtin_bit_cast(uint32_t, ps.lower);
-        t[RQ_REC_DELTA] = __builtin_bit_cast(uint32_t, ps.delta);
-        t[RQ_REC_SUMQ] = __builtin_bit_cast(uint32_t, ps.sumq);
-        t[RQ_REC_YCD] = __builtin_bit_cast(uint32_t, ps.ycd);
-        t[RQ_REC_YCD_SQRT] = __builtin_bit_cast(uint32_t, ps.ycd_sqrt);
+        stage_tail_static(ps, in, p - ps.row * nprobe, s_lo, s_hi, t);
         t[RQ_REC_THR] = __builtin_bit_cast(uint32_t, thr[ps.row]);
-        t[RQ_REC_LO] = lo;
-        t[RQ_REC_HI] = hi;
-        t[RQ_REC_ROW] = ps.row;
-        t[RQ_REC_SLOT] = p - ps.row * nprobe;
-        t[RQ_REC_LIST_BEGIN] = ps.list_begin;
-        t[RQ_REC_LIST_LEN] = ps.list_len;
         // Integer form of the gate (used by the matrix-core scan).  With F = factor_ip * delta < 0,
         //   rough < thr  <=>  s > S* = [ (thr - ycd) + (-1) cds + (-lower) ppc + ysq eb ] / (2 F) + sumq / 2
         // (real arithmetic), a rank-5 bilinear form in u'_c = (1, cds, ppc, eb)/fip, 1  and v'_q.  The scan
@@ -1513,13 +1663,7 @@ __device__ __forceinline__ void stage_fill_item(const PairScalars *__restrict__ 
         // candidate the exact f32 expression would pass; where the scales make the bound unsafe (or
         // delta <= 0) the query is marked "always flagged" (-S* = +inf) and every candidate takes the
         // exact path.
-        const float th = thr[ps.row];
-        const float inv2d = 0.5f / ps.delta;
-        float v[4] = {(th - ps.ycd) * inv2d, -inv2d, -ps.lower * inv2d, ps.ycd_sqrt * inv2d};
-        const float qb = (fabsf(th - ps.ycd) + fs.cds_max + fabsf(ps.lower) * fs.ppc_absmax + ps.ycd_sqrt * fs.eb_max) *
-                         fs.invfip_absmax * fabsf(inv2d);
-        const bool safe = ps.delta > 0.0f && qb + ps.sumq < 524288.0f;  // also false for NaN / inf
-        const float margin = 2.0f + qb * (1.0f / 8192.0f) + (qb + ps.sumq) * (1.0f / 262144.0f);
+        const StageGate g = stage_gate(ps.lower, ps.delta, ps.sumq, ps.ycd, ps.ycd_sqrt, thr[ps.row], fs);
         if (tile_images == 2) {
             // Additive gate (scan_mfma_kernel<.., ADD>): the query's side of  S* >= B_q + G_c,  B_q = sum_r U0[r] v'_q[r] + sumq / 2 with
             // the list's reference U0 (U0[2] = 0), as the accumulator's start value C_q = -(B_q - margin) / 2 (the dot products come
@@ -1527,46 +1671,12 @@ __device__ __forceinline__ void stage_fill_item(const PairScalars *__restrict__ 
             // the bf16 form's (2 for the f32 rounding of the exact expression; qb 2^-13 covers, many times over, the f32 roundings
             // of B_q, of v' inside the list's V0 / DV and of the candidate's u' -- all relative 2^-22 of terms bounded by qb) with a
             // wider share for the matrix unit's own accumulation of C_q + s/2 (f32, magnitudes below qb + sumq).
-            const float4 u0 = list_uref[list_id];
-            float bq = u0.x * v[0];
-            bq += u0.y * v[1];
-            bq += u0.w * v[3];
-            bq += 0.5f * ps.sumq;
-            const float margin_a = 2.0f + qb * (1.0f / 8192.0f) + (qb + ps.sumq) * (1.0f / 65536.0f);
-            float cq = -0.5f * (bq - margin_a);
-            if (!safe || !(fabsf(cq) < 1.0e37f)) cq = __builtin_inff();  // always flagged: the exact path decides
+            const float cq = stage_gate_cq(g, ps.sumq, list_uref[list_id]);
             if (sub == 5) *cdst = cq;
             if (sub < 3) *reinterpret_cast<uint4 *>(tdst + 4 * sub) = make_uint4(t[4 * sub], t[4 * sub + 1], t[4 * sub + 2], t[4 * sub + 3]);
             return;
         }
-        const float v4 = -0.5f * (0.5f * ps.sumq - margin);
-        uint32_t vh[4], vl[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float x = -0.5f * v[i];
-            vh[i] = bf16_rne(x);
-            vl[i] = bf16_rne(x - bf16_to_f32(vh[i]));
-        }
-        uint32_t c0 = bf16_rne(v4);
-        const float r1 = v4 - bf16_to_f32(c0);
-        uint32_t c1 = bf16_rne(r1);
-        uint32_t c2 = bf16_rne(r1 - bf16_to_f32(c1));
-        if (!safe) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) vh[i] = 0, vl[i] = 0;
-            c0 = 0x7F80u, c1 = 0, c2 = 0;  // +inf * 1: -S* = +inf
-        }
-        // A operand of the threshold MFMA, element e of lane half h = slot 8h + e:
-        //   vh0 vh0 vl0 vh1 vh1 vl1 c0 c1 | vh2 vh2 vl2 vh3 vh3 vl3 c2 0     against the candidate side's
-        //   uh0 ul0 uh0 uh1 ul1 uh1  1  1 | uh2 ul2 uh2 uh3 ul3 uh3  1 0
-        t[RQ_REC_V0 + 0] = vh[0] | (vh[0] << 16);
-        t[RQ_REC_V0 + 1] = vl[0] | (vh[1] << 16);
-        t[RQ_REC_V0 + 2] = vh[1] | (vl[1] << 16);
-        t[RQ_REC_V0 + 3] = c0 | (c1 << 16);
-        t[RQ_REC_V0 + 4] = vh[2] | (vh[2] << 16);
-        t[RQ_REC_V0 + 5] = vl[2] | (vh[3] << 16);
-        t[RQ_REC_V0 + 6] = vh[3] | (vl[3] << 16);
-        t[RQ_REC_V0 + 7] = c2;
+        stage_gate_bf16(g, ps.sumq, t + RQ_REC_V0);
         // Dense run directory of a VALU stage: list position p of this pair lives in cell CELL0 + p / 64.  Cells follow
         // the stream: floor(stream_begin / 64) + 2 slot + 1 - floor(s_lo / 64) leaves every list its own cells (the two
         // spare cells per slot absorb the roundings of stream_begin and of the list's length) and never goes negative
@@ -1603,6 +1713,33 @@ __global__ __launch_bounds__(256) void stage_fill_kernel(const PairScalars *__re
                     recs, fs, tile_images, rank, blk_base, k, list_uref);
 }
 
+// block reduction of the per-thread min / max of v' (256 threads) and the list's V0 / DV
+__device__ __forceinline__ void vrange_reduce_store(float *lo, float *hi, uint32_t c, float4 *__restrict__ vref, float (*red)[8] /* LDS: [4][8] */) {
+    const float inf = __builtin_inff();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        for (int o = 32; o >= 1; o >>= 1) lo[r] = fminf(lo[r], __shfl_xor(lo[r], o, 64)), hi[r] = fmaxf(hi[r], __shfl_xor(hi[r], o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[threadIdx.x >> 6][r] = lo[r], red[threadIdx.x >> 6][4 + r] = hi[r];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float v0[4], dv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float l = fminf(fminf(red[0][r], red[1][r]), fminf(red[2][r], red[3][r]));
+            const float u = fmaxf(fmaxf(red[0][4 + r], red[1][4 + r]), fmaxf(red[2][4 + r], red[3][4 + r]));
+            const bool any = l <= u && u < inf && l > -inf;
+            v0[r] = any ? 0.5f * l + 0.5f * u : 0.0f;
+            // half-range, widened so that |v - v0| <= dv survives the roundings of v0 and of the subtraction
+            dv[r] = any ? fmaxf(u - v0[r], v0[r] - l) * 1.000001f : 0.0f;
+        }
+        vref[2 * c] = make_float4(v0[0], v0[1], v0[2], v0[3]);
+        vref[2 * c + 1] = make_float4(dv[0], dv[1], dv[2], dv[3]);
+    }
+}
 // Additive gate of the matrix-core scan: centre V0 and half-range DV of v'_q = ((thr - ycd), -1, -lower, sqrt(ycd)) / (2 delta)
 // over the pairs of a stage that probe list c (the records of group c, tile images of the additive format), written as
 // two float4 per list.  Pairs whose start value is +inf (always flagged: stage_fill_kernel) take no part.  One block per list.
@@ -1628,31 +1765,65 @@ __global__ __launch_bounds__(256) void group_vrange_kernel(const uint32_t *__res
         for (int r = 0; r < 4; ++r) lo[r] = fminf(lo[r], v[r]), hi[r] = fmaxf(hi[r], v[r]);
     }
     __shared__ float red[4][8];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        for (int o = 32; o >= 1; o >>= 1) lo[r] = fminf(lo[r], __shfl_xor(lo[r], o, 64)), hi[r] = fmaxf(hi[r], __shfl_xor(hi[r], o, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[threadIdx.x >> 6][r] = lo[r], red[threadIdx.x >> 6][4 + r] = hi[r];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float v0[4], dv[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float l = fminf(fminf(red[0][r], red[1][r]), fminf(red[2][r], red[3][r]));
-            const float u = fmaxf(fmaxf(red[0][4 + r], red[1][4 + r]), fmaxf(red[2][4 + r], red[3][4 + r]));
-            const bool any = l <= u && u < inf && l > -inf;
-            v0[r] = any ? 0.5f * l + 0.5f * u : 0.0f;
-            // half-range, widened so that |v - v0| <= dv survives the roundings of v0 and of the subtraction
-            dv[r] = any ? fmaxf(u - v0[r], v0[r] - l) * 1.000001f : 0.0f;
-        }
-        vref[2 * c] = make_float4(v0[0], v0[1], v0[2], v0[3]);
-        vref[2 * c + 1] = make_float4(dv[0], dv[1], dv[2], dv[3]);
-    }
+    vrange_reduce_store(lo, hi, c, vref, red);
 }
 
+// The final stage's tails when the quantisation has placed the operand rows and the threshold-free tail dwords already
+// (PrepPlace): one block per list walks the list's group in placement order, reads a row's tail and the query's threshold and
+// writes what depends on the threshold -- t[RQ_REC_THR] and, bf16 form, the operand at RQ_REC_V0; additive form, C_q, and the
+// list's V0 / DV on the way (group_vrange_kernel's result without its second read of the tails).  Operand rows are not touched.
+__global__ __launch_bounds__(256) void stage_tail_kernel(uint32_t *__restrict__ recs, const uint32_t *__restrict__ grp_start,
+                                                         const uint32_t *__restrict__ grp_cnt, const float *__restrict__ thr,
+                                                         uint32_t opdw, const FactorStats fs, uint32_t tile_images,
+                                                         const float4 *__restrict__ list_uref, float4 *__restrict__ vref) {
+    const uint32_t c = blockIdx.x, n = grp_cnt[c], st0 = grp_start[c];
+    const bool additive = tile_images == 2;
+    const uint32_t opld = rq_img_opld(opdw, additive), img = rq_img_dwords(opdw, additive);
+    const uint32_t taild = additive ? RQ_RECA_TAIL : RQ_REC_TAIL;
+    const float inf = __builtin_inff();
+    float lo[4] = {inf, inf, inf, inf}, hi[4] = {-inf, -inf, -inf, -inf};
+    float4 u0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (additive && n) u0 = list_uref[c];
+    for (uint32_t i = threadIdx.x; i < n; i += 256) {
+        const uint32_t at = st0 + i;
+        uint32_t *base = recs + (uint64_t)(at >> 5) * img + 32 * opld;
+        uint32_t *t = base + (at & 31u) * taild;
+        const uint4 t0 = *reinterpret_cast<const uint4 *>(t), t1 = *reinterpret_cast<const uint4 *>(t + 4);
+        const float lower = __builtin_bit_cast(float, t0.x), delta = __builtin_bit_cast(float, t0.y);
+        const float sumq = __builtin_bit_cast(float, t0.z), ycd = __builtin_bit_cast(float, t0.w);
+        const float ysq = __builtin_bit_cast(float, t1.x);
+        static_assert(RQ_REC_LOWER == 0 && RQ_REC_DELTA == 1 && RQ_REC_SUMQ == 2 && RQ_REC_YCD == 3 && RQ_REC_YCD_SQRT == 4 && RQ_REC_THR == 5,
+                      "the first six tail dwords");
+        const float th = thr[t[RQ_REC_ROW]];
+        t[RQ_REC_THR] = __builtin_bit_cast(uint32_t, th);
+        const StageGate g = stage_gate(lower, delta, sumq, ycd, ysq, th, fs);
+        if (additive) {
+            const float cq = stage_gate_cq(g, sumq, u0);
+            base[32 * RQ_RECA_TAIL + (at & 31u)] = __builtin_bit_cast(uint32_t, cq);
+            if (!(cq < inf)) continue;  // always flagged: takes no part in the list's range
+#pragma unroll
+            for (int r = 0; r < 4; ++r) lo[r] = fminf(lo[r], g.v[r]), hi[r] = fmaxf(hi[r], g.v[r]);
+        } else {
+            uint32_t t8[8];
+            stage_gate_bf16(g, sumq, t8);
+            *reinterpret_cast<uint4 *>(t + RQ_REC_V0) = make_uint4(t8[0], t8[1], t8[2], t8[3]);
+            *reinterpret_cast<uint4 *>(t + RQ_REC_V0 + 4) = make_uint4(t8[4], t8[5], t8[6], t8[7]);
+        }
+    }
+    __shared__ float red[4][8];
+    if (additive) vrange_reduce_store(lo, hi, c, vref, red);
+}
+
+// One launch for the words a pass wants zeroed before its first kernel (run_pass, option prep_placement)
+struct ClearSpans {
+    uint32_t *p[6];
+    uint32_t n[6];
+};
+__global__ __launch_bounds__(256) void clear_words_kernel(const ClearSpans cs) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+        for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < cs.n[j]; i += gridDim.x * 256) cs.p[j][i] = 0u;
+}
 
 // generic-W fallback (dim/64 not in the templated set): code words re-read per query (L1-resident).  FILT: the filtered form
 // (scan_generic_filtered_kernel; a.x holds the filter's position bitmap)

@@ -828,6 +828,11 @@ rq_status rq_set_option(const char *name, int value) {
         g_group_rank = value;
         return RQ_OK;
     }
+    if (std::string(name) == "prep_placement") {  // 1 (default) = final matrix-core stage planned before the query quantisation, operand rows written in place; 0 = the older kernels everywhere (results identical)
+        if (value < 0 || value > 1) return fail(RQ_ERR_INVALID, "prep_placement must be 0 or 1");
+        g_prep_placement = value;
+        return RQ_OK;
+    }
     if (std::string(name) == "rerank_shadow") {  // fp16 shadow rows (rerank pre-filter) for indexes built / loaded from now on
         if (value < 0 || value > 2) return fail(RQ_ERR_INVALID, "rerank_shadow must be 0 (never), 1 (fp16 rows when they fit) or 2 (8-bit rows when they fit)");
         g_rerank_shadow = value;
