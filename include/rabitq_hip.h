@@ -79,7 +79,7 @@ typedef struct {
  * "coarse_tiled_from", "rerank_shadow" = 2 -- the new default; 0.5.0: option "split_rows", rq_info_t.split_rows appended, RQ_ARR_BASE
  * refused for split rows as for tiers; 0.6.0: filtered queries -- rq_filter_* and rq_query_batch*_filtered, additions only;
  * 0.7.0: in-place mutation -- rq_add / rq_remove / rq_last_mutate_stats, additions only; a filter made before a mutation of its
- * index is refused).
+ * index is refused; later in 0.7, additions only: range search -- rq_range_search* and rq_range_result_*).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -233,6 +233,43 @@ rq_status rq_query_batch_filtered(const rq_index *idx, const rq_filter *filter, 
 rq_status rq_query_batch_device_filtered(const rq_index *idx, const rq_filter *filter, const float *d_queries,
                                          uint32_t nq, uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank,
                                          float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n);
+
+/* ---- range search: every neighbour within a per-query radius ----------------------------------------------------- */
+/* For query b with radius r_b (f32, squared L2 like every distance of this header), its probe lists as the plain query ranks
+ * them, and every stored row u of those lists, the answer is the SET
+ *     { (accurate(b,u), id(u)) : rough(b,u) < r_b  and  accurate(b,u) < r_b }
+ * with the plain query's own estimate (src/rabitq.rs:336-367) and exact distance (src/simd.rs:14-73), bit for bit: the
+ * reference's ranker (src/rerank.rs:83-92) with its threshold held at r_b and no bound on the number kept.  Both comparisons are
+ * strict f32 "<": a NaN radius admits nothing, r_b <= 0 returns nothing, f32::MAX returns every probed row whose two distances
+ * are finite and below it.  A row whose ESTIMATE is not below r_b is left out even if its exact distance is: that is the
+ * reference's gate and the documented approximation of this call (as of rq_query_batch_device_seeded).  Each query's results
+ * are ascending by (distance, id).  Counters: rough += rows of the probed lists (with a filter: the admitted ones), precise +=
+ * candidates with rough < r_b (admitted ones), query += nq.  An empty answer is RQ_OK with all counts 0.
+ * filter: NULL = none; else the same set intersected with the admitted rows (a filter of another index or made before a
+ * mutation: RQ_ERR_INVALID).  Validation otherwise as rq_query_batch_device without topk.  Any index the plain query accepts
+ * is accepted (tiered, split rows, shards of rq_shard_index: ids are the original ones, a caller unites the shards' answers).
+ * The library sizes the result itself -- hit counts, prefix sum, one allocation of exactly `total` entries per array; no
+ * result length is bounded by anything but memory (RQ_ERR_OOM when it does not fit; the index is untouched).  On any error
+ * *out is NULL.  Safe to call concurrently with other queries on the index.  rq_last_profile() is filled as by the other
+ * query calls, re-runs included: retries = queries whose candidates exceeded the pass's uniform buffers and were run again on
+ * their own; scan_candidates, scan_launches and the ms_* fields then hold the re-runs' scans as well (the rough counter does not:
+ * it counts a probed row once); ms_sort also holds everything behind the hit counts (offsets, emission, sort, split).
+ * A range call leaves no trace in how later top-k calls on the index run (their learnt buffer sizes and scan gate).
+ * rq_range_search_device: queries (nq x len) and radii (nq) in device memory; rq_range_search: both in host memory.
+ * The result owns three DEVICE arrays, valid until it is freed: lims, nq + 1 u64 (lims[0] = 0, lims[nq] = total), and dist /
+ * id, `total` entries each; query b's results are entries [lims[b], lims[b + 1]).  rq_range_result_copy copies them to host
+ * arrays of those sizes (dist / id may be NULL when total == 0).  Free the result before its index;
+ * rq_range_result_free(NULL) is a no-op. */
+typedef struct rq_range_result rq_range_result;
+rq_status rq_range_search_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq,
+                                 uint32_t len, uint32_t probe, const float *d_radius, rq_range_result **out);
+rq_status rq_range_search(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len,
+                          uint32_t probe, const float *radius, rq_range_result **out);
+rq_status rq_range_result_info(const rq_range_result *r, uint32_t *out_nq, uint64_t *out_total);
+rq_status rq_range_result_device_ptrs(const rq_range_result *r, const uint64_t **d_lims, const float **d_dist,
+                                      const uint32_t **d_id);
+rq_status rq_range_result_copy(const rq_range_result *r, uint64_t *lims, float *dist, uint32_t *id);
+void rq_range_result_free(rq_range_result *r);
 
 /* ---- in-place mutation: add and remove rows ------------------------------------------------------------------------ */
 /* After any sequence of rq_add / rq_remove the index equals, bit for bit, the index rq_build produces from its live rows S in

@@ -4,9 +4,9 @@ Host-side mirror of the crate's public surface (`pub use rabitq::RaBitQ`, src/li
 C ABI in include/rabitq_hip.h.  All arithmetic runs in hand-written HIP kernels
 (rabitq_amd/csrc); there is no CPU fallback.
 """
-from .index import RaBitQ, Filter, pack_filter_bits, metrics, metrics_reset, metrics_str, calculate_recall  # noqa: F401
+from .index import RaBitQ, Filter, RangeResult, pack_filter_bits, metrics, metrics_reset, metrics_str, calculate_recall  # noqa: F401
 from . import ops, vecs  # noqa: F401
 from ._lib import RabitqError, build  # noqa: F401
 
-__all__ = ["RaBitQ", "Filter", "pack_filter_bits", "metrics", "metrics_reset", "metrics_str", "calculate_recall", "ops", "vecs", "RabitqError",
+__all__ = ["RaBitQ", "Filter", "RangeResult", "pack_filter_bits", "metrics", "metrics_reset", "metrics_str", "calculate_recall", "ops", "vecs", "RabitqError",
            "build"]

@@ -20,6 +20,10 @@ struct QueryParams {
     // are settled before the quantisation, and the rough counter counts admitted rows.  Every pass of the call carries it (overlapped
     // passes, overflow re-runs, arena repeats).
     const rq_filter *filter = nullptr;
+    // Range pass (host_range.h): thr_init holds the radii, the whole stream runs as ONE stage under them (re-runs too: a fixed
+    // threshold has nothing to learn), and behind the exact distances the pass only counts each query's hits (ws.range_hits) --
+    // no run ordering, no replay, no result rows; topk is 1 (the ranker state is allocated, not used).
+    bool range = false;
 };
 
 #define RQ_DEFAULT_CAP 4096u
@@ -92,11 +96,13 @@ static rq_status finish_pass(const rq_index *idx, Workspace &ws, PassResult *res
     res->precise = ws.h_totals[1];
     res->overflowed = ws.h_totals[2];
     res->max_need = ws.h_totals[4];
-    if (rq_large_batch(nq)) hints_of(idx, ws.pend_filter).big_dirs.store((uint32_t)ws.h_totals[7]);
+    if (rq_large_batch(nq) && !ws.pend_range) hints_of(idx, ws.pend_filter).big_dirs.store((uint32_t)ws.h_totals[7]);
     // The additive gate is a looser test than the rank-5 threshold it replaces: an index / workload on which it sends more than
     // 3 % of the sub-tile steps down the exact path (each costs ~10 plain steps) goes back to the bf16 threshold MFMA for good
     // (results do not depend on the choice; option scan_gate pins it)
-    if (ws.pend_additive && ws.h_totals[8] >= 4096 && ws.h_totals[9] * 32 > ws.h_totals[8])
+    // (a range pass does not feed the decision: its one stage covers the nearest list too and its radii may admit everything, which
+    // says nothing about the final stages of the top-k passes the flag steers)
+    if (ws.pend_additive && !ws.pend_range && ws.h_totals[8] >= 4096 && ws.h_totals[9] * 32 > ws.h_totals[8])
         const_cast<rq_index *>(idx)->additive_loose.store(1);
     if (prof_acc) prof_acc->matrix_subtile_steps += ws.h_totals[8], prof_acc->matrix_exact_steps += ws.h_totals[9];
     if (prof_acc) prof_acc->coarse_fallback_rows += (uint32_t)std::min<unsigned long long>(ws.h_totals[10], 0xFFFFFFFFull);
@@ -165,6 +171,7 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
     uint32_t nlive = 0;
     const rq_filter *filt = qp.filter;
     ws.pend_filter = filt;
+    ws.pend_range = qp.range;
     // shortest list of the pass: a filtered pass settles the pairs whose list admits nothing as empty ones, so no slot bound can be
     // derived from stream positions (as on a shard)
     const uint32_t min_len = filt ? 0u : idx->min_list_len;
@@ -226,7 +233,7 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
     const uint32_t *probe_cluster = ws.probe_cluster.p;
     const float *probe_dist = ws.probe_dist.p;
     const uint32_t *rerank_order = nullptr;
-    const bool one_stage = qp.thr_init != nullptr && d_row_map == nullptr;  // thresholds are already tight: nothing to learn in early stages
+    const bool one_stage = qp.range || (qp.thr_init != nullptr && d_row_map == nullptr);  // thresholds are already tight: nothing to learn in early stages
     // matrix cores pay once many queries share each list AND survivors are rare, i.e. past the nearest list
     // (stages inside it leave hundreds of survivors per query: the exact path dominates there and the VALU
     // kernel wins, measured at any batch size)
@@ -759,7 +766,7 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
         // small batch: one fused launch per stage (launch-bound regime) -- unless the survivor buffers are large (queries
         // re-run after an overflow: tens of thousands of survivors each): one block per query would rerank and order
         // those alone, the large-batch kernels spread them over the chip
-        if (!rq_large_batch(nq) && qp.cap <= 4 * RQ_DEFAULT_CAP) {
+        if (!qp.range && !rq_large_batch(nq) && qp.cap <= 4 * RQ_DEFAULT_CAP) {
             pf.begin(PF_RERANK);
             const uint32_t fin_threads = nq <= 16 ? 1024u : 256u;  // a handful of queries: more lanes on each one's rerank
             // survivor buffers beyond the default mean this index / these queries leave long run directories (overflow
@@ -816,7 +823,11 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
             else
                 accurate_kernel<<<dim3(gx, nq), 256, (size_t)dim * sizeof(float), st>>>(ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim,
                                                                                         rerank_order, probe_cluster, nprobe);
+            if (qp.range)  // every survivor has its exact distance (or +inf: proven outside the radius): count the hits, nothing to order
+                range_count_kernel<<<ceil_div(nq, 4), 256, 0, st>>>(ws.surv.p, ws.surv_cnt.p, qp.cap, ws.thr.p, nq, ws.range_hits.p, ws.need.p,
+                                                                    ws.ovf.p, ws.precise.p, ws.nsurv.p);
             pf.end();
+            if (qp.range) continue;
             if (!dense_cells) {
                 pf.begin(PF_SORT);
                 sort_runs_kernel<<<nq, 64, 0, st>>>(ws.runs.p, ws.surv_cnt.p, seg, ws.big_list.p, ws.big_list.p + nq, 512u,
@@ -843,7 +854,9 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
     if (sb_results_done) {
         // written by sb_query_kernel / sb_finish_kernel together with the totals
     } else {
-    if (qp.heuristic) {
+    if (qp.range) {
+        // (the hits stay in the survivor buffers: the caller sizes the result from their counts and emits their keys)
+    } else if (qp.heuristic) {
         sort_survivors_kernel<<<nq, 256, 0, st>>>(ws.arr.p, ws.arr_len.p, qp.hcap);
         finalize_heuristic_kernel<<<ceil_div((uint64_t)nq * topk, 256), 256, 0, st>>>(rs, nq, topk, d_row_map, idx->map_ids.p,
                                                                                        d_out_dist, d_out_id, d_out_n);

@@ -57,6 +57,11 @@ struct DevBuf {
         return RQ_OK;
     }
     rq_status ensure(size_t n) { return n <= count && p ? RQ_OK : alloc(n); }
+    void take(DevBuf &o) {  // this buffer becomes o's allocation (o is left empty)
+        release();
+        p = o.p, count = o.count;
+        o.p = nullptr, o.count = 0;
+    }
 };
 
 // Sized out-structs (include/rabitq_hip.h): write at most the bytes the caller's struct has.
@@ -212,6 +217,10 @@ struct Workspace {
     DevBuf<float> sh_dist;
     DevBuf<uint32_t> sh_id, sh_n;
     DevBuf<unsigned long long> sh_packed, sh_gathered, sh_merged;
+    DevBuf<uint32_t> range_hits;               // range passes (host_range.h): per query, the candidates inside its radius
+    DevBuf<uint32_t> range_lists;              //   the segmented sort's three segment lists (by length class) ...
+    DevBuf<unsigned long long> range_counters; //   ... and their lengths + the longest segment
+    bool pend_range = false;                   // the pending pass is a range pass (it orders no run directories: the long-directory hint keeps its value)
     DevBuf<uint32_t> ovf, q_cap;               // per query: overflow flag; segment capacity of the final stage (segmented passes)
     DevBuf<unsigned long long> q_base;         // per query: first slot of its segment
     DevBuf<SurvRec> arena_recs;                // arena stages: survivors of all queries, unordered (256 shards)
@@ -267,6 +276,7 @@ struct rq_index {
     std::atomic<uint32_t> cap_hint{0};  // survivor-buffer capacity learnt from earlier batches
     std::atomic<uint64_t> arena_hint{0};  // slots the largest arena stage of earlier batches needed (+ headroom)
     std::atomic<uint32_t> big_dirs_hint{0};  // most long run directories (> 512 runs) a stage of a recent pass produced
+    std::atomic<uint32_t> range_cap_hint{0};  // survivor-buffer capacity learnt from range passes most of whose queries overflowed (host_range.h)
     uint64_t pass_budget = 24ull << 30;  // bytes of survivor / run buffers one query pass may use (set by finish_index)
     // tile tables of the cluster-major scans: per tile size, one {list, first, list begin, list length} entry per
     // existing (list, tile); built on first use from the host copy of the offsets
@@ -749,6 +759,8 @@ static rq_status ensure_kernel_attributes() {
         set(reinterpret_cast<const void *>(group_rank_kernel), 32768 * 4, "group_rank_kernel");
         set(reinterpret_cast<const void *>(sb_front_kernel), 140 * 1024, "sb_front_kernel");
         set(reinterpret_cast<const void *>(sort_runs_mid_kernel), RQ_SORT_MID_LDS_WORDS * 8, "sort_runs_mid_kernel");  // (+ 34 KiB of static LDS)
+        set(reinterpret_cast<const void *>(range_sort_block_kernel<1024, RQ_RANGE_TILE>), RQ_RANGE_TILE * 8, "range_sort_block_kernel");
+        set(reinterpret_cast<const void *>(range_sort_tile_kernel), RQ_RANGE_TILE * 8, "range_sort_tile_kernel");
         set(reinterpret_cast<const void *>(assign_approx_kernel<6, 1>), (int)assign_lds_bytes<6, 1>(), "assign_approx_kernel<6,1>");
         set(reinterpret_cast<const void *>(assign_approx_kernel<8, 1>), (int)assign_lds_bytes<8, 1>(), "assign_approx_kernel<8,1>");
         set(reinterpret_cast<const void *>(assign_approx_kernel<12, 1>), (int)assign_lds_bytes<12, 1>(), "assign_approx_kernel<12,1>");

@@ -30,10 +30,12 @@
 #include "common.h"
 #include "kernels_build.h"
 #include "kernels_query.h"
+#include "kernels_range.h"
 #include "kernels_small.h"
 
 #include "host_state.h"
 #include "host_query.h"
+#include "host_range.h"
 #include "host_build.h"
 #include "host_mutate.h"
 
@@ -626,6 +628,47 @@ rq_status rq_query_batch_filtered(const rq_index *idx, const rq_filter *filter, 
                                   uint32_t *out_n) {
     return query_batch_host(idx, filter, queries, nq, len, probe, topk, heuristic_rank, out_dist, out_id, out_n);
 }
+
+// ---- range search: every neighbour inside a per-query radius, as a result object sized by the library (host_range.h) ----
+rq_status rq_range_search_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
+                                 uint32_t probe, const float *d_radius, rq_range_result **out) {
+    return range_device(const_cast<rq_index *>(idx), filter, d_queries, nq, len, probe, d_radius, out);
+}
+rq_status rq_range_search(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len,
+                          uint32_t probe, const float *radius, rq_range_result **out) {
+    if (!out) return fail(RQ_ERR_INVALID, "null argument");
+    *out = nullptr;
+    RQC(ensure_device());
+    if (!idx || (nq && (!queries || !radius))) return fail(RQ_ERR_INVALID, "null argument");
+    void *dq = nullptr, *dr = nullptr;
+    if (nq) {
+        RQC(g_staging.get(0, (uint64_t)nq * len * 4, &dq));
+        RQC(g_staging.get(3, (uint64_t)nq * 4, &dr));
+        HIPC(hipMemcpy(dq, queries, (uint64_t)nq * len * 4, hipMemcpyHostToDevice));
+        HIPC(hipMemcpy(dr, radius, (uint64_t)nq * 4, hipMemcpyHostToDevice));
+    }
+    return range_device(const_cast<rq_index *>(idx), filter, (const float *)dq, nq, len, probe, (const float *)dr, out);
+}
+rq_status rq_range_result_info(const rq_range_result *r, uint32_t *out_nq, uint64_t *out_total) {
+    if (!r || !out_nq || !out_total) return fail(RQ_ERR_INVALID, "null argument");
+    *out_nq = r->nq, *out_total = r->total;
+    return RQ_OK;
+}
+rq_status rq_range_result_device_ptrs(const rq_range_result *r, const uint64_t **d_lims, const float **d_dist, const uint32_t **d_id) {
+    if (!r || !d_lims || !d_dist || !d_id) return fail(RQ_ERR_INVALID, "null argument");
+    *d_lims = reinterpret_cast<const uint64_t *>(r->lims.p), *d_dist = r->dist.p, *d_id = r->id.p;
+    return RQ_OK;
+}
+rq_status rq_range_result_copy(const rq_range_result *r, uint64_t *lims, float *dist, uint32_t *id) {
+    if (!r || !lims || (r->total && (!dist || !id))) return fail(RQ_ERR_INVALID, "null argument");
+    HIPC(hipMemcpy(lims, r->lims.p, ((size_t)r->nq + 1) * 8, hipMemcpyDeviceToHost));
+    if (r->total) {
+        HIPC(hipMemcpy(dist, r->dist.p, (size_t)r->total * 4, hipMemcpyDeviceToHost));
+        HIPC(hipMemcpy(id, r->id.p, (size_t)r->total * 4, hipMemcpyDeviceToHost));
+    }
+    return RQ_OK;
+}
+void rq_range_result_free(rq_range_result *r) { delete r; }
 
 // ---- filters: the allow-list in the index's terms (position bitmap + admitted rows per list), made once ----
 rq_status rq_filter_create(const rq_index *idx, const uint32_t *allow_bits, uint64_t nbits, int bits_on_device, rq_filter **out) {

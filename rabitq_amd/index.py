@@ -85,6 +85,50 @@ def _fh(filter):
     return filter._h if filter is not None else None
 
 
+class RangeResult:
+    """The answer of a range search (rq_range_search*), owned by the library and resident on the device: `nq` queries, `total`
+    (distance, id) entries, query b's at [lims[b], lims[b + 1]) ascending by (distance, id).  Holds a reference to its index, so
+    the index outlives it; close() (or the context manager) frees the device arrays."""
+
+    def __init__(self, index: "RaBitQ", handle):
+        self.index = index
+        self._h = handle
+        nq, total = C.c_uint32(), C.c_uint64()
+        check(lib().rq_range_result_info(self._h, C.byref(nq), C.byref(total)))
+        self.nq, self.total = int(nq.value), int(total.value)
+
+    def device_ptrs(self):
+        """-> (lims, dist, ids) raw device addresses: nq + 1 u64, total f32, total u32; valid until close()."""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().rq_range_result_device_ptrs(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value or 0, b.value or 0, c.value or 0
+
+    def to_host(self):
+        """-> (lims u64[nq + 1], dist f32[total], ids u32[total]) as numpy arrays."""
+        lims = np.empty(self.nq + 1, dtype=np.uint64)
+        dist = np.empty(self.total, dtype=np.float32)
+        ids = np.empty(self.total, dtype=np.uint32)
+        check(lib().rq_range_result_copy(self._h, _addr(lims), _addr(dist), _addr(ids)))
+        return lims, dist, ids
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().rq_range_result_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class RaBitQ:
     """Device-resident RaBitQ index.  Construct with `from_path`, `build`, `load_from_dir` or
     `from_arrays`; query with `query` (one vector, like the crate) or `query_batch`."""
@@ -351,6 +395,31 @@ class RaBitQ:
             check(lib().rq_query_batch_device_filtered(self._h, _fh(filter), C.c_void_p(q_ptr), nq, length, probe, topk,
                                                        int(heuristic_rank), C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr),
                                                        C.c_void_p(out_n_ptr)))
+
+    # ---- range search: every neighbour within a per-query radius --------------------------------
+    def range_search(self, queries, probe: int, radius, filter: Filter = None):
+        """B queries -> (lims u64[B + 1], dist f32[total], ids u32[total]): query b's neighbours with estimate and exact squared
+        distance both strictly below radius[b] (a scalar = the same radius for every query), among the rows of its `probe` nearest
+        lists, at [lims[b], lims[b + 1]) ascending by (distance, id).  filter: only its rows can be returned."""
+        q = _f32(queries)
+        if q.ndim != 2:
+            raise _lib.RabitqError(-1, "queries must be 2-D")
+        r = np.asarray(radius, dtype=np.float32)
+        r = np.full(q.shape[0], r, dtype=np.float32) if r.ndim == 0 else np.ascontiguousarray(r.reshape(-1))
+        if r.size != q.shape[0]:
+            raise _lib.RabitqError(-1, f"radius must be a scalar or one value per query ({q.shape[0]}), not {r.size}")
+        h = C.c_void_p()
+        check(lib().rq_range_search(self._h, _fh(filter), _addr(q), q.shape[0], q.shape[1], probe, _addr(r), C.byref(h)))
+        with RangeResult(self, h) as res:
+            return res.to_host()
+
+    def range_search_device(self, q_ptr: int, nq: int, length: int, probe: int, radius_ptr: int, filter: Filter = None) -> RangeResult:
+        """Queries (nq x length) and radii (nq f32) already in device memory (raw addresses) -> a RangeResult whose arrays stay
+        on the device."""
+        h = C.c_void_p()
+        check(lib().rq_range_search_device(self._h, _fh(filter), C.c_void_p(q_ptr), nq, length, probe, C.c_void_p(radius_ptr),
+                                           C.byref(h)))
+        return RangeResult(self, h)
 
     def query_batch_device_begin(self, q_ptr: int, nq: int, length: int, probe: int, topk: int, out_dist_ptr: int,
                                  out_id_ptr: int, out_n_ptr: int, heuristic_rank: bool = False):
