@@ -55,6 +55,8 @@ def lib():
         sz = C.c_size_t
         L.rqo_l2_squared_distance.restype = C.c_float
         L.rqo_l2_squared_distance.argtypes = [_f32p, _f32p, sz]
+        L.rqo_l2_squared_distance_rows.restype = None
+        L.rqo_l2_squared_distance_rows.argtypes = [_f32p, _f32p, _u64p, sz, sz, _f32p]
         L.rqo_vector_dot_product.restype = C.c_float
         L.rqo_vector_dot_product.argtypes = [_f32p, _f32p, sz]
         L.rqo_min_max_residual.restype = None
@@ -123,6 +125,19 @@ def _f32(a):
 def l2_squared_distance(a, b) -> float:
     a, b = _f32(a), _f32(b)
     return float(lib().rqo_l2_squared_distance(_p(a, _f32p), _p(b, _f32p), a.size))
+
+
+def l2_squared_distance_rows(query, base, positions) -> np.ndarray:
+    """f32[m]: the squared distance of `query` to the rows `positions` of the row-major matrix `base` (contiguous f32; the
+    query as long as a row), each through rqo_l2_squared_distance."""
+    assert base.dtype == np.float32 and base.flags.c_contiguous and base.ndim == 2
+    query = _f32(query)
+    assert query.size == base.shape[1]
+    pos = np.ascontiguousarray(positions, dtype=np.uint64)
+    assert pos.size == 0 or int(pos.max()) < base.shape[0]
+    out = np.empty(pos.size, dtype=np.float32)
+    lib().rqo_l2_squared_distance_rows(_p(query, _f32p), _p(base, _f32p), _p(pos, _u64p), pos.size, base.shape[1], _p(out, _f32p))
+    return out
 
 
 def vector_dot_product(a, b) -> float:

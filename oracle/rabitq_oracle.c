@@ -56,6 +56,12 @@ float rqo_l2_squared_distance(const float *lhs, const float *rhs, size_t n) {
     return res;
 }
 
+/* Test-model helper, no counterpart in the reference: out[i] = rqo_l2_squared_distance(query, base + pos[i] * n, n) for m rows
+ * of a row-major matrix -- one call per query instead of one per candidate.  The single-pair entry does the arithmetic. */
+void rqo_l2_squared_distance_rows(const float *query, const float *base, const uint64_t *pos, size_t m, size_t n, float *out) {
+    for (size_t i = 0; i < m; ++i) out[i] = rqo_l2_squared_distance(query, base + (size_t)pos[i] * n, n);
+}
+
 /* simd.rs:257-314.  Same structure with acc = fma(x, y, acc). */
 float rqo_vector_dot_product(const float *lhs, const float *rhs, size_t n) {
     __m256 acc = _mm256_setzero_ps();

@@ -34,6 +34,8 @@ extern "C" {
 
 /* ---- src/simd.rs kernels (AVX2/FMA restatements, same lane and reduction order) ---- */
 float rqo_l2_squared_distance(const float *lhs, const float *rhs, size_t n);      /* simd.rs:14-73   */
+void rqo_l2_squared_distance_rows(const float *query, const float *base, const uint64_t *pos, size_t m, size_t n,
+                                  float *out);   /* rows x one query through the entry above (test models) */
 float rqo_vector_dot_product(const float *lhs, const float *rhs, size_t n);       /* simd.rs:257-314 */
 void rqo_min_max_residual(float *res, const float *x, const float *y, size_t n,
                           float *out_min, float *out_max);                        /* simd.rs:117-173 */

@@ -31,7 +31,7 @@ KINDS = ["gauss", "gauss", "sift_u8", "sparse", "student_t", "tight", "near_ties
 SCALES = [1e-3, 1.0, 1.0, 40.0, 1e3, 3e4]
 KNOB_DEFAULTS = {"base_device_mb": -1, "max_scan_blocks": 0, "scan_tile_table": 1, "group_rank": 1, "rerank_shadow": 2,
                  "coarse_impl": 0, "dense_dir": 1, "small_batch": 0, "scan_impl": 0, "small_batch_span": 2560, "stage_growth": 0,
-                 "survivor_segments": 1, "scan_gate": 0, "split_rows": 1}
+                 "survivor_segments": 1, "scan_gate": 0, "split_rows": 1, "prep_placement": 1, "pair_split": 1, "assign_impl": 0}
 
 
 def make_case(rng, it, nmax):
@@ -88,14 +88,10 @@ def make_case(rng, it, nmax):
     return x, centres, P, queries, dict(n=n, d=d, k=k, nq=nq, kind=kind, scale=scale, queries=qkind)
 
 
-def fuzz_round(rq, oracle, rng, it, nmax=12000):
-    """One round: build both indexes, compare two (probe, topk, ranker) configurations.  Returns the description and, for
-    forced matrix-core rounds, (sub-tile steps, exact-path steps) of the integer gate."""
-    from rabitq_amd import index as ix
-    from tests.test_gpu_parity import _compare_with_oracle
-    x, centres, P, queries, desc = make_case(rng, it, nmax)
-    oidx = oracle.OracleIndex.build(x, centres, P)
-    # engine knobs that must never change a result
+def draw_knobs(rng, it):
+    """Engine knobs that must never change a result.  The first fourteen come from the round's generator, draw for draw as they
+    always did; the later ones (prep_placement, pair_split, assign_impl) from a child generator seeded by the round number alone,
+    so that the cases and configurations of rounds recorded before they existed stay what they were."""
     knobs = {"base_device_mb": int(rng.choice([-1, -1, 0, 1])), "max_scan_blocks": int(rng.choice([0, 0, 3, 40])),
              "scan_tile_table": int(rng.choice([0, 1, 2])), "group_rank": int(rng.choice([0, 1, 2])),
              "rerank_shadow": int(rng.choice([0, 1, 2, 2])), "coarse_impl": int(rng.choice([0, 1, 2, 3, 4])),
@@ -103,6 +99,19 @@ def fuzz_round(rq, oracle, rng, it, nmax=12000):
              "small_batch_span": int(rng.choice([100, 2560, 2560, 65536])), "stage_growth": int(rng.choice([0, 0, 2, 16])),
              "scan_impl": int(rng.choice([0, 1, 2])), "survivor_segments": int(rng.choice([1, 1, 2])),
              "scan_gate": int(rng.choice([0, 1, 2])), "split_rows": int(rng.choice([0, 1, 1, 2, 2]))}
+    child = np.random.default_rng([0xFEA7, it])
+    knobs.update(prep_placement=int(child.choice([0, 1])), pair_split=int(child.choice([0, 1])), assign_impl=int(child.choice([0, 1])))
+    return knobs
+
+
+def fuzz_round(rq, oracle, rng, it, nmax=12000):
+    """One round: build both indexes, compare two (probe, topk, ranker) configurations.  Returns the description and, for
+    forced matrix-core rounds, (sub-tile steps, exact-path steps) of the integer gate."""
+    from rabitq_amd import index as ix
+    from tests.models import compare_with_oracle as _compare_with_oracle
+    x, centres, P, queries, desc = make_case(rng, it, nmax)
+    oidx = oracle.OracleIndex.build(x, centres, P)
+    knobs = draw_knobs(rng, it)
     gate = None
     try:
         for name, v in knobs.items():

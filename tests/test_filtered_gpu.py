@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from tests import synth
+from tests.models import bits, sub_arrays
 
 pytestmark = pytest.mark.gpu
 
@@ -27,22 +28,6 @@ def rq():
     assert os.path.exists(_lib.SO_PATH), "librabitq_hip.so must be built in-tree"
     _lib.check(_lib.lib().rq_init(0))
     return rabitq_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def sub_arrays(g, allowed):
-    """The reference arrays of the sub-index: every list keeps its admitted rows (allowed: bool mask over ids) in stored order."""
-    offs, mids = g.offsets.astype(np.int64), g.map_ids
-    keep = np.zeros(mids.size, dtype=bool)
-    inr = mids < allowed.size
-    keep[inr] = allowed[mids[inr]]
-    lists = np.repeat(np.arange(g.k), np.diff(offs))
-    new_off = np.zeros(g.k + 1, dtype=np.uint32)
-    new_off[1:] = np.cumsum(np.bincount(lists[keep], minlength=g.k))
-    return g.base[keep], g.orthogonal, g.centroids, new_off, mids[keep], g.codes[keep], g.factors[keep]
 
 
 def check_same(rq, gidx, filt, sidx, queries, probe, topk, heur, what=""):

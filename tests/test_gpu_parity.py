@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import synth
+from tests.models import bits, compare_with_oracle as _compare_with_oracle
 
 pytestmark = pytest.mark.gpu
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz")))
@@ -20,10 +21,6 @@ IDS = [os.path.basename(p)[:-4] for p in GOLDEN]
 # scan implementation x gate of the matrix-core scan: VALU (v_dot8), matrix cores with the bf16 rank-5 threshold MFMA, matrix cores
 # with the additive bound (dim 64 / 128; elsewhere the option leaves the bf16 form in place)
 SCAN_VARIANTS = [(1, 0), (2, 1), (2, 2)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
 
 
 def assert_bits_equal(a, b, what=""):
@@ -362,24 +359,6 @@ def test_prefiltered_coarse_ranking_equals_exact_order_kernels(rq, d, k, nq, pro
     finally:
         ix.set_option("coarse_impl", 0)
     idx.close()
-
-
-def _compare_with_oracle(rq, oracle, oidx, gidx, queries, probe, topk, heur):
-    rq.metrics_reset()
-    d, ids, cnt = gidx.query_batch(queries, probe, topk, heur)
-    tot_r = tot_p = 0
-    for qi, q in enumerate(queries):
-        oracle.metrics_reset()
-        od, oi = oidx.query(q, probe, topk, heur)
-        m = oracle.metrics()
-        tot_r += m["rough"]
-        tot_p += m["precise"]
-        n = int(cnt[qi])
-        assert n == oi.size, (qi, n, oi.size)
-        assert np.array_equal(ids[qi, :n], oi), (qi, ids[qi, :n], oi)
-        assert np.array_equal(bits(d[qi, :n]), bits(od)), qi
-    m = rq.metrics()
-    assert (m["rough"], m["precise"], m["query"]) == (tot_r, tot_p, len(queries))
 
 
 @pytest.mark.parametrize("n,d,k", [(3000, 64, 9), (200_000, 128, 64), (60_000, 128, 700), (9000, 256, 20), (40_000, 512, 16),

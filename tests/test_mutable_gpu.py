@@ -12,10 +12,10 @@ import numpy as np
 import pytest
 
 from tests import synth
+from tests.models import ARRAYS, Live, bits, check_oracle, sub_arrays
 
 pytestmark = pytest.mark.gpu
 
-ARRAYS = ("base", "orthogonal", "centroids", "offsets", "codes", "factors")
 
 
 @pytest.fixture(scope="module")
@@ -25,32 +25,6 @@ def rq():
     assert os.path.exists(_lib.SO_PATH), "librabitq_hip.so must be built in-tree"
     _lib.check(_lib.lib().rq_init(0))
     return rabitq_amd
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-class Live:
-    """The live rows S of a mutated index, kept on the host: id -> row."""
-
-    def __init__(self, ids, rows):
-        self.rows = {int(i): r for i, r in zip(ids, rows)}
-
-    def add(self, ids, rows):
-        for i, r in zip(ids, rows):
-            assert int(i) not in self.rows
-            self.rows[int(i)] = r
-
-    def remove(self, ids):
-        for i in ids:
-            self.rows.pop(int(i), None)
-
-    def sorted(self):
-        ids = np.array(sorted(self.rows), dtype=np.uint32)
-        d = len(next(iter(self.rows.values()))) if self.rows else 0
-        rows = np.array([self.rows[int(i)] for i in ids], dtype=np.float32).reshape(len(ids), d)
-        return ids, rows
 
 
 def canonical(rq, live, centres, P):
@@ -104,19 +78,6 @@ def assert_same_queries(rq, g, c, ids, queries, probes, topk=10, what=""):
     for qi in range(nq):
         n = int(na[qi])
         assert np.array_equal(ia[qi, :n], ids[ib[qi, :n]]) and np.array_equal(bits(da[qi, :n]), bits(db[qi, :n])), (what, qi)
-
-
-def check_oracle(oracle, g, live, centres, P, what=""):
-    """The same contract against the CPU oracle's build (oracle.rqo_build) of S in id order, map_ids translated."""
-    ids, rows = live.sorted()
-    o = oracle.OracleIndex.build(rows, centres, P)
-    try:
-        assert (g.n, g.k) == (o.n, o.k), what
-        for name in ARRAYS:
-            assert np.array_equal(bits(getattr(g, name)), bits(getattr(o, name))), (what, "oracle", name)
-        assert np.array_equal(g.map_ids, ids[o.map_ids]), (what, "oracle", "map_ids")
-    finally:
-        o.close()
 
 
 def check(rq, g, live, centres, P, queries, probes, what=""):
@@ -195,16 +156,6 @@ def test_keys_and_ties(rq, oracle):
     queries = (centres[rng.integers(0, k, 64)] + 0.5 * rng.standard_normal((64, d))).astype(np.float32)
     check(rq, g, live, centres, P, queries, (2, k), "explicit ids")
     g.close()
-
-
-def sub_arrays(g, keep_ids):
-    """The arrays of the index with every list keeping the rows of keep_ids (bool mask over ids) in stored order."""
-    offs, mids = g.offsets.astype(np.int64), g.map_ids
-    keep = keep_ids[mids]
-    lists = np.repeat(np.arange(g.k), np.diff(offs))
-    new_off = np.zeros(g.k + 1, dtype=np.uint32)
-    new_off[1:] = np.cumsum(np.bincount(lists[keep], minlength=g.k))
-    return g.base[keep], g.orthogonal, g.centroids, new_off, mids[keep], g.codes[keep], g.factors[keep]
 
 
 @pytest.mark.parametrize("d,k", [(128, 64), (64, 1024)])

@@ -13,10 +13,10 @@ import numpy as np
 import pytest
 
 from tests import synth
+from tests.models import FMAX, Ref, run_range as run, same_range as same, sub_arrays
 
 pytestmark = pytest.mark.gpu
 
-FMAX = np.finfo(np.float32).max
 
 
 @pytest.fixture(scope="module")
@@ -27,92 +27,6 @@ def rq():
     assert os.path.exists(_lib.SO_PATH), "librabitq_hip.so must be built in-tree"
     _lib.check(_lib.lib().rq_init(0))
     return rabitq_amd
-
-
-class Ref:
-    """The expected answer from the oracle's stage functions: rough and accurate of every probed row, the two strict comparisons,
-    the order.  `oidx`: an oracle.OracleIndex (built, or a view of the engine's arrays)."""
-
-    def __init__(self, oracle, oidx):
-        self.o, self.idx = oracle, oidx
-        self.offsets = oidx.offsets.astype(np.int64)
-        self.map_ids = oidx.map_ids
-        self.base = np.ascontiguousarray(oidx.base)
-        self.dim = oidx.dim
-        self._l2 = oracle.lib().rqo_l2_squared_distance
-        self._f32p = C.POINTER(C.c_float)
-
-    def rows(self, q, probe):
-        """-> (positions, rough) of every stored row of the query's probe lists, in visiting order."""
-        y = self.idx.rotate_query(q)
-        cl, cd = self.idx.coarse_rank(y, probe)
-        pos, rough = [], []
-        for c, ycd in zip(cl, cd):
-            c = int(c)
-            if self.offsets[c + 1] == self.offsets[c]:
-                continue
-            lo, delta, s, planes = self.idx.query_prep(y, c)
-            rough.append(self.idx.scan_cluster(c, ycd, planes, lo, np.float32(s), delta))
-            pos.append(np.arange(self.offsets[c], self.offsets[c + 1]))
-        if not pos:
-            return np.zeros(0, np.int64), np.zeros(0, np.float32)
-        return np.concatenate(pos), np.concatenate(rough)
-
-    def accurate(self, q, positions):
-        qp = np.zeros(self.dim, dtype=np.float32)
-        qp[:q.size] = q
-        qptr = qp.ctypes.data_as(self._f32p)
-        addr, stride = self.base.ctypes.data, self.dim * 4
-        out = np.empty(len(positions), dtype=np.float32)
-        for i, p in enumerate(positions):
-            out[i] = self._l2(qptr, C.cast(addr + int(p) * stride, self._f32p), self.dim)
-        return out
-
-    def answer(self, queries, probe, radii):
-        """-> lims u64[nq + 1], dist, ids, counters {rough, precise}, gated = rows with accurate < r <= rough among the rows whose
-        exact distance was looked at (only computed where cheap: see `gated_rows`)."""
-        lims, dist, ids = [0], [], []
-        tot_rough = tot_precise = 0
-        for q, r in zip(queries, radii):
-            r = np.float32(r)
-            pos, rough = self.rows(q, probe)
-            tot_rough += pos.size
-            cand = pos[rough < r]          # (False for a NaN radius)
-            tot_precise += cand.size
-            acc = self.accurate(q, cand)
-            hit = acc < r
-            d, i = acc[hit], self.map_ids[cand[hit]]
-            order = np.lexsort((i, d.view(np.int32)))   # accurate >= +0: Ord32 is the bit pattern
-            dist.append(d[order])
-            ids.append(i[order])
-            lims.append(lims[-1] + int(hit.sum()))
-        return (np.array(lims, dtype=np.uint64), np.concatenate(dist).astype(np.float32) if dist else np.zeros(0, np.float32),
-                np.concatenate(ids).astype(np.uint32) if ids else np.zeros(0, np.uint32), {"rough": tot_rough, "precise": tot_precise})
-
-    def gated_rows(self, q, probe, r):
-        """rows of the probe lists with accurate < r <= rough: what the reference's gate leaves out."""
-        r = np.float32(r)
-        pos, rough = self.rows(q, probe)
-        out = pos[~(rough < r)]
-        return int((self.accurate(q, out) < r).sum())
-
-
-def same(got, want, what=""):
-    gl, gd, gi = got
-    wl, wd, wi = want
-    assert gl.dtype == np.uint64 and gd.dtype == np.float32 and gi.dtype == np.uint32
-    assert np.array_equal(gl, wl), (what, "lims", np.nonzero(gl != wl)[0][:5], gl[:8], wl[:8])
-    assert np.array_equal(gi, wi), (what, "ids", np.nonzero(gi != wi)[0][:5])
-    assert np.array_equal(gd.view(np.uint32), wd.view(np.uint32)), (what, "distance bits", np.nonzero(gd.view(np.uint32) != wd.view(np.uint32))[0][:5])
-
-
-def run(rq, gidx, queries, probe, radii, filter=None):
-    """-> (lims, dist, ids), counter deltas, profile"""
-    from rabitq_amd import index as ix
-    rq.metrics_reset()
-    got = gidx.range_search(queries, probe, radii, filter=filter)
-    m = rq.metrics()
-    return got, m, ix.last_profile()
 
 
 def kth_radii(gidx, queries, probe, scales, topk=10):
@@ -309,17 +223,6 @@ def test_consistent_with_plain_query(rq, oracle):
     idx.close()
 
 
-def _sub_arrays(g, allowed):
-    offs, mids = g.offsets.astype(np.int64), g.map_ids
-    keep = np.zeros(mids.size, dtype=bool)
-    inr = mids < allowed.size
-    keep[inr] = allowed[mids[inr]]
-    lists = np.repeat(np.arange(g.k), np.diff(offs))
-    new_off = np.zeros(g.k + 1, dtype=np.uint32)
-    new_off[1:] = np.cumsum(np.bincount(lists[keep], minlength=g.k))
-    return g.base[keep], g.orthogonal, g.centroids, new_off, mids[keep], g.codes[keep], g.factors[keep]
-
-
 @pytest.mark.parametrize("name", ["half", "pct1", "empty", "full"])
 def test_filters(rq, oracle, name):
     """5. The filtered range answer = the unfiltered one with the non-admitted ids removed = the oracle's on the sub-index;
@@ -333,7 +236,7 @@ def test_filters(rq, oracle, name):
     rng = np.random.default_rng(5)
     allowed = {"half": rng.random(n) < 0.5, "pct1": rng.random(n) < 0.01, "empty": np.zeros(n, bool), "full": np.ones(n, bool)}[name]
     plain, _, _ = run(rq, gidx, queries, probe, radii)
-    sub = _sub_arrays(gidx, allowed)
+    sub = sub_arrays(gidx, allowed)
     ov = oracle.OracleIndex.view(gidx.dim, *sub)
     want = Ref(oracle, ov).answer(queries, probe, radii)
     with gidx.make_filter(mask=allowed) as f:
