@@ -115,13 +115,8 @@ static rq_status range_rerun_overflowed(rq_index *idx, Workspace *ws, const Quer
     const uint32_t npb = std::min(qp.probe, idx->k);
     const uint64_t budget = 4ull << 30;  // survivor records + run directories of one re-run (48 B per slot), unless one query alone needs more
     const uint64_t max_m = std::max<uint64_t>(1, std::min<uint64_t>(RQ_MAX_NQ_PER_PASS, (1ull << 22) / npb));
-    Workspace *rwsp = ws_acquire(idx);  // (pooled: its buffers persist across calls)
-    struct RelR {
-        rq_index *i;
-        Workspace *w;
-        ~RelR() { ws_release(i, w); }
-    } relr{idx, rwsp};
-    Workspace &rws = *rwsp;
+    WsLease lease(idx, ws_acquire(idx));  // (pooled: its buffers persist across calls)
+    Workspace &rws = *lease.w;
     for (size_t o = 0; o < over.size();) {
         size_t e = o;
         uint32_t ncap = 0;
@@ -202,22 +197,6 @@ static rq_status range_sort_segments(Workspace &ws, unsigned long long *keys, co
     return RQ_OK;
 }
 
-static rq_status range_validate(const rq_index *idx, const rq_filter *filter, const float *d_q, uint32_t len, uint32_t probe,
-                                const float *d_radius) {
-    RQC(ensure_device());
-    RQC(ensure_kernel_attributes());
-    if (!idx || !d_q || !d_radius) return fail(RQ_ERR_INVALID, "null argument");
-    if (idx->dim != (len + 63) / 64 * 64)  // rabitq.rs:275
-        return fail(RQ_ERR_DIM_MISMATCH, "query length " + std::to_string(len) + " does not pad to index dim " + std::to_string(idx->dim));
-    if (probe == 0 || idx->k == 0) return fail(RQ_ERR_INVALID, "probe == 0 (the reference panics at rabitq.rs:295)");
-    if (std::min(probe, idx->k) > RQ_MAX_PROBE) return fail(RQ_ERR_UNSUPPORTED, "probe > 16384 not supported");
-    if (idx->dim > 4096) return fail(RQ_ERR_UNSUPPORTED, "dim > 4096 not supported");
-    if (filter && filter->idx != idx) return fail(RQ_ERR_INVALID, "the filter was made for another index");
-    if (filter && filter->generation != idx->generation)
-        return fail(RQ_ERR_INVALID, "the filter was made before the index was last mutated (rq_add / rq_remove): make it again");
-    return RQ_OK;
-}
-
 static rq_status range_device_impl(rq_index *idx, const rq_filter *filter, const float *d_q, uint32_t nq, uint32_t len, uint32_t probe,
                                    const float *d_radius, rq_range_result **out) {
     std::unique_ptr<rq_range_result> res(new rq_range_result());
@@ -225,11 +204,7 @@ static rq_status range_device_impl(rq_index *idx, const rq_filter *filter, const
     rq_profile_t prof;
     memset(&prof, 0, sizeof prof);
     Workspace *ws = ws_acquire(idx);
-    struct Rel {
-        rq_index *i;
-        Workspace *w;
-        ~Rel() { ws_release(i, w); }
-    } rel{idx, ws};
+    WsLease rel(idx, ws);
     if (!ws->stream) HIPC(hipStreamCreateWithFlags(&ws->stream, hipStreamNonBlocking));
     if (!ws->h_totals) HIPC(hipHostMalloc((void **)&ws->h_totals, 16 * sizeof(unsigned long long)));
     hipStream_t st = ws->stream;
@@ -306,7 +281,7 @@ static rq_status range_device(rq_index *idx, const rq_filter *filter, const floa
         RQC(ensure_device());
         if (!idx) return fail(RQ_ERR_INVALID, "null argument");
     } else {
-        RQC(range_validate(idx, filter, d_q, len, probe, d_radius));
+        RQC(validate_call(idx, !d_q || !d_radius, len, probe, 1u, filter));
     }
     if (nq == 0) {
         std::unique_ptr<rq_range_result> res(new rq_range_result());

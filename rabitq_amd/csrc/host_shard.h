@@ -188,11 +188,7 @@ static rq_status sharded_step(rq_index *mi, void *nccl_comm, uint32_t world, uin
     const uint32_t npb = std::min(probe, std::max(mi->k, 1u));
     const uint32_t width = shared ? 2 * topk : topk;  // keys per query and rank in the final all-gather
     Workspace *ws = ws_acquire(mi);
-    struct Rel {
-        rq_index *i;
-        Workspace *w;
-        ~Rel() { ws_release(i, w); }
-    } rel{mi, ws};
+    WsLease rel(mi, ws);
     if (!ws->stream) HIPC(hipStreamCreateWithFlags(&ws->stream, hipStreamNonBlocking));
     hipStream_t st = ws->stream;
     RQC(ws->sh_flag.ensure(8));  // [0..3] handshake, [4] status of the final gather

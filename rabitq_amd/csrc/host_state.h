@@ -176,15 +176,24 @@ struct Prof {
 struct StreamRange {
     uint32_t s_lo, s_hi;
 };
+#define RQ_MAX_STAGES 40  // stages of one pass (host_plan.h): the geometric schedule ends within 32 doublings of a 32-bit stream position
+// context of a pass that has been enqueued but not yet finished: run_pass assigns it once, finish_pass reads it
+struct PendingPass {
+    uint64_t seg_slots = 0;  // slots of the final stage's segments (0: uniform geometry)
+    uint32_t cap = 0;        // uniform capacity of the pass
+    uint32_t nq = 0;
+    StreamRange matrix_ranges[RQ_MAX_STAGES];  // stream ranges scanned on the matrix cores (profiling only)
+    uint32_t n_matrix_ranges = 0;
+    const struct rq_filter *filter = nullptr;  // the pass's filter (its stream lengths are in stream_len; its hints)
+    bool additive = false;        // the pass ran a matrix-core stage with the additive gate (finish_pass reads its flag rate)
+    uint32_t matrix_stages = 0;   // matrix-core stages of the pass
+    bool prefiltered = false;     // the pass ranked its lists through the matrix-core pre-filter (totals[12] = rows that fell back)
+    bool range = false;           // a range pass (it orders no run directories: the long-directory hint keeps its value)
+};
 struct Workspace {
     hipStream_t stream = nullptr;
     bool busy = false;
-    // context of a pass that has been enqueued but not yet finished (finish_pass)
-    size_t pend_total_span = 0;
-    uint64_t pend_seg_slots = 0;  // slots of the final stage's segments (0: uniform geometry)
-    uint32_t pend_cap = 0;        // uniform capacity of the pass
-    uint32_t pend_nq = 0;
-    std::vector<StreamRange> pend_matrix_ranges;  // stream ranges scanned on the matrix cores (profiling only)
+    PendingPass pend;
     DevBuf<float> qpad, y, dist, probe_dist, thr, recent;
     DevBuf<float> retry_q, retry_pd, retry_pc;  // overflow re-runs: the affected queries (and their probe lists)
     DevBuf<uint32_t> retry_rows;
@@ -204,11 +213,7 @@ struct Workspace {
     DevBuf<uint32_t> qf6;
     DevBuf<unsigned long long> rough_cnt, totals, surv_cnt, stat;
     DevBuf<unsigned long long> stream_len;  // filtered passes: per query, the stream's length (rough_cnt holds the admitted rows)
-    const struct rq_filter *pend_filter = nullptr;  // the pending pass's filter (its stream lengths are in stream_len; its hints)
     DevBuf<float4> grp_vref;  // additive gate: per list, centre and half-range of v' over the stage's pairs (group_vrange_kernel)
-    bool pend_additive = false;  // the pass ran a matrix-core stage with the additive gate (finish_pass reads its flag rate)
-    uint32_t pend_matrix_stages = 0;  // matrix-core stages of the pass
-    bool pend_prefiltered = false;    // the pass ranked its lists through the matrix-core pre-filter (totals[12] = rows that fell back)
     DevBuf<SurvRec> surv, arr;
     DevBuf<RunRec> runs, runs_tmp;
     bool use_runs_tmp = false;
@@ -220,7 +225,6 @@ struct Workspace {
     DevBuf<uint32_t> range_hits;               // range passes (host_range.h): per query, the candidates inside its radius
     DevBuf<uint32_t> range_lists;              //   the segmented sort's three segment lists (by length class) ...
     DevBuf<unsigned long long> range_counters; //   ... and their lengths + the longest segment
-    bool pend_range = false;                   // the pending pass is a range pass (it orders no run directories: the long-directory hint keeps its value)
     DevBuf<uint32_t> ovf, q_cap;               // per query: overflow flag; segment capacity of the final stage (segmented passes)
     DevBuf<unsigned long long> q_base;         // per query: first slot of its segment
     DevBuf<SurvRec> arena_recs;                // arena stages: survivors of all queries, unordered (256 shards)
@@ -322,6 +326,31 @@ static PassHints hints_of(const rq_index *idx, const rq_filter *f) {
     rq_index *m = const_cast<rq_index *>(idx);
     return PassHints{m->cap_hint, m->arena_hint, m->big_dirs_hint};
 }
+
+static Workspace *ws_acquire(rq_index *idx) {
+    std::lock_guard<std::mutex> g(idx->ws_mu);
+    for (auto &w : idx->ws_pool)
+        if (!w->busy) {
+            w->busy = true;
+            return w.get();
+        }
+    idx->ws_pool.emplace_back(new Workspace());
+    idx->ws_pool.back()->busy = true;
+    return idx->ws_pool.back().get();
+}
+static void ws_release(rq_index *idx, Workspace *w) {
+    std::lock_guard<std::mutex> g(idx->ws_mu);
+    w->busy = false;
+}
+// A workspace held for a scope: goes back to the index's pool at its end (w == nullptr: nothing held).
+struct WsLease {
+    rq_index *idx;
+    Workspace *w;
+    WsLease(rq_index *i, Workspace *ws) : idx(i), w(ws) {}
+    WsLease(const WsLease &) = delete;
+    WsLease &operator=(const WsLease &) = delete;
+    ~WsLease() { if (w) ws_release(idx, w); }
+};
 
 // ------------------------------------------------------------------------------------------------
 // small init kernels

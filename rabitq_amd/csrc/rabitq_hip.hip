@@ -34,6 +34,7 @@
 #include "kernels_small.h"
 
 #include "host_state.h"
+#include "host_plan.h"
 #include "host_query.h"
 #include "host_range.h"
 #include "host_build.h"
@@ -448,11 +449,7 @@ rq_status rq_coarse_topk_device(const rq_index *idx, const float *d_queries, uin
     // deployments, so nothing may be allocated or freed per call
     rq_index *mi = const_cast<rq_index *>(idx);
     Workspace *ws = ws_acquire(mi);
-    struct Rel {
-        rq_index *i;
-        Workspace *w;
-        ~Rel() { ws_release(i, w); }
-    } rel{mi, ws};
+    WsLease rel(mi, ws);
     if (!ws->stream) HIPC(hipStreamCreateWithFlags(&ws->stream, hipStreamNonBlocking));
     hipStream_t st = ws->stream;
     // the distance matrix is chunk x kc floats: queries go through in chunks of at most 2^31 cells (8 GiB), so that a
