@@ -67,7 +67,7 @@ typedef struct {
     uint64_t n;            /* number of vectors */
     uint64_t n_hbm;        /* raw vectors resident in HBM; the other n - n_hbm (list tails) are in pinned host memory */
     uint32_t split_rows;   /* 1: the raw vectors are stored as split rows (option "split_rows"); appended in 0.5.0 */
-    uint32_t reserved0;
+    uint32_t metric;       /* RQ_METRIC_L2 or RQ_METRIC_COSINE (was reserved0, always 0, before 0.8.0) */
 } rq_info_t;
 
 /* ---- library ------------------------------------------------------------------------------- */
@@ -79,13 +79,37 @@ typedef struct {
  * "coarse_tiled_from", "rerank_shadow" = 2 -- the new default; 0.5.0: option "split_rows", rq_info_t.split_rows appended, RQ_ARR_BASE
  * refused for split rows as for tiers; 0.6.0: filtered queries -- rq_filter_* and rq_query_batch*_filtered, additions only;
  * 0.7.0: in-place mutation -- rq_add / rq_remove / rq_last_mutate_stats, additions only; a filter made before a mutation of its
- * index is refused; later in 0.7, additions only: range search -- rq_range_search* and rq_range_result_*).
+ * index is refused; later in 0.7, additions only: range search -- rq_range_search* and rq_range_result_*;
+ * 0.8.0: cosine metric -- rq_*_metric, rq_normalize*, rq_info_t.reserved0 became metric, additions only).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
 const char *rq_version(void);
 const char *rq_last_error(void);              /* thread-local message of the last failure        */
 rq_status rq_init(int device);                /* select the HIP device for this process          */
+
+/* ---- metric ---------------------------------------------------------------------------------- */
+/* The metric is a property of the index.  RQ_METRIC_L2 (what every entry point without a metric argument means) is the
+ * reference's squared L2 distance.  RQ_METRIC_COSINE normalises on the GPU every raw row that enters the index (build,
+ * streamed build, rq_add) and every raw query row (every query entry point that takes queries: plain, filtered, range,
+ * _begin / _end, probed, seeded, rq_coarse_topk_device, rq_coarse_rank, the sharded step), and is otherwise the L2 engine:
+ * a cosine index made from (base, centroids, P) equals, bit for bit, the L2 index made from (N(base) row by row, centroids,
+ * P) -- every array (RQ_ARR_BASE returns the normalised rows), rq_info, the five files of rq_dump_dir -- and a query q
+ * returns exactly what that L2 index returns for N(q): ids, order, distance bits, out_n, status and counters.  Distances
+ * are therefore |N(x) - N(q)|^2 = 2 - 2 cos(x, q), unscaled; radii (rq_range_search*) and initial thresholds
+ * (rq_query_batch_device_seeded) are in that unit.  Centroids are used as given (train them on normalised rows:
+ * rq_normalize_device).  The reference has no counterpart (its README lists cosine similarity as missing).
+ * N(x), on the row zero-padded to dim = ceil64(d): s = vector_dot_product(x, x) in the order of src/simd.rs:257-314 (eight
+ * lanes, one fused multiply-add per lane and 8-element chunk in sequence, then the 8-lane fold); nrm = sqrtf(s), correctly
+ * rounded; if nrm is a normal number (f32::is_normal, the test of src/rabitq.rs:210-215) N(x)_i = x_i / nrm, an IEEE f32
+ * division; otherwise N(x) = x bit for bit (a zero row, a subnormal or overflowed norm, a row holding inf or NaN).
+ * rq_rerank and rq_query_prep take already-prepared inputs (a padded query, rotated queries) and do not normalise:
+ * pass N(q) / its rotation.  An unknown metric is refused with RQ_ERR_INVALID. */
+enum { RQ_METRIC_L2 = 0, RQ_METRIC_COSINE = 1 };
+/* N(x) of n rows of d floats; out is n x ceil64(d) (d <= 4096).  rq_normalize: host pointers; rq_normalize_device: device
+ * pointers, returns with `out` complete. */
+rq_status rq_normalize(const float *x, uint64_t n, uint32_t d, float *out);
+rq_status rq_normalize_device(const float *d_x, uint64_t n, uint32_t d, float *d_out);
 
 /* ---- build: RaBitQ::from_path, src/rabitq.rs:159-265 ---------------------------------------- */
 /* `orthogonal` is the dim x dim rotation P (row-major, P[r][c]); the reference draws it from an
@@ -100,6 +124,13 @@ rq_status rq_build_device(const float *d_base, uint64_t n, uint32_t d, const flo
 /* From .fvecs files exactly as RaBitQ::from_path(base_path, centroid_path). */
 rq_status rq_build_from_path(const char *base_fvecs, const char *centroid_fvecs,
                              const float *orthogonal, uint64_t seed, rq_index **out);
+/* The three builds with a metric (RQ_METRIC_L2: exactly the calls above). */
+rq_status rq_build_metric(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k,
+                          const float *orthogonal, uint64_t seed, uint32_t metric, rq_index **out);
+rq_status rq_build_device_metric(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids,
+                                 uint32_t k, const float *orthogonal_host, uint64_t seed, uint32_t metric, rq_index **out);
+rq_status rq_build_from_path_metric(const char *base_fvecs, const char *centroid_fvecs,
+                                    const float *orthogonal, uint64_t seed, uint32_t metric, rq_index **out);
 
 /* ---- streamed two-pass build: from_path for inputs that need not be resident (e.g. 100M x 768 = 307 GB) ---- */
 /* The same result as rq_build_device, with the n x d input fed chunk by chunk, twice:
@@ -125,6 +156,9 @@ typedef struct {
 } rq_build_stats_t;
 rq_status rq_builder_create(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
                             uint64_t seed, uint64_t max_device_base_bytes, rq_builder **out);
+/* rq_builder_create with a metric: on a cosine builder both passes normalise their chunks (the same kernel, the same bits). */
+rq_status rq_builder_create_metric(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
+                                   uint64_t seed, uint64_t max_device_base_bytes, uint32_t metric, rq_builder **out);
 rq_status rq_builder_assign_chunk(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m);
 rq_status rq_builder_order(rq_builder *b);
 rq_status rq_builder_place_chunk(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m);
@@ -140,12 +174,15 @@ rq_status rq_kmeans_device(const float *d_base, uint64_t n, uint32_t d, uint32_t
                            uint32_t points_per_centroid, uint64_t seed, float *d_centroids_out);
 
 /* ---- persistence: load_from_dir / dump_to_dir, src/rabitq.rs:84-156 -------------------------- */
-/* Byte-compatible with the crate's five-file directory (vecs framing: src/utils.rs:280-364). */
+/* Byte-compatible with the crate's five-file directory (vecs framing: src/utils.rs:280-364).  A cosine index writes a sixth
+ * file, `metric`, holding the text "cosine\n" (an L2 dump stays exactly the five files); rq_load_dir sets the metric when the
+ * file is present (unknown content: RQ_ERR_IO). */
 rq_status rq_load_dir(const char *dir, rq_index **out);
 rq_status rq_dump_dir(const rq_index *idx, const char *dir);
 /* load_from_json / dump_to_json, src/rabitq.rs:72-81: the serde_json image of the `RaBitQ` struct (faer `Mat`s as
  * {"nrows","ncols","data": row-major}; base dim x n, centroids dim x k).  A debugging format in the reference too: the
- * text is ~10x the binary directory, so use rq_load_dir / rq_dump_dir for anything large. */
+ * text is ~10x the binary directory, so use rq_load_dir / rq_dump_dir for anything large.  A cosine index adds the member
+ * "metric":"cosine" (serde ignores unknown members: the reference still loads the file); rq_load_json reads it when present. */
 rq_status rq_load_json(const char *path, rq_index **out);
 rq_status rq_dump_json(const rq_index *idx, const char *path);
 void rq_free(rq_index *idx);
@@ -157,6 +194,12 @@ rq_status rq_from_arrays(uint32_t dim, uint64_t n, uint32_t k, const float *base
                          const float *orthogonal, const float *centroids, const uint32_t *offsets,
                          const uint32_t *map_ids, const uint64_t *codes, const rq_factor_t *factors,
                          rq_index **out);
+/* The same with a metric.  The arrays are taken as they are (as rq_from_arrays trusts codes and factors: `base` of a cosine
+ * index holds normalised rows already); the metric only marks the index, so that its queries and added rows are normalised. */
+rq_status rq_from_arrays_metric(uint32_t dim, uint64_t n, uint32_t k, const float *base,
+                                const float *orthogonal, const float *centroids, const uint32_t *offsets,
+                                const uint32_t *map_ids, const uint64_t *codes, const rq_factor_t *factors,
+                                uint32_t metric, rq_index **out);
 
 rq_status rq_info(const rq_index *idx, rq_info_t *out);
 /* Copy one array of the index back to host memory (sizes as in rq_from_arrays). */
@@ -282,6 +325,8 @@ void rq_range_result_free(rq_range_result *r);
  * RQ_ERR_INVALID: an index with a rq_query_batch_device_begin ticket whose _end has not run.  No query may run on the index while
  * it is mutated (the caller serialises, as Rust's &mut self does).  Workspaces and tile tables of the old layout are released.
  *
+ * On a cosine index rq_add normalises the new rows, and the invariant reads: the index equals rq_build_metric(live ORIGINAL
+ * rows, RQ_METRIC_COSINE).
  * rq_add: insert m rows (m x d f32, row-major; host or device memory per rows_on_device).  d must pad to the index's dim
  * (ceil64(d) == dim), else RQ_ERR_DIM_MISMATCH.  ids: NULL = the next ids, first = 1 + the largest id the index holds (0 if
  * empty), returned in *out_first_id (RQ_ERR_UNSUPPORTED if the last would pass 2^32 - 1); else m explicit u32 ids in the same

@@ -20,7 +20,8 @@ STATUS_NAMES = {0: "RQ_OK", -1: "RQ_ERR_INVALID", -2: "RQ_ERR_DIM_MISMATCH", -3:
 
 # every symbol include/rabitq_hip.h declares (checked by tests/test_abi.py against the header)
 EXPORTS = [
-    "rq_version", "rq_abi_version", "rq_last_error", "rq_init", "rq_build", "rq_build_device", "rq_build_from_path", "rq_kmeans_device", "rq_builder_create", "rq_builder_assign_chunk", "rq_builder_order", "rq_builder_place_chunk", "rq_builder_finish", "rq_builder_free", "rq_builder_stats", "rq_load_dir",
+    "rq_version", "rq_abi_version", "rq_last_error", "rq_init", "rq_normalize", "rq_normalize_device", "rq_build", "rq_build_device", "rq_build_from_path",
+    "rq_build_metric", "rq_build_device_metric", "rq_build_from_path_metric", "rq_builder_create_metric", "rq_from_arrays_metric", "rq_kmeans_device", "rq_builder_create", "rq_builder_assign_chunk", "rq_builder_order", "rq_builder_place_chunk", "rq_builder_finish", "rq_builder_free", "rq_builder_stats", "rq_load_dir",
     "rq_dump_dir", "rq_load_json", "rq_dump_json", "rq_free", "rq_from_arrays", "rq_info", "rq_get_array", "rq_get_device_ptr", "rq_query",
     "rq_query_batch", "rq_query_batch_device", "rq_query_batch_device_begin", "rq_query_batch_device_end", "rq_filter_create", "rq_filter_rows", "rq_filter_free", "rq_query_batch_filtered", "rq_query_batch_device_filtered", "rq_range_search", "rq_range_search_device", "rq_range_result_info", "rq_range_result_device_ptrs", "rq_range_result_copy", "rq_range_result_free", "rq_add", "rq_remove", "rq_last_mutate_stats", "rq_coarse_topk_device", "rq_merge_smallest_u64_device", "rq_query_batch_device_probed", "rq_query_batch_device_seeded", "rq_partition_lists", "rq_shard_index", "rq_query_batch_sharded_device", "rq_set_collectives", "rq_metrics", "rq_metrics_reset", "rq_rotate", "rq_rotate_device",
     "rq_quantize_pack",
@@ -32,6 +33,19 @@ class RabitqError(RuntimeError):
     def __init__(self, status, message):
         super().__init__(f"{STATUS_NAMES.get(status, status)}: {message}")
         self.status = status
+
+
+METRIC_L2, METRIC_COSINE = 0, 1   # RQ_METRIC_*
+METRICS = {"l2": METRIC_L2, "cosine": METRIC_COSINE}
+
+
+def metric_id(metric) -> int:
+    """"l2" / "cosine" (or an RQ_METRIC_* value) -> the C ABI's metric id."""
+    if isinstance(metric, str):
+        if metric.lower() not in METRICS:
+            raise ValueError(f"metric must be one of {sorted(METRICS)}, not {metric!r}")
+        return METRICS[metric.lower()]
+    return int(metric)
 
 
 ABI_VERSION = 4   # RQ_ABI_VERSION of include/rabitq_hip.h this mirror was written against
@@ -47,7 +61,7 @@ class _Sized(C.Structure):
 
 class Info(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("dim", C.c_uint32), ("k", C.c_uint32), ("max_list_len", C.c_uint32),
-                ("n", C.c_uint64), ("n_hbm", C.c_uint64), ("split_rows", C.c_uint32), ("reserved0", C.c_uint32)]
+                ("n", C.c_uint64), ("n_hbm", C.c_uint64), ("split_rows", C.c_uint32), ("metric", C.c_uint32)]
 
 
 class MetricsT(C.Structure):
@@ -117,6 +131,13 @@ def lib():
         "rq_build": (i32, [f32p, u64, u32, f32p, u32, f32p, u64, pp]),
         "rq_build_device": (i32, [f32p, u64, u32, f32p, u32, f32p, u64, pp]),
         "rq_build_from_path": (i32, [C.c_char_p, C.c_char_p, f32p, u64, pp]),
+        "rq_normalize": (i32, [f32p, u64, u32, f32p]),
+        "rq_normalize_device": (i32, [f32p, u64, u32, f32p]),
+        "rq_build_metric": (i32, [f32p, u64, u32, f32p, u32, f32p, u64, u32, pp]),
+        "rq_build_device_metric": (i32, [f32p, u64, u32, f32p, u32, f32p, u64, u32, pp]),
+        "rq_build_from_path_metric": (i32, [C.c_char_p, C.c_char_p, f32p, u64, u32, pp]),
+        "rq_builder_create_metric": (i32, [u64, u32, f32p, u32, f32p, u64, u64, u32, pp]),
+        "rq_from_arrays_metric": (i32, [u32, u64, u32, f32p, f32p, f32p, u32p, u32p, u64p, vp, u32, pp]),
         "rq_kmeans_device": (i32, [f32p, u64, u32, u32, u32, u32, u64, f32p]),
         "rq_builder_create": (i32, [u64, u32, f32p, u32, f32p, u64, u64, pp]),
         "rq_builder_assign_chunk": (i32, [vp, f32p, u64, u64]),

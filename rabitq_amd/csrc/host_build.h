@@ -367,7 +367,7 @@ static rq_status builder_alloc_pass1(rq_builder *b) {
     RQC(b->codes_tmp.alloc(n * idx->W));
     RQC(b->factors_tmp.alloc(n));
     const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(n, 1), RQ_BUILD_CHUNK);
-    if (b->d != dim) RQC(b->xpad.alloc(chunk * dim));
+    if (b->d != dim || idx->metric == RQ_METRIC_COSINE) RQC(b->xpad.alloc(chunk * dim));
     RQC(b->xrot.alloc(chunk * dim));
     if (assign_has_mfma(idx->W) && g_assign_impl.load() != 1) RQC(assign_aux_init(idx, b->assign_aux, chunk));
     for (auto &e : b->ev) HIPC(hipEventCreate(&e));
@@ -375,11 +375,12 @@ static rq_status builder_alloc_pass1(rq_builder *b) {
 }
 
 static rq_status builder_create(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
-                                uint64_t seed, uint64_t max_device_base_bytes, rq_builder **out) {
+                                uint64_t seed, uint64_t max_device_base_bytes, uint32_t metric, rq_builder **out) {
     RQC(ensure_device());
     RQC(ensure_kernel_attributes());
     if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
     *out = nullptr;
+    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, "unknown metric " + std::to_string(metric));
     if (!d_centroids || d == 0 || k == 0) return fail(RQ_ERR_INVALID, "bad build arguments");
     if (n >= 0xFFFFFFFFull) return fail(RQ_ERR_UNSUPPORTED, "n must fit u32 ids (rabitq.rs:64-65)");
     const uint32_t dim = (d + 63) / 64 * 64;  // rabitq.rs:168-179
@@ -387,7 +388,7 @@ static rq_status builder_create(uint64_t n, uint32_t d, const float *d_centroids
     std::unique_ptr<rq_builder> b(new rq_builder());
     b->idx.reset(new rq_index());
     rq_index *idx = b->idx.get();
-    idx->dim = dim, idx->k = k, idx->n = n, idx->W = dim / 64;
+    idx->dim = dim, idx->k = k, idx->n = n, idx->W = dim / 64, idx->metric = metric;
     b->d = d, b->budget = max_device_base_bytes;
 
     std::vector<float> Pgen;
@@ -424,7 +425,10 @@ static rq_status builder_assign(rq_builder *b, const float *d_rows, uint64_t i0,
     for (uint64_t c0 = 0; c0 < m; c0 += RQ_BUILD_CHUNK) {
         const uint64_t mm = std::min<uint64_t>(RQ_BUILD_CHUNK, m - c0), at = i0 + c0;
         const float *src = d_rows + c0 * d;
-        if (d != dim) {
+        if (idx->metric == RQ_METRIC_COSINE) {  // pad + normalise in one launch: everything behind it sees N(x)
+            launch_normalize(src, mm, d, dim, b->xpad.p, nullptr);
+            src = b->xpad.p;
+        } else if (d != dim) {
             pad_rows_kernel<<<ceil_div(mm * dim, 256), 256>>>(src, b->xpad.p, mm, d, dim);
             src = b->xpad.p;
         }
@@ -508,8 +512,11 @@ static rq_status builder_place(rq_builder *b, const float *d_rows, uint64_t i0, 
     if (i0 > idx->n || m > idx->n - i0) return fail(RQ_ERR_INVALID, "chunk outside [0, n)");
     if (!b->cov_place.add(i0, m)) return fail(RQ_ERR_INVALID, "rq_builder_place_chunk: rows [" + std::to_string(i0) + ", " + std::to_string(i0 + m) + ") overlap rows already placed");
     if (m) {
-        place_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(m, 4), 1u << 20), 256>>>(d_rows, i0, m, b->d, idx->dim,
-                                                                                          b->pos_of_id.p, idx->view());
+        if (idx->metric == RQ_METRIC_COSINE)  // the same kernel as pass 1, storing N(x) at the row's final position
+            launch_normalize(d_rows, m, b->d, idx->dim, nullptr, nullptr, b->pos_of_id.p, i0, idx->view());
+        else
+            place_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(m, 4), 1u << 20), 256>>>(d_rows, i0, m, b->d, idx->dim,
+                                                                                              b->pos_of_id.p, idx->view());
         HIPC(hipDeviceSynchronize());  // the caller may reuse d_rows right away
         HIPC(hipGetLastError());
     }
@@ -529,12 +536,12 @@ static rq_status builder_finish(rq_builder *bp, rq_index **out) {
 }
 
 static rq_status build_device(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
-                              const float *orthogonal_host, uint64_t seed, rq_index **out) {
+                              const float *orthogonal_host, uint64_t seed, uint32_t metric, rq_index **out) {
     if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
     *out = nullptr;
     if (n && !d_base) return fail(RQ_ERR_INVALID, "bad build arguments");
     rq_builder *b = nullptr;
-    RQC(builder_create(n, d, d_centroids, k, orthogonal_host, seed, 0, &b));
+    RQC(builder_create(n, d, d_centroids, k, orthogonal_host, seed, 0, metric, &b));
     std::unique_ptr<rq_builder> guard(b);
     RQC(builder_assign(b, d_base, 0, n));
     RQC(builder_order(b));
@@ -586,17 +593,18 @@ static rq_status write_record(FILE *f, const void *data, uint32_t count, size_t 
 static rq_status copy_base_rows(const rq_index *idx, uint64_t i0, uint64_t m, float *buf, bool to_index);
 static rq_status from_arrays(uint32_t dim, uint64_t n, uint32_t k, const float *base, const float *orthogonal,
                              const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
-                             const uint64_t *codes, const rq_factor_t *factors, rq_index **out) {
+                             const uint64_t *codes, const rq_factor_t *factors, uint32_t metric, rq_index **out) {
     RQC(ensure_device());
     RQC(ensure_kernel_attributes());
     if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
     *out = nullptr;
+    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, "unknown metric " + std::to_string(metric));
     if (dim == 0 || dim % 64 != 0) return fail(RQ_ERR_DIM_MISMATCH, "dim must be a non-zero multiple of 64 (rabitq.rs:109)");
     if (!orthogonal || !centroids || !offsets || (n && (!base || !map_ids || !codes || !factors)))
         return fail(RQ_ERR_INVALID, "null array");
     if (n >= 0xFFFFFFFFull) return fail(RQ_ERR_UNSUPPORTED, "n must fit u32");
     std::unique_ptr<rq_index> idx(new rq_index());
-    idx->dim = dim, idx->n = n, idx->k = k, idx->W = dim / 64;
+    idx->dim = dim, idx->n = n, idx->k = k, idx->W = dim / 64, idx->metric = metric;
     RQC(idx->P.alloc((size_t)dim * dim));
     RQC(idx->centroids.alloc((size_t)k * dim));
     RQC(idx->offsets.alloc((size_t)k + 1));

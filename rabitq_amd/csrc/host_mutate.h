@@ -301,6 +301,15 @@ static rq_status index_add(rq_index *idx, const float *rows, uint64_t m, uint32_
     if (!idx->row_order_ok)
         return fail(RQ_ERR_UNSUPPORTED, "a list of this index is not in the build's order (distance to its centroid, then id): rows can be "
                                         "removed from it, but not added (an index from rq_from_arrays / rq_load_dir whose ids were remapped?)");
+    DevBuf<float> normed;  // cosine: N(row), padded -- pass 1 and the gather then take the rows as an L2 build of N(rows) does
+    if (idx->metric == RQ_METRIC_COSINE) {
+        RQC(normed.alloc(m * idx->dim));
+        launch_normalize(d_rows, m, d, idx->dim, normed.p, nullptr);
+        HIPC(hipDeviceSynchronize());
+        HIPC(hipGetLastError());
+        staged.release();
+        d_rows = normed.p, d = idx->dim;
+    }
     RQC(new_rows_prepare(idx, d_rows, m, d, ranks.p, nr));
     ranks.release();
     return relayout(idx, nullptr, {}, &nr);

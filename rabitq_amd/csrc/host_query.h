@@ -184,8 +184,15 @@ struct Pass {
         if (sa.stamps) HIPC(hipMemsetAsync(ws.stat.p, 0, 8, st));
         else HIPC(hipMemsetAsync(ws.stat.p, 0, 256 * sizeof(unsigned long long), st));  // (the counters of a final matrix-core stage, if any)
         pf.begin(PF_COARSE);
+        const float *sb_q = d_q;
+        uint32_t sb_len = qp.len;
+        if (idx->metric == RQ_METRIC_COSINE) {  // N(q), padded: what the front kernel rotates and hands on as qpad
+            RQC(ws.qnorm.ensure((uint64_t)nq * dim));
+            launch_normalize(d_q, nq, qp.len, dim, ws.qnorm.p, st);
+            sb_q = ws.qnorm.p, sb_len = dim;
+        }
         sb_front_kernel<<<dim3(ceil_div(k, RQ_SB_LISTS), ceil_div(nq, RQ_SB_QT)), 256, (size_t)2 * RQ_SB_QT * dim * sizeof(float), st>>>(
-            d_q, qp.len, idx->P.p, idx->centroids.p, ws.y.p, ws.qpad.p, ws.dist.p, k, dim, nq, ws.totals.p, ws.big_list.p + nq);
+            sb_q, sb_len, idx->P.p, idx->centroids.p, ws.y.p, ws.qpad.p, ws.dist.p, k, dim, nq, ws.totals.p, ws.big_list.p + nq);
         pf.end();
         pf.begin(PF_EARLY);
         const size_t dyn = (size_t)RQ_SB_CAP * sizeof(SurvRec) + (size_t)dim * 4 + (size_t)topk * 16;
@@ -215,7 +222,10 @@ struct Pass {
     // 1. pad (rabitq.rs:277-280) + rotate (:282); 2. coarse distances + probe selection (:283-297), unless the caller supplied the lists
     rq_status rotate_coarse() {
         pf.begin(PF_ROTATE);
-        if (qp.len != dim) {
+        if (idx->metric == RQ_METRIC_COSINE) {  // pad + normalise in one launch (also when nothing is padded): rotation and rerank see N(q)
+            launch_normalize(d_q, nq, qp.len, dim, ws.qpad.p, st);
+            qpad = ws.qpad.p;
+        } else if (qp.len != dim) {
             pad_rows_kernel<<<ceil_div((uint64_t)nq * dim, 256), 256, 0, st>>>(d_q, ws.qpad.p, nq, qp.len, dim);
             qpad = ws.qpad.p;
         }

@@ -195,6 +195,7 @@ struct Workspace {
     bool busy = false;
     PendingPass pend;
     DevBuf<float> qpad, y, dist, probe_dist, thr, recent;
+    DevBuf<float> qnorm;  // cosine indexes, small-batch path: N(q), which sb_front_kernel reads in place of the caller's rows
     DevBuf<float> retry_q, retry_pd, retry_pc;  // overflow re-runs: the affected queries (and their probe lists)
     DevBuf<uint32_t> retry_rows;
     DevBuf<uint32_t> q_hist, q_start, q_order;  // rerank order of a large batch (queries grouped by nearest list)
@@ -248,6 +249,7 @@ struct rq_index {
     uint32_t dim = 0, k = 0, W = 0, max_list_len = 0;
     uint32_t min_list_len = 0;  // 0 if some list is empty (then no slot bound can be derived from stream positions)
     uint64_t n = 0;
+    uint32_t metric = RQ_METRIC_L2;  // RQ_METRIC_COSINE: raw rows were normalised on their way in, raw queries are on theirs
     // raw vectors (cluster order, un-rotated).  Untiered (n_dev == n, the usual case): row p at base + p*dim.  Tiered
     // (they do not fit the HBM budget): per list the first h_c members in HBM, the tail in pinned host memory mapped
     // into the device address space (BaseView / ListTier); n_dev = sum of h_c.
@@ -556,6 +558,30 @@ static void launch_rotate(const float *x, const float *P, float *out, uint64_t n
             rotate_valu_kernel<<<dim3(ceil_div(m, 4), dim / 64), dim3(64, 4), 0, st>>>(xs, P, os, m, dim);
         }
     }
+}
+
+// Cosine metric: pad + normalise n rows of length d (normalize_rows_kernel).  place == nullptr: into the dense n x dim `out`;
+// else row r goes to position place[i0 + r] of `view` (the build's pass 2).  dim <= 4096.
+static bool metric_known(uint32_t metric) { return metric == RQ_METRIC_L2 || metric == RQ_METRIC_COSINE; }
+static void launch_normalize(const float *in, uint64_t n, uint32_t d, uint32_t dim, float *out, hipStream_t st,
+                             const uint32_t *place = nullptr, uint64_t i0 = 0, const BaseView view = BaseView{}) {
+    if (n == 0) return;
+    const uint32_t vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+    const uint32_t rw = dim <= 512 ? 8 : dim <= 1024 ? 4 : dim <= 2048 ? 2 : 1;
+    const size_t lds = ((size_t)rw * (dim + 8) + rw) * sizeof(float);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(ceil_div(n, rw), 256u * 10u * 8u);  // grid-stride: ten waves per CU, eight rounds
+#define RQ_NORM(RW) \
+    do { \
+        if (place) normalize_rows_kernel<RW, true><<<grid, 64, lds, st>>>(in, n, d, dim, vec, nullptr, place, i0, view); \
+        else normalize_rows_kernel<RW, false><<<grid, 64, lds, st>>>(in, n, d, dim, vec, out, nullptr, 0, view); \
+    } while (0)
+    switch (rw) {
+        case 8: RQ_NORM(8); break;
+        case 4: RQ_NORM(4); break;
+        case 2: RQ_NORM(2); break;
+        default: RQ_NORM(1); break;
+    }
+#undef RQ_NORM
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -448,6 +448,102 @@ __global__ __launch_bounds__(256) void place_rows_kernel(const float *__restrict
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Cosine metric (RQ_METRIC_COSINE): N(x) of the zero-padded row, the one new piece of arithmetic.
+//   s   = vector_dot_product(x, x) in the reference's order (src/simd.rs:257-314): AVX lane l accumulates
+//         acc_l = fma(x[8c + l], x[8c + l], acc_l) over the chunks c in sequence, then the fixed 8-lane fold
+//   nrm = sqrtf(s);  N(x)_i = x_i / nrm (IEEE division) if nrm is a normal number (f32::is_normal, as at
+//         src/rabitq.rs:210-215), else N(x) = x bit for bit (zero row, subnormal or overflowed norm, inf / NaN)
+// One wave per block, RW rows per wave (8 for dim <= 512 down to 1 for dim <= 4096), 64 / RW lanes per row.  A lane reads
+// its share of the row once (16-byte loads when the input allows them) and keeps it in registers -- at most
+// RQ_NORM_NV float4 for every shape -- while a copy goes through LDS to the eight serial chains of each row: there GPU
+// lane 8 * row + l is AVX lane l (rows RW.. idle), reading x[8c + l] at a row stride of dim + 8 floats so that the rows of
+// one read sit 8 banks apart.  The chains are dim / 8 dependent FMAs long; per CU up to ten waves keep 80 of them in
+// flight, several times what the row's two trips through HBM take, so the kernel runs at the memory rate.
+// Then the registers are divided and written once: PLACE = false to the dense n x dim `out` (rq_normalize*, the build's
+// pass 1, the queries), PLACE = true to the row's final position in whichever tier and row format holds it (the build's
+// pass 2: place_rows_kernel's stores).  Both passes therefore store the same bits.
+// dynamic LDS: (RW * (dim + 8) + RW) floats.
+// ------------------------------------------------------------------------------------------------
+#define RQ_NORM_NV 16
+template <int RW, bool PLACE>
+__global__ __launch_bounds__(64) void normalize_rows_kernel(const float *__restrict__ in, uint64_t n, uint32_t d, uint32_t dim,
+                                                            uint32_t vec /* 16-byte loads and stores are aligned */,
+                                                            float *__restrict__ out, const uint32_t *__restrict__ pos_of_id,
+                                                            uint64_t i0, const BaseView view) {
+    extern __shared__ __attribute__((aligned(16))) float nrm_lds[];
+    constexpr uint32_t LPR = 64 / RW;
+    const uint32_t lane = threadIdx.x, rr = lane / LPR, g = lane % LPR;
+    const uint32_t S = dim + 8, np = dim / 4;
+    float *scale = nrm_lds + RW * S;
+    const uint32_t cr = lane >> 3, cl = lane & 7;  // the chains' view of the wave
+    for (uint64_t r0 = (uint64_t)blockIdx.x * RW; r0 < n; r0 += (uint64_t)gridDim.x * RW) {
+        const uint64_t r = r0 + rr;
+        const bool live = r < n;
+        const float *src = in + r * d;
+        float4 v[RQ_NORM_NV];
+#pragma unroll
+        for (int i = 0; i < RQ_NORM_NV; ++i) {
+            const uint32_t p = g + i * LPR, e = 4 * p;
+            v[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (p < np) {
+                if (live) {
+                    if (vec) {  // (d is a multiple of 4: a piece is inside the row or all padding)
+                        if (e < d) v[i] = *reinterpret_cast<const float4 *>(src + e);
+                    } else {
+                        v[i].x = e < d ? src[e] : 0.0f, v[i].y = e + 1 < d ? src[e + 1] : 0.0f;
+                        v[i].z = e + 2 < d ? src[e + 2] : 0.0f, v[i].w = e + 3 < d ? src[e + 3] : 0.0f;
+                    }
+                }
+                *reinterpret_cast<float4 *>(nrm_lds + rr * S + e) = v[i];
+            }
+        }
+        __syncthreads();
+        float acc = 0.0f;
+        if (cr < RW) {
+            const float *xr = nrm_lds + cr * S + cl;
+            for (uint32_t c = 0; c < dim; c += 64) {  // eight chunks' reads in flight ahead of their FMAs
+                float t[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) t[u] = xr[c + 8 * u];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) acc = fmaf(t[u], t[u], acc);
+            }
+        }
+        const float s = reduce8_lanes(acc);
+        if (cr < RW && cl == 0) {
+            const float nrm = sqrtf(s);
+            const bool normal = (nrm >= 1.17549435e-38f) && (nrm <= 3.402823466e+38f);  // f32::is_normal (nrm >= 0 or NaN)
+            scale[cr] = normal ? nrm : 0.0f;  // 0: the row stays as it is
+        }
+        __syncthreads();
+        const float nrm = scale[rr];
+        if (!live) continue;  // (wave-uniform loop bounds: every lane still reaches the barriers of the next round)
+        RowRef dst{out + r * dim, false};
+        if (PLACE) dst = view.row(pos_of_id[i0 + r], dim);
+#pragma unroll
+        for (int i = 0; i < RQ_NORM_NV; ++i) {
+            const uint32_t p = g + i * LPR, e = 4 * p;
+            if (p >= np) continue;
+            float4 o = v[i];
+            if (nrm != 0.0f) o.x = o.x / nrm, o.y = o.y / nrm, o.z = o.z / nrm, o.w = o.w / nrm;
+            float *w = const_cast<float *>(dst.p);
+            if (PLACE && dst.split) {  // split rows (common.h): two elements per 32-bit word of each plane
+                const uint32_t b0 = __builtin_bit_cast(uint32_t, o.x), b1 = __builtin_bit_cast(uint32_t, o.y);
+                const uint32_t b2 = __builtin_bit_cast(uint32_t, o.z), b3 = __builtin_bit_cast(uint32_t, o.w);
+                uint32_t *hp = reinterpret_cast<uint32_t *>(w), *lp = hp + dim / 2;
+                *reinterpret_cast<uint2 *>(hp + e / 2) = make_uint2(((b0 + 0x8000u) >> 16) | ((b1 + 0x8000u) & 0xFFFF0000u),
+                                                                    ((b2 + 0x8000u) >> 16) | ((b3 + 0x8000u) & 0xFFFF0000u));
+                *reinterpret_cast<uint2 *>(lp + e / 2) = make_uint2((b0 & 0xFFFFu) | (b1 << 16), (b2 & 0xFFFFu) | (b3 << 16));
+            } else if (PLACE || vec) {  // (index rows are 4 * dim bytes apart from a hipMalloc / hipHostMalloc base: aligned)
+                *reinterpret_cast<float4 *>(w + e) = o;
+            } else {
+                w[e] = o.x, w[e + 1] = o.y, w[e + 2] = o.z, w[e + 3] = o.w;
+            }
+        }
+    }
+}
+
 // out[0] = longest list, out[1] = shortest list (0 if any list is empty); out preset to {0, 0xFFFFFFFF}
 __global__ void max_list_len_kernel(const uint32_t *__restrict__ offsets, uint32_t k, uint32_t *__restrict__ out) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -100,14 +100,51 @@ rq_status rq_kmeans_device(const float *d_base, uint64_t n, uint32_t d, uint32_t
     return RQ_OK;
 }
 
-rq_status rq_build_device(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
-                          const float *orthogonal_host, uint64_t seed, rq_index **out) {
-    return build_device(d_base, n, d, d_centroids, k, orthogonal_host, seed, out);
+// ---- cosine metric: N(x) on its own (the build, rq_add and every query pass run the same kernel) ----
+rq_status rq_normalize_device(const float *d_x, uint64_t n, uint32_t d, float *d_out) {
+    RQC(ensure_device());
+    if (n && (!d_x || !d_out)) return fail(RQ_ERR_INVALID, "null argument");
+    if (d == 0) return fail(RQ_ERR_INVALID, "d == 0");
+    const uint32_t dim = (d + 63) / 64 * 64;
+    if (dim > 4096) return fail(RQ_ERR_UNSUPPORTED, "dim > 4096 not supported");
+    for (uint64_t r0 = 0; r0 < n; r0 += RQ_BUILD_CHUNK)  // (row offsets of a chunk keep the 16-byte alignment of the whole)
+        launch_normalize(d_x + r0 * d, std::min<uint64_t>(RQ_BUILD_CHUNK, n - r0), d, dim, d_out + r0 * dim, nullptr);
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipGetLastError());
+    return RQ_OK;
+}
+rq_status rq_normalize(const float *x, uint64_t n, uint32_t d, float *out) {
+    RQC(ensure_device());
+    if (n && (!x || !out)) return fail(RQ_ERR_INVALID, "null argument");
+    if (d == 0) return fail(RQ_ERR_INVALID, "d == 0");
+    const uint32_t dim = (d + 63) / 64 * 64;
+    if (dim > 4096) return fail(RQ_ERR_UNSUPPORTED, "dim > 4096 not supported");
+    if (n == 0) return RQ_OK;
+    DevBuf<float> dx, dout;
+    RQC(dx.alloc(n * d));
+    RQC(dout.alloc(n * dim));
+    HIPC(hipMemcpy(dx.p, x, n * d * 4, hipMemcpyHostToDevice));
+    RQC(rq_normalize_device(dx.p, n, d, dout.p));
+    HIPC(hipMemcpy(out, dout.p, n * dim * 4, hipMemcpyDeviceToHost));
+    return RQ_OK;
 }
 
+rq_status rq_build_device_metric(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
+                                 const float *orthogonal_host, uint64_t seed, uint32_t metric, rq_index **out) {
+    return build_device(d_base, n, d, d_centroids, k, orthogonal_host, seed, metric, out);
+}
+rq_status rq_build_device(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
+                          const float *orthogonal_host, uint64_t seed, rq_index **out) {
+    return build_device(d_base, n, d, d_centroids, k, orthogonal_host, seed, RQ_METRIC_L2, out);
+}
+
+rq_status rq_builder_create_metric(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
+                                   uint64_t seed, uint64_t max_device_base_bytes, uint32_t metric, rq_builder **out) {
+    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, metric, out);
+}
 rq_status rq_builder_create(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
                             uint64_t seed, uint64_t max_device_base_bytes, rq_builder **out) {
-    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, out);
+    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, RQ_METRIC_L2, out);
 }
 rq_status rq_builder_assign_chunk(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m) { return builder_assign(b, d_rows, i0, m); }
 rq_status rq_builder_order(rq_builder *b) { return builder_order(b); }
@@ -119,21 +156,27 @@ rq_status rq_builder_stats(const rq_builder *b, rq_build_stats_t *out) {
     return copy_out_sized(out, b->stats);
 }
 
-rq_status rq_build(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k,
-                   const float *orthogonal, uint64_t seed, rq_index **out) {
+rq_status rq_build_metric(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k,
+                          const float *orthogonal, uint64_t seed, uint32_t metric, rq_index **out) {
     RQC(ensure_device());
     if ((n && !base) || !centroids) return fail(RQ_ERR_INVALID, "null argument");
+    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, "unknown metric " + std::to_string(metric));
     DevBuf<float> db, dc;
     RQC(db.alloc(n * d));
     RQC(dc.alloc((size_t)k * d));
     if (n) HIPC(hipMemcpy(db.p, base, n * d * 4, hipMemcpyHostToDevice));
     if (k) HIPC(hipMemcpy(dc.p, centroids, (size_t)k * d * 4, hipMemcpyHostToDevice));
-    return build_device(db.p, n, d, dc.p, k, orthogonal, seed, out);
+    return build_device(db.p, n, d, dc.p, k, orthogonal, seed, metric, out);
+}
+rq_status rq_build(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k,
+                   const float *orthogonal, uint64_t seed, rq_index **out) {
+    return rq_build_metric(base, n, d, centroids, k, orthogonal, seed, RQ_METRIC_L2, out);
 }
 
-rq_status rq_build_from_path(const char *base_fvecs, const char *centroid_fvecs, const float *orthogonal,
-                             uint64_t seed, rq_index **out) {
+rq_status rq_build_from_path_metric(const char *base_fvecs, const char *centroid_fvecs, const float *orthogonal,
+                                    uint64_t seed, uint32_t metric, rq_index **out) {
     if (!base_fvecs || !centroid_fvecs) return fail(RQ_ERR_INVALID, "null path");
+    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, "unknown metric " + std::to_string(metric));
     VecsFile b, c;
     RQC(read_vecs_file(base_fvecs, 4, b));      // rabitq.rs:160
     RQC(read_vecs_file(centroid_fvecs, 4, c));  // :163
@@ -144,14 +187,23 @@ rq_status rq_build_from_path(const char *base_fvecs, const char *centroid_fvecs,
         if (l != d) return fail(RQ_ERR_IO, "ragged base.fvecs");
     for (uint32_t l : c.lens)
         if (l != d) return fail(RQ_ERR_IO, "ragged centroids.fvecs");
-    return rq_build(reinterpret_cast<const float *>(b.data.data()), b.lens.size(), d,
-                    reinterpret_cast<const float *>(c.data.data()), (uint32_t)c.lens.size(), orthogonal, seed, out);
+    return rq_build_metric(reinterpret_cast<const float *>(b.data.data()), b.lens.size(), d,
+                           reinterpret_cast<const float *>(c.data.data()), (uint32_t)c.lens.size(), orthogonal, seed, metric, out);
+}
+rq_status rq_build_from_path(const char *base_fvecs, const char *centroid_fvecs, const float *orthogonal,
+                             uint64_t seed, rq_index **out) {
+    return rq_build_from_path_metric(base_fvecs, centroid_fvecs, orthogonal, seed, RQ_METRIC_L2, out);
 }
 
 rq_status rq_from_arrays(uint32_t dim, uint64_t n, uint32_t k, const float *base, const float *orthogonal,
                          const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
                          const uint64_t *codes, const rq_factor_t *factors, rq_index **out) {
-    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, out);
+    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, RQ_METRIC_L2, out);
+}
+rq_status rq_from_arrays_metric(uint32_t dim, uint64_t n, uint32_t k, const float *base, const float *orthogonal,
+                                const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
+                                const uint64_t *codes, const rq_factor_t *factors, uint32_t metric, rq_index **out) {
+    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, metric, out);
 }
 
 // rabitq.rs:84-125
@@ -165,6 +217,14 @@ rq_status rq_load_dir(const char *dir, rq_index **out) {
     RQC(read_vecs_file(d + "/factors.fvecs", 4, fac));
     RQC(read_vecs_file(d + "/x_binary_vec.u64vecs", 8, bin));
     RQC(read_vecs_file(d + "/base.fvecs", 4, base));
+    uint32_t metric = RQ_METRIC_L2;  // the sixth file of a cosine index's dump
+    if (FILE *mf = fopen((d + "/metric").c_str(), "rb")) {
+        char buf[32] = {0};
+        const size_t got = fread(buf, 1, sizeof buf - 1, mf);
+        fclose(mf);
+        if (std::string(buf, got) == "cosine\n") metric = RQ_METRIC_COSINE;
+        else if (std::string(buf, got) != "l2\n") return fail(RQ_ERR_IO, "metric: unknown content in " + d + "/metric");
+    }
     const uint32_t dim = (uint32_t)ortho.lens.size();  // :108 dim = orthogonal.nrows()
     if (dim == 0 || dim % 64 != 0) return fail(RQ_ERR_DIM_MISMATCH, "orthogonal.fvecs: dim % 64 != 0 (rabitq.rs:109)");
     if (cent.lens.size() != dim || oi.lens.size() != 2) return fail(RQ_ERR_IO, "malformed index directory");
@@ -197,7 +257,7 @@ rq_status rq_load_dir(const char *dir, rq_index **out) {
     return from_arrays(dim, n, k, reinterpret_cast<const float *>(base.data.data()),
                        reinterpret_cast<const float *>(ortho.data.data()), c.data(), oip, oip + (total - last),
                        reinterpret_cast<const uint64_t *>(bin.data.data()),
-                       reinterpret_cast<const rq_factor_t *>(fac.data.data()), out);
+                       reinterpret_cast<const rq_factor_t *>(fac.data.data()), metric, out);
 }
 
 rq_status rq_get_array(const rq_index *idx, int which, void *dst, uint64_t dst_bytes);
@@ -270,7 +330,15 @@ rq_status rq_dump_dir(const rq_index *idx, const char *dir) {
     RQC(open("x_binary_vec.u64vecs", &f));
     s = write_record(f, codes.data(), (uint32_t)(n * (dim / 64)), 8, "x_binary_vec.u64vecs");
     fclose(f);
-    return s;
+    RQC(s);
+    if (idx->metric == RQ_METRIC_COSINE) {  // (an L2 dump stays the crate's five files)
+        RQC(open("metric", &f));
+        const bool ok = fputs("cosine\n", f) >= 0;
+        if (fclose(f) != 0 || !ok) return fail(RQ_ERR_IO, "write error on " + d + "/metric");
+    } else {
+        remove((d + "/metric").c_str());  // (a directory that held a cosine dump before)
+    }
+    return RQ_OK;
 }
 
 // ---- JSON persistence: load_from_json / dump_to_json, src/rabitq.rs:72-81 ------------------------------------
@@ -317,7 +385,9 @@ rq_status rq_dump_json(const rq_index *idx, const char *path) {
         o.raw(",\"error_bound\":"), o.f32(fac[4 * i + 2]);
         o.raw(",\"center_distance_square\":"), o.f32(fac[4 * i + 3]), o.raw("}");
     }
-    o.raw("]}");
+    o.raw("]");
+    if (idx->metric == RQ_METRIC_COSINE) o.raw(",\"metric\":\"cosine\"");  // (an unknown member to the reference's serde derive: ignored)
+    o.raw("}");
     const bool closed = fclose(f) == 0;
     if (!o.ok || !closed) return fail(RQ_ERR_IO, std::string("write error on ") + path);
     return RQ_OK;
@@ -340,6 +410,7 @@ rq_status rq_load_json(const char *path, rq_index **out) {
     std::vector<float> base, P, cent, bias;
     std::vector<unsigned long long> off, ids, codes;
     std::vector<rq_factor_t> fac;
+    std::string metric_name;
     bool good = in.need('{');
     if (good && !in.lit('}')) {
         do {
@@ -367,11 +438,19 @@ rq_status rq_load_json(const char *path, rq_index **out) {
                     } while (in.lit(','));
                     return in.need('}');
                 });
-            else good = in.skip();
+            else if (k == "metric") {
+                in.ws();
+                const char *v0 = in.p;
+                good = in.skip();
+                if (good) metric_name.assign(v0, in.p);
+            } else good = in.skip();
         } while (good && in.lit(','));
         good = good && in.need('}');
     }
     if (!good) return fail(RQ_ERR_IO, std::string("deserialize error in ") + path + (in.err.empty() ? "" : ": " + in.err));
+    uint32_t metric = RQ_METRIC_L2;
+    if (metric_name == "\"cosine\"") metric = RQ_METRIC_COSINE;
+    else if (!metric_name.empty() && metric_name != "\"l2\"") return fail(RQ_ERR_IO, std::string("unknown metric ") + metric_name + " in " + path);
     const uint64_t n = ids.size(), k = off.empty() ? 0 : off.size() - 1;
     if (dim == 0 || dim % 64 || pr != dim || pc != dim || P.size() != dim * dim || br != dim || bc != n || base.size() != dim * n ||
         cr != dim || cc != k || cent.size() != dim * k || off.empty() || fac.size() != n || codes.size() != n * (dim / 64) ||
@@ -388,7 +467,7 @@ rq_status rq_load_json(const char *path, rq_index **out) {
     std::vector<uint32_t> off32(off.begin(), off.end()), ids32(ids.begin(), ids.end());
     std::vector<uint64_t> codes64(codes.begin(), codes.end());
     return from_arrays((uint32_t)dim, n, (uint32_t)k, base_rows.data(), P.data(), cent_rows.data(), off32.data(), ids32.data(),
-                       codes64.data(), fac.data(), out);
+                       codes64.data(), fac.data(), metric, out);
 }
 
 void rq_free(rq_index *idx) { delete idx; }
@@ -397,7 +476,7 @@ rq_status rq_info(const rq_index *idx, rq_info_t *out) {
     if (!idx || !out) return fail(RQ_ERR_INVALID, "null argument");
     rq_info_t full{};
     full.dim = idx->dim, full.k = idx->k, full.n = idx->n, full.max_list_len = idx->max_list_len, full.n_hbm = idx->n_dev;
-    full.split_rows = idx->split_rows ? 1u : 0u;
+    full.split_rows = idx->split_rows ? 1u : 0u, full.metric = idx->metric;
     return copy_out_sized(out, full);
 }
 
@@ -457,11 +536,15 @@ rq_status rq_coarse_topk_device(const rq_index *idx, const float *d_queries, uin
     const uint32_t chunk = (uint32_t)std::min<uint64_t>(nq, std::max<uint64_t>(1024, (1ull << 31) / std::max(kc, idx->k)));
     RQC(ws->y.ensure((uint64_t)chunk * dim));
     RQC(ws->dist.ensure((uint64_t)chunk * std::max(kc, idx->k)));
-    if (len != dim) RQC(ws->qpad.ensure((uint64_t)chunk * dim));
+    const bool cosine = idx->metric == RQ_METRIC_COSINE;
+    if (len != dim || cosine) RQC(ws->qpad.ensure((uint64_t)chunk * dim));
     for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
         const uint32_t m = std::min(chunk, nq - q0);
         const float *qp = d_queries + (uint64_t)q0 * len;
-        if (len != dim) {
+        if (cosine) {
+            launch_normalize(qp, m, len, dim, ws->qpad.p, st);
+            qp = ws->qpad.p;
+        } else if (len != dim) {
             pad_rows_kernel<<<ceil_div((uint64_t)m * dim, 256), 256, 0, st>>>(qp, ws->qpad.p, m, len, dim);
             qp = ws->qpad.p;
         }
@@ -1007,7 +1090,8 @@ rq_status rq_coarse_rank(const rq_index *idx, const float *queries, uint32_t nq,
     RQC(pd.alloc((uint64_t)nq * nprobe));
     RQC(pc.alloc((uint64_t)nq * nprobe));
     HIPC(hipMemcpy(dq.p, queries, (uint64_t)nq * len * 4, hipMemcpyHostToDevice));
-    pad_rows_kernel<<<ceil_div((uint64_t)nq * dim, 256), 256>>>(dq.p, qpad.p, nq, len, dim);
+    if (idx->metric == RQ_METRIC_COSINE) launch_normalize(dq.p, nq, len, dim, qpad.p, nullptr);
+    else pad_rows_kernel<<<ceil_div((uint64_t)nq * dim, 256), 256>>>(dq.p, qpad.p, nq, len, dim);
     launch_rotate(qpad.p, idx->P.p, y.p, nq, dim, nq >= 32, nullptr);
     coarse_dist_kernel<4><<<dim3(ceil_div(nq, 4), ceil_div(k, 256)), 256, 4 * dim * sizeof(float)>>>(
         idx->cent_t.p, y.p, dist.p, k, dim, nq, k);

@@ -143,43 +143,47 @@ class RaBitQ:
         self.dim, self.k, self.n, self.max_list_len = int(info.dim), int(info.k), int(info.n), int(info.max_list_len)
         self.n_hbm = int(info.n_hbm)      # raw vectors in HBM; the other n - n_hbm live in pinned host memory
         self.split_rows = bool(info.split_rows)   # raw vectors stored as two 16-bit planes per row (option "split_rows")
+        self.metric = "cosine" if info.metric == _lib.METRIC_COSINE else "l2"   # a cosine index normalises rows and queries itself
 
     # ---- RaBitQ::from_path (src/rabitq.rs:159) ------------------------------------------------
     @classmethod
-    def from_path(cls, base_path, centroid_path, orthogonal=None, seed: int = 0) -> "RaBitQ":
+    def from_path(cls, base_path, centroid_path, orthogonal=None, seed: int = 0, metric="l2") -> "RaBitQ":
         """Build from base.fvecs + centroids.fvecs.  `orthogonal` (dim x dim, P[r][c]) fixes the
-        rotation the reference draws unseeded (src/utils.rs:16-20); None = seeded Gaussian-QR."""
+        rotation the reference draws unseeded (src/utils.rs:16-20); None = seeded Gaussian-QR.
+        metric: "l2" (the reference) or "cosine": rows and queries are normalised on the GPU, distances are 2 - 2 cos."""
         h = C.c_void_p()
         P = _f32(orthogonal) if orthogonal is not None else None
-        check(lib().rq_build_from_path(os.fsencode(base_path), os.fsencode(centroid_path), _addr(P), seed, C.byref(h)))
+        check(lib().rq_build_from_path_metric(os.fsencode(base_path), os.fsencode(centroid_path), _addr(P), seed,
+                                              _lib.metric_id(metric), C.byref(h)))
         return cls(h)
 
     @classmethod
-    def build(cls, base, centroids, orthogonal=None, seed: int = 0) -> "RaBitQ":
+    def build(cls, base, centroids, orthogonal=None, seed: int = 0, metric="l2") -> "RaBitQ":
         """from_path on in-memory arrays (base n x d, centroids k x d)."""
         base, centroids = _f32(base), _f32(centroids)
         if base.ndim != 2 or centroids.ndim != 2 or base.shape[1] != centroids.shape[1]:
             raise _lib.RabitqError(-2, "base and centroids must be 2-D with the same dimension (rabitq.rs:165)")
         P = _f32(orthogonal) if orthogonal is not None else None
         h = C.c_void_p()
-        check(lib().rq_build(_addr(base), base.shape[0], base.shape[1], _addr(centroids), centroids.shape[0], _addr(P),
-                             seed, C.byref(h)))
+        check(lib().rq_build_metric(_addr(base), base.shape[0], base.shape[1], _addr(centroids), centroids.shape[0], _addr(P),
+                                    seed, _lib.metric_id(metric), C.byref(h)))
         return cls(h)
 
     @classmethod
     def build_device(cls, base_ptr: int, n: int, d: int, centroids_ptr: int, k: int, orthogonal=None,
-                     seed: int = 0) -> "RaBitQ":
+                     seed: int = 0, metric="l2") -> "RaBitQ":
         """Build from device-resident arrays (raw HIP device addresses, e.g. torch.Tensor.data_ptr())."""
         P = _f32(orthogonal) if orthogonal is not None else None
         h = C.c_void_p()
-        check(lib().rq_build_device(C.c_void_p(base_ptr), n, d, C.c_void_p(centroids_ptr), k, _addr(P), seed, C.byref(h)))
+        check(lib().rq_build_device_metric(C.c_void_p(base_ptr), n, d, C.c_void_p(centroids_ptr), k, _addr(P), seed,
+                                           _lib.metric_id(metric), C.byref(h)))
         return cls(h)
 
     @classmethod
     def builder(cls, n: int, d: int, centroids_ptr: int, k: int, orthogonal=None, seed: int = 0,
-                max_device_base_bytes: int = 0) -> "Builder":
+                max_device_base_bytes: int = 0, metric="l2") -> "Builder":
         """Streamed two-pass build for inputs that are not resident (include/rabitq_hip.h: rq_builder_*)."""
-        return Builder(n, d, centroids_ptr, k, orthogonal, seed, max_device_base_bytes)
+        return Builder(n, d, centroids_ptr, k, orthogonal, seed, max_device_base_bytes, metric)
 
     # ---- load_from_dir / dump_to_dir (src/rabitq.rs:84, :128) ---------------------------------
     @classmethod
@@ -202,16 +206,17 @@ class RaBitQ:
         check(lib().rq_dump_json(self._h, os.fsencode(path)))
 
     @classmethod
-    def from_arrays(cls, base, orthogonal, centroids, offsets, map_ids, codes, factors) -> "RaBitQ":
-        """From the reference's in-memory arrays (what load_from_dir produces)."""
+    def from_arrays(cls, base, orthogonal, centroids, offsets, map_ids, codes, factors, metric="l2") -> "RaBitQ":
+        """From the reference's in-memory arrays (what load_from_dir produces).  The arrays are taken as they are; metric="cosine"
+        only marks the index, so that its queries and added rows are normalised (`base` then holds normalised rows already)."""
         base, orthogonal, centroids, factors = _f32(base), _f32(orthogonal), _f32(centroids), _f32(factors)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
         map_ids = np.ascontiguousarray(map_ids, dtype=np.uint32)
         codes = np.ascontiguousarray(codes, dtype=np.uint64)
         h = C.c_void_p()
-        check(lib().rq_from_arrays(orthogonal.shape[0], map_ids.size, offsets.size - 1, _addr(base), _addr(orthogonal),
-                                   _addr(centroids), _addr(offsets), _addr(map_ids), _addr(codes), _addr(factors),
-                                   C.byref(h)))
+        check(lib().rq_from_arrays_metric(orthogonal.shape[0], map_ids.size, offsets.size - 1, _addr(base), _addr(orthogonal),
+                                          _addr(centroids), _addr(offsets), _addr(map_ids), _addr(codes), _addr(factors),
+                                          _lib.metric_id(metric), C.byref(h)))
         return cls(h)
 
     def rotate_device(self, x_ptr: int, n: int, out_ptr: int) -> float:
@@ -489,10 +494,11 @@ class RaBitQ:
 class Builder:
     """assign_chunk every row -> order() -> place_chunk every row -> finish() -> RaBitQ.  Chunks are device pointers."""
 
-    def __init__(self, n, d, centroids_ptr, k, orthogonal=None, seed=0, max_device_base_bytes=0):
+    def __init__(self, n, d, centroids_ptr, k, orthogonal=None, seed=0, max_device_base_bytes=0, metric="l2"):
         P = _f32(orthogonal) if orthogonal is not None else None
         self._b = C.c_void_p()
-        check(lib().rq_builder_create(n, d, C.c_void_p(centroids_ptr), k, _addr(P), seed, max_device_base_bytes, C.byref(self._b)))
+        check(lib().rq_builder_create_metric(n, d, C.c_void_p(centroids_ptr), k, _addr(P), seed, max_device_base_bytes,
+                                             _lib.metric_id(metric), C.byref(self._b)))
 
     def assign_chunk(self, rows_ptr: int, i0: int, m: int) -> None:
         check(lib().rq_builder_assign_chunk(self._b, C.c_void_p(rows_ptr), i0, m))

@@ -17,6 +17,26 @@ def rotate(x, orthogonal, use_mfma: bool = True):
     return out
 
 
+def normalize(x):
+    """N(x) row by row, the cosine metric's normalisation (include/rabitq_hip.h: rq_normalize): n x d -> n x ceil64(d)."""
+    x = _f32(x)
+    if x.ndim != 2:
+        raise ValueError("x must be 2-D (n x d)")
+    out = np.empty((x.shape[0], (x.shape[1] + 63) // 64 * 64), np.float32)
+    check(lib().rq_normalize(_addr(x), x.shape[0], x.shape[1], _addr(out)))
+    return out
+
+
+def normalize_device(x_ptr: int, n: int, d: int, out_ptr: int) -> None:
+    """rq_normalize on device-resident rows (raw addresses); out is n x ceil64(d)."""
+    check(lib().rq_normalize_device(C.c_void_p(x_ptr), n, d, C.c_void_p(out_ptr)))
+
+
+def cosine_similarity(dist):
+    """The cosine a cosine index's distance stands for: dist = 2 - 2 cos  ->  cos = 1 - dist / 2."""
+    return 1.0 - np.asarray(dist) / 2.0
+
+
 def quantize_pack(x_rot, centroids_rot):
     """labels, centroid distances, codes, factors for already-rotated vectors (rabitq.rs:203-229)."""
     x, c = _f32(x_rot), _f32(centroids_rot)
