@@ -130,7 +130,7 @@ struct ListTier {  // one per list
 // first the dim upper halves of the f32 words rounded to nearest (h = (bits + 0x8000) >> 16: a bf16 image of the row with relative
 // error <= 2^-8 per element), then the dim lower halves unchanged -- so that bits = (h << 16) + sext16(lo) restores every word
 // exactly.  The re-ranker reads the first plane alone (half the bytes), proves most survivors out of the top-k with it
-// (accurate_split_kernel, kernels_query.h) and fetches the second plane only for the rest.  Both tiers use the layout: over the
+// (accurate_split_kernel, kernels_rerank.h) and fetches the second plane only for the rest.  Both tiers use the layout: over the
 // host link the first plane alone is half the bytes as well.
 struct RowRef {
     const float *p;  // the row's 4*dim bytes

@@ -4,7 +4,7 @@
 // ------------------------------------------------------------------------------------------------
 // index construction helpers
 // ------------------------------------------------------------------------------------------------
-// fp16 shadow of the raw vectors (kernels_query.h: rerank pre-filter).  Only for untiered indexes, and only when the
+// fp16 shadow of the raw vectors (kernels_rerank.h: rerank pre-filter).  Only for untiered indexes, and only when the
 // 2*dim bytes per vector still leave the query workspaces their room; it costs one streaming pass over `base`.
 #define RQ_SHADOW_MIN_ROWS 1ull
 static std::atomic<int> g_rerank_shadow{2};  // shadow rows for the rerank pre-filter: 0 never, 1 fp16 when they fit, 2 8-bit (one affine map per list) when they fit
@@ -78,7 +78,7 @@ static rq_status derive_shadow_rows(rq_index *idx) {
     size_t free_b = 0, total_b = 0;
     HIPC(hipMemGetInfo(&free_b, &total_b));
     if (free_b < bytes + (48ull << 30) && bytes > (1ull << 30)) return RQ_OK;  // keep the survivor buffers their share
-    if (kind == 2) {  // one byte per dimension, per-list affine map, measured error bound (kernels_query.h)
+    if (kind == 2) {  // one byte per dimension, per-list affine map, measured error bound (kernels_rerank.h)
         if (idx->base_q8.alloc(total) != RQ_OK || idx->list_q8.alloc(std::max<uint32_t>(idx->k, 1)) != RQ_OK) {
             (void)hipGetLastError();
             idx->base_q8.release();

@@ -1930,30 +1930,7 @@ __global__ __launch_bounds__(256) void scan_dense_kernel(const uint32_t *__restr
     out[i] = rough_distance(s, factors[list_begin + i], lower, delta, sumq, ycd, sqrtf(ycd));
 }
 
-// ------------------------------------------------------------------------------------------------
-// Rerank distances (src/rerank.rs:85-90 -> src/simd.rs:14-73): accurate = ||base[pos] - q||^2 in
-// the ORIGINAL space, exact AVX2 order.  8 GPU lanes play the 8 AVX lanes of one candidate (lane l
-// runs the fused chain over elements 8c + l), so a wave reranks 8 survivors at a time and each
-// 32-byte sector of the 4*dim-byte row is consumed by exactly one load.  In the query pipeline this
-// is phase (A) of stage_finish_kernel.
-// ------------------------------------------------------------------------------------------------
-// flat variant for the per-stage test entry rq_rerank: positions given directly
-__global__ __launch_bounds__(256) void accurate_flat_kernel(const uint32_t *__restrict__ pos, uint32_t m,
-                                                            const BaseView base,
-                                                            const float *__restrict__ q, uint32_t dim,
-                                                            float *__restrict__ out) {
-    const uint32_t l = threadIdx.x & 7;
-    uint32_t i = blockIdx.x * 32 + (threadIdx.x >> 3);
-    if (i >= m) return;
-    const RowRef x = base.row(pos[i], dim);
-    float acc = 0.0f;
-    for (uint32_t c = 0; c < dim; c += 8) {
-        float d = rq_row_get(x, dim, c + l) - q[c + l];
-        acc = fmaf(d, d, acc);
-    }
-    acc = reduce8_lanes(acc);
-    if (l == 0) out[i] = acc;
-}
+#include "kernels_rerank.h"  // the exact re-rank stage: exact distances, shadow rows, pre-filter kernels
 
 // ------------------------------------------------------------------------------------------------
 // Restore the reference's visiting order among a query's survivors: ascending (slot, position)
@@ -2403,76 +2380,6 @@ __device__ __forceinline__ void replay_wave(const SurvRec *__restrict__ recs, co
     }
 }
 
-// exact f32 L2 of one SPLIT row (common.h: two 16-bit planes) against the query in LDS by a pair of lanes: the words are restored
-// exactly, the arithmetic is accurate_rows' (lane half hf = AVX lanes 4hf..4hf+3, chunks of 64 dimensions in order)
-__device__ __forceinline__ float exact_l2_pair_split(const float *__restrict__ row, const float *q_lds, uint32_t dim, uint32_t hf) {
-    const uint16_t *hp = reinterpret_cast<const uint16_t *>(row) + 4 * hf, *lp = hp + dim;
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-    for (uint32_t c = 0; c < dim; c += 64) {
-        uint2 hv[8], lv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) hv[u] = *reinterpret_cast<const uint2 *>(hp + c + 8 * u);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) lv[u] = *reinterpret_cast<const uint2 *>(lp + c + 8 * u);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const float4 qv = *reinterpret_cast<const float4 *>(q_lds + c + 8 * u + 4 * hf);
-            const float x0 = __builtin_bit_cast(float, (hv[u].x << 16) + (uint32_t)(int32_t)(int16_t)lv[u].x);
-            const float x1 = __builtin_bit_cast(float, (hv[u].x & 0xFFFF0000u) + (uint32_t)((int32_t)lv[u].x >> 16));
-            const float x2 = __builtin_bit_cast(float, (hv[u].y << 16) + (uint32_t)(int32_t)(int16_t)lv[u].y);
-            const float x3 = __builtin_bit_cast(float, (hv[u].y & 0xFFFF0000u) + (uint32_t)((int32_t)lv[u].y >> 16));
-            const float d0 = x0 - qv.x, d1 = x1 - qv.y, d2 = x2 - qv.z, d3 = x3 - qv.w;
-            a0 = fmaf(d0, d0, a0), a1 = fmaf(d1, d1, a1), a2 = fmaf(d2, d2, a2), a3 = fmaf(d3, d3, a3);
-        }
-    }
-    const float c0 = a0 + __shfl_xor(a0, 1, 2), c1 = a1 + __shfl_xor(a1, 1, 2);
-    const float c2 = a2 + __shfl_xor(a2, 1, 2), c3 = a3 + __shfl_xor(a3, 1, 2);
-    return (c0 + c1) + (c2 + c3);
-}
-
-// Exact f32 L2 of survivors recs[first], recs[first + step], ... against the query held in LDS
-// (src/rerank.rs:85-90; lane order of src/simd.rs:14-73).  TWO lanes per candidate: lane half hf carries
-// AVX lanes 4hf..4hf+3 (elements 8c + 4hf + 0..3, one 16-byte load per chunk); the fold
-// ((a0+a4)+(a1+a5)) + ((a2+a6)+(a3+a7)) needs one exchange between the two lanes.  A row is fetched 8
-// chunks (64 dimensions, 8 x 16 bytes per lane) at a time so that every lane keeps 8 loads in flight
-// (this is a random 512-byte-row gather: latency-bound unless enough bytes are outstanding).
-__device__ __forceinline__ void accurate_rows(SurvRec *__restrict__ recs, uint32_t n, const BaseView &base,
-                                              const float *q_lds, uint32_t dim, uint32_t first, uint32_t step,
-                                              const uint32_t *__restrict__ probe_row /* the query's probed lists, by slot */) {
-    const uint32_t hf = threadIdx.x & 1;
-    for (uint32_t i = first; i < n; i += step) {
-        const float *x;
-        if (base.host == nullptr && !base.split) {
-            x = base.dev + (uint64_t)recs[i].pos * dim + 4 * hf;
-        } else {  // tiered: the survivor's slot names its list, the list's tier record places the row (HBM or host link)
-            const RowRef rr = base.row_of_slot(recs[i].pos, probe_row, recs[i].slot, dim);
-            if (rr.split) {  // (a pair of lanes shares its survivor: the branch does not split the pair)
-                const float r = exact_l2_pair_split(rr.p, q_lds, dim, hf);
-                if (hf == 0) recs[i].accurate = r;
-                continue;
-            }
-            x = rr.p + 4 * hf;
-        }
-        float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-        for (uint32_t c = 0; c < dim; c += 64) {  // dim is a multiple of 64
-            float4 xv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) xv[u] = *reinterpret_cast<const float4 *>(x + c + 8 * u);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float4 qv = *reinterpret_cast<const float4 *>(q_lds + c + 8 * u + 4 * hf);
-                const float d0 = xv[u].x - qv.x, d1 = xv[u].y - qv.y, d2 = xv[u].z - qv.z, d3 = xv[u].w - qv.w;
-                a0 = fmaf(d0, d0, a0), a1 = fmaf(d1, d1, a1), a2 = fmaf(d2, d2, a2), a3 = fmaf(d3, d3, a3);
-            }
-        }
-        // c_i = a_i + a_{i+4}: the partner lane holds the other half (commutative, so both lanes agree)
-        const float c0 = a0 + __shfl_xor(a0, 1, 2), c1 = a1 + __shfl_xor(a1, 1, 2);
-        const float c2 = a2 + __shfl_xor(a2, 1, 2), c3 = a3 + __shfl_xor(a3, 1, 2);
-        const float r = (c0 + c1) + (c2 + c3);
-        if (hf == 0) recs[i].accurate = r;
-    }
-}
-
 // One block per query finishes a stage: (A) exact rerank distances of the stage's survivors
 // (src/rerank.rs:85-90, 8 lanes = the 8 AVX lanes of src/simd.rs:14-73), (B) sort of the run
 // directory into the reference's visiting order, (C) wave 0 replays the ranker.
@@ -2535,537 +2442,6 @@ __global__ void order_scatter_kernel(const uint32_t *__restrict__ probe_cluster,
     const uint32_t c = probe_cluster[(uint64_t)b * nprobe];
     const uint32_t g = c < k ? c : k;
     order[start[g] + atomicAdd(&cursor[g], 1u)] = b;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Rerank pre-filter: an fp16 shadow of the raw vectors (derived state, half the bytes of a row).
-//
-// The re-ranker's exact distance only matters when it can pass `accurate < threshold` (src/rerank.rs:91): a
-// survivor whose exact distance PROVABLY is >= the threshold its stage started with (the threshold only falls)
-// is rejected by the reference whatever the exact value is.  For such a survivor the 4*dim-byte row is never
-// fetched: the 2*dim-byte shadow row x~ gives
-//     ||x - q||  >=  ||x~ - q|| - ||x - x~||,      ||x - x~|| <= 2^-11 ||x|| + sqrt(dim) 2^-25
-// (fp16 round-to-nearest: relative 2^-11 per normal element, absolute 2^-25 per subnormal one; an element beyond
-// the fp16 range becomes inf and disables the test), and the reference's f32 evaluation of ||x - q||^2
-// (src/simd.rs:14-73: dim/8 fused multiply-adds per AVX lane + 3 adds, non-negative terms) is at least
-// (1 - (dim/8 + 5) 2^-24) of the real value.  Every quantity below is rounded against the test (factors
-// 1 -/+ eps with eps = (dim/4 + 64) 2^-24), so the bound can only be lower than the exact f32 result: a rejected
-// survivor gets accurate = +inf, which fails `accurate < threshold` exactly as its exact value would.  Everything
-// else goes through the exact path unchanged; results are bit-identical with and without the shadow.
-// ------------------------------------------------------------------------------------------------
-typedef _Float16 rq_half8 __attribute__((ext_vector_type(8)));
-
-// 8 consecutive elements per thread; total = n * dim (a multiple of 64)
-__global__ __launch_bounds__(256) void half_rows_kernel(const float *__restrict__ base, uint64_t total,
-                                                        _Float16 *__restrict__ out) {
-    for (uint64_t i = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 8; i < total; i += (uint64_t)gridDim.x * 2048) {
-        const float4 a = *reinterpret_cast<const float4 *>(base + i), b = *reinterpret_cast<const float4 *>(base + i + 4);
-        rq_half8 h;
-        h[0] = (_Float16)a.x, h[1] = (_Float16)a.y, h[2] = (_Float16)a.z, h[3] = (_Float16)a.w;
-        h[4] = (_Float16)b.x, h[5] = (_Float16)b.y, h[6] = (_Float16)b.z, h[7] = (_Float16)b.w;
-        *reinterpret_cast<rq_half8 *>(out + i) = h;
-    }
-}
-
-// exact f32 L2 of one row against the query in LDS by a PAIR of lanes (see accurate_rows); x already offset by 4*hf
-__device__ __forceinline__ float exact_l2_pair(const float *__restrict__ x, const float *q_lds, uint32_t dim, uint32_t hf) {
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-    for (uint32_t c = 0; c < dim; c += 64) {
-        float4 xv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) xv[u] = *reinterpret_cast<const float4 *>(x + c + 8 * u);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const float4 qv = *reinterpret_cast<const float4 *>(q_lds + c + 8 * u + 4 * hf);
-            const float d0 = xv[u].x - qv.x, d1 = xv[u].y - qv.y, d2 = xv[u].z - qv.z, d3 = xv[u].w - qv.w;
-            a0 = fmaf(d0, d0, a0), a1 = fmaf(d1, d1, a1), a2 = fmaf(d2, d2, a2), a3 = fmaf(d3, d3, a3);
-        }
-    }
-    const float c0 = a0 + __shfl_xor(a0, 1, 2), c1 = a1 + __shfl_xor(a1, 1, 2);
-    const float c2 = a2 + __shfl_xor(a2, 1, 2), c3 = a3 + __shfl_xor(a3, 1, 2);
-    return (c0 + c1) + (c2 + c3);
-}
-
-// grid (gx, nq), block 256 = 128 survivors per round, two lanes each.  Round: shadow-row test of 128 survivors; the
-// ones it cannot reject queue up in LDS and are re-ranked exactly 128 at a time, so both phases keep every lane busy.
-__global__ __launch_bounds__(256) void accurate_filtered_kernel(SurvRec *__restrict__ surv,
-                                                                const unsigned long long *__restrict__ surv_cnt,
-                                                                const QSeg seg, const float *__restrict__ base,
-                                                                const _Float16 *__restrict__ base_h,
-                                                                const float *__restrict__ qpad, uint32_t dim,
-                                                                const uint32_t *__restrict__ order,
-                                                                const float *__restrict__ thr_start,
-                                                                uint32_t *__restrict__ nshadow) {
-    extern __shared__ __attribute__((aligned(16))) float acc_q[];  // dim floats (the padded query)
-    __shared__ uint32_t queue[256];
-    __shared__ uint32_t qn;
-    const uint32_t b = order ? order[blockIdx.y] : blockIdx.y;
-    const uint32_t n = (uint32_t)surv_cnt[b];
-    if (n > seg.capof(b) || n == 0) return;  // overflowed: this query is re-run with a larger buffer
-    for (uint32_t c = threadIdx.x * 4; c < dim; c += 1024)
-        *reinterpret_cast<float4 *>(acc_q + c) = *reinterpret_cast<const float4 *>(qpad + (uint64_t)b * dim + c);
-    if (threadIdx.x == 0) qn = 0;
-    __syncthreads();
-    SurvRec *recs = surv + seg.at(b);
-    const uint32_t hf = threadIdx.x & 1, pair = threadIdx.x >> 1;
-    const float thr = thr_start[b];
-    const bool test = thr > 1e-30f && thr < 3.0e38f;  // a finite, normal threshold (false for NaN / inf: everything is exact)
-    const float eps = (float)(dim / 4 + 64) * 5.9604645e-8f, down = 1.0f - eps, up = 1.0f + eps;
-    const float abs_err = sqrtf((float)dim) * 3.0e-8f;  // sqrt(dim) * 2^-25, rounded up
-    uint32_t rejected = 0;
-    for (uint32_t i0 = blockIdx.x * 128; i0 < n; i0 += gridDim.x * 128) {
-        const uint32_t i = i0 + pair;
-        bool exact = i < n;
-        if (exact && test) {
-            const _Float16 *x = base_h + (uint64_t)recs[i].pos * dim + 8 * hf;
-            float d0 = 0.0f, d1 = 0.0f, n0 = 0.0f, n1 = 0.0f;
-            for (uint32_t c = 0; c < dim; c += 128) {  // 256 bytes of the row: 8 x 16 bytes per lane in flight
-                rq_half8 xv[8];
-                const bool full = dim - c >= 128;  // dim is a multiple of 64: the last chunk may be a half one
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-                    if (u < 4 || full) xv[u] = *reinterpret_cast<const rq_half8 *>(x + c + 16 * u);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    if (!(u < 4 || full)) continue;
-                    const float4 qa = *reinterpret_cast<const float4 *>(acc_q + c + 16 * u + 8 * hf);
-                    const float4 qb = *reinterpret_cast<const float4 *>(acc_q + c + 16 * u + 8 * hf + 4);
-                    const float x0 = (float)xv[u][0], x1 = (float)xv[u][1], x2 = (float)xv[u][2], x3 = (float)xv[u][3];
-                    const float x4 = (float)xv[u][4], x5 = (float)xv[u][5], x6 = (float)xv[u][6], x7 = (float)xv[u][7];
-                    const float e0 = x0 - qa.x, e1 = x1 - qa.y, e2 = x2 - qa.z, e3 = x3 - qa.w;
-                    const float e4 = x4 - qb.x, e5 = x5 - qb.y, e6 = x6 - qb.z, e7 = x7 - qb.w;
-                    d0 = fmaf(e0, e0, d0), d1 = fmaf(e1, e1, d1), d0 = fmaf(e2, e2, d0), d1 = fmaf(e3, e3, d1);
-                    d0 = fmaf(e4, e4, d0), d1 = fmaf(e5, e5, d1), d0 = fmaf(e6, e6, d0), d1 = fmaf(e7, e7, d1);
-                    n0 = fmaf(x0, x0, n0), n1 = fmaf(x1, x1, n1), n0 = fmaf(x2, x2, n0), n1 = fmaf(x3, x3, n1);
-                    n0 = fmaf(x4, x4, n0), n1 = fmaf(x5, x5, n1), n0 = fmaf(x6, x6, n0), n1 = fmaf(x7, x7, n1);
-                }
-            }
-            float dt = d0 + d1, nx = n0 + n1;
-            dt += __shfl_xor(dt, 1, 2), nx += __shfl_xor(nx, 1, 2);
-#ifdef RQ_EXP_SHADOW_SLACK  // developer experiment (scripts/exp/shadow_slack.sh, rerank_shadow = 1): what a coarser shadow would still reject
-            const float err = (sqrtf(nx) * up) * 4.8877e-4f + abs_err + RQ_EXP_SHADOW_SLACK;
-#else
-            const float err = (sqrtf(nx) * up) * 4.8877e-4f + abs_err;  // >= 2^-11 (1 + 2^-10) ||x~|| + sqrt(dim) 2^-25 >= ||x - x~||
-#endif
-            const float t = sqrtf(dt * down) * down - err * up;
-            if (t > 0.0f && (t * t) * (down * down) > thr) {  // false for NaN
-                exact = false;
-                if (hf == 0) recs[i].accurate = __builtin_inff();
-                ++rejected;
-            }
-        }
-        if (exact && hf == 0) queue[atomicAdd(&qn, 1u)] = i;  // at most 127 waiting + 128 new
-        __syncthreads();
-        const uint32_t waiting = qn;  // the same value in every thread: nobody touches qn before the next barrier
-        __syncthreads();
-        if (waiting >= 128) {
-            const uint32_t j = queue[waiting - 128 + pair];
-            const float r = exact_l2_pair(base + (uint64_t)recs[j].pos * dim + 4 * hf, acc_q, dim, hf);
-            if (hf == 0) recs[j].accurate = r;
-            if (threadIdx.x == 0) qn = waiting - 128;
-            __syncthreads();  // the queue's top 128 entries are free again, qn is set
-        }
-    }
-    const uint32_t waiting = qn;
-    if (pair < waiting) {
-        const uint32_t j = queue[pair];
-        const float r = exact_l2_pair(base + (uint64_t)recs[j].pos * dim + 4 * hf, acc_q, dim, hf);
-        if (hf == 0) recs[j].accurate = r;
-    }
-    uint32_t rj = hf == 0 ? rejected : 0u;  // per-query counter (one address per query: no hot spot)
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) rj += __shfl_xor(rj, o, 64);
-    if ((threadIdx.x & 63) == 0 && rj) atomicAdd(&nshadow[b], rj);
-}
-
-#define RQ_ACC8_LDS_PROBES 1024u  // probe lists whose maps / tier records the re-rankers stage in LDS (16 B each)
-// ------------------------------------------------------------------------------------------------
-// Rerank over SPLIT rows (common.h: indexes whose raw vectors leave no room for shadow rows -- tiered ones, and untiered ones that
-// fill most of the HBM): the
-// first plane of a split row IS one: x^ = the row rounded to bf16, ||x - x^|| <= 2^-8 / (1 - 2^-8) ||x^|| (+ 2^-134 per subnormal
-// element).  Same test as accurate_filtered_kernel's with that error term; a survivor it cannot reject has its second plane fetched
-// and the words restored exactly, so results are bit-identical to the plain layout's.  Host-tier rows are split rows too (half
-// the bytes over the host link for the ones the test rejects).  2*dim bytes per survivor instead of 4*dim for the ones the test rejects.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void accurate_split_kernel(SurvRec *__restrict__ surv,
-                                                             const unsigned long long *__restrict__ surv_cnt,
-                                                             const QSeg seg, const BaseView base,
-                                                             const float *__restrict__ qpad, uint32_t dim,
-                                                             const uint32_t *__restrict__ order,
-                                                             const float *__restrict__ thr_start,
-                                                             const uint32_t *__restrict__ probe_cluster, uint32_t nprobe,
-                                                             uint32_t *__restrict__ nshadow) {
-    extern __shared__ __attribute__((aligned(16))) float acc_q[];  // dim floats (the padded query), then -- when they fit -- the nprobe lists' tier records
-    __shared__ uint32_t queue[256];
-    __shared__ uint32_t qn;
-    const uint32_t b = order ? order[blockIdx.y] : blockIdx.y;
-    const uint32_t n = (uint32_t)surv_cnt[b];
-    if (n > seg.capof(b) || n == 0) return;  // overflowed: this query is re-run with a larger buffer
-    SurvRec *recs = surv + seg.at(b);
-    const uint32_t *probe_row = probe_cluster + (uint64_t)b * nprobe;
-    const uint32_t hf = threadIdx.x & 1, pair = threadIdx.x >> 1;
-    // a chain of dependent gathers (survivor record -> its list's tier record -> the row): the first round's records are requested
-    // before anything else, every later round's while the current one is worked on, the tier records are staged in LDS once per block
-    const uint32_t i_first = blockIdx.x * 128;
-    SurvRec nxt = recs[i_first + pair < n ? i_first + pair : 0u];
-    ListTier *ltl = reinterpret_cast<ListTier *>(acc_q + dim);
-    const bool lt_lds = base.host != nullptr && nprobe <= RQ_ACC8_LDS_PROBES;  // (launch: LDS for them only then; an untiered index has no tier records)
-    for (uint32_t c = threadIdx.x * 4; c < dim; c += 1024)
-        *reinterpret_cast<float4 *>(acc_q + c) = *reinterpret_cast<const float4 *>(qpad + (uint64_t)b * dim + c);
-    if (lt_lds)
-        for (uint32_t sl = threadIdx.x; sl < nprobe; sl += 256)  // (a padded probe slot -- id 0xFFFFFFFF, "no list" -- has no survivors and no record)
-            ltl[sl] = probe_row[sl] < base.k ? base.lt[probe_row[sl]] : ListTier{0u, 0u, 0u, 0u};
-    if (threadIdx.x == 0) qn = 0;
-    __syncthreads();
-    const float thr = thr_start ? thr_start[b] : __builtin_inff();
-    const bool test = thr > 1e-30f && thr < 3.0e38f;  // a finite, normal threshold (false for NaN / inf: everything is exact)
-    const float eps = (float)(dim / 4 + 64) * 5.9604645e-8f, down = 1.0f - eps, up = 1.0f + eps;
-    auto row_of = [&](const SurvRec &r) { return lt_lds ? base.row_in_list(r.pos, ltl[r.slot], dim) : base.row_of_slot(r.pos, probe_row, r.slot, dim); };
-    auto exact_of = [&](uint32_t j) {
-        const RowRef rr = row_of(recs[j]);
-        const float r = rr.split ? exact_l2_pair_split(rr.p, acc_q, dim, hf) : exact_l2_pair(rr.p + 4 * hf, acc_q, dim, hf);
-        if (hf == 0) recs[j].accurate = r;
-    };
-    uint32_t rejected = 0;
-    for (uint32_t i0 = i_first; i0 < n; i0 += gridDim.x * 128) {
-        const uint32_t i = i0 + pair;
-        bool exact = i < n;
-        const SurvRec cur = nxt;
-        {  // the next round's record (clamped: the last prefetch re-reads record 0)
-            const uint32_t jn = i + gridDim.x * 128;
-            nxt = recs[jn < n ? jn : 0u];
-        }
-        if (exact && test) {
-            const RowRef rr = row_of(cur);
-#ifdef RQ_EXP_COUNT_HOST  // developer experiment: the counter reports the host-tier survivors instead of the rejected ones
-            if (!rr.split) ++rejected;
-#endif
-            if (rr.split) {
-                const uint16_t *x = reinterpret_cast<const uint16_t *>(rr.p) + 8 * hf;
-                float d0 = 0.0f, d1 = 0.0f, n0 = 0.0f, n1 = 0.0f;
-                for (uint32_t c = 0; c < dim; c += 128) {  // 256 bytes of the plane: 8 x 16 bytes per lane in flight
-                    uint4 xv[8];
-                    const bool full = dim - c >= 128;  // dim is a multiple of 64: the last chunk may be a half one
-#pragma unroll
-                    for (int u = 0; u < 8; ++u)
-                        if (u < 4 || full) xv[u] = *reinterpret_cast<const uint4 *>(x + c + 16 * u);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        if (!(u < 4 || full)) continue;
-                        const float4 qa = *reinterpret_cast<const float4 *>(acc_q + c + 16 * u + 8 * hf);
-                        const float4 qb = *reinterpret_cast<const float4 *>(acc_q + c + 16 * u + 8 * hf + 4);
-                        const float x0 = __builtin_bit_cast(float, xv[u].x << 16), x1 = __builtin_bit_cast(float, xv[u].x & 0xFFFF0000u);
-                        const float x2 = __builtin_bit_cast(float, xv[u].y << 16), x3 = __builtin_bit_cast(float, xv[u].y & 0xFFFF0000u);
-                        const float x4 = __builtin_bit_cast(float, xv[u].z << 16), x5 = __builtin_bit_cast(float, xv[u].z & 0xFFFF0000u);
-                        const float x6 = __builtin_bit_cast(float, xv[u].w << 16), x7 = __builtin_bit_cast(float, xv[u].w & 0xFFFF0000u);
-                        const float e0 = x0 - qa.x, e1 = x1 - qa.y, e2 = x2 - qa.z, e3 = x3 - qa.w;
-                        const float e4 = x4 - qb.x, e5 = x5 - qb.y, e6 = x6 - qb.z, e7 = x7 - qb.w;
-                        d0 = fmaf(e0, e0, d0), d1 = fmaf(e1, e1, d1), d0 = fmaf(e2, e2, d0), d1 = fmaf(e3, e3, d1);
-                        d0 = fmaf(e4, e4, d0), d1 = fmaf(e5, e5, d1), d0 = fmaf(e6, e6, d0), d1 = fmaf(e7, e7, d1);
-                        n0 = fmaf(x0, x0, n0), n1 = fmaf(x1, x1, n1), n0 = fmaf(x2, x2, n0), n1 = fmaf(x3, x3, n1);
-                        n0 = fmaf(x4, x4, n0), n1 = fmaf(x5, x5, n1), n0 = fmaf(x6, x6, n0), n1 = fmaf(x7, x7, n1);
-                    }
-                }
-                float dt = d0 + d1, nx = n0 + n1;
-                dt += __shfl_xor(dt, 1, 2), nx += __shfl_xor(nx, 1, 2);
-                // >= 2^-8 / (1 - 2^-8) ||x^|| + sqrt(dim) 2^-134 >= ||x - x^||  (3.9216e-3 > 2^-8 / (1 - 2^-8) = 3.92157e-3; an
-                // x^ with an infinite element makes err infinite and t NaN or -inf: no rejection)
-                const float err = (sqrtf(nx) * up) * 3.9216e-3f + 1.0e-37f;
-                const float t = sqrtf(dt * down) * down - err * up;
-                if (t > 0.0f && (t * t) * (down * down) > thr) {  // false for NaN
-                    exact = false;
-                    if (hf == 0) recs[i].accurate = __builtin_inff();
-#ifndef RQ_EXP_COUNT_HOST
-                    ++rejected;
-#endif
-                }
-            }
-        }
-        if (exact && hf == 0) queue[atomicAdd(&qn, 1u)] = i;  // at most 127 waiting + 128 new
-        __syncthreads();
-        const uint32_t waiting = qn;  // the same value in every thread: nobody touches qn before the next barrier
-        __syncthreads();
-        if (waiting >= 128) {
-            exact_of(queue[waiting - 128 + pair]);
-            if (threadIdx.x == 0) qn = waiting - 128;
-            __syncthreads();  // the queue's top 128 entries are free again, qn is set
-        }
-    }
-    const uint32_t waiting = qn;
-    if (pair < waiting) exact_of(queue[pair]);
-    uint32_t rj = hf == 0 ? rejected : 0u;  // per-query counter (one address per query: no hot spot)
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) rj += __shfl_xor(rj, o, 64);
-    if ((threadIdx.x & 63) == 0 && rj) atomicAdd(&nshadow[b], rj);
-}
-
-// ------------------------------------------------------------------------------------------------
-// The 8-bit shadow (round 4): one BYTE per dimension instead of the fp16 shadow's two.
-//
-// Every list c has an affine map of its own, x^_i = lo_c + s_c * code_i with lo_c = the smallest and lo_c + 255 s_c = the largest
-// coordinate of any of its rows (q8_range_kernel), so no coordinate clips and |x_i - x^_i| <= s_c / 2 up to rounding.  The bound
-// the pre-filter needs, ||x - x^|| over the rows of the list, is not derived but MEASURED while the codes are written
-// (q8_encode_kernel: the largest row norm of x - fmaf(s_c, code, lo_c) over the list, x^ evaluated exactly as the re-ranker evaluates
-// it -- round 5; for dimensions whose rows do not map onto a power-of-two thread group: the largest |x_i - x^_i| times sqrt(dim)).
-// The test itself is accurate_filtered_kernel's: d^ = ||x^ - q|| in f32, t = d^ (1 - eps) - err, and a survivor is
-// dropped only if t^2 (1 - eps) still exceeds the stage's threshold -- the f32 row is then never read (128 instead of 256 shadow
-// bytes per survivor at dim 128; measured on the benchmark mixture: 86 % of the survivors rejected against the fp16 shadow's 92 %).
-// A list with a non-finite coordinate gets err = inf: nothing of it is ever rejected.
-// ------------------------------------------------------------------------------------------------
-// whether q8_encode_kernel measures row norms of the error (list_q8[c].w) for this dimension: its dim / 16 threads per row must be
-// a power-of-two group inside one wave
-__host__ __device__ __forceinline__ bool q8_row_norms(uint32_t dim) {
-    const uint32_t tpr = dim / 16;
-    return tpr >= 1 && tpr <= 64 && (tpr & (tpr - 1)) == 0;
-}
-// one block per list: lo, s (and the error accumulator cleared)
-__global__ __launch_bounds__(256) void q8_range_kernel(const float *__restrict__ base, const uint32_t *__restrict__ offsets, uint32_t dim,
-                                                       float4 *__restrict__ list_q8) {
-    __shared__ float smn[4], smx[4];
-    __shared__ uint32_t sbad[4];
-    const uint32_t c = blockIdx.x;
-    const uint64_t e0 = (uint64_t)offsets[c] * dim, e1 = (uint64_t)offsets[c + 1] * dim;
-    float mn = 3.402823466e+38f, mx = -3.402823466e+38f;
-    uint32_t bad = 0;
-    for (uint64_t e = e0 + threadIdx.x * 4ull; e < e1; e += 1024) {  // dim is a multiple of 64: rows are whole float4s
-        const float4 v = *reinterpret_cast<const float4 *>(base + e);
-        const float ve[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (!(fabsf(ve[i]) < 3.0e38f)) bad = 1;  // NaN / inf / huge
-            mn = ve[i] < mn ? ve[i] : mn;
-            mx = ve[i] > mx ? ve[i] : mx;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const float a = __shfl_xor(mn, o, 64), b = __shfl_xor(mx, o, 64);
-        mn = a < mn ? a : mn, mx = b > mx ? b : mx;
-        bad |= __shfl_xor(bad, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) smn[threadIdx.x >> 6] = mn, smx[threadIdx.x >> 6] = mx, sbad[threadIdx.x >> 6] = bad;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) mn = smn[w] < mn ? smn[w] : mn, mx = smx[w] > mx ? smx[w] : mx, bad |= sbad[w];
-        float lo = mn, sc = (mx - mn) * (1.0f / 255.0f);
-        if (e1 == e0) lo = 0.0f, sc = 1.0f;
-        if (!(sc > 0.0f)) sc = 1.0f;                       // all coordinates equal (or an empty list): code 0 everywhere
-        if (!(sc < 3.0e38f) || !(fabsf(lo) < 3.0e38f)) bad = 1;
-        // .z: the largest |x_i - x^_i| of the list as the bits of a non-negative float (atomicMax by q8_encode_kernel); inf: never reject
-        list_q8[c] = make_float4(bad ? 0.0f : lo, bad ? 1.0f : sc, bad ? __builtin_inff() : 0.0f, bad ? __builtin_inff() : 0.0f);  // .w: the largest row norm of the error, likewise
-    }
-}
-// grid (ceil(longest list / 256), k): 256 rows of one list per block; dim / 16 threads per row, 16 codes (one 16-byte store) each
-__global__ __launch_bounds__(256) void q8_encode_kernel(const float *__restrict__ base, const uint32_t *__restrict__ offsets, uint32_t dim,
-                                                        float4 *__restrict__ list_q8, uint8_t *__restrict__ out) {
-    __shared__ float smax[4], snorm[4];
-    const uint32_t c = blockIdx.y, r0 = offsets[c] + blockIdx.x * 256u, r1 = offsets[c + 1];
-    if (r0 >= r1) return;
-    const float4 par = list_q8[c];
-    const float lo = par.x, sc = par.y, inv = 1.0f / sc;
-    const uint32_t tpr = dim / 16, rows_per_pass = 256 / tpr;  // dim <= 4096
-    const uint32_t rr = threadIdx.x / tpr, g = threadIdx.x - rr * tpr;
-    const bool row_norms = q8_row_norms(dim);  // the tpr threads of a row are an aligned power-of-two group of one wave
-    float emax = 0.0f, nmax = 0.0f;
-    for (uint32_t r = r0 + rr; r < r1 && r < r0 + 256u && rr < rows_per_pass; r += rows_per_pass) {
-        float e2 = 0.0f;
-        const float *x = base + (uint64_t)r * dim + 16 * g;
-        uint32_t w[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float4 v = *reinterpret_cast<const float4 *>(x + 4 * u);
-            const float ve[4] = {v.x, v.y, v.z, v.w};
-            w[u] = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float t = rintf((ve[i] - lo) * inv);
-                t = t < 0.0f ? 0.0f : (t > 255.0f ? 255.0f : t);  // (NaN: a list with one has err = inf already)
-                const uint32_t code = (uint32_t)t;
-                const float e = fabsf(ve[i] - fmaf(sc, (float)code, lo));  // exactly the re-ranker's x^
-                emax = (e > emax || !(e < 3.0e38f)) ? (e < 3.0e38f ? e : __builtin_inff()) : emax;
-                e2 = fmaf(e, e, e2);
-                w[u] |= code << (8 * i);
-            }
-        }
-        *reinterpret_cast<uint4 *>(out + (uint64_t)r * dim + 16 * g) = make_uint4(w[0], w[1], w[2], w[3]);
-        if (row_norms) {  // ||x - x^||^2 of the row: the group's partial sums folded (every thread of the group is in this iteration)
-            for (uint32_t o = tpr >> 1; o >= 1; o >>= 1) e2 += __shfl_xor(e2, (int)o, 64);
-            nmax = (e2 > nmax || !(e2 < 3.0e38f)) ? (e2 < 3.0e38f ? e2 : __builtin_inff()) : nmax;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const float a = __shfl_xor(emax, o, 64), b = __shfl_xor(nmax, o, 64);
-        emax = a > emax ? a : emax, nmax = b > nmax ? b : nmax;
-    }
-    if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = emax, snorm[threadIdx.x >> 6] = nmax;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w2 = 1; w2 < 4; ++w2) emax = smax[w2] > emax ? smax[w2] : emax, nmax = snorm[w2] > nmax ? snorm[w2] : nmax;
-        atomicMax(reinterpret_cast<unsigned int *>(&list_q8[c].z), __builtin_bit_cast(unsigned int, emax));  // non-negative floats order as their bits
-        // .w: the largest ||x - x^|| over the list's rows, rounded up past the f32 evaluation above (dim fused multiply-adds + a sqrt)
-        const float nrm = sqrtf(nmax) * (1.0f + (float)(dim + 8) * 6.0e-8f);
-        if (row_norms) atomicMax(reinterpret_cast<unsigned int *>(&list_q8[c].w), __builtin_bit_cast(unsigned int, nrm));
-    }
-}
-
-// accurate_filtered_kernel with the 8-bit shadow: grid (gx, nq), block 256 = 256 survivors per round, two lanes each and two
-// survivors per lane pair (lane half hf takes the 16-dimension groups 2u + hf of a row; both survivors' pieces are requested
-// before either is used: a 128-byte row is four 16-byte loads per lane, too few in flight to keep the memory busy one row at a time)
-#ifndef RQ_ACC8_WAVES
-#define RQ_ACC8_WAVES 4  // waves per SIMD the register budget is cut for (round 4: 132 registers, three waves; four: rerank 4.76 -> 4.35 ms per step)
-#endif
-__global__ __launch_bounds__(256, RQ_ACC8_WAVES) void accurate_filtered8_kernel(SurvRec *__restrict__ surv,
-                                                                 const unsigned long long *__restrict__ surv_cnt,
-                                                                 const QSeg seg, const float *__restrict__ base,
-                                                                 const uint8_t *__restrict__ base_q8, const float4 *__restrict__ list_q8,
-                                                                 const float *__restrict__ qpad, uint32_t dim,
-                                                                 const uint32_t *__restrict__ order,
-                                                                 const float *__restrict__ thr_start,
-                                                                 const uint32_t *__restrict__ probe_cluster, uint32_t nprobe,
-                                                                 uint32_t *__restrict__ nshadow, uint32_t nlists) {
-    extern __shared__ __attribute__((aligned(16))) float acc_q[];  // dim floats (the padded query), then -- when they fit -- the nprobe lists' (lo, s, err)
-    __shared__ uint32_t queue[512];
-    __shared__ uint32_t qn;
-    const uint32_t b = order ? order[blockIdx.y] : blockIdx.y;
-    const uint32_t n = (uint32_t)surv_cnt[b];
-    if (n > seg.capof(b) || n == 0) return;  // overflowed: this query is re-run with a larger buffer
-    SurvRec *recs = surv + seg.at(b);
-    const uint32_t hf = threadIdx.x & 1, pair = threadIdx.x >> 1;
-    // The kernel is a chain of dependent gathers (survivor record -> its list's map and its shadow row -> the f32 row of the few that
-    // stay), i.e. bound by how many of them are in flight: the first round's records are requested before anything else, every later
-    // round's while the current one is being worked on, and the lists' maps are staged in LDS once per block (one dependent round
-    // trip less per round: probe list -> map was two)
-    const uint32_t i_first = blockIdx.x * 256;
-    SurvRec nxt[2];
-    nxt[0] = recs[i_first + pair < n ? i_first + pair : 0u], nxt[1] = recs[i_first + 128 + pair < n ? i_first + 128 + pair : 0u];
-    const uint32_t *pc = probe_cluster + (uint64_t)b * nprobe;
-    float4 *lpar = reinterpret_cast<float4 *>(acc_q + dim);
-    const bool par_lds = nprobe <= RQ_ACC8_LDS_PROBES;  // (launch: LDS for them only then)
-    for (uint32_t c = threadIdx.x * 4; c < dim; c += 1024)
-        *reinterpret_cast<float4 *>(acc_q + c) = *reinterpret_cast<const float4 *>(qpad + (uint64_t)b * dim + c);
-    if (par_lds)
-        for (uint32_t sl = threadIdx.x; sl < nprobe; sl += 256)  // (a padded probe slot -- id 0xFFFFFFFF, "no list" -- has no survivors and no map)
-            lpar[sl] = pc[sl] < nlists ? list_q8[pc[sl]] : make_float4(0.0f, 1.0f, __builtin_inff(), __builtin_inff());
-    if (threadIdx.x == 0) qn = 0;
-    __syncthreads();
-    const float thr = thr_start[b];
-    const bool test = thr > 1e-30f && thr < 3.0e38f;  // a finite, normal threshold (false for NaN / inf: everything is exact)
-    const float eps = (float)(dim / 4 + 64) * 5.9604645e-8f, down = 1.0f - eps, up = 1.0f + eps;
-    const float sqd = sqrtf((float)dim) * 1.001f;
-    const bool rown = q8_row_norms(dim);
-    const uint32_t ngrp = dim / 16;
-    uint32_t rejected = 0;
-    for (uint32_t i0 = i_first; i0 < n; i0 += gridDim.x * 256) {
-        uint32_t iv[2] = {i0 + pair, i0 + 128 + pair};
-        bool exact[2] = {iv[0] < n, iv[1] < n};
-        const SurvRec cur[2] = {nxt[0], nxt[1]};
-        {  // the next round's records (clamped: the last prefetch re-reads record 0)
-            const uint32_t j0 = i0 + gridDim.x * 256 + pair, j1 = j0 + 128;
-            nxt[0] = recs[j0 < n ? j0 : 0u], nxt[1] = recs[j1 < n ? j1 : 0u];
-        }
-        if (test) {
-            float4 par[2];
-            const uint8_t *x[2];
-#pragma unroll
-            for (int v = 0; v < 2; ++v) {
-                par[v] = par_lds ? lpar[cur[v].slot] : list_q8[pc[cur[v].slot]];  // lo, s, max |x_i - x^_i| of the list
-                x[v] = base_q8 + (uint64_t)cur[v].pos * dim;
-            }
-            float d0[2] = {0.0f, 0.0f}, d1[2] = {0.0f, 0.0f};
-            for (uint32_t g0 = hf; g0 < ngrp; g0 += 8) {  // four 16-byte pieces of each row in flight per lane
-                uint4 cv[2][4];
-#pragma unroll
-                for (int v = 0; v < 2; ++v)
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (g0 + 2 * u < ngrp) cv[v][u] = *reinterpret_cast<const uint4 *>(x[v] + 16 * (g0 + 2 * u));
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (!(g0 + 2 * u < ngrp)) continue;
-                    const float *q = acc_q + 16 * (g0 + 2 * u);
-#pragma unroll
-                    for (int wi = 0; wi < 4; ++wi) {
-                        const float4 qa = *reinterpret_cast<const float4 *>(q + 4 * wi);
-#pragma unroll
-                        for (int v = 0; v < 2; ++v) {
-                            const uint32_t wv = wi == 0 ? cv[v][u].x : (wi == 1 ? cv[v][u].y : (wi == 2 ? cv[v][u].z : cv[v][u].w));
-                            const float e0 = fmaf(par[v].y, (float)(wv & 255u), par[v].x) - qa.x;
-                            const float e1 = fmaf(par[v].y, (float)((wv >> 8) & 255u), par[v].x) - qa.y;
-                            const float e2 = fmaf(par[v].y, (float)((wv >> 16) & 255u), par[v].x) - qa.z;
-                            const float e3 = fmaf(par[v].y, (float)(wv >> 24), par[v].x) - qa.w;
-                            d0[v] = fmaf(e0, e0, d0[v]), d1[v] = fmaf(e1, e1, d1[v]), d0[v] = fmaf(e2, e2, d0[v]), d1[v] = fmaf(e3, e3, d1[v]);
-                        }
-                    }
-                    // (the query pieces of the later groups are read when their turn comes: hoisted, the sixteen 16-byte LDS reads of
-                    // a round held 64 registers and cost the kernel a wave per SIMD)
-                    asm volatile("" ::: "memory");
-                }
-            }
-#pragma unroll
-            for (int v = 0; v < 2; ++v) {
-                float dt = d0[v] + d1[v];
-                dt += __shfl_xor(dt, 1, 2);
-                // >= ||x - x^||: the largest row norm of the error measured over the list (dimensions q8_encode_kernel measures it for),
-                // else sqrt(dim) max |x_i - x^_i|   (inf: a list that is never rejected)
-                const float err = rown ? par[v].w * up : (par[v].z * up) * sqd;
-                const float t = sqrtf(dt * down) * down - err * up;
-                if (exact[v] && t > 0.0f && (t * t) * (down * down) > thr) {  // false for NaN
-                    exact[v] = false;
-                    if (hf == 0) recs[iv[v]].accurate = __builtin_inff();
-                    ++rejected;
-                }
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < 2; ++v)
-            if (exact[v] && hf == 0) queue[atomicAdd(&qn, 1u)] = iv[v];  // at most 127 waiting + 256 new
-        __syncthreads();
-        uint32_t waiting = qn;  // the same value in every thread: nobody touches qn before the next barrier
-        __syncthreads();
-        while (waiting >= 128) {  // block-uniform
-            const uint32_t j = queue[waiting - 128 + pair];
-            const float r = exact_l2_pair(base + (uint64_t)recs[j].pos * dim + 4 * hf, acc_q, dim, hf);
-            if (hf == 0) recs[j].accurate = r;
-            waiting -= 128;
-            __syncthreads();  // the queue's top 128 entries are free again
-            if (threadIdx.x == 0) qn = waiting;
-            __syncthreads();
-        }
-    }
-    const uint32_t waiting = qn;
-    if (pair < waiting) {
-        const uint32_t j = queue[pair];
-        const float r = exact_l2_pair(base + (uint64_t)recs[j].pos * dim + 4 * hf, acc_q, dim, hf);
-        if (hf == 0) recs[j].accurate = r;
-    }
-    uint32_t rj = hf == 0 ? rejected : 0u;  // per-query counter (one address per query: no hot spot)
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) rj += __shfl_xor(rj, o, 64);
-    if ((threadIdx.x & 63) == 0 && rj) atomicAdd(&nshadow[b], rj);
-}
-
-// ---- the same three phases as separate launches: better for large batches, where all queries'
-// survivors are reranked with full-chip parallelism before the (latency-bound) replay --------------
-// grid (gx, nq); block 256
-__global__ __launch_bounds__(256) void accurate_kernel(SurvRec *__restrict__ surv,
-                                                       const unsigned long long *__restrict__ surv_cnt,
-                                                       const QSeg seg, const BaseView base,
-                                                       const float *__restrict__ qpad, uint32_t dim,
-                                                       const uint32_t *__restrict__ order,
-                                                       const uint32_t *__restrict__ probe_cluster, uint32_t nprobe) {
-    // TWO lanes per candidate: lane half hf carries AVX lanes 4hf..4hf+3 (elements 8c + 4hf + 0..3, one
-    // 16-byte load per chunk), so a row is fetched with float4 loads; the fold
-    // ((a0+a4)+(a1+a5)) + ((a2+a6)+(a3+a7)) needs one exchange between the two lanes.
-    extern __shared__ __attribute__((aligned(16))) float acc_q[];  // dynamic LDS: dim floats (the padded query)
-    const uint32_t b = order ? order[blockIdx.y] : blockIdx.y;  // consecutive blocks: queries of the same nearest list
-    const uint32_t n = (uint32_t)surv_cnt[b];
-    if (n > seg.capof(b) || n == 0) return;  // overflowed: this query is re-run with a larger buffer
-    for (uint32_t c = threadIdx.x * 4; c < dim; c += 1024)
-        *reinterpret_cast<float4 *>(acc_q + c) = *reinterpret_cast<const float4 *>(qpad + (uint64_t)b * dim + c);
-    __syncthreads();
-    accurate_rows(surv + seg.at(b), n, base, acc_q, dim, blockIdx.x * 128 + (threadIdx.x >> 1), gridDim.x * 128,
-                  probe_cluster + (uint64_t)b * nprobe);
 }
 
 // `runs_src`: where the stage's unsorted descriptors are when not in `runs` itself (an arena stage scatters them into the

@@ -4,7 +4,7 @@
 // making a variable-length result: hit counts, offsets (u64), keys written straight to their query's segment, a segmented
 // sort binned by segment length, and the split of the sorted keys into the result's distance / id arrays.
 //
-// The exact distances themselves are the top-k path's kernels (accurate_kernel / accurate_filtered8_kernel /
+// The exact distances themselves are the top-k path's kernels (kernels_rerank.h: accurate_kernel / accurate_filtered8_kernel /
 // accurate_filtered_kernel / accurate_split_kernel, launched with the radii as thresholds): they write SurvRec::accurate in
 // place -- +inf where a shadow row proves accurate >= r_b -- so the distance bits are the plain query's by construction.
 #pragma once

@@ -278,54 +278,29 @@ __device__ __forceinline__ void select_merge16(const unsigned long long (*cand)[
     probe_dist[(uint64_t)b * nprobe + rank] = ord32_unbias((uint32_t)(key >> 32));
 }
 
-// accurate_rows for the block's LDS-resident survivors (same arithmetic: two lanes per row, lane half hf = AVX lanes
-// 4hf..4hf+3 of src/simd.rs:14-73, chunks of 64 dimensions in order): up to dim 128 every load of a row is issued before
-// the first one is used.
+// accurate_rows for the block's LDS-resident survivors (same arithmetic: exact_l2_acc64 over chunks of 64 dimensions in order, then
+// exact_l2_fold): up to dim 128 every load of a row is issued before the first one is used.
 template <int W>
 __device__ __forceinline__ void sb_accurate_rows(SurvRec *recs, uint32_t n, const BaseView &base, const float *q_lds,
                                                  uint32_t dim, const uint32_t *__restrict__ probe_row) {
     const uint32_t hf = threadIdx.x & 1;
     for (uint32_t i = threadIdx.x >> 1; i < n; i += 512) {
-        const float *x;
-        if (base.host == nullptr && !base.split) {
-            x = base.dev + (uint64_t)recs[i].pos * dim + 4 * hf;
-        } else {
-            const RowRef rr = base.row_of_slot(recs[i].pos, probe_row, recs[i].slot, dim);
-            if (rr.split) {
-                const float r = exact_l2_pair_split(rr.p, q_lds, dim, hf);
-                if (hf == 0) recs[i].accurate = r;
-                continue;
-            }
-            x = rr.p + 4 * hf;
-        }
-        float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-        auto chunk = [&](const float4 (&xv)[8], uint32_t c) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float4 qv = *reinterpret_cast<const float4 *>(q_lds + c + 8 * u + 4 * hf);
-                const float d0 = xv[u].x - qv.x, d1 = xv[u].y - qv.y, d2 = xv[u].z - qv.z, d3 = xv[u].w - qv.w;
-                a0 = fmaf(d0, d0, a0), a1 = fmaf(d1, d1, a1), a2 = fmaf(d2, d2, a2), a3 = fmaf(d3, d3, a3);
-            }
-        };
-        if constexpr (W <= 2) {
+        const RowRef rr = rerank_row(base, recs[i], probe_row, dim);
+        float r;
+        if (W > 2 || rr.split) {
+            r = exact_l2_row(rr, q_lds, dim, hf);
+        } else if constexpr (W <= 2) {
+            const float *x = rr.p + 4 * hf;
+            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
             float4 xv[W][8];
 #pragma unroll
             for (int w = 0; w < W; ++w)
 #pragma unroll
                 for (int u = 0; u < 8; ++u) xv[w][u] = *reinterpret_cast<const float4 *>(x + 64 * w + 8 * u);
 #pragma unroll
-            for (int w = 0; w < W; ++w) chunk(xv[w], 64 * w);
-        } else {
-            for (uint32_t c = 0; c < dim; c += 64) {
-                float4 xv[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) xv[u] = *reinterpret_cast<const float4 *>(x + c + 8 * u);
-                chunk(xv, c);
-            }
+            for (int w = 0; w < W; ++w) exact_l2_acc64(xv[w], q_lds + 64 * w + 4 * hf, a0, a1, a2, a3);
+            r = exact_l2_fold(a0, a1, a2, a3);
         }
-        const float c0 = a0 + __shfl_xor(a0, 1, 2), c1 = a1 + __shfl_xor(a1, 1, 2);
-        const float c2 = a2 + __shfl_xor(a2, 1, 2), c3 = a3 + __shfl_xor(a3, 1, 2);
-        const float r = (c0 + c1) + (c2 + c3);
         if (hf == 0) recs[i].accurate = r;
     }
 }

@@ -3,6 +3,8 @@ sub-index a filter stands for, the live rows of a mutated index and their canoni
 answer assembled from the oracle's stage functions.  Nothing here asks the engine what the answer is.  Not a conftest: import it.
 
 tests/test_fuzz_models.py checks the assembly itself (range and filter answers) against plain float64."""
+import ctypes as C
+
 import numpy as np
 
 ARRAYS = ("base", "orthogonal", "centroids", "offsets", "codes", "factors")
@@ -137,17 +139,27 @@ class Ref:
         """-> (positions, rough) of every stored row of the query's probe lists, in visiting order."""
         y = self.idx.rotate_query(q)
         cl, cd = self.idx.coarse_rank(y, probe)
-        pos, rough = [], []
-        for c, ycd in zip(cl, cd):
-            c = int(c)
-            if self.offsets[c + 1] == self.offsets[c]:
-                continue
-            lo, delta, s, planes = self.idx.query_prep(y, c)
-            rough.append(self.idx.scan_cluster(c, ycd, planes, lo, np.float32(s), delta))
-            pos.append(np.arange(self.offsets[c], self.offsets[c + 1]))
-        if not pos:
+        cl = cl.astype(np.int64)
+        begin, end = self.offsets[cl], self.offsets[cl + 1]
+        total = int((end - begin).sum())
+        if total == 0:
             return np.zeros(0, np.int64), np.zeros(0, np.float32)
-        return np.concatenate(pos), np.concatenate(rough)
+        # rqo_query_prep + rqo_scan_cluster per list, each list's rough distances written straight to their place in `rough` (the
+        # calls of OracleIndex.query_prep / scan_cluster without their per-call arrays, which cost seconds over 100 000 lists)
+        L, ptr = self.o.lib(), self.idx._ptr
+        f32p, u64p = C.POINTER(C.c_float), C.POINTER(C.c_uint64)
+        rough = np.empty(total, dtype=np.float32)
+        planes = np.zeros(self.dim // 64 * 4, dtype=np.uint64)
+        yp, pp, ra = y.ctypes.data_as(f32p), planes.ctypes.data_as(u64p), rough.ctypes.data
+        lo, delta, s = C.c_float(), C.c_float(), C.c_uint32()
+        at = 0
+        for c, ycd, ln in zip(cl.tolist(), cd.tolist(), (end - begin).tolist()):
+            if ln == 0:
+                continue
+            L.rqo_query_prep(ptr, yp, c, C.byref(lo), C.byref(delta), C.byref(s), pp)
+            L.rqo_scan_cluster(ptr, c, ycd, pp, lo, C.c_float(s.value), delta, C.cast(ra + 4 * at, f32p))
+            at += ln
+        return np.concatenate([np.arange(b, e) for b, e in zip(begin.tolist(), end.tolist()) if e > b]), rough
 
     def accurate(self, q, positions):
         """rqo_l2_squared_distance(query, row) of every position (one call: rqo_l2_squared_distance_rows)."""

@@ -1984,6 +1984,49 @@ def test_rerank_shadow_rows_keep_results_exact(rq, oracle, d, kind, shadow, tmp_
     oidx.close()
 
 
+def test_rerank_prefilter_with_more_probed_lists_than_fit_in_lds(rq, oracle):
+    """More than RQ_ACC8_LDS_PROBES (1024) probed lists: the 8-bit pre-filter reads its lists' maps, and the split-row pre-filter
+    its lists' tier records, from global memory instead of LDS.  1100 lists, all probed, 256 queries (the smallest batch that takes
+    the large-batch stages), both rankers, then one range search whose radii are the oracle's 10th distances (a range pass always
+    runs the pre-filter: its radii are the thresholds) -- on the default index (rerank_shadow = 2) and on a tiered split-row one,
+    everything bit for bit the oracle's, and every pass must have rejected rows through the pre-filter."""
+    from rabitq_amd import index as ix
+    from tests.models import Ref, run_range, same_range
+    n, d, k, nq, probe = 110_000, 64, 1100, 256, 1100
+    x, centres, _ = synth.mixture(n, d, k, sigma=0.7, seed=61, centre_scale=0.6)
+    queries, _, _ = synth.mixture(nq, d, k, sigma=0.7, seed=62, centre_scale=0.6)
+    P = synth.random_orthogonal(d, seed=63)
+    oidx = oracle.OracleIndex.build(x, centres, P)
+    seen = []
+    radii = want = None
+    ix.set_profiling(1)
+    try:
+        for leg in ("8-bit shadow", "tiered split rows"):
+            if leg == "tiered split rows":
+                ix.set_option("base_device_mb", max(1, (n * d * 4 * 4 // 5) >> 20))   # split rows, list tails in host memory
+            gidx = rq.RaBitQ.build(x, centres, P)
+            assert (leg == "8-bit shadow") != (gidx.split_rows and gidx.n_hbm < gidx.n), leg
+            for heur in (False, True):
+                _compare_with_oracle(rq, oracle, oidx, gidx, queries, probe, 10, heur, seen=seen if radii is None and not heur else None)
+                pr = ix.last_profile()
+                print(leg, "heuristic" if heur else "heap", "rejects", pr["rerank_shadow_rejects"], "of", pr["rerank_candidates"])
+                assert pr["rerank_shadow_rejects"] > 0, (leg, heur, pr)
+            if radii is None:   # the oracle's side of the range search: once, for both legs
+                radii = np.array([od.max() for od, _ in seen], dtype=np.float32)
+                assert all(od.size == 10 for od, _ in seen)
+                want = Ref(oracle, oidx).answer(queries, probe, radii)
+            got, m, pr = run_range(rq, gidx, queries, probe, radii)
+            same_range(got, want[:3], leg)
+            assert (m["rough"], m["precise"], m["query"]) == (want[3]["rough"], want[3]["precise"], nq), (leg, m, want[3])
+            print(leg, "range rejects", pr["rerank_shadow_rejects"], "of", pr["rerank_candidates"])
+            assert pr["rerank_shadow_rejects"] > 0, (leg, pr)
+            gidx.close()
+    finally:
+        ix.set_profiling(0)
+        ix.set_option("base_device_mb", -1)
+        oidx.close()
+
+
 def test_dense_directory_falls_back_when_a_stage_has_more_cells_than_capacity(rq, oracle):
     """One list of 600 000 vectors, a large batch: the geometric stage [40 960, 327 680) spans 4 480 directory cells, more
     than the default survivor capacity (4 096), so that stage appends and sorts its runs while its neighbours use dense
