@@ -184,3 +184,44 @@ struct BaseView {
         return row_in_list(p, lt[lo], dim);
     }
 };
+
+// ------------------------------------------------------------------------------------------------
+// Bitonic sort (flip / disperse form: every compare-exchange puts the smaller element at the lower
+// index, so elements at index >= n can be treated as +inf and are never touched).
+// ------------------------------------------------------------------------------------------------
+template <typename T, typename KeyFn>
+__device__ __forceinline__ void bitonic_sort_block(T *a, uint32_t n, KeyFn key) {
+    if (n < 2) return;
+    uint32_t p2 = 1;
+    while (p2 < n) p2 <<= 1;
+    const uint32_t half = p2 >> 1;
+    for (uint32_t k = 2; k <= p2; k <<= 1) {
+        // flip
+        for (uint32_t t = threadIdx.x; t < half; t += blockDim.x) {
+            uint32_t hk = k >> 1;
+            uint32_t blk = t / hk, off = t - blk * hk;
+            uint32_t i = blk * k + off, j = blk * k + k - 1 - off;
+            if (j < n) {
+                T ai = a[i], aj = a[j];
+                if (key(aj) < key(ai)) {
+                    a[i] = aj;
+                    a[j] = ai;
+                }
+            }
+        }
+        __syncthreads();
+        for (uint32_t s = k >> 2; s >= 1; s >>= 1) {
+            for (uint32_t t = threadIdx.x; t < half; t += blockDim.x) {
+                uint32_t i = (t / s) * (2 * s) + (t % s), j = i + s;
+                if (j < n) {
+                    T ai = a[i], aj = a[j];
+                    if (key(aj) < key(ai)) {
+                        a[i] = aj;
+                        a[j] = ai;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}

@@ -471,6 +471,25 @@ static void launch_coarse(const float *cent_t, const float *y, float *dist, uint
                                                                                                     kstride);
 }
 
+// registers per lane of the wave-per-query selections (the row of k <= 8192 distances in registers): f(integral_constant<int, KPL>)
+template <typename F>
+static void with_row_kpl(uint32_t k, F f) {
+    if (k <= 1024) f(std::integral_constant<int, 16>{});
+    else if (k <= 4096) f(std::integral_constant<int, 64>{});
+    else f(std::integral_constant<int, 128>{});
+}
+// probe selection: one wave per query when the row fits in registers and nprobe <= 64, else one block per query
+static void launch_select(const float *dist, uint32_t k, uint32_t nprobe, uint32_t *out_cluster, float *out_dist,
+                          uint32_t id_offset, uint32_t out_stride, uint32_t nq, hipStream_t st) {
+    if (select_is_wave(k, nprobe, nq)) {
+        with_row_kpl(k, [&](auto kpl) {
+            select_probe_wave_kernel<decltype(kpl)::value><<<ceil_div(nq, 4), 256, 0, st>>>(dist, k, nprobe, out_cluster, out_dist, id_offset, out_stride, nq);
+        });
+        return;
+    }
+    select_probe_kernel<<<nq, 256, (size_t)nprobe * 8, st>>>(dist, k, nprobe, out_cluster, out_dist, id_offset, out_stride);
+}
+
 // Coarse ranking of nq rotated queries against ALL k lists: the matrix-core pre-filter + exact-order refinement where it applies
 // (coarse_impl 3, or -- once measured faster -- auto for big batches), else the exact-order distance kernels + selection.
 static std::atomic<int> g_pair_split{1};  // sharded passes: pairs of empty lists settled by a thread each, quantisation over the listed others (0 = lane group per pair: test hook)
@@ -526,12 +545,12 @@ static void launch_coarse_prefiltered(const rq_index *idx, const float *y, float
 #undef RQ_TILED
         // rows the tiled kernel could not handle hold exact-order distances now: the block-per-query selection takes them (it exits at once for the others)
         select_probe_kernel<<<nq, 256, (size_t)nprobe * 8, st>>>(dist, k, nprobe, out_cluster, out_dist, 0u, out_stride, redo);
-    } else if (k <= 1024)
-        select_refine_wave_kernel<16><<<g, b, 0, st>>>(dist, y, idx->centroids.p, idx->cent_norm_max, k, dim, nprobe, out_cluster, out_dist, out_stride, nq, fallback_rows);
-    else if (k <= 4096)
-        select_refine_wave_kernel<64><<<g, b, 0, st>>>(dist, y, idx->centroids.p, idx->cent_norm_max, k, dim, nprobe, out_cluster, out_dist, out_stride, nq, fallback_rows);
-    else
-        select_refine_wave_kernel<128><<<g, b, 0, st>>>(dist, y, idx->centroids.p, idx->cent_norm_max, k, dim, nprobe, out_cluster, out_dist, out_stride, nq, fallback_rows);
+    } else {
+        with_row_kpl(k, [&](auto kpl) {
+            select_refine_wave_kernel<decltype(kpl)::value><<<g, b, 0, st>>>(dist, y, idx->centroids.p, idx->cent_norm_max, k, dim, nprobe, out_cluster, out_dist,
+                                                                             out_stride, nq, fallback_rows);
+        });
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -756,19 +775,6 @@ static uint32_t scan_tile(uint32_t W) {
         case 1: case 2: case 3: case 4: case 6: case 8: return 512;
         default: return 256;
     }
-}
-
-// probe selection: one wave per query when the row fits in registers and nprobe <= 64, else one block per query
-static void launch_select(const float *dist, uint32_t k, uint32_t nprobe, uint32_t *out_cluster, float *out_dist,
-                          uint32_t id_offset, uint32_t out_stride, uint32_t nq, hipStream_t st) {
-    if (select_is_wave(k, nprobe, nq)) {
-        const dim3 g(ceil_div(nq, 4)), b(256);
-        if (k <= 1024) select_probe_wave_kernel<16><<<g, b, 0, st>>>(dist, k, nprobe, out_cluster, out_dist, id_offset, out_stride, nq);
-        else if (k <= 4096) select_probe_wave_kernel<64><<<g, b, 0, st>>>(dist, k, nprobe, out_cluster, out_dist, id_offset, out_stride, nq);
-        else select_probe_wave_kernel<128><<<g, b, 0, st>>>(dist, k, nprobe, out_cluster, out_dist, id_offset, out_stride, nq);
-        return;
-    }
-    select_probe_kernel<<<nq, 256, (size_t)nprobe * 8, st>>>(dist, k, nprobe, out_cluster, out_dist, id_offset, out_stride);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -666,17 +666,9 @@ __global__ __launch_bounds__(256) void list_uref_kernel(const float4 *__restrict
 // src/utils.rs:261-277: the first j minimising the exact-order f32 distance).
 //
 // The exact-order VALU kernels above are 3 n k dim flop of vector work: 2.9 of the 3.1 s of a 100M x 128 build.
-// Here every (vector, centroid) distance is first APPROXIMATED as (|c|^2 + |x|^2) - 2 <c~, x~> with the inner products
-// from v_mfma_f32_32x32x16_bf16 (operands rounded to bf16, f32 accumulation: 16x the f32 MFMA rate), which is within
-//     m_x = (2^-8 + (2 dim + 64) 2^-24) 1.05 (Cmax + |x|)^2
-// of the reference's f32 value e_j (src/simd.rs:14-73).  bf16 keeps 8 significant bits: round-to-nearest is 2^-8 relative per
-// operand, so |<x,c> - <x~,c~>| <= (2^-7 + 2^-16) |x||c|, the term -2<x,c> of the distance is off by at most
-// (2^-6 + 2^-15) |x||c| <= (2^-8 + 2^-17) (|x|+|c|)^2   (|x||c| <= (|x|+|c|)^2 / 4): the first term of m_x, with its 2^-17
-// tail inside the factor 1.05 -- that factor is LOAD-BEARING (it is the only slack over the bf16 bound: do not tighten it).
-// The f32 accumulation of the 128-term products, the two norms (a dim-long f32 fma chain each) and the reference's own chain
-// ((dim/8 + 5) 2^-24 relative) are all inside the second term; Cmax = the largest centroid norm.  So the exact minimiser j*
-// (and every exact tie) has
-//     a_{j*} <= e_{j*} + m <= e_j + m <= a_j + 2 m   for every j,   in particular   a_{j*} <= a_min + 2 m:
+// Here every (vector, centroid) distance is first APPROXIMATED with bf16 inner products from the matrix cores, within m_x of the
+// reference's f32 value, so that the exact minimiser j* (and every exact tie) has a_{j*} <= a_min + 2 m_x (prefilter_bound,
+// kernels_coarse.h, has m_x and the argument):
 // pass 1 finds a_min per vector, pass 2 lists the lists with a <= a_min + 2 m (one on well separated data, a few on
 // overlapping clusters), assign_refine_kernel recomputes THOSE in the reference's lane order and takes the first
 // minimum.  Vectors with no candidate (non-finite input) or more than RQ_ASSIGN_CAND of them (near-equidistant
@@ -688,15 +680,6 @@ __global__ __launch_bounds__(256) void list_uref_kernel(const float4 *__restrict
 // (lane & 31), the 16 registers x 2 half-waves = the 32 lists of the tile.
 // ------------------------------------------------------------------------------------------------
 #define RQ_ASSIGN_CAND 16u
-typedef __bf16 asg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float asg_f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ uint32_t asg_bf16_pair(float lo, float hi) {  // two f32 -> packed bf16 (round to nearest even)
-    uint32_t a = __builtin_bit_cast(uint32_t, lo), b = __builtin_bit_cast(uint32_t, hi);
-    a += 0x7FFFu + ((a >> 16) & 1u);
-    b += 0x7FFFu + ((b >> 16) & 1u);
-    return (a >> 16) | (b & 0xFFFF0000u);
-}
 // rows x dim f32 -> bf16 (round to nearest even), 8 elements per thread
 __global__ __launch_bounds__(256) void to_bf16_kernel(const float *__restrict__ in, uint64_t total, uint16_t *__restrict__ out) {
     const uint64_t i = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 8;
@@ -727,9 +710,8 @@ __global__ __launch_bounds__(256, (W <= 4 ? 2 : 1)) void assign_approx_kernel(co
                                                               uint32_t k, uint32_t *__restrict__ cand /* n x RQ_ASSIGN_CAND */,
                                                               uint32_t *__restrict__ cand_cnt /* n, zeroed */) {
     constexpr int DIM = 64 * W, NM = DIM / 16;             // MFMAs per (vector tile, centroid tile)
-    constexpr uint32_t ROWB = DIM * 2 + 16;                // LDS row stride of a centroid tile, bytes
-    constexpr uint32_t TILEB = 32 * ROWB;
-    extern __shared__ __attribute__((aligned(16))) unsigned char asg_lds[];  // 2 x (tile image | 32 norms)
+    constexpr uint32_t ROWB = CentTile<W>::ROWB, TILEB = CentTile<W>::TILEB;
+    extern __shared__ __attribute__((aligned(16))) unsigned char asg_lds[];  // the two images of CentTile<W>
     const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31, kh = lane >> 5;
     const uint64_t v0 = ((uint64_t)blockIdx.x * 4 + wave) * (32 * NT);
     // ---- this wave's vectors: bf16 B fragments (k-elements 16 m + 8 kh .. + 7 of vector v0 + 32 tile + col) and |x|^2 -------
@@ -752,41 +734,18 @@ __global__ __launch_bounds__(256, (W <= 4 ? 2 : 1)) void assign_approx_kernel(co
         xn[tl] = s + __shfl_xor(s, 32, 64);  // both halves of the vector
     }
     const uint32_t ntile = (k + 31) / 32;
-    auto stage = [&](uint32_t tile, uint4 (&regs)[(32 * DIM * 2 / 16 + 255) / 256], float &cn) {  // global -> registers
-        constexpr uint32_t PIECES = 32 * DIM * 2 / 16;  // 16-byte pieces of the tile
-#pragma unroll
-        for (uint32_t i = 0; i < (PIECES + 255) / 256; ++i) {
-            const uint32_t pc = t + 256 * i, row = pc / (DIM / 8), within = pc - row * (DIM / 8);
-            const uint32_t j = 32 * tile + row;
-            regs[i] = make_uint4(0u, 0u, 0u, 0u);
-            if (pc < PIECES && j < k) regs[i] = *reinterpret_cast<const uint4 *>(cent_bf + (uint64_t)j * DIM + 8 * within);
-        }
-        cn = __builtin_inff();  // a row past the last list: never the minimum, never a candidate
-        if (t < 32 && 32 * tile + t < k) cn = cnorm[32 * tile + t];
-    };
-    auto land = [&](uint32_t buf, const uint4 (&regs)[(32 * DIM * 2 / 16 + 255) / 256], float cn) {  // registers -> LDS
-        constexpr uint32_t PIECES = 32 * DIM * 2 / 16;
-        unsigned char *img = asg_lds + buf * (TILEB + 128);
-#pragma unroll
-        for (uint32_t i = 0; i < (PIECES + 255) / 256; ++i) {
-            const uint32_t pc = t + 256 * i, row = pc / (DIM / 8), within = pc - row * (DIM / 8);
-            if (pc < PIECES) *reinterpret_cast<uint4 *>(img + row * ROWB + 16 * within) = regs[i];
-        }
-        if (t < 32) reinterpret_cast<float *>(img + TILEB)[t] = cn;
-    };
     float tmin[NT], thr[NT];
 #pragma unroll
     for (int tl = 0; tl < NT; ++tl) tmin[tl] = __builtin_inff(), thr[tl] = 0.0f;
     for (int pass = 0; pass < 2; ++pass) {
-        uint4 regs[(32 * DIM * 2 / 16 + 255) / 256];
-        float cn_next;
+        CentTile<W> next;  // (norm of a row past the last list: +inf, never the minimum, never a candidate)
         __syncthreads();  // the previous pass's last tile has been consumed
-        stage(0, regs, cn_next);
-        land(0, regs, cn_next);
+        next.stage(cent_bf, cnorm, k, 0, __builtin_inff());
+        next.land(asg_lds, 0);
         for (uint32_t tile = 0; tile < ntile; ++tile) {
             __syncthreads();  // tile `tile` is in LDS; the other buffer is free
-            if (tile + 1 < ntile) stage(tile + 1, regs, cn_next);
-            const unsigned char *img = asg_lds + (tile & 1u) * (TILEB + 128);
+            if (tile + 1 < ntile) next.stage(cent_bf, cnorm, k, tile + 1, __builtin_inff());
+            const unsigned char *img = CentTile<W>::image(asg_lds, tile & 1u);
             const float *cnp = reinterpret_cast<const float *>(img + TILEB);
             asg_f32x16 acc[NT];
 #pragma unroll
@@ -819,118 +778,16 @@ __global__ __launch_bounds__(256, (W <= 4 ? 2 : 1)) void assign_approx_kernel(co
                     }
                 }
             }
-            if (tile + 1 < ntile) land((tile + 1) & 1u, regs, cn_next);
+            if (tile + 1 < ntile) next.land(asg_lds, (tile + 1) & 1u);
         }
         if (pass == 0) {
 #pragma unroll
             for (int tl = 0; tl < NT; ++tl) {
                 const float other = __shfl_xor(tmin[tl], 32, 64);  // the other 16 rows of every tile
                 tmin[tl] = fminf(tmin[tl], other);
-                const float rad = cmax + sqrtf(xn[tl]) * 1.000001f;
-                const float mx = (0.00390625f + (float)(2 * DIM + 64) * 5.9604645e-8f) * 1.05f * (rad * rad);
-                thr[tl] = tmin[tl] + 2.0f * mx;          // (inf / NaN -> no candidate -> the exact-order kernel takes the vector)
-                thr[tl] = thr[tl] + fabsf(thr[tl]) * 1.0e-6f;  // the comparison's own rounding
+                thr[tl] = prefilter_bound(tmin[tl], cmax, xn[tl], DIM);  // (inf / NaN -> no candidate -> the exact-order kernel takes the vector)
             }
         }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Coarse ranking through the same pre-filter (round 4; src/rabitq.rs:283-297: all k exact-order distances, select the nprobe
-// smallest, sort them).  coarse_approx_kernel writes, for every query, a'_j = |c_j|^2 - 2 <c~_j, y~> (the approximation above minus
-// the query's own |y|^2, a constant of the row) for every list; select_refine_wave_kernel (kernels_query.h) finds the nprobe-th
-// smallest a' of a row, lists the lists within 2 m_y above it (the true nprobe nearest are among them: the nprobe smallest-a' lists
-// all have e <= a' + |y|^2 + m, so the nprobe-th smallest exact distance is <= tau + m, and every list at or below it has
-// a' + |y|^2 <= e + m <= tau + 2 m), recomputes THOSE in the reference's lane order and selects / sorts on the exact values.
-// Roles are swapped against assign_approx_kernel (queries = A rows, lists = B columns), so that a wave's stores are 128-byte
-// runs of one query's row.
-// ------------------------------------------------------------------------------------------------
-template <int W, int NT>
-__global__ __launch_bounds__(256, (W <= 4 ? 2 : 1)) void coarse_approx_kernel(const float *__restrict__ y /* nq x dim, rotated queries */,
-                                                              const uint16_t *__restrict__ cent_bf /* k x dim bf16 */,
-                                                              const float *__restrict__ cnorm, uint32_t nq, uint32_t k,
-                                                              float *__restrict__ dist /* nq x k */,
-                                                              const uint16_t *__restrict__ y_bf /* nq x dim bf16 (to_bf16_kernel of y), or null */) {
-    constexpr int DIM = 64 * W, NM = DIM / 16;
-    constexpr uint32_t ROWB = DIM * 2 + 16, TILEB = 32 * ROWB;
-    extern __shared__ __attribute__((aligned(16))) unsigned char asg_lds[];  // 2 x (tile image | 32 norms), as assign_approx_kernel
-    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31, kh = lane >> 5;
-    const uint32_t v0 = (blockIdx.x * 4 + wave) * (32 * NT);
-    asg_bf16x8 afrag[NT][NM];  // k-elements 16 m + 8 kh .. + 7 of query v0 + 32 tile + col
-#pragma unroll
-    for (int tl = 0; tl < NT; ++tl) {
-        const uint32_t v = v0 + 32 * tl + col;
-        const uint64_t vr = v < nq ? v : (nq - 1);
-        if constexpr (NM > 32) {
-            // dim > 512: the fragments come pre-rounded (to_bf16_kernel over the query rows, the rounding of asg_bf16_pair), one 16-byte
-            // load per slab straight into its place.  Converted here, the f32 loads of all dim / 16 slabs were in flight beside the
-            // fragments (384 + 192 registers at dim 768): 142 registers went to scratch memory in round 4 -- the only kernel of the
-            // query path that needed any, and a dispatch that needs more scratch than the queue holds is set up and torn down around
-            // the launch by the runtime (the 20 ms that appeared BETWEEN launches behind this kernel)
-            const uint16_t *xb = y_bf + vr * DIM + 8 * kh;
-#pragma unroll
-            for (int m = 0; m < NM; ++m) afrag[tl][m] = __builtin_bit_cast(asg_bf16x8, *reinterpret_cast<const uint4 *>(xb + 16 * m));
-        } else {
-        const float *xp = y + vr * DIM + 8 * kh;
-#pragma unroll
-        for (int m = 0; m < NM; ++m) {
-            const float4 a = *reinterpret_cast<const float4 *>(xp + 16 * m), b = *reinterpret_cast<const float4 *>(xp + 16 * m + 4);
-            const uint4 pk = make_uint4(asg_bf16_pair(a.x, a.y), asg_bf16_pair(a.z, a.w), asg_bf16_pair(b.x, b.y), asg_bf16_pair(b.z, b.w));
-            afrag[tl][m] = __builtin_bit_cast(asg_bf16x8, pk);
-        }
-        }
-    }
-    const uint32_t ntile = (k + 31) / 32;
-    constexpr uint32_t PIECES = 32 * DIM * 2 / 16, NREG = (PIECES + 255) / 256;
-    auto stage = [&](uint32_t tile, uint4 (&regs)[NREG], float &cn) {  // global -> registers
-#pragma unroll
-        for (uint32_t i = 0; i < NREG; ++i) {
-            const uint32_t pc = t + 256 * i, row = pc / (DIM / 8), within = pc - row * (DIM / 8);
-            const uint32_t j = 32 * tile + row;
-            regs[i] = make_uint4(0u, 0u, 0u, 0u);
-            if (pc < PIECES && j < k) regs[i] = *reinterpret_cast<const uint4 *>(cent_bf + (uint64_t)j * DIM + 8 * within);
-        }
-        cn = 0.0f;
-        if (t < 32 && 32 * tile + t < k) cn = cnorm[32 * tile + t];
-    };
-    auto land = [&](uint32_t buf, const uint4 (&regs)[NREG], float cn) {  // registers -> LDS
-        unsigned char *img = asg_lds + buf * (TILEB + 128);
-#pragma unroll
-        for (uint32_t i = 0; i < NREG; ++i) {
-            const uint32_t pc = t + 256 * i, row = pc / (DIM / 8), within = pc - row * (DIM / 8);
-            if (pc < PIECES) *reinterpret_cast<uint4 *>(img + row * ROWB + 16 * within) = regs[i];
-        }
-        if (t < 32) reinterpret_cast<float *>(img + TILEB)[t] = cn;
-    };
-    uint4 regs[NREG];
-    float cn_next;
-    stage(0, regs, cn_next);
-    land(0, regs, cn_next);
-    for (uint32_t tile = 0; tile < ntile; ++tile) {
-        __syncthreads();  // tile `tile` is in LDS; the other buffer is free
-        if (tile + 1 < ntile) stage(tile + 1, regs, cn_next);
-        const unsigned char *img = asg_lds + (tile & 1u) * (TILEB + 128);
-        const float cn = reinterpret_cast<const float *>(img + TILEB)[col];  // |c|^2 of this lane's list
-        asg_f32x16 acc[NT];
-#pragma unroll
-        for (int tl = 0; tl < NT; ++tl) acc[tl] = asg_f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int m = 0; m < NM; ++m) {
-            const asg_bf16x8 cf = *reinterpret_cast<const asg_bf16x8 *>(img + col * ROWB + (16 * m + 8 * kh) * 2);
-#pragma unroll
-            for (int tl = 0; tl < NT; ++tl) acc[tl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag[tl][m], cf, acc[tl], 0, 0, 0);
-        }
-        const uint32_t j = 32 * tile + col;
-        if (j < k) {
-#pragma unroll
-            for (int tl = 0; tl < NT; ++tl)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {  // register r of lane half kh = query row (r & 3) + 8 (r >> 2) + 4 kh of the tile
-                    const uint32_t v = v0 + 32 * tl + (uint32_t)((r & 3) + 8 * (r >> 2)) + 4 * kh;
-                    if (v < nq) dist[(uint64_t)v * k + j] = fmaf(-2.0f, acc[tl][r], cn);
-                }
-        }
-        if (tile + 1 < ntile) land((tile + 1) & 1u, regs, cn_next);
     }
 }
 

@@ -8,12 +8,12 @@
 //   * the scan filters against the per-query re-rank threshold in-kernel and emits only
 //     survivors; exact f32 distances are computed for survivors only; an ordered replay of the
 //     reference's heap logic over (rough, accurate) pairs reproduces its result id-for-id.
+//
+// The coarse ranking (src/rabitq.rs:283-297) is in kernels_coarse.h, the re-rank stage in kernels_rerank.h.
 #pragma once
-#ifndef RQ_COLLECT_UNROLL
-#define RQ_COLLECT_UNROLL 8  // 16 tiles per step: coarse 1.07 -> 1.03 ms per step (4: the round-4 form; 16 no better)
-#endif
 #include "common.h"
 #include "kernels_scan_common.h"
+#include "kernels_coarse.h"
 
 #pragma clang fp contract(off)
 
@@ -49,813 +49,6 @@ __global__ __launch_bounds__(256) void rotate_valu_kernel(const float *__restric
         for (int l = 0; l < 8; ++l) acc[l] = fmaf(xr[c + l], P[(uint64_t)(c + l) * dim + j], acc[l]);
     }
     out[r * dim + j] = reduce8_regs(acc);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Coarse distances (src/rabitq.rs:285-293): dist[q][j] = l2_squared_distance(centroid_j, y_q) in
-// the exact order of src/simd.rs:14-73 (diff rounded, then fused square-accumulate per AVX lane).
-// lane <-> centroid j over the TRANSPOSED rotated centroids cent_t[dim][k] (coalesced; this is also
-// the reference's on-disk centroids.fvecs layout), QT queries per thread held in LDS (broadcast).
-// ------------------------------------------------------------------------------------------------
-// Large batches: the same distances with the QUERY side in scalar registers.  A lane still owns one list; the block's
-// QT queries are read through the scalar unit (their rows are wave-uniform), 16 dimensions of one query per
-// s_load_dwordx16, and enter the packed ops as SGPR pairs: two neighbouring dimensions (= two neighbouring AVX
-// lanes of src/simd.rs:14-73, each with its own accumulator and per-component rounding) per v_pk_add_f32 /
-// v_pk_fma_f32.  No LDS: the LDS-broadcast form above spends as many LDS cycles as VALU cycles per element and
-// stalls at half the packed-f32 rate.  QT queries per centroid element loaded (8: 86 VGPRs, five waves per SIMD; 16 was
-// measured slower, three waves per SIMD do not cover the scalar loads).
-template <int QT>
-__global__ __launch_bounds__(256) void coarse_dist_sreg_kernel(const float *__restrict__ cent_t,
-                                                               const float *__restrict__ y, float *__restrict__ dist,
-                                                               uint32_t k, uint32_t dim, uint32_t nq, uint32_t kstride) {
-    const uint32_t q0 = blockIdx.x * QT;
-    const uint32_t j = blockIdx.y * 256 + threadIdx.x;
-    const bool live = j < k;
-    const float *cp = cent_t + (live ? j : 0);
-    f32x2 acc[QT][4];  // [query][pair of AVX lanes]
-#pragma unroll
-    for (int v = 0; v < QT; ++v)
-#pragma unroll
-        for (int l = 0; l < 4; ++l) acc[v][l] = f32x2{0.0f, 0.0f};
-    static_assert(QT % 4 == 0, "queries are fetched four at a time");
-    for (uint32_t c = 0; c < dim; c += 16) {  // dim is a multiple of 64
-        float ce[16];
-#pragma unroll
-        for (int l = 0; l < 16; ++l) ce[l] = cp[(uint64_t)(c + l) * kstride];  // 16 loads in flight
-#pragma unroll
-        for (int v0 = 0; v0 < QT; v0 += 4) {
-            float yv[4][16];  // four queries x 16 dimensions: four s_load_dwordx16 issued together
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const uint32_t q = q0 + v0 + v < nq ? q0 + v0 + v : nq - 1;  // uniform; rows past the batch are computed and dropped
-                const float *yq = y + (uint64_t)q * dim + c;
-#pragma unroll
-                for (int l = 0; l < 16; ++l) yv[v][l] = yq[l];
-            }
-#pragma unroll
-            for (int h = 0; h < 2; ++h)  // the two 8-dimension steps of the chunk, in order (one accumulator chain per AVX lane)
-#pragma unroll
-                for (int v = 0; v < 4; ++v)
-#pragma unroll
-                    for (int l = 0; l < 4; ++l) {
-                        const f32x2 c2 = {ce[8 * h + 2 * l], ce[8 * h + 2 * l + 1]};
-                        const f32x2 y2 = {yv[v][8 * h + 2 * l], yv[v][8 * h + 2 * l + 1]};
-                        const f32x2 d2 = c2 - y2;
-                        acc[v0 + v][l] = __builtin_elementwise_fma(d2, d2, acc[v0 + v][l]);
-                    }
-        }
-    }
-    if (live) {
-#pragma unroll
-        for (int v = 0; v < QT; ++v) {
-            float a[8];
-#pragma unroll
-            for (int l = 0; l < 4; ++l) a[2 * l] = acc[v][l].x, a[2 * l + 1] = acc[v][l].y;
-            if (q0 + v < nq) dist[(uint64_t)(q0 + v) * k + j] = reduce8_regs(a);
-        }
-    }
-}
-
-template <int QT>
-__global__ __launch_bounds__(256) void coarse_dist_kernel(const float *__restrict__ cent_t,
-                                                          const float *__restrict__ y,
-                                                          float *__restrict__ dist, uint32_t k,
-                                                          uint32_t dim, uint32_t nq, uint32_t kstride) {
-    // cent_t points at the first list of the range; k = number of lists ranked, kstride = row stride
-    extern __shared__ __attribute__((aligned(16))) float ys[];  // [dim][QT]: one ds_read_b128 = 4 queries at one dimension
-    const uint32_t q0 = blockIdx.x * QT;
-    const uint32_t j = blockIdx.y * 256 + threadIdx.x;
-    for (uint32_t i = threadIdx.x; i < QT * dim; i += 256) {
-        uint32_t v = i / dim, e = i - v * dim;  // coalesced reads of y, transposed into LDS
-        ys[e * QT + v] = (q0 + v < nq) ? y[(uint64_t)(q0 + v) * dim + e] : 0.0f;
-    }
-    __syncthreads();
-    static_assert(QT % 4 == 0, "queries are processed in packed pairs, read four at a time");
-    f32x2 acc[QT / 2][8];  // [query pair][AVX lane]: v_pk_add_f32 + v_pk_fma_f32, per-component rounding
-#pragma unroll
-    for (int v = 0; v < QT / 2; ++v)
-#pragma unroll
-        for (int l = 0; l < 8; ++l) acc[v][l] = f32x2{0.0f, 0.0f};
-    const bool live = j < k;
-    const float *cp = cent_t + (live ? j : 0);
-    for (uint32_t c = 0; c < dim; c += 8) {
-        float ce[8];
-#pragma unroll
-        for (int l = 0; l < 8; ++l) ce[l] = cp[(uint64_t)(c + l) * kstride];  // 8 loads in flight
-#pragma unroll
-        for (int l = 0; l < 8; ++l) {
-            const f32x2 ce2 = {ce[l], ce[l]};
-#pragma unroll
-            for (int v4 = 0; v4 < QT / 4; ++v4) {
-                const float4 yq = *reinterpret_cast<const float4 *>(&ys[(c + l) * QT + 4 * v4]);
-                const f32x2 y01 = {yq.x, yq.y}, y23 = {yq.z, yq.w};
-                const f32x2 d01 = ce2 - y01, d23 = ce2 - y23;
-                acc[2 * v4][l] = __builtin_elementwise_fma(d01, d01, acc[2 * v4][l]);
-                acc[2 * v4 + 1][l] = __builtin_elementwise_fma(d23, d23, acc[2 * v4 + 1][l]);
-            }
-        }
-    }
-    if (live) {
-#pragma unroll
-        for (int v = 0; v < QT / 2; ++v) {
-            float a0[8], a1[8];
-#pragma unroll
-            for (int l = 0; l < 8; ++l) a0[l] = acc[v][l].x, a1[l] = acc[v][l].y;
-            if (q0 + 2 * v < nq) dist[(uint64_t)(q0 + 2 * v) * k + j] = reduce8_regs(a0);
-            if (q0 + 2 * v + 1 < nq) dist[(uint64_t)(q0 + 2 * v + 1) * k + j] = reduce8_regs(a1);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Bitonic sort (flip / disperse form: every compare-exchange puts the smaller element at the lower
-// index, so elements at index >= n can be treated as +inf and are never touched).
-// ------------------------------------------------------------------------------------------------
-template <typename T, typename KeyFn>
-__device__ __forceinline__ void bitonic_sort_block(T *a, uint32_t n, KeyFn key) {
-    if (n < 2) return;
-    uint32_t p2 = 1;
-    while (p2 < n) p2 <<= 1;
-    const uint32_t half = p2 >> 1;
-    for (uint32_t k = 2; k <= p2; k <<= 1) {
-        // flip
-        for (uint32_t t = threadIdx.x; t < half; t += blockDim.x) {
-            uint32_t hk = k >> 1;
-            uint32_t blk = t / hk, off = t - blk * hk;
-            uint32_t i = blk * k + off, j = blk * k + k - 1 - off;
-            if (j < n) {
-                T ai = a[i], aj = a[j];
-                if (key(aj) < key(ai)) {
-                    a[i] = aj;
-                    a[j] = ai;
-                }
-            }
-        }
-        __syncthreads();
-        for (uint32_t s = k >> 2; s >= 1; s >>= 1) {
-            for (uint32_t t = threadIdx.x; t < half; t += blockDim.x) {
-                uint32_t i = (t / s) * (2 * s) + (t % s), j = i + s;
-                if (j < n) {
-                    T ai = a[i], aj = a[j];
-                    if (key(aj) < key(ai)) {
-                        a[i] = aj;
-                        a[j] = ai;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Probe selection (src/rabitq.rs:294-297): the `nprobe` smallest (distance, cluster id) pairs in
-// ascending order.  total_cmp order == Ord32 order; the composite u64 (biased Ord32 << 32 | id) is
-// unique, so an 8-bit-per-pass radix select finds the nprobe-th key exactly, then the selected keys
-// are bitonic-sorted in LDS.  Exactly-equal distances are ordered by cluster id (the reference's
-// select_nth_unstable leaves that order unspecified).  One 256-thread block per query.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void select_probe_kernel(const float *__restrict__ dist, uint32_t k,
-                                                           uint32_t nprobe,
-                                                           uint32_t *__restrict__ out_cluster,
-                                                           float *__restrict__ out_dist, uint32_t id_offset,
-                                                           uint32_t out_stride, const uint32_t *__restrict__ only_rows = nullptr /* per row: 0 = skip */) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    uint64_t *keys = reinterpret_cast<uint64_t *>(smem_raw);  // nprobe entries
-    if (only_rows && only_rows[blockIdx.x] == 0u) return;
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t s_sel, s_want, s_done, s_cnt;
-    const uint32_t b = blockIdx.x, tid = threadIdx.x;
-    const float *d = dist + (uint64_t)b * k;
-
-    uint64_t prefix = 0, mask = 0, T = ~0ull;
-    uint32_t want = nprobe;  // rank (1-based) of the wanted key inside the current prefix group
-    bool done = false;
-    for (int pass = 7; pass >= 0 && !done; --pass) {
-        const int shift = pass * 8;
-        hist[tid] = 0;
-        __syncthreads();
-        for (uint32_t j = tid; j < k; j += 256) {
-            uint64_t key = ((uint64_t)ord32_biased(d[j]) << 32) | j;
-            if ((key & mask) == prefix) atomicAdd(&hist[(uint32_t)(key >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (tid < 64) {  // wave 0: locate the bin holding rank `want`
-            uint32_t h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-            uint32_t s = h0 + h1 + h2 + h3, incl = s;
-            for (int o = 1; o < 64; o <<= 1) {
-                uint32_t up = __shfl_up(incl, o, 64);
-                if ((int)tid >= o) incl += up;
-            }
-            uint32_t excl = incl - s;
-            if (excl < want && want <= incl) {
-                uint32_t r = want - excl, sel, cntbin;
-                if (r <= h0) { sel = 0; cntbin = h0; }
-                else if (r <= h0 + h1) { sel = 1; r -= h0; cntbin = h1; }
-                else if (r <= h0 + h1 + h2) { sel = 2; r -= h0 + h1; cntbin = h2; }
-                else { sel = 3; r -= h0 + h1 + h2; cntbin = h3; }
-                s_sel = 4 * tid + sel;
-                s_want = r;
-                s_done = (cntbin == r) ? 1u : 0u;  // the whole bin is taken: lower bits don't matter
-            }
-        }
-        __syncthreads();
-        prefix |= (uint64_t)s_sel << shift;
-        mask |= 0xFFull << shift;
-        want = s_want;
-        if (s_done) {
-            T = prefix | ~mask;
-            done = true;
-        }
-        __syncthreads();
-    }
-    if (!done) T = prefix;
-    if (tid == 0) s_cnt = 0;
-    __syncthreads();
-    for (uint32_t j = tid; j < k; j += 256) {
-        uint64_t key = ((uint64_t)ord32_biased(d[j]) << 32) | j;
-        if (key <= T) {
-            uint32_t p = atomicAdd(&s_cnt, 1u);
-            if (p < nprobe) keys[p] = key;
-        }
-    }
-    __syncthreads();
-    bitonic_sort_block(keys, nprobe, [](uint64_t v) { return v; });
-    for (uint32_t i = tid; i < nprobe; i += 256) {
-        uint64_t key = keys[i];
-        out_cluster[(uint64_t)b * out_stride + i] = (uint32_t)key + id_offset;
-        out_dist[(uint64_t)b * out_stride + i] = ord32_unbias((uint32_t)(key >> 32));
-    }
-    for (uint32_t i = nprobe + tid; i < out_stride; i += 256) {  // fewer lists than requested: "no list"
-        out_cluster[(uint64_t)b * out_stride + i] = 0xFFFFFFFFu;
-        out_dist[(uint64_t)b * out_stride + i] = __builtin_inff();
-    }
-}
-
-// The same selection with ONE WAVE per query, for nprobe <= 64 and k <= 64*KPL: the row of distances lives
-// in registers (lane l holds lists l, l+64, ...), the nprobe-th smallest key is found by bisection on
-// the monotone u32 image of the distance (count = per-lane compares + one wave reduction, typically
-// ~20 steps, stopping as soon as a threshold selects exactly nprobe), ties at the threshold are broken
-// by list id (a second bisection, rare), the winners are compacted by ballot and sorted across the 64
-// lanes with a shuffle bitonic network.  No LDS atomics, no block barriers.
-// One wave's selection for query row b; `win`: 64 u64 of LDS owned by the calling wave.
-template <int KPL>
-__device__ __forceinline__ void select_probe_wave(const float *__restrict__ dist, uint32_t k, uint32_t nprobe,
-                                                  uint32_t *__restrict__ out_cluster, float *__restrict__ out_dist,
-                                                  uint32_t id_offset, uint32_t out_stride, uint32_t b,
-                                                  unsigned long long *win) {
-    const uint32_t lane = threadIdx.x & 63;
-    const float *d = dist + (uint64_t)b * k;
-    uint32_t key[KPL];
-    uint32_t kmin = 0xFFFFFFFFu, kmax = 0u;
-    // register i of lane l holds list list_of(i) = 256 (i / 4) + 4 l + (i % 4): the row is read 16 bytes per lane, 1 KiB
-    // per wave instruction (rows are 16-byte aligned whenever k % 4 == 0; else element by element)
-    auto list_of = [&](int i) { return 256u * (uint32_t)(i >> 2) + 4u * lane + (uint32_t)(i & 3); };
-    const bool vec4 = (k & 3u) == 0u;
-#pragma unroll
-    for (int i4 = 0; i4 < KPL; i4 += 4) {
-        const uint32_t j0 = list_of(i4);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (vec4 && j0 < k) {
-            v = *reinterpret_cast<const float4 *>(d + j0);
-        } else if (!vec4) {
-            if (j0 < k) v.x = d[j0];
-            if (j0 + 1 < k) v.y = d[j0 + 1];
-            if (j0 + 2 < k) v.z = d[j0 + 2];
-            if (j0 + 3 < k) v.w = d[j0 + 3];
-        }
-        const float ve[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int i = i4 + e;
-            key[i] = 0xFFFFFFFFu;  // "no list": above every real key (a NaN distance with all-ones payload is not supported)
-            if (j0 + e < k) {
-                key[i] = ord32_biased(ve[e]);
-                kmin = key[i] < kmin ? key[i] : kmin;
-                kmax = key[i] > kmax ? key[i] : kmax;
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const uint32_t a = __shfl_xor(kmin, o, 64), c = __shfl_xor(kmax, o, 64);
-        kmin = a < kmin ? a : kmin;
-        kmax = c > kmax ? c : kmax;
-    }
-    // wave-wide count of keys <= t: one compare per register, the lane counts come out of the scalar unit
-    // (ballot + s_bcnt1), no cross-lane shuffles in the bisection loop
-    auto count_le = [&](uint32_t t) {
-        uint32_t c = 0;
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) c += (uint32_t)__popcll(__ballot(key[i] <= t));
-        return c;
-    };
-    // smallest T with count(key <= T) >= nprobe (nprobe <= k, so T <= kmax)
-    // (kmin / kmax are the same in every lane after the butterfly: said explicitly, the bisection runs on scalar registers)
-    kmin = __builtin_amdgcn_readfirstlane(kmin), kmax = __builtin_amdgcn_readfirstlane(kmax);
-    uint32_t lo = kmin, hi = kmax, T = kmax;
-    bool exact = false;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        const uint32_t c = count_le(mid);
-        if (c == nprobe) {
-            T = mid;
-            exact = true;
-            break;
-        }
-        if (c > nprobe) hi = mid;
-        else lo = mid + 1;
-    }
-    if (!exact) T = lo;
-    uint32_t J = 0xFFFFFFFFu;  // among keys == T only ids <= J are taken
-    if (!exact) {
-        const uint32_t c_le = count_le(T);
-        if (c_le > nprobe) {  // ties at the threshold: the smallest list ids win
-            const uint32_t c_lt = T ? count_le(T - 1) : 0u;
-            const uint32_t need = nprobe - c_lt;  // >= 1
-            uint32_t jl = 0, jh = k - 1;
-            while (jl < jh) {
-                const uint32_t jm = jl + ((jh - jl) >> 1);
-                uint32_t c = 0;
-#pragma unroll
-                for (int i = 0; i < KPL; ++i) c += (key[i] == T && list_of(i) <= jm) ? 1u : 0u;
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
-                c = __builtin_amdgcn_readfirstlane(c);
-                if (c >= need) jh = jm;
-                else jl = jm + 1;
-            }
-            J = jl;
-        }
-    }
-    // compact the nprobe winners (key, id) into LDS
-    uint32_t base = 0;
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) {
-        const uint32_t j = list_of(i);
-        const bool take = key[i] < T || (key[i] == T && j <= J && j < k);
-        const uint64_t m = __ballot(take);
-        if (m) {  // wave-uniform
-            if (take) win[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = ((unsigned long long)key[i] << 32) | j;
-            base += (uint32_t)__popcll(m);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    unsigned long long v = lane < nprobe ? win[lane] : ~0ull;
-    // bitonic sort across the 64 lanes, ascending
-#pragma unroll
-    for (int size = 2; size <= 64; size <<= 1)
-#pragma unroll
-        for (int stride = size >> 1; stride >= 1; stride >>= 1) {
-            const unsigned long long other = __shfl_xor(v, stride, 64);
-            const bool up = (lane & size) == 0 || size == 64;
-            const bool lower = (lane & stride) == 0;
-            const bool take_min = lower == up;
-            const unsigned long long mn = other < v ? other : v, mx = other < v ? v : other;
-            v = take_min ? mn : mx;
-        }
-    if (lane < nprobe) {
-        out_cluster[(uint64_t)b * out_stride + lane] = (uint32_t)v + id_offset;
-        out_dist[(uint64_t)b * out_stride + lane] = ord32_unbias((uint32_t)(v >> 32));
-    }
-    for (uint32_t i = nprobe + lane; i < out_stride; i += 64) {  // fewer lists than requested: "no list"
-        out_cluster[(uint64_t)b * out_stride + i] = 0xFFFFFFFFu;
-        out_dist[(uint64_t)b * out_stride + i] = __builtin_inff();
-    }
-}
-template <int KPL>
-__global__ __launch_bounds__(256) void select_probe_wave_kernel(const float *__restrict__ dist, uint32_t k,
-                                                                uint32_t nprobe, uint32_t *__restrict__ out_cluster,
-                                                                float *__restrict__ out_dist, uint32_t id_offset,
-                                                                uint32_t out_stride, uint32_t nq) {
-    __shared__ unsigned long long win[4][64];
-    const uint32_t wave = threadIdx.x >> 6, b = blockIdx.x * 4 + wave;
-    if (b >= nq) return;
-    select_probe_wave<KPL>(dist, k, nprobe, out_cluster, out_dist, id_offset, out_stride, b, win[wave]);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Probe selection behind the matrix-core pre-filter of the coarse ranking (coarse_approx_kernel, kernels_build.h): `dist` holds
-// APPROXIMATE values a'_j = |c_j|^2 - 2 <c~_j, y~> (bf16 operands), each within m_y of e_j - |y|^2 (e_j = the reference's exact-order
-// f32 distance).  One wave per query:
-//   1. tau = the nprobe-th smallest a' of the row (the bisection of select_probe_wave);
-//   2. candidates = the lists with a' <= tau + 2 m_y: the true nprobe nearest -- and every exact tie with the nprobe-th -- are among
-//      them (kernels_build.h has the argument); typically nprobe + a few dozen;
-//   3. their EXACT distances in the reference's lane order (src/simd.rs:14-73: 8 GPU lanes = the 8 AVX lanes of one list, folded by
-//      reduce8_lanes), 8 lists per wave step;
-//   4. the nprobe smallest (distance, list id) keys of the candidates, ascending: exactly what select_probe_wave returns from a row of
-//      exact distances.
-// A row with more than RQ_COARSE_CAND candidates (near-equidistant centroids) or a margin that is not finite (NaN / inf input) is
-// ranked the plain way instead: the wave recomputes ALL k distances in exact order into the row and runs select_probe_wave on it.
-// ------------------------------------------------------------------------------------------------
-#define RQ_COARSE_CAND 256u
-// exact-order distance (src/simd.rs:14-73) of four lists per 8-lane group to the query row yr: lane al of a group carries AVX
-// lane al; all 8 lanes of the group return the folded sum.  dim is a multiple of 64: eight AVX steps at a time, all the loads
-// of a chunk in flight before the first is used (one load per step, as a plain loop compiles to, made the caller a chain of
-// 256 dependent L2 round trips per query).
-__device__ __forceinline__ void coarse_exact_dist4(const float *__restrict__ centroids, const float *__restrict__ yr, uint32_t dim,
-                                                   uint32_t al, const uint32_t (&jj)[4], float (&ee)[4]) {
-    const float *cp[4];
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) cp[q] = centroids + (uint64_t)jj[q] * dim + al;
-    for (uint32_t e0 = 0; e0 < dim; e0 += 64) {
-        float vv[4][8], yv[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            yv[i] = yr[e0 + 8 * i + al];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) vv[q][i] = cp[q][e0 + 8 * i];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float df = vv[q][i] - yv[i];
-                acc[q] = fmaf(df, df, acc[q]);
-            }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ee[q] = reduce8_lanes(acc[q]);
-}
-
-// The candidate lists wn[0 .. c2) (list ids; c2 <= RQ_COARSE_CAND, >= nprobe) of query row b: exact keys in the reference's lane
-// order, bitonic sort of the RQ_COARSE_CAND slots across the wave, the nprobe smallest written out in ascending order.
-__device__ __forceinline__ void coarse_refine_tail(unsigned long long *wn, uint32_t c2, const float *__restrict__ centroids,
-                                                   const float *__restrict__ yr, uint32_t dim, uint32_t nprobe, uint32_t b,
-                                                   uint32_t *__restrict__ out_cluster, float *__restrict__ out_dist, uint32_t out_stride) {
-    const uint32_t lane = threadIdx.x & 63, grp = lane >> 3, al = lane & 7;
-    // exact keys, 32 candidates per step
-    for (uint32_t c0 = 0; c0 < c2; c0 += 32) {
-        uint32_t jj[4];
-        float ee[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) jj[q] = c0 + 8 * q + grp < c2 ? (uint32_t)wn[c0 + 8 * q + grp] : 0u;
-        coarse_exact_dist4(centroids, yr, dim, al, jj, ee);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (c0 + 8 * q + grp < c2 && al == 0) wn[c0 + 8 * q + grp] = ((unsigned long long)ord32_biased(ee[q]) << 32) | jj[q];
-    }
-    for (uint32_t i = c2 + lane; i < RQ_COARSE_CAND; i += 64) wn[i] = ~0ull;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    // bitonic sort of the RQ_COARSE_CAND slots, ascending: element index i = lane + 64 s (s = the lane's slot); at a step (size, stride)
-    // element i keeps the minimum of (i, i ^ stride) iff ((i & stride) == 0) == ((i & size) == 0)  (the last size ascends everywhere)
-    constexpr int NS = RQ_COARSE_CAND / 64;
-    unsigned long long vs[NS];
-#pragma unroll
-    for (int sl = 0; sl < NS; ++sl) vs[sl] = wn[lane + 64 * sl];
-#pragma unroll
-    for (int size = 2; size <= 64 * NS; size <<= 1)
-#pragma unroll
-        for (int stride = size >> 1; stride >= 1; stride >>= 1) {
-            if (stride >= 64) {  // the partner is another slot of the same lane
-                const int ss = stride / 64;
-#pragma unroll
-                for (int sl = 0; sl < NS; ++sl) {
-                    if (sl & ss) continue;
-                    const bool asc = size >= 64 * NS || ((64 * sl) & size) == 0;
-                    const unsigned long long a0 = vs[sl], b0 = vs[sl | ss];
-                    const unsigned long long mn = a0 < b0 ? a0 : b0, mxv = a0 < b0 ? b0 : a0;
-                    vs[sl] = asc ? mn : mxv, vs[sl | ss] = asc ? mxv : mn;
-                }
-            } else {
-                const bool lower = (lane & stride) == 0;
-#pragma unroll
-                for (int sl = 0; sl < NS; ++sl) {
-                    const unsigned long long o = __shfl_xor(vs[sl], stride, 64);
-                    const bool asc = size < 64 ? (lane & size) == 0 : (size >= 64 * NS || ((64 * sl) & size) == 0);
-                    const unsigned long long mn = o < vs[sl] ? o : vs[sl], mxv = o < vs[sl] ? vs[sl] : o;
-                    vs[sl] = lower == asc ? mn : mxv;
-                }
-            }
-        }
-    const unsigned long long v0 = vs[0];
-    // v0 of lane l = the l-th smallest key
-    if (lane < nprobe) {
-        out_cluster[(uint64_t)b * out_stride + lane] = (uint32_t)v0;
-        out_dist[(uint64_t)b * out_stride + lane] = ord32_unbias((uint32_t)(v0 >> 32));
-    }
-    for (uint32_t i = nprobe + lane; i < out_stride; i += 64) {  // fewer lists than requested: "no list"
-        out_cluster[(uint64_t)b * out_stride + i] = 0xFFFFFFFFu;
-        out_dist[(uint64_t)b * out_stride + i] = __builtin_inff();
-    }
-}
-
-// the query's margin of the matrix-core pre-filter (kernels_build.h) -> the biased key of tau + 2 m (0xFFFFFFFF: not finite)
-__device__ __forceinline__ uint32_t coarse_margin_key(const float *__restrict__ yr, uint32_t dim, float cmax, float tau) {
-    const uint32_t lane = threadIdx.x & 63;
-    float yn = 0.0f;  // |y|^2 from an f32 sum (any order: its rounding is inside the factors below)
-    for (uint32_t e = lane; e < dim; e += 64) yn = fmaf(yr[e], yr[e], yn);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) yn += __shfl_xor(yn, o, 64);
-    const float rad = cmax + sqrtf(yn) * 1.000001f;
-    const float mx = (0.00390625f + (float)(2 * dim + 64) * 5.9604645e-8f) * 1.05f * (rad * rad);
-    float thr2 = tau + 2.0f * mx;
-    thr2 = thr2 + fabsf(thr2) * 1.0e-6f;  // the comparison's own rounding
-    const bool fin = fabsf(thr2) < 3.0e38f && fabsf(tau) < 3.0e38f;  // false for NaN / inf
-    return fin ? ord32_biased(thr2) : 0xFFFFFFFFu;
-}
-
-template <int KPL>
-__global__ __launch_bounds__(256) void select_refine_wave_kernel(float *__restrict__ dist, const float *__restrict__ y,
-                                                                 const float *__restrict__ centroids, float cmax, uint32_t k, uint32_t dim,
-                                                                 uint32_t nprobe, uint32_t *__restrict__ out_cluster,
-                                                                 float *__restrict__ out_dist, uint32_t out_stride, uint32_t nq,
-                                                                 unsigned long long *__restrict__ fallback_rows /* counter, may be null */) {
-    __shared__ unsigned long long win[4][RQ_COARSE_CAND];
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, b = blockIdx.x * 4 + wave;
-    if (b >= nq) return;
-    unsigned long long *wn = win[wave];
-    float *d = dist + (uint64_t)b * k;
-    const float *yr = y + (uint64_t)b * dim;
-    const uint32_t grp = lane >> 3, al = lane & 7;  // 8 lanes per list: AVX lane al of list slot grp
-    uint32_t key[KPL];
-    uint32_t kmin = 0xFFFFFFFFu, kmax = 0u;
-    auto list_of = [&](int i) { return 256u * (uint32_t)(i >> 2) + 4u * lane + (uint32_t)(i & 3); };
-    const bool vec4 = (k & 3u) == 0u;
-#pragma unroll
-    for (int i4 = 0; i4 < KPL; i4 += 4) {
-        const uint32_t j0 = list_of(i4);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (vec4 && j0 < k) {
-            v = *reinterpret_cast<const float4 *>(d + j0);
-        } else if (!vec4) {
-            if (j0 < k) v.x = d[j0];
-            if (j0 + 1 < k) v.y = d[j0 + 1];
-            if (j0 + 2 < k) v.z = d[j0 + 2];
-            if (j0 + 3 < k) v.w = d[j0 + 3];
-        }
-        const float ve[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int i = i4 + e;
-            key[i] = 0xFFFFFFFFu;
-            if (j0 + e < k) {
-                key[i] = ord32_biased(ve[e]);
-                kmin = key[i] < kmin ? key[i] : kmin;
-                kmax = key[i] > kmax ? key[i] : kmax;
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const uint32_t a = __shfl_xor(kmin, o, 64), c = __shfl_xor(kmax, o, 64);
-        kmin = a < kmin ? a : kmin;
-        kmax = c > kmax ? c : kmax;
-    }
-    auto count_le = [&](uint32_t t) {
-        uint32_t c = 0;
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) c += (uint32_t)__popcll(__ballot(key[i] <= t));
-        return c;
-    };
-    kmin = __builtin_amdgcn_readfirstlane(kmin), kmax = __builtin_amdgcn_readfirstlane(kmax);
-    // ANY T with count(key <= T) >= nprobe bounds the nprobe-th smallest a' from above, which is all the candidate rule needs: the
-    // bisection stops as soon as the count lands in [nprobe, nprobe + 12] (7-9 steps instead of the ~25 an exact threshold takes;
-    // the price is up to 12 more candidates)
-    uint32_t lo = kmin, hi = kmax;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        const uint32_t c = count_le(mid);
-        if (c >= nprobe) {
-            hi = mid;
-            if (c <= nprobe + 12) break;
-        } else {
-            lo = mid + 1;
-        }
-    }
-    const float tau = ord32_unbias(hi);
-    const uint32_t T2 = coarse_margin_key(yr, dim, cmax, tau);
-    const bool fin = T2 != 0xFFFFFFFFu;
-    const uint32_t c2 = fin ? count_le(T2) : 0xFFFFFFFFu;
-    if (!(c2 <= RQ_COARSE_CAND) || c2 < nprobe) {  // (wave-uniform) the plain way: every distance in exact order, then the exact selection
-        for (uint32_t j0 = 0; j0 < k; j0 += 32) {
-            uint32_t jj[4];
-            float ee[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) jj[q] = j0 + 8 * q + grp < k ? j0 + 8 * q + grp : 0u;
-            coarse_exact_dist4(centroids, yr, dim, al, jj, ee);
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (j0 + 8 * q + grp < k && al == 0) d[j0 + 8 * q + grp] = ee[q];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's own stores: read back below by other lanes of the wave
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        if (fallback_rows && lane == 0) atomicAdd(fallback_rows, 1ull);
-        select_probe_wave<KPL>(dist, k, nprobe, out_cluster, out_dist, 0u, out_stride, b, wn);
-        return;
-    }
-    // candidate ids into LDS (low half of the slots), in register order
-    uint32_t base = 0;
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) {
-        const bool take = key[i] <= T2;
-        const uint64_t m = __ballot(take);
-        if (m) {  // wave-uniform
-            if (take) wn[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = list_of(i);
-            base += (uint32_t)__popcll(m);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    coarse_refine_tail(wn, c2, centroids, yr, dim, nprobe, b, out_cluster, out_dist, out_stride);
-}
-
-
-// The same for MORE lists than a wave can hold in registers (k > 8192: the probe ranking of a multi-GPU deployment is over the
-// lists of ALL shards -- 32 768 at eight GPUs).  One sweep over the row of approximate distances leaves the minimum of every
-// TILE of 32 consecutive lists (k / 32 keys: 16 per lane at k = 32 768).  The nprobe-th smallest tile minimum bounds the row's
-// nprobe-th smallest a' from above (those nprobe minima are nprobe different lists), and tightly: the nearest lists of a query
-// rarely share a tile.  Only the tiles whose minimum is within the margin are read again for the candidates (a few dozen
-// 128-byte pieces instead of the row).  A row that cannot be handled (more than RQ_COARSE_CAND candidates, a margin that is not
-// finite) gets all its distances in exact order and its flag set: select_probe_kernel then selects those rows (redo_flag).
-// dynamic LDS: 4 x 64 TPL dwords (tile keys, then the flagged tiles, per wave)
-template <int TPL>
-__global__ __launch_bounds__(256) void select_refine_tiled_kernel(float *__restrict__ dist, const float *__restrict__ y,
-                                                                  const float *__restrict__ centroids, float cmax, uint32_t k, uint32_t dim,
-                                                                  uint32_t nprobe, uint32_t *__restrict__ out_cluster,
-                                                                  float *__restrict__ out_dist, uint32_t out_stride, uint32_t nq,
-                                                                  uint32_t *__restrict__ redo_flag,
-                                                                  unsigned long long *__restrict__ fallback_rows /* counter, may be null */) {
-    __shared__ unsigned long long win[4][RQ_COARSE_CAND];
-    extern __shared__ __attribute__((aligned(16))) uint32_t tile_lds[];
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, b = blockIdx.x * 4 + wave;
-    if (b >= nq) return;
-    unsigned long long *wn = win[wave];
-    uint32_t *tkeys = tile_lds + wave * (64 * TPL);
-    float *d = dist + (uint64_t)b * k;
-    const float *yr = y + (uint64_t)b * dim;
-    const uint32_t grp = lane >> 3, al = lane & 7;
-    const uint32_t ntile = (k + 31) / 32;  // <= 64 TPL (host)
-    const bool vec4 = (k & 3u) == 0u;
-    // sweep: 32 tiles (1024 lists) per step -- four 16-byte loads in flight per lane --, 4 lists per lane and load, the 8 lanes of
-    // a group fold one tile
-    for (uint32_t t0 = 0; t0 < ntile; t0 += 32) {
-        float4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const uint32_t j0 = (t0 + 8 * u) * 32 + lane * 4;
-            v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (vec4 && j0 < k) {
-                v[u] = *reinterpret_cast<const float4 *>(d + j0);
-            } else if (!vec4) {
-                if (j0 < k) v[u].x = d[j0];
-                if (j0 + 1 < k) v[u].y = d[j0 + 1];
-                if (j0 + 2 < k) v[u].z = d[j0 + 2];
-                if (j0 + 3 < k) v[u].w = d[j0 + 3];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const uint32_t j0 = (t0 + 8 * u) * 32 + lane * 4;
-            const float ve[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-            uint32_t mn = 0xFFFFFFFFu;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const uint32_t key = j0 + e < k ? ord32_biased(ve[e]) : 0xFFFFFFFFu;
-                mn = key < mn ? key : mn;
-            }
-#pragma unroll
-            for (int o = 4; o >= 1; o >>= 1) {
-                const uint32_t a = __shfl_xor(mn, o, 8);
-                mn = a < mn ? a : mn;
-            }
-            if (al == 0 && t0 + 8 * u + grp < 64 * TPL) tkeys[t0 + 8 * u + grp] = mn;  // (tiles past the last one come out as "no list")
-        }
-    }
-    for (uint32_t i = ((ntile + 31) & ~31u) + lane; i < 64 * TPL; i += 64) tkeys[i] = 0xFFFFFFFFu;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    uint32_t tk[TPL];  // tile lane + 64 i
-    uint32_t kmin = 0xFFFFFFFFu, kmax = 0u;
-#pragma unroll
-    for (int i = 0; i < TPL; ++i) {
-        tk[i] = tkeys[lane + 64 * i];
-        if (lane + 64 * i < ntile) {
-            kmin = tk[i] < kmin ? tk[i] : kmin;
-            kmax = tk[i] > kmax ? tk[i] : kmax;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const uint32_t a = __shfl_xor(kmin, o, 64), c = __shfl_xor(kmax, o, 64);
-        kmin = a < kmin ? a : kmin;
-        kmax = c > kmax ? c : kmax;
-    }
-    kmin = __builtin_amdgcn_readfirstlane(kmin), kmax = __builtin_amdgcn_readfirstlane(kmax);
-    auto count_le = [&](uint32_t t) {
-        uint32_t c = 0;
-#pragma unroll
-        for (int i = 0; i < TPL; ++i) c += (uint32_t)__popcll(__ballot(tk[i] <= t && lane + 64 * i < ntile));
-        return c;
-    };
-    uint32_t lo = kmin, hi = kmax;  // (ntile >= nprobe: count_le(kmax) = ntile >= nprobe)
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        const uint32_t c = count_le(mid);
-        if (c >= nprobe) {
-            hi = mid;
-            if (c <= nprobe + 12) break;
-        } else {
-            lo = mid + 1;
-        }
-    }
-    // every lane has its tile keys in registers by now: the LDS copy becomes the list of flagged tiles
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    // the lists with a' <= T (key << 32 | list id into the candidate slots): only tiles whose minimum is <= T are read again.
-    // false: more than RQ_COARSE_CAND of them
-    uint32_t base = 0;
-    auto collect = [&](uint32_t T) -> bool {
-        uint32_t nf = 0;
-#pragma unroll
-        for (int i = 0; i < TPL; ++i) {
-            const bool take = tk[i] <= T && lane + 64 * i < ntile;
-            const uint64_t m = __ballot(take);
-            if (m) {
-                if (take) tkeys[nf + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = lane + 64 * i;
-                nf += (uint32_t)__popcll(m);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        base = 0;
-        bool fits = true;
-        constexpr int CU_ = RQ_COLLECT_UNROLL;
-        for (uint32_t s0 = 0; fits && s0 < nf; s0 += 2 * CU_) {  // 2 CU_ flagged tiles per step (one per half-wave, CU_ loads in flight per lane:
-                                                                 // one at a time the loop was a chain of ~50 dependent L2 round trips per query)
-            uint32_t jv[CU_];
-            float dv[CU_];
-#pragma unroll
-            for (int u = 0; u < CU_; ++u) {
-                const uint32_t ti = s0 + 2 * u + (lane >> 5);
-                jv[u] = ti < nf ? tkeys[ti] * 32 + (lane & 31) : 0xFFFFFFFFu;
-            }
-#pragma unroll
-            for (int u = 0; u < CU_; ++u) dv[u] = jv[u] < k ? d[jv[u]] : 0.0f;
-#pragma unroll
-            for (int u = 0; u < CU_; ++u) {
-                const uint32_t key = ord32_biased(dv[u]);
-                const bool take = jv[u] < k && key <= T;
-                const uint64_t m = __ballot(take);
-                if (m) {  // wave-uniform
-                    const uint32_t cnt = (uint32_t)__popcll(m);
-                    if (base + cnt > RQ_COARSE_CAND) fits = false;
-                    else if (take) wn[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = ((unsigned long long)key << 32) | jv[u];
-                    base += cnt;
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        return fits;
-    };
-    // first with the bound the tile minima give (tight when the nearest lists sit in different tiles)
-    uint32_t T2 = ntile >= nprobe ? coarse_margin_key(yr, dim, cmax, ord32_unbias(hi)) : 0xFFFFFFFFu;
-    bool ok = T2 != 0xFFFFFFFFu;
-    if (ok && !collect(T2)) {
-        // too many lists within the margin of that bound (wide margins: high dimensions): the row's nprobe-th smallest a' itself --
-        // every list at or below the tile bound `hi` is collected (there are at least nprobe), bisection over those keys as the
-        // single-wave kernel does over the row -- and the margin from there
-        ok = collect(hi);
-        if (ok) {
-            uint32_t kk[RQ_COARSE_CAND / 64];
-#pragma unroll
-            for (int i = 0; i < (int)(RQ_COARSE_CAND / 64); ++i) kk[i] = lane + 64 * i < base ? (uint32_t)(wn[lane + 64 * i] >> 32) : 0xFFFFFFFFu;
-            uint32_t l2 = kmin, h2 = hi;
-            while (l2 < h2) {
-                const uint32_t mid = l2 + ((h2 - l2) >> 1);
-                uint32_t c = 0;
-#pragma unroll
-                for (int i = 0; i < (int)(RQ_COARSE_CAND / 64); ++i) c += (uint32_t)__popcll(__ballot(kk[i] <= mid));
-                if (c >= nprobe) {
-                    h2 = mid;
-                    if (c <= nprobe + 12) break;
-                } else {
-                    l2 = mid + 1;
-                }
-            }
-            T2 = coarse_margin_key(yr, dim, cmax, ord32_unbias(h2));
-            ok = T2 != 0xFFFFFFFFu && collect(T2);
-        }
-    }
-    if (!ok || base < nprobe) {  // (wave-uniform) the plain way: every distance in exact order; the block-per-query selection takes the row
-        for (uint32_t j0 = 0; j0 < k; j0 += 32) {
-            uint32_t jj[4];
-            float ee[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) jj[q] = j0 + 8 * q + grp < k ? j0 + 8 * q + grp : 0u;
-            coarse_exact_dist4(centroids, yr, dim, al, jj, ee);
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (j0 + 8 * q + grp < k && al == 0) d[j0 + 8 * q + grp] = ee[q];
-        }
-        if (lane == 0) {
-            redo_flag[b] = 1u;
-            if (fallback_rows) atomicAdd(fallback_rows, 1ull);
-        }
-        return;
-    }
-    if (lane == 0) redo_flag[b] = 0u;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    coarse_refine_tail(wn, base, centroids, yr, dim, nprobe, b, out_cluster, out_dist, out_stride);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -138,119 +138,18 @@ __global__ __launch_bounds__(256) void sb_front_kernel(const float *__restrict__
 // ------------------------------------------------------------------------------------------------
 // Probe selection, two levels (the same result as select_probe_wave: the nprobe smallest (Ord32 distance, list id)
 // pairs, ascending).  Level 1: each of the 16 waves selects the `want` smallest of its slice of the distance row
-// (<= 512 lists: 8 registers per lane) by bisection on the monotone u32 key, ties by list id, and sorts them across its
-// lanes; level 2 (select_merge16): every candidate's global rank = its place in its own slice + the number of smaller
-// keys in the other 15 sorted slices (binary searches in LDS) -- keys are unique, so ranks are a permutation and the
-// winners land at their final positions.
+// (<= 512 lists: 8 registers per lane) with the wave selection of kernels_coarse.h (select_row_wave: bisection on the
+// monotone u32 key, ties by list id, sorted across the lanes); level 2 (select_merge16): every candidate's global rank = its
+// place in its own slice + the number of smaller keys in the other 15 sorted slices (binary searches in LDS) -- keys are
+// unique, so ranks are a permutation and the winners land at their final positions.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void select_slice_wave(const float *__restrict__ d, uint32_t slen, uint32_t want, bool vec4,
                                                   uint32_t id_offset, unsigned long long *__restrict__ out /* 64, LDS */,
                                                   unsigned long long *win /* 64, LDS, this wave's */) {
-    constexpr int KPL = 8;
     const uint32_t lane = threadIdx.x & 63;
-    uint32_t key[KPL];
-    uint32_t kmin = 0xFFFFFFFFu, kmax = 0u;
-    auto list_of = [&](int i) { return 256u * (uint32_t)(i >> 2) + 4u * lane + (uint32_t)(i & 3); };
-#pragma unroll
-    for (int i4 = 0; i4 < KPL; i4 += 4) {
-        const uint32_t j0 = list_of(i4);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (vec4 && j0 + 3 < slen) {
-            v = *reinterpret_cast<const float4 *>(d + j0);
-        } else {
-            if (j0 < slen) v.x = d[j0];
-            if (j0 + 1 < slen) v.y = d[j0 + 1];
-            if (j0 + 2 < slen) v.z = d[j0 + 2];
-            if (j0 + 3 < slen) v.w = d[j0 + 3];
-        }
-        const float ve[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int i = i4 + e;
-            key[i] = 0xFFFFFFFFu;  // "no list"
-            if (j0 + e < slen) {
-                key[i] = ord32_biased(ve[e]);
-                kmin = key[i] < kmin ? key[i] : kmin;
-                kmax = key[i] > kmax ? key[i] : kmax;
-            }
-        }
-    }
     out[lane] = ~0ull;
-    if (want == 0) return;  // wave-uniform
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const uint32_t a = __shfl_xor(kmin, o, 64), c = __shfl_xor(kmax, o, 64);
-        kmin = a < kmin ? a : kmin;
-        kmax = c > kmax ? c : kmax;
-    }
-    auto count_le = [&](uint32_t t) {
-        uint32_t c = 0;
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) c += (uint32_t)__popcll(__ballot(key[i] <= t));
-        return c;
-    };
-    // (the same in every lane after the butterfly: said explicitly so that the bisection below runs on scalar registers)
-    kmin = __builtin_amdgcn_readfirstlane(kmin), kmax = __builtin_amdgcn_readfirstlane(kmax);
-    uint32_t lo = kmin, hi = kmax, T = kmax;
-    bool exact = false;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        const uint32_t c = count_le(mid);
-        if (c == want) {
-            T = mid;
-            exact = true;
-            break;
-        }
-        if (c > want) hi = mid;
-        else lo = mid + 1;
-    }
-    if (!exact) T = lo;
-    uint32_t J = 0xFFFFFFFFu;  // among keys == T only (slice-local) ids <= J are taken
-    if (!exact) {
-        const uint32_t c_le = count_le(T);
-        if (c_le > want) {  // ties at the threshold: the smallest list ids win
-            const uint32_t c_lt = T ? count_le(T - 1) : 0u;
-            const uint32_t need = want - c_lt;  // >= 1
-            uint32_t jl = 0, jh = slen - 1;
-            while (jl < jh) {
-                const uint32_t jm = jl + ((jh - jl) >> 1);
-                uint32_t c = 0;
-#pragma unroll
-                for (int i = 0; i < KPL; ++i) c += (key[i] == T && list_of(i) <= jm) ? 1u : 0u;
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
-                c = __builtin_amdgcn_readfirstlane(c);
-                if (c >= need) jh = jm;
-                else jl = jm + 1;
-            }
-            J = jl;
-        }
-    }
-    uint32_t base = 0;
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) {
-        const uint32_t j = list_of(i);
-        const bool take = j < slen && (key[i] < T || (key[i] == T && j <= J));
-        const uint64_t m = __ballot(take);
-        if (m) {
-            if (take) win[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = ((unsigned long long)key[i] << 32) | (j + id_offset);
-            base += (uint32_t)__popcll(m);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    unsigned long long v = lane < want ? win[lane] : ~0ull;
-#pragma unroll
-    for (int size = 2; size <= 64; size <<= 1)
-#pragma unroll
-        for (int stride = size >> 1; stride >= 1; stride >>= 1) {
-            const unsigned long long other = __shfl_xor(v, stride, 64);
-            const bool up = (lane & size) == 0 || size == 64;
-            const bool lower = (lane & stride) == 0;
-            const bool take_min = lower == up;
-            const unsigned long long mn = other < v ? other : v, mx = other < v ? v : other;
-            v = take_min ? mn : mx;
-        }
-    out[lane] = v;
+    if (want == 0) return;  // wave-uniform (an empty slice)
+    out[lane] = select_row_wave<8>(d, slen, want, vec4, id_offset, win);
 }
 
 // level 2, all 1024 threads (thread = candidate (w, i)); cand[16][64] sorted ascending per slice, padded with ~0

@@ -10,7 +10,7 @@ import os
 import numpy as np
 import pytest
 
-from tests import synth
+from tests import coarse_cases, synth
 from tests.models import bits, compare_with_oracle as _compare_with_oracle
 
 pytestmark = pytest.mark.gpu
@@ -311,36 +311,17 @@ def test_additive_gate_falls_back_when_it_flags_too_much(rq, oracle):
     oidx.close()
 
 
-@pytest.mark.parametrize("d,k,nq,probe,kind", [(128, 4096, 3000, 64, "mixture"), (128, 300, 2500, 64, "mixture"), (64, 1000, 2100, 33, "ties"),
-                                                  (256, 700, 2100, 64, "equidistant"), (768, 260, 2100, 20, "mixture"),
-                                                  (128, 5000, 2200, 64, "scaled"), (128, 130, 2100, 1, "nan"),
-                                                  # more lists than one wave holds in registers (the ranking of a multi-GPU deployment is over
-                                                  # all shards' lists): the tile-minima selection, its per-row fall-back included
-                                                  (128, 9000, 2100, 64, "mixture"), (64, 33000, 2050, 33, "mixture"), (128, 20000, 2100, 64, "ties"),
-                                                  (128, 10000, 2060, 64, "equidistant"), (128, 8300, 2100, 40, "nan"), (128, 16500, 2100, 64, "scaled"),
-                                                  (64, 40001, 2050, 64, "mixture")])
+@pytest.mark.parametrize("d,k,nq,probe,kind", coarse_cases.PREFILTER_CASES)
 def test_prefiltered_coarse_ranking_equals_exact_order_kernels(rq, d, k, nq, probe, kind):
     """Coarse ranking through the bf16 matrix-core pre-filter + exact-order refinement (coarse_impl = 3; automatic for big batches)
     against the plain exact-order kernel + selection (rq_coarse_rank): list ids and distance bits of every probe list.
     ties: duplicate centroids (exact ties at the selection threshold); equidistant: centroids on a sphere around the queries (more
-    candidates than the refinement holds: the in-kernel exact fall-back); scaled: coordinates x 3e3; nan: a NaN query."""
+    candidates than the refinement holds: the in-kernel exact fall-back); scaled: coordinates x 3e3; nan: a NaN query.  The inputs
+    come from tests/coarse_cases.py; test_coarse_cases.py shows that its last case drives the tiled selection through its second collect."""
     import torch
     from rabitq_amd import index as ix
     dev = torch.device("cuda", 0)
-    rng = np.random.default_rng(d + k)
-    centres = rng.standard_normal((k, d)).astype(np.float32)
-    queries = (centres[rng.integers(0, k, nq)] + 0.5 * rng.standard_normal((nq, d))).astype(np.float32)
-    if kind == "ties":
-        centres[k // 2:] = centres[: k - k // 2]            # every centroid twice
-    elif kind == "equidistant":
-        centres /= np.linalg.norm(centres, axis=1, keepdims=True)
-        queries = (1e-3 * rng.standard_normal((nq, d))).astype(np.float32)   # all lists at distance ~1: hundreds within the margin
-    elif kind == "scaled":
-        centres *= np.float32(3e3)
-        queries *= np.float32(3e3)
-    elif kind == "nan":
-        queries[5, 3] = np.nan
-    x = centres[rng.integers(0, k, 4 * k)] + 0.1 * rng.standard_normal((4 * k, d)).astype(np.float32)
+    centres, queries, x = coarse_cases.prefilter_case(d, k, nq, kind)
     idx = rq.RaBitQ.build(x.astype(np.float32), centres, synth.random_orthogonal(d, seed=9))
     _, want_cl, want_cd = rq.ops.coarse_rank(idx, queries, probe)          # the plain exact-order kernel + selection
     q = torch.from_numpy(queries).to(dev)
@@ -407,6 +388,32 @@ def test_small_batch_path_matches_oracle(rq, oracle, n, d, k):
             assert (ma["rough"], ma["precise"]) == (2 * mb["rough"], 2 * mb["precise"])   # ma: two calls since the reset
     finally:
         ix.set_option("small_batch", 0)
+    gidx.close()
+    oidx.close()
+
+
+def test_probe_selection_splits_tied_pairs(rq, oracle):
+    """Exact ties AT the selection threshold, in both wave selections (kernels_coarse.h): every centroid appears twice, at
+    neighbouring list ids, so an odd probe count always cuts a pair and the smaller id must win (the oracle's order: ascending
+    list id among equal distances).  40 queries take the small-batch path, where each of the 16 slices of 76 lists selects its own
+    33 smallest (a cut pair in every slice) before the merge; 100 queries take select_probe_wave_kernel<64> over the whole row.
+    probe = 1 cuts the nearest pair.  The twin with the larger id owns no vectors (assignment takes the first minimum), so a pair
+    cut the wrong way changes the candidates scanned, which the comparison counts (rough / precise), and at probe = 1 the answer."""
+    from rabitq_amd import index as ix
+    d, k, n = 64, 1200, 6000
+    rng = np.random.default_rng(d + k)
+    centres = rng.standard_normal((k, d)).astype(np.float32)
+    centres[1::2] = centres[0::2]
+    x = (centres[rng.integers(0, k, n)] + 0.3 * rng.standard_normal((n, d))).astype(np.float32)
+    queries = (centres[rng.integers(0, k, 100)] + 0.5 * rng.standard_normal((100, d))).astype(np.float32)
+    P = synth.random_orthogonal(d, seed=d + 7)
+    oidx = oracle.OracleIndex.build(x, centres, P)
+    gidx = rq.RaBitQ.build(x, centres, P)
+    assert np.array_equal(gidx.offsets, oidx.offsets) and np.all(np.diff(oidx.offsets.astype(np.int64))[1::2] == 0)
+    for nq, small in ((40, 1), (100, 0)):
+        for probe in (33, 1):
+            _compare_with_oracle(rq, oracle, oidx, gidx, queries[:nq], probe, 10, False)
+            assert ix.last_profile()["small_batch_passes"] == small, (nq, probe)
     gidx.close()
     oidx.close()
 
