@@ -580,6 +580,7 @@ rq_status rq_set_profiling(int level);
  * list-major once its (query, list) pairs reach k / this; default 32), "stage_settle_pct" (where a large batch's early stages end,
  * in percent of the average list length; default 100), "scan_debug": measurement hooks under which every result is UNCHANGED -- 128 (kept for older hosts: the sub-tile /
  * exact-path step counters of rq_profile_t are always on since ABI revision 4), 512 no shadow rows in the rerank,
+ * 2048 long run directories skip the cell bitmap (they are ordered by the slot buckets, or the bitonic sort: a test hook),
  * 4096 the phases of the small-batch kernel, 16384 the stage list of every pass (stderr).  Any other bit is refused with
  * RQ_ERR_INVALID by this library: the TIMING ABLATIONS of the matrix-core scan (1, 2, 4, 64, 1024, 8192: results are WRONG) and
  * its in-kernel cycle counters (256) are compiled only into the developer build (make -C rabitq_amd/csrc dev ->

@@ -225,3 +225,87 @@ __device__ __forceinline__ void bitonic_sort_block(T *a, uint32_t n, KeyFn key) 
         }
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// Integer prefix sums.  All of them add in lane / wave / element order; the sums are integer, so no result depends on that.
+// ------------------------------------------------------------------------------------------------
+// inclusive prefix sum across the 64 lanes of a wave: lane l receives v of lanes 0 .. l (every lane of the wave must call)
+template <typename T>
+__device__ __forceinline__ T wave_incl_scan(T v) {
+    const int lane = (int)(threadIdx.x & 63);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T up = __shfl_up(v, o, 64);
+        if (lane >= o) v += up;
+    }
+    return v;
+}
+
+// Exclusive prefix sum of n values of any length by ONE block of 1024 threads: rounds of 1024 elements, a carry between the
+// rounds, three barriers per round.  value(i) is element i, store(i, excl, v) receives its exclusive prefix (and the value);
+// the total is returned to every thread.  I: the index type (64-bit where n may be within 1024 of 2^32).
+template <typename T, typename I, typename ValueFn, typename StoreFn>
+__device__ __forceinline__ T block_scan_chunked(I n, ValueFn value, StoreFn store) {
+    __shared__ T wsum[16];
+    __shared__ T carry;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    if (tid == 0) carry = 0;
+    __syncthreads();
+    for (I base = 0; base < n; base += 1024) {
+        const I i = base + tid;
+        const T v = i < n ? (T)value(i) : (T)0;
+        const T incl = wave_incl_scan(v);
+        if (lane == 63) wsum[wid] = incl;
+        __syncthreads();
+        T woff = 0;
+        for (uint32_t w = 0; w < wid; ++w) woff += wsum[w];
+        const T c0 = carry;
+        if (i < n) store(i, c0 + woff + incl - v, v);
+        __syncthreads();
+        if (tid == 1023) carry = c0 + woff + incl;
+        __syncthreads();
+    }
+    return carry;
+}
+
+// Exclusive prefix sum of n values (LDS-resident, a few per thread) by the whole block, any block size up to 1024: every thread
+// owns a contiguous stretch of ceil(n / blockDim.x) elements, sums it, the stretch sums are scanned across the block (wsum: 16
+// words of LDS, free on entry), and the thread walks its stretch again: store(i, excl) receives element i's exclusive prefix
+// and may overwrite what value(i) reads.  TOTAL: the sum of all n values is returned to every thread (block-uniform; 0
+// otherwise: callers that do not need it add up the waves before their own only).  One barrier inside; the caller puts one
+// behind the call before anybody reads another thread's stores.
+template <bool TOTAL = false, typename ValueFn, typename StoreFn>
+__device__ __forceinline__ uint32_t block_scan_stretch(uint32_t n, uint32_t *wsum, ValueFn value, StoreFn store) {
+    const uint32_t tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t per = (n + nthr - 1) / nthr, i0 = tid * per < n ? tid * per : n, i1 = i0 + per < n ? i0 + per : n;
+    uint32_t sum = 0;
+    for (uint32_t i = i0; i < i1; ++i) sum += value(i);
+    const uint32_t incl = wave_incl_scan(sum);
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    uint32_t run = incl - sum, all = 0;
+    if constexpr (TOTAL) {
+        for (uint32_t w = 0; w < (nthr >> 6); ++w) {
+            if (w < wave) run += wsum[w];
+            all += wsum[w];
+        }
+    } else {
+        for (uint32_t w = 0; w < wave; ++w) run += wsum[w];
+    }
+    for (uint32_t i = i0; i < i1; ++i) {
+        const uint32_t c = value(i);
+        store(i, run);
+        run += c;
+    }
+    return all;
+}
+
+// pref[0 .. 64]: exclusive prefix sums of a chunk of 64 counts in LDS (pref[0] = 0).  The largest r < 64 with pref[r] <= e, i.e.
+// the run that element e < pref[64] of the chunk belongs to, empty runs skipped: a six-step bisection.
+__device__ __forceinline__ uint32_t run_of_prefix(const uint32_t *pref, uint32_t e) {
+    uint32_t lo = 0;
+#pragma unroll
+    for (int step = 32; step >= 1; step >>= 1)
+        if (lo + step < 64 && pref[lo + step] <= e) lo += step;
+    return lo;
+}

@@ -559,6 +559,9 @@ struct Pass {
         return RQ_OK;
     }
 
+    // sort_runs_mid_kernel's bitmap words; scan_debug bit 2048 (test hook): none, so long directories take the fall-back orderings
+    uint32_t mid_lds_words() const { return (pl.dbg & 2048) ? 0u : RQ_SORT_MID_LDS_WORDS; }
+
     // small batch: one fused launch per stage (launch-bound regime)
     void stage_finish_small(StageRun &r) {
         const QSeg &seg = r.seg;
@@ -572,7 +575,7 @@ struct Pass {
             sort_runs_kernel<<<nq, 64, 0, st>>>(ws.runs.p, ws.surv_cnt.p, seg, ws.big_list.p, ws.big_list.p + nq, RQ_SORT_LDS_RECS, nullptr);
             sort_runs_mid_kernel<<<std::min(nq, 256u), 256, RQ_SORT_MID_LDS_WORDS * 8, st>>>(ws.runs.p, ws.use_runs_tmp ? ws.runs_tmp.p : nullptr, ws.surv_cnt.p,
                                                                                           seg, ws.big_list.p, ws.big_list.p + nq, nprobe, 0u,
-                                                                                          RQ_SORT_MID_LDS_WORDS);
+                                                                                          mid_lds_words());
         }
         if (pl.small && !qp.heuristic) {  // small-batch path, heap ranker: the stage's finish also writes the results and the totals
             // a handful of queries: their final-stage survivors (~1000 rows each) are gathered by the whole chip -- one block
@@ -629,7 +632,7 @@ struct Pass {
             // queries with long run directories (loose thresholds, very unequal lists): cell-bitmap ordering, persistent blocks walking the list
             sort_runs_mid_kernel<<<pl.mid_blocks, 256, RQ_SORT_MID_LDS_WORDS * 8, st>>>(ws.runs.p, (ws.use_runs_tmp || r.runs_in_tmp) ? ws.runs_tmp.p : nullptr,
                                                                                        ws.surv_cnt.p, seg, ws.big_list.p, ws.big_list.p + nq, nprobe,
-                                                                                       r.runs_in_tmp ? 1u : 0u, RQ_SORT_MID_LDS_WORDS);
+                                                                                       r.runs_in_tmp ? 1u : 0u, mid_lds_words());
             pf.end();
         }
         pf.begin(PF_REPLAY);

@@ -378,11 +378,7 @@ __global__ __launch_bounds__(256) void select_probe_kernel(const float *__restri
         __syncthreads();
         if (tid < 64) {  // wave 0: locate the bin holding rank `want`
             uint32_t h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-            uint32_t s = h0 + h1 + h2 + h3, incl = s;
-            for (int o = 1; o < 64; o <<= 1) {
-                uint32_t up = __shfl_up(incl, o, 64);
-                if ((int)tid >= o) incl += up;
-            }
+            const uint32_t s = h0 + h1 + h2 + h3, incl = wave_incl_scan(s);
             uint32_t excl = incl - s;
             if (excl < want && want <= incl) {
                 uint32_t r = want - excl, sel, cntbin;

@@ -1,15 +1,19 @@
-// kernels_query.h -- gfx950 kernels for RaBitQ::query (src/rabitq.rs:268-367, src/rerank.rs).
+// kernels_query.h -- gfx950 kernels of RaBitQ::query (src/rabitq.rs:268-367) around the scan: what prepares a stage and
+// what moves its survivors.  The stages themselves live in headers of their own, included here in pipeline order:
+//   kernels_coarse.h   the coarse ranking (src/rabitq.rs:283-297)
+//   kernels_scan_*.h   the scan (translation units of their own; kernels_scan_common.h: the record layout shared with them)
+//   kernels_rerank.h   exact distances of the survivors (src/rerank.rs:85-90)
+//   kernels_replay.h   the survivors' visiting order, the replay of the reference's rankers, the result writers
+// In this file: query padding and the VALU rotation, the shard merge, the per-(query, list) quantisation (prep_*), the
+// candidate stream's prefix sums (pair_prefix_*), the filter bitmaps, a stage's work lists (group_*, stage_fill_*,
+// stage_tail_kernel), the generic-width and dense scans; behind the includes: the rerank order of a large batch (order_*), the
+// survivor arena (seg_exact / arena_scatter / seg_scan), the dense directory's clear and the scan's step counters (stat_fold).
 //
-// Mapping (MI355X-first, not a translation of the reference's per-vector SIMD loop):
-//   * candidates live one-per-lane in VGPRs (code words + Factor), queries stream through the
-//     scalar unit: every per-query operand (bit planes, lower/delta/sum, threshold) is
-//     wave-uniform, so it is fetched with s_load and fed to VALU ops as an SGPR operand.  A list is
-//     read from HBM once per launch and scored against every query of the batch that probes it.
-//   * the scan filters against the per-query re-rank threshold in-kernel and emits only
-//     survivors; exact f32 distances are computed for survivors only; an ordered replay of the
-//     reference's heap logic over (rough, accurate) pairs reproduces its result id-for-id.
-//
-// The coarse ranking (src/rabitq.rs:283-297) is in kernels_coarse.h, the re-rank stage in kernels_rerank.h.
+// Mapping (MI355X-first, not a translation of the reference's per-vector SIMD loop): candidates live one per lane in VGPRs,
+// queries stream through the scalar unit -- every per-query operand is wave-uniform and reaches the VALU as an SGPR operand --
+// and a list is read from HBM once per launch for every query of the batch that probes it.  The scan emits only the survivors
+// of the per-query re-rank threshold; exact f32 distances are computed for those alone; an ordered replay of the reference's
+// heap logic over (rough, accurate) pairs reproduces its result id for id.
 #pragma once
 #include "common.h"
 #include "kernels_scan_common.h"
@@ -515,12 +519,7 @@ __device__ __forceinline__ void pair_prefix_row(PairScalars *__restrict__ scal, 
             len = c < nlists ? offsets[c + 1] - offsets[c] : 0u;
         } else
             len = s < nprobe ? ps->list_len : 0;
-        unsigned long long incl = len;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long up = __shfl_up(incl, o, 64);
-            if ((int)lane >= o) incl += up;
-        }
+        const unsigned long long incl = wave_incl_scan(len);
         const unsigned long long begin = carry + incl - len;
         if (s < nprobe) *(begin_out ? begin_out + (uint64_t)b * nprobe + s : &ps->stream_begin) = begin > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)begin;
         carry += __shfl(incl, 63, 64);
@@ -665,27 +664,9 @@ __global__ __launch_bounds__(1024) void group_rank_kernel(const PairScalars *__r
 __global__ __launch_bounds__(1024) void group_scan_kernel(uint32_t *__restrict__ cnt, uint32_t k,
                                                           uint32_t *__restrict__ start, uint32_t pad32,
                                                           uint32_t *__restrict__ recs, uint32_t opdw) {
-    __shared__ uint32_t wsum[16];
-    __shared__ uint32_t carry;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < k; base += 1024) {
-        uint32_t i = base + tid;
-        uint32_t v = i < k ? cnt[i] : 0;
-        if (pad32 & 1u) v = (v + 31u) & ~31u;
-        uint32_t incl = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            uint32_t up = __shfl_up(incl, o, 64);
-            if ((int)lane >= o) incl += up;
-        }
-        if (lane == 63) wsum[wid] = incl;
-        __syncthreads();
-        uint32_t woff = 0;
-        for (uint32_t w = 0; w < wid; ++w) woff += wsum[w];
-        uint32_t c0 = carry;
-        if (i < k) {
-            const uint32_t st0 = c0 + woff + incl - v;
+    const uint32_t total = block_scan_chunked<uint32_t, uint32_t>(
+        k, [&](uint32_t i) { return (pad32 & 1u) ? (cnt[i] + 31u) & ~31u : cnt[i]; },
+        [&](uint32_t i, uint32_t st0, uint32_t v) {
             start[i] = st0;
             if ((pad32 & 1u) && recs) {
                 const uint32_t real = cnt[i];
@@ -702,12 +683,8 @@ __global__ __launch_bounds__(1024) void group_scan_kernel(uint32_t *__restrict__
                 }
             }
             if (!(pad32 & 2u)) cnt[i] = 0;  // bit 1: the places are already known (group_rank_kernel), cnt stays the count
-        }
-        __syncthreads();
-        if (tid == 1023) carry = c0 + woff + incl;
-        __syncthreads();
-    }
-    if (tid == 0) start[k] = carry;
+        });
+    if (threadIdx.x == 0) start[k] = total;
 }
 
 // f32 -> bf16 bits (round to nearest even) and back; finite inputs well inside the f32 range
@@ -1124,498 +1101,7 @@ __global__ __launch_bounds__(256) void scan_dense_kernel(const uint32_t *__restr
 }
 
 #include "kernels_rerank.h"  // the exact re-rank stage: exact distances, shadow rows, pre-filter kernels
-
-// ------------------------------------------------------------------------------------------------
-// Restore the reference's visiting order among a query's survivors: ascending (slot, position)
-// (src/rabitq.rs:304 outer loop, :348 inner loop).  One block per query; LDS when it fits.
-// ------------------------------------------------------------------------------------------------
-#define RQ_SORT_LDS_RECS 2048
-template <typename T, uint32_t LDS_RECS = RQ_SORT_LDS_RECS>
-__device__ __forceinline__ void sort_segment(T *recs, uint32_t n, const T *src = nullptr /* the unsorted records, when not in place */) {
-    __shared__ T lds[LDS_RECS];
-    if (!src) src = recs;
-    if (n < 2 && src == recs) return;
-    auto key = [](const T &r) { return surv_key(r); };
-    if (n <= LDS_RECS) {
-        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) lds[i] = src[i];
-        __syncthreads();
-        bitonic_sort_block(lds, n, key);
-        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) recs[i] = lds[i];
-    } else {
-        if (src != recs) {
-            for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) recs[i] = src[i];
-            __threadfence_block();
-        }
-        __syncthreads();
-        bitonic_sort_block(recs, n, key);  // in global memory (L2), rare
-    }
-}
-// The run directory ordered by (slot, position) without a comparison sort over the whole directory: runs are
-// bucketed by probe slot into a second buffer (LDS histogram + scatter: O(n)), then every bucket -- the runs one list
-// contributed -- is ordered by position by ONE wave through rank counting (a run's final place is the number of
-// smaller positions in its bucket; the bucket's positions are staged through LDS in chunks and compared four at a
-// time) and written back to the directory at its final index.  Block-cooperative; needs nslots <= MAX_SLOTS.
-#define RQ_BUCKET_CHUNK 1024u
-#define RQ_SORT_MID_LDS_WORDS 14336u  // dwords of each of the two dynamic-LDS arrays of order_runs_bitmap: 458 752 cells = 14.7M list positions per query
-template <uint32_t MAX_SLOTS>
-__device__ __forceinline__ void sort_runs_by_slot(RunRec *__restrict__ dir, RunRec *__restrict__ tmp, uint32_t n, uint32_t nslots) {
-    __shared__ uint32_t start[MAX_SLOTS + 1], cursor[MAX_SLOTS];
-    __shared__ uint32_t wsum[16];
-    __shared__ __attribute__((aligned(16))) uint32_t keys[4][RQ_BUCKET_CHUNK];  // per wave (blocks of 256 threads)
-    const uint32_t tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nwaves = nthr >> 6;
-    for (uint32_t i = tid; i < nslots; i += nthr) cursor[i] = 0;
-    __syncthreads();
-    for (uint32_t i = tid; i < n; i += nthr) atomicAdd(&cursor[dir[i].slot], 1u);
-    __syncthreads();
-    {  // exclusive scan of the bucket sizes: each thread owns a contiguous stretch of buckets
-        const uint32_t per = (nslots + nthr - 1) / nthr, b0 = tid * per < nslots ? tid * per : nslots;
-        const uint32_t b1 = b0 + per < nslots ? b0 + per : nslots;
-        uint32_t sum = 0;
-        for (uint32_t i = b0; i < b1; ++i) sum += cursor[i];
-        uint32_t incl = sum;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t up = __shfl_up(incl, o, 64);
-            if ((int)lane >= o) incl += up;
-        }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        uint32_t run = incl - sum;
-        for (uint32_t w = 0; w < wave; ++w) run += wsum[w];
-        for (uint32_t i = b0; i < b1; ++i) {
-            const uint32_t c = cursor[i];
-            start[i] = run;
-            cursor[i] = run;
-            run += c;
-        }
-        if (tid == 0) start[nslots] = n;
-    }
-    __syncthreads();
-    for (uint32_t i = tid; i < n; i += nthr) {
-        const RunRec r = dir[i];
-        tmp[atomicAdd(&cursor[r.slot], 1u)] = r;
-    }
-    __threadfence_block();
-    __syncthreads();  // every record is in tmp (bucketed); dir is free to receive the final order
-    for (uint32_t sl = wave; sl < nslots; sl += nwaves) {  // one wave per bucket
-        const uint32_t b0 = start[sl], m = start[sl + 1] - b0;
-        if (m == 0) continue;
-        const RunRec *seg = tmp + b0;
-        if (m == 1) {
-            if (lane == 0) dir[b0] = seg[0];
-            continue;
-        }
-        const bool one_chunk = m <= RQ_BUCKET_CHUNK;  // the usual case: the bucket's positions are staged once
-        auto stage_keys = [&](uint32_t c0, uint32_t cm) {
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();  // the previous contents have been consumed by every lane
-            for (uint32_t t = lane; t < ((cm + 3) & ~3u); t += 64) keys[wave][t] = t < cm ? seg[c0 + t].pos : 0xFFFFFFFFu;
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        };
-        if (one_chunk) stage_keys(0, m);
-        for (uint32_t e0 = 0; e0 < m; e0 += 64) {  // 64 runs of the bucket at a time, one per lane
-            RunRec mine;
-            mine.pos = 0xFFFFFFFFu;
-            if (e0 + lane < m) mine = seg[e0 + lane];
-            uint32_t rank = 0;
-            for (uint32_t c0 = 0; c0 < m; c0 += RQ_BUCKET_CHUNK) {
-                const uint32_t cm = m - c0 < RQ_BUCKET_CHUNK ? m - c0 : RQ_BUCKET_CHUNK;
-                if (!one_chunk) stage_keys(c0, cm);
-                for (uint32_t t = 0; t < cm; t += 4) {
-                    const uint4 kq = *reinterpret_cast<const uint4 *>(&keys[wave][t]);  // same address in every lane: broadcast
-                    rank += (kq.x < mine.pos ? 1u : 0u) + (kq.y < mine.pos ? 1u : 0u) + (kq.z < mine.pos ? 1u : 0u) +
-                            (kq.w < mine.pos ? 1u : 0u);
-                }
-            }
-            if (e0 + lane < m) dir[b0 + rank] = mine;  // positions are unique within a bucket: ranks are a permutation
-        }
-    }
-}
-
-// The same ordering in O(n), for directories whose position span fits an LDS bitmap (the usual case: the final stage of a
-// batch on an index with very unequal lists leaves tens of thousands of runs per query, thousands per list, where the rank
-// counting above is quadratic).  Within a probe slot (= one list) the runs of one stage sit on distinct 32-position
-// cells of the list (a run = one query x one 32- or 64-position sub-tile, common.h), so a run's final index is the number
-// of occupied cells before its own: cell = cellbase[slot] + (pos - minpos[slot]) / 32 over a bitmap of the query's cells
-// (one bit per 32 list positions of every probed list that contributed), rank = popcount prefix.  Three passes over the
-// descriptors (L2), no comparison.  `src` are the unsorted descriptors, `out` receives the order (out != src).  Returns
-// false -- nothing written -- when the bitmap does not fit `cap_words` or two runs share a cell (not produced by the
-// scans; the caller then falls back to the bucket ranking).
-template <uint32_t MAX_SLOTS>
-__device__ __forceinline__ bool order_runs_bitmap(const RunRec *src, RunRec *out, uint32_t n, uint32_t nslots, uint32_t *words /* [cap_words] */,
-                                                  uint32_t *wpre /* [cap_words] */, uint32_t cap_words) {
-    __shared__ uint32_t minpos[MAX_SLOTS], cellbase[MAX_SLOTS];  // cellbase holds the slot's largest position first
-    __shared__ uint32_t bsum[17];
-    const uint32_t tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6;
-    for (uint32_t i = tid; i < nslots; i += nthr) minpos[i] = 0xFFFFFFFFu, cellbase[i] = 0u;
-    __syncthreads();
-    for (uint32_t i = tid; i < n; i += nthr) {
-        const RunRec r = src[i];
-        atomicMin(&minpos[r.slot], r.pos);
-        atomicMax(&cellbase[r.slot], r.pos);
-    }
-    __syncthreads();
-    // exclusive scan of the slots' cell counts (each thread owns a contiguous stretch of slots)
-    uint32_t total_cells;
-    {
-        const uint32_t per = (nslots + nthr - 1) / nthr, b0 = tid * per < nslots ? tid * per : nslots;
-        const uint32_t b1 = b0 + per < nslots ? b0 + per : nslots;
-        uint32_t sum = 0;
-        for (uint32_t i = b0; i < b1; ++i) sum += minpos[i] == 0xFFFFFFFFu ? 0u : ((cellbase[i] - minpos[i]) >> 5) + 1u;
-        uint32_t incl = sum;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t up = __shfl_up(incl, o, 64);
-            if ((int)lane >= o) incl += up;
-        }
-        if (lane == 63) bsum[wave] = incl;
-        __syncthreads();
-        uint32_t run = incl - sum, all = 0;
-        for (uint32_t w = 0; w < (nthr >> 6); ++w) {
-            if (w < wave) run += bsum[w];
-            all += bsum[w];
-        }
-        total_cells = all;
-        for (uint32_t i = b0; i < b1; ++i) {
-            const uint32_t c = minpos[i] == 0xFFFFFFFFu ? 0u : ((cellbase[i] - minpos[i]) >> 5) + 1u;
-            cellbase[i] = run;
-            run += c;
-        }
-    }
-    const uint32_t nwords = (total_cells + 31) >> 5;
-    if (nwords > cap_words) return false;  // (block-uniform)
-    for (uint32_t i = tid; i < nwords; i += nthr) words[i] = 0u;
-    __syncthreads();
-    for (uint32_t i = tid; i < n; i += nthr) {
-        const RunRec r = src[i];
-        const uint32_t cell = cellbase[r.slot] + ((r.pos - minpos[r.slot]) >> 5);
-        atomicOr(&words[cell >> 5], 1u << (cell & 31u));
-    }
-    __syncthreads();
-    {  // exclusive popcount prefix over the words
-        const uint32_t per = (nwords + nthr - 1) / nthr, w0 = tid * per < nwords ? tid * per : nwords;
-        const uint32_t w1 = w0 + per < nwords ? w0 + per : nwords;
-        uint32_t sum = 0;
-        for (uint32_t i = w0; i < w1; ++i) sum += (uint32_t)__popc(words[i]);
-        uint32_t incl = sum;
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t up = __shfl_up(incl, o, 64);
-            if ((int)lane >= o) incl += up;
-        }
-        __syncthreads();  // bsum is free again
-        if (lane == 63) bsum[wave] = incl;
-        __syncthreads();
-        uint32_t run = incl - sum, all = 0;
-        for (uint32_t w = 0; w < (nthr >> 6); ++w) {
-            if (w < wave) run += bsum[w];
-            all += bsum[w];
-        }
-        if (all != n) return false;  // two runs on one cell (block-uniform)
-        for (uint32_t i = w0; i < w1; ++i) {
-            wpre[i] = run;
-            run += (uint32_t)__popc(words[i]);
-        }
-    }
-    __syncthreads();
-    for (uint32_t i = tid; i < n; i += nthr) {
-        const RunRec r = src[i];
-        const uint32_t cell = cellbase[r.slot] + ((r.pos - minpos[r.slot]) >> 5);
-        out[wpre[cell >> 5] + (uint32_t)__popc(words[cell >> 5] & ((1u << (cell & 31u)) - 1u))] = r;
-    }
-    return true;
-}
-
-// heuristic ranker's accepted array (src/rerank.rs:170-176): by (Ord32(accurate), arrival)
-__global__ __launch_bounds__(256) void sort_survivors_kernel(SurvRec *__restrict__ surv,
-                                                             const uint32_t *__restrict__ surv_cnt,
-                                                             uint32_t cap) {
-    const uint32_t b = blockIdx.x;
-    uint32_t n = surv_cnt[b];
-    n = n < cap ? n : cap;
-    sort_segment(surv + (uint64_t)b * cap, n);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Ordered replay of the re-rankers over (rough, accurate) pairs: HeapReRanker::rank_batch
-// (src/rerank.rs:81-106) and HeuristicReRanker::rank_batch (:143-168), with Rust's
-// std BinaryHeap push / pop (sift_up; sift_down_to_bottom + sift_up) on (Ord32, AlwaysEqual) items
-// so that evictions among equal keys match.  One wave per query; survivors are taken 64 at a time
-// and only lanes with rough < threshold are visited (ballot), the threshold being re-applied after
-// every change.  State persists across stages in global memory.
-// ------------------------------------------------------------------------------------------------
-struct ReplayState {
-    float *thr;              // nq
-    uint32_t *heap_len;      // nq
-    int32_t *heap_key;       // nq * topk
-    uint32_t *heap_id;       // nq * topk
-    uint32_t *precise;       // nq   (rerank.rs:91 / :153)
-    uint32_t *need;          // nq   max survivor count of a stage (sizes re-runs and the learnt capacities)
-    uint32_t *ovf;           // nq   1 = a stage dropped records (count > the query's capacity): the query is re-run
-    uint32_t *nsurv;         // nq   survivors replayed (= accurate distances computed)
-    uint32_t *nshadow;       // nq   of those: rejected by the fp16 shadow rows, f32 row never read
-    // heuristic ranker
-    float *recent_max;       // nq
-    uint32_t *win_count;     // nq
-    uint32_t *arr_len;       // nq   accepted so far (may exceed hcap -> overflow)
-    SurvRec *arr;            // nq * hcap : {pos = arrival index, slot = biased Ord32(acc), accurate = id bits}
-    uint32_t hcap;
-};
-
-#define RQ_MAX_TOPK 2048
-
-// One wave replays a query's survivors (run directory `dir`, records `recs`) through the ranker.
-// CONTIG: the survivors are recs[0 .. nruns) in visiting order already (no run directory: `dir` is unused and `nruns`
-// counts records) -- the small-batch kernel's LDS-resident survivors.
-template <bool HEURISTIC, bool REGHEAP = false, bool CONTIG = false>
-__device__ __forceinline__ void replay_wave(const SurvRec *__restrict__ recs, const RunRec *__restrict__ dir,
-                                            uint32_t nruns, uint32_t topk,
-                                            uint32_t b, const ReplayState &st, int32_t *hkey, uint32_t *hid) {
-    const uint32_t lane = threadIdx.x & 63;
-    // Everything that steers the loops below is the same in every lane; saying so (v_readfirstlane / v_readlane) keeps the
-    // loop counters, the heap indices and the branch conditions in scalar registers.  Left to the compiler's divergence
-    // analysis, a bound that came out of a memory load or a cross-lane shuffle made the survivor loop "divergent" and with
-    // it every value it carries: the sift loops then ran under exec masks with their indices in vector registers.
-    nruns = __builtin_amdgcn_readfirstlane(nruns);
-    topk = __builtin_amdgcn_readfirstlane(topk);
-    float thr = st.thr[b];
-    uint32_t precise = 0;
-    uint32_t hlen = 0, wcount = 0, alen = 0;
-    float recent = 0.0f;
-    // REGHEAP (topk < 64: BinaryHeap::push before pop holds topk + 1 elements): the heap lives in one register pair, element i in lane i, read and written with
-    // v_readlane / a lane-select at wave-uniform indices: a sift step is a few scalar instructions instead of a chain of
-    // dependent LDS round trips (the replay of a stage was bound by exactly that latency)
-    int32_t rk = 0;
-    uint32_t ri = 0;
-    auto HK = [&](uint32_t idx) -> int32_t {
-        if constexpr (REGHEAP) return __builtin_amdgcn_readlane(rk, (int)idx);
-        else return hkey[idx];
-    };
-    auto HI = [&](uint32_t idx) -> uint32_t {
-        if constexpr (REGHEAP) return (uint32_t)__builtin_amdgcn_readlane((int)ri, (int)idx);
-        else return hid[idx];
-    };
-    auto SETH = [&](uint32_t idx, int32_t k, uint32_t i) {
-        if constexpr (REGHEAP) {
-            rk = lane == idx ? k : rk;  // (no writelane builtin in this toolchain: a compare and two selects)
-            ri = lane == idx ? i : ri;
-        } else {
-            hkey[idx] = k, hid[idx] = i;
-        }
-    };
-    if constexpr (!HEURISTIC) {
-        hlen = __builtin_amdgcn_readfirstlane(st.heap_len[b]);
-        if constexpr (REGHEAP) {
-            if (lane < hlen) rk = st.heap_key[(uint64_t)b * topk + lane], ri = st.heap_id[(uint64_t)b * topk + lane];
-        } else {
-            for (uint32_t i = lane; i < hlen; i += 64) {
-                hkey[i] = st.heap_key[(uint64_t)b * topk + i];
-                hid[i] = st.heap_id[(uint64_t)b * topk + i];
-            }
-        }
-    } else {
-        recent = st.recent_max[b];
-        wcount = __builtin_amdgcn_readfirstlane(st.win_count[b]);
-        alen = __builtin_amdgcn_readfirstlane(st.arr_len[b]);
-    }
-    // The survivors are replayed in stream order = directory order, then record order inside a run.  The
-    // directory is read 64 descriptors at a time; within such a chunk the stream is cut into batches of 64
-    // survivors (whatever runs they belong to): lane i finds its (run, offset) by a binary search over
-    // the chunk's prefix sums in LDS, so a batch costs one round trip however many short runs it spans,
-    // and batch k+1 is in flight while batch k is replayed.
-    __shared__ uint32_t s_pref[CONTIG ? 1 : 65], s_base[CONTIG ? 1 : 64];
-    for (uint32_t c0 = 0; c0 < (CONTIG ? (nruns ? 1u : 0u) : nruns); c0 += 64) {
-        uint32_t total = nruns;
-        if constexpr (!CONTIG) {
-            uint32_t dbase = 0, dcnt = 0;
-            if (c0 + lane < nruns) dbase = dir[c0 + lane].base, dcnt = dir[c0 + lane].cnt;
-            uint32_t incl = dcnt;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t up = __shfl_up(incl, o, 64);
-                if ((int)lane >= o) incl += up;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // previous chunk's readers are done (one wave)
-            s_pref[lane + 1] = incl;
-            s_base[lane] = dbase;
-            if (lane == 0) s_pref[0] = 0;
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-        auto fetch = [&](uint32_t off, SurvRec &rec) {
-            const uint32_t t = off + lane;
-            rec.pos = 0, rec.slot = 0, rec.rough = 0.0f, rec.accurate = 0.0f;
-            if (t < total) {
-                if constexpr (CONTIG) {
-                    rec = recs[t];
-                } else {
-                    uint32_t lo = 0;  // largest r with s_pref[r] <= t
-#pragma unroll
-                    for (int step = 32; step >= 1; step >>= 1)
-                        if (lo + step < 64 && s_pref[lo + step] <= t) lo += step;
-                    rec = recs[s_base[lo] + (t - s_pref[lo])];
-                }
-            }
-        };
-        SurvRec nxt;
-        fetch(0, nxt);
-        for (uint32_t off = 0; off < total; off += 64) {
-            const bool have = off + lane < total;
-            const SurvRec r = nxt;
-            if (off + 64 < total) fetch(off + 64, nxt);  // wave-uniform
-        uint64_t m = __ballot(have && r.rough < thr);  // rerank.rs:84 / :146: candidates the reference reranks
-        while (m) {
-            // the threshold only moves when a candidate is accepted (rerank.rs:92 / :154), so everything before
-            // the next acceptance is counted in one step instead of visited one by one
-            const uint64_t acc_m = __ballot(have && r.rough < thr && r.accurate < thr) & m;
-            if (acc_m == 0) {
-                precise += (uint32_t)__popcll(m);
-                break;
-            }
-            const int i = __builtin_ctzll(acc_m);
-            const uint64_t upto = (2ull << i) - 1ull;  // lanes 0..i (i = 63 wraps to all ones)
-            precise += (uint32_t)__popcll(m & upto);
-            m &= ~upto;
-            // (lane i's values through v_readlane: i is wave-uniform, a shuffle would go through LDS)
-            const float acc = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, r.accurate), i));
-            // the rankers carry the cluster-order POSITION; finalize_* maps it to the original id (rabitq.rs:324)
-            const uint32_t id = (uint32_t)__builtin_amdgcn_readlane((int)r.pos, i);
-            if constexpr (!HEURISTIC) {
-                // push: append + sift_up(0, old_len)
-                int32_t key = ord32_from_f32(acc);
-                uint32_t idv = id;
-                if constexpr (REGHEAP) {  // every lane holds the same values: keep them (and the control flow) scalar
-                    key = (int32_t)__builtin_amdgcn_readfirstlane((uint32_t)key);
-                    idv = __builtin_amdgcn_readfirstlane(idv);
-                }
-                uint32_t p = hlen++;
-                while (p > 0) {
-                    uint32_t parent = (p - 1) >> 1;
-                    int32_t pk = HK(parent);
-                    if (key <= pk) break;
-                    uint32_t pid = HI(parent);
-                    SETH(p, pk, pid);
-                    p = parent;
-                }
-                SETH(p, key, idv);
-                if (hlen > topk) {  // pop: last -> root, sift_down_to_bottom(0), sift_up
-                    --hlen;
-                    int32_t hk = HK(hlen);
-                    uint32_t hi = HI(hlen);
-                    if (hlen > 0) {
-                        const uint32_t end = hlen;
-                        uint32_t q = 0, child = 1;
-                        while (child + 1 < end) {
-                            int32_t kl = HK(child), kr = HK(child + 1);
-                            if (kl <= kr) child += 1;
-                            int32_t ck = HK(child);
-                            uint32_t ci = HI(child);
-                            SETH(q, ck, ci);
-                            q = child;
-                            child = 2 * q + 1;
-                        }
-                        if (child == end - 1) {
-                            int32_t ck = HK(child);
-                            uint32_t ci = HI(child);
-                            SETH(q, ck, ci);
-                            q = child;
-                        }
-                        while (q > 0) {  // sift_up(0, q) of the hole element
-                            uint32_t parent = (q - 1) >> 1;
-                            int32_t pk = HK(parent);
-                            if (hk <= pk) break;
-                            uint32_t pid = HI(parent);
-                            SETH(q, pk, pid);
-                            q = parent;
-                        }
-                        SETH(q, hk, hi);
-                    }
-                }
-                if (hlen == topk) thr = ord32_to_f32(HK(0));  // rerank.rs:98-100
-            } else {
-                if (alen < st.hcap && lane == 0) {
-                    SurvRec e;
-                    e.pos = alen;
-                    e.slot = ord32_biased(acc);
-                    e.rough = acc;
-                    e.accurate = __builtin_bit_cast(float, id);
-                    st.arr[(uint64_t)b * st.hcap + alen] = e;
-                }
-                ++alen;
-                ++wcount;
-                recent = (acc > recent || recent != recent) ? acc : recent;  // f32::max
-                if (wcount >= 12) {                                          // consts.rs:12
-                    thr = recent;
-                    wcount = 0;
-                    recent = -3.402823466e+38f;
-                }
-            }
-            m &= __ballot(have && r.rough < thr);
-        }
-        }
-    }
-    if constexpr (!HEURISTIC) {
-        if constexpr (REGHEAP) {
-            if (lane < hlen) st.heap_key[(uint64_t)b * topk + lane] = rk, st.heap_id[(uint64_t)b * topk + lane] = ri;
-        } else {
-            for (uint32_t i = lane; i < hlen; i += 64) {
-                st.heap_key[(uint64_t)b * topk + i] = hkey[i];
-                st.heap_id[(uint64_t)b * topk + i] = hid[i];
-            }
-        }
-        if (lane == 0) st.heap_len[b] = hlen;
-    } else if (lane == 0) {
-        st.recent_max[b] = recent;
-        st.win_count[b] = wcount;
-        st.arr_len[b] = alen;
-    }
-    if (lane == 0) {
-        st.thr[b] = thr;
-        st.precise[b] += precise;
-    }
-}
-
-// One block per query finishes a stage: (A) exact rerank distances of the stage's survivors
-// (src/rerank.rs:85-90, 8 lanes = the 8 AVX lanes of src/simd.rs:14-73), (B) sort of the run
-// directory into the reference's visiting order, (C) wave 0 replays the ranker.
-template <bool HEURISTIC>
-__global__ __launch_bounds__(1024) void stage_finish_kernel(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
-                                                           unsigned long long *__restrict__ surv_cnt, const QSeg seg,
-                                                           const BaseView base,
-                                                           const float *__restrict__ qpad, uint32_t dim, uint32_t topk,
-                                                           ReplayState st, const uint32_t *__restrict__ probe_cluster,
-                                                           uint32_t nprobe, uint32_t presorted) {
-    __shared__ int32_t hkey[HEURISTIC ? 1 : RQ_MAX_TOPK];
-    __shared__ uint32_t hid[HEURISTIC ? 1 : RQ_MAX_TOPK];
-    extern __shared__ __attribute__((aligned(16))) float fin_q[];  // dim floats: the padded query
-    const uint32_t b = blockIdx.x;
-    const unsigned long long cnt64 = surv_cnt[b];
-    const uint32_t cnt = (uint32_t)cnt64;
-    const uint32_t cap = seg.capof(b);
-    const uint64_t qat = seg.at(b);
-    const bool overflow = cnt > cap;  // records were dropped: the query is re-run with a larger buffer
-    const uint32_t n = overflow ? 0 : cnt;
-    const uint32_t nruns = overflow ? 0 : (uint32_t)(cnt64 >> 32);
-    __syncthreads();  // every thread has read the counter before thread 0 resets it
-    if (threadIdx.x == 0) {
-        if (cnt > st.need[b]) st.need[b] = cnt;
-        if (overflow) st.ovf[b] = 1u;
-        st.nsurv[b] += n;
-        surv_cnt[b] = 0;  // ready for the next stage
-    }
-    if (n == 0) return;
-    SurvRec *recs = surv + qat;
-    {  // (A)
-        for (uint32_t c = threadIdx.x * 4; c < dim; c += blockDim.x * 4)
-            *reinterpret_cast<float4 *>(fin_q + c) = *reinterpret_cast<const float4 *>(qpad + (uint64_t)b * dim + c);
-        __syncthreads();
-        accurate_rows(recs, n, base, fin_q, dim, threadIdx.x >> 1, blockDim.x >> 1, probe_cluster + (uint64_t)b * nprobe);  // 256 or 1024 threads per query
-    }
-    // (B): up to RQ_SORT_LDS_RECS descriptors in LDS; longer directories were already ordered by sort_runs_mid_kernel
-    // when the host launched it ahead of this kernel (presorted != 0), else (rare) bitonic in global memory
-    if (nruns <= RQ_SORT_LDS_RECS || !presorted) sort_segment(runs + qat, nruns);
-    __syncthreads();                                  // (A)'s stores and (B)'s order visible to wave 0
-    if (threadIdx.x < 64)                             // (C)
-        replay_wave<HEURISTIC>(recs, runs + qat, nruns, topk, b, st, hkey, hid);
-}
+#include "kernels_replay.h"  // survivor ordering, the rankers' replay, the result writers
 
 // Rerank order of a large batch: queries grouped by their nearest list (counting sort: histogram, scan by
 // group_scan_kernel, scatter).  Queries of one cluster rerank largely the same rows; handled back to back,
@@ -1635,104 +1121,6 @@ __global__ void order_scatter_kernel(const uint32_t *__restrict__ probe_cluster,
     const uint32_t c = probe_cluster[(uint64_t)b * nprobe];
     const uint32_t g = c < k ? c : k;
     order[start[g] + atomicAdd(&cursor[g], 1u)] = b;
-}
-
-// `runs_src`: where the stage's unsorted descriptors are when not in `runs` itself (an arena stage scatters them into the
-// second directory buffer, so that the ordering pass is the one that writes the directory); same geometry.
-__global__ __launch_bounds__(64) void sort_runs_kernel(RunRec *__restrict__ runs,
-                                                        const unsigned long long *__restrict__ surv_cnt,
-                                                        const QSeg seg, uint32_t *__restrict__ big_list,
-                                                        uint32_t *__restrict__ big_count, uint32_t list_above,
-                                                        const RunRec *runs_src) {
-    const uint32_t b = blockIdx.x;
-    const unsigned long long c = surv_cnt[b];
-    if ((uint32_t)c > seg.capof(b)) return;
-    // early stages leave a few dozen runs per query, the stages around one list's worth a few hundred (more at dim 64,
-    // where the estimates are noisier): 512 descriptors = 8 KiB of LDS per 64-thread block keep them out of global memory
-    const uint32_t nruns = (uint32_t)(c >> 32);
-    if (list_above != 512u) {  // small-batch path: only list the directories stage_finish_kernel cannot sort in LDS
-        if (nruns > list_above && threadIdx.x == 0) big_list[atomicAdd(big_count, 1u)] = b;
-        return;
-    }
-    if (nruns > 512) {  // a loose threshold: handed to sort_runs_mid_kernel (cell bitmap, or slot buckets + rank counting)
-        if (threadIdx.x == 0) big_list[atomicAdd(big_count, 1u)] = b;
-        return;
-    }
-    sort_segment<RunRec, 512>(runs + seg.at(b), nruns, runs_src ? runs_src + seg.at(b) : nullptr);
-}
-
-// Directories of more than 512 runs, listed by sort_runs_kernel, are ordered by a persistent launch that walks the
-// list (it exits at once when the list is empty, the common case): the cell bitmap (order_runs_bitmap, dynamic LDS:
-// 2 x lds_words dwords), else slot-bucketing + per-bucket rank counting through the second directory buffer; the last
-// block out resets the counter for the next stage.  src_is_tmp: the unsorted descriptors are in runs_tmp.
-__global__ __launch_bounds__(256) void sort_runs_mid_kernel(RunRec *__restrict__ runs, RunRec *__restrict__ runs_tmp,
-                                                            const unsigned long long *__restrict__ surv_cnt, const QSeg seg,
-                                                            const uint32_t *__restrict__ big_list,
-                                                            uint32_t *__restrict__ big_count /* [0] entries, [1] blocks done, [2] most entries of a stage */,
-                                                            uint32_t nslots, uint32_t src_is_tmp, uint32_t lds_words) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t mid_lds[];
-    const uint32_t total = big_count[0];
-    for (uint32_t i = blockIdx.x; i < total; i += gridDim.x) {
-        const uint32_t b = big_list[i], n = (uint32_t)(surv_cnt[b] >> 32);
-        RunRec *dir = runs + seg.at(b), *tmp = runs_tmp ? runs_tmp + seg.at(b) : nullptr;
-        bool done = false;
-        if (nslots <= 1024 && tmp && lds_words) {
-            if (src_is_tmp) {
-                done = order_runs_bitmap<1024>(tmp, dir, n, nslots, mid_lds, mid_lds + lds_words, lds_words);
-            } else {
-                done = order_runs_bitmap<1024>(dir, tmp, n, nslots, mid_lds, mid_lds + lds_words, lds_words);
-                if (done) {  // back into the directory (the block's own writes: L2)
-                    __threadfence_block();
-                    __syncthreads();
-                    for (uint32_t e = threadIdx.x; e < n; e += blockDim.x) dir[e] = tmp[e];
-                }
-            }
-        }
-        if (!done) {
-            if (src_is_tmp && tmp) {  // the fall-backs order the directory itself
-                __syncthreads();
-                for (uint32_t e = threadIdx.x; e < n; e += blockDim.x) dir[e] = tmp[e];
-                __threadfence_block();
-                __syncthreads();
-            }
-            if (nslots <= 1024 && tmp) sort_runs_by_slot<1024>(dir, tmp, n, nslots);
-            else sort_segment<RunRec, 16>(dir, n);  // more than 1024 probe slots, or no second buffer yet: bitonic sort in global memory
-        }
-        __syncthreads();
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {  // every block reads `total` before it counts itself done: the last one out may reset both
-        __threadfence();
-        if (atomicAdd(big_count + 1, 1u) + 1 == gridDim.x) {
-            if (total > big_count[2]) big_count[2] = total;  // for the host: sizes the next pass's launch
-            big_count[0] = 0;
-            big_count[1] = 0;
-        }
-    }
-}
-
-template <bool HEURISTIC, bool REGHEAP = false>
-__global__ __launch_bounds__(64) void replay_kernel(const SurvRec *__restrict__ surv, const RunRec *__restrict__ runs,
-                                                    unsigned long long *__restrict__ surv_cnt, const QSeg seg, uint32_t topk,
-                                                    ReplayState st, uint32_t dense_cells) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char replay_smem[];  // topk * 8 bytes (heap ranker)
-    int32_t *hkey = reinterpret_cast<int32_t *>(replay_smem);
-    uint32_t *hid = reinterpret_cast<uint32_t *>(replay_smem) + topk;
-    const uint32_t b = blockIdx.x;
-    const unsigned long long cnt64 = surv_cnt[b];
-    const uint32_t cnt = (uint32_t)cnt64;
-    const bool overflow = cnt > seg.capof(b);
-    const uint32_t n = overflow ? 0 : cnt;
-    // dense directory: every cell of the stage is a descriptor (count 0 where nothing survived), already in order
-    const uint32_t nruns = overflow ? 0 : (dense_cells ? dense_cells : (uint32_t)(cnt64 >> 32));
-    if (threadIdx.x == 0) {
-        if (cnt > st.need[b]) st.need[b] = cnt;
-        if (overflow) st.ovf[b] = 1u;
-        st.nsurv[b] += n;
-        surv_cnt[b] = 0;  // ready for the next stage
-    }
-    if (n == 0) return;
-    replay_wave<HEURISTIC, REGHEAP>(surv + seg.at(b), runs + seg.at(b), nruns, topk, b, st, hkey, hid);
 }
 
 // Segment sizing of an arena stage: query b's segment = its exact survivor count (surv_cnt low word, counted by the scan)
@@ -1800,12 +1188,7 @@ __global__ __launch_bounds__(256) void arena_scatter_kernel(const SurvRec *__res
             s_src[wave][lane] = d.w;
             s_dst[wave][lane] = qat + base;
         }
-        uint32_t incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t up = __shfl_up(incl, o, 64);
-            if ((int)lane >= o) incl += up;
-        }
+        const uint32_t incl = wave_incl_scan(cnt);
         s_pref[wave][lane + 1] = incl;
         if (lane == 0) s_pref[wave][0] = 0;
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -1819,10 +1202,7 @@ __global__ __launch_bounds__(256) void arena_scatter_kernel(const SurvRec *__res
                 const uint32_t e = e0 + 64 * v + lane;
                 dst[v] = ~0ull;
                 if (e < total) {
-                    uint32_t lo = 0;  // largest r with s_pref[r] <= e
-#pragma unroll
-                    for (int step = 32; step >= 1; step >>= 1)
-                        if (lo + step < 64 && s_pref[wave][lo + step] <= e) lo += step;
+                    const uint32_t lo = run_of_prefix(s_pref[wave], e);
                     const uint32_t i = e - s_pref[wave][lo];
                     rec[v] = arena_recs[s_src[wave][lo] + i];
                     dst[v] = s_dst[wave][lo] + i;
@@ -1839,30 +1219,9 @@ __global__ __launch_bounds__(256) void arena_scatter_kernel(const SurvRec *__res
 // exclusive scan of q_cap into q_base (u64); out_total[0] = the sum.  One block of 1024 threads, any nq.
 __global__ __launch_bounds__(1024) void seg_scan_kernel(const uint32_t *__restrict__ q_cap, uint32_t nq,
                                                         unsigned long long *__restrict__ q_base, unsigned long long *__restrict__ out_total) {
-    __shared__ unsigned long long wsum[16];
-    __shared__ unsigned long long carry;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < nq; base += 1024) {
-        const uint32_t i = base + tid;
-        const unsigned long long v = i < nq ? q_cap[i] : 0ull;
-        unsigned long long incl = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long up = __shfl_up(incl, o, 64);
-            if ((int)lane >= o) incl += up;
-        }
-        if (lane == 63) wsum[wid] = incl;
-        __syncthreads();
-        unsigned long long woff = 0;
-        for (uint32_t w = 0; w < wid; ++w) woff += wsum[w];
-        const unsigned long long c0 = carry;
-        if (i < nq) q_base[i] = c0 + woff + incl - v;
-        __syncthreads();
-        if (tid == 1023) carry = c0 + woff + incl;
-        __syncthreads();
-    }
-    if (tid == 0) out_total[0] = carry;
+    const unsigned long long total = block_scan_chunked<unsigned long long, uint32_t>(
+        nq, [&](uint32_t i) { return q_cap[i]; }, [&](uint32_t i, unsigned long long at, unsigned long long) { q_base[i] = at; });
+    if (threadIdx.x == 0) out_total[0] = total;
 }
 
 // dense run directory of a stage: cells [0, ncells) of every query start empty
@@ -1875,96 +1234,9 @@ __global__ void clear_dir_kernel(RunRec *__restrict__ runs, uint32_t nq, const Q
     runs[seg.at(b) + c] = z;
 }
 
-// ranker state of a fresh query (src/rerank.rs:70-77, :129-139) + per-query counters, one launch
-// thr_init (seeded passes): the threshold a query starts with instead of f32::MAX, row_map: pass row -> row of thr_init
-__global__ void init_state_kernel(ReplayState st, unsigned long long *__restrict__ surv_cnt, uint32_t nq,
-                                  const float *__restrict__ thr_init, const uint32_t *__restrict__ row_map) {
-    uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nq) return;
-    st.thr[b] = thr_init ? thr_init[row_map ? row_map[b] : b] : 3.402823466e+38f;  // f32::MAX
-    st.recent_max[b] = -3.402823466e+38f;  // f32::MIN
-    st.heap_len[b] = 0, st.precise[b] = 0, st.need[b] = 0, st.ovf[b] = 0, st.nsurv[b] = 0, st.nshadow[b] = 0, st.win_count[b] = 0, st.arr_len[b] = 0;
-    surv_cnt[b] = 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Results (src/rerank.rs:108-113 heap Vec order; :170-176 the topk smallest, here sorted).
-// ------------------------------------------------------------------------------------------------
-__global__ void finalize_heap_kernel(const ReplayState st, uint32_t nq, uint32_t topk,
-                                     const uint32_t *__restrict__ row_map, const uint32_t *__restrict__ map_ids,
-                                     float *__restrict__ out_dist, uint32_t *__restrict__ out_id,
-                                     uint32_t *__restrict__ out_n) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nq * topk) return;
-    uint32_t b = i / topk, e = i - b * topk;
-    uint32_t ob = row_map ? row_map[b] : b;
-    uint32_t len = st.heap_len[b];
-    if (e < len) {
-        out_dist[(uint64_t)ob * topk + e] = ord32_to_f32(st.heap_key[(uint64_t)b * topk + e]);
-        out_id[(uint64_t)ob * topk + e] = map_ids[st.heap_id[(uint64_t)b * topk + e]];  // position -> original id
-    }
-    if (e == 0) out_n[ob] = len;
-}
-
-__global__ void finalize_heuristic_kernel(const ReplayState st, uint32_t nq, uint32_t topk,
-                                          const uint32_t *__restrict__ row_map, const uint32_t *__restrict__ map_ids,
-                                          float *__restrict__ out_dist, uint32_t *__restrict__ out_id,
-                                          uint32_t *__restrict__ out_n) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nq * topk) return;
-    uint32_t b = i / topk, e = i - b * topk;
-    uint32_t ob = row_map ? row_map[b] : b;
-    uint32_t len = st.arr_len[b];
-    len = len < st.hcap ? len : st.hcap;
-    uint32_t take = len < topk ? len : topk;
-    if (e < take) {
-        const SurvRec &r = st.arr[(uint64_t)b * st.hcap + e];
-        out_dist[(uint64_t)ob * topk + e] = r.rough;
-        out_id[(uint64_t)ob * topk + e] = map_ids[__builtin_bit_cast(uint32_t, r.accurate)];  // position -> original id
-    }
-    if (e == 0) out_n[ob] = take;
-}
-
-// per-batch totals for METRICS (src/metrics.rs:44-53): sums of the per-query counters.
-// out4[0..5) = {rough, precise (queries without overflow only), #overflowed queries, accurate distances
-// computed, max buffer need}
 // sums the matrix-core scan's 64 counter pairs into out[0] (sub-tile steps) and out[1] (steps that took the exact path)
 __global__ __launch_bounds__(64) void stat_fold_kernel(const unsigned long long *__restrict__ stat, unsigned long long *__restrict__ out) {
     unsigned long long a = stat[2 * threadIdx.x], b = stat[2 * threadIdx.x + 1];
     for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64), b += __shfl_xor(b, o, 64);
     if (threadIdx.x == 0) out[0] = a, out[1] = b;
-}
-__global__ __launch_bounds__(256) void metrics_sum_kernel(const unsigned long long *__restrict__ rough,
-                                                          const uint32_t *__restrict__ precise,
-                                                          const uint32_t *__restrict__ need,
-                                                          const uint32_t *__restrict__ arr_len,
-                                                          const uint32_t *__restrict__ nsurv,
-                                                          const uint32_t *__restrict__ nshadow, uint32_t nq,
-                                                          const uint32_t *__restrict__ ovf, uint32_t hcap,
-                                                          unsigned long long *__restrict__ out4) {
-    __shared__ unsigned long long s[6];
-    if (threadIdx.x < 6) s[threadIdx.x] = 0;
-    __syncthreads();
-    unsigned long long r = 0, p = 0, o = 0, a = 0, mx = 0, sh = 0;
-    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < nq; i += gridDim.x * 256) {
-        const bool ok = !ovf[i] && (!arr_len || arr_len[i] <= hcap);
-        r += rough[i];
-        p += ok ? precise[i] : 0;
-        o += ok ? 0 : 1;
-        a += nsurv[i];
-        sh += nshadow[i];
-        const unsigned long long al = arr_len ? arr_len[i] : 0ull;
-        unsigned long long nd = need[i] > al ? (unsigned long long)need[i] : al;
-        mx = nd > mx ? nd : mx;
-    }
-    atomicAdd(&s[0], r);
-    atomicAdd(&s[1], p);
-    atomicAdd(&s[2], o);
-    atomicAdd(&s[3], a);
-    atomicMax(&s[4], mx);
-    atomicAdd(&s[5], sh);
-    __syncthreads();
-    if (threadIdx.x < 4) atomicAdd(&out4[threadIdx.x], s[threadIdx.x]);
-    if (threadIdx.x == 5) atomicAdd(&out4[5], s[5]);
-    if (threadIdx.x == 4) atomicMax(&out4[4], s[4]);
 }

@@ -45,31 +45,9 @@ __global__ __launch_bounds__(256) void range_count_kernel(const SurvRec *__restr
 // would make this a serial tail of milliseconds beside passes that take seconds -- a multi-block scan is not worth it here).
 template <typename T>
 __global__ __launch_bounds__(1024) void range_scan_kernel(const T *__restrict__ cnt, uint32_t n, unsigned long long *__restrict__ lims) {
-    __shared__ unsigned long long wsum[16];
-    __shared__ unsigned long long carry;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (uint64_t base = 0; base < n; base += 1024) {  // (64-bit: n may be within 1024 of 2^32)
-        const uint64_t i = base + tid;
-        const unsigned long long v = i < n ? (unsigned long long)cnt[i] : 0ull;
-        unsigned long long incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long up = __shfl_up(incl, o, 64);
-            if ((int)lane >= o) incl += up;
-        }
-        if (lane == 63) wsum[wid] = incl;
-        __syncthreads();
-        unsigned long long woff = 0;
-        for (uint32_t w = 0; w < wid; ++w) woff += wsum[w];
-        const unsigned long long c0 = carry;
-        if (i < n) lims[i] = c0 + woff + incl - v;
-        __syncthreads();
-        if (tid == 1023) carry = c0 + woff + incl;
-        __syncthreads();
-    }
-    if (tid == 0) lims[n] = carry;
+    const unsigned long long total = block_scan_chunked<unsigned long long, uint64_t>(  // (64-bit index: n may be within 1024 of 2^32)
+        (uint64_t)n, [&](uint64_t i) { return cnt[i]; }, [&](uint64_t i, unsigned long long at, unsigned long long) { lims[i] = at; });
+    if (threadIdx.x == 0) lims[n] = total;
 }
 
 // The hits' keys, written straight to the query's segment [lims[b], lims[b + 1]) in survivor order (ballot ranks: no atomics).

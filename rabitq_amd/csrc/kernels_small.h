@@ -244,10 +244,7 @@ __device__ __forceinline__ void sb_write_results(const ReplayState &st, uint32_t
                                                  unsigned long long rough, uint32_t cap, unsigned long long *__restrict__ totals) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t len = st.heap_len[sb];
-    for (uint32_t e = lane; e < len; e += 64) {
-        out_dist[(uint64_t)b * topk + e] = ord32_to_f32(st.heap_key[(uint64_t)sb * topk + e]);
-        out_id[(uint64_t)b * topk + e] = map_ids[st.heap_id[(uint64_t)sb * topk + e]];  // position -> original id
-    }
+    for (uint32_t e = lane; e < len; e += 64) heap_result_entry(st, sb, b, e, topk, map_ids, out_dist, out_id);
     if (lane == 0) {
         out_n[b] = len;
         const uint32_t need = st.need[sb];
@@ -494,20 +491,9 @@ __global__ __launch_bounds__(1024) void sb_finish_kernel(SurvRec *__restrict__ s
     __shared__ uint32_t hid[REGHEAP ? 1 : RQ_MAX_TOPK];
     extern __shared__ __attribute__((aligned(16))) float fin_q[];  // dim floats: the padded query | 2 x RQ_SBF_RUNS descriptors | RQ_SBF_RECS records
     const uint32_t b = blockIdx.x;
-    const unsigned long long cnt64 = surv_cnt[b];
-    const uint32_t cnt = (uint32_t)cnt64;
-    const uint32_t cap = seg.capof(b);
-    const uint64_t qat = seg.at(b);
-    const bool overflow = cnt > cap;  // records were dropped: the query is re-run with a larger buffer
-    const uint32_t n = overflow ? 0 : cnt;
-    const uint32_t nruns = overflow ? 0 : (uint32_t)(cnt64 >> 32);
-    __syncthreads();  // every thread has read the counter before thread 0 resets it
-    if (threadIdx.x == 0) {
-        if (cnt > st.need[b]) st.need[b] = cnt;
-        if (overflow) st.ovf[b] = 1u;
-        st.nsurv[b] += n;
-        surv_cnt[b] = 0;
-    }
+    const StageCounts sc = stage_begin<true>(surv_cnt, seg, b, st);
+    const uint32_t n = sc.n, nruns = sc.nruns, cap = sc.cap;
+    const uint64_t qat = sc.qat;
     if (n) {  // block-uniform
         SurvRec *recs = surv + qat;
         for (uint32_t c = threadIdx.x * 4; c < dim; c += blockDim.x * 4)
@@ -516,6 +502,8 @@ __global__ __launch_bounds__(1024) void sb_finish_kernel(SurvRec *__restrict__ s
         if (!(presorted & 2u))  // bit 1: the exact distances were computed by a whole-chip launch already
             accurate_rows(recs, n, base, fin_q, dim, threadIdx.x >> 1, blockDim.x >> 1, probe_cluster + (uint64_t)b * nprobe);
         if (nruns <= RQ_SBF_RUNS && n <= RQ_SBF_RECS && nprobe <= 64) {
+            // (Not sort_runs_by_slot: its per-wave key staging, keys[4][1024], assumes a 256-thread block and would add 16 KiB of
+            // static LDS to the ~100 KiB of dynamic LDS this kernel runs with; the ordering below shares the stretch scan only.)
             // The usual case, all in LDS: the run directory is ordered by (probe slot, position) with a counting sort on the
             // slot and rank counting inside a slot's bucket (four barriers instead of a bitonic network's fifty), the
             // survivors are gathered into visiting order by the whole block, and the ranker replays over contiguous LDS
@@ -534,13 +522,7 @@ __global__ __launch_bounds__(1024) void sb_finish_kernel(SurvRec *__restrict__ s
             }
             __syncthreads();
             if (t < 64) {
-                const uint32_t h = hist[t];
-                uint32_t incl = h;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const uint32_t up = __shfl_up(incl, o, 64);
-                    if ((int)t >= o) incl += up;
-                }
+                const uint32_t h = hist[t], incl = wave_incl_scan(h);
                 bstart[t] = incl - h, bcur[t] = incl - h;
                 if (t == 63) bstart[64] = incl;
             }
@@ -555,25 +537,8 @@ __global__ __launch_bounds__(1024) void sb_finish_kernel(SurvRec *__restrict__ s
                 R[lo + rank] = me;
             }
             __syncthreads();
-            {  // exclusive prefix sums of the ordered runs' counts (B is free now): every thread owns a contiguous stretch
-                const uint32_t per = (nruns + nt - 1) / nt, i0 = t * per < nruns ? t * per : nruns, i1 = i0 + per < nruns ? i0 + per : nruns;
-                uint32_t sum = 0;
-                for (uint32_t i = i0; i < i1; ++i) sum += R[i].cnt;
-                uint32_t incl = sum;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const uint32_t up = __shfl_up(incl, o, 64);
-                    if ((int)(t & 63) >= o) incl += up;
-                }
-                if ((t & 63) == 63) wsum[t >> 6] = incl;
-                __syncthreads();
-                uint32_t run = incl - sum;
-                for (uint32_t w = 0; w < (t >> 6); ++w) run += wsum[w];
-                for (uint32_t i = i0; i < i1; ++i) {
-                    off[i] = run;
-                    run += R[i].cnt;
-                }
-            }
+            // exclusive prefix sums of the ordered runs' counts (B is free now)
+            block_scan_stretch(nruns, wsum, [&](uint32_t i) { return R[i].cnt; }, [&](uint32_t i, uint32_t at) { off[i] = at; });
             __syncthreads();
             for (uint32_t e = t; e < n; e += nt) {  // record e of the visiting order: its run by bisection over the prefix sums
                 uint32_t lo = 0, hi = nruns;  // largest r with off[r] <= e

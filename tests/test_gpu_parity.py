@@ -186,7 +186,7 @@ OPTION_VALUES = {
     "scan_impl": [0, 1, 2], "scan_gate": [0, 1, 2], "coarse_impl": [0, 1, 2, 3, 4], "coarse_tiled_from": [0, 4096, 1000000], "group_rank": [0, 1, 2], "scan_tile_table": [0, 1, 2],
     "dense_dir": [0, 1], "small_batch": [0, 1], "small_batch_span": [64, 2560, 100000], "stage_growth": [0, 2, 16],
     "survivor_segments": [0, 1, 2], "max_scan_blocks": [0, 1, 7], "shared_thresholds": [0, 1, 2], "assign_impl": [0, 1],
-    "rerank_shadow": [0, 1, 2], "pair_split": [0, 1], "scan_debug": [0, 128, 512, 4096, 16384, 128 | 512 | 4096],
+    "rerank_shadow": [0, 1, 2], "pair_split": [0, 1], "scan_debug": [0, 128, 512, 2048, 4096, 16384, 128 | 512 | 4096],
     "split_rows": [0, 1, 2], "pass_overlap": [0, 1], "large_batch_from": [2, 256, 100000], "cluster_major_div": [2, 32, 1024], "stage_settle_pct": [25, 100, 400],
 }
 OPTION_DEFAULTS = {"scan_impl": 0, "scan_gate": 0, "coarse_impl": 0, "coarse_tiled_from": 4096, "group_rank": 1, "scan_tile_table": 1, "dense_dir": 1,
@@ -1765,14 +1765,16 @@ def test_arena_allocation_failure_falls_back_to_uniform_buffers(rq):
     assert r.returncode == 0 and "DEV_HOOK_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
 
 
-@pytest.mark.parametrize("dense_dir", [0, 1])
-def test_long_run_directories_large_batch(rq, oracle, dense_dir):
+@pytest.mark.parametrize("dense_dir,scan_debug", [(0, 0), (1, 0), (0, 2048)], ids=["0", "1", "0-no_bitmap"])
+def test_long_run_directories_large_batch(rq, oracle, dense_dir, scan_debug):
     """Loose thresholds (deep top-k, one long list) leave more than 512 survivor runs per query in a large batch.
-    dense_dir = 0: runs are appended and the directories ordered by the slot-bucketed rank sort (sort_runs_mid_kernel),
-    several stages in a row; dense_dir = 1 (default): the VALU stages write their runs into directories indexed by
-    stream position (stage_fill_kernel: RQ_REC_CELL0) and nothing is sorted."""
+    dense_dir = 0: runs are appended and the long directories ordered by sort_runs_mid_kernel, several stages in a row: by the
+    cell bitmap (order_runs_bitmap), and under scan_debug = 2048, which withholds the bitmap, by its fall-backs -- the first
+    call has no second directory buffer yet and sorts them bitonically in global memory, the later ones bucket the runs by probe
+    slot and rank inside a bucket (sort_runs_by_slot; two probe slots: buckets beyond RQ_BUCKET_CHUNK runs, staged in chunks).
+    dense_dir = 1 (default): the VALU stages write their runs into directories indexed by stream position (stage_fill_kernel:
+    RQ_REC_CELL0) and nothing is sorted."""
     from rabitq_amd import index as ix
-    ix.set_option("dense_dir", dense_dir)
     n, d, k = 200_000, 64, 2
     rng = np.random.default_rng(15)
     centres = np.stack([np.zeros(d, np.float32), np.full(d, 5.0, np.float32)])
@@ -1784,15 +1786,20 @@ def test_long_run_directories_large_batch(rq, oracle, dense_dir):
     # queries at the data's own radius: their neighbours are spread over the whole (centre-distance ordered) list, so the
     # threshold learnt from the list's head stays loose and every later stage leaves thousands of sparse survivors
     queries = (x[rng.integers(3000, n, 260)] + 0.1 * rng.standard_normal((260, d))).astype(np.float32)
-    _compare_with_oracle(rq, oracle, oidx, gidx, queries, 2, 200, False)   # default buffers overflow: re-runs, capacity learnt
-    _compare_with_oracle(rq, oracle, oidx, gidx, queries, 2, 200, False)   # now the whole batch stays on the large-batch path
-    pr = ix.last_profile()
-    assert pr["retries"] == 0 and pr["rerank_candidates"] / 260 > 4096, (pr["retries"], pr["rerank_candidates"] / 260)
-    _compare_with_oracle(rq, oracle, oidx, gidx, queries, 1, 100, False)
-    _compare_with_oracle(rq, oracle, oidx, gidx, queries, 2, 50, True)
-    ix.set_option("dense_dir", 1)
-    gidx.close()
-    oidx.close()
+    try:
+        ix.set_option("dense_dir", dense_dir)
+        ix.set_option("scan_debug", scan_debug)
+        _compare_with_oracle(rq, oracle, oidx, gidx, queries, 2, 200, False)   # default buffers overflow: re-runs, capacity learnt
+        _compare_with_oracle(rq, oracle, oidx, gidx, queries, 2, 200, False)   # now the whole batch stays on the large-batch path
+        pr = ix.last_profile()
+        assert pr["retries"] == 0 and pr["rerank_candidates"] / 260 > 4096, (pr["retries"], pr["rerank_candidates"] / 260)
+        _compare_with_oracle(rq, oracle, oidx, gidx, queries, 1, 100, False)
+        _compare_with_oracle(rq, oracle, oidx, gidx, queries, 2, 50, True)
+    finally:
+        ix.set_option("dense_dir", 1)
+        ix.set_option("scan_debug", 0)
+        gidx.close()
+        oidx.close()
 
 
 @pytest.mark.parametrize("tiered", [True, False])
