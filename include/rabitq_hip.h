@@ -80,7 +80,9 @@ typedef struct {
  * refused for split rows as for tiers; 0.6.0: filtered queries -- rq_filter_* and rq_query_batch*_filtered, additions only;
  * 0.7.0: in-place mutation -- rq_add / rq_remove / rq_last_mutate_stats, additions only; a filter made before a mutation of its
  * index is refused; later in 0.7, additions only: range search -- rq_range_search* and rq_range_result_*;
- * 0.8.0: cosine metric -- rq_*_metric, rq_normalize*, rq_info_t.reserved0 became metric, additions only).
+ * 0.8.0: cosine metric -- rq_*_metric, rq_normalize*, rq_info_t.reserved0 became metric, additions only;
+ * later in 0.8, additions only: rq_query_batch_device_begin_filtered, option "small_batch_filtered" -- filtered batches of <= 64
+ * queries on the small-batch path).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -247,6 +249,7 @@ rq_status rq_query_batch_device_begin(const rq_index *idx, const float *d_querie
                                       float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n,
                                       rq_ticket **out_ticket);
 rq_status rq_query_batch_device_end(rq_ticket *ticket);
+/* (the filtered _begin, rq_query_batch_device_begin_filtered, is declared with the filters below; _end is the same call) */
 
 /* ---- filtered queries: answer from a subset of the index (an allow-list of vector ids) ------------------------ */
 /* A filter is a set of admitted ids: the original row ids that map_ids holds (global ids on a shard carved by rq_shard_index).
@@ -269,13 +272,27 @@ rq_status rq_filter_create(const rq_index *idx, const uint32_t *allow_bits, uint
 rq_status rq_filter_rows(const rq_filter *f, uint64_t *out_admitted); /* rows of the index the filter admits */
 void rq_filter_free(rq_filter *f);
 /* rq_query_batch / rq_query_batch_device with a filter (filter == NULL: the unfiltered call).  Batches of <= 64 queries take the
- * staged launches, not the small-batch path (option "small_batch"), when filtered. */
+ * small-batch path (options "small_batch", "small_batch_filtered") like unfiltered ones, with its filtered kernels; a filter too
+ * sparse for a query's block to fill the ranker within its reach keeps the staged launches (the rule is under
+ * "small_batch_filtered" below).  A filter keeps its own learnt survivor capacities: after calls that overflowed, its capacity can
+ * exceed what the small-batch path holds (4 x 4096 records per query), and later batches of that filter then take the staged
+ * launches -- with the same results. */
 rq_status rq_query_batch_filtered(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq,
                                   uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank, float *out_dist,
                                   uint32_t *out_id, uint32_t *out_n);
 rq_status rq_query_batch_device_filtered(const rq_index *idx, const rq_filter *filter, const float *d_queries,
                                          uint32_t nq, uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank,
                                          float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n);
+/* rq_query_batch_device_begin with a filter (filter == NULL: rq_query_batch_device_begin itself); the ticket is ended by
+ * rq_query_batch_device_end.  The filter is validated as by rq_query_batch_device_filtered (another index's filter, or one made
+ * before a mutation: RQ_ERR_INVALID, no ticket) and travels in the ticket: _end's re-runs and capacity updates use it, so the
+ * filter must outlive the ticket (free it after _end).  Returning at once: a filtered batch on the small-batch path does; a
+ * filtered batch on the staged launches returns from _begin only after its pair split -- the pairs whose list admits nothing are
+ * settled and the others counted, one read-back, exactly exception (ii) of rq_query_batch_device_begin. */
+rq_status rq_query_batch_device_begin_filtered(const rq_index *idx, const rq_filter *filter, const float *d_queries,
+                                               uint32_t nq, uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank,
+                                               float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n,
+                                               rq_ticket **out_ticket);
 
 /* ---- range search: every neighbour within a per-query radius ----------------------------------------------------- */
 /* For query b with radius r_b (f32, squared L2 like every distance of this header), its probe lists as the plain query ranks
@@ -556,6 +573,11 @@ rq_status rq_set_profiling(int level);
  * "small_batch": 0 (default) = batches of <= 64 queries (the reference's one-query-per-call loop included) run as a handful
  * of fat launches (kernels_small.h) whenever the shape allows (nprobe <= 64, <= 8192 lists, topk <= 256, dim in {64, 128,
  * 256, 512, 768, 1024}), 1 = never (test hook).  Identical results.
+ * "small_batch_filtered": filtered batches on the small-batch path: 1 (default) = automatic -- taken when 16 x topk admitted
+ * candidates, which fill the ranker, lie within the 65 536 stored stream positions a query's block scans at most, i.e.
+ * 16 x topk x (stored rows of the lists that admit anything) / (admitted rows) <= 65 536; the block's stage boundaries are stretched
+ * by the same ratio --, 0 = never (filtered batches take the staged launches), 2 = whenever the shape allows (tests).
+ * Identical results.
  * "dense_dir": test hook, 1 (default) = the VALU stages of large batches write their survivor runs into a directory
  * indexed by stream position (nothing to sort), 0 = runs are appended and the directory is sorted.
  * "prep_placement": 1 (default) = a pass whose only matrix-core stage is the final one groups that stage before the query

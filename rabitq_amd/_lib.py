@@ -23,7 +23,7 @@ EXPORTS = [
     "rq_version", "rq_abi_version", "rq_last_error", "rq_init", "rq_normalize", "rq_normalize_device", "rq_build", "rq_build_device", "rq_build_from_path",
     "rq_build_metric", "rq_build_device_metric", "rq_build_from_path_metric", "rq_builder_create_metric", "rq_from_arrays_metric", "rq_kmeans_device", "rq_builder_create", "rq_builder_assign_chunk", "rq_builder_order", "rq_builder_place_chunk", "rq_builder_finish", "rq_builder_free", "rq_builder_stats", "rq_load_dir",
     "rq_dump_dir", "rq_load_json", "rq_dump_json", "rq_free", "rq_from_arrays", "rq_info", "rq_get_array", "rq_get_device_ptr", "rq_query",
-    "rq_query_batch", "rq_query_batch_device", "rq_query_batch_device_begin", "rq_query_batch_device_end", "rq_filter_create", "rq_filter_rows", "rq_filter_free", "rq_query_batch_filtered", "rq_query_batch_device_filtered", "rq_range_search", "rq_range_search_device", "rq_range_result_info", "rq_range_result_device_ptrs", "rq_range_result_copy", "rq_range_result_free", "rq_add", "rq_remove", "rq_last_mutate_stats", "rq_coarse_topk_device", "rq_merge_smallest_u64_device", "rq_query_batch_device_probed", "rq_query_batch_device_seeded", "rq_partition_lists", "rq_shard_index", "rq_query_batch_sharded_device", "rq_set_collectives", "rq_metrics", "rq_metrics_reset", "rq_rotate", "rq_rotate_device",
+    "rq_query_batch", "rq_query_batch_device", "rq_query_batch_device_begin", "rq_query_batch_device_end", "rq_filter_create", "rq_filter_rows", "rq_filter_free", "rq_query_batch_filtered", "rq_query_batch_device_filtered", "rq_query_batch_device_begin_filtered", "rq_range_search", "rq_range_search_device", "rq_range_result_info", "rq_range_result_device_ptrs", "rq_range_result_copy", "rq_range_result_free", "rq_add", "rq_remove", "rq_last_mutate_stats", "rq_coarse_topk_device", "rq_merge_smallest_u64_device", "rq_query_batch_device_probed", "rq_query_batch_device_seeded", "rq_partition_lists", "rq_shard_index", "rq_query_batch_sharded_device", "rq_set_collectives", "rq_metrics", "rq_metrics_reset", "rq_rotate", "rq_rotate_device",
     "rq_quantize_pack",
     "rq_coarse_rank", "rq_query_prep", "rq_scan", "rq_rerank", "rq_set_profiling", "rq_set_option", "rq_last_profile",
 ]
@@ -165,6 +165,7 @@ def lib():
         "rq_filter_free": (None, [vp]),
         "rq_query_batch_filtered": (i32, [vp, vp, f32p, u32, u32, u32, u32, C.c_int, f32p, u32p, u32p]),
         "rq_query_batch_device_filtered": (i32, [vp, vp, f32p, u32, u32, u32, u32, C.c_int, f32p, u32p, u32p]),
+        "rq_query_batch_device_begin_filtered": (i32, [vp, vp, f32p, u32, u32, u32, u32, C.c_int, f32p, u32p, u32p, pp]),
         "rq_range_search": (i32, [vp, vp, f32p, u32, u32, u32, f32p, pp]),
         "rq_range_search_device": (i32, [vp, vp, f32p, u32, u32, u32, f32p, pp]),
         "rq_range_result_info": (i32, [vp, C.POINTER(u32), C.POINTER(u64)]),

@@ -29,6 +29,7 @@ struct QueryParams {
 #define RQ_MAX_CAP_HINT 32768u
 #define RQ_MAX_NQ_PER_PASS 65536u
 #define RQ_MAX_PROBE 16384u
+#define RQ_SB_FILT_REACH 65536u  // stored stream positions a query's block scans at most on a filtered small-batch pass
 
 // The dimensions with a lane-group quantisation kernel and its shape: X(dim, lanes per pair, rounds, pairs per block and round, pairs
 // in flight per lane group).  Every other dimension takes the generic prep_kernel (and neither a listed nor a placed pass).
@@ -130,19 +131,36 @@ static void plan_pass(const rq_index *idx, const QueryParams &qp, bool has_row_m
 
     // ---- the stage list ---------------------------------------------------------------------------------------------
     // small batches: few, fat launches (kernels_small.h)
-    // (filtered passes take the staged launches: the small-batch kernels have no filtered form yet)
     const bool sb_w = W == 1 || W == 2 || W == 4 || W == 8 || W == 12 || W == 16;
-    pl.small = g_small_batch.load() == 0 && nq <= RQ_SB_MAX_NQ && !ext_lists && !has_row_map && !qp.thr_init && !filt && sb_w &&
+    pl.small = g_small_batch.load() == 0 && nq <= RQ_SB_MAX_NQ && !ext_lists && !has_row_map && !qp.thr_init && sb_w &&
                k <= RQ_SB_MAX_K && nprobe <= 64 && topk <= RQ_SB_MAX_TOPK && qp.cap <= 4 * RQ_DEFAULT_CAP;
+    // A filtered pass (option small_batch_filtered: 0 never, 1 automatic, 2 whenever the shape allows): the block's stage boundaries
+    // are stretched by 1 / density, the filter's density inside the lists that admit anything (lists that admit nothing take no stream
+    // positions), so that the ranker sees as many ADMITTED candidates per stage as an unfiltered pass sees candidates -- but a
+    // query's block never scans more than RQ_SB_FILT_REACH stored positions.  Automatic: the path is taken when the first stage
+    // (16 x topk admitted candidates, which fill the heap) fits that reach; a sparser filter would hand the final stage a threshold
+    // that is still f32::MAX, and every admitted row of the probed lists would survive it: such passes stay on the staged launches.
+    uint64_t sb_first = 16ull * std::max<uint32_t>(topk, 1), sb_span = (uint64_t)std::max(1, g_sb_span.load());
+    if (pl.small && filt) {
+        const int fopt = g_sb_filtered.load();
+        const double dens = filt->live_rows ? (double)filt->rows / (double)filt->live_rows : 0.0;
+        const double first_f = dens > 0.0 ? (double)sb_first / dens : 2.0 * RQ_SB_FILT_REACH;
+        pl.small = fopt == 2 || (fopt == 1 && first_f <= (double)RQ_SB_FILT_REACH);
+        sb_span = dens > 0.0 ? (uint64_t)std::min<double>((double)sb_span / dens, (double)RQ_SB_FILT_REACH) : RQ_SB_FILT_REACH;
+        sb_first = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::min<double>(first_f, (double)RQ_SB_FILT_REACH), sb_span));
+    }
     if (pl.small) {
         // the early stages run inside one block per query: the first one takes what would be two (16 x topk candidates
         // under threshold f32::MAX cost one gather round), and the in-block part ends after 64 K candidates at the latest
-        plan_stages(idx, nq, nprobe, 16ull * std::max<uint32_t>(topk, 1), gopt >= 2 ? (uint64_t)gopt : 8, (uint64_t)std::max(1, g_sb_span.load()), pl);
+        plan_stages(idx, nq, nprobe, sb_first, gopt >= 2 ? (uint64_t)gopt : 8, sb_span, pl);
         if (pl.nstages > RQ_SB_MAX_STAGES) pl.small = false;
     }
     if (pl.small) {
         // a short remainder (small indexes, few probes) is scanned in the block as well: no further launch
-        const bool whole = pl.sb_whole = pl.nstages == 0 || (total_max - pl.st[pl.nstages - 1].s_lo) * (uint64_t)(dim / 8 + 16) <= (1ull << 20);
+        // (filtered: only within the block's reach; and a stream that the stretched first stage covers alone stays in the block --
+        // handed on, its one stage would run under threshold f32::MAX)
+        const bool fits = pl.nstages == 0 || (total_max - pl.st[pl.nstages - 1].s_lo) * (uint64_t)(dim / 8 + 16) <= (1ull << 20);
+        const bool whole = pl.sb_whole = filt ? pl.nstages == 0 || ((fits || pl.nstages == 1) && total_max <= RQ_SB_FILT_REACH) : fits;
         pl.sb_nstages = whole ? pl.nstages : pl.nstages - 1;
         for (uint32_t i = 0; i < pl.sb_nstages; ++i) pl.sb_lo[i] = pl.st[i].s_lo, pl.sb_hi[i] = pl.st[i].s_hi;
         const StagePlan fin = whole ? StagePlan{} : pl.st[pl.nstages - 1];

@@ -131,6 +131,25 @@ static rq_status finish_pass(const rq_index *idx, Workspace &ws, PassResult *res
     return RQ_OK;
 }
 
+// sb_query_kernel<W, mode, filtered>: one block per query (the filtered instantiations: inst_small_filt.hip)
+template <int W>
+static void launch_sb_query_w(int mode, uint32_t nq, size_t dyn, hipStream_t st, const SbArgs &sa) {
+    if (mode == 2) sb_query_kernel<W, 2, false><<<nq, 1024, dyn, st>>>(sa);
+    else if (mode == 1) sb_query_kernel<W, 1, false><<<nq, 1024, dyn, st>>>(sa);
+    else sb_query_kernel<W, 0, false><<<nq, 1024, dyn, st>>>(sa);
+}
+static void launch_sb_query(uint32_t W, int mode, bool filtered, uint32_t nq, size_t dyn, hipStream_t st, const SbArgs &sa) {
+    if (filtered) return launch_sb_query_filtered(W, mode, nq, dyn, st, sa);
+    switch (W) {
+        case 1: launch_sb_query_w<1>(mode, nq, dyn, st, sa); break;
+        case 2: launch_sb_query_w<2>(mode, nq, dyn, st, sa); break;
+        case 4: launch_sb_query_w<4>(mode, nq, dyn, st, sa); break;
+        case 8: launch_sb_query_w<8>(mode, nq, dyn, st, sa); break;
+        case 12: launch_sb_query_w<12>(mode, nq, dyn, st, sa); break;
+        default: launch_sb_query_w<16>(mode, nq, dyn, st, sa); break;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // one pass: the plan (host_plan.h) executed as phases
 // ------------------------------------------------------------------------------------------------
@@ -180,6 +199,11 @@ struct Pass {
         sa.scal = ws.scal.p, sa.qnib = ws.qnib.p, sa.rough_cnt = ws.rough_cnt.p, sa.surv_cnt = ws.surv_cnt.p, sa.totals = ws.totals.p;
         sa.rs = rs, sa.out_dist = d_out_dist, sa.out_id = d_out_id, sa.out_n = d_out_n, sa.recs = ws.recs.p, sa.fs = idx->fstats;
         sa.k = k, sa.dim = dim, sa.nprobe = nprobe, sa.topk = topk, sa.cap = qp.cap, sa.hcap = qp.hcap;
+        const rq_filter *filt = qp.filter;
+        if (filt) {
+            RQC(ws.stream_len.ensure(nq));
+            sa.pos_bits = filt->pos_bits.p, sa.sub_off = filt->sub_off.p, sa.stream_len = ws.stream_len.p;
+        }
         sa.stamps = (pl.dbg & 4096) ? ws.stat.p : nullptr;
         if (sa.stamps) HIPC(hipMemsetAsync(ws.stat.p, 0, 8, st));
         else HIPC(hipMemsetAsync(ws.stat.p, 0, 256 * sizeof(unsigned long long), st));  // (the counters of a final matrix-core stage, if any)
@@ -197,21 +221,7 @@ struct Pass {
         pf.begin(PF_EARLY);
         const size_t dyn = (size_t)RQ_SB_CAP * sizeof(SurvRec) + (size_t)dim * 4 + (size_t)topk * 16;
         const int mode = qp.heuristic ? 2 : (topk < 64 ? 1 : 0);
-#define RQ_SBQ(WW)                                                             \
-    do {                                                                       \
-        if (mode == 2) sb_query_kernel<WW, 2><<<nq, 1024, dyn, st>>>(sa);      \
-        else if (mode == 1) sb_query_kernel<WW, 1><<<nq, 1024, dyn, st>>>(sa); \
-        else sb_query_kernel<WW, 0><<<nq, 1024, dyn, st>>>(sa);                \
-    } while (0)
-        switch (W) {
-            case 1: RQ_SBQ(1); break;
-            case 2: RQ_SBQ(2); break;
-            case 4: RQ_SBQ(4); break;
-            case 8: RQ_SBQ(8); break;
-            case 12: RQ_SBQ(12); break;
-            default: RQ_SBQ(16); break;
-        }
-#undef RQ_SBQ
+        launch_sb_query(W, mode, filt != nullptr, nq, dyn, st, sa);
         pf.end();
         qpad = ws.qpad.p;
         sb_results_done = pl.sb_whole && !qp.heuristic;
@@ -1048,10 +1058,10 @@ struct rq_ticket {
 
 static rq_status query_device_begin(rq_index *idx, const float *d_q, uint32_t nq, uint32_t len, uint32_t probe,
                                     uint32_t topk, bool heuristic, float *d_out_dist, uint32_t *d_out_id,
-                                    uint32_t *d_out_n, rq_ticket **out) {
+                                    uint32_t *d_out_n, rq_ticket **out, const rq_filter *filter = nullptr) {
     if (!out) return fail(RQ_ERR_INVALID, "null argument");
     *out = nullptr;
-    RQC(validate_query(idx, d_q, len, probe, topk, d_out_dist, d_out_id, d_out_n));
+    RQC(validate_query(idx, d_q, len, probe, topk, d_out_dist, d_out_id, d_out_n, filter));
     std::unique_ptr<rq_ticket> t(new rq_ticket());
     t->idx = idx;
     memset(&t->prof, 0, sizeof t->prof);
@@ -1061,9 +1071,9 @@ static rq_status query_device_begin(rq_index *idx, const float *d_q, uint32_t nq
         explicit Open(rq_index *x) : i(x) { i->open_tickets.fetch_add(1); }
         ~Open() { if (!keep) i->open_tickets.fetch_sub(1); }
     } open(idx);
-    t->qp = topk_pass_params(idx, nq, len, probe, topk, heuristic, nullptr, false, false);
+    t->qp = topk_pass_params(idx, nq, len, probe, topk, heuristic, filter, false, false);  // (the filter travels in the ticket's parameters: _end's re-runs and hint updates use it)
     if (nq == 0 || t->qp.nq < nq) {  // nothing to overlap / several passes: synchronous
-        t->status = query_device(idx, d_q, nq, len, probe, topk, heuristic, d_out_dist, d_out_id, d_out_n);
+        t->status = query_device(idx, d_q, nq, len, probe, topk, heuristic, d_out_dist, d_out_id, d_out_n, nullptr, nullptr, nullptr, nullptr, filter);
         t->done = true;
         open.keep = true;
         *out = t.release();

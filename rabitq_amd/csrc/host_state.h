@@ -307,6 +307,7 @@ struct rq_filter {
     DevBuf<uint32_t> sub_off;       // k + 1: list offsets of the sub-index (admitted rows of list c = sub_off[c + 1] - sub_off[c])
     DevBuf<ScanExtra> extra;        // what the filtered scans read through ScanArgs::x outside arena stages: only `allow` is set
     uint64_t rows = 0;              // admitted rows of the whole index
+    uint64_t live_rows = 0;         // stored rows of the lists that admit anything (rows / live_rows: the filter's density inside the lists a pass scans)
     // what its passes learnt about their survivor buffers (as rq_index::cap_hint / arena_hint / big_dirs_hint): a filter whose rows
     // are far from the queries lets many more candidates through than the unfiltered query, and must not resize the index's
     // unfiltered passes -- nor they its
@@ -703,6 +704,7 @@ static std::atomic<int> g_shared_thr{1};  // rq_query_batch_sharded_device: thre
 static std::atomic<int> g_sb_span{2560};  // developer knob: stream positions a query's block scans itself at most (small-batch path)
 static std::atomic<int> g_seg_opt{1};  // per-query survivor segments in the final stage: 0 never, 1 once the index has shown that the default capacity overflows, 2 every large batch (tests)
 static std::atomic<int> g_pass_overlap{1};  // a call of several passes keeps two of them in flight (1, default) or runs them one after the other (0)
+static std::atomic<int> g_sb_filtered{1};  // filtered passes on the small-batch path: 0 = never (staged launches), 1 = automatic (plan_pass), 2 = whenever the shape allows (tests)
 static std::atomic<int> g_small_batch{0};  // small-batch path (kernels_small.h): 0 = whenever it applies (default), 1 = never (test hook)
 static std::atomic<int> g_dense_dir{1};  // dense run directories for the VALU stages of large batches (0 = always append + sort: test hook)
 
@@ -802,6 +804,9 @@ static hipError_t set_scan_mfma_attr() {
     return hipFuncSetAttribute(reinterpret_cast<const void *>(scan_mfma_kernel<W, NT, true, false, true>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)scan_mfma_ring_bytes(W));
 }
+// the filtered instantiations of sb_query_kernel live in a translation unit of their own (inst_small_filt.hip)
+void launch_sb_query_filtered(uint32_t W, int mode, uint32_t nq, size_t dyn, hipStream_t st, const SbArgs &sa);
+hipError_t sb_query_filtered_set_attributes(int bytes);
 static rq_status ensure_kernel_attributes() {
     static std::once_flag once;
     static hipError_t err = hipSuccess;
@@ -831,9 +836,9 @@ static rq_status ensure_kernel_attributes() {
         set(reinterpret_cast<const void *>(sb_finish_kernel<true>), 104 * 1024, "sb_finish_kernel");   // (+ 33 KiB of static LDS)
         set(reinterpret_cast<const void *>(sb_finish_kernel<false>), 104 * 1024, "sb_finish_kernel");  // (+ 49 KiB of static LDS)
 #define RQ_SBQ_ATTR(WW)                                                                                  \
-    set(reinterpret_cast<const void *>(sb_query_kernel<WW, 0>), 120 * 1024, "sb_query_kernel");          \
-    set(reinterpret_cast<const void *>(sb_query_kernel<WW, 1>), 120 * 1024, "sb_query_kernel");          \
-    set(reinterpret_cast<const void *>(sb_query_kernel<WW, 2>), 120 * 1024, "sb_query_kernel")
+    set(reinterpret_cast<const void *>(sb_query_kernel<WW, 0, false>), 120 * 1024, "sb_query_kernel");   \
+    set(reinterpret_cast<const void *>(sb_query_kernel<WW, 1, false>), 120 * 1024, "sb_query_kernel");   \
+    set(reinterpret_cast<const void *>(sb_query_kernel<WW, 2, false>), 120 * 1024, "sb_query_kernel")
         RQ_SBQ_ATTR(1);
         RQ_SBQ_ATTR(2);
         RQ_SBQ_ATTR(4);
@@ -841,6 +846,7 @@ static rq_status ensure_kernel_attributes() {
         RQ_SBQ_ATTR(12);
         RQ_SBQ_ATTR(16);
 #undef RQ_SBQ_ATTR
+        if (err == hipSuccess && (err = sb_query_filtered_set_attributes(120 * 1024)) != hipSuccess) what = "sb_query_kernel (filtered)";
         auto chk = [&](hipError_t e, const char *name) {
             if (err == hipSuccess && e != hipSuccess) err = e, what = name;
         };

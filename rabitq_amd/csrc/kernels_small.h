@@ -234,6 +234,10 @@ struct SbArgs {
     uint32_t fill_final;  // 1: the pair-major work records of the stage [final_lo, end) are written here
     uint32_t final_lo;
     unsigned long long *stamps;  // developer hook (scan_debug bit 4096): block 0 records the 100 MHz clock at its phase boundaries
+    // filtered pass (FILT instantiations): the filter's position bitmap and the sub-index's list offsets; the
+    // stream keeps the stored positions (their lengths go to stream_len), only the rough counter follows the sub-index
+    const uint32_t *pos_bits, *sub_off;
+    unsigned long long *stream_len;
 };
 
 // results of a finished query (src/rerank.rs:108-113: the heap's Vec order) and its share of the pass totals
@@ -258,7 +262,9 @@ __device__ __forceinline__ void sb_write_results(const ReplayState &st, uint32_t
 }
 
 // MODE 0: heap ranker, heap in LDS; 1: heap ranker, heap in a register pair (topk < 64); 2: heuristic ranker
-template <int W, int MODE>
+// FILT: only rows the filter admits pass the gate (rough < thr && admitted(pos)), a probe slot whose list admits nothing is skipped
+// before anything of it is fetched, and the rough counter sums the admitted rows of the probed lists
+template <int W, int MODE, bool FILT>
 __global__ __launch_bounds__(1024) void sb_query_kernel(const SbArgs a) {
     constexpr bool HEUR = MODE == 2, REGHEAP = MODE == 1;
     constexpr int LP = W == 1 ? 16 : (W == 2 ? 32 : 64), R = W <= 4 ? 1 : W / 4;
@@ -271,6 +277,7 @@ __global__ __launch_bounds__(1024) void sb_query_kernel(const SbArgs a) {
     __shared__ uint32_t wcnt[4][16];
     __shared__ float s_thr, s_recent;
     __shared__ uint32_t s_hlen, s_precise, s_need, s_nsurv, s_nshadow, s_wcount, s_alen, s_ovf;
+    __shared__ uint32_t s_adm[FILT ? 64 : 1];  // (FILT) admitted rows of every probe slot's list (nprobe <= 64 on this path)
     const uint32_t b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const uint32_t k = a.k, dim = a.dim, nprobe = a.nprobe, topk = a.topk;
     uint32_t n_stamp = 0;
@@ -312,7 +319,21 @@ __global__ __launch_bounds__(1024) void sb_query_kernel(const SbArgs a) {
     }
     __syncthreads();
     stamp();
-    if (wave == 0) pair_prefix_row(a.scal, b, nprobe, a.rough_cnt);
+    if constexpr (FILT) {
+        // the in-block twin of pair_split_kernel + pair_prefix_filtered_kernel: a list that admits nothing is settled as an empty
+        // one (as on the staged filtered route: it takes no stream positions, so a filter of whole lists leaves the stream of its
+        // sub-index), every other list keeps its stored positions; the rough counter comes from the sub-index's offsets
+        if (wave == 0) {
+            const uint32_t c = lane < nprobe ? a.probe_cluster[(uint64_t)b * nprobe + lane] : 0xFFFFFFFFu;
+            const uint32_t adm = c < k ? a.sub_off[c + 1] - a.sub_off[c] : 0u;
+            s_adm[lane] = adm;  // (the scan loop's skip test)
+            if (lane < nprobe && adm == 0u) a.scal[(uint64_t)b * nprobe + lane].list_len = 0u;
+            __threadfence_block();
+            pair_prefix_row(a.scal, b, nprobe, a.rough_cnt, a.probe_cluster, a.sub_off, k, a.stream_len);
+        }
+    } else {
+        if (wave == 0) pair_prefix_row(a.scal, b, nprobe, a.rough_cnt);
+    }
     __syncthreads();
     stamp();
 
@@ -346,6 +367,9 @@ __global__ __launch_bounds__(1024) void sb_query_kernel(const SbArgs a) {
     for (uint32_t sg = 0; sg < a.nstages; ++sg) {
         const uint32_t s_lo = a.s_lo[sg], s_hi = a.s_hi[sg];
         for (uint32_t slot = 0; slot < nprobe; ++slot) {
+            if constexpr (FILT) {  // nothing admitted in this list (scalar, block-uniform): none of its operands is fetched
+                if (__builtin_amdgcn_readfirstlane(s_adm[slot]) == 0u) continue;
+            }
             PairScalars ps = a.scal[(uint64_t)b * nprobe + slot];
             {  // the same record in every lane: held in scalar registers, so that the loops below are scalar-controlled and the
                // query-side terms of the rough distance enter the vector ops as scalar operands
@@ -391,6 +415,7 @@ __global__ __launch_bounds__(1024) void sb_query_kernel(const SbArgs a) {
                 const float thr = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, s_thr)));
                 uint32_t pos[CPT], code[CPT][2 * W];
                 float4 fac[CPT];
+                uint32_t adw[FILT ? CPT : 1];  // (FILT) the candidates' admission words, in the same batch of loads
                 bool in[CPT];
 #pragma unroll
                 for (int c = 0; c < CPT; ++c) {  // sub-tile c: positions p0 + 1024 c + t
@@ -412,6 +437,7 @@ __global__ __launch_bounds__(1024) void sb_query_kernel(const SbArgs a) {
                         }
                     }
                     fac[c] = a.factors[pos[c]];
+                    if constexpr (FILT) adw[c] = a.pos_bits[pos[c] >> 5];
                 }
                 float rough[CPT];
                 uint64_t m[CPT];
@@ -424,7 +450,9 @@ __global__ __launch_bounds__(1024) void sb_query_kernel(const SbArgs a) {
                         for (int p = 0; p < 4; ++p) cp[p] += (uint32_t)__builtin_popcount(code[c][i] & plane(p, i));
                     const uint32_t acc = cp[0] + (cp[1] << 1) + (cp[2] << 2) + (cp[3] << 3);
                     rough[c] = rough_distance(acc, fac[c], ps.lower, ps.delta, ps.sumq, ps.ycd, ps.ycd_sqrt);  // src/rabitq.rs:352-363
-                    m[c] = __ballot(in[c] && rough[c] < thr);                                                   // src/rerank.rs:84
+                    bool pass = in[c] && rough[c] < thr;                                                        // src/rerank.rs:84
+                    if constexpr (FILT) pass = pass && ((adw[c] >> (pos[c] & 31u)) & 1u);
+                    m[c] = __ballot(pass);
                     if (lane == 0) wcnt[c][wave] = (uint32_t)__popcll(m[c]);
                 }
                 __syncthreads();

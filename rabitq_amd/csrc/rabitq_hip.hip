@@ -621,6 +621,12 @@ rq_status rq_query_batch_device_begin(const rq_index *idx, const float *d_querie
     return query_device_begin(const_cast<rq_index *>(idx), d_queries, nq, len, probe, topk, heuristic_rank != 0,
                               d_out_dist, d_out_id, d_out_n, out_ticket);
 }
+rq_status rq_query_batch_device_begin_filtered(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq,
+                                               uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank, float *d_out_dist,
+                                               uint32_t *d_out_id, uint32_t *d_out_n, rq_ticket **out_ticket) {
+    return query_device_begin(const_cast<rq_index *>(idx), d_queries, nq, len, probe, topk, heuristic_rank != 0,
+                              d_out_dist, d_out_id, d_out_n, out_ticket, filter);
+}
 rq_status rq_query_batch_device_end(rq_ticket *ticket) { return query_device_end(ticket); }
 
 // Device staging of the host-pointer entry points: grown on demand, kept per host thread so a
@@ -795,6 +801,10 @@ rq_status rq_filter_create(const rq_index *idx, const uint32_t *allow_bits, uint
     hx.allow = f->pos_bits.p;
     HIPC(hipMemcpy(f->extra.p, &hx, sizeof hx, hipMemcpyHostToDevice));
     f->rows = h_off[idx->k];
+    if (idx->h_offsets.size() == (size_t)idx->k + 1) {
+        for (uint32_t c = 0; c < idx->k; ++c) f->live_rows += h_cnt[c] ? idx->h_offsets[c + 1] - idx->h_offsets[c] : 0u;
+    } else
+        f->live_rows = n;
     *out = f.release();
     return RQ_OK;
 }
@@ -934,6 +944,11 @@ rq_status rq_set_option(const char *name, int value) {
     if (std::string(name) == "small_batch") {  // 0 = batches of <= 64 queries take the few-launch path when it applies, 1 = never
         if (value < 0 || value > 1) return fail(RQ_ERR_INVALID, "small_batch must be 0 or 1");
         g_small_batch = value;
+        return RQ_OK;
+    }
+    if (std::string(name) == "small_batch_filtered") {  // filtered batches of <= 64 queries on the few-launch path (results identical for every value)
+        if (value < 0 || value > 2) return fail(RQ_ERR_INVALID, "small_batch_filtered must be 0, 1 or 2");
+        g_sb_filtered = value;
         return RQ_OK;
     }
     if (std::string(name) == "dense_dir") {  // test hook: 0 = run descriptors always appended and sorted, 1 = dense directories where they fit

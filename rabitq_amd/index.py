@@ -427,13 +427,19 @@ class RaBitQ:
         return RangeResult(self, h)
 
     def query_batch_device_begin(self, q_ptr: int, nq: int, length: int, probe: int, topk: int, out_dist_ptr: int,
-                                 out_id_ptr: int, out_n_ptr: int, heuristic_rank: bool = False):
+                                 out_id_ptr: int, out_n_ptr: int, heuristic_rank: bool = False, filter: Filter = None):
         """Enqueue a device-resident batch and return a ticket; finish it with query_batch_device_end(ticket).
-        Batches begun back to back overlap on the device (each has its own workspace and stream)."""
+        Batches begun back to back overlap on the device (each has its own workspace and stream).
+        filter: only its rows can be returned; it must stay open until the ticket has been ended."""
         t = C.c_void_p()
-        check(lib().rq_query_batch_device_begin(self._h, C.c_void_p(q_ptr), nq, length, probe, topk, int(heuristic_rank),
-                                                C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr), C.c_void_p(out_n_ptr),
-                                                C.byref(t)))
+        if filter is None:
+            check(lib().rq_query_batch_device_begin(self._h, C.c_void_p(q_ptr), nq, length, probe, topk, int(heuristic_rank),
+                                                    C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr), C.c_void_p(out_n_ptr),
+                                                    C.byref(t)))
+        else:
+            check(lib().rq_query_batch_device_begin_filtered(self._h, _fh(filter), C.c_void_p(q_ptr), nq, length, probe, topk,
+                                                             int(heuristic_rank), C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr),
+                                                             C.c_void_p(out_n_ptr), C.byref(t)))
         return t
 
     @staticmethod

@@ -10,7 +10,7 @@ synthetic mixture of tests/synth.py as bench.py generates it).  Prints ONE JSON 
   sub_index_...      the by-list filter's sub-index built on its own: its unfiltered call timed, and whether its results (ids mapped
                      back) equal the filtered call's bit for bit
   small_calls        median ms per call of one query per call (host entry) and of 64 queries per call (device entry):
-                     unfiltered, random 10 %, 10 % by lists
+                     unfiltered, random 10 % and 1 %, 10 % by lists
   recall10_filtered  recall@10 of --gt-queries queries with the random 10 % filter against brute force over the admitted rows
 
   python scripts/filtered_bench.py [--vectors 100000000] [--steps 5]
@@ -202,11 +202,11 @@ def main():
         prof[name] = {key: (round(p[key], 2) if isinstance(p[key], float) else p[key]) for key in
                       ("ms_scan", "ms_scan_matrix", "ms_rerank", "ms_total", "scan_candidates", "rerank_candidates")}
         rqi.set_option("scan_gate", 0)
-    # small calls: one query per call through the host entry (the reference's own loop; filtered calls take the staged launches,
-    # unfiltered ones the small-batch path) and 64 queries per device call; median wall time per call
+    # small calls: one query per call through the host entry (the reference's own loop) and 64 queries per device call, on the
+    # small-batch path with or without a filter (option small_batch_filtered); median wall time per call
     small = {}
     qhost = qsets[0][:200].cpu().numpy()
-    for name, filt in (("unfiltered", None), ("10", filters["10"]), ("10_lists", filters["10_lists"])):
+    for name, filt in (("unfiltered", None), ("10", filters["10"]), ("1", filters["1"]), ("10_lists", filters["10_lists"])):
         t1 = []
         for i in range(qhost.shape[0]):
             ts = time.perf_counter()
