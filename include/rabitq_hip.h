@@ -67,7 +67,7 @@ typedef struct {
     uint64_t n;            /* number of vectors */
     uint64_t n_hbm;        /* raw vectors resident in HBM; the other n - n_hbm (list tails) are in pinned host memory */
     uint32_t split_rows;   /* 1: the raw vectors are stored as split rows (option "split_rows"); appended in 0.5.0 */
-    uint32_t metric;       /* RQ_METRIC_L2 or RQ_METRIC_COSINE (was reserved0, always 0, before 0.8.0) */
+    uint32_t metric;       /* RQ_METRIC_L2, RQ_METRIC_COSINE or RQ_METRIC_IP (was reserved0, always 0, before 0.8.0) */
 } rq_info_t;
 
 /* ---- library ------------------------------------------------------------------------------- */
@@ -82,7 +82,8 @@ typedef struct {
  * index is refused; later in 0.7, additions only: range search -- rq_range_search* and rq_range_result_*;
  * 0.8.0: cosine metric -- rq_*_metric, rq_normalize*, rq_info_t.reserved0 became metric, additions only;
  * later in 0.8, additions only: rq_query_batch_device_begin_filtered, option "small_batch_filtered" -- filtered batches of <= 64
- * queries on the small-batch path).
+ * queries on the small-batch path;
+ * 0.9.0: inner-product metric, additions only -- RQ_METRIC_IP, rq_*_ip, rq_ip_*, rq_augment*, rq_row_sqnorm_max*).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -107,11 +108,61 @@ rq_status rq_init(int device);                /* select the HIP device for this 
  * division; otherwise N(x) = x bit for bit (a zero row, a subnormal or overflowed norm, a row holding inf or NaN).
  * rq_rerank and rq_query_prep take already-prepared inputs (a padded query, rotated queries) and do not normalise:
  * pass N(q) / its rotation.  An unknown metric is refused with RQ_ERR_INVALID. */
-enum { RQ_METRIC_L2 = 0, RQ_METRIC_COSINE = 1 };
+enum { RQ_METRIC_L2 = 0, RQ_METRIC_COSINE = 1, RQ_METRIC_IP = 2 };
 /* N(x) of n rows of d floats; out is n x ceil64(d) (d <= 4096).  rq_normalize: host pointers; rq_normalize_device: device
  * pointers, returns with `out` complete. */
 rq_status rq_normalize(const float *x, uint64_t n, uint32_t d, float *out);
 rq_status rq_normalize_device(const float *d_x, uint64_t n, uint32_t d, float *d_out);
+
+/* ---- inner-product metric (maximum inner product search) -------------------------------------- */
+/* RQ_METRIC_IP answers "which rows have the largest dot product with q" with the L2 engine, by the standard reduction: with S
+ * a bound on the squared row norms, every row gets one more coordinate sqrt(S - |x|^2) and every query a zero, so that
+ * |A(x) - Q(q)|^2 = S + |q|^2 - 2<x, q> and ascending L2 order is descending inner-product order.  An IP index has three
+ * parameters: d, the raw row length (1 <= d <= 4095); dim = ceil64(d + 1); S, an f32, finite and >= 0.
+ * Row map A(x; S), on the row zero-padded to dim: s = vector_dot_product(x, x) in the order of src/simd.rs:257-314 (the chain
+ * of N(x) above); the row is valid iff s is finite and s <= S (f32 compare); A(x)_i = x_i bit for bit for i < d; A(x)_d =
+ * sqrtf(S - s), one f32 subtraction and a correctly rounded root; every other coordinate is 0.
+ * Query map Q(q): q zero-padded to dim (slot d is 0); no arithmetic.
+ * An IP index of (base, centroids, P, S) equals, bit for bit, the L2 index of (A(base), centroids zero-extended to dim, P):
+ * every array (RQ_ARR_BASE returns the augmented rows), rq_info (metric = RQ_METRIC_IP), the dump.  A query of exactly d
+ * floats (otherwise RQ_ERR_DIM_MISMATCH) returns exactly what that L2 index returns for Q(q): ids, order, distance bits,
+ * out_n, status, counters -- on every query entry (plain, filtered, range, _begin / _end, probed, seeded, coarse, sharded).
+ * Distances are D = |A(x) - Q(q)|^2, unscaled; radii and seeded thresholds are in that unit.  The two conversions, in f32 with
+ * s_q = vector_dot_product(Q(q), Q(q)) in the same order:  ip = 0.5f * ((S + s_q) - D);  radius = (S + s_q) - 2.0f * min_ip.
+ * The index dimension grows by the extra coordinate: for d a multiple of 64 that is one more 64-wide word (128 -> 192).
+ * The *_metric entries take no d / S and keep refusing metric id 2.
+ *
+ * The builds are the L2 signatures plus centroid_cols and sq_bound.  centroids are k x centroid_cols, d <= centroid_cols <=
+ * dim, missing columns are zero (a caller who trains on augmented rows, rq_augment_device, passes d + 1 or dim).  sq_bound:
+ * NaN = automatic, S = the largest s of the input, bit for bit (the streamed builder has no automatic mode and refuses NaN:
+ * take rq_row_sqnorm_max_device over the chunks).  A negative or infinite bound, or an invalid row, is RQ_ERR_INVALID,
+ * rq_last_error names the first offending row, and no index is made; a builder whose chunk was refused can only be freed. */
+rq_status rq_build_ip(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k, const float *orthogonal,
+                      uint64_t seed, uint32_t centroid_cols, float sq_bound, rq_index **out);
+rq_status rq_build_device_ip(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
+                             const float *orthogonal_host, uint64_t seed, uint32_t centroid_cols, float sq_bound, rq_index **out);
+/* (the centroid file's records have centroid_cols = their length) */
+rq_status rq_build_from_path_ip(const char *base_fvecs, const char *centroid_fvecs, const float *orthogonal, uint64_t seed,
+                                float sq_bound, rq_index **out);
+/* d of an IP index and its S; RQ_ERR_INVALID on an index of another metric */
+rq_status rq_ip_params(const rq_index *idx, uint32_t *d, float *sq_bound);
+/* A(x; sq_bound) of n rows of d floats into out, n x ceil64(d + 1); the refusals of the builds (sq_bound = NaN: automatic). */
+rq_status rq_augment(const float *x, uint64_t n, uint32_t d, float sq_bound, float *out);
+rq_status rq_augment_device(const float *d_x, uint64_t n, uint32_t d, float sq_bound, float *d_out);
+/* The largest s of n rows of d floats (0 for n = 0) into *out_max (host memory in both forms); a row whose s is inf or NaN:
+ * RQ_ERR_INVALID. */
+rq_status rq_row_sqnorm_max(const float *x, uint64_t n, uint32_t d, float *out_max);
+rq_status rq_row_sqnorm_max_device(const float *d_x, uint64_t n, uint32_t d, float *out_max);
+/* ip of returned distances: dist and out_ip are nq x topk, n (nullable) the nq result counts: slots at or past n[q] get -inf.
+ * radius of a smallest wanted inner product per query: min_ip and out_radius are nq floats.  queries: nq x len, len = d.
+ * Plain form: host pointers; _device: device pointers, returns with the output complete. */
+rq_status rq_ip_from_dist(const rq_index *idx, const float *queries, uint32_t nq, uint32_t len, const float *dist, uint32_t topk,
+                          const uint32_t *n, float *out_ip);
+rq_status rq_ip_from_dist_device(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t len, const float *d_dist,
+                                 uint32_t topk, const uint32_t *d_n, float *d_out_ip);
+rq_status rq_ip_radius(const rq_index *idx, const float *queries, uint32_t nq, uint32_t len, const float *min_ip, float *out_radius);
+rq_status rq_ip_radius_device(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t len, const float *d_min_ip,
+                              float *d_out_radius);
 
 /* ---- build: RaBitQ::from_path, src/rabitq.rs:159-265 ---------------------------------------- */
 /* `orthogonal` is the dim x dim rotation P (row-major, P[r][c]); the reference draws it from an
@@ -161,6 +212,11 @@ rq_status rq_builder_create(uint64_t n, uint32_t d, const float *d_centroids, ui
 /* rq_builder_create with a metric: on a cosine builder both passes normalise their chunks (the same kernel, the same bits). */
 rq_status rq_builder_create_metric(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
                                    uint64_t seed, uint64_t max_device_base_bytes, uint32_t metric, rq_builder **out);
+/* The streamed build of an inner-product index: both passes augment their chunks with sq_bound (the same kernel, the same
+ * bits); a chunk holding an invalid row is refused with RQ_ERR_INVALID, after which the builder can only be freed. */
+rq_status rq_builder_create_ip(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
+                               uint64_t seed, uint64_t max_device_base_bytes, uint32_t centroid_cols, float sq_bound,
+                               rq_builder **out);
 rq_status rq_builder_assign_chunk(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m);
 rq_status rq_builder_order(rq_builder *b);
 rq_status rq_builder_place_chunk(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m);
@@ -178,13 +234,14 @@ rq_status rq_kmeans_device(const float *d_base, uint64_t n, uint32_t d, uint32_t
 /* ---- persistence: load_from_dir / dump_to_dir, src/rabitq.rs:84-156 -------------------------- */
 /* Byte-compatible with the crate's five-file directory (vecs framing: src/utils.rs:280-364).  A cosine index writes a sixth
  * file, `metric`, holding the text "cosine\n" (an L2 dump stays exactly the five files); rq_load_dir sets the metric when the
- * file is present (unknown content: RQ_ERR_IO). */
+ * file is present (unknown content: RQ_ERR_IO).  An inner-product index writes "ip <d> <S as 8 hex digits>\n". */
 rq_status rq_load_dir(const char *dir, rq_index **out);
 rq_status rq_dump_dir(const rq_index *idx, const char *dir);
 /* load_from_json / dump_to_json, src/rabitq.rs:72-81: the serde_json image of the `RaBitQ` struct (faer `Mat`s as
  * {"nrows","ncols","data": row-major}; base dim x n, centroids dim x k).  A debugging format in the reference too: the
  * text is ~10x the binary directory, so use rq_load_dir / rq_dump_dir for anything large.  A cosine index adds the member
- * "metric":"cosine" (serde ignores unknown members: the reference still loads the file); rq_load_json reads it when present. */
+ * "metric":"cosine" (serde ignores unknown members: the reference still loads the file); rq_load_json reads it when present.  An
+ * inner-product index adds "metric":"ip","ip_d":<d>,"ip_sq_bound_bits":<the bits of S as an integer>. */
 rq_status rq_load_json(const char *path, rq_index **out);
 rq_status rq_dump_json(const rq_index *idx, const char *path);
 void rq_free(rq_index *idx);
@@ -202,6 +259,12 @@ rq_status rq_from_arrays_metric(uint32_t dim, uint64_t n, uint32_t k, const floa
                                 const float *orthogonal, const float *centroids, const uint32_t *offsets,
                                 const uint32_t *map_ids, const uint64_t *codes, const rq_factor_t *factors,
                                 uint32_t metric, rq_index **out);
+/* The same for an inner-product index of row length d and bound sq_bound (dim = ceil64(d + 1), else RQ_ERR_DIM_MISMATCH);
+ * `base` holds augmented rows already. */
+rq_status rq_from_arrays_ip(uint32_t dim, uint64_t n, uint32_t k, const float *base,
+                            const float *orthogonal, const float *centroids, const uint32_t *offsets,
+                            const uint32_t *map_ids, const uint64_t *codes, const rq_factor_t *factors,
+                            uint32_t d, float sq_bound, rq_index **out);
 
 rq_status rq_info(const rq_index *idx, rq_info_t *out);
 /* Copy one array of the index back to host memory (sizes as in rq_from_arrays). */
@@ -343,7 +406,9 @@ void rq_range_result_free(rq_range_result *r);
  * it is mutated (the caller serialises, as Rust's &mut self does).  Workspaces and tile tables of the old layout are released.
  *
  * On a cosine index rq_add normalises the new rows, and the invariant reads: the index equals rq_build_metric(live ORIGINAL
- * rows, RQ_METRIC_COSINE).
+ * rows, RQ_METRIC_COSINE).  On an inner-product index rq_add takes rows of the index's d floats and augments them with the
+ * index's S; a row with s > S or a non-finite s is RQ_ERR_INVALID with the index untouched; the invariant reads: the index
+ * equals rq_build_ip(live ORIGINAL rows, the same S).
  * rq_add: insert m rows (m x d f32, row-major; host or device memory per rows_on_device).  d must pad to the index's dim
  * (ceil64(d) == dim), else RQ_ERR_DIM_MISMATCH.  ids: NULL = the next ids, first = 1 + the largest id the index holds (0 if
  * empty), returned in *out_first_id (RQ_ERR_UNSUPPORTED if the last would pass 2^32 - 1); else m explicit u32 ids in the same

@@ -6,8 +6,8 @@ C ABI in include/rabitq_hip.h.  All arithmetic runs in hand-written HIP kernels
 """
 from .index import RaBitQ, Filter, RangeResult, pack_filter_bits, metrics, metrics_reset, metrics_str, calculate_recall  # noqa: F401
 from . import ops, vecs  # noqa: F401
-from .ops import normalize, cosine_similarity  # noqa: F401
+from .ops import normalize, cosine_similarity, augment, row_sqnorm_max  # noqa: F401
 from ._lib import RabitqError, build  # noqa: F401
 
-__all__ = ["RaBitQ", "Filter", "RangeResult", "pack_filter_bits", "metrics", "metrics_reset", "metrics_str", "calculate_recall", "normalize", "cosine_similarity", "ops", "vecs", "RabitqError",
+__all__ = ["RaBitQ", "Filter", "RangeResult", "pack_filter_bits", "metrics", "metrics_reset", "metrics_str", "calculate_recall", "normalize", "cosine_similarity", "augment", "row_sqnorm_max", "ops", "vecs", "RabitqError",
            "build"]

@@ -20,7 +20,8 @@ STATUS_NAMES = {0: "RQ_OK", -1: "RQ_ERR_INVALID", -2: "RQ_ERR_DIM_MISMATCH", -3:
 
 # every symbol include/rabitq_hip.h declares (checked by tests/test_abi.py against the header)
 EXPORTS = [
-    "rq_version", "rq_abi_version", "rq_last_error", "rq_init", "rq_normalize", "rq_normalize_device", "rq_build", "rq_build_device", "rq_build_from_path",
+    "rq_version", "rq_abi_version", "rq_last_error", "rq_init", "rq_normalize", "rq_normalize_device", "rq_build_ip", "rq_build_device_ip", "rq_build_from_path_ip", "rq_builder_create_ip", "rq_from_arrays_ip",
+    "rq_ip_params", "rq_augment", "rq_augment_device", "rq_row_sqnorm_max", "rq_row_sqnorm_max_device", "rq_ip_from_dist", "rq_ip_from_dist_device", "rq_ip_radius", "rq_ip_radius_device", "rq_build", "rq_build_device", "rq_build_from_path",
     "rq_build_metric", "rq_build_device_metric", "rq_build_from_path_metric", "rq_builder_create_metric", "rq_from_arrays_metric", "rq_kmeans_device", "rq_builder_create", "rq_builder_assign_chunk", "rq_builder_order", "rq_builder_place_chunk", "rq_builder_finish", "rq_builder_free", "rq_builder_stats", "rq_load_dir",
     "rq_dump_dir", "rq_load_json", "rq_dump_json", "rq_free", "rq_from_arrays", "rq_info", "rq_get_array", "rq_get_device_ptr", "rq_query",
     "rq_query_batch", "rq_query_batch_device", "rq_query_batch_device_begin", "rq_query_batch_device_end", "rq_filter_create", "rq_filter_rows", "rq_filter_free", "rq_query_batch_filtered", "rq_query_batch_device_filtered", "rq_query_batch_device_begin_filtered", "rq_range_search", "rq_range_search_device", "rq_range_result_info", "rq_range_result_device_ptrs", "rq_range_result_copy", "rq_range_result_free", "rq_add", "rq_remove", "rq_last_mutate_stats", "rq_coarse_topk_device", "rq_merge_smallest_u64_device", "rq_query_batch_device_probed", "rq_query_batch_device_seeded", "rq_partition_lists", "rq_shard_index", "rq_query_batch_sharded_device", "rq_set_collectives", "rq_metrics", "rq_metrics_reset", "rq_rotate", "rq_rotate_device",
@@ -36,11 +37,13 @@ class RabitqError(RuntimeError):
 
 
 METRIC_L2, METRIC_COSINE = 0, 1   # RQ_METRIC_*
-METRICS = {"l2": METRIC_L2, "cosine": METRIC_COSINE}
+METRIC_IP = 2
+METRICS = {"l2": METRIC_L2, "cosine": METRIC_COSINE, "ip": METRIC_IP}
+METRIC_NAMES = {v: k for k, v in METRICS.items()}
 
 
 def metric_id(metric) -> int:
-    """"l2" / "cosine" (or an RQ_METRIC_* value) -> the C ABI's metric id."""
+    """"l2" / "cosine" / "ip" (or an RQ_METRIC_* value) -> the C ABI's metric id."""
     if isinstance(metric, str):
         if metric.lower() not in METRICS:
             raise ValueError(f"metric must be one of {sorted(METRICS)}, not {metric!r}")
@@ -138,6 +141,20 @@ def lib():
         "rq_build_from_path_metric": (i32, [C.c_char_p, C.c_char_p, f32p, u64, u32, pp]),
         "rq_builder_create_metric": (i32, [u64, u32, f32p, u32, f32p, u64, u64, u32, pp]),
         "rq_from_arrays_metric": (i32, [u32, u64, u32, f32p, f32p, f32p, u32p, u32p, u64p, vp, u32, pp]),
+        "rq_build_ip": (i32, [f32p, u64, u32, f32p, u32, f32p, u64, u32, flt, pp]),
+        "rq_build_device_ip": (i32, [f32p, u64, u32, f32p, u32, f32p, u64, u32, flt, pp]),
+        "rq_build_from_path_ip": (i32, [C.c_char_p, C.c_char_p, f32p, u64, flt, pp]),
+        "rq_builder_create_ip": (i32, [u64, u32, f32p, u32, f32p, u64, u64, u32, flt, pp]),
+        "rq_from_arrays_ip": (i32, [u32, u64, u32, f32p, f32p, f32p, u32p, u32p, u64p, vp, u32, flt, pp]),
+        "rq_ip_params": (i32, [vp, C.POINTER(u32), C.POINTER(flt)]),
+        "rq_augment": (i32, [f32p, u64, u32, flt, f32p]),
+        "rq_augment_device": (i32, [f32p, u64, u32, flt, f32p]),
+        "rq_row_sqnorm_max": (i32, [f32p, u64, u32, C.POINTER(flt)]),
+        "rq_row_sqnorm_max_device": (i32, [f32p, u64, u32, C.POINTER(flt)]),
+        "rq_ip_from_dist": (i32, [vp, f32p, u32, u32, f32p, u32, u32p, f32p]),
+        "rq_ip_from_dist_device": (i32, [vp, f32p, u32, u32, f32p, u32, u32p, f32p]),
+        "rq_ip_radius": (i32, [vp, f32p, u32, u32, f32p, f32p]),
+        "rq_ip_radius_device": (i32, [vp, f32p, u32, u32, f32p, f32p]),
         "rq_kmeans_device": (i32, [f32p, u64, u32, u32, u32, u32, u64, f32p]),
         "rq_builder_create": (i32, [u64, u32, f32p, u32, f32p, u64, u64, pp]),
         "rq_builder_assign_chunk": (i32, [vp, f32p, u64, u64]),

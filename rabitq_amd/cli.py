@@ -1,7 +1,7 @@
 """Benchmark harness with the reference CLI's behaviour (crates/cli/src/main.rs:11-83):
 
     python -m rabitq_amd.cli -b base.fvecs -c centroids.fvecs -q query.fvecs -t truth.ivecs \
-                             -s saved_dir [-p 100] [-k 10] [-h | --heuristic-rank] [--metric l2|cosine]
+                             -s saved_dir [-p 100] [-k 10] [-h | --heuristic-rank] [--metric l2|cosine|ip]
 
 * the flags are the reference's, letter for letter: `-h` is the heuristic re-ranker there (`#[argh(switch, short = 'h')]`,
   main.rs:35-37), not help -- argh reserves only `--help` -- so a caller script written for the reference CLI runs unchanged;
@@ -38,9 +38,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("-h", "--heuristic-rank", "--heuristic_rank", dest="heuristic_rank", action="store_true", help="heuristic re-rank (maybe faster when topk is large)")
     ap.add_argument("--batch", type=int, default=0, help="also time batches of this many queries")
     ap.add_argument("--seed", type=int, default=0, help="seed of the generated rotation when building")
-    ap.add_argument("--metric", choices=["l2", "cosine"], default="l2",
+    ap.add_argument("--metric", choices=["l2", "cosine", "ip"], default="l2",
                     help="metric of the index when building (a saved index keeps its own): cosine normalises rows and queries "
-                         "on the GPU, distances are 2 - 2 cos")
+                         "on the GPU, distances are 2 - 2 cos; ip is maximum inner product search (rows get one more "
+                         "coordinate, distances are S + |q|^2 - 2<x, q> with S the largest squared row norm)")
     return ap
 
 

@@ -318,6 +318,11 @@ struct rq_builder {
     DevBuf<float4> factors_tmp;
     AssignAux assign_aux;
     uint64_t assigned = 0, placed = 0;
+    // inner-product metric: the word augment_rows_kernel records the first invalid row of a chunk in; s of every input row where
+    // the caller has it already (the one-shot builds; null: the kernel runs the chain); a refused chunk ends the builder
+    DevBuf<uint32_t> ip_bad;
+    const float *ip_s_pre = nullptr;
+    bool refused = false;
     // Rows each pass has seen, as disjoint [begin, end) intervals: chunks may come in any order and size, but every row
     // exactly once per pass.  A duplicated chunk would leave other rows with uninitialised labels / codes (and then
     // index the list histogram with garbage), so overlap is refused here and gaps by the row counts in order / finish.
@@ -368,6 +373,7 @@ static rq_status builder_alloc_pass1(rq_builder *b) {
     RQC(b->factors_tmp.alloc(n));
     const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(n, 1), RQ_BUILD_CHUNK);
     if (b->d != dim || idx->metric == RQ_METRIC_COSINE) RQC(b->xpad.alloc(chunk * dim));
+    if (idx->metric == RQ_METRIC_IP) RQC(b->ip_bad.alloc(1));
     RQC(b->xrot.alloc(chunk * dim));
     if (assign_has_mfma(idx->W) && g_assign_impl.load() != 1) RQC(assign_aux_init(idx, b->assign_aux, chunk));
     for (auto &e : b->ev) HIPC(hipEventCreate(&e));
@@ -375,20 +381,28 @@ static rq_status builder_alloc_pass1(rq_builder *b) {
 }
 
 static rq_status builder_create(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
-                                uint64_t seed, uint64_t max_device_base_bytes, uint32_t metric, rq_builder **out) {
+                                uint64_t seed, uint64_t max_device_base_bytes, uint32_t metric, rq_builder **out,
+                                uint32_t cent_cols = 0, float sq_bound = 0.0f) {
     RQC(ensure_device());
     RQC(ensure_kernel_attributes());
     if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
     *out = nullptr;
-    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, "unknown metric " + std::to_string(metric));
+    const bool ip = metric == RQ_METRIC_IP;  // (only the _ip entries pass it: the *_metric entries have refused it)
+    if (!ip && !metric_known(metric)) return fail(RQ_ERR_INVALID, metric_refusal(metric));
     if (!d_centroids || d == 0 || k == 0) return fail(RQ_ERR_INVALID, "bad build arguments");
     if (n >= 0xFFFFFFFFull) return fail(RQ_ERR_UNSUPPORTED, "n must fit u32 ids (rabitq.rs:64-65)");
-    const uint32_t dim = (d + 63) / 64 * 64;  // rabitq.rs:168-179
-    if (dim > 4096) return fail(RQ_ERR_UNSUPPORTED, "dim > 4096 not supported");
+    const uint32_t dim = ip ? ip_dim(d) : (d + 63) / 64 * 64;  // rabitq.rs:168-179
+    if (dim > 4096) return fail(RQ_ERR_UNSUPPORTED, ip ? "d > 4095 not supported by the inner-product metric" : "dim > 4096 not supported");
+    if (!ip) cent_cols = d;
+    if (cent_cols < d || cent_cols > dim)
+        return fail(RQ_ERR_INVALID, "centroid_cols " + std::to_string(cent_cols) + " outside [d, dim] = [" + std::to_string(d) + ", " + std::to_string(dim) + "]");
+    if (ip && !(sq_bound >= 0.0f && sq_bound <= 3.402823466e+38f))
+        return fail(RQ_ERR_INVALID, "sq_bound must be finite and >= 0 (the streamed builder has no automatic mode: rq_row_sqnorm_max_device)");
     std::unique_ptr<rq_builder> b(new rq_builder());
     b->idx.reset(new rq_index());
     rq_index *idx = b->idx.get();
     idx->dim = dim, idx->k = k, idx->n = n, idx->W = dim / 64, idx->metric = metric;
+    if (ip) idx->ip_d = d, idx->ip_S = sq_bound;
     b->d = d, b->budget = max_device_base_bytes;
 
     std::vector<float> Pgen;
@@ -402,7 +416,7 @@ static rq_status builder_create(uint64_t n, uint32_t d, const float *d_centroids
     // centroids: pad, rotate (rabitq.rs:189), transpose for the lane<->centroid kernels
     DevBuf<float> cpad;
     RQC(cpad.alloc((size_t)k * dim));
-    pad_rows_kernel<<<ceil_div((uint64_t)k * dim, 256), 256>>>(d_centroids, cpad.p, k, d, dim);
+    pad_rows_kernel<<<ceil_div((uint64_t)k * dim, 256), 256>>>(d_centroids, cpad.p, k, cent_cols, dim);
     RQC(idx->centroids.alloc((size_t)k * dim));
     launch_rotate(cpad.p, idx->P.p, idx->centroids.p, k, dim, true, nullptr);
     RQC(idx->cent_t.alloc((size_t)dim * k));
@@ -414,9 +428,19 @@ static rq_status builder_create(uint64_t n, uint32_t d, const float *d_centroids
     return RQ_OK;
 }
 
+// inner-product builder: the first invalid row of the chunk just augmented, if any (after a synchronisation)
+static rq_status builder_ip_check(rq_builder *b) {
+    uint32_t bad = 0xFFFFFFFFu;
+    HIPC(hipMemcpy(&bad, b->ip_bad.p, 4, hipMemcpyDeviceToHost));
+    if (bad == 0xFFFFFFFFu) return RQ_OK;
+    b->refused = true;
+    return fail(RQ_ERR_INVALID, "row " + std::to_string(bad) + ": its squared norm is not finite or exceeds sq_bound (the builder can only be freed now)");
+}
+
 // pass 1 for rows [i0, i0 + m) of the input (d_rows: m x d, device)
 static rq_status builder_assign(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m) {
     if (!b || (m && !d_rows)) return fail(RQ_ERR_INVALID, "null argument");
+    if (b->refused) return fail(RQ_ERR_INVALID, "a chunk of this builder was refused: it can only be freed");
     if (b->ordered) return fail(RQ_ERR_INVALID, "rq_builder_assign_chunk after rq_builder_order");
     rq_index *idx = b->idx.get();
     if (i0 > idx->n || m > idx->n - i0) return fail(RQ_ERR_INVALID, "chunk outside [0, n)");
@@ -427,6 +451,10 @@ static rq_status builder_assign(rq_builder *b, const float *d_rows, uint64_t i0,
         const float *src = d_rows + c0 * d;
         if (idx->metric == RQ_METRIC_COSINE) {  // pad + normalise in one launch: everything behind it sees N(x)
             launch_normalize(src, mm, d, dim, b->xpad.p, nullptr);
+            src = b->xpad.p;
+        } else if (idx->metric == RQ_METRIC_IP) {  // pad + augment in one launch: everything behind it sees A(x)
+            HIPC(hipMemset(b->ip_bad.p, 0xFF, 4));
+            launch_augment(src, mm, d, dim, idx->ip_S, b->ip_s_pre, b->xpad.p, b->ip_bad.p, nullptr, nullptr, at);
             src = b->xpad.p;
         } else if (d != dim) {
             pad_rows_kernel<<<ceil_div(mm * dim, 256), 256>>>(src, b->xpad.p, mm, d, dim);
@@ -442,6 +470,7 @@ static rq_status builder_assign(rq_builder *b, const float *d_rows, uint64_t i0,
         HIPC(hipEventRecord(b->ev[3], nullptr));
         HIPC(hipEventSynchronize(b->ev[3]));  // the chunk buffers are reused by the next chunk (and by the caller)
         HIPC(hipGetLastError());
+        if (idx->metric == RQ_METRIC_IP) RQC(builder_ip_check(b));  // (read where the chunk is waited for anyway)
         float t01 = 0, t12 = 0, t23 = 0;
         HIPC(hipEventElapsedTime(&t01, b->ev[0], b->ev[1]));
         HIPC(hipEventElapsedTime(&t12, b->ev[1], b->ev[2]));
@@ -457,6 +486,7 @@ static rq_status builder_assign(rq_builder *b, const float *d_rows, uint64_t i0,
 // cluster ordering (rabitq.rs:232-252) of everything but the raw vectors
 static rq_status builder_order(rq_builder *b) {
     if (!b) return fail(RQ_ERR_INVALID, "null builder");
+    if (b->refused) return fail(RQ_ERR_INVALID, "a chunk of this builder was refused: it can only be freed");
     if (b->ordered) return fail(RQ_ERR_INVALID, "rq_builder_order called twice");
     rq_index *idx = b->idx.get();
     const uint64_t n = idx->n;
@@ -507,6 +537,7 @@ static rq_status builder_order(rq_builder *b) {
 // pass 2 for rows [i0, i0 + m)
 static rq_status builder_place(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m) {
     if (!b || (m && !d_rows)) return fail(RQ_ERR_INVALID, "null argument");
+    if (b->refused) return fail(RQ_ERR_INVALID, "a chunk of this builder was refused: it can only be freed");
     if (!b->ordered) return fail(RQ_ERR_INVALID, "rq_builder_place_chunk before rq_builder_order");
     rq_index *idx = b->idx.get();
     if (i0 > idx->n || m > idx->n - i0) return fail(RQ_ERR_INVALID, "chunk outside [0, n)");
@@ -514,11 +545,15 @@ static rq_status builder_place(rq_builder *b, const float *d_rows, uint64_t i0, 
     if (m) {
         if (idx->metric == RQ_METRIC_COSINE)  // the same kernel as pass 1, storing N(x) at the row's final position
             launch_normalize(d_rows, m, b->d, idx->dim, nullptr, nullptr, b->pos_of_id.p, i0, idx->view());
-        else
+        else if (idx->metric == RQ_METRIC_IP) {  // the same kernel as pass 1 (a caller feeding other rows than it did then is refused)
+            HIPC(hipMemset(b->ip_bad.p, 0xFF, 4));
+            launch_augment(d_rows, m, b->d, idx->dim, idx->ip_S, b->ip_s_pre, nullptr, b->ip_bad.p, nullptr, b->pos_of_id.p, i0, idx->view());
+        } else
             place_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(m, 4), 1u << 20), 256>>>(d_rows, i0, m, b->d, idx->dim,
                                                                                               b->pos_of_id.p, idx->view());
         HIPC(hipDeviceSynchronize());  // the caller may reuse d_rows right away
         HIPC(hipGetLastError());
+        if (idx->metric == RQ_METRIC_IP) RQC(builder_ip_check(b));
     }
     b->placed += m;
     return RQ_OK;
@@ -528,6 +563,7 @@ static rq_status builder_finish(rq_builder *bp, rq_index **out) {
     if (!bp || !out) return fail(RQ_ERR_INVALID, "null argument");
     std::unique_ptr<rq_builder> b(bp);  // consumed whatever happens
     *out = nullptr;
+    if (b->refused) return fail(RQ_ERR_INVALID, "a chunk of this builder was refused");
     if (!b->ordered || b->placed != b->idx->n) return fail(RQ_ERR_INVALID, "rq_builder_finish before every row was placed");
     b->pos_of_id.release();
     RQC(finish_index(b->idx.get()));
@@ -543,6 +579,55 @@ static rq_status build_device(const float *d_base, uint64_t n, uint32_t d, const
     rq_builder *b = nullptr;
     RQC(builder_create(n, d, d_centroids, k, orthogonal_host, seed, 0, metric, &b));
     std::unique_ptr<rq_builder> guard(b);
+    RQC(builder_assign(b, d_base, 0, n));
+    RQC(builder_order(b));
+    RQC(builder_place(b, d_base, 0, n));
+    return builder_finish(guard.release(), out);
+}
+
+// s of n rows of d floats (device) into out_s (nullable, n floats); *out_max = the largest finite s, *out_bad = the first row whose
+// s is not finite or exceeds sq_bound (0xFFFFFFFF: none).  dim: the padded length the chain runs over (a multiple of 64 >= d).
+static rq_status row_sqnorms(const float *d_x, uint64_t n, uint32_t d, uint32_t dim, float sq_bound, float *out_s, float *out_max,
+                             uint32_t *out_bad) {
+    DevBuf<uint32_t> stat;
+    RQC(stat.alloc(3));
+    HIPC(hipMemcpy(stat.p, RQ_SQNORM_STAT_INIT, 12, hipMemcpyHostToDevice));
+    for (uint64_t r0 = 0; r0 < n; r0 += RQ_BUILD_CHUNK)
+        launch_row_sqnorm(d_x + r0 * d, std::min<uint64_t>(RQ_BUILD_CHUNK, n - r0), d, dim, sq_bound, r0, out_s ? out_s + r0 : nullptr, stat.p, nullptr);
+    uint32_t h[3];
+    HIPC(hipMemcpy(h, stat.p, 12, hipMemcpyDeviceToHost));
+    HIPC(hipGetLastError());
+    memcpy(out_max, &h[0], 4);
+    *out_bad = h[1];
+    return RQ_OK;
+}
+// sq_bound of an _ip call resolved against the input: NaN = the largest s; the refusals the contract lists.  s_out: n floats.
+static rq_status ip_resolve_bound(const float *d_x, uint64_t n, uint32_t d, float *sq_bound, float *s_out) {
+    const bool automatic = *sq_bound != *sq_bound;
+    if (!automatic && !(*sq_bound >= 0.0f && *sq_bound <= 3.402823466e+38f)) return fail(RQ_ERR_INVALID, "sq_bound must be finite and >= 0, or NaN for the largest squared norm of the input");
+    float mx = 0.0f;
+    uint32_t bad = 0xFFFFFFFFu;
+    RQC(row_sqnorms(d_x, n, d, ip_dim(d), automatic ? __builtin_inff() : *sq_bound, s_out, &mx, &bad));
+    if (bad != 0xFFFFFFFFu)
+        return fail(RQ_ERR_INVALID, "row " + std::to_string(bad) + ": its squared norm is not finite" + (automatic ? "" : " or exceeds sq_bound"));
+    if (automatic) *sq_bound = mx;
+    return RQ_OK;
+}
+
+static rq_status build_device_ip(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
+                                 const float *orthogonal_host, uint64_t seed, uint32_t cent_cols, float sq_bound, rq_index **out) {
+    RQC(ensure_device());
+    if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
+    *out = nullptr;
+    if ((n && !d_base) || d == 0) return fail(RQ_ERR_INVALID, "bad build arguments");
+    if (d > 4095) return fail(RQ_ERR_UNSUPPORTED, "d > 4095 not supported by the inner-product metric");
+    DevBuf<float> s;  // computed once: the bound, the validity of every row and slot d of both passes come from it
+    RQC(s.alloc(n));
+    RQC(ip_resolve_bound(d_base, n, d, &sq_bound, s.p));
+    rq_builder *b = nullptr;
+    RQC(builder_create(n, d, d_centroids, k, orthogonal_host, seed, 0, RQ_METRIC_IP, &b, cent_cols, sq_bound));
+    std::unique_ptr<rq_builder> guard(b);
+    b->ip_s_pre = s.p;
     RQC(builder_assign(b, d_base, 0, n));
     RQC(builder_order(b));
     RQC(builder_place(b, d_base, 0, n));
@@ -593,18 +678,24 @@ static rq_status write_record(FILE *f, const void *data, uint32_t count, size_t 
 static rq_status copy_base_rows(const rq_index *idx, uint64_t i0, uint64_t m, float *buf, bool to_index);
 static rq_status from_arrays(uint32_t dim, uint64_t n, uint32_t k, const float *base, const float *orthogonal,
                              const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
-                             const uint64_t *codes, const rq_factor_t *factors, uint32_t metric, rq_index **out) {
+                             const uint64_t *codes, const rq_factor_t *factors, uint32_t metric, rq_index **out,
+                             uint32_t ip_d = 0, float ip_S = 0.0f) {
     RQC(ensure_device());
     RQC(ensure_kernel_attributes());
     if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
     *out = nullptr;
-    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, "unknown metric " + std::to_string(metric));
+    const bool ip = metric == RQ_METRIC_IP;  // (only the _ip entry and the loaders pass it)
+    if (!ip && !metric_known(metric)) return fail(RQ_ERR_INVALID, metric_refusal(metric));
     if (dim == 0 || dim % 64 != 0) return fail(RQ_ERR_DIM_MISMATCH, "dim must be a non-zero multiple of 64 (rabitq.rs:109)");
+    if (ip && (ip_d == 0 || ip_d > 4095 || ip_dim(ip_d) != dim))
+        return fail(RQ_ERR_DIM_MISMATCH, "inner-product index: dim " + std::to_string(dim) + " is not ceil64(d + 1) for d = " + std::to_string(ip_d));
+    if (ip && !(ip_S >= 0.0f && ip_S <= 3.402823466e+38f)) return fail(RQ_ERR_INVALID, "inner-product index: sq_bound must be finite and >= 0");
     if (!orthogonal || !centroids || !offsets || (n && (!base || !map_ids || !codes || !factors)))
         return fail(RQ_ERR_INVALID, "null array");
     if (n >= 0xFFFFFFFFull) return fail(RQ_ERR_UNSUPPORTED, "n must fit u32");
     std::unique_ptr<rq_index> idx(new rq_index());
     idx->dim = dim, idx->n = n, idx->k = k, idx->W = dim / 64, idx->metric = metric;
+    if (ip) idx->ip_d = ip_d, idx->ip_S = ip_S;
     RQC(idx->P.alloc((size_t)dim * dim));
     RQC(idx->centroids.alloc((size_t)k * dim));
     RQC(idx->offsets.alloc((size_t)k + 1));

@@ -252,7 +252,9 @@ static rq_status index_add(rq_index *idx, const float *rows, uint64_t m, uint32_
     mutate_stats_begin(idx);
     RQC(mutate_refusals(idx));
     if (m && !rows) return fail(RQ_ERR_INVALID, "null rows with m > 0");
-    if (d == 0 || (d + 63) / 64 * 64 != idx->dim)
+    if (idx->metric == RQ_METRIC_IP && d != idx->ip_d)
+        return fail(RQ_ERR_DIM_MISMATCH, "row length " + std::to_string(d) + " is not the inner-product index's row length " + std::to_string(idx->ip_d));
+    if (d == 0 || !raw_len_ok(idx, d))
         return fail(RQ_ERR_DIM_MISMATCH, "row length " + std::to_string(d) + " does not pad to index dim " + std::to_string(idx->dim));
     if (m >= 0xFFFFFFFFull || idx->n + m >= 0xFFFFFFFFull) return fail(RQ_ERR_UNSUPPORTED, "n must fit u32 ids (rabitq.rs:64-65)");
     uint64_t top = 0, hits = 0;
@@ -307,6 +309,19 @@ static rq_status index_add(rq_index *idx, const float *rows, uint64_t m, uint32_
         launch_normalize(d_rows, m, d, idx->dim, normed.p, nullptr);
         HIPC(hipDeviceSynchronize());
         HIPC(hipGetLastError());
+        staged.release();
+        d_rows = normed.p, d = idx->dim;
+    } else if (idx->metric == RQ_METRIC_IP) {  // A(row; the index's S): refused before anything of the index is touched
+        DevBuf<uint32_t> bad;
+        RQC(normed.alloc(m * idx->dim));
+        RQC(bad.alloc(1));
+        HIPC(hipMemset(bad.p, 0xFF, 4));
+        launch_augment(d_rows, m, d, idx->dim, idx->ip_S, nullptr, normed.p, bad.p, nullptr);
+        uint32_t h_bad = 0;
+        HIPC(hipMemcpy(&h_bad, bad.p, 4, hipMemcpyDeviceToHost));
+        HIPC(hipGetLastError());
+        if (h_bad != 0xFFFFFFFFu)
+            return fail(RQ_ERR_INVALID, "row " + std::to_string(h_bad) + " of the batch: its squared norm is not finite or exceeds the index's sq_bound");
         staged.release();
         d_rows = normed.p, d = idx->dim;
     }

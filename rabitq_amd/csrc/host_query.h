@@ -737,7 +737,9 @@ static rq_status validate_call(const rq_index *idx, bool args_null, uint32_t len
     RQC(ensure_device());
     RQC(ensure_kernel_attributes());
     if (!idx || args_null) return fail(RQ_ERR_INVALID, "null argument");
-    if (idx->dim != (len + 63) / 64 * 64)  // rabitq.rs:275
+    if (idx->metric == RQ_METRIC_IP && len != idx->ip_d)
+        return fail(RQ_ERR_DIM_MISMATCH, "query length " + std::to_string(len) + " is not the inner-product index's row length " + std::to_string(idx->ip_d));
+    if (!raw_len_ok(idx, len))  // rabitq.rs:275
         return fail(RQ_ERR_DIM_MISMATCH, "query length " + std::to_string(len) + " does not pad to index dim " +
                                              std::to_string(idx->dim));
     if (probe == 0 || idx->k == 0) return fail(RQ_ERR_INVALID, "probe == 0 (the reference panics at rabitq.rs:295)");

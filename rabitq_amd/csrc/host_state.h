@@ -250,6 +250,10 @@ struct rq_index {
     uint32_t min_list_len = 0;  // 0 if some list is empty (then no slot bound can be derived from stream positions)
     uint64_t n = 0;
     uint32_t metric = RQ_METRIC_L2;  // RQ_METRIC_COSINE: raw rows were normalised on their way in, raw queries are on theirs
+    // RQ_METRIC_IP: rows of ip_d floats were augmented (A(x; ip_S), slot ip_d = sqrtf(ip_S - |x|^2)) on their way in, dim =
+    // ceil64(ip_d + 1); queries have exactly ip_d floats and are zero-padded to dim by the ordinary pad path
+    uint32_t ip_d = 0;
+    float ip_S = 0.0f;
     // raw vectors (cluster order, un-rotated).  Untiered (n_dev == n, the usual case): row p at base + p*dim.  Tiered
     // (they do not fit the HBM budget): per list the first h_c members in HBM, the tail in pinned host memory mapped
     // into the device address space (BaseView / ListTier); n_dev = sum of h_c.
@@ -603,6 +607,59 @@ static void launch_normalize(const float *in, uint64_t n, uint32_t d, uint32_t d
     }
 #undef RQ_NORM
 }
+
+// Inner-product metric.  metric_known stays the test of the *_metric entries (they take no d / S: RQ_METRIC_IP has the _ip entries).
+static uint32_t ip_dim(uint32_t d) { return (d + 1 + 63) / 64 * 64; }
+// the length a raw query or a raw added row of this index must have
+static bool raw_len_ok(const rq_index *idx, uint32_t len) {
+    return idx->metric == RQ_METRIC_IP ? len == idx->ip_d : (len != 0 && idx->dim == (len + 63) / 64 * 64);
+}
+static std::string metric_refusal(uint32_t metric) {
+    return "unknown metric " + std::to_string(metric) + (metric == RQ_METRIC_IP ? ": the inner-product metric takes a row length and a norm bound, use the _ip entries" : "");
+}
+struct SqnormLaunch {
+    uint32_t vec, rw, grid;
+    size_t lds;
+    SqnormLaunch(const float *in, const float *out, uint64_t n, uint32_t d, uint32_t dim) {
+        vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+        rw = dim <= 512 ? 8 : dim <= 1024 ? 4 : dim <= 2048 ? 2 : 1;
+        lds = ((size_t)rw * (dim + 8) + rw) * sizeof(float);
+        grid = (uint32_t)std::min<uint64_t>(ceil_div(n, rw), 256u * 10u * 8u);  // as launch_normalize
+    }
+};
+// A(x; S) of n rows of d floats (augment_rows_kernel): dense into `out`, or (place) to position place[i0 + r] of `view`.
+// s_pre (nullable): s of row r at s_pre[i0 + r].  bad_row: one device word, preset to 0xFFFFFFFF by the caller.
+static void launch_augment(const float *in, uint64_t n, uint32_t d, uint32_t dim, float sq_bound, const float *s_pre, float *out,
+                           uint32_t *bad_row, hipStream_t st, const uint32_t *place = nullptr, uint64_t i0 = 0,
+                           const BaseView view = BaseView{}) {
+    if (n == 0) return;
+    const SqnormLaunch L(in, out, n, d, dim);
+#define RQ_AUG(RW) \
+    do { \
+        if (place) augment_rows_kernel<RW, true><<<L.grid, 64, L.lds, st>>>(in, n, d, dim, L.vec, sq_bound, s_pre, nullptr, place, i0, view, bad_row); \
+        else augment_rows_kernel<RW, false><<<L.grid, 64, L.lds, st>>>(in, n, d, dim, L.vec, sq_bound, s_pre, out, nullptr, i0, view, bad_row); \
+    } while (0)
+    switch (L.rw) {
+        case 8: RQ_AUG(8); break;
+        case 4: RQ_AUG(4); break;
+        case 2: RQ_AUG(2); break;
+        default: RQ_AUG(1); break;
+    }
+#undef RQ_AUG
+}
+// s of n rows (row_sqnorm_kernel); stat: three device words preset to {0, 0xFFFFFFFF, 0}; rows are numbered from i0 in stat[1]
+static void launch_row_sqnorm(const float *in, uint64_t n, uint32_t d, uint32_t dim, float sq_bound, uint64_t i0, float *out_s,
+                              uint32_t *stat, hipStream_t st) {
+    if (n == 0) return;
+    const SqnormLaunch L(in, nullptr, n, d, dim);
+    switch (L.rw) {
+        case 8: row_sqnorm_kernel<8><<<L.grid, 64, L.lds, st>>>(in, n, d, dim, L.vec, sq_bound, i0, out_s, stat); break;
+        case 4: row_sqnorm_kernel<4><<<L.grid, 64, L.lds, st>>>(in, n, d, dim, L.vec, sq_bound, i0, out_s, stat); break;
+        case 2: row_sqnorm_kernel<2><<<L.grid, 64, L.lds, st>>>(in, n, d, dim, L.vec, sq_bound, i0, out_s, stat); break;
+        default: row_sqnorm_kernel<1><<<L.grid, 64, L.lds, st>>>(in, n, d, dim, L.vec, sq_bound, i0, out_s, stat); break;
+    }
+}
+static const uint32_t RQ_SQNORM_STAT_INIT[3] = {0u, 0xFFFFFFFFu, 0u};
 
 // ------------------------------------------------------------------------------------------------
 // scan dispatch on W = dim / 64

@@ -466,6 +466,55 @@ __global__ __launch_bounds__(256) void place_rows_kernel(const float *__restrict
 // dynamic LDS: (RW * (dim + 8) + RW) floats.
 // ------------------------------------------------------------------------------------------------
 #define RQ_NORM_NV 16
+// The pieces normalize_rows_kernel shares with the inner-product kernels below (augment_rows_kernel, row_sqnorm_kernel).  They
+// are macros, not inline functions: behind a function boundary the compiler schedules normalize_rows_kernel differently
+// (every one of the three, tried alone, changed its ISA), and a macro expands to the statements the kernel had, token for
+// token.  They use the kernels' common locals: nrm_lds, S, np, LPR, g, rr, cr, cl, d, dim, vec.
+// RQ_SQCHAIN_STAGE: a lane's share of one row (piece p = g + i * LPR, zero beyond d and for a row that is not LIVE) into V[],
+// and, with TO_LDS, a copy to the row's LDS image.
+#define RQ_SQCHAIN_STAGE(SRC, LIVE, TO_LDS, V) \
+    _Pragma("unroll") for (int i = 0; i < RQ_NORM_NV; ++i) { \
+        const uint32_t p = g + i * LPR, e = 4 * p; \
+        V[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); \
+        if (p < np) { \
+            if (LIVE) { \
+                if (vec) { /* (d is a multiple of 4: a piece is inside the row or all padding) */ \
+                    if (e < d) V[i] = *reinterpret_cast<const float4 *>(SRC + e); \
+                } else { \
+                    V[i].x = e < d ? SRC[e] : 0.0f, V[i].y = e + 1 < d ? SRC[e + 1] : 0.0f; \
+                    V[i].z = e + 2 < d ? SRC[e + 2] : 0.0f, V[i].w = e + 3 < d ? SRC[e + 3] : 0.0f; \
+                } \
+            } \
+            if (TO_LDS) *reinterpret_cast<float4 *>(nrm_lds + rr * S + e) = V[i]; \
+        } \
+    }
+// RQ_SQCHAIN_SUM: ACC (a float preset to 0) becomes this lane's chain of s = vector_dot_product(x, x) over the staged rows;
+// reduce8_lanes(ACC) is then the s of row cr on lanes 8 * cr .. 8 * cr + 7 (cr < RW).
+#define RQ_SQCHAIN_SUM(ACC) \
+    if (cr < RW) { \
+        const float *xr = nrm_lds + cr * S + cl; \
+        for (uint32_t c = 0; c < dim; c += 64) { /* eight chunks' reads in flight ahead of their FMAs */ \
+            float t[8]; \
+            _Pragma("unroll") for (int u = 0; u < 8; ++u) t[u] = xr[c + 8 * u]; \
+            _Pragma("unroll") for (int u = 0; u < 8; ++u) ACC = fmaf(t[u], t[u], ACC); \
+        } \
+    }
+// RQ_ROW_STORE_PIECE: elements e .. e + 3 (the float4 O) of a row to DST, a RowRef: dense, or the row's final tier and format.
+#define RQ_ROW_STORE_PIECE(DST, O) \
+    float *w = const_cast<float *>(DST.p); \
+    if (PLACE && DST.split) { /* split rows (common.h): two elements per 32-bit word of each plane */ \
+        const uint32_t b0 = __builtin_bit_cast(uint32_t, O.x), b1 = __builtin_bit_cast(uint32_t, O.y); \
+        const uint32_t b2 = __builtin_bit_cast(uint32_t, O.z), b3 = __builtin_bit_cast(uint32_t, O.w); \
+        uint32_t *hp = reinterpret_cast<uint32_t *>(w), *lp = hp + dim / 2; \
+        *reinterpret_cast<uint2 *>(hp + e / 2) = make_uint2(((b0 + 0x8000u) >> 16) | ((b1 + 0x8000u) & 0xFFFF0000u), \
+                                                            ((b2 + 0x8000u) >> 16) | ((b3 + 0x8000u) & 0xFFFF0000u)); \
+        *reinterpret_cast<uint2 *>(lp + e / 2) = make_uint2((b0 & 0xFFFFu) | (b1 << 16), (b2 & 0xFFFFu) | (b3 << 16)); \
+    } else if (PLACE || vec) { /* (index rows are 4 * dim bytes apart from a hipMalloc / hipHostMalloc base: aligned) */ \
+        *reinterpret_cast<float4 *>(w + e) = O; \
+    } else { \
+        w[e] = O.x, w[e + 1] = O.y, w[e + 2] = O.z, w[e + 3] = O.w; \
+    }
+
 template <int RW, bool PLACE>
 __global__ __launch_bounds__(64) void normalize_rows_kernel(const float *__restrict__ in, uint64_t n, uint32_t d, uint32_t dim,
                                                             uint32_t vec /* 16-byte loads and stores are aligned */,
@@ -482,34 +531,10 @@ __global__ __launch_bounds__(64) void normalize_rows_kernel(const float *__restr
         const bool live = r < n;
         const float *src = in + r * d;
         float4 v[RQ_NORM_NV];
-#pragma unroll
-        for (int i = 0; i < RQ_NORM_NV; ++i) {
-            const uint32_t p = g + i * LPR, e = 4 * p;
-            v[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (p < np) {
-                if (live) {
-                    if (vec) {  // (d is a multiple of 4: a piece is inside the row or all padding)
-                        if (e < d) v[i] = *reinterpret_cast<const float4 *>(src + e);
-                    } else {
-                        v[i].x = e < d ? src[e] : 0.0f, v[i].y = e + 1 < d ? src[e + 1] : 0.0f;
-                        v[i].z = e + 2 < d ? src[e + 2] : 0.0f, v[i].w = e + 3 < d ? src[e + 3] : 0.0f;
-                    }
-                }
-                *reinterpret_cast<float4 *>(nrm_lds + rr * S + e) = v[i];
-            }
-        }
+        RQ_SQCHAIN_STAGE(src, live, true, v)
         __syncthreads();
         float acc = 0.0f;
-        if (cr < RW) {
-            const float *xr = nrm_lds + cr * S + cl;
-            for (uint32_t c = 0; c < dim; c += 64) {  // eight chunks' reads in flight ahead of their FMAs
-                float t[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) t[u] = xr[c + 8 * u];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) acc = fmaf(t[u], t[u], acc);
-            }
-        }
+        RQ_SQCHAIN_SUM(acc)
         const float s = reduce8_lanes(acc);
         if (cr < RW && cl == 0) {
             const float nrm = sqrtf(s);
@@ -527,21 +552,132 @@ __global__ __launch_bounds__(64) void normalize_rows_kernel(const float *__restr
             if (p >= np) continue;
             float4 o = v[i];
             if (nrm != 0.0f) o.x = o.x / nrm, o.y = o.y / nrm, o.z = o.z / nrm, o.w = o.w / nrm;
-            float *w = const_cast<float *>(dst.p);
-            if (PLACE && dst.split) {  // split rows (common.h): two elements per 32-bit word of each plane
-                const uint32_t b0 = __builtin_bit_cast(uint32_t, o.x), b1 = __builtin_bit_cast(uint32_t, o.y);
-                const uint32_t b2 = __builtin_bit_cast(uint32_t, o.z), b3 = __builtin_bit_cast(uint32_t, o.w);
-                uint32_t *hp = reinterpret_cast<uint32_t *>(w), *lp = hp + dim / 2;
-                *reinterpret_cast<uint2 *>(hp + e / 2) = make_uint2(((b0 + 0x8000u) >> 16) | ((b1 + 0x8000u) & 0xFFFF0000u),
-                                                                    ((b2 + 0x8000u) >> 16) | ((b3 + 0x8000u) & 0xFFFF0000u));
-                *reinterpret_cast<uint2 *>(lp + e / 2) = make_uint2((b0 & 0xFFFFu) | (b1 << 16), (b2 & 0xFFFFu) | (b3 << 16));
-            } else if (PLACE || vec) {  // (index rows are 4 * dim bytes apart from a hipMalloc / hipHostMalloc base: aligned)
-                *reinterpret_cast<float4 *>(w + e) = o;
-            } else {
-                w[e] = o.x, w[e + 1] = o.y, w[e + 2] = o.z, w[e + 3] = o.w;
-            }
+            RQ_ROW_STORE_PIECE(dst, o)
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Inner-product metric (RQ_METRIC_IP): A(x; S) of the zero-padded row, dim = ceil64(d + 1).
+//   s = vector_dot_product(x, x), the chain above;  A(x)_i = x_i bit for bit (i < d);  A(x)_d = sqrtf(S - s);  the rest 0
+//   a row is valid iff s is finite and s <= S; the smallest index of an invalid row goes to *bad_row by atomicMin (preset to
+//   0xFFFFFFFF; the host reads it where it synchronises anyway)
+// The twin of normalize_rows_kernel: the same split of the wave, the same LDS trip (row stride dim + 8 floats: the rows of one
+// chain read sit 8 banks apart), the row held in registers and written once, densely or to its final tier and row format, so
+// that both passes of a streamed build store the same bits.  s_pre (nullable): the row's s, already computed by
+// row_sqnorm_kernel (the one-shot builds, which need the largest s before the first row can be written): the LDS trip and the
+// chains are skipped, the kernel is one read and one write of the row.
+// dynamic LDS: (RW * (dim + 8) + RW) floats.
+// ------------------------------------------------------------------------------------------------
+template <int RW, bool PLACE>
+__global__ __launch_bounds__(64) void augment_rows_kernel(const float *__restrict__ in, uint64_t n, uint32_t d, uint32_t dim,
+                                                          uint32_t vec, float sq_bound, const float *__restrict__ s_pre,
+                                                          float *__restrict__ out, const uint32_t *__restrict__ pos_of_id,
+                                                          uint64_t i0, const BaseView view, uint32_t *__restrict__ bad_row) {
+    extern __shared__ __attribute__((aligned(16))) float nrm_lds[];
+    constexpr uint32_t LPR = 64 / RW;
+    const uint32_t lane = threadIdx.x, rr = lane / LPR, g = lane % LPR;
+    const uint32_t S = dim + 8, np = dim / 4;
+    float *slot = nrm_lds + RW * S;
+    const uint32_t cr = lane >> 3, cl = lane & 7;
+    const bool chain = s_pre == nullptr;
+    for (uint64_t r0 = (uint64_t)blockIdx.x * RW; r0 < n; r0 += (uint64_t)gridDim.x * RW) {
+        const uint64_t r = r0 + rr;
+        const bool live = r < n;
+        const float *src = in + r * d;
+        float4 v[RQ_NORM_NV];
+        RQ_SQCHAIN_STAGE(src, live, chain, v)
+        __syncthreads();
+        float s = 0.0f;
+        if (chain) {
+            RQ_SQCHAIN_SUM(s)
+            s = reduce8_lanes(s);
+        }
+        if (cr < RW && cl == 0 && r0 + cr < n) {
+            if (!chain) s = s_pre[i0 + r0 + cr];
+            if (!(s <= sq_bound)) atomicMin(bad_row, (uint32_t)(i0 + r0 + cr));  // (sq_bound is finite: also s = inf, s = NaN)
+            slot[cr] = sqrtf(sq_bound - s);
+        }
+        __syncthreads();
+        const float extra = slot[rr];
+        if (!live) continue;
+        RowRef dst{out + r * dim, false};
+        if (PLACE) dst = view.row(pos_of_id[i0 + r], dim);
+#pragma unroll
+        for (int i = 0; i < RQ_NORM_NV; ++i) {
+            const uint32_t p = g + i * LPR, e = 4 * p;
+            if (p >= np) continue;
+            float4 o = v[i];
+            if (d - e < 4u) {  // e <= d < e + 4: the piece that holds slot d
+                const uint32_t c = d - e;
+                o.x = c == 0 ? extra : o.x, o.y = c == 1 ? extra : o.y, o.z = c == 2 ? extra : o.z, o.w = c == 3 ? extra : o.w;
+            }
+            RQ_ROW_STORE_PIECE(dst, o)
+        }
+    }
+}
+
+// s of every row (out_s, nullable), and over all rows: stat[0] = atomicMax of the bit patterns of the finite s (s >= 0, so the
+// patterns order as the values do; preset 0), stat[1] = atomicMin of the indices of rows whose s is not finite or exceeds
+// sq_bound (preset 0xFFFFFFFF; pass +inf for no bound), stat[2] = 1 if some s is inf or NaN.  One atomic per block and word.
+// Also the s_q of the two conversions (rows = queries, d = their length).  The chain and its launch shape are the twin's.
+template <int RW>
+__global__ __launch_bounds__(64) void row_sqnorm_kernel(const float *__restrict__ in, uint64_t n, uint32_t d, uint32_t dim,
+                                                        uint32_t vec, float sq_bound, uint64_t i0, float *__restrict__ out_s,
+                                                        uint32_t *__restrict__ stat) {
+    extern __shared__ __attribute__((aligned(16))) float nrm_lds[];
+    constexpr uint32_t LPR = 64 / RW;
+    const uint32_t lane = threadIdx.x, rr = lane / LPR, g = lane % LPR;
+    const uint32_t S = dim + 8, np = dim / 4;
+    const uint32_t cr = lane >> 3, cl = lane & 7;
+    uint32_t mx = 0, bad = 0xFFFFFFFFu, nonfinite = 0;
+    for (uint64_t r0 = (uint64_t)blockIdx.x * RW; r0 < n; r0 += (uint64_t)gridDim.x * RW) {
+        const uint64_t r = r0 + rr;
+        const float *src = in + r * d;
+        const bool live = r < n;
+        float4 v[RQ_NORM_NV];
+        RQ_SQCHAIN_STAGE(src, live, true, v)
+        __syncthreads();
+        float acc = 0.0f;
+        RQ_SQCHAIN_SUM(acc)
+        const float s = reduce8_lanes(acc);
+        if (cr < RW && cl == 0 && r0 + cr < n) {
+            if (out_s) out_s[r0 + cr] = s;
+            const bool finite = s <= 3.402823466e+38f;  // (s >= 0 or NaN)
+            if (finite) mx = max(mx, __builtin_bit_cast(uint32_t, s));
+            else nonfinite = 1;
+            if (!finite || !(s <= sq_bound)) bad = min(bad, (uint32_t)(i0 + r0 + cr));
+        }
+        __syncthreads();  // (the next round's staging overwrites the rows the chains read)
+    }
+    for (int o = 32; o; o >>= 1) {
+        mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+        bad = min(bad, (uint32_t)__shfl_xor((int)bad, o));
+        nonfinite |= (uint32_t)__shfl_xor((int)nonfinite, o);
+    }
+    if (lane == 0) {
+        if (mx) atomicMax(stat, mx);
+        if (bad != 0xFFFFFFFFu) atomicMin(stat + 1, bad);
+        if (nonfinite) atomicMax(stat + 2, 1u);
+    }
+}
+
+// The two conversions of an inner-product index, in f32 as the contract states them (no contraction: -ffp-contract=off).
+//   ip = 0.5f * ((S + s_q) - D) for the first n[q] (all topk if n is null) slots of query q; the other slots get -inf
+__global__ __launch_bounds__(256) void ip_from_dist_kernel(const float *__restrict__ dist, const float *__restrict__ s_q,
+                                                           const uint32_t *__restrict__ n, float sq_bound, uint32_t nq,
+                                                           uint32_t topk, float *__restrict__ out_ip) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < (uint64_t)nq * topk; i += (uint64_t)gridDim.x * 256) {
+        const uint32_t q = (uint32_t)(i / topk), j = (uint32_t)(i % topk);
+        const float c = sq_bound + s_q[q];
+        out_ip[i] = (!n || j < n[q]) ? 0.5f * (c - dist[i]) : -__builtin_inff();
+    }
+}
+//   radius = (S + s_q) - 2.0f * min_ip
+__global__ __launch_bounds__(256) void ip_radius_kernel(const float *__restrict__ min_ip, const float *__restrict__ s_q,
+                                                        float sq_bound, uint32_t nq, float *__restrict__ out_radius) {
+    const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+    if (q < nq) out_radius[q] = (sq_bound + s_q[q]) - 2.0f * min_ip[q];
 }
 
 // out[0] = longest list, out[1] = shortest list (0 if any list is empty); out preset to {0, 0xFFFFFFFF}

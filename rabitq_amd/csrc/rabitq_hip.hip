@@ -131,7 +131,152 @@ rq_status rq_normalize(const float *x, uint64_t n, uint32_t d, float *out) {
 
 rq_status rq_build_device_metric(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
                                  const float *orthogonal_host, uint64_t seed, uint32_t metric, rq_index **out) {
+    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, metric_refusal(metric));
     return build_device(d_base, n, d, d_centroids, k, orthogonal_host, seed, metric, out);
+}
+
+// ---- inner-product metric: the builds, A(x; S), the largest s and the two conversions ----
+rq_status rq_build_device_ip(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
+                             const float *orthogonal_host, uint64_t seed, uint32_t centroid_cols, float sq_bound, rq_index **out) {
+    return build_device_ip(d_base, n, d, d_centroids, k, orthogonal_host, seed, centroid_cols, sq_bound, out);
+}
+rq_status rq_build_ip(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k, const float *orthogonal,
+                      uint64_t seed, uint32_t centroid_cols, float sq_bound, rq_index **out) {
+    RQC(ensure_device());
+    if (out) *out = nullptr;
+    if ((n && !base) || !centroids) return fail(RQ_ERR_INVALID, "null argument");
+    if (d == 0 || d > 4095) return fail(d ? RQ_ERR_UNSUPPORTED : RQ_ERR_INVALID, "d must be in [1, 4095]");
+    if (centroid_cols < d || centroid_cols > ip_dim(d)) return fail(RQ_ERR_INVALID, "centroid_cols outside [d, ceil64(d + 1)]");
+    DevBuf<float> db, dc;
+    RQC(db.alloc(n * d));
+    RQC(dc.alloc((size_t)k * centroid_cols));
+    if (n) HIPC(hipMemcpy(db.p, base, n * d * 4, hipMemcpyHostToDevice));
+    if (k) HIPC(hipMemcpy(dc.p, centroids, (size_t)k * centroid_cols * 4, hipMemcpyHostToDevice));
+    return build_device_ip(db.p, n, d, dc.p, k, orthogonal, seed, centroid_cols, sq_bound, out);
+}
+rq_status rq_build_from_path_ip(const char *base_fvecs, const char *centroid_fvecs, const float *orthogonal, uint64_t seed,
+                                float sq_bound, rq_index **out) {
+    if (!base_fvecs || !centroid_fvecs) return fail(RQ_ERR_INVALID, "null path");
+    VecsFile b, c;
+    RQC(read_vecs_file(base_fvecs, 4, b));
+    RQC(read_vecs_file(centroid_fvecs, 4, c));
+    if (b.lens.empty() || c.lens.empty()) return fail(RQ_ERR_IO, "empty fvecs file");
+    const uint32_t d = b.lens[0], cc = c.lens[0];
+    for (uint32_t l : b.lens)
+        if (l != d) return fail(RQ_ERR_IO, "ragged base.fvecs");
+    for (uint32_t l : c.lens)
+        if (l != cc) return fail(RQ_ERR_IO, "ragged centroids.fvecs");
+    if (d == 0 || d > 4095 || cc < d || cc > ip_dim(d)) return fail(RQ_ERR_DIM_MISMATCH, "centroid records must hold between d and ceil64(d + 1) values");
+    return rq_build_ip(reinterpret_cast<const float *>(b.data.data()), b.lens.size(), d,
+                       reinterpret_cast<const float *>(c.data.data()), (uint32_t)c.lens.size(), orthogonal, seed, cc, sq_bound, out);
+}
+rq_status rq_ip_params(const rq_index *idx, uint32_t *d, float *sq_bound) {
+    if (!idx || !d || !sq_bound) return fail(RQ_ERR_INVALID, "null argument");
+    if (idx->metric != RQ_METRIC_IP) return fail(RQ_ERR_INVALID, "not an inner-product index");
+    *d = idx->ip_d, *sq_bound = idx->ip_S;
+    return RQ_OK;
+}
+rq_status rq_row_sqnorm_max_device(const float *d_x, uint64_t n, uint32_t d, float *out_max) {
+    RQC(ensure_device());
+    if ((n && !d_x) || !out_max) return fail(RQ_ERR_INVALID, "null argument");
+    if (d == 0 || d > 4096) return fail(d ? RQ_ERR_UNSUPPORTED : RQ_ERR_INVALID, "d must be in [1, 4096]");
+    uint32_t bad = 0xFFFFFFFFu;
+    RQC(row_sqnorms(d_x, n, d, (d + 63) / 64 * 64, __builtin_inff(), nullptr, out_max, &bad));
+    if (bad != 0xFFFFFFFFu) return fail(RQ_ERR_INVALID, "row " + std::to_string(bad) + ": its squared norm is not finite");
+    return RQ_OK;
+}
+rq_status rq_row_sqnorm_max(const float *x, uint64_t n, uint32_t d, float *out_max) {
+    RQC(ensure_device());
+    if ((n && !x) || !out_max) return fail(RQ_ERR_INVALID, "null argument");
+    DevBuf<float> dx;
+    RQC(dx.alloc(n * d));
+    if (n && d) HIPC(hipMemcpy(dx.p, x, n * d * 4, hipMemcpyHostToDevice));
+    return rq_row_sqnorm_max_device(dx.p, n, d, out_max);
+}
+rq_status rq_augment_device(const float *d_x, uint64_t n, uint32_t d, float sq_bound, float *d_out) {
+    RQC(ensure_device());
+    if (n && (!d_x || !d_out)) return fail(RQ_ERR_INVALID, "null argument");
+    if (d == 0 || d > 4095) return fail(d ? RQ_ERR_UNSUPPORTED : RQ_ERR_INVALID, "d must be in [1, 4095]");
+    const uint32_t dim = ip_dim(d);
+    DevBuf<float> s;
+    DevBuf<uint32_t> bad;
+    RQC(s.alloc(n));
+    RQC(bad.alloc(1));
+    RQC(ip_resolve_bound(d_x, n, d, &sq_bound, s.p));  // (every row is valid from here on)
+    HIPC(hipMemset(bad.p, 0xFF, 4));
+    for (uint64_t r0 = 0; r0 < n; r0 += RQ_BUILD_CHUNK)
+        launch_augment(d_x + r0 * d, std::min<uint64_t>(RQ_BUILD_CHUNK, n - r0), d, dim, sq_bound, s.p, d_out + r0 * dim, bad.p, nullptr, nullptr, r0);
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipGetLastError());
+    return RQ_OK;
+}
+rq_status rq_augment(const float *x, uint64_t n, uint32_t d, float sq_bound, float *out) {
+    RQC(ensure_device());
+    if (n && (!x || !out)) return fail(RQ_ERR_INVALID, "null argument");
+    if (d == 0 || d > 4095) return fail(d ? RQ_ERR_UNSUPPORTED : RQ_ERR_INVALID, "d must be in [1, 4095]");
+    DevBuf<float> dx, dout;
+    RQC(dx.alloc(n * d));
+    RQC(dout.alloc(n * ip_dim(d)));
+    if (n) HIPC(hipMemcpy(dx.p, x, n * d * 4, hipMemcpyHostToDevice));
+    RQC(rq_augment_device(dx.p, n, d, sq_bound, dout.p));
+    if (n) HIPC(hipMemcpy(out, dout.p, n * ip_dim(d) * 4, hipMemcpyDeviceToHost));
+    return RQ_OK;
+}
+// s_q of the queries of an inner-product index (row_sqnorm_kernel over Q(q)), then one of the two conversions
+static rq_status ip_convert(const rq_index *idx, const float *d_q, uint32_t nq, uint32_t len, const float *d_in, uint32_t topk,
+                            const uint32_t *d_n, float *d_out, bool radius) {
+    RQC(ensure_device());
+    if (!idx || (nq && (!d_q || !d_in || !d_out))) return fail(RQ_ERR_INVALID, "null argument");
+    if (idx->metric != RQ_METRIC_IP) return fail(RQ_ERR_INVALID, "not an inner-product index");
+    if (len != idx->ip_d) return fail(RQ_ERR_DIM_MISMATCH, "query length is not the inner-product index's row length");
+    if (!radius && topk == 0) return fail(RQ_ERR_INVALID, "topk == 0");
+    if (nq == 0) return RQ_OK;
+    DevBuf<float> sq;
+    DevBuf<uint32_t> stat;
+    RQC(sq.alloc(nq));
+    RQC(stat.alloc(3));
+    HIPC(hipMemcpy(stat.p, RQ_SQNORM_STAT_INIT, 12, hipMemcpyHostToDevice));
+    launch_row_sqnorm(d_q, nq, len, idx->dim, __builtin_inff(), 0, sq.p, stat.p, nullptr);
+    if (radius) ip_radius_kernel<<<ceil_div(nq, 256), 256>>>(d_in, sq.p, idx->ip_S, nq, d_out);
+    else ip_from_dist_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div((uint64_t)nq * topk, 256), 1u << 20), 256>>>(d_in, sq.p, d_n, idx->ip_S, nq, topk, d_out);
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipGetLastError());
+    return RQ_OK;
+}
+static rq_status ip_convert_host(const rq_index *idx, const float *q, uint32_t nq, uint32_t len, const float *in, uint32_t topk,
+                                 const uint32_t *n, float *out, bool radius) {
+    RQC(ensure_device());
+    if (!idx || (nq && (!q || !in || !out))) return fail(RQ_ERR_INVALID, "null argument");
+    const uint64_t cells = radius ? nq : (uint64_t)nq * topk;
+    DevBuf<float> dq, din, dout;
+    DevBuf<uint32_t> dn;
+    RQC(dq.alloc((uint64_t)nq * len));
+    RQC(din.alloc(cells));
+    RQC(dout.alloc(cells));
+    if (nq && len) HIPC(hipMemcpy(dq.p, q, (uint64_t)nq * len * 4, hipMemcpyHostToDevice));
+    if (cells) HIPC(hipMemcpy(din.p, in, cells * 4, hipMemcpyHostToDevice));
+    if (n && nq) {
+        RQC(dn.alloc(nq));
+        HIPC(hipMemcpy(dn.p, n, (uint64_t)nq * 4, hipMemcpyHostToDevice));
+    }
+    RQC(ip_convert(idx, dq.p, nq, len, din.p, topk, n ? dn.p : nullptr, dout.p, radius));
+    if (cells) HIPC(hipMemcpy(out, dout.p, cells * 4, hipMemcpyDeviceToHost));
+    return RQ_OK;
+}
+rq_status rq_ip_from_dist_device(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t len, const float *d_dist,
+                                 uint32_t topk, const uint32_t *d_n, float *d_out_ip) {
+    return ip_convert(idx, d_queries, nq, len, d_dist, topk, d_n, d_out_ip, false);
+}
+rq_status rq_ip_from_dist(const rq_index *idx, const float *queries, uint32_t nq, uint32_t len, const float *dist, uint32_t topk,
+                          const uint32_t *n, float *out_ip) {
+    return ip_convert_host(idx, queries, nq, len, dist, topk, n, out_ip, false);
+}
+rq_status rq_ip_radius_device(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t len, const float *d_min_ip,
+                              float *d_out_radius) {
+    return ip_convert(idx, d_queries, nq, len, d_min_ip, 1, nullptr, d_out_radius, true);
+}
+rq_status rq_ip_radius(const rq_index *idx, const float *queries, uint32_t nq, uint32_t len, const float *min_ip, float *out_radius) {
+    return ip_convert_host(idx, queries, nq, len, min_ip, 1, nullptr, out_radius, true);
 }
 rq_status rq_build_device(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
                           const float *orthogonal_host, uint64_t seed, rq_index **out) {
@@ -140,7 +285,13 @@ rq_status rq_build_device(const float *d_base, uint64_t n, uint32_t d, const flo
 
 rq_status rq_builder_create_metric(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
                                    uint64_t seed, uint64_t max_device_base_bytes, uint32_t metric, rq_builder **out) {
+    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, metric_refusal(metric));
     return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, metric, out);
+}
+rq_status rq_builder_create_ip(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
+                               uint64_t seed, uint64_t max_device_base_bytes, uint32_t centroid_cols, float sq_bound,
+                               rq_builder **out) {
+    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, RQ_METRIC_IP, out, centroid_cols, sq_bound);
 }
 rq_status rq_builder_create(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
                             uint64_t seed, uint64_t max_device_base_bytes, rq_builder **out) {
@@ -160,7 +311,7 @@ rq_status rq_build_metric(const float *base, uint64_t n, uint32_t d, const float
                           const float *orthogonal, uint64_t seed, uint32_t metric, rq_index **out) {
     RQC(ensure_device());
     if ((n && !base) || !centroids) return fail(RQ_ERR_INVALID, "null argument");
-    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, "unknown metric " + std::to_string(metric));
+    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, metric_refusal(metric));
     DevBuf<float> db, dc;
     RQC(db.alloc(n * d));
     RQC(dc.alloc((size_t)k * d));
@@ -176,7 +327,7 @@ rq_status rq_build(const float *base, uint64_t n, uint32_t d, const float *centr
 rq_status rq_build_from_path_metric(const char *base_fvecs, const char *centroid_fvecs, const float *orthogonal,
                                     uint64_t seed, uint32_t metric, rq_index **out) {
     if (!base_fvecs || !centroid_fvecs) return fail(RQ_ERR_INVALID, "null path");
-    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, "unknown metric " + std::to_string(metric));
+    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, metric_refusal(metric));
     VecsFile b, c;
     RQC(read_vecs_file(base_fvecs, 4, b));      // rabitq.rs:160
     RQC(read_vecs_file(centroid_fvecs, 4, c));  // :163
@@ -203,7 +354,13 @@ rq_status rq_from_arrays(uint32_t dim, uint64_t n, uint32_t k, const float *base
 rq_status rq_from_arrays_metric(uint32_t dim, uint64_t n, uint32_t k, const float *base, const float *orthogonal,
                                 const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
                                 const uint64_t *codes, const rq_factor_t *factors, uint32_t metric, rq_index **out) {
+    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, metric_refusal(metric));
     return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, metric, out);
+}
+rq_status rq_from_arrays_ip(uint32_t dim, uint64_t n, uint32_t k, const float *base, const float *orthogonal,
+                            const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
+                            const uint64_t *codes, const rq_factor_t *factors, uint32_t d, float sq_bound, rq_index **out) {
+    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, RQ_METRIC_IP, out, d, sq_bound);
 }
 
 // rabitq.rs:84-125
@@ -217,16 +374,28 @@ rq_status rq_load_dir(const char *dir, rq_index **out) {
     RQC(read_vecs_file(d + "/factors.fvecs", 4, fac));
     RQC(read_vecs_file(d + "/x_binary_vec.u64vecs", 8, bin));
     RQC(read_vecs_file(d + "/base.fvecs", 4, base));
-    uint32_t metric = RQ_METRIC_L2;  // the sixth file of a cosine index's dump
+    uint32_t metric = RQ_METRIC_L2, ip_d = 0;  // the sixth file of a cosine or inner-product index's dump
+    float ip_S = 0.0f;
     if (FILE *mf = fopen((d + "/metric").c_str(), "rb")) {
         char buf[32] = {0};
         const size_t got = fread(buf, 1, sizeof buf - 1, mf);
         fclose(mf);
-        if (std::string(buf, got) == "cosine\n") metric = RQ_METRIC_COSINE;
-        else if (std::string(buf, got) != "l2\n") return fail(RQ_ERR_IO, "metric: unknown content in " + d + "/metric");
+        const std::string text(buf, got);
+        if (text == "cosine\n") metric = RQ_METRIC_COSINE;
+        else if (text.compare(0, 3, "ip ") == 0) {  // "ip <d> <S as 8 hex digits>\n", exactly as rq_dump_dir writes it
+            unsigned pd = 0, bits = 0;
+            char canon[32];
+            if (sscanf(text.c_str(), "ip %u %8x", &pd, &bits) != 2) return fail(RQ_ERR_IO, "metric: malformed content in " + d + "/metric");
+            snprintf(canon, sizeof canon, "ip %u %08x\n", pd, bits);
+            if (text != canon) return fail(RQ_ERR_IO, "metric: malformed content in " + d + "/metric");
+            metric = RQ_METRIC_IP, ip_d = pd;
+            memcpy(&ip_S, &bits, 4);
+            if (ip_d == 0 || ip_d > 4095 || !(ip_S >= 0.0f && ip_S <= 3.402823466e+38f)) return fail(RQ_ERR_IO, "metric: malformed content in " + d + "/metric");
+        } else if (text != "l2\n") return fail(RQ_ERR_IO, "metric: unknown content in " + d + "/metric");
     }
     const uint32_t dim = (uint32_t)ortho.lens.size();  // :108 dim = orthogonal.nrows()
     if (dim == 0 || dim % 64 != 0) return fail(RQ_ERR_DIM_MISMATCH, "orthogonal.fvecs: dim % 64 != 0 (rabitq.rs:109)");
+    if (metric == RQ_METRIC_IP && ip_dim(ip_d) != dim) return fail(RQ_ERR_IO, "metric: d does not belong to the index's dim in " + d + "/metric");
     if (cent.lens.size() != dim || oi.lens.size() != 2) return fail(RQ_ERR_IO, "malformed index directory");
     const uint32_t k = cent.lens[0];
     // every record length is checked before anything is indexed by it (the reference's matrix_from_fvecs panics on
@@ -257,7 +426,7 @@ rq_status rq_load_dir(const char *dir, rq_index **out) {
     return from_arrays(dim, n, k, reinterpret_cast<const float *>(base.data.data()),
                        reinterpret_cast<const float *>(ortho.data.data()), c.data(), oip, oip + (total - last),
                        reinterpret_cast<const uint64_t *>(bin.data.data()),
-                       reinterpret_cast<const rq_factor_t *>(fac.data.data()), metric, out);
+                       reinterpret_cast<const rq_factor_t *>(fac.data.data()), metric, out, ip_d, ip_S);
 }
 
 rq_status rq_get_array(const rq_index *idx, int which, void *dst, uint64_t dst_bytes);
@@ -331,9 +500,11 @@ rq_status rq_dump_dir(const rq_index *idx, const char *dir) {
     s = write_record(f, codes.data(), (uint32_t)(n * (dim / 64)), 8, "x_binary_vec.u64vecs");
     fclose(f);
     RQC(s);
-    if (idx->metric == RQ_METRIC_COSINE) {  // (an L2 dump stays the crate's five files)
+    if (idx->metric != RQ_METRIC_L2) {  // (an L2 dump stays the crate's five files)
         RQC(open("metric", &f));
-        const bool ok = fputs("cosine\n", f) >= 0;
+        char text[32] = "cosine\n";
+        if (idx->metric == RQ_METRIC_IP) snprintf(text, sizeof text, "ip %u %08x\n", idx->ip_d, __builtin_bit_cast(uint32_t, idx->ip_S));
+        const bool ok = fputs(text, f) >= 0;
         if (fclose(f) != 0 || !ok) return fail(RQ_ERR_IO, "write error on " + d + "/metric");
     } else {
         remove((d + "/metric").c_str());  // (a directory that held a cosine dump before)
@@ -386,6 +557,11 @@ rq_status rq_dump_json(const rq_index *idx, const char *path) {
         o.raw(",\"center_distance_square\":"), o.f32(fac[4 * i + 3]), o.raw("}");
     }
     o.raw("]");
+    if (idx->metric == RQ_METRIC_IP) {
+        const std::string m = ",\"metric\":\"ip\",\"ip_d\":" + std::to_string(idx->ip_d) + ",\"ip_sq_bound_bits\":" +
+                              std::to_string(__builtin_bit_cast(uint32_t, idx->ip_S));
+        o.raw(m.c_str());
+    }
     if (idx->metric == RQ_METRIC_COSINE) o.raw(",\"metric\":\"cosine\"");  // (an unknown member to the reference's serde derive: ignored)
     o.raw("}");
     const bool closed = fclose(f) == 0;
@@ -411,6 +587,7 @@ rq_status rq_load_json(const char *path, rq_index **out) {
     std::vector<unsigned long long> off, ids, codes;
     std::vector<rq_factor_t> fac;
     std::string metric_name;
+    unsigned long long ip_d = 0, ip_bits = 1ull << 32;  // members of an inner-product index (the preset: absent)
     bool good = in.need('{');
     if (good && !in.lit('}')) {
         do {
@@ -443,19 +620,29 @@ rq_status rq_load_json(const char *path, rq_index **out) {
                 const char *v0 = in.p;
                 good = in.skip();
                 if (good) metric_name.assign(v0, in.p);
-            } else good = in.skip();
+            } else if (k == "ip_d") good = in.num_u64(ip_d);
+            else if (k == "ip_sq_bound_bits") good = in.num_u64(ip_bits);
+            else good = in.skip();
         } while (good && in.lit(','));
         good = good && in.need('}');
     }
     if (!good) return fail(RQ_ERR_IO, std::string("deserialize error in ") + path + (in.err.empty() ? "" : ": " + in.err));
     uint32_t metric = RQ_METRIC_L2;
+    float ip_S = 0.0f;
     if (metric_name == "\"cosine\"") metric = RQ_METRIC_COSINE;
-    else if (!metric_name.empty() && metric_name != "\"l2\"") return fail(RQ_ERR_IO, std::string("unknown metric ") + metric_name + " in " + path);
+    else if (metric_name == "\"ip\"") {
+        const uint32_t bits = (uint32_t)ip_bits;
+        memcpy(&ip_S, &bits, 4);
+        if (ip_d == 0 || ip_d > 4095 || ip_bits >> 32 || !(ip_S >= 0.0f && ip_S <= 3.402823466e+38f))
+            return fail(RQ_ERR_IO, std::string("inner-product index without a valid ip_d / ip_sq_bound_bits in ") + path);
+        metric = RQ_METRIC_IP;
+    } else if (!metric_name.empty() && metric_name != "\"l2\"") return fail(RQ_ERR_IO, std::string("unknown metric ") + metric_name + " in " + path);
     const uint64_t n = ids.size(), k = off.empty() ? 0 : off.size() - 1;
     if (dim == 0 || dim % 64 || pr != dim || pc != dim || P.size() != dim * dim || br != dim || bc != n || base.size() != dim * n ||
         cr != dim || cc != k || cent.size() != dim * k || off.empty() || fac.size() != n || codes.size() != n * (dim / 64) ||
         off.back() != n)
         return fail(RQ_ERR_IO, std::string("inconsistent index in ") + path);
+    if (metric == RQ_METRIC_IP && ip_dim((uint32_t)ip_d) != dim) return fail(RQ_ERR_IO, std::string("ip_d does not belong to dim in ") + path);
     for (uint64_t j = 0; j + 1 < off.size(); ++j)
         if (off[j] > off[j + 1]) return fail(RQ_ERR_IO, "offsets are not non-decreasing");
     // Mat (dim x cols, row-major sequence) -> one vector per row
@@ -467,7 +654,7 @@ rq_status rq_load_json(const char *path, rq_index **out) {
     std::vector<uint32_t> off32(off.begin(), off.end()), ids32(ids.begin(), ids.end());
     std::vector<uint64_t> codes64(codes.begin(), codes.end());
     return from_arrays((uint32_t)dim, n, (uint32_t)k, base_rows.data(), P.data(), cent_rows.data(), off32.data(), ids32.data(),
-                       codes64.data(), fac.data(), metric, out);
+                       codes64.data(), fac.data(), metric, out, (uint32_t)ip_d, ip_S);
 }
 
 void rq_free(rq_index *idx) { delete idx; }
@@ -519,7 +706,7 @@ rq_status rq_coarse_topk_device(const rq_index *idx, const float *d_queries, uin
                                 float *d_out_dist) {
     RQC(ensure_device());
     if (!idx || !d_queries || !d_out_cluster || !d_out_dist) return fail(RQ_ERR_INVALID, "null argument");
-    if (idx->dim != (len + 63) / 64 * 64) return fail(RQ_ERR_DIM_MISMATCH, "query length does not pad to dim");
+    if (!raw_len_ok(idx, len)) return fail(RQ_ERR_DIM_MISMATCH, "query length does not pad to dim (an inner-product index: is not its row length)");
     if (probe == 0 || list_lo >= list_hi || list_hi > idx->k) return fail(RQ_ERR_INVALID, "bad list range / probe");
     if (probe > RQ_MAX_PROBE) return fail(RQ_ERR_UNSUPPORTED, "probe > 16384");
     if (nq == 0) return RQ_OK;
@@ -1092,7 +1279,7 @@ rq_status rq_coarse_rank(const rq_index *idx, const float *queries, uint32_t nq,
                          float *out_y, uint32_t *out_cluster, float *out_dist) {
     RQC(ensure_device());
     if (!idx || !queries || !out_cluster || !out_dist) return fail(RQ_ERR_INVALID, "null argument");
-    if (idx->dim != (len + 63) / 64 * 64) return fail(RQ_ERR_DIM_MISMATCH, "query length does not pad to dim");
+    if (!raw_len_ok(idx, len)) return fail(RQ_ERR_DIM_MISMATCH, "query length does not pad to dim (an inner-product index: is not its row length)");
     if (probe == 0) return fail(RQ_ERR_INVALID, "probe == 0");
     const uint32_t dim = idx->dim, k = idx->k, nprobe = std::min(probe, k);
     if (nprobe > RQ_MAX_PROBE) return fail(RQ_ERR_UNSUPPORTED, "probe > 16384");

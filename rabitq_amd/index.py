@@ -20,6 +20,11 @@ def _addr(a):
     return C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(0)
 
 
+def _sq_bound(max_sq_norm) -> float:
+    """max_sq_norm= of the inner-product constructors -> the C ABI's sq_bound (None: NaN, the largest squared norm of the input)."""
+    return float("nan") if max_sq_norm is None else float(max_sq_norm)
+
+
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
@@ -143,24 +148,40 @@ class RaBitQ:
         self.dim, self.k, self.n, self.max_list_len = int(info.dim), int(info.k), int(info.n), int(info.max_list_len)
         self.n_hbm = int(info.n_hbm)      # raw vectors in HBM; the other n - n_hbm live in pinned host memory
         self.split_rows = bool(info.split_rows)   # raw vectors stored as two 16-bit planes per row (option "split_rows")
-        self.metric = "cosine" if info.metric == _lib.METRIC_COSINE else "l2"   # a cosine index normalises rows and queries itself
+        self.metric = _lib.METRIC_NAMES.get(int(info.metric), "l2")   # a cosine index normalises rows and queries itself; an "ip" index augments rows
+        self._ip_d = self.ip_params[0] if self.metric == "ip" else 0   # the raw row length add() and the queries must have
 
     # ---- RaBitQ::from_path (src/rabitq.rs:159) ------------------------------------------------
     @classmethod
-    def from_path(cls, base_path, centroid_path, orthogonal=None, seed: int = 0, metric="l2") -> "RaBitQ":
+    def from_path(cls, base_path, centroid_path, orthogonal=None, seed: int = 0, metric="l2", max_sq_norm=None) -> "RaBitQ":
         """Build from base.fvecs + centroids.fvecs.  `orthogonal` (dim x dim, P[r][c]) fixes the
         rotation the reference draws unseeded (src/utils.rs:16-20); None = seeded Gaussian-QR.
-        metric: "l2" (the reference) or "cosine": rows and queries are normalised on the GPU, distances are 2 - 2 cos."""
+        metric: "l2" (the reference) or "cosine": rows and queries are normalised on the GPU, distances are 2 - 2 cos; or "ip":
+        maximum inner product search, rows get one more coordinate sqrt(S - |x|^2) (index dim = ceil64(d + 1)), distances are
+        S + |q|^2 - 2<x, q> (inner_product() converts), S = max_sq_norm (None: the largest squared row norm)."""
         h = C.c_void_p()
         P = _f32(orthogonal) if orthogonal is not None else None
+        if _lib.metric_id(metric) == _lib.METRIC_IP:
+            check(lib().rq_build_from_path_ip(os.fsencode(base_path), os.fsencode(centroid_path), _addr(P), seed,
+                                              _sq_bound(max_sq_norm), C.byref(h)))
+            return cls(h)
         check(lib().rq_build_from_path_metric(os.fsencode(base_path), os.fsencode(centroid_path), _addr(P), seed,
                                               _lib.metric_id(metric), C.byref(h)))
         return cls(h)
 
     @classmethod
-    def build(cls, base, centroids, orthogonal=None, seed: int = 0, metric="l2") -> "RaBitQ":
-        """from_path on in-memory arrays (base n x d, centroids k x d)."""
+    def build(cls, base, centroids, orthogonal=None, seed: int = 0, metric="l2", max_sq_norm=None) -> "RaBitQ":
+        """from_path on in-memory arrays (base n x d, centroids k x d; metric="ip": k x c with d <= c <= ceil64(d + 1), missing
+        columns are zero)."""
         base, centroids = _f32(base), _f32(centroids)
+        if _lib.metric_id(metric) == _lib.METRIC_IP:
+            if base.ndim != 2 or centroids.ndim != 2:
+                raise _lib.RabitqError(-2, "base and centroids must be 2-D")
+            P = _f32(orthogonal) if orthogonal is not None else None
+            h = C.c_void_p()
+            check(lib().rq_build_ip(_addr(base), base.shape[0], base.shape[1], _addr(centroids), centroids.shape[0], _addr(P),
+                                    seed, centroids.shape[1], _sq_bound(max_sq_norm), C.byref(h)))
+            return cls(h)
         if base.ndim != 2 or centroids.ndim != 2 or base.shape[1] != centroids.shape[1]:
             raise _lib.RabitqError(-2, "base and centroids must be 2-D with the same dimension (rabitq.rs:165)")
         P = _f32(orthogonal) if orthogonal is not None else None
@@ -171,19 +192,25 @@ class RaBitQ:
 
     @classmethod
     def build_device(cls, base_ptr: int, n: int, d: int, centroids_ptr: int, k: int, orthogonal=None,
-                     seed: int = 0, metric="l2") -> "RaBitQ":
-        """Build from device-resident arrays (raw HIP device addresses, e.g. torch.Tensor.data_ptr())."""
+                     seed: int = 0, metric="l2", max_sq_norm=None, centroid_cols: int = None) -> "RaBitQ":
+        """Build from device-resident arrays (raw HIP device addresses, e.g. torch.Tensor.data_ptr()).  metric="ip": the
+        centroids are k x centroid_cols (None: d)."""
         P = _f32(orthogonal) if orthogonal is not None else None
         h = C.c_void_p()
+        if _lib.metric_id(metric) == _lib.METRIC_IP:
+            check(lib().rq_build_device_ip(C.c_void_p(base_ptr), n, d, C.c_void_p(centroids_ptr), k, _addr(P), seed,
+                                           d if centroid_cols is None else centroid_cols, _sq_bound(max_sq_norm), C.byref(h)))
+            return cls(h)
         check(lib().rq_build_device_metric(C.c_void_p(base_ptr), n, d, C.c_void_p(centroids_ptr), k, _addr(P), seed,
                                            _lib.metric_id(metric), C.byref(h)))
         return cls(h)
 
     @classmethod
     def builder(cls, n: int, d: int, centroids_ptr: int, k: int, orthogonal=None, seed: int = 0,
-                max_device_base_bytes: int = 0, metric="l2") -> "Builder":
-        """Streamed two-pass build for inputs that are not resident (include/rabitq_hip.h: rq_builder_*)."""
-        return Builder(n, d, centroids_ptr, k, orthogonal, seed, max_device_base_bytes, metric)
+                max_device_base_bytes: int = 0, metric="l2", max_sq_norm=None, centroid_cols: int = None) -> "Builder":
+        """Streamed two-pass build for inputs that are not resident (include/rabitq_hip.h: rq_builder_*).  metric="ip" needs
+        max_sq_norm (the largest row_sqnorm_max over the chunks): the streamed build has no automatic bound."""
+        return Builder(n, d, centroids_ptr, k, orthogonal, seed, max_device_base_bytes, metric, max_sq_norm, centroid_cols)
 
     # ---- load_from_dir / dump_to_dir (src/rabitq.rs:84, :128) ---------------------------------
     @classmethod
@@ -206,7 +233,8 @@ class RaBitQ:
         check(lib().rq_dump_json(self._h, os.fsencode(path)))
 
     @classmethod
-    def from_arrays(cls, base, orthogonal, centroids, offsets, map_ids, codes, factors, metric="l2") -> "RaBitQ":
+    def from_arrays(cls, base, orthogonal, centroids, offsets, map_ids, codes, factors, metric="l2", max_sq_norm=None,
+                    d: int = None) -> "RaBitQ":
         """From the reference's in-memory arrays (what load_from_dir produces).  The arrays are taken as they are; metric="cosine"
         only marks the index, so that its queries and added rows are normalised (`base` then holds normalised rows already)."""
         base, orthogonal, centroids, factors = _f32(base), _f32(orthogonal), _f32(centroids), _f32(factors)
@@ -214,6 +242,13 @@ class RaBitQ:
         map_ids = np.ascontiguousarray(map_ids, dtype=np.uint32)
         codes = np.ascontiguousarray(codes, dtype=np.uint64)
         h = C.c_void_p()
+        if metric == "ip" and max_sq_norm is not None:   # an inner-product index: `base` holds augmented rows, d = the raw row length
+            if d is None:
+                raise ValueError('from_arrays(metric="ip") needs d, the raw row length')
+            check(lib().rq_from_arrays_ip(orthogonal.shape[0], map_ids.size, offsets.size - 1, _addr(base), _addr(orthogonal),
+                                          _addr(centroids), _addr(offsets), _addr(map_ids), _addr(codes), _addr(factors),
+                                          int(d), float(max_sq_norm), C.byref(h)))
+            return cls(h)
         check(lib().rq_from_arrays_metric(orthogonal.shape[0], map_ids.size, offsets.size - 1, _addr(base), _addr(orthogonal),
                                           _addr(centroids), _addr(offsets), _addr(map_ids), _addr(codes), _addr(factors),
                                           _lib.metric_id(metric), C.byref(h)))
@@ -297,7 +332,10 @@ class RaBitQ:
             raise TypeError(f"vectors must be real numbers, not {v.dtype}")
         if v.ndim != 2:
             raise ValueError(f"vectors must be 2-D (m x d), not {v.ndim}-D")
-        if v.shape[1] == 0 or (v.shape[1] + 63) // 64 * 64 != self.dim:
+        if getattr(self, "_ip_d", 0):   # rows of an inner-product index's own d: rq_add augments them
+            if v.shape[1] != self._ip_d:
+                raise _lib.RabitqError(-2, f"row length {v.shape[1]} is not the inner-product index's row length {self._ip_d}")
+        elif v.shape[1] == 0 or (v.shape[1] + 63) // 64 * 64 != self.dim:
             raise _lib.RabitqError(-2, f"row length {v.shape[1]} does not pad to index dim {self.dim}")
         return _f32(v)
 
@@ -402,13 +440,47 @@ class RaBitQ:
                                                        C.c_void_p(out_n_ptr)))
 
     # ---- range search: every neighbour within a per-query radius --------------------------------
-    def range_search(self, queries, probe: int, radius, filter: Filter = None):
+    @property
+    def ip_params(self):
+        """(d, S) of an inner-product index: the raw row length and the bound on the squared row norms."""
+        d, s = C.c_uint32(), C.c_float()
+        check(lib().rq_ip_params(self._h, C.byref(d), C.byref(s)))
+        return int(d.value), np.float32(s.value)
+
+    def inner_product(self, dist, queries, counts=None):
+        """The inner products an "ip" index's distances stand for: ip = 0.5 * ((S + |q|^2) - dist), in f32 on the GPU.  dist is
+        B x topk as query_batch returns it; with counts (its third result) the slots past a query's count get -inf."""
+        q, dist = _f32(queries), _f32(dist)
+        if q.ndim != 2 or dist.ndim != 2 or dist.shape[0] != q.shape[0]:
+            raise _lib.RabitqError(-1, "queries must be B x d and dist B x topk")
+        n = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+        out = np.empty_like(dist)
+        check(lib().rq_ip_from_dist(self._h, _addr(q), q.shape[0], q.shape[1], _addr(dist), dist.shape[1], _addr(n), _addr(out)))
+        return out
+
+    def ip_radius(self, queries, min_ip):
+        """The range_search radius that stands for "inner product above min_ip" on an "ip" index, one per query."""
+        q = _f32(queries)
+        m = np.asarray(min_ip, dtype=np.float32)
+        m = np.full(q.shape[0], m, dtype=np.float32) if m.ndim == 0 else np.ascontiguousarray(m.reshape(-1))
+        if q.ndim != 2 or m.size != q.shape[0]:
+            raise _lib.RabitqError(-1, "queries must be B x d and min_ip a scalar or one value per query")
+        out = np.empty(q.shape[0], np.float32)
+        check(lib().rq_ip_radius(self._h, _addr(q), q.shape[0], q.shape[1], _addr(m), _addr(out)))
+        return out
+
+    def range_search(self, queries, probe: int, radius=None, filter: Filter = None, min_ip=None):
         """B queries -> (lims u64[B + 1], dist f32[total], ids u32[total]): query b's neighbours with estimate and exact squared
         distance both strictly below radius[b] (a scalar = the same radius for every query), among the rows of its `probe` nearest
-        lists, at [lims[b], lims[b + 1]) ascending by (distance, id).  filter: only its rows can be returned."""
+        lists, at [lims[b], lims[b + 1]) ascending by (distance, id).  filter: only its rows can be returned.
+        min_ip (an "ip" index, instead of radius): the neighbours whose inner product is above min_ip[b] (ip_radius)."""
         q = _f32(queries)
         if q.ndim != 2:
             raise _lib.RabitqError(-1, "queries must be 2-D")
+        if (radius is None) == (min_ip is None):
+            raise _lib.RabitqError(-1, "give either radius or min_ip")
+        if min_ip is not None:
+            radius = self.ip_radius(q, min_ip)
         r = np.asarray(radius, dtype=np.float32)
         r = np.full(q.shape[0], r, dtype=np.float32) if r.ndim == 0 else np.ascontiguousarray(r.reshape(-1))
         if r.size != q.shape[0]:
@@ -500,9 +572,14 @@ class RaBitQ:
 class Builder:
     """assign_chunk every row -> order() -> place_chunk every row -> finish() -> RaBitQ.  Chunks are device pointers."""
 
-    def __init__(self, n, d, centroids_ptr, k, orthogonal=None, seed=0, max_device_base_bytes=0, metric="l2"):
+    def __init__(self, n, d, centroids_ptr, k, orthogonal=None, seed=0, max_device_base_bytes=0, metric="l2", max_sq_norm=None,
+                 centroid_cols=None):
         P = _f32(orthogonal) if orthogonal is not None else None
         self._b = C.c_void_p()
+        if _lib.metric_id(metric) == _lib.METRIC_IP:
+            check(lib().rq_builder_create_ip(n, d, C.c_void_p(centroids_ptr), k, _addr(P), seed, max_device_base_bytes,
+                                             d if centroid_cols is None else centroid_cols, _sq_bound(max_sq_norm), C.byref(self._b)))
+            return
         check(lib().rq_builder_create_metric(n, d, C.c_void_p(centroids_ptr), k, _addr(P), seed, max_device_base_bytes,
                                              _lib.metric_id(metric), C.byref(self._b)))
 

@@ -32,6 +32,39 @@ def normalize_device(x_ptr: int, n: int, d: int, out_ptr: int) -> None:
     check(lib().rq_normalize_device(C.c_void_p(x_ptr), n, d, C.c_void_p(out_ptr)))
 
 
+def augment(x, max_sq_norm=None):
+    """A(x; S) row by row, the inner-product metric's augmentation (include/rabitq_hip.h: rq_augment): n x d -> n x ceil64(d + 1)
+    with slot d = sqrt(S - |x|^2); S = max_sq_norm (None: the largest squared row norm).  What a caller trains centroids on."""
+    x = _f32(x)
+    if x.ndim != 2:
+        raise ValueError("x must be 2-D (n x d)")
+    out = np.empty((x.shape[0], (x.shape[1] + 64) // 64 * 64), np.float32)
+    check(lib().rq_augment(_addr(x), x.shape[0], x.shape[1], float("nan") if max_sq_norm is None else float(max_sq_norm), _addr(out)))
+    return out
+
+
+def augment_device(x_ptr: int, n: int, d: int, max_sq_norm, out_ptr: int) -> None:
+    """rq_augment on device-resident rows (raw addresses); out is n x ceil64(d + 1)."""
+    check(lib().rq_augment_device(C.c_void_p(x_ptr), n, d, float("nan") if max_sq_norm is None else float(max_sq_norm), C.c_void_p(out_ptr)))
+
+
+def row_sqnorm_max(x) -> np.float32:
+    """The largest squared row norm of x (n x d) as the inner-product metric computes it: the automatic bound S."""
+    x = _f32(x)
+    if x.ndim != 2:
+        raise ValueError("x must be 2-D (n x d)")
+    out = C.c_float()
+    check(lib().rq_row_sqnorm_max(_addr(x), x.shape[0], x.shape[1], C.byref(out)))
+    return np.float32(out.value)
+
+
+def row_sqnorm_max_device(x_ptr: int, n: int, d: int) -> np.float32:
+    """rq_row_sqnorm_max on device-resident rows (a raw address)."""
+    out = C.c_float()
+    check(lib().rq_row_sqnorm_max_device(C.c_void_p(x_ptr), n, d, C.byref(out)))
+    return np.float32(out.value)
+
+
 def cosine_similarity(dist):
     """The cosine a cosine index's distance stands for: dist = 2 - 2 cos  ->  cos = 1 - dist / 2."""
     return 1.0 - np.asarray(dist) / 2.0
