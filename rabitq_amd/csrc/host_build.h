@@ -288,8 +288,7 @@ static rq_status alloc_base_tiers(rq_index *idx, uint64_t budget_bytes, const ui
     idx->n_dev = hbm;
     idx->split_rows = g_split_rows.load() != 0;  // both tiers as split rows (common.h): the re-ranker's pre-filter where no shadow fits
     RQC(idx->base.alloc(hbm * idx->dim));
-    RQC(idx->list_tier.alloc(k));
-    HIPC(hipMemcpy(idx->list_tier.p, idx->h_list_tier.data(), (size_t)k * sizeof(ListTier), hipMemcpyHostToDevice));
+    RQC(idx->list_tier.upload(idx->h_list_tier.data(), k));
     hipError_t e = hipHostMalloc((void **)&idx->base_host, std::max<uint64_t>(host, 1) * row, hipHostMallocMapped | hipHostMallocPortable);
     if (e != hipSuccess) {
         idx->base_host = nullptr;
@@ -372,8 +371,8 @@ static rq_status builder_alloc_pass1(rq_builder *b) {
     RQC(b->codes_tmp.alloc(n * idx->W));
     RQC(b->factors_tmp.alloc(n));
     const uint64_t chunk = std::min<uint64_t>(std::max<uint64_t>(n, 1), RQ_BUILD_CHUNK);
-    if (b->d != dim || idx->metric == RQ_METRIC_COSINE) RQC(b->xpad.alloc(chunk * dim));
-    if (idx->metric == RQ_METRIC_IP) RQC(b->ip_bad.alloc(1));
+    if (b->d != dim || idx->metric.id != RQ_METRIC_L2) RQC(b->xpad.alloc(chunk * dim));  // (an L2 row of dim floats is rotated where it is)
+    if (metric_refuses_rows(idx->metric)) RQC(b->ip_bad.alloc(1));
     RQC(b->xrot.alloc(chunk * dim));
     if (assign_has_mfma(idx->W) && g_assign_impl.load() != 1) RQC(assign_aux_init(idx, b->assign_aux, chunk));
     for (auto &e : b->ev) HIPC(hipEventCreate(&e));
@@ -381,28 +380,24 @@ static rq_status builder_alloc_pass1(rq_builder *b) {
 }
 
 static rq_status builder_create(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
-                                uint64_t seed, uint64_t max_device_base_bytes, uint32_t metric, rq_builder **out,
-                                uint32_t cent_cols = 0, float sq_bound = 0.0f) {
+                                uint64_t seed, uint64_t max_device_base_bytes, const MetricSpec &metric, uint32_t cent_cols, rq_builder **out) {
     RQC(ensure_device());
     RQC(ensure_kernel_attributes());
     if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
     *out = nullptr;
-    const bool ip = metric == RQ_METRIC_IP;  // (only the _ip entries pass it: the *_metric entries have refused it)
-    if (!ip && !metric_known(metric)) return fail(RQ_ERR_INVALID, metric_refusal(metric));
     if (!d_centroids || d == 0 || k == 0) return fail(RQ_ERR_INVALID, "bad build arguments");
     if (n >= 0xFFFFFFFFull) return fail(RQ_ERR_UNSUPPORTED, "n must fit u32 ids (rabitq.rs:64-65)");
-    const uint32_t dim = ip ? ip_dim(d) : (d + 63) / 64 * 64;  // rabitq.rs:168-179
-    if (dim > 4096) return fail(RQ_ERR_UNSUPPORTED, ip ? "d > 4095 not supported by the inner-product metric" : "dim > 4096 not supported");
-    if (!ip) cent_cols = d;
-    if (cent_cols < d || cent_cols > dim)
-        return fail(RQ_ERR_INVALID, "centroid_cols " + std::to_string(cent_cols) + " outside [d, dim] = [" + std::to_string(d) + ", " + std::to_string(dim) + "]");
-    if (ip && !(sq_bound >= 0.0f && sq_bound <= 3.402823466e+38f))
+    const uint32_t dim = metric_dim(metric, d);
+    if (dim > 4096) return fail(RQ_ERR_UNSUPPORTED, "dim > 4096 (an inner-product index: d > 4095) not supported");
+    if (!metric_centroid_cols_ok(metric, d, cent_cols))
+        return fail(RQ_ERR_INVALID, "centroid_cols " + std::to_string(cent_cols) + " is not a record length this metric takes for d = " + std::to_string(d));
+    if (metric.id != RQ_METRIC_IP) RQC(metric_entry_check(metric.id));
+    else if (!ip_bound_ok(metric.S))
         return fail(RQ_ERR_INVALID, "sq_bound must be finite and >= 0 (the streamed builder has no automatic mode: rq_row_sqnorm_max_device)");
     std::unique_ptr<rq_builder> b(new rq_builder());
     b->idx.reset(new rq_index());
     rq_index *idx = b->idx.get();
     idx->dim = dim, idx->k = k, idx->n = n, idx->W = dim / 64, idx->metric = metric;
-    if (ip) idx->ip_d = d, idx->ip_S = sq_bound;
     b->d = d, b->budget = max_device_base_bytes;
 
     std::vector<float> Pgen;
@@ -410,8 +405,7 @@ static rq_status builder_create(uint64_t n, uint32_t d, const float *d_centroids
         gen_orthogonal(dim, seed, Pgen);  // utils.rs:16-20, seeded
         orthogonal_host = Pgen.data();
     }
-    RQC(idx->P.alloc((size_t)dim * dim));
-    HIPC(hipMemcpy(idx->P.p, orthogonal_host, (size_t)dim * dim * 4, hipMemcpyHostToDevice));
+    RQC(idx->P.upload(orthogonal_host, (size_t)dim * dim));
 
     // centroids: pad, rotate (rabitq.rs:189), transpose for the lane<->centroid kernels
     DevBuf<float> cpad;
@@ -428,13 +422,12 @@ static rq_status builder_create(uint64_t n, uint32_t d, const float *d_centroids
     return RQ_OK;
 }
 
-// inner-product builder: the first invalid row of the chunk just augmented, if any (after a synchronisation)
-static rq_status builder_ip_check(rq_builder *b) {
-    uint32_t bad = 0xFFFFFFFFu;
-    HIPC(hipMemcpy(&bad, b->ip_bad.p, 4, hipMemcpyDeviceToHost));
-    if (bad == 0xFFFFFFFFu) return RQ_OK;
-    b->refused = true;
-    return fail(RQ_ERR_INVALID, "row " + std::to_string(bad) + ": its squared norm is not finite or exceeds sq_bound (the builder can only be freed now)");
+// after a chunk's transform has been waited for: the row it refused, if any (a refused chunk ends the builder)
+static rq_status builder_rows_check(rq_builder *b) {
+    if (!metric_refuses_rows(b->idx->metric)) return RQ_OK;
+    const rq_status s = bad_row_check(b->ip_bad.p, ":", "sq_bound (the builder can only be freed now)");
+    b->refused = s == RQ_ERR_INVALID;
+    return s;
 }
 
 // pass 1 for rows [i0, i0 + m) of the input (d_rows: m x d, device)
@@ -448,18 +441,8 @@ static rq_status builder_assign(rq_builder *b, const float *d_rows, uint64_t i0,
     const uint32_t d = b->d, dim = idx->dim;
     for (uint64_t c0 = 0; c0 < m; c0 += RQ_BUILD_CHUNK) {
         const uint64_t mm = std::min<uint64_t>(RQ_BUILD_CHUNK, m - c0), at = i0 + c0;
-        const float *src = d_rows + c0 * d;
-        if (idx->metric == RQ_METRIC_COSINE) {  // pad + normalise in one launch: everything behind it sees N(x)
-            launch_normalize(src, mm, d, dim, b->xpad.p, nullptr);
-            src = b->xpad.p;
-        } else if (idx->metric == RQ_METRIC_IP) {  // pad + augment in one launch: everything behind it sees A(x)
-            HIPC(hipMemset(b->ip_bad.p, 0xFF, 4));
-            launch_augment(src, mm, d, dim, idx->ip_S, b->ip_s_pre, b->xpad.p, b->ip_bad.p, nullptr, nullptr, at);
-            src = b->xpad.p;
-        } else if (d != dim) {
-            pad_rows_kernel<<<ceil_div(mm * dim, 256), 256>>>(src, b->xpad.p, mm, d, dim);
-            src = b->xpad.p;
-        }
+        const float *src;
+        RQC(transform_rows(idx->metric, dim, d_rows + c0 * d, mm, d, at, b->xpad.p, nullptr, BaseView{}, b->ip_s_pre, b->ip_bad.p, &src));
         HIPC(hipEventRecord(b->ev[0], nullptr));
         launch_rotate(src, idx->P.p, b->xrot.p, mm, dim, true, nullptr);
         HIPC(hipEventRecord(b->ev[1], nullptr));
@@ -470,7 +453,7 @@ static rq_status builder_assign(rq_builder *b, const float *d_rows, uint64_t i0,
         HIPC(hipEventRecord(b->ev[3], nullptr));
         HIPC(hipEventSynchronize(b->ev[3]));  // the chunk buffers are reused by the next chunk (and by the caller)
         HIPC(hipGetLastError());
-        if (idx->metric == RQ_METRIC_IP) RQC(builder_ip_check(b));  // (read where the chunk is waited for anyway)
+        RQC(builder_rows_check(b));  // (read where the chunk is waited for anyway)
         float t01 = 0, t12 = 0, t23 = 0;
         HIPC(hipEventElapsedTime(&t01, b->ev[0], b->ev[1]));
         HIPC(hipEventElapsedTime(&t12, b->ev[1], b->ev[2]));
@@ -543,17 +526,11 @@ static rq_status builder_place(rq_builder *b, const float *d_rows, uint64_t i0, 
     if (i0 > idx->n || m > idx->n - i0) return fail(RQ_ERR_INVALID, "chunk outside [0, n)");
     if (!b->cov_place.add(i0, m)) return fail(RQ_ERR_INVALID, "rq_builder_place_chunk: rows [" + std::to_string(i0) + ", " + std::to_string(i0 + m) + ") overlap rows already placed");
     if (m) {
-        if (idx->metric == RQ_METRIC_COSINE)  // the same kernel as pass 1, storing N(x) at the row's final position
-            launch_normalize(d_rows, m, b->d, idx->dim, nullptr, nullptr, b->pos_of_id.p, i0, idx->view());
-        else if (idx->metric == RQ_METRIC_IP) {  // the same kernel as pass 1 (a caller feeding other rows than it did then is refused)
-            HIPC(hipMemset(b->ip_bad.p, 0xFF, 4));
-            launch_augment(d_rows, m, b->d, idx->dim, idx->ip_S, b->ip_s_pre, nullptr, b->ip_bad.p, nullptr, b->pos_of_id.p, i0, idx->view());
-        } else
-            place_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(m, 4), 1u << 20), 256>>>(d_rows, i0, m, b->d, idx->dim,
-                                                                                              b->pos_of_id.p, idx->view());
+        // the same transform as pass 1, stored at the row's final position (inner product: a caller feeding other rows than it did then is refused)
+        RQC(transform_rows(idx->metric, idx->dim, d_rows, m, b->d, i0, nullptr, b->pos_of_id.p, idx->view(), b->ip_s_pre, b->ip_bad.p));
         HIPC(hipDeviceSynchronize());  // the caller may reuse d_rows right away
         HIPC(hipGetLastError());
-        if (idx->metric == RQ_METRIC_IP) RQC(builder_ip_check(b));
+        RQC(builder_rows_check(b));
     }
     b->placed += m;
     return RQ_OK;
@@ -571,27 +548,12 @@ static rq_status builder_finish(rq_builder *bp, rq_index **out) {
     return RQ_OK;
 }
 
-static rq_status build_device(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
-                              const float *orthogonal_host, uint64_t seed, uint32_t metric, rq_index **out) {
-    if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
-    *out = nullptr;
-    if (n && !d_base) return fail(RQ_ERR_INVALID, "bad build arguments");
-    rq_builder *b = nullptr;
-    RQC(builder_create(n, d, d_centroids, k, orthogonal_host, seed, 0, metric, &b));
-    std::unique_ptr<rq_builder> guard(b);
-    RQC(builder_assign(b, d_base, 0, n));
-    RQC(builder_order(b));
-    RQC(builder_place(b, d_base, 0, n));
-    return builder_finish(guard.release(), out);
-}
-
 // s of n rows of d floats (device) into out_s (nullable, n floats); *out_max = the largest finite s, *out_bad = the first row whose
 // s is not finite or exceeds sq_bound (0xFFFFFFFF: none).  dim: the padded length the chain runs over (a multiple of 64 >= d).
 static rq_status row_sqnorms(const float *d_x, uint64_t n, uint32_t d, uint32_t dim, float sq_bound, float *out_s, float *out_max,
                              uint32_t *out_bad) {
     DevBuf<uint32_t> stat;
-    RQC(stat.alloc(3));
-    HIPC(hipMemcpy(stat.p, RQ_SQNORM_STAT_INIT, 12, hipMemcpyHostToDevice));
+    RQC(stat.upload(RQ_SQNORM_STAT_INIT, 3));
     for (uint64_t r0 = 0; r0 < n; r0 += RQ_BUILD_CHUNK)
         launch_row_sqnorm(d_x + r0 * d, std::min<uint64_t>(RQ_BUILD_CHUNK, n - r0), d, dim, sq_bound, r0, out_s ? out_s + r0 : nullptr, stat.p, nullptr);
     uint32_t h[3];
@@ -604,30 +566,32 @@ static rq_status row_sqnorms(const float *d_x, uint64_t n, uint32_t d, uint32_t 
 // sq_bound of an _ip call resolved against the input: NaN = the largest s; the refusals the contract lists.  s_out: n floats.
 static rq_status ip_resolve_bound(const float *d_x, uint64_t n, uint32_t d, float *sq_bound, float *s_out) {
     const bool automatic = *sq_bound != *sq_bound;
-    if (!automatic && !(*sq_bound >= 0.0f && *sq_bound <= 3.402823466e+38f)) return fail(RQ_ERR_INVALID, "sq_bound must be finite and >= 0, or NaN for the largest squared norm of the input");
+    if (!automatic && !ip_bound_ok(*sq_bound)) return fail(RQ_ERR_INVALID, "sq_bound must be finite and >= 0, or NaN for the largest squared norm of the input");
     float mx = 0.0f;
-    uint32_t bad = 0xFFFFFFFFu;
-    RQC(row_sqnorms(d_x, n, d, ip_dim(d), automatic ? __builtin_inff() : *sq_bound, s_out, &mx, &bad));
-    if (bad != 0xFFFFFFFFu)
-        return fail(RQ_ERR_INVALID, "row " + std::to_string(bad) + ": its squared norm is not finite" + (automatic ? "" : " or exceeds sq_bound"));
+    uint32_t bad = RQ_NO_BAD_ROW;
+    RQC(row_sqnorms(d_x, n, d, ceil64(d + 1), automatic ? __builtin_inff() : *sq_bound, s_out, &mx, &bad));
+    RQC(bad_row_refusal(bad, ":", automatic ? nullptr : "sq_bound"));
     if (automatic) *sq_bound = mx;
     return RQ_OK;
 }
 
-static rq_status build_device_ip(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
-                                 const float *orthogonal_host, uint64_t seed, uint32_t cent_cols, float sq_bound, rq_index **out) {
-    RQC(ensure_device());
+// The one-shot build from device-resident rows: the five builder calls.  An inner-product build first resolves its bound.
+static rq_status build_device(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, uint32_t cent_cols,
+                              const float *orthogonal_host, uint64_t seed, MetricSpec metric, rq_index **out) {
     if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
     *out = nullptr;
-    if ((n && !d_base) || d == 0) return fail(RQ_ERR_INVALID, "bad build arguments");
-    if (d > 4095) return fail(RQ_ERR_UNSUPPORTED, "d > 4095 not supported by the inner-product metric");
-    DevBuf<float> s;  // computed once: the bound, the validity of every row and slot d of both passes come from it
-    RQC(s.alloc(n));
-    RQC(ip_resolve_bound(d_base, n, d, &sq_bound, s.p));
+    if (n && !d_base) return fail(RQ_ERR_INVALID, "bad build arguments");
+    DevBuf<float> s;  // inner product: computed once -- the bound, the validity of every row and slot d of both passes come from it
+    if (metric.id == RQ_METRIC_IP) {
+        RQC(ensure_device());
+        RQC(ip_d_check(d));
+        RQC(s.alloc(n));
+        RQC(ip_resolve_bound(d_base, n, d, &metric.S, s.p));
+    }
     rq_builder *b = nullptr;
-    RQC(builder_create(n, d, d_centroids, k, orthogonal_host, seed, 0, RQ_METRIC_IP, &b, cent_cols, sq_bound));
+    RQC(builder_create(n, d, d_centroids, k, orthogonal_host, seed, 0, metric, cent_cols, &b));
     std::unique_ptr<rq_builder> guard(b);
-    b->ip_s_pre = s.p;
+    if (metric.id == RQ_METRIC_IP) b->ip_s_pre = s.p;
     RQC(builder_assign(b, d_base, 0, n));
     RQC(builder_order(b));
     RQC(builder_place(b, d_base, 0, n));
@@ -678,24 +642,23 @@ static rq_status write_record(FILE *f, const void *data, uint32_t count, size_t 
 static rq_status copy_base_rows(const rq_index *idx, uint64_t i0, uint64_t m, float *buf, bool to_index);
 static rq_status from_arrays(uint32_t dim, uint64_t n, uint32_t k, const float *base, const float *orthogonal,
                              const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
-                             const uint64_t *codes, const rq_factor_t *factors, uint32_t metric, rq_index **out,
-                             uint32_t ip_d = 0, float ip_S = 0.0f) {
+                             const uint64_t *codes, const rq_factor_t *factors, const MetricSpec &metric, rq_index **out) {
     RQC(ensure_device());
     RQC(ensure_kernel_attributes());
     if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
     *out = nullptr;
-    const bool ip = metric == RQ_METRIC_IP;  // (only the _ip entry and the loaders pass it)
-    if (!ip && !metric_known(metric)) return fail(RQ_ERR_INVALID, metric_refusal(metric));
+    if (metric.id != RQ_METRIC_IP) RQC(metric_entry_check(metric.id));
     if (dim == 0 || dim % 64 != 0) return fail(RQ_ERR_DIM_MISMATCH, "dim must be a non-zero multiple of 64 (rabitq.rs:109)");
-    if (ip && (ip_d == 0 || ip_d > 4095 || ip_dim(ip_d) != dim))
-        return fail(RQ_ERR_DIM_MISMATCH, "inner-product index: dim " + std::to_string(dim) + " is not ceil64(d + 1) for d = " + std::to_string(ip_d));
-    if (ip && !(ip_S >= 0.0f && ip_S <= 3.402823466e+38f)) return fail(RQ_ERR_INVALID, "inner-product index: sq_bound must be finite and >= 0");
+    if (metric.id == RQ_METRIC_IP) {  // the arrays are taken as they are: a d that cannot be this dim's is a mismatch of the two
+        if (!ip_d_ok(metric.d, dim))
+            return fail(RQ_ERR_DIM_MISMATCH, "inner-product index: dim " + std::to_string(dim) + " is not ceil64(d + 1) for d = " + std::to_string(metric.d));
+        if (!ip_bound_ok(metric.S)) return fail(RQ_ERR_INVALID, "inner-product index: sq_bound must be finite and >= 0");
+    }
     if (!orthogonal || !centroids || !offsets || (n && (!base || !map_ids || !codes || !factors)))
         return fail(RQ_ERR_INVALID, "null array");
     if (n >= 0xFFFFFFFFull) return fail(RQ_ERR_UNSUPPORTED, "n must fit u32");
     std::unique_ptr<rq_index> idx(new rq_index());
     idx->dim = dim, idx->n = n, idx->k = k, idx->W = dim / 64, idx->metric = metric;
-    if (ip) idx->ip_d = ip_d, idx->ip_S = ip_S;
     RQC(idx->P.alloc((size_t)dim * dim));
     RQC(idx->centroids.alloc((size_t)k * dim));
     RQC(idx->offsets.alloc((size_t)k + 1));
@@ -717,6 +680,62 @@ static rq_status from_arrays(uint32_t dim, uint64_t n, uint32_t k, const float *
     HIPC(hipMemcpy(idx->offsets.p, offsets, ((size_t)k + 1) * 4, hipMemcpyHostToDevice));
     RQC(finish_index(idx.get()));
     *out = idx.release();
+    return RQ_OK;
+}
+
+// rows and centroid records (k x cent_cols) in host memory: staged once, then the device build
+static rq_status build_host(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k, uint32_t cent_cols,
+                            const float *orthogonal, uint64_t seed, const MetricSpec &metric, rq_index **out) {
+    RQC(ensure_device());
+    if (out) *out = nullptr;
+    if ((n && !base) || !centroids) return fail(RQ_ERR_INVALID, "null argument");
+    if (metric.id == RQ_METRIC_IP) RQC(ip_d_check(d));
+    if (!metric_centroid_cols_ok(metric, d, cent_cols)) return fail(RQ_ERR_INVALID, "centroid_cols outside [d, ceil64(d + 1)]");
+    DevBuf<float> db, dc;
+    RQC(db.upload(base, n * d));
+    RQC(dc.upload(centroids, (size_t)k * cent_cols));
+    return build_device(db.p, n, d, dc.p, k, cent_cols, orthogonal, seed, metric, out);
+}
+// base.fvecs + centroids.fvecs (rabitq.rs:160-165); the row length is the base file's, the centroid records' what the metric takes for it
+static rq_status build_from_path(const char *base_fvecs, const char *centroid_fvecs, const float *orthogonal, uint64_t seed,
+                                 MetricSpec metric, rq_index **out) {
+    if (!base_fvecs || !centroid_fvecs) return fail(RQ_ERR_INVALID, "null path");
+    VecsFile b, c;
+    RQC(read_vecs_file(base_fvecs, 4, b));      // rabitq.rs:160
+    RQC(read_vecs_file(centroid_fvecs, 4, c));  // :163
+    if (b.lens.empty() || c.lens.empty()) return fail(RQ_ERR_IO, "empty fvecs file");
+    const uint32_t d = b.lens[0], cc = c.lens[0];
+    for (uint32_t l : b.lens)
+        if (l != d) return fail(RQ_ERR_IO, "ragged base.fvecs");
+    for (uint32_t l : c.lens)
+        if (l != cc) return fail(RQ_ERR_IO, "ragged centroids.fvecs");
+    if (metric.id == RQ_METRIC_IP) metric.d = d;
+    if ((metric.id == RQ_METRIC_IP && !ip_d_ok(d)) || !metric_centroid_cols_ok(metric, d, cc))
+        return fail(RQ_ERR_DIM_MISMATCH, "base and centroid dimensions differ (rabitq.rs:165; an inner-product build: centroid records hold between d and ceil64(d + 1) values)");
+    return build_host(reinterpret_cast<const float *>(b.data.data()), b.lens.size(), d, reinterpret_cast<const float *>(c.data.data()),
+                      (uint32_t)c.lens.size(), cc, orthogonal, seed, metric, out);
+}
+
+// n rows of d floats -> n x dim through transform_rows, chunk by chunk (row offsets of a chunk keep the 16-byte alignment of the whole)
+static rq_status transform_all_rows(const MetricSpec &m, uint32_t dim, const float *d_x, uint64_t n, uint32_t d, const float *s_pre, uint32_t *bad_row, float *d_out) {
+    for (uint64_t r0 = 0; r0 < n; r0 += RQ_BUILD_CHUNK)
+        RQC(transform_rows(m, dim, d_x + r0 * d, std::min<uint64_t>(RQ_BUILD_CHUNK, n - r0), d, r0, d_out + r0 * dim, nullptr, BaseView{}, s_pre, bad_row));
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipGetLastError());
+    return RQ_OK;
+}
+// the host twin of a `_device` entry over rows: n x d in, n x out_cols out (0: nothing comes back); d_ok: the entry's own verdict
+// on d, made by the caller without a device and honoured before anything is staged
+template <typename F>
+static rq_status with_staged_rows(const float *x, uint64_t n, uint32_t d, float *out, uint32_t out_cols, rq_status d_ok, F &&device_entry) {
+    RQC(ensure_device());
+    if (n && (!x || (out_cols && !out))) return fail(RQ_ERR_INVALID, "null argument");
+    RQC(d_ok);
+    DevBuf<float> dx, dout;
+    RQC(dx.upload(x, n * d));
+    RQC(dout.alloc(n * out_cols));
+    RQC(device_entry(dx.p, dout.p));
+    if (n * out_cols) HIPC(hipMemcpy(out, dout.p, n * out_cols * 4, hipMemcpyDeviceToHost));
     return RQ_OK;
 }
 

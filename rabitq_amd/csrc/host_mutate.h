@@ -252,10 +252,7 @@ static rq_status index_add(rq_index *idx, const float *rows, uint64_t m, uint32_
     mutate_stats_begin(idx);
     RQC(mutate_refusals(idx));
     if (m && !rows) return fail(RQ_ERR_INVALID, "null rows with m > 0");
-    if (idx->metric == RQ_METRIC_IP && d != idx->ip_d)
-        return fail(RQ_ERR_DIM_MISMATCH, "row length " + std::to_string(d) + " is not the inner-product index's row length " + std::to_string(idx->ip_d));
-    if (d == 0 || !raw_len_ok(idx, d))
-        return fail(RQ_ERR_DIM_MISMATCH, "row length " + std::to_string(d) + " does not pad to index dim " + std::to_string(idx->dim));
+    RQC(raw_len_check(idx, "row", d));
     if (m >= 0xFFFFFFFFull || idx->n + m >= 0xFFFFFFFFull) return fail(RQ_ERR_UNSUPPORTED, "n must fit u32 ids (rabitq.rs:64-65)");
     uint64_t top = 0, hits = 0;
     NewRows nr;
@@ -276,14 +273,11 @@ static rq_status index_add(rq_index *idx, const float *rows, uint64_t m, uint32_
             if (out_first_id) *out_first_id = 0;
             return RQ_OK;
         }
-        RQC(nr.ids.alloc(m));
-        HIPC(hipMemcpy(nr.ids.p, sorted.data(), m * 4, hipMemcpyHostToDevice));
+        RQC(nr.ids.upload(sorted.data(), m));
         RQC(scan_ids(idx, nr.ids.p, m, &top, &hits));
         if (hits) return fail(RQ_ERR_INVALID, std::to_string(hits) + " of the ids are already in the index");
-        RQC(nr.src.alloc(m));
-        RQC(ranks.alloc(m));
-        HIPC(hipMemcpy(nr.src.p, order.data(), m * 4, hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(ranks.p, rank.data(), m * 4, hipMemcpyHostToDevice));
+        RQC(nr.src.upload(order.data(), m));
+        RQC(ranks.upload(rank.data(), m));
         if (out_first_id) *out_first_id = sorted[0];
     } else {  // the next ids: 1 + the largest id the index holds
         RQC(scan_ids(idx, nullptr, 0, &top, &hits));
@@ -295,35 +289,25 @@ static rq_status index_add(rq_index *idx, const float *rows, uint64_t m, uint32_
     DevBuf<float> staged;  // host rows are copied once
     const float *d_rows = rows;
     if (!rows_on_device) {
-        RQC(staged.alloc(m * d));
-        HIPC(hipMemcpy(staged.p, rows, m * d * 4, hipMemcpyHostToDevice));
+        RQC(staged.upload(rows, m * d));
         d_rows = staged.p;
     }
     RQC(ensure_row_keys(idx));
     if (!idx->row_order_ok)
         return fail(RQ_ERR_UNSUPPORTED, "a list of this index is not in the build's order (distance to its centroid, then id): rows can be "
                                         "removed from it, but not added (an index from rq_from_arrays / rq_load_dir whose ids were remapped?)");
-    DevBuf<float> normed;  // cosine: N(row), padded -- pass 1 and the gather then take the rows as an L2 build of N(rows) does
-    if (idx->metric == RQ_METRIC_COSINE) {
-        RQC(normed.alloc(m * idx->dim));
-        launch_normalize(d_rows, m, d, idx->dim, normed.p, nullptr);
+    if (idx->metric.id != RQ_METRIC_L2) {  // N(row) / A(row; the index's S), padded: pass 1 and the gather then take the rows as an L2 build of them does
+        DevBuf<float> stored;
+        DevBuf<uint32_t> bad;
+        RQC(stored.alloc(m * idx->dim));
+        const bool refuses = metric_refuses_rows(idx->metric);
+        if (refuses) RQC(bad.alloc(1));
+        RQC(transform_rows(idx->metric, idx->dim, d_rows, m, d, 0, stored.p, nullptr, BaseView{}, nullptr, bad.p));
         HIPC(hipDeviceSynchronize());
         HIPC(hipGetLastError());
-        staged.release();
-        d_rows = normed.p, d = idx->dim;
-    } else if (idx->metric == RQ_METRIC_IP) {  // A(row; the index's S): refused before anything of the index is touched
-        DevBuf<uint32_t> bad;
-        RQC(normed.alloc(m * idx->dim));
-        RQC(bad.alloc(1));
-        HIPC(hipMemset(bad.p, 0xFF, 4));
-        launch_augment(d_rows, m, d, idx->dim, idx->ip_S, nullptr, normed.p, bad.p, nullptr);
-        uint32_t h_bad = 0;
-        HIPC(hipMemcpy(&h_bad, bad.p, 4, hipMemcpyDeviceToHost));
-        HIPC(hipGetLastError());
-        if (h_bad != 0xFFFFFFFFu)
-            return fail(RQ_ERR_INVALID, "row " + std::to_string(h_bad) + " of the batch: its squared norm is not finite or exceeds the index's sq_bound");
-        staged.release();
-        d_rows = normed.p, d = idx->dim;
+        if (refuses) RQC(bad_row_check(bad.p, " of the batch:", "the index's sq_bound"));  // refused before anything of the index is touched
+        staged.take(stored);  // (the raw copy is released)
+        d_rows = staged.p, d = idx->dim;
     }
     RQC(new_rows_prepare(idx, d_rows, m, d, ranks.p, nr));
     ranks.release();
@@ -343,8 +327,7 @@ static rq_status index_remove(rq_index *idx, const uint32_t *id_bits, uint64_t n
     DevBuf<uint32_t> staged, pos_bits, counts;
     const uint32_t *d_bits = id_bits;
     if (!bits_on_device) {
-        RQC(staged.alloc(in_words));
-        HIPC(hipMemcpy(staged.p, id_bits, in_words * 4, hipMemcpyHostToDevice));
+        RQC(staged.upload(id_bits, in_words));
         d_bits = staged.p;
     }
     RQC(pos_bits.alloc(nwords));

@@ -208,13 +208,9 @@ struct Pass {
         if (sa.stamps) HIPC(hipMemsetAsync(ws.stat.p, 0, 8, st));
         else HIPC(hipMemsetAsync(ws.stat.p, 0, 256 * sizeof(unsigned long long), st));  // (the counters of a final matrix-core stage, if any)
         pf.begin(PF_COARSE);
-        const float *sb_q = d_q;
-        uint32_t sb_len = qp.len;
-        if (idx->metric == RQ_METRIC_COSINE) {  // N(q), padded: what the front kernel rotates and hands on as qpad
-            RQC(ws.qnorm.ensure((uint64_t)nq * dim));
-            launch_normalize(d_q, nq, qp.len, dim, ws.qnorm.p, st);
-            sb_q = ws.qnorm.p, sb_len = dim;
-        }
+        const float *sb_q;  // (cosine: N(q), padded -- what the front kernel rotates and hands on as qpad; else the raw queries: it pads them itself)
+        uint32_t sb_len;
+        RQC(transform_queries(idx, d_q, nq, qp.len, /*want_padded=*/false, ws.qnorm, st, &sb_q, &sb_len));
         sb_front_kernel<<<dim3(ceil_div(k, RQ_SB_LISTS), ceil_div(nq, RQ_SB_QT)), 256, (size_t)2 * RQ_SB_QT * dim * sizeof(float), st>>>(
             sb_q, sb_len, idx->P.p, idx->centroids.p, ws.y.p, ws.qpad.p, ws.dist.p, k, dim, nq, ws.totals.p, ws.big_list.p + nq);
         pf.end();
@@ -232,13 +228,7 @@ struct Pass {
     // 1. pad (rabitq.rs:277-280) + rotate (:282); 2. coarse distances + probe selection (:283-297), unless the caller supplied the lists
     rq_status rotate_coarse() {
         pf.begin(PF_ROTATE);
-        if (idx->metric == RQ_METRIC_COSINE) {  // pad + normalise in one launch (also when nothing is padded): rotation and rerank see N(q)
-            launch_normalize(d_q, nq, qp.len, dim, ws.qpad.p, st);
-            qpad = ws.qpad.p;
-        } else if (qp.len != dim) {
-            pad_rows_kernel<<<ceil_div((uint64_t)nq * dim, 256), 256, 0, st>>>(d_q, ws.qpad.p, nq, qp.len, dim);
-            qpad = ws.qpad.p;
-        }
+        RQC(transform_queries(idx, d_q, nq, qp.len, /*want_padded=*/true, ws.qpad, st, &qpad));
         launch_rotate(qpad, idx->P.p, ws.y.p, nq, dim, nq >= 32, st);
         pf.end();
         if (ext_cluster) {
@@ -737,11 +727,7 @@ static rq_status validate_call(const rq_index *idx, bool args_null, uint32_t len
     RQC(ensure_device());
     RQC(ensure_kernel_attributes());
     if (!idx || args_null) return fail(RQ_ERR_INVALID, "null argument");
-    if (idx->metric == RQ_METRIC_IP && len != idx->ip_d)
-        return fail(RQ_ERR_DIM_MISMATCH, "query length " + std::to_string(len) + " is not the inner-product index's row length " + std::to_string(idx->ip_d));
-    if (!raw_len_ok(idx, len))  // rabitq.rs:275
-        return fail(RQ_ERR_DIM_MISMATCH, "query length " + std::to_string(len) + " does not pad to index dim " +
-                                             std::to_string(idx->dim));
+    RQC(raw_len_check(idx, "query", len));
     if (probe == 0 || idx->k == 0) return fail(RQ_ERR_INVALID, "probe == 0 (the reference panics at rabitq.rs:295)");
     if (topk == 0 || topk > RQ_MAX_TOPK) return fail(RQ_ERR_UNSUPPORTED, "topk must be in [1, 2048]");
     if (std::min(probe, idx->k) > RQ_MAX_PROBE) return fail(RQ_ERR_UNSUPPORTED, "probe > 16384 not supported");

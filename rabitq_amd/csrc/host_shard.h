@@ -45,7 +45,7 @@ rq_status rq_shard_index(const rq_index *idx, const uint32_t *owner, uint32_t ra
     noff[k] = (uint32_t)n_local;
     std::unique_ptr<rq_index> sh(new rq_index());
     sh->dim = dim, sh->k = k, sh->n = n_local, sh->W = idx->W;
-    sh->is_shard = true, sh->metric = idx->metric, sh->ip_d = idx->ip_d, sh->ip_S = idx->ip_S;
+    sh->is_shard = true, sh->metric = idx->metric;
     RQC(sh->P.alloc((size_t)dim * dim));
     RQC(sh->centroids.alloc((size_t)k * dim));
     RQC(sh->offsets.alloc((size_t)k + 1));
@@ -227,7 +227,8 @@ static rq_status sharded_step(rq_index *mi, void *nccl_comm, uint32_t world, uin
             }
         }
         uint32_t h = 0x9E3779B9u;
-        for (uint32_t v : {nq, len, probe, topk, world, (uint32_t)heuristic, (uint32_t)shared, mi->k, mi->dim, mi->metric, mi->ip_d, __builtin_bit_cast(uint32_t, mi->ip_S)}) h = (h ^ v) * 0x01000193u;
+        for (uint32_t v : {nq, len, probe, topk, world, (uint32_t)heuristic, (uint32_t)shared, mi->k, mi->dim}) h = (h ^ v) * 0x01000193u;
+        h = metric_hash(mi->metric, h);
         const int32_t hs = (int32_t)(h & 0x3FFFFFFFu);
         const int32_t hand[4] = {hs, -hs, err != RQ_OK ? 1 : 0, 0};
         // a local HIP failure here must not keep this rank out of the collective (its peers would block in it): it is folded into

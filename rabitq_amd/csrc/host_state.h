@@ -1,5 +1,6 @@
 // host_state.h -- part of the host side of librabitq_hip.so (one translation unit: rabitq_hip.hip includes the host_*.h files in order;
-// they are not stand-alone headers).  Errors, device buffers, metrics / profiling, the per-call workspace, struct rq_index, the process-global options and the kernel launch helpers.
+// they are not stand-alone headers).  Errors, device buffers, metrics / profiling, the per-call workspace, struct rq_index, the process-global options and the kernel launch helpers
+// (those of the metrics: host_metric.h).
 #pragma once
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -57,6 +58,11 @@ struct DevBuf {
         return RQ_OK;
     }
     rq_status ensure(size_t n) { return n <= count && p ? RQ_OK : alloc(n); }
+    rq_status upload(const T *host, size_t n) {  // a fresh allocation of n elements holding the host array (nothing is copied for n == 0)
+        if (rq_status s = alloc(n)) return s;
+        hipError_t e = n ? hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
+        return e == hipSuccess ? RQ_OK : fail(RQ_ERR_HIP, std::string("hipMemcpy to the device: ") + hipGetErrorString(e));
+    }
     void take(DevBuf &o) {  // this buffer becomes o's allocation (o is left empty)
         release();
         p = o.p, count = o.count;
@@ -245,15 +251,20 @@ struct Workspace {
     }
 };
 
+// The metric of an index (what it decides is in host_metric.h).  RQ_METRIC_COSINE: raw rows were normalised on their way in, raw
+// queries are on theirs.  RQ_METRIC_IP: rows of d floats were augmented (A(x; S), slot d = sqrtf(S - |x|^2)) on their way in, dim =
+// ceil64(d + 1); queries have exactly d floats and are zero-padded to dim by the ordinary pad path.  d and S are zero otherwise.
+struct MetricSpec {
+    uint32_t id = RQ_METRIC_L2;
+    uint32_t d = 0;
+    float S = 0.0f;
+};
+
 struct rq_index {
     uint32_t dim = 0, k = 0, W = 0, max_list_len = 0;
     uint32_t min_list_len = 0;  // 0 if some list is empty (then no slot bound can be derived from stream positions)
     uint64_t n = 0;
-    uint32_t metric = RQ_METRIC_L2;  // RQ_METRIC_COSINE: raw rows were normalised on their way in, raw queries are on theirs
-    // RQ_METRIC_IP: rows of ip_d floats were augmented (A(x; ip_S), slot ip_d = sqrtf(ip_S - |x|^2)) on their way in, dim =
-    // ceil64(ip_d + 1); queries have exactly ip_d floats and are zero-padded to dim by the ordinary pad path
-    uint32_t ip_d = 0;
-    float ip_S = 0.0f;
+    MetricSpec metric;
     // raw vectors (cluster order, un-rotated).  Untiered (n_dev == n, the usual case): row p at base + p*dim.  Tiered
     // (they do not fit the HBM budget): per list the first h_c members in HBM, the tail in pinned host memory mapped
     // into the device address space (BaseView / ListTier); n_dev = sum of h_c.
@@ -583,83 +594,6 @@ static void launch_rotate(const float *x, const float *P, float *out, uint64_t n
         }
     }
 }
-
-// Cosine metric: pad + normalise n rows of length d (normalize_rows_kernel).  place == nullptr: into the dense n x dim `out`;
-// else row r goes to position place[i0 + r] of `view` (the build's pass 2).  dim <= 4096.
-static bool metric_known(uint32_t metric) { return metric == RQ_METRIC_L2 || metric == RQ_METRIC_COSINE; }
-static void launch_normalize(const float *in, uint64_t n, uint32_t d, uint32_t dim, float *out, hipStream_t st,
-                             const uint32_t *place = nullptr, uint64_t i0 = 0, const BaseView view = BaseView{}) {
-    if (n == 0) return;
-    const uint32_t vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
-    const uint32_t rw = dim <= 512 ? 8 : dim <= 1024 ? 4 : dim <= 2048 ? 2 : 1;
-    const size_t lds = ((size_t)rw * (dim + 8) + rw) * sizeof(float);
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(ceil_div(n, rw), 256u * 10u * 8u);  // grid-stride: ten waves per CU, eight rounds
-#define RQ_NORM(RW) \
-    do { \
-        if (place) normalize_rows_kernel<RW, true><<<grid, 64, lds, st>>>(in, n, d, dim, vec, nullptr, place, i0, view); \
-        else normalize_rows_kernel<RW, false><<<grid, 64, lds, st>>>(in, n, d, dim, vec, out, nullptr, 0, view); \
-    } while (0)
-    switch (rw) {
-        case 8: RQ_NORM(8); break;
-        case 4: RQ_NORM(4); break;
-        case 2: RQ_NORM(2); break;
-        default: RQ_NORM(1); break;
-    }
-#undef RQ_NORM
-}
-
-// Inner-product metric.  metric_known stays the test of the *_metric entries (they take no d / S: RQ_METRIC_IP has the _ip entries).
-static uint32_t ip_dim(uint32_t d) { return (d + 1 + 63) / 64 * 64; }
-// the length a raw query or a raw added row of this index must have
-static bool raw_len_ok(const rq_index *idx, uint32_t len) {
-    return idx->metric == RQ_METRIC_IP ? len == idx->ip_d : (len != 0 && idx->dim == (len + 63) / 64 * 64);
-}
-static std::string metric_refusal(uint32_t metric) {
-    return "unknown metric " + std::to_string(metric) + (metric == RQ_METRIC_IP ? ": the inner-product metric takes a row length and a norm bound, use the _ip entries" : "");
-}
-struct SqnormLaunch {
-    uint32_t vec, rw, grid;
-    size_t lds;
-    SqnormLaunch(const float *in, const float *out, uint64_t n, uint32_t d, uint32_t dim) {
-        vec = d % 4 == 0 && (reinterpret_cast<uintptr_t>(in) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
-        rw = dim <= 512 ? 8 : dim <= 1024 ? 4 : dim <= 2048 ? 2 : 1;
-        lds = ((size_t)rw * (dim + 8) + rw) * sizeof(float);
-        grid = (uint32_t)std::min<uint64_t>(ceil_div(n, rw), 256u * 10u * 8u);  // as launch_normalize
-    }
-};
-// A(x; S) of n rows of d floats (augment_rows_kernel): dense into `out`, or (place) to position place[i0 + r] of `view`.
-// s_pre (nullable): s of row r at s_pre[i0 + r].  bad_row: one device word, preset to 0xFFFFFFFF by the caller.
-static void launch_augment(const float *in, uint64_t n, uint32_t d, uint32_t dim, float sq_bound, const float *s_pre, float *out,
-                           uint32_t *bad_row, hipStream_t st, const uint32_t *place = nullptr, uint64_t i0 = 0,
-                           const BaseView view = BaseView{}) {
-    if (n == 0) return;
-    const SqnormLaunch L(in, out, n, d, dim);
-#define RQ_AUG(RW) \
-    do { \
-        if (place) augment_rows_kernel<RW, true><<<L.grid, 64, L.lds, st>>>(in, n, d, dim, L.vec, sq_bound, s_pre, nullptr, place, i0, view, bad_row); \
-        else augment_rows_kernel<RW, false><<<L.grid, 64, L.lds, st>>>(in, n, d, dim, L.vec, sq_bound, s_pre, out, nullptr, i0, view, bad_row); \
-    } while (0)
-    switch (L.rw) {
-        case 8: RQ_AUG(8); break;
-        case 4: RQ_AUG(4); break;
-        case 2: RQ_AUG(2); break;
-        default: RQ_AUG(1); break;
-    }
-#undef RQ_AUG
-}
-// s of n rows (row_sqnorm_kernel); stat: three device words preset to {0, 0xFFFFFFFF, 0}; rows are numbered from i0 in stat[1]
-static void launch_row_sqnorm(const float *in, uint64_t n, uint32_t d, uint32_t dim, float sq_bound, uint64_t i0, float *out_s,
-                              uint32_t *stat, hipStream_t st) {
-    if (n == 0) return;
-    const SqnormLaunch L(in, nullptr, n, d, dim);
-    switch (L.rw) {
-        case 8: row_sqnorm_kernel<8><<<L.grid, 64, L.lds, st>>>(in, n, d, dim, L.vec, sq_bound, i0, out_s, stat); break;
-        case 4: row_sqnorm_kernel<4><<<L.grid, 64, L.lds, st>>>(in, n, d, dim, L.vec, sq_bound, i0, out_s, stat); break;
-        case 2: row_sqnorm_kernel<2><<<L.grid, 64, L.lds, st>>>(in, n, d, dim, L.vec, sq_bound, i0, out_s, stat); break;
-        default: row_sqnorm_kernel<1><<<L.grid, 64, L.lds, st>>>(in, n, d, dim, L.vec, sq_bound, i0, out_s, stat); break;
-    }
-}
-static const uint32_t RQ_SQNORM_STAT_INIT[3] = {0u, 0xFFFFFFFFu, 0u};
 
 // ------------------------------------------------------------------------------------------------
 // scan dispatch on W = dim / 64

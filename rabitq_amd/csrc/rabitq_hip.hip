@@ -34,6 +34,7 @@
 #include "kernels_small.h"
 
 #include "host_state.h"
+#include "host_metric.h"
 #include "host_plan.h"
 #include "host_query.h"
 #include "host_range.h"
@@ -100,145 +101,69 @@ rq_status rq_kmeans_device(const float *d_base, uint64_t n, uint32_t d, uint32_t
     return RQ_OK;
 }
 
-// ---- cosine metric: N(x) on its own (the build, rq_add and every query pass run the same kernel) ----
+// ---- the row transforms on their own (the builds, rq_add and every query pass run the same kernels) ----
+static rq_status normalize_d_check(uint32_t d) {
+    if (d == 0) return fail(RQ_ERR_INVALID, "d == 0");
+    return d <= 4096 ? RQ_OK : fail(RQ_ERR_UNSUPPORTED, "dim > 4096 not supported");
+}
 rq_status rq_normalize_device(const float *d_x, uint64_t n, uint32_t d, float *d_out) {
     RQC(ensure_device());
     if (n && (!d_x || !d_out)) return fail(RQ_ERR_INVALID, "null argument");
-    if (d == 0) return fail(RQ_ERR_INVALID, "d == 0");
-    const uint32_t dim = (d + 63) / 64 * 64;
-    if (dim > 4096) return fail(RQ_ERR_UNSUPPORTED, "dim > 4096 not supported");
-    for (uint64_t r0 = 0; r0 < n; r0 += RQ_BUILD_CHUNK)  // (row offsets of a chunk keep the 16-byte alignment of the whole)
-        launch_normalize(d_x + r0 * d, std::min<uint64_t>(RQ_BUILD_CHUNK, n - r0), d, dim, d_out + r0 * dim, nullptr);
-    HIPC(hipDeviceSynchronize());
-    HIPC(hipGetLastError());
-    return RQ_OK;
+    RQC(normalize_d_check(d));
+    return transform_all_rows(MetricSpec{RQ_METRIC_COSINE}, ceil64(d), d_x, n, d, nullptr, nullptr, d_out);
 }
 rq_status rq_normalize(const float *x, uint64_t n, uint32_t d, float *out) {
-    RQC(ensure_device());
-    if (n && (!x || !out)) return fail(RQ_ERR_INVALID, "null argument");
-    if (d == 0) return fail(RQ_ERR_INVALID, "d == 0");
-    const uint32_t dim = (d + 63) / 64 * 64;
-    if (dim > 4096) return fail(RQ_ERR_UNSUPPORTED, "dim > 4096 not supported");
-    if (n == 0) return RQ_OK;
-    DevBuf<float> dx, dout;
-    RQC(dx.alloc(n * d));
-    RQC(dout.alloc(n * dim));
-    HIPC(hipMemcpy(dx.p, x, n * d * 4, hipMemcpyHostToDevice));
-    RQC(rq_normalize_device(dx.p, n, d, dout.p));
-    HIPC(hipMemcpy(out, dout.p, n * dim * 4, hipMemcpyDeviceToHost));
-    return RQ_OK;
+    return with_staged_rows(x, n, d, out, ceil64(d), normalize_d_check(d), [&](const float *dx, float *dout) { return rq_normalize_device(dx, n, d, dout); });
 }
 
-rq_status rq_build_device_metric(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
-                                 const float *orthogonal_host, uint64_t seed, uint32_t metric, rq_index **out) {
-    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, metric_refusal(metric));
-    return build_device(d_base, n, d, d_centroids, k, orthogonal_host, seed, metric, out);
-}
-
-// ---- inner-product metric: the builds, A(x; S), the largest s and the two conversions ----
-rq_status rq_build_device_ip(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
-                             const float *orthogonal_host, uint64_t seed, uint32_t centroid_cols, float sq_bound, rq_index **out) {
-    return build_device_ip(d_base, n, d, d_centroids, k, orthogonal_host, seed, centroid_cols, sq_bound, out);
-}
-rq_status rq_build_ip(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k, const float *orthogonal,
-                      uint64_t seed, uint32_t centroid_cols, float sq_bound, rq_index **out) {
-    RQC(ensure_device());
-    if (out) *out = nullptr;
-    if ((n && !base) || !centroids) return fail(RQ_ERR_INVALID, "null argument");
-    if (d == 0 || d > 4095) return fail(d ? RQ_ERR_UNSUPPORTED : RQ_ERR_INVALID, "d must be in [1, 4095]");
-    if (centroid_cols < d || centroid_cols > ip_dim(d)) return fail(RQ_ERR_INVALID, "centroid_cols outside [d, ceil64(d + 1)]");
-    DevBuf<float> db, dc;
-    RQC(db.alloc(n * d));
-    RQC(dc.alloc((size_t)k * centroid_cols));
-    if (n) HIPC(hipMemcpy(db.p, base, n * d * 4, hipMemcpyHostToDevice));
-    if (k) HIPC(hipMemcpy(dc.p, centroids, (size_t)k * centroid_cols * 4, hipMemcpyHostToDevice));
-    return build_device_ip(db.p, n, d, dc.p, k, orthogonal, seed, centroid_cols, sq_bound, out);
-}
-rq_status rq_build_from_path_ip(const char *base_fvecs, const char *centroid_fvecs, const float *orthogonal, uint64_t seed,
-                                float sq_bound, rq_index **out) {
-    if (!base_fvecs || !centroid_fvecs) return fail(RQ_ERR_INVALID, "null path");
-    VecsFile b, c;
-    RQC(read_vecs_file(base_fvecs, 4, b));
-    RQC(read_vecs_file(centroid_fvecs, 4, c));
-    if (b.lens.empty() || c.lens.empty()) return fail(RQ_ERR_IO, "empty fvecs file");
-    const uint32_t d = b.lens[0], cc = c.lens[0];
-    for (uint32_t l : b.lens)
-        if (l != d) return fail(RQ_ERR_IO, "ragged base.fvecs");
-    for (uint32_t l : c.lens)
-        if (l != cc) return fail(RQ_ERR_IO, "ragged centroids.fvecs");
-    if (d == 0 || d > 4095 || cc < d || cc > ip_dim(d)) return fail(RQ_ERR_DIM_MISMATCH, "centroid records must hold between d and ceil64(d + 1) values");
-    return rq_build_ip(reinterpret_cast<const float *>(b.data.data()), b.lens.size(), d,
-                       reinterpret_cast<const float *>(c.data.data()), (uint32_t)c.lens.size(), orthogonal, seed, cc, sq_bound, out);
-}
+// ---- inner-product metric: A(x; S), the largest s and the two conversions ----
 rq_status rq_ip_params(const rq_index *idx, uint32_t *d, float *sq_bound) {
     if (!idx || !d || !sq_bound) return fail(RQ_ERR_INVALID, "null argument");
-    if (idx->metric != RQ_METRIC_IP) return fail(RQ_ERR_INVALID, "not an inner-product index");
-    *d = idx->ip_d, *sq_bound = idx->ip_S;
+    if (idx->metric.id != RQ_METRIC_IP) return fail(RQ_ERR_INVALID, "not an inner-product index");
+    *d = idx->metric.d, *sq_bound = idx->metric.S;
     return RQ_OK;
 }
 rq_status rq_row_sqnorm_max_device(const float *d_x, uint64_t n, uint32_t d, float *out_max) {
     RQC(ensure_device());
     if ((n && !d_x) || !out_max) return fail(RQ_ERR_INVALID, "null argument");
     if (d == 0 || d > 4096) return fail(d ? RQ_ERR_UNSUPPORTED : RQ_ERR_INVALID, "d must be in [1, 4096]");
-    uint32_t bad = 0xFFFFFFFFu;
-    RQC(row_sqnorms(d_x, n, d, (d + 63) / 64 * 64, __builtin_inff(), nullptr, out_max, &bad));
-    if (bad != 0xFFFFFFFFu) return fail(RQ_ERR_INVALID, "row " + std::to_string(bad) + ": its squared norm is not finite");
-    return RQ_OK;
+    uint32_t bad = RQ_NO_BAD_ROW;
+    RQC(row_sqnorms(d_x, n, d, ceil64(d), __builtin_inff(), nullptr, out_max, &bad));
+    return bad_row_refusal(bad, ":", nullptr);
 }
 rq_status rq_row_sqnorm_max(const float *x, uint64_t n, uint32_t d, float *out_max) {
-    RQC(ensure_device());
-    if ((n && !x) || !out_max) return fail(RQ_ERR_INVALID, "null argument");
-    DevBuf<float> dx;
-    RQC(dx.alloc(n * d));
-    if (n && d) HIPC(hipMemcpy(dx.p, x, n * d * 4, hipMemcpyHostToDevice));
-    return rq_row_sqnorm_max_device(dx.p, n, d, out_max);
+    return with_staged_rows(x, n, d, nullptr, 0, RQ_OK, [&](const float *dx, float *) { return rq_row_sqnorm_max_device(dx, n, d, out_max); });
 }
 rq_status rq_augment_device(const float *d_x, uint64_t n, uint32_t d, float sq_bound, float *d_out) {
     RQC(ensure_device());
     if (n && (!d_x || !d_out)) return fail(RQ_ERR_INVALID, "null argument");
-    if (d == 0 || d > 4095) return fail(d ? RQ_ERR_UNSUPPORTED : RQ_ERR_INVALID, "d must be in [1, 4095]");
-    const uint32_t dim = ip_dim(d);
+    RQC(ip_d_check(d));
     DevBuf<float> s;
     DevBuf<uint32_t> bad;
     RQC(s.alloc(n));
     RQC(bad.alloc(1));
     RQC(ip_resolve_bound(d_x, n, d, &sq_bound, s.p));  // (every row is valid from here on)
-    HIPC(hipMemset(bad.p, 0xFF, 4));
-    for (uint64_t r0 = 0; r0 < n; r0 += RQ_BUILD_CHUNK)
-        launch_augment(d_x + r0 * d, std::min<uint64_t>(RQ_BUILD_CHUNK, n - r0), d, dim, sq_bound, s.p, d_out + r0 * dim, bad.p, nullptr, nullptr, r0);
-    HIPC(hipDeviceSynchronize());
-    HIPC(hipGetLastError());
-    return RQ_OK;
+    return transform_all_rows(metric_ip(d, sq_bound), ceil64(d + 1), d_x, n, d, s.p, bad.p, d_out);
 }
 rq_status rq_augment(const float *x, uint64_t n, uint32_t d, float sq_bound, float *out) {
-    RQC(ensure_device());
-    if (n && (!x || !out)) return fail(RQ_ERR_INVALID, "null argument");
-    if (d == 0 || d > 4095) return fail(d ? RQ_ERR_UNSUPPORTED : RQ_ERR_INVALID, "d must be in [1, 4095]");
-    DevBuf<float> dx, dout;
-    RQC(dx.alloc(n * d));
-    RQC(dout.alloc(n * ip_dim(d)));
-    if (n) HIPC(hipMemcpy(dx.p, x, n * d * 4, hipMemcpyHostToDevice));
-    RQC(rq_augment_device(dx.p, n, d, sq_bound, dout.p));
-    if (n) HIPC(hipMemcpy(out, dout.p, n * ip_dim(d) * 4, hipMemcpyDeviceToHost));
-    return RQ_OK;
+    return with_staged_rows(x, n, d, out, ceil64(d + 1), ip_d_check(d), [&](const float *dx, float *dout) { return rq_augment_device(dx, n, d, sq_bound, dout); });
 }
 // s_q of the queries of an inner-product index (row_sqnorm_kernel over Q(q)), then one of the two conversions
 static rq_status ip_convert(const rq_index *idx, const float *d_q, uint32_t nq, uint32_t len, const float *d_in, uint32_t topk,
                             const uint32_t *d_n, float *d_out, bool radius) {
     RQC(ensure_device());
     if (!idx || (nq && (!d_q || !d_in || !d_out))) return fail(RQ_ERR_INVALID, "null argument");
-    if (idx->metric != RQ_METRIC_IP) return fail(RQ_ERR_INVALID, "not an inner-product index");
-    if (len != idx->ip_d) return fail(RQ_ERR_DIM_MISMATCH, "query length is not the inner-product index's row length");
+    if (idx->metric.id != RQ_METRIC_IP) return fail(RQ_ERR_INVALID, "not an inner-product index");
+    RQC(raw_len_check(idx, "query", len));
     if (!radius && topk == 0) return fail(RQ_ERR_INVALID, "topk == 0");
     if (nq == 0) return RQ_OK;
     DevBuf<float> sq;
     DevBuf<uint32_t> stat;
     RQC(sq.alloc(nq));
-    RQC(stat.alloc(3));
-    HIPC(hipMemcpy(stat.p, RQ_SQNORM_STAT_INIT, 12, hipMemcpyHostToDevice));
+    RQC(stat.upload(RQ_SQNORM_STAT_INIT, 3));
     launch_row_sqnorm(d_q, nq, len, idx->dim, __builtin_inff(), 0, sq.p, stat.p, nullptr);
-    if (radius) ip_radius_kernel<<<ceil_div(nq, 256), 256>>>(d_in, sq.p, idx->ip_S, nq, d_out);
-    else ip_from_dist_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div((uint64_t)nq * topk, 256), 1u << 20), 256>>>(d_in, sq.p, d_n, idx->ip_S, nq, topk, d_out);
+    if (radius) ip_radius_kernel<<<ceil_div(nq, 256), 256>>>(d_in, sq.p, idx->metric.S, nq, d_out);
+    else ip_from_dist_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div((uint64_t)nq * topk, 256), 1u << 20), 256>>>(d_in, sq.p, d_n, idx->metric.S, nq, topk, d_out);
     HIPC(hipDeviceSynchronize());
     HIPC(hipGetLastError());
     return RQ_OK;
@@ -250,15 +175,10 @@ static rq_status ip_convert_host(const rq_index *idx, const float *q, uint32_t n
     const uint64_t cells = radius ? nq : (uint64_t)nq * topk;
     DevBuf<float> dq, din, dout;
     DevBuf<uint32_t> dn;
-    RQC(dq.alloc((uint64_t)nq * len));
-    RQC(din.alloc(cells));
+    RQC(dq.upload(q, (uint64_t)nq * len));
+    RQC(din.upload(in, cells));
     RQC(dout.alloc(cells));
-    if (nq && len) HIPC(hipMemcpy(dq.p, q, (uint64_t)nq * len * 4, hipMemcpyHostToDevice));
-    if (cells) HIPC(hipMemcpy(din.p, in, cells * 4, hipMemcpyHostToDevice));
-    if (n && nq) {
-        RQC(dn.alloc(nq));
-        HIPC(hipMemcpy(dn.p, n, (uint64_t)nq * 4, hipMemcpyHostToDevice));
-    }
+    if (n) RQC(dn.upload(n, nq));
     RQC(ip_convert(idx, dq.p, nq, len, din.p, topk, n ? dn.p : nullptr, dout.p, radius));
     if (cells) HIPC(hipMemcpy(out, dout.p, cells * 4, hipMemcpyDeviceToHost));
     return RQ_OK;
@@ -278,24 +198,36 @@ rq_status rq_ip_radius_device(const rq_index *idx, const float *d_queries, uint3
 rq_status rq_ip_radius(const rq_index *idx, const float *queries, uint32_t nq, uint32_t len, const float *min_ip, float *out_radius) {
     return ip_convert_host(idx, queries, nq, len, min_ip, 1, nullptr, out_radius, true);
 }
+
+// ---- the builds: every entry forwards to build_device / build_host / build_from_path / builder_create / from_arrays with its MetricSpec ----
+// (the *_metric entries take no d / S: they refuse RQ_METRIC_IP, and any id they do not know, before anything else)
 rq_status rq_build_device(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
                           const float *orthogonal_host, uint64_t seed, rq_index **out) {
-    return build_device(d_base, n, d, d_centroids, k, orthogonal_host, seed, RQ_METRIC_L2, out);
+    return build_device(d_base, n, d, d_centroids, k, d, orthogonal_host, seed, MetricSpec{}, out);
+}
+rq_status rq_build_device_metric(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
+                                 const float *orthogonal_host, uint64_t seed, uint32_t metric, rq_index **out) {
+    RQC(metric_entry_check(metric));
+    return build_device(d_base, n, d, d_centroids, k, d, orthogonal_host, seed, MetricSpec{metric}, out);
+}
+rq_status rq_build_device_ip(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
+                             const float *orthogonal_host, uint64_t seed, uint32_t centroid_cols, float sq_bound, rq_index **out) {
+    return build_device(d_base, n, d, d_centroids, k, centroid_cols, orthogonal_host, seed, metric_ip(d, sq_bound), out);
 }
 
+rq_status rq_builder_create(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
+                            uint64_t seed, uint64_t max_device_base_bytes, rq_builder **out) {
+    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, MetricSpec{}, d, out);
+}
 rq_status rq_builder_create_metric(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
                                    uint64_t seed, uint64_t max_device_base_bytes, uint32_t metric, rq_builder **out) {
-    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, metric_refusal(metric));
-    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, metric, out);
+    RQC(metric_entry_check(metric));
+    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, MetricSpec{metric}, d, out);
 }
 rq_status rq_builder_create_ip(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
                                uint64_t seed, uint64_t max_device_base_bytes, uint32_t centroid_cols, float sq_bound,
                                rq_builder **out) {
-    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, RQ_METRIC_IP, out, centroid_cols, sq_bound);
-}
-rq_status rq_builder_create(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
-                            uint64_t seed, uint64_t max_device_base_bytes, rq_builder **out) {
-    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, RQ_METRIC_L2, out);
+    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, metric_ip(d, sq_bound), centroid_cols, out);
 }
 rq_status rq_builder_assign_chunk(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m) { return builder_assign(b, d_rows, i0, m); }
 rq_status rq_builder_order(rq_builder *b) { return builder_order(b); }
@@ -307,60 +239,49 @@ rq_status rq_builder_stats(const rq_builder *b, rq_build_stats_t *out) {
     return copy_out_sized(out, b->stats);
 }
 
-rq_status rq_build_metric(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k,
-                          const float *orthogonal, uint64_t seed, uint32_t metric, rq_index **out) {
-    RQC(ensure_device());
-    if ((n && !base) || !centroids) return fail(RQ_ERR_INVALID, "null argument");
-    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, metric_refusal(metric));
-    DevBuf<float> db, dc;
-    RQC(db.alloc(n * d));
-    RQC(dc.alloc((size_t)k * d));
-    if (n) HIPC(hipMemcpy(db.p, base, n * d * 4, hipMemcpyHostToDevice));
-    if (k) HIPC(hipMemcpy(dc.p, centroids, (size_t)k * d * 4, hipMemcpyHostToDevice));
-    return build_device(db.p, n, d, dc.p, k, orthogonal, seed, metric, out);
-}
 rq_status rq_build(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k,
                    const float *orthogonal, uint64_t seed, rq_index **out) {
-    return rq_build_metric(base, n, d, centroids, k, orthogonal, seed, RQ_METRIC_L2, out);
+    return build_host(base, n, d, centroids, k, d, orthogonal, seed, MetricSpec{}, out);
+}
+rq_status rq_build_metric(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k,
+                          const float *orthogonal, uint64_t seed, uint32_t metric, rq_index **out) {
+    RQC(metric_entry_check(metric));
+    return build_host(base, n, d, centroids, k, d, orthogonal, seed, MetricSpec{metric}, out);
+}
+rq_status rq_build_ip(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k, const float *orthogonal,
+                      uint64_t seed, uint32_t centroid_cols, float sq_bound, rq_index **out) {
+    return build_host(base, n, d, centroids, k, centroid_cols, orthogonal, seed, metric_ip(d, sq_bound), out);
 }
 
-rq_status rq_build_from_path_metric(const char *base_fvecs, const char *centroid_fvecs, const float *orthogonal,
-                                    uint64_t seed, uint32_t metric, rq_index **out) {
-    if (!base_fvecs || !centroid_fvecs) return fail(RQ_ERR_INVALID, "null path");
-    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, metric_refusal(metric));
-    VecsFile b, c;
-    RQC(read_vecs_file(base_fvecs, 4, b));      // rabitq.rs:160
-    RQC(read_vecs_file(centroid_fvecs, 4, c));  // :163
-    if (b.lens.empty() || c.lens.empty()) return fail(RQ_ERR_IO, "empty fvecs file");
-    uint32_t d = b.lens[0];
-    if (c.lens[0] != d) return fail(RQ_ERR_DIM_MISMATCH, "base and centroid dimensions differ (rabitq.rs:165)");
-    for (uint32_t l : b.lens)
-        if (l != d) return fail(RQ_ERR_IO, "ragged base.fvecs");
-    for (uint32_t l : c.lens)
-        if (l != d) return fail(RQ_ERR_IO, "ragged centroids.fvecs");
-    return rq_build_metric(reinterpret_cast<const float *>(b.data.data()), b.lens.size(), d,
-                           reinterpret_cast<const float *>(c.data.data()), (uint32_t)c.lens.size(), orthogonal, seed, metric, out);
-}
 rq_status rq_build_from_path(const char *base_fvecs, const char *centroid_fvecs, const float *orthogonal,
                              uint64_t seed, rq_index **out) {
-    return rq_build_from_path_metric(base_fvecs, centroid_fvecs, orthogonal, seed, RQ_METRIC_L2, out);
+    return build_from_path(base_fvecs, centroid_fvecs, orthogonal, seed, MetricSpec{}, out);
+}
+rq_status rq_build_from_path_metric(const char *base_fvecs, const char *centroid_fvecs, const float *orthogonal,
+                                    uint64_t seed, uint32_t metric, rq_index **out) {
+    RQC(metric_entry_check(metric));
+    return build_from_path(base_fvecs, centroid_fvecs, orthogonal, seed, MetricSpec{metric}, out);
+}
+rq_status rq_build_from_path_ip(const char *base_fvecs, const char *centroid_fvecs, const float *orthogonal, uint64_t seed,
+                                float sq_bound, rq_index **out) {
+    return build_from_path(base_fvecs, centroid_fvecs, orthogonal, seed, metric_ip(0, sq_bound), out);  // (d: the base file's record length)
 }
 
 rq_status rq_from_arrays(uint32_t dim, uint64_t n, uint32_t k, const float *base, const float *orthogonal,
                          const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
                          const uint64_t *codes, const rq_factor_t *factors, rq_index **out) {
-    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, RQ_METRIC_L2, out);
+    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, MetricSpec{}, out);
 }
 rq_status rq_from_arrays_metric(uint32_t dim, uint64_t n, uint32_t k, const float *base, const float *orthogonal,
                                 const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
                                 const uint64_t *codes, const rq_factor_t *factors, uint32_t metric, rq_index **out) {
-    if (!metric_known(metric)) return fail(RQ_ERR_INVALID, metric_refusal(metric));
-    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, metric, out);
+    RQC(metric_entry_check(metric));
+    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, MetricSpec{metric}, out);
 }
 rq_status rq_from_arrays_ip(uint32_t dim, uint64_t n, uint32_t k, const float *base, const float *orthogonal,
                             const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
                             const uint64_t *codes, const rq_factor_t *factors, uint32_t d, float sq_bound, rq_index **out) {
-    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, RQ_METRIC_IP, out, d, sq_bound);
+    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, metric_ip(d, sq_bound), out);
 }
 
 // rabitq.rs:84-125
@@ -374,28 +295,17 @@ rq_status rq_load_dir(const char *dir, rq_index **out) {
     RQC(read_vecs_file(d + "/factors.fvecs", 4, fac));
     RQC(read_vecs_file(d + "/x_binary_vec.u64vecs", 8, bin));
     RQC(read_vecs_file(d + "/base.fvecs", 4, base));
-    uint32_t metric = RQ_METRIC_L2, ip_d = 0;  // the sixth file of a cosine or inner-product index's dump
-    float ip_S = 0.0f;
+    MetricSpec metric;  // the sixth file of a cosine or inner-product index's dump
     if (FILE *mf = fopen((d + "/metric").c_str(), "rb")) {
         char buf[32] = {0};
         const size_t got = fread(buf, 1, sizeof buf - 1, mf);
         fclose(mf);
-        const std::string text(buf, got);
-        if (text == "cosine\n") metric = RQ_METRIC_COSINE;
-        else if (text.compare(0, 3, "ip ") == 0) {  // "ip <d> <S as 8 hex digits>\n", exactly as rq_dump_dir writes it
-            unsigned pd = 0, bits = 0;
-            char canon[32];
-            if (sscanf(text.c_str(), "ip %u %8x", &pd, &bits) != 2) return fail(RQ_ERR_IO, "metric: malformed content in " + d + "/metric");
-            snprintf(canon, sizeof canon, "ip %u %08x\n", pd, bits);
-            if (text != canon) return fail(RQ_ERR_IO, "metric: malformed content in " + d + "/metric");
-            metric = RQ_METRIC_IP, ip_d = pd;
-            memcpy(&ip_S, &bits, 4);
-            if (ip_d == 0 || ip_d > 4095 || !(ip_S >= 0.0f && ip_S <= 3.402823466e+38f)) return fail(RQ_ERR_IO, "metric: malformed content in " + d + "/metric");
-        } else if (text != "l2\n") return fail(RQ_ERR_IO, "metric: unknown content in " + d + "/metric");
+        if (!metric_from_file_text(std::string(buf, got), &metric)) return fail(RQ_ERR_IO, "metric: unknown or malformed content in " + d + "/metric");
     }
     const uint32_t dim = (uint32_t)ortho.lens.size();  // :108 dim = orthogonal.nrows()
     if (dim == 0 || dim % 64 != 0) return fail(RQ_ERR_DIM_MISMATCH, "orthogonal.fvecs: dim % 64 != 0 (rabitq.rs:109)");
-    if (metric == RQ_METRIC_IP && ip_dim(ip_d) != dim) return fail(RQ_ERR_IO, "metric: d does not belong to the index's dim in " + d + "/metric");
+    if (metric.id == RQ_METRIC_IP && !(ip_d_ok(metric.d, dim) && ip_bound_ok(metric.S)))
+        return fail(RQ_ERR_IO, "metric: no valid d and bound of an inner-product index of this dim in " + d + "/metric");
     if (cent.lens.size() != dim || oi.lens.size() != 2) return fail(RQ_ERR_IO, "malformed index directory");
     const uint32_t k = cent.lens[0];
     // every record length is checked before anything is indexed by it (the reference's matrix_from_fvecs panics on
@@ -426,7 +336,7 @@ rq_status rq_load_dir(const char *dir, rq_index **out) {
     return from_arrays(dim, n, k, reinterpret_cast<const float *>(base.data.data()),
                        reinterpret_cast<const float *>(ortho.data.data()), c.data(), oip, oip + (total - last),
                        reinterpret_cast<const uint64_t *>(bin.data.data()),
-                       reinterpret_cast<const rq_factor_t *>(fac.data.data()), metric, out, ip_d, ip_S);
+                       reinterpret_cast<const rq_factor_t *>(fac.data.data()), metric, out);
 }
 
 rq_status rq_get_array(const rq_index *idx, int which, void *dst, uint64_t dst_bytes);
@@ -500,11 +410,10 @@ rq_status rq_dump_dir(const rq_index *idx, const char *dir) {
     s = write_record(f, codes.data(), (uint32_t)(n * (dim / 64)), 8, "x_binary_vec.u64vecs");
     fclose(f);
     RQC(s);
-    if (idx->metric != RQ_METRIC_L2) {  // (an L2 dump stays the crate's five files)
+    const std::string tag = metric_file_text(idx->metric);
+    if (!tag.empty()) {  // (an L2 dump stays the crate's five files)
         RQC(open("metric", &f));
-        char text[32] = "cosine\n";
-        if (idx->metric == RQ_METRIC_IP) snprintf(text, sizeof text, "ip %u %08x\n", idx->ip_d, __builtin_bit_cast(uint32_t, idx->ip_S));
-        const bool ok = fputs(text, f) >= 0;
+        const bool ok = fputs(tag.c_str(), f) >= 0;
         if (fclose(f) != 0 || !ok) return fail(RQ_ERR_IO, "write error on " + d + "/metric");
     } else {
         remove((d + "/metric").c_str());  // (a directory that held a cosine dump before)
@@ -557,12 +466,7 @@ rq_status rq_dump_json(const rq_index *idx, const char *path) {
         o.raw(",\"center_distance_square\":"), o.f32(fac[4 * i + 3]), o.raw("}");
     }
     o.raw("]");
-    if (idx->metric == RQ_METRIC_IP) {
-        const std::string m = ",\"metric\":\"ip\",\"ip_d\":" + std::to_string(idx->ip_d) + ",\"ip_sq_bound_bits\":" +
-                              std::to_string(__builtin_bit_cast(uint32_t, idx->ip_S));
-        o.raw(m.c_str());
-    }
-    if (idx->metric == RQ_METRIC_COSINE) o.raw(",\"metric\":\"cosine\"");  // (an unknown member to the reference's serde derive: ignored)
+    o.raw(metric_json_members(idx->metric).c_str());
     o.raw("}");
     const bool closed = fclose(f) == 0;
     if (!o.ok || !closed) return fail(RQ_ERR_IO, std::string("write error on ") + path);
@@ -587,7 +491,7 @@ rq_status rq_load_json(const char *path, rq_index **out) {
     std::vector<unsigned long long> off, ids, codes;
     std::vector<rq_factor_t> fac;
     std::string metric_name;
-    unsigned long long ip_d = 0, ip_bits = 1ull << 32;  // members of an inner-product index (the preset: absent)
+    unsigned long long ip_d = 1ull << 32, ip_bits = 1ull << 32;  // members of an inner-product index (the preset: absent)
     bool good = in.need('{');
     if (good && !in.lit('}')) {
         do {
@@ -627,22 +531,16 @@ rq_status rq_load_json(const char *path, rq_index **out) {
         good = good && in.need('}');
     }
     if (!good) return fail(RQ_ERR_IO, std::string("deserialize error in ") + path + (in.err.empty() ? "" : ": " + in.err));
-    uint32_t metric = RQ_METRIC_L2;
-    float ip_S = 0.0f;
-    if (metric_name == "\"cosine\"") metric = RQ_METRIC_COSINE;
-    else if (metric_name == "\"ip\"") {
-        const uint32_t bits = (uint32_t)ip_bits;
-        memcpy(&ip_S, &bits, 4);
-        if (ip_d == 0 || ip_d > 4095 || ip_bits >> 32 || !(ip_S >= 0.0f && ip_S <= 3.402823466e+38f))
-            return fail(RQ_ERR_IO, std::string("inner-product index without a valid ip_d / ip_sq_bound_bits in ") + path);
-        metric = RQ_METRIC_IP;
-    } else if (!metric_name.empty() && metric_name != "\"l2\"") return fail(RQ_ERR_IO, std::string("unknown metric ") + metric_name + " in " + path);
+    MetricSpec metric;
+    if (!metric_from_json(metric_name, ip_d, ip_bits, &metric))
+        return fail(RQ_ERR_IO, std::string("unknown metric ") + metric_name + ", or an inner-product index without its ip_d / ip_sq_bound_bits, in " + path);
     const uint64_t n = ids.size(), k = off.empty() ? 0 : off.size() - 1;
     if (dim == 0 || dim % 64 || pr != dim || pc != dim || P.size() != dim * dim || br != dim || bc != n || base.size() != dim * n ||
         cr != dim || cc != k || cent.size() != dim * k || off.empty() || fac.size() != n || codes.size() != n * (dim / 64) ||
         off.back() != n)
         return fail(RQ_ERR_IO, std::string("inconsistent index in ") + path);
-    if (metric == RQ_METRIC_IP && ip_dim((uint32_t)ip_d) != dim) return fail(RQ_ERR_IO, std::string("ip_d does not belong to dim in ") + path);
+    if (metric.id == RQ_METRIC_IP && !(ip_d_ok(metric.d, (uint32_t)dim) && ip_bound_ok(metric.S)))
+        return fail(RQ_ERR_IO, std::string("no valid ip_d / ip_sq_bound_bits of an inner-product index of this dim in ") + path);
     for (uint64_t j = 0; j + 1 < off.size(); ++j)
         if (off[j] > off[j + 1]) return fail(RQ_ERR_IO, "offsets are not non-decreasing");
     // Mat (dim x cols, row-major sequence) -> one vector per row
@@ -654,7 +552,7 @@ rq_status rq_load_json(const char *path, rq_index **out) {
     std::vector<uint32_t> off32(off.begin(), off.end()), ids32(ids.begin(), ids.end());
     std::vector<uint64_t> codes64(codes.begin(), codes.end());
     return from_arrays((uint32_t)dim, n, (uint32_t)k, base_rows.data(), P.data(), cent_rows.data(), off32.data(), ids32.data(),
-                       codes64.data(), fac.data(), metric, out, (uint32_t)ip_d, ip_S);
+                       codes64.data(), fac.data(), metric, out);
 }
 
 void rq_free(rq_index *idx) { delete idx; }
@@ -663,7 +561,7 @@ rq_status rq_info(const rq_index *idx, rq_info_t *out) {
     if (!idx || !out) return fail(RQ_ERR_INVALID, "null argument");
     rq_info_t full{};
     full.dim = idx->dim, full.k = idx->k, full.n = idx->n, full.max_list_len = idx->max_list_len, full.n_hbm = idx->n_dev;
-    full.split_rows = idx->split_rows ? 1u : 0u, full.metric = idx->metric;
+    full.split_rows = idx->split_rows ? 1u : 0u, full.metric = idx->metric.id;
     return copy_out_sized(out, full);
 }
 
@@ -706,7 +604,7 @@ rq_status rq_coarse_topk_device(const rq_index *idx, const float *d_queries, uin
                                 float *d_out_dist) {
     RQC(ensure_device());
     if (!idx || !d_queries || !d_out_cluster || !d_out_dist) return fail(RQ_ERR_INVALID, "null argument");
-    if (!raw_len_ok(idx, len)) return fail(RQ_ERR_DIM_MISMATCH, "query length does not pad to dim (an inner-product index: is not its row length)");
+    RQC(raw_len_check(idx, "query", len));
     if (probe == 0 || list_lo >= list_hi || list_hi > idx->k) return fail(RQ_ERR_INVALID, "bad list range / probe");
     if (probe > RQ_MAX_PROBE) return fail(RQ_ERR_UNSUPPORTED, "probe > 16384");
     if (nq == 0) return RQ_OK;
@@ -723,18 +621,10 @@ rq_status rq_coarse_topk_device(const rq_index *idx, const float *d_queries, uin
     const uint32_t chunk = (uint32_t)std::min<uint64_t>(nq, std::max<uint64_t>(1024, (1ull << 31) / std::max(kc, idx->k)));
     RQC(ws->y.ensure((uint64_t)chunk * dim));
     RQC(ws->dist.ensure((uint64_t)chunk * std::max(kc, idx->k)));
-    const bool cosine = idx->metric == RQ_METRIC_COSINE;
-    if (len != dim || cosine) RQC(ws->qpad.ensure((uint64_t)chunk * dim));
     for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
         const uint32_t m = std::min(chunk, nq - q0);
-        const float *qp = d_queries + (uint64_t)q0 * len;
-        if (cosine) {
-            launch_normalize(qp, m, len, dim, ws->qpad.p, st);
-            qp = ws->qpad.p;
-        } else if (len != dim) {
-            pad_rows_kernel<<<ceil_div((uint64_t)m * dim, 256), 256, 0, st>>>(qp, ws->qpad.p, m, len, dim);
-            qp = ws->qpad.p;
-        }
+        const float *qp;  // (the first chunk is the largest: the scratch buffer is sized once)
+        RQC(transform_queries(idx, d_queries + (uint64_t)q0 * len, m, len, /*want_padded=*/true, ws->qpad, st, &qp));
         launch_rotate(qp, idx->P.p, ws->y.p, m, dim, m >= 32, st);
         if (kc == idx->k && coarse_prefilter_applies(idx, m, np)) {
             RQC(ws->coarse_redo.ensure(m));
@@ -1201,11 +1091,9 @@ rq_status rq_rotate(const float *x, uint64_t n, uint32_t dim, const float *ortho
     if (!x || !orthogonal || !out) return fail(RQ_ERR_INVALID, "null argument");
     if (dim == 0 || dim % 64) return fail(RQ_ERR_DIM_MISMATCH, "dim must be a multiple of 64");
     DevBuf<float> dx, dp, dout;
-    RQC(dx.alloc(n * dim));
-    RQC(dp.alloc((size_t)dim * dim));
+    RQC(dx.upload(x, n * dim));
+    RQC(dp.upload(orthogonal, (size_t)dim * dim));
     RQC(dout.alloc(n * dim));
-    HIPC(hipMemcpy(dx.p, x, n * dim * 4, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(dp.p, orthogonal, (size_t)dim * dim * 4, hipMemcpyHostToDevice));
     launch_rotate(dx.p, dp.p, dout.p, n, dim, use_mfma != 0, nullptr);
     HIPC(hipDeviceSynchronize());
     HIPC(hipGetLastError());
@@ -1245,15 +1133,13 @@ rq_status rq_quantize_pack(const float *x_rot, uint64_t n, uint32_t dim, const f
     DevBuf<uint32_t> dl;
     DevBuf<uint64_t> dc;
     DevBuf<float4> df;
-    RQC(dx.alloc(n * dim));
-    RQC(tmp.centroids.alloc((size_t)k * dim));
+    RQC(dx.upload(x_rot, n * dim));
+    RQC(tmp.centroids.upload(centroids_rot, (size_t)k * dim));
     RQC(tmp.cent_t.alloc((size_t)k * dim));
     RQC(dd.alloc(n));
     RQC(dl.alloc(n));
     RQC(dc.alloc(n * tmp.W));
     RQC(df.alloc(n));
-    HIPC(hipMemcpy(dx.p, x_rot, n * dim * 4, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(tmp.centroids.p, centroids_rot, (size_t)k * dim * 4, hipMemcpyHostToDevice));
     transpose_kernel<<<dim3(ceil_div(dim, 32), ceil_div(k, 32)), dim3(32, 8)>>>(tmp.centroids.p, tmp.cent_t.p, k, dim);
     AssignAux ax;  // the build's assignment path: matrix-core pre-filter + exact refinement (option assign_impl)
     HIPC(hipDeviceSynchronize());
@@ -1279,22 +1165,20 @@ rq_status rq_coarse_rank(const rq_index *idx, const float *queries, uint32_t nq,
                          float *out_y, uint32_t *out_cluster, float *out_dist) {
     RQC(ensure_device());
     if (!idx || !queries || !out_cluster || !out_dist) return fail(RQ_ERR_INVALID, "null argument");
-    if (!raw_len_ok(idx, len)) return fail(RQ_ERR_DIM_MISMATCH, "query length does not pad to dim (an inner-product index: is not its row length)");
+    RQC(raw_len_check(idx, "query", len));
     if (probe == 0) return fail(RQ_ERR_INVALID, "probe == 0");
     const uint32_t dim = idx->dim, k = idx->k, nprobe = std::min(probe, k);
     if (nprobe > RQ_MAX_PROBE) return fail(RQ_ERR_UNSUPPORTED, "probe > 16384");
     DevBuf<float> dq, qpad, y, dist, pd;
     DevBuf<uint32_t> pc;
-    RQC(dq.alloc((uint64_t)nq * len));
-    RQC(qpad.alloc((uint64_t)nq * dim));
+    RQC(dq.upload(queries, (uint64_t)nq * len));
     RQC(y.alloc((uint64_t)nq * dim));
     RQC(dist.alloc((uint64_t)nq * k));
     RQC(pd.alloc((uint64_t)nq * nprobe));
     RQC(pc.alloc((uint64_t)nq * nprobe));
-    HIPC(hipMemcpy(dq.p, queries, (uint64_t)nq * len * 4, hipMemcpyHostToDevice));
-    if (idx->metric == RQ_METRIC_COSINE) launch_normalize(dq.p, nq, len, dim, qpad.p, nullptr);
-    else pad_rows_kernel<<<ceil_div((uint64_t)nq * dim, 256), 256>>>(dq.p, qpad.p, nq, len, dim);
-    launch_rotate(qpad.p, idx->P.p, y.p, nq, dim, nq >= 32, nullptr);
+    const float *qrows;
+    RQC(transform_queries(idx, dq.p, nq, len, /*want_padded=*/true, qpad, nullptr, &qrows));
+    launch_rotate(qrows, idx->P.p, y.p, nq, dim, nq >= 32, nullptr);
     coarse_dist_kernel<4><<<dim3(ceil_div(nq, 4), ceil_div(k, 256)), 256, 4 * dim * sizeof(float)>>>(
         idx->cent_t.p, y.p, dist.p, k, dim, nq, k);
     launch_select(dist.p, k, nprobe, pc.p, pd.p, 0, nprobe, nq, nullptr);
@@ -1318,14 +1202,12 @@ rq_status rq_query_prep(const rq_index *idx, const float *y, uint32_t nq, const 
     DevBuf<uint32_t> dc, dsum;
     DevBuf<PairScalars> scal;
     DevBuf<uint64_t> planes;
-    RQC(dy.alloc((uint64_t)nq * dim));
+    RQC(dy.upload(y, (uint64_t)nq * dim));
     RQC(ycd.alloc(nq));
-    RQC(dc.alloc(nq));
+    RQC(dc.upload(cluster, nq));
     RQC(dsum.alloc(nq));
     RQC(scal.alloc(nq));
     RQC(planes.alloc((uint64_t)nq * 4 * W));
-    HIPC(hipMemcpy(dy.p, y, (uint64_t)nq * dim * 4, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(dc.p, cluster, nq * 4, hipMemcpyHostToDevice));
     HIPC(hipMemset(ycd.p, 0, nq * 4));
     prep_kernel<<<ceil_div(nq, 4), 256>>>(dy.p, idx->centroids.p, idx->offsets.p, dc.p, ycd.p, nq, 1, dim, scal.p,
                                           planes.p, nullptr, nullptr, dsum.p, idx->k, 0u);
@@ -1350,9 +1232,8 @@ rq_status rq_scan(const rq_index *idx, uint32_t cluster, float y_c_distance_squa
     if (len == 0) return RQ_OK;
     DevBuf<uint64_t> dpl;
     DevBuf<float> dout;
-    RQC(dpl.alloc(4 * idx->W));
+    RQC(dpl.upload(planes, 4 * idx->W));
     RQC(dout.alloc(len));
-    HIPC(hipMemcpy(dpl.p, planes, 4 * idx->W * 8, hipMemcpyHostToDevice));
     scan_dense_kernel<<<ceil_div(len, 256), 256>>>(reinterpret_cast<const uint32_t *>(idx->codes.p), idx->factors.p,
                                                    off[0], len, idx->W, reinterpret_cast<const uint32_t *>(dpl.p),
                                                    lower_bound, delta, scalar_sum, y_c_distance_square, dout.p);
@@ -1371,11 +1252,9 @@ rq_status rq_rerank(const rq_index *idx, const float *query_padded, const uint32
     if (m == 0) return RQ_OK;
     DevBuf<float> dq, dout;
     DevBuf<uint32_t> dp;
-    RQC(dq.alloc(idx->dim));
+    RQC(dq.upload(query_padded, idx->dim));
     RQC(dout.alloc(m));
-    RQC(dp.alloc(m));
-    HIPC(hipMemcpy(dq.p, query_padded, idx->dim * 4, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(dp.p, pos, m * 4, hipMemcpyHostToDevice));
+    RQC(dp.upload(pos, m));
     accurate_flat_kernel<<<ceil_div(m, 32), 256>>>(dp.p, m, idx->view(), dq.p, idx->dim, dout.p);
     HIPC(hipDeviceSynchronize());
     HIPC(hipGetLastError());

@@ -114,8 +114,9 @@ def test_vecs_roundtrip(tmp_path):
     assert vecs.read_vecs(tmp_path / "b.u64vecs", np.uint64)[0].tolist() == [1, 2**63]
 
 
-def _write_dir(tmp, dim=64, k=3, n=5, **bad):
-    """A well-formed five-file index directory (src/rabitq.rs:128-156), optionally broken in one place."""
+def _write_dir(tmp, dim=64, k=3, n=5, metric=None, **bad):
+    """A well-formed five-file index directory (src/rabitq.rs:128-156), optionally broken in one place; `metric`: the text of
+    a sixth file `metric` (None: no such file)."""
     from rabitq_amd import vecs
     rng = np.random.default_rng(0)
     os.makedirs(tmp, exist_ok=True)
@@ -141,30 +142,84 @@ def _write_dir(tmp, dim=64, k=3, n=5, **bad):
     vecs.write_vecs(os.path.join(tmp, "offsets_ids.ivecs"), recs)
     vecs.write_vecs(os.path.join(tmp, "factors.fvecs"), [rng.standard_normal(4 * n).astype(np.float32)])
     vecs.write_vecs(os.path.join(tmp, "x_binary_vec.u64vecs"), [np.arange(n * dim // 64, dtype=np.uint64)])
+    if metric is not None:
+        with open(os.path.join(tmp, "metric"), "w", newline="") as f:
+            f.write(metric)
+
+
+# the `metric` file of a dim-64 directory: texts rq_load_dir refuses (RQ_ERR_IO) and texts it takes (None: no file)
+METRIC_FILE_REFUSED = ["hamming\n", "cosine", "l2", "", "ip 63 zzzzzzzz\n", "ip 63 3f800000", "ip 063 3f800000\n", "ip 0 3f800000\n",
+                       "ip 63 bf800000\n", "ip 63 7f800000\n", "ip 63 7fc00000\n", "ip 64 3f800000\n", "ip 63 3F800000\n",
+                       "ip 63 3f800000\n\n", "ip  63 3f800000\n", "ip 63 3f80000\n", "ip 4096 3f800000\n"]
+METRIC_FILE_ACCEPTED = [None, "l2\n", "cosine\n", "ip 63 3f800000\n", "ip 1 00000000\n", "ip 63 7f7fffff\n"]
 
 
 @pytest.mark.parametrize("bad", ["short_ortho_row", "ragged_centroids", "short_base_row", "bad_offsets", "offsets_end",
-                                 "three_records"])
+                                 "three_records"] +
+                         [pytest.param(("metric", t, False), id="metric-refused-%d" % i) for i, t in enumerate(METRIC_FILE_REFUSED)] +
+                         [pytest.param(("metric", t, True), id="metric-accepted-%d" % i) for i, t in enumerate(METRIC_FILE_ACCEPTED)])
 def test_load_dir_rejects_malformed_directories(L, tmp_path, bad):
     """rq_load_dir validates every record length before indexing by it (the reference's matrix_from_fvecs panics on
-    ragged input): RQ_ERR_IO, no heap over-read, and no device needed to say so."""
+    ragged input): RQ_ERR_IO, no heap over-read, and no device needed to say so.  The `metric` file likewise: a text that
+    rq_dump_dir does not write is RQ_ERR_IO; one it does write gets past parsing (to the device, or to its absence)."""
     import ctypes as C
-    _write_dir(str(tmp_path / "idx"), **{bad: True})
+    accepted = False
+    if isinstance(bad, tuple):
+        accepted = bad[2]
+        _write_dir(str(tmp_path / "idx"), metric=bad[1])
+    else:
+        _write_dir(str(tmp_path / "idx"), **{bad: True})
     h = C.c_void_p()
     st = L.rq_load_dir(os.fsencode(str(tmp_path / "idx")), C.byref(h))
+    if accepted:
+        assert st in (0, -5), (bad, st, L.rq_last_error())
+        if h.value:
+            L.rq_free(h)
+        return
     assert st == -3, (bad, st, L.rq_last_error())
     assert not h.value
 
 
+def _empty_json(members):
+    """A consistent index without vectors (dim 64, n = 0, one empty list, a 64 x 64 orthogonal) as rq_dump_json writes one, plus
+    `members`.  (One list, not none: with k = 0 the centroid array is empty, and on a machine with a device the load then ends
+    in RQ_ERR_INVALID "null array" whatever the metric members say -- past parsing, but neither 0 nor -5.)"""
+    eye = ",".join("1.0" if i // 64 == i % 64 else "0.0" for i in range(64 * 64))
+    return ('{"dim":64,"base":{"nrows":64,"ncols":0,"data":[]},"orthogonal":{"nrows":64,"ncols":64,"data":[' + eye + ']},'
+            '"centroids":{"nrows":64,"ncols":1,"data":[' + ",".join(["0.0"] * 64) + ']},"rand_bias":[' + ",".join(["0.5"] * 64) +
+            '],"offsets":[0,0],"map_ids":[],"x_binary_vec":[],"factors":[]' + members + '}')
+
+
+# the metric members of a JSON index: refused (RQ_ERR_IO) and taken; 1065353216 = bits of 1.0f, 3212836864 of -1.0f, 2139095040 of +inf
+JSON_METRIC_REFUSED = [',"metric":"ip"', ',"metric":"ip","ip_d":63', ',"metric":"ip","ip_sq_bound_bits":1065353216',
+                       ',"metric":"ip","ip_d":63,"ip_sq_bound_bits":4294967296', ',"metric":"ip","ip_d":64,"ip_sq_bound_bits":1065353216',
+                       ',"metric":"ip","ip_d":0,"ip_sq_bound_bits":1065353216', ',"metric":"ip","ip_d":63,"ip_sq_bound_bits":3212836864',
+                       ',"metric":"ip","ip_d":63,"ip_sq_bound_bits":2139095040', ',"metric":"hamming"', ',"metric":7']
+JSON_METRIC_ACCEPTED = ['', ',"metric":"l2"', ',"metric":"cosine"', ',"metric":"ip","ip_d":63,"ip_sq_bound_bits":1065353216',
+                        ',"ip_d":63,"ip_sq_bound_bits":1065353216']
+
+
 @pytest.mark.parametrize("text", ["", "{", '{"dim": 64}', '{"dim":64,"base":{"nrows":64,"ncols":1,"data":[null]}}',
-                                  '{"dim":63,"orthogonal":{"nrows":63,"ncols":63,"data":[]}}'])
+                                  '{"dim":63,"orthogonal":{"nrows":63,"ncols":63,"data":[]}}'] +
+                         [pytest.param(("refused", m), id="metric-refused-%d" % i) for i, m in enumerate(JSON_METRIC_REFUSED)] +
+                         [pytest.param(("accepted", m), id="metric-accepted-%d" % i) for i, m in enumerate(JSON_METRIC_ACCEPTED)])
 def test_load_json_rejects_malformed_text(L, tmp_path, text):
-    """rq_load_json: "deserialize error" (src/rabitq.rs:74) is RQ_ERR_IO, decided before any device work."""
+    """rq_load_json: "deserialize error" (src/rabitq.rs:74) is RQ_ERR_IO, decided before any device work.  So are metric
+    members that rq_dump_json does not write; the ones it writes get past parsing (to the device, or to its absence)."""
     import ctypes as C
+    accepted = False
+    if isinstance(text, tuple):
+        accepted, text = text[0] == "accepted", _empty_json(text[1])
     f = tmp_path / "idx.json"
     f.write_text(text)
     h = C.c_void_p()
-    assert L.rq_load_json(os.fsencode(str(f)), C.byref(h)) == -3, L.rq_last_error()
+    st = L.rq_load_json(os.fsencode(str(f)), C.byref(h))
+    if accepted:
+        assert st in (0, -5), (st, L.rq_last_error())
+        if h.value:
+            L.rq_free(h)
+        return
+    assert st == -3, (st, L.rq_last_error())
     assert not h.value
     assert L.rq_load_json(os.fsencode(str(tmp_path / "missing.json")), C.byref(h)) == -3
 
