@@ -565,7 +565,7 @@ typedef struct {
     uint64_t scan_bytes;       /* algorithmic bytes over all scan launches of the call */
     uint64_t scan_candidates;  /* (query, candidate) pairs scanned                      */
     uint64_t rerank_candidates;/* accurate distances computed (superset of `precise`)   */
-    uint32_t scan_launches;
+    uint32_t scan_launches;    /* scan kernel launches (a stage whose grid is issued in chunks counts each of them) */
     uint32_t retries;          /* queries re-run because a survivor buffer overflowed   */
     /* the matrix-core launches alone (a subset of the scan figures above) */
     float ms_scan_matrix;      /* device time of the scan_mfma_kernel launches           */
@@ -668,16 +668,20 @@ rq_status rq_set_profiling(int level);
  * in percent of the average list length; default 100), "scan_debug": measurement hooks under which every result is UNCHANGED -- 128 (kept for older hosts: the sub-tile /
  * exact-path step counters of rq_profile_t are always on since ABI revision 4), 512 no shadow rows in the rerank,
  * 2048 long run directories skip the cell bitmap (they are ordered by the slot buckets, or the bitonic sort: a test hook),
- * 4096 the phases of the small-batch kernel, 16384 the stage list of every pass (stderr).  Any other bit is refused with
+ * 4096 the phases of the small-batch kernel, 16384 the stage list of every pass (stderr; with one `[rabitq_hip] plan:` line of
+ * key=value tokens per pass, per stage and per coarse ranking, which tests/test_option_paths_gpu.py reads).  Any other bit is refused with
  * RQ_ERR_INVALID by this library: the TIMING ABLATIONS of the matrix-core scan (1, 2, 4, 64, 1024, 8192: results are WRONG) and
  * its in-kernel cycle counters (256) are compiled only into the developer build (make -C rabitq_amd/csrc dev ->
  * librabitq_hip_dev.so, -DRQ_DEV_ABLATIONS; scripts/exp/ select it through RABITQ_HIP_SO), so the shipped kernels carry none
  * of those branches.
  *
  * Threading: options are process-global and result-neutral (every value of every option leaves ids, distances and counters
- * unchanged: tests/test_gpu_parity.py::test_every_option_value_keeps_golden_results).  A pass reads the ones that pick a
- * kernel or a record format once per stage, so changing an option while queries are in flight on other threads only
- * changes which kernels later stages / passes use (test_options_flipped_under_concurrent_queries).
+ * unchanged: tests/test_gpu_parity.py::test_every_option_value_keeps_golden_results on a small golden, and
+ * tests/test_option_paths_gpu.py::test_option_value_runs_its_path_and_keeps_results on indexes and batches where the value's
+ * code path is shown to run).  A pass reads the ones its plan depends on ONCE, before anything is enqueued (plan_pass: the batch
+ * form of "large_batch_from", the stage boundaries, engines, record layouts); whatever executes the pass asks the plan.  Changing
+ * an option while queries are in flight on other threads therefore only changes which kernels later passes use
+ * (test_options_flipped_under_concurrent_queries).
  * Removed in ABI revision 3: "scan_dense", "coarse_impl" = 3 (both answer RQ_ERR_INVALID). */
 rq_status rq_set_option(const char *name, int value);
 rq_status rq_last_profile(rq_profile_t *out);

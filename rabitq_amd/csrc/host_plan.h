@@ -63,6 +63,7 @@ struct StagePlan {
 struct PassPlan {
     uint32_t nprobe, npairs;
     uint32_t dbg;   // option scan_debug, one snapshot for the whole pass (as of every other option the plan reads)
+    bool large;     // the large-batch form of the stages (option large_batch_from, read once: whatever executes the pass asks the plan)
     bool small;     // few, fat launches (kernels_small.h): the early stages run inside one block per query
     uint32_t sb_nstages, sb_lo[RQ_SB_MAX_STAGES], sb_hi[RQ_SB_MAX_STAGES], sb_final_lo;
     bool sb_whole, sb_fill_final;
@@ -77,8 +78,9 @@ struct PassPlan {
     StagePlan st[RQ_MAX_STAGES];
 };
 
-// first_hi: end of the first stage; settle_cap: where the early stages must end at the latest
-static void plan_stages(const rq_index *idx, uint32_t nq, uint32_t nprobe, uint64_t first_hi, uint64_t growth, uint64_t settle_cap, PassPlan &pl) {
+// first_hi: end of the first stage; settle_cap: where the early stages must end at the latest; settle_pct: option stage_settle_pct as
+// plan_pass read it (pl.large: the batch form it decided on)
+static void plan_stages(const rq_index *idx, uint32_t nprobe, uint64_t first_hi, uint64_t growth, uint64_t settle_cap, uint64_t settle_pct, PassPlan &pl) {
     pl.nstages = 0;
     const uint64_t total_max = std::min<uint64_t>((uint64_t)nprobe * idx->max_list_len, idx->n);
     uint64_t lo = 0, hi = first_hi;
@@ -87,7 +89,7 @@ static void plan_stages(const rq_index *idx, uint32_t nq, uint32_t nprobe, uint6
     // nearest list of many queries is one of the long ones, so the bar is the LONGEST list (capped: a single
     // monster list must not push the whole batch through many thin stages)
     uint64_t settle = std::min(settle_cap, std::max<uint64_t>(avg, std::min<uint64_t>(idx->max_list_len, 16 * avg)));
-    if (rq_large_batch(nq)) settle = std::max<uint64_t>(1, settle * (uint64_t)g_stage_settle_pct.load() / 100);
+    if (pl.large) settle = std::max<uint64_t>(1, settle * settle_pct / 100);
     while (lo < total_max) {
         // past the first two lists' worth of candidates the threshold is already tight: scan the rest of
         // the stream as ONE stage (every list then meets all its queries at once: full 32-query tiles)
@@ -116,7 +118,7 @@ static void plan_pass(const rq_index *idx, const QueryParams &qp, bool has_row_m
     const rq_filter *filt = qp.filter;
     const bool large = rq_large_batch(nq), fused = scan_is_fused(W);
     pl = PassPlan{};
-    pl.nprobe = nprobe, pl.npairs = npairs;
+    pl.nprobe = nprobe, pl.npairs = npairs, pl.large = large;
     // shortest list of the pass: a filtered pass settles the pairs whose list admits nothing as empty ones, so no slot bound can be
     // derived from stream positions (as on a shard)
     const uint32_t min_len = filt ? 0u : idx->min_list_len;
@@ -125,6 +127,7 @@ static void plan_pass(const rq_index *idx, const QueryParams &qp, bool has_row_m
     const int gate_opt = g_scan_gate.load(), rank_opt = g_group_rank.load(), tt_opt = g_scan_tile_table.load(), gopt = g_stage_growth.load();
     const bool dense_opt = g_dense_dir.load() != 0, additive_loose = idx->additive_loose.load() != 0;
     const uint64_t settle_pct = (uint64_t)g_stage_settle_pct.load();
+    const uint32_t cm_div = (uint32_t)g_cluster_major_div.load();
     const uint64_t avg_len = std::max<uint64_t>(1, idx->n / std::max<uint32_t>(idx->nonempty_lists, 1));
     const uint64_t total_max = std::min<uint64_t>((uint64_t)nprobe * idx->max_list_len, idx->n);
     const bool one_stage = qp.range || (qp.thr_init != nullptr && !has_row_map);  // thresholds are already tight: nothing to learn in early stages
@@ -152,7 +155,7 @@ static void plan_pass(const rq_index *idx, const QueryParams &qp, bool has_row_m
     if (pl.small) {
         // the early stages run inside one block per query: the first one takes what would be two (16 x topk candidates
         // under threshold f32::MAX cost one gather round), and the in-block part ends after 64 K candidates at the latest
-        plan_stages(idx, nq, nprobe, sb_first, gopt >= 2 ? (uint64_t)gopt : 8, sb_span, pl);
+        plan_stages(idx, nprobe, sb_first, gopt >= 2 ? (uint64_t)gopt : 8, sb_span, settle_pct, pl);
         if (pl.nstages > RQ_SB_MAX_STAGES) pl.small = false;
     }
     if (pl.small) {
@@ -182,7 +185,7 @@ static void plan_pass(const rq_index *idx, const QueryParams &qp, bool has_row_m
         // the first stage runs with threshold f32::MAX (everything survives) until the ranker's heap is full; in a large
         // batch it also takes what would be the next stage (whose threshold -- the worst of the first topk -- lets most
         // of it through anyway): one stage of launches less for ~1 % more exact distances
-        plan_stages(idx, nq, nprobe, (uint64_t)std::max<uint32_t>(topk, 1) * (large ? growth : 1), growth, ~0ull, pl);
+        plan_stages(idx, nprobe, (uint64_t)std::max<uint32_t>(topk, 1) * (large ? growth : 1), growth, ~0ull, settle_pct, pl);
     }
 
     // ---- every stage's engine, grouping, gate and geometry --------------------------------------------------------------
@@ -199,7 +202,7 @@ static void plan_pass(const rq_index *idx, const QueryParams &qp, bool has_row_m
         // that rule): a pair-major EARLY stage launches a block for every (query, probe slot, tile) although only the first slots are in
         // it -- at 512 queries the early stages took 1.06 ms pair-major against 0.3 list-major (batch 256: 1.43 -> 1.12 ms per call,
         // 512: 2.42 -> 1.62)
-        s.cluster_major = s.matrix || (s.est_pairs >= k / (pl.small ? 2u : (uint32_t)g_cluster_major_div.load()) && s.est_pairs > 64);
+        s.cluster_major = s.matrix || (s.est_pairs >= k / (pl.small ? 2u : cm_div) && s.est_pairs > 64);
         // an arena stage: a stage that can exceed the uniform survivor capacity; its scan instantiation has its own tile
         s.arena_stage = qp.seg_final && s.span > qp.cap && fused && large;
         // (filtered stages run the bf16 threshold form: the filtered instantiations exist for that gate only)
@@ -276,11 +279,20 @@ static void plan_pass(const rq_index *idx, const QueryParams &qp, bool has_row_m
     const uint32_t big_hint = hints_of(idx, filt).big_dirs.load();
     pl.mid_blocks = big_hint == 0 ? 64u : std::min(4096u, std::max(256u, big_hint / 4));
 
-    if (pl.dbg & 16384)  // developer hook: the pass's stage list
+    if (pl.dbg & 16384) {  // developer hook: the pass's stage list, and the plan as key=value tokens (one line per pass, one per stage)
+        fprintf(stderr, "[rabitq_hip] plan: pass nq=%u nprobe=%u large=%d small=%d will_list=%d placed=%d fin_additive=%d qn_slots=%u nstages=%u seg_final=%d sb_nstages=%u sb_whole=%d\n",
+                nq, nprobe, (int)pl.large, (int)pl.small, (int)pl.will_list, (int)pl.placed, (int)pl.fin_additive, pl.qn_slots, pl.nstages, (int)qp.seg_final,
+                pl.small ? pl.sb_nstages : 0u, (int)(pl.small && pl.sb_whole));
+        for (uint32_t i = 0; pl.small && i < pl.sb_nstages; ++i)  // (the stages a small batch runs inside its block per query)
+            fprintf(stderr, "[rabitq_hip] plan: sb_stage=%u lo=%u hi=%u\n", i, pl.sb_lo[i], pl.sb_hi[i]);
         for (uint32_t i = 0; i < pl.nstages; ++i) {
             const StagePlan &s = pl.st[i];
             fprintf(stderr, "[rabitq_hip] stage %u: [%u, %u) span %llu est_pairs %llu %s\n", i, s.s_lo, s.s_hi, (unsigned long long)s.span,
                     (unsigned long long)s.est_pairs, s.matrix ? "matrix cores" : (s.cluster_major ? "VALU, list-major" : "VALU, pair-major"));
             if (s.placed) fprintf(stderr, "[rabitq_hip] stage %u: placed ahead of the quantisation (%s gate)\n", i, pl.fin_additive ? "additive" : "bf16");
+            fprintf(stderr, "[rabitq_hip] plan: stage=%u lo=%u hi=%u matrix=%d cluster_major=%d ranked=%d additive=%d arena=%d placed=%d table=%d dense_cells=%u slot_hi=%u\n",
+                    i, s.s_lo, s.s_hi, (int)s.matrix, (int)s.cluster_major, (int)s.ranked, (int)s.additive, (int)s.arena_stage, (int)s.placed, (int)s.want_table,
+                    s.dense_cells, s.slot_hi);
         }
+    }
 }

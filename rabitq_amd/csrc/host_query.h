@@ -69,7 +69,7 @@ static rq_status finish_pass(const rq_index *idx, Workspace &ws, PassResult *res
     res->precise = ws.h_totals[1];
     res->overflowed = ws.h_totals[2];
     res->max_need = ws.h_totals[4];
-    if (rq_large_batch(nq) && !ws.pend.range) hints_of(idx, ws.pend.filter).big_dirs.store((uint32_t)ws.h_totals[7]);
+    if (ws.pend.large && !ws.pend.range) hints_of(idx, ws.pend.filter).big_dirs.store((uint32_t)ws.h_totals[7]);
     // The additive gate is a looser test than the rank-5 threshold it replaces: an index / workload on which it sends more than
     // 3 % of the sub-tile steps down the exact path (each costs ~10 plain steps) goes back to the bf16 threshold MFMA for good
     // (results do not depend on the choice; option scan_gate pins it)
@@ -271,7 +271,7 @@ struct Pass {
             cs.p[1] = reinterpret_cast<uint32_t *>(ws.stat.p), cs.n[1] = 512;    // the matrix-core scan's step counters (+ developer hooks)
             cs.p[2] = ws.big_list.p + nq, cs.n[2] = 3;
             cs.p[3] = ws.fin_grp_cnt.p, cs.n[3] = k + 4;
-            if (rq_large_batch(nq)) cs.p[4] = ws.q_hist.p, cs.n[4] = k + 2;
+            if (pl.large) cs.p[4] = ws.q_hist.p, cs.n[4] = k + 2;
             clear_words_kernel<<<std::max(2u, ceil_div(k + 4, 256)), 256, 0, st>>>(cs);
         }
         pair_prefix_lens_kernel<<<ceil_div(nq, 4), 256, 0, st>>>(idx->offsets.p, probe_cluster, k, nq, nprobe, ws.rough_cnt.p, ws.pair_begin.p, ws.scal.p);
@@ -344,7 +344,7 @@ struct Pass {
 
     // the rerank order of a large batch; 4. ranker state (rerank.rs:70-77, :129-139) and per-query counters
     rq_status orders_state() {
-        if (rq_large_batch(nq)) {  // large batch: rerank queries of the same nearest list back to back (cache locality of the row gather)
+        if (pl.large) {  // large batch: rerank queries of the same nearest list back to back (cache locality of the row gather)
             if (!pl.placed) HIPC(hipMemsetAsync(ws.q_hist.p, 0, (size_t)(k + 2) * 4, st));
             order_count_kernel<<<ceil_div(nq, 256), 256, 0, st>>>(probe_cluster, nprobe, nq, k, ws.q_hist.p);
             group_scan_kernel<<<1, 1024, 0, st>>>(ws.q_hist.p, k + 1, ws.q_start.p, 0u, nullptr, 0u);  // also zeroes the histogram: cursor
@@ -550,10 +550,13 @@ struct Pass {
             stage_launch_scan(r);
         }
         if (s.matrix) pend.matrix_stages++;
-        if (prof_acc && s.additive) prof_acc->matrix_additive_launches++;
-        if (prof_acc) prof_acc->scan_launches++;
+        // (launches, not stages: a grid beyond the launch bound -- or option max_scan_blocks -- is issued in chunks; an empty grid still
+        // counts as the stage's one)
+        const uint32_t launches = std::max(1u, scan_chunk_count(a));
+        if (prof_acc && s.additive) prof_acc->matrix_additive_launches += launches;
+        if (prof_acc) prof_acc->scan_launches += launches;
         if (prof_acc && s.matrix) {
-            prof_acc->matrix_launches++;
+            prof_acc->matrix_launches += launches;
             pend.matrix_ranges[pend.n_matrix_ranges++] = {s.s_lo, s.s_hi};
         }
         return RQ_OK;
@@ -671,7 +674,7 @@ struct Pass {
             stat_fold_kernel<<<1, 64, 0, st>>>(ws.stat.p, ws.stat.p + 200);
             HIPC(hipMemcpyAsync(ws.h_totals + 8, ws.stat.p + 200, 16, hipMemcpyDeviceToHost, st));
         }
-        if (rq_large_batch(nq))  // (the long-directory hint only sizes launches of large batches: a small batch saves the copy's round trip)
+        if (pl.large)  // (the long-directory hint only sizes launches of large batches: a small batch saves the copy's round trip)
             HIPC(hipMemcpyAsync(ws.h_totals + 7, ws.big_list.p + nq + 2, 4, hipMemcpyDeviceToHost, st));
         ws.pend = pend;
         return RQ_OK;
@@ -693,7 +696,7 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
     c.rs.thr = ws.thr.p, c.rs.heap_len = ws.heap_len.p, c.rs.heap_key = ws.heap_key.p, c.rs.heap_id = ws.heap_id.p;
     c.rs.precise = ws.precise.p, c.rs.need = ws.need.p, c.rs.nsurv = ws.nsurv.p, c.rs.nshadow = ws.nshadow.p, c.rs.recent_max = ws.recent.p, c.rs.win_count = ws.win_count.p;
     c.rs.arr_len = ws.arr_len.p, c.rs.arr = ws.arr.p, c.rs.hcap = qp.hcap, c.rs.ovf = ws.ovf.p;
-    c.pend.nq = qp.nq, c.pend.cap = qp.cap, c.pend.filter = qp.filter, c.pend.range = qp.range;
+    c.pend.nq = qp.nq, c.pend.cap = qp.cap, c.pend.filter = qp.filter, c.pend.range = qp.range, c.pend.large = pl.large;
     Prof &pf = ws.prof;
     pf.reset(g_profiling.load(), ws.stream);
     pf.begin(PF_TOTAL);
@@ -714,7 +717,7 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
         RQC(c.stage_scan(r));
         // (a small batch whose survivor buffers are large -- queries re-run after an overflow: tens of thousands of survivors each --
         // takes the large-batch kernels: one block per query would rerank and order those alone, they spread them over the chip)
-        if (!qp.range && !rq_large_batch(qp.nq) && qp.cap <= 4 * RQ_DEFAULT_CAP) c.stage_finish_small(r);
+        if (!qp.range && !pl.large && qp.cap <= 4 * RQ_DEFAULT_CAP) c.stage_finish_small(r);
         else c.stage_finish_large(r);
     }
     RQC(c.results(total_span));

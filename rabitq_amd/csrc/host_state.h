@@ -195,6 +195,7 @@ struct PendingPass {
     uint32_t matrix_stages = 0;   // matrix-core stages of the pass
     bool prefiltered = false;     // the pass ranked its lists through the matrix-core pre-filter (totals[12] = rows that fell back)
     bool range = false;           // a range pass (it orders no run directories: the long-directory hint keeps its value)
+    bool large = false;           // the pass ran the large-batch form of the stages (PassPlan::large)
 };
 struct Workspace {
     hipStream_t stream = nullptr;
@@ -477,7 +478,10 @@ static bool select_is_wave(uint32_t k, uint32_t nprobe, uint32_t nq) { return np
 static void launch_coarse(const float *cent_t, const float *y, float *dist, uint32_t k, uint32_t dim, uint32_t nq,
                           uint32_t kstride, hipStream_t st) {
     const int impl = g_coarse_impl.load();
-    if ((impl == 2 || (impl == 0 && nq >= 2048)) && nq > 0)  // many queries per list: query side in SGPRs
+    const bool sreg = (impl == 2 || (impl == 0 && nq >= 2048)) && nq > 0;
+    if (g_scan_dbg.load() & 16384)  // developer hook: the exact-order distance kernel of this ranking
+        fprintf(stderr, "[rabitq_hip] plan: coarse=exact kernel=%s nq=%u k=%u\n", sreg ? "sreg" : (nq >= 64 && dim <= 2048 ? "lds8" : "lds4"), nq, k);
+    if (sreg)  // many queries per list: query side in SGPRs
         coarse_dist_sreg_kernel<8><<<dim3(ceil_div(nq, 8), ceil_div(k, 256)), 256, 0, st>>>(cent_t, y, dist, k, dim, nq, kstride);
     else if (nq >= 64 && dim <= 2048)  // 8 queries per thread: 8 packed VALU ops per centroid element loaded
         coarse_dist_kernel<8><<<dim3(ceil_div(nq, 8), ceil_div(k, 256)), 256, 8 * dim * sizeof(float), st>>>(cent_t, y, dist, k, dim, nq,
@@ -549,6 +553,8 @@ static void launch_coarse_prefiltered(const rq_index *idx, const float *y, float
     // holds is set up and torn down around the launch -- and needs no scratch any more.)
     const bool tiled = redo != nullptr && ntile >= nprobe &&
                        (k > 8192 || impl == 4 || (impl != 3 && k >= (uint32_t)g_coarse_tiled_from.load() && idx->W <= 8));
+    if (g_scan_dbg.load() & 16384)  // developer hook: which selection the pre-filtered ranking takes
+        fprintf(stderr, "[rabitq_hip] plan: coarse=%s nq=%u k=%u nprobe=%u\n", tiled ? "prefilter_tiled" : "prefilter_regs", nq, k, nprobe);
     if (tiled) {
 #define RQ_TILED(TPL)                                                                                                             \
     select_refine_tiled_kernel<TPL><<<g, b, 4 * 64 * (TPL) * 4, st>>>(dist, y, idx->centroids.p, idx->cent_norm_max, k, dim, nprobe, out_cluster, \
@@ -639,6 +645,15 @@ static void launch_scan_chunks(const ScanArgs &a, F &&launch) {
             c.ngroups = std::min(gchunk, a.ngroups - g0);
             launch(c, dim3(c.ngroups * c.tiles_per_group));
         }
+}
+
+// launches launch_scan_chunks issues for these arguments (rq_profile_t::scan_launches counts them, not the stages)
+static uint32_t scan_chunk_count(const ScanArgs &a) {
+    if (a.ngroups == 0 || a.tiles_per_group == 0) return 0;
+    const uint32_t maxb = std::max(1u, g_max_scan_blocks.load());
+    const uint32_t tchunk = std::min(a.tiles_per_group, maxb);
+    const uint32_t gchunk = std::max(1u, maxb / tchunk);
+    return ceil_div(a.tiles_per_group, tchunk) * ceil_div(a.ngroups, gchunk);
 }
 
 #define SCAN_ARGS p.codes, p.factors, p.offsets, p.grp_start, p.recs, p.surv, p.runs, p.surv_cnt, p.tile_table, a

@@ -231,8 +231,9 @@ def test_every_option_value_keeps_golden_results(rq):
 
 
 def test_options_flipped_under_concurrent_queries(rq, oracle):
-    """Options are process-global; a pass reads the kernel-selecting ones once per stage, so flipping them while other threads
-    query the same handle changes which kernels run, never a result."""
+    """Options are process-global; a pass reads the ones its plan depends on once, in plan_pass (the batch form, the stage
+    boundaries and the records' layout among them), so flipping them while other threads query the same handle changes which
+    kernels later passes run, never a result."""
     import threading
     from rabitq_amd import index as ix
     n, d, k = 16000, 128, 20
@@ -247,7 +248,9 @@ def test_options_flipped_under_concurrent_queries(rq, oracle):
 
     def flipper():
         rng = np.random.default_rng(5)
-        names = ["scan_impl", "scan_gate", "group_rank", "scan_tile_table", "dense_dir", "small_batch", "stage_growth", "coarse_impl"]
+        # (the planner's knobs too: a pass reads each of them once, in plan_pass, and everything that executes it asks the plan)
+        names = ["scan_impl", "scan_gate", "group_rank", "scan_tile_table", "dense_dir", "small_batch", "stage_growth", "coarse_impl",
+                 "large_batch_from", "cluster_major_div", "stage_settle_pct"]
         while not stop.is_set():
             name = names[int(rng.integers(len(names)))]
             ix.set_option(name, int(rng.choice(OPTION_VALUES[name])))
