@@ -1,7 +1,7 @@
 // host_plan.h -- part of the host side of librabitq_hip.so (one translation unit: rabitq_hip.hip includes the host_*.h files in order;
 // they are not stand-alone headers).  What one query pass will do, decided ONCE before anything is enqueued: plan_pass reads the index,
 // the pass's parameters and one snapshot of the options and hints; it makes no HIP call, launches nothing and reads no workspace
-// buffer.  host_query.h (run_pass) executes the plan.
+// buffer.  host_query.h (run_pass) executes the plan; host_call.h decides which passes a call runs.
 #pragma once
 struct QueryParams {
     uint32_t nq, len, probe, topk;
@@ -24,6 +24,46 @@ struct QueryParams {
     // no run ordering, no replay, no result rows; topk is 1 (the ranker state is allocated, not used).
     bool range = false;
 };
+
+// The device arrays of a query call, or of one pass of it (QueryCall::at).
+struct QueryIO {
+    const float *d_q = nullptr;  // nq x len
+    float *out_dist = nullptr;   // nq x topk (a range call has no result rows: null)
+    uint32_t *out_id = nullptr, *out_n = nullptr;
+    // nq x min(probe, k): if given, the probe lists are taken from there (visiting order as supplied; id 0xFFFFFFFF = no list)
+    // instead of being ranked here
+    const uint32_t *ext_cluster = nullptr;
+    const float *ext_dist = nullptr;
+    const float *thr_init = nullptr;  // nq: a seeded call's initial thresholds, a range call's radii (QueryParams::thr_init)
+};
+// One query call as every layer below the C entries sees it.  Overflow re-runs address a pass's arrays through a row map, so they take
+// the pass's QueryCall as it is.
+struct QueryCall {
+    rq_index *idx = nullptr;
+    const rq_filter *filter = nullptr;
+    uint32_t len = 0, probe = 0, topk = 0;
+    bool heuristic = false;
+    QueryIO io;
+    uint32_t npb() const { return std::min(probe, idx->k); }  // columns of the probe lists
+    // The call of a pass that starts at query q0: the one place that knows the arrays' strides.
+    QueryCall at(uint64_t q0) const {
+        QueryCall c = *this;
+        c.io.d_q = io.d_q + q0 * len;
+        c.io.out_dist = io.out_dist ? io.out_dist + q0 * topk : nullptr;
+        c.io.out_id = io.out_id ? io.out_id + q0 * topk : nullptr;
+        c.io.out_n = io.out_n ? io.out_n + q0 : nullptr;
+        c.io.ext_cluster = io.ext_cluster ? io.ext_cluster + q0 * npb() : nullptr;
+        c.io.ext_dist = io.ext_dist ? io.ext_dist + q0 * npb() : nullptr;
+        c.io.thr_init = io.thr_init ? io.thr_init + q0 : nullptr;
+        return c;
+    }
+};
+// The parameters of a pass of `c` over nq queries with the given capacities (what the call decides; the caller adds seg_final / ext_lists / range).
+static QueryParams pass_params(const QueryCall &c, uint32_t nq, uint32_t cap, uint32_t hcap) {
+    QueryParams qp{nq, c.len, c.probe, c.topk, c.heuristic, cap, hcap};
+    qp.thr_init = c.io.thr_init, qp.filter = c.filter;
+    return qp;
+}
 
 #define RQ_DEFAULT_CAP 4096u
 #define RQ_MAX_CAP_HINT 32768u

@@ -1,5 +1,5 @@
 // host_query.h -- part of the host side of librabitq_hip.so (one translation unit: rabitq_hip.hip includes the host_*.h files in order;
-// they are not stand-alone headers).  The query pipeline: RaBitQ::query (src/rabitq.rs:268-333) as staged passes -- run_pass, capacities and re-runs, the begin / end halves of a batch call.
+// they are not stand-alone headers).  The query pipeline: RaBitQ::query (src/rabitq.rs:268-333) as staged passes -- a pass's workspace, its phases, run_pass and finish_pass (what turns a call into passes: host_call.h).
 #pragma once
 // ------------------------------------------------------------------------------------------------
 // the query pipeline
@@ -7,8 +7,7 @@
 static rq_status ws_prepare(const rq_index *idx, Workspace &ws, const QueryParams &qp) {
     const uint32_t nprobe = std::min(qp.probe, idx->k);
     const uint64_t nq = qp.nq, npairs = nq * nprobe;
-    if (!ws.stream) HIPC(hipStreamCreateWithFlags(&ws.stream, hipStreamNonBlocking));
-    if (!ws.h_totals) HIPC(hipHostMalloc((void **)&ws.h_totals, 16 * sizeof(unsigned long long)));
+    RQC(ws_ensure_stream(ws));
     RQC(ws.qpad.ensure(nq * idx->dim));
     RQC(ws.y.ensure(nq * idx->dim));
     if (!qp.ext_lists) RQC(ws.dist.ensure(nq * idx->k));
@@ -52,6 +51,7 @@ static rq_status ws_prepare(const rq_index *idx, Workspace &ws, const QueryParam
     RQC(ws.row_map.ensure(nq));
     RQC(ws.big_list.ensure(nq + 3));  // [nq] = entries, [nq + 1] = blocks done, [nq + 2] = most entries of any stage of the pass
     if (qp.heuristic) RQC(ws.arr.ensure(nq * qp.hcap));
+    if (qp.range) RQC(ws.range_hits.ensure(nq));
     return RQ_OK;
 }
 
@@ -171,13 +171,10 @@ struct Pass {
     Prof &pf;
     hipStream_t st;
     const uint32_t dim, k, W, nq, topk, nprobe, npairs;
-    const float *d_q;
-    const uint32_t *d_row_map, *ext_cluster;
-    const float *ext_dist;
-    float *d_out_dist;
-    uint32_t *d_out_id, *d_out_n;
+    const QueryIO &io;  // the pass's arrays
+    const uint32_t *d_row_map;
     rq_profile_t *prof_acc;
-    const float *qpad;              // the queries, padded to dim (d_q itself when nothing was padded)
+    const float *qpad;              // the queries, padded to dim (io.d_q itself when nothing was padded)
     const uint32_t *probe_cluster;  // the probe lists: ranked here, or the caller's
     const float *probe_dist;
     ReplayState rs;
@@ -197,7 +194,7 @@ struct Pass {
         sa.dist = ws.dist.p, sa.y = ws.y.p, sa.qpad = ws.qpad.p, sa.probe_cluster = ws.probe_cluster.p, sa.probe_dist = ws.probe_dist.p;
         sa.qf6 = pl.write_q6 ? ws.qf6.p : nullptr;
         sa.scal = ws.scal.p, sa.qnib = ws.qnib.p, sa.rough_cnt = ws.rough_cnt.p, sa.surv_cnt = ws.surv_cnt.p, sa.totals = ws.totals.p;
-        sa.rs = rs, sa.out_dist = d_out_dist, sa.out_id = d_out_id, sa.out_n = d_out_n, sa.recs = ws.recs.p, sa.fs = idx->fstats;
+        sa.rs = rs, sa.out_dist = io.out_dist, sa.out_id = io.out_id, sa.out_n = io.out_n, sa.recs = ws.recs.p, sa.fs = idx->fstats;
         sa.k = k, sa.dim = dim, sa.nprobe = nprobe, sa.topk = topk, sa.cap = qp.cap, sa.hcap = qp.hcap;
         const rq_filter *filt = qp.filter;
         if (filt) {
@@ -210,7 +207,7 @@ struct Pass {
         pf.begin(PF_COARSE);
         const float *sb_q;  // (cosine: N(q), padded -- what the front kernel rotates and hands on as qpad; else the raw queries: it pads them itself)
         uint32_t sb_len;
-        RQC(transform_queries(idx, d_q, nq, qp.len, /*want_padded=*/false, ws.qnorm, st, &sb_q, &sb_len));
+        RQC(transform_queries(idx, io.d_q, nq, qp.len, /*want_padded=*/false, ws.qnorm, st, &sb_q, &sb_len));
         sb_front_kernel<<<dim3(ceil_div(k, RQ_SB_LISTS), ceil_div(nq, RQ_SB_QT)), 256, (size_t)2 * RQ_SB_QT * dim * sizeof(float), st>>>(
             sb_q, sb_len, idx->P.p, idx->centroids.p, ws.y.p, ws.qpad.p, ws.dist.p, k, dim, nq, ws.totals.p, ws.big_list.p + nq);
         pf.end();
@@ -228,11 +225,11 @@ struct Pass {
     // 1. pad (rabitq.rs:277-280) + rotate (:282); 2. coarse distances + probe selection (:283-297), unless the caller supplied the lists
     rq_status rotate_coarse() {
         pf.begin(PF_ROTATE);
-        RQC(transform_queries(idx, d_q, nq, qp.len, /*want_padded=*/true, ws.qpad, st, &qpad));
+        RQC(transform_queries(idx, io.d_q, nq, qp.len, /*want_padded=*/true, ws.qpad, st, &qpad));
         launch_rotate(qpad, idx->P.p, ws.y.p, nq, dim, nq >= 32, st);
         pf.end();
-        if (ext_cluster) {
-            probe_cluster = ext_cluster, probe_dist = ext_dist;
+        if (io.ext_cluster) {
+            probe_cluster = io.ext_cluster, probe_dist = io.ext_dist;
         } else if (coarse_prefilter_applies(idx, nq, nprobe)) {
             pf.begin(PF_COARSE);
             HIPC(hipMemsetAsync(ws.totals.p + 12, 0, 8, st));
@@ -591,7 +588,7 @@ struct Pass {
             auto finish = topk < 64 ? sb_finish_kernel<true> : sb_finish_kernel<false>;
             finish<<<nq, fin_threads, (size_t)dim * sizeof(float) + (2 * RQ_SBF_RUNS + RQ_SBF_RECS) * 16, st>>>(
                 ws.surv.p, ws.runs.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, topk, rs, probe_cluster, nprobe, flags,
-                idx->map_ids.p, d_out_dist, d_out_id, d_out_n, ws.rough_cnt.p, ws.totals.p);
+                idx->map_ids.p, io.out_dist, io.out_id, io.out_n, ws.rough_cnt.p, ws.totals.p);
             sb_results_done = true;
         } else {
             auto finish = qp.heuristic ? stage_finish_kernel<true> : stage_finish_kernel<false>;
@@ -656,10 +653,10 @@ struct Pass {
             if (qp.heuristic && !qp.range) {
                 sort_survivors_kernel<<<nq, 256, 0, st>>>(ws.arr.p, ws.arr_len.p, qp.hcap);
                 finalize_heuristic_kernel<<<ceil_div((uint64_t)nq * topk, 256), 256, 0, st>>>(rs, nq, topk, d_row_map, idx->map_ids.p,
-                                                                                               d_out_dist, d_out_id, d_out_n);
+                                                                                               io.out_dist, io.out_id, io.out_n);
             } else if (!qp.range) {
-                finalize_heap_kernel<<<ceil_div((uint64_t)nq * topk, 256), 256, 0, st>>>(rs, nq, topk, d_row_map, idx->map_ids.p, d_out_dist,
-                                                                                          d_out_id, d_out_n);
+                finalize_heap_kernel<<<ceil_div((uint64_t)nq * topk, 256), 256, 0, st>>>(rs, nq, topk, d_row_map, idx->map_ids.p, io.out_dist,
+                                                                                          io.out_id, io.out_n);
             }
             metrics_sum_kernel<<<std::min(256u, ceil_div(nq, 256)), 256, 0, st>>>(
                 ws.rough_cnt.p, ws.precise.p, ws.need.p, qp.heuristic ? ws.arr_len.p : nullptr, ws.nsurv.p, ws.nshadow.p, nq, ws.ovf.p, qp.hcap,
@@ -681,18 +678,16 @@ struct Pass {
     }
 };
 
-// Runs one pass over nq queries already resident at d_q (nq x len).  Results go to row
-// row_map[b] (or b) of the output arrays.  On return the stream is synchronised.
-// ext_cluster / ext_dist (nq x min(probe,k), device): if given, the probe lists are taken from there
-// (visiting order as supplied; id 0xFFFFFFFF = no list) instead of being ranked here.
-static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, const QueryParams &qp,
-                          const uint32_t *d_row_map, float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n,
-                          PassResult *res, rq_profile_t *prof_acc, const uint32_t *ext_cluster = nullptr,
-                          const float *ext_dist = nullptr, bool defer = false) {
+// Runs one pass of `call` (already advanced to the pass's first query) over qp.nq queries.  Results go to row row_map[b] (or b) of
+// the call's output arrays.  On return the stream is synchronised, unless `defer`: the caller then finishes the pass (finish_pass).
+static rq_status run_pass(Workspace &ws, const QueryCall &call, const QueryParams &qp, const uint32_t *d_row_map, PassResult *res,
+                          rq_profile_t *prof_acc, bool defer) {
+    const rq_index *idx = call.idx;
+    const QueryIO &io = call.io;
     PassPlan pl;
-    plan_pass(idx, qp, d_row_map != nullptr, ext_cluster != nullptr, pl);
-    Pass c{idx, ws, qp, pl, ws.prof, ws.stream, idx->dim, idx->k, idx->W, qp.nq, qp.topk, pl.nprobe, pl.npairs, d_q, d_row_map, ext_cluster, ext_dist,
-           d_out_dist, d_out_id, d_out_n, prof_acc, d_q, ws.probe_cluster.p, ws.probe_dist.p};
+    plan_pass(idx, qp, d_row_map != nullptr, io.ext_cluster != nullptr, pl);
+    Pass c{idx, ws, qp, pl, ws.prof, ws.stream, idx->dim, idx->k, idx->W, qp.nq, qp.topk, pl.nprobe, pl.npairs, io, d_row_map,
+           prof_acc, io.d_q, ws.probe_cluster.p, ws.probe_dist.p};
     c.rs.thr = ws.thr.p, c.rs.heap_len = ws.heap_len.p, c.rs.heap_key = ws.heap_key.p, c.rs.heap_id = ws.heap_id.p;
     c.rs.precise = ws.precise.p, c.rs.need = ws.need.p, c.rs.nsurv = ws.nsurv.p, c.rs.nshadow = ws.nshadow.p, c.rs.recent_max = ws.recent.p, c.rs.win_count = ws.win_count.p;
     c.rs.arr_len = ws.arr_len.p, c.rs.arr = ws.arr.p, c.rs.hcap = qp.hcap, c.rs.ovf = ws.ovf.p;
@@ -721,381 +716,6 @@ static rq_status run_pass(const rq_index *idx, Workspace &ws, const float *d_q, 
         else c.stage_finish_large(r);
     }
     RQC(c.results(total_span));
-    if (defer) return RQ_OK;  // the caller finishes the pass later (rq_query_batch_device_end)
+    if (defer) return RQ_OK;
     return finish_pass(idx, ws, res, prof_acc);
 }
-
-// The checks every query entry shares (args_null: one of the entry's own pointer arguments is null; a range call has topk = 1).
-static rq_status validate_call(const rq_index *idx, bool args_null, uint32_t len, uint32_t probe, uint32_t topk, const rq_filter *filter) {
-    RQC(ensure_device());
-    RQC(ensure_kernel_attributes());
-    if (!idx || args_null) return fail(RQ_ERR_INVALID, "null argument");
-    RQC(raw_len_check(idx, "query", len));
-    if (probe == 0 || idx->k == 0) return fail(RQ_ERR_INVALID, "probe == 0 (the reference panics at rabitq.rs:295)");
-    if (topk == 0 || topk > RQ_MAX_TOPK) return fail(RQ_ERR_UNSUPPORTED, "topk must be in [1, 2048]");
-    if (std::min(probe, idx->k) > RQ_MAX_PROBE) return fail(RQ_ERR_UNSUPPORTED, "probe > 16384 not supported");
-    if (idx->dim > 4096) return fail(RQ_ERR_UNSUPPORTED, "dim > 4096 not supported");
-    if (filter && filter->idx != idx) return fail(RQ_ERR_INVALID, "the filter was made for another index");
-    if (filter && filter->generation != idx->generation)
-        return fail(RQ_ERR_INVALID, "the filter was made before the index was last mutated (rq_add / rq_remove): make it again");
-    return RQ_OK;
-}
-static rq_status validate_query(const rq_index *idx, const float *d_q, uint32_t len, uint32_t probe, uint32_t topk,
-                                const float *d_out_dist, const uint32_t *d_out_id, const uint32_t *d_out_n, const rq_filter *filter = nullptr) {
-    return validate_call(idx, !d_q || !d_out_dist || !d_out_id || !d_out_n, len, probe, topk, filter);
-}
-
-// Uniform survivor capacity of a pass over `remaining` queries, and whether its final stage is segmented.  An index whose
-// batches overflowed the default capacity (cap_hint) used to size EVERY query of a pass for the worst one (learnt capacity
-// 32 768: 100 GB for a 65 536-query pass of the hard benchmark distribution); large batches now keep the default
-// capacity for the stages that cannot exceed it and give every other stage per-query segments.
-static uint32_t pass_capacity(const rq_index *idx, uint32_t remaining, bool seeded, bool *seg, const rq_filter *filter = nullptr) {
-    const uint32_t hint = hints_of(idx, filter).cap.load();
-    const int opt = g_seg_opt.load();
-    *seg = !seeded && rq_large_batch(remaining) && scan_is_fused(idx->W) && (opt >= 2 || (opt == 1 && hint > RQ_DEFAULT_CAP));
-    if (*seg) return RQ_DEFAULT_CAP;  // stages that cannot exceed it stay uniform, the others are segmented
-    return std::max(RQ_DEFAULT_CAP, hint);
-}
-
-// queries per pass: survivor / run buffers are 32 B per slot per query (keep one pass under ~24 GiB) and
-// (query, list) pairs per pass <= 2^22 (bounds the per-pair buffers and every launch size)
-static uint32_t pass_queries(const rq_index *idx, uint32_t remaining, uint32_t probe, uint32_t cap0, bool seg, bool ext_lists = false,
-                             const rq_filter *filter = nullptr) {
-    // survivor records + run directory: 32 B per slot per query, 48 B when the pass also keeps the second directory buffer
-    // (ws_prepare: capacities beyond the default, segmented passes, long directories); the budget is a third of the HBM that
-    // was free once the index was resident (at least 4 GiB: an index that fills the HBM -- 100M x 768 -- still answers a
-    // 32 768-query batch in ONE pass; split in two, every block of the matrix-core scan paid its start-up twice: a third
-    // of that launch at dim 768)
-    const uint64_t slot_bytes = cap0 > RQ_DEFAULT_CAP || seg || hints_of(idx, filter).big_dirs.load() > 0 ? 48 : 32;
-    // Probe lists supplied by the caller = a shard of a multi-GPU deployment: most of a query's probed lists live on other ranks
-    // (empty here: skipped before any per-pair work), and the step's batch grows with the number of ranks so that a list still
-    // meets as many queries as on one GPU -- cut into passes of 65 536 queries, each pass of an 8-GPU step would bring a list
-    // 128 queries instead of 1024 and the matrix-core scan would run at half its rate (one-rank-of-eight rehearsal: 0.19 of
-    // peak).  Such passes may hold 16 x the queries / pairs (per-pair buffers: ~200 B per pair, 6.7 GB at 2^25 pairs).
-    const uint64_t max_nq = ext_lists ? 16ull * RQ_MAX_NQ_PER_PASS : RQ_MAX_NQ_PER_PASS, max_pairs = ext_lists ? (1ull << 26) : (1ull << 22);
-    uint32_t step_nq = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(remaining, max_nq),
-                                                    std::max<uint64_t>(1, idx->pass_budget / ((uint64_t)cap0 * slot_bytes)));
-    return std::min<uint32_t>(step_nq, (uint32_t)std::max<uint64_t>(1, max_pairs / std::min(probe, idx->k)));
-}
-
-// The parameters of the next top-k pass of a call with `remaining` queries to go: how many of them it takes and its capacities.
-// (seeded: the call carries initial thresholds -- the caller sets thr_init; ext_lists: the probe lists come from the caller)
-static QueryParams topk_pass_params(const rq_index *idx, uint32_t remaining, uint32_t len, uint32_t probe, uint32_t topk, bool heuristic,
-                                    const rq_filter *filter, bool seeded, bool ext_lists) {
-    bool seg = false;
-    const uint32_t cap0 = pass_capacity(idx, remaining, seeded, &seg, filter);
-    const uint32_t step_nq = pass_queries(idx, remaining, probe, cap0, seg, ext_lists, filter);
-    QueryParams qp{step_nq, len, probe, topk, heuristic, cap0, std::max(cap0, std::max(RQ_DEFAULT_CAP, hints_of(idx, filter).cap.load()))};
-    qp.seg_final = seg && rq_large_batch(step_nq);
-    qp.ext_lists = ext_lists;
-    qp.filter = filter;
-    return qp;
-}
-
-// Runs a first pass of a call (prepared workspace, no row map).  When it gives up inside an arena stage -- no room for the survivor
-// arena, or it kept overflowing -- the pass is run once more on the uniform buffers (qp.seg_final is cleared), where a query that
-// overflows is simply re-run with the capacity it asks for: slower, never wrong.
-static rq_status run_pass_or_uniform(const rq_index *idx, Workspace &ws, const float *d_q, QueryParams &qp, float *d_out_dist, uint32_t *d_out_id,
-                                     uint32_t *d_out_n, PassResult *pr, rq_profile_t *prof, const uint32_t *ext_cluster, const float *ext_dist,
-                                     bool defer) {
-    ws.arena_failed = false;
-    const rq_status st = run_pass(idx, ws, d_q, qp, nullptr, d_out_dist, d_out_id, d_out_n, pr, prof, ext_cluster, ext_dist, defer);
-    if (st == RQ_OK || !ws.arena_failed || !qp.seg_final) return st;
-    (void)hipStreamSynchronize(ws.stream);
-    // a failed hipMalloc leaves hipErrorOutOfMemory as the thread's last error (sticky on ROCm 7.2): the repeat's own
-    // hipGetLastError() check must not pick it up; the arena of earlier batches goes back to the pool the repeat allocates from
-    (void)hipGetLastError();
-    ws.arena_recs.release(), ws.arena_runs.release(), ws.scan_extra.release(), ws.arena_places.release();
-    ws.arena_failed = false;
-    qp.seg_final = false;
-    RQC(ws_prepare(idx, ws, qp));
-    *pr = PassResult();
-    return run_pass(idx, ws, d_q, qp, nullptr, d_out_dist, d_out_id, d_out_n, pr, prof, ext_cluster, ext_dist, defer);
-}
-
-// After a finished pass: remember the capacity it needed and re-run exactly the queries whose survivor
-// buffers overflowed, with the capacity they asked for.  All pointers are those of the pass (already offset).
-static rq_status after_pass(rq_index *idx, Workspace *ws, const QueryParams &qp, const float *d_q, float *d_out_dist,
-                            uint32_t *d_out_id, uint32_t *d_out_n, const uint32_t *ext_cluster, const float *ext_dist,
-                            const PassResult &pr, rq_profile_t &prof, uint64_t &tot_precise) {
-    const uint32_t len = qp.len, probe = qp.probe, topk = qp.topk;
-    const bool heuristic = qp.heuristic;
-    const uint32_t npb = std::min(probe, idx->k);
-    if (pr.max_need > qp.cap) {  // remember (with headroom) so that later batches do not overflow
-        // ... but only up to RQ_MAX_CAP_HINT: survivor buffers are cap x 32 B for EVERY query of the pass, so one outlier
-        // query (a loose threshold after an unlucky nearest list) must not shrink the passes of all later batches; beyond
-        // the bound the outliers are simply re-run below with the capacity they asked for
-        uint32_t want = pow2_ceil((uint32_t)std::min<uint64_t>(pr.max_need + pr.max_need / 4, RQ_MAX_CAP_HINT));
-        std::atomic<uint32_t> &cap_hint = hints_of(idx, qp.filter).cap;
-        uint32_t cur = cap_hint.load();
-        while (cur < want && !cap_hint.compare_exchange_weak(cur, want)) {}
-    }
-    if (!pr.overflowed) return RQ_OK;
-    uint32_t cap = qp.cap, hcap = qp.hcap;
-    std::vector<uint32_t> h_need(qp.nq), h_alen(qp.nq), h_ovf(qp.nq), over_rows;
-    HIPC(hipMemcpy(h_need.data(), ws->need.p, qp.nq * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(h_alen.data(), ws->arr_len.p, qp.nq * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(h_ovf.data(), ws->ovf.p, qp.nq * 4, hipMemcpyDeviceToHost));
-    uint32_t max_need = 0, max_alen = 0;
-    for (uint32_t b = 0; b < qp.nq; ++b)
-        if (h_ovf[b] || (heuristic && h_alen[b] > hcap)) {
-            over_rows.push_back(b);
-            max_need = std::max(max_need, h_need[b]);
-            max_alen = std::max(max_alen, h_alen[b]);
-        }
-    int guard = 0;
-    while (!over_rows.empty() && guard++ < 8) {
-        prof.retries += (uint32_t)over_rows.size();
-        uint32_t ncap = std::max(cap * 2, pow2_ceil(max_need));
-        uint32_t nhcap = heuristic ? std::max(hcap * 2, pow2_ceil(std::max(max_alen, max_need))) : hcap;
-        // bound the retry workspace to ~4 GiB of survivor records
-        uint32_t chunk = (uint32_t)std::max<uint64_t>(1, (4ull << 30) / ((uint64_t)(ncap + nhcap) * sizeof(SurvRec)));
-        std::vector<uint32_t> still;
-        // a pooled workspace (its buffers persist: a workload whose outliers overflow every batch must not pay
-        // hipMalloc / hipFree of gigabytes per batch)
-        WsLease lease(idx, ws_acquire(idx));
-        Workspace &rws = *lease.w;
-        DevBuf<float> &sub_q = rws.retry_q;
-        DevBuf<uint32_t> &sub_rows = rws.retry_rows;
-        for (size_t o = 0; o < over_rows.size(); o += chunk) {
-            uint32_t m = (uint32_t)std::min<size_t>(chunk, over_rows.size() - o);
-            QueryParams rq{m, len, probe, topk, heuristic, ncap, nhcap};
-            rq.thr_init = qp.thr_init;  // indexed through the row map
-            rq.filter = qp.filter;
-            RQC(ws_prepare(idx, rws, rq));
-            RQC(sub_q.ensure((uint64_t)m * len));
-            RQC(sub_rows.ensure(m));
-            HIPC(hipMemcpy(sub_rows.p, over_rows.data() + o, m * 4, hipMemcpyHostToDevice));
-            gather_rows_kernel<<<ceil_div((uint64_t)m * len, 256), 256, 0, rws.stream>>>(d_q, sub_rows.p, m, len, sub_q.p);
-            PassResult rr;
-            const uint32_t *sub_pc = nullptr;
-            const float *sub_pd = nullptr;
-            DevBuf<float> &sub_probe_d = rws.retry_pd, &sub_probe_c = rws.retry_pc;
-            if (ext_cluster) {  // the caller's probe lists, restricted to the re-run queries
-                RQC(sub_probe_c.ensure((uint64_t)m * npb));
-                RQC(sub_probe_d.ensure((uint64_t)m * npb));
-                gather_rows_kernel<<<ceil_div((uint64_t)m * npb, 256), 256, 0, rws.stream>>>(
-                    reinterpret_cast<const float *>(ext_cluster), sub_rows.p, m, npb, sub_probe_c.p);
-                gather_rows_kernel<<<ceil_div((uint64_t)m * npb, 256), 256, 0, rws.stream>>>(ext_dist, sub_rows.p, m, npb,
-                                                                                              sub_probe_d.p);
-                sub_pc = reinterpret_cast<const uint32_t *>(sub_probe_c.p);
-                sub_pd = sub_probe_d.p;
-            }
-            RQC(run_pass(idx, rws, sub_q.p, rq, sub_rows.p, d_out_dist, d_out_id, d_out_n, &rr, nullptr, sub_pc, sub_pd));
-            tot_precise += rr.precise;
-            if (rr.overflowed) {
-                std::vector<uint32_t> n2(m), a2(m), o2(m);
-                HIPC(hipMemcpy(n2.data(), rws.need.p, m * 4, hipMemcpyDeviceToHost));
-                HIPC(hipMemcpy(a2.data(), rws.arr_len.p, m * 4, hipMemcpyDeviceToHost));
-                HIPC(hipMemcpy(o2.data(), rws.ovf.p, m * 4, hipMemcpyDeviceToHost));
-                for (uint32_t b = 0; b < m; ++b)
-                    if (o2[b] || (heuristic && a2[b] > nhcap)) {
-                        still.push_back(over_rows[o + b]);
-                        max_need = std::max(max_need, n2[b]);
-                        max_alen = std::max(max_alen, a2[b]);
-                    }
-            }
-        }
-        cap = ncap, hcap = nhcap;
-        over_rows.swap(still);
-    }
-    if (!over_rows.empty()) return fail(RQ_ERR_OOM, "survivor buffers kept overflowing");
-    return RQ_OK;
-}
-
-// tail of every query call: the reference's panics and counters
-static rq_status conclude_query(uint32_t nq, bool heuristic, const uint32_t *d_out_n, uint64_t tot_rough,
-                                uint64_t tot_precise, const rq_profile_t &prof) {
-    bool any_empty = false;
-    if (heuristic) {  // rerank.rs:171-173: an empty array panics in the reference
-        std::vector<uint32_t> h_n(nq);
-        HIPC(hipMemcpy(h_n.data(), d_out_n, nq * 4, hipMemcpyDefault));  // d_out_n may be device or mapped host memory
-        for (uint32_t v : h_n) any_empty |= (v == 0);
-    }
-    g_rough.fetch_add(tot_rough, std::memory_order_relaxed);      // rerank.rs:105
-    g_precise.fetch_add(tot_precise, std::memory_order_relaxed);  // rerank.rs:104
-    g_query.fetch_add(nq, std::memory_order_relaxed);             // rabitq.rs:331
-    g_profile = prof;
-    if (any_empty) return fail(RQ_ERR_EMPTY, "heuristic ranker accepted no candidate for at least one query");
-    return RQ_OK;
-}
-
-// queries/outputs in device memory
-static rq_status query_device(rq_index *idx, const float *d_q, uint32_t nq, uint32_t len, uint32_t probe,
-                              uint32_t topk, bool heuristic, float *d_out_dist, uint32_t *d_out_id,
-                              uint32_t *d_out_n, const uint32_t *ext_cluster = nullptr,
-                              const float *ext_dist = nullptr, Workspace *use_ws = nullptr, const float *ext_thr = nullptr,
-                              const rq_filter *filter = nullptr) {
-    RQC(validate_query(idx, d_q, len, probe, topk, d_out_dist, d_out_id, d_out_n, filter));
-    if (nq == 0) return RQ_OK;
-    rq_profile_t prof;
-    memset(&prof, 0, sizeof prof);
-    Workspace *ws = use_ws ? use_ws : ws_acquire(idx);  // use_ws: the caller holds (and releases) the workspace
-    WsLease rel(idx, use_ws ? nullptr : ws);
-    uint64_t tot_rough = 0, tot_precise = 0;
-    const uint32_t npb = std::min(probe, idx->k);
-    // A call of several passes (more than 65 536 queries) keeps TWO passes in flight, each on a workspace and stream of its own -- what
-    // rq_query_batch_device_begin / _end let a caller do with two batches, done here for one large batch: pass i + 1 is enqueued
-    // before pass i is waited for, so the thin launches at either end of a pass overlap the other pass's wide ones (+4 %: 131 072
-    // queries 33.9 -> 32.6 ms per call).  Results are those of the passes run one after the other.
-    if (!use_ws && !ext_cluster && !ext_thr && g_pass_overlap.load()) {
-        const QueryParams first = topk_pass_params(idx, nq, len, probe, topk, heuristic, filter, false, false);
-        const uint32_t cap_first = first.cap, first_nq = first.nq;
-        // (only with room for a second workspace: an index that fills the HBM -- configs[3] -- runs its passes one after the other;
-        // rough size of a pass's buffers: survivor records + directories, per-pair records and operands, distances, ranker state)
-        bool room = false;
-        if (first_nq < nq) {
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                const uint64_t need = (uint64_t)first_nq * ((uint64_t)cap_first * 48 + (uint64_t)npb * 320 + (uint64_t)idx->dim * 8 + (uint64_t)idx->k * 4 + 4096);
-                room = free_b > need + (6ull << 30);
-            }
-        }
-        if (first_nq < nq && room) {
-            ws_release(idx, ws);  // (the passes take workspaces of their own from the pool, this one among them)
-            rel.w = nullptr;
-            struct Flight {
-                Workspace *ws = nullptr;
-                QueryParams qp{};
-                uint32_t q0 = 0;
-            } fl[2];
-            auto finish = [&](Flight &f) -> rq_status {
-                if (!f.ws) return RQ_OK;
-                Workspace *w = f.ws;
-                f.ws = nullptr;
-                WsLease r(idx, w);
-                PassResult pr;
-                RQC(finish_pass(idx, *w, &pr, &prof));
-                tot_rough += pr.rough;
-                tot_precise += pr.precise;
-                return after_pass(idx, w, f.qp, d_q + (uint64_t)f.q0 * len, d_out_dist + (uint64_t)f.q0 * topk, d_out_id + (uint64_t)f.q0 * topk,
-                                  d_out_n + f.q0, nullptr, nullptr, pr, prof, tot_precise);
-            };
-            auto drain = [&]() {  // (an error path: nothing may stay in flight, every workspace goes back)
-                for (Flight &f : fl)
-                    if (f.ws) {
-                        (void)hipStreamSynchronize(f.ws->stream);
-                        ws_release(idx, f.ws);
-                        f.ws = nullptr;
-                    }
-            };
-            uint32_t slot = 0;
-            for (uint32_t q0 = 0, step_nq = 0; q0 < nq; q0 += step_nq, slot ^= 1u) {
-                rq_status st = finish(fl[slot]);  // the pass before the previous one
-                const QueryParams next = topk_pass_params(idx, nq - q0, len, probe, topk, heuristic, filter, false, false);
-                step_nq = next.nq;
-                Flight &f = fl[slot];
-                if (st == RQ_OK) {
-                    f.qp = next;
-                    f.q0 = q0;
-                    f.ws = ws_acquire(idx);
-                    st = ws_prepare(idx, *f.ws, f.qp);
-                }
-                if (st == RQ_OK) {
-                    PassResult pr;
-                    st = run_pass_or_uniform(idx, *f.ws, d_q + (uint64_t)q0 * len, f.qp, d_out_dist + (uint64_t)q0 * topk, d_out_id + (uint64_t)q0 * topk,
-                                             d_out_n + q0, &pr, &prof, nullptr, nullptr, true);
-                }
-                if (st != RQ_OK) {
-                    drain();
-                    return st;
-                }
-            }
-            for (uint32_t i = 0; i < 2; ++i, slot ^= 1u) {  // oldest first
-                const rq_status st = finish(fl[slot]);
-                if (st != RQ_OK) {
-                    drain();
-                    return st;
-                }
-            }
-            return conclude_query(nq, heuristic, d_out_n, tot_rough, tot_precise, prof);
-        }
-    }
-    for (uint32_t q0 = 0, step_nq = 0; q0 < nq; q0 += step_nq) {
-        QueryParams qp = topk_pass_params(idx, nq - q0, len, probe, topk, heuristic, filter, ext_thr != nullptr, ext_cluster != nullptr);
-        step_nq = qp.nq;
-        qp.thr_init = ext_thr ? ext_thr + q0 : nullptr;
-        RQC(ws_prepare(idx, *ws, qp));
-        PassResult pr;
-        const float *q_at = d_q + (uint64_t)q0 * len;
-        float *od = d_out_dist + (uint64_t)q0 * topk;
-        uint32_t *oi = d_out_id + (uint64_t)q0 * topk, *on = d_out_n + q0;
-        const uint32_t *ec = ext_cluster ? ext_cluster + (uint64_t)q0 * npb : nullptr;
-        const float *ed = ext_dist ? ext_dist + (uint64_t)q0 * npb : nullptr;
-        RQC(run_pass_or_uniform(idx, *ws, q_at, qp, od, oi, on, &pr, &prof, ec, ed, false));
-        tot_rough += pr.rough;
-        tot_precise += pr.precise;
-        RQC(after_pass(idx, ws, qp, q_at, od, oi, on, ec, ed, pr, prof, tot_precise));
-    }
-    return conclude_query(nq, heuristic, d_out_n, tot_rough, tot_precise, prof);
-}
-
-// The same call split in two, so that a caller can keep several batches in flight (each on its own
-// workspace and HIP stream): begin enqueues the whole pass and returns, end waits for it and does the
-// (rare) overflow re-runs.  Calls that need more than one pass run synchronously inside begin.
-struct rq_ticket {
-    rq_index *idx = nullptr;
-    Workspace *ws = nullptr;
-    QueryParams qp{};
-    const float *d_q = nullptr;
-    float *d_out_dist = nullptr;
-    uint32_t *d_out_id = nullptr, *d_out_n = nullptr;
-    const uint32_t *ext_cluster = nullptr;
-    const float *ext_dist = nullptr;
-    rq_profile_t prof;
-    bool done = false;
-    rq_status status = RQ_OK;
-};
-
-static rq_status query_device_begin(rq_index *idx, const float *d_q, uint32_t nq, uint32_t len, uint32_t probe,
-                                    uint32_t topk, bool heuristic, float *d_out_dist, uint32_t *d_out_id,
-                                    uint32_t *d_out_n, rq_ticket **out, const rq_filter *filter = nullptr) {
-    if (!out) return fail(RQ_ERR_INVALID, "null argument");
-    *out = nullptr;
-    RQC(validate_query(idx, d_q, len, probe, topk, d_out_dist, d_out_id, d_out_n, filter));
-    std::unique_ptr<rq_ticket> t(new rq_ticket());
-    t->idx = idx;
-    memset(&t->prof, 0, sizeof t->prof);
-    struct Open {  // counted while the ticket is outstanding (rq_add / rq_remove refuse to relayout under it)
-        rq_index *i;
-        bool keep = false;
-        explicit Open(rq_index *x) : i(x) { i->open_tickets.fetch_add(1); }
-        ~Open() { if (!keep) i->open_tickets.fetch_sub(1); }
-    } open(idx);
-    t->qp = topk_pass_params(idx, nq, len, probe, topk, heuristic, filter, false, false);  // (the filter travels in the ticket's parameters: _end's re-runs and hint updates use it)
-    if (nq == 0 || t->qp.nq < nq) {  // nothing to overlap / several passes: synchronous
-        t->status = query_device(idx, d_q, nq, len, probe, topk, heuristic, d_out_dist, d_out_id, d_out_n, nullptr, nullptr, nullptr, nullptr, filter);
-        t->done = true;
-        open.keep = true;
-        *out = t.release();
-        return RQ_OK;
-    }
-    t->d_q = d_q, t->d_out_dist = d_out_dist, t->d_out_id = d_out_id, t->d_out_n = d_out_n;
-    t->ws = ws_acquire(idx);
-    rq_status st = ws_prepare(idx, *t->ws, t->qp);
-    PassResult pr;
-    if (st == RQ_OK) st = run_pass_or_uniform(idx, *t->ws, d_q, t->qp, d_out_dist, d_out_id, d_out_n, &pr, &t->prof, nullptr, nullptr, true);
-    if (st != RQ_OK) {
-        (void)hipStreamSynchronize(t->ws->stream);
-        ws_release(idx, t->ws);
-        return st;
-    }
-    open.keep = true;
-    *out = t.release();
-    return RQ_OK;
-}
-
-static rq_status query_device_end(rq_ticket *tk) {
-    if (!tk) return fail(RQ_ERR_INVALID, "null ticket");
-    std::unique_ptr<rq_ticket> t(tk);
-    t->idx->open_tickets.fetch_sub(1);
-    if (t->done) return t->status;
-    WsLease rel(t->idx, t->ws);
-    PassResult pr;
-    RQC(finish_pass(t->idx, *t->ws, &pr, &t->prof));
-    uint64_t tot_precise = pr.precise;
-    RQC(after_pass(t->idx, t->ws, t->qp, t->d_q, t->d_out_dist, t->d_out_id, t->d_out_n, nullptr, nullptr, pr, t->prof,
-                   tot_precise));
-    return conclude_query(t->qp.nq, t->qp.heuristic, t->d_out_n, pr.rough, tot_precise, t->prof);
-}
-

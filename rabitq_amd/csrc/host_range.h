@@ -86,17 +86,15 @@ static rq_status range_make_piece(const rq_index *idx, Workspace &ws, uint32_t m
     return RQ_OK;
 }
 
-// The queries of a finished pass whose survivors did not fit `cap`: again, grouped by need (ascending: a query that admits a
-// whole list does not size the buffers of the ones that missed by a little), every group with the capacity its largest
-// exact count asks for.  One re-run always suffices: the count under a fixed radius does not depend on the capacity.
-static rq_status range_rerun_overflowed(rq_index *idx, Workspace *ws, const QueryParams &qp, const float *d_q, uint32_t q0,
-                                        rq_profile_t &prof, uint64_t &tot_precise, std::vector<std::unique_ptr<RangePiece>> &pieces) {
-    std::vector<uint32_t> h_need(qp.nq), h_ovf(qp.nq);
-    HIPC(hipMemcpy(h_need.data(), ws->need.p, (size_t)qp.nq * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(h_ovf.data(), ws->ovf.p, (size_t)qp.nq * 4, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> over;
-    for (uint32_t b = 0; b < qp.nq; ++b)
-        if (h_ovf[b]) over.push_back(b);
+// The queries of a finished pass (`c`: its call, at query q0 of the range call) whose survivors did not fit `cap`: again, grouped by
+// need (ascending: a query that admits a whole list does not size the buffers of the ones that missed by a little), every group with
+// the capacity its largest exact count asks for.  One re-run always suffices: the count under a fixed radius does not depend on the capacity.
+static rq_status range_rerun_overflowed(Workspace &ws, const QueryCall &c, const QueryParams &qp, uint32_t q0, CallTotals &tot,
+                                        std::vector<std::unique_ptr<RangePiece>> &pieces) {
+    rq_index *idx = c.idx;
+    Overflowed ov;
+    RQC(read_overflowed(ws, qp.nq, false, false, 0, ov));
+    std::vector<uint32_t> &over = ov.rows, &h_need = ov.need;
     std::sort(over.begin(), over.end(), [&](uint32_t a, uint32_t b) { return h_need[a] != h_need[b] ? h_need[a] < h_need[b] : a < b; });
     // A workload most of whose queries admit more than the buffers hold (loose radii everywhere) should not scan twice from now
     // on: when an eighth of the pass overflowed, remember the capacity the overflowed queries needed -- up to RQ_MAX_CAP_HINT, the
@@ -112,9 +110,8 @@ static rq_status range_rerun_overflowed(rq_index *idx, Workspace *ws, const Quer
             while (cur < want && !idx->range_cap_hint.compare_exchange_weak(cur, want)) {}
         }
     }
-    const uint32_t npb = std::min(qp.probe, idx->k);
     const uint64_t budget = 4ull << 30;  // survivor records + run directories of one re-run (48 B per slot), unless one query alone needs more
-    const uint64_t max_m = std::max<uint64_t>(1, std::min<uint64_t>(RQ_MAX_NQ_PER_PASS, (1ull << 22) / npb));
+    const uint64_t max_m = std::max<uint64_t>(1, std::min<uint64_t>(RQ_MAX_NQ_PER_PASS, (1ull << 22) / c.npb()));
     WsLease lease(idx, ws_acquire(idx));  // (pooled: its buffers persist across calls)
     Workspace &rws = *lease.w;
     for (size_t o = 0; o < over.size();) {
@@ -123,30 +120,22 @@ static rq_status range_rerun_overflowed(rq_index *idx, Workspace *ws, const Quer
         while (e < over.size() && e - o < max_m) {
             const uint32_t need = h_need[over[e]];
             if (need > (1u << 31)) return fail(RQ_ERR_OOM, "a query admits more than 2^31 candidates: the result does not fit");
-            const uint32_t c = std::max(2 * RQ_DEFAULT_CAP, pow2_ceil(need));
-            if (e > o && (uint64_t)(e - o + 1) * c * 48ull > budget) break;
-            ncap = c, ++e;
+            const uint32_t cap = std::max(2 * RQ_DEFAULT_CAP, pow2_ceil(need));
+            if (e > o && (uint64_t)(e - o + 1) * cap * 48ull > budget) break;
+            ncap = cap, ++e;
         }
         const uint32_t m = (uint32_t)(e - o);
-        prof.retries += m;
-        QueryParams rq{m, qp.len, qp.probe, 1u, false, ncap, ncap};
-        rq.thr_init = qp.thr_init;  // indexed through the row map
-        rq.filter = qp.filter;
+        tot.prof.retries += m;
+        QueryParams rq = pass_params(c, m, ncap, ncap);
         rq.range = true;
-        RQC(ws_prepare(idx, rws, rq));
-        RQC(rws.range_hits.ensure(m));
-        RQC(rws.retry_q.ensure((uint64_t)m * qp.len));
-        RQC(rws.retry_rows.ensure(m));
-        HIPC(hipMemcpy(rws.retry_rows.p, over.data() + o, (size_t)m * 4, hipMemcpyHostToDevice));
-        gather_rows_kernel<<<ceil_div((uint64_t)m * qp.len, 256), 256, 0, rws.stream>>>(d_q, rws.retry_rows.p, m, qp.len, rws.retry_q.p);
         PassResult rr;
         // (the profile takes the re-run in: its launches and times, the rows it scans AGAIN -- scan_candidates is what was scanned,
         // the rough counter what the reference counts -- and the candidates and shadow rejects the first pass could not keep)
-        RQC(run_pass(idx, rws, rws.retry_q.p, rq, rws.retry_rows.p, nullptr, nullptr, nullptr, &rr, &prof));
+        RQC(rerun_rows(rws, c, rq, over.data() + o, &rr, &tot.prof));
         if (rr.overflowed) return fail(RQ_ERR_HIP, "range re-run: survivor count changed between runs");
-        tot_precise += rr.precise;
+        tot.precise += rr.precise;
         std::unique_ptr<RangePiece> piece;
-        RQC(range_make_piece(idx, rws, m, ncap, q0, rws.retry_rows.p, prof, &piece));
+        RQC(range_make_piece(idx, rws, m, ncap, q0, rws.retry_rows.p, tot.prof, &piece));
         pieces.push_back(std::move(piece));
         o = e;
     }
@@ -201,33 +190,28 @@ static rq_status range_device_impl(rq_index *idx, const rq_filter *filter, const
                                    const float *d_radius, rq_range_result **out) {
     std::unique_ptr<rq_range_result> res(new rq_range_result());
     res->nq = nq;
-    rq_profile_t prof;
-    memset(&prof, 0, sizeof prof);
+    CallTotals tot;
+    rq_profile_t &prof = tot.prof;
     Workspace *ws = ws_acquire(idx);
     WsLease rel(idx, ws);
-    if (!ws->stream) HIPC(hipStreamCreateWithFlags(&ws->stream, hipStreamNonBlocking));
-    if (!ws->h_totals) HIPC(hipHostMalloc((void **)&ws->h_totals, 16 * sizeof(unsigned long long)));
+    RQC(ws_ensure_stream(*ws));
     hipStream_t st = ws->stream;
-    uint64_t tot_rough = 0, tot_precise = 0;
+    const QueryCall call{idx, filter, len, probe, 1u, false, QueryIO{d_q, nullptr, nullptr, nullptr, nullptr, nullptr, d_radius}};
     std::vector<std::unique_ptr<RangePiece>> pieces;
     for (uint32_t q0 = 0, step_nq = 0; q0 < nq; q0 += step_nq) {
+        const QueryCall pc = call.at(q0);
         const uint32_t cap0 = std::max(RQ_DEFAULT_CAP, idx->range_cap_hint.load());
-        step_nq = pass_queries(idx, nq - q0, probe, cap0, false, false, filter);
-        QueryParams qp{step_nq, len, probe, 1u, false, cap0, cap0};
-        qp.thr_init = d_radius + q0;
-        qp.filter = filter;
+        step_nq = pass_queries(pc, nq - q0, cap0, false);
+        QueryParams qp = pass_params(pc, step_nq, cap0, cap0);
         qp.range = true;
         RQC(ws_prepare(idx, *ws, qp));
-        RQC(ws->range_hits.ensure(step_nq));
-        const float *q_at = d_q + (uint64_t)q0 * len;
         PassResult pr;
-        RQC(run_pass(idx, *ws, q_at, qp, nullptr, nullptr, nullptr, nullptr, &pr, &prof));
-        tot_rough += pr.rough;
-        tot_precise += pr.precise;
+        RQC(run_pass(*ws, pc, qp, nullptr, &pr, &prof, false));
+        tot.rough += pr.rough, tot.precise += pr.precise;
         std::unique_ptr<RangePiece> piece;
         RQC(range_make_piece(idx, *ws, step_nq, cap0, q0, nullptr, prof, &piece));
         pieces.push_back(std::move(piece));
-        if (pr.overflowed) RQC(range_rerun_overflowed(idx, ws, qp, q_at, q0, prof, tot_precise, pieces));
+        if (pr.overflowed) RQC(range_rerun_overflowed(*ws, pc, qp, q0, tot, pieces));
     }
     // unite the pieces
     RangeTimer tm;
@@ -265,10 +249,7 @@ static rq_status range_device_impl(rq_index *idx, const rq_filter *filter, const
     tm.end(prof);
     HIPC(hipStreamSynchronize(st));
     HIPC(hipGetLastError());
-    g_rough.fetch_add(tot_rough, std::memory_order_relaxed);
-    g_precise.fetch_add(tot_precise, std::memory_order_relaxed);
-    g_query.fetch_add(nq, std::memory_order_relaxed);
-    g_profile = prof;
+    count_call(nq, tot);
     *out = res.release();
     return RQ_OK;
 }

@@ -189,14 +189,18 @@ static rq_status sharded_step(rq_index *mi, void *nccl_comm, uint32_t world, uin
     const uint32_t width = shared ? 2 * topk : topk;  // keys per query and rank in the final all-gather
     Workspace *ws = ws_acquire(mi);
     WsLease rel(mi, ws);
-    if (!ws->stream) HIPC(hipStreamCreateWithFlags(&ws->stream, hipStreamNonBlocking));
+    RQC(ws_ensure_stream(*ws));
     hipStream_t st = ws->stream;
     RQC(ws->sh_flag.ensure(8));  // [0..3] handshake, [4] status of the final gather
     // ---- 0. local validation + every buffer of the step, then the handshake ---------------------------------------------
     const uint64_t cells = (uint64_t)nq * topk, pcells = (uint64_t)nq * npb;
     const uint64_t out_stride = (uint64_t)nq * width + 1;  // a rank's block of the final all-gather: keys + status word
     int my_rank = 0;
-    rq_status err = validate_query(mi, d_queries, len, probe, topk, d_out_dist, d_out_id, d_out_n);
+    rq_status err = validate_query(QueryCall{mi, nullptr, len, probe, topk, heuristic, QueryIO{d_queries, d_out_dist, d_out_id, d_out_n}});
+    // this shard's answer to (part of) the step: a call on the step's workspace over the probe lists pcx / pdx (null: ranked by the call)
+    auto local_call = [&](uint32_t call_probe, float *od, uint32_t *oi, uint32_t *on, const uint32_t *pcx, const float *pdx, const float *thr) {
+        return query_device(QueryCall{mi, nullptr, len, call_probe, topk, heuristic, QueryIO{d_queries, od, oi, on, pcx, pdx, thr}}, nq, ws);
+    };
     const bool sliced = api && world > 1;
     const uint64_t pchunk = (uint64_t)((nq + world - 1) / world) * npb;  // probe-list keys a rank contributes (query-sliced coarse ranking)
     auto alloc_all = [&]() -> rq_status {
@@ -296,7 +300,7 @@ static rq_status sharded_step(rq_index *mi, void *nccl_comm, uint32_t world, uin
     note_hip(hipMemsetAsync(ws->sh_packed.p, 0xFF, (out_stride - 1) * 8, st), "hipMemsetAsync");  // nothing found (yet)
     if (shared) {
         if (err == RQ_OK) {
-            note(query_device(mi, d_queries, nq, len, 1, topk, heuristic, ws->sh_dist.p, ws->sh_id.p, ws->sh_n.p, pc_a, pd_a, ws));
+            note(local_call(1, ws->sh_dist.p, ws->sh_id.p, ws->sh_n.p, pc_a, pd_a, nullptr));
             profile_add(prof_sum, g_profile);
         }
         if (err == RQ_OK) kth_threshold_kernel<<<ceil_div(nq, 256), 256, 0, st>>>(ws->sh_dist.p, ws->sh_n.p, nq, topk, ws->sh_thr.p);
@@ -308,14 +312,13 @@ static rq_status sharded_step(rq_index *mi, void *nccl_comm, uint32_t world, uin
         note_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
         if (err == RQ_OK) pack_topk_keys_at_kernel<<<ceil_div(cells, 256), 256, 0, st>>>(ws->sh_dist.p, ws->sh_id.p, ws->sh_n.p, nq, topk, id_offset, width, 0, ws->sh_packed.p);
         if (err == RQ_OK && npb > 1) {
-            note(query_device(mi, d_queries, nq, len, npb - 1, topk, heuristic, ws->sh_dist_b.p, ws->sh_id_b.p, ws->sh_n_b.p, pc_b, pd_b, ws, ws->sh_thr.p));
+            note(local_call(npb - 1, ws->sh_dist_b.p, ws->sh_id_b.p, ws->sh_n_b.p, pc_b, pd_b, ws->sh_thr.p));
             profile_add(prof_sum, g_profile);
             if (err == RQ_OK) pack_topk_keys_at_kernel<<<ceil_div(cells, 256), 256, 0, st>>>(ws->sh_dist_b.p, ws->sh_id_b.p, ws->sh_n_b.p, nq, topk, id_offset, width, topk, ws->sh_packed.p);
         }
     } else if (err == RQ_OK) {
         // every rank walks the same probe list; a list another rank owns is simply empty here (skipped before any per-pair work)
-        note(query_device(mi, d_queries, nq, len, probe, topk, heuristic, ws->sh_dist.p, ws->sh_id.p, ws->sh_n.p, need_lists ? pc : nullptr,
-                          need_lists ? pd : nullptr, ws));
+        note(local_call(probe, ws->sh_dist.p, ws->sh_id.p, ws->sh_n.p, need_lists ? pc : nullptr, need_lists ? pd : nullptr, nullptr));
         profile_add(prof_sum, g_profile);
         if (err == RQ_OK) pack_topk_keys_kernel<<<ceil_div(cells, 256), 256, 0, st>>>(ws->sh_dist.p, ws->sh_id.p, ws->sh_n.p, nq, topk, id_offset, ws->sh_packed.p);
     }

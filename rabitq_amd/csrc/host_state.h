@@ -361,6 +361,12 @@ static void ws_release(rq_index *idx, Workspace *w) {
     std::lock_guard<std::mutex> g(idx->ws_mu);
     w->busy = false;
 }
+// A workspace's stream and pinned block, made on its first use.
+static rq_status ws_ensure_stream(Workspace &ws) {
+    if (!ws.stream) HIPC(hipStreamCreateWithFlags(&ws.stream, hipStreamNonBlocking));
+    if (!ws.h_totals) HIPC(hipHostMalloc((void **)&ws.h_totals, 16 * sizeof(unsigned long long)));
+    return RQ_OK;
+}
 // A workspace held for a scope: goes back to the index's pool at its end (w == nullptr: nothing held).
 struct WsLease {
     rq_index *idx;

@@ -37,6 +37,7 @@
 #include "host_metric.h"
 #include "host_plan.h"
 #include "host_query.h"
+#include "host_call.h"
 #include "host_range.h"
 #include "host_build.h"
 #include "host_mutate.h"
@@ -658,14 +659,18 @@ rq_status rq_merge_smallest_u64_device(const uint64_t *d_in, uint32_t world, uin
     return RQ_OK;
 }
 
+// The call description of a C entry (host_plan.h: QueryCall).
+static QueryCall topk_call(const rq_index *idx, const rq_filter *filter, uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank, const QueryIO &io) {
+    return QueryCall{const_cast<rq_index *>(idx), filter, len, probe, topk, heuristic_rank != 0, io};
+}
+
 rq_status rq_query_batch_device_probed(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t len,
                                        const uint32_t *d_probe_cluster, const float *d_probe_dist, uint32_t probe,
                                        uint32_t topk, int heuristic_rank, float *d_out_dist, uint32_t *d_out_id,
                                        uint32_t *d_out_n) {
     if (!d_probe_cluster || !d_probe_dist) return fail(RQ_ERR_INVALID, "null probe lists");
     if (idx && probe > idx->k) return fail(RQ_ERR_INVALID, "probe lists must have min(probe, k) columns: pass probe <= k");
-    return query_device(const_cast<rq_index *>(idx), d_queries, nq, len, probe, topk, heuristic_rank != 0, d_out_dist,
-                        d_out_id, d_out_n, d_probe_cluster, d_probe_dist);
+    return query_device(topk_call(idx, nullptr, len, probe, topk, heuristic_rank, {d_queries, d_out_dist, d_out_id, d_out_n, d_probe_cluster, d_probe_dist}), nq, nullptr);
 }
 
 rq_status rq_query_batch_device_seeded(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t len,
@@ -674,35 +679,31 @@ rq_status rq_query_batch_device_seeded(const rq_index *idx, const float *d_queri
                                        uint32_t *d_out_id, uint32_t *d_out_n) {
     if (!d_probe_cluster || !d_probe_dist || !d_thr_init) return fail(RQ_ERR_INVALID, "null probe lists / thresholds");
     if (idx && probe > idx->k) return fail(RQ_ERR_INVALID, "probe lists must have min(probe, k) columns: pass probe <= k");
-    return query_device(const_cast<rq_index *>(idx), d_queries, nq, len, probe, topk, heuristic_rank != 0, d_out_dist,
-                        d_out_id, d_out_n, d_probe_cluster, d_probe_dist, nullptr, d_thr_init);
+    return query_device(topk_call(idx, nullptr, len, probe, topk, heuristic_rank, {d_queries, d_out_dist, d_out_id, d_out_n, d_probe_cluster, d_probe_dist, d_thr_init}),
+                        nq, nullptr);
 }
 
 rq_status rq_query_batch_device(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t len,
                                 uint32_t probe, uint32_t topk, int heuristic_rank, float *d_out_dist,
                                 uint32_t *d_out_id, uint32_t *d_out_n) {
-    return query_device(const_cast<rq_index *>(idx), d_queries, nq, len, probe, topk, heuristic_rank != 0, d_out_dist,
-                        d_out_id, d_out_n);
+    return query_device(topk_call(idx, nullptr, len, probe, topk, heuristic_rank, {d_queries, d_out_dist, d_out_id, d_out_n}), nq, nullptr);
 }
 
 rq_status rq_query_batch_device_filtered(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq,
                                          uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank, float *d_out_dist,
                                          uint32_t *d_out_id, uint32_t *d_out_n) {
-    return query_device(const_cast<rq_index *>(idx), d_queries, nq, len, probe, topk, heuristic_rank != 0, d_out_dist,
-                        d_out_id, d_out_n, nullptr, nullptr, nullptr, nullptr, filter);
+    return query_device(topk_call(idx, filter, len, probe, topk, heuristic_rank, {d_queries, d_out_dist, d_out_id, d_out_n}), nq, nullptr);
 }
 
 rq_status rq_query_batch_device_begin(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t len,
                                       uint32_t probe, uint32_t topk, int heuristic_rank, float *d_out_dist,
                                       uint32_t *d_out_id, uint32_t *d_out_n, rq_ticket **out_ticket) {
-    return query_device_begin(const_cast<rq_index *>(idx), d_queries, nq, len, probe, topk, heuristic_rank != 0,
-                              d_out_dist, d_out_id, d_out_n, out_ticket);
+    return query_device_begin(topk_call(idx, nullptr, len, probe, topk, heuristic_rank, {d_queries, d_out_dist, d_out_id, d_out_n}), nq, out_ticket);
 }
 rq_status rq_query_batch_device_begin_filtered(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq,
                                                uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank, float *d_out_dist,
                                                uint32_t *d_out_id, uint32_t *d_out_n, rq_ticket **out_ticket) {
-    return query_device_begin(const_cast<rq_index *>(idx), d_queries, nq, len, probe, topk, heuristic_rank != 0,
-                              d_out_dist, d_out_id, d_out_n, out_ticket, filter);
+    return query_device_begin(topk_call(idx, filter, len, probe, topk, heuristic_rank, {d_queries, d_out_dist, d_out_id, d_out_n}), nq, out_ticket);
 }
 rq_status rq_query_batch_device_end(rq_ticket *ticket) { return query_device_end(ticket); }
 
@@ -758,9 +759,8 @@ static rq_status query_batch_host(const rq_index *idx, const rq_filter *filter, 
         HIPC(hipHostGetDevicePointer(&dev, pin, 0));
         char *h = static_cast<char *>(pin), *d = static_cast<char *>(dev);
         memcpy(h, queries, (size_t)nq * len * 4);
-        rq_status s = query_device(const_cast<rq_index *>(idx), (const float *)d, nq, len, probe, topk, heuristic_rank != 0,
-                                   (float *)(d + qb), (uint32_t *)(d + qb + ob), (uint32_t *)(d + qb + 2 * ob), nullptr, nullptr, nullptr,
-                                   nullptr, filter);
+        rq_status s = query_device(topk_call(idx, filter, len, probe, topk, heuristic_rank,
+                                             {(const float *)d, (float *)(d + qb), (uint32_t *)(d + qb + ob), (uint32_t *)(d + qb + 2 * ob)}), nq, nullptr);
         if (s != RQ_OK && s != RQ_ERR_EMPTY) return s;
         memcpy(out_dist, h + qb, (size_t)nq * topk * 4);
         memcpy(out_id, h + qb + ob, (size_t)nq * topk * 4);
@@ -773,8 +773,7 @@ static rq_status query_batch_host(const rq_index *idx, const rq_filter *filter, 
     RQC(g_staging.get(2, (uint64_t)nq * topk * 4, &di));
     RQC(g_staging.get(3, (uint64_t)nq * 4, &dn));
     HIPC(hipMemcpy(dq, queries, (uint64_t)nq * len * 4, hipMemcpyHostToDevice));
-    rq_status s = query_device(const_cast<rq_index *>(idx), (const float *)dq, nq, len, probe, topk, heuristic_rank != 0,
-                               (float *)dd, (uint32_t *)di, (uint32_t *)dn, nullptr, nullptr, nullptr, nullptr, filter);
+    rq_status s = query_device(topk_call(idx, filter, len, probe, topk, heuristic_rank, {(const float *)dq, (float *)dd, (uint32_t *)di, (uint32_t *)dn}), nq, nullptr);
     if (s != RQ_OK && s != RQ_ERR_EMPTY) return s;
     HIPC(hipMemcpy(out_dist, dd, (uint64_t)nq * topk * 4, hipMemcpyDeviceToHost));
     HIPC(hipMemcpy(out_id, di, (uint64_t)nq * topk * 4, hipMemcpyDeviceToHost));

@@ -1282,6 +1282,75 @@ def test_call_of_several_passes_overlaps_them_with_the_same_results(rq):
     idx.close()
 
 
+def test_overflow_reruns_inside_the_second_pass_of_a_call(rq, oracle):
+    """Overflow re-runs in a pass that does not start at query 0: the re-run's row map and the pass's offset into the call's arrays
+    meet.  70 000 queries at 32 far, short lists (100 rows: nothing overflows, so the first pass of 65 536 teaches the index no
+    capacity), except four planted ones in the second pass that sit in the one long list (12 000 rows): topk = 600 puts 600 x 8 or more
+    positions into the first stage, whose threshold is f32::MAX -- more than the default capacity of 4096.  The whole call with two
+    passes in flight, the whole call with the passes one after the other and the two passes as separate calls, each on a fresh
+    index (a learnt capacity would change later calls), give the same bits; the planted rows are the CPU oracle's."""
+    import torch
+    from rabitq_amd import index as ix
+    dev = torch.device("cuda", 0)
+    d, n0, far, per, nq, cut, probe, topk = 64, 12_000, 32, 100, 70_000, 65_536, 1, 600
+    planted = [65_536, 65_537, 68_000, 69_999]
+    rng = np.random.default_rng(411)
+    # far centres: norm 40 (rows of list 0 have norm ~8, at most ~13: nearer the origin; a point drawn at a far centre is ~8 from it,
+    # ~41 from the origin and ~57 from the other far centres)
+    fc = rng.standard_normal((far, d)).astype(np.float32)
+    fc *= np.float32(40.0) / np.linalg.norm(fc, axis=1, keepdims=True).astype(np.float32)
+    centres = np.concatenate([np.zeros((1, d), np.float32), fc])
+    x = np.concatenate([rng.standard_normal((n0, d)).astype(np.float32),
+                        np.repeat(fc, per, axis=0) + rng.standard_normal((far * per, d)).astype(np.float32)])
+    P = synth.random_orthogonal(d, seed=412)
+    queries = fc[rng.integers(0, far, nq)] + rng.standard_normal((nq, d)).astype(np.float32)
+    queries[planted] = rng.standard_normal((len(planted), d)).astype(np.float32) * np.float32(0.2)
+    q = torch.from_numpy(np.ascontiguousarray(queries)).to(dev)
+
+    def run(idx, lo, hi):
+        m = hi - lo
+        od = torch.zeros((m, topk), device=dev)
+        oi = torch.zeros((m, topk), device=dev, dtype=torch.int32)
+        on = torch.zeros(m, device=dev, dtype=torch.int32)
+        rq.metrics_reset()
+        idx.query_batch_device(q[lo:hi].data_ptr(), m, d, probe, topk, od.data_ptr(), oi.data_ptr(), on.data_ptr())
+        torch.cuda.synchronize()
+        mt = rq.metrics()
+        return od.view(torch.int32), oi, on, (mt["rough"], mt["precise"], mt["query"]), ix.last_profile()["retries"]
+
+    def fresh():
+        return rq.RaBitQ.build(x, centres, P)
+
+    try:
+        idx = fresh()
+        a = run(idx, 0, nq)
+        idx.close()
+        ix.set_option("pass_overlap", 0)
+        idx = fresh()
+        b = run(idx, 0, nq)
+        idx.close()
+        idx = fresh()
+        c1, c2 = run(idx, 0, cut), run(idx, cut, nq)
+        idx.close()
+    finally:
+        ix.set_option("pass_overlap", 1)
+    for name, r in (("overlapped call", a), ("serial call", b), ("second slice", c2)):
+        print(f"{name}: retries {r[4]}, metrics {r[3]}")
+        assert r[4] >= 4, f"{name}: the test no longer exercises the overflow path"
+    for i in range(3):
+        assert torch.equal(a[i], b[i]), i
+        assert torch.equal(a[i][:cut], c1[i]) and torch.equal(a[i][cut:], c2[i]), i
+    assert a[3] == b[3] and a[3] == tuple(s1 + s2 for s1, s2 in zip(c1[3], c2[3]))
+    oidx = oracle.OracleIndex.build(x, centres, P)
+    cnt = a[2].cpu().numpy()
+    for p in planted:
+        assert cnt[p] == topk, (p, cnt[p])
+        od, oi = oidx.query(queries[p], probe, topk, False)
+        assert np.array_equal(a[1][p].cpu().numpy(), oi), p
+        assert np.array_equal(a[0][p].cpu().numpy().view(np.uint32), od.view(np.uint32)), p
+    oidx.close()
+
+
 # ---- batches in flight: begin / end halves of the device batch call -----------------------------------
 def test_begin_end_batches_overlap_and_match_sync(rq):
     import torch
