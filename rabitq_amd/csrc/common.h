@@ -54,6 +54,21 @@ __device__ __forceinline__ int32_t cvtps_epi32(float x) {
     return (int32_t)0x80000000;
 }
 
+// One 16-byte-per-lane LDS-DMA copy: lane l's 16 bytes at gsrc land at LDS byte address lds_dst + 16 l
+// (lds_dst wave-uniform).  Issued from an asm statement so that the compiler's own s_waitcnt bookkeeping
+// does not drain it early; completion is counted by hand (s_waitcnt vmcnt(N)) before the first read
+// (a read by another wave of the block: before the barrier that precedes it).
+__device__ __forceinline__ void glds16(const void *gsrc, uint32_t lds_dst) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(gsrc), "s"(lds_dst)
+                 : "memory");
+}
+__device__ __forceinline__ uint32_t lds_addr(const void *p) {
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
+}
+
 // Survivor record produced by the scan kernel and consumed by rerank / sort / replay.
 struct __attribute__((aligned(16))) SurvRec {
     uint32_t pos;    // cluster-order position j (src/rabitq.rs:348)

@@ -95,6 +95,9 @@ struct StagePlan {
     bool arena_stage;    // can exceed the uniform survivor capacity: appends to the shared arena
     bool placed;         // grouped before the quantisation, which wrote its operand rows in place
     bool want_table;     // one block per existing (list, tile), if the index has the table
+    bool prefilter;      // stage_finish_large: the thresholds are finite, the survivors go through the index's shadow rows first ...
+    bool rerank_q8;      // ... the 8-bit ones ...
+    bool rerank_ring;    // ... which travel through the LDS ring (accurate_ring8_kernel; else accurate_filtered8_kernel's registers)
     uint32_t slot_hi, stage_pairs;  // probe slots the stage can touch, and its work items
     uint32_t dense_cells;           // cells of the dense run directory (0: runs are appended and sorted)
     uint32_t tile, tiles_per_group;
@@ -149,6 +152,20 @@ static void plan_stages(const rq_index *idx, uint32_t nprobe, uint64_t first_hi,
         if (lo < settle && hi > settle) hi = settle;
     }
 }
+
+// The rerank pre-filter's route for the 8-bit shadow rows (kernels_rerank.h): true = accurate_ring8_kernel, false =
+// accurate_filtered8_kernel.  The ring is instantiated for the dimensions whose rows are 4 .. 16 pieces of 16 bytes (dim 64, 128, 192,
+// 256); beside the query and the probed lists' maps (at most RQ_ACC8_LDS_PROBES of them: the ring kernel reads the maps from LDS only)
+// its two slots take at most 1 + 16 + 64 KB there, inside the 156 KB the kernels are registered with (ensure_kernel_attributes).
+// scan_debug bit 32768 (measurements, tests) keeps the register kernel.
+static inline uint32_t rerank_ring_lds(uint32_t dim, uint32_t nprobe) { return dim * 4u + nprobe * 16u + q8_ring_bytes(RQ_RING_V, dim); }
+static inline bool rerank_ring_rule(uint32_t dim, uint32_t nprobe, uint32_t dbg) {
+    return !(dbg & 32768u) && (dim == 64 || dim == 128 || dim == 192 || dim == 256) && nprobe <= RQ_ACC8_LDS_PROBES;
+}
+// whether a pass's stages finish with the full-chip kernels (stage_finish_large: rerank, run-directory sort, replay) -- large batches,
+// range calls, and small batches whose survivor buffers are large (queries re-run after an overflow: tens of thousands of survivors
+// each, which one block per query would rerank and order alone)
+static inline bool finish_large(const PassPlan &pl, const QueryParams &qp) { return qp.range || pl.large || qp.cap > 4 * RQ_DEFAULT_CAP; }
 
 // has_row_map: the pass re-runs overflowed queries of an earlier one; ext_lists: the probe lists come from the caller.
 static void plan_pass(const rq_index *idx, const QueryParams &qp, bool has_row_map, bool ext_lists, PassPlan &pl) {
@@ -274,6 +291,10 @@ static void plan_pass(const rq_index *idx, const QueryParams &qp, bool has_row_m
             const uint64_t cells = (uint64_t)((s.s_hi - 1) >> 6) - (s.s_lo >> 6) + 2ull * s.slot_hi + 2;
             if (cells <= qp.cap) s.dense_cells = (uint32_t)cells;
         }
+        // past the first stage the thresholds are finite: survivors go through the shadow rows first (stage_finish_large)
+        s.prefilter = (i > 0 || qp.thr_init) && !(pl.dbg & 512);
+        s.rerank_q8 = s.prefilter && idx->base_q8.p != nullptr;
+        s.rerank_ring = s.rerank_q8 && rerank_ring_rule(dim, nprobe, pl.dbg);
     }
 
     // ---- the quantisation ---------------------------------------------------------------------------------------------
@@ -333,6 +354,8 @@ static void plan_pass(const rq_index *idx, const QueryParams &qp, bool has_row_m
             fprintf(stderr, "[rabitq_hip] plan: stage=%u lo=%u hi=%u matrix=%d cluster_major=%d ranked=%d additive=%d arena=%d placed=%d table=%d dense_cells=%u slot_hi=%u\n",
                     i, s.s_lo, s.s_hi, (int)s.matrix, (int)s.cluster_major, (int)s.ranked, (int)s.additive, (int)s.arena_stage, (int)s.placed, (int)s.want_table,
                     s.dense_cells, s.slot_hi);
+            // (outside the `plan:` lines, whose token set is fixed)
+            if (s.rerank_q8 && finish_large(pl, qp)) fprintf(stderr, "[rabitq_hip] stage %u: rerank=%s\n", i, s.rerank_ring ? "ring" : "regs");
         }
     }
 }

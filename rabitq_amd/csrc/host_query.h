@@ -598,15 +598,28 @@ struct Pass {
         pf.end();
     }
 
+    // the 8-bit pre-filter with its rows through the LDS ring (plan: rerank_ring_rule; dim = 16 NPC)
+    template <int NPC>
+    void launch_ring8(uint32_t gx, const QSeg &seg) {
+        accurate_ring8_kernel<RQ_RING_V, NPC><<<dim3(gx, nq), 256, rerank_ring_lds(dim, nprobe), st>>>(
+            ws.surv.p, ws.surv_cnt.p, seg, idx->base.p, idx->base_q8.p, idx->list_q8.p, qpad, rerank_order, ws.thr.p, probe_cluster, nprobe,
+            ws.nshadow.p, k);
+    }
+
     // large batch: full-chip rerank, then run-directory sort, then one replay wave per query
     void stage_finish_large(StageRun &r) {
         const uint32_t dense_cells = r.s.dense_cells;
         const QSeg &seg = r.seg;
         pf.begin(PF_RERANK);
         const uint32_t gx = std::max(1u, std::min(16u, 4096u / std::max(nq, 1u)));
-        // past the first stage the thresholds are finite: survivors go through the fp16 shadow rows first
-        const bool prefilter = (r.no > 0 || qp.thr_init) && !(pl.dbg & 512);
-        if (idx->base_q8.p && prefilter)
+        // past the first stage the thresholds are finite: survivors go through the shadow rows first (the plan's rule, and its route)
+        const bool prefilter = r.s.prefilter;
+        if (r.s.rerank_ring) {
+            if (dim == 64) launch_ring8<4>(gx, seg);
+            else if (dim == 128) launch_ring8<8>(gx, seg);
+            else if (dim == 192) launch_ring8<12>(gx, seg);
+            else launch_ring8<16>(gx, seg);
+        } else if (r.s.rerank_q8)
             accurate_filtered8_kernel<<<dim3(gx, nq), 256, (size_t)dim * sizeof(float) + (nprobe <= RQ_ACC8_LDS_PROBES ? (size_t)nprobe * 16 : 0), st>>>(
                 ws.surv.p, ws.surv_cnt.p, seg, idx->base.p, idx->base_q8.p, idx->list_q8.p, qpad, dim, rerank_order, ws.thr.p,
                 probe_cluster, nprobe, ws.nshadow.p, k);
@@ -710,10 +723,8 @@ static rq_status run_pass(Workspace &ws, const QueryCall &call, const QueryParam
         StageRun r{pl.st[i], i};
         RQC(c.stage_group_fill(r));
         RQC(c.stage_scan(r));
-        // (a small batch whose survivor buffers are large -- queries re-run after an overflow: tens of thousands of survivors each --
-        // takes the large-batch kernels: one block per query would rerank and order those alone, they spread them over the chip)
-        if (!qp.range && !pl.large && qp.cap <= 4 * RQ_DEFAULT_CAP) c.stage_finish_small(r);
-        else c.stage_finish_large(r);
+        if (finish_large(pl, qp)) c.stage_finish_large(r);  // (host_plan.h: also a small batch whose survivor buffers are large)
+        else c.stage_finish_small(r);
     }
     RQC(c.results(total_span));
     if (defer) return RQ_OK;

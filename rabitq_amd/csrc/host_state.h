@@ -836,6 +836,10 @@ static rq_status ensure_kernel_attributes() {
         set(reinterpret_cast<const void *>(merge_smallest_u64_kernel), 16384 * 8, "merge_smallest_u64_kernel");
         set(reinterpret_cast<const void *>(group_rank_kernel), 32768 * 4, "group_rank_kernel");
         set(reinterpret_cast<const void *>(sb_front_kernel), 140 * 1024, "sb_front_kernel");
+        set(reinterpret_cast<const void *>(accurate_ring8_kernel<RQ_RING_V, 4>), 156 * 1024, "accurate_ring8_kernel<4>");
+        set(reinterpret_cast<const void *>(accurate_ring8_kernel<RQ_RING_V, 8>), 156 * 1024, "accurate_ring8_kernel<8>");
+        set(reinterpret_cast<const void *>(accurate_ring8_kernel<RQ_RING_V, 12>), 156 * 1024, "accurate_ring8_kernel<12>");
+        set(reinterpret_cast<const void *>(accurate_ring8_kernel<RQ_RING_V, 16>), 156 * 1024, "accurate_ring8_kernel<16>");
         set(reinterpret_cast<const void *>(sort_runs_mid_kernel), RQ_SORT_MID_LDS_WORDS * 8, "sort_runs_mid_kernel");  // (+ 34 KiB of static LDS)
         set(reinterpret_cast<const void *>(range_sort_block_kernel<1024, RQ_RANGE_TILE>), RQ_RANGE_TILE * 8, "range_sort_block_kernel");
         set(reinterpret_cast<const void *>(range_sort_tile_kernel), RQ_RANGE_TILE * 8, "range_sort_tile_kernel");

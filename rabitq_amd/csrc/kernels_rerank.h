@@ -147,6 +147,10 @@ __global__ __launch_bounds__(256) void half_rows_kernel(const float *__restrict_
 //   bound(cur, q, hf, up, dt, err)  per survivor of the pair: dt = ||x~ - q||^2 of its shadow row x~ (both lanes hold it), err >= ||x - x~||
 //                             (inf: never rejected)
 //   exact(rec, q, hf)         the exact distance of a queued survivor
+//   P::RING                   the shadow rows travel through an LDS ring, one round ahead of the test (ShadowQ8Ring below): the
+//                             records are then kept TWO rounds ahead, ring_issue(records of the next round, slot) starts the copies
+//                             of the next round's rows before this round is tested, ring_wait(whether copies were just issued)
+//                             retires this round's, and bound() reads slot ring_slot
 // grid (gx, nq), block 256 = 128 V survivors per round, two lanes each.  Round: shadow-row test of 128 V survivors; the ones it
 // cannot reject queue up in LDS and are re-ranked exactly 128 at a time, so both phases keep every lane busy.
 // The kernel is a chain of dependent gathers (survivor record -> its list's map or tier record and its shadow row -> the f32 row of
@@ -168,9 +172,13 @@ __device__ __forceinline__ void rerank_prefiltered(P &pol, SurvRec *__restrict__
     SurvRec *recs = surv + seg.at(b);
     const uint32_t hf = threadIdx.x & 1, pair = threadIdx.x >> 1;
     const uint32_t i_first = blockIdx.x * (128 * V), stride = gridDim.x * (128 * V);
-    SurvRec nxt[V];
+    SurvRec nxt[V], nxt2[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) nxt[v] = recs[i_first + 128 * v + pair < n ? i_first + 128 * v + pair : 0u];
+    if constexpr (P::RING) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) nxt2[v] = recs[i_first + stride + 128 * v + pair < n ? i_first + stride + 128 * v + pair : 0u];
+    }
     for (uint32_t c = threadIdx.x * 4; c < dim; c += 1024)
         *reinterpret_cast<float4 *>(acc_q + c) = *reinterpret_cast<const float4 *>(qpad + (uint64_t)b * dim + c);
     pol.stage(acc_q + dim, b);
@@ -184,14 +192,39 @@ __device__ __forceinline__ void rerank_prefiltered(P &pol, SurvRec *__restrict__
         if (hf == 0) recs[j].accurate = r;
     };
     uint32_t rejected = 0;
+    if constexpr (P::RING) {
+        pol.ring_slot = 0;
+        if (test && i_first < n) pol.ring_issue(nxt, 0u);  // (block-uniform)
+    }
     for (uint32_t i0 = i_first; i0 < n; i0 += stride) {
         uint32_t iv[V];
         bool exact[V];
         SurvRec cur[V];
+        if constexpr (P::RING) {
+            // the next round's rows are requested before this round's are waited for: they fly while this round is tested.  The
+            // records of the round after that are requested behind them (ring_wait counts the copies only).
 #pragma unroll
-        for (int v = 0; v < V; ++v) {  // this round's records, and the next round's requested (clamped: the last prefetch re-reads record 0)
-            iv[v] = i0 + 128 * v + pair, exact[v] = iv[v] < n, cur[v] = nxt[v];
-            nxt[v] = recs[iv[v] + stride < n ? iv[v] + stride : 0u];
+            for (int v = 0; v < V; ++v) {
+                iv[v] = i0 + 128 * v + pair, exact[v] = iv[v] < n, cur[v] = nxt[v], nxt[v] = nxt2[v];
+                // the records are pinned down HERE, before the next copies are issued (they were requested a round ago, behind this
+                // round's copies): the compiler's own wait for them would otherwise come where their fields are first used, behind
+                // ring_issue, and drain the copies just issued with it.  Requests return in order, so this wait also retires
+                // this round's copies; ring_wait states that condition by itself instead of leaning on where the compiler waits.
+                asm volatile("" ::"v"(nxt[v].pos), "v"(nxt[v].slot));
+            }
+            if (test) {
+                const bool more = i0 + stride < n;  // block-uniform
+                if (more) pol.ring_issue(nxt, pol.ring_slot ^ 1u);
+                pol.ring_wait(more);
+            }
+#pragma unroll
+            for (int v = 0; v < V; ++v) nxt2[v] = recs[iv[v] + 2 * stride < n ? iv[v] + 2 * stride : 0u];
+        } else {
+#pragma unroll
+            for (int v = 0; v < V; ++v) {  // this round's records, and the next round's requested (clamped: the last prefetch re-reads record 0)
+                iv[v] = i0 + 128 * v + pair, exact[v] = iv[v] < n, cur[v] = nxt[v];
+                nxt[v] = recs[iv[v] + stride < n ? iv[v] + stride : 0u];
+            }
         }
         if (test && exact[0]) {  // (a pair past the end has nothing to test; its survivor 0 is the lowest)
             float dt[V], err[V];
@@ -222,6 +255,7 @@ __device__ __forceinline__ void rerank_prefiltered(P &pol, SurvRec *__restrict__
             if (threadIdx.x == 0) qn = waiting;
             __syncthreads();
         }
+        if constexpr (P::RING) pol.ring_slot ^= 1u;
     }
     if (pair < qn) exact_of(queue[pair]);
     uint32_t rj = hf == 0 ? rejected : 0u;  // per-query counter (one address per query: no hot spot)
@@ -262,6 +296,7 @@ __device__ __forceinline__ void shadow16_bound(const uint16_t *__restrict__ x, c
 }
 
 struct ShadowHalf {  // fp16 rows beside the f32 ones (untiered, plain)
+    static constexpr bool RING = false;
     static constexpr int V = 1;
     const float *base;
     const _Float16 *base_h;
@@ -307,6 +342,7 @@ __global__ __launch_bounds__(256) void accurate_filtered_kernel(SurvRec *__restr
 // the bytes over the host link for the ones the test rejects).  2*dim bytes per survivor instead of 4*dim for the ones the test rejects.
 // ------------------------------------------------------------------------------------------------
 struct ShadowPlane {
+    static constexpr bool RING = false;
     static constexpr int V = 1;
     const BaseView &base;       // (the kernel's argument itself: its fields stay scalar operands)
     const uint32_t *probe_row;  // the query's probed lists, by slot
@@ -465,11 +501,62 @@ __global__ __launch_bounds__(256) void q8_encode_kernel(const float *__restrict_
     }
 }
 
+// The test quantities of the V survivors of a lane pair from their 8-bit rows: piece(v, g) = the 16 codes of group g (dimensions
+// 16 g .. 16 g + 15) of survivor v's row, par[v] = its list's map.  Lane half hf takes the groups 2u + hf; the pieces of every survivor
+// are requested before any is used.  ONE copy of the arithmetic: whatever route the bytes take, the decisions are the same.
+template <int V, class Piece>
+__device__ __forceinline__ void q8_bound(const float4 (&par)[V], Piece piece, const float *q_lds, uint32_t dim, uint32_t hf, float up,
+                                         float (&dt)[V], float (&err)[V]) {
+    const uint32_t ngrp = dim / 16;
+    float d0[V], d1[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) d0[v] = 0.0f, d1[v] = 0.0f;
+    for (uint32_t g0 = hf; g0 < ngrp; g0 += 8) {  // four 16-byte pieces of each row in flight per lane
+        uint4 cv[V][4];
+#pragma unroll
+        for (int v = 0; v < V; ++v)
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (g0 + 2 * u < ngrp) cv[v][u] = piece(v, g0 + 2 * u);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (!(g0 + 2 * u < ngrp)) continue;
+            const float *q = q_lds + 16 * (g0 + 2 * u);
+#pragma unroll
+            for (int wi = 0; wi < 4; ++wi) {
+                const float4 qa = *reinterpret_cast<const float4 *>(q + 4 * wi);
+#pragma unroll
+                for (int v = 0; v < V; ++v) {
+                    const uint32_t wv = wi == 0 ? cv[v][u].x : (wi == 1 ? cv[v][u].y : (wi == 2 ? cv[v][u].z : cv[v][u].w));
+                    const float e0 = fmaf(par[v].y, (float)(wv & 255u), par[v].x) - qa.x;
+                    const float e1 = fmaf(par[v].y, (float)((wv >> 8) & 255u), par[v].x) - qa.y;
+                    const float e2 = fmaf(par[v].y, (float)((wv >> 16) & 255u), par[v].x) - qa.z;
+                    const float e3 = fmaf(par[v].y, (float)(wv >> 24), par[v].x) - qa.w;
+                    d0[v] = fmaf(e0, e0, d0[v]), d1[v] = fmaf(e1, e1, d1[v]), d0[v] = fmaf(e2, e2, d0[v]), d1[v] = fmaf(e3, e3, d1[v]);
+                }
+            }
+            // (the query pieces of the later groups are read when their turn comes: hoisted, the sixteen 16-byte LDS reads of
+            // a round held 64 registers and cost the kernel a wave per SIMD)
+            asm volatile("" ::: "memory");
+        }
+    }
+    const float sqd = sqrtf((float)dim) * 1.001f;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        dt[v] = d0[v] + d1[v];
+        dt[v] += __shfl_xor(dt[v], 1, 2);
+        // >= ||x - x^||: the largest row norm of the error measured over the list (dimensions q8_encode_kernel measures it for),
+        // else sqrt(dim) max |x_i - x^_i|   (inf: a list that is never rejected)
+        err[v] = q8_row_norms(dim) ? par[v].w * up : (par[v].z * up) * sqd;
+    }
+}
+
 // accurate_filtered_kernel with the 8-bit shadow: two survivors per lane pair (lane half hf takes the 16-dimension groups 2u + hf of
 // a row; both survivors' pieces are requested before either is used: a 128-byte row is four 16-byte loads per lane, too few in
 // flight to keep the memory busy one row at a time)
 struct ShadowQ8 {
     static constexpr int V = 2;
+    static constexpr bool RING = false;
     const float *base;
     const uint8_t *base_q8;
     const float4 *list_q8;      // per list: lo, s, max |x_i - x^_i|, max ||x - x^||
@@ -485,7 +572,6 @@ struct ShadowQ8 {
         lpar = l;
     }
     __device__ __forceinline__ void bound(const SurvRec (&cur)[2], const float *q_lds, uint32_t hf, float up, float (&dt)[2], float (&err)[2]) const {
-        const uint32_t ngrp = dim / 16;
         float4 par[2];
         const uint8_t *x[2];
 #pragma unroll
@@ -493,45 +579,7 @@ struct ShadowQ8 {
             par[v] = lpar ? lpar[cur[v].slot] : list_q8[probe_row[cur[v].slot]];
             x[v] = base_q8 + (uint64_t)cur[v].pos * dim;
         }
-        float d0[2] = {0.0f, 0.0f}, d1[2] = {0.0f, 0.0f};
-        for (uint32_t g0 = hf; g0 < ngrp; g0 += 8) {  // four 16-byte pieces of each row in flight per lane
-            uint4 cv[2][4];
-#pragma unroll
-            for (int v = 0; v < 2; ++v)
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (g0 + 2 * u < ngrp) cv[v][u] = *reinterpret_cast<const uint4 *>(x[v] + 16 * (g0 + 2 * u));
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (!(g0 + 2 * u < ngrp)) continue;
-                const float *q = q_lds + 16 * (g0 + 2 * u);
-#pragma unroll
-                for (int wi = 0; wi < 4; ++wi) {
-                    const float4 qa = *reinterpret_cast<const float4 *>(q + 4 * wi);
-#pragma unroll
-                    for (int v = 0; v < 2; ++v) {
-                        const uint32_t wv = wi == 0 ? cv[v][u].x : (wi == 1 ? cv[v][u].y : (wi == 2 ? cv[v][u].z : cv[v][u].w));
-                        const float e0 = fmaf(par[v].y, (float)(wv & 255u), par[v].x) - qa.x;
-                        const float e1 = fmaf(par[v].y, (float)((wv >> 8) & 255u), par[v].x) - qa.y;
-                        const float e2 = fmaf(par[v].y, (float)((wv >> 16) & 255u), par[v].x) - qa.z;
-                        const float e3 = fmaf(par[v].y, (float)(wv >> 24), par[v].x) - qa.w;
-                        d0[v] = fmaf(e0, e0, d0[v]), d1[v] = fmaf(e1, e1, d1[v]), d0[v] = fmaf(e2, e2, d0[v]), d1[v] = fmaf(e3, e3, d1[v]);
-                    }
-                }
-                // (the query pieces of the later groups are read when their turn comes: hoisted, the sixteen 16-byte LDS reads of
-                // a round held 64 registers and cost the kernel a wave per SIMD)
-                asm volatile("" ::: "memory");
-            }
-        }
-        const float sqd = sqrtf((float)dim) * 1.001f;
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            dt[v] = d0[v] + d1[v];
-            dt[v] += __shfl_xor(dt[v], 1, 2);
-            // >= ||x - x^||: the largest row norm of the error measured over the list (dimensions q8_encode_kernel measures it for),
-            // else sqrt(dim) max |x_i - x^_i|   (inf: a list that is never rejected)
-            err[v] = q8_row_norms(dim) ? par[v].w * up : (par[v].z * up) * sqd;
-        }
+        q8_bound<2>(par, [&](int v, uint32_t g) { return *reinterpret_cast<const uint4 *>(x[v] + 16 * g); }, q_lds, dim, hf, up, dt, err);
     }
     __device__ __forceinline__ float exact(const SurvRec &r, const float *q_lds, uint32_t hf) const {
         return exact_l2_pair(base + (uint64_t)r.pos * dim + 4 * hf, q_lds, dim, hf);
@@ -551,6 +599,95 @@ __global__ __launch_bounds__(256, RQ_ACC8_WAVES) void accurate_filtered8_kernel(
                                                                  uint32_t *__restrict__ nshadow, uint32_t nlists) {
     ShadowQ8 pol{base, base_q8, list_q8, probe_cluster, nprobe, nlists, dim, nullptr};
     rerank_prefiltered(pol, surv, surv_cnt, seg, qpad, dim, order, thr_start, nshadow);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The 8-bit shadow rows through an LDS ring (dimensions 64 .. 256).  In accurate_filtered8_kernel a round's loads and its arithmetic
+// are serialised inside every wave (request 8 pieces per lane, wait, ~400 VALU instructions per 64 survivors, barriers), and a wave load touches 32
+// rows for 32 bytes each.  Here a wave copies the rows of ITS OWN 32 lane pairs into LDS with global_load_lds_dwordx4 (glds16): NPC =
+// dim / 16 consecutive lanes fetch one row, so a request covers whole rows, one instruction lands 1 KiB, and no register holds the
+// bytes on the way.  Each wave owns two slots of 32 V rows; the copies of round r + 1 are issued before round r is tested and stay in
+// flight under it.  The slots are private to the wave, so what orders a read behind the copies is the wave's own counted
+// s_waitcnt vmcnt (ring_wait: the copies just issued are the youngest requests, everything older has landed) and nothing else: no
+// barrier is added, and a slot is refilled a round after the values read from it were consumed.
+// Row r of a wave's slot lies at 16 NPC r; its 16-byte piece g lies at position q8_ring_piece(r, g): the lane groups of ds_read_b128
+// (16 lanes = 8 lane pairs, which read the same piece index of 8 different rows) would otherwise meet on the same banks 2 (dim 64),
+// 4 (128) or 8 (256) times over; the copying lane picks the piece it fetches, so the exchange costs nothing.  (dim 192: 12 pieces do
+// not exchange by xor; left as it is, two-way.)
+// The arithmetic is q8_bound, the one accurate_filtered8_kernel runs: decisions, counters and outputs are the same bit for bit.
+// ------------------------------------------------------------------------------------------------
+template <int NPC>
+__device__ __forceinline__ uint32_t q8_ring_piece(uint32_t r, uint32_t g) {
+    if constexpr (NPC == 4) return g ^ (2u * ((r >> 2) & 1u));
+    if constexpr (NPC == 8) return g ^ (2u * ((r >> 1) & 3u));
+    if constexpr (NPC == 16) return g ^ (2u * (r & 7u));
+    return g;
+}
+__host__ __device__ constexpr uint32_t q8_ring_bytes(uint32_t v, uint32_t dim) { return 2u * 4u * 32u * v * dim; }  // two slots, four waves, 32 v rows each
+template <int VV, int NPC>
+struct ShadowQ8Ring : ShadowQ8 {
+    static constexpr int V = VV;
+    static constexpr bool RING = true;
+    static constexpr uint32_t DIM = 16u * NPC, WAVE_BYTES = 32u * VV * DIM, SLOT_BYTES = 4u * WAVE_BYTES, NI = VV * NPC / 2;  // NI: copies per wave and round
+    uint32_t rows;         // this lane pair's first row in slot 0, in bytes from the start of the dynamic LDS
+    uint32_t wave_lds;     // LDS byte address of this wave's part of slot 0 (wave-uniform)
+    uint32_t ring_slot;    // the slot the current round reads
+    __device__ __forceinline__ void stage(float *behind, uint32_t b) {
+        ShadowQ8::stage(behind, b);  // (the launch rule keeps nprobe <= RQ_ACC8_LDS_PROBES: the maps are in LDS)
+        const uint32_t ring = 4u * DIM + 16u * nprobe, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        wave_lds = lds_addr(dyn()) + ring + wave * WAVE_BYTES;
+        rows = ring + wave * WAVE_BYTES + ((threadIdx.x & 63u) >> 1) * DIM;
+    }
+    // The block's dynamic LDS, named here so that every read below is an LDS read to the compiler: through the generic pointers of
+    // ShadowQ8 (lpar) it emits FLAT loads, which count on vmcnt too -- waiting for one would drain the copies in flight.
+    __device__ __forceinline__ static const uint8_t *dyn() {
+        extern __shared__ __attribute__((aligned(16))) uint8_t rq_ring_lds[];
+        return rq_ring_lds;
+    }
+    // the rows of the records nx (lane pair p holds the records of rows p and, V = 2, 32 + p) -> slot
+    __device__ __forceinline__ void ring_issue(const SurvRec (&nx)[VV], uint32_t slot) const {
+        const uint32_t lane = threadIdx.x & 63u, dst = wave_lds + slot * SLOT_BYTES;
+#pragma unroll
+        for (uint32_t j = 0; j < NI; ++j) {
+            const uint32_t v = j / (NPC / 2), at = 64u * (j % (NPC / 2)) + lane, r = at / NPC, p = at % NPC;  // position p of row r (of survivor v)
+            const uint32_t pos = (uint32_t)__shfl((int)nx[v < VV ? v : 0].pos, (int)(2u * r), 64);
+            glds16(base_q8 + (uint64_t)pos * DIM + 16u * q8_ring_piece<NPC>(r, p), dst + 1024u * j);
+        }
+    }
+    // everything but the NI copies just issued has landed (requests return in order); none issued: everything has
+    __device__ __forceinline__ void ring_wait(bool issued) const {
+        if (issued) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __device__ __forceinline__ void bound(const SurvRec (&cur)[VV], const float *q_lds, uint32_t hf, float up, float (&dt)[VV], float (&err)[VV]) const {
+        float4 par[VV];
+#pragma unroll
+        for (int v = 0; v < VV; ++v) par[v] = reinterpret_cast<const float4 *>(dyn() + 4u * DIM)[cur[v].slot];
+        const uint8_t *x = dyn() + rows + ring_slot * SLOT_BYTES;
+        const uint32_t r = (threadIdx.x & 63u) >> 1;
+        q8_bound<VV>(par, [&](int v, uint32_t g) { return *reinterpret_cast<const uint4 *>(x + v * (32u * DIM) + 16u * q8_ring_piece<NPC>(r, g)); },
+                     q_lds, DIM, hf, up, dt, err);
+    }
+};
+// Geometry, by measurement on the headline workload (profiles/rerank_ring_ab_runs.txt): one survivor per lane pair and round -- 16 dim
+// bytes of ring per wave, four blocks per CU at dim 128 as in accurate_filtered8_kernel -- beat the parent; two per pair (two blocks
+// per CU) lost to it.  The register budget follows the blocks the ring's LDS leaves room for.
+#ifndef RQ_RING_V
+#define RQ_RING_V 1
+#endif
+__host__ __device__ constexpr int q8_ring_waves(int npc) { return npc <= 8 ? 4 : 2; }
+template <int VV, int NPC>
+__global__ __launch_bounds__(256, q8_ring_waves(NPC)) void accurate_ring8_kernel(SurvRec *__restrict__ surv, const unsigned long long *__restrict__ surv_cnt,
+                                                             const QSeg seg, const float *__restrict__ base,
+                                                             const uint8_t *__restrict__ base_q8, const float4 *__restrict__ list_q8,
+                                                             const float *__restrict__ qpad, const uint32_t *__restrict__ order,
+                                                             const float *__restrict__ thr_start,
+                                                             const uint32_t *__restrict__ probe_cluster, uint32_t nprobe,
+                                                             uint32_t *__restrict__ nshadow, uint32_t nlists) {
+    ShadowQ8Ring<VV, NPC> pol;
+    pol.base = base, pol.base_q8 = base_q8, pol.list_q8 = list_q8, pol.probe_row = probe_cluster, pol.nprobe = nprobe, pol.nlists = nlists;
+    pol.dim = 16u * NPC, pol.lpar = nullptr;
+    rerank_prefiltered(pol, surv, surv_cnt, seg, qpad, 16u * NPC, order, thr_start, nshadow);
 }
 
 // ---- the same three phases as separate launches: better for large batches, where all queries'

@@ -39,20 +39,7 @@ typedef int v4i32 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 #endif
 
-// One 16-byte-per-lane LDS-DMA copy: lane l's 16 bytes at gsrc land at LDS byte address lds_dst + 16 l
-// (lds_dst wave-uniform).  Issued from an asm statement so that the compiler's own s_waitcnt bookkeeping
-// does not drain it early; completion is counted by hand (s_waitcnt vmcnt(N)) before the barrier that
-// precedes the first read.
-__device__ __forceinline__ void glds16(const void *gsrc, uint32_t lds_dst) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds_dst)
-                 : "memory");
-}
-__device__ __forceinline__ uint32_t lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
+// (glds16 / lds_addr, the LDS-DMA copy the query ring is filled with: common.h)
 
 // ADD (additive gate; dim <= 128, uniform survivor buffers): the rank-5 threshold S*(c, q) = sum_r u'_c[r] v'_q[r] + v4_q is replaced
 // by the additive lower bound
