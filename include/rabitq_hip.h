@@ -672,7 +672,10 @@ rq_status rq_set_profiling(int level);
  * key=value tokens per pass, per stage and per coarse ranking, which tests/test_option_paths_gpu.py reads; a large batch's stages whose survivors go through
  * the 8-bit shadow rows add a line `stage <i>: rerank=ring` or `rerank=regs`), 32768 the 8-bit rerank pre-filter reads its shadow rows
  * into registers (accurate_filtered8_kernel) where it would send them through the LDS ring (dimensions 64, 128, 192, 256 with at most
- * 1024 probed lists: accurate_ring8_kernel) -- the switch for A/B runs, bench.py --option scan_debug=32768.  Any other bit is refused with
+ * 1024 probed lists: accurate_ring8_kernel) -- the switch for A/B runs, bench.py --option scan_debug=32768 --, 65536 the pre-filtered coarse ranking of
+ * a big batch over 4096 .. 8192 lists (dim <= 256) writes the nq x k matrix of approximate distances and selects from it
+ * (coarse_approx_kernel + select_refine_tiled_kernel, trace `coarse=prefilter_tiled`) where it would emit candidates straight from the
+ * matrix-core pass (coarse_candidates_kernel + refine_candidates_kernel, `coarse=prefilter_fused`).  Any other bit is refused with
  * RQ_ERR_INVALID by this library: the TIMING ABLATIONS of the matrix-core scan (1, 2, 4, 64, 1024, 8192: results are WRONG) and
  * its in-kernel cycle counters (256) are compiled only into the developer build (make -C rabitq_amd/csrc dev ->
  * librabitq_hip_dev.so, -DRQ_DEV_ABLATIONS; scripts/exp/ select it through RABITQ_HIP_SO), so the shipped kernels carry none

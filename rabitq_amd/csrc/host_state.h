@@ -479,8 +479,12 @@ __global__ void unpack_topk_keys_kernel(const unsigned long long *__restrict__ k
 // coarse ranking distances (src/rabitq.rs:283-287), every query against the lists [first, first + k) of cent_t
 static std::atomic<int> g_coarse_impl{0};  // 0 auto, 1 LDS-broadcast kernels, 2 scalar-register kernel, 3 bf16-MFMA pre-filter + exact refinement wherever it applies (row in registers up to 8192 lists), 4 the same with the tile-minima selection wherever it applies
 static std::atomic<int> g_scan_dbg{0};
-// the probe selection runs one wave per query (row in registers) for these shapes, one block per query otherwise
-static bool select_is_wave(uint32_t k, uint32_t nprobe, uint32_t nq) { return nprobe <= 64 && k <= 8192 && nq >= 8; }
+// the probe selection runs one wave per query (row in registers) for these shapes, one block per query otherwise.
+// Up to 4096 lists only: select_probe_wave_kernel<128> (4097 .. 8192 lists; 256 VGPRs, 91 AGPRs and 325 spilled SGPRs) returned lists
+// beyond the true nprobe-th at 8000 and 8192 lists -- on ~2000 of 2048 mixture rows, against a float64 model and against the
+// block-per-query selection of the same rows (7000 and fewer were right) -- so those rows go to the block-per-query selection until
+// that instantiation is understood.  select_refine_wave_kernel<128> still calls it for its fall-back rows (coarse_impl 3 / dim > 512).
+static bool select_is_wave(uint32_t k, uint32_t nprobe, uint32_t nq) { return nprobe <= 64 && k <= 4096 && nq >= 8; }
 static void launch_coarse(const float *cent_t, const float *y, float *dist, uint32_t k, uint32_t dim, uint32_t nq,
                           uint32_t kstride, hipStream_t st) {
     const int impl = g_coarse_impl.load();
@@ -528,12 +532,46 @@ static bool coarse_prefilter_applies(const rq_index *idx, uint32_t nq, uint32_t 
     return (impl == 3 || impl == 4 || (impl == 0 && nq >= 2048)) && coarse_prefilter_has(idx->W) && std::isfinite(idx->cent_norm_max) &&
            idx->cent_bf.p != nullptr && nprobe <= 64 && nq >= 8 && idx->k >= 64 && nprobe >= 1 && idx->k <= 65536;
 }
-// redo: nq flags (only written / read when k > 8192)
+// coarse_candidates_kernel: the two centroid-tile images, then 4 waves x NT x 32 queries x ntile tile keys
+template <int W, int NT>
+static size_t coarse_candidates_lds_bytes(uint32_t ntile) { return assign_lds_bytes<W, NT>() + (size_t)4 * NT * 32 * ntile * 4; }
+#define RQ_LDS_PER_BLOCK (160u * 1024u)
+// The route without the nq x k matrix (coarse_candidates_kernel + refine_candidates_kernel): the automatic rule only, from 4096 lists
+// (below, rows of the matrix are short and the kernels that read them are not where the time goes) to 8192 (the tile keys of 128
+// queries stay in LDS), dim <= 256 (wider margins overflow the candidate slots, and this route has no second collect), and
+// only where the tile keys fit beside the centroid images (dim 256 stops at 7936 lists).  scan_debug bit 65536 keeps the two-kernel route.
+static bool coarse_fused_applies(const rq_index *idx, uint32_t nprobe, bool have_redo) {
+    const uint32_t k = idx->k, ntile = ceil_div(k, 32u);
+    if (g_coarse_impl.load() != 0 || (g_scan_dbg.load() & 65536) || !have_redo || k < 4096 || k > 8192 || idx->W > 4 || ntile < nprobe) return false;
+    const size_t images = 2 * (32 * ((size_t)idx->dim * 2 + 16) + 128);
+    return images + (size_t)4 * 32 * ntile * 4 <= RQ_LDS_PER_BLOCK;
+}
+// redo: nq words (the tiled selection's flags; the matrix-free route's candidate counts, then its flags); null: rows in registers only
 // y_bf: room for nq x dim bf16 (the query rows pre-rounded for the wide instantiation; any workspace buffer that is free at this point)
 static void launch_coarse_prefiltered(const rq_index *idx, const float *y, float *dist, uint32_t nq, uint32_t nprobe, uint32_t *out_cluster,
                                       float *out_dist, uint32_t out_stride, unsigned long long *fallback_rows, uint32_t *redo, hipStream_t st,
                                       uint16_t *y_bf) {
     const uint32_t k = idx->k, dim = idx->dim;
+    if (coarse_fused_applies(idx, nprobe, redo != nullptr)) {
+        const uint32_t ntile = ceil_div(k, 32u);
+        if (g_scan_dbg.load() & 16384) fprintf(stderr, "[rabitq_hip] plan: coarse=prefilter_fused nq=%u k=%u nprobe=%u\n", nq, k, nprobe);
+        // two query tiles per wave where their tile keys fit (dim <= 128 up to 4544 lists), else one
+#define RQ_CCK(WW, NT)                                                                                                                   \
+    coarse_candidates_kernel<WW, NT><<<ceil_div(nq, 128 * NT), 256, coarse_candidates_lds_bytes<WW, NT>(ntile), st>>>(                   \
+        y, idx->cent_bf.p, idx->cent_sqnorm.p, idx->cent_norm_max, nq, k, nprobe, dist, redo)
+        if (idx->W == 1 && coarse_candidates_lds_bytes<1, 2>(ntile) <= RQ_LDS_PER_BLOCK) RQ_CCK(1, 2);
+        else if (idx->W == 2 && coarse_candidates_lds_bytes<2, 2>(ntile) <= RQ_LDS_PER_BLOCK) RQ_CCK(2, 2);
+        else if (idx->W == 1) RQ_CCK(1, 1);
+        else if (idx->W == 2) RQ_CCK(2, 1);
+        else if (idx->W == 3) RQ_CCK(3, 1);
+        else RQ_CCK(4, 1);
+#undef RQ_CCK
+        refine_candidates_kernel<<<ceil_div(nq, 4), 256, 0, st>>>(dist, y, idx->centroids.p, k, dim, nprobe, out_cluster, out_dist, out_stride, nq, redo,
+                                                                  fallback_rows);
+        // rows that overflowed the slots hold exact-order distances now: the block-per-query selection takes them (it exits at once for the others)
+        select_probe_kernel<<<nq, 256, (size_t)nprobe * 8, st>>>(dist, k, nprobe, out_cluster, out_dist, 0u, out_stride, redo);
+        return;
+    }
     if (idx->W > 8) to_bf16_kernel<<<ceil_div((uint64_t)nq * dim / 8, 256), 256, 0, st>>>(y, (uint64_t)nq * dim, y_bf);
 #define RQ_CAP(WW, NT)                                                                                                      \
     coarse_approx_kernel<WW, NT><<<ceil_div(nq, 128 * NT), 256, assign_lds_bytes<WW, NT>(), st>>>(y, idx->cent_bf.p, idx->cent_sqnorm.p, nq, \
@@ -849,6 +887,12 @@ static rq_status ensure_kernel_attributes() {
         set(reinterpret_cast<const void *>(coarse_approx_kernel<6, 1>), (int)assign_lds_bytes<6, 1>(), "coarse_approx_kernel<6,1>");
         set(reinterpret_cast<const void *>(coarse_approx_kernel<8, 1>), (int)assign_lds_bytes<8, 1>(), "coarse_approx_kernel<8,1>");
         set(reinterpret_cast<const void *>(coarse_approx_kernel<12, 1>), (int)assign_lds_bytes<12, 1>(), "coarse_approx_kernel<12,1>");
+        set(reinterpret_cast<const void *>(coarse_candidates_kernel<1, 2>), (int)RQ_LDS_PER_BLOCK, "coarse_candidates_kernel<1,2>");
+        set(reinterpret_cast<const void *>(coarse_candidates_kernel<2, 2>), (int)RQ_LDS_PER_BLOCK, "coarse_candidates_kernel<2,2>");
+        set(reinterpret_cast<const void *>(coarse_candidates_kernel<1, 1>), (int)RQ_LDS_PER_BLOCK, "coarse_candidates_kernel<1,1>");
+        set(reinterpret_cast<const void *>(coarse_candidates_kernel<2, 1>), (int)RQ_LDS_PER_BLOCK, "coarse_candidates_kernel<2,1>");
+        set(reinterpret_cast<const void *>(coarse_candidates_kernel<3, 1>), (int)RQ_LDS_PER_BLOCK, "coarse_candidates_kernel<3,1>");
+        set(reinterpret_cast<const void *>(coarse_candidates_kernel<4, 1>), (int)RQ_LDS_PER_BLOCK, "coarse_candidates_kernel<4,1>");
         set(reinterpret_cast<const void *>(sb_finish_kernel<true>), 104 * 1024, "sb_finish_kernel");   // (+ 33 KiB of static LDS)
         set(reinterpret_cast<const void *>(sb_finish_kernel<false>), 104 * 1024, "sb_finish_kernel");  // (+ 49 KiB of static LDS)
 #define RQ_SBQ_ATTR(WW)                                                                                  \

@@ -861,3 +861,208 @@ __global__ __launch_bounds__(256, (W <= 4 ? 2 : 1)) void coarse_approx_kernel(co
         if (tile + 1 < ntile) next.land(asg_lds, (tile + 1) & 1u);
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// The pre-filter without the nq x k matrix (4096 <= k <= 8192, dim <= 256): coarse_candidates_kernel runs the matrix-core pass TWICE
+// and stores only what the refinement needs, refine_candidates_kernel is the tail of select_refine_tiled_kernel.
+// Orientation of assign_approx_kernel (lists = MFMA rows, queries = columns): a lane owns ONE query (column `col`, shared by the two
+// half-waves) and its 16 accumulator registers are 16 of a tile's 32 lists, so everything per query is lane-private.
+//   sweep 1: a'_j = |c_j|^2 - 2 <c~_j, y~> as in coarse_approx_kernel; the minimum of every 32-list tile, as a key, into LDS
+//            ([tile][query]: the 32 lanes of a half-wave read 32 consecutive words);
+//   between: per lane, tau = any bound with at least nprobe tile keys at or below it (the rule of bisect_loose; the half-waves count
+//            the even and the odd tiles), T2 = prefilter_bound(tau, ...): the threshold select_refine_tiled_kernel's first collect uses;
+//   sweep 2: the same MFMAs again (the same instruction sequence on the same operands: the values are sweep 1's, bit for bit); every
+//            list with a' <= T2 is appended -- its id, 16 bits -- to the query's RQ_COARSE_CAND slots in LDS (over the tile keys, dead
+//            by then: 32 queries x 256 x 2 bytes are the keys of 128 tiles, and k >= 4096).  The count keeps advancing past
+//            RQ_COARSE_CAND, the stores stop.
+//   after:   the slots of every row that fits go to the first RQ_COARSE_CAND words of the query's row of `dist` (nobody else's).
+// cand_cnt[q] = the count, 0xFFFFFFFF where the margin is not finite.  Comparisons are on the f32 values (a superset of what the key
+// comparison selects: -0 <= +0); NaN never compares true, and a NaN / inf row has no finite margin in the first place.
+// Rows past the last list are zeros with the norm RQ_COARSE_PAD_NORM: finite (no inf - inf), above every finite T2 (|T2| < 3.0e38
+// is what "finite" means below) and, should it ever be a tile's minimum, a tau that is not "finite" either; the last tile's are
+// masked by index as well.
+// dynamic LDS: the two images of CentTile<W>, then 4 waves x NT x ntile x 32 tile keys (coarse_candidates_lds_bytes, host_state.h).
+// ------------------------------------------------------------------------------------------------
+#define RQ_COARSE_PAD_NORM 3.0e38f
+// the bisection stops at any bound that selects nprobe .. nprobe + RQ_FUSED_WINDOW tile keys: narrower than bisect_loose's 12, because
+// a step costs this kernel ntile / 2 LDS reads per lane (a few per cent of a sweep) while every spare candidate is a store here and an
+// exact distance in refine_candidates_kernel, and a row past the slots has no second collect to fall back on
+#define RQ_FUSED_WINDOW 4u
+template <int W, int NT>
+__global__ __launch_bounds__(256) void coarse_candidates_kernel(const float *__restrict__ y /* nq x dim, rotated queries */,
+                                                                const uint16_t *__restrict__ cent_bf /* k x dim bf16 */,
+                                                                const float *__restrict__ cnorm, float cmax, uint32_t nq, uint32_t k,
+                                                                uint32_t nprobe, float *__restrict__ dist /* nq x k: candidate slots */,
+                                                                uint32_t *__restrict__ cand_cnt /* nq */) {
+    constexpr int DIM = 64 * W, NM = DIM / 16;
+    constexpr uint32_t ROWB = CentTile<W>::ROWB, TILEB = CentTile<W>::TILEB;
+    extern __shared__ __attribute__((aligned(16))) unsigned char asg_lds[];
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31, kh = lane >> 5;
+    const uint32_t ntile = (k + 31) / 32;  // >= nprobe (host)
+    uint32_t *tkeys = reinterpret_cast<uint32_t *>(asg_lds + 2 * (TILEB + 128)) + wave * (NT * 32) * ntile;  // [tl][tile][col]
+    const uint32_t v0 = (blockIdx.x * 4 + wave) * (32 * NT);
+    asg_bf16x8 bfrag[NT][NM];  // k-elements 16 m + 8 kh .. + 7 of query v0 + 32 tl + col
+    float yn[NT];              // |y|^2
+#pragma unroll
+    for (int tl = 0; tl < NT; ++tl) {
+        const uint32_t v = v0 + 32 * tl + col;
+        const float *xp = y + (uint64_t)(v < nq ? v : (nq - 1)) * DIM + 8 * kh;
+        float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll
+        for (int m = 0; m < NM; ++m) {
+            const float4 a = *reinterpret_cast<const float4 *>(xp + 16 * m), b = *reinterpret_cast<const float4 *>(xp + 16 * m + 4);
+            s0 = fmaf(a.x, a.x, s0), s1 = fmaf(a.y, a.y, s1), s0 = fmaf(a.z, a.z, s0), s1 = fmaf(a.w, a.w, s1);
+            s0 = fmaf(b.x, b.x, s0), s1 = fmaf(b.y, b.y, s1), s0 = fmaf(b.z, b.z, s0), s1 = fmaf(b.w, b.w, s1);
+            const uint4 pk = make_uint4(asg_bf16_pair(a.x, a.y), asg_bf16_pair(a.z, a.w), asg_bf16_pair(b.x, b.y), asg_bf16_pair(b.z, b.w));
+            bfrag[tl][m] = __builtin_bit_cast(asg_bf16x8, pk);
+        }
+        const float s = s0 + s1;
+        yn[tl] = s + __shfl_xor(s, 32, 64);  // both halves of the row
+    }
+    float thr[NT];        // T2 (sweep 2)
+    bool fin[NT];         // the margin is finite
+    uint32_t kmin[NT], kmax[NT], cnt[NT];
+#pragma unroll
+    for (int tl = 0; tl < NT; ++tl) thr[tl] = 0.0f, fin[tl] = false, kmin[tl] = 0xFFFFFFFFu, kmax[tl] = 0u, cnt[tl] = 0u;
+    for (int pass = 0; pass < 2; ++pass) {
+        CentTile<W> next;
+        __syncthreads();  // the previous sweep's last tile has been consumed
+        next.stage(cent_bf, cnorm, k, 0, RQ_COARSE_PAD_NORM);
+        next.land(asg_lds, 0);
+        for (uint32_t tile = 0; tile < ntile; ++tile) {
+            __syncthreads();  // tile `tile` is in LDS; the other buffer is free
+            if (tile + 1 < ntile) next.stage(cent_bf, cnorm, k, tile + 1, RQ_COARSE_PAD_NORM);
+            const unsigned char *img = CentTile<W>::image(asg_lds, tile & 1u);
+            const float *cnp = reinterpret_cast<const float *>(img + TILEB);
+            asg_f32x16 acc[NT];
+#pragma unroll
+            for (int tl = 0; tl < NT; ++tl) acc[tl] = asg_f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int m = 0; m < NM; ++m) {
+                const asg_bf16x8 af = *reinterpret_cast<const asg_bf16x8 *>(img + col * ROWB + (16 * m + 8 * kh) * 2);
+#pragma unroll
+                for (int tl = 0; tl < NT; ++tl) acc[tl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfrag[tl][m], acc[tl], 0, 0, 0);
+            }
+            float cnr[16];  // |c|^2 of this lane's 16 lists: list = 32 tile + (r & 3) + 8 (r >> 2) + 4 kh
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 c4 = *reinterpret_cast<const float4 *>(cnp + 8 * g + 4 * kh);
+                cnr[4 * g] = c4.x, cnr[4 * g + 1] = c4.y, cnr[4 * g + 2] = c4.z, cnr[4 * g + 3] = c4.w;
+            }
+            const bool ragged = 32 * tile + 32 > k;  // (uniform) the last tile, with rows past the last list
+#pragma unroll
+            for (int tl = 0; tl < NT; ++tl) {
+                if (pass == 0) {
+                    float mn = __builtin_inff();
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) mn = fminf(mn, fmaf(-2.0f, acc[tl][r], cnr[r]));
+                    mn = fminf(mn, __shfl_xor(mn, 32, 64));  // the other 16 lists of the tile
+                    const uint32_t key = ord32_biased(mn);
+                    kmin[tl] = key < kmin[tl] ? key : kmin[tl];
+                    kmax[tl] = key > kmax[tl] ? key : kmax[tl];
+                    if (kh == 0) tkeys[(tl * ntile + tile) * 32 + col] = key;
+                } else {
+                    uint32_t mine = 0;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) mine |= fmaf(-2.0f, acc[tl][r], cnr[r]) <= thr[tl] ? (1u << r) : 0u;
+                    if (ragged) {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            if (32 * tile + (uint32_t)((r & 3) + 8 * (r >> 2)) + 4 * kh >= k) mine &= ~(1u << r);
+                    }
+                    if (!fin[tl]) mine = 0;
+                    const uint32_t other = (uint32_t)__shfl_xor((int)mine, 32, 64);
+                    const uint32_t c_mine = (uint32_t)__popc(mine), c_other = (uint32_t)__popc(other);
+                    uint32_t at = cnt[tl] + (kh ? c_other : 0u);  // the lower half-wave's lists first
+                    cnt[tl] += c_mine + c_other;
+                    // staged in LDS, over the tile keys (dead by now): a store to global memory here would have every tile's
+                    // `land` wait for it, since loads and stores share one counter
+                    uint16_t *cand = reinterpret_cast<uint16_t *>(tkeys + tl * ntile * 32) + col * RQ_COARSE_CAND;
+                    while (mine) {
+                        const uint32_t r = (uint32_t)__builtin_ctz(mine);
+                        mine &= mine - 1u;
+                        if (at < RQ_COARSE_CAND) cand[at] = (uint16_t)(32 * tile + (r & 3u) + 8u * (r >> 2) + 4u * kh);
+                        ++at;
+                    }
+                }
+            }
+            if (tile + 1 < ntile) next.land(asg_lds, (tile + 1) & 1u);
+        }
+        if (pass == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // this wave's tile keys: read back by both of its half-waves
+#pragma unroll
+            for (int tl = 0; tl < NT; ++tl) {
+                // bisect_loose per lane: the two half-waves of a query hold the same lo / hi and count the tiles of their parity
+                const uint32_t *tk = tkeys + tl * ntile * 32 + col;
+                uint32_t lo = kmin[tl], hi = kmax[tl];
+                bool open = lo < hi;
+                while (__ballot(open)) {
+                    const uint32_t mid = lo + ((hi - lo) >> 1);
+                    uint32_t c = 0;
+#pragma unroll 16
+                    for (uint32_t i = kh; i < ntile; i += 2) c += tk[i * 32] <= mid ? 1u : 0u;  // (16 reads in flight)
+                    c += (uint32_t)__shfl_xor((int)c, 32, 64);
+                    if (open) {
+                        if (c >= nprobe) {
+                            hi = mid;
+                            if (c <= nprobe + RQ_FUSED_WINDOW) open = false;
+                        } else {
+                            lo = mid + 1;
+                        }
+                        open = open && lo < hi;
+                    }
+                }
+                const float tau = ord32_unbias(hi);
+                const float t2 = prefilter_bound(tau, cmax, yn[tl], DIM);
+                fin[tl] = fabsf(t2) < 3.0e38f && fabsf(tau) < 3.0e38f;  // false for NaN / inf
+                thr[tl] = t2;
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the staged ids: written by the query's two lanes, read by the whole wave
+#pragma unroll
+    for (int tl = 0; tl < NT; ++tl) {
+        const uint32_t v = v0 + 32 * tl + col;
+        const uint32_t cval = fin[tl] ? cnt[tl] : 0xFFFFFFFFu;
+        if (kh == 0 && v < nq) cand_cnt[v] = cval;
+        // the ids of the rows that go on to the refinement, 256 bytes per wave store
+        const uint16_t *cand = reinterpret_cast<const uint16_t *>(tkeys + tl * ntile * 32);
+        for (uint32_t qi = 0; qi < 32; ++qi) {
+            const uint32_t c = (uint32_t)__shfl((int)cval, (int)qi, 64), vq = v0 + 32 * tl + qi;  // (uniform)
+            if (vq >= nq || c > RQ_COARSE_CAND) continue;
+            uint32_t *slots = reinterpret_cast<uint32_t *>(dist + (uint64_t)vq * k);
+            for (uint32_t s = lane; s < c; s += 64) slots[s] = cand[qi * RQ_COARSE_CAND + s];
+        }
+    }
+}
+
+// One wave per query behind coarse_candidates_kernel: the candidate ids from the row's slots, coarse_refine_tail.  A row with more
+// than RQ_COARSE_CAND candidates, fewer than nprobe (none: the margin is never negative) or no finite margin is ranked the plain
+// way, as select_refine_tiled_kernel's last branch does: all its distances in exact order, its flag set for select_probe_kernel.
+// cnt_flag: in, the row's candidate count; out, its redo flag.
+__global__ __launch_bounds__(256) void refine_candidates_kernel(float *__restrict__ dist, const float *__restrict__ y,
+                                                                const float *__restrict__ centroids, uint32_t k, uint32_t dim, uint32_t nprobe,
+                                                                uint32_t *__restrict__ out_cluster, float *__restrict__ out_dist,
+                                                                uint32_t out_stride, uint32_t nq, uint32_t *__restrict__ cnt_flag,
+                                                                unsigned long long *__restrict__ fallback_rows /* counter, may be null */) {
+    __shared__ unsigned long long win[4][RQ_COARSE_CAND];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, b = blockIdx.x * 4 + wave;
+    if (b >= nq) return;
+    unsigned long long *wn = win[wave];
+    float *d = dist + (uint64_t)b * k;
+    const float *yr = y + (uint64_t)b * dim;
+    const uint32_t c2 = __builtin_amdgcn_readfirstlane(cnt_flag[b]);
+    if (c2 > RQ_COARSE_CAND || c2 < nprobe) {  // (wave-uniform) the plain way; the block-per-query selection takes the row
+        coarse_exact_row(centroids, yr, dim, k, d);
+        if (lane == 0) {
+            cnt_flag[b] = 1u;
+            if (fallback_rows) atomicAdd(fallback_rows, 1ull);
+        }
+        return;
+    }
+    const uint32_t *slots = reinterpret_cast<const uint32_t *>(d);
+    for (uint32_t i = lane; i < c2; i += 64) wn[i] = slots[i];
+    if (lane == 0) cnt_flag[b] = 0u;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    coarse_refine_tail(wn, c2, centroids, yr, dim, nprobe, b, out_cluster, out_dist, out_stride);
+}

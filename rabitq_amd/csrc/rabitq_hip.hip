@@ -1060,13 +1060,15 @@ rq_status rq_set_option(const char *name, int value) {
     if (std::string(name) == "scan_debug") {
         // Measurement hooks that leave every result unchanged: 128 (kept for older hosts: the step counters are always on now),
         // 512 (rerank without the fp16 shadow rows), 2048 (long run directories are ordered without the cell bitmap), 4096 (phase stamps of the small-batch block), 16384 (stage list on stderr),
-        // 32768 (the 8-bit rerank pre-filter reads its shadow rows into registers: the kernel from before the LDS ring).
+        // 32768 (the 8-bit rerank pre-filter reads its shadow rows into registers: the kernel from before the LDS ring),
+        // 65536 (the pre-filtered coarse ranking of 4096 .. 8192 lists writes the nq x k matrix of approximate distances and selects
+        // from it: the two kernels from before coarse_candidates_kernel).
         // The timing ablations (1, 2, 4, 64, 1024, 8192: results are WRONG) and the in-kernel cycle counters (256) exist in
         // the developer build only (make dev -> librabitq_hip_dev.so, -DRQ_DEV_ABLATIONS).
 #ifdef RQ_DEV_ABLATIONS
         const int allowed = 0x7FFFFFFF;
 #else
-        const int allowed = 128 | 512 | 2048 | 4096 | 16384 | 32768;
+        const int allowed = 128 | 512 | 2048 | 4096 | 16384 | 32768 | 65536;
 #endif
         if (value < 0 || (value & ~allowed)) return fail(RQ_ERR_INVALID, "scan_debug: this bit exists in the developer build only (librabitq_hip_dev.so)");
         g_scan_dbg = value;
