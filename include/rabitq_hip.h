@@ -83,7 +83,8 @@ typedef struct {
  * 0.8.0: cosine metric -- rq_*_metric, rq_normalize*, rq_info_t.reserved0 became metric, additions only;
  * later in 0.8, additions only: rq_query_batch_device_begin_filtered, option "small_batch_filtered" -- filtered batches of <= 64
  * queries on the small-batch path;
- * 0.9.0: inner-product metric, additions only -- RQ_METRIC_IP, rq_*_ip, rq_ip_*, rq_augment*, rq_row_sqnorm_max*).
+ * 0.9.0: inner-product metric, additions only -- RQ_METRIC_IP, rq_*_ip, rq_ip_*, rq_augment*, rq_row_sqnorm_max*;
+ * 0.10.0: half-precision rows, additions only -- RQ_ROWS_*, rq_*_rows, rq_row_type, rq_widen*, RQ_ARR_BASE_ROWS).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -163,6 +164,54 @@ rq_status rq_ip_from_dist_device(const rq_index *idx, const float *d_queries, ui
 rq_status rq_ip_radius(const rq_index *idx, const float *queries, uint32_t nq, uint32_t len, const float *min_ip, float *out_radius);
 rq_status rq_ip_radius_device(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t len, const float *d_min_ip,
                               float *d_out_radius);
+
+/* ---- half-precision rows: f16 / bf16 raw vectors stored as given (0.10.0, additions only) ------ */
+/* The row type is a property of the index.  RQ_ROWS_F32 (what every entry point without a row_type means) stores 4*dim bytes per
+ * raw vector.  RQ_ROWS_F16 (IEEE binary16) and RQ_ROWS_BF16 store the caller's 2-byte elements as given, n x dim of them, the
+ * padding slots +0: 2*dim bytes per vector, no f32 copy, no shadow rows, no split rows (the options "rerank_shadow" and
+ * "split_rows" do not apply), and the build never holds an n x dim f32 array either (typed chunks are widened into a bounded
+ * staging buffer).  Widening W is exact: f16 -> f32 the IEEE conversion (subnormals kept; a NaN stays a NaN, payload unspecified),
+ * bf16 -> f32 bits << 16.  A half-row L2 index made from rows h (n x d), centroids (f32, k x d), P and seed equals, bit for bit,
+ * the index rq_build_device makes from W(h): codes, factors, offsets, map_ids, centroids; RQ_ARR_BASE returns W(h) in cluster
+ * order, zero-padded; rq_info is equal (n_hbm == n, split_rows == 0); every query entry (plain, filtered, range, _begin / _end,
+ * probed, seeded, coarse, rq_rerank, shards of rq_shard_index -- they inherit the row type) returns the same ids, order, distance
+ * bits, counts, status and counters.  Queries stay f32 (rq_widen* converts a caller's half-precision queries).  The reference
+ * has no counterpart.
+ * Cosine: the stored row is R_t(N(W(h))), R_t = round to nearest even to the row type (f16: subnormal results kept, overflow to
+ * inf; bf16, non-NaN: (u + 0x7FFF + ((u >> 16) & 1)) >> 16 on the f32 bits u), and the index equals the L2 index of
+ * W(R_t(N(W(h)))): rotation, assignment and quantisation see the rounded rows.  Rows N leaves untouched stay bit for bit.
+ * Refused: RQ_METRIC_IP with half rows (the extra coordinate is not representable), rq_add / rq_remove on a half-row index, a
+ * half-row index that does not fit the HBM budget (option "base_device_mb" included; there are no tiers for half rows),
+ * rq_get_device_ptr(RQ_ARR_BASE) -- all RQ_ERR_UNSUPPORTED; an unknown row_type: RQ_ERR_INVALID.
+ * RQ_ARR_BASE_ROWS (rq_get_array, rq_get_device_ptr): the stored n x dim 2-byte rows, n * dim * 2 bytes; RQ_ERR_INVALID on an f32
+ * index.  Persistence: rq_dump_dir writes the crate's files with base.fvecs widened (the reference loads it and answers
+ * identically) plus a file `rows` holding "f16\n" / "bf16\n"; rq_load_dir with a `rows` file stores half rows (a value of
+ * base.fvecs the type cannot hold, or an unknown text: RQ_ERR_IO); the JSON image carries "rows":"f16" / "bf16" likewise. */
+enum { RQ_ROWS_F32 = 0, RQ_ROWS_F16 = 1, RQ_ROWS_BF16 = 2 };
+struct rq_builder;
+/* rq_build_metric / rq_build_device_metric with typed rows: base is n x d elements of row_type (host / device memory; 2-byte
+ * aligned is enough), centroids stay f32. */
+rq_status rq_build_rows(const void *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k, const float *orthogonal,
+                        uint64_t seed, uint32_t metric, uint32_t row_type, rq_index **out);
+rq_status rq_build_device_rows(const void *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
+                               const float *orthogonal_host, uint64_t seed, uint32_t metric, uint32_t row_type, rq_index **out);
+/* The streamed build with typed chunks: a builder made with row_type != RQ_ROWS_F32 takes its chunks (m x d elements of its
+ * type, device memory) through the two _rows calls and refuses the plain chunk calls (RQ_ERR_INVALID); a plain builder, this
+ * entry with RQ_ROWS_F32 included, the other way round.  order / finish / free / stats are the plain builder's. */
+rq_status rq_builder_create_rows(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
+                                 uint64_t seed, uint64_t max_device_base_bytes, uint32_t metric, uint32_t row_type,
+                                 struct rq_builder **out);
+rq_status rq_builder_assign_chunk_rows(struct rq_builder *b, const void *d_rows, uint64_t i0, uint64_t m);
+rq_status rq_builder_place_chunk_rows(struct rq_builder *b, const void *d_rows, uint64_t i0, uint64_t m);
+/* rq_from_arrays_metric with base n x dim elements of row_type (cluster order), taken as they are. */
+rq_status rq_from_arrays_rows(uint32_t dim, uint64_t n, uint32_t k, const void *base, const float *orthogonal,
+                              const float *centroids, const uint32_t *offsets, const uint32_t *map_ids, const uint64_t *codes,
+                              const rq_factor_t *factors, uint32_t metric, uint32_t row_type, rq_index **out);
+rq_status rq_row_type(const rq_index *idx, uint32_t *out);
+/* out[i] = W(x[i]) for `count` elements of row_type (any count; x 2-byte aligned).  rq_widen: host pointers; rq_widen_device:
+ * device pointers, returns with `out` complete. */
+rq_status rq_widen(const void *x, uint32_t row_type, uint64_t count, float *out);
+rq_status rq_widen_device(const void *d_x, uint32_t row_type, uint64_t count, float *d_out);
 
 /* ---- build: RaBitQ::from_path, src/rabitq.rs:159-265 ---------------------------------------- */
 /* `orthogonal` is the dim x dim rotation P (row-major, P[r][c]); the reference draws it from an
@@ -269,7 +318,8 @@ rq_status rq_from_arrays_ip(uint32_t dim, uint64_t n, uint32_t k, const float *b
 rq_status rq_info(const rq_index *idx, rq_info_t *out);
 /* Copy one array of the index back to host memory (sizes as in rq_from_arrays). */
 enum { RQ_ARR_BASE = 0, RQ_ARR_ORTHOGONAL, RQ_ARR_CENTROIDS, RQ_ARR_OFFSETS, RQ_ARR_MAP_IDS,
-       RQ_ARR_CODES, RQ_ARR_FACTORS };
+       RQ_ARR_CODES, RQ_ARR_FACTORS,
+       RQ_ARR_BASE_ROWS /* = 7: the stored 2-byte rows of a half-precision index, n * dim * 2 bytes (an f32 index: RQ_ERR_INVALID) */ };
 rq_status rq_get_array(const rq_index *idx, int which, void *dst, uint64_t dst_bytes);
 /* Device pointer of one array (valid until rq_free); for zero-copy hand-over to a caller that
  * already lives on the GPU.  RQ_ARR_BASE: every row at its position -- only when n_hbm == n; on a tiered index (list

@@ -27,6 +27,8 @@ EXPORTS = [
     "rq_query_batch", "rq_query_batch_device", "rq_query_batch_device_begin", "rq_query_batch_device_end", "rq_filter_create", "rq_filter_rows", "rq_filter_free", "rq_query_batch_filtered", "rq_query_batch_device_filtered", "rq_query_batch_device_begin_filtered", "rq_range_search", "rq_range_search_device", "rq_range_result_info", "rq_range_result_device_ptrs", "rq_range_result_copy", "rq_range_result_free", "rq_add", "rq_remove", "rq_last_mutate_stats", "rq_coarse_topk_device", "rq_merge_smallest_u64_device", "rq_query_batch_device_probed", "rq_query_batch_device_seeded", "rq_partition_lists", "rq_shard_index", "rq_query_batch_sharded_device", "rq_set_collectives", "rq_metrics", "rq_metrics_reset", "rq_rotate", "rq_rotate_device",
     "rq_quantize_pack",
     "rq_coarse_rank", "rq_query_prep", "rq_scan", "rq_rerank", "rq_set_profiling", "rq_set_option", "rq_last_profile",
+    "rq_build_rows", "rq_build_device_rows", "rq_builder_create_rows", "rq_builder_assign_chunk_rows", "rq_builder_place_chunk_rows",
+    "rq_from_arrays_rows", "rq_row_type", "rq_widen", "rq_widen_device",
 ]
 
 
@@ -49,6 +51,20 @@ def metric_id(metric) -> int:
             raise ValueError(f"metric must be one of {sorted(METRICS)}, not {metric!r}")
         return METRICS[metric.lower()]
     return int(metric)
+
+
+ROWS_F32, ROWS_F16, ROWS_BF16 = 0, 1, 2   # RQ_ROWS_*
+ROW_TYPES = {"f32": ROWS_F32, "f16": ROWS_F16, "bf16": ROWS_BF16}
+ROW_TYPE_NAMES = {v: k for k, v in ROW_TYPES.items()}
+
+
+def row_type_id(rows) -> int:
+    """"f32" / "f16" / "bf16" (or an RQ_ROWS_* value) -> the C ABI's row_type."""
+    if isinstance(rows, str):
+        if rows.lower() not in ROW_TYPES:
+            raise ValueError(f"rows must be one of {sorted(ROW_TYPES)}, not {rows!r}")
+        return ROW_TYPES[rows.lower()]
+    return int(rows)
 
 
 ABI_VERSION = 4   # RQ_ABI_VERSION of include/rabitq_hip.h this mirror was written against
@@ -212,6 +228,15 @@ def lib():
         "rq_set_profiling": (i32, [C.c_int]),
         "rq_set_option": (i32, [C.c_char_p, C.c_int]),
         "rq_last_profile": (i32, [C.POINTER(ProfileT)]),
+        "rq_build_rows": (i32, [vp, u64, u32, f32p, u32, f32p, u64, u32, u32, pp]),
+        "rq_build_device_rows": (i32, [vp, u64, u32, f32p, u32, f32p, u64, u32, u32, pp]),
+        "rq_builder_create_rows": (i32, [u64, u32, f32p, u32, f32p, u64, u64, u32, u32, pp]),
+        "rq_builder_assign_chunk_rows": (i32, [vp, vp, u64, u64]),
+        "rq_builder_place_chunk_rows": (i32, [vp, vp, u64, u64]),
+        "rq_from_arrays_rows": (i32, [u32, u64, u32, vp, f32p, f32p, u32p, u32p, u64p, vp, u32, u32, pp]),
+        "rq_row_type": (i32, [vp, C.POINTER(u32)]),
+        "rq_widen": (i32, [vp, u32, u64, f32p]),
+        "rq_widen_device": (i32, [vp, u32, u64, f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the .so lacks a declared symbol

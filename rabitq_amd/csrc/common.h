@@ -147,21 +147,71 @@ struct ListTier {  // one per list
 // exactly.  The re-ranker reads the first plane alone (half the bytes), proves most survivors out of the top-k with it
 // (accurate_split_kernel, kernels_rerank.h) and fetches the second plane only for the rest.  Both tiers use the layout: over the
 // host link the first plane alone is half the bytes as well.
+// Half-precision rows (row_type RQ_ROWS_F16 = 1, RQ_ROWS_BF16 = 2; include/rabitq_hip.h): the index stores the caller's 2-byte
+// elements as given, 2*dim bytes per row, never tiered, never split, no shadow rows.  Widening W to f32 is exact (f16: the IEEE
+// conversion, subnormals kept; bf16: bits << 16), so every distance is the f32 index's of W(rows), bit for bit.
+#define RQ_ROWS_F32_ 0u
+#define RQ_ROWS_F16_ 1u
+#define RQ_ROWS_BF16_ 2u
+// W of one stored element
+__host__ __device__ __forceinline__ float rq_widen_elem(uint16_t h, uint32_t fmt) {
+    if (fmt == RQ_ROWS_BF16_) return __builtin_bit_cast(float, (uint32_t)h << 16);
+#ifdef __HIP_DEVICE_COMPILE__
+    return (float)__builtin_bit_cast(_Float16, h);
+#else
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, ex = (h >> 10) & 31u, man = h & 0x3FFu;
+    if (ex == 31u) return __builtin_bit_cast(float, sign | 0x7F800000u | (man ? 0x00400000u | (man << 13) : 0u));
+    if (ex != 0u) return __builtin_bit_cast(float, sign | ((ex + 112u) << 23) | (man << 13));
+    const float mag = (float)man * 5.9604644775390625e-8f;  // man * 2^-24: exact
+    return sign ? -mag : mag;
+#endif
+}
+// R_t of one f32 value: round to nearest even to the storage type (f16: subnormal results kept, overflow to inf; bf16:
+// (u + 0x7FFF + ((u >> 16) & 1)) >> 16 on the bits u).  A NaN stays a NaN, and one whose low 16 bits are zero keeps its bf16 bits.
+__host__ __device__ __forceinline__ uint16_t rq_narrow_elem(float v, uint32_t fmt) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    if (fmt == RQ_ROWS_BF16_) {
+        if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | ((u & 0xFFFFu) ? 0x40u : 0u));
+        return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+    }
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_bit_cast(uint16_t, (_Float16)v);
+#else
+    const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7FFFFFFFu;
+    if (a > 0x7F800000u) return (uint16_t)(sign | 0x7E00u | ((a >> 13) & 0x3FFu));
+    if (a >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);  // >= 65520 rounds to inf (inf itself included)
+    if (a < 0x33000001u) return (uint16_t)sign;               // <= 2^-25 rounds to zero (the tie goes to the even 0)
+    const uint32_t e = a >> 23;
+    // 24-bit significand shifted so that the result counts units of the target's last place (normal: 2^(e-127-10), subnormal: 2^-24)
+    const uint32_t sig = (a & 0x7FFFFFu) | 0x800000u, sh = e >= 113u ? 13u : 126u - e;
+    const uint32_t q = sig >> sh, rem = sig & ((1u << sh) - 1u), halfway = 1u << (sh - 1u);
+    const uint32_t r = q + ((rem > halfway || (rem == halfway && (q & 1u))) ? 1u : 0u);
+    // normal: q carries the hidden bit (0x400 .. 0x7FF), so adding (e - 113) << 10 lands the exponent, and a carry out of the
+    // significand moves into it; subnormal: r is the significand itself (a carry to 0x400 is the smallest normal)
+    return (uint16_t)(sign | (e >= 113u ? ((e - 113u) << 10) + r : r));
+#endif
+}
 struct RowRef {
-    const float *p;  // the row's 4*dim bytes
+    const float *p;  // the row's 4*dim bytes (a half-precision row: its 2*dim bytes)
     bool split;      // stored as two 16-bit planes
+    uint32_t fmt;    // RQ_ROWS_*: 0 = f32 (plain or split), else the 2-byte element type
 };
 __host__ __device__ __forceinline__ uint32_t rq_split_join(uint32_t h16, uint32_t lo16) {
     return (h16 << 16) + (uint32_t)(int32_t)(int16_t)lo16;
 }
-// element e of a row / its store (cold paths: placement, dumps, shards, rq_rerank)
+// element e of a row / its store (cold paths: placement, dumps, shards, rq_rerank); a half-precision row widens / narrows
 __host__ __device__ __forceinline__ float rq_row_get(const RowRef r, uint32_t dim, uint32_t e) {
+    if (r.fmt) return rq_widen_elem(reinterpret_cast<const uint16_t *>(r.p)[e], r.fmt);
     if (!r.split) return r.p[e];
     const uint16_t *h = reinterpret_cast<const uint16_t *>(r.p);
     return __builtin_bit_cast(float, rq_split_join(h[e], h[dim + e]));
 }
 __host__ __device__ __forceinline__ void rq_row_put(const RowRef r, uint32_t dim, uint32_t e, float v) {
     float *w = const_cast<float *>(r.p);
+    if (r.fmt) {
+        reinterpret_cast<uint16_t *>(w)[e] = rq_narrow_elem(v, r.fmt);
+        return;
+    }
     if (!r.split) {
         w[e] = v;
         return;
@@ -176,20 +226,25 @@ struct BaseView {
     const ListTier *lt;  // k entries (tiered indexes only)
     uint32_t k;
     uint32_t split;      // the rows (of both tiers) are split rows
+    uint32_t fmt;        // RQ_ROWS_*: half-precision rows (untiered, never split) lie 2*dim bytes apart
+    // row of position p of an untiered index
+    __host__ __device__ __forceinline__ RowRef row_at(uint64_t p, uint32_t dim) const {
+        return RowRef{dev + p * (fmt ? dim >> 1 : dim), split != 0, fmt};
+    }
     // row of position p that belongs to list c
     __host__ __device__ __forceinline__ RowRef row_in_list(uint64_t p, const ListTier &t, uint32_t dim) const {
         const uint64_t local = p - t.off;
-        if (local < t.h) return RowRef{dev + ((uint64_t)t.hbm_base + local) * dim, split != 0};
-        return RowRef{host + ((uint64_t)t.host_base + (local - t.h)) * dim, split != 0};
+        if (local < t.h) return RowRef{dev + ((uint64_t)t.hbm_base + local) * dim, split != 0, 0u};
+        return RowRef{host + ((uint64_t)t.host_base + (local - t.h)) * dim, split != 0, 0u};
     }
     // row of position p whose list is probe_row[slot] (the re-rankers: a survivor record names its slot)
     __device__ __forceinline__ RowRef row_of_slot(uint64_t p, const uint32_t *__restrict__ probe_row, uint32_t slot, uint32_t dim) const {
-        if (!host) return RowRef{dev + p * dim, split != 0};
+        if (!host) return RowRef{dev + p * dim, split != 0, 0u};  // (f32 rows only: the re-rankers of half-precision rows use row_at)
         return row_in_list(p, lt[probe_row[slot]], dim);
     }
     // row of position p, list unknown: bisection over the lists (cold paths: placement, dumps, shards, rq_rerank)
     __host__ __device__ __forceinline__ RowRef row(uint64_t p, uint32_t dim) const {
-        if (!host) return RowRef{dev + p * dim, split != 0};
+        if (!host) return row_at(p, dim);
         uint32_t lo = 0, hi = k;  // largest c with lt[c].off <= p (empty lists share their start with the next one)
         while (hi - lo > 1) {
             const uint32_t mid = lo + ((hi - lo) >> 1);

@@ -73,7 +73,8 @@ static rq_status derive_shadow_rows(rq_index *idx) {
     idx->list_q8.release();
     int kind = g_rerank_shadow.load();
     if (kind == 2 && idx->dim > 4096) kind = 1;  // (the 8-bit encoder handles rows of up to 4096 dimensions: wider vectors take the fp16 rows)
-    if (!kind || idx->base_host != nullptr || idx->split_rows || idx->n < RQ_SHADOW_MIN_ROWS) return RQ_OK;
+    // (a half-precision index stores no shadow rows: its survivors read their 2*dim-byte rows)
+    if (!kind || idx->base_host != nullptr || idx->split_rows || idx->row_type || idx->n < RQ_SHADOW_MIN_ROWS) return RQ_OK;
     const uint64_t total = idx->n * idx->dim, bytes = total * (kind == 2 ? 1 : 2);
     size_t free_b = 0, total_b = 0;
     HIPC(hipMemGetInfo(&free_b, &total_b));
@@ -245,7 +246,7 @@ static std::atomic<int> g_split_rows{1};           // indexes built from now on 
 #define RQ_HBM_RESERVE_BYTES (12ull << 30)
 // h_offsets: the k+1 list offsets on the host (the split is per list)
 static rq_status alloc_base_tiers(rq_index *idx, uint64_t budget_bytes, const uint32_t *h_offsets) {
-    const uint64_t row = (uint64_t)idx->dim * 4, want = idx->n * row;
+    const uint64_t row = idx->row_bytes(), want = idx->n * row;
     uint64_t cap = budget_bytes;
     if (budget_bytes == 0) {
         const int64_t opt = g_base_device_mb.load();
@@ -259,6 +260,13 @@ static rq_status alloc_base_tiers(rq_index *idx, uint64_t budget_bytes, const ui
         }
     }
     const uint64_t budget_rows = cap == ~0ull ? idx->n : std::min<uint64_t>(idx->n, cap / row);
+    if (idx->row_type) {  // half-precision rows: in HBM at their positions or not at all (no tiers, no split rows, no shadow rows)
+        if (budget_rows < idx->n)
+            return fail(RQ_ERR_UNSUPPORTED, "the half-precision rows of this index (" + std::to_string(want) + " bytes) do not fit the HBM budget: there are no tiers for half rows");
+        idx->n_dev = idx->n, idx->split_rows = false;
+        RQC(idx->base.alloc((idx->n * idx->dim + 1) / 2));  // (n x dim 2-byte elements)
+        return RQ_OK;
+    }
     if (budget_rows >= idx->n) {  // everything in HBM, rows at their positions
         idx->n_dev = idx->n;
         // Will shadow rows fit beside them (derive_shadow_rows' rule, asked before the rows are placed)?  If not, the rows are stored
@@ -313,6 +321,7 @@ struct rq_builder {
     uint64_t budget = 0;
     DevBuf<uint32_t> label, pos_of_id;
     DevBuf<float> mind, xpad, xrot;
+    DevBuf<float> wide;  // a half-precision builder (idx->row_type): the typed chunk widened, at most RQ_BUILD_CHUNK x d f32 -- the only f32 image of the input
     DevBuf<uint64_t> codes_tmp;
     DevBuf<float4> factors_tmp;
     AssignAux assign_aux;
@@ -361,6 +370,45 @@ struct rq_builder {
 };
 #define RQ_BUILD_CHUNK (1ull << 20)
 
+// ---- half-precision rows (include/rabitq_hip.h, "half-precision rows") ----
+// the row types an entry takes, and the one metric that has none
+static rq_status row_type_check(uint32_t row_type, const MetricSpec &metric) {
+    if (row_type > RQ_ROWS_BF16) return fail(RQ_ERR_INVALID, "unknown row_type " + std::to_string(row_type));
+    if (row_type && metric.id == RQ_METRIC_IP)
+        return fail(RQ_ERR_UNSUPPORTED, "the inner-product metric has no half-precision rows: its extra coordinate sqrt(S - |x|^2) is not representable in the row type");
+    return RQ_OK;
+}
+// the stored tag: the `rows` file of a dumped directory ("f16\n" / "bf16\n"), the "rows" member of a JSON dump
+static const char *row_type_text(uint32_t row_type) { return row_type == RQ_ROWS_BF16 ? "bf16" : "f16"; }
+static bool row_type_from_text(const std::string &text, uint32_t *row_type) {
+    if (text == "f16") *row_type = RQ_ROWS_F16;
+    else if (text == "bf16") *row_type = RQ_ROWS_BF16;
+    else return false;
+    return true;
+}
+// f32 values a loader found where half-precision rows are announced -> the type's elements; a value the type cannot hold
+// (W(R_t(v)) != v bit for bit; a NaN counts as held) is RQ_ERR_IO
+static rq_status narrow_exact(const float *v, uint64_t count, uint32_t row_type, std::vector<uint16_t> &out, const std::string &where) {
+    out.resize(count);
+    for (uint64_t i = 0; i < count; ++i) {
+        out[i] = rq_narrow_elem(v[i], row_type);
+        const float back = rq_widen_elem(out[i], row_type);
+        if (__builtin_bit_cast(uint32_t, back) != __builtin_bit_cast(uint32_t, v[i]) && v[i] == v[i])
+            return fail(RQ_ERR_IO, where + ": value " + std::to_string(i) + " is not representable in the row type the index announces");
+    }
+    return RQ_OK;
+}
+// `count` elements widened on the null stream (widen_rows_kernel)
+static void launch_widen(const uint16_t *d_x, uint32_t row_type, uint64_t count, float *d_out) {
+    if (count) widen_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(count, 256), 1u << 20), 256>>>(d_x, row_type, count, d_out);
+}
+// a typed builder takes its chunks through the _rows calls only, a plain one through the plain calls only
+static rq_status builder_chunk_type_check(const rq_builder *b, bool typed) {
+    if ((b->idx->row_type != RQ_ROWS_F32) == typed) return RQ_OK;
+    return fail(RQ_ERR_INVALID, typed ? "this builder takes f32 chunks: use rq_builder_assign_chunk / rq_builder_place_chunk"
+                                      : "this builder takes chunks of its row type: use rq_builder_assign_chunk_rows / rq_builder_place_chunk_rows");
+}
+
 // pass-1 state of a builder whose index already holds its shape (n, dim, k, W) and the rotated centroids (centroids, cent_t)
 static rq_status builder_alloc_pass1(rq_builder *b) {
     rq_index *idx = b->idx.get();
@@ -374,13 +422,16 @@ static rq_status builder_alloc_pass1(rq_builder *b) {
     if (b->d != dim || idx->metric.id != RQ_METRIC_L2) RQC(b->xpad.alloc(chunk * dim));  // (an L2 row of dim floats is rotated where it is)
     if (metric_refuses_rows(idx->metric)) RQC(b->ip_bad.alloc(1));
     RQC(b->xrot.alloc(chunk * dim));
+    if (idx->row_type) RQC(b->wide.alloc(chunk * b->d));
     if (assign_has_mfma(idx->W) && g_assign_impl.load() != 1) RQC(assign_aux_init(idx, b->assign_aux, chunk));
     for (auto &e : b->ev) HIPC(hipEventCreate(&e));
     return RQ_OK;
 }
 
 static rq_status builder_create(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
-                                uint64_t seed, uint64_t max_device_base_bytes, const MetricSpec &metric, uint32_t cent_cols, rq_builder **out) {
+                                uint64_t seed, uint64_t max_device_base_bytes, const MetricSpec &metric, uint32_t cent_cols, rq_builder **out,
+                                uint32_t row_type = RQ_ROWS_F32) {
+    RQC(row_type_check(row_type, metric));
     RQC(ensure_device());
     RQC(ensure_kernel_attributes());
     if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
@@ -397,7 +448,7 @@ static rq_status builder_create(uint64_t n, uint32_t d, const float *d_centroids
     std::unique_ptr<rq_builder> b(new rq_builder());
     b->idx.reset(new rq_index());
     rq_index *idx = b->idx.get();
-    idx->dim = dim, idx->k = k, idx->n = n, idx->W = dim / 64, idx->metric = metric;
+    idx->dim = dim, idx->k = k, idx->n = n, idx->W = dim / 64, idx->metric = metric, idx->row_type = row_type;
     b->d = d, b->budget = max_device_base_bytes;
 
     std::vector<float> Pgen;
@@ -431,8 +482,11 @@ static rq_status builder_rows_check(rq_builder *b) {
 }
 
 // pass 1 for rows [i0, i0 + m) of the input (d_rows: m x d, device)
-static rq_status builder_assign(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m) {
-    if (!b || (m && !d_rows)) return fail(RQ_ERR_INVALID, "null argument");
+// (typed: the call came through the _rows entry -- the rows are m x d elements of the builder's row type)
+static rq_status builder_assign(rq_builder *b, const void *d_rows_any, uint64_t i0, uint64_t m, bool typed = false) {
+    if (!b || (m && !d_rows_any)) return fail(RQ_ERR_INVALID, "null argument");
+    RQC(builder_chunk_type_check(b, typed));
+    const float *d_rows = static_cast<const float *>(d_rows_any);
     if (b->refused) return fail(RQ_ERR_INVALID, "a chunk of this builder was refused: it can only be freed");
     if (b->ordered) return fail(RQ_ERR_INVALID, "rq_builder_assign_chunk after rq_builder_order");
     rq_index *idx = b->idx.get();
@@ -441,8 +495,15 @@ static rq_status builder_assign(rq_builder *b, const float *d_rows, uint64_t i0,
     const uint32_t d = b->d, dim = idx->dim;
     for (uint64_t c0 = 0; c0 < m; c0 += RQ_BUILD_CHUNK) {
         const uint64_t mm = std::min<uint64_t>(RQ_BUILD_CHUNK, m - c0), at = i0 + c0;
-        const float *src;
-        RQC(transform_rows(idx->metric, dim, d_rows + c0 * d, mm, d, at, b->xpad.p, nullptr, BaseView{}, b->ip_s_pre, b->ip_bad.p, &src));
+        const float *src, *in = d_rows + c0 * d;
+        if (typed) {  // W(chunk) into the staging buffer: everything behind it is the f32 build's
+            launch_widen(static_cast<const uint16_t *>(d_rows_any) + c0 * d, idx->row_type, mm * d, b->wide.p);
+            in = b->wide.p;
+        }
+        RQC(transform_rows(idx->metric, dim, in, mm, d, at, b->xpad.p, nullptr, BaseView{}, b->ip_s_pre, b->ip_bad.p, &src));
+        // a cosine index stores R_t(N(W(h))): rotation, assignment and quantisation see the rounded rows (src is xpad here)
+        if (typed && idx->metric.id == RQ_METRIC_COSINE)
+            round_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(mm * dim, 256), 1u << 20), 256>>>(b->xpad.p, idx->row_type, mm * dim);
         HIPC(hipEventRecord(b->ev[0], nullptr));
         launch_rotate(src, idx->P.p, b->xrot.p, mm, dim, true, nullptr);
         HIPC(hipEventRecord(b->ev[1], nullptr));
@@ -475,7 +536,8 @@ static rq_status builder_order(rq_builder *b) {
     const uint64_t n = idx->n;
     const uint32_t k = idx->k;
     if (b->assigned != n) return fail(RQ_ERR_INVALID, "rq_builder_order before every row was assigned");
-    b->xpad.release();
+    // (a half-precision cosine builder normalises its chunks into xpad again in pass 2; `wide` stays for both passes)
+    if (!(idx->row_type && idx->metric.id == RQ_METRIC_COSINE)) b->xpad.release(), b->wide.release();
     b->xrot.release();
     {
         AssignAux &ax = b->assign_aux;
@@ -518,14 +580,35 @@ static rq_status builder_order(rq_builder *b) {
 }
 
 // pass 2 for rows [i0, i0 + m)
-static rq_status builder_place(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m) {
-    if (!b || (m && !d_rows)) return fail(RQ_ERR_INVALID, "null argument");
+static rq_status builder_place(rq_builder *b, const void *d_rows_any, uint64_t i0, uint64_t m, bool typed = false) {
+    if (!b || (m && !d_rows_any)) return fail(RQ_ERR_INVALID, "null argument");
+    RQC(builder_chunk_type_check(b, typed));
+    const float *d_rows = static_cast<const float *>(d_rows_any);
     if (b->refused) return fail(RQ_ERR_INVALID, "a chunk of this builder was refused: it can only be freed");
     if (!b->ordered) return fail(RQ_ERR_INVALID, "rq_builder_place_chunk before rq_builder_order");
     rq_index *idx = b->idx.get();
     if (i0 > idx->n || m > idx->n - i0) return fail(RQ_ERR_INVALID, "chunk outside [0, n)");
     if (!b->cov_place.add(i0, m)) return fail(RQ_ERR_INVALID, "rq_builder_place_chunk: rows [" + std::to_string(i0) + ", " + std::to_string(i0 + m) + ") overlap rows already placed");
-    if (m) {
+    if (m && typed) {
+        // L2: the 2-byte elements go to the row's final position as they are; cosine: the chunk is widened and normalised as in
+        // pass 1 (the same kernels, the same bits) and narrowed with R_t where it is stored
+        const uint16_t *rows = static_cast<const uint16_t *>(d_rows_any);
+        uint16_t *out = reinterpret_cast<uint16_t *>(idx->base.p);
+        const uint32_t d = b->d, dim = idx->dim;
+        if (idx->metric.id != RQ_METRIC_COSINE) {
+            place_half_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(m, 4), 1u << 20), 256>>>(rows, i0, m, d, dim, b->pos_of_id.p, out);
+        } else {
+            for (uint64_t c0 = 0; c0 < m; c0 += RQ_BUILD_CHUNK) {
+                const uint64_t mm = std::min<uint64_t>(RQ_BUILD_CHUNK, m - c0);
+                launch_widen(rows + c0 * d, idx->row_type, mm * d, b->wide.p);
+                RQC(transform_rows(idx->metric, dim, b->wide.p, mm, d, i0 + c0, b->xpad.p, nullptr, BaseView{}, nullptr, nullptr));
+                place_narrow_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(mm, 4), 1u << 20), 256>>>(b->xpad.p, i0 + c0, mm, dim, idx->row_type,
+                                                                                                       b->pos_of_id.p, out);
+            }
+        }
+        HIPC(hipDeviceSynchronize());  // the caller may reuse d_rows right away
+        HIPC(hipGetLastError());
+    } else if (m) {
         // the same transform as pass 1, stored at the row's final position (inner product: a caller feeding other rows than it did then is refused)
         RQC(transform_rows(idx->metric, idx->dim, d_rows, m, b->d, i0, nullptr, b->pos_of_id.p, idx->view(), b->ip_s_pre, b->ip_bad.p));
         HIPC(hipDeviceSynchronize());  // the caller may reuse d_rows right away
@@ -543,6 +626,7 @@ static rq_status builder_finish(rq_builder *bp, rq_index **out) {
     if (b->refused) return fail(RQ_ERR_INVALID, "a chunk of this builder was refused");
     if (!b->ordered || b->placed != b->idx->n) return fail(RQ_ERR_INVALID, "rq_builder_finish before every row was placed");
     b->pos_of_id.release();
+    b->wide.release(), b->xpad.release();
     RQC(finish_index(b->idx.get()));
     *out = b->idx.release();
     return RQ_OK;
@@ -576,10 +660,14 @@ static rq_status ip_resolve_bound(const float *d_x, uint64_t n, uint32_t d, floa
 }
 
 // The one-shot build from device-resident rows: the five builder calls.  An inner-product build first resolves its bound.
-static rq_status build_device(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, uint32_t cent_cols,
-                              const float *orthogonal_host, uint64_t seed, MetricSpec metric, rq_index **out) {
+// row_type: d_base holds n x d elements of that type (the chunks then go through the typed calls).
+static rq_status build_device(const void *d_base_any, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, uint32_t cent_cols,
+                              const float *orthogonal_host, uint64_t seed, MetricSpec metric, rq_index **out, uint32_t row_type = RQ_ROWS_F32) {
     if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
     *out = nullptr;
+    RQC(row_type_check(row_type, metric));
+    const float *d_base = static_cast<const float *>(d_base_any);
+    const bool typed = row_type != RQ_ROWS_F32;
     if (n && !d_base) return fail(RQ_ERR_INVALID, "bad build arguments");
     DevBuf<float> s;  // inner product: computed once -- the bound, the validity of every row and slot d of both passes come from it
     if (metric.id == RQ_METRIC_IP) {
@@ -589,12 +677,12 @@ static rq_status build_device(const float *d_base, uint64_t n, uint32_t d, const
         RQC(ip_resolve_bound(d_base, n, d, &metric.S, s.p));
     }
     rq_builder *b = nullptr;
-    RQC(builder_create(n, d, d_centroids, k, orthogonal_host, seed, 0, metric, cent_cols, &b));
+    RQC(builder_create(n, d, d_centroids, k, orthogonal_host, seed, 0, metric, cent_cols, &b, row_type));
     std::unique_ptr<rq_builder> guard(b);
     if (metric.id == RQ_METRIC_IP) b->ip_s_pre = s.p;
-    RQC(builder_assign(b, d_base, 0, n));
+    RQC(builder_assign(b, d_base_any, 0, n, typed));
     RQC(builder_order(b));
-    RQC(builder_place(b, d_base, 0, n));
+    RQC(builder_place(b, d_base_any, 0, n, typed));
     return builder_finish(guard.release(), out);
 }
 
@@ -640,9 +728,13 @@ static rq_status write_record(FILE *f, const void *data, uint32_t count, size_t 
 }
 
 static rq_status copy_base_rows(const rq_index *idx, uint64_t i0, uint64_t m, float *buf, bool to_index);
-static rq_status from_arrays(uint32_t dim, uint64_t n, uint32_t k, const float *base, const float *orthogonal,
+// row_type: `base` holds n x dim elements of that type, stored as they are
+static rq_status from_arrays(uint32_t dim, uint64_t n, uint32_t k, const void *base_any, const float *orthogonal,
                              const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
-                             const uint64_t *codes, const rq_factor_t *factors, const MetricSpec &metric, rq_index **out) {
+                             const uint64_t *codes, const rq_factor_t *factors, const MetricSpec &metric, rq_index **out,
+                             uint32_t row_type = RQ_ROWS_F32) {
+    const float *base = static_cast<const float *>(base_any);
+    RQC(row_type_check(row_type, metric));
     RQC(ensure_device());
     RQC(ensure_kernel_attributes());
     if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
@@ -658,7 +750,7 @@ static rq_status from_arrays(uint32_t dim, uint64_t n, uint32_t k, const float *
         return fail(RQ_ERR_INVALID, "null array");
     if (n >= 0xFFFFFFFFull) return fail(RQ_ERR_UNSUPPORTED, "n must fit u32");
     std::unique_ptr<rq_index> idx(new rq_index());
-    idx->dim = dim, idx->n = n, idx->k = k, idx->W = dim / 64, idx->metric = metric;
+    idx->dim = dim, idx->n = n, idx->k = k, idx->W = dim / 64, idx->metric = metric, idx->row_type = row_type;
     RQC(idx->P.alloc((size_t)dim * dim));
     RQC(idx->centroids.alloc((size_t)k * dim));
     RQC(idx->offsets.alloc((size_t)k + 1));
@@ -670,7 +762,8 @@ static rq_status from_arrays(uint32_t dim, uint64_t n, uint32_t k, const float *
     if (k && offsets[k] != n) return fail(RQ_ERR_INVALID, "offsets[k] != n");
     RQC(alloc_base_tiers(idx.get(), 0, offsets));
     if (n) {
-        RQC(copy_base_rows(idx.get(), 0, n, const_cast<float *>(base), /*to_index=*/true));
+        if (row_type) HIPC(hipMemcpy(idx->base.p, base_any, n * dim * 2, hipMemcpyHostToDevice));
+        else RQC(copy_base_rows(idx.get(), 0, n, const_cast<float *>(base), /*to_index=*/true));
         HIPC(hipMemcpy(idx->map_ids.p, map_ids, n * 4, hipMemcpyHostToDevice));
         HIPC(hipMemcpy(idx->codes.p, codes, n * idx->W * 8, hipMemcpyHostToDevice));
         HIPC(hipMemcpy(idx->factors.p, factors, n * 16, hipMemcpyHostToDevice));
@@ -911,6 +1004,24 @@ static rq_status copy_base_rows(const rq_index *idx, uint64_t i0, uint64_t m, fl
     std::vector<uint32_t> planes;  // split rows (common.h): transcoded here, on the host -- this is the dump / load path
     auto dev_copy = [&](uint64_t dev_row, uint64_t rows, float *hp) -> rq_status {
         if (!rows) return RQ_OK;
+        if (idx->row_type) {  // half-precision rows: widened (narrowed with R_t) here, on the host, in pieces
+            const uint64_t piece = std::max<uint64_t>(1, (64ull << 20) / dim);
+            std::vector<uint16_t> typed;
+            uint16_t *dev = reinterpret_cast<uint16_t *>(idx->base.p);
+            for (uint64_t r0 = 0; r0 < rows; r0 += piece) {
+                const uint64_t nr = std::min(piece, rows - r0), cells = nr * dim;
+                typed.resize(cells);
+                float *h = hp + r0 * dim;
+                if (to_index) {
+                    for (uint64_t e = 0; e < cells; ++e) typed[e] = rq_narrow_elem(h[e], idx->row_type);
+                    HIPC(hipMemcpy(dev + (dev_row + r0) * dim, typed.data(), cells * 2, hipMemcpyHostToDevice));
+                } else {
+                    HIPC(hipMemcpy(typed.data(), dev + (dev_row + r0) * dim, cells * 2, hipMemcpyDeviceToHost));
+                    for (uint64_t e = 0; e < cells; ++e) h[e] = rq_widen_elem(typed[e], idx->row_type);
+                }
+            }
+            return RQ_OK;
+        }
         if (!idx->split_rows) {
             if (to_index) HIPC(hipMemcpy(idx->base.p + dev_row * dim, hp, rows * dim * 4, hipMemcpyHostToDevice));
             else HIPC(hipMemcpy(hp, idx->base.p + dev_row * dim, rows * dim * 4, hipMemcpyDeviceToHost));

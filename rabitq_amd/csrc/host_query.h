@@ -567,6 +567,7 @@ struct Pass {
         const QSeg &seg = r.seg;
         pf.begin(PF_RERANK);
         const uint32_t fin_threads = nq <= 16 ? 1024u : 256u;  // a handful of queries: more lanes on each one's rerank
+        const bool half_rows = idx->row_type != RQ_ROWS_F32;    // the kernels whose rerank reads 2-byte rows (kernels_rerank.h: accurate_rows<true>)
         // survivor buffers beyond the default mean this index / these queries leave long run directories (overflow
         // re-runs, loose thresholds): those are ordered by the slot-bucketed kernel first; the fused kernel then sorts
         // only what fits its LDS
@@ -581,17 +582,20 @@ struct Pass {
             // a handful of queries: their final-stage survivors (~1000 rows each) are gathered by the whole chip -- one block
             // per query would pull them through a single CU's memory pipeline (~30 GB/s)
             if (nq <= 32) {
-                accurate_kernel<<<dim3(std::max(1u, std::min(16u, 256u / nq)), nq), 256, (size_t)dim * sizeof(float), st>>>(
+                auto accurate = half_rows ? accurate_half_kernel : accurate_kernel;
+                accurate<<<dim3(std::max(1u, std::min(16u, 256u / nq)), nq), 256, (size_t)dim * sizeof(float), st>>>(
                     ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, nullptr, probe_cluster, nprobe);
                 flags |= 2u;
             }
-            auto finish = topk < 64 ? sb_finish_kernel<true> : sb_finish_kernel<false>;
+            auto finish = half_rows ? (topk < 64 ? sb_finish_half_kernel<true> : sb_finish_half_kernel<false>)
+                                    : (topk < 64 ? sb_finish_kernel<true> : sb_finish_kernel<false>);
             finish<<<nq, fin_threads, (size_t)dim * sizeof(float) + (2 * RQ_SBF_RUNS + RQ_SBF_RECS) * 16, st>>>(
                 ws.surv.p, ws.runs.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, topk, rs, probe_cluster, nprobe, flags,
                 idx->map_ids.p, io.out_dist, io.out_id, io.out_n, ws.rough_cnt.p, ws.totals.p);
             sb_results_done = true;
         } else {
-            auto finish = qp.heuristic ? stage_finish_kernel<true> : stage_finish_kernel<false>;
+            auto finish = half_rows ? (qp.heuristic ? stage_finish_half_kernel<true> : stage_finish_half_kernel<false>)
+                                    : (qp.heuristic ? stage_finish_kernel<true> : stage_finish_kernel<false>);
             finish<<<nq, fin_threads, (size_t)dim * sizeof(float), st>>>(ws.surv.p, ws.runs.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, topk, rs,
                                                                          probe_cluster, nprobe, flags);
         }
@@ -630,6 +634,9 @@ struct Pass {
         else if (idx->split_rows && prefilter)  // tiered: the rows' own first plane is the pre-filter
             accurate_split_kernel<<<dim3(gx, nq), 256, (size_t)dim * sizeof(float) + (nprobe <= RQ_ACC8_LDS_PROBES ? (size_t)nprobe * 16 : 0), st>>>(
                 ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, rerank_order, ws.thr.p, probe_cluster, nprobe, ws.nshadow.p);
+        else if (idx->row_type)  // half-precision rows: every survivor reads its 2*dim-byte row (no shadow rows, no first plane)
+            accurate_half_kernel<<<dim3(gx, nq), 256, (size_t)dim * sizeof(float), st>>>(ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim,
+                                                                                         rerank_order, probe_cluster, nprobe);
         else
             accurate_kernel<<<dim3(gx, nq), 256, (size_t)dim * sizeof(float), st>>>(ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim,
                                                                                     rerank_order, probe_cluster, nprobe);

@@ -275,7 +275,11 @@ struct rq_index {
     DevBuf<ListTier> list_tier;      // k entries, tiered indexes only
     std::vector<ListTier> h_list_tier;
     bool split_rows = false;         // the raw vectors are split rows (common.h; set with the tiers, tiered indexes only)
-    BaseView view() const { return BaseView{base.p, base_host_dev, list_tier.p, k, split_rows ? 1u : 0u}; }
+    // RQ_ROWS_*: a half-precision index keeps the caller's 2-byte elements in `base` (n x dim of them, 2*dim bytes per row, padding
+    // +0): always untiered, never split, no shadow rows, never mutated
+    uint32_t row_type = RQ_ROWS_F32;
+    size_t row_bytes() const { return (size_t)dim * (row_type ? 2 : 4); }
+    BaseView view() const { return BaseView{base.p, base_host_dev, list_tier.p, k, split_rows ? 1u : 0u, row_type}; }
     ~rq_index() {
         if (base_host) (void)hipHostFree(base_host);
     }
@@ -895,6 +899,8 @@ static rq_status ensure_kernel_attributes() {
         set(reinterpret_cast<const void *>(coarse_candidates_kernel<4, 1>), (int)RQ_LDS_PER_BLOCK, "coarse_candidates_kernel<4,1>");
         set(reinterpret_cast<const void *>(sb_finish_kernel<true>), 104 * 1024, "sb_finish_kernel");   // (+ 33 KiB of static LDS)
         set(reinterpret_cast<const void *>(sb_finish_kernel<false>), 104 * 1024, "sb_finish_kernel");  // (+ 49 KiB of static LDS)
+        set(reinterpret_cast<const void *>(sb_finish_half_kernel<true>), 104 * 1024, "sb_finish_half_kernel");
+        set(reinterpret_cast<const void *>(sb_finish_half_kernel<false>), 104 * 1024, "sb_finish_half_kernel");
 #define RQ_SBQ_ATTR(WW)                                                                                  \
     set(reinterpret_cast<const void *>(sb_query_kernel<WW, 0, false>), 120 * 1024, "sb_query_kernel");   \
     set(reinterpret_cast<const void *>(sb_query_kernel<WW, 1, false>), 120 * 1024, "sb_query_kernel");   \

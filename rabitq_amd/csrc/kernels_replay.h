@@ -431,12 +431,12 @@ __device__ __forceinline__ StageCounts stage_begin(unsigned long long *__restric
 // One block per query finishes a stage: (A) exact rerank distances of the stage's survivors
 // (src/rerank.rs:85-90, 8 lanes = the 8 AVX lanes of src/simd.rs:14-73), (B) sort of the run
 // directory into the reference's visiting order, (C) wave 0 replays the ranker.
-template <bool HEURISTIC>
-__global__ __launch_bounds__(1024) void stage_finish_kernel(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
-                                                           unsigned long long *__restrict__ surv_cnt, const QSeg seg,
-                                                           const BaseView base,
+template <bool HEURISTIC, bool HALF>
+__device__ __forceinline__ void stage_finish_body(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
+                                                           unsigned long long *__restrict__ surv_cnt, const QSeg &seg,
+                                                           const BaseView &base,
                                                            const float *__restrict__ qpad, uint32_t dim, uint32_t topk,
-                                                           ReplayState st, const uint32_t *__restrict__ probe_cluster,
+                                                           const ReplayState &st, const uint32_t *__restrict__ probe_cluster,
                                                            uint32_t nprobe, uint32_t presorted) {
     __shared__ int32_t hkey[HEURISTIC ? 1 : RQ_MAX_TOPK];
     __shared__ uint32_t hid[HEURISTIC ? 1 : RQ_MAX_TOPK];
@@ -451,7 +451,7 @@ __global__ __launch_bounds__(1024) void stage_finish_kernel(SurvRec *__restrict_
         for (uint32_t c = threadIdx.x * 4; c < dim; c += blockDim.x * 4)
             *reinterpret_cast<float4 *>(fin_q + c) = *reinterpret_cast<const float4 *>(qpad + (uint64_t)b * dim + c);
         __syncthreads();
-        accurate_rows(recs, n, base, fin_q, dim, threadIdx.x >> 1, blockDim.x >> 1, probe_cluster + (uint64_t)b * nprobe);  // 256 or 1024 threads per query
+        accurate_rows<HALF>(recs, n, base, fin_q, dim, threadIdx.x >> 1, blockDim.x >> 1, probe_cluster + (uint64_t)b * nprobe);  // 256 or 1024 threads per query
     }
     // (B): up to RQ_SORT_LDS_RECS descriptors in LDS; longer directories were already ordered by sort_runs_mid_kernel
     // when the host launched it ahead of this kernel (presorted != 0), else (rare) bitonic in global memory
@@ -459,6 +459,25 @@ __global__ __launch_bounds__(1024) void stage_finish_kernel(SurvRec *__restrict_
     __syncthreads();                                  // (A)'s stores and (B)'s order visible to wave 0
     if (threadIdx.x < 64)                             // (C)
         replay_wave<HEURISTIC>(recs, runs + qat, nruns, topk, b, st, hkey, hid);
+}
+template <bool HEURISTIC>
+__global__ __launch_bounds__(1024) void stage_finish_kernel(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
+                                                           unsigned long long *__restrict__ surv_cnt, const QSeg seg,
+                                                           const BaseView base,
+                                                           const float *__restrict__ qpad, uint32_t dim, uint32_t topk,
+                                                           ReplayState st, const uint32_t *__restrict__ probe_cluster,
+                                                           uint32_t nprobe, uint32_t presorted) {
+    stage_finish_body<HEURISTIC, false>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted);
+}
+// stage_finish_kernel of a half-precision index: phase (A) reads 2-byte rows (accurate_rows<true>)
+template <bool HEURISTIC>
+__global__ __launch_bounds__(1024) void stage_finish_half_kernel(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
+                                                                unsigned long long *__restrict__ surv_cnt, const QSeg seg,
+                                                                const BaseView base,
+                                                                const float *__restrict__ qpad, uint32_t dim, uint32_t topk,
+                                                                ReplayState st, const uint32_t *__restrict__ probe_cluster,
+                                                                uint32_t nprobe, uint32_t presorted) {
+    stage_finish_body<HEURISTIC, true>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted);
 }
 
 // `runs_src`: where the stage's unsorted descriptors are when not in `runs` itself (an arena stage scatters them into the

@@ -85,26 +85,85 @@ __device__ __forceinline__ float exact_l2_pair_split(const float *__restrict__ r
     }
     return exact_l2_fold(a0, a1, a2, a3);
 }
-__device__ __forceinline__ float exact_l2_row(const RowRef rr, const float *q_lds, uint32_t dim, uint32_t hf) {
+// a HALF-PRECISION row (common.h: 2-byte elements as the caller gave them): lane half hf's elements 8u + 4hf + 0..3 of a chunk are
+// 8 bytes, widened exactly (f16: v_cvt_f32_f16, subnormals kept; bf16: bits << 16), and the arithmetic is exact_l2_pair's --
+// exact_l2_acc64 per 64 dimensions in chunk order, every fused chain inside its lane, then exact_l2_fold.  A round takes 128
+// dimensions (16 x 8 bytes per lane: the 128 bytes in flight of exact_l2_pair's round) and the odd 64 of dim = 64 (2m + 1) last.
+// x = the row + 4*hf elements.
+template <bool BF16>
+__device__ __forceinline__ void half_widen64(const uint2 *hv, float4 (&xv)[8]) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        if constexpr (BF16) {
+            xv[u].x = __builtin_bit_cast(float, hv[u].x << 16), xv[u].y = __builtin_bit_cast(float, hv[u].x & 0xFFFF0000u);
+            xv[u].z = __builtin_bit_cast(float, hv[u].y << 16), xv[u].w = __builtin_bit_cast(float, hv[u].y & 0xFFFF0000u);
+        } else {
+            typedef _Float16 rq_half2 __attribute__((ext_vector_type(2)));
+            const rq_half2 a = __builtin_bit_cast(rq_half2, hv[u].x), b = __builtin_bit_cast(rq_half2, hv[u].y);
+            xv[u].x = (float)a[0], xv[u].y = (float)a[1], xv[u].z = (float)b[0], xv[u].w = (float)b[1];
+        }
+    }
+}
+template <bool BF16>
+__device__ __forceinline__ float exact_l2_pair_half(const uint16_t *__restrict__ x, const float *q_lds, uint32_t dim, uint32_t hf) {
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+    uint32_t c = 0;
+    for (; c + 128 <= dim; c += 128) {
+        uint2 hv[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) hv[u] = *reinterpret_cast<const uint2 *>(x + c + 8 * u);
+        float4 xv[8];
+        half_widen64<BF16>(hv, xv);
+        exact_l2_acc64(xv, q_lds + c + 4 * hf, a0, a1, a2, a3);
+        half_widen64<BF16>(hv + 8, xv);
+        exact_l2_acc64(xv, q_lds + c + 64 + 4 * hf, a0, a1, a2, a3);
+    }
+    if (c < dim) {  // dim is a multiple of 64: one half round is left
+        uint2 hv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) hv[u] = *reinterpret_cast<const uint2 *>(x + c + 8 * u);
+        float4 xv[8];
+        half_widen64<BF16>(hv, xv);
+        exact_l2_acc64(xv, q_lds + c + 4 * hf, a0, a1, a2, a3);
+    }
+    return exact_l2_fold(a0, a1, a2, a3);
+}
+// an f32 row, plain or split
+__device__ __forceinline__ float exact_l2_row_f32(const RowRef rr, const float *q_lds, uint32_t dim, uint32_t hf) {
     // (a pair of lanes shares its survivor: the branch does not split the pair)
     return rr.split ? exact_l2_pair_split(rr.p, q_lds, dim, hf) : exact_l2_pair(rr.p + 4 * hf, q_lds, dim, hf);
 }
+// a half-precision row of either type
+__device__ __forceinline__ float exact_l2_row_half(const RowRef rr, const float *q_lds, uint32_t dim, uint32_t hf) {
+    const uint16_t *x = reinterpret_cast<const uint16_t *>(rr.p) + 4 * hf;
+    return rr.fmt == RQ_ROWS_BF16_ ? exact_l2_pair_half<true>(x, q_lds, dim, hf) : exact_l2_pair_half<false>(x, q_lds, dim, hf);
+}
+// a row of any format: the dispatch on RowRef's run-time fields
+__device__ __forceinline__ float exact_l2_row(const RowRef rr, const float *q_lds, uint32_t dim, uint32_t hf) {
+    return rr.fmt ? exact_l2_row_half(rr, q_lds, dim, hf) : exact_l2_row_f32(rr, q_lds, dim, hf);
+}
 
 // The row of a survivor: at its position in an untiered plain index (nothing else is read); else the survivor's slot names its
-// list, the list's tier record places the row (HBM or host link).
+// list, the list's tier record places the row (HBM or host link).  (Half-precision rows: half_rows_exact below.)
 __device__ __forceinline__ RowRef rerank_row(const BaseView &base, const SurvRec &r, const uint32_t *__restrict__ probe_row /* the query's probed lists, by slot */,
                                              uint32_t dim) {
-    if (base.host == nullptr && !base.split) return RowRef{base.dev + (uint64_t)r.pos * dim, false};
+    if (base.host == nullptr && !base.split) return RowRef{base.dev + (uint64_t)r.pos * dim, false, 0u};
     return base.row_of_slot(r.pos, probe_row, r.slot, dim);
 }
 
-// Exact f32 L2 of survivors recs[first], recs[first + step], ... against the query held in LDS
+// Exact f32 L2 of survivors recs[first], recs[first + step], ... against the query held in LDS.  HALF: the kernels a half-precision
+// index is given (every row at its position, 2*dim bytes apart: nothing but the row is read).  The launch picks the instantiation
+// from the index's row type, so the f32 kernels' loop -- whose two rounds of loads the compiler issues together -- is compiled
+// exactly as it was without the other format in it; which of the two half types a row holds stays a run-time field.
+template <bool HALF = false>
 __device__ __forceinline__ void accurate_rows(SurvRec *__restrict__ recs, uint32_t n, const BaseView &base,
                                               const float *q_lds, uint32_t dim, uint32_t first, uint32_t step,
                                               const uint32_t *__restrict__ probe_row) {
     const uint32_t hf = threadIdx.x & 1;
     for (uint32_t i = first; i < n; i += step) {
-        const float r = exact_l2_row(rerank_row(base, recs[i], probe_row, dim), q_lds, dim, hf);
+        float r;
+        if constexpr (HALF) r = exact_l2_row_half(base.row_at(recs[i].pos, dim), q_lds, dim, hf);
+        else r = exact_l2_row_f32(rerank_row(base, recs[i], probe_row, dim), q_lds, dim, hf);
         if (hf == 0) recs[i].accurate = r;
     }
 }
@@ -377,7 +436,7 @@ struct ShadowPlane {
         // x^ with an infinite element makes err infinite and t NaN or -inf: no rejection)
         err[0] = (sqrtf(nx) * up) * 3.9216e-3f + 1.0e-37f;
     }
-    __device__ __forceinline__ float exact(const SurvRec &r, const float *q_lds, uint32_t hf) const { return exact_l2_row(row_of(r), q_lds, dim, hf); }
+    __device__ __forceinline__ float exact(const SurvRec &r, const float *q_lds, uint32_t hf) const { return exact_l2_row_f32(row_of(r), q_lds, dim, hf); }
 };
 __global__ __launch_bounds__(256) void accurate_split_kernel(SurvRec *__restrict__ surv,
                                                              const unsigned long long *__restrict__ surv_cnt,
@@ -693,12 +752,10 @@ __global__ __launch_bounds__(256, q8_ring_waves(NPC)) void accurate_ring8_kernel
 // ---- the same three phases as separate launches: better for large batches, where all queries'
 // survivors are reranked with full-chip parallelism before the (latency-bound) replay --------------
 // grid (gx, nq); block 256
-__global__ __launch_bounds__(256) void accurate_kernel(SurvRec *__restrict__ surv,
-                                                       const unsigned long long *__restrict__ surv_cnt,
-                                                       const QSeg seg, const BaseView base,
-                                                       const float *__restrict__ qpad, uint32_t dim,
-                                                       const uint32_t *__restrict__ order,
-                                                       const uint32_t *__restrict__ probe_cluster, uint32_t nprobe) {
+template <bool HALF>
+__device__ __forceinline__ void accurate_body(SurvRec *__restrict__ surv, const unsigned long long *__restrict__ surv_cnt, const QSeg &seg,
+                                              const BaseView &base, const float *__restrict__ qpad, uint32_t dim,
+                                              const uint32_t *__restrict__ order, const uint32_t *__restrict__ probe_cluster, uint32_t nprobe) {
     // TWO lanes per candidate: lane half hf carries AVX lanes 4hf..4hf+3 (elements 8c + 4hf + 0..3, one
     // 16-byte load per chunk), so a row is fetched with float4 loads; the fold
     // ((a0+a4)+(a1+a5)) + ((a2+a6)+(a3+a7)) needs one exchange between the two lanes.
@@ -709,7 +766,24 @@ __global__ __launch_bounds__(256) void accurate_kernel(SurvRec *__restrict__ sur
     for (uint32_t c = threadIdx.x * 4; c < dim; c += 1024)
         *reinterpret_cast<float4 *>(acc_q + c) = *reinterpret_cast<const float4 *>(qpad + (uint64_t)b * dim + c);
     __syncthreads();
-    accurate_rows(surv + seg.at(b), n, base, acc_q, dim, blockIdx.x * 128 + (threadIdx.x >> 1), gridDim.x * 128,
-                  probe_cluster + (uint64_t)b * nprobe);
+    accurate_rows<HALF>(surv + seg.at(b), n, base, acc_q, dim, blockIdx.x * 128 + (threadIdx.x >> 1), gridDim.x * 128,
+                        probe_cluster + (uint64_t)b * nprobe);
+}
+__global__ __launch_bounds__(256) void accurate_kernel(SurvRec *__restrict__ surv,
+                                                       const unsigned long long *__restrict__ surv_cnt,
+                                                       const QSeg seg, const BaseView base,
+                                                       const float *__restrict__ qpad, uint32_t dim,
+                                                       const uint32_t *__restrict__ order,
+                                                       const uint32_t *__restrict__ probe_cluster, uint32_t nprobe) {
+    accurate_body<false>(surv, surv_cnt, seg, base, qpad, dim, order, probe_cluster, nprobe);
+}
+// accurate_kernel of a half-precision index (host_query.h launches it wherever that index would get accurate_kernel)
+__global__ __launch_bounds__(256) void accurate_half_kernel(SurvRec *__restrict__ surv,
+                                                            const unsigned long long *__restrict__ surv_cnt,
+                                                            const QSeg seg, const BaseView base,
+                                                            const float *__restrict__ qpad, uint32_t dim,
+                                                            const uint32_t *__restrict__ order,
+                                                            const uint32_t *__restrict__ probe_cluster, uint32_t nprobe) {
+    accurate_body<true>(surv, surv_cnt, seg, base, qpad, dim, order, probe_cluster, nprobe);
 }
 

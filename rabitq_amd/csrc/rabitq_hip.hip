@@ -230,6 +230,72 @@ rq_status rq_builder_create_ip(uint64_t n, uint32_t d, const float *d_centroids,
                                rq_builder **out) {
     return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, metric_ip(d, sq_bound), centroid_cols, out);
 }
+// ---- half-precision rows: the typed twins of the builds above ----
+rq_status rq_build_device_rows(const void *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
+                               const float *orthogonal_host, uint64_t seed, uint32_t metric, uint32_t row_type, rq_index **out) {
+    if (out) *out = nullptr;
+    RQC(row_type_check(row_type, MetricSpec{metric}));
+    RQC(metric_entry_check(metric));
+    return build_device(d_base, n, d, d_centroids, k, d, orthogonal_host, seed, MetricSpec{metric}, out, row_type);
+}
+rq_status rq_build_rows(const void *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k, const float *orthogonal,
+                        uint64_t seed, uint32_t metric, uint32_t row_type, rq_index **out) {
+    if (out) *out = nullptr;
+    RQC(row_type_check(row_type, MetricSpec{metric}));
+    RQC(metric_entry_check(metric));
+    if (row_type == RQ_ROWS_F32) return build_host(static_cast<const float *>(base), n, d, centroids, k, d, orthogonal, seed, MetricSpec{metric}, out);
+    RQC(ensure_device());
+    if ((n && !base) || !centroids) return fail(RQ_ERR_INVALID, "null argument");
+    DevBuf<uint16_t> db;  // the typed rows are staged as they are: no f32 image of the input is made
+    DevBuf<float> dc;
+    RQC(db.upload(static_cast<const uint16_t *>(base), n * d));
+    RQC(dc.upload(centroids, (size_t)k * d));
+    return build_device(db.p, n, d, dc.p, k, d, orthogonal, seed, MetricSpec{metric}, out, row_type);
+}
+rq_status rq_builder_create_rows(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
+                                 uint64_t seed, uint64_t max_device_base_bytes, uint32_t metric, uint32_t row_type, rq_builder **out) {
+    if (out) *out = nullptr;
+    RQC(row_type_check(row_type, MetricSpec{metric}));
+    RQC(metric_entry_check(metric));
+    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, MetricSpec{metric}, d, out, row_type);
+}
+rq_status rq_builder_assign_chunk_rows(rq_builder *b, const void *d_rows, uint64_t i0, uint64_t m) { return builder_assign(b, d_rows, i0, m, true); }
+rq_status rq_builder_place_chunk_rows(rq_builder *b, const void *d_rows, uint64_t i0, uint64_t m) { return builder_place(b, d_rows, i0, m, true); }
+rq_status rq_from_arrays_rows(uint32_t dim, uint64_t n, uint32_t k, const void *base, const float *orthogonal, const float *centroids,
+                              const uint32_t *offsets, const uint32_t *map_ids, const uint64_t *codes, const rq_factor_t *factors,
+                              uint32_t metric, uint32_t row_type, rq_index **out) {
+    if (out) *out = nullptr;
+    RQC(row_type_check(row_type, MetricSpec{metric}));
+    RQC(metric_entry_check(metric));
+    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, MetricSpec{metric}, out, row_type);
+}
+rq_status rq_row_type(const rq_index *idx, uint32_t *out) {
+    if (!idx || !out) return fail(RQ_ERR_INVALID, "null argument");
+    *out = idx->row_type;
+    return RQ_OK;
+}
+rq_status rq_widen_device(const void *d_x, uint32_t row_type, uint64_t count, float *d_out) {
+    RQC(ensure_device());
+    if (row_type != RQ_ROWS_F16 && row_type != RQ_ROWS_BF16) return fail(RQ_ERR_INVALID, "row_type must be RQ_ROWS_F16 or RQ_ROWS_BF16");
+    if (count && (!d_x || !d_out)) return fail(RQ_ERR_INVALID, "null argument");
+    launch_widen(static_cast<const uint16_t *>(d_x), row_type, count, d_out);
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipGetLastError());
+    return RQ_OK;
+}
+rq_status rq_widen(const void *x, uint32_t row_type, uint64_t count, float *out) {
+    RQC(ensure_device());
+    if (row_type != RQ_ROWS_F16 && row_type != RQ_ROWS_BF16) return fail(RQ_ERR_INVALID, "row_type must be RQ_ROWS_F16 or RQ_ROWS_BF16");
+    if (count && (!x || !out)) return fail(RQ_ERR_INVALID, "null argument");
+    DevBuf<uint16_t> dx;
+    DevBuf<float> dout;
+    RQC(dx.upload(static_cast<const uint16_t *>(x), count));
+    RQC(dout.alloc(count));
+    RQC(rq_widen_device(dx.p, row_type, count, dout.p));
+    if (count) HIPC(hipMemcpy(out, dout.p, count * 4, hipMemcpyDeviceToHost));
+    return RQ_OK;
+}
+
 rq_status rq_builder_assign_chunk(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m) { return builder_assign(b, d_rows, i0, m); }
 rq_status rq_builder_order(rq_builder *b) { return builder_order(b); }
 rq_status rq_builder_place_chunk(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m) { return builder_place(b, d_rows, i0, m); }
@@ -303,6 +369,15 @@ rq_status rq_load_dir(const char *dir, rq_index **out) {
         fclose(mf);
         if (!metric_from_file_text(std::string(buf, got), &metric)) return fail(RQ_ERR_IO, "metric: unknown or malformed content in " + d + "/metric");
     }
+    uint32_t row_type = RQ_ROWS_F32;  // the `rows` file of a half-precision index's dump
+    if (FILE *rf = fopen((d + "/rows").c_str(), "rb")) {
+        char buf[16] = {0};
+        const size_t got = fread(buf, 1, sizeof buf - 1, rf);
+        fclose(rf);
+        const std::string text(buf, got);
+        if (text.empty() || text.back() != '\n' || !row_type_from_text(text.substr(0, text.size() - 1), &row_type))
+            return fail(RQ_ERR_IO, "rows: unknown content in " + d + "/rows");
+    }
     const uint32_t dim = (uint32_t)ortho.lens.size();  // :108 dim = orthogonal.nrows()
     if (dim == 0 || dim % 64 != 0) return fail(RQ_ERR_DIM_MISMATCH, "orthogonal.fvecs: dim % 64 != 0 (rabitq.rs:109)");
     if (metric.id == RQ_METRIC_IP && !(ip_d_ok(metric.d, dim) && ip_bound_ok(metric.S)))
@@ -334,10 +409,17 @@ rq_status rq_load_dir(const char *dir, rq_index **out) {
     if (oip[k] != n) return fail(RQ_ERR_IO, "offsets[k] != number of vectors");
     for (uint32_t j = 0; j < k; ++j)
         if (oip[j] > oip[j + 1]) return fail(RQ_ERR_IO, "offsets are not non-decreasing");
-    return from_arrays(dim, n, k, reinterpret_cast<const float *>(base.data.data()),
+    if (row_type && metric.id == RQ_METRIC_IP) return fail(RQ_ERR_IO, "rows: an inner-product index has no half-precision rows (" + d + ")");
+    std::vector<uint16_t> typed;  // half-precision rows: every value of base.fvecs must be one of the type's
+    const void *base_arg = base.data.data();
+    if (row_type) {
+        RQC(narrow_exact(reinterpret_cast<const float *>(base.data.data()), n * dim, row_type, typed, d + "/base.fvecs"));
+        base_arg = typed.data();
+    }
+    return from_arrays(dim, n, k, base_arg,
                        reinterpret_cast<const float *>(ortho.data.data()), c.data(), oip, oip + (total - last),
                        reinterpret_cast<const uint64_t *>(bin.data.data()),
-                       reinterpret_cast<const rq_factor_t *>(fac.data.data()), metric, out);
+                       reinterpret_cast<const rq_factor_t *>(fac.data.data()), metric, out, row_type);
 }
 
 rq_status rq_get_array(const rq_index *idx, int which, void *dst, uint64_t dst_bytes);
@@ -419,6 +501,13 @@ rq_status rq_dump_dir(const rq_index *idx, const char *dir) {
     } else {
         remove((d + "/metric").c_str());  // (a directory that held a cosine dump before)
     }
+    if (idx->row_type) {  // base.fvecs above holds W(rows): the reference loads the directory and answers identically
+        RQC(open("rows", &f));
+        const bool ok = fputs(row_type_text(idx->row_type), f) >= 0 && fputc('\n', f) >= 0;
+        if (fclose(f) != 0 || !ok) return fail(RQ_ERR_IO, "write error on " + d + "/rows");
+    } else {
+        remove((d + "/rows").c_str());
+    }
     return RQ_OK;
 }
 
@@ -468,6 +557,7 @@ rq_status rq_dump_json(const rq_index *idx, const char *path) {
     }
     o.raw("]");
     o.raw(metric_json_members(idx->metric).c_str());
+    if (idx->row_type) o.raw(",\"rows\":\""), o.raw(row_type_text(idx->row_type)), o.raw("\"");
     o.raw("}");
     const bool closed = fclose(f) == 0;
     if (!o.ok || !closed) return fail(RQ_ERR_IO, std::string("write error on ") + path);
@@ -491,7 +581,7 @@ rq_status rq_load_json(const char *path, rq_index **out) {
     std::vector<float> base, P, cent, bias;
     std::vector<unsigned long long> off, ids, codes;
     std::vector<rq_factor_t> fac;
-    std::string metric_name;
+    std::string metric_name, rows_name;
     unsigned long long ip_d = 1ull << 32, ip_bits = 1ull << 32;  // members of an inner-product index (the preset: absent)
     bool good = in.need('{');
     if (good && !in.lit('}')) {
@@ -525,6 +615,11 @@ rq_status rq_load_json(const char *path, rq_index **out) {
                 const char *v0 = in.p;
                 good = in.skip();
                 if (good) metric_name.assign(v0, in.p);
+            } else if (k == "rows") {
+                in.ws();
+                const char *v0 = in.p;
+                good = in.skip();
+                if (good) rows_name.assign(v0, in.p);
             } else if (k == "ip_d") good = in.num_u64(ip_d);
             else if (k == "ip_sq_bound_bits") good = in.num_u64(ip_bits);
             else good = in.skip();
@@ -552,8 +647,18 @@ rq_status rq_load_json(const char *path, rq_index **out) {
     }
     std::vector<uint32_t> off32(off.begin(), off.end()), ids32(ids.begin(), ids.end());
     std::vector<uint64_t> codes64(codes.begin(), codes.end());
-    return from_arrays((uint32_t)dim, n, (uint32_t)k, base_rows.data(), P.data(), cent_rows.data(), off32.data(), ids32.data(),
-                       codes64.data(), fac.data(), metric, out);
+    uint32_t row_type = RQ_ROWS_F32;
+    if (!rows_name.empty() && !(rows_name.size() > 2 && rows_name.front() == '"' && rows_name.back() == '"' &&
+                                row_type_from_text(rows_name.substr(1, rows_name.size() - 2), &row_type) && metric.id != RQ_METRIC_IP))
+        return fail(RQ_ERR_IO, std::string("unknown \"rows\" member ") + rows_name + " in " + path);
+    std::vector<uint16_t> typed;
+    const void *base_arg = base_rows.data();
+    if (row_type) {
+        RQC(narrow_exact(base_rows.data(), n * dim, row_type, typed, path));
+        base_arg = typed.data();
+    }
+    return from_arrays((uint32_t)dim, n, (uint32_t)k, base_arg, P.data(), cent_rows.data(), off32.data(), ids32.data(),
+                       codes64.data(), fac.data(), metric, out, row_type);
 }
 
 void rq_free(rq_index *idx) { delete idx; }
@@ -574,6 +679,8 @@ rq_status rq_get_device_ptr(const rq_index *idx, int which, const void **out_ptr
                 return fail(RQ_ERR_UNSUPPORTED, "the raw vectors of this index are tiered (HBM + pinned host memory): no single device array; use rq_get_array");
             if (idx->split_rows)  // (common.h) not an array of f32 rows
                 return fail(RQ_ERR_UNSUPPORTED, "the raw vectors of this index are stored as split rows (two 16-bit planes per row): no f32 device array; use rq_get_array");
+            if (idx->row_type)
+                return fail(RQ_ERR_UNSUPPORTED, "the raw vectors of this index are half-precision rows: no f32 device array; use rq_get_array, or RQ_ARR_BASE_ROWS for the stored rows");
             *out_ptr = idx->base.p, *out_bytes = idx->n_dev * idx->dim * 4;
             break;
         case RQ_ARR_ORTHOGONAL: *out_ptr = idx->P.p, *out_bytes = (uint64_t)idx->dim * idx->dim * 4; break;
@@ -582,6 +689,10 @@ rq_status rq_get_device_ptr(const rq_index *idx, int which, const void **out_ptr
         case RQ_ARR_MAP_IDS: *out_ptr = idx->map_ids.p, *out_bytes = idx->n * 4; break;
         case RQ_ARR_CODES: *out_ptr = idx->codes.p, *out_bytes = idx->n * idx->W * 8; break;
         case RQ_ARR_FACTORS: *out_ptr = idx->factors.p, *out_bytes = idx->n * 16; break;
+        case RQ_ARR_BASE_ROWS:
+            if (!idx->row_type) return fail(RQ_ERR_INVALID, "RQ_ARR_BASE_ROWS: this index stores f32 rows (RQ_ARR_BASE)");
+            *out_ptr = idx->base.p, *out_bytes = idx->n * idx->dim * 2;
+            break;
         default: return fail(RQ_ERR_INVALID, "unknown array id");
     }
     return RQ_OK;
@@ -590,7 +701,7 @@ rq_status rq_get_device_ptr(const rq_index *idx, int which, const void **out_ptr
 rq_status rq_get_array(const rq_index *idx, int which, void *dst, uint64_t dst_bytes) {
     const void *p;
     uint64_t bytes;
-    if (idx && which == RQ_ARR_BASE && (idx->n_dev < idx->n || idx->split_rows)) {  // both tiers / split rows
+    if (idx && which == RQ_ARR_BASE && (idx->n_dev < idx->n || idx->split_rows || idx->row_type)) {  // both tiers / split rows / half rows (widened)
         if (!dst || dst_bytes < idx->n * idx->dim * 4) return fail(RQ_ERR_INVALID, "destination too small");
         return copy_base_rows(idx, 0, idx->n, static_cast<float *>(dst), false);
     }

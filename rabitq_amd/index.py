@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import BuildStatsT, Info, MetricsT, ProfileT, check, lib
 
-ARR_BASE, ARR_ORTHOGONAL, ARR_CENTROIDS, ARR_OFFSETS, ARR_MAP_IDS, ARR_CODES, ARR_FACTORS = range(7)
+ARR_BASE, ARR_ORTHOGONAL, ARR_CENTROIDS, ARR_OFFSETS, ARR_MAP_IDS, ARR_CODES, ARR_FACTORS, ARR_BASE_ROWS = range(8)
 
 
 def _addr(a):
@@ -26,7 +26,33 @@ def _sq_bound(max_sq_norm) -> float:
 
 
 def _f32(a):
+    """-> contiguous f32 (float16 input is widened here, on the host: exact)."""
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _typed_rows(base, rows):
+    """(base, rows=) of the constructors -> (contiguous array as the library reads it, RQ_ROWS_* id).  rows=None: float16 arrays
+    are f16 rows, everything else f32.  rows="f16" takes float16 (or uint16 bit patterns), rows="bf16" uint16 bit patterns."""
+    a = np.asarray(base)
+    rt = (_lib.ROWS_F16 if a.dtype == np.float16 else _lib.ROWS_F32) if rows is None else _lib.row_type_id(rows)
+    if rt == _lib.ROWS_F32:
+        return _f32(a), rt
+    if rt == _lib.ROWS_F16 and a.dtype == np.float16:
+        return np.ascontiguousarray(a), rt
+    if a.dtype != np.uint16:
+        raise TypeError(f"rows={_lib.ROW_TYPE_NAMES.get(rt, rt)!r} takes a uint16 array of bit patterns"
+                        + (" or a float16 array" if rt == _lib.ROWS_F16 else "") + f", not {a.dtype}")
+    return np.ascontiguousarray(a), rt
+
+
+def widen(x, rows="f16"):
+    """W(x): f16 / bf16 elements (float16, or uint16 bit patterns) -> f32, on the GPU (rq_widen); any shape."""
+    a, rt = _typed_rows(x, rows)
+    if rt == _lib.ROWS_F32:
+        return a
+    out = np.empty(a.shape, dtype=np.float32)
+    check(lib().rq_widen(_addr(a), rt, a.size, _addr(out)))
+    return out
 
 
 def pack_filter_bits(ids=None, mask=None, nbits=None):
@@ -150,6 +176,9 @@ class RaBitQ:
         self.split_rows = bool(info.split_rows)   # raw vectors stored as two 16-bit planes per row (option "split_rows")
         self.metric = _lib.METRIC_NAMES.get(int(info.metric), "l2")   # a cosine index normalises rows and queries itself; an "ip" index augments rows
         self._ip_d = self.ip_params[0] if self.metric == "ip" else 0   # the raw row length add() and the queries must have
+        rt = C.c_uint32()
+        check(lib().rq_row_type(self._h, C.byref(rt)))
+        self.row_type = _lib.ROW_TYPE_NAMES.get(int(rt.value), "f32")   # "f16" / "bf16": the raw vectors are stored in that type, 2*dim bytes each
 
     # ---- RaBitQ::from_path (src/rabitq.rs:159) ------------------------------------------------
     @classmethod
@@ -170,10 +199,20 @@ class RaBitQ:
         return cls(h)
 
     @classmethod
-    def build(cls, base, centroids, orthogonal=None, seed: int = 0, metric="l2", max_sq_norm=None) -> "RaBitQ":
+    def build(cls, base, centroids, orthogonal=None, seed: int = 0, metric="l2", max_sq_norm=None, rows=None) -> "RaBitQ":
         """from_path on in-memory arrays (base n x d, centroids k x d; metric="ip": k x c with d <= c <= ceil64(d + 1), missing
-        columns are zero)."""
-        base, centroids = _f32(base), _f32(centroids)
+        columns are zero).  A float16 `base` (or rows="f16" / rows="bf16" with a uint16 array of bit patterns) makes a half-precision
+        index: the rows are stored as given, 2*dim bytes each."""
+        base, rt = _typed_rows(base, rows)
+        centroids = _f32(centroids)
+        if rt != _lib.ROWS_F32:
+            if base.ndim != 2 or centroids.ndim != 2 or base.shape[1] != centroids.shape[1]:
+                raise _lib.RabitqError(-2, "base and centroids must be 2-D with the same dimension (rabitq.rs:165)")
+            P = _f32(orthogonal) if orthogonal is not None else None
+            h = C.c_void_p()
+            check(lib().rq_build_rows(_addr(base), base.shape[0], base.shape[1], _addr(centroids), centroids.shape[0], _addr(P),
+                                      seed, _lib.metric_id(metric), rt, C.byref(h)))
+            return cls(h)
         if _lib.metric_id(metric) == _lib.METRIC_IP:
             if base.ndim != 2 or centroids.ndim != 2:
                 raise _lib.RabitqError(-2, "base and centroids must be 2-D")
@@ -192,11 +231,15 @@ class RaBitQ:
 
     @classmethod
     def build_device(cls, base_ptr: int, n: int, d: int, centroids_ptr: int, k: int, orthogonal=None,
-                     seed: int = 0, metric="l2", max_sq_norm=None, centroid_cols: int = None) -> "RaBitQ":
+                     seed: int = 0, metric="l2", max_sq_norm=None, centroid_cols: int = None, rows="f32") -> "RaBitQ":
         """Build from device-resident arrays (raw HIP device addresses, e.g. torch.Tensor.data_ptr()).  metric="ip": the
-        centroids are k x centroid_cols (None: d)."""
+        centroids are k x centroid_cols (None: d).  rows="f16" / "bf16": base_ptr holds n x d elements of that type."""
         P = _f32(orthogonal) if orthogonal is not None else None
         h = C.c_void_p()
+        if _lib.row_type_id(rows) != _lib.ROWS_F32:
+            check(lib().rq_build_device_rows(C.c_void_p(base_ptr), n, d, C.c_void_p(centroids_ptr), k, _addr(P), seed,
+                                             _lib.metric_id(metric), _lib.row_type_id(rows), C.byref(h)))
+            return cls(h)
         if _lib.metric_id(metric) == _lib.METRIC_IP:
             check(lib().rq_build_device_ip(C.c_void_p(base_ptr), n, d, C.c_void_p(centroids_ptr), k, _addr(P), seed,
                                            d if centroid_cols is None else centroid_cols, _sq_bound(max_sq_norm), C.byref(h)))
@@ -207,10 +250,11 @@ class RaBitQ:
 
     @classmethod
     def builder(cls, n: int, d: int, centroids_ptr: int, k: int, orthogonal=None, seed: int = 0,
-                max_device_base_bytes: int = 0, metric="l2", max_sq_norm=None, centroid_cols: int = None) -> "Builder":
+                max_device_base_bytes: int = 0, metric="l2", max_sq_norm=None, centroid_cols: int = None, rows="f32") -> "Builder":
         """Streamed two-pass build for inputs that are not resident (include/rabitq_hip.h: rq_builder_*).  metric="ip" needs
-        max_sq_norm (the largest row_sqnorm_max over the chunks): the streamed build has no automatic bound."""
-        return Builder(n, d, centroids_ptr, k, orthogonal, seed, max_device_base_bytes, metric, max_sq_norm, centroid_cols)
+        max_sq_norm (the largest row_sqnorm_max over the chunks): the streamed build has no automatic bound.  rows="f16" /
+        "bf16": the chunks hold elements of that type."""
+        return Builder(n, d, centroids_ptr, k, orthogonal, seed, max_device_base_bytes, metric, max_sq_norm, centroid_cols, rows)
 
     # ---- load_from_dir / dump_to_dir (src/rabitq.rs:84, :128) ---------------------------------
     @classmethod
@@ -234,14 +278,21 @@ class RaBitQ:
 
     @classmethod
     def from_arrays(cls, base, orthogonal, centroids, offsets, map_ids, codes, factors, metric="l2", max_sq_norm=None,
-                    d: int = None) -> "RaBitQ":
+                    d: int = None, rows=None) -> "RaBitQ":
         """From the reference's in-memory arrays (what load_from_dir produces).  The arrays are taken as they are; metric="cosine"
-        only marks the index, so that its queries and added rows are normalised (`base` then holds normalised rows already)."""
-        base, orthogonal, centroids, factors = _f32(base), _f32(orthogonal), _f32(centroids), _f32(factors)
+        only marks the index, so that its queries and added rows are normalised (`base` then holds normalised rows already).
+        A float16 `base` (or rows="f16" / "bf16" with uint16 bit patterns), n x dim, makes a half-precision index."""
+        base, rt = _typed_rows(base, rows)
+        orthogonal, centroids, factors = _f32(orthogonal), _f32(centroids), _f32(factors)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
         map_ids = np.ascontiguousarray(map_ids, dtype=np.uint32)
         codes = np.ascontiguousarray(codes, dtype=np.uint64)
         h = C.c_void_p()
+        if rt != _lib.ROWS_F32:
+            check(lib().rq_from_arrays_rows(orthogonal.shape[0], map_ids.size, offsets.size - 1, _addr(base), _addr(orthogonal),
+                                            _addr(centroids), _addr(offsets), _addr(map_ids), _addr(codes), _addr(factors),
+                                            _lib.metric_id(metric), rt, C.byref(h)))
+            return cls(h)
         if metric == "ip" and max_sq_norm is not None:   # an inner-product index: `base` holds augmented rows, d = the raw row length
             if d is None:
                 raise ValueError('from_arrays(metric="ip") needs d, the raw row length')
@@ -279,7 +330,15 @@ class RaBitQ:
 
     @property
     def base(self):
+        """The raw vectors as f32, cluster order (a half-precision index: its rows widened)."""
         return self._get(ARR_BASE, (self.n, self.dim), np.float32)
+
+    @property
+    def base_rows(self):
+        """The raw vectors in the type the index stores: float32, float16, or (bf16) uint16 bit patterns."""
+        if self.row_type == "f32":
+            return self.base
+        return self._get(ARR_BASE_ROWS, (self.n, self.dim), np.float16 if self.row_type == "f16" else np.uint16)
 
     @property
     def orthogonal(self):
@@ -573,9 +632,14 @@ class Builder:
     """assign_chunk every row -> order() -> place_chunk every row -> finish() -> RaBitQ.  Chunks are device pointers."""
 
     def __init__(self, n, d, centroids_ptr, k, orthogonal=None, seed=0, max_device_base_bytes=0, metric="l2", max_sq_norm=None,
-                 centroid_cols=None):
+                 centroid_cols=None, rows="f32"):
         P = _f32(orthogonal) if orthogonal is not None else None
         self._b = C.c_void_p()
+        self._typed = _lib.row_type_id(rows) != _lib.ROWS_F32   # chunks of the builder's row type go through the _rows calls
+        if self._typed:
+            check(lib().rq_builder_create_rows(n, d, C.c_void_p(centroids_ptr), k, _addr(P), seed, max_device_base_bytes,
+                                               _lib.metric_id(metric), _lib.row_type_id(rows), C.byref(self._b)))
+            return
         if _lib.metric_id(metric) == _lib.METRIC_IP:
             check(lib().rq_builder_create_ip(n, d, C.c_void_p(centroids_ptr), k, _addr(P), seed, max_device_base_bytes,
                                              d if centroid_cols is None else centroid_cols, _sq_bound(max_sq_norm), C.byref(self._b)))
@@ -584,13 +648,15 @@ class Builder:
                                              _lib.metric_id(metric), C.byref(self._b)))
 
     def assign_chunk(self, rows_ptr: int, i0: int, m: int) -> None:
-        check(lib().rq_builder_assign_chunk(self._b, C.c_void_p(rows_ptr), i0, m))
+        fn = lib().rq_builder_assign_chunk_rows if self._typed else lib().rq_builder_assign_chunk
+        check(fn(self._b, C.c_void_p(rows_ptr), i0, m))
 
     def order(self) -> None:
         check(lib().rq_builder_order(self._b))
 
     def place_chunk(self, rows_ptr: int, i0: int, m: int) -> None:
-        check(lib().rq_builder_place_chunk(self._b, C.c_void_p(rows_ptr), i0, m))
+        fn = lib().rq_builder_place_chunk_rows if self._typed else lib().rq_builder_place_chunk
+        check(fn(self._b, C.c_void_p(rows_ptr), i0, m))
 
     def stats(self) -> dict:
         st = BuildStatsT()
