@@ -84,7 +84,8 @@ typedef struct {
  * later in 0.8, additions only: rq_query_batch_device_begin_filtered, option "small_batch_filtered" -- filtered batches of <= 64
  * queries on the small-batch path;
  * 0.9.0: inner-product metric, additions only -- RQ_METRIC_IP, rq_*_ip, rq_ip_*, rq_augment*, rq_row_sqnorm_max*;
- * 0.10.0: half-precision rows, additions only -- RQ_ROWS_*, rq_*_rows, rq_row_type, rq_widen*, RQ_ARR_BASE_ROWS).
+ * 0.10.0: half-precision rows, additions only -- RQ_ROWS_*, rq_*_rows, rq_row_type, rq_widen*, RQ_ARR_BASE_ROWS;
+ * 0.11.0: byte rows, two more values of row_type and no new symbol -- RQ_ROWS_U8, RQ_ROWS_I8).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -186,8 +187,21 @@ rq_status rq_ip_radius_device(const rq_index *idx, const float *d_queries, uint3
  * RQ_ARR_BASE_ROWS (rq_get_array, rq_get_device_ptr): the stored n x dim 2-byte rows, n * dim * 2 bytes; RQ_ERR_INVALID on an f32
  * index.  Persistence: rq_dump_dir writes the crate's files with base.fvecs widened (the reference loads it and answers
  * identically) plus a file `rows` holding "f16\n" / "bf16\n"; rq_load_dir with a `rows` file stores half rows (a value of
- * base.fvecs the type cannot hold, or an unknown text: RQ_ERR_IO); the JSON image carries "rows":"f16" / "bf16" likewise. */
-enum { RQ_ROWS_F32 = 0, RQ_ROWS_F16 = 1, RQ_ROWS_BF16 = 2 };
+ * base.fvecs the type cannot hold, or an unknown text: RQ_ERR_IO); the JSON image carries "rows":"f16" / "bf16" likewise.
+ *
+ * Byte rows (0.11.0): RQ_ROWS_U8 and RQ_ROWS_I8 store the caller's n x d one-byte elements as given, n x dim of them, the padding
+ * slots 0x00: dim bytes per vector, no f32 copy, no shadow rows, no split rows, no tiers, and the build never holds an n x dim f32
+ * array.  W(u8) = the integer as f32, W(i8) = the two's-complement integer as f32; both are exact, and the narrowing the loaders
+ * use is the exact inverse on representable values.  A byte-row L2 index of (b, centroids, P) equals, bit for bit, the f32 L2 index
+ * of (W(b), centroids, P): every array, rq_info, and the ids, order, distance bits, counts, status and counters of every query
+ * entry listed above.  Queries, centroids and P stay f32.  Every _rows entry, rq_row_type and rq_widen* (`count` one-byte elements,
+ * any alignment) take the two values; RQ_ARR_BASE returns W(b), RQ_ARR_BASE_ROWS the stored n * dim bytes.
+ * Refused, each leaving nothing allocated and the index untouched: RQ_METRIC_COSINE (a normalised row is not a value of the type)
+ * and RQ_METRIC_IP with byte rows, rq_add / rq_remove, an index over the HBM budget, rq_get_device_ptr(RQ_ARR_BASE) -- all
+ * RQ_ERR_UNSUPPORTED.  Values 3, 6 and above remain RQ_ERR_INVALID.  Persistence: base.fvecs holds W(b), the `rows` file "u8\n" /
+ * "i8\n", the JSON member "rows":"u8" / "i8"; a load whose base.fvecs holds a value the named type cannot represent (0.5, 256,
+ * -1 or -0 under u8, a NaN), or an unknown text, is RQ_ERR_IO. */
+enum { RQ_ROWS_F32 = 0, RQ_ROWS_F16 = 1, RQ_ROWS_BF16 = 2, RQ_ROWS_U8 = 4, RQ_ROWS_I8 = 5 };
 struct rq_builder;
 /* rq_build_metric / rq_build_device_metric with typed rows: base is n x d elements of row_type (host / device memory; 2-byte
  * aligned is enough), centroids stay f32. */
@@ -208,7 +222,7 @@ rq_status rq_from_arrays_rows(uint32_t dim, uint64_t n, uint32_t k, const void *
                               const float *centroids, const uint32_t *offsets, const uint32_t *map_ids, const uint64_t *codes,
                               const rq_factor_t *factors, uint32_t metric, uint32_t row_type, rq_index **out);
 rq_status rq_row_type(const rq_index *idx, uint32_t *out);
-/* out[i] = W(x[i]) for `count` elements of row_type (any count; x 2-byte aligned).  rq_widen: host pointers; rq_widen_device:
+/* out[i] = W(x[i]) for `count` elements of row_type (any count; x 2-byte aligned, byte elements: any alignment).  rq_widen: host pointers; rq_widen_device:
  * device pointers, returns with `out` complete. */
 rq_status rq_widen(const void *x, uint32_t row_type, uint64_t count, float *out);
 rq_status rq_widen_device(const void *d_x, uint32_t row_type, uint64_t count, float *d_out);
@@ -319,7 +333,7 @@ rq_status rq_info(const rq_index *idx, rq_info_t *out);
 /* Copy one array of the index back to host memory (sizes as in rq_from_arrays). */
 enum { RQ_ARR_BASE = 0, RQ_ARR_ORTHOGONAL, RQ_ARR_CENTROIDS, RQ_ARR_OFFSETS, RQ_ARR_MAP_IDS,
        RQ_ARR_CODES, RQ_ARR_FACTORS,
-       RQ_ARR_BASE_ROWS /* = 7: the stored 2-byte rows of a half-precision index, n * dim * 2 bytes (an f32 index: RQ_ERR_INVALID) */ };
+       RQ_ARR_BASE_ROWS /* = 7: the stored rows of a half-precision (n * dim * 2 bytes) or byte-row (n * dim bytes) index (an f32 index: RQ_ERR_INVALID) */ };
 rq_status rq_get_array(const rq_index *idx, int which, void *dst, uint64_t dst_bytes);
 /* Device pointer of one array (valid until rq_free); for zero-copy hand-over to a caller that
  * already lives on the GPU.  RQ_ARR_BASE: every row at its position -- only when n_hbm == n; on a tiered index (list

@@ -53,13 +53,13 @@ def metric_id(metric) -> int:
     return int(metric)
 
 
-ROWS_F32, ROWS_F16, ROWS_BF16 = 0, 1, 2   # RQ_ROWS_*
-ROW_TYPES = {"f32": ROWS_F32, "f16": ROWS_F16, "bf16": ROWS_BF16}
+ROWS_F32, ROWS_F16, ROWS_BF16, ROWS_U8, ROWS_I8 = 0, 1, 2, 4, 5   # RQ_ROWS_*
+ROW_TYPES = {"f32": ROWS_F32, "f16": ROWS_F16, "bf16": ROWS_BF16, "u8": ROWS_U8, "i8": ROWS_I8}
 ROW_TYPE_NAMES = {v: k for k, v in ROW_TYPES.items()}
 
 
 def row_type_id(rows) -> int:
-    """"f32" / "f16" / "bf16" (or an RQ_ROWS_* value) -> the C ABI's row_type."""
+    """"f32" / "f16" / "bf16" / "u8" / "i8" (or an RQ_ROWS_* value) -> the C ABI's row_type."""
     if isinstance(rows, str):
         if rows.lower() not in ROW_TYPES:
             raise ValueError(f"rows must be one of {sorted(ROW_TYPES)}, not {rows!r}")

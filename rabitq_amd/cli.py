@@ -42,6 +42,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="metric of the index when building (a saved index keeps its own): cosine normalises rows and queries "
                          "on the GPU, distances are 2 - 2 cos; ip is maximum inner product search (rows get one more "
                          "coordinate, distances are S + |q|^2 - 2<x, q> with S the largest squared row norm)")
+    ap.add_argument("--rows", choices=["u8", "i8"], default=None,
+                    help="build a byte-row index (L2 only): the base is a .bvecs file whose one-byte elements are stored as given, "
+                         "dim bytes per vector; the centroids stay an fvecs file")
     return ap
 
 
@@ -53,7 +56,11 @@ def main(argv=None) -> int:
         index = RaBitQ.load_from_dir(args.saved)
     else:
         print("training...")
-        index = RaBitQ.from_path(args.base, args.centroids, seed=args.seed, metric=args.metric)
+        if args.rows:
+            base = vecs.read_bvecs(args.base, np.uint8 if args.rows == "u8" else np.int8)
+            index = RaBitQ.build(base, vecs.read_matrix(args.centroids), seed=args.seed, metric=args.metric, rows=args.rows)
+        else:
+            index = RaBitQ.from_path(args.base, args.centroids, seed=args.seed, metric=args.metric)
         print(f"saving to local file: {args.saved!r}")
         index.dump_to_dir(args.saved)
 

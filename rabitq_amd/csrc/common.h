@@ -153,7 +153,26 @@ struct ListTier {  // one per list
 #define RQ_ROWS_F32_ 0u
 #define RQ_ROWS_F16_ 1u
 #define RQ_ROWS_BF16_ 2u
-// W of one stored element
+// Byte rows (row_type RQ_ROWS_U8 = 4, RQ_ROWS_I8 = 5): the caller's one-byte elements as given, dim bytes per row, padding 0x00,
+// never tiered, never split, no shadow rows.  W(u8) = the integer as f32, W(i8) = the two's-complement integer as f32: both exact,
+// so every distance is the f32 index's of W(rows), bit for bit.
+#define RQ_ROWS_U8_ 4u
+#define RQ_ROWS_I8_ 5u
+__host__ __device__ __forceinline__ bool rq_rows_are_bytes(uint32_t fmt) { return fmt >= RQ_ROWS_U8_; }
+// f32 slots (4 bytes) one stored row of dim elements takes: the stride of BaseView::dev
+__host__ __device__ __forceinline__ uint32_t rq_row_slots(uint32_t fmt, uint32_t dim) {
+    return fmt == RQ_ROWS_F32_ ? dim : rq_rows_are_bytes(fmt) ? dim >> 2 : dim >> 1;
+}
+// W of one stored byte, and its inverse on representable values (anything else: clamped and truncated -- the loaders check with
+// narrow_exact, host_build.h, before they store)
+__host__ __device__ __forceinline__ float rq_widen_byte(uint8_t b, uint32_t fmt) {
+    return fmt == RQ_ROWS_I8_ ? (float)(int32_t)(int8_t)b : (float)(uint32_t)b;
+}
+__host__ __device__ __forceinline__ uint8_t rq_narrow_byte(float v, uint32_t fmt) {
+    if (fmt == RQ_ROWS_I8_) return (uint8_t)(int8_t)(int32_t)(v >= 127.0f ? 127.0f : v >= -128.0f ? v : -128.0f);  // (a NaN: -128)
+    return (uint8_t)(uint32_t)(v >= 255.0f ? 255.0f : v >= 0.0f ? v : 0.0f);                                         // (a NaN: 0)
+}
+// W of one stored 2-byte element
 __host__ __device__ __forceinline__ float rq_widen_elem(uint16_t h, uint32_t fmt) {
     if (fmt == RQ_ROWS_BF16_) return __builtin_bit_cast(float, (uint32_t)h << 16);
 #ifdef __HIP_DEVICE_COMPILE__
@@ -192,15 +211,16 @@ __host__ __device__ __forceinline__ uint16_t rq_narrow_elem(float v, uint32_t fm
 #endif
 }
 struct RowRef {
-    const float *p;  // the row's 4*dim bytes (a half-precision row: its 2*dim bytes)
+    const float *p;  // the row's 4*dim bytes (a half-precision row: its 2*dim bytes; a byte row: its dim bytes)
     bool split;      // stored as two 16-bit planes
-    uint32_t fmt;    // RQ_ROWS_*: 0 = f32 (plain or split), else the 2-byte element type
+    uint32_t fmt;    // RQ_ROWS_*: 0 = f32 (plain or split), else the 2-byte or one-byte element type
 };
 __host__ __device__ __forceinline__ uint32_t rq_split_join(uint32_t h16, uint32_t lo16) {
     return (h16 << 16) + (uint32_t)(int32_t)(int16_t)lo16;
 }
-// element e of a row / its store (cold paths: placement, dumps, shards, rq_rerank); a half-precision row widens / narrows
+// element e of a row / its store (cold paths: placement, dumps, shards, rq_rerank); a half-precision or byte row widens / narrows
 __host__ __device__ __forceinline__ float rq_row_get(const RowRef r, uint32_t dim, uint32_t e) {
+    if (rq_rows_are_bytes(r.fmt)) return rq_widen_byte(reinterpret_cast<const uint8_t *>(r.p)[e], r.fmt);
     if (r.fmt) return rq_widen_elem(reinterpret_cast<const uint16_t *>(r.p)[e], r.fmt);
     if (!r.split) return r.p[e];
     const uint16_t *h = reinterpret_cast<const uint16_t *>(r.p);
@@ -208,6 +228,10 @@ __host__ __device__ __forceinline__ float rq_row_get(const RowRef r, uint32_t di
 }
 __host__ __device__ __forceinline__ void rq_row_put(const RowRef r, uint32_t dim, uint32_t e, float v) {
     float *w = const_cast<float *>(r.p);
+    if (rq_rows_are_bytes(r.fmt)) {
+        reinterpret_cast<uint8_t *>(w)[e] = rq_narrow_byte(v, r.fmt);
+        return;
+    }
     if (r.fmt) {
         reinterpret_cast<uint16_t *>(w)[e] = rq_narrow_elem(v, r.fmt);
         return;
@@ -226,10 +250,10 @@ struct BaseView {
     const ListTier *lt;  // k entries (tiered indexes only)
     uint32_t k;
     uint32_t split;      // the rows (of both tiers) are split rows
-    uint32_t fmt;        // RQ_ROWS_*: half-precision rows (untiered, never split) lie 2*dim bytes apart
+    uint32_t fmt;        // RQ_ROWS_*: half-precision rows (untiered, never split) lie 2*dim bytes apart, byte rows dim bytes
     // row of position p of an untiered index
     __host__ __device__ __forceinline__ RowRef row_at(uint64_t p, uint32_t dim) const {
-        return RowRef{dev + p * (fmt ? dim >> 1 : dim), split != 0, fmt};
+        return RowRef{dev + p * rq_row_slots(fmt, dim), split != 0, fmt};
     }
     // row of position p that belongs to list c
     __host__ __device__ __forceinline__ RowRef row_in_list(uint64_t p, const ListTier &t, uint32_t dim) const {

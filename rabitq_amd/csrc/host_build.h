@@ -260,11 +260,11 @@ static rq_status alloc_base_tiers(rq_index *idx, uint64_t budget_bytes, const ui
         }
     }
     const uint64_t budget_rows = cap == ~0ull ? idx->n : std::min<uint64_t>(idx->n, cap / row);
-    if (idx->row_type) {  // half-precision rows: in HBM at their positions or not at all (no tiers, no split rows, no shadow rows)
+    if (idx->row_type) {  // half-precision and byte rows: in HBM at their positions or not at all (no tiers, no split rows, no shadow rows)
         if (budget_rows < idx->n)
-            return fail(RQ_ERR_UNSUPPORTED, "the half-precision rows of this index (" + std::to_string(want) + " bytes) do not fit the HBM budget: there are no tiers for half rows");
+            return fail(RQ_ERR_UNSUPPORTED, "the typed rows of this index (" + std::to_string(want) + " bytes) do not fit the HBM budget: there are no tiers for half-precision or byte rows");
         idx->n_dev = idx->n, idx->split_rows = false;
-        RQC(idx->base.alloc((idx->n * idx->dim + 1) / 2));  // (n x dim 2-byte elements)
+        RQC(idx->base.alloc((want + 3) / 4));  // (n x dim 2-byte or one-byte elements)
         return RQ_OK;
     }
     if (budget_rows >= idx->n) {  // everything in HBM, rows at their positions
@@ -370,37 +370,50 @@ struct rq_builder {
 };
 #define RQ_BUILD_CHUNK (1ull << 20)
 
-// ---- half-precision rows (include/rabitq_hip.h, "half-precision rows") ----
-// the row types an entry takes, and the one metric that has none
+// ---- typed rows (include/rabitq_hip.h, "half-precision rows" and "byte rows") ----
+static bool row_type_known(uint32_t row_type) { return row_type <= RQ_ROWS_BF16 || row_type == RQ_ROWS_U8 || row_type == RQ_ROWS_I8; }
+// the row types an entry takes, and the metrics that have none
 static rq_status row_type_check(uint32_t row_type, const MetricSpec &metric) {
-    if (row_type > RQ_ROWS_BF16) return fail(RQ_ERR_INVALID, "unknown row_type " + std::to_string(row_type));
+    if (!row_type_known(row_type)) return fail(RQ_ERR_INVALID, "unknown row_type " + std::to_string(row_type));
     if (row_type && metric.id == RQ_METRIC_IP)
-        return fail(RQ_ERR_UNSUPPORTED, "the inner-product metric has no half-precision rows: its extra coordinate sqrt(S - |x|^2) is not representable in the row type");
+        return fail(RQ_ERR_UNSUPPORTED, "the inner-product metric has no typed rows: its extra coordinate sqrt(S - |x|^2) is not representable in the row type");
+    if (rq_rows_are_bytes(row_type) && metric.id == RQ_METRIC_COSINE)
+        return fail(RQ_ERR_UNSUPPORTED, "the cosine metric has no byte rows: a normalised row is not a value of the row type");
     return RQ_OK;
 }
-// the stored tag: the `rows` file of a dumped directory ("f16\n" / "bf16\n"), the "rows" member of a JSON dump
-static const char *row_type_text(uint32_t row_type) { return row_type == RQ_ROWS_BF16 ? "bf16" : "f16"; }
+// the stored tag: the `rows` file of a dumped directory ("f16\n" / "bf16\n" / "u8\n" / "i8\n"), the "rows" member of a JSON dump
+static const char *row_type_text(uint32_t row_type) {
+    return row_type == RQ_ROWS_U8 ? "u8" : row_type == RQ_ROWS_I8 ? "i8" : row_type == RQ_ROWS_BF16 ? "bf16" : "f16";
+}
 static bool row_type_from_text(const std::string &text, uint32_t *row_type) {
     if (text == "f16") *row_type = RQ_ROWS_F16;
     else if (text == "bf16") *row_type = RQ_ROWS_BF16;
+    else if (text == "u8") *row_type = RQ_ROWS_U8;
+    else if (text == "i8") *row_type = RQ_ROWS_I8;
     else return false;
     return true;
 }
-// f32 values a loader found where half-precision rows are announced -> the type's elements; a value the type cannot hold
-// (W(R_t(v)) != v bit for bit; a NaN counts as held) is RQ_ERR_IO
-static rq_status narrow_exact(const float *v, uint64_t count, uint32_t row_type, std::vector<uint16_t> &out, const std::string &where) {
-    out.resize(count);
+// f32 values a loader found where typed rows are announced -> the type's elements (`out`: count elements of the type, as bytes);
+// a value the type cannot hold (W(R_t(v)) != v bit for bit; for the half-precision types a NaN counts as held) is RQ_ERR_IO
+static rq_status narrow_exact(const float *v, uint64_t count, uint32_t row_type, std::vector<uint8_t> &out, const std::string &where) {
+    const bool bytes = rq_rows_are_bytes(row_type);
+    out.resize(count * (bytes ? 1 : 2));
+    uint16_t *o16 = reinterpret_cast<uint16_t *>(out.data());
     for (uint64_t i = 0; i < count; ++i) {
-        out[i] = rq_narrow_elem(v[i], row_type);
-        const float back = rq_widen_elem(out[i], row_type);
-        if (__builtin_bit_cast(uint32_t, back) != __builtin_bit_cast(uint32_t, v[i]) && v[i] == v[i])
+        float back;
+        if (bytes) out[i] = rq_narrow_byte(v[i], row_type), back = rq_widen_byte(out[i], row_type);
+        else o16[i] = rq_narrow_elem(v[i], row_type), back = rq_widen_elem(o16[i], row_type);
+        if (__builtin_bit_cast(uint32_t, back) != __builtin_bit_cast(uint32_t, v[i]) && (bytes || v[i] == v[i]))
             return fail(RQ_ERR_IO, where + ": value " + std::to_string(i) + " is not representable in the row type the index announces");
     }
     return RQ_OK;
 }
-// `count` elements widened on the null stream (widen_rows_kernel)
-static void launch_widen(const uint16_t *d_x, uint32_t row_type, uint64_t count, float *d_out) {
-    if (count) widen_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(count, 256), 1u << 20), 256>>>(d_x, row_type, count, d_out);
+// `count` elements widened on the null stream (widen_rows_kernel / widen_byte_rows_kernel)
+static void launch_widen(const void *d_x, uint32_t row_type, uint64_t count, float *d_out) {
+    if (!count) return;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(ceil_div(count, 256), 1u << 20);
+    if (rq_rows_are_bytes(row_type)) widen_byte_rows_kernel<<<grid, 256>>>(static_cast<const uint8_t *>(d_x), row_type, count, d_out);
+    else widen_rows_kernel<<<grid, 256>>>(static_cast<const uint16_t *>(d_x), row_type, count, d_out);
 }
 // a typed builder takes its chunks through the _rows calls only, a plain one through the plain calls only
 static rq_status builder_chunk_type_check(const rq_builder *b, bool typed) {
@@ -497,7 +510,7 @@ static rq_status builder_assign(rq_builder *b, const void *d_rows_any, uint64_t 
         const uint64_t mm = std::min<uint64_t>(RQ_BUILD_CHUNK, m - c0), at = i0 + c0;
         const float *src, *in = d_rows + c0 * d;
         if (typed) {  // W(chunk) into the staging buffer: everything behind it is the f32 build's
-            launch_widen(static_cast<const uint16_t *>(d_rows_any) + c0 * d, idx->row_type, mm * d, b->wide.p);
+            launch_widen(static_cast<const uint8_t *>(d_rows_any) + c0 * d * idx->row_elem_bytes(), idx->row_type, mm * d, b->wide.p);
             in = b->wide.p;
         }
         RQC(transform_rows(idx->metric, dim, in, mm, d, at, b->xpad.p, nullptr, BaseView{}, b->ip_s_pre, b->ip_bad.p, &src));
@@ -589,7 +602,12 @@ static rq_status builder_place(rq_builder *b, const void *d_rows_any, uint64_t i
     rq_index *idx = b->idx.get();
     if (i0 > idx->n || m > idx->n - i0) return fail(RQ_ERR_INVALID, "chunk outside [0, n)");
     if (!b->cov_place.add(i0, m)) return fail(RQ_ERR_INVALID, "rq_builder_place_chunk: rows [" + std::to_string(i0) + ", " + std::to_string(i0 + m) + ") overlap rows already placed");
-    if (m && typed) {
+    if (m && typed && idx->byte_rows()) {  // one-byte elements go to the row's final position as they are (L2 only)
+        place_byte_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(m, 4), 1u << 20), 256>>>(static_cast<const uint8_t *>(d_rows_any), i0, m, b->d, idx->dim,
+                                                                                              b->pos_of_id.p, reinterpret_cast<uint8_t *>(idx->base.p));
+        HIPC(hipDeviceSynchronize());  // the caller may reuse d_rows right away
+        HIPC(hipGetLastError());
+    } else if (m && typed) {
         // L2: the 2-byte elements go to the row's final position as they are; cosine: the chunk is widened and normalised as in
         // pass 1 (the same kernels, the same bits) and narrowed with R_t where it is stored
         const uint16_t *rows = static_cast<const uint16_t *>(d_rows_any);
@@ -762,7 +780,7 @@ static rq_status from_arrays(uint32_t dim, uint64_t n, uint32_t k, const void *b
     if (k && offsets[k] != n) return fail(RQ_ERR_INVALID, "offsets[k] != n");
     RQC(alloc_base_tiers(idx.get(), 0, offsets));
     if (n) {
-        if (row_type) HIPC(hipMemcpy(idx->base.p, base_any, n * dim * 2, hipMemcpyHostToDevice));
+        if (row_type) HIPC(hipMemcpy(idx->base.p, base_any, n * idx->row_bytes(), hipMemcpyHostToDevice));
         else RQC(copy_base_rows(idx.get(), 0, n, const_cast<float *>(base), /*to_index=*/true));
         HIPC(hipMemcpy(idx->map_ids.p, map_ids, n * 4, hipMemcpyHostToDevice));
         HIPC(hipMemcpy(idx->codes.p, codes, n * idx->W * 8, hipMemcpyHostToDevice));
@@ -1012,7 +1030,16 @@ static rq_status copy_base_rows(const rq_index *idx, uint64_t i0, uint64_t m, fl
                 const uint64_t nr = std::min(piece, rows - r0), cells = nr * dim;
                 typed.resize(cells);
                 float *h = hp + r0 * dim;
-                if (to_index) {
+                if (idx->byte_rows()) {  // (one byte per cell: the lower half of the staging vector)
+                    uint8_t *tb = reinterpret_cast<uint8_t *>(typed.data()), *devb = reinterpret_cast<uint8_t *>(idx->base.p) + (dev_row + r0) * dim;
+                    if (to_index) {
+                        for (uint64_t e = 0; e < cells; ++e) tb[e] = rq_narrow_byte(h[e], idx->row_type);
+                        HIPC(hipMemcpy(devb, tb, cells, hipMemcpyHostToDevice));
+                    } else {
+                        HIPC(hipMemcpy(tb, devb, cells, hipMemcpyDeviceToHost));
+                        for (uint64_t e = 0; e < cells; ++e) h[e] = rq_widen_byte(tb[e], idx->row_type);
+                    }
+                } else if (to_index) {
                     for (uint64_t e = 0; e < cells; ++e) typed[e] = rq_narrow_elem(h[e], idx->row_type);
                     HIPC(hipMemcpy(dev + (dev_row + r0) * dim, typed.data(), cells * 2, hipMemcpyHostToDevice));
                 } else {

@@ -562,12 +562,15 @@ struct Pass {
     // sort_runs_mid_kernel's bitmap words; scan_debug bit 2048 (test hook): none, so long directories take the fall-back orderings
     uint32_t mid_lds_words() const { return (pl.dbg & 2048) ? 0u : RQ_SORT_MID_LDS_WORDS; }
 
+    // the row kind of the index: which of the rerank kernels' twins a launch takes
+    int row_kind() const { return idx->row_type == RQ_ROWS_F32 ? ROW_KIND_F32 : idx->byte_rows() ? ROW_KIND_BYTE : ROW_KIND_HALF; }
+
     // small batch: one fused launch per stage (launch-bound regime)
     void stage_finish_small(StageRun &r) {
         const QSeg &seg = r.seg;
         pf.begin(PF_RERANK);
         const uint32_t fin_threads = nq <= 16 ? 1024u : 256u;  // a handful of queries: more lanes on each one's rerank
-        const bool half_rows = idx->row_type != RQ_ROWS_F32;    // the kernels whose rerank reads 2-byte rows (kernels_rerank.h: accurate_rows<true>)
+        const int kind = row_kind();  // the kernels whose rerank reads the index's rows (kernels_rerank.h: accurate_rows<KIND>)
         // survivor buffers beyond the default mean this index / these queries leave long run directories (overflow
         // re-runs, loose thresholds): those are ordered by the slot-bucketed kernel first; the fused kernel then sorts
         // only what fits its LDS
@@ -582,20 +585,22 @@ struct Pass {
             // a handful of queries: their final-stage survivors (~1000 rows each) are gathered by the whole chip -- one block
             // per query would pull them through a single CU's memory pipeline (~30 GB/s)
             if (nq <= 32) {
-                auto accurate = half_rows ? accurate_half_kernel : accurate_kernel;
+                auto accurate = kind == ROW_KIND_BYTE ? accurate_byte_kernel : kind == ROW_KIND_HALF ? accurate_half_kernel : accurate_kernel;
                 accurate<<<dim3(std::max(1u, std::min(16u, 256u / nq)), nq), 256, (size_t)dim * sizeof(float), st>>>(
                     ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, nullptr, probe_cluster, nprobe);
                 flags |= 2u;
             }
-            auto finish = half_rows ? (topk < 64 ? sb_finish_half_kernel<true> : sb_finish_half_kernel<false>)
-                                    : (topk < 64 ? sb_finish_kernel<true> : sb_finish_kernel<false>);
+            auto finish = kind == ROW_KIND_BYTE   ? (topk < 64 ? sb_finish_byte_kernel<true> : sb_finish_byte_kernel<false>)
+                          : kind == ROW_KIND_HALF ? (topk < 64 ? sb_finish_half_kernel<true> : sb_finish_half_kernel<false>)
+                                                  : (topk < 64 ? sb_finish_kernel<true> : sb_finish_kernel<false>);
             finish<<<nq, fin_threads, (size_t)dim * sizeof(float) + (2 * RQ_SBF_RUNS + RQ_SBF_RECS) * 16, st>>>(
                 ws.surv.p, ws.runs.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, topk, rs, probe_cluster, nprobe, flags,
                 idx->map_ids.p, io.out_dist, io.out_id, io.out_n, ws.rough_cnt.p, ws.totals.p);
             sb_results_done = true;
         } else {
-            auto finish = half_rows ? (qp.heuristic ? stage_finish_half_kernel<true> : stage_finish_half_kernel<false>)
-                                    : (qp.heuristic ? stage_finish_kernel<true> : stage_finish_kernel<false>);
+            auto finish = kind == ROW_KIND_BYTE   ? (qp.heuristic ? stage_finish_byte_kernel<true> : stage_finish_byte_kernel<false>)
+                          : kind == ROW_KIND_HALF ? (qp.heuristic ? stage_finish_half_kernel<true> : stage_finish_half_kernel<false>)
+                                                  : (qp.heuristic ? stage_finish_kernel<true> : stage_finish_kernel<false>);
             finish<<<nq, fin_threads, (size_t)dim * sizeof(float), st>>>(ws.surv.p, ws.runs.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, topk, rs,
                                                                          probe_cluster, nprobe, flags);
         }
@@ -634,7 +639,10 @@ struct Pass {
         else if (idx->split_rows && prefilter)  // tiered: the rows' own first plane is the pre-filter
             accurate_split_kernel<<<dim3(gx, nq), 256, (size_t)dim * sizeof(float) + (nprobe <= RQ_ACC8_LDS_PROBES ? (size_t)nprobe * 16 : 0), st>>>(
                 ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, rerank_order, ws.thr.p, probe_cluster, nprobe, ws.nshadow.p);
-        else if (idx->row_type)  // half-precision rows: every survivor reads its 2*dim-byte row (no shadow rows, no first plane)
+        else if (row_kind() == ROW_KIND_BYTE)  // byte rows: every survivor reads its dim-byte row (no shadow rows, no first plane)
+            accurate_byte_kernel<<<dim3(gx, nq), 256, (size_t)dim * sizeof(float), st>>>(ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim,
+                                                                                         rerank_order, probe_cluster, nprobe);
+        else if (idx->row_type)  // half-precision rows: every survivor reads its 2*dim-byte row
             accurate_half_kernel<<<dim3(gx, nq), 256, (size_t)dim * sizeof(float), st>>>(ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim,
                                                                                          rerank_order, probe_cluster, nprobe);
         else

@@ -276,9 +276,12 @@ struct rq_index {
     std::vector<ListTier> h_list_tier;
     bool split_rows = false;         // the raw vectors are split rows (common.h; set with the tiers, tiered indexes only)
     // RQ_ROWS_*: a half-precision index keeps the caller's 2-byte elements in `base` (n x dim of them, 2*dim bytes per row, padding
-    // +0): always untiered, never split, no shadow rows, never mutated
+    // +0), a byte-row index (RQ_ROWS_U8 / RQ_ROWS_I8) the caller's one-byte elements (dim bytes per row, padding 0x00): always
+    // untiered, never split, no shadow rows, never mutated
     uint32_t row_type = RQ_ROWS_F32;
-    size_t row_bytes() const { return (size_t)dim * (row_type ? 2 : 4); }
+    bool byte_rows() const { return rq_rows_are_bytes(row_type); }
+    size_t row_elem_bytes() const { return row_type == RQ_ROWS_F32 ? 4 : byte_rows() ? 1 : 2; }
+    size_t row_bytes() const { return (size_t)dim * row_elem_bytes(); }
     BaseView view() const { return BaseView{base.p, base_host_dev, list_tier.p, k, split_rows ? 1u : 0u, row_type}; }
     ~rq_index() {
         if (base_host) (void)hipHostFree(base_host);
@@ -417,7 +420,14 @@ __global__ __launch_bounds__(256) void shard_gather_kernel(const uint32_t *__res
         }
         const uint64_t src = (uint64_t)old_off[lo] + (p - new_off[lo]);
         const RowRef srow = base_in.row(src, dim), drow = base_out.row(p, dim);
-        for (uint32_t e = lane; e < dim; e += 64) rq_row_put(drow, dim, e, rq_row_get(srow, dim, e));
+        if (rq_rows_are_bytes(base_in.fmt) || rq_rows_are_bytes(base_out.fmt)) {  // (a shard inherits the row type: bytes are copied as they are)
+            const uint8_t *s = reinterpret_cast<const uint8_t *>(srow.p);
+            uint8_t *d = reinterpret_cast<uint8_t *>(const_cast<float *>(drow.p));
+            for (uint32_t e = lane; e < dim; e += 64) d[e] = s[e];
+        } else {  // (fmt & 3: no byte type here -- said so that the loop is compiled without the byte forms of get / put, as it was)
+            const RowRef s{srow.p, srow.split, srow.fmt & 3u}, d{drow.p, drow.split, drow.fmt & 3u};
+            for (uint32_t e = lane; e < dim; e += 64) rq_row_put(d, dim, e, rq_row_get(s, dim, e));
+        }
         for (uint32_t w = lane; w < W; w += 64) codes_out[p * W + w] = codes_in[src * W + w];
         if (lane == 0) {
             factors_out[p] = factors_in[src];
@@ -901,6 +911,8 @@ static rq_status ensure_kernel_attributes() {
         set(reinterpret_cast<const void *>(sb_finish_kernel<false>), 104 * 1024, "sb_finish_kernel");  // (+ 49 KiB of static LDS)
         set(reinterpret_cast<const void *>(sb_finish_half_kernel<true>), 104 * 1024, "sb_finish_half_kernel");
         set(reinterpret_cast<const void *>(sb_finish_half_kernel<false>), 104 * 1024, "sb_finish_half_kernel");
+        set(reinterpret_cast<const void *>(sb_finish_byte_kernel<true>), 104 * 1024, "sb_finish_byte_kernel");
+        set(reinterpret_cast<const void *>(sb_finish_byte_kernel<false>), 104 * 1024, "sb_finish_byte_kernel");
 #define RQ_SBQ_ATTR(WW)                                                                                  \
     set(reinterpret_cast<const void *>(sb_query_kernel<WW, 0, false>), 120 * 1024, "sb_query_kernel");   \
     set(reinterpret_cast<const void *>(sb_query_kernel<WW, 1, false>), 120 * 1024, "sb_query_kernel");   \

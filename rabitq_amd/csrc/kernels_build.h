@@ -482,6 +482,21 @@ __global__ __launch_bounds__(256) void place_narrow_rows_kernel(const float *__r
         for (uint32_t e = lane; e < dim; e += 64) w[e] = rq_narrow_elem(src[e], fmt);
     }
 }
+// Byte rows (common.h: RQ_ROWS_U8 / RQ_ROWS_I8): the byte forms of widen_rows_kernel and place_half_rows_kernel, element-wise as
+// well (the input is only 1-byte aligned); L2 only, so there is no rounding and no narrowing placement.
+__global__ __launch_bounds__(256) void widen_byte_rows_kernel(const uint8_t *__restrict__ x, uint32_t fmt, uint64_t count, float *__restrict__ out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (uint64_t)gridDim.x * 256) out[i] = rq_widen_byte(x[i], fmt);
+}
+// m x d one-byte elements copied as they are, padding 0x00; one wave per row
+__global__ __launch_bounds__(256) void place_byte_rows_kernel(const uint8_t *__restrict__ rows, uint64_t i0, uint64_t m, uint32_t d, uint32_t dim,
+                                                              const uint32_t *__restrict__ pos_of_id, uint8_t *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < m; r += (uint64_t)gridDim.x * 4) {
+        uint8_t *w = out + (uint64_t)pos_of_id[i0 + r] * dim;
+        const uint8_t *src = rows + r * d;
+        for (uint32_t e = lane; e < dim; e += 64) w[e] = e < d ? src[e] : (uint8_t)0;
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 // Cosine metric (RQ_METRIC_COSINE): N(x) of the zero-padded row, the one new piece of arithmetic.

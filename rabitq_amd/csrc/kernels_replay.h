@@ -431,7 +431,7 @@ __device__ __forceinline__ StageCounts stage_begin(unsigned long long *__restric
 // One block per query finishes a stage: (A) exact rerank distances of the stage's survivors
 // (src/rerank.rs:85-90, 8 lanes = the 8 AVX lanes of src/simd.rs:14-73), (B) sort of the run
 // directory into the reference's visiting order, (C) wave 0 replays the ranker.
-template <bool HEURISTIC, bool HALF>
+template <bool HEURISTIC, int KIND>
 __device__ __forceinline__ void stage_finish_body(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
                                                            unsigned long long *__restrict__ surv_cnt, const QSeg &seg,
                                                            const BaseView &base,
@@ -451,7 +451,7 @@ __device__ __forceinline__ void stage_finish_body(SurvRec *__restrict__ surv, Ru
         for (uint32_t c = threadIdx.x * 4; c < dim; c += blockDim.x * 4)
             *reinterpret_cast<float4 *>(fin_q + c) = *reinterpret_cast<const float4 *>(qpad + (uint64_t)b * dim + c);
         __syncthreads();
-        accurate_rows<HALF>(recs, n, base, fin_q, dim, threadIdx.x >> 1, blockDim.x >> 1, probe_cluster + (uint64_t)b * nprobe);  // 256 or 1024 threads per query
+        accurate_rows<KIND>(recs, n, base, fin_q, dim, threadIdx.x >> 1, blockDim.x >> 1, probe_cluster + (uint64_t)b * nprobe);  // 256 or 1024 threads per query
     }
     // (B): up to RQ_SORT_LDS_RECS descriptors in LDS; longer directories were already ordered by sort_runs_mid_kernel
     // when the host launched it ahead of this kernel (presorted != 0), else (rare) bitonic in global memory
@@ -467,9 +467,9 @@ __global__ __launch_bounds__(1024) void stage_finish_kernel(SurvRec *__restrict_
                                                            const float *__restrict__ qpad, uint32_t dim, uint32_t topk,
                                                            ReplayState st, const uint32_t *__restrict__ probe_cluster,
                                                            uint32_t nprobe, uint32_t presorted) {
-    stage_finish_body<HEURISTIC, false>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted);
+    stage_finish_body<HEURISTIC, ROW_KIND_F32>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted);
 }
-// stage_finish_kernel of a half-precision index: phase (A) reads 2-byte rows (accurate_rows<true>)
+// stage_finish_kernel of a half-precision index: phase (A) reads 2-byte rows (accurate_rows<ROW_KIND_HALF>)
 template <bool HEURISTIC>
 __global__ __launch_bounds__(1024) void stage_finish_half_kernel(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
                                                                 unsigned long long *__restrict__ surv_cnt, const QSeg seg,
@@ -477,7 +477,17 @@ __global__ __launch_bounds__(1024) void stage_finish_half_kernel(SurvRec *__rest
                                                                 const float *__restrict__ qpad, uint32_t dim, uint32_t topk,
                                                                 ReplayState st, const uint32_t *__restrict__ probe_cluster,
                                                                 uint32_t nprobe, uint32_t presorted) {
-    stage_finish_body<HEURISTIC, true>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted);
+    stage_finish_body<HEURISTIC, ROW_KIND_HALF>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted);
+}
+// stage_finish_kernel of a byte-row index: phase (A) reads one-byte rows (accurate_rows<ROW_KIND_BYTE>)
+template <bool HEURISTIC>
+__global__ __launch_bounds__(1024) void stage_finish_byte_kernel(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
+                                                                unsigned long long *__restrict__ surv_cnt, const QSeg seg,
+                                                                const BaseView base,
+                                                                const float *__restrict__ qpad, uint32_t dim, uint32_t topk,
+                                                                ReplayState st, const uint32_t *__restrict__ probe_cluster,
+                                                                uint32_t nprobe, uint32_t presorted) {
+    stage_finish_body<HEURISTIC, ROW_KIND_BYTE>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted);
 }
 
 // `runs_src`: where the stage's unsorted descriptors are when not in `runs` itself (an arena stage scatters them into the

@@ -128,6 +128,78 @@ __device__ __forceinline__ float exact_l2_pair_half(const uint16_t *__restrict__
     }
     return exact_l2_fold(a0, a1, a2, a3);
 }
+// a BYTE row (common.h: one-byte elements as the caller gave them): lane half hf's elements 8u + 4hf + 0..3 of a chunk are ONE
+// dword, widened exactly in registers (u8: the four byte-to-f32 conversions; i8: a sign-extending extract and the integer
+// conversion), and the arithmetic is exact_l2_pair's -- exact_l2_acc64 per 64 dimensions in chunk order, every fused chain inside
+// its lane, then exact_l2_fold.  A round takes 256 dimensions (the 128 bytes per lane in flight of exact_l2_pair's round), then
+// one tail of 128 and one of 64 dimensions as dim requires.  How the dwords reach the lane is RQ_BYTE_PAIR_LOADS:
+//   false  a dword load per chunk (32 per round), nothing crosses lanes before the fold;
+//   true   an 8-byte load per TWO chunks (16 per round): lane hf fetches chunk 2j + hf whole and the pair swaps the halves it
+//          fetched for each other (one exchange of raw bytes per two chunks; the accumulators still never leave their lane).
+// Measured on 100M x 128 / 40M x 768 u8 rows, 65 536 queries: 6.17 / 17.79 ms of rerank with dword loads, 3.05 / 6.61 ms with pair
+// loads -- a wave's dword load touches 32 rows for 8 bytes each, and the gather is bound by those requests.
+constexpr bool RQ_BYTE_PAIR_LOADS = true;
+template <bool SIGNED>
+__device__ __forceinline__ void byte_widen64(const uint32_t *bv, float4 (&xv)[8]) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const uint32_t w = bv[u];
+        if constexpr (SIGNED) {
+            const int32_t s = (int32_t)w;
+            xv[u].x = (float)((s << 24) >> 24), xv[u].y = (float)((s << 16) >> 24);
+            xv[u].z = (float)((s << 8) >> 24), xv[u].w = (float)(s >> 24);
+        } else {
+            xv[u].x = (float)(w & 0xFFu), xv[u].y = (float)((w >> 8) & 0xFFu);
+            xv[u].z = (float)((w >> 16) & 0xFFu), xv[u].w = (float)(w >> 24);
+        }
+    }
+}
+// CHUNKS x 64 dimensions of the row from byte `row` on (no lane offset in it): every load first, then widen and accumulate chunk
+// by chunk; q = the query from the same dimension on, + 4*hf
+template <bool SIGNED, int CHUNKS>
+__device__ __forceinline__ void exact_l2_byte_round(const uint8_t *__restrict__ row, uint32_t hf, const float *q, float &a0, float &a1, float &a2,
+                                                    float &a3) {
+    uint32_t bv[8 * CHUNKS];  // bv[u] = elements 8u + 4hf + 0..3
+    if constexpr (RQ_BYTE_PAIR_LOADS) {
+        uint2 v[4 * CHUNKS];  // v[j] = chunk 2j + hf: .x its elements 0..3, .y its elements 4..7
+#pragma unroll
+        for (int j = 0; j < 4 * CHUNKS; ++j) v[j] = *reinterpret_cast<const uint2 *>(row + 16 * j + 8 * hf);
+#pragma unroll
+        for (int j = 0; j < 4 * CHUNKS; ++j) {
+            // lane 0 needs elements 0..3 of both chunks (its own .x and lane 1's), lane 1 elements 4..7 (lane 0's .y and its own)
+            const uint32_t recv = (uint32_t)__shfl_xor((int)(hf ? v[j].x : v[j].y), 1, 2);
+            bv[2 * j] = hf ? recv : v[j].x;
+            bv[2 * j + 1] = hf ? v[j].y : recv;
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < 8 * CHUNKS; ++u) bv[u] = *reinterpret_cast<const uint32_t *>(row + 8 * u + 4 * hf);
+    }
+#pragma unroll
+    for (int h = 0; h < CHUNKS; ++h) {
+        float4 xv[8];
+        byte_widen64<SIGNED>(bv + 8 * h, xv);
+        exact_l2_acc64(xv, q + 64 * h, a0, a1, a2, a3);
+    }
+}
+// ROUND: the chunks of the full round (4: 256 dimensions; 1: the 64-dimension form for kernels short of registers)
+template <bool SIGNED, int ROUND = 4>
+__device__ __forceinline__ float exact_l2_pair_byte(const uint8_t *__restrict__ row, const float *q_lds, uint32_t dim, uint32_t hf) {
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+    const float *q = q_lds + 4 * hf;
+    uint32_t c = 0;
+    for (; c + 64 * ROUND <= dim; c += 64 * ROUND) exact_l2_byte_round<SIGNED, ROUND>(row + c, hf, q + c, a0, a1, a2, a3);
+    if constexpr (ROUND >= 4) {
+        if (c + 128 <= dim) {
+            exact_l2_byte_round<SIGNED, 2>(row + c, hf, q + c, a0, a1, a2, a3);
+            c += 128;
+        }
+    }
+    if constexpr (ROUND >= 2) {
+        if (c < dim) exact_l2_byte_round<SIGNED, 1>(row + c, hf, q + c, a0, a1, a2, a3);  // dim is a multiple of 64
+    }
+    return exact_l2_fold(a0, a1, a2, a3);
+}
 // an f32 row, plain or split
 __device__ __forceinline__ float exact_l2_row_f32(const RowRef rr, const float *q_lds, uint32_t dim, uint32_t hf) {
     // (a pair of lanes shares its survivor: the branch does not split the pair)
@@ -138,31 +210,42 @@ __device__ __forceinline__ float exact_l2_row_half(const RowRef rr, const float 
     const uint16_t *x = reinterpret_cast<const uint16_t *>(rr.p) + 4 * hf;
     return rr.fmt == RQ_ROWS_BF16_ ? exact_l2_pair_half<true>(x, q_lds, dim, hf) : exact_l2_pair_half<false>(x, q_lds, dim, hf);
 }
-// a row of any format: the dispatch on RowRef's run-time fields
+// a byte row of either type
+template <int ROUND = 4>
+__device__ __forceinline__ float exact_l2_row_byte(const RowRef rr, const float *q_lds, uint32_t dim, uint32_t hf) {
+    const uint8_t *x = reinterpret_cast<const uint8_t *>(rr.p);
+    return rr.fmt == RQ_ROWS_I8_ ? exact_l2_pair_byte<true, ROUND>(x, q_lds, dim, hf) : exact_l2_pair_byte<false, ROUND>(x, q_lds, dim, hf);
+}
+// a row of any format: the dispatch on RowRef's run-time fields (BYTE_ROUND: exact_l2_pair_byte's ROUND)
+template <int BYTE_ROUND = 4>
 __device__ __forceinline__ float exact_l2_row(const RowRef rr, const float *q_lds, uint32_t dim, uint32_t hf) {
+    if (rq_rows_are_bytes(rr.fmt)) return exact_l2_row_byte<BYTE_ROUND>(rr, q_lds, dim, hf);
     return rr.fmt ? exact_l2_row_half(rr, q_lds, dim, hf) : exact_l2_row_f32(rr, q_lds, dim, hf);
 }
 
 // The row of a survivor: at its position in an untiered plain index (nothing else is read); else the survivor's slot names its
-// list, the list's tier record places the row (HBM or host link).  (Half-precision rows: half_rows_exact below.)
+// list, the list's tier record places the row (HBM or host link).  (Half-precision and byte rows: BaseView::row_at.)
 __device__ __forceinline__ RowRef rerank_row(const BaseView &base, const SurvRec &r, const uint32_t *__restrict__ probe_row /* the query's probed lists, by slot */,
                                              uint32_t dim) {
     if (base.host == nullptr && !base.split) return RowRef{base.dev + (uint64_t)r.pos * dim, false, 0u};
     return base.row_of_slot(r.pos, probe_row, r.slot, dim);
 }
 
-// Exact f32 L2 of survivors recs[first], recs[first + step], ... against the query held in LDS.  HALF: the kernels a half-precision
-// index is given (every row at its position, 2*dim bytes apart: nothing but the row is read).  The launch picks the instantiation
-// from the index's row type, so the f32 kernels' loop -- whose two rounds of loads the compiler issues together -- is compiled
-// exactly as it was without the other format in it; which of the two half types a row holds stays a run-time field.
-template <bool HALF = false>
+// Exact f32 L2 of survivors recs[first], recs[first + step], ... against the query held in LDS.  KIND: the row kind of the kernels
+// an index is given -- ROW_KIND_HALF / ROW_KIND_BYTE: every row at its position, 2*dim / dim bytes apart, nothing but the row is
+// read.  The launch picks the instantiation from the index's row type, so the f32 kernels' loop -- whose two rounds of loads the
+// compiler issues together -- is compiled exactly as it was without the other formats in it; which of the two types of its kind a
+// row holds stays a run-time field.
+enum { ROW_KIND_F32 = 0, ROW_KIND_HALF = 1, ROW_KIND_BYTE = 2 };
+template <int KIND = ROW_KIND_F32>
 __device__ __forceinline__ void accurate_rows(SurvRec *__restrict__ recs, uint32_t n, const BaseView &base,
                                               const float *q_lds, uint32_t dim, uint32_t first, uint32_t step,
                                               const uint32_t *__restrict__ probe_row) {
     const uint32_t hf = threadIdx.x & 1;
     for (uint32_t i = first; i < n; i += step) {
         float r;
-        if constexpr (HALF) r = exact_l2_row_half(base.row_at(recs[i].pos, dim), q_lds, dim, hf);
+        if constexpr (KIND == ROW_KIND_BYTE) r = exact_l2_row_byte(RowRef{base.dev + (uint64_t)recs[i].pos * (dim >> 2), false, base.fmt}, q_lds, dim, hf);
+        else if constexpr (KIND == ROW_KIND_HALF) r = exact_l2_row_half(base.row_at(recs[i].pos, dim), q_lds, dim, hf);
         else r = exact_l2_row_f32(rerank_row(base, recs[i], probe_row, dim), q_lds, dim, hf);
         if (hf == 0) recs[i].accurate = r;
     }
@@ -752,7 +835,7 @@ __global__ __launch_bounds__(256, q8_ring_waves(NPC)) void accurate_ring8_kernel
 // ---- the same three phases as separate launches: better for large batches, where all queries'
 // survivors are reranked with full-chip parallelism before the (latency-bound) replay --------------
 // grid (gx, nq); block 256
-template <bool HALF>
+template <int KIND>
 __device__ __forceinline__ void accurate_body(SurvRec *__restrict__ surv, const unsigned long long *__restrict__ surv_cnt, const QSeg &seg,
                                               const BaseView &base, const float *__restrict__ qpad, uint32_t dim,
                                               const uint32_t *__restrict__ order, const uint32_t *__restrict__ probe_cluster, uint32_t nprobe) {
@@ -766,7 +849,7 @@ __device__ __forceinline__ void accurate_body(SurvRec *__restrict__ surv, const 
     for (uint32_t c = threadIdx.x * 4; c < dim; c += 1024)
         *reinterpret_cast<float4 *>(acc_q + c) = *reinterpret_cast<const float4 *>(qpad + (uint64_t)b * dim + c);
     __syncthreads();
-    accurate_rows<HALF>(surv + seg.at(b), n, base, acc_q, dim, blockIdx.x * 128 + (threadIdx.x >> 1), gridDim.x * 128,
+    accurate_rows<KIND>(surv + seg.at(b), n, base, acc_q, dim, blockIdx.x * 128 + (threadIdx.x >> 1), gridDim.x * 128,
                         probe_cluster + (uint64_t)b * nprobe);
 }
 __global__ __launch_bounds__(256) void accurate_kernel(SurvRec *__restrict__ surv,
@@ -775,7 +858,7 @@ __global__ __launch_bounds__(256) void accurate_kernel(SurvRec *__restrict__ sur
                                                        const float *__restrict__ qpad, uint32_t dim,
                                                        const uint32_t *__restrict__ order,
                                                        const uint32_t *__restrict__ probe_cluster, uint32_t nprobe) {
-    accurate_body<false>(surv, surv_cnt, seg, base, qpad, dim, order, probe_cluster, nprobe);
+    accurate_body<ROW_KIND_F32>(surv, surv_cnt, seg, base, qpad, dim, order, probe_cluster, nprobe);
 }
 // accurate_kernel of a half-precision index (host_query.h launches it wherever that index would get accurate_kernel)
 __global__ __launch_bounds__(256) void accurate_half_kernel(SurvRec *__restrict__ surv,
@@ -784,6 +867,15 @@ __global__ __launch_bounds__(256) void accurate_half_kernel(SurvRec *__restrict_
                                                             const float *__restrict__ qpad, uint32_t dim,
                                                             const uint32_t *__restrict__ order,
                                                             const uint32_t *__restrict__ probe_cluster, uint32_t nprobe) {
-    accurate_body<true>(surv, surv_cnt, seg, base, qpad, dim, order, probe_cluster, nprobe);
+    accurate_body<ROW_KIND_HALF>(surv, surv_cnt, seg, base, qpad, dim, order, probe_cluster, nprobe);
+}
+// accurate_kernel of a byte-row index
+__global__ __launch_bounds__(256) void accurate_byte_kernel(SurvRec *__restrict__ surv,
+                                                            const unsigned long long *__restrict__ surv_cnt,
+                                                            const QSeg seg, const BaseView base,
+                                                            const float *__restrict__ qpad, uint32_t dim,
+                                                            const uint32_t *__restrict__ order,
+                                                            const uint32_t *__restrict__ probe_cluster, uint32_t nprobe) {
+    accurate_body<ROW_KIND_BYTE>(surv, surv_cnt, seg, base, qpad, dim, order, probe_cluster, nprobe);
 }
 

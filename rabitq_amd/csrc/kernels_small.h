@@ -188,7 +188,8 @@ __device__ __forceinline__ void sb_accurate_rows(SurvRec *recs, uint32_t n, cons
         const RowRef rr = base.fmt ? base.row_at(recs[i].pos, dim) : rerank_row(base, recs[i], probe_row, dim);
         float r;
         if (W > 2 || rr.split || rr.fmt) {
-            r = exact_l2_row(rr, q_lds, dim, hf);
+            // (byte rows in 64-dimension rounds: with the 256-dimension round beside the other formats this kernel spilled registers)
+            r = exact_l2_row<1>(rr, q_lds, dim, hf);
         } else if constexpr (W <= 2) {
             const float *x = rr.p + 4 * hf;
             float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
@@ -507,7 +508,7 @@ __global__ __launch_bounds__(1024) void sb_query_kernel(const SbArgs a) {
 // (stage_finish_kernel<false>), then the results and the query's share of the totals (finalize_heap_kernel +
 // metrics_sum_kernel).  Heap ranker only.
 // ------------------------------------------------------------------------------------------------
-template <bool REGHEAP, bool HALF>
+template <bool REGHEAP, int KIND>
 __device__ __forceinline__ void sb_finish_body(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
                                                          unsigned long long *__restrict__ surv_cnt, const QSeg &seg,
                                                          const BaseView &base, const float *__restrict__ qpad, uint32_t dim,
@@ -529,7 +530,7 @@ __device__ __forceinline__ void sb_finish_body(SurvRec *__restrict__ surv, RunRe
             *reinterpret_cast<float4 *>(fin_q + c) = *reinterpret_cast<const float4 *>(qpad + (uint64_t)b * dim + c);
         __syncthreads();
         if (!(presorted & 2u))  // bit 1: the exact distances were computed by a whole-chip launch already
-            accurate_rows<HALF>(recs, n, base, fin_q, dim, threadIdx.x >> 1, blockDim.x >> 1, probe_cluster + (uint64_t)b * nprobe);
+            accurate_rows<KIND>(recs, n, base, fin_q, dim, threadIdx.x >> 1, blockDim.x >> 1, probe_cluster + (uint64_t)b * nprobe);
         if (nruns <= RQ_SBF_RUNS && n <= RQ_SBF_RECS && nprobe <= 64) {
             // (Not sort_runs_by_slot: its per-wave key staging, keys[4][1024], assumes a 256-thread block and would add 16 KiB of
             // static LDS to the ~100 KiB of dynamic LDS this kernel runs with; the ordering below shares the stretch scan only.)
@@ -599,10 +600,10 @@ __global__ __launch_bounds__(1024) void sb_finish_kernel(SurvRec *__restrict__ s
                                                          float *__restrict__ out_dist, uint32_t *__restrict__ out_id,
                                                          uint32_t *__restrict__ out_n, const unsigned long long *__restrict__ rough_cnt,
                                                          unsigned long long *__restrict__ totals) {
-    sb_finish_body<REGHEAP, false>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted, map_ids, out_dist,
+    sb_finish_body<REGHEAP, ROW_KIND_F32>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted, map_ids, out_dist,
                                    out_id, out_n, rough_cnt, totals);
 }
-// sb_finish_kernel of a half-precision index: its rerank reads 2-byte rows (accurate_rows<true>)
+// sb_finish_kernel of a half-precision index: its rerank reads 2-byte rows (accurate_rows<ROW_KIND_HALF>)
 template <bool REGHEAP>
 __global__ __launch_bounds__(1024) void sb_finish_half_kernel(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
                                                               unsigned long long *__restrict__ surv_cnt, const QSeg seg,
@@ -612,6 +613,19 @@ __global__ __launch_bounds__(1024) void sb_finish_half_kernel(SurvRec *__restric
                                                               float *__restrict__ out_dist, uint32_t *__restrict__ out_id,
                                                               uint32_t *__restrict__ out_n, const unsigned long long *__restrict__ rough_cnt,
                                                               unsigned long long *__restrict__ totals) {
-    sb_finish_body<REGHEAP, true>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted, map_ids, out_dist,
+    sb_finish_body<REGHEAP, ROW_KIND_HALF>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted, map_ids, out_dist,
                                   out_id, out_n, rough_cnt, totals);
+}
+// sb_finish_kernel of a byte-row index: its rerank reads one-byte rows (accurate_rows<ROW_KIND_BYTE>)
+template <bool REGHEAP>
+__global__ __launch_bounds__(1024) void sb_finish_byte_kernel(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
+                                                              unsigned long long *__restrict__ surv_cnt, const QSeg seg,
+                                                              const BaseView base, const float *__restrict__ qpad, uint32_t dim,
+                                                              uint32_t topk, ReplayState st, const uint32_t *__restrict__ probe_cluster,
+                                                              uint32_t nprobe, uint32_t presorted, const uint32_t *__restrict__ map_ids,
+                                                              float *__restrict__ out_dist, uint32_t *__restrict__ out_id,
+                                                              uint32_t *__restrict__ out_n, const unsigned long long *__restrict__ rough_cnt,
+                                                              unsigned long long *__restrict__ totals) {
+    sb_finish_body<REGHEAP, ROW_KIND_BYTE>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted, map_ids, out_dist,
+                                           out_id, out_n, rough_cnt, totals);
 }

@@ -246,9 +246,9 @@ rq_status rq_build_rows(const void *base, uint64_t n, uint32_t d, const float *c
     if (row_type == RQ_ROWS_F32) return build_host(static_cast<const float *>(base), n, d, centroids, k, d, orthogonal, seed, MetricSpec{metric}, out);
     RQC(ensure_device());
     if ((n && !base) || !centroids) return fail(RQ_ERR_INVALID, "null argument");
-    DevBuf<uint16_t> db;  // the typed rows are staged as they are: no f32 image of the input is made
+    DevBuf<uint8_t> db;  // the typed rows are staged as they are: no f32 image of the input is made
     DevBuf<float> dc;
-    RQC(db.upload(static_cast<const uint16_t *>(base), n * d));
+    RQC(db.upload(static_cast<const uint8_t *>(base), n * d * (rq_rows_are_bytes(row_type) ? 1 : 2)));
     RQC(dc.upload(centroids, (size_t)k * d));
     return build_device(db.p, n, d, dc.p, k, d, orthogonal, seed, MetricSpec{metric}, out, row_type);
 }
@@ -276,20 +276,20 @@ rq_status rq_row_type(const rq_index *idx, uint32_t *out) {
 }
 rq_status rq_widen_device(const void *d_x, uint32_t row_type, uint64_t count, float *d_out) {
     RQC(ensure_device());
-    if (row_type != RQ_ROWS_F16 && row_type != RQ_ROWS_BF16) return fail(RQ_ERR_INVALID, "row_type must be RQ_ROWS_F16 or RQ_ROWS_BF16");
+    if (row_type == RQ_ROWS_F32 || !row_type_known(row_type)) return fail(RQ_ERR_INVALID, "row_type must be RQ_ROWS_F16, RQ_ROWS_BF16, RQ_ROWS_U8 or RQ_ROWS_I8");
     if (count && (!d_x || !d_out)) return fail(RQ_ERR_INVALID, "null argument");
-    launch_widen(static_cast<const uint16_t *>(d_x), row_type, count, d_out);
+    launch_widen(d_x, row_type, count, d_out);
     HIPC(hipDeviceSynchronize());
     HIPC(hipGetLastError());
     return RQ_OK;
 }
 rq_status rq_widen(const void *x, uint32_t row_type, uint64_t count, float *out) {
     RQC(ensure_device());
-    if (row_type != RQ_ROWS_F16 && row_type != RQ_ROWS_BF16) return fail(RQ_ERR_INVALID, "row_type must be RQ_ROWS_F16 or RQ_ROWS_BF16");
+    if (row_type == RQ_ROWS_F32 || !row_type_known(row_type)) return fail(RQ_ERR_INVALID, "row_type must be RQ_ROWS_F16, RQ_ROWS_BF16, RQ_ROWS_U8 or RQ_ROWS_I8");
     if (count && (!x || !out)) return fail(RQ_ERR_INVALID, "null argument");
-    DevBuf<uint16_t> dx;
+    DevBuf<uint8_t> dx;
     DevBuf<float> dout;
-    RQC(dx.upload(static_cast<const uint16_t *>(x), count));
+    RQC(dx.upload(static_cast<const uint8_t *>(x), count * (rq_rows_are_bytes(row_type) ? 1 : 2)));
     RQC(dout.alloc(count));
     RQC(rq_widen_device(dx.p, row_type, count, dout.p));
     if (count) HIPC(hipMemcpy(out, dout.p, count * 4, hipMemcpyDeviceToHost));
@@ -369,7 +369,7 @@ rq_status rq_load_dir(const char *dir, rq_index **out) {
         fclose(mf);
         if (!metric_from_file_text(std::string(buf, got), &metric)) return fail(RQ_ERR_IO, "metric: unknown or malformed content in " + d + "/metric");
     }
-    uint32_t row_type = RQ_ROWS_F32;  // the `rows` file of a half-precision index's dump
+    uint32_t row_type = RQ_ROWS_F32;  // the `rows` file of a half-precision or byte-row index's dump
     if (FILE *rf = fopen((d + "/rows").c_str(), "rb")) {
         char buf[16] = {0};
         const size_t got = fread(buf, 1, sizeof buf - 1, rf);
@@ -409,8 +409,9 @@ rq_status rq_load_dir(const char *dir, rq_index **out) {
     if (oip[k] != n) return fail(RQ_ERR_IO, "offsets[k] != number of vectors");
     for (uint32_t j = 0; j < k; ++j)
         if (oip[j] > oip[j + 1]) return fail(RQ_ERR_IO, "offsets are not non-decreasing");
-    if (row_type && metric.id == RQ_METRIC_IP) return fail(RQ_ERR_IO, "rows: an inner-product index has no half-precision rows (" + d + ")");
-    std::vector<uint16_t> typed;  // half-precision rows: every value of base.fvecs must be one of the type's
+    if (row_type && (metric.id == RQ_METRIC_IP || (rq_rows_are_bytes(row_type) && metric.id != RQ_METRIC_L2)))
+        return fail(RQ_ERR_IO, "rows: an index of this metric has no rows of the announced type (" + d + ")");
+    std::vector<uint8_t> typed;  // typed rows: every value of base.fvecs must be one of the type's
     const void *base_arg = base.data.data();
     if (row_type) {
         RQC(narrow_exact(reinterpret_cast<const float *>(base.data.data()), n * dim, row_type, typed, d + "/base.fvecs"));
@@ -649,9 +650,10 @@ rq_status rq_load_json(const char *path, rq_index **out) {
     std::vector<uint64_t> codes64(codes.begin(), codes.end());
     uint32_t row_type = RQ_ROWS_F32;
     if (!rows_name.empty() && !(rows_name.size() > 2 && rows_name.front() == '"' && rows_name.back() == '"' &&
-                                row_type_from_text(rows_name.substr(1, rows_name.size() - 2), &row_type) && metric.id != RQ_METRIC_IP))
+                                row_type_from_text(rows_name.substr(1, rows_name.size() - 2), &row_type) && metric.id != RQ_METRIC_IP &&
+                                !(rq_rows_are_bytes(row_type) && metric.id != RQ_METRIC_L2)))
         return fail(RQ_ERR_IO, std::string("unknown \"rows\" member ") + rows_name + " in " + path);
-    std::vector<uint16_t> typed;
+    std::vector<uint8_t> typed;
     const void *base_arg = base_rows.data();
     if (row_type) {
         RQC(narrow_exact(base_rows.data(), n * dim, row_type, typed, path));
@@ -680,7 +682,7 @@ rq_status rq_get_device_ptr(const rq_index *idx, int which, const void **out_ptr
             if (idx->split_rows)  // (common.h) not an array of f32 rows
                 return fail(RQ_ERR_UNSUPPORTED, "the raw vectors of this index are stored as split rows (two 16-bit planes per row): no f32 device array; use rq_get_array");
             if (idx->row_type)
-                return fail(RQ_ERR_UNSUPPORTED, "the raw vectors of this index are half-precision rows: no f32 device array; use rq_get_array, or RQ_ARR_BASE_ROWS for the stored rows");
+                return fail(RQ_ERR_UNSUPPORTED, "the raw vectors of this index are half-precision or byte rows: no f32 device array; use rq_get_array, or RQ_ARR_BASE_ROWS for the stored rows");
             *out_ptr = idx->base.p, *out_bytes = idx->n_dev * idx->dim * 4;
             break;
         case RQ_ARR_ORTHOGONAL: *out_ptr = idx->P.p, *out_bytes = (uint64_t)idx->dim * idx->dim * 4; break;
@@ -691,7 +693,7 @@ rq_status rq_get_device_ptr(const rq_index *idx, int which, const void **out_ptr
         case RQ_ARR_FACTORS: *out_ptr = idx->factors.p, *out_bytes = idx->n * 16; break;
         case RQ_ARR_BASE_ROWS:
             if (!idx->row_type) return fail(RQ_ERR_INVALID, "RQ_ARR_BASE_ROWS: this index stores f32 rows (RQ_ARR_BASE)");
-            *out_ptr = idx->base.p, *out_bytes = idx->n * idx->dim * 2;
+            *out_ptr = idx->base.p, *out_bytes = idx->n * idx->row_bytes();
             break;
         default: return fail(RQ_ERR_INVALID, "unknown array id");
     }

@@ -30,13 +30,21 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+_BYTE_DTYPE = {_lib.ROWS_U8: np.uint8, _lib.ROWS_I8: np.int8}   # byte rows: the array type each takes and base_rows returns
+
+
 def _typed_rows(base, rows):
     """(base, rows=) of the constructors -> (contiguous array as the library reads it, RQ_ROWS_* id).  rows=None: float16 arrays
-    are f16 rows, everything else f32.  rows="f16" takes float16 (or uint16 bit patterns), rows="bf16" uint16 bit patterns."""
+    are f16 rows, everything else f32 (a uint8 array too: it is converted).  rows="f16" takes float16 (or uint16 bit patterns),
+    rows="bf16" uint16 bit patterns, rows="u8" a uint8 array, rows="i8" an int8 array."""
     a = np.asarray(base)
     rt = (_lib.ROWS_F16 if a.dtype == np.float16 else _lib.ROWS_F32) if rows is None else _lib.row_type_id(rows)
     if rt == _lib.ROWS_F32:
         return _f32(a), rt
+    if rt in _BYTE_DTYPE:
+        if a.dtype != _BYTE_DTYPE[rt]:
+            raise TypeError(f"rows={_lib.ROW_TYPE_NAMES[rt]!r} takes a {np.dtype(_BYTE_DTYPE[rt]).name} array, not {a.dtype}")
+        return np.ascontiguousarray(a), rt
     if rt == _lib.ROWS_F16 and a.dtype == np.float16:
         return np.ascontiguousarray(a), rt
     if a.dtype != np.uint16:
@@ -46,7 +54,8 @@ def _typed_rows(base, rows):
 
 
 def widen(x, rows="f16"):
-    """W(x): f16 / bf16 elements (float16, or uint16 bit patterns) -> f32, on the GPU (rq_widen); any shape."""
+    """W(x): f16 / bf16 elements (float16, or uint16 bit patterns) or, rows="u8" / "i8", uint8 / int8 elements -> f32, on the GPU
+    (rq_widen); any shape."""
     a, rt = _typed_rows(x, rows)
     if rt == _lib.ROWS_F32:
         return a
@@ -178,7 +187,7 @@ class RaBitQ:
         self._ip_d = self.ip_params[0] if self.metric == "ip" else 0   # the raw row length add() and the queries must have
         rt = C.c_uint32()
         check(lib().rq_row_type(self._h, C.byref(rt)))
-        self.row_type = _lib.ROW_TYPE_NAMES.get(int(rt.value), "f32")   # "f16" / "bf16": the raw vectors are stored in that type, 2*dim bytes each
+        self.row_type = _lib.ROW_TYPE_NAMES.get(int(rt.value), "f32")   # "f16" / "bf16" / "u8" / "i8": the raw vectors are stored in that type, 2*dim / dim bytes each
 
     # ---- RaBitQ::from_path (src/rabitq.rs:159) ------------------------------------------------
     @classmethod
@@ -202,7 +211,8 @@ class RaBitQ:
     def build(cls, base, centroids, orthogonal=None, seed: int = 0, metric="l2", max_sq_norm=None, rows=None) -> "RaBitQ":
         """from_path on in-memory arrays (base n x d, centroids k x d; metric="ip": k x c with d <= c <= ceil64(d + 1), missing
         columns are zero).  A float16 `base` (or rows="f16" / rows="bf16" with a uint16 array of bit patterns) makes a half-precision
-        index: the rows are stored as given, 2*dim bytes each."""
+        index: the rows are stored as given, 2*dim bytes each.  rows="u8" with a uint8 array / rows="i8" with an int8 array makes a
+        byte-row index (L2 only), dim bytes each; without rows= such an array is converted to f32."""
         base, rt = _typed_rows(base, rows)
         centroids = _f32(centroids)
         if rt != _lib.ROWS_F32:
@@ -233,7 +243,7 @@ class RaBitQ:
     def build_device(cls, base_ptr: int, n: int, d: int, centroids_ptr: int, k: int, orthogonal=None,
                      seed: int = 0, metric="l2", max_sq_norm=None, centroid_cols: int = None, rows="f32") -> "RaBitQ":
         """Build from device-resident arrays (raw HIP device addresses, e.g. torch.Tensor.data_ptr()).  metric="ip": the
-        centroids are k x centroid_cols (None: d).  rows="f16" / "bf16": base_ptr holds n x d elements of that type."""
+        centroids are k x centroid_cols (None: d).  rows="f16" / "bf16" / "u8" / "i8": base_ptr holds n x d elements of that type."""
         P = _f32(orthogonal) if orthogonal is not None else None
         h = C.c_void_p()
         if _lib.row_type_id(rows) != _lib.ROWS_F32:
@@ -253,7 +263,7 @@ class RaBitQ:
                 max_device_base_bytes: int = 0, metric="l2", max_sq_norm=None, centroid_cols: int = None, rows="f32") -> "Builder":
         """Streamed two-pass build for inputs that are not resident (include/rabitq_hip.h: rq_builder_*).  metric="ip" needs
         max_sq_norm (the largest row_sqnorm_max over the chunks): the streamed build has no automatic bound.  rows="f16" /
-        "bf16": the chunks hold elements of that type."""
+        "bf16" / "u8" / "i8": the chunks hold elements of that type."""
         return Builder(n, d, centroids_ptr, k, orthogonal, seed, max_device_base_bytes, metric, max_sq_norm, centroid_cols, rows)
 
     # ---- load_from_dir / dump_to_dir (src/rabitq.rs:84, :128) ---------------------------------
@@ -281,7 +291,8 @@ class RaBitQ:
                     d: int = None, rows=None) -> "RaBitQ":
         """From the reference's in-memory arrays (what load_from_dir produces).  The arrays are taken as they are; metric="cosine"
         only marks the index, so that its queries and added rows are normalised (`base` then holds normalised rows already).
-        A float16 `base` (or rows="f16" / "bf16" with uint16 bit patterns), n x dim, makes a half-precision index."""
+        A float16 `base` (or rows="f16" / "bf16" with uint16 bit patterns), n x dim, makes a half-precision index; rows="u8" /
+        "i8" with a uint8 / int8 array a byte-row index."""
         base, rt = _typed_rows(base, rows)
         orthogonal, centroids, factors = _f32(orthogonal), _f32(centroids), _f32(factors)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
@@ -330,14 +341,16 @@ class RaBitQ:
 
     @property
     def base(self):
-        """The raw vectors as f32, cluster order (a half-precision index: its rows widened)."""
+        """The raw vectors as f32, cluster order (a half-precision or byte-row index: its rows widened)."""
         return self._get(ARR_BASE, (self.n, self.dim), np.float32)
 
     @property
     def base_rows(self):
-        """The raw vectors in the type the index stores: float32, float16, or (bf16) uint16 bit patterns."""
+        """The raw vectors in the type the index stores: float32, float16, (bf16) uint16 bit patterns, uint8 or int8."""
         if self.row_type == "f32":
             return self.base
+        if self.row_type in ("u8", "i8"):
+            return self._get(ARR_BASE_ROWS, (self.n, self.dim), _BYTE_DTYPE[_lib.ROW_TYPES[self.row_type]])
         return self._get(ARR_BASE_ROWS, (self.n, self.dim), np.float16 if self.row_type == "f16" else np.uint16)
 
     @property
