@@ -85,7 +85,8 @@ typedef struct {
  * queries on the small-batch path;
  * 0.9.0: inner-product metric, additions only -- RQ_METRIC_IP, rq_*_ip, rq_ip_*, rq_augment*, rq_row_sqnorm_max*;
  * 0.10.0: half-precision rows, additions only -- RQ_ROWS_*, rq_*_rows, rq_row_type, rq_widen*, RQ_ARR_BASE_ROWS;
- * 0.11.0: byte rows, two more values of row_type and no new symbol -- RQ_ROWS_U8, RQ_ROWS_I8).
+ * 0.11.0: byte rows, two more values of row_type and no new symbol -- RQ_ROWS_U8, RQ_ROWS_I8;
+ * later in 0.11, additions only: exact search -- rq_exact_search*, rq_last_exact_stats).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -457,6 +458,66 @@ rq_status rq_range_result_device_ptrs(const rq_range_result *r, const uint64_t *
                                       const uint32_t **d_id);
 rq_status rq_range_result_copy(const rq_range_result *r, uint64_t *lims, float *dist, uint32_t *id);
 void rq_range_result_free(rq_range_result *r);
+
+/* ---- exact search: brute-force top-k over the stored rows (later in 0.11, additions only) --------------------------- */
+/* The true nearest neighbours, on the GPU: what the approximate entries above are measured against.  Queries are raw, exactly as
+ * rq_query_batch_device takes them (the same `len` rules; a cosine index normalises them, an inner-product index pads the zero
+ * coordinate); let q' be the padded, transformed query the rerank sees.  For a stored row r let e(r) be the value rq_rerank returns
+ * for the row's position against q' (the src/simd.rs:14-73 order).  The result of query b is, of the stored rows the filter admits
+ * (filter == NULL: all rows) whose e(r) is below f32::MAX -- the query's own rule: a row at inf / NaN is never returned --, the topk
+ * smallest by (Ord32(e), id), ascending, as (distance, id); out_n[b] = how many there are (<= topk); slots past out_n[b] are left
+ * untouched, as the top-k query leaves them.  Distances are in the index's space, like the query's: |x - q|^2, 2 - 2 cos for cosine,
+ * S + |q|^2 - 2<x, q> for inner product (rq_ip_from_dist converts).  The result does not depend on `params`, on options, on the
+ * batch size or on how the work was split.
+ * Accepted: L2 / cosine / inner-product indexes whose raw vectors are all in HBM as plain f32, f16 / bf16 or u8 / i8 rows; shards of
+ * rq_shard_index (ids are their map_ids); mutated indexes.  filter: as validated by the filtered query (another index's, or one made
+ * before a mutation: RQ_ERR_INVALID).  topk in [1, 2048] and dim <= 4096, else RQ_ERR_UNSUPPORTED; a null pointer: RQ_ERR_INVALID;
+ * a tiered index (list tails in host memory) or a split-row index: RQ_ERR_UNSUPPORTED with nothing allocated.  nq == 0 is RQ_OK.  An
+ * index or filter with no admitted row returns out_n = 0 everywhere with the status of the filtered query (RQ_OK).
+ * A row whose squared norm is not a finite f32 (overflow included) is never judged by the approximation below: it always gets its
+ * exact distance, so it is returned exactly when its e is below f32::MAX and among the topk smallest, like any other row.
+ * Method: (1) a bound T_b >= the topk-th smallest e: the topk-th smallest exact distance over a sample of the admitted
+ * rows (every stride-th position, about sqrt(rows x topk) of them; f32::MAX where the sample holds fewer than topk admitted rows);
+ * (2) one pass over the rows that approximates every (query, row) distance with bf16 matrix-core products and keeps the pairs within
+ * a proven margin of T_b; (3) the exact distance of those pairs and the selection.  The bound changes the work, never the answer.
+ * The call touches no counter of rq_metrics.  Dimensions above 2432 run without (1) and (2): every admitted pair gets its exact
+ * distance.
+ * rq_exact_search_device: queries (nq x len) and outputs (nq x topk, nq x topk, nq) in device memory; rq_exact_search: host memory.
+ * params (nullable; sized struct, zero = automatic; TEST HOOKS, results never depend on them): seed_probe = sample rows of the bound
+ * per topk (the sample has seed_probe x topk rows); cand_per_query = initial candidate slots per query (a pass whose candidates overflow them is run again with the count it
+ * learnt); flags bit 0 = no seed (every bound is f32::MAX), bit 1 = no pre-filter (the exact distance of every admitted pair).
+ * rq_last_exact_stats: the calling thread's last exact search -- device time (ms, summed over launches) of the bound (ms_seed: the
+ * sample's exact distances and selection), the scan, the exact distances and the selection; seed_probe = rows of the sample (0: no
+ * bound was made); seed_unfilled = queries whose bound is f32::MAX; candidates = pairs the scan kept; exact = exact distances
+ * computed, the sample's included; reruns = scan launches repeated because a query's candidates did not fit its slots (the capacity
+ * learnt is remembered with the index or filter: a later call starts from it); row_bytes_read = bytes of raw rows the scan launches
+ * covered (algorithmic: n x row bytes per launch; a batch of up to 4096 queries is ONE launch, re-runs count again); scan_launches =
+ * those launches.  A launch that overflowed stops behind the scan: nothing is computed or written from its candidates. */
+typedef struct {
+    uint32_t struct_size; /* in: sizeof(rq_exact_params_t) */
+    uint32_t seed_probe;
+    uint32_t cand_per_query;
+    uint32_t flags;
+} rq_exact_params_t;
+typedef struct {
+    uint32_t struct_size; /* in: sizeof(rq_exact_stats_t) of the caller */
+    uint32_t seed_probe;
+    float ms_seed, ms_scan, ms_exact, ms_select;
+    uint32_t seed_unfilled;
+    uint32_t reruns;
+    uint64_t candidates;
+    uint64_t exact;
+    uint64_t row_bytes_read;
+    uint32_t scan_launches;
+    uint32_t reserved0;
+} rq_exact_stats_t;
+rq_status rq_exact_search_device(const rq_index *idx, const rq_filter *filter /* nullable */, const float *d_queries, uint32_t nq,
+                                 uint32_t len, uint32_t topk, const rq_exact_params_t *params /* nullable */, float *d_out_dist,
+                                 uint32_t *d_out_id, uint32_t *d_out_n);
+rq_status rq_exact_search(const rq_index *idx, const rq_filter *filter /* nullable */, const float *queries, uint32_t nq, uint32_t len,
+                          uint32_t topk, const rq_exact_params_t *params /* nullable */, float *out_dist, uint32_t *out_id,
+                          uint32_t *out_n);
+rq_status rq_last_exact_stats(rq_exact_stats_t *out);
 
 /* ---- in-place mutation: add and remove rows ------------------------------------------------------------------------ */
 /* After any sequence of rq_add / rq_remove the index equals, bit for bit, the index rq_build produces from its live rows S in

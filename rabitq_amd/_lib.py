@@ -29,6 +29,7 @@ EXPORTS = [
     "rq_coarse_rank", "rq_query_prep", "rq_scan", "rq_rerank", "rq_set_profiling", "rq_set_option", "rq_last_profile",
     "rq_build_rows", "rq_build_device_rows", "rq_builder_create_rows", "rq_builder_assign_chunk_rows", "rq_builder_place_chunk_rows",
     "rq_from_arrays_rows", "rq_row_type", "rq_widen", "rq_widen_device",
+    "rq_exact_search", "rq_exact_search_device", "rq_last_exact_stats",
 ]
 
 
@@ -108,6 +109,21 @@ class MutateStatsT(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32)] + [(n, C.c_float) for n in (
         "ms_keys", "ms_assign", "ms_alloc", "ms_merge", "ms_gather", "ms_derive", "ms_free", "ms_total")] + [
         ("rows_before", C.c_uint64), ("rows_after", C.c_uint64), ("gather_bytes", C.c_uint64)]
+
+
+class ExactParamsT(_Sized):
+    """rq_exact_params_t: test hooks of the exact search (zero = automatic; results never depend on them)."""
+    _fields_ = [("struct_size", C.c_uint32), ("seed_probe", C.c_uint32), ("cand_per_query", C.c_uint32), ("flags", C.c_uint32)]
+
+
+EXACT_NO_SEED, EXACT_NO_PREFILTER = 1, 2   # rq_exact_params_t.flags
+
+
+class ExactStatsT(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("seed_probe", C.c_uint32)] + [(n, C.c_float) for n in (
+        "ms_seed", "ms_scan", "ms_exact", "ms_select")] + [
+        ("seed_unfilled", C.c_uint32), ("reruns", C.c_uint32), ("candidates", C.c_uint64), ("exact", C.c_uint64),
+        ("row_bytes_read", C.c_uint64), ("scan_launches", C.c_uint32), ("reserved0", C.c_uint32)]
 
 
 def build(force: bool = False) -> str:
@@ -237,6 +253,9 @@ def lib():
         "rq_row_type": (i32, [vp, C.POINTER(u32)]),
         "rq_widen": (i32, [vp, u32, u64, f32p]),
         "rq_widen_device": (i32, [vp, u32, u64, f32p]),
+        "rq_exact_search": (i32, [vp, vp, f32p, u32, u32, u32, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
+        "rq_exact_search_device": (i32, [vp, vp, f32p, u32, u32, u32, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
+        "rq_last_exact_stats": (i32, [C.POINTER(ExactStatsT)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the .so lacks a declared symbol

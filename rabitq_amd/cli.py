@@ -1,7 +1,7 @@
 """Benchmark harness with the reference CLI's behaviour (crates/cli/src/main.rs:11-83):
 
     python -m rabitq_amd.cli -b base.fvecs -c centroids.fvecs -q query.fvecs -t truth.ivecs \
-                             -s saved_dir [-p 100] [-k 10] [-h | --heuristic-rank] [--metric l2|cosine|ip]
+                             -s saved_dir [-p 100] [-k 10] [-h | --heuristic-rank] [--metric l2|cosine|ip] [--make-truth]
 
 * the flags are the reference's, letter for letter: `-h` is the heuristic re-ranker there (`#[argh(switch, short = 'h')]`,
   main.rs:35-37), not help -- argh reserves only `--help` -- so a caller script written for the reference CLI runs unchanged;
@@ -12,7 +12,9 @@
   (main.rs:66-80) -- the faithful, latency-bound number; `--batch B` additionally reports the
   batched throughput the GPU engine is designed for;
 * prints mean recall@k against the ground-truth ivecs (src/utils.rs:367-379) and the METRICS line
-  (src/metrics.rs:30-41).
+  (src/metrics.rs:30-41);
+* `--make-truth`: when the `-t` file does not exist, the exact top-max(topk, 100) of the query file is computed on the GPU
+  (RaBitQ.exact_search) and written there as .ivecs first; an existing file is never overwritten.
 """
 from __future__ import annotations
 
@@ -45,7 +47,28 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--rows", choices=["u8", "i8"], default=None,
                     help="build a byte-row index (L2 only): the base is a .bvecs file whose one-byte elements are stored as given, "
                          "dim bytes per vector; the centroids stay an fvecs file")
+    ap.add_argument("--make-truth", dest="make_truth", action="store_true",
+                    help="when the truth path does not exist: compute the exact top-max(topk, 100) of the queries on the GPU "
+                         "and write it there as .ivecs (an existing file is left alone)")
     return ap
+
+
+def make_truth(index, queries, path, topk: int) -> bool:
+    """Write the exact top-max(topk, 100) ids of `queries` to `path` as .ivecs unless the file exists -> whether it was written.
+    A query with fewer stored rows than that gets a shorter record."""
+    if os.path.exists(path):
+        return False
+    k = max(topk, 100)
+    ids = np.zeros((0, k), np.uint32)
+    cnt = np.zeros(0, np.uint32)
+    for s in range(0, len(queries), 4096):
+        _, i_, c_ = index.exact_search(np.stack(queries[s:s + 4096]), k)
+        ids, cnt = np.concatenate([ids, i_]), np.concatenate([cnt, c_])
+    if len(cnt) and int(cnt.min()) == k:
+        vecs.write_ivecs(path, ids)
+    else:
+        vecs.write_vecs(path, [ids[j, :cnt[j]].astype("<i4") for j in range(len(cnt))])
+    return True
 
 
 def main(argv=None) -> int:
@@ -65,6 +88,8 @@ def main(argv=None) -> int:
         index.dump_to_dir(args.saved)
 
     queries = vecs.read_vecs(args.query, np.float32)
+    if args.make_truth and make_truth(index, queries, args.truth, args.topk):
+        print(f"ground truth written to {args.truth!r} (exact search, top {max(args.topk, 100)})")
     truth = vecs.read_vecs(args.truth, np.int32)
     print("querying...")
     metrics_reset()

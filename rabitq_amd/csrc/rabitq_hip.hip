@@ -41,6 +41,7 @@
 #include "host_range.h"
 #include "host_build.h"
 #include "host_mutate.h"
+#include "host_exact.h"
 
 // ------------------------------------------------------------------------------------------------
 // extern "C"
@@ -1003,6 +1004,20 @@ rq_status rq_filter_rows(const rq_filter *f, uint64_t *out_admitted) {
     return RQ_OK;
 }
 void rq_filter_free(rq_filter *f) { delete f; }
+
+// ---- exact search (host_exact.h): brute-force top-k over the stored rows ----
+rq_status rq_exact_search_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len, uint32_t topk,
+                                 const rq_exact_params_t *params, float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n) {
+    return exact_search_device(idx, filter, d_queries, nq, len, topk, params, d_out_dist, d_out_id, d_out_n);
+}
+rq_status rq_exact_search(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len, uint32_t topk,
+                          const rq_exact_params_t *params, float *out_dist, uint32_t *out_id, uint32_t *out_n) {
+    return exact_search_host(idx, filter, queries, nq, len, topk, params, out_dist, out_id, out_n);
+}
+rq_status rq_last_exact_stats(rq_exact_stats_t *out) {
+    if (!out) return fail(RQ_ERR_INVALID, "null argument");
+    return copy_out_sized(out, g_exact_stats);
+}
 
 // ---- in-place mutation (host_mutate.h): the index afterwards equals a fresh build of its live rows, bit for bit ----
 static rq_status mutate_done(const rq_index *idx, rq_status s, std::chrono::steady_clock::time_point t0) {

@@ -511,6 +511,77 @@ class RaBitQ:
                                                        int(heuristic_rank), C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr),
                                                        C.c_void_p(out_n_ptr)))
 
+    # ---- exact search: brute-force top-k over the stored rows (rq_exact_search*) -----------------
+    @staticmethod
+    def _exact_params(params):
+        """None, an ExactParamsT, or a dict of its fields (seed_probe, cand_per_query, flags: test hooks, result-neutral)."""
+        if params is None or isinstance(params, _lib.ExactParamsT):
+            return params
+        return _lib.ExactParamsT(**params)
+
+    def exact_search(self, queries, topk: int, filter: Filter = None, params=None):
+        """The true topk nearest stored rows of every query, on the GPU -> (dist B x topk f32, ids B x topk u32, counts B u32),
+        ascending by (distance, id); slots past a query's count hold NaN / 0xFFFFFFFF.  filter: only its rows can be returned."""
+        q = _f32(queries)
+        if q.ndim != 2:
+            raise _lib.RabitqError(-1, "queries must be 2-D")
+        B = q.shape[0]
+        d = np.full((B, max(topk, 1)), np.nan, dtype=np.float32)
+        ids = np.full((B, max(topk, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        cnt = np.zeros(B, dtype=np.uint32)
+        prm = self._exact_params(params)
+        check(lib().rq_exact_search(self._h, _fh(filter), _addr(q), B, q.shape[1], topk, C.byref(prm) if prm is not None else None,
+                                    _addr(d), _addr(ids), _addr(cnt)))
+        return d, ids, cnt
+
+    def exact_search_device(self, q_ptr: int, nq: int, length: int, topk: int, out_dist_ptr: int, out_id_ptr: int, out_n_ptr: int,
+                            filter: Filter = None, params=None):
+        """exact_search with queries and outputs already in device memory (raw addresses)."""
+        prm = self._exact_params(params)
+        check(lib().rq_exact_search_device(self._h, _fh(filter), C.c_void_p(q_ptr), nq, length, topk,
+                                           C.byref(prm) if prm is not None else None, C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr),
+                                           C.c_void_p(out_n_ptr)))
+
+    @staticmethod
+    def _recall_of(ids, cnt, exact_ids, exact_cnt) -> float:
+        """mean over the queries with a non-empty exact answer of |query ids n exact ids| / exact count"""
+        vals = [len(np.intersect1d(ids[b, :cnt[b]], exact_ids[b, :exact_cnt[b]])) / int(exact_cnt[b])
+                for b in range(len(exact_cnt)) if exact_cnt[b]]
+        return float(np.mean(vals)) if vals else 1.0
+
+    def recall(self, queries, probe: int, topk: int, filter: Filter = None, heuristic_rank: bool = False) -> float:
+        """What fraction of the true topk neighbours query_batch(queries, probe, topk) returns: the mean over the queries of
+        |query ids n exact ids| / exact count (queries whose exact answer is empty are left out; none left: 1.0)."""
+        _, eids, ecnt = self.exact_search(queries, topk, filter)
+        _, ids, cnt = self.query_batch(queries, probe, topk, heuristic_rank, filter)
+        return self._recall_of(ids, cnt, eids, ecnt)
+
+    def tune_nprobe(self, queries, topk: int, target_recall: float, filter: Filter = None):
+        """The smallest nprobe whose recall on these queries reaches target_recall -> (nprobe, recall); (k, recall at k) when the
+        target is out of reach.  The exact answer is computed once; every probe value tried is one query_batch: doubling from 1
+        until the target is met, then bisection between the last miss and the first hit."""
+        _, eids, ecnt = self.exact_search(queries, topk, filter)
+        seen = {}
+
+        def at(p):
+            if p not in seen:
+                _, ids, cnt = self.query_batch(queries, p, topk, False, filter)
+                seen[p] = self._recall_of(ids, cnt, eids, ecnt)
+            return seen[p]
+
+        lo, hi = 0, 1                      # lo: the largest value known to miss (0: none), hi: the value being tried
+        while at(hi) < target_recall:
+            if hi >= self.k:
+                return self.k, at(self.k)
+            lo, hi = hi, min(2 * hi, self.k)
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            if at(mid) >= target_recall:
+                hi = mid
+            else:
+                lo = mid
+        return hi, at(hi)
+
     # ---- range search: every neighbour within a per-query radius --------------------------------
     @property
     def ip_params(self):
@@ -728,6 +799,13 @@ def last_mutate_stats() -> dict:
     st = _lib.MutateStatsT()
     check(lib().rq_last_mutate_stats(C.byref(st)))
     return {name: getattr(st, name) for name, _ in _lib.MutateStatsT._fields_ if name not in ("struct_size", "reserved0")}
+
+
+def last_exact_stats() -> dict:
+    """The calling thread's last exact search (include/rabitq_hip.h: rq_last_exact_stats)."""
+    st = _lib.ExactStatsT()
+    check(lib().rq_last_exact_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _lib.ExactStatsT._fields_ if name not in ("struct_size", "reserved0")}
 
 
 def calculate_recall(truth, res, topk: int) -> float:

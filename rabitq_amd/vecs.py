@@ -36,6 +36,16 @@ def write_vecs(path, records) -> None:
             f.write(r.tobytes())
 
 
+def write_ivecs(path, rows) -> None:
+    """n x m integer rows (ids) -> an .ivecs file: records of [u32 LE m][m x i32 LE], one per row (a ground-truth file).
+    The format's elements are i32: a uint32 id of 2^31 or more is stored as its two's-complement bit pattern (read it back with
+    read_vecs(path, np.int32) and .view(np.uint32))."""
+    a = np.asarray(rows)
+    if a.ndim != 2 or a.dtype.kind not in "iu":
+        raise ValueError("write_ivecs takes a 2-D integer array")
+    write_vecs(path, list(a.astype("<i4")))
+
+
 def read_bvecs(path, dtype=np.uint8) -> np.ndarray:
     """A .bvecs file (SIFT1B / BIGANN): records of [u32 LE dim][dim x one byte], all of the same dim -> n x dim, uint8 (or int8:
     the same bytes read as two's complement).  What RaBitQ.build(rows="u8" / "i8") takes."""
