@@ -8,6 +8,9 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from typing import NamedTuple
+
+import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("RABITQ_HIP_SO") or os.path.join(_HERE, "librabitq_hip.so")   # (override: kernel experiments)
@@ -54,9 +57,28 @@ def metric_id(metric) -> int:
     return int(metric)
 
 
-ROWS_F32, ROWS_F16, ROWS_BF16, ROWS_U8, ROWS_I8 = 0, 1, 2, 4, 5   # RQ_ROWS_*
-ROW_TYPES = {"f32": ROWS_F32, "f16": ROWS_F16, "bf16": ROWS_BF16, "u8": ROWS_U8, "i8": ROWS_I8}
-ROW_TYPE_NAMES = {v: k for k, v in ROW_TYPES.items()}
+class RowType(NamedTuple):
+    """One row type (RQ_ROWS_* of include/rabitq_hip.h), as the Python layer sees it."""
+    name: str          # the rows= argument and RaBitQ.row_type
+    id: int            # the C ABI's row_type
+    takes: tuple       # numpy dtypes an array of these rows may have (f32: anything, it is converted)
+    returns: type      # numpy dtype base_rows returns
+    elem_bytes: int
+
+
+# the one table of row types: everything below, index.py and cli.py read it
+ROW_TABLE = (
+    RowType("f32", 0, (), np.float32, 4),
+    RowType("f16", 1, (np.float16, np.uint16), np.float16, 2),   # (uint16: bit patterns)
+    RowType("bf16", 2, (np.uint16,), np.uint16, 2),              # bit patterns only: numpy has no bfloat16
+    RowType("u8", 4, (np.uint8,), np.uint8, 1),
+    RowType("i8", 5, (np.int8,), np.int8, 1),
+)
+ROWS_F32, ROWS_F16, ROWS_BF16, ROWS_U8, ROWS_I8 = (t.id for t in ROW_TABLE)   # RQ_ROWS_*
+ROW_TYPES = {t.name: t.id for t in ROW_TABLE}
+ROW_TYPE_NAMES = {t.id: t.name for t in ROW_TABLE}
+ROW_TYPE_BY_ID = {t.id: t for t in ROW_TABLE}
+ROW_TYPE_BY_NAME = {t.name: t for t in ROW_TABLE}
 
 
 def row_type_id(rows) -> int:

@@ -24,7 +24,7 @@ import time
 
 import numpy as np
 
-from . import RaBitQ, calculate_recall, metrics_reset, metrics_str, vecs
+from . import RaBitQ, _lib, calculate_recall, metrics_reset, metrics_str, vecs
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -44,7 +44,7 @@ def build_parser() -> argparse.ArgumentParser:
                     help="metric of the index when building (a saved index keeps its own): cosine normalises rows and queries "
                          "on the GPU, distances are 2 - 2 cos; ip is maximum inner product search (rows get one more "
                          "coordinate, distances are S + |q|^2 - 2<x, q> with S the largest squared row norm)")
-    ap.add_argument("--rows", choices=["u8", "i8"], default=None,
+    ap.add_argument("--rows", choices=[t.name for t in _lib.ROW_TABLE if t.elem_bytes == 1], default=None,
                     help="build a byte-row index (L2 only): the base is a .bvecs file whose one-byte elements are stored as given, "
                          "dim bytes per vector; the centroids stay an fvecs file")
     ap.add_argument("--make-truth", dest="make_truth", action="store_true",
@@ -80,7 +80,7 @@ def main(argv=None) -> int:
     else:
         print("training...")
         if args.rows:
-            base = vecs.read_bvecs(args.base, np.uint8 if args.rows == "u8" else np.int8)
+            base = vecs.read_bvecs(args.base, _lib.ROW_TYPE_BY_NAME[args.rows].returns)
             index = RaBitQ.build(base, vecs.read_matrix(args.centroids), seed=args.seed, metric=args.metric, rows=args.rows)
         else:
             index = RaBitQ.from_path(args.base, args.centroids, seed=args.seed, metric=args.metric)

@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "rows.h"  // RowSpec: the row types (RQ_ROWS_*), their element widen / narrow
 
 #pragma clang fp contract(off)
 
@@ -147,69 +148,7 @@ struct ListTier {  // one per list
 // exactly.  The re-ranker reads the first plane alone (half the bytes), proves most survivors out of the top-k with it
 // (accurate_split_kernel, kernels_rerank.h) and fetches the second plane only for the rest.  Both tiers use the layout: over the
 // host link the first plane alone is half the bytes as well.
-// Half-precision rows (row_type RQ_ROWS_F16 = 1, RQ_ROWS_BF16 = 2; include/rabitq_hip.h): the index stores the caller's 2-byte
-// elements as given, 2*dim bytes per row, never tiered, never split, no shadow rows.  Widening W to f32 is exact (f16: the IEEE
-// conversion, subnormals kept; bf16: bits << 16), so every distance is the f32 index's of W(rows), bit for bit.
-#define RQ_ROWS_F32_ 0u
-#define RQ_ROWS_F16_ 1u
-#define RQ_ROWS_BF16_ 2u
-// Byte rows (row_type RQ_ROWS_U8 = 4, RQ_ROWS_I8 = 5): the caller's one-byte elements as given, dim bytes per row, padding 0x00,
-// never tiered, never split, no shadow rows.  W(u8) = the integer as f32, W(i8) = the two's-complement integer as f32: both exact,
-// so every distance is the f32 index's of W(rows), bit for bit.
-#define RQ_ROWS_U8_ 4u
-#define RQ_ROWS_I8_ 5u
-__host__ __device__ __forceinline__ bool rq_rows_are_bytes(uint32_t fmt) { return fmt >= RQ_ROWS_U8_; }
-// f32 slots (4 bytes) one stored row of dim elements takes: the stride of BaseView::dev
-__host__ __device__ __forceinline__ uint32_t rq_row_slots(uint32_t fmt, uint32_t dim) {
-    return fmt == RQ_ROWS_F32_ ? dim : rq_rows_are_bytes(fmt) ? dim >> 2 : dim >> 1;
-}
-// W of one stored byte, and its inverse on representable values (anything else: clamped and truncated -- the loaders check with
-// narrow_exact, host_build.h, before they store)
-__host__ __device__ __forceinline__ float rq_widen_byte(uint8_t b, uint32_t fmt) {
-    return fmt == RQ_ROWS_I8_ ? (float)(int32_t)(int8_t)b : (float)(uint32_t)b;
-}
-__host__ __device__ __forceinline__ uint8_t rq_narrow_byte(float v, uint32_t fmt) {
-    if (fmt == RQ_ROWS_I8_) return (uint8_t)(int8_t)(int32_t)(v >= 127.0f ? 127.0f : v >= -128.0f ? v : -128.0f);  // (a NaN: -128)
-    return (uint8_t)(uint32_t)(v >= 255.0f ? 255.0f : v >= 0.0f ? v : 0.0f);                                         // (a NaN: 0)
-}
-// W of one stored 2-byte element
-__host__ __device__ __forceinline__ float rq_widen_elem(uint16_t h, uint32_t fmt) {
-    if (fmt == RQ_ROWS_BF16_) return __builtin_bit_cast(float, (uint32_t)h << 16);
-#ifdef __HIP_DEVICE_COMPILE__
-    return (float)__builtin_bit_cast(_Float16, h);
-#else
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, ex = (h >> 10) & 31u, man = h & 0x3FFu;
-    if (ex == 31u) return __builtin_bit_cast(float, sign | 0x7F800000u | (man ? 0x00400000u | (man << 13) : 0u));
-    if (ex != 0u) return __builtin_bit_cast(float, sign | ((ex + 112u) << 23) | (man << 13));
-    const float mag = (float)man * 5.9604644775390625e-8f;  // man * 2^-24: exact
-    return sign ? -mag : mag;
-#endif
-}
-// R_t of one f32 value: round to nearest even to the storage type (f16: subnormal results kept, overflow to inf; bf16:
-// (u + 0x7FFF + ((u >> 16) & 1)) >> 16 on the bits u).  A NaN stays a NaN, and one whose low 16 bits are zero keeps its bf16 bits.
-__host__ __device__ __forceinline__ uint16_t rq_narrow_elem(float v, uint32_t fmt) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, v);
-    if (fmt == RQ_ROWS_BF16_) {
-        if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | ((u & 0xFFFFu) ? 0x40u : 0u));
-        return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-    }
-#ifdef __HIP_DEVICE_COMPILE__
-    return __builtin_bit_cast(uint16_t, (_Float16)v);
-#else
-    const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7FFFFFFFu;
-    if (a > 0x7F800000u) return (uint16_t)(sign | 0x7E00u | ((a >> 13) & 0x3FFu));
-    if (a >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);  // >= 65520 rounds to inf (inf itself included)
-    if (a < 0x33000001u) return (uint16_t)sign;               // <= 2^-25 rounds to zero (the tie goes to the even 0)
-    const uint32_t e = a >> 23;
-    // 24-bit significand shifted so that the result counts units of the target's last place (normal: 2^(e-127-10), subnormal: 2^-24)
-    const uint32_t sig = (a & 0x7FFFFFu) | 0x800000u, sh = e >= 113u ? 13u : 126u - e;
-    const uint32_t q = sig >> sh, rem = sig & ((1u << sh) - 1u), halfway = 1u << (sh - 1u);
-    const uint32_t r = q + ((rem > halfway || (rem == halfway && (q & 1u))) ? 1u : 0u);
-    // normal: q carries the hidden bit (0x400 .. 0x7FF), so adding (e - 113) << 10 lands the exponent, and a carry out of the
-    // significand moves into it; subnormal: r is the significand itself (a carry to 0x400 is the smallest normal)
-    return (uint16_t)(sign | (e >= 113u ? ((e - 113u) << 10) + r : r));
-#endif
-}
+// (Half-precision and byte rows, which store the caller's elements as given: rows.h.)
 struct RowRef {
     const float *p;  // the row's 4*dim bytes (a half-precision row: its 2*dim bytes; a byte row: its dim bytes)
     bool split;      // stored as two 16-bit planes
@@ -220,7 +159,7 @@ __host__ __device__ __forceinline__ uint32_t rq_split_join(uint32_t h16, uint32_
 }
 // element e of a row / its store (cold paths: placement, dumps, shards, rq_rerank); a half-precision or byte row widens / narrows
 __host__ __device__ __forceinline__ float rq_row_get(const RowRef r, uint32_t dim, uint32_t e) {
-    if (rq_rows_are_bytes(r.fmt)) return rq_widen_byte(reinterpret_cast<const uint8_t *>(r.p)[e], r.fmt);
+    if (RowSpec{r.fmt}.bytes()) return rq_widen_byte(reinterpret_cast<const uint8_t *>(r.p)[e], r.fmt);
     if (r.fmt) return rq_widen_elem(reinterpret_cast<const uint16_t *>(r.p)[e], r.fmt);
     if (!r.split) return r.p[e];
     const uint16_t *h = reinterpret_cast<const uint16_t *>(r.p);
@@ -228,7 +167,7 @@ __host__ __device__ __forceinline__ float rq_row_get(const RowRef r, uint32_t di
 }
 __host__ __device__ __forceinline__ void rq_row_put(const RowRef r, uint32_t dim, uint32_t e, float v) {
     float *w = const_cast<float *>(r.p);
-    if (rq_rows_are_bytes(r.fmt)) {
+    if (RowSpec{r.fmt}.bytes()) {
         reinterpret_cast<uint8_t *>(w)[e] = rq_narrow_byte(v, r.fmt);
         return;
     }
@@ -244,6 +183,28 @@ __host__ __device__ __forceinline__ void rq_row_put(const RowRef r, uint32_t dim
     uint16_t *h = reinterpret_cast<uint16_t *>(w);
     h[e] = (uint16_t)((bits + 0x8000u) >> 16), h[dim + e] = (uint16_t)bits;
 }
+// the 8-element form of rq_row_get for an unsplit row: elements e0 .. e0 + 7 (e0 a multiple of 8), widened exactly, one load per lane
+__device__ __forceinline__ void rq_row_get8(const RowRef rr, uint32_t e0, float (&v)[8]) {
+    if (RowSpec{rr.fmt}.bytes()) {
+        const uint2 w = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint8_t *>(rr.p) + e0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[i] = rq_widen_byte((uint8_t)(w.x >> (8 * i)), rr.fmt);
+            v[4 + i] = rq_widen_byte((uint8_t)(w.y >> (8 * i)), rr.fmt);
+        }
+    } else if (rr.fmt) {
+        const uint4 w = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(rr.p) + e0);
+        const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[2 * i] = rq_widen_elem((uint16_t)ww[i], rr.fmt);
+            v[2 * i + 1] = rq_widen_elem((uint16_t)(ww[i] >> 16), rr.fmt);
+        }
+    } else {
+        const float4 a = *reinterpret_cast<const float4 *>(rr.p + e0), b = *reinterpret_cast<const float4 *>(rr.p + e0 + 4);
+        v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
+    }
+}
 struct BaseView {
     const float *dev;    // HBM tier
     const float *host;   // device-visible address of the pinned host tier; nullptr = every row is in HBM, at its position
@@ -253,7 +214,7 @@ struct BaseView {
     uint32_t fmt;        // RQ_ROWS_*: half-precision rows (untiered, never split) lie 2*dim bytes apart, byte rows dim bytes
     // row of position p of an untiered index
     __host__ __device__ __forceinline__ RowRef row_at(uint64_t p, uint32_t dim) const {
-        return RowRef{dev + p * rq_row_slots(fmt, dim), split != 0, fmt};
+        return RowRef{dev + p * RowSpec{fmt}.row_slots(dim), split != 0, fmt};
     }
     // row of position p that belongs to list c
     __host__ __device__ __forceinline__ RowRef row_in_list(uint64_t p, const ListTier &t, uint32_t dim) const {

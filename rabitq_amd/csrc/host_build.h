@@ -74,7 +74,7 @@ static rq_status derive_shadow_rows(rq_index *idx) {
     int kind = g_rerank_shadow.load();
     if (kind == 2 && idx->dim > 4096) kind = 1;  // (the 8-bit encoder handles rows of up to 4096 dimensions: wider vectors take the fp16 rows)
     // (a half-precision index stores no shadow rows: its survivors read their 2*dim-byte rows)
-    if (!kind || idx->base_host != nullptr || idx->split_rows || idx->row_type || idx->n < RQ_SHADOW_MIN_ROWS) return RQ_OK;
+    if (!kind || idx->base_host != nullptr || idx->split_rows || idx->rows.typed() || idx->n < RQ_SHADOW_MIN_ROWS) return RQ_OK;
     const uint64_t total = idx->n * idx->dim, bytes = total * (kind == 2 ? 1 : 2);
     size_t free_b = 0, total_b = 0;
     HIPC(hipMemGetInfo(&free_b, &total_b));
@@ -260,7 +260,7 @@ static rq_status alloc_base_tiers(rq_index *idx, uint64_t budget_bytes, const ui
         }
     }
     const uint64_t budget_rows = cap == ~0ull ? idx->n : std::min<uint64_t>(idx->n, cap / row);
-    if (idx->row_type) {  // half-precision and byte rows: in HBM at their positions or not at all (no tiers, no split rows, no shadow rows)
+    if (idx->rows.typed()) {  // half-precision and byte rows: in HBM at their positions or not at all (no tiers, no split rows, no shadow rows)
         if (budget_rows < idx->n)
             return fail(RQ_ERR_UNSUPPORTED, "the typed rows of this index (" + std::to_string(want) + " bytes) do not fit the HBM budget: there are no tiers for half-precision or byte rows");
         idx->n_dev = idx->n, idx->split_rows = false;
@@ -321,7 +321,7 @@ struct rq_builder {
     uint64_t budget = 0;
     DevBuf<uint32_t> label, pos_of_id;
     DevBuf<float> mind, xpad, xrot;
-    DevBuf<float> wide;  // a half-precision builder (idx->row_type): the typed chunk widened, at most RQ_BUILD_CHUNK x d f32 -- the only f32 image of the input
+    DevBuf<float> wide;  // a typed builder (idx->rows): the typed chunk widened, at most RQ_BUILD_CHUNK x d f32 -- the only f32 image of the input
     DevBuf<uint64_t> codes_tmp;
     DevBuf<float4> factors_tmp;
     AssignAux assign_aux;
@@ -370,54 +370,49 @@ struct rq_builder {
 };
 #define RQ_BUILD_CHUNK (1ull << 20)
 
-// ---- typed rows (include/rabitq_hip.h, "half-precision rows" and "byte rows") ----
-static bool row_type_known(uint32_t row_type) { return row_type <= RQ_ROWS_BF16 || row_type == RQ_ROWS_U8 || row_type == RQ_ROWS_I8; }
+// ---- typed rows (include/rabitq_hip.h, "half-precision rows" and "byte rows"; what a row type is: RowSpec, rows.h) ----
+// Rows as a caller handed them over: elements of `type`, row after row (the f32 entries: RQ_ROWS_F32)
+struct RowsIn {
+    const void *p;
+    RowSpec type;
+    bool typed_call;  // through a _rows entry with a typed row type: the chunk calls then are the _rows ones
+    static RowsIn plain(const float *p) { return RowsIn{p, RowSpec{}, false}; }
+    static RowsIn of(const void *p, RowSpec type) { return RowsIn{p, type, type.typed()}; }
+    // a chunk of the _rows chunk entries: elements of the builder's own row type (which the builder may refuse: builder_chunk_type_check)
+    static RowsIn chunk_rows(const rq_builder *b, const void *p) { return RowsIn{p, b ? b->idx->rows : RowSpec{}, true}; }
+    const float *f32() const { return static_cast<const float *>(p); }
+    const void *at(uint64_t elem) const { return static_cast<const uint8_t *>(p) + elem * type.elem_bytes(); }
+};
 // the row types an entry takes, and the metrics that have none
-static rq_status row_type_check(uint32_t row_type, const MetricSpec &metric) {
-    if (!row_type_known(row_type)) return fail(RQ_ERR_INVALID, "unknown row_type " + std::to_string(row_type));
-    if (row_type && metric.id == RQ_METRIC_IP)
-        return fail(RQ_ERR_UNSUPPORTED, "the inner-product metric has no typed rows: its extra coordinate sqrt(S - |x|^2) is not representable in the row type");
-    if (rq_rows_are_bytes(row_type) && metric.id == RQ_METRIC_COSINE)
-        return fail(RQ_ERR_UNSUPPORTED, "the cosine metric has no byte rows: a normalised row is not a value of the row type");
-    return RQ_OK;
-}
-// the stored tag: the `rows` file of a dumped directory ("f16\n" / "bf16\n" / "u8\n" / "i8\n"), the "rows" member of a JSON dump
-static const char *row_type_text(uint32_t row_type) {
-    return row_type == RQ_ROWS_U8 ? "u8" : row_type == RQ_ROWS_I8 ? "i8" : row_type == RQ_ROWS_BF16 ? "bf16" : "f16";
-}
-static bool row_type_from_text(const std::string &text, uint32_t *row_type) {
-    if (text == "f16") *row_type = RQ_ROWS_F16;
-    else if (text == "bf16") *row_type = RQ_ROWS_BF16;
-    else if (text == "u8") *row_type = RQ_ROWS_U8;
-    else if (text == "i8") *row_type = RQ_ROWS_I8;
-    else return false;
-    return true;
+static rq_status row_type_check(RowSpec rows, const MetricSpec &metric) {
+    if (!rows.known()) return fail(RQ_ERR_INVALID, "unknown row_type " + std::to_string(rows.id));
+    if (rows.allowed_with(metric.id)) return RQ_OK;
+    return fail(RQ_ERR_UNSUPPORTED, metric.id == RQ_METRIC_IP
+                                        ? "the inner-product metric has no typed rows: its extra coordinate sqrt(S - |x|^2) is not representable in the row type"
+                                        : "the cosine metric has no byte rows: a normalised row is not a value of the row type");
 }
 // f32 values a loader found where typed rows are announced -> the type's elements (`out`: count elements of the type, as bytes);
 // a value the type cannot hold (W(R_t(v)) != v bit for bit; for the half-precision types a NaN counts as held) is RQ_ERR_IO
-static rq_status narrow_exact(const float *v, uint64_t count, uint32_t row_type, std::vector<uint8_t> &out, const std::string &where) {
-    const bool bytes = rq_rows_are_bytes(row_type);
-    out.resize(count * (bytes ? 1 : 2));
-    uint16_t *o16 = reinterpret_cast<uint16_t *>(out.data());
+static rq_status narrow_exact(const float *v, uint64_t count, RowSpec rows, std::vector<uint8_t> &out, const std::string &where) {
+    out.resize(count * rows.elem_bytes());
     for (uint64_t i = 0; i < count; ++i) {
-        float back;
-        if (bytes) out[i] = rq_narrow_byte(v[i], row_type), back = rq_widen_byte(out[i], row_type);
-        else o16[i] = rq_narrow_elem(v[i], row_type), back = rq_widen_elem(o16[i], row_type);
-        if (__builtin_bit_cast(uint32_t, back) != __builtin_bit_cast(uint32_t, v[i]) && (bytes || v[i] == v[i]))
+        rows.narrow(out.data(), i, v[i]);
+        const float back = rows.widen(out.data(), i);
+        if (__builtin_bit_cast(uint32_t, back) != __builtin_bit_cast(uint32_t, v[i]) && (rows.bytes() || v[i] == v[i]))
             return fail(RQ_ERR_IO, where + ": value " + std::to_string(i) + " is not representable in the row type the index announces");
     }
     return RQ_OK;
 }
-// `count` elements widened on the null stream (widen_rows_kernel / widen_byte_rows_kernel)
-static void launch_widen(const void *d_x, uint32_t row_type, uint64_t count, float *d_out) {
+// `count` elements of a typed spec widened on the null stream (widen_rows_kernel)
+static void launch_widen(const void *d_x, RowSpec rows, uint64_t count, float *d_out) {
     if (!count) return;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(ceil_div(count, 256), 1u << 20);
-    if (rq_rows_are_bytes(row_type)) widen_byte_rows_kernel<<<grid, 256>>>(static_cast<const uint8_t *>(d_x), row_type, count, d_out);
-    else widen_rows_kernel<<<grid, 256>>>(static_cast<const uint16_t *>(d_x), row_type, count, d_out);
+    if (rows.bytes()) widen_rows_kernel<<<grid, 256>>>(static_cast<const uint8_t *>(d_x), rows.id, count, d_out);
+    else widen_rows_kernel<<<grid, 256>>>(static_cast<const uint16_t *>(d_x), rows.id, count, d_out);
 }
 // a typed builder takes its chunks through the _rows calls only, a plain one through the plain calls only
 static rq_status builder_chunk_type_check(const rq_builder *b, bool typed) {
-    if ((b->idx->row_type != RQ_ROWS_F32) == typed) return RQ_OK;
+    if (b->idx->rows.typed() == typed) return RQ_OK;
     return fail(RQ_ERR_INVALID, typed ? "this builder takes f32 chunks: use rq_builder_assign_chunk / rq_builder_place_chunk"
                                       : "this builder takes chunks of its row type: use rq_builder_assign_chunk_rows / rq_builder_place_chunk_rows");
 }
@@ -435,16 +430,16 @@ static rq_status builder_alloc_pass1(rq_builder *b) {
     if (b->d != dim || idx->metric.id != RQ_METRIC_L2) RQC(b->xpad.alloc(chunk * dim));  // (an L2 row of dim floats is rotated where it is)
     if (metric_refuses_rows(idx->metric)) RQC(b->ip_bad.alloc(1));
     RQC(b->xrot.alloc(chunk * dim));
-    if (idx->row_type) RQC(b->wide.alloc(chunk * b->d));
+    if (idx->rows.typed()) RQC(b->wide.alloc(chunk * b->d));
     if (assign_has_mfma(idx->W) && g_assign_impl.load() != 1) RQC(assign_aux_init(idx, b->assign_aux, chunk));
     for (auto &e : b->ev) HIPC(hipEventCreate(&e));
     return RQ_OK;
 }
 
 static rq_status builder_create(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
-                                uint64_t seed, uint64_t max_device_base_bytes, const MetricSpec &metric, uint32_t cent_cols, rq_builder **out,
-                                uint32_t row_type = RQ_ROWS_F32) {
-    RQC(row_type_check(row_type, metric));
+                                uint64_t seed, uint64_t max_device_base_bytes, const MetricSpec &metric, RowSpec rows, uint32_t cent_cols,
+                                rq_builder **out) {
+    RQC(row_type_check(rows, metric));
     RQC(ensure_device());
     RQC(ensure_kernel_attributes());
     if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
@@ -461,7 +456,7 @@ static rq_status builder_create(uint64_t n, uint32_t d, const float *d_centroids
     std::unique_ptr<rq_builder> b(new rq_builder());
     b->idx.reset(new rq_index());
     rq_index *idx = b->idx.get();
-    idx->dim = dim, idx->k = k, idx->n = n, idx->W = dim / 64, idx->metric = metric, idx->row_type = row_type;
+    idx->dim = dim, idx->k = k, idx->n = n, idx->W = dim / 64, idx->metric = metric, idx->rows = rows;
     b->d = d, b->budget = max_device_base_bytes;
 
     std::vector<float> Pgen;
@@ -495,11 +490,9 @@ static rq_status builder_rows_check(rq_builder *b) {
 }
 
 // pass 1 for rows [i0, i0 + m) of the input (d_rows: m x d, device)
-// (typed: the call came through the _rows entry -- the rows are m x d elements of the builder's row type)
-static rq_status builder_assign(rq_builder *b, const void *d_rows_any, uint64_t i0, uint64_t m, bool typed = false) {
-    if (!b || (m && !d_rows_any)) return fail(RQ_ERR_INVALID, "null argument");
-    RQC(builder_chunk_type_check(b, typed));
-    const float *d_rows = static_cast<const float *>(d_rows_any);
+static rq_status builder_assign(rq_builder *b, const RowsIn rows, uint64_t i0, uint64_t m) {
+    if (!b || (m && !rows.p)) return fail(RQ_ERR_INVALID, "null argument");
+    RQC(builder_chunk_type_check(b, rows.typed_call));
     if (b->refused) return fail(RQ_ERR_INVALID, "a chunk of this builder was refused: it can only be freed");
     if (b->ordered) return fail(RQ_ERR_INVALID, "rq_builder_assign_chunk after rq_builder_order");
     rq_index *idx = b->idx.get();
@@ -508,15 +501,15 @@ static rq_status builder_assign(rq_builder *b, const void *d_rows_any, uint64_t 
     const uint32_t d = b->d, dim = idx->dim;
     for (uint64_t c0 = 0; c0 < m; c0 += RQ_BUILD_CHUNK) {
         const uint64_t mm = std::min<uint64_t>(RQ_BUILD_CHUNK, m - c0), at = i0 + c0;
-        const float *src, *in = d_rows + c0 * d;
-        if (typed) {  // W(chunk) into the staging buffer: everything behind it is the f32 build's
-            launch_widen(static_cast<const uint8_t *>(d_rows_any) + c0 * d * idx->row_elem_bytes(), idx->row_type, mm * d, b->wide.p);
+        const float *src, *in = static_cast<const float *>(rows.at(c0 * d));
+        if (rows.typed_call) {  // W(chunk) into the staging buffer: everything behind it is the f32 build's
+            launch_widen(rows.at(c0 * d), idx->rows, mm * d, b->wide.p);
             in = b->wide.p;
         }
         RQC(transform_rows(idx->metric, dim, in, mm, d, at, b->xpad.p, nullptr, BaseView{}, b->ip_s_pre, b->ip_bad.p, &src));
         // a cosine index stores R_t(N(W(h))): rotation, assignment and quantisation see the rounded rows (src is xpad here)
-        if (typed && idx->metric.id == RQ_METRIC_COSINE)
-            round_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(mm * dim, 256), 1u << 20), 256>>>(b->xpad.p, idx->row_type, mm * dim);
+        if (rows.typed_call && idx->metric.id == RQ_METRIC_COSINE)
+            round_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(mm * dim, 256), 1u << 20), 256>>>(b->xpad.p, idx->rows.id, mm * dim);
         HIPC(hipEventRecord(b->ev[0], nullptr));
         launch_rotate(src, idx->P.p, b->xrot.p, mm, dim, true, nullptr);
         HIPC(hipEventRecord(b->ev[1], nullptr));
@@ -550,7 +543,7 @@ static rq_status builder_order(rq_builder *b) {
     const uint32_t k = idx->k;
     if (b->assigned != n) return fail(RQ_ERR_INVALID, "rq_builder_order before every row was assigned");
     // (a half-precision cosine builder normalises its chunks into xpad again in pass 2; `wide` stays for both passes)
-    if (!(idx->row_type && idx->metric.id == RQ_METRIC_COSINE)) b->xpad.release(), b->wide.release();
+    if (!(idx->rows.typed() && idx->metric.id == RQ_METRIC_COSINE)) b->xpad.release(), b->wide.release();
     b->xrot.release();
     {
         AssignAux &ax = b->assign_aux;
@@ -593,45 +586,41 @@ static rq_status builder_order(rq_builder *b) {
 }
 
 // pass 2 for rows [i0, i0 + m)
-static rq_status builder_place(rq_builder *b, const void *d_rows_any, uint64_t i0, uint64_t m, bool typed = false) {
-    if (!b || (m && !d_rows_any)) return fail(RQ_ERR_INVALID, "null argument");
-    RQC(builder_chunk_type_check(b, typed));
-    const float *d_rows = static_cast<const float *>(d_rows_any);
+static rq_status builder_place(rq_builder *b, const RowsIn rows, uint64_t i0, uint64_t m) {
+    if (!b || (m && !rows.p)) return fail(RQ_ERR_INVALID, "null argument");
+    RQC(builder_chunk_type_check(b, rows.typed_call));
     if (b->refused) return fail(RQ_ERR_INVALID, "a chunk of this builder was refused: it can only be freed");
     if (!b->ordered) return fail(RQ_ERR_INVALID, "rq_builder_place_chunk before rq_builder_order");
     rq_index *idx = b->idx.get();
     if (i0 > idx->n || m > idx->n - i0) return fail(RQ_ERR_INVALID, "chunk outside [0, n)");
     if (!b->cov_place.add(i0, m)) return fail(RQ_ERR_INVALID, "rq_builder_place_chunk: rows [" + std::to_string(i0) + ", " + std::to_string(i0 + m) + ") overlap rows already placed");
-    if (m && typed && idx->byte_rows()) {  // one-byte elements go to the row's final position as they are (L2 only)
-        place_byte_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(m, 4), 1u << 20), 256>>>(static_cast<const uint8_t *>(d_rows_any), i0, m, b->d, idx->dim,
-                                                                                              b->pos_of_id.p, reinterpret_cast<uint8_t *>(idx->base.p));
-        HIPC(hipDeviceSynchronize());  // the caller may reuse d_rows right away
-        HIPC(hipGetLastError());
-    } else if (m && typed) {
-        // L2: the 2-byte elements go to the row's final position as they are; cosine: the chunk is widened and normalised as in
-        // pass 1 (the same kernels, the same bits) and narrowed with R_t where it is stored
-        const uint16_t *rows = static_cast<const uint16_t *>(d_rows_any);
-        uint16_t *out = reinterpret_cast<uint16_t *>(idx->base.p);
-        const uint32_t d = b->d, dim = idx->dim;
-        if (idx->metric.id != RQ_METRIC_COSINE) {
-            place_half_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(m, 4), 1u << 20), 256>>>(rows, i0, m, d, dim, b->pos_of_id.p, out);
-        } else {
-            for (uint64_t c0 = 0; c0 < m; c0 += RQ_BUILD_CHUNK) {
-                const uint64_t mm = std::min<uint64_t>(RQ_BUILD_CHUNK, m - c0);
-                launch_widen(rows + c0 * d, idx->row_type, mm * d, b->wide.p);
-                RQC(transform_rows(idx->metric, dim, b->wide.p, mm, d, i0 + c0, b->xpad.p, nullptr, BaseView{}, nullptr, nullptr));
-                place_narrow_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(mm, 4), 1u << 20), 256>>>(b->xpad.p, i0 + c0, mm, dim, idx->row_type,
-                                                                                                       b->pos_of_id.p, out);
-            }
-        }
-        HIPC(hipDeviceSynchronize());  // the caller may reuse d_rows right away
-        HIPC(hipGetLastError());
+    if (m && rows.typed_call && idx->metric.id != RQ_METRIC_COSINE) {
+        // copied as they are (byte rows, L2 half-precision rows): the elements go to the row's final position unchanged
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(ceil_div(m, 4), 1u << 20);
+        if (idx->rows.bytes())
+            place_typed_rows_kernel<<<grid, 256>>>(static_cast<const uint8_t *>(rows.p), i0, m, b->d, idx->dim, b->pos_of_id.p, reinterpret_cast<uint8_t *>(idx->base.p));
+        else
+            place_typed_rows_kernel<<<grid, 256>>>(static_cast<const uint16_t *>(rows.p), i0, m, b->d, idx->dim, b->pos_of_id.p, reinterpret_cast<uint16_t *>(idx->base.p));
+    } else if (m && !rows.typed_call) {
+        // transformed, then stored: the same transform as pass 1, stored at the row's final position (inner product: a caller feeding
+        // other rows than it did then is refused) ...
+        RQC(transform_rows(idx->metric, idx->dim, rows.f32(), m, b->d, i0, nullptr, b->pos_of_id.p, idx->view(), b->ip_s_pre, b->ip_bad.p));
     } else if (m) {
-        // the same transform as pass 1, stored at the row's final position (inner product: a caller feeding other rows than it did then is refused)
-        RQC(transform_rows(idx->metric, idx->dim, d_rows, m, b->d, i0, nullptr, b->pos_of_id.p, idx->view(), b->ip_s_pre, b->ip_bad.p));
-        HIPC(hipDeviceSynchronize());  // the caller may reuse d_rows right away
+        // ... cosine half-precision rows: the chunk is widened and normalised as in pass 1 (the same kernels, the same bits) and
+        // narrowed with R_t where it is stored
+        const uint32_t d = b->d, dim = idx->dim;
+        for (uint64_t c0 = 0; c0 < m; c0 += RQ_BUILD_CHUNK) {
+            const uint64_t mm = std::min<uint64_t>(RQ_BUILD_CHUNK, m - c0);
+            launch_widen(rows.at(c0 * d), idx->rows, mm * d, b->wide.p);
+            RQC(transform_rows(idx->metric, dim, b->wide.p, mm, d, i0 + c0, b->xpad.p, nullptr, BaseView{}, nullptr, nullptr));
+            place_narrow_rows_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(mm, 4), 1u << 20), 256>>>(b->xpad.p, i0 + c0, mm, dim, idx->rows.id, b->pos_of_id.p,
+                                                                                                   reinterpret_cast<uint16_t *>(idx->base.p));
+        }
+    }
+    if (m) {
+        HIPC(hipDeviceSynchronize());  // the caller may reuse the rows right away
         HIPC(hipGetLastError());
-        RQC(builder_rows_check(b));
+        RQC(builder_rows_check(b));  // (a metric that refuses rows has no typed rows)
     }
     b->placed += m;
     return RQ_OK;
@@ -678,29 +667,27 @@ static rq_status ip_resolve_bound(const float *d_x, uint64_t n, uint32_t d, floa
 }
 
 // The one-shot build from device-resident rows: the five builder calls.  An inner-product build first resolves its bound.
-// row_type: d_base holds n x d elements of that type (the chunks then go through the typed calls).
-static rq_status build_device(const void *d_base_any, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, uint32_t cent_cols,
-                              const float *orthogonal_host, uint64_t seed, MetricSpec metric, rq_index **out, uint32_t row_type = RQ_ROWS_F32) {
+// base: n x d elements of its row type (typed rows: the chunks then go through the typed calls).
+static rq_status build_device(const RowsIn base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, uint32_t cent_cols,
+                              const float *orthogonal_host, uint64_t seed, MetricSpec metric, rq_index **out) {
     if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
     *out = nullptr;
-    RQC(row_type_check(row_type, metric));
-    const float *d_base = static_cast<const float *>(d_base_any);
-    const bool typed = row_type != RQ_ROWS_F32;
-    if (n && !d_base) return fail(RQ_ERR_INVALID, "bad build arguments");
+    RQC(row_type_check(base.type, metric));
+    if (n && !base.p) return fail(RQ_ERR_INVALID, "bad build arguments");
     DevBuf<float> s;  // inner product: computed once -- the bound, the validity of every row and slot d of both passes come from it
     if (metric.id == RQ_METRIC_IP) {
         RQC(ensure_device());
         RQC(ip_d_check(d));
         RQC(s.alloc(n));
-        RQC(ip_resolve_bound(d_base, n, d, &metric.S, s.p));
+        RQC(ip_resolve_bound(base.f32(), n, d, &metric.S, s.p));
     }
     rq_builder *b = nullptr;
-    RQC(builder_create(n, d, d_centroids, k, orthogonal_host, seed, 0, metric, cent_cols, &b, row_type));
+    RQC(builder_create(n, d, d_centroids, k, orthogonal_host, seed, 0, metric, base.type, cent_cols, &b));
     std::unique_ptr<rq_builder> guard(b);
     if (metric.id == RQ_METRIC_IP) b->ip_s_pre = s.p;
-    RQC(builder_assign(b, d_base_any, 0, n, typed));
+    RQC(builder_assign(b, base, 0, n));
     RQC(builder_order(b));
-    RQC(builder_place(b, d_base_any, 0, n, typed));
+    RQC(builder_place(b, base, 0, n));
     return builder_finish(guard.release(), out);
 }
 
@@ -746,13 +733,11 @@ static rq_status write_record(FILE *f, const void *data, uint32_t count, size_t 
 }
 
 static rq_status copy_base_rows(const rq_index *idx, uint64_t i0, uint64_t m, float *buf, bool to_index);
-// row_type: `base` holds n x dim elements of that type, stored as they are
-static rq_status from_arrays(uint32_t dim, uint64_t n, uint32_t k, const void *base_any, const float *orthogonal,
+// base: n x dim elements of its row type, typed rows stored as they are
+static rq_status from_arrays(uint32_t dim, uint64_t n, uint32_t k, const RowsIn base, const float *orthogonal,
                              const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
-                             const uint64_t *codes, const rq_factor_t *factors, const MetricSpec &metric, rq_index **out,
-                             uint32_t row_type = RQ_ROWS_F32) {
-    const float *base = static_cast<const float *>(base_any);
-    RQC(row_type_check(row_type, metric));
+                             const uint64_t *codes, const rq_factor_t *factors, const MetricSpec &metric, rq_index **out) {
+    RQC(row_type_check(base.type, metric));
     RQC(ensure_device());
     RQC(ensure_kernel_attributes());
     if (!out) return fail(RQ_ERR_INVALID, "null out pointer");
@@ -764,11 +749,11 @@ static rq_status from_arrays(uint32_t dim, uint64_t n, uint32_t k, const void *b
             return fail(RQ_ERR_DIM_MISMATCH, "inner-product index: dim " + std::to_string(dim) + " is not ceil64(d + 1) for d = " + std::to_string(metric.d));
         if (!ip_bound_ok(metric.S)) return fail(RQ_ERR_INVALID, "inner-product index: sq_bound must be finite and >= 0");
     }
-    if (!orthogonal || !centroids || !offsets || (n && (!base || !map_ids || !codes || !factors)))
+    if (!orthogonal || !centroids || !offsets || (n && (!base.p || !map_ids || !codes || !factors)))
         return fail(RQ_ERR_INVALID, "null array");
     if (n >= 0xFFFFFFFFull) return fail(RQ_ERR_UNSUPPORTED, "n must fit u32");
     std::unique_ptr<rq_index> idx(new rq_index());
-    idx->dim = dim, idx->n = n, idx->k = k, idx->W = dim / 64, idx->metric = metric, idx->row_type = row_type;
+    idx->dim = dim, idx->n = n, idx->k = k, idx->W = dim / 64, idx->metric = metric, idx->rows = base.type;
     RQC(idx->P.alloc((size_t)dim * dim));
     RQC(idx->centroids.alloc((size_t)k * dim));
     RQC(idx->offsets.alloc((size_t)k + 1));
@@ -780,8 +765,8 @@ static rq_status from_arrays(uint32_t dim, uint64_t n, uint32_t k, const void *b
     if (k && offsets[k] != n) return fail(RQ_ERR_INVALID, "offsets[k] != n");
     RQC(alloc_base_tiers(idx.get(), 0, offsets));
     if (n) {
-        if (row_type) HIPC(hipMemcpy(idx->base.p, base_any, n * idx->row_bytes(), hipMemcpyHostToDevice));
-        else RQC(copy_base_rows(idx.get(), 0, n, const_cast<float *>(base), /*to_index=*/true));
+        if (base.type.typed()) HIPC(hipMemcpy(idx->base.p, base.p, n * idx->row_bytes(), hipMemcpyHostToDevice));
+        else RQC(copy_base_rows(idx.get(), 0, n, const_cast<float *>(base.f32()), /*to_index=*/true));
         HIPC(hipMemcpy(idx->map_ids.p, map_ids, n * 4, hipMemcpyHostToDevice));
         HIPC(hipMemcpy(idx->codes.p, codes, n * idx->W * 8, hipMemcpyHostToDevice));
         HIPC(hipMemcpy(idx->factors.p, factors, n * 16, hipMemcpyHostToDevice));
@@ -794,18 +779,20 @@ static rq_status from_arrays(uint32_t dim, uint64_t n, uint32_t k, const void *b
     return RQ_OK;
 }
 
-// rows and centroid records (k x cent_cols) in host memory: staged once, then the device build
-static rq_status build_host(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k, uint32_t cent_cols,
+// rows (of any row type, staged as they are: no f32 image of typed rows is made) and centroid records (k x cent_cols) in host
+// memory: staged once, then the device build
+static rq_status build_host(const RowsIn base, uint64_t n, uint32_t d, const float *centroids, uint32_t k, uint32_t cent_cols,
                             const float *orthogonal, uint64_t seed, const MetricSpec &metric, rq_index **out) {
     RQC(ensure_device());
     if (out) *out = nullptr;
-    if ((n && !base) || !centroids) return fail(RQ_ERR_INVALID, "null argument");
+    if ((n && !base.p) || !centroids) return fail(RQ_ERR_INVALID, "null argument");
     if (metric.id == RQ_METRIC_IP) RQC(ip_d_check(d));
     if (!metric_centroid_cols_ok(metric, d, cent_cols)) return fail(RQ_ERR_INVALID, "centroid_cols outside [d, ceil64(d + 1)]");
-    DevBuf<float> db, dc;
-    RQC(db.upload(base, n * d));
+    DevBuf<uint8_t> db;
+    DevBuf<float> dc;
+    RQC(db.upload(static_cast<const uint8_t *>(base.p), base.type.row_bytes(d) * n));
     RQC(dc.upload(centroids, (size_t)k * cent_cols));
-    return build_device(db.p, n, d, dc.p, k, cent_cols, orthogonal, seed, metric, out);
+    return build_device(RowsIn::of(db.p, base.type), n, d, dc.p, k, cent_cols, orthogonal, seed, metric, out);
 }
 // base.fvecs + centroids.fvecs (rabitq.rs:160-165); the row length is the base file's, the centroid records' what the metric takes for it
 static rq_status build_from_path(const char *base_fvecs, const char *centroid_fvecs, const float *orthogonal, uint64_t seed,
@@ -823,7 +810,7 @@ static rq_status build_from_path(const char *base_fvecs, const char *centroid_fv
     if (metric.id == RQ_METRIC_IP) metric.d = d;
     if ((metric.id == RQ_METRIC_IP && !ip_d_ok(d)) || !metric_centroid_cols_ok(metric, d, cc))
         return fail(RQ_ERR_DIM_MISMATCH, "base and centroid dimensions differ (rabitq.rs:165; an inner-product build: centroid records hold between d and ceil64(d + 1) values)");
-    return build_host(reinterpret_cast<const float *>(b.data.data()), b.lens.size(), d, reinterpret_cast<const float *>(c.data.data()),
+    return build_host(RowsIn::plain(reinterpret_cast<const float *>(b.data.data())), b.lens.size(), d, reinterpret_cast<const float *>(c.data.data()),
                       (uint32_t)c.lens.size(), cc, orthogonal, seed, metric, out);
 }
 
@@ -1022,29 +1009,21 @@ static rq_status copy_base_rows(const rq_index *idx, uint64_t i0, uint64_t m, fl
     std::vector<uint32_t> planes;  // split rows (common.h): transcoded here, on the host -- this is the dump / load path
     auto dev_copy = [&](uint64_t dev_row, uint64_t rows, float *hp) -> rq_status {
         if (!rows) return RQ_OK;
-        if (idx->row_type) {  // half-precision rows: widened (narrowed with R_t) here, on the host, in pieces
+        if (idx->rows.typed()) {  // typed rows: widened (narrowed with R_t) here, on the host, in pieces
+            const RowSpec rs = idx->rows;
             const uint64_t piece = std::max<uint64_t>(1, (64ull << 20) / dim);
-            std::vector<uint16_t> typed;
-            uint16_t *dev = reinterpret_cast<uint16_t *>(idx->base.p);
+            std::vector<uint8_t> typed;
             for (uint64_t r0 = 0; r0 < rows; r0 += piece) {
                 const uint64_t nr = std::min(piece, rows - r0), cells = nr * dim;
-                typed.resize(cells);
+                typed.resize(cells * rs.elem_bytes());
                 float *h = hp + r0 * dim;
-                if (idx->byte_rows()) {  // (one byte per cell: the lower half of the staging vector)
-                    uint8_t *tb = reinterpret_cast<uint8_t *>(typed.data()), *devb = reinterpret_cast<uint8_t *>(idx->base.p) + (dev_row + r0) * dim;
-                    if (to_index) {
-                        for (uint64_t e = 0; e < cells; ++e) tb[e] = rq_narrow_byte(h[e], idx->row_type);
-                        HIPC(hipMemcpy(devb, tb, cells, hipMemcpyHostToDevice));
-                    } else {
-                        HIPC(hipMemcpy(tb, devb, cells, hipMemcpyDeviceToHost));
-                        for (uint64_t e = 0; e < cells; ++e) h[e] = rq_widen_byte(tb[e], idx->row_type);
-                    }
-                } else if (to_index) {
-                    for (uint64_t e = 0; e < cells; ++e) typed[e] = rq_narrow_elem(h[e], idx->row_type);
-                    HIPC(hipMemcpy(dev + (dev_row + r0) * dim, typed.data(), cells * 2, hipMemcpyHostToDevice));
+                uint8_t *dev = reinterpret_cast<uint8_t *>(idx->base.p) + (dev_row + r0) * rs.row_bytes(idx->dim);
+                if (to_index) {
+                    for (uint64_t e = 0; e < cells; ++e) rs.narrow(typed.data(), e, h[e]);
+                    HIPC(hipMemcpy(dev, typed.data(), typed.size(), hipMemcpyHostToDevice));
                 } else {
-                    HIPC(hipMemcpy(typed.data(), dev + (dev_row + r0) * dim, cells * 2, hipMemcpyDeviceToHost));
-                    for (uint64_t e = 0; e < cells; ++e) h[e] = rq_widen_elem(typed[e], idx->row_type);
+                    HIPC(hipMemcpy(typed.data(), dev, typed.size(), hipMemcpyDeviceToHost));
+                    for (uint64_t e = 0; e < cells; ++e) h[e] = rs.widen(typed.data(), e);
                 }
             }
             return RQ_OK;

@@ -54,7 +54,7 @@ static rq_status mutate_refusals(const rq_index *idx) {
     if (!idx) return fail(RQ_ERR_INVALID, "null index");
     if (idx->base_host) return fail(RQ_ERR_UNSUPPORTED, "the raw vectors of this index are tiered (HBM + pinned host memory): it cannot be mutated");
     if (idx->split_rows) return fail(RQ_ERR_UNSUPPORTED, "the raw vectors of this index are stored as split rows: it cannot be mutated");
-    if (idx->row_type) return fail(RQ_ERR_UNSUPPORTED, "the raw vectors of this index are half-precision or byte rows: it cannot be mutated");
+    if (idx->rows.typed()) return fail(RQ_ERR_UNSUPPORTED, "the raw vectors of this index are half-precision or byte rows: it cannot be mutated");
     if (idx->is_shard) return fail(RQ_ERR_UNSUPPORTED, "a shard made by rq_shard_index cannot be mutated (its ids are global)");
     if (idx->dim > 4096) return fail(RQ_ERR_UNSUPPORTED, "dim > 4096 not supported");
     if (idx->open_tickets.load()) return fail(RQ_ERR_INVALID, "a rq_query_batch_device_begin ticket of this index has not ended");
@@ -99,7 +99,7 @@ static rq_status new_rows_prepare(const rq_index *idx, const float *d_rows, uint
     HIPC(hipMemcpy(bx->centroids.p, idx->centroids.p, (size_t)k * dim * 4, hipMemcpyDeviceToDevice));
     HIPC(hipMemcpy(bx->cent_t.p, idx->cent_t.p, (size_t)k * dim * 4, hipMemcpyDeviceToDevice));
     RQC(builder_alloc_pass1(b));
-    RQC(builder_assign(b, d_rows, 0, m));
+    RQC(builder_assign(b, RowsIn::plain(d_rows), 0, m));
     b->xpad.release();
     b->xrot.release();
     DevBuf<uint32_t> cnt;

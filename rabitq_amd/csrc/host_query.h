@@ -562,15 +562,19 @@ struct Pass {
     // sort_runs_mid_kernel's bitmap words; scan_debug bit 2048 (test hook): none, so long directories take the fall-back orderings
     uint32_t mid_lds_words() const { return (pl.dbg & 2048) ? 0u : RQ_SORT_MID_LDS_WORDS; }
 
-    // the row kind of the index: which of the rerank kernels' twins a launch takes
-    int row_kind() const { return idx->row_type == RQ_ROWS_F32 ? ROW_KIND_F32 : idx->byte_rows() ? ROW_KIND_BYTE : ROW_KIND_HALF; }
+    // the exact rerank of every survivor by the whole chip (grid (gx, nq)), reading the index's rows as they are stored
+    void launch_accurate(uint32_t gx, const QSeg &seg, const uint32_t *order) {
+        with_row_kind(idx->rows.kind(), [&](auto row_kind) {
+            accurate_kernel<decltype(row_kind)::value><<<dim3(gx, nq), 256, (size_t)dim * sizeof(float), st>>>(ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim,
+                                                                                                            order, probe_cluster, nprobe);
+        });
+    }
 
     // small batch: one fused launch per stage (launch-bound regime)
     void stage_finish_small(StageRun &r) {
         const QSeg &seg = r.seg;
         pf.begin(PF_RERANK);
         const uint32_t fin_threads = nq <= 16 ? 1024u : 256u;  // a handful of queries: more lanes on each one's rerank
-        const int kind = row_kind();  // the kernels whose rerank reads the index's rows (kernels_rerank.h: accurate_rows<KIND>)
         // survivor buffers beyond the default mean this index / these queries leave long run directories (overflow
         // re-runs, loose thresholds): those are ordered by the slot-bucketed kernel first; the fused kernel then sorts
         // only what fits its LDS
@@ -585,24 +589,24 @@ struct Pass {
             // a handful of queries: their final-stage survivors (~1000 rows each) are gathered by the whole chip -- one block
             // per query would pull them through a single CU's memory pipeline (~30 GB/s)
             if (nq <= 32) {
-                auto accurate = kind == ROW_KIND_BYTE ? accurate_byte_kernel : kind == ROW_KIND_HALF ? accurate_half_kernel : accurate_kernel;
-                accurate<<<dim3(std::max(1u, std::min(16u, 256u / nq)), nq), 256, (size_t)dim * sizeof(float), st>>>(
-                    ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, nullptr, probe_cluster, nprobe);
+                launch_accurate(std::max(1u, std::min(16u, 256u / nq)), seg, nullptr);
                 flags |= 2u;
             }
-            auto finish = kind == ROW_KIND_BYTE   ? (topk < 64 ? sb_finish_byte_kernel<true> : sb_finish_byte_kernel<false>)
-                          : kind == ROW_KIND_HALF ? (topk < 64 ? sb_finish_half_kernel<true> : sb_finish_half_kernel<false>)
-                                                  : (topk < 64 ? sb_finish_kernel<true> : sb_finish_kernel<false>);
-            finish<<<nq, fin_threads, (size_t)dim * sizeof(float) + (2 * RQ_SBF_RUNS + RQ_SBF_RECS) * 16, st>>>(
-                ws.surv.p, ws.runs.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, topk, rs, probe_cluster, nprobe, flags,
-                idx->map_ids.p, io.out_dist, io.out_id, io.out_n, ws.rough_cnt.p, ws.totals.p);
+            with_row_kind(idx->rows.kind(), [&](auto row_kind) {  // the kernels whose rerank reads the index's rows (kernels_rerank.h: accurate_rows<KIND>)
+                constexpr int K = decltype(row_kind)::value;
+                auto finish = topk < 64 ? sb_finish_kernel<true, K> : sb_finish_kernel<false, K>;
+                finish<<<nq, fin_threads, (size_t)dim * sizeof(float) + (2 * RQ_SBF_RUNS + RQ_SBF_RECS) * 16, st>>>(
+                    ws.surv.p, ws.runs.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, topk, rs, probe_cluster, nprobe, flags,
+                    idx->map_ids.p, io.out_dist, io.out_id, io.out_n, ws.rough_cnt.p, ws.totals.p);
+            });
             sb_results_done = true;
         } else {
-            auto finish = kind == ROW_KIND_BYTE   ? (qp.heuristic ? stage_finish_byte_kernel<true> : stage_finish_byte_kernel<false>)
-                          : kind == ROW_KIND_HALF ? (qp.heuristic ? stage_finish_half_kernel<true> : stage_finish_half_kernel<false>)
-                                                  : (qp.heuristic ? stage_finish_kernel<true> : stage_finish_kernel<false>);
-            finish<<<nq, fin_threads, (size_t)dim * sizeof(float), st>>>(ws.surv.p, ws.runs.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, topk, rs,
-                                                                         probe_cluster, nprobe, flags);
+            with_row_kind(idx->rows.kind(), [&](auto row_kind) {
+                constexpr int K = decltype(row_kind)::value;
+                auto finish = qp.heuristic ? stage_finish_kernel<true, K> : stage_finish_kernel<false, K>;
+                finish<<<nq, fin_threads, (size_t)dim * sizeof(float), st>>>(ws.surv.p, ws.runs.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, topk, rs,
+                                                                             probe_cluster, nprobe, flags);
+            });
         }
         pf.end();
     }
@@ -639,15 +643,8 @@ struct Pass {
         else if (idx->split_rows && prefilter)  // tiered: the rows' own first plane is the pre-filter
             accurate_split_kernel<<<dim3(gx, nq), 256, (size_t)dim * sizeof(float) + (nprobe <= RQ_ACC8_LDS_PROBES ? (size_t)nprobe * 16 : 0), st>>>(
                 ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim, rerank_order, ws.thr.p, probe_cluster, nprobe, ws.nshadow.p);
-        else if (row_kind() == ROW_KIND_BYTE)  // byte rows: every survivor reads its dim-byte row (no shadow rows, no first plane)
-            accurate_byte_kernel<<<dim3(gx, nq), 256, (size_t)dim * sizeof(float), st>>>(ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim,
-                                                                                         rerank_order, probe_cluster, nprobe);
-        else if (idx->row_type)  // half-precision rows: every survivor reads its 2*dim-byte row
-            accurate_half_kernel<<<dim3(gx, nq), 256, (size_t)dim * sizeof(float), st>>>(ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim,
-                                                                                         rerank_order, probe_cluster, nprobe);
-        else
-            accurate_kernel<<<dim3(gx, nq), 256, (size_t)dim * sizeof(float), st>>>(ws.surv.p, ws.surv_cnt.p, seg, idx->view(), qpad, dim,
-                                                                                    rerank_order, probe_cluster, nprobe);
+        else  // every survivor reads its row: 4*dim bytes, or the 2*dim / dim bytes of a half-precision / byte row (no shadow rows, no first plane)
+            launch_accurate(gx, seg, rerank_order);
         if (qp.range)  // every survivor has its exact distance (or +inf: proven outside the radius): count the hits, nothing to order
             range_count_kernel<<<ceil_div(nq, 4), 256, 0, st>>>(ws.surv.p, ws.surv_cnt.p, qp.cap, ws.thr.p, nq, ws.range_hits.p, ws.need.p,
                                                                 ws.ovf.p, ws.precise.p, ws.nsurv.p);

@@ -45,7 +45,7 @@ rq_status rq_shard_index(const rq_index *idx, const uint32_t *owner, uint32_t ra
     noff[k] = (uint32_t)n_local;
     std::unique_ptr<rq_index> sh(new rq_index());
     sh->dim = dim, sh->k = k, sh->n = n_local, sh->W = idx->W;
-    sh->is_shard = true, sh->metric = idx->metric, sh->row_type = idx->row_type;
+    sh->is_shard = true, sh->metric = idx->metric, sh->rows = idx->rows;
     RQC(sh->P.alloc((size_t)dim * dim));
     RQC(sh->centroids.alloc((size_t)k * dim));
     RQC(sh->offsets.alloc((size_t)k + 1));

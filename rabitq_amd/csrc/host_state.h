@@ -275,14 +275,12 @@ struct rq_index {
     DevBuf<ListTier> list_tier;      // k entries, tiered indexes only
     std::vector<ListTier> h_list_tier;
     bool split_rows = false;         // the raw vectors are split rows (common.h; set with the tiers, tiered indexes only)
-    // RQ_ROWS_*: a half-precision index keeps the caller's 2-byte elements in `base` (n x dim of them, 2*dim bytes per row, padding
+    // the row type (rows.h): a half-precision index keeps the caller's 2-byte elements in `base` (n x dim of them, 2*dim bytes per row, padding
     // +0), a byte-row index (RQ_ROWS_U8 / RQ_ROWS_I8) the caller's one-byte elements (dim bytes per row, padding 0x00): always
     // untiered, never split, no shadow rows, never mutated
-    uint32_t row_type = RQ_ROWS_F32;
-    bool byte_rows() const { return rq_rows_are_bytes(row_type); }
-    size_t row_elem_bytes() const { return row_type == RQ_ROWS_F32 ? 4 : byte_rows() ? 1 : 2; }
-    size_t row_bytes() const { return (size_t)dim * row_elem_bytes(); }
-    BaseView view() const { return BaseView{base.p, base_host_dev, list_tier.p, k, split_rows ? 1u : 0u, row_type}; }
+    RowSpec rows;
+    size_t row_bytes() const { return rows.row_bytes(dim); }
+    BaseView view() const { return BaseView{base.p, base_host_dev, list_tier.p, k, split_rows ? 1u : 0u, rows.id}; }
     ~rq_index() {
         if (base_host) (void)hipHostFree(base_host);
     }
@@ -422,7 +420,7 @@ __global__ __launch_bounds__(256) void shard_gather_kernel(const uint32_t *__res
         }
         const uint64_t src = (uint64_t)old_off[lo] + (p - new_off[lo]);
         const RowRef srow = base_in.row(src, dim), drow = base_out.row(p, dim);
-        if (rq_rows_are_bytes(base_in.fmt) || rq_rows_are_bytes(base_out.fmt)) {  // (a shard inherits the row type: bytes are copied as they are)
+        if (RowSpec{base_in.fmt}.bytes() || RowSpec{base_out.fmt}.bytes()) {  // (a shard inherits the row type: bytes are copied as they are)
             const uint8_t *s = reinterpret_cast<const uint8_t *>(srow.p);
             uint8_t *d = reinterpret_cast<uint8_t *>(const_cast<float *>(drow.p));
             for (uint32_t e = lane; e < dim; e += 64) d[e] = s[e];
@@ -873,6 +871,16 @@ static hipError_t set_scan_mfma_attr() {
 // the filtered instantiations of sb_query_kernel live in a translation unit of their own (inst_small_filt.hip)
 void launch_sb_query_filtered(uint32_t W, int mode, uint32_t nq, size_t dyn, hipStream_t st, const SbArgs &sa);
 hipError_t sb_query_filtered_set_attributes(int bytes);
+// f(integral_constant<KIND>): the run-time row kind (RowSpec::kind) as the constant the rerank kernels are instantiated on
+template <typename F>
+static void with_row_kind(int kind, F &&f) {
+    switch (kind) {
+        case ROW_KIND_BYTE: f(std::integral_constant<int, ROW_KIND_BYTE>{}); break;
+        case ROW_KIND_HALF: f(std::integral_constant<int, ROW_KIND_HALF>{}); break;
+        default: f(std::integral_constant<int, ROW_KIND_F32>{}); break;
+    }
+}
+
 static rq_status ensure_kernel_attributes() {
     static std::once_flag once;
     static hipError_t err = hipSuccess;
@@ -909,12 +917,12 @@ static rq_status ensure_kernel_attributes() {
         set(reinterpret_cast<const void *>(coarse_candidates_kernel<2, 1>), (int)RQ_LDS_PER_BLOCK, "coarse_candidates_kernel<2,1>");
         set(reinterpret_cast<const void *>(coarse_candidates_kernel<3, 1>), (int)RQ_LDS_PER_BLOCK, "coarse_candidates_kernel<3,1>");
         set(reinterpret_cast<const void *>(coarse_candidates_kernel<4, 1>), (int)RQ_LDS_PER_BLOCK, "coarse_candidates_kernel<4,1>");
-        set(reinterpret_cast<const void *>(sb_finish_kernel<true>), 104 * 1024, "sb_finish_kernel");   // (+ 33 KiB of static LDS)
-        set(reinterpret_cast<const void *>(sb_finish_kernel<false>), 104 * 1024, "sb_finish_kernel");  // (+ 49 KiB of static LDS)
-        set(reinterpret_cast<const void *>(sb_finish_half_kernel<true>), 104 * 1024, "sb_finish_half_kernel");
-        set(reinterpret_cast<const void *>(sb_finish_half_kernel<false>), 104 * 1024, "sb_finish_half_kernel");
-        set(reinterpret_cast<const void *>(sb_finish_byte_kernel<true>), 104 * 1024, "sb_finish_byte_kernel");
-        set(reinterpret_cast<const void *>(sb_finish_byte_kernel<false>), 104 * 1024, "sb_finish_byte_kernel");
+        for (int kind : {ROW_KIND_F32, ROW_KIND_HALF, ROW_KIND_BYTE})
+            with_row_kind(kind, [&](auto row_kind) {
+                constexpr int K = decltype(row_kind)::value;
+                set(reinterpret_cast<const void *>(sb_finish_kernel<true, K>), 104 * 1024, "sb_finish_kernel");   // (+ 33 KiB of static LDS)
+                set(reinterpret_cast<const void *>(sb_finish_kernel<false, K>), 104 * 1024, "sb_finish_kernel");  // (+ 49 KiB of static LDS)
+            });
 #define RQ_SBQ_ATTR(WW)                                                                                  \
     set(reinterpret_cast<const void *>(sb_query_kernel<WW, 0, false>), 120 * 1024, "sb_query_kernel");   \
     set(reinterpret_cast<const void *>(sb_query_kernel<WW, 1, false>), 120 * 1024, "sb_query_kernel");   \

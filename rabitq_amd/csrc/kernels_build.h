@@ -449,30 +449,37 @@ __global__ __launch_bounds__(256) void place_rows_kernel(const float *__restrict
 }
 
 // ------------------------------------------------------------------------------------------------
-// Half-precision rows (common.h; row_type of include/rabitq_hip.h): the streamed build widens every typed chunk into a bounded f32
-// staging buffer and runs the f32 kernels of pass 1 on it; pass 2 stores 2-byte rows.  All four kernels are element-wise (the
-// input is only 2-byte aligned), grid-stride, and touch nothing beyond `count` elements / `m` rows.
+// Typed rows (rows.h; row_type of include/rabitq_hip.h): the streamed build widens every typed chunk into a bounded f32 staging
+// buffer and runs the f32 kernels of pass 1 on it; pass 2 stores the rows in their type.  All four kernels are element-wise (the
+// input is only aligned to its element), grid-stride, and touch nothing beyond `count` elements / `m` rows.  E: the stored element,
+// uint16_t (f16 / bf16) or uint8_t (u8 / i8).
 // ------------------------------------------------------------------------------------------------
 // out[i] = W(x[i]) (rq_widen*, the builder's staging)
-__global__ __launch_bounds__(256) void widen_rows_kernel(const uint16_t *__restrict__ x, uint32_t fmt, uint64_t count, float *__restrict__ out) {
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (uint64_t)gridDim.x * 256) out[i] = rq_widen_elem(x[i], fmt);
+template <typename E>
+__global__ __launch_bounds__(256) void widen_rows_kernel(const E *__restrict__ x, uint32_t fmt, uint64_t count, float *__restrict__ out) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (uint64_t)gridDim.x * 256) {
+        if constexpr (sizeof(E) == 1) out[i] = rq_widen_byte(x[i], fmt);
+        else out[i] = rq_widen_elem(x[i], fmt);
+    }
 }
-// x[i] = W(R_t(x[i])): a cosine build's dense normalised rows as the index will store them, ahead of the rotation
+// x[i] = W(R_t(x[i])): a cosine build's dense normalised rows as the index will store them, ahead of the rotation (half-precision
+// only: the cosine metric has no byte rows)
 __global__ __launch_bounds__(256) void round_rows_kernel(float *__restrict__ x, uint32_t fmt, uint64_t count) {
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (uint64_t)gridDim.x * 256)
         x[i] = rq_widen_elem(rq_narrow_elem(x[i], fmt), fmt);
 }
-// place_rows_kernel for typed rows (m x d 2-byte elements, copied as they are, padding +0); one wave per row
-__global__ __launch_bounds__(256) void place_half_rows_kernel(const uint16_t *__restrict__ rows, uint64_t i0, uint64_t m, uint32_t d, uint32_t dim,
-                                                              const uint32_t *__restrict__ pos_of_id, uint16_t *__restrict__ out) {
+// place_rows_kernel for typed rows (m x d elements, copied as they are, padding zero bits); one wave per row
+template <typename E>
+__global__ __launch_bounds__(256) void place_typed_rows_kernel(const E *__restrict__ rows, uint64_t i0, uint64_t m, uint32_t d, uint32_t dim,
+                                                               const uint32_t *__restrict__ pos_of_id, E *__restrict__ out) {
     const uint32_t lane = threadIdx.x & 63;
     for (uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < m; r += (uint64_t)gridDim.x * 4) {
-        uint16_t *w = out + (uint64_t)pos_of_id[i0 + r] * dim;
-        const uint16_t *src = rows + r * d;
-        for (uint32_t e = lane; e < dim; e += 64) w[e] = e < d ? src[e] : (uint16_t)0;
+        E *w = out + (uint64_t)pos_of_id[i0 + r] * dim;
+        const E *src = rows + r * d;
+        for (uint32_t e = lane; e < dim; e += 64) w[e] = e < d ? src[e] : (E)0;
     }
 }
-// the same from dense f32 rows (m x dim, already padded: a cosine build's N(W(h))), narrowed with R_t on the way
+// the same from dense f32 rows (m x dim, already padded: a cosine build's N(W(h))), narrowed with R_t on the way (half-precision only)
 __global__ __launch_bounds__(256) void place_narrow_rows_kernel(const float *__restrict__ rows, uint64_t i0, uint64_t m, uint32_t dim, uint32_t fmt,
                                                                 const uint32_t *__restrict__ pos_of_id, uint16_t *__restrict__ out) {
     const uint32_t lane = threadIdx.x & 63;
@@ -480,21 +487,6 @@ __global__ __launch_bounds__(256) void place_narrow_rows_kernel(const float *__r
         uint16_t *w = out + (uint64_t)pos_of_id[i0 + r] * dim;
         const float *src = rows + r * dim;
         for (uint32_t e = lane; e < dim; e += 64) w[e] = rq_narrow_elem(src[e], fmt);
-    }
-}
-// Byte rows (common.h: RQ_ROWS_U8 / RQ_ROWS_I8): the byte forms of widen_rows_kernel and place_half_rows_kernel, element-wise as
-// well (the input is only 1-byte aligned); L2 only, so there is no rounding and no narrowing placement.
-__global__ __launch_bounds__(256) void widen_byte_rows_kernel(const uint8_t *__restrict__ x, uint32_t fmt, uint64_t count, float *__restrict__ out) {
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (uint64_t)gridDim.x * 256) out[i] = rq_widen_byte(x[i], fmt);
-}
-// m x d one-byte elements copied as they are, padding 0x00; one wave per row
-__global__ __launch_bounds__(256) void place_byte_rows_kernel(const uint8_t *__restrict__ rows, uint64_t i0, uint64_t m, uint32_t d, uint32_t dim,
-                                                              const uint32_t *__restrict__ pos_of_id, uint8_t *__restrict__ out) {
-    const uint32_t lane = threadIdx.x & 63;
-    for (uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < m; r += (uint64_t)gridDim.x * 4) {
-        uint8_t *w = out + (uint64_t)pos_of_id[i0 + r] * dim;
-        const uint8_t *src = rows + r * d;
-        for (uint32_t e = lane; e < dim; e += 64) w[e] = e < d ? src[e] : (uint8_t)0;
     }
 }
 

@@ -97,29 +97,6 @@ __device__ __forceinline__ float ex_pair_bound(float T, float xs, float qs, floa
 }
 __device__ __forceinline__ float ex_margin_factor(uint32_t dim) { return (0.00390625f + (float)(2 * dim + 64) * 5.9604645e-8f) * 1.05f; }
 
-// elements e0 .. e0 + 7 of a stored row, widened exactly
-__device__ __forceinline__ void ex_load8(const RowRef rr, uint32_t e0, float (&v)[8]) {
-    if (rq_rows_are_bytes(rr.fmt)) {
-        const uint2 w = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint8_t *>(rr.p) + e0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[i] = rq_widen_byte((uint8_t)(w.x >> (8 * i)), rr.fmt);
-            v[4 + i] = rq_widen_byte((uint8_t)(w.y >> (8 * i)), rr.fmt);
-        }
-    } else if (rr.fmt) {
-        const uint4 w = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(rr.p) + e0);
-        const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i] = rq_widen_elem((uint16_t)ww[i], rr.fmt);
-            v[2 * i + 1] = rq_widen_elem((uint16_t)(ww[i] >> 16), rr.fmt);
-        }
-    } else {
-        const float4 a = *reinterpret_cast<const float4 *>(rr.p + e0), b = *reinterpret_cast<const float4 *>(rr.p + e0 + 4);
-        v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
-    }
-}
-
 // One wave per query row of the launch (rows nq .. nq32 - 1 are padding: zeros): the bf16 image and the two norm terms.
 __global__ __launch_bounds__(256) void exact_prep_kernel(const ExactArgs a) {
     const uint32_t lane = threadIdx.x & 63, q = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -185,7 +162,7 @@ __global__ __launch_bounds__(256, (RT == 1 ? 1 : 2)) void exact_scan_kernel(cons
                 unsigned char *img = ex_lds + lr * ROWB;
                 for (uint32_t pc = sub; pc < dim / 8; pc += 8) {
                     float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                    if (ok) ex_load8(rr, 8 * pc, v);
+                    if (ok) rq_row_get8(rr, 8 * pc, v);
 #pragma unroll
                     for (int i = 0; i < 8; ++i) s = fmaf(v[i], v[i], s);
                     *reinterpret_cast<uint4 *>(img + 16 * pc) =

@@ -460,34 +460,16 @@ __device__ __forceinline__ void stage_finish_body(SurvRec *__restrict__ surv, Ru
     if (threadIdx.x < 64)                             // (C)
         replay_wave<HEURISTIC>(recs, runs + qat, nruns, topk, b, st, hkey, hid);
 }
-template <bool HEURISTIC>
+// KIND: the row kind of the index, phase (A)'s accurate_rows<KIND> (the launch: with_row_kind).  The body is a function of its own
+// because the kernels were compiled that way: written into the kernel, the same statements schedule differently.
+template <bool HEURISTIC, int KIND>
 __global__ __launch_bounds__(1024) void stage_finish_kernel(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
                                                            unsigned long long *__restrict__ surv_cnt, const QSeg seg,
                                                            const BaseView base,
                                                            const float *__restrict__ qpad, uint32_t dim, uint32_t topk,
                                                            ReplayState st, const uint32_t *__restrict__ probe_cluster,
                                                            uint32_t nprobe, uint32_t presorted) {
-    stage_finish_body<HEURISTIC, ROW_KIND_F32>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted);
-}
-// stage_finish_kernel of a half-precision index: phase (A) reads 2-byte rows (accurate_rows<ROW_KIND_HALF>)
-template <bool HEURISTIC>
-__global__ __launch_bounds__(1024) void stage_finish_half_kernel(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
-                                                                unsigned long long *__restrict__ surv_cnt, const QSeg seg,
-                                                                const BaseView base,
-                                                                const float *__restrict__ qpad, uint32_t dim, uint32_t topk,
-                                                                ReplayState st, const uint32_t *__restrict__ probe_cluster,
-                                                                uint32_t nprobe, uint32_t presorted) {
-    stage_finish_body<HEURISTIC, ROW_KIND_HALF>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted);
-}
-// stage_finish_kernel of a byte-row index: phase (A) reads one-byte rows (accurate_rows<ROW_KIND_BYTE>)
-template <bool HEURISTIC>
-__global__ __launch_bounds__(1024) void stage_finish_byte_kernel(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
-                                                                unsigned long long *__restrict__ surv_cnt, const QSeg seg,
-                                                                const BaseView base,
-                                                                const float *__restrict__ qpad, uint32_t dim, uint32_t topk,
-                                                                ReplayState st, const uint32_t *__restrict__ probe_cluster,
-                                                                uint32_t nprobe, uint32_t presorted) {
-    stage_finish_body<HEURISTIC, ROW_KIND_BYTE>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted);
+    stage_finish_body<HEURISTIC, KIND>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted);
 }
 
 // `runs_src`: where the stage's unsorted descriptors are when not in `runs` itself (an arena stage scatters them into the

@@ -208,18 +208,18 @@ __device__ __forceinline__ float exact_l2_row_f32(const RowRef rr, const float *
 // a half-precision row of either type
 __device__ __forceinline__ float exact_l2_row_half(const RowRef rr, const float *q_lds, uint32_t dim, uint32_t hf) {
     const uint16_t *x = reinterpret_cast<const uint16_t *>(rr.p) + 4 * hf;
-    return rr.fmt == RQ_ROWS_BF16_ ? exact_l2_pair_half<true>(x, q_lds, dim, hf) : exact_l2_pair_half<false>(x, q_lds, dim, hf);
+    return rr.fmt == RQ_ROWS_BF16 ? exact_l2_pair_half<true>(x, q_lds, dim, hf) : exact_l2_pair_half<false>(x, q_lds, dim, hf);
 }
 // a byte row of either type
 template <int ROUND = 4>
 __device__ __forceinline__ float exact_l2_row_byte(const RowRef rr, const float *q_lds, uint32_t dim, uint32_t hf) {
     const uint8_t *x = reinterpret_cast<const uint8_t *>(rr.p);
-    return rr.fmt == RQ_ROWS_I8_ ? exact_l2_pair_byte<true, ROUND>(x, q_lds, dim, hf) : exact_l2_pair_byte<false, ROUND>(x, q_lds, dim, hf);
+    return rr.fmt == RQ_ROWS_I8 ? exact_l2_pair_byte<true, ROUND>(x, q_lds, dim, hf) : exact_l2_pair_byte<false, ROUND>(x, q_lds, dim, hf);
 }
 // a row of any format: the dispatch on RowRef's run-time fields (BYTE_ROUND: exact_l2_pair_byte's ROUND)
 template <int BYTE_ROUND = 4>
 __device__ __forceinline__ float exact_l2_row(const RowRef rr, const float *q_lds, uint32_t dim, uint32_t hf) {
-    if (rq_rows_are_bytes(rr.fmt)) return exact_l2_row_byte<BYTE_ROUND>(rr, q_lds, dim, hf);
+    if (RowSpec{rr.fmt}.bytes()) return exact_l2_row_byte<BYTE_ROUND>(rr, q_lds, dim, hf);
     return rr.fmt ? exact_l2_row_half(rr, q_lds, dim, hf) : exact_l2_row_f32(rr, q_lds, dim, hf);
 }
 
@@ -235,8 +235,7 @@ __device__ __forceinline__ RowRef rerank_row(const BaseView &base, const SurvRec
 // an index is given -- ROW_KIND_HALF / ROW_KIND_BYTE: every row at its position, 2*dim / dim bytes apart, nothing but the row is
 // read.  The launch picks the instantiation from the index's row type, so the f32 kernels' loop -- whose two rounds of loads the
 // compiler issues together -- is compiled exactly as it was without the other formats in it; which of the two types of its kind a
-// row holds stays a run-time field.
-enum { ROW_KIND_F32 = 0, ROW_KIND_HALF = 1, ROW_KIND_BYTE = 2 };
+// row holds stays a run-time field.  (ROW_KIND_*: rows.h.)
 template <int KIND = ROW_KIND_F32>
 __device__ __forceinline__ void accurate_rows(SurvRec *__restrict__ recs, uint32_t n, const BaseView &base,
                                               const float *q_lds, uint32_t dim, uint32_t first, uint32_t step,
@@ -835,10 +834,14 @@ __global__ __launch_bounds__(256, q8_ring_waves(NPC)) void accurate_ring8_kernel
 // ---- the same three phases as separate launches: better for large batches, where all queries'
 // survivors are reranked with full-chip parallelism before the (latency-bound) replay --------------
 // grid (gx, nq); block 256
+// KIND: the row kind of the index (accurate_rows<KIND>); the launch picks the instantiation (host_query.h: with_row_kind)
 template <int KIND>
-__device__ __forceinline__ void accurate_body(SurvRec *__restrict__ surv, const unsigned long long *__restrict__ surv_cnt, const QSeg &seg,
-                                              const BaseView &base, const float *__restrict__ qpad, uint32_t dim,
-                                              const uint32_t *__restrict__ order, const uint32_t *__restrict__ probe_cluster, uint32_t nprobe) {
+__global__ __launch_bounds__(256) void accurate_kernel(SurvRec *__restrict__ surv,
+                                                       const unsigned long long *__restrict__ surv_cnt,
+                                                       const QSeg seg, const BaseView base,
+                                                       const float *__restrict__ qpad, uint32_t dim,
+                                                       const uint32_t *__restrict__ order,
+                                                       const uint32_t *__restrict__ probe_cluster, uint32_t nprobe) {
     // TWO lanes per candidate: lane half hf carries AVX lanes 4hf..4hf+3 (elements 8c + 4hf + 0..3, one
     // 16-byte load per chunk), so a row is fetched with float4 loads; the fold
     // ((a0+a4)+(a1+a5)) + ((a2+a6)+(a3+a7)) needs one exchange between the two lanes.
@@ -851,31 +854,5 @@ __device__ __forceinline__ void accurate_body(SurvRec *__restrict__ surv, const 
     __syncthreads();
     accurate_rows<KIND>(surv + seg.at(b), n, base, acc_q, dim, blockIdx.x * 128 + (threadIdx.x >> 1), gridDim.x * 128,
                         probe_cluster + (uint64_t)b * nprobe);
-}
-__global__ __launch_bounds__(256) void accurate_kernel(SurvRec *__restrict__ surv,
-                                                       const unsigned long long *__restrict__ surv_cnt,
-                                                       const QSeg seg, const BaseView base,
-                                                       const float *__restrict__ qpad, uint32_t dim,
-                                                       const uint32_t *__restrict__ order,
-                                                       const uint32_t *__restrict__ probe_cluster, uint32_t nprobe) {
-    accurate_body<ROW_KIND_F32>(surv, surv_cnt, seg, base, qpad, dim, order, probe_cluster, nprobe);
-}
-// accurate_kernel of a half-precision index (host_query.h launches it wherever that index would get accurate_kernel)
-__global__ __launch_bounds__(256) void accurate_half_kernel(SurvRec *__restrict__ surv,
-                                                            const unsigned long long *__restrict__ surv_cnt,
-                                                            const QSeg seg, const BaseView base,
-                                                            const float *__restrict__ qpad, uint32_t dim,
-                                                            const uint32_t *__restrict__ order,
-                                                            const uint32_t *__restrict__ probe_cluster, uint32_t nprobe) {
-    accurate_body<ROW_KIND_HALF>(surv, surv_cnt, seg, base, qpad, dim, order, probe_cluster, nprobe);
-}
-// accurate_kernel of a byte-row index
-__global__ __launch_bounds__(256) void accurate_byte_kernel(SurvRec *__restrict__ surv,
-                                                            const unsigned long long *__restrict__ surv_cnt,
-                                                            const QSeg seg, const BaseView base,
-                                                            const float *__restrict__ qpad, uint32_t dim,
-                                                            const uint32_t *__restrict__ order,
-                                                            const uint32_t *__restrict__ probe_cluster, uint32_t nprobe) {
-    accurate_body<ROW_KIND_BYTE>(surv, surv_cnt, seg, base, qpad, dim, order, probe_cluster, nprobe);
 }
 

@@ -591,7 +591,9 @@ __device__ __forceinline__ void sb_finish_body(SurvRec *__restrict__ surv, RunRe
     if (threadIdx.x < 64)  // the same wave that wrote the state (and thread 0's counter updates above): program order
         sb_write_results(st, b, b, topk, map_ids, out_dist, out_id, out_n, rough_cnt[b], cap, totals);
 }
-template <bool REGHEAP>
+// KIND: the row kind of the index (accurate_rows<KIND>; the launch: with_row_kind).  (A body function for the reason given at
+// stage_finish_kernel.)
+template <bool REGHEAP, int KIND>
 __global__ __launch_bounds__(1024) void sb_finish_kernel(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
                                                          unsigned long long *__restrict__ surv_cnt, const QSeg seg,
                                                          const BaseView base, const float *__restrict__ qpad, uint32_t dim,
@@ -600,32 +602,6 @@ __global__ __launch_bounds__(1024) void sb_finish_kernel(SurvRec *__restrict__ s
                                                          float *__restrict__ out_dist, uint32_t *__restrict__ out_id,
                                                          uint32_t *__restrict__ out_n, const unsigned long long *__restrict__ rough_cnt,
                                                          unsigned long long *__restrict__ totals) {
-    sb_finish_body<REGHEAP, ROW_KIND_F32>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted, map_ids, out_dist,
-                                   out_id, out_n, rough_cnt, totals);
-}
-// sb_finish_kernel of a half-precision index: its rerank reads 2-byte rows (accurate_rows<ROW_KIND_HALF>)
-template <bool REGHEAP>
-__global__ __launch_bounds__(1024) void sb_finish_half_kernel(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
-                                                              unsigned long long *__restrict__ surv_cnt, const QSeg seg,
-                                                              const BaseView base, const float *__restrict__ qpad, uint32_t dim,
-                                                              uint32_t topk, ReplayState st, const uint32_t *__restrict__ probe_cluster,
-                                                              uint32_t nprobe, uint32_t presorted, const uint32_t *__restrict__ map_ids,
-                                                              float *__restrict__ out_dist, uint32_t *__restrict__ out_id,
-                                                              uint32_t *__restrict__ out_n, const unsigned long long *__restrict__ rough_cnt,
-                                                              unsigned long long *__restrict__ totals) {
-    sb_finish_body<REGHEAP, ROW_KIND_HALF>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted, map_ids, out_dist,
-                                  out_id, out_n, rough_cnt, totals);
-}
-// sb_finish_kernel of a byte-row index: its rerank reads one-byte rows (accurate_rows<ROW_KIND_BYTE>)
-template <bool REGHEAP>
-__global__ __launch_bounds__(1024) void sb_finish_byte_kernel(SurvRec *__restrict__ surv, RunRec *__restrict__ runs,
-                                                              unsigned long long *__restrict__ surv_cnt, const QSeg seg,
-                                                              const BaseView base, const float *__restrict__ qpad, uint32_t dim,
-                                                              uint32_t topk, ReplayState st, const uint32_t *__restrict__ probe_cluster,
-                                                              uint32_t nprobe, uint32_t presorted, const uint32_t *__restrict__ map_ids,
-                                                              float *__restrict__ out_dist, uint32_t *__restrict__ out_id,
-                                                              uint32_t *__restrict__ out_n, const unsigned long long *__restrict__ rough_cnt,
-                                                              unsigned long long *__restrict__ totals) {
-    sb_finish_body<REGHEAP, ROW_KIND_BYTE>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted, map_ids, out_dist,
-                                           out_id, out_n, rough_cnt, totals);
+    sb_finish_body<REGHEAP, KIND>(surv, runs, surv_cnt, seg, base, qpad, dim, topk, st, probe_cluster, nprobe, presorted, map_ids, out_dist, out_id,
+                                  out_n, rough_cnt, totals);
 }

@@ -205,101 +205,99 @@ rq_status rq_ip_radius(const rq_index *idx, const float *queries, uint32_t nq, u
 // (the *_metric entries take no d / S: they refuse RQ_METRIC_IP, and any id they do not know, before anything else)
 rq_status rq_build_device(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
                           const float *orthogonal_host, uint64_t seed, rq_index **out) {
-    return build_device(d_base, n, d, d_centroids, k, d, orthogonal_host, seed, MetricSpec{}, out);
+    return build_device(RowsIn::plain(d_base), n, d, d_centroids, k, d, orthogonal_host, seed, MetricSpec{}, out);
 }
 rq_status rq_build_device_metric(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
                                  const float *orthogonal_host, uint64_t seed, uint32_t metric, rq_index **out) {
     RQC(metric_entry_check(metric));
-    return build_device(d_base, n, d, d_centroids, k, d, orthogonal_host, seed, MetricSpec{metric}, out);
+    return build_device(RowsIn::plain(d_base), n, d, d_centroids, k, d, orthogonal_host, seed, MetricSpec{metric}, out);
 }
 rq_status rq_build_device_ip(const float *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
                              const float *orthogonal_host, uint64_t seed, uint32_t centroid_cols, float sq_bound, rq_index **out) {
-    return build_device(d_base, n, d, d_centroids, k, centroid_cols, orthogonal_host, seed, metric_ip(d, sq_bound), out);
+    return build_device(RowsIn::plain(d_base), n, d, d_centroids, k, centroid_cols, orthogonal_host, seed, metric_ip(d, sq_bound), out);
 }
 
 rq_status rq_builder_create(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
                             uint64_t seed, uint64_t max_device_base_bytes, rq_builder **out) {
-    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, MetricSpec{}, d, out);
+    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, MetricSpec{}, RowSpec{}, d, out);
 }
 rq_status rq_builder_create_metric(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
                                    uint64_t seed, uint64_t max_device_base_bytes, uint32_t metric, rq_builder **out) {
     RQC(metric_entry_check(metric));
-    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, MetricSpec{metric}, d, out);
+    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, MetricSpec{metric}, RowSpec{}, d, out);
 }
 rq_status rq_builder_create_ip(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
                                uint64_t seed, uint64_t max_device_base_bytes, uint32_t centroid_cols, float sq_bound,
                                rq_builder **out) {
-    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, metric_ip(d, sq_bound), centroid_cols, out);
+    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, metric_ip(d, sq_bound), RowSpec{}, centroid_cols, out);
 }
-// ---- half-precision rows: the typed twins of the builds above ----
+// ---- typed rows: the twins of the builds above that take a row type ----
 rq_status rq_build_device_rows(const void *d_base, uint64_t n, uint32_t d, const float *d_centroids, uint32_t k,
                                const float *orthogonal_host, uint64_t seed, uint32_t metric, uint32_t row_type, rq_index **out) {
     if (out) *out = nullptr;
-    RQC(row_type_check(row_type, MetricSpec{metric}));
+    RQC(row_type_check(RowSpec{row_type}, MetricSpec{metric}));
     RQC(metric_entry_check(metric));
-    return build_device(d_base, n, d, d_centroids, k, d, orthogonal_host, seed, MetricSpec{metric}, out, row_type);
+    return build_device(RowsIn::of(d_base, RowSpec{row_type}), n, d, d_centroids, k, d, orthogonal_host, seed, MetricSpec{metric}, out);
 }
 rq_status rq_build_rows(const void *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k, const float *orthogonal,
                         uint64_t seed, uint32_t metric, uint32_t row_type, rq_index **out) {
     if (out) *out = nullptr;
-    RQC(row_type_check(row_type, MetricSpec{metric}));
+    RQC(row_type_check(RowSpec{row_type}, MetricSpec{metric}));
     RQC(metric_entry_check(metric));
-    if (row_type == RQ_ROWS_F32) return build_host(static_cast<const float *>(base), n, d, centroids, k, d, orthogonal, seed, MetricSpec{metric}, out);
-    RQC(ensure_device());
-    if ((n && !base) || !centroids) return fail(RQ_ERR_INVALID, "null argument");
-    DevBuf<uint8_t> db;  // the typed rows are staged as they are: no f32 image of the input is made
-    DevBuf<float> dc;
-    RQC(db.upload(static_cast<const uint8_t *>(base), n * d * (rq_rows_are_bytes(row_type) ? 1 : 2)));
-    RQC(dc.upload(centroids, (size_t)k * d));
-    return build_device(db.p, n, d, dc.p, k, d, orthogonal, seed, MetricSpec{metric}, out, row_type);
+    return build_host(RowsIn::of(base, RowSpec{row_type}), n, d, centroids, k, d, orthogonal, seed, MetricSpec{metric}, out);
 }
 rq_status rq_builder_create_rows(uint64_t n, uint32_t d, const float *d_centroids, uint32_t k, const float *orthogonal_host,
                                  uint64_t seed, uint64_t max_device_base_bytes, uint32_t metric, uint32_t row_type, rq_builder **out) {
     if (out) *out = nullptr;
-    RQC(row_type_check(row_type, MetricSpec{metric}));
+    RQC(row_type_check(RowSpec{row_type}, MetricSpec{metric}));
     RQC(metric_entry_check(metric));
-    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, MetricSpec{metric}, d, out, row_type);
+    return builder_create(n, d, d_centroids, k, orthogonal_host, seed, max_device_base_bytes, MetricSpec{metric}, RowSpec{row_type}, d, out);
 }
-rq_status rq_builder_assign_chunk_rows(rq_builder *b, const void *d_rows, uint64_t i0, uint64_t m) { return builder_assign(b, d_rows, i0, m, true); }
-rq_status rq_builder_place_chunk_rows(rq_builder *b, const void *d_rows, uint64_t i0, uint64_t m) { return builder_place(b, d_rows, i0, m, true); }
+rq_status rq_builder_assign_chunk_rows(rq_builder *b, const void *d_rows, uint64_t i0, uint64_t m) { return builder_assign(b, RowsIn::chunk_rows(b, d_rows), i0, m); }
+rq_status rq_builder_place_chunk_rows(rq_builder *b, const void *d_rows, uint64_t i0, uint64_t m) { return builder_place(b, RowsIn::chunk_rows(b, d_rows), i0, m); }
 rq_status rq_from_arrays_rows(uint32_t dim, uint64_t n, uint32_t k, const void *base, const float *orthogonal, const float *centroids,
                               const uint32_t *offsets, const uint32_t *map_ids, const uint64_t *codes, const rq_factor_t *factors,
                               uint32_t metric, uint32_t row_type, rq_index **out) {
     if (out) *out = nullptr;
-    RQC(row_type_check(row_type, MetricSpec{metric}));
+    RQC(row_type_check(RowSpec{row_type}, MetricSpec{metric}));
     RQC(metric_entry_check(metric));
-    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, MetricSpec{metric}, out, row_type);
+    return from_arrays(dim, n, k, RowsIn::of(base, RowSpec{row_type}), orthogonal, centroids, offsets, map_ids, codes, factors, MetricSpec{metric}, out);
 }
 rq_status rq_row_type(const rq_index *idx, uint32_t *out) {
     if (!idx || !out) return fail(RQ_ERR_INVALID, "null argument");
-    *out = idx->row_type;
+    *out = idx->rows.id;
     return RQ_OK;
+}
+// the row types rq_widen* take: the typed ones
+static rq_status widen_type_check(RowSpec rows) {
+    if (rows.known() && rows.typed()) return RQ_OK;
+    return fail(RQ_ERR_INVALID, "row_type must be RQ_ROWS_F16, RQ_ROWS_BF16, RQ_ROWS_U8 or RQ_ROWS_I8");
 }
 rq_status rq_widen_device(const void *d_x, uint32_t row_type, uint64_t count, float *d_out) {
     RQC(ensure_device());
-    if (row_type == RQ_ROWS_F32 || !row_type_known(row_type)) return fail(RQ_ERR_INVALID, "row_type must be RQ_ROWS_F16, RQ_ROWS_BF16, RQ_ROWS_U8 or RQ_ROWS_I8");
+    RQC(widen_type_check(RowSpec{row_type}));
     if (count && (!d_x || !d_out)) return fail(RQ_ERR_INVALID, "null argument");
-    launch_widen(d_x, row_type, count, d_out);
+    launch_widen(d_x, RowSpec{row_type}, count, d_out);
     HIPC(hipDeviceSynchronize());
     HIPC(hipGetLastError());
     return RQ_OK;
 }
 rq_status rq_widen(const void *x, uint32_t row_type, uint64_t count, float *out) {
     RQC(ensure_device());
-    if (row_type == RQ_ROWS_F32 || !row_type_known(row_type)) return fail(RQ_ERR_INVALID, "row_type must be RQ_ROWS_F16, RQ_ROWS_BF16, RQ_ROWS_U8 or RQ_ROWS_I8");
+    RQC(widen_type_check(RowSpec{row_type}));
     if (count && (!x || !out)) return fail(RQ_ERR_INVALID, "null argument");
     DevBuf<uint8_t> dx;
     DevBuf<float> dout;
-    RQC(dx.upload(static_cast<const uint8_t *>(x), count * (rq_rows_are_bytes(row_type) ? 1 : 2)));
+    RQC(dx.upload(static_cast<const uint8_t *>(x), count * RowSpec{row_type}.elem_bytes()));
     RQC(dout.alloc(count));
     RQC(rq_widen_device(dx.p, row_type, count, dout.p));
     if (count) HIPC(hipMemcpy(out, dout.p, count * 4, hipMemcpyDeviceToHost));
     return RQ_OK;
 }
 
-rq_status rq_builder_assign_chunk(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m) { return builder_assign(b, d_rows, i0, m); }
+rq_status rq_builder_assign_chunk(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m) { return builder_assign(b, RowsIn::plain(d_rows), i0, m); }
 rq_status rq_builder_order(rq_builder *b) { return builder_order(b); }
-rq_status rq_builder_place_chunk(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m) { return builder_place(b, d_rows, i0, m); }
+rq_status rq_builder_place_chunk(rq_builder *b, const float *d_rows, uint64_t i0, uint64_t m) { return builder_place(b, RowsIn::plain(d_rows), i0, m); }
 rq_status rq_builder_finish(rq_builder *b, rq_index **out) { return builder_finish(b, out); }
 void rq_builder_free(rq_builder *b) { delete b; }
 rq_status rq_builder_stats(const rq_builder *b, rq_build_stats_t *out) {
@@ -309,16 +307,16 @@ rq_status rq_builder_stats(const rq_builder *b, rq_build_stats_t *out) {
 
 rq_status rq_build(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k,
                    const float *orthogonal, uint64_t seed, rq_index **out) {
-    return build_host(base, n, d, centroids, k, d, orthogonal, seed, MetricSpec{}, out);
+    return build_host(RowsIn::plain(base), n, d, centroids, k, d, orthogonal, seed, MetricSpec{}, out);
 }
 rq_status rq_build_metric(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k,
                           const float *orthogonal, uint64_t seed, uint32_t metric, rq_index **out) {
     RQC(metric_entry_check(metric));
-    return build_host(base, n, d, centroids, k, d, orthogonal, seed, MetricSpec{metric}, out);
+    return build_host(RowsIn::plain(base), n, d, centroids, k, d, orthogonal, seed, MetricSpec{metric}, out);
 }
 rq_status rq_build_ip(const float *base, uint64_t n, uint32_t d, const float *centroids, uint32_t k, const float *orthogonal,
                       uint64_t seed, uint32_t centroid_cols, float sq_bound, rq_index **out) {
-    return build_host(base, n, d, centroids, k, centroid_cols, orthogonal, seed, metric_ip(d, sq_bound), out);
+    return build_host(RowsIn::plain(base), n, d, centroids, k, centroid_cols, orthogonal, seed, metric_ip(d, sq_bound), out);
 }
 
 rq_status rq_build_from_path(const char *base_fvecs, const char *centroid_fvecs, const float *orthogonal,
@@ -338,18 +336,18 @@ rq_status rq_build_from_path_ip(const char *base_fvecs, const char *centroid_fve
 rq_status rq_from_arrays(uint32_t dim, uint64_t n, uint32_t k, const float *base, const float *orthogonal,
                          const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
                          const uint64_t *codes, const rq_factor_t *factors, rq_index **out) {
-    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, MetricSpec{}, out);
+    return from_arrays(dim, n, k, RowsIn::plain(base), orthogonal, centroids, offsets, map_ids, codes, factors, MetricSpec{}, out);
 }
 rq_status rq_from_arrays_metric(uint32_t dim, uint64_t n, uint32_t k, const float *base, const float *orthogonal,
                                 const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
                                 const uint64_t *codes, const rq_factor_t *factors, uint32_t metric, rq_index **out) {
     RQC(metric_entry_check(metric));
-    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, MetricSpec{metric}, out);
+    return from_arrays(dim, n, k, RowsIn::plain(base), orthogonal, centroids, offsets, map_ids, codes, factors, MetricSpec{metric}, out);
 }
 rq_status rq_from_arrays_ip(uint32_t dim, uint64_t n, uint32_t k, const float *base, const float *orthogonal,
                             const float *centroids, const uint32_t *offsets, const uint32_t *map_ids,
                             const uint64_t *codes, const rq_factor_t *factors, uint32_t d, float sq_bound, rq_index **out) {
-    return from_arrays(dim, n, k, base, orthogonal, centroids, offsets, map_ids, codes, factors, metric_ip(d, sq_bound), out);
+    return from_arrays(dim, n, k, RowsIn::plain(base), orthogonal, centroids, offsets, map_ids, codes, factors, metric_ip(d, sq_bound), out);
 }
 
 // rabitq.rs:84-125
@@ -370,13 +368,13 @@ rq_status rq_load_dir(const char *dir, rq_index **out) {
         fclose(mf);
         if (!metric_from_file_text(std::string(buf, got), &metric)) return fail(RQ_ERR_IO, "metric: unknown or malformed content in " + d + "/metric");
     }
-    uint32_t row_type = RQ_ROWS_F32;  // the `rows` file of a half-precision or byte-row index's dump
+    RowSpec rows;  // the `rows` file of a half-precision or byte-row index's dump
     if (FILE *rf = fopen((d + "/rows").c_str(), "rb")) {
         char buf[16] = {0};
         const size_t got = fread(buf, 1, sizeof buf - 1, rf);
         fclose(rf);
         const std::string text(buf, got);
-        if (text.empty() || text.back() != '\n' || !row_type_from_text(text.substr(0, text.size() - 1), &row_type))
+        if (text.empty() || text.back() != '\n' || !RowSpec::from_tag(text.data(), text.size() - 1, &rows))
             return fail(RQ_ERR_IO, "rows: unknown content in " + d + "/rows");
     }
     const uint32_t dim = (uint32_t)ortho.lens.size();  // :108 dim = orthogonal.nrows()
@@ -410,18 +408,14 @@ rq_status rq_load_dir(const char *dir, rq_index **out) {
     if (oip[k] != n) return fail(RQ_ERR_IO, "offsets[k] != number of vectors");
     for (uint32_t j = 0; j < k; ++j)
         if (oip[j] > oip[j + 1]) return fail(RQ_ERR_IO, "offsets are not non-decreasing");
-    if (row_type && (metric.id == RQ_METRIC_IP || (rq_rows_are_bytes(row_type) && metric.id != RQ_METRIC_L2)))
+    if (!rows.allowed_with(metric.id))
         return fail(RQ_ERR_IO, "rows: an index of this metric has no rows of the announced type (" + d + ")");
     std::vector<uint8_t> typed;  // typed rows: every value of base.fvecs must be one of the type's
-    const void *base_arg = base.data.data();
-    if (row_type) {
-        RQC(narrow_exact(reinterpret_cast<const float *>(base.data.data()), n * dim, row_type, typed, d + "/base.fvecs"));
-        base_arg = typed.data();
-    }
-    return from_arrays(dim, n, k, base_arg,
+    if (rows.typed()) RQC(narrow_exact(reinterpret_cast<const float *>(base.data.data()), n * dim, rows, typed, d + "/base.fvecs"));
+    return from_arrays(dim, n, k, RowsIn::of(rows.typed() ? typed.data() : base.data.data(), rows),
                        reinterpret_cast<const float *>(ortho.data.data()), c.data(), oip, oip + (total - last),
                        reinterpret_cast<const uint64_t *>(bin.data.data()),
-                       reinterpret_cast<const rq_factor_t *>(fac.data.data()), metric, out, row_type);
+                       reinterpret_cast<const rq_factor_t *>(fac.data.data()), metric, out);
 }
 
 rq_status rq_get_array(const rq_index *idx, int which, void *dst, uint64_t dst_bytes);
@@ -503,9 +497,9 @@ rq_status rq_dump_dir(const rq_index *idx, const char *dir) {
     } else {
         remove((d + "/metric").c_str());  // (a directory that held a cosine dump before)
     }
-    if (idx->row_type) {  // base.fvecs above holds W(rows): the reference loads the directory and answers identically
+    if (idx->rows.typed()) {  // base.fvecs above holds W(rows): the reference loads the directory and answers identically
         RQC(open("rows", &f));
-        const bool ok = fputs(row_type_text(idx->row_type), f) >= 0 && fputc('\n', f) >= 0;
+        const bool ok = fputs(idx->rows.tag(), f) >= 0 && fputc('\n', f) >= 0;
         if (fclose(f) != 0 || !ok) return fail(RQ_ERR_IO, "write error on " + d + "/rows");
     } else {
         remove((d + "/rows").c_str());
@@ -559,7 +553,7 @@ rq_status rq_dump_json(const rq_index *idx, const char *path) {
     }
     o.raw("]");
     o.raw(metric_json_members(idx->metric).c_str());
-    if (idx->row_type) o.raw(",\"rows\":\""), o.raw(row_type_text(idx->row_type)), o.raw("\"");
+    if (idx->rows.typed()) o.raw(",\"rows\":\""), o.raw(idx->rows.tag()), o.raw("\"");
     o.raw("}");
     const bool closed = fclose(f) == 0;
     if (!o.ok || !closed) return fail(RQ_ERR_IO, std::string("write error on ") + path);
@@ -649,19 +643,14 @@ rq_status rq_load_json(const char *path, rq_index **out) {
     }
     std::vector<uint32_t> off32(off.begin(), off.end()), ids32(ids.begin(), ids.end());
     std::vector<uint64_t> codes64(codes.begin(), codes.end());
-    uint32_t row_type = RQ_ROWS_F32;
+    RowSpec rows;
     if (!rows_name.empty() && !(rows_name.size() > 2 && rows_name.front() == '"' && rows_name.back() == '"' &&
-                                row_type_from_text(rows_name.substr(1, rows_name.size() - 2), &row_type) && metric.id != RQ_METRIC_IP &&
-                                !(rq_rows_are_bytes(row_type) && metric.id != RQ_METRIC_L2)))
+                                RowSpec::from_tag(rows_name.data() + 1, rows_name.size() - 2, &rows) && rows.allowed_with(metric.id)))
         return fail(RQ_ERR_IO, std::string("unknown \"rows\" member ") + rows_name + " in " + path);
     std::vector<uint8_t> typed;
-    const void *base_arg = base_rows.data();
-    if (row_type) {
-        RQC(narrow_exact(base_rows.data(), n * dim, row_type, typed, path));
-        base_arg = typed.data();
-    }
-    return from_arrays((uint32_t)dim, n, (uint32_t)k, base_arg, P.data(), cent_rows.data(), off32.data(), ids32.data(),
-                       codes64.data(), fac.data(), metric, out, row_type);
+    if (rows.typed()) RQC(narrow_exact(base_rows.data(), n * dim, rows, typed, path));
+    return from_arrays((uint32_t)dim, n, (uint32_t)k, RowsIn::of(rows.typed() ? (const void *)typed.data() : base_rows.data(), rows), P.data(), cent_rows.data(), off32.data(), ids32.data(),
+                       codes64.data(), fac.data(), metric, out);
 }
 
 void rq_free(rq_index *idx) { delete idx; }
@@ -682,7 +671,7 @@ rq_status rq_get_device_ptr(const rq_index *idx, int which, const void **out_ptr
                 return fail(RQ_ERR_UNSUPPORTED, "the raw vectors of this index are tiered (HBM + pinned host memory): no single device array; use rq_get_array");
             if (idx->split_rows)  // (common.h) not an array of f32 rows
                 return fail(RQ_ERR_UNSUPPORTED, "the raw vectors of this index are stored as split rows (two 16-bit planes per row): no f32 device array; use rq_get_array");
-            if (idx->row_type)
+            if (idx->rows.typed())
                 return fail(RQ_ERR_UNSUPPORTED, "the raw vectors of this index are half-precision or byte rows: no f32 device array; use rq_get_array, or RQ_ARR_BASE_ROWS for the stored rows");
             *out_ptr = idx->base.p, *out_bytes = idx->n_dev * idx->dim * 4;
             break;
@@ -693,7 +682,7 @@ rq_status rq_get_device_ptr(const rq_index *idx, int which, const void **out_ptr
         case RQ_ARR_CODES: *out_ptr = idx->codes.p, *out_bytes = idx->n * idx->W * 8; break;
         case RQ_ARR_FACTORS: *out_ptr = idx->factors.p, *out_bytes = idx->n * 16; break;
         case RQ_ARR_BASE_ROWS:
-            if (!idx->row_type) return fail(RQ_ERR_INVALID, "RQ_ARR_BASE_ROWS: this index stores f32 rows (RQ_ARR_BASE)");
+            if (!idx->rows.typed()) return fail(RQ_ERR_INVALID, "RQ_ARR_BASE_ROWS: this index stores f32 rows (RQ_ARR_BASE)");
             *out_ptr = idx->base.p, *out_bytes = idx->n * idx->row_bytes();
             break;
         default: return fail(RQ_ERR_INVALID, "unknown array id");
@@ -704,7 +693,7 @@ rq_status rq_get_device_ptr(const rq_index *idx, int which, const void **out_ptr
 rq_status rq_get_array(const rq_index *idx, int which, void *dst, uint64_t dst_bytes) {
     const void *p;
     uint64_t bytes;
-    if (idx && which == RQ_ARR_BASE && (idx->n_dev < idx->n || idx->split_rows || idx->row_type)) {  // both tiers / split rows / half rows (widened)
+    if (idx && which == RQ_ARR_BASE && (idx->n_dev < idx->n || idx->split_rows || idx->rows.typed())) {  // both tiers / split rows / half rows (widened)
         if (!dst || dst_bytes < idx->n * idx->dim * 4) return fail(RQ_ERR_INVALID, "destination too small");
         return copy_base_rows(idx, 0, idx->n, static_cast<float *>(dst), false);
     }

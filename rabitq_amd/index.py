@@ -30,24 +30,18 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-_BYTE_DTYPE = {_lib.ROWS_U8: np.uint8, _lib.ROWS_I8: np.int8}   # byte rows: the array type each takes and base_rows returns
-
-
 def _typed_rows(base, rows):
     """(base, rows=) of the constructors -> (contiguous array as the library reads it, RQ_ROWS_* id).  rows=None: float16 arrays
     are f16 rows, everything else f32 (a uint8 array too: it is converted).  rows="f16" takes float16 (or uint16 bit patterns),
-    rows="bf16" uint16 bit patterns, rows="u8" a uint8 array, rows="i8" an int8 array."""
+    rows="bf16" uint16 bit patterns, rows="u8" a uint8 array, rows="i8" an int8 array (_lib.ROW_TABLE)."""
     a = np.asarray(base)
     rt = (_lib.ROWS_F16 if a.dtype == np.float16 else _lib.ROWS_F32) if rows is None else _lib.row_type_id(rows)
     if rt == _lib.ROWS_F32:
         return _f32(a), rt
-    if rt in _BYTE_DTYPE:
-        if a.dtype != _BYTE_DTYPE[rt]:
-            raise TypeError(f"rows={_lib.ROW_TYPE_NAMES[rt]!r} takes a {np.dtype(_BYTE_DTYPE[rt]).name} array, not {a.dtype}")
-        return np.ascontiguousarray(a), rt
-    if rt == _lib.ROWS_F16 and a.dtype == np.float16:
-        return np.ascontiguousarray(a), rt
-    if a.dtype != np.uint16:
+    t = _lib.ROW_TYPE_BY_ID.get(rt)
+    if a.dtype not in (t.takes if t else (np.uint16,)):   # (an id the table does not know: the library refuses it)
+        if t and t.elem_bytes == 1:
+            raise TypeError(f"rows={t.name!r} takes a {np.dtype(t.returns).name} array, not {a.dtype}")
         raise TypeError(f"rows={_lib.ROW_TYPE_NAMES.get(rt, rt)!r} takes a uint16 array of bit patterns"
                         + (" or a float16 array" if rt == _lib.ROWS_F16 else "") + f", not {a.dtype}")
     return np.ascontiguousarray(a), rt
@@ -349,9 +343,7 @@ class RaBitQ:
         """The raw vectors in the type the index stores: float32, float16, (bf16) uint16 bit patterns, uint8 or int8."""
         if self.row_type == "f32":
             return self.base
-        if self.row_type in ("u8", "i8"):
-            return self._get(ARR_BASE_ROWS, (self.n, self.dim), _BYTE_DTYPE[_lib.ROW_TYPES[self.row_type]])
-        return self._get(ARR_BASE_ROWS, (self.n, self.dim), np.float16 if self.row_type == "f16" else np.uint16)
+        return self._get(ARR_BASE_ROWS, (self.n, self.dim), _lib.ROW_TYPE_BY_NAME[self.row_type].returns)
 
     @property
     def orthogonal(self):

@@ -184,7 +184,7 @@ def test_queries_equal_the_oracle(rq, oracle, world, case, heur):
         for nq in sizes:
             prof = check_topk(rq, c["gidx"], c["q"][:nq], ans[:nq], PROBE, topk, heur, (case, heur, topk, nq))
             # nq <= 64 at a width the small-batch kernels are instantiated for: the small-batch path; nq <= 64 at another width: one
-            # fused launch per stage (stage_finish_byte_kernel reranks); nq >= 300: the staged launches (accurate_byte_kernel)
+            # fused launch per stage (stage_finish_kernel<*, ROW_KIND_BYTE> reranks); nq >= 300: the staged launches (accurate_kernel<ROW_KIND_BYTE>)
             assert (prof["small_batch_passes"] > 0) == (nq <= 64 and c["dim"] // 64 in SB_WIDTHS), (case, heur, topk, nq, prof["small_batch_passes"])
             assert prof["rerank_shadow_rejects"] == 0
 
@@ -536,12 +536,12 @@ def test_refusals(rq, world, rows):
 # ---- 8. the new kernels ran ----------------------------------------------------------------------------------------------
 def test_the_byte_kernels_ran(rq, world):
     """The profile fields tests/test_option_paths_gpu.py reads, on a byte index.  A batch with small_batch_passes > 0 ran the
-    small-batch path: its rerank is sb_query_kernel's run-time byte branch (and, heap ranker with nq <= 32, accurate_byte_kernel),
-    its finish sb_finish_byte_kernel (heap ranker) or stage_finish_byte_kernel (heuristic ranker).  A batch with
-    small_batch_passes == 0 ran the staged launches: the flat rerank accurate_byte_kernel and stage_finish_byte_kernel.  The host
+    small-batch path: its rerank is sb_query_kernel's run-time byte branch (and, heap ranker with nq <= 32, accurate_kernel<ROW_KIND_BYTE>),
+    its finish sb_finish_kernel<*, ROW_KIND_BYTE> (heap ranker) or stage_finish_kernel<*, ROW_KIND_BYTE> (heuristic ranker).  A batch with
+    small_batch_passes == 0 ran the staged launches: the flat rerank accurate_kernel<ROW_KIND_BYTE> and stage_finish_kernel<*, ROW_KIND_BYTE>.  The host
     has no other kernels to launch for a byte index; rerank_candidates > 0 shows survivors were reranked, rerank_shadow_rejects == 0
     that no shadow row stood in for a byte row.  The profile has no field that tells sb_query_kernel's own rerank from
-    sb_finish_byte_kernel's: both belong to a small-batch pass."""
+    sb_finish_kernel<*, ROW_KIND_BYTE>'s: both belong to a small-batch pass."""
     from rabitq_amd import index as ix
     c = world(("u8", 128, 20000, 32))
     g, q = c["gidx"], c["q"]
@@ -551,7 +551,7 @@ def test_the_byte_kernels_ran(rq, world):
         rq.metrics_reset()
         g.query_batch(q[:nq], PROBE, 10, heur)
         seen[name] = (ix.last_profile(), rq.metrics())
-    # dim 192 has no small-batch path: a batch of 16 is one fused launch per stage, reranked by stage_finish_byte_kernel itself
+    # dim 192 has no small-batch path: a batch of 16 is one fused launch per stage, reranked by stage_finish_kernel<*, ROW_KIND_BYTE> itself
     c3 = world(("u8", 192, 5000, 16))
     rq.metrics_reset()
     c3["gidx"].query_batch(c3["q"][:16], PROBE, 10, False)

@@ -200,7 +200,7 @@ def test_queries_equal_the_oracle(rq, oracle, world, case, heur):
         ans = oracle_answers(oracle, c["oidx"], c["q"][:max(sizes)], PROBE, topk, heur)
         for nq in sizes:
             prof = check_topk(rq, c["gidx"], c["q"][:nq], ans[:nq], PROBE, topk, heur, (case, heur, topk, nq))
-            # nq <= 64: the small-batch path (sb_query_kernel / the finish kernels); nq >= 300: the staged launches (accurate_half_kernel)
+            # nq <= 64: the small-batch path (sb_query_kernel / the finish kernels); nq >= 300: the staged launches (accurate_kernel<ROW_KIND_HALF>)
             assert (prof["small_batch_passes"] > 0) == (nq <= 64), (case, heur, topk, nq, prof["small_batch_passes"])
             assert prof["rerank_shadow_rejects"] == 0
 
