@@ -86,7 +86,8 @@ typedef struct {
  * 0.9.0: inner-product metric, additions only -- RQ_METRIC_IP, rq_*_ip, rq_ip_*, rq_augment*, rq_row_sqnorm_max*;
  * 0.10.0: half-precision rows, additions only -- RQ_ROWS_*, rq_*_rows, rq_row_type, rq_widen*, RQ_ARR_BASE_ROWS;
  * 0.11.0: byte rows, two more values of row_type and no new symbol -- RQ_ROWS_U8, RQ_ROWS_I8;
- * later in 0.11, additions only: exact search -- rq_exact_search*, rq_last_exact_stats).
+ * later in 0.11, additions only: exact search -- rq_exact_search*, rq_last_exact_stats; exact range search --
+ * rq_exact_range_search*).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -518,6 +519,39 @@ rq_status rq_exact_search(const rq_index *idx, const rq_filter *filter /* nullab
                           uint32_t topk, const rq_exact_params_t *params /* nullable */, float *out_dist, uint32_t *out_id,
                           uint32_t *out_n);
 rq_status rq_last_exact_stats(rq_exact_stats_t *out);
+
+/* ---- exact range search: every stored row within a per-query radius (later in 0.11, additions only) ----------------- */
+/* What rq_range_search* is measured against, as rq_exact_search* is for the top-k entries.  Queries are raw, exactly as
+ * rq_exact_search_device takes them (the same `len` rules; cosine normalised, inner product padded); q' and e(r) as defined there.
+ * The answer of query b is the SET
+ *     { (e(r), id(r)) : r admitted by the filter (NULL: every stored row),  e(r) < radius_b,  e(r) < f32::MAX }
+ * with both comparisons strict f32 "<", the comparison rq_range_search uses: a NaN radius or a radius <= 0 admits nothing, +inf and
+ * f32::MAX admit every admitted row whose e is below f32::MAX.  Each query's entries ascend by (distance, id).  The result does not
+ * depend on `params`, on options, on the batch size or on how the work was split.
+ * The result is an ordinary rq_range_result (lims nq + 1 u64, dist / id of exactly `total` entries), served by
+ * rq_range_result_info / _device_ptrs / _copy / _free; on any error *out is NULL and nothing stays allocated.  nq == 0 behaves as
+ * rq_range_search does.  An index or filter with no admitted row gives all counts 0 with RQ_OK.
+ * Accepted and refused as rq_exact_search*: L2 / cosine / inner-product indexes, f32, f16 / bf16, u8 / i8 rows, shards of
+ * rq_shard_index (ids are their map_ids), mutated indexes; tiered and split-row indexes: RQ_ERR_UNSUPPORTED before anything is
+ * allocated; a foreign or stale filter: RQ_ERR_INVALID; dim <= 4096.  No counter of rq_metrics is touched, and no trace is left in
+ * how later top-k, range or exact top-k calls run (the capacity this call learns is a hint of its own).
+ * Method: the exact search's scan with T_b = radius_b -- no sample, no seed pass -- appending the kept (query, row)
+ * pairs to one arena per launch; one pass over the arena for the exact distances, keys and per-query hit counts; prefix sum, one
+ * allocation of exactly the hits, scatter into per-query segments; the range search's segment sort and key split.  A launch whose
+ * pairs overflow its arena is run again with the count it learnt (nothing downstream runs on an overflowed launch); a group whose
+ * arena would exceed the slot budget is split, down to one query; a single query that still does not fit is RQ_ERR_OOM.
+ * params (nullable; the struct and the refusal of unknown flag bits of rq_exact_search; TEST HOOKS): flags bit 1 = no pre-filter
+ * (every admitted pair gets its exact distance; also what dimensions above 2432 run); flags bit 0 and seed_probe are accepted and
+ * have no effect (there is no sample); cand_per_query = initial arena records of a launch per query of that launch; zero = automatic.
+ * rq_last_exact_stats is filled by these calls too: seed_probe = 0, ms_seed = 0, seed_unfilled = 0; ms_scan; ms_exact; ms_select =
+ * everything behind the exact distances (counts, offsets, scatter, sort, split); candidates = pairs the scan kept; exact =
+ * candidates; reruns, scan_launches and row_bytes_read as above. */
+rq_status rq_exact_range_search_device(const rq_index *idx, const rq_filter *filter /* nullable */, const float *d_queries,
+                                       uint32_t nq, uint32_t len, const float *d_radius,
+                                       const rq_exact_params_t *params /* nullable */, rq_range_result **out);
+rq_status rq_exact_range_search(const rq_index *idx, const rq_filter *filter /* nullable */, const float *queries, uint32_t nq,
+                                uint32_t len, const float *radius, const rq_exact_params_t *params /* nullable */,
+                                rq_range_result **out);
 
 /* ---- in-place mutation: add and remove rows ------------------------------------------------------------------------ */
 /* After any sequence of rq_add / rq_remove the index equals, bit for bit, the index rq_build produces from its live rows S in

@@ -33,6 +33,7 @@ EXPORTS = [
     "rq_build_rows", "rq_build_device_rows", "rq_builder_create_rows", "rq_builder_assign_chunk_rows", "rq_builder_place_chunk_rows",
     "rq_from_arrays_rows", "rq_row_type", "rq_widen", "rq_widen_device",
     "rq_exact_search", "rq_exact_search_device", "rq_last_exact_stats",
+    "rq_exact_range_search", "rq_exact_range_search_device",
 ]
 
 
@@ -278,6 +279,8 @@ def lib():
         "rq_exact_search": (i32, [vp, vp, f32p, u32, u32, u32, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
         "rq_exact_search_device": (i32, [vp, vp, f32p, u32, u32, u32, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
         "rq_last_exact_stats": (i32, [C.POINTER(ExactStatsT)]),
+        "rq_exact_range_search": (i32, [vp, vp, f32p, u32, u32, f32p, C.POINTER(ExactParamsT), pp]),
+        "rq_exact_range_search_device": (i32, [vp, vp, f32p, u32, u32, f32p, C.POINTER(ExactParamsT), pp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the .so lacks a declared symbol

@@ -186,6 +186,44 @@ static rq_status range_sort_segments(Workspace &ws, unsigned long long *keys, co
     return RQ_OK;
 }
 
+// The tail of a range call: the runs' pieces united into the call's offsets and keys (one piece covering the call in order: adopted
+// as it is), the segments sorted, the keys split into the result's arrays.  Also the tail of the exact range search
+// (host_exact_range.h), whose pieces are built from keys that are already segmented.
+static rq_status range_finish_pieces(Workspace &ws, std::vector<std::unique_ptr<RangePiece>> &pieces, uint32_t nq, rq_range_result *res) {
+    hipStream_t st = ws.stream;
+    DevBuf<unsigned long long> keys;
+    if (pieces.size() == 1 && !pieces[0]->has_rows) {  // one pass, nothing re-run: its offsets and keys are the call's
+        res->lims.take(pieces[0]->lims);
+        keys.take(pieces[0]->keys);
+        res->total = pieces[0]->total;
+    } else {
+        DevBuf<unsigned long long> counts;
+        RQC(counts.alloc(nq));
+        RQC(res->lims.alloc((size_t)nq + 1));
+        HIPC(hipMemsetAsync(counts.p, 0, (size_t)nq * 8, st));
+        for (auto &p : pieces)
+            if (p->total) range_piece_counts_kernel<<<ceil_div(p->m, 256), 256, 0, st>>>(p->lims.p, p->has_rows ? p->rows.p : nullptr, p->q0, p->m, counts.p);
+        range_scan_kernel<unsigned long long><<<1, 1024, 0, st>>>(counts.p, nq, res->lims.p);
+        unsigned long long *h_total = ws.h_totals + RQ_HT_RANGE_TOTAL;
+        HIPC(hipMemcpyAsync(h_total, res->lims.p + nq, 8, hipMemcpyDeviceToHost, st));
+        HIPC(hipStreamSynchronize(st));
+        res->total = *h_total;
+        RQC(keys.alloc(res->total));
+        for (auto &p : pieces)
+            if (p->total)
+                range_piece_scatter_kernel<<<ceil_div(p->m, 4), 256, 0, st>>>(p->keys.p, p->lims.p, p->has_rows ? p->rows.p : nullptr, p->q0, p->m,
+                                                                            res->lims.p, keys.p);
+        HIPC(hipStreamSynchronize(st));
+        pieces.clear();
+    }
+    if (res->total) RQC(range_sort_segments(ws, keys.p, res->lims.p, nq, res->total));
+    RQC(res->dist.alloc(res->total));
+    RQC(res->id.alloc(res->total));
+    if (res->total)
+        range_split_kernel<<<(uint32_t)std::min<uint64_t>(4096, (res->total + 255) / 256), 256, 0, st>>>(keys.p, res->total, res->dist.p, res->id.p);
+    return RQ_OK;  // (the key array is freed here: hipFree waits for the split)
+}
+
 static rq_status range_device_impl(rq_index *idx, const rq_filter *filter, const float *d_q, uint32_t nq, uint32_t len, uint32_t probe,
                                    const float *d_radius, rq_range_result **out) {
     std::unique_ptr<rq_range_result> res(new rq_range_result());
@@ -213,39 +251,9 @@ static rq_status range_device_impl(rq_index *idx, const rq_filter *filter, const
         pieces.push_back(std::move(piece));
         if (pr.overflowed) RQC(range_rerun_overflowed(*ws, pc, qp, q0, tot, pieces));
     }
-    // unite the pieces
     RangeTimer tm;
     tm.begin(st);
-    DevBuf<unsigned long long> keys;
-    if (pieces.size() == 1 && !pieces[0]->has_rows) {  // one pass, nothing re-run: its offsets and keys are the call's
-        res->lims.take(pieces[0]->lims);
-        keys.take(pieces[0]->keys);
-        res->total = pieces[0]->total;
-    } else {
-        DevBuf<unsigned long long> counts;
-        RQC(counts.alloc(nq));
-        RQC(res->lims.alloc((size_t)nq + 1));
-        HIPC(hipMemsetAsync(counts.p, 0, (size_t)nq * 8, st));
-        for (auto &p : pieces)
-            if (p->total) range_piece_counts_kernel<<<ceil_div(p->m, 256), 256, 0, st>>>(p->lims.p, p->has_rows ? p->rows.p : nullptr, p->q0, p->m, counts.p);
-        range_scan_kernel<unsigned long long><<<1, 1024, 0, st>>>(counts.p, nq, res->lims.p);
-        unsigned long long *h_total = ws->h_totals + RQ_HT_RANGE_TOTAL;
-        HIPC(hipMemcpyAsync(h_total, res->lims.p + nq, 8, hipMemcpyDeviceToHost, st));
-        HIPC(hipStreamSynchronize(st));
-        res->total = *h_total;
-        RQC(keys.alloc(res->total));
-        for (auto &p : pieces)
-            if (p->total)
-                range_piece_scatter_kernel<<<ceil_div(p->m, 4), 256, 0, st>>>(p->keys.p, p->lims.p, p->has_rows ? p->rows.p : nullptr, p->q0, p->m,
-                                                                            res->lims.p, keys.p);
-        HIPC(hipStreamSynchronize(st));
-        pieces.clear();
-    }
-    if (res->total) RQC(range_sort_segments(*ws, keys.p, res->lims.p, nq, res->total));
-    RQC(res->dist.alloc(res->total));
-    RQC(res->id.alloc(res->total));
-    if (res->total)
-        range_split_kernel<<<(uint32_t)std::min<uint64_t>(4096, (res->total + 255) / 256), 256, 0, st>>>(keys.p, res->total, res->dist.p, res->id.p);
+    RQC(range_finish_pieces(*ws, pieces, nq, res.get()));
     tm.end(prof);
     HIPC(hipStreamSynchronize(st));
     HIPC(hipGetLastError());

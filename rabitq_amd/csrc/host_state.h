@@ -305,6 +305,7 @@ struct rq_index {
     std::atomic<uint32_t> big_dirs_hint{0};  // most long run directories (> 512 runs) a stage of a recent pass produced
     std::atomic<uint32_t> exact_cap_hint{0};  // candidate slots per query the exact search learnt on this index (host_exact.h)
     std::atomic<uint32_t> range_cap_hint{0};  // survivor-buffer capacity learnt from range passes most of whose queries overflowed (host_range.h)
+    std::atomic<uint32_t> exact_range_cap_hint{0};  // arena records per query the exact range search learnt on this index (host_exact_range.h)
     uint64_t pass_budget = 24ull << 30;  // bytes of survivor / run buffers one query pass may use (set by finish_index)
     // tile tables of the cluster-major scans: per tile size, one {list, first, list begin, list length} entry per
     // existing (list, tile); built on first use from the host copy of the offsets
@@ -337,6 +338,7 @@ struct rq_filter {
     std::atomic<uint64_t> arena_hint{0};
     std::atomic<uint32_t> big_dirs_hint{0};
     std::atomic<uint32_t> exact_cap_hint{0};  // as rq_index::exact_cap_hint, for the exact searches under this filter
+    std::atomic<uint32_t> exact_range_cap_hint{0};  // as rq_index::exact_range_cap_hint, for the exact range searches under this filter
 };
 // The learnt survivor-buffer hints a pass reads and updates: the index's own, or the filter's on a filtered pass.
 struct PassHints {

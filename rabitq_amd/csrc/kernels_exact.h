@@ -44,10 +44,16 @@ struct ExactArgs {
     float *qn2, *qsn;           // nq32: |q'|^2 and sqrt(|q'|^2) * 1.000001
     float *thr;                 // nq: T_q
     uint32_t nq, nq32;          // queries of this launch, rounded up to whole 32-query MFMA tiles
-    uint32_t cap;               // candidate slots per query
-    uint32_t *cand;             // nq x cap: positions
-    unsigned int *cnt;          // nq: candidates emitted (keeps counting past cap: the overflow is cnt > cap)
-    unsigned long long *keys;   // nq x cap: ord32_biased(e) << 32 | id, ~0 = not in the answer
+    uint32_t cap;               // candidate slots per query (range form: records of the launch's shared arena)
+    union {
+        uint32_t *cand;         // nq x cap: positions
+        uint2 *rec;             // range form: cap records, x = query of the launch, y = position
+    };
+    union {
+        unsigned int *cnt;      // nq: candidates emitted (keeps counting past cap: the overflow is cnt > cap)
+        unsigned long long *rec_count;  // range form: ONE count of the records appended (likewise past cap)
+    };
+    unsigned long long *keys;   // nq x cap: ord32_biased(e) << 32 | id, ~0 = not in the answer (range form: cap keys, one per record)
     uint32_t topk;
     float *out_dist;            // nq x topk
     uint32_t *out_id, *out_n;
@@ -73,6 +79,23 @@ void launch_exact_thr(const float *seed_dist, const uint32_t *seed_n, uint32_t n
 void launch_exact_scan(const ExactArgs &a, bool prefilter, hipStream_t st);
 void launch_exact_dist(const ExactArgs &a, hipStream_t st);
 void launch_exact_select(const ExactArgs &a, hipStream_t st);
+
+// ---- the range form (rq_exact_range_search*, host_exact_range.h) ----
+// T_q is the query's radius and nothing cuts at a topk, so the answers are wildly uneven: the scan appends its kept pairs as
+// (query, position) records to ONE arena shared by the launch's queries (work memory follows the pairs kept, not nq x the largest
+// answer), one pass gives every record its exact distance and key and counts the hits per query, and after the prefix sum of the
+// counts (range_scan_kernel, kernels_range.h) the live keys are scattered into per-query segments of exactly the hits.
+// ExactArgs::topk / out_* are not read by these launches.
+struct ExactSegments {
+    uint32_t *hits;                  // nq: live keys per query (zeroed by the host)
+    uint32_t *cursor;                // nq: the scatter's next free slot of every segment (zeroed by the host)
+    const unsigned long long *lims;  // nq + 1: the segments' offsets
+    unsigned long long *out;         // lims[nq] keys: the segments
+};
+void launch_exact_range_thr(const float *radius, uint32_t nq, float *thr, hipStream_t st);  // T_q = r_q, or a bound that keeps nothing (NaN, r_q <= 0)
+void launch_exact_range_scan(const ExactArgs &a, bool prefilter, hipStream_t st);
+void launch_exact_range_dist(const ExactArgs &a, uint32_t *hits, uint32_t records, hipStream_t st);
+void launch_exact_range_scatter(const ExactArgs &a, const ExactSegments &sg, uint32_t records, hipStream_t st);
 
 #ifdef RQ_EXACT_KERNELS
 #include "kernels_rerank.h"
@@ -137,7 +160,11 @@ __global__ __launch_bounds__(256) void exact_thr_kernel(const float *__restrict_
 // per lane and tile for the lane's whole count; the count runs on past the capacity while the stores stop, and the host runs the
 // launch again with what the count has learnt.  PRE = false (no pre-filter: the test hook, and dimensions whose tile does not fit):
 // no image, no MFMA, every admitted row is kept.
-template <int RT, bool PRE>
+// RANGE (rq_exact_range_search*): the same tile, MFMAs and margin with T_q = the radius; kept pairs go to the launch's shared arena
+// as (query, position) records.  The lanes' counts are summed over the wave (an inclusive scan by shuffles: six steps per tile, next
+// to dim / 16 x RT MFMAs) and ONE lane reserves the wave's records with one 64-bit atomic; again the count runs on past the capacity
+// while the stores stop.  A query whose bound is not above zero (NaN or non-positive radius) emits nothing, wild rows included.
+template <int RT, bool PRE, bool RANGE = false>
 __global__ __launch_bounds__(256, (RT == 1 ? 1 : 2)) void exact_scan_kernel(const ExactArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ex_lds[];
     const uint32_t dim = a.dim, ROWB = dim * 2 + 16;
@@ -221,6 +248,38 @@ __global__ __launch_bounds__(256, (RT == 1 ? 1 : 2)) void exact_scan_kernel(cons
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) mine[rt] = amask[rt];
         }
+        if constexpr (RANGE) {
+            // (the wave is whole here: the loop over g is uniform and nothing above leaves it)
+            const bool live = q < a.nq && a.thr[q] > 0.0f;
+            uint32_t c = 0;
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                if (!live) mine[rt] = 0u;
+                c += (uint32_t)__popc(mine[rt]);
+            }
+            uint32_t inc = c;  // inclusive prefix of the lanes' counts
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t up = __shfl_up(inc, o, 64);
+                if (lane >= (uint32_t)o) inc += up;
+            }
+            const uint32_t total = __shfl(inc, 63, 64);
+            if (total == 0) continue;
+            unsigned long long first = 0;
+            if (lane == 63) first = atomicAdd(a.rec_count, (unsigned long long)total);
+            unsigned long long at = __shfl(first, 63, 64) + (inc - c);
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                uint32_t mk = mine[rt];
+                while (mk) {
+                    const uint32_t r = (uint32_t)__builtin_ctz(mk);
+                    mk &= mk - 1u;
+                    if (at < a.cap) a.rec[at] = make_uint2(q, ((uint32_t)tile0 + rt * 32 + (r & 3u) + 8u * (r >> 2) + 4u * kh) * a.stride);
+                    ++at;
+                }
+            }
+            continue;
+        }
         if (q >= a.nq) continue;
         uint32_t c = 0;
 #pragma unroll
@@ -238,6 +297,55 @@ __global__ __launch_bounds__(256, (RT == 1 ? 1 : 2)) void exact_scan_kernel(cons
                 ++at;
             }
         }
+    }
+}
+
+// The range form's bounds: T_q = the radius; a NaN or non-positive radius admits nothing and must not reach the scan's test, which
+// keeps a pair on a NaN -- such a query gets -f32::MAX, and the scan emits nothing for a bound that is not above zero.
+__global__ __launch_bounds__(256) void exact_range_thr_kernel(const float *__restrict__ radius, uint32_t nq, float *__restrict__ thr) {
+    const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+    if (q < nq) thr[q] = radius[q] > 0.0f ? radius[q] : -3.4028234663852886e38f;
+}
+
+// Exact distances of the arena's records: one pass over the m records, 128 per block and round, a pair of lanes per record
+// (exact_l2_row).  A block sees many queries, so q' is read from qpad in global memory (the L2 holds the launch's queries).  The key
+// of a record with e < T_q (the radius) and e < f32::MAX, ~0 for every other one (a NaN fails both), and the hits counted per query:
+// a wave whose 32 records belong to one query -- the scan writes a lane's pairs of a tile side by side -- adds its count once.
+__global__ __launch_bounds__(256) void exact_range_dist_kernel(const ExactArgs a, uint32_t *__restrict__ hit_cnt, uint32_t m) {
+    const uint32_t dim = a.dim, hf = threadIdx.x & 1, lane = threadIdx.x & 63;
+    const uint32_t rounds = (uint32_t)(((uint64_t)m + 127) / 128);
+    for (uint32_t rd = blockIdx.x; rd < rounds; rd += gridDim.x) {
+        const uint64_t i = (uint64_t)rd * 128 + (threadIdx.x >> 1);
+        const bool have = i < m;  // (the same for the two lanes of a pair)
+        const uint2 rec = have ? a.rec[i] : make_uint2(0xFFFFFFFFu, 0u);
+        bool hit = false;
+        if (have) {
+            const float e = exact_l2_row(a.base.row_at(rec.y, dim), a.qpad + (uint64_t)rec.x * dim, dim, hf);
+            if (hf == 0) {
+                hit = e < a.thr[rec.x] && e < 3.4028234663852886e38f;
+                a.keys[i] = hit ? ((unsigned long long)ord32_biased(e) << 32) | a.map_ids[rec.y] : ~0ull;
+            }
+        }
+        const unsigned long long hits = __ballot(hit);
+        const uint32_t q0 = __shfl(rec.x, 0, 64);
+        if (__all(!have || rec.x == q0)) {
+            if (lane == 0 && hits) atomicAdd(&hit_cnt[q0], (uint32_t)__popcll(hits));
+        } else if (hit) {
+            atomicAdd(&hit_cnt[rec.x], 1u);
+        }
+    }
+}
+
+// The live keys into their query's segment [lims[q], lims[q + 1]): one thread per record, the place from the segment's cursor.  The
+// order inside a segment is whatever the atomics give; the segments are sorted afterwards (keys are unique: one per id).
+__global__ __launch_bounds__(256) void exact_range_scatter_kernel(const uint2 *__restrict__ rec, const unsigned long long *__restrict__ keys,
+                                                                  uint32_t m, const ExactSegments sg) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (uint64_t)gridDim.x * 256) {
+        const unsigned long long key = keys[i];
+        if (key == ~0ull) continue;
+        const uint32_t q = rec[i].x;
+        const unsigned long long o = sg.lims[q] + atomicAdd(&sg.cursor[q], 1u);
+        if (o < sg.lims[q + 1]) sg.out[o] = key;
     }
 }
 

@@ -42,6 +42,7 @@
 #include "host_build.h"
 #include "host_mutate.h"
 #include "host_exact.h"
+#include "host_exact_range.h"
 
 // ------------------------------------------------------------------------------------------------
 // extern "C"
@@ -1002,6 +1003,15 @@ rq_status rq_exact_search_device(const rq_index *idx, const rq_filter *filter, c
 rq_status rq_exact_search(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len, uint32_t topk,
                           const rq_exact_params_t *params, float *out_dist, uint32_t *out_id, uint32_t *out_n) {
     return exact_search_host(idx, filter, queries, nq, len, topk, params, out_dist, out_id, out_n);
+}
+// ---- exact range search (host_exact_range.h): every stored row within a per-query radius, as an rq_range_result ----
+rq_status rq_exact_range_search_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
+                                       const float *d_radius, const rq_exact_params_t *params, rq_range_result **out) {
+    return exact_range_device(idx, filter, d_queries, nq, len, d_radius, params, out);
+}
+rq_status rq_exact_range_search(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len,
+                                const float *radius, const rq_exact_params_t *params, rq_range_result **out) {
+    return exact_range_host(idx, filter, queries, nq, len, radius, params, out);
 }
 rq_status rq_last_exact_stats(rq_exact_stats_t *out) {
     if (!out) return fail(RQ_ERR_INVALID, "null argument");

@@ -633,6 +633,58 @@ class RaBitQ:
                                            C.byref(h)))
         return RangeResult(self, h)
 
+    # ---- exact range search: every stored row within a per-query radius (rq_exact_range_search*) ----
+    def _radii(self, q, radius, min_ip):
+        """One f32 radius per query from radius= (a scalar or one per query) or min_ip= (an "ip" index: ip_radius)."""
+        if (radius is None) == (min_ip is None):
+            raise _lib.RabitqError(-1, "give either radius or min_ip")
+        if min_ip is not None:
+            radius = self.ip_radius(q, min_ip)
+        r = np.asarray(radius, dtype=np.float32)
+        r = np.full(q.shape[0], r, dtype=np.float32) if r.ndim == 0 else np.ascontiguousarray(r.reshape(-1))
+        if r.size != q.shape[0]:
+            raise _lib.RabitqError(-1, f"radius must be a scalar or one value per query ({q.shape[0]}), not {r.size}")
+        return r
+
+    def exact_range_search(self, queries, radius=None, filter: Filter = None, min_ip=None, params=None):
+        """B queries -> (lims u64[B + 1], dist f32[total], ids u32[total]): EVERY stored row whose exact squared distance is strictly
+        below radius[b] (a scalar = the same radius for every query), at [lims[b], lims[b + 1]) ascending by (distance, id): what
+        range_search is measured against.  filter: only its rows can be returned.  min_ip (an "ip" index, instead of radius): the rows
+        whose inner product is above min_ip[b] (ip_radius).  params: the exact search's test hooks (result-neutral)."""
+        q = _f32(queries)
+        if q.ndim != 2:
+            raise _lib.RabitqError(-1, "queries must be 2-D")
+        r = self._radii(q, radius, min_ip)
+        prm = self._exact_params(params)
+        h = C.c_void_p()
+        check(lib().rq_exact_range_search(self._h, _fh(filter), _addr(q), q.shape[0], q.shape[1], _addr(r),
+                                          C.byref(prm) if prm is not None else None, C.byref(h)))
+        with RangeResult(self, h) as res:
+            return res.to_host()
+
+    def exact_range_search_device(self, q_ptr: int, nq: int, length: int, radius_ptr: int, filter: Filter = None, params=None) -> RangeResult:
+        """exact_range_search with queries (nq x length) and radii (nq f32) already in device memory (raw addresses) -> a
+        RangeResult whose arrays stay on the device."""
+        prm = self._exact_params(params)
+        h = C.c_void_p()
+        check(lib().rq_exact_range_search_device(self._h, _fh(filter), C.c_void_p(q_ptr), nq, length, C.c_void_p(radius_ptr),
+                                                 C.byref(prm) if prm is not None else None, C.byref(h)))
+        return RangeResult(self, h)
+
+    def range_recall(self, queries, probe: int, radius=None, filter: Filter = None, min_ip=None) -> float:
+        """What fraction of the exact range answer range_search(queries, probe, ...) returns, pooled over the queries:
+        sum_b |A_b n E_b| / sum_b |E_b| (A: the approximate answer's ids, E: the exact one's); 1.0 when E is empty everywhere."""
+        q = _f32(queries)
+        if q.ndim != 2:
+            raise _lib.RabitqError(-1, "queries must be 2-D")
+        r = self._radii(q, radius, min_ip)
+        el, _, ei = self.exact_range_search(q, radius=r, filter=filter)
+        al, _, ai = self.range_search(q, probe, radius=r, filter=filter)
+        if int(el[-1]) == 0:
+            return 1.0
+        found = sum(len(np.intersect1d(ai[int(al[b]):int(al[b + 1])], ei[int(el[b]):int(el[b + 1])])) for b in range(q.shape[0]))
+        return found / int(el[-1])
+
     def query_batch_device_begin(self, q_ptr: int, nq: int, length: int, probe: int, topk: int, out_dist_ptr: int,
                                  out_id_ptr: int, out_n_ptr: int, heuristic_rank: bool = False, filter: Filter = None):
         """Enqueue a device-resident batch and return a ticket; finish it with query_batch_device_end(ticket).
