@@ -87,7 +87,7 @@ typedef struct {
  * 0.10.0: half-precision rows, additions only -- RQ_ROWS_*, rq_*_rows, rq_row_type, rq_widen*, RQ_ARR_BASE_ROWS;
  * 0.11.0: byte rows, two more values of row_type and no new symbol -- RQ_ROWS_U8, RQ_ROWS_I8;
  * later in 0.11, additions only: exact search -- rq_exact_search*, rq_last_exact_stats; exact range search --
- * rq_exact_range_search*).
+ * rq_exact_range_search*; rq_exact_stats_t.reserved0 became scan_subtiles).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -493,7 +493,9 @@ void rq_range_result_free(rq_range_result *r);
  * computed, the sample's included; reruns = scan launches repeated because a query's candidates did not fit its slots (the capacity
  * learnt is remembered with the index or filter: a later call starts from it); row_bytes_read = bytes of raw rows the scan launches
  * covered (algorithmic: n x row bytes per launch; a batch of up to 4096 queries is ONE launch, re-runs count again); scan_launches =
- * those launches.  A launch that overflowed stops behind the scan: nothing is computed or written from its candidates. */
+ * those launches; scan_subtiles = 32-row sub-tiles per block of those launches' scan (4, 2 or 1 by dimension; 0: the scan ran without
+ * the pre-filter -- flags bit 1, or a dimension above 2432).  A launch that overflowed stops behind the scan: nothing is computed
+ * or written from its candidates. */
 typedef struct {
     uint32_t struct_size; /* in: sizeof(rq_exact_params_t) */
     uint32_t seed_probe;
@@ -510,7 +512,7 @@ typedef struct {
     uint64_t exact;
     uint64_t row_bytes_read;
     uint32_t scan_launches;
-    uint32_t reserved0;
+    uint32_t scan_subtiles; /* 4, 2 or 1; 0 = the scan ran without the pre-filter (was reserved0, always 0) */
 } rq_exact_stats_t;
 rq_status rq_exact_search_device(const rq_index *idx, const rq_filter *filter /* nullable */, const float *d_queries, uint32_t nq,
                                  uint32_t len, uint32_t topk, const rq_exact_params_t *params /* nullable */, float *d_out_dist,

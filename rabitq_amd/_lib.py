@@ -146,7 +146,7 @@ class ExactStatsT(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("seed_probe", C.c_uint32)] + [(n, C.c_float) for n in (
         "ms_seed", "ms_scan", "ms_exact", "ms_select")] + [
         ("seed_unfilled", C.c_uint32), ("reruns", C.c_uint32), ("candidates", C.c_uint64), ("exact", C.c_uint64),
-        ("row_bytes_read", C.c_uint64), ("scan_launches", C.c_uint32), ("reserved0", C.c_uint32)]
+        ("row_bytes_read", C.c_uint64), ("scan_launches", C.c_uint32), ("scan_subtiles", C.c_uint32)]
 
 
 def build(force: bool = False) -> str:

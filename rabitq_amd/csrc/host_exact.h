@@ -87,6 +87,7 @@ static rq_status exact_search_device(const rq_index *idx, const rq_filter *filte
     const uint64_t slot_budget = std::max<uint64_t>(64ull << 20, std::min<uint64_t>(RQ_EXACT_SLOT_BUDGET, free_b / 3));
     rq_exact_stats_t &stats = g_exact_stats;
     stats.seed_probe = no_seed ? 0u : sample_rows;
+    stats.scan_subtiles = prefilter ? exact_scan_subtiles(idx->dim) : 0u;  // (the decision launch_exact_scan takes for the counted launches)
 
     DevBuf<float> seed_dist, qscratch, thr, qn2, qsn;
     DevBuf<uint32_t> seed_id, seed_n, cand;

@@ -53,6 +53,7 @@ static rq_status exact_range_impl(rq_index *idx, const rq_filter *filter, const 
         return RQ_OK;
     };
     const bool prefilter = !(prm.flags & RQ_EXACT_NO_PREFILTER) && exact_scan_subtiles(idx->dim) != 0;
+    stats.scan_subtiles = prefilter ? exact_scan_subtiles(idx->dim) : 0u;  // (the decision launch_exact_range_scan takes)
     // the records per query earlier calls on this index / filter learnt -- a hint of its own: the exact top-k's slots and the range
     // passes' survivor buffers are sized by theirs; the test hook overrides it
     std::atomic<uint32_t> &cap_hint = filter ? const_cast<rq_filter *>(filter)->exact_range_cap_hint : idx->exact_range_cap_hint;

@@ -124,8 +124,9 @@ def test_exact_structs_match_the_compiled_header(tmp_path):
 #include "rabitq_hip.h"
 int main(void) {
     printf("%zu %zu %zu %zu\\n", sizeof(rq_exact_params_t), offsetof(rq_exact_params_t, seed_probe), offsetof(rq_exact_params_t, cand_per_query), offsetof(rq_exact_params_t, flags));
-    printf("%zu %zu %zu %zu %zu %zu %zu\\n", sizeof(rq_exact_stats_t), offsetof(rq_exact_stats_t, ms_seed), offsetof(rq_exact_stats_t, seed_unfilled),
-           offsetof(rq_exact_stats_t, reruns), offsetof(rq_exact_stats_t, candidates), offsetof(rq_exact_stats_t, row_bytes_read), offsetof(rq_exact_stats_t, scan_launches));
+    printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(rq_exact_stats_t), offsetof(rq_exact_stats_t, ms_seed), offsetof(rq_exact_stats_t, seed_unfilled),
+           offsetof(rq_exact_stats_t, reruns), offsetof(rq_exact_stats_t, candidates), offsetof(rq_exact_stats_t, row_bytes_read), offsetof(rq_exact_stats_t, scan_launches),
+           offsetof(rq_exact_stats_t, scan_subtiles));
     return 0;
 }''')
     exe = tmp_path / "layout"
@@ -134,7 +135,8 @@ int main(void) {
     P, S = _lib.ExactParamsT, _lib.ExactStatsT
     assert rows[0] == [C.sizeof(P), P.seed_probe.offset, P.cand_per_query.offset, P.flags.offset]
     assert rows[1] == [C.sizeof(S), S.ms_seed.offset, S.seed_unfilled.offset, S.reruns.offset, S.candidates.offset,
-                       S.row_bytes_read.offset, S.scan_launches.offset]
+                       S.row_bytes_read.offset, S.scan_launches.offset, S.scan_subtiles.offset]
+    assert S.scan_subtiles.offset == 60 and C.sizeof(S) == 64                # the word that was reserved0: the layout did not move
 
 
 def test_write_ivecs_roundtrip(tmp_path):

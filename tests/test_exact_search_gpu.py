@@ -24,7 +24,9 @@ F32 = np.float32
 INVALID, UNSUPPORTED = -1, -6
 QGROUP = 4096        # queries one scan launch takes (include/rabitq_hip.h: "a batch of up to 4096 queries is ONE launch")
 NO_SEED, NO_PREFILTER = 1, 2
-# d -> (n, k, queries).  n: at least three row tiles of the scan (128 rows up to dim 192, 64 up to 448, 32 beyond) and a ragged tail
+# d -> (n, k, queries).  n: many row tiles of the scan and a ragged tail.  The dims here are tile heights RT = 4 (128 rows: up to dim 192)
+# and RT = 1 (32 rows: dim 512 .. 2432) only; RT = 2 (64 rows: dim 256 .. 448) and the boundary dims of every height are in
+# tests/test_exact_scan_instantiations_gpu.py
 SHAPES = {64: (3001, 16, 300), 100: (4003, 64, 40), 128: (6000, 64, 300), 192: (3005, 16, 40), 768: (3003, 16, 40)}
 
 
