@@ -87,7 +87,9 @@ typedef struct {
  * 0.10.0: half-precision rows, additions only -- RQ_ROWS_*, rq_*_rows, rq_row_type, rq_widen*, RQ_ARR_BASE_ROWS;
  * 0.11.0: byte rows, two more values of row_type and no new symbol -- RQ_ROWS_U8, RQ_ROWS_I8;
  * later in 0.11, additions only: exact search -- rq_exact_search*, rq_last_exact_stats; exact range search --
- * rq_exact_range_search*; rq_exact_stats_t.reserved0 became scan_subtiles).
+ * rq_exact_range_search*; rq_exact_stats_t.reserved0 became scan_subtiles;
+ * later in 0.11, additions only: adaptive probing -- rq_probe_rule_t, rq_query_batch_adaptive, rq_query_batch_device_adaptive,
+ * rq_probe_counts_device).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -554,6 +556,42 @@ rq_status rq_exact_range_search_device(const rq_index *idx, const rq_filter *fil
 rq_status rq_exact_range_search(const rq_index *idx, const rq_filter *filter /* nullable */, const float *queries, uint32_t nq,
                                 uint32_t len, const float *radius, const rq_exact_params_t *params /* nullable */,
                                 rq_range_result **out);
+
+/* ---- adaptive probing: each query's probe list cut by centroid distance (later in 0.11, additions only) ----------------- */
+/* Every query of a plain call visits `probe` lists; these entries let each query stop where its centroids stop being near.
+ * Let d_0 <= d_1 <= ... <= d_{m-1}, m = min(probe, k), be the query's coarse distances in visiting order (the f32 values the
+ * coarse ranking produces, what rq_coarse_rank returns).  The rule:
+ *     t = ratio * d_0            one f32 multiplication, round to nearest; ratio = +inf: t = +inf
+ *     p = length of the longest prefix whose entries all satisfy d_j <= t   (a NaN compares false)
+ *     n = min(cap, max(min_probe, p)), clamped to [1, m];  cap = max_probe[query] clamped to [1, m], or m without the array
+ * The query visits its first n lists and no others: its ids, distance bits, count, status and its contribution to the rough /
+ * precise counters of rq_metrics are bit for bit those of the same entry called with probe = n, for both rankers.  ratio = +inf
+ * (or min_probe >= m) cuts nothing; max_probe with ratio = +inf is a per-query nprobe for callers with a rule of their own.
+ * Refused with RQ_ERR_INVALID: a NULL rule, struct_size != sizeof(rq_probe_rule_t), ratio NaN or negative, min_probe == 0,
+ * reserved != 0, and whatever the plain entry refuses (NULL outputs among them; out_nprobe alone may be NULL).
+ * Accepted wherever the plain (or filtered) entry is: every metric and row type, tiered, split-row and mutated indexes, any nq
+ * (a call of more than 65 536 queries applies the rule in every pass).  A call with a rule runs the staged launches at any batch
+ * size (never the few-launch path of batches <= 64 queries) and is planned like a call over caller-supplied probe lists
+ * (DESIGN 4.15).  Not offered with a rule yet: tickets (_begin / _end), the sharded step, range search. */
+typedef struct {
+    uint32_t struct_size;       /* in: sizeof(rq_probe_rule_t) */
+    uint32_t min_probe;         /* >= 1 */
+    float    ratio;             /* >= 0 or +inf */
+    uint32_t reserved;          /* 0 */
+    const uint32_t *max_probe;  /* nullable; nq entries; device memory for the _device entries, host memory otherwise */
+} rq_probe_rule_t;
+rq_status rq_query_batch_device_adaptive(const rq_index *idx, const rq_filter *filter /* nullable */, const float *d_queries,
+                                         uint32_t nq, uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank,
+                                         const rq_probe_rule_t *rule, float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n,
+                                         uint32_t *d_out_nprobe /* nullable; nq: the lists each query visited */);
+rq_status rq_query_batch_adaptive(const rq_index *idx, const rq_filter *filter /* nullable */, const float *queries,
+                                  uint32_t nq, uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank,
+                                  const rq_probe_rule_t *rule, float *out_dist, uint32_t *out_id, uint32_t *out_n,
+                                  uint32_t *out_nprobe /* nullable; nq: the lists each query visited */);
+/* Only the query transform, the rotation, the coarse ranking and the cut: d_out_nprobe[b] = n of query b under the rule.  The cheap
+ * way to look at a rule's distribution before paying for the scans; no counter of rq_metrics moves. */
+rq_status rq_probe_counts_device(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t len, uint32_t probe,
+                                 const rq_probe_rule_t *rule, uint32_t *d_out_nprobe);
 
 /* ---- in-place mutation: add and remove rows ------------------------------------------------------------------------ */
 /* After any sequence of rq_add / rq_remove the index equals, bit for bit, the index rq_build produces from its live rows S in

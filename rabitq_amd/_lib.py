@@ -34,6 +34,7 @@ EXPORTS = [
     "rq_from_arrays_rows", "rq_row_type", "rq_widen", "rq_widen_device",
     "rq_exact_search", "rq_exact_search_device", "rq_last_exact_stats",
     "rq_exact_range_search", "rq_exact_range_search_device",
+    "rq_query_batch_adaptive", "rq_query_batch_device_adaptive", "rq_probe_counts_device",
 ]
 
 
@@ -147,6 +148,12 @@ class ExactStatsT(_Sized):
         "ms_seed", "ms_scan", "ms_exact", "ms_select")] + [
         ("seed_unfilled", C.c_uint32), ("reruns", C.c_uint32), ("candidates", C.c_uint64), ("exact", C.c_uint64),
         ("row_bytes_read", C.c_uint64), ("scan_launches", C.c_uint32), ("scan_subtiles", C.c_uint32)]
+
+
+class ProbeRuleT(_Sized):
+    """rq_probe_rule_t: adaptive probing's cut rule (max_probe: a raw address, device or host as the entry says; 0 = none)."""
+    _fields_ = [("struct_size", C.c_uint32), ("min_probe", C.c_uint32), ("ratio", C.c_float), ("reserved", C.c_uint32),
+                ("max_probe", C.c_void_p)]
 
 
 def build(force: bool = False) -> str:
@@ -281,6 +288,9 @@ def lib():
         "rq_last_exact_stats": (i32, [C.POINTER(ExactStatsT)]),
         "rq_exact_range_search": (i32, [vp, vp, f32p, u32, u32, f32p, C.POINTER(ExactParamsT), pp]),
         "rq_exact_range_search_device": (i32, [vp, vp, f32p, u32, u32, f32p, C.POINTER(ExactParamsT), pp]),
+        "rq_query_batch_adaptive": (i32, [vp, vp, f32p, u32, u32, u32, u32, C.c_int, C.POINTER(ProbeRuleT), f32p, u32p, u32p, u32p]),
+        "rq_query_batch_device_adaptive": (i32, [vp, vp, f32p, u32, u32, u32, u32, C.c_int, C.POINTER(ProbeRuleT), f32p, u32p, u32p, u32p]),
+        "rq_probe_counts_device": (i32, [vp, f32p, u32, u32, u32, C.POINTER(ProbeRuleT), u32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the .so lacks a declared symbol

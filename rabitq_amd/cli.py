@@ -47,6 +47,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--rows", choices=[t.name for t in _lib.ROW_TABLE if t.elem_bytes == 1], default=None,
                     help="build a byte-row index (L2 only): the base is a .bvecs file whose one-byte elements are stored as given, "
                          "dim bytes per vector; the centroids stay an fvecs file")
+    ap.add_argument("--probe-ratio", dest="probe_ratio", type=float, default=None, metavar="R",
+                    help="adaptive probing: every query visits only the lists whose centroid distance is within R times its nearest "
+                         "one's, at most --probe of them (inf: no cut); also prints the mean and maximum number of lists visited")
+    ap.add_argument("--min-probe", dest="min_probe", type=int, default=1, metavar="M", help="with --probe-ratio: never fewer than M lists")
     ap.add_argument("--make-truth", dest="make_truth", action="store_true",
                     help="when the truth path does not exist: compute the exact top-max(topk, 100) of the queries on the GPU "
                          "and write it there as .ivecs (an existing file is left alone)")
@@ -104,6 +108,20 @@ def main(argv=None) -> int:
     n = len(queries)
     print(f"QPS: {n / total_time}, recall: {recall / n}")
     print(f"Metrics [{metrics_str()}]")
+    if args.probe_ratio is not None:      # the same queries, each cut by its centroid distances (one query per call, timed alike)
+        metrics_reset()
+        total_time, recall, visited = 0.0, 0.0, []
+        for i, q in enumerate(queries):
+            t0 = time.perf_counter()
+            _, ids, cnt, npr = index.query_batch_adaptive(np.asarray(q, np.float32)[None, :], args.probe, args.topk, args.probe_ratio,
+                                                          args.min_probe, None, args.heuristic_rank)
+            total_time += time.perf_counter() - t0
+            got = ids[0, :cnt[0]].tolist()
+            recall += calculate_recall(truth[i], got + [-1] * (args.topk - len(got)), args.topk)
+            visited.append(int(npr[0]))
+        print(f"adaptive (ratio {args.probe_ratio}, min {args.min_probe}): QPS: {n / total_time}, recall: {recall / n}, "
+              f"lists visited: mean {np.mean(visited):.2f}, max {max(visited) if visited else 0}")
+        print(f"Metrics [{metrics_str()}]")
     if args.batch > 0:
         q = np.stack(queries)
         t0 = time.perf_counter()
@@ -114,6 +132,19 @@ def main(argv=None) -> int:
                 hits += len(set(ids[j, :cnt[j]].tolist()) & set(truth[s + j][:args.topk].tolist()))
         dt = time.perf_counter() - t0
         print(f"batched ({args.batch}): QPS: {n / dt}, recall: {hits / (n * args.topk)}")
+        if args.probe_ratio is not None:
+            t0 = time.perf_counter()
+            hits, visited = 0, []
+            for s in range(0, n, args.batch):
+                _, ids, cnt, npr = index.query_batch_adaptive(q[s:s + args.batch], args.probe, args.topk, args.probe_ratio, args.min_probe,
+                                                              None, args.heuristic_rank)
+                visited.append(npr)
+                for j in range(ids.shape[0]):
+                    hits += len(set(ids[j, :cnt[j]].tolist()) & set(truth[s + j][:args.topk].tolist()))
+            dt = time.perf_counter() - t0
+            visited = np.concatenate(visited)
+            print(f"batched adaptive ({args.batch}, ratio {args.probe_ratio}, min {args.min_probe}): QPS: {n / dt}, "
+                  f"recall: {hits / (n * args.topk)}, lists visited: mean {visited.mean():.2f}, max {int(visited.max())}")
     return 0
 
 

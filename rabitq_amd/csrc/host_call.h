@@ -159,6 +159,11 @@ static rq_status after_pass(Workspace &ws, const QueryCall &c, const QueryParams
         while (cur < want && !cap_hint.compare_exchange_weak(cur, want)) {}
     }
     if (!pr.overflowed) return RQ_OK;
+    // a cut pass (adaptive probing): the re-runs must see the same cut lists -- the pass's rows, still in `ws`, are their probe lists
+    // (gathered through the row map like a caller's), and they carry no rule
+    QueryCall rc = c;
+    if (c.rule.on() && !c.io.ext_cluster) rc.io.ext_cluster = ws.probe_cluster.p, rc.io.ext_dist = ws.probe_dist.p;
+    rc.rule = ProbeRule{};
     uint32_t cap = qp.cap, hcap = qp.hcap, max_need = 0, max_alen = 0;
     std::vector<uint32_t> over_rows;
     Overflowed ov;
@@ -187,7 +192,7 @@ static rq_status after_pass(Workspace &ws, const QueryCall &c, const QueryParams
         for (size_t o = 0; o < over_rows.size(); o += chunk) {
             uint32_t m = (uint32_t)std::min<size_t>(chunk, over_rows.size() - o);
             PassResult rr;
-            RQC(rerun_rows(*lease.w, c, pass_params(c, m, cap, hcap), over_rows.data() + o, &rr, nullptr));
+            RQC(rerun_rows(*lease.w, rc, pass_params(rc, m, cap, hcap), over_rows.data() + o, &rr, nullptr));
             tot.precise += rr.precise;
             if (rr.overflowed) RQC(collect(*lease.w, m, over_rows.data() + o, still));
         }
@@ -290,6 +295,40 @@ static rq_status query_device(const QueryCall &call, uint32_t nq, Workspace *use
     }
     for (uint32_t i = 0; i < depth; ++i, slot = (slot + 1) % depth) RQC(fl[slot].end(tot));  // oldest first
     return conclude_query(call, nq, tot);
+}
+
+// Adaptive probing's look at a rule (rq_probe_counts_device): the query transform, the rotation, the coarse ranking and the cut of
+// every query -- the front of a pass (Pass::rotate_coarse), nothing behind it.  call.rule.out_nprobe receives the counts; no counter of
+// rq_metrics moves.
+static rq_status probe_counts_device(const QueryCall &call, uint32_t nq) {
+    RQC(validate_call(call.idx, !call.io.d_q || !call.rule.out_nprobe, call.len, call.probe, 1, nullptr));
+    if (nq == 0) return RQ_OK;
+    rq_index *idx = call.idx;
+    WsLease lease(idx, ws_acquire(idx));
+    Workspace &ws = *lease.w;
+    RQC(ws_ensure_stream(ws));
+    const uint32_t m = call.npb();
+    const uint32_t step = (uint32_t)std::min<uint64_t>(RQ_MAX_NQ_PER_PASS, std::max<uint64_t>(1, (1ull << 22) / m));  // (a top-k pass's bounds)
+    for (uint64_t q0 = 0; q0 < nq; q0 += step) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(step, nq - q0);
+        const QueryCall pc = call.at(q0);
+        const QueryParams qp = pass_params(pc, n, 0, 0);
+        RQC(ws.qpad.ensure((uint64_t)n * idx->dim));
+        RQC(ws.y.ensure((uint64_t)n * idx->dim));
+        RQC(ws.dist.ensure((uint64_t)n * idx->k));
+        RQC(ws.probe_dist.ensure((uint64_t)n * m));
+        RQC(ws.probe_cluster.ensure((uint64_t)n * m));
+        RQC(ws.totals.ensure(16));
+        PassPlan pl{};
+        pl.nprobe = m, pl.npairs = n * m;
+        ws.prof.reset(0, ws.stream);
+        Pass c{idx, ws, qp, pl, ws.prof, ws.stream, idx->dim, idx->k, idx->W, n, 1u, m, n * m, pc.io, nullptr, nullptr, pc.io.d_q,
+               ws.probe_cluster.p, ws.probe_dist.p};
+        RQC(c.rotate_coarse());
+        HIPC(hipStreamSynchronize(ws.stream));
+        HIPC(hipGetLastError());
+    }
+    return RQ_OK;
 }
 
 // The same call split in two, so that a caller can keep several batches in flight (each on its own workspace and HIP stream): a

@@ -23,6 +23,10 @@ struct QueryParams {
     // threshold has nothing to learn), and behind the exact distances the pass only counts each query's hits (ws.range_hits) --
     // no run ordering, no replay, no result rows; topk is 1 (the ranker state is allocated, not used).
     bool range = false;
+    // Adaptive probing (rq_probe_rule_t; kernels_coarse.h: probe_cut_kernel): the pass cuts every query's ranked probe row at the end of
+    // rotate_coarse and is planned like a pass over caller-supplied lists (plan_pass).  Overflow re-runs carry no rule:
+    // they take the pass's cut rows as their probe lists.
+    ProbeRule rule;
 };
 
 // The device arrays of a query call, or of one pass of it (QueryCall::at).
@@ -44,6 +48,7 @@ struct QueryCall {
     uint32_t len = 0, probe = 0, topk = 0;
     bool heuristic = false;
     QueryIO io;
+    ProbeRule rule;  // adaptive probing (rule.on()): caps and the nprobe output advance with the pass
     uint32_t npb() const { return std::min(probe, idx->k); }  // columns of the probe lists
     // The call of a pass that starts at query q0: the one place that knows the arrays' strides.
     QueryCall at(uint64_t q0) const {
@@ -55,13 +60,15 @@ struct QueryCall {
         c.io.ext_cluster = io.ext_cluster ? io.ext_cluster + q0 * npb() : nullptr;
         c.io.ext_dist = io.ext_dist ? io.ext_dist + q0 * npb() : nullptr;
         c.io.thr_init = io.thr_init ? io.thr_init + q0 : nullptr;
+        c.rule.caps = rule.caps ? rule.caps + q0 : nullptr;
+        c.rule.out_nprobe = rule.out_nprobe ? rule.out_nprobe + q0 : nullptr;
         return c;
     }
 };
 // The parameters of a pass of `c` over nq queries with the given capacities (what the call decides; the caller adds seg_final / ext_lists / range).
 static QueryParams pass_params(const QueryCall &c, uint32_t nq, uint32_t cap, uint32_t hcap) {
     QueryParams qp{nq, c.len, c.probe, c.topk, c.heuristic, cap, hcap};
-    qp.thr_init = c.io.thr_init, qp.filter = c.filter;
+    qp.thr_init = c.io.thr_init, qp.filter = c.filter, qp.rule = c.rule;
     return qp;
 }
 
@@ -167,8 +174,13 @@ static inline bool rerank_ring_rule(uint32_t dim, uint32_t nprobe, uint32_t dbg)
 // each, which one block per query would rerank and order alone)
 static inline bool finish_large(const PassPlan &pl, const QueryParams &qp) { return qp.range || pl.large || qp.cap > 4 * RQ_DEFAULT_CAP; }
 
-// has_row_map: the pass re-runs overflowed queries of an earlier one; ext_lists: the probe lists come from the caller.
-static void plan_pass(const rq_index *idx, const QueryParams &qp, bool has_row_map, bool ext_lists, PassPlan &pl) {
+// has_row_map: the pass re-runs overflowed queries of an earlier one; caller_lists: the probe lists come from the caller.
+// A cut pass (qp.rule.on(): adaptive probing) is planned as a pass over caller-supplied lists: its rows hold "no list" slots like a
+// shard's, so it never takes the small-batch path (sb_query_kernel selects its lists itself) and gives up the placed final stage
+// and the slot_hi / qn_slots reach bounds.  (The bounds would still hold for a prefix cut -- the slots that remain keep their
+// stream positions -- and only the placed stage's kernels would need reading; neither has been measured on a cut pass yet.)
+static void plan_pass(const rq_index *idx, const QueryParams &qp, bool has_row_map, bool caller_lists, PassPlan &pl) {
+    const bool ext_lists = caller_lists || qp.rule.on();
     const uint32_t dim = idx->dim, k = idx->k, W = idx->W;
     const uint32_t nq = qp.nq, nprobe = std::min(qp.probe, k), topk = qp.topk;
     const uint32_t npairs = nq * nprobe;

@@ -247,6 +247,15 @@ struct Pass {
             launch_select(ws.dist.p, k, nprobe, ws.probe_cluster.p, ws.probe_dist.p, 0, nprobe, nq, st);
             pf.end();
         }
+        // adaptive probing: cut the ranked rows in place, whichever form filled them (the pre-filtered form's fallback rows are
+        // finished inside its launches); on the pass's stream, no host wait
+        if (qp.rule.on() && !io.ext_cluster) {
+            pf.begin(PF_SELECT);
+            RQC(ws.probe_n.ensure(nq));
+            probe_cut_kernel<<<ceil_div(nq, 4), 256, 0, st>>>(ws.probe_cluster.p, ws.probe_dist.p, nprobe, nq, qp.rule.ratio, qp.rule.min_probe,
+                                                              qp.rule.caps, ws.probe_n.p, qp.rule.out_nprobe);
+            pf.end();
+        }
         return RQ_OK;
     }
 

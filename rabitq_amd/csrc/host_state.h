@@ -207,6 +207,7 @@ struct Workspace {
     DevBuf<uint32_t> retry_rows;
     DevBuf<uint32_t> q_hist, q_start, q_order;  // rerank order of a large batch (queries grouped by nearest list)
     DevBuf<uint32_t> live_list;                 // sharded passes: the (query, list) pairs whose list has members here, + their count
+    DevBuf<uint32_t> probe_n;                   // adaptive probing: per query, the lists its cut row keeps (probe_cut_kernel)
     DevBuf<uint32_t> coarse_redo;               // pre-filtered coarse ranking over more than 8192 lists: rows left to the block-per-query selection
     DevBuf<uint32_t> pair_rank, rank_base;      // group_rank_kernel: places of a big stage's pairs inside their groups
     // final stage placed ahead of the quantisation (option prep_placement): its tile images, the pairs' stream positions, and its own

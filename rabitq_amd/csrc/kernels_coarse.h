@@ -1066,3 +1066,54 @@ __global__ __launch_bounds__(256) void refine_candidates_kernel(float *__restric
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     coarse_refine_tail(wn, c2, centroids, yr, dim, nprobe, b, out_cluster, out_dist, out_stride);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Adaptive probing (rq_probe_rule_t): a query's probe row d_0 <= d_1 <= ... <= d_{m-1} is cut behind the longest prefix whose
+// entries all satisfy d_j <= t, t = ratio * d_0 (one f32 multiplication; ratio = +inf: t = +inf, also where d_0 = 0); a NaN
+// compares false.  n = min(cap, max(min_probe, prefix)) clamped to [1, m], cap = the query's entry of `caps` clamped to [1, m] (no
+// array: m).  Slots n .. m-1 become (0xFFFFFFFF, +inf) = "no list", which every kernel behind the coarse ranking skips before any
+// per-pair work; n goes to row_n and, if given, to out_n.
+// One wave per query, 64 slots of the row per step: a ballot of the test, the first clear bit ends the prefix.
+// ------------------------------------------------------------------------------------------------
+struct ProbeRule {
+    float ratio = 0.0f;
+    uint32_t min_probe = 0;             // 0: no rule (every other field is ignored)
+    const uint32_t *caps = nullptr;     // device, one entry per query of the pass; or null
+    uint32_t *out_nprobe = nullptr;     // device, one entry per query of the pass; or null
+    bool on() const { return min_probe != 0; }
+};
+__global__ __launch_bounds__(256) void probe_cut_kernel(uint32_t *__restrict__ probe_cluster, float *__restrict__ probe_dist, uint32_t m,
+                                                        uint32_t nq, float ratio, uint32_t min_probe, const uint32_t *__restrict__ caps,
+                                                        uint32_t *__restrict__ row_n, uint32_t *__restrict__ out_n) {
+    const uint32_t lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= nq || m == 0) return;  // (wave-uniform)
+    uint32_t *pc = probe_cluster + (uint64_t)b * m;
+    float *pd = probe_dist + (uint64_t)b * m;
+    const float inf = __builtin_inff();
+    const float t = ratio == inf ? inf : ratio * pd[0];
+    uint32_t p = 0;
+    for (uint32_t s0 = 0; s0 < m; s0 += 64) {
+        const uint32_t s = s0 + lane, width = m - s0 < 64u ? m - s0 : 64u;
+        const bool ok = s < m && pd[s] <= t;
+        const unsigned long long have = width == 64u ? ~0ull : (1ull << width) - 1ull;
+        const unsigned long long clear = ~__ballot(ok) & have;
+        if (clear) {
+            p += (uint32_t)__ffsll(clear) - 1u;
+            break;
+        }
+        p += width;
+    }
+    uint32_t cap = m;
+    if (caps) {
+        const uint32_t c = caps[b];
+        cap = c < 1u ? 1u : (c > m ? m : c);
+    }
+    uint32_t n = p > min_probe ? p : min_probe;
+    n = n < cap ? n : cap;
+    n = n < 1u ? 1u : (n > m ? m : n);
+    for (uint32_t s = n + lane; s < m; s += 64) pc[s] = 0xFFFFFFFFu, pd[s] = inf;
+    if (lane == 0) {
+        row_n[b] = n;
+        if (out_n) out_n[b] = n;
+    }
+}

@@ -895,6 +895,65 @@ rq_status rq_query_batch_filtered(const rq_index *idx, const rq_filter *filter, 
     return query_batch_host(idx, filter, queries, nq, len, probe, topk, heuristic_rank, out_dist, out_id, out_n);
 }
 
+// ---- adaptive probing: each query's probe list cut by centroid distance (kernels_coarse.h: probe_cut_kernel) ----
+static rq_status probe_rule_check(const rq_probe_rule_t *rule, const uint32_t *d_caps, uint32_t *d_out_nprobe, ProbeRule *out) {
+    if (!rule) return fail(RQ_ERR_INVALID, "null rule");
+    if (rule->struct_size != sizeof(rq_probe_rule_t)) return fail(RQ_ERR_INVALID, "rq_probe_rule_t: struct_size is not this library's sizeof(rq_probe_rule_t)");
+    if (rule->min_probe == 0) return fail(RQ_ERR_INVALID, "rq_probe_rule_t: min_probe must be >= 1");
+    if (!(rule->ratio >= 0.0f)) return fail(RQ_ERR_INVALID, "rq_probe_rule_t: ratio must be >= 0 or +inf");
+    if (rule->reserved != 0) return fail(RQ_ERR_INVALID, "rq_probe_rule_t: reserved must be 0");
+    out->ratio = rule->ratio, out->min_probe = rule->min_probe, out->caps = d_caps, out->out_nprobe = d_out_nprobe;
+    return RQ_OK;
+}
+
+rq_status rq_query_batch_device_adaptive(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
+                                         uint32_t probe, uint32_t topk, int heuristic_rank, const rq_probe_rule_t *rule,
+                                         float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n, uint32_t *d_out_nprobe) {
+    QueryCall call = topk_call(idx, filter, len, probe, topk, heuristic_rank, {d_queries, d_out_dist, d_out_id, d_out_n});
+    RQC(probe_rule_check(rule, rule ? rule->max_probe : nullptr, d_out_nprobe, &call.rule));
+    return query_device(call, nq, nullptr);
+}
+
+rq_status rq_probe_counts_device(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t len, uint32_t probe,
+                                 const rq_probe_rule_t *rule, uint32_t *d_out_nprobe) {
+    QueryCall call = topk_call(idx, nullptr, len, probe, 1, 0, {d_queries});
+    RQC(probe_rule_check(rule, rule ? rule->max_probe : nullptr, d_out_nprobe, &call.rule));
+    return probe_counts_device(call, nq);
+}
+
+// (host pointers: queries, caps and the four outputs staged through one device block of this thread)
+static thread_local HostStaging g_staging_adaptive;
+rq_status rq_query_batch_adaptive(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len,
+                                  uint32_t probe, uint32_t topk, int heuristic_rank, const rq_probe_rule_t *rule, float *out_dist,
+                                  uint32_t *out_id, uint32_t *out_n, uint32_t *out_nprobe) {
+    RQC(ensure_device());
+    if (!idx || !queries || !out_dist || !out_id || !out_n) return fail(RQ_ERR_INVALID, "null argument");
+    ProbeRule pr;
+    RQC(probe_rule_check(rule, nullptr, nullptr, &pr));
+    if (filter && filter->idx != idx) return fail(RQ_ERR_INVALID, "the filter was made for another index");
+    if (nq == 0) return RQ_OK;
+    if (topk == 0) return fail(RQ_ERR_UNSUPPORTED, "topk must be in [1, 2048]");
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t qb = pad((size_t)nq * len * 4), ob = pad((size_t)nq * topk * 4), nb = pad((size_t)nq * 4);
+    void *blk;
+    RQC(g_staging_adaptive.get(0, qb + 2 * ob + 3 * nb, &blk));
+    char *d = static_cast<char *>(blk);
+    float *dq = (float *)d, *dd = (float *)(d + qb);
+    uint32_t *di = (uint32_t *)(d + qb + ob), *dn = (uint32_t *)(d + qb + 2 * ob), *dnp = (uint32_t *)(d + qb + 2 * ob + nb),
+             *dcap = (uint32_t *)(d + qb + 2 * ob + 2 * nb);
+    HIPC(hipMemcpy(dq, queries, (size_t)nq * len * 4, hipMemcpyHostToDevice));
+    if (rule->max_probe) HIPC(hipMemcpy(dcap, rule->max_probe, (size_t)nq * 4, hipMemcpyHostToDevice));
+    QueryCall call = topk_call(idx, filter, len, probe, topk, heuristic_rank, {dq, dd, di, dn});
+    call.rule = pr, call.rule.caps = rule->max_probe ? dcap : nullptr, call.rule.out_nprobe = dnp;
+    const rq_status s = query_device(call, nq, nullptr);
+    if (s != RQ_OK && s != RQ_ERR_EMPTY) return s;
+    HIPC(hipMemcpy(out_dist, dd, (size_t)nq * topk * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(out_id, di, (size_t)nq * topk * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(out_n, dn, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    if (out_nprobe) HIPC(hipMemcpy(out_nprobe, dnp, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    return s;
+}
+
 // ---- range search: every neighbour inside a per-query radius, as a result object sized by the library (host_range.h) ----
 rq_status rq_range_search_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
                                  uint32_t probe, const float *d_radius, rq_range_result **out) {

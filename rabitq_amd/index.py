@@ -574,6 +574,109 @@ class RaBitQ:
                 lo = mid
         return hi, at(hi)
 
+    # ---- adaptive probing: each query's probe list cut by centroid distance (rq_probe_rule_t) ----
+    @staticmethod
+    def _probe_rule(ratio, min_probe, caps_addr):
+        """-> the rq_probe_rule_t of (ratio, min_probe) with max_probe at the raw address caps_addr (None: no array)."""
+        return _lib.ProbeRuleT(min_probe=int(min_probe), ratio=float(ratio), reserved=0, max_probe=caps_addr)
+
+    @staticmethod
+    def _caps(max_probe, B):
+        """max_probe= -> None, or a contiguous uint32[B] (a scalar is one cap for every query)."""
+        if max_probe is None:
+            return None
+        return np.array(np.broadcast_to(np.asarray(max_probe, dtype=np.uint32), (B,)), dtype=np.uint32, order="C")   # (a writable copy)
+
+    def query_batch_adaptive(self, queries, probe: int, topk: int, ratio: float = float("inf"), min_probe: int = 1, max_probe=None,
+                             heuristic_rank: bool = False, filter: Filter = None):
+        """query_batch with every query's probe list cut by centroid distance -> (dist, ids, counts, nprobe uint32[B]).
+        With d_0 <= d_1 <= ... the query's coarse distances over its min(probe, k) nearest lists, the query visits
+        n = min(cap, max(min_probe, p)) of them, p = the longest prefix with d_j <= ratio * d_0 (f32) and cap = its entry of
+        max_probe (None: no cap); its row is exactly that of query_batch(probe=n).  ratio=inf cuts nothing; max_probe with
+        ratio=inf is a per-query nprobe."""
+        q = _f32(queries)
+        if q.ndim != 2:
+            raise _lib.RabitqError(-1, "queries must be 2-D")
+        B = q.shape[0]
+        d = np.full((B, max(topk, 1)), np.nan, dtype=np.float32)
+        ids = np.full((B, max(topk, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        cnt = np.zeros(B, dtype=np.uint32)
+        npr = np.zeros(B, dtype=np.uint32)
+        caps = self._caps(max_probe, B)
+        rule = self._probe_rule(ratio, min_probe, caps.ctypes.data if caps is not None else None)
+        st = lib().rq_query_batch_adaptive(self._h, _fh(filter), _addr(q), B, q.shape[1], probe, topk, int(heuristic_rank),
+                                           C.byref(rule), _addr(d), _addr(ids), _addr(cnt), _addr(npr))
+        if st != _lib.RQ_ERR_EMPTY:
+            check(st)
+        return d, ids, cnt, npr
+
+    def query_batch_adaptive_device(self, q_ptr: int, nq: int, length: int, probe: int, topk: int, out_dist_ptr: int,
+                                    out_id_ptr: int, out_n_ptr: int, out_nprobe_ptr: int = None, ratio: float = float("inf"),
+                                    min_probe: int = 1, max_probe_ptr: int = None, heuristic_rank: bool = False, filter: Filter = None):
+        """query_batch_adaptive with queries, caps (max_probe_ptr: uint32[nq] or None) and outputs already in device memory (raw
+        addresses; out_nprobe_ptr may be None)."""
+        rule = self._probe_rule(ratio, min_probe, max_probe_ptr)
+        check(lib().rq_query_batch_device_adaptive(self._h, _fh(filter), C.c_void_p(q_ptr), nq, length, probe, topk,
+                                                   int(heuristic_rank), C.byref(rule), C.c_void_p(out_dist_ptr),
+                                                   C.c_void_p(out_id_ptr), C.c_void_p(out_n_ptr), C.c_void_p(out_nprobe_ptr)))
+
+    def probe_counts(self, queries, probe: int, ratio: float, min_probe: int = 1, max_probe=None) -> np.ndarray:
+        """How many lists each query would visit under the rule of query_batch_adaptive -> uint32[B].  Runs only the query
+        transform, the rotation, the coarse ranking and the cut (rq_probe_counts_device); the arrays travel through torch."""
+        import torch
+        q = _f32(queries)
+        if q.ndim != 2:
+            raise _lib.RabitqError(-1, "queries must be 2-D")
+        B = q.shape[0]
+        _lib.check(lib().rq_init(0))
+        dq = torch.from_numpy(q).cuda()
+        caps = self._caps(max_probe, B)
+        dcaps = torch.from_numpy(caps.view(np.int32)).cuda() if caps is not None else None
+        out = torch.zeros(max(B, 1), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        rule = self._probe_rule(ratio, min_probe, dcaps.data_ptr() if dcaps is not None else None)
+        check(lib().rq_probe_counts_device(self._h, C.c_void_p(dq.data_ptr()), B, q.shape[1], probe, C.byref(rule),
+                                           C.c_void_p(out.data_ptr())))
+        return out[:B].cpu().numpy().view(np.uint32).copy()
+
+    def tune_probe_ratio(self, queries, probe: int, topk: int, target_recall: float, min_probe: int = 1, filter: Filter = None):
+        """A ratio for query_batch_adaptive(queries, probe, topk, ratio, min_probe) whose recall on these queries reaches
+        target_recall -> (ratio, recall, mean_nprobe).  The exact answer is computed once.  If ratio=inf (no cut) misses the target:
+        (inf, that recall, min(probe, k)).  Otherwise 12 steps of geometric bisection on the ratio between 1 and the largest finite
+        d_{m-1} / d_0 of the batch; the smallest ratio tried that meets the target is returned.  As with tune_nprobe, recall is
+        only nearly monotone in the ratio: a smaller ratio than the one returned may also meet the target."""
+        _, eids, ecnt = self.exact_search(queries, topk, filter)
+        m = min(int(probe), self.k)
+
+        def at(r):
+            _, ids, cnt, npr = self.query_batch_adaptive(queries, probe, topk, r, min_probe, None, False, filter)
+            return self._recall_of(ids, cnt, eids, ecnt), float(np.mean(npr)) if len(npr) else float(m)
+
+        rec_inf, _ = at(float("inf"))
+        if rec_inf < target_recall:
+            return float("inf"), rec_inf, float(m)
+        q = _f32(queries)
+        cd = np.empty((q.shape[0], m), dtype=np.float32)
+        cc = np.empty((q.shape[0], m), dtype=np.uint32)
+        check(lib().rq_coarse_rank(self._h, _addr(q), q.shape[0], q.shape[1], m, _addr(None), _addr(cc), _addr(cd)))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            spread = cd[:, -1].astype(np.float64) / cd[:, 0].astype(np.float64)
+        spread = spread[np.isfinite(spread)]
+        hi = float(np.float32(max(1.0, float(spread.max()) if spread.size else 1.0)) * np.float32(1.0 + 2.0 ** -20))
+        rec_hi, mean_hi = at(hi)
+        if rec_hi < target_recall:          # (rows whose d_0 is 0 or not finite are cut by every finite ratio)
+            return float("inf"), rec_inf, float(m)
+        best = (hi, rec_hi, mean_hi)
+        lo = 1.0
+        for _ in range(12):
+            mid = float(np.sqrt(lo * hi))
+            rec, mean = at(mid)
+            if rec >= target_recall:
+                hi, best = mid, (mid, rec, mean)
+            else:
+                lo = mid
+        return best
+
     # ---- range search: every neighbour within a per-query radius --------------------------------
     @property
     def ip_params(self):
