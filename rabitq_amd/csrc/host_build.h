@@ -7,7 +7,6 @@
 // fp16 shadow of the raw vectors (kernels_rerank.h: rerank pre-filter).  Only for untiered indexes, and only when the
 // 2*dim bytes per vector still leave the query workspaces their room; it costs one streaming pass over `base`.
 #define RQ_SHADOW_MIN_ROWS 1ull
-static std::atomic<int> g_rerank_shadow{2};  // shadow rows for the rerank pre-filter: 0 never, 1 fp16 when they fit, 2 8-bit (one affine map per list) when they fit
 static rq_status derive_shadow_rows(rq_index *idx);
 static rq_status finish_index(rq_index *idx) {
     // derived state: transposed centroids, longest list
@@ -170,7 +169,6 @@ static void launch_assign(const float *xrot, const rq_index *idx, uint64_t n, ui
 
 // Nearest list through the matrix cores (kernels_build.h: assign_approx_kernel + assign_refine_kernel; exact results):
 // what it needs besides the index's rotated centroids, built once per build, plus per-chunk scratch.
-static std::atomic<int> g_assign_impl{0};  // 0 = matrix-core pre-filter where the kernel exists (default), 1 = exact-order VALU kernels only
 struct AssignAux {
     DevBuf<uint16_t> cent_bf;  // k x dim bf16
     DevBuf<float> cnorm, redo_x, redo_dist;
@@ -178,7 +176,6 @@ struct AssignAux {
     float cmax = INFINITY;
     uint64_t redone = 0;  // vectors that went through the exact-order kernel (no or too many candidates)
 };
-static bool assign_has_mfma(uint32_t W) { return W == 1 || W == 2 || W == 3 || W == 4 || W == 6 || W == 8 || W == 12; }
 static rq_status assign_aux_init(const rq_index *idx, AssignAux &ax, uint64_t chunk_rows) {
     const uint64_t cells = (uint64_t)idx->k * idx->dim;
     RQC(ax.cent_bf.alloc(cells));
@@ -201,23 +198,20 @@ static rq_status launch_assign_prefiltered(const float *xrot, const rq_index *id
                                            float *dist) {
     if (n == 0) return RQ_OK;
     const uint32_t W = idx->W, k = idx->k;
-    if (g_assign_impl.load() == 1 || !assign_has_mfma(W) || !std::isfinite(ax.cmax)) {
+    if (g_assign_impl.load() == 1 || !bf16_tile_has(W) || !std::isfinite(ax.cmax)) {
         launch_assign(xrot, idx, n, label, dist, nullptr);
         return RQ_OK;
     }
     HIPC(hipMemsetAsync(ax.cand_cnt.p, 0, n * 4, nullptr));
     HIPC(hipMemsetAsync(ax.redo_cnt.p, 0, 4, nullptr));
 #define RQ_ASG(WW, NT)                                                                                                   \
-    assign_approx_kernel<WW, NT><<<ceil_div(n, 128 * NT), 256, assign_lds_bytes<WW, NT>(), nullptr>>>(                  \
-        xrot, ax.cent_bf.p, ax.cnorm.p, ax.cmax, n, k, ax.cand.p, ax.cand_cnt.p)
+    case WW:                                                                                                             \
+        assign_approx_kernel<WW, NT><<<ceil_div(n, 128 * NT), 256, assign_lds_bytes<WW, NT>(), nullptr>>>(              \
+            xrot, ax.cent_bf.p, ax.cnorm.p, ax.cmax, n, k, ax.cand.p, ax.cand_cnt.p);                                    \
+        break;
     switch (W) {
-        case 1: RQ_ASG(1, 2); break;
-        case 2: RQ_ASG(2, 2); break;
-        case 3: RQ_ASG(3, 1); break;
-        case 4: RQ_ASG(4, 1); break;
-        case 6: RQ_ASG(6, 1); break;
-        case 8: RQ_ASG(8, 1); break;
-        default: RQ_ASG(12, 1); break;
+        RQ_BF16_TILE_SHAPES(RQ_ASG)
+        default: break;  // (not reached: bf16_tile_has above is made from the same list)
     }
 #undef RQ_ASG
     assign_refine_kernel<<<ceil_div(2 * n, 256), 256>>>(xrot, idx->centroids.p, n, idx->dim, ax.cand.p, ax.cand_cnt.p, label, dist,
@@ -241,8 +235,6 @@ static rq_status launch_assign_prefiltered(const float *xrot, const rq_index *id
 // query workspaces and the caller), ~0 = everything in HBM, else an explicit cap ("base_device_mb" option / the
 // builder's argument).  The rest goes to pinned, device-mapped host memory.
 // ------------------------------------------------------------------------------------------------
-static std::atomic<int64_t> g_base_device_mb{-1};  // -1 = automatic
-static std::atomic<int> g_split_rows{1};           // indexes built from now on with no room for shadow rows keep their raw vectors as split rows (0: plain f32, the round-4 layout; 2: always)
 #define RQ_HBM_RESERVE_BYTES (12ull << 30)
 // h_offsets: the k+1 list offsets on the host (the split is per list)
 static rq_status alloc_base_tiers(rq_index *idx, uint64_t budget_bytes, const uint32_t *h_offsets) {
@@ -431,7 +423,7 @@ static rq_status builder_alloc_pass1(rq_builder *b) {
     if (metric_refuses_rows(idx->metric)) RQC(b->ip_bad.alloc(1));
     RQC(b->xrot.alloc(chunk * dim));
     if (idx->rows.typed()) RQC(b->wide.alloc(chunk * b->d));
-    if (assign_has_mfma(idx->W) && g_assign_impl.load() != 1) RQC(assign_aux_init(idx, b->assign_aux, chunk));
+    if (bf16_tile_has(idx->W) && g_assign_impl.load() != 1) RQC(assign_aux_init(idx, b->assign_aux, chunk));
     for (auto &e : b->ev) HIPC(hipEventCreate(&e));
     return RQ_OK;
 }

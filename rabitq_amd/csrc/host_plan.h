@@ -166,13 +166,21 @@ static void plan_stages(const rq_index *idx, uint32_t nprobe, uint64_t first_hi,
 // its two slots take at most 1 + 16 + 64 KB there, inside the 156 KB the kernels are registered with (ensure_kernel_attributes).
 // scan_debug bit 32768 (measurements, tests) keeps the register kernel.
 static inline uint32_t rerank_ring_lds(uint32_t dim, uint32_t nprobe) { return dim * 4u + nprobe * 16u + q8_ring_bytes(RQ_RING_V, dim); }
+static inline bool rerank_ring_has(uint32_t dim) {  // (dim is a multiple of 64)
+    switch (dim / 16) { RQ_RING8_NPC(RQ_SHAPE_CASE) return true; default: return false; }
+}
 static inline bool rerank_ring_rule(uint32_t dim, uint32_t nprobe, uint32_t dbg) {
-    return !(dbg & 32768u) && (dim == 64 || dim == 128 || dim == 192 || dim == 256) && nprobe <= RQ_ACC8_LDS_PROBES;
+    return !(dbg & 32768u) && rerank_ring_has(dim) && nprobe <= RQ_ACC8_LDS_PROBES;
 }
 // whether a pass's stages finish with the full-chip kernels (stage_finish_large: rerank, run-directory sort, replay) -- large batches,
 // range calls, and small batches whose survivor buffers are large (queries re-run after an overflow: tens of thousands of survivors
 // each, which one block per query would rerank and order alone)
 static inline bool finish_large(const PassPlan &pl, const QueryParams &qp) { return qp.range || pl.large || qp.cap > 4 * RQ_DEFAULT_CAP; }
+
+// the widths with a small-batch path (sb_query_kernel: host_query.h launches it, inst_small_filt.hip its filtered instantiations)
+static inline bool small_batch_has(uint32_t W) {
+    switch (W) { RQ_SMALL_BATCH_WIDTHS(RQ_SHAPE_CASE) return true; default: return false; }
+}
 
 // has_row_map: the pass re-runs overflowed queries of an earlier one; caller_lists: the probe lists come from the caller.
 // A cut pass (qp.rule.on(): adaptive probing) is planned as a pass over caller-supplied lists: its rows hold "no list" slots like a
@@ -203,7 +211,7 @@ static void plan_pass(const rq_index *idx, const QueryParams &qp, bool has_row_m
 
     // ---- the stage list ---------------------------------------------------------------------------------------------
     // small batches: few, fat launches (kernels_small.h)
-    const bool sb_w = W == 1 || W == 2 || W == 4 || W == 8 || W == 12 || W == 16;
+    const bool sb_w = small_batch_has(W);
     pl.small = g_small_batch.load() == 0 && nq <= RQ_SB_MAX_NQ && !ext_lists && !has_row_map && !qp.thr_init && sb_w &&
                k <= RQ_SB_MAX_K && nprobe <= 64 && topk <= RQ_SB_MAX_TOPK && qp.cap <= 4 * RQ_DEFAULT_CAP;
     // A filtered pass (option small_batch_filtered: 0 never, 1 automatic, 2 whenever the shape allows): the block's stage boundaries

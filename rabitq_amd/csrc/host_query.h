@@ -140,14 +140,12 @@ static void launch_sb_query_w(int mode, uint32_t nq, size_t dyn, hipStream_t st,
 }
 static void launch_sb_query(uint32_t W, int mode, bool filtered, uint32_t nq, size_t dyn, hipStream_t st, const SbArgs &sa) {
     if (filtered) return launch_sb_query_filtered(W, mode, nq, dyn, st, sa);
+#define RQ_SBQ(WW) case WW: launch_sb_query_w<WW>(mode, nq, dyn, st, sa); break;
     switch (W) {
-        case 1: launch_sb_query_w<1>(mode, nq, dyn, st, sa); break;
-        case 2: launch_sb_query_w<2>(mode, nq, dyn, st, sa); break;
-        case 4: launch_sb_query_w<4>(mode, nq, dyn, st, sa); break;
-        case 8: launch_sb_query_w<8>(mode, nq, dyn, st, sa); break;
-        case 12: launch_sb_query_w<12>(mode, nq, dyn, st, sa); break;
-        default: launch_sb_query_w<16>(mode, nq, dyn, st, sa); break;
+        RQ_SMALL_BATCH_WIDTHS(RQ_SBQ)
+        default: break;  // (not reached: plan_pass takes the path for small_batch_has(W) only, which is made from the same list)
     }
+#undef RQ_SBQ
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -637,10 +635,12 @@ struct Pass {
         // past the first stage the thresholds are finite: survivors go through the shadow rows first (the plan's rule, and its route)
         const bool prefilter = r.s.prefilter;
         if (r.s.rerank_ring) {
-            if (dim == 64) launch_ring8<4>(gx, seg);
-            else if (dim == 128) launch_ring8<8>(gx, seg);
-            else if (dim == 192) launch_ring8<12>(gx, seg);
-            else launch_ring8<16>(gx, seg);
+#define RQ_RING8(NPC) case NPC: launch_ring8<NPC>(gx, seg); break;
+            switch (dim / 16) {
+                RQ_RING8_NPC(RQ_RING8)
+                default: break;  // (not reached: rerank_ring_rule admits the dimensions of the same list only)
+            }
+#undef RQ_RING8
         } else if (r.s.rerank_q8)
             accurate_filtered8_kernel<<<dim3(gx, nq), 256, (size_t)dim * sizeof(float) + (nprobe <= RQ_ACC8_LDS_PROBES ? (size_t)nprobe * 16 : 0), st>>>(
                 ws.surv.p, ws.surv_cnt.p, seg, idx->base.p, idx->base_q8.p, idx->list_q8.p, qpad, dim, rerank_order, ws.thr.p,

@@ -881,7 +881,7 @@ __global__ __launch_bounds__(256, (W <= 4 ? 2 : 1)) void coarse_approx_kernel(co
 // Rows past the last list are zeros with the norm RQ_COARSE_PAD_NORM: finite (no inf - inf), above every finite T2 (|T2| < 3.0e38
 // is what "finite" means below) and, should it ever be a tile's minimum, a tau that is not "finite" either; the last tile's are
 // masked by index as well.
-// dynamic LDS: the two images of CentTile<W>, then 4 waves x NT x ntile x 32 tile keys (coarse_candidates_lds_bytes, host_state.h).
+// dynamic LDS: the two images of CentTile<W>, then 4 waves x NT x ntile x 32 tile keys (coarse_candidates_lds_bytes, host_launch.h).
 // ------------------------------------------------------------------------------------------------
 #define RQ_COARSE_PAD_NORM 3.0e38f
 // the bisection stops at any bound that selects nprobe .. nprobe + RQ_FUSED_WINDOW tile keys: narrower than bisect_loose's 12, because

@@ -33,7 +33,10 @@
 #include "kernels_range.h"
 #include "kernels_small.h"
 
+#include "kernel_shapes.h"
 #include "host_state.h"
+#include "host_options.h"
+#include "host_launch.h"
 #include "host_metric.h"
 #include "host_plan.h"
 #include "host_query.h"
@@ -1117,150 +1120,21 @@ rq_status rq_metrics_reset(void) {
 
 rq_status rq_set_option(const char *name, int value) {
     if (!name) return fail(RQ_ERR_INVALID, "null option name");
-    if (std::string(name) == "scan_impl") {
-        if (value < 0 || value > 2) return fail(RQ_ERR_INVALID, "scan_impl must be 0 (auto), 1 (valu) or 2 (mfma)");
-        g_scan_impl = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "cluster_major_div") {  // developer knob (results identical for every value)
-        if (value < 1 || value > 4096) return fail(RQ_ERR_INVALID, "cluster_major_div must be in [1, 4096]");
-        g_cluster_major_div = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "large_batch_from") {  // developer knob (results identical for every value): queries from which a batch takes the large-batch form of the stages
-        if (value < 2 || value > (1 << 20)) return fail(RQ_ERR_INVALID, "large_batch_from must be in [2, 2^20]");
-        g_large_from = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "stage_settle_pct") {  // developer knob (results identical for every value): end of the early stages of a large batch, percent of the average list length
-        if (value < 1 || value > 400) return fail(RQ_ERR_INVALID, "stage_settle_pct must be in [1, 400]");
-        g_stage_settle_pct = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "stage_growth") {  // geometric growth of the early stages (0 = default: 16 below 32 768 queries, 8 from there on)
-        if (value != 0 && (value < 2 || value > 64)) return fail(RQ_ERR_INVALID, "stage_growth must be 0 or in [2, 64]");
-        g_stage_growth = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "base_device_mb") {  // HBM budget of the raw vectors for indexes built / loaded from now on:
-                                                  // -1 = automatic (default), else MiB; the rest goes to pinned host memory
-        if (value < -1) return fail(RQ_ERR_INVALID, "base_device_mb must be >= -1");
-        g_base_device_mb = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "pass_overlap") {  // a call of several passes: two in flight (1, default) or one after the other (0); results identical
-        if (value < 0 || value > 1) return fail(RQ_ERR_INVALID, "pass_overlap must be 0 or 1");
-        g_pass_overlap = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "split_rows") {  // tiered indexes built / loaded from now on: raw vectors as two 16-bit planes (1, default) or plain f32 (0)
-        if (value < 0 || value > 2) return fail(RQ_ERR_INVALID, "split_rows must be 0, 1 or 2");
-        g_split_rows = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "scan_tile_table") {  // full-list stages launch one block per existing (list, tile): 0 never, 1 auto, 2 always
-        if (value < 0 || value > 2) return fail(RQ_ERR_INVALID, "scan_tile_table must be 0 (never), 1 (auto) or 2 (always)");
-        g_scan_tile_table = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "max_scan_blocks") {  // test hook: blocks per scan launch (0 = the hardware bound), forces chunked stages
-        if (value < 0) return fail(RQ_ERR_INVALID, "max_scan_blocks must be >= 0");
-        g_max_scan_blocks = value == 0 ? RQ_MAX_BLOCKS_256 : std::min<uint32_t>((uint32_t)value, RQ_MAX_BLOCKS_256);
-        return RQ_OK;
-    }
-    if (std::string(name) == "pair_split") {  // test hook: 1 (default) = sharded passes list their non-empty pairs before the query quantisation, 0 = never
-        if (value < 0 || value > 1) return fail(RQ_ERR_INVALID, "pair_split must be 0 or 1");
-        g_pair_split = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "coarse_tiled_from") {  // developer knob: list count from which the pre-filtered ranking selects through tile minima
-        if (value < 0) return fail(RQ_ERR_INVALID, "coarse_tiled_from must be >= 0");
-        g_coarse_tiled_from = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "coarse_impl") {  // test hook: coarse-distance kernel (0 auto, 1 LDS broadcast, 2 scalar registers)
-        if (value < 0 || value > 4) return fail(RQ_ERR_INVALID, "coarse_impl must be 0, 1, 2, 3 or 4");
-        g_coarse_impl = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "survivor_segments") {  // 0 never, 1 automatic (default), 2 every batch of >= 256 queries (tests); developer build: 3 = 2 with every arena stage failing (the fall-back)
-#ifdef RQ_DEV_ABLATIONS
-        if (value < 0 || value > 3) return fail(RQ_ERR_INVALID, "survivor_segments must be 0, 1, 2 or 3");
-#else
-        if (value == 3) return fail(RQ_ERR_INVALID, "survivor_segments = 3 (allocation-failure injection) exists in the developer build only (make dev)");
-        if (value < 0 || value > 2) return fail(RQ_ERR_INVALID, "survivor_segments must be 0, 1 or 2");
+    const OptionRow *o = nullptr;
+    for (const OptionRow &r : g_options)
+        if (!strcmp(r.name, name)) o = &r;
+    if (!o) return fail(RQ_ERR_INVALID, std::string("unknown option ") + name);
+    // the rules that are not a plain range (host_options.h names them on their rows)
+#ifndef RQ_DEV_ABLATIONS
+    if (o->var == &g_seg_opt && value == 3)
+        return fail(RQ_ERR_INVALID, "survivor_segments = 3 (allocation-failure injection) exists in the developer build only (make dev)");
 #endif
-        g_seg_opt = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "assign_impl") {  // nearest-list assignment of builds started from now on: 0 = matrix-core pre-filter + exact refinement, 1 = exact-order VALU kernels only
-        if (value < 0 || value > 1) return fail(RQ_ERR_INVALID, "assign_impl must be 0 or 1");
-        g_assign_impl = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "small_batch_span") {  // developer knob (results identical for every value)
-        if (value < 1) return fail(RQ_ERR_INVALID, "small_batch_span must be >= 1");
-        g_sb_span = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "small_batch") {  // 0 = batches of <= 64 queries take the few-launch path when it applies, 1 = never
-        if (value < 0 || value > 1) return fail(RQ_ERR_INVALID, "small_batch must be 0 or 1");
-        g_small_batch = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "small_batch_filtered") {  // filtered batches of <= 64 queries on the few-launch path (results identical for every value)
-        if (value < 0 || value > 2) return fail(RQ_ERR_INVALID, "small_batch_filtered must be 0, 1 or 2");
-        g_sb_filtered = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "dense_dir") {  // test hook: 0 = run descriptors always appended and sorted, 1 = dense directories where they fit
-        if (value < 0 || value > 1) return fail(RQ_ERR_INVALID, "dense_dir must be 0 or 1");
-        g_dense_dir = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "shared_thresholds") {  // rq_query_batch_sharded_device: 0 = every shard on its own thresholds, 1 = shared when world > 1, 2 = always
-        if (value < 0 || value > 2) return fail(RQ_ERR_INVALID, "shared_thresholds must be 0, 1 or 2");
-        g_shared_thr = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "group_rank") {  // test hook: how a cluster-major stage places its pairs (0 atomics per pair, 1 auto, 2 ranked)
-        if (value < 0 || value > 2) return fail(RQ_ERR_INVALID, "group_rank must be 0, 1 or 2");
-        g_group_rank = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "prep_placement") {  // 1 (default) = final matrix-core stage planned before the query quantisation, operand rows written in place; 0 = the older kernels everywhere (results identical)
-        if (value < 0 || value > 1) return fail(RQ_ERR_INVALID, "prep_placement must be 0 or 1");
-        g_prep_placement = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "rerank_shadow") {  // fp16 shadow rows (rerank pre-filter) for indexes built / loaded from now on
-        if (value < 0 || value > 2) return fail(RQ_ERR_INVALID, "rerank_shadow must be 0 (never), 1 (fp16 rows when they fit) or 2 (8-bit rows when they fit)");
-        g_rerank_shadow = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "scan_gate") {  // gate of the matrix-core scan (results never depend on it): 0 auto, 1 bf16 threshold, 2 additive where it exists
-        if (value < 0 || value > 2) return fail(RQ_ERR_INVALID, "scan_gate must be 0, 1 or 2");
-        g_scan_gate = value;
-        return RQ_OK;
-    }
-    if (std::string(name) == "scan_debug") {
-        // Measurement hooks that leave every result unchanged: 128 (kept for older hosts: the step counters are always on now),
-        // 512 (rerank without the fp16 shadow rows), 2048 (long run directories are ordered without the cell bitmap), 4096 (phase stamps of the small-batch block), 16384 (stage list on stderr),
-        // 32768 (the 8-bit rerank pre-filter reads its shadow rows into registers: the kernel from before the LDS ring),
-        // 65536 (the pre-filtered coarse ranking of 4096 .. 8192 lists writes the nq x k matrix of approximate distances and selects
-        // from it: the two kernels from before coarse_candidates_kernel).
-        // The timing ablations (1, 2, 4, 64, 1024, 8192: results are WRONG) and the in-kernel cycle counters (256) exist in
-        // the developer build only (make dev -> librabitq_hip_dev.so, -DRQ_DEV_ABLATIONS).
-#ifdef RQ_DEV_ABLATIONS
-        const int allowed = 0x7FFFFFFF;
-#else
-        const int allowed = 128 | 512 | 2048 | 4096 | 16384 | 32768 | 65536;
-#endif
-        if (value < 0 || (value & ~allowed)) return fail(RQ_ERR_INVALID, "scan_debug: this bit exists in the developer build only (librabitq_hip_dev.so)");
-        g_scan_dbg = value;
-        return RQ_OK;
-    }
-    return fail(RQ_ERR_INVALID, std::string("unknown option ") + name);
+    const bool odd = (o->var == &g_stage_growth && value == 1) || (o->var == &g_scan_dbg && (value & ~RQ_OPT_DEBUG_BITS));
+    if (value < o->lo || value > o->hi || odd) return fail(RQ_ERR_INVALID, o->refused);
+    if (o->var) *o->var = value;
+    else if (!strcmp(name, "base_device_mb")) g_base_device_mb = value;
+    else g_max_scan_blocks = value == 0 ? RQ_MAX_BLOCKS_256 : std::min<uint32_t>((uint32_t)value, RQ_MAX_BLOCKS_256);  // "max_scan_blocks"
+    return RQ_OK;
 }
 
 rq_status rq_set_profiling(int level) {
@@ -1331,7 +1205,7 @@ rq_status rq_quantize_pack(const float *x_rot, uint64_t n, uint32_t dim, const f
     transpose_kernel<<<dim3(ceil_div(dim, 32), ceil_div(k, 32)), dim3(32, 8)>>>(tmp.centroids.p, tmp.cent_t.p, k, dim);
     AssignAux ax;  // the build's assignment path: matrix-core pre-filter + exact refinement (option assign_impl)
     HIPC(hipDeviceSynchronize());
-    if (assign_has_mfma(tmp.W) && g_assign_impl.load() != 1) RQC(assign_aux_init(&tmp, ax, std::min<uint64_t>(std::max<uint64_t>(n, 1), 1ull << 20)));
+    if (bf16_tile_has(tmp.W) && g_assign_impl.load() != 1) RQC(assign_aux_init(&tmp, ax, std::min<uint64_t>(std::max<uint64_t>(n, 1), 1ull << 20)));
     for (uint64_t i0 = 0; i0 < n; i0 += (1ull << 20)) {  // chunked: launches stay far below 2^32 threads
         const uint64_t m = std::min<uint64_t>(1ull << 20, n - i0);
         RQC(launch_assign_prefiltered(dx.p + i0 * dim, &tmp, ax, m, dl.p + i0, dd.p + i0));

@@ -11,9 +11,11 @@ BAND = 32       # counts this close to CAND are not trusted: the model uses exac
 
 # (d, k, nq, probe, kind): the smallest shapes at which each piece can go wrong -- whole and ragged list / query tiles, both ends of
 # the route's list range, every dimension with an instantiation of its own, one and two query tiles per wave (dim <= 128 holds two
-# up to 4544 lists), probe counts 1 / 33 / 64, and the input kinds of coarse_cases at >= 4096 lists
+# up to 4544 lists, dim 64 up to 4800: launched_shape below; tests/test_kernel_shapes.py checks that the cases launch every shape
+# of the kernel's list),
+# probe counts 1 / 33 / 64, and the input kinds of coarse_cases at >= 4096 lists
 CASES = [(128, 4096, 2048, 64, "mixture"), (128, 4100, 2048 + 37, 64, "mixture"), (128, 8192, 2048, 64, "mixture"),
-         (64, 4096, 2048, 33, "mixture"), (256, 4096, 2048, 64, "mixture"), (192, 4128, 2050, 64, "mixture"), (128, 4096, 2048, 1, "mixture"),
+         (64, 4096, 2048, 33, "mixture"), (64, 4832, 2048, 33, "mixture"), (256, 4096, 2048, 64, "mixture"), (192, 4128, 2050, 64, "mixture"), (128, 4096, 2048, 1, "mixture"),
          (64, 4096, 2100, 33, "ties"), (128, 5000, 2200, 64, "scaled"), (128, 4100, 2100, 40, "nan"), (128, 4096, 2060, 64, "equidistant"),
          (128, 4096, 2048, 64, "mixed")]
 
@@ -21,6 +23,18 @@ CASES = [(128, 4096, 2048, 64, "mixture"), (128, 4100, 2048 + 37, 64, "mixture")
 # NEAR queries are drawn next to the copied centroid -- all CLUMP copies are within the margin of their nprobe-th nearest list, more
 # than the slots hold --, the others around ordinary centroids
 CLUMP, CLUMP_AT, NEAR = 400, 1000, 12
+
+
+LDS_PER_BLOCK = 160 * 1024      # RQ_LDS_PER_BLOCK
+
+
+def launched_shape(d, k, shapes):
+    """-> (W, NT) of the coarse_candidates_kernel instantiation the route launches at this shape (launch_coarse_prefiltered,
+    host_launch.h): the first of `shapes` (the kernel's (W, NT) list, in its order: two query tiles per wave before one) of this
+    width whose two centroid-tile images and tile keys of 4 waves x NT x 32 queries fit in LDS; None: no such shape."""
+    W, ntile = d // 64, (k + 31) // 32
+    images = 2 * (32 * (64 * W * 2 + 16) + 128)
+    return next(((w, nt) for w, nt in shapes if w == W and images + 4 * nt * 32 * ntile * 4 <= LDS_PER_BLOCK), None)
 
 
 def case(d, k, nq, kind):

@@ -29,7 +29,7 @@ U8_SHAPES = [(64, 3000, 8), (100, 5000, 16), (128, 20000, 32), (192, 5000, 16), 
 I8_SHAPES = [(100, 5000, 16), (128, 20000, 32), (448, 3000, 8)]
 CASES = [("u8",) + s for s in U8_SHAPES] + [("i8",) + s for s in I8_SHAPES]
 CASE_IDS = ["%s-d%d-n%d-k%d" % c for c in CASES]
-SB_WIDTHS = (1, 2, 4, 8, 12, 16)   # dim / 64 of the sb_query_kernel instantiations (host_plan.h): other widths have no small-batch path
+SB_WIDTHS = (1, 2, 4, 8, 12, 16)   # dim / 64 of the sb_query_kernel instantiations (kernel_shapes.h; tests/test_kernel_shapes.py compares): other widths have no small-batch path
 
 
 @pytest.fixture(scope="module")

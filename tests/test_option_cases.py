@@ -13,12 +13,18 @@ from tests import option_cases as oc
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def option_rows():
+    """-> [(name, default)]: the rows of the option table rq_set_option looks its argument up in (host_options.h: the X(...) rows
+    of RQ_OPTIONS and the two written-out rows of g_options)."""
+    src = open(os.path.join(ROOT, "rabitq_amd", "csrc", "host_options.h")).read()
+    src = src[src.index("#define RQ_OPTIONS(X)"):]
+    rows = re.findall(r'^\s*(?:X\(|\{)"([a-z0-9_]+)", *&?\w+, *(-?\d+),', src, flags=re.M)
+    return [(name, int(default)) for name, default in rows]
+
+
 def option_names():
-    """The names rq_set_option compares its argument with."""
-    src = open(os.path.join(ROOT, "rabitq_amd", "csrc", "rabitq_hip.hip")).read()
-    body = src[src.index("rq_status rq_set_option(const char *name, int value) {"):]
-    body = body[:body.index("\nrq_status rq_set_profiling")]
-    return re.findall(r'std::string\(name\) == "([a-z0-9_]+)"', body)
+    """The names rq_set_option knows."""
+    return [name for name, _ in option_rows()]
 
 
 def test_every_option_has_a_row():
@@ -31,6 +37,7 @@ def test_every_option_has_a_row():
     engaged = {r.option for r in oc.ENGAGED}
     assert set(names) - engaged == {"pass_overlap", "shared_thresholds"}, sorted(set(names) - engaged)
     assert set(oc.DEFAULTS) == set(names)
+    assert dict(option_rows()) == oc.DEFAULTS     # the table's default column, option by option
 
 
 def test_every_value_of_the_golden_sweep_has_a_row():
