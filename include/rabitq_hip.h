@@ -89,7 +89,9 @@ typedef struct {
  * later in 0.11, additions only: exact search -- rq_exact_search*, rq_last_exact_stats; exact range search --
  * rq_exact_range_search*; rq_exact_stats_t.reserved0 became scan_subtiles;
  * later in 0.11, additions only: adaptive probing -- rq_probe_rule_t, rq_query_batch_adaptive, rq_query_batch_device_adaptive,
- * rq_probe_counts_device).
+ * rq_probe_counts_device;
+ * later in 0.11, additions only: centroid training -- rq_train_params_t, rq_train_stats_t, rq_train_centroids,
+ * rq_train_centroids_device).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -297,6 +299,51 @@ rq_status rq_builder_stats(const rq_builder *b, rq_build_stats_t *out);
  * No parity target (faiss is not available; results depend on the seed): judged by recall. */
 rq_status rq_kmeans_device(const float *d_base, uint64_t n, uint32_t d, uint32_t k, uint32_t iters,
                            uint32_t points_per_centroid, uint64_t seed, float *d_centroids_out);
+
+/* ---- centroid training with a contract: deterministic k-means for every build ------------------ */
+/* Trains the k centroids a build of (rows, metric, row_type) takes, reproducibly to the bit: two runs of one seed, the host and
+ * the device entry, and both values of option "assign_impl" return the same bits, and tests/train_model.py computes them on the
+ * CPU.  With cols = d (RQ_METRIC_IP: d + 1) and dim = ceil64(cols):
+ *  1. sample: ns = min(n, max(points_per_centroid, 1) * k) rows; every row in order when ns == n, else row r of the sample is row
+ *     lo + mix64(seed * 0x100000001B3 + r) mod (hi - lo) with lo = floor(r n / ns), hi = floor((r + 1) n / ns) (u64; mix64 is
+ *     splitmix64's finaliser as rq_kmeans_device uses it): distinct, ascending, one per stratum;
+ *  2. the sampled rows are widened (W) and transformed as the build transforms them (N(x) for cosine, A(x; S) for the inner
+ *     product, zero padding to dim);
+ *  3. centroid j starts as transformed sample row floor(j ns / k);
+ *  4. iteration t = 0 .. iters - 1: label and distance of every sample row (the build's nearest-list rule: exact-order f32
+ *     distance, first minimum); if t > 0 and no label changed, stop with iters_run = t; centroid = f32 sum of its members in
+ *     ascending sample position, strictly left to right, divided by (float)count; objective[t] = the members' distances summed in
+ *     f64, per cluster in ascending sample position, then over the clusters ascending; then every empty cluster e, ascending, takes
+ *     half of the largest cluster (lowest index on ties; fewer than 2 members: e keeps its centroid): with eps = 2^-10,
+ *     cent[e][c] = cent[donor][c] * (c even ? 1 + eps : 1 - eps), cent[donor][c] *= (c even ? 1 - eps : 1 + eps),
+ *     count[e] = count[donor] / 2, count[donor] -= count[e], splits += 1;
+ *  5. out: k x cols f32 (an inner-product build takes them with centroid_cols = d + 1).
+ * Refused: n < k, k == 0, d == 0 or NULL arguments, a sample row with a non-finite element or (inner product) one A refuses, an
+ * sq_bound that is neither NaN nor finite and >= 0 (RQ_ERR_INVALID); a row type the metric does not go with, dim > 4096,
+ * n >= 2^32, ns * dim > 2^31 (RQ_ERR_UNSUPPORTED).  Nothing is written to the outputs then. */
+typedef struct {
+    uint32_t struct_size;         /* in: sizeof(rq_train_params_t) */
+    uint32_t iters;               /* iteration cap */
+    uint32_t points_per_centroid; /* sample size per centroid (0 counts as 1) */
+    uint64_t seed;
+    uint32_t metric;              /* RQ_METRIC_* */
+    uint32_t row_type;            /* RQ_ROWS_*: the element type of the rows */
+    float sq_bound;               /* RQ_METRIC_IP: S; NaN = the largest squared row norm over all n rows (rq_row_sqnorm_max*) */
+} rq_train_params_t;
+typedef struct {
+    uint32_t struct_size; /* in: sizeof(rq_train_stats_t) of the caller */
+    uint32_t iters_run;   /* iterations whose centroid update ran (== iters when the cap ended the training) */
+    uint32_t sample_rows; /* ns */
+    uint32_t splits;
+} rq_train_stats_t;
+/* d_rows: n x d elements of params->row_type, device; d_centroids_out: k x cols f32, device; objective_out: host, params->iters
+ * doubles of which the first iters_run are written (may be NULL); stats_out: host (may be NULL). */
+rq_status rq_train_centroids_device(const void *d_rows, uint64_t n, uint32_t d, uint32_t k, const rq_train_params_t *params,
+                                    float *d_centroids_out, double *objective_out, rq_train_stats_t *stats_out);
+/* The same with rows and centroids_out in host memory: the sample is drawn on the host and only its ns rows are uploaded (an
+ * inner-product run with sq_bound NaN first asks rq_row_sqnorm_max, which stages all n rows once). */
+rq_status rq_train_centroids(const void *rows, uint64_t n, uint32_t d, uint32_t k, const rq_train_params_t *params,
+                             float *centroids_out, double *objective_out, rq_train_stats_t *stats_out);
 
 /* ---- persistence: load_from_dir / dump_to_dir, src/rabitq.rs:84-156 -------------------------- */
 /* Byte-compatible with the crate's five-file directory (vecs framing: src/utils.rs:280-364).  A cosine index writes a sixth

@@ -35,6 +35,7 @@ EXPORTS = [
     "rq_exact_search", "rq_exact_search_device", "rq_last_exact_stats",
     "rq_exact_range_search", "rq_exact_range_search_device",
     "rq_query_batch_adaptive", "rq_query_batch_device_adaptive", "rq_probe_counts_device",
+    "rq_train_centroids", "rq_train_centroids_device",
 ]
 
 
@@ -154,6 +155,16 @@ class ProbeRuleT(_Sized):
     """rq_probe_rule_t: adaptive probing's cut rule (max_probe: a raw address, device or host as the entry says; 0 = none)."""
     _fields_ = [("struct_size", C.c_uint32), ("min_probe", C.c_uint32), ("ratio", C.c_float), ("reserved", C.c_uint32),
                 ("max_probe", C.c_void_p)]
+
+
+class TrainParamsT(_Sized):
+    """rq_train_params_t: what the centroid trainer is asked for (sq_bound: the inner-product metric's S, NaN = automatic)."""
+    _fields_ = [("struct_size", C.c_uint32), ("iters", C.c_uint32), ("points_per_centroid", C.c_uint32), ("seed", C.c_uint64),
+                ("metric", C.c_uint32), ("row_type", C.c_uint32), ("sq_bound", C.c_float)]
+
+
+class TrainStatsT(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("iters_run", C.c_uint32), ("sample_rows", C.c_uint32), ("splits", C.c_uint32)]
 
 
 def build(force: bool = False) -> str:
@@ -291,6 +302,8 @@ def lib():
         "rq_query_batch_adaptive": (i32, [vp, vp, f32p, u32, u32, u32, u32, C.c_int, C.POINTER(ProbeRuleT), f32p, u32p, u32p, u32p]),
         "rq_query_batch_device_adaptive": (i32, [vp, vp, f32p, u32, u32, u32, u32, C.c_int, C.POINTER(ProbeRuleT), f32p, u32p, u32p, u32p]),
         "rq_probe_counts_device": (i32, [vp, f32p, u32, u32, u32, C.POINTER(ProbeRuleT), u32p]),
+        "rq_train_centroids": (i32, [vp, u64, u32, u32, C.POINTER(TrainParamsT), f32p, vp, C.POINTER(TrainStatsT)]),
+        "rq_train_centroids_device": (i32, [vp, u64, u32, u32, C.POINTER(TrainParamsT), f32p, vp, C.POINTER(TrainStatsT)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the .so lacks a declared symbol

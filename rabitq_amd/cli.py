@@ -14,7 +14,9 @@
 * prints mean recall@k against the ground-truth ivecs (src/utils.rs:367-379) and the METRICS line
   (src/metrics.rs:30-41);
 * `--make-truth`: when the `-t` file does not exist, the exact top-max(topk, 100) of the query file is computed on the GPU
-  (RaBitQ.exact_search) and written there as .ivecs first; an existing file is never overwritten.
+  (RaBitQ.exact_search) and written there as .ivecs first; an existing file is never overwritten;
+* `--train K [--train-iters I]`: when the `-c` file does not exist, K centroids are trained from the base file on the GPU
+  (train_centroids, deterministic) and written there as .fvecs first; an existing file is used as it is.
 """
 from __future__ import annotations
 
@@ -24,7 +26,7 @@ import time
 
 import numpy as np
 
-from . import RaBitQ, _lib, calculate_recall, metrics_reset, metrics_str, vecs
+from . import RaBitQ, _lib, calculate_recall, metrics_reset, metrics_str, train_centroids, vecs
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -54,7 +56,21 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--make-truth", dest="make_truth", action="store_true",
                     help="when the truth path does not exist: compute the exact top-max(topk, 100) of the queries on the GPU "
                          "and write it there as .ivecs (an existing file is left alone)")
+    ap.add_argument("--train", type=int, default=0, metavar="K",
+                    help="when the centroids path does not exist: train K lists from the base file on the GPU (--metric / --rows "
+                         "respected, --seed is the sample's seed too) and write them there as .fvecs (an existing file is used as it is)")
+    ap.add_argument("--train-iters", dest="train_iters", type=int, default=20, metavar="I", help="with --train: the iteration cap")
     return ap
+
+
+def train_missing_centroids(args) -> bool:
+    """--train K: write the centroid file unless it exists -> whether it was written.  k x d records (--metric ip: k x (d + 1), the
+    centroids of the augmented rows -- a record length the inner-product build takes)."""
+    if not args.train or os.path.exists(args.centroids):
+        return False
+    base = vecs.read_bvecs(args.base, _lib.ROW_TYPE_BY_NAME[args.rows].returns) if args.rows else vecs.read_matrix(args.base)
+    vecs.write_vecs(args.centroids, train_centroids(base, args.train, iters=args.train_iters, seed=args.seed, metric=args.metric, rows=args.rows))
+    return True
 
 
 def make_truth(index, queries, path, topk: int) -> bool:
@@ -82,6 +98,8 @@ def main(argv=None) -> int:
         print(f"loading from {args.saved!r}...")
         index = RaBitQ.load_from_dir(args.saved)
     else:
+        if train_missing_centroids(args):
+            print(f"{args.train} centroids trained and written to {args.centroids!r}")
         print("training...")
         if args.rows:
             base = vecs.read_bvecs(args.base, _lib.ROW_TYPE_BY_NAME[args.rows].returns)

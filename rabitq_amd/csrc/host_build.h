@@ -176,11 +176,10 @@ struct AssignAux {
     float cmax = INFINITY;
     uint64_t redone = 0;  // vectors that went through the exact-order kernel (no or too many candidates)
 };
-static rq_status assign_aux_init(const rq_index *idx, AssignAux &ax, uint64_t chunk_rows) {
+// the per-centroid parts (bf16 image, norms, cmax) from the index's current centroids: once per build, once per iteration of the
+// trainer (host_train.h), whose centroids move; nothing is allocated
+static rq_status assign_aux_refresh(const rq_index *idx, AssignAux &ax) {
     const uint64_t cells = (uint64_t)idx->k * idx->dim;
-    RQC(ax.cent_bf.alloc(cells));
-    RQC(ax.cnorm.alloc(idx->k));
-    RQC(ax.redo_cnt.alloc(2));
     HIPC(hipMemset(ax.redo_cnt.p, 0, 8));
     to_bf16_kernel<<<ceil_div(cells, 2048), 256>>>(idx->centroids.p, cells, ax.cent_bf.p);
     row_sqnorm_kernel<<<ceil_div(idx->k, 256), 256>>>(idx->centroids.p, idx->k, idx->dim, ax.cnorm.p, ax.redo_cnt.p + 1);
@@ -188,6 +187,13 @@ static rq_status assign_aux_init(const rq_index *idx, AssignAux &ax, uint64_t ch
     HIPC(hipMemcpy(&bits, ax.redo_cnt.p + 1, 4, hipMemcpyDeviceToHost));
     const float m2 = __builtin_bit_cast(float, bits);
     ax.cmax = std::isfinite(m2) && m2 < 1.0e30f ? std::sqrt(m2) * 1.000001f : INFINITY;  // inf: every vector goes to the exact-order kernel
+    return RQ_OK;
+}
+static rq_status assign_aux_init(const rq_index *idx, AssignAux &ax, uint64_t chunk_rows) {
+    RQC(ax.cent_bf.alloc((uint64_t)idx->k * idx->dim));
+    RQC(ax.cnorm.alloc(idx->k));
+    RQC(ax.redo_cnt.alloc(2));
+    RQC(assign_aux_refresh(idx, ax));
     RQC(ax.cand.alloc(chunk_rows * RQ_ASSIGN_CAND));
     RQC(ax.cand_cnt.alloc(chunk_rows));
     RQC(ax.redo.alloc(chunk_rows));

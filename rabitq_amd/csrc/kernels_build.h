@@ -737,7 +737,7 @@ __global__ void max_list_len_kernel(const uint32_t *__restrict__ offsets, uint32
 // the nearest-centroid kernels above.  No parity target (faiss is absent, results are seed
 // dependent): judged by recall only.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t rq_mix64(uint64_t x) {  // splitmix64
+__host__ __device__ __forceinline__ uint64_t rq_mix64(uint64_t x) {  // splitmix64 (host: the trainer's host entry draws the same sample)
     x += 0x9E3779B97F4A7C15ull;
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;

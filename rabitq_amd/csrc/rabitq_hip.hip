@@ -32,6 +32,7 @@
 #include "kernels_query.h"
 #include "kernels_range.h"
 #include "kernels_small.h"
+#include "kernels_train.h"
 
 #include "kernel_shapes.h"
 #include "host_state.h"
@@ -46,6 +47,7 @@
 #include "host_mutate.h"
 #include "host_exact.h"
 #include "host_exact_range.h"
+#include "host_train.h"
 
 // ------------------------------------------------------------------------------------------------
 // extern "C"
@@ -105,6 +107,16 @@ rq_status rq_kmeans_device(const float *d_base, uint64_t n, uint32_t d, uint32_t
     HIPC(hipDeviceSynchronize());
     HIPC(hipGetLastError());
     return RQ_OK;
+}
+
+// ---- centroid training with a contract (host_train.h) ----
+rq_status rq_train_centroids_device(const void *d_rows, uint64_t n, uint32_t d, uint32_t k, const rq_train_params_t *params,
+                                    float *d_centroids_out, double *objective_out, rq_train_stats_t *stats_out) {
+    return train_device(d_rows, n, d, k, params, d_centroids_out, objective_out, stats_out);
+}
+rq_status rq_train_centroids(const void *rows, uint64_t n, uint32_t d, uint32_t k, const rq_train_params_t *params, float *centroids_out,
+                             double *objective_out, rq_train_stats_t *stats_out) {
+    return train_host(rows, n, d, k, params, centroids_out, objective_out, stats_out);
 }
 
 // ---- the row transforms on their own (the builds, rq_add and every query pass run the same kernels) ----

@@ -58,6 +58,50 @@ def widen(x, rows="f16"):
     return out
 
 
+class TrainStats:
+    """What a training run did (rq_train_stats_t + the objective): `iters_run` iterations updated the centroids (== iters when the
+    cap ended it), on `sample_rows` rows, with `splits` empty-cluster splits; `objective[t]` is iteration t's sum of squared
+    distances of the sample rows to their centroids (f64), one entry per iteration run."""
+
+    def __init__(self, iters_run: int, sample_rows: int, splits: int, objective):
+        self.iters_run, self.sample_rows, self.splits, self.objective = iters_run, sample_rows, splits, objective
+
+    def __repr__(self):
+        return f"TrainStats(iters_run={self.iters_run}, sample_rows={self.sample_rows}, splits={self.splits}, objective={self.objective!r})"
+
+
+def _train_call(entry, rows_addr, n, d, k, out_addr, iters, points_per_centroid, seed, metric, max_sq_norm, rt) -> TrainStats:
+    p = _lib.TrainParamsT(iters=iters, points_per_centroid=points_per_centroid, seed=seed, metric=_lib.metric_id(metric), row_type=rt,
+                          sq_bound=_sq_bound(max_sq_norm))
+    st = _lib.TrainStatsT()
+    obj = np.zeros(max(iters, 1), dtype=np.float64)
+    check(entry(rows_addr, n, d, k, C.byref(p), out_addr, _addr(obj), C.byref(st)))
+    return TrainStats(int(st.iters_run), int(st.sample_rows), int(st.splits), obj[:st.iters_run].copy())
+
+
+def train_centroids(base, k: int, iters: int = 20, points_per_centroid: int = 256, seed: int = 0, metric="l2", max_sq_norm=None,
+                    rows=None, return_stats: bool = False):
+    """Train the k centroids a build of (base, metric, rows) takes: deterministic k-means on the GPU (rq_train_centroids), the same
+    bits for the same arguments on every run.  base: n x d as RaBitQ.build takes it (rows= too).  -> k x d f32 (metric="ip":
+    k x (d + 1), the centroids of the augmented rows, S = max_sq_norm or the largest squared row norm); with return_stats also a
+    TrainStats."""
+    base, rt = _typed_rows(base, rows)
+    if base.ndim != 2:
+        raise _lib.RabitqError(-2, "base must be 2-D (n x d)")
+    n, d = base.shape
+    out = np.empty((k, d + 1 if _lib.metric_id(metric) == _lib.METRIC_IP else d), dtype=np.float32)
+    st = _train_call(lib().rq_train_centroids, _addr(base), n, d, k, _addr(out), iters, points_per_centroid, seed, metric, max_sq_norm, rt)
+    return (out, st) if return_stats else out
+
+
+def train_centroids_device(base_ptr: int, n: int, d: int, k: int, out_ptr: int, iters: int = 20, points_per_centroid: int = 256,
+                           seed: int = 0, metric="l2", max_sq_norm=None, rows="f32") -> TrainStats:
+    """train_centroids on device-resident rows (raw addresses): base_ptr holds n x d elements of `rows`, out_ptr receives k x d f32
+    (metric="ip": k x (d + 1))."""
+    return _train_call(lib().rq_train_centroids_device, C.c_void_p(base_ptr), n, d, k, C.c_void_p(out_ptr), iters, points_per_centroid,
+                       seed, metric, max_sq_norm, _lib.row_type_id(rows))
+
+
 def pack_filter_bits(ids=None, mask=None, nbits=None):
     """An allow-list as the bitmap rq_filter_create reads -> (words u32, nbits): bit (id & 31) of word id >> 5 set = id admitted.
     `ids`: admitted ids (any order, repeats allowed; ids >= nbits are dropped -- the library never admits them); nbits defaults to
@@ -206,7 +250,10 @@ class RaBitQ:
         """from_path on in-memory arrays (base n x d, centroids k x d; metric="ip": k x c with d <= c <= ceil64(d + 1), missing
         columns are zero).  A float16 `base` (or rows="f16" / rows="bf16" with a uint16 array of bit patterns) makes a half-precision
         index: the rows are stored as given, 2*dim bytes each.  rows="u8" with a uint8 array / rows="i8" with an int8 array makes a
-        byte-row index (L2 only), dim bytes each; without rows= such an array is converted to f32."""
+        byte-row index (L2 only), dim bytes each; without rows= such an array is converted to f32.
+        centroids=<int>: that many lists are trained first (train_centroids with this build's metric, rows, max_sq_norm and seed)."""
+        if isinstance(centroids, (int, np.integer)) and not isinstance(centroids, bool):
+            centroids = train_centroids(base, int(centroids), seed=seed, metric=metric, max_sq_norm=max_sq_norm, rows=rows)
         base, rt = _typed_rows(base, rows)
         centroids = _f32(centroids)
         if rt != _lib.ROWS_F32:
@@ -237,7 +284,15 @@ class RaBitQ:
     def build_device(cls, base_ptr: int, n: int, d: int, centroids_ptr: int, k: int, orthogonal=None,
                      seed: int = 0, metric="l2", max_sq_norm=None, centroid_cols: int = None, rows="f32") -> "RaBitQ":
         """Build from device-resident arrays (raw HIP device addresses, e.g. torch.Tensor.data_ptr()).  metric="ip": the
-        centroids are k x centroid_cols (None: d).  rows="f16" / "bf16" / "u8" / "i8": base_ptr holds n x d elements of that type."""
+        centroids are k x centroid_cols (None: d).  rows="f16" / "bf16" / "u8" / "i8": base_ptr holds n x d elements of that type.
+        centroids_ptr=None: k lists are trained on the device first (train_centroids_device with this build's metric, rows,
+        max_sq_norm and seed; the centroid buffer is a torch tensor that lives for the call)."""
+        if centroids_ptr is None:
+            import torch
+            ip = _lib.metric_id(metric) == _lib.METRIC_IP
+            learnt = torch.empty((k, d + 1 if ip else d), dtype=torch.float32, device="cuda")
+            train_centroids_device(base_ptr, n, d, k, learnt.data_ptr(), seed=seed, metric=metric, max_sq_norm=max_sq_norm, rows=rows)
+            centroids_ptr, centroid_cols = learnt.data_ptr(), (d + 1 if ip else None)
         P = _f32(orthogonal) if orthogonal is not None else None
         h = C.c_void_p()
         if _lib.row_type_id(rows) != _lib.ROWS_F32:
