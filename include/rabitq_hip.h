@@ -91,7 +91,8 @@ typedef struct {
  * later in 0.11, additions only: adaptive probing -- rq_probe_rule_t, rq_query_batch_adaptive, rq_query_batch_device_adaptive,
  * rq_probe_counts_device;
  * later in 0.11, additions only: centroid training -- rq_train_params_t, rq_train_stats_t, rq_train_centroids,
- * rq_train_centroids_device).
+ * rq_train_centroids_device;
+ * 0.12.0: merge and extract, additions only -- RQ_MERGE_IDS_*, rq_merge_from, rq_extract; rq_last_mutate_stats reports them too).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -682,6 +683,49 @@ rq_status rq_add(rq_index *idx, const float *rows, uint64_t m, uint32_t d, const
                  uint32_t *out_first_id);
 rq_status rq_remove(rq_index *idx, const uint32_t *id_bits, uint64_t nbits, int bits_on_device, uint64_t *out_removed);
 rq_status rq_last_mutate_stats(rq_mutate_stats_t *out);
+
+/* ---- merge two indexes, extract a sub-index ------------------------------------------------------------------------------ */
+/* Both work on stored rows as they stand: nothing is rotated, assigned, quantised -- or, on a cosine or inner-product index,
+ * transformed -- again.  A row's list, order key, codes and factors depend only on the row, the rotation and the centroids, so
+ * two indexes over the same rotation and centroids merge by a per-list two-way merge of their order keys and one gather.
+ *
+ * rq_merge_from: dst receives the live rows of src.  With S = the live rows of dst joined with those of src under their new ids,
+ * dst afterwards equals canonical(S) of the section above, bit for bit: every array, rq_info, rq_dump_dir's files, and the ids,
+ * distance bits, counts, status and counters of every query.  For a cosine or inner-product index that is rq_build_metric /
+ * rq_build_ip of the ORIGINAL rows (the same S for inner product) -- which no sequence of rq_add can produce, since rq_add
+ * would transform the stored rows a second time.
+ *   id_mode: RQ_MERGE_IDS_KEEP = src's ids as they are; RQ_MERGE_IDS_SHIFT = src id + id_shift; RQ_MERGE_IDS_APPEND = src id +
+ *   (1 + the largest id dst holds; 0 if dst is empty), id_shift ignored.  *out_shift (nullable) = the shift applied (0 for KEEP).
+ *   src is not changed (its key cache may be derived); it stays a valid index and the caller still frees it.  dst's generation
+ *   is bumped (filters made before are refused), its tile tables and workspaces are released, its learnt hints stay; its key
+ *   cache is valid afterwards, so a following rq_add / rq_remove derives nothing.  An empty src succeeds and leaves dst as it
+ *   was, generation included (as an empty rq_add); an empty dst is allowed.
+ *   Memory: the merged arrays are built beside the old ones and moved into dst only after everything has succeeded, so the peak
+ *   is dst + src + the merged arrays; RQ_ERR_OOM leaves both indexes as they were.
+ * rq_extract: *out = a new index over src's rotation, centroids, metric (with its S and d) and dim, holding exactly the live rows
+ * of src whose id bit is set (the rq_filter_create / rq_remove bitmap format; ids at or past nbits are not taken, bits of ids src
+ * does not hold are ignored), ids kept: what rq_remove of the complement would leave in src, which is canonical of those rows.
+ * src is unchanged.  No bit set (or nbits == 0) gives a valid empty index.  id_bits == NULL with nbits == RQ_EXTRACT_ALL_IDS takes
+ * every row: a copy of src, for which no bitmap is made.  Every list keeps the order it has, so -- like
+ * rq_remove -- extraction does not need the order precondition.  The caller frees *out with rq_free.
+ * Refused with both indexes untouched and nothing left allocated (rq_last_error says which check failed):
+ *   RQ_ERR_INVALID: a null handle (checked before the device is looked for: these two entries answer RQ_ERR_INVALID to it on a
+ *   machine without a GPU too, where rq_add / rq_remove, which look for the device first, answer RQ_ERR_NO_DEVICE); dst == src; an unknown id_mode; dim, k or metric differ, or the inner-product S (compared as
+ *   bits) or d; the rotation or the rotated centroids differ in any bit (compared on the device as bit patterns; the message names
+ *   the array and the first differing element); a rq_query_batch_device_begin ticket of either index has not ended; under KEEP (and
+ *   SHIFT) ids of src that dst already holds -- the message gives their count.
+ *   RQ_ERR_UNSUPPORTED: either index is one rq_add refuses (tiered, split rows, half-precision or byte rows, a shard, dim > 4096);
+ *   a list of either index is out of the build's order (rq_merge_from only; see the precondition of rq_add); the shifted ids
+ *   would pass 2^32 - 1 or the row count what u32 ids allow (a largest new id of exactly 2^32 - 1 is accepted).
+ * rq_last_mutate_stats reports the calling thread's last rq_merge_from / rq_extract as well: ms_assign is 0 (there is no pass 1),
+ * ms_keys covers both indexes' key caches, gather_bytes counts what the gather of these entries moves, rows_after is dst's (the
+ * new index's) row count. */
+#define RQ_MERGE_IDS_KEEP   0u  /* src ids as they are; none may be in dst */
+#define RQ_MERGE_IDS_SHIFT  1u  /* src id + id_shift; none may be in dst */
+#define RQ_MERGE_IDS_APPEND 2u  /* src id + (1 + largest id dst holds; 0 if dst is empty); id_shift ignored */
+rq_status rq_merge_from(rq_index *dst, rq_index *src, uint32_t id_mode, uint32_t id_shift, uint32_t *out_shift);
+#define RQ_EXTRACT_ALL_IDS  0xFFFFFFFFFFFFFFFFull  /* nbits of rq_extract with id_bits == NULL: every row of src */
+rq_status rq_extract(rq_index *src, const uint32_t *id_bits, uint64_t nbits, int bits_on_device, rq_index **out);
 
 /* ---- sharded deployments (one index shard per GPU / process) ----------------------------------- */
 /* The coarse ranking of src/rabitq.rs:283-297 restricted to lists [list_lo, list_hi): the `probe`

@@ -36,6 +36,7 @@ EXPORTS = [
     "rq_exact_range_search", "rq_exact_range_search_device",
     "rq_query_batch_adaptive", "rq_query_batch_device_adaptive", "rq_probe_counts_device",
     "rq_train_centroids", "rq_train_centroids_device",
+    "rq_merge_from", "rq_extract",
 ]
 
 
@@ -49,6 +50,8 @@ METRIC_L2, METRIC_COSINE = 0, 1   # RQ_METRIC_*
 METRIC_IP = 2
 METRICS = {"l2": METRIC_L2, "cosine": METRIC_COSINE, "ip": METRIC_IP}
 METRIC_NAMES = {v: k for k, v in METRICS.items()}
+MERGE_IDS_KEEP, MERGE_IDS_SHIFT, MERGE_IDS_APPEND = 0, 1, 2   # RQ_MERGE_IDS_*
+EXTRACT_ALL_IDS = 0xFFFFFFFFFFFFFFFF   # RQ_EXTRACT_ALL_IDS
 
 
 def metric_id(metric) -> int:
@@ -265,6 +268,8 @@ def lib():
         "rq_add": (i32, [vp, f32p, u64, u32, u32p, C.c_int, u32p]),
         "rq_remove": (i32, [vp, u32p, u64, C.c_int, u64p]),
         "rq_last_mutate_stats": (i32, [C.POINTER(MutateStatsT)]),
+        "rq_merge_from": (i32, [vp, vp, u32, u32, u32p]),
+        "rq_extract": (i32, [vp, u32p, u64, C.c_int, pp]),
         "rq_coarse_topk_device": (i32, [vp, f32p, u32, u32, u32, u32, u32, u32p, f32p]),
         "rq_merge_smallest_u64_device": (i32, [vp, u32, u32, u32, u32, vp]),
         "rq_query_batch_device_probed": (i32, [vp, f32p, u32, u32, u32p, f32p, u32, u32, C.c_int, f32p, u32p, u32p]),

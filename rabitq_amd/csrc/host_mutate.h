@@ -6,7 +6,7 @@
 // The key word of every stored row (row_key), once per index: the stored rows are the build's zero-padded input, so rotating
 // them again (same kernel, same P) and taking the distance to their own list's centroid in the assignment's lane order gives
 // back the build's key bit for bit.
-static thread_local rq_mutate_stats_t g_mutate_stats;  // the calling thread's last rq_add / rq_remove (rq_last_mutate_stats)
+static thread_local rq_mutate_stats_t g_mutate_stats;  // the calling thread's last rq_add / rq_remove / rq_merge_from / rq_extract (rq_last_mutate_stats)
 struct PhaseClock {  // wall time of a phase; every phase ends in a device synchronisation, so it covers the device work too
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
     float lap() {
@@ -49,6 +49,11 @@ static rq_status ensure_row_keys(rq_index *idx) {
     g_mutate_stats.ms_keys = clk.lap();
     return RQ_OK;
 }
+
+// what rq_add and rq_merge_from answer where ensure_row_keys found a list out of order
+static const char *const kOrderRefusal =
+    "a list of this index is not in the build's order (distance to its centroid, then id): rows can be "
+    "removed from it, but not added (an index from rq_from_arrays / rq_load_dir whose ids were remapped?)";
 
 static rq_status mutate_refusals(const rq_index *idx) {
     if (!idx) return fail(RQ_ERR_INVALID, "null index");
@@ -116,6 +121,44 @@ static rq_status new_rows_prepare(const rq_index *idx, const float *d_rows, uint
     b->label.release();
     b->mind.release();
     g_mutate_stats.ms_assign = clk.lap();
+    return RQ_OK;
+}
+
+// The commit of a relayout (rq_add / rq_remove; rq_merge_from, host_merge.h): the new layout's arrays and derived state move into
+// *idx, the old ones leave with nx; the generation is bumped, workspaces and tile tables go, the learnt hints stay.
+static rq_status commit_layout(rq_index *idx, std::unique_ptr<rq_index> &nx, PhaseClock &clk) {
+    rq_mutate_stats_t &st = g_mutate_stats;
+    swap_buf(idx->base, nx->base), swap_buf(idx->P, nx->P), swap_buf(idx->centroids, nx->centroids), swap_buf(idx->cent_t, nx->cent_t);
+    swap_buf(idx->base_h, nx->base_h), swap_buf(idx->base_q8, nx->base_q8), swap_buf(idx->list_q8, nx->list_q8);
+    swap_buf(idx->offsets, nx->offsets), swap_buf(idx->map_ids, nx->map_ids), swap_buf(idx->codes, nx->codes);
+    swap_buf(idx->factors, nx->factors), swap_buf(idx->list_uref, nx->list_uref), swap_buf(idx->cent_bf, nx->cent_bf);
+    swap_buf(idx->cent_sqnorm, nx->cent_sqnorm), swap_buf(idx->row_key, nx->row_key);
+    idx->n = nx->n, idx->n_dev = nx->n_dev, idx->max_list_len = nx->max_list_len, idx->min_list_len = nx->min_list_len;
+    idx->cent_norm_max = nx->cent_norm_max, idx->nonempty_lists = nx->nonempty_lists, idx->fstats = nx->fstats;
+    idx->pass_budget = nx->pass_budget;
+    idx->h_offsets.swap(nx->h_offsets);
+    idx->row_key_valid = true;
+    {  // workspaces and tile tables describe the old layout (no query runs during a mutation; the learnt hints stay)
+        std::lock_guard<std::mutex> g(idx->tt_mu);
+        idx->tile_tables.clear();
+    }
+    {
+        std::lock_guard<std::mutex> g(idx->ws_mu);
+        idx->ws_pool.clear();
+    }
+    ++idx->generation;
+    nx.reset();  // the old layout's arrays
+    HIPC(hipDeviceSynchronize());
+    st.ms_free = clk.lap();
+    // The derived state was chosen while the old layout still held its HBM: a shadow that did not fit then, and the pass budget,
+    // are decided again now, as a fresh build would decide them.
+    // (Both are optional refinements of a committed index: a failure here leaves the shadow out, it does not fail the call.)
+    if (!idx->base_q8.p && !idx->base_h.p) (void)derive_shadow_rows(idx);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        idx->pass_budget = std::min<uint64_t>(std::max<uint64_t>(free_b / 3, 4ull << 30), 96ull << 30);
+    (void)hipGetLastError();
+    st.ms_derive += clk.lap();
     return RQ_OK;
 }
 
@@ -192,39 +235,7 @@ static rq_status relayout(rq_index *idx, const uint32_t *drop_bits, const std::v
     nx->row_key_valid = true;
     st.ms_derive = clk.lap();
 
-    // commit: the new arrays into *idx, the old ones leave with nx
-    swap_buf(idx->base, nx->base), swap_buf(idx->P, nx->P), swap_buf(idx->centroids, nx->centroids), swap_buf(idx->cent_t, nx->cent_t);
-    swap_buf(idx->base_h, nx->base_h), swap_buf(idx->base_q8, nx->base_q8), swap_buf(idx->list_q8, nx->list_q8);
-    swap_buf(idx->offsets, nx->offsets), swap_buf(idx->map_ids, nx->map_ids), swap_buf(idx->codes, nx->codes);
-    swap_buf(idx->factors, nx->factors), swap_buf(idx->list_uref, nx->list_uref), swap_buf(idx->cent_bf, nx->cent_bf);
-    swap_buf(idx->cent_sqnorm, nx->cent_sqnorm), swap_buf(idx->row_key, nx->row_key);
-    idx->n = nx->n, idx->n_dev = nx->n_dev, idx->max_list_len = nx->max_list_len, idx->min_list_len = nx->min_list_len;
-    idx->cent_norm_max = nx->cent_norm_max, idx->nonempty_lists = nx->nonempty_lists, idx->fstats = nx->fstats;
-    idx->pass_budget = nx->pass_budget;
-    idx->h_offsets.swap(nx->h_offsets);
-    idx->row_key_valid = true;
-    {  // workspaces and tile tables describe the old layout (no query runs during a mutation; the learnt hints stay)
-        std::lock_guard<std::mutex> g(idx->tt_mu);
-        idx->tile_tables.clear();
-    }
-    {
-        std::lock_guard<std::mutex> g(idx->ws_mu);
-        idx->ws_pool.clear();
-    }
-    ++idx->generation;
-    nx.reset();  // the old layout's arrays
-    HIPC(hipDeviceSynchronize());
-    st.ms_free = clk.lap();
-    // The derived state was chosen while the old layout still held its HBM: a shadow that did not fit then, and the pass budget,
-    // are decided again now, as a fresh build would decide them.
-    // (Both are optional refinements of a committed index: a failure here leaves the shadow out, it does not fail the call.)
-    if (!idx->base_q8.p && !idx->base_h.p) (void)derive_shadow_rows(idx);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-        idx->pass_budget = std::min<uint64_t>(std::max<uint64_t>(free_b / 3, 4ull << 30), 96ull << 30);
-    (void)hipGetLastError();
-    st.ms_derive += clk.lap();
-    return RQ_OK;
+    return commit_layout(idx, nx, clk);
 }
 
 // 1 + the largest id the index holds (0 if empty), and how many of its ids are among the m ascending ids `sorted` (device; nullable)
@@ -294,9 +305,7 @@ static rq_status index_add(rq_index *idx, const float *rows, uint64_t m, uint32_
         d_rows = staged.p;
     }
     RQC(ensure_row_keys(idx));
-    if (!idx->row_order_ok)
-        return fail(RQ_ERR_UNSUPPORTED, "a list of this index is not in the build's order (distance to its centroid, then id): rows can be "
-                                        "removed from it, but not added (an index from rq_from_arrays / rq_load_dir whose ids were remapped?)");
+    if (!idx->row_order_ok) return fail(RQ_ERR_UNSUPPORTED, kOrderRefusal);
     if (idx->metric.id != RQ_METRIC_L2) {  // N(row) / A(row; the index's S), padded: pass 1 and the gather then take the rows as an L2 build of them does
         DevBuf<float> stored;
         DevBuf<uint32_t> bad;

@@ -33,6 +33,7 @@
 #include "kernels_range.h"
 #include "kernels_small.h"
 #include "kernels_train.h"
+#include "kernels_merge.h"
 
 #include "kernel_shapes.h"
 #include "host_state.h"
@@ -45,6 +46,7 @@
 #include "host_range.h"
 #include "host_build.h"
 #include "host_mutate.h"
+#include "host_merge.h"
 #include "host_exact.h"
 #include "host_exact_range.h"
 #include "host_train.h"
@@ -1107,6 +1109,16 @@ rq_status rq_add(rq_index *idx, const float *rows, uint64_t m, uint32_t d, const
 rq_status rq_remove(rq_index *idx, const uint32_t *id_bits, uint64_t nbits, int bits_on_device, uint64_t *out_removed) {
     const auto t0 = std::chrono::steady_clock::now();
     return mutate_done(idx, index_remove(idx, id_bits, nbits, bits_on_device, out_removed), t0);
+}
+// merge / extract (host_merge.h): the same invariant with no pass 1 -- rows, codes and factors move as they stand
+rq_status rq_merge_from(rq_index *dst, rq_index *src, uint32_t id_mode, uint32_t id_shift, uint32_t *out_shift) {
+    const auto t0 = std::chrono::steady_clock::now();
+    return mutate_done(dst, index_merge_from(dst, src, id_mode, id_shift, out_shift), t0);
+}
+rq_status rq_extract(rq_index *src, const uint32_t *id_bits, uint64_t nbits, int bits_on_device, rq_index **out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const rq_status s = index_extract(src, id_bits, nbits, bits_on_device, out);
+    return mutate_done(out ? *out : nullptr, s, t0);  // (rows_after: the new index's)
 }
 rq_status rq_last_mutate_stats(rq_mutate_stats_t *out) {
     if (!out) return fail(RQ_ERR_INVALID, "null argument");

@@ -512,6 +512,50 @@ class RaBitQ:
         self.remove(ids=idv)
         self.add(rows, idv)
 
+    # ---- merge / extract: stored rows move as they stand, nothing is quantised again ----------------
+    def merge_from(self, other: "RaBitQ", ids="append") -> int:
+        """Take in the live rows of `other`, an index over the same rotation, centroids, metric and dim (rq_merge_from): this
+        index afterwards equals a fresh build of both row sets.  ids: "append" = other's ids + (1 + the largest id held here),
+        "keep" = other's ids as they are (none may be held here), or an int shift added to other's ids.  -> the shift applied.
+        `other` is not changed and stays usable; filters made on this index before are refused afterwards."""
+        if not isinstance(other, RaBitQ):
+            raise TypeError(f"other must be a RaBitQ index, not {type(other).__name__}")
+        if other is self:
+            raise ValueError("an index cannot be merged into itself")
+        if isinstance(ids, str):
+            modes = {"append": _lib.MERGE_IDS_APPEND, "keep": _lib.MERGE_IDS_KEEP}
+            if ids not in modes:
+                raise ValueError(f'ids must be "append", "keep" or an int shift, not {ids!r}')
+            mode, shift = modes[ids], 0
+        elif isinstance(ids, (int, np.integer)) and not isinstance(ids, bool):
+            if not 0 <= int(ids) <= 0xFFFFFFFF:
+                raise ValueError("ids are u32: 0 <= shift < 2^32")
+            mode, shift = _lib.MERGE_IDS_SHIFT, int(ids)
+        else:
+            raise TypeError(f'ids must be "append", "keep" or an int shift, not {type(ids).__name__}')
+        applied = C.c_uint32()
+        check(lib().rq_merge_from(self._h, other._h, mode, shift, C.byref(applied)))
+        self._refresh()
+        return int(applied.value)
+
+    def extract(self, ids=None, mask=None) -> "RaBitQ":
+        """A new index holding the rows whose ids are in `ids` (an id array) or where `mask` (a boolean mask over ids) is set, ids
+        kept (rq_extract): what remove() of the complement would leave, without touching this index."""
+        if ids is not None:
+            a = np.asarray(ids)
+            if a.size and a.dtype.kind not in "iu":
+                raise TypeError(f"ids must be integers, not {a.dtype}")
+        words, nbits = pack_filter_bits(ids=ids, mask=mask)
+        h = C.c_void_p()
+        check(lib().rq_extract(self._h, _addr(words), nbits, 0, C.byref(h)))
+        return type(self)(h)
+
+    def copy(self) -> "RaBitQ":
+        """A second index equal to this one: extract() with every id (no bitmap is made: RQ_EXTRACT_ALL_IDS)."""
+        h = C.c_void_p()
+        check(lib().rq_extract(self._h, None, _lib.EXTRACT_ALL_IDS, 0, C.byref(h)))
+        return type(self)(h)
+
     # ---- RaBitQ::query (src/rabitq.rs:268) ------------------------------------------------------
     def query(self, query, probe: int, topk: int, heuristic_rank: bool = False, filter: Filter = None):
         """-> list of (distance, original id), at most topk, in the reference's (unspecified,
@@ -997,7 +1041,7 @@ def last_profile() -> dict:
 
 
 def last_mutate_stats() -> dict:
-    """The calling thread's last add / remove by phase (include/rabitq_hip.h: rq_last_mutate_stats)."""
+    """The calling thread's last add / remove / merge_from / extract by phase (include/rabitq_hip.h: rq_last_mutate_stats)."""
     st = _lib.MutateStatsT()
     check(lib().rq_last_mutate_stats(C.byref(st)))
     return {name: getattr(st, name) for name, _ in _lib.MutateStatsT._fields_ if name not in ("struct_size", "reserved0")}
