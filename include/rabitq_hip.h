@@ -92,7 +92,9 @@ typedef struct {
  * rq_probe_counts_device;
  * later in 0.11, additions only: centroid training -- rq_train_params_t, rq_train_stats_t, rq_train_centroids,
  * rq_train_centroids_device;
- * 0.12.0: merge and extract, additions only -- RQ_MERGE_IDS_*, rq_merge_from, rq_extract; rq_last_mutate_stats reports them too).
+ * 0.12.0: merge and extract, additions only -- RQ_MERGE_IDS_*, rq_merge_from, rq_extract; rq_last_mutate_stats reports them too;
+ * 0.13.0: lazy removal, additions only -- rq_remove_lazy, rq_compact, rq_pending_removals; an index with pending removals
+ * refuses the entries that have no filtered form, and a filter made before a marking rq_remove_lazy is refused).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -683,6 +685,44 @@ rq_status rq_add(rq_index *idx, const float *rows, uint64_t m, uint32_t d, const
                  uint32_t *out_first_id);
 rq_status rq_remove(rq_index *idx, const uint32_t *id_bits, uint64_t nbits, int bits_on_device, uint64_t *out_removed);
 rq_status rq_last_mutate_stats(rq_mutate_stats_t *out);
+
+/* ---- lazy removal: mark rows dead without a relayout, compact later ------------------------------------------------------- */
+/* Let D be the ids marked dead since the last relayout (the pending removals).  An index with pending removals answers every query
+ * entry that has a filtered form as the same index after rq_remove(D) would, bit for bit: ids in order, distance bits, counts,
+ * status and the rough / precise / query counters of rq_metrics.  The dead rows stay stored; the index owns a filter of its live
+ * rows and every such entry runs under it (or under the caller's filter, which excludes the dead rows already).  rq_compact
+ * turns the index into rq_remove(D)'s: arrays, rq_info, dump files.  An index without pending removals behaves as before.
+ * rq_remove_lazy: mark the ids set in the bitmap (rq_remove's format and limits).  Ids the index does not hold and ids already
+ *   dead are ignored; *out_marked (nullable) = rows newly dead (0: nothing changed).  One pass over the ids on the device, n / 8
+ *   bytes written: no relayout, no second copy of the arrays; the generation is not bumped, tile tables, workspaces and learnt
+ *   hints stay.  A call that marks anything bumps the index's removal epoch: filters made before it are refused with
+ *   RQ_ERR_INVALID (make them again); a call that marks nothing leaves them valid.  Accepted on every index that accepts a
+ *   filter: every metric and row type, tiered and split-row indexes, mutated and merged ones, lists out of the build's order.
+ *   Refused, index unchanged: RQ_ERR_UNSUPPORTED a shard made by rq_shard_index; RQ_ERR_INVALID a null handle (checked before the
+ *   device is looked for), nbits > 2^32, a null bitmap with nbits > 0, a rq_query_batch_device_begin ticket that has not ended.
+ *   No query may run during the call.
+ * rq_compact: rq_remove of the pending removals in one relayout; *out_removed (nullable) = rows dropped.  With none pending it
+ *   succeeds and changes nothing, the generation included.  It has rq_remove's refusals: a half-precision, byte-row, tiered or
+ *   split-row index answers RQ_ERR_UNSUPPORTED and keeps its pending removals (until it is rebuilt).  rq_last_mutate_stats reports
+ *   it as a remove.
+ * rq_pending_removals: *out_dead = stored rows that are dead.  rq_info.n stays the stored row count.
+ * With removals pending:
+ *   rq_query*, rq_query_batch* (plain, _device, _begin / _end, _adaptive), rq_range_search*, rq_exact_search*,
+ *     rq_exact_range_search* with filter == NULL run under the live filter: the filtered pass, that filter's own hints, the
+ *     small-batch rule of filtered batches with the live filter's density;
+ *   rq_filter_create admits allowed AND live rows (rq_filter_rows counts those);
+ *   rq_probe_counts_device, rq_coarse_rank, rq_rotate*, rq_query_prep are unchanged (they read no row);
+ *   rq_remove drops the pending and the requested rows in one relayout (*out_removed counts the rows that were live);
+ *   rq_add and rq_merge_from with such a dst compact first (one more relayout; rq_last_mutate_stats adds the phases up; on an
+ *     error the index is as it was or compacted, a pending removal is never lost); rq_merge_from with such a src is
+ *     RQ_ERR_UNSUPPORTED (src is never written: compact it or extract its live rows first);
+ *   rq_extract keeps requested AND live rows;
+ *   rq_dump_dir, rq_dump_json, rq_shard_index, rq_query_batch_device_probed, _seeded and rq_query_batch_sharded_device answer
+ *     RQ_ERR_UNSUPPORTED ("pending removals: rq_compact first"): they have no filtered form, and a dump would bring the dead rows back;
+ *   rq_get_array, rq_get_device_ptr, rq_scan, rq_rerank, rq_quantize_pack see the stored rows, dead ones included. */
+rq_status rq_remove_lazy(rq_index *idx, const uint32_t *id_bits, uint64_t nbits, int bits_on_device, uint64_t *out_marked);
+rq_status rq_compact(rq_index *idx, uint64_t *out_removed);
+rq_status rq_pending_removals(const rq_index *idx, uint64_t *out_dead);
 
 /* ---- merge two indexes, extract a sub-index ------------------------------------------------------------------------------ */
 /* Both work on stored rows as they stand: nothing is rotated, assigned, quantised -- or, on a cosine or inner-product index,

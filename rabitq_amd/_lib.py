@@ -37,6 +37,7 @@ EXPORTS = [
     "rq_query_batch_adaptive", "rq_query_batch_device_adaptive", "rq_probe_counts_device",
     "rq_train_centroids", "rq_train_centroids_device",
     "rq_merge_from", "rq_extract",
+    "rq_remove_lazy", "rq_compact", "rq_pending_removals",
 ]
 
 
@@ -270,6 +271,9 @@ def lib():
         "rq_last_mutate_stats": (i32, [C.POINTER(MutateStatsT)]),
         "rq_merge_from": (i32, [vp, vp, u32, u32, u32p]),
         "rq_extract": (i32, [vp, u32p, u64, C.c_int, pp]),
+        "rq_remove_lazy": (i32, [vp, u32p, u64, C.c_int, u64p]),
+        "rq_compact": (i32, [vp, u64p]),
+        "rq_pending_removals": (i32, [vp, u64p]),
         "rq_coarse_topk_device": (i32, [vp, f32p, u32, u32, u32, u32, u32, u32p, f32p]),
         "rq_merge_smallest_u64_device": (i32, [vp, u32, u32, u32, u32, vp]),
         "rq_query_batch_device_probed": (i32, [vp, f32p, u32, u32, u32p, f32p, u32, u32, C.c_int, f32p, u32p, u32p]),

@@ -16,6 +16,8 @@ static rq_status validate_call(const rq_index *idx, bool args_null, uint32_t len
     if (filter && filter->idx != idx) return fail(RQ_ERR_INVALID, "the filter was made for another index");
     if (filter && filter->generation != idx->generation)
         return fail(RQ_ERR_INVALID, "the filter was made before the index was last mutated (rq_add / rq_remove): make it again");
+    if (filter && filter->removal_epoch != idx->removal_epoch)
+        return fail(RQ_ERR_INVALID, "the filter was made before rows of the index were last marked dead (rq_remove_lazy): make it again");
     return RQ_OK;
 }
 static rq_status validate_query(const QueryCall &c) {

@@ -125,6 +125,8 @@ static rq_status index_merge_from(rq_index *dst, rq_index *src, uint32_t id_mode
     if (id_mode > RQ_MERGE_IDS_APPEND) return fail(RQ_ERR_INVALID, "unknown id_mode " + std::to_string(id_mode) + " (RQ_MERGE_IDS_KEEP, _SHIFT or _APPEND)");
     RQC(mutate_refusals(dst));
     RQC(mutate_refusals(src));
+    if (src->live)  // (src is never written: the caller compacts it, or extracts its live rows, first)
+        return fail(RQ_ERR_UNSUPPORTED, "src has pending removals (rq_remove_lazy): rq_compact it, or rq_extract its live rows, first");
     if (dst->dim != src->dim) return fail(RQ_ERR_INVALID, "the two indexes differ in dim: " + std::to_string(dst->dim) + " and " + std::to_string(src->dim));
     if (dst->k != src->k) return fail(RQ_ERR_INVALID, "the two indexes differ in k: " + std::to_string(dst->k) + " and " + std::to_string(src->k));
     if (dst->metric.id != src->metric.id) return fail(RQ_ERR_INVALID, "the two indexes differ in metric");
@@ -133,6 +135,8 @@ static rq_status index_merge_from(rq_index *dst, rq_index *src, uint32_t id_mode
     RQC(same_bits_check("the rotation P", dst->P.p, src->P.p, (uint64_t)dst->dim * dst->dim));
     RQC(same_bits_check("the rotated centroids", dst->centroids.p, src->centroids.p, (uint64_t)dst->k * dst->dim));
     if (dst->n + src->n >= 0xFFFFFFFFull) return fail(RQ_ERR_UNSUPPORTED, "n must fit u32 ids (rabitq.rs:64-65)");
+    CompactFirst pending;  // a dst with pending removals is compacted before its ids are looked at (a dead row's id is free again)
+    RQC(pending.run(dst));
     uint64_t top_dst = 0, top_src = 0, hits = 0;
     RQC(scan_ids(dst, nullptr, 0, &top_dst, &hits));
     RQC(scan_ids(src, nullptr, 0, &top_src, &hits));
@@ -186,6 +190,7 @@ static rq_status index_extract(rq_index *src, const uint32_t *id_bits, uint64_t 
     RQC(counts.alloc(std::max<uint64_t>(k, 1)));
     HIPC(hipMemset(pos_bits.p, every_id ? 0xFF : 0, nwords * 4));
     if (n && !every_id) filter_positions_kernel<<<(uint32_t)((n + 255) / 256), 256>>>(src->map_ids.p, n, d_bits, nbits, pos_bits.p, nwords);
+    if (src->live) bitmap_and_kernel<<<bitmap_grid(nwords), 256>>>(pos_bits.p, src->live->pos_bits.p, nwords);  // keep = requested AND live
     if (k) filter_lists_kernel<<<(uint32_t)k, 256>>>(pos_bits.p, src->offsets.p, counts.p);  // (masks each list's first and last word)
     std::vector<uint32_t> kept(k), h_out(k + 1, 0);
     if (k) HIPC(hipMemcpy(kept.data(), counts.p, k * 4, hipMemcpyDeviceToHost));

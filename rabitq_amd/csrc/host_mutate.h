@@ -1,6 +1,8 @@
 // host_mutate.h -- part of the host side of librabitq_hip.so (one translation unit: rabitq_hip.hip includes the host_*.h files in order;
 // they are not stand-alone headers).  In-place mutation (rq_add / rq_remove): one relayout from (index, rows to drop, new rows)
-// to the index a fresh build of the live rows would produce, bit for bit.
+// to the index a fresh build of the live rows would produce, bit for bit.  Lazy removal (rq_remove_lazy / rq_compact,
+// DESIGN §4.18): rows marked dead in a filter the index owns, dropped by the next relayout; and what a filter derives from its
+// position bitmap (filter_finish), shared with rq_filter_create.
 #pragma once
 
 // The key word of every stored row (row_key), once per index: the stored rows are the build's zero-padded input, so rotating
@@ -138,6 +140,8 @@ static rq_status commit_layout(rq_index *idx, std::unique_ptr<rq_index> &nx, Pha
     idx->pass_budget = nx->pass_budget;
     idx->h_offsets.swap(nx->h_offsets);
     idx->row_key_valid = true;
+    delete idx->live;  // the pending removals went with the old layout (every relayout of a pending index drops them)
+    idx->live = nullptr;
     {  // workspaces and tile tables describe the old layout (no query runs during a mutation; the learnt hints stay)
         std::lock_guard<std::mutex> g(idx->tt_mu);
         idx->tile_tables.clear();
@@ -257,6 +261,139 @@ static void mutate_stats_begin(const rq_index *idx) {
     g_mutate_stats.rows_before = g_mutate_stats.rows_after = idx ? idx->n : 0;
 }
 
+// ---- filters and lazy removal -----------------------------------------------------------------------------------
+// What follows from a filter's position bitmap (f->pos_bits, filled by work already enqueued on `st`, in idx's layout): the admitted
+// rows per list, their prefix sums (the sub-index's offsets, device and host), the ScanExtra and the row counts.  The caller's
+// filters (rq_filter_create) and the index's live filter (rq_remove_lazy) are finished here.
+static rq_status filter_finish(const rq_index *idx, rq_filter *f, hipStream_t st) {
+    const uint32_t k = idx->k;
+    DevBuf<uint32_t> counts;
+    RQC(counts.alloc(std::max<uint32_t>(k, 1)));
+    RQC(f->sub_off.alloc((size_t)k + 1));
+    RQC(f->extra.alloc(1));
+    if (k) filter_lists_kernel<<<k, 256, 0, st>>>(f->pos_bits.p, idx->offsets.p, counts.p);
+    std::vector<uint32_t> h_cnt(k);
+    std::vector<uint32_t> &h_off = f->h_sub_off;
+    h_off.assign((size_t)k + 1, 0);
+    if (k) HIPC(hipMemcpyAsync(h_cnt.data(), counts.p, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+    HIPC(hipStreamSynchronize(st));
+    HIPC(hipGetLastError());
+    for (uint32_t c = 0; c < k; ++c) h_off[c + 1] = h_off[c] + h_cnt[c];  // the sub-index's offsets (<= n < 2^32)
+    HIPC(hipMemcpy(f->sub_off.p, h_off.data(), h_off.size() * 4, hipMemcpyHostToDevice));
+    ScanExtra hx{};
+    hx.allow = f->pos_bits.p;
+    HIPC(hipMemcpy(f->extra.p, &hx, sizeof hx, hipMemcpyHostToDevice));
+    f->rows = h_off[k];
+    f->live_rows = 0;
+    if (idx->h_offsets.size() == (size_t)k + 1) {
+        for (uint32_t c = 0; c < k; ++c) f->live_rows += h_cnt[c] ? idx->h_offsets[c + 1] - idx->h_offsets[c] : 0u;
+    } else
+        f->live_rows = idx->n;
+    f->idx = idx;
+    f->generation = idx->generation;
+    f->removal_epoch = idx->removal_epoch;
+    return RQ_OK;
+}
+
+// words of a position bitmap over n positions: whole 64-position waves, and never empty
+static uint64_t pos_bitmap_words(uint64_t n) { return (n + 63) / 64 * 2 + 2; }
+static uint32_t bitmap_grid(uint64_t nwords) { return (uint32_t)std::min<uint64_t>(ceil_div(nwords, 256), 4096); }
+
+// rq_remove_lazy: the rows whose id bit is set leave the live filter; nothing of the index's arrays moves.  The new bitmap and
+// what follows from it are made beside the old ones and swapped in only when everything has succeeded.
+static rq_status index_remove_lazy(rq_index *idx, const uint32_t *id_bits, uint64_t nbits, int bits_on_device, uint64_t *out_marked) {
+    if (!idx) return fail(RQ_ERR_INVALID, "null index");  // (before the device is looked for, as rq_merge_from)
+    RQC(ensure_device());
+    if (out_marked) *out_marked = 0;
+    if (idx->is_shard) return fail(RQ_ERR_UNSUPPORTED, "a shard made by rq_shard_index cannot be mutated (its ids are global)");
+    if (nbits > (1ull << 32)) return fail(RQ_ERR_INVALID, "nbits > 2^32 (ids are u32)");
+    if (!id_bits && nbits > 0) return fail(RQ_ERR_INVALID, "null bitmap with nbits > 0");
+    if (idx->open_tickets.load()) return fail(RQ_ERR_INVALID, "a rq_query_batch_device_begin ticket of this index has not ended");
+    const uint64_t n = idx->n, nwords = pos_bitmap_words(n), in_words = (nbits + 31) / 32;
+    if (n == 0 || nbits == 0) return RQ_OK;
+    DevBuf<uint32_t> staged;
+    const uint32_t *d_bits = id_bits;
+    if (!bits_on_device) {
+        RQC(staged.upload(id_bits, in_words));
+        d_bits = staged.p;
+    }
+    std::unique_ptr<rq_filter> nf(new rq_filter());
+    DevBuf<unsigned long long> marked;
+    RQC(nf->pos_bits.alloc(nwords));
+    RQC(marked.alloc(1));
+    HIPC(hipMemset(nf->pos_bits.p, 0, nwords * 4));
+    HIPC(hipMemset(marked.p, 0, 8));
+    tombstone_positions_kernel<<<(uint32_t)((n + 255) / 256), 256>>>(idx->map_ids.p, n, d_bits, nbits, idx->live ? idx->live->pos_bits.p : nullptr,
+                                                                     nf->pos_bits.p, nwords, marked.p);
+    unsigned long long h_marked = 0;
+    HIPC(hipMemcpy(&h_marked, marked.p, 8, hipMemcpyDeviceToHost));
+    HIPC(hipGetLastError());
+    if (h_marked == 0) return RQ_OK;  // nothing changed: the epoch stays, earlier filters stay valid
+    RQC(filter_finish(idx, nf.get(), nullptr));
+    if (!idx->live) {
+        idx->live = nf.release();
+    } else {  // in place: the filter object and the hints its passes learnt stay
+        rq_filter *L = idx->live;
+        swap_buf(L->pos_bits, nf->pos_bits), swap_buf(L->sub_off, nf->sub_off), swap_buf(L->extra, nf->extra);
+        L->h_sub_off.swap(nf->h_sub_off);
+        L->rows = nf->rows, L->live_rows = nf->live_rows;
+    }
+    idx->live->removal_epoch = ++idx->removal_epoch;
+    if (out_marked) *out_marked = h_marked;
+    return RQ_OK;
+}
+
+// The relayout that drops the pending removals (the index has some, and mutate_refusals has passed): rq_remove of the dead rows.
+static rq_status compact_relayout(rq_index *idx) {
+    const uint64_t k = idx->k, nwords = pos_bitmap_words(idx->n);
+    DevBuf<uint32_t> drop;
+    RQC(drop.alloc(nwords));
+    HIPC(hipMemset(drop.p, 0, nwords * 4));
+    bitmap_or_not_kernel<<<bitmap_grid(nwords), 256>>>(drop.p, idx->live->pos_bits.p, nwords);
+    HIPC(hipGetLastError());
+    std::vector<uint32_t> dropped(k);
+    const std::vector<uint32_t> &so = idx->live->h_sub_off;
+    for (uint32_t c = 0; c < k; ++c) dropped[c] = idx->h_offsets[c + 1] - idx->h_offsets[c] - (so[c + 1] - so[c]);
+    RQC(ensure_row_keys(idx));
+    return relayout(idx, drop.p, dropped, nullptr);
+}
+
+// rq_add / rq_merge_from on an index with pending removals compact it first: one more relayout, whose phases are added to the
+// call's own when it ends (rows_before stays the stored row count the call found).
+struct CompactFirst {
+    rq_mutate_stats_t pre{};
+    bool on = false;
+    rq_status run(rq_index *idx) {
+        if (!idx->live) return RQ_OK;
+        RQC(compact_relayout(idx));
+        pre = g_mutate_stats, on = true;
+        const uint64_t rows_before = pre.rows_before;
+        mutate_stats_begin(idx);
+        g_mutate_stats.rows_before = rows_before;
+        return RQ_OK;
+    }
+    ~CompactFirst() {
+        if (!on) return;
+        rq_mutate_stats_t &st = g_mutate_stats;
+        st.ms_keys += pre.ms_keys, st.ms_assign += pre.ms_assign, st.ms_alloc += pre.ms_alloc, st.ms_merge += pre.ms_merge;
+        st.ms_gather += pre.ms_gather, st.ms_derive += pre.ms_derive, st.ms_free += pre.ms_free, st.gather_bytes += pre.gather_bytes;
+    }
+};
+
+static rq_status index_compact(rq_index *idx, uint64_t *out_removed) {
+    if (!idx) return fail(RQ_ERR_INVALID, "null index");  // (before the device is looked for)
+    RQC(ensure_device());
+    RQC(ensure_kernel_attributes());
+    mutate_stats_begin(idx);
+    if (out_removed) *out_removed = 0;
+    if (!idx->live) return RQ_OK;  // nothing pending: nothing changes, the generation stays
+    RQC(mutate_refusals(idx));
+    const uint64_t total = idx->pending();
+    RQC(compact_relayout(idx));
+    if (out_removed) *out_removed = total;
+    return RQ_OK;
+}
+
 static rq_status index_add(rq_index *idx, const float *rows, uint64_t m, uint32_t d, const uint32_t *ids, int rows_on_device,
                            uint32_t *out_first_id) {
     RQC(ensure_device());
@@ -266,6 +403,8 @@ static rq_status index_add(rq_index *idx, const float *rows, uint64_t m, uint32_
     if (m && !rows) return fail(RQ_ERR_INVALID, "null rows with m > 0");
     RQC(raw_len_check(idx, "row", d));
     if (m >= 0xFFFFFFFFull || idx->n + m >= 0xFFFFFFFFull) return fail(RQ_ERR_UNSUPPORTED, "n must fit u32 ids (rabitq.rs:64-65)");
+    CompactFirst pending;  // (before the ids are looked at: a dead row's id is free again)
+    RQC(pending.run(idx));
     uint64_t top = 0, hits = 0;
     NewRows nr;
     std::vector<uint32_t> h_ids;
@@ -333,17 +472,19 @@ static rq_status index_remove(rq_index *idx, const uint32_t *id_bits, uint64_t n
     if (!id_bits && nbits > 0) return fail(RQ_ERR_INVALID, "null bitmap with nbits > 0");
     if (out_removed) *out_removed = 0;
     const uint64_t n = idx->n, k = idx->k, nwords = (n + 63) / 64 * 2 + 2, in_words = (nbits + 31) / 32;
-    if (n == 0 || nbits == 0) return RQ_OK;
+    const uint64_t pending = idx->pending();  // rows marked dead by rq_remove_lazy: this relayout drops them with the requested ones
+    if (n == 0 || (nbits == 0 && !pending)) return RQ_OK;
     DevBuf<uint32_t> staged, pos_bits, counts;
     const uint32_t *d_bits = id_bits;
-    if (!bits_on_device) {
+    if (!bits_on_device && in_words) {
         RQC(staged.upload(id_bits, in_words));
         d_bits = staged.p;
     }
     RQC(pos_bits.alloc(nwords));
     RQC(counts.alloc(std::max<uint64_t>(k, 1)));
     HIPC(hipMemset(pos_bits.p, 0, nwords * 4));
-    filter_positions_kernel<<<(uint32_t)((n + 255) / 256), 256>>>(idx->map_ids.p, n, d_bits, nbits, pos_bits.p, nwords);
+    if (nbits) filter_positions_kernel<<<(uint32_t)((n + 255) / 256), 256>>>(idx->map_ids.p, n, d_bits, nbits, pos_bits.p, nwords);
+    if (pending) bitmap_or_not_kernel<<<bitmap_grid(nwords), 256>>>(pos_bits.p, idx->live->pos_bits.p, nwords);
     if (k) filter_lists_kernel<<<(uint32_t)k, 256>>>(pos_bits.p, idx->offsets.p, counts.p);
     std::vector<uint32_t> dropped(k);
     if (k) HIPC(hipMemcpy(dropped.data(), counts.p, k * 4, hipMemcpyDeviceToHost));
@@ -355,6 +496,6 @@ static rq_status index_remove(rq_index *idx, const uint32_t *id_bits, uint64_t n
     counts.release();
     RQC(ensure_row_keys(idx));
     RQC(relayout(idx, pos_bits.p, dropped, nullptr));
-    if (out_removed) *out_removed = total;
+    if (out_removed) *out_removed = total - pending;  // (rows that were live; the pending ones were counted when they were marked)
     return RQ_OK;
 }

@@ -34,6 +34,7 @@ rq_status rq_shard_index(const rq_index *idx, const uint32_t *owner, uint32_t ra
     RQC(ensure_kernel_attributes());
     if (!idx || !owner || !out) return fail(RQ_ERR_INVALID, "null argument");
     *out = nullptr;
+    if (idx->live) return fail(RQ_ERR_UNSUPPORTED, kPendingRefusal);
     const uint32_t k = idx->k, dim = idx->dim;
     std::vector<uint32_t> off((size_t)k + 1), noff((size_t)k + 1);
     RQC(rq_get_array(idx, RQ_ARR_OFFSETS, off.data(), off.size() * 4));
@@ -351,6 +352,7 @@ rq_status rq_query_batch_sharded_device(const rq_index *shard, void *nccl_comm, 
     RQC(ensure_device());
     RQC(ensure_kernel_attributes());
     if (!shard || world == 0) return fail(RQ_ERR_INVALID, "null argument");
+    if (shard->live) return fail(RQ_ERR_UNSUPPORTED, kPendingRefusal);
     if (world > 1 && !nccl_comm) return fail(RQ_ERR_INVALID, "world > 1 needs an RCCL communicator");
     // limits that depend on the arguments only: every rank takes the same branch here
     if (topk == 0 || topk > RQ_MAX_TOPK || (uint64_t)world * topk > 8192) return fail(RQ_ERR_UNSUPPORTED, "topk in [1, 2048] and world * topk <= 8192");

@@ -281,9 +281,7 @@ struct rq_index {
     RowSpec rows;
     size_t row_bytes() const { return rows.row_bytes(dim); }
     BaseView view() const { return BaseView{base.p, base_host_dev, list_tier.p, k, split_rows ? 1u : 0u, rows.id}; }
-    ~rq_index() {
-        if (base_host) (void)hipHostFree(base_host);
-    }
+    ~rq_index();  // (defined below struct rq_filter: it frees the live filter)
     DevBuf<float> base, P, centroids, cent_t;
     DevBuf<_Float16> base_h;  // fp16 shadow of `base` (rerank pre-filter, derived; untiered indexes with HBM to spare; option rerank_shadow = 1)
     DevBuf<uint8_t> base_q8;  // 8-bit shadow of `base`, one affine map per list (the default pre-filter: half the fp16 shadow's bytes per survivor)
@@ -319,6 +317,12 @@ struct rq_index {
     bool is_shard = false;        // made by rq_shard_index: added ids would collide with other ranks' ids, so it is never mutated
     uint64_t generation = 0;      // bumped by every relayout; a filter made for an older generation is refused
     std::atomic<int> open_tickets{0};  // rq_query_batch_device_begin tickets whose _end has not run
+    // lazy removal (rq_remove_lazy): the filter of the live rows, owned; null while no removal is pending.  Every query
+    // entry that has a filtered form runs under it when the caller brings no filter of their own (live_or).  Updated in place by
+    // rq_remove_lazy (its hints stay), dropped by every relayout (commit_layout).
+    struct rq_filter *live = nullptr;
+    uint64_t removal_epoch = 0;   // bumped by every rq_remove_lazy that marks a row; a filter made under an older epoch is refused
+    inline uint64_t pending() const;  // stored rows that are dead
 };
 
 // A query-time allow-list (rq_filter_create), in the index's own terms: one bit per cluster-order position and the admitted rows
@@ -339,7 +343,18 @@ struct rq_filter {
     std::atomic<uint32_t> big_dirs_hint{0};
     std::atomic<uint32_t> exact_cap_hint{0};  // as rq_index::exact_cap_hint, for the exact searches under this filter
     std::atomic<uint32_t> exact_range_cap_hint{0};  // as rq_index::exact_range_cap_hint, for the exact range searches under this filter
+    uint64_t removal_epoch = 0;     // idx->removal_epoch when it was made (a marking rq_remove_lazy since then: refused)
+    std::vector<uint32_t> h_sub_off;  // host copy of sub_off (k + 1)
 };
+inline rq_index::~rq_index() {
+    if (base_host) (void)hipHostFree(base_host);
+    delete live;
+}
+inline uint64_t rq_index::pending() const { return live ? n - live->rows : 0; }
+// The filter a query entry runs under: the caller's, else the index's live filter (null while no removal is pending).  A caller's
+// filter made on an index with pending removals already excludes the dead rows (rq_filter_create).
+static const rq_filter *live_or(const rq_index *idx, const rq_filter *filter) { return filter ? filter : (idx ? idx->live : nullptr); }
+static const char *const kPendingRefusal = "pending removals: rq_compact first (this entry has no filtered form, and a dump would bring the dead rows back)";
 // The learnt survivor-buffer hints a pass reads and updates: the index's own, or the filter's on a filtered pass.
 struct PassHints {
     std::atomic<uint32_t> &cap;

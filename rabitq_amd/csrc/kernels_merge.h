@@ -1,4 +1,5 @@
-// kernels_merge.h -- gfx950 kernels of rq_merge_from / rq_extract (host_merge.h), wave64.
+// kernels_merge.h -- gfx950 kernels of rq_merge_from / rq_extract (host_merge.h) and, at the end, of lazy removal
+// (rq_remove_lazy / rq_compact, host_mutate.h), wave64.
 // Two indexes over the same rotation and centroids hold, list by list, rows in one order: the 64-bit key
 // row_key << 32 | id (kernels_build.h, "In-place mutation").  Their merge is a per-list two-way merge by that key and one
 // gather of whole rows; nothing is rotated, assigned or quantised again.
@@ -201,4 +202,49 @@ __global__ __launch_bounds__(256) void merge_gather_kernel(const uint32_t *__res
                     if (ok[r] && e < V) base_o[q[r] * V + e] = v[r];
             }
     }
+}
+
+// ---- lazy removal (rq_remove_lazy / rq_compact) ----------------------------------------------------------------------
+// The live bitmap of an index (the position bitmap of its owned filter) after marking the rows whose id bit is set in `drop_ids`:
+// live' = live & ~drop, drop = drop_ids[map_ids[pos]] (ids >= nbits are not marked).  One wave covers 64 positions, as
+// filter_positions_kernel does: the drop bits come from ONE ballot, the two new words leave in two plain 32-bit stores (lanes 0
+// and 1).  live_in == nullptr: nothing was dead before -- the old words are "every position below n", so the bits past the last
+// position stay clear.  *marked (preset to 0) += the rows that were live and are not any more: one LDS word per block, one
+// integer atomic per block that marked anything.  live_out is another buffer than live_in (the host swaps them only when the
+// whole call has succeeded); its words past the last wave are preset to zero by the host.
+__global__ __launch_bounds__(256) void tombstone_positions_kernel(const uint32_t *__restrict__ map_ids, uint64_t n,
+                                                                  const uint32_t *__restrict__ drop_ids, uint64_t nbits,
+                                                                  const uint32_t *__restrict__ live_in, uint32_t *__restrict__ live_out,
+                                                                  uint64_t nwords, unsigned long long *__restrict__ marked) {
+    __shared__ uint32_t s_marked;
+    const uint64_t pos = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63;
+    if (threadIdx.x == 0) s_marked = 0;
+    __syncthreads();
+    bool drop = false;
+    if (pos < n) {
+        const uint32_t id = map_ids[pos];
+        drop = (uint64_t)id < nbits && ((drop_ids[id >> 5] >> (id & 31u)) & 1u);
+    }
+    const uint64_t d = __ballot(drop);
+    const uint64_t w = (pos - lane) >> 5;  // first of the wave's two words (nwords is even: w < nwords covers both)
+    uint64_t old = __ballot(pos < n);
+    if (live_in) old = w < nwords ? ((uint64_t)live_in[w] | ((uint64_t)live_in[w + 1] << 32)) : 0ull;
+    const uint64_t now = old & ~d;
+    if (lane < 2 && w + lane < nwords) live_out[w + lane] = (uint32_t)(now >> (32 * lane));
+    const uint32_t newly = (uint32_t)__popcll(old & d);
+    if (lane == 0 && newly) atomicAdd(&s_marked, newly);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_marked) atomicAdd(marked, (unsigned long long)s_marked);
+}
+
+// bits &= live over the nwords words of two position bitmaps of one layout: a caller's filter made on an index with pending
+// removals admits allowed AND live rows; rq_extract keeps requested AND live rows.
+__global__ __launch_bounds__(256) void bitmap_and_kernel(uint32_t *__restrict__ bits, const uint32_t *__restrict__ live, uint64_t nwords) {
+    for (uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x; w < nwords; w += (uint64_t)gridDim.x * 256) bits[w] &= live[w];
+}
+// bits |= ~live: the drop bits of a relayout on an index with pending removals (rq_compact: bits preset to 0; rq_remove: the
+// requested rows).  Bits past the last position come out set; every reader of drop bits looks at positions inside a list only.
+__global__ __launch_bounds__(256) void bitmap_or_not_kernel(uint32_t *__restrict__ bits, const uint32_t *__restrict__ live, uint64_t nwords) {
+    for (uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x; w < nwords; w += (uint64_t)gridDim.x * 256) bits[w] |= ~live[w];
 }

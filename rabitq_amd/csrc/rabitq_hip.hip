@@ -441,6 +441,7 @@ rq_status rq_get_array(const rq_index *idx, int which, void *dst, uint64_t dst_b
 // rabitq.rs:128-156
 rq_status rq_dump_dir(const rq_index *idx, const char *dir) {
     if (!idx || !dir) return fail(RQ_ERR_INVALID, "null argument");
+    if (idx->live) return fail(RQ_ERR_UNSUPPORTED, kPendingRefusal);
     mkdir(dir, 0777);
     const std::string d(dir);
     const uint32_t dim = idx->dim, k = idx->k;
@@ -536,6 +537,7 @@ rq_status rq_dump_dir(const rq_index *idx, const char *dir) {
 
 rq_status rq_dump_json(const rq_index *idx, const char *path) {
     if (!idx || !path) return fail(RQ_ERR_INVALID, "null argument");
+    if (idx->live) return fail(RQ_ERR_UNSUPPORTED, kPendingRefusal);
     const uint64_t n = idx->n, dim = idx->dim, k = idx->k;
     std::vector<float> base(n * dim), P(dim * dim), C(k * dim), fac(n * 4);
     std::vector<uint32_t> off(k + 1), ids(n);
@@ -780,9 +782,10 @@ rq_status rq_merge_smallest_u64_device(const uint64_t *d_in, uint32_t world, uin
     return RQ_OK;
 }
 
-// The call description of a C entry (host_plan.h: QueryCall).
+// The call description of a C entry (host_plan.h: QueryCall).  A call without a filter on an index with pending removals runs under
+// the index's live filter (live_or): nothing behind this point knows the difference.
 static QueryCall topk_call(const rq_index *idx, const rq_filter *filter, uint32_t len, uint32_t probe, uint32_t topk, int heuristic_rank, const QueryIO &io) {
-    return QueryCall{const_cast<rq_index *>(idx), filter, len, probe, topk, heuristic_rank != 0, io};
+    return QueryCall{const_cast<rq_index *>(idx), live_or(idx, filter), len, probe, topk, heuristic_rank != 0, io};
 }
 
 rq_status rq_query_batch_device_probed(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t len,
@@ -790,6 +793,7 @@ rq_status rq_query_batch_device_probed(const rq_index *idx, const float *d_queri
                                        uint32_t topk, int heuristic_rank, float *d_out_dist, uint32_t *d_out_id,
                                        uint32_t *d_out_n) {
     if (!d_probe_cluster || !d_probe_dist) return fail(RQ_ERR_INVALID, "null probe lists");
+    if (idx && idx->live) return fail(RQ_ERR_UNSUPPORTED, kPendingRefusal);
     if (idx && probe > idx->k) return fail(RQ_ERR_INVALID, "probe lists must have min(probe, k) columns: pass probe <= k");
     return query_device(topk_call(idx, nullptr, len, probe, topk, heuristic_rank, {d_queries, d_out_dist, d_out_id, d_out_n, d_probe_cluster, d_probe_dist}), nq, nullptr);
 }
@@ -799,6 +803,7 @@ rq_status rq_query_batch_device_seeded(const rq_index *idx, const float *d_queri
                                        uint32_t topk, int heuristic_rank, const float *d_thr_init, float *d_out_dist,
                                        uint32_t *d_out_id, uint32_t *d_out_n) {
     if (!d_probe_cluster || !d_probe_dist || !d_thr_init) return fail(RQ_ERR_INVALID, "null probe lists / thresholds");
+    if (idx && idx->live) return fail(RQ_ERR_UNSUPPORTED, kPendingRefusal);
     if (idx && probe > idx->k) return fail(RQ_ERR_INVALID, "probe lists must have min(probe, k) columns: pass probe <= k");
     return query_device(topk_call(idx, nullptr, len, probe, topk, heuristic_rank, {d_queries, d_out_dist, d_out_id, d_out_n, d_probe_cluster, d_probe_dist, d_thr_init}),
                         nq, nullptr);
@@ -934,6 +939,7 @@ rq_status rq_query_batch_device_adaptive(const rq_index *idx, const rq_filter *f
 rq_status rq_probe_counts_device(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t len, uint32_t probe,
                                  const rq_probe_rule_t *rule, uint32_t *d_out_nprobe) {
     QueryCall call = topk_call(idx, nullptr, len, probe, 1, 0, {d_queries});
+    call.filter = nullptr;  // (no row is read: pending removals change nothing here)
     RQC(probe_rule_check(rule, rule ? rule->max_probe : nullptr, d_out_nprobe, &call.rule));
     return probe_counts_device(call, nq);
 }
@@ -974,7 +980,7 @@ rq_status rq_query_batch_adaptive(const rq_index *idx, const rq_filter *filter, 
 // ---- range search: every neighbour inside a per-query radius, as a result object sized by the library (host_range.h) ----
 rq_status rq_range_search_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
                                  uint32_t probe, const float *d_radius, rq_range_result **out) {
-    return range_device(const_cast<rq_index *>(idx), filter, d_queries, nq, len, probe, d_radius, out);
+    return range_device(const_cast<rq_index *>(idx), live_or(idx, filter), d_queries, nq, len, probe, d_radius, out);
 }
 rq_status rq_range_search(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len,
                           uint32_t probe, const float *radius, rq_range_result **out) {
@@ -989,7 +995,7 @@ rq_status rq_range_search(const rq_index *idx, const rq_filter *filter, const fl
         HIPC(hipMemcpy(dq, queries, (uint64_t)nq * len * 4, hipMemcpyHostToDevice));
         HIPC(hipMemcpy(dr, radius, (uint64_t)nq * 4, hipMemcpyHostToDevice));
     }
-    return range_device(const_cast<rq_index *>(idx), filter, (const float *)dq, nq, len, probe, (const float *)dr, out);
+    return range_device(const_cast<rq_index *>(idx), live_or(idx, filter), (const float *)dq, nq, len, probe, (const float *)dr, out);
 }
 rq_status rq_range_result_info(const rq_range_result *r, uint32_t *out_nq, uint64_t *out_total) {
     if (!r || !out_nq || !out_total) return fail(RQ_ERR_INVALID, "null argument");
@@ -1021,9 +1027,7 @@ rq_status rq_filter_create(const rq_index *idx, const uint32_t *allow_bits, uint
     if (!allow_bits && nbits > 0) return fail(RQ_ERR_INVALID, "null bitmap with nbits > 0");
     RQC(ensure_device());
     std::unique_ptr<rq_filter> f(new rq_filter());
-    f->idx = idx;
-    f->generation = idx->generation;
-    const uint64_t n = idx->n, nwords = (n + 63) / 64 * 2 + 2;  // (whole 64-position waves, and never empty)
+    const uint64_t n = idx->n, nwords = pos_bitmap_words(n);
     const uint64_t in_words = (nbits + 31) / 32;
     DevBuf<uint32_t> staged;  // the caller's bitmap in device memory (host bitmaps are copied)
     const uint32_t *d_allow = allow_bits;
@@ -1034,10 +1038,6 @@ rq_status rq_filter_create(const rq_index *idx, const uint32_t *allow_bits, uint
         d_allow = staged.p;
     }
     RQC(f->pos_bits.alloc(nwords));
-    RQC(f->sub_off.alloc((size_t)idx->k + 1));
-    RQC(f->extra.alloc(1));
-    DevBuf<uint32_t> counts;
-    RQC(counts.alloc(std::max<uint32_t>(idx->k, 1)));
     hipStream_t st = nullptr;
     HIPC(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     struct StreamGuard {
@@ -1046,21 +1046,9 @@ rq_status rq_filter_create(const rq_index *idx, const uint32_t *allow_bits, uint
     } sg{st};
     HIPC(hipMemsetAsync(f->pos_bits.p, 0, nwords * 4, st));
     if (n) filter_positions_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(idx->map_ids.p, n, d_allow, nbits, f->pos_bits.p, nwords);
-    if (idx->k) filter_lists_kernel<<<idx->k, 256, 0, st>>>(f->pos_bits.p, idx->offsets.p, counts.p);
-    std::vector<uint32_t> h_cnt(idx->k), h_off((size_t)idx->k + 1, 0);
-    if (idx->k) HIPC(hipMemcpyAsync(h_cnt.data(), counts.p, (size_t)idx->k * 4, hipMemcpyDeviceToHost, st));
-    HIPC(hipStreamSynchronize(st));
-    HIPC(hipGetLastError());
-    for (uint32_t c = 0; c < idx->k; ++c) h_off[c + 1] = h_off[c] + h_cnt[c];  // the sub-index's offsets (<= n < 2^32)
-    HIPC(hipMemcpy(f->sub_off.p, h_off.data(), h_off.size() * 4, hipMemcpyHostToDevice));
-    ScanExtra hx{};
-    hx.allow = f->pos_bits.p;
-    HIPC(hipMemcpy(f->extra.p, &hx, sizeof hx, hipMemcpyHostToDevice));
-    f->rows = h_off[idx->k];
-    if (idx->h_offsets.size() == (size_t)idx->k + 1) {
-        for (uint32_t c = 0; c < idx->k; ++c) f->live_rows += h_cnt[c] ? idx->h_offsets[c + 1] - idx->h_offsets[c] : 0u;
-    } else
-        f->live_rows = n;
+    // an index with pending removals (rq_remove_lazy): admitted = allowed AND live
+    if (idx->live) bitmap_and_kernel<<<bitmap_grid(nwords), 256, 0, st>>>(f->pos_bits.p, idx->live->pos_bits.p, nwords);
+    RQC(filter_finish(idx, f.get(), st));
     *out = f.release();
     return RQ_OK;
 }
@@ -1074,20 +1062,20 @@ void rq_filter_free(rq_filter *f) { delete f; }
 // ---- exact search (host_exact.h): brute-force top-k over the stored rows ----
 rq_status rq_exact_search_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len, uint32_t topk,
                                  const rq_exact_params_t *params, float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n) {
-    return exact_search_device(idx, filter, d_queries, nq, len, topk, params, d_out_dist, d_out_id, d_out_n);
+    return exact_search_device(idx, live_or(idx, filter), d_queries, nq, len, topk, params, d_out_dist, d_out_id, d_out_n);
 }
 rq_status rq_exact_search(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len, uint32_t topk,
                           const rq_exact_params_t *params, float *out_dist, uint32_t *out_id, uint32_t *out_n) {
-    return exact_search_host(idx, filter, queries, nq, len, topk, params, out_dist, out_id, out_n);
+    return exact_search_host(idx, live_or(idx, filter), queries, nq, len, topk, params, out_dist, out_id, out_n);
 }
 // ---- exact range search (host_exact_range.h): every stored row within a per-query radius, as an rq_range_result ----
 rq_status rq_exact_range_search_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
                                        const float *d_radius, const rq_exact_params_t *params, rq_range_result **out) {
-    return exact_range_device(idx, filter, d_queries, nq, len, d_radius, params, out);
+    return exact_range_device(idx, live_or(idx, filter), d_queries, nq, len, d_radius, params, out);
 }
 rq_status rq_exact_range_search(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len,
                                 const float *radius, const rq_exact_params_t *params, rq_range_result **out) {
-    return exact_range_host(idx, filter, queries, nq, len, radius, params, out);
+    return exact_range_host(idx, live_or(idx, filter), queries, nq, len, radius, params, out);
 }
 rq_status rq_last_exact_stats(rq_exact_stats_t *out) {
     if (!out) return fail(RQ_ERR_INVALID, "null argument");
@@ -1119,6 +1107,21 @@ rq_status rq_extract(rq_index *src, const uint32_t *id_bits, uint64_t nbits, int
     const auto t0 = std::chrono::steady_clock::now();
     const rq_status s = index_extract(src, id_bits, nbits, bits_on_device, out);
     return mutate_done(out ? *out : nullptr, s, t0);  // (rows_after: the new index's)
+}
+// lazy removal (host_mutate.h): mark rows dead in the index's live filter, drop them in one relayout later
+rq_status rq_remove_lazy(rq_index *idx, const uint32_t *id_bits, uint64_t nbits, int bits_on_device, uint64_t *out_marked) {
+    const rq_status s = index_remove_lazy(idx, id_bits, nbits, bits_on_device, out_marked);
+    if (s != RQ_OK) (void)hipGetLastError();  // (a failed hipMalloc's sticky error must not fail the next call)
+    return s;
+}
+rq_status rq_compact(rq_index *idx, uint64_t *out_removed) {
+    const auto t0 = std::chrono::steady_clock::now();
+    return mutate_done(idx, index_compact(idx, out_removed), t0);
+}
+rq_status rq_pending_removals(const rq_index *idx, uint64_t *out_dead) {
+    if (!idx || !out_dead) return fail(RQ_ERR_INVALID, "null argument");
+    *out_dead = idx->pending();
+    return RQ_OK;
 }
 rq_status rq_last_mutate_stats(rq_mutate_stats_t *out) {
     if (!out) return fail(RQ_ERR_INVALID, "null argument");

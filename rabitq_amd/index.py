@@ -226,6 +226,14 @@ class RaBitQ:
         rt = C.c_uint32()
         check(lib().rq_row_type(self._h, C.byref(rt)))
         self.row_type = _lib.ROW_TYPE_NAMES.get(int(rt.value), "f32")   # "f16" / "bf16" / "u8" / "i8": the raw vectors are stored in that type, 2*dim / dim bytes each
+        dead = C.c_uint64()
+        check(lib().rq_pending_removals(self._h, C.byref(dead)))
+        self.pending_removals = int(dead.value)   # stored rows marked dead by remove(lazy=True) and not compacted yet (n counts them)
+
+    @property
+    def live_n(self) -> int:
+        """Rows a query can return: n - pending_removals."""
+        return self.n - self.pending_removals
 
     # ---- RaBitQ::from_path (src/rabitq.rs:159) ------------------------------------------------
     @classmethod
@@ -323,6 +331,7 @@ class RaBitQ:
         return cls(h)
 
     def dump_to_dir(self, path) -> None:
+        """Refused (RQ_ERR_UNSUPPORTED) while removals are pending: a dump would bring the dead rows back -- compact() first."""
         check(lib().rq_dump_dir(self._h, os.fsencode(path)))
 
     # ---- load_from_json / dump_to_json (src/rabitq.rs:72-81) -------------------------------------
@@ -333,6 +342,7 @@ class RaBitQ:
         return cls(h)
 
     def dump_to_json(self, path) -> None:
+        """Refused (RQ_ERR_UNSUPPORTED) while removals are pending: a dump would bring the dead rows back -- compact() first."""
         check(lib().rq_dump_json(self._h, os.fsencode(path)))
 
     @classmethod
@@ -472,7 +482,8 @@ class RaBitQ:
     def add(self, vectors, ids=None) -> np.ndarray:
         """Insert rows (m x d, d padding to dim) -> the u32 ids they got: `ids` (absent from the index, unique), or by default
         the next ids after the largest the index holds.  One relayout (include/rabitq_hip.h: rq_add); filters made before it
-        are refused afterwards."""
+        are refused afterwards.  With removals pending the index is compacted first (one more relayout): the id of a dead row
+        is free again, and the next ids follow the largest LIVE id."""
         rows = self._rows(vectors)
         m = rows.shape[0]
         idv = self._ids(ids, m) if ids is not None else None
@@ -489,27 +500,40 @@ class RaBitQ:
         self._refresh()
         return int(first.value)
 
-    def remove(self, ids=None, mask=None) -> int:
+    def remove(self, ids=None, mask=None, lazy: bool = False) -> int:
         """Remove the ids `ids` (an id array) or those where `mask` (a boolean mask over ids) is set; ids not in the index are
-        ignored.  -> rows removed.  One relayout (rq_remove) unless nothing matched."""
+        ignored.  -> rows removed.  One relayout (rq_remove) unless nothing matched; it drops pending removals too.
+        lazy=True (rq_remove_lazy): the rows are only marked dead -- no relayout, no second copy of the arrays, and it works on
+        typed, tiered and split-row indexes too.  Every query answers as after the eager removal, through the filtered pass,
+        until compact(); -> rows newly dead (ids already dead are ignored).  Filters made before a call that marks anything
+        are refused afterwards."""
         if ids is not None:
             a = np.asarray(ids)
             if a.size and a.dtype.kind not in "iu":
                 raise TypeError(f"ids must be integers, not {a.dtype}")
         words, nbits = pack_filter_bits(ids=ids, mask=mask)
         removed = C.c_uint64()
-        check(lib().rq_remove(self._h, _addr(words), nbits, 0, C.byref(removed)))
+        entry = lib().rq_remove_lazy if lazy else lib().rq_remove
+        check(entry(self._h, _addr(words), nbits, 0, C.byref(removed)))
         self._refresh()
         return int(removed.value)
 
-    def update(self, ids, vectors) -> None:
+    def compact(self) -> int:
+        """Drop the pending removals in one relayout (rq_compact) -> rows dropped; 0 and no change when none is pending.  An index
+        that cannot be mutated eagerly (typed, tiered or split rows) answers RQ_ERR_UNSUPPORTED and keeps its pending removals."""
+        removed = C.c_uint64()
+        check(lib().rq_compact(self._h, C.byref(removed)))
+        self._refresh()
+        return int(removed.value)
+
+    def update(self, ids, vectors, lazy: bool = False) -> None:
         """Give the ids `ids` the rows `vectors` (ids not in the index are inserted): remove followed by add with those ids --
-        two relayouts, not one."""
+        two relayouts, not one.  `lazy` goes to the remove (the add then compacts first: still two relayouts, no eager scan)."""
         rows = self._rows(vectors)
         idv = self._ids(ids, rows.shape[0])
         if np.unique(idv).size != idv.size:
             raise ValueError("ids must be unique")
-        self.remove(ids=idv)
+        self.remove(ids=idv, lazy=lazy)
         self.add(rows, idv)
 
     # ---- merge / extract: stored rows move as they stand, nothing is quantised again ----------------
@@ -517,7 +541,9 @@ class RaBitQ:
         """Take in the live rows of `other`, an index over the same rotation, centroids, metric and dim (rq_merge_from): this
         index afterwards equals a fresh build of both row sets.  ids: "append" = other's ids + (1 + the largest id held here),
         "keep" = other's ids as they are (none may be held here), or an int shift added to other's ids.  -> the shift applied.
-        `other` is not changed and stays usable; filters made on this index before are refused afterwards."""
+        `other` is not changed and stays usable; filters made on this index before are refused afterwards.  With removals
+        pending here the index is compacted first; with removals pending in `other` the call is refused (RQ_ERR_UNSUPPORTED):
+        compact `other`, or extract its live rows, first."""
         if not isinstance(other, RaBitQ):
             raise TypeError(f"other must be a RaBitQ index, not {type(other).__name__}")
         if other is self:
@@ -540,7 +566,8 @@ class RaBitQ:
 
     def extract(self, ids=None, mask=None) -> "RaBitQ":
         """A new index holding the rows whose ids are in `ids` (an id array) or where `mask` (a boolean mask over ids) is set, ids
-        kept (rq_extract): what remove() of the complement would leave, without touching this index."""
+        kept (rq_extract): what remove() of the complement would leave, without touching this index.  Rows marked dead by
+        remove(lazy=True) are never taken."""
         if ids is not None:
             a = np.asarray(ids)
             if a.size and a.dtype.kind not in "iu":
@@ -551,7 +578,8 @@ class RaBitQ:
         return type(self)(h)
 
     def copy(self) -> "RaBitQ":
-        """A second index equal to this one: extract() with every id (no bitmap is made: RQ_EXTRACT_ALL_IDS)."""
+        """A second index equal to this one: extract() with every id (no bitmap is made: RQ_EXTRACT_ALL_IDS).  With removals
+        pending the copy holds the live rows only -- it is this index compacted."""
         h = C.c_void_p()
         check(lib().rq_extract(self._h, None, _lib.EXTRACT_ALL_IDS, 0, C.byref(h)))
         return type(self)(h)
@@ -941,7 +969,8 @@ class RaBitQ:
         return owner, load
 
     def shard(self, owner, rank: int) -> "RaBitQ":
-        """The shard of `rank`: same centroids and rotation, only the lists with owner[c] == rank (original ids kept)."""
+        """The shard of `rank`: same centroids and rotation, only the lists with owner[c] == rank (original ids kept).
+        Refused (RQ_ERR_UNSUPPORTED) while removals are pending: compact() first.  A shard itself refuses remove(lazy=True)."""
         owner = np.ascontiguousarray(owner, dtype=np.uint32)
         assert owner.size == self.k
         h = C.c_void_p()
