@@ -1020,178 +1020,3 @@ __global__ void assign_scatter_kernel(const uint32_t *__restrict__ redo, uint32_
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < m) label[redo[i]] = lab_in[i], dist[redo[i]] = dist_in[i];
 }
-
-// ------------------------------------------------------------------------------------------------
-// In-place mutation (host_mutate.h: rq_add / rq_remove).  A relayout builds the arrays a fresh build of the live rows would
-// produce: every list keeps the build's order, the 64-bit key ord32_biased(dist to the list's centroid) << 32 | id.
-// ------------------------------------------------------------------------------------------------
-// The key word of stored rows p0 .. p0+m (rotated in xrot, m x dim): the distance to the row's own list's centroid in the
-// lane order of assign_refine_kernel, with its clamp (a minimum that is not below f32::MAX is f32::MAX: NaN / inf rows, list 0).
-__global__ __launch_bounds__(256) void row_key_kernel(const float *__restrict__ xrot, uint64_t p0, uint64_t m, uint32_t dim,
-                                                      const float *__restrict__ centroids, const uint32_t *__restrict__ offsets,
-                                                      uint32_t k, uint32_t *__restrict__ row_key) {
-    const uint32_t hf = threadIdx.x & 1;
-    const uint64_t v = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 1;
-    if (v >= m) return;
-    const uint64_t p = p0 + v;
-    uint32_t lo = 0, hi = k;  // largest c with offsets[c] <= p (empty lists share their start with the next one)
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (offsets[mid] <= p) lo = mid;
-        else hi = mid;
-    }
-    const float dd = pair_l2sq_exact(xrot + v * dim + 4 * hf, centroids + (uint64_t)lo * dim + 4 * hf, dim);
-    if (hf == 0) row_key[p] = ord32_biased(dd < 3.402823466e+38f ? dd : 3.402823466e+38f);
-}
-
-// out[0] = 1 + the largest id in map_ids (0 if n == 0), out[1] = ids of map_ids found among the m ascending ids `sorted`
-// (nullable); out preset to 0
-__global__ __launch_bounds__(256) void id_scan_kernel(const uint32_t *__restrict__ map_ids, uint64_t n, const uint32_t *__restrict__ sorted,
-                                                      uint32_t m, unsigned long long *__restrict__ out) {
-    unsigned long long top = 0, hits = 0;
-    for (uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (uint64_t)gridDim.x * 256) {
-        const uint32_t id = map_ids[p];
-        top = (unsigned long long)id + 1 > top ? (unsigned long long)id + 1 : top;
-        if (sorted && m) {
-            uint32_t lo = 0, hi = m;  // first batch id not below `id`
-            while (lo < hi) {
-                const uint32_t mid = lo + ((hi - lo) >> 1);
-                if (sorted[mid] < id) lo = mid + 1;
-                else hi = mid;
-            }
-            hits += lo < m && sorted[lo] == id ? 1u : 0u;
-        }
-    }
-    for (int o = 32; o >= 1; o >>= 1) {
-        const unsigned long long t = __shfl_xor(top, o, 64), h = __shfl_xor(hits, o, 64);
-        top = t > top ? t : top;
-        hits += h;
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (top) atomicMax(out, top);
-        if (hits) atomicAdd(out + 1, hits);
-    }
-}
-
-// Adjacent rows of a list out of the build's order (key not strictly above its predecessor's), one block per list, counted
-// into *bad.  An index made by rq_build / rq_add never has one; rq_from_arrays / rq_load_dir take whatever order they are given.
-__global__ __launch_bounds__(256) void list_order_kernel(const uint32_t *__restrict__ offsets, const uint32_t *__restrict__ row_key,
-                                                         const uint32_t *__restrict__ map_ids, unsigned int *__restrict__ bad) {
-    const uint32_t b = offsets[blockIdx.x], e = offsets[blockIdx.x + 1];
-    uint32_t cnt = 0;
-    for (uint32_t p = b + 1 + threadIdx.x; p < e; p += 256) {
-        const unsigned long long k0 = ((unsigned long long)row_key[p - 1] << 32) | map_ids[p - 1];
-        const unsigned long long k1 = ((unsigned long long)row_key[p] << 32) | map_ids[p];
-        cnt += k0 < k1 ? 0u : 1u;
-    }
-    if (cnt) atomicAdd(bad, cnt);
-}
-
-// the key of sorted new row j: its sort key's low word is the row's rank among the batch's ids; the id is new_ids[rank]
-// (ascending) or id0 + rank
-__device__ __forceinline__ unsigned long long mut_new_key(const unsigned long long *__restrict__ new_keys,
-                                                          const uint32_t *__restrict__ new_ids, uint32_t id0, uint32_t j) {
-    const unsigned long long k64 = new_keys[j];
-    const uint32_t r = (uint32_t)k64;
-    return (k64 & 0xFFFFFFFF00000000ull) | (new_ids ? new_ids[r] : id0 + r);
-}
-
-// Merge path, one block per list: the destination of every row of the new layout, as src_of_dst[dst] = old position p
-// (< n_old) or n_old + j for sorted new row j.  A kept old row lands at (its rank among the list's kept rows) + (new keys
-// below its key); new row j at (its rank among the list's new rows) + (old keys below its key).  Keys are unique (ids
-// are), so "below" and "at or below" agree.  drop_bits (nullable): old positions that leave; a relayout either drops rows
-// or adds them, never both (the new rows' ranks count every old row of the list).
-__global__ __launch_bounds__(256) void mutate_merge_kernel(const uint32_t *__restrict__ old_off, const uint32_t *__restrict__ row_key,
-                                                           const uint32_t *__restrict__ map_ids, const uint32_t *__restrict__ drop_bits,
-                                                           const uint32_t *__restrict__ new_off,
-                                                           const unsigned long long *__restrict__ new_keys,
-                                                           const uint32_t *__restrict__ new_ids, uint32_t id0,
-                                                           const uint32_t *__restrict__ out_off, uint32_t n_old,
-                                                           uint32_t *__restrict__ src_of_dst) {
-    __shared__ uint32_t wsum[4];
-    __shared__ uint32_t s_run;
-    const uint32_t c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t ob = old_off[c], oe = old_off[c + 1], nb = new_off[c], ne = new_off[c + 1], out_b = out_off[c];
-    if (tid == 0) s_run = 0;
-    __syncthreads();
-    for (uint32_t t0 = ob; t0 < oe; t0 += 256) {
-        const uint32_t p = t0 + tid;
-        const bool keep = p < oe && !(drop_bits && ((drop_bits[p >> 5] >> (p & 31u)) & 1u));
-        const uint64_t mask = __ballot(keep);
-        if (lane == 0) wsum[wave] = (uint32_t)__popcll(mask);
-        __syncthreads();
-        uint32_t woff = 0, total = 0;
-        for (uint32_t w = 0; w < 4; ++w) woff += w < wave ? wsum[w] : 0u, total += wsum[w];
-        const uint32_t run = s_run;
-        if (keep) {
-            const unsigned long long key = ((unsigned long long)row_key[p] << 32) | map_ids[p];
-            uint32_t lo = nb, hi = ne;  // first new row whose key is not below `key`
-            while (lo < hi) {
-                const uint32_t mid = lo + ((hi - lo) >> 1);
-                if (mut_new_key(new_keys, new_ids, id0, mid) < key) lo = mid + 1;
-                else hi = mid;
-            }
-            const uint32_t below = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-            src_of_dst[out_b + run + woff + below + (lo - nb)] = p;
-        }
-        __syncthreads();
-        if (tid == 0) s_run = run + total;
-        __syncthreads();
-    }
-    for (uint32_t j = nb + tid; j < ne; j += 256) {
-        const unsigned long long key = mut_new_key(new_keys, new_ids, id0, j);
-        uint32_t lo = ob, hi = oe;  // first old row whose key is not below `key`
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if ((((unsigned long long)row_key[mid] << 32) | map_ids[mid]) < key) lo = mid + 1;
-            else hi = mid;
-        }
-        src_of_dst[out_b + (j - nb) + (lo - ob)] = n_old + j;
-    }
-}
-
-// The new layout's rows, one wave per destination row (16-byte accesses for f32 rows): raw vector, codes, factors, id and
-// key word from the old arrays or from the new rows (m x d input rows, zero-padded to dim as the build does; codes /
-// factors of pass 1 indexed by input row; new_src: input row of batch rank r, nullptr = r).
-__global__ __launch_bounds__(256) void mutate_gather_kernel(const uint32_t *__restrict__ src_of_dst, uint64_t n_out, uint32_t n_old,
-                                                            uint32_t m_new, uint32_t dim, uint32_t W, const float *__restrict__ base,
-                                                            const uint64_t *__restrict__ codes, const float4 *__restrict__ factors,
-                                                            const uint32_t *__restrict__ map_ids, const uint32_t *__restrict__ row_key,
-                                                            const unsigned long long *__restrict__ new_keys,
-                                                            const uint32_t *__restrict__ new_ids, uint32_t id0,
-                                                            const uint32_t *__restrict__ new_src, const float *__restrict__ rows,
-                                                            uint32_t d, const uint64_t *__restrict__ new_codes,
-                                                            const float4 *__restrict__ new_factors, float *__restrict__ base_o,
-                                                            uint64_t *__restrict__ codes_o, float4 *__restrict__ factors_o,
-                                                            uint32_t *__restrict__ map_ids_o, uint32_t *__restrict__ row_key_o,
-                                                            unsigned int *__restrict__ holes) {
-    const uint32_t lane = threadIdx.x & 63;
-    const bool rows_vec = d == dim && ((reinterpret_cast<uintptr_t>(rows) & 15u) == 0);
-    for (uint64_t q = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); q < n_out; q += (uint64_t)gridDim.x * 4) {
-        const uint32_t s = src_of_dst[q];
-        if (s - n_old >= m_new && s >= n_old) {  // a destination the merge did not fill: counted, and the relayout is refused
-            if (lane == 0) atomicAdd(holes, 1u);
-            continue;
-        }
-        float4 *dst = reinterpret_cast<float4 *>(base_o + q * dim);
-        if (s < n_old) {
-            const float4 *src = reinterpret_cast<const float4 *>(base + (uint64_t)s * dim);
-            for (uint32_t e = lane; e < dim / 4; e += 64) dst[e] = src[e];
-            for (uint32_t w = lane; w < W; w += 64) codes_o[q * W + w] = codes[(uint64_t)s * W + w];
-            if (lane == 0) factors_o[q] = factors[s], map_ids_o[q] = map_ids[s], row_key_o[q] = row_key[s];
-        } else {
-            const unsigned long long k64 = new_keys[s - n_old];
-            const uint32_t r = (uint32_t)k64, i = new_src ? new_src[r] : r;
-            const float *src = rows + (uint64_t)i * d;
-            if (rows_vec) {
-                for (uint32_t e = lane; e < dim / 4; e += 64) dst[e] = reinterpret_cast<const float4 *>(src)[e];
-            } else {
-                float *w = base_o + q * dim;
-                for (uint32_t e = lane; e < dim; e += 64) w[e] = e < d ? src[e] : 0.0f;
-            }
-            for (uint32_t w = lane; w < W; w += 64) codes_o[q * W + w] = new_codes[(uint64_t)i * W + w];
-            if (lane == 0)
-                factors_o[q] = new_factors[i], map_ids_o[q] = new_ids ? new_ids[r] : id0 + r, row_key_o[q] = (uint32_t)(k64 >> 32);
-        }
-    }
-}

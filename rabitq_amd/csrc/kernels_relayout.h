@@ -1,9 +1,95 @@
-// kernels_merge.h -- gfx950 kernels of rq_merge_from / rq_extract (host_merge.h) and, at the end, of lazy removal
-// (rq_remove_lazy / rq_compact, host_mutate.h), wave64.
-// Two indexes over the same rotation and centroids hold, list by list, rows in one order: the 64-bit key
-// row_key << 32 | id (kernels_build.h, "In-place mutation").  Their merge is a per-list two-way merge by that key and one
-// gather of whole rows; nothing is rotated, assigned or quantised again.
+// kernels_relayout.h -- everything a relayout launches (host_relayout.h): rq_add, rq_remove, rq_compact,
+// rq_merge_from and rq_extract, and, at the end, lazy removal (rq_remove_lazy, host_mutate.h), wave64.
+// A relayout builds the arrays a fresh build of the live rows would produce.  Every list keeps the build's order, the 64-bit key
+// ord32_biased(dist to the list's centroid) << 32 | id, so two sides over the same rotation and centroids (two indexes, or an
+// index and a batch that has been through pass 1) merge list by list with a two-way merge by that key and one gather of whole
+// rows; nothing stored is rotated, assigned or quantised again.
 #pragma once
+
+// ---- the order key ---------------------------------------------------------------------------------------------------------------
+// The key word of stored rows p0 .. p0+m (rotated in xrot, m x dim): the distance to the row's own list's centroid in the
+// lane order of assign_refine_kernel, with its clamp (a minimum that is not below f32::MAX is f32::MAX: NaN / inf rows, list 0).
+__global__ __launch_bounds__(256) void row_key_kernel(const float *__restrict__ xrot, uint64_t p0, uint64_t m, uint32_t dim,
+                                                      const float *__restrict__ centroids, const uint32_t *__restrict__ offsets,
+                                                      uint32_t k, uint32_t *__restrict__ row_key) {
+    const uint32_t hf = threadIdx.x & 1;
+    const uint64_t v = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 1;
+    if (v >= m) return;
+    const uint64_t p = p0 + v;
+    uint32_t lo = 0, hi = k;  // largest c with offsets[c] <= p (empty lists share their start with the next one)
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (offsets[mid] <= p) lo = mid;
+        else hi = mid;
+    }
+    const float dd = pair_l2sq_exact(xrot + v * dim + 4 * hf, centroids + (uint64_t)lo * dim + 4 * hf, dim);
+    if (hf == 0) row_key[p] = ord32_biased(dd < 3.402823466e+38f ? dd : 3.402823466e+38f);
+}
+
+// out[0] = 1 + the largest id in map_ids (0 if n == 0), out[1] = ids of map_ids found among the m ascending ids `sorted`
+// (nullable); out preset to 0
+__global__ __launch_bounds__(256) void id_scan_kernel(const uint32_t *__restrict__ map_ids, uint64_t n, const uint32_t *__restrict__ sorted,
+                                                      uint32_t m, unsigned long long *__restrict__ out) {
+    unsigned long long top = 0, hits = 0;
+    for (uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (uint64_t)gridDim.x * 256) {
+        const uint32_t id = map_ids[p];
+        top = (unsigned long long)id + 1 > top ? (unsigned long long)id + 1 : top;
+        if (sorted && m) {
+            uint32_t lo = 0, hi = m;  // first batch id not below `id`
+            while (lo < hi) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if (sorted[mid] < id) lo = mid + 1;
+                else hi = mid;
+            }
+            hits += lo < m && sorted[lo] == id ? 1u : 0u;
+        }
+    }
+    for (int o = 32; o >= 1; o >>= 1) {
+        const unsigned long long t = __shfl_xor(top, o, 64), h = __shfl_xor(hits, o, 64);
+        top = t > top ? t : top;
+        hits += h;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (top) atomicMax(out, top);
+        if (hits) atomicAdd(out + 1, hits);
+    }
+}
+
+// Adjacent rows of a list out of the build's order (key not strictly above its predecessor's), one block per list, counted
+// into *bad.  An index made by rq_build / rq_add never has one; rq_from_arrays / rq_load_dir take whatever order they are given.
+__global__ __launch_bounds__(256) void list_order_kernel(const uint32_t *__restrict__ offsets, const uint32_t *__restrict__ row_key,
+                                                         const uint32_t *__restrict__ map_ids, unsigned int *__restrict__ bad) {
+    const uint32_t b = offsets[blockIdx.x], e = offsets[blockIdx.x + 1];
+    uint32_t cnt = 0;
+    for (uint32_t p = b + 1 + threadIdx.x; p < e; p += 256) {
+        const unsigned long long k0 = ((unsigned long long)row_key[p - 1] << 32) | map_ids[p - 1];
+        const unsigned long long k1 = ((unsigned long long)row_key[p] << 32) | map_ids[p];
+        cnt += k0 < k1 ? 0u : 1u;
+    }
+    if (cnt) atomicAdd(bad, cnt);
+}
+
+// The batch of an rq_add as a side of the merge, in the shape of an index's arrays: sorted row j of the batch (keys: grouped by
+// list, each list ascending by ord32_biased(dist) << 32 | rank of the row's id within the batch) gets its key word, its id
+// (ids[rank], ascending; nullptr: id0 + rank), the codes and factors pass 1 left by input row (src[rank]; nullptr: rank) and its
+// raw vector, m x d input rows zero-padded to dim as the build pads them.  One wave per row.
+__global__ __launch_bounds__(256) void batch_side_kernel(const unsigned long long *__restrict__ keys, uint64_t m, uint32_t dim, uint32_t W,
+                                                         const uint32_t *__restrict__ ids, uint32_t id0, const uint32_t *__restrict__ src,
+                                                         const float *__restrict__ rows, uint32_t d, const uint64_t *__restrict__ codes_in,
+                                                         const float4 *__restrict__ factors_in, float *__restrict__ base_o,
+                                                         uint64_t *__restrict__ codes_o, float4 *__restrict__ factors_o,
+                                                         uint32_t *__restrict__ map_ids_o, uint32_t *__restrict__ row_key_o) {
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint64_t j = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); j < m; j += (uint64_t)gridDim.x * 4) {
+        const unsigned long long k64 = keys[j];
+        const uint32_t r = (uint32_t)k64, i = src ? src[r] : r;
+        const float *in = rows + (uint64_t)i * d;
+        float *out = base_o + j * dim;
+        for (uint32_t e = lane; e < dim; e += 64) out[e] = e < d ? in[e] : 0.0f;
+        for (uint32_t w = lane; w < W; w += 64) codes_o[j * W + w] = codes_in[(uint64_t)i * W + w];
+        if (lane == 0) factors_o[j] = factors_in[i], map_ids_o[j] = ids ? ids[r] : id0 + r, row_key_o[j] = (uint32_t)(k64 >> 32);
+    }
+}
 
 // ---- checks that run before anything is built ----------------------------------------------------------------------------------
 // First element at which two arrays differ as bit patterns (NaNs compare too), *first preset to ~0.
@@ -62,8 +148,9 @@ __device__ __forceinline__ uint32_t merge_keys_below(const uint32_t *__restrict_
 // n_a + position of index B.  A kept row of A lands at (its rank among the list's kept rows of A) + (keys of B below its key);
 // a row of B at (its rank in B's list) + (keys of A below its key): keys never tie (ids are unique across both, which the host
 // has checked), so the places are a permutation of the merged list.  B's ids count with `shift_b` added.
-// keep_a (nullable, position bitmap): the rows of A that stay -- rq_extract, which has no B (off_b == nullptr: every list of B is
-// empty); a merge keeps every row of A.  With keep_a the ranks of B would have to count kept rows only: never both.
+// keep_a (nullable, position bitmap, read at positions inside a list only): the rows of A that stay -- rq_remove, rq_compact and
+// rq_extract, which have no B (off_b == nullptr: every list of B is empty); rq_add and rq_merge_from keep every row of A.  With
+// keep_a the ranks of B would have to count kept rows only: never both.
 __global__ __launch_bounds__(256) void merge_lists_kernel(const uint32_t *__restrict__ off_a, const uint32_t *__restrict__ key_a,
                                                           const uint32_t *__restrict__ ids_a, const uint32_t *__restrict__ keep_a,
                                                           const uint32_t *__restrict__ off_b, const uint32_t *__restrict__ key_b,
@@ -238,13 +325,13 @@ __global__ __launch_bounds__(256) void tombstone_positions_kernel(const uint32_t
     if (threadIdx.x == 0 && s_marked) atomicAdd(marked, (unsigned long long)s_marked);
 }
 
-// bits &= live over the nwords words of two position bitmaps of one layout: a caller's filter made on an index with pending
-// removals admits allowed AND live rows; rq_extract keeps requested AND live rows.
-__global__ __launch_bounds__(256) void bitmap_and_kernel(uint32_t *__restrict__ bits, const uint32_t *__restrict__ live, uint64_t nwords) {
-    for (uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x; w < nwords; w += (uint64_t)gridDim.x * 256) bits[w] &= live[w];
-}
-// bits |= ~live: the drop bits of a relayout on an index with pending removals (rq_compact: bits preset to 0; rq_remove: the
-// requested rows).  Bits past the last position come out set; every reader of drop bits looks at positions inside a list only.
-__global__ __launch_bounds__(256) void bitmap_or_not_kernel(uint32_t *__restrict__ bits, const uint32_t *__restrict__ live, uint64_t nwords) {
-    for (uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x; w < nwords; w += (uint64_t)gridDim.x * 256) bits[w] |= ~live[w];
+// bits = (bits ^ flip) & live over the nwords words of two position bitmaps of one layout (live nullable: no removal is pending,
+// every position counts as live).  flip == 0: a caller's filter made on an index with pending removals admits allowed AND live
+// rows, rq_extract keeps requested AND live rows.  flip == ~0: the keep bits of rq_remove, NOT requested AND live; without a
+// live bitmap the bits past the last position come out set, and every reader of keep bits looks at positions inside a list only
+// (filter_lists_kernel masks each list's first and last word, merge_lists_kernel reads bit p for off[c] <= p < off[c + 1]).
+__global__ __launch_bounds__(256) void bitmap_and_live_kernel(uint32_t *__restrict__ bits, uint32_t flip, const uint32_t *__restrict__ live,
+                                                              uint64_t nwords) {
+    for (uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x; w < nwords; w += (uint64_t)gridDim.x * 256)
+        bits[w] = (bits[w] ^ flip) & (live ? live[w] : ~0u);
 }

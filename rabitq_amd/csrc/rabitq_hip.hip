@@ -33,7 +33,7 @@
 #include "kernels_range.h"
 #include "kernels_small.h"
 #include "kernels_train.h"
-#include "kernels_merge.h"
+#include "kernels_relayout.h"
 
 #include "kernel_shapes.h"
 #include "host_state.h"
@@ -45,8 +45,8 @@
 #include "host_call.h"
 #include "host_range.h"
 #include "host_build.h"
+#include "host_relayout.h"
 #include "host_mutate.h"
-#include "host_merge.h"
 #include "host_exact.h"
 #include "host_exact_range.h"
 #include "host_train.h"
@@ -1023,32 +1023,18 @@ rq_status rq_filter_create(const rq_index *idx, const uint32_t *allow_bits, uint
     if (!out) return fail(RQ_ERR_INVALID, "null argument");
     *out = nullptr;
     if (!idx) return fail(RQ_ERR_INVALID, "null index");
-    if (nbits > (1ull << 32)) return fail(RQ_ERR_INVALID, "nbits > 2^32 (ids are u32)");
-    if (!allow_bits && nbits > 0) return fail(RQ_ERR_INVALID, "null bitmap with nbits > 0");
+    RQC(id_bits_check(allow_bits, nbits));
     RQC(ensure_device());
     std::unique_ptr<rq_filter> f(new rq_filter());
-    const uint64_t n = idx->n, nwords = pos_bitmap_words(n);
-    const uint64_t in_words = (nbits + 31) / 32;
-    DevBuf<uint32_t> staged;  // the caller's bitmap in device memory (host bitmaps are copied)
-    const uint32_t *d_allow = allow_bits;
-    if (!bits_on_device || nbits == 0) {
-        RQC(staged.alloc(std::max<uint64_t>(in_words, 1)));
-        HIPC(hipMemset(staged.p, 0, std::max<uint64_t>(in_words, 1) * 4));
-        if (in_words) HIPC(hipMemcpy(staged.p, allow_bits, in_words * 4, hipMemcpyHostToDevice));
-        d_allow = staged.p;
-    }
-    RQC(f->pos_bits.alloc(nwords));
     hipStream_t st = nullptr;
     HIPC(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     struct StreamGuard {
         hipStream_t s;
         ~StreamGuard() { (void)hipStreamDestroy(s); }
     } sg{st};
-    HIPC(hipMemsetAsync(f->pos_bits.p, 0, nwords * 4, st));
-    if (n) filter_positions_kernel<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(idx->map_ids.p, n, d_allow, nbits, f->pos_bits.p, nwords);
-    // an index with pending removals (rq_remove_lazy): admitted = allowed AND live
-    if (idx->live) bitmap_and_kernel<<<bitmap_grid(nwords), 256, 0, st>>>(f->pos_bits.p, idx->live->pos_bits.p, nwords);
-    RQC(filter_finish(idx, f.get(), st));
+    // (on an index with pending removals, rq_remove_lazy: admitted = allowed AND live)
+    RQC(position_bits(idx, allow_bits, nbits, bits_on_device, false, 0u, st, f->pos_bits, f->h_sub_off));
+    RQC(filter_finish(idx, f.get()));
     *out = f.release();
     return RQ_OK;
 }
@@ -1098,7 +1084,7 @@ rq_status rq_remove(rq_index *idx, const uint32_t *id_bits, uint64_t nbits, int 
     const auto t0 = std::chrono::steady_clock::now();
     return mutate_done(idx, index_remove(idx, id_bits, nbits, bits_on_device, out_removed), t0);
 }
-// merge / extract (host_merge.h): the same invariant with no pass 1 -- rows, codes and factors move as they stand
+// merge / extract (host_mutate.h): the same invariant with no pass 1 -- rows, codes and factors move as they stand
 rq_status rq_merge_from(rq_index *dst, rq_index *src, uint32_t id_mode, uint32_t id_shift, uint32_t *out_shift) {
     const auto t0 = std::chrono::steady_clock::now();
     return mutate_done(dst, index_merge_from(dst, src, id_mode, id_shift, out_shift), t0);

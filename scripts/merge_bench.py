@@ -1,7 +1,7 @@
 """rq_merge_from at the headline shape (BASELINE configs[2]: 100M x 128, 4096 lists, the synthetic mixture of tests/synth.py), as
 99M + 1M and as 50M + 50M.  Prints ONE JSON line (and writes it to --out).  Per split:
   add     (only where the second part has at most --add-limit rows) rq_add of the second part's raw rows to a build of the first:
-          the route there was before rq_merge_from.  Wall ms, rq_last_mutate_stats' phases, mutate_gather_kernel's GB/s
+          pass 1 of them, then the same merge and gather.  Wall ms, rq_last_mutate_stats' phases, the gather's GB/s
   rebuild_engine_ms  rq_build of all rows through the streamed builder, the calls timed as bench.py times its build (after a
           warm-up build); the index it leaves is the one the merged index is compared with
   merge   rq_merge_from(first, second, APPEND): wall ms, the phases, merge_gather_kernel's GB/s on the bytes it must move, the

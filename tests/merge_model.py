@@ -1,4 +1,4 @@
-"""A numpy model of the per-list merge behind rq_merge_from / rq_extract (kernels_merge.h: merge_lists_kernel), written the way the
+"""A numpy model of the per-list merge behind rq_merge_from / rq_extract (kernels_relayout.h: merge_lists_kernel), written the way the
 kernel places rows -- by ranks and counts, never by sorting -- so that tests/test_merge_model.py can hold it against a plain sort.
 
 An index is (offsets[k + 1], key words[n], ids[n]); inside a list the rows ascend by the 64-bit key (key word << 32 | id).  Not a

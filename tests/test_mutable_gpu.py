@@ -155,6 +155,62 @@ def test_keys_and_ties(rq, oracle):
     live.add([4, 3, 1 << 20], rows)
     queries = (centres[rng.integers(0, k, 64)] + 0.5 * rng.standard_normal((64, d))).astype(np.float32)
     check(rq, g, live, centres, P, queries, (2, k), "explicit ids")
+    # ties across the two sides of the merge, explicit ids on both sides of the stored twin's: the copy of stored row 5 under id 4
+    # sits right before its twin, the copy of stored row 7 under a larger id right after it
+    g.add(x0[[7]], ids=np.array([(1 << 20) + 1]))
+    live.add([(1 << 20) + 1], x0[[7]])
+    where = {int(i): p for p, i in enumerate(g.map_ids)}
+    assert where[4] + 1 == where[5] and where[3] + 1 == where[6] and where[7] + 1 == where[(1 << 20) + 1]
+    check(rq, g, live, centres, P, queries, (k,), "explicit ids, twin above")
+    g.close()
+
+
+def same_as_rebuild(rq, g, live, centres, P, queries, what):
+    """offsets, map_ids, codes, factors, base and one query batch of g against the build of its live rows, bit for bit."""
+    c, ids = canonical(rq, live, centres, P)
+    try:
+        assert_same_arrays(g, c, ids, what)
+        (a, ma), (b, mb) = run(rq, g, queries, g.k, 10, False), run(rq, c, queries, g.k, 10, False)
+        assert np.array_equal(a[2], b[2]), (what, "counts")
+        for qi in range(len(queries)):
+            n = int(a[2][qi])
+            assert np.array_equal(a[1][qi, :n], ids[b[1][qi, :n]]) and np.array_equal(bits(a[0][qi, :n]), bits(b[0][qi, :n])), (what, qi)
+        assert ma == mb, (what, ma, mb)
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("d", [64, 128, 192, 300, 4096])
+def test_add_remove_compact_through_every_gather_shape(rq, d):
+    """rq_add, rq_remove and rq_remove_lazy + rq_compact through the gather's sub-groups of 16, 32 and 64 lanes (48 of them used at
+    dim 192), rows longer than one wave's step (dim 320, from d = 300: padded rows), and the largest dim; no output row count is
+    a multiple of 16, the most rows a wave moves per step.  The stored ids are the even numbers, the added ids odd ones given in
+    shuffled order, so the two sides interleave in every list."""
+    dim, k = (d + 63) // 64 * 64, 8
+    n0, m = (301, 101) if dim == 4096 else (1501, 401)
+    x, centres, _ = synth.mixture(n0 + m, d, k, sigma=0.8, seed=d + 7, centre_scale=0.6)
+    P = synth.random_orthogonal(dim, seed=d + 1) if dim <= 320 else np.eye(dim, dtype=np.float32)[::-1].copy()
+    queries, _, _ = synth.mixture(48, d, k, sigma=0.8, seed=d + 9, centre_scale=0.6)
+    rng = np.random.default_rng(d)
+    b = rq.RaBitQ.build(x[:n0], centres, P)
+    stored = (2 * np.arange(n0)).astype(np.uint32)                      # (a monotone renaming: every list keeps the build's order)
+    g = rq.RaBitQ.from_arrays(b.base, b.orthogonal, b.centroids, b.offsets, stored[b.map_ids], b.codes, b.factors)
+    b.close()
+    live = Live(stored, x[:n0])
+    new_ids = (2 * rng.choice(n0 + 50, m, replace=False) + 1).astype(np.uint32)    # odd ids in no order, a few past every stored id
+    assert np.array_equal(g.add(x[n0:], ids=new_ids), new_ids)
+    live.add(new_ids, x[n0:])
+    same_as_rebuild(rq, g, live, centres, P, queries, (d, "add"))
+    gone = np.array(sorted(live.rows), dtype=np.uint32)[::3]                       # a scattered third, of both sides
+    assert g.remove(ids=gone) == gone.size
+    live.remove(gone)
+    same_as_rebuild(rq, g, live, centres, P, queries, (d, "remove"))
+    dead = np.array(sorted(live.rows), dtype=np.uint32)[[0, 7, 100, 101, -1]]
+    assert g.remove(ids=dead, lazy=True) == dead.size and g.compact() == dead.size
+    live.remove(dead)
+    same_as_rebuild(rq, g, live, centres, P, queries, (d, "compact"))
+    assert g.n == n0 + m - gone.size - dead.size
+    assert all(rows % 16 for rows in (n0 + m, n0 + m - gone.size, g.n))
     g.close()
 
 
@@ -464,21 +520,56 @@ def test_remapped_ids_and_out_of_order_lists(rq):
     sub = rq.RaBitQ.from_arrays(arrs[0][keep], arrs[1], arrs[2], new_off, arrs[4][keep], arrs[5][keep], arrs[6][keep])
     assert_same_arrays(g, sub, np.arange(1 << 20, dtype=np.uint32), "out-of-order remove")
     sub.close()
+    # ... and so do rq_remove_lazy + rq_compact (the keep branch of the merge reads no keys); rq_add is refused as before
+    dead = perm[1::8]
+    assert g.remove(ids=dead, lazy=True) == dead.size and g.compact() == dead.size
+    keep &= ~np.isin(arrs[4], dead)
+    new_off[1:] = np.cumsum(np.bincount(lists[keep], minlength=k))
+    sub = rq.RaBitQ.from_arrays(arrs[0][keep], arrs[1], arrs[2], new_off, arrs[4][keep], arrs[5][keep], arrs[6][keep])
+    assert_same_arrays(g, sub, np.arange(1 << 20, dtype=np.uint32), "out-of-order compact")
+    a, c2 = g.query_batch(queries, k, 10), sub.query_batch(queries, k, 10)
+    for u, v in zip(a, c2):
+        assert np.array_equal(bits(u), bits(v)), "out-of-order compact: queries"
+    sub.close()
+    with pytest.raises(_lib.RabitqError) as e:
+        g.add(x[3000:3005])
+    assert e.value.status == -6 and "not in the build's order" in str(e.value)
     g.close()
     b.close()
 
 
 def test_add_to_an_emptied_index(rq):
-    """Remove every row, then add: the first default id is 0 again, and the index is canonical(S) of the new rows."""
+    """Remove every row (no row left to gather), then add (side A of the merge has no rows: every row comes from the batch): the
+    first default id is 0 again, and the index is canonical(S) of the new rows.  Then empty one list and add a batch that gives that
+    list all of its rows and another list none."""
     d, k = 64, 12
     x, centres, _ = synth.mixture(2000, d, k, sigma=0.8, seed=71, centre_scale=0.6)
     P = synth.random_orthogonal(d, seed=72)
     queries, _, _ = synth.mixture(50, d, k, sigma=0.8, seed=73, centre_scale=0.6)
     g = rq.RaBitQ.build(x[:1000], centres, P)
+    label0 = np.empty(1000, dtype=np.int64)                  # the list of each of the first 1000 rows
+    label0[g.map_ids] = np.repeat(np.arange(k), np.diff(g.offsets.astype(np.int64)))
     assert g.remove(ids=np.arange(1000)) == 1000 and g.n == 0
+    assert not g.offsets.any() and g.map_ids.size == 0 and g.codes.size == 0 and g.base.size == 0
     got = g.add(x[1000:])
     assert np.array_equal(got, np.arange(1000, dtype=np.uint32))
-    check(rq, g, Live(got, x[1000:]), centres, P, queries, (3, k), "emptied then added")
+    live = Live(got, x[1000:])
+    check(rq, g, live, centres, P, queries, (3, k), "emptied then added")
+    offs = g.offsets.astype(np.int64)
+    filled, skipped = 5, 9
+    gone = g.map_ids[offs[filled]:offs[filled + 1]].copy()
+    assert gone.size and g.remove(ids=gone) == gone.size
+    live.remove(gone)
+    offs = g.offsets.astype(np.int64)
+    assert offs[filled + 1] == offs[filled]
+    batch = x[:1000][label0 != skipped]                      # rows for every list but one, the emptied list among them
+    in_filled = int((label0 == filled).sum())
+    assert in_filled and (label0 == skipped).any()
+    got = g.add(batch)
+    live.add(got, batch)
+    after = g.offsets.astype(np.int64)
+    assert after[filled + 1] - after[filled] == in_filled and after[skipped + 1] - after[skipped] == offs[skipped + 1] - offs[skipped] > 0
+    check(rq, g, live, centres, P, queries, (3, k), "one list filled by the batch alone, one list without a new row")
     g.close()
 
 
