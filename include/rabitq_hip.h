@@ -94,7 +94,9 @@ typedef struct {
  * rq_train_centroids_device;
  * 0.12.0: merge and extract, additions only -- RQ_MERGE_IDS_*, rq_merge_from, rq_extract; rq_last_mutate_stats reports them too;
  * 0.13.0: lazy removal, additions only -- rq_remove_lazy, rq_compact, rq_pending_removals; an index with pending removals
- * refuses the entries that have no filtered form, and a filter made before a marking rq_remove_lazy is refused).
+ * refuses the entries that have no filtered form, and a filter made before a marking rq_remove_lazy is refused;
+ * 0.14.0: rows by id, additions only -- rq_locate*, rq_fetch_rows*, rq_fetch_stored*, rq_pair_distances*, rq_neighbours_of*,
+ * rq_neighbours_of_exact*, rq_by_id_stats_t, rq_last_by_id_stats; they read the index and change nothing of it).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -723,6 +725,80 @@ rq_status rq_last_mutate_stats(rq_mutate_stats_t *out);
 rq_status rq_remove_lazy(rq_index *idx, const uint32_t *id_bits, uint64_t nbits, int bits_on_device, uint64_t *out_marked);
 rq_status rq_compact(rq_index *idx, uint64_t *out_removed);
 rq_status rq_pending_removals(const rq_index *idx, uint64_t *out_dead);
+
+/* ---- rows by id: locate, fetch, exact distances to known ids, the neighbours of a stored row ------------------------------- */
+/* Every entry here takes u32 ids, the ids the queries return and the mutations name, and reads the index: no array, hint, option
+ * or counter of the index changes, so they are allowed on every index -- every metric and row type, tiered and split-row indexes,
+ * shards of rq_shard_index (their ids are global: an id of another shard is absent), with removals pending (a dead row's id is
+ * absent) and while rq_query_batch_device_begin tickets are open.  An id the index does not hold is ABSENT; absence is an answer,
+ * not an error.  Ids may repeat in a request.  No relayout (rq_add, rq_remove, rq_compact, rq_merge_from) may run during a call.
+ * Behind them sits the index's id directory, id -> position: made on the first by-id call after the index was made or last
+ * relaid out (one pass over the ids), kept until the next relayout, never touched by a query.  It is a u32 array over the ids
+ * below top = 1 + the largest stored id where top <= 4 n + 65536 (4 * top bytes), else a hash table of the power of two >= 2 n
+ * 64-bit slots (16 to 32 bytes per row); rq_last_by_id_stats says which.  An index that is never asked by id pays nothing.
+ * Each entry has a host-pointer form and a _device form (every pointer in device memory, 16-byte aligned row outputs; it returns
+ * with its outputs complete).  m == 0 succeeds and touches nothing.  Refused with RQ_ERR_INVALID before a device is looked for:
+ * a null index, a null ids or output pointer with m > 0 (nq > 0, c > 0).
+ * rq_locate: out_pos[i] = the cluster-order position of ids[i] (what rq_rerank takes and rq_get_array's rows are ordered by), or
+ *   RQ_POS_ABSENT.  A position is valid until the next relayout.
+ * rq_fetch_rows: out_rows (m x dim f32) row i = the row RQ_ARR_BASE holds at that position, bit for bit -- W(stored) of a
+ *   half-precision or byte row, the joined planes of a split row, either tier of a tiered index, the normalised row of a cosine
+ *   index, the augmented row of an inner-product index; out_found[i] = 1.  An absent id: a row of zeros, out_found[i] = 0.
+ *   out_found is nullable.
+ * rq_fetch_stored: the same rows as RQ_ARR_BASE_ROWS holds them, dim x elem_bytes bytes per row (an absent id: zero bytes); an
+ *   index of f32 rows answers RQ_ERR_INVALID, as rq_get_array(RQ_ARR_BASE_ROWS) does.
+ * rq_pair_distances: query i (nq x length, raw: it goes through the index's query transform and padding as in every query entry)
+ *   against its own c ids, ids[i * c .. i * c + c) -> out_dist[i * c + j], bit for bit what rq_rerank returns for that id's
+ *   position and the prepared query; an absent id gives +inf.  (An inner-product index: the L2 distance to the augmented row, as
+ *   every entry returns it; rq_ip_from_dist converts.)
+ * rq_neighbours_of: the neighbours of stored rows.  Let L = the inner-product index's d, else dim, and q_i = the first L floats
+ *   of rq_fetch_rows(ids[i]).  Row i of the outputs (m x topk) is row i of rq_query_batch[_filtered](q, probe, topk + 1,
+ *   heuristic_rank, filter) with one entry removed: the first whose id equals ids[i], or, if there is none (the row is outside the
+ *   probed lists or the filter, or the ranker dropped it), the last one.  The remaining entries keep the plain call's order; a row
+ *   with fewer than topk of them is padded with NaN / 0xFFFFFFFF, and so is the whole row of an absent id (out_found[i] = 0).
+ *   filter == NULL with removals pending: the live filter, as in the plain entry.  Status and refusals are the plain entry's at
+ *   topk + 1 (so topk <= 2047; RQ_ERR_EMPTY after a heuristic call that left a row empty, outputs written), rq_metrics counts the
+ *   plain call.  On the device: lookup, gather into the query buffer, the plain entry's driver, one kernel that drops the entry.
+ * rq_neighbours_of_exact: the same over rq_exact_search(q, topk + 1, filter, params) -- ascending by (distance, id), so the row
+ *   itself comes first unless a bitwise-equal row has a smaller id; refused where the exact search is (tiered and split-row
+ *   indexes: RQ_ERR_UNSUPPORTED).  params as in rq_exact_search (nullable).
+ * rq_last_by_id_stats: the calling thread's last by-id call. */
+#define RQ_POS_ABSENT 0xFFFFFFFFu
+enum { RQ_DIRECTORY_NONE = 0, RQ_DIRECTORY_DENSE = 1, RQ_DIRECTORY_HASH = 2 };
+typedef struct {
+    uint32_t struct_size;      /* set to sizeof(rq_by_id_stats_t) before the call */
+    uint32_t form;             /* RQ_DIRECTORY_* of the directory the call used */
+    uint64_t directory_bytes;  /* device memory it takes */
+    float ms_build;            /* wall ms its build took (whichever call made it), the scan for the largest id included */
+    uint32_t longest_chain;    /* hash form: slots the longest insertion looked at while building (1 = every id in its home slot) */
+    uint64_t found, absent;    /* ids of the call that have / do not have a live row */
+    uint64_t gather_bytes;     /* the row gather of the call: every found row read once + every destination row written once, + the positions */
+    float ms_gather;           /* device ms of that gather (0: the call gathers no rows) */
+    float ms_lookup;           /* device ms of the id lookup */
+    uint32_t built;            /* 1: this call made the directory */
+    uint32_t reserved0;
+} rq_by_id_stats_t;
+rq_status rq_locate(const rq_index *idx, const uint32_t *ids, uint64_t m, uint32_t *out_pos);
+rq_status rq_locate_device(const rq_index *idx, const uint32_t *d_ids, uint64_t m, uint32_t *d_out_pos);
+rq_status rq_fetch_rows(const rq_index *idx, const uint32_t *ids, uint64_t m, float *out_rows, uint32_t *out_found);
+rq_status rq_fetch_rows_device(const rq_index *idx, const uint32_t *d_ids, uint64_t m, float *d_out_rows, uint32_t *d_out_found);
+rq_status rq_fetch_stored(const rq_index *idx, const uint32_t *ids, uint64_t m, void *out_rows, uint32_t *out_found);
+rq_status rq_fetch_stored_device(const rq_index *idx, const uint32_t *d_ids, uint64_t m, void *d_out_rows, uint32_t *d_out_found);
+rq_status rq_pair_distances(const rq_index *idx, const float *queries, uint32_t nq, uint32_t length, const uint32_t *ids, uint32_t c,
+                            float *out_dist);
+rq_status rq_pair_distances_device(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t length, const uint32_t *d_ids,
+                                   uint32_t c, float *d_out_dist);
+rq_status rq_neighbours_of(const rq_index *idx, const uint32_t *ids, uint32_t m, uint32_t probe, uint32_t topk, int heuristic_rank,
+                           const rq_filter *filter, float *out_dist, uint32_t *out_ids, uint32_t *out_found);
+rq_status rq_neighbours_of_device(const rq_index *idx, const uint32_t *d_ids, uint32_t m, uint32_t probe, uint32_t topk,
+                                  int heuristic_rank, const rq_filter *filter, float *d_out_dist, uint32_t *d_out_ids,
+                                  uint32_t *d_out_found);
+rq_status rq_neighbours_of_exact(const rq_index *idx, const uint32_t *ids, uint32_t m, uint32_t topk, const rq_filter *filter,
+                                 const rq_exact_params_t *params, float *out_dist, uint32_t *out_ids, uint32_t *out_found);
+rq_status rq_neighbours_of_exact_device(const rq_index *idx, const uint32_t *d_ids, uint32_t m, uint32_t topk, const rq_filter *filter,
+                                        const rq_exact_params_t *params, float *d_out_dist, uint32_t *d_out_ids,
+                                        uint32_t *d_out_found);
+rq_status rq_last_by_id_stats(rq_by_id_stats_t *out);
 
 /* ---- merge two indexes, extract a sub-index ------------------------------------------------------------------------------ */
 /* Both work on stored rows as they stand: nothing is rotated, assigned, quantised -- or, on a cosine or inner-product index,

@@ -38,6 +38,9 @@ EXPORTS = [
     "rq_train_centroids", "rq_train_centroids_device",
     "rq_merge_from", "rq_extract",
     "rq_remove_lazy", "rq_compact", "rq_pending_removals",
+    "rq_locate", "rq_locate_device", "rq_fetch_rows", "rq_fetch_rows_device", "rq_fetch_stored", "rq_fetch_stored_device",
+    "rq_pair_distances", "rq_pair_distances_device", "rq_neighbours_of", "rq_neighbours_of_device", "rq_neighbours_of_exact",
+    "rq_neighbours_of_exact_device", "rq_last_by_id_stats",
 ]
 
 
@@ -169,6 +172,17 @@ class TrainParamsT(_Sized):
 
 class TrainStatsT(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("iters_run", C.c_uint32), ("sample_rows", C.c_uint32), ("splits", C.c_uint32)]
+
+
+POS_ABSENT = 0xFFFFFFFF   # RQ_POS_ABSENT
+DIRECTORY_FORMS = {0: "none", 1: "dense", 2: "hash"}   # RQ_DIRECTORY_*
+
+
+class ByIdStatsT(_Sized):
+    """rq_by_id_stats_t: the calling thread's last by-id call (locate / fetch / distances_to / neighbours_of)."""
+    _fields_ = [("struct_size", C.c_uint32), ("form", C.c_uint32), ("directory_bytes", C.c_uint64), ("ms_build", C.c_float),
+                ("longest_chain", C.c_uint32), ("found", C.c_uint64), ("absent", C.c_uint64), ("gather_bytes", C.c_uint64),
+                ("ms_gather", C.c_float), ("ms_lookup", C.c_float), ("built", C.c_uint32), ("reserved0", C.c_uint32)]
 
 
 def build(force: bool = False) -> str:
@@ -313,6 +327,19 @@ def lib():
         "rq_probe_counts_device": (i32, [vp, f32p, u32, u32, u32, C.POINTER(ProbeRuleT), u32p]),
         "rq_train_centroids": (i32, [vp, u64, u32, u32, C.POINTER(TrainParamsT), f32p, vp, C.POINTER(TrainStatsT)]),
         "rq_train_centroids_device": (i32, [vp, u64, u32, u32, C.POINTER(TrainParamsT), f32p, vp, C.POINTER(TrainStatsT)]),
+        "rq_locate": (i32, [vp, u32p, u64, u32p]),
+        "rq_locate_device": (i32, [vp, u32p, u64, u32p]),
+        "rq_fetch_rows": (i32, [vp, u32p, u64, f32p, u32p]),
+        "rq_fetch_rows_device": (i32, [vp, u32p, u64, f32p, u32p]),
+        "rq_fetch_stored": (i32, [vp, u32p, u64, vp, u32p]),
+        "rq_fetch_stored_device": (i32, [vp, u32p, u64, vp, u32p]),
+        "rq_pair_distances": (i32, [vp, f32p, u32, u32, u32p, u32, f32p]),
+        "rq_pair_distances_device": (i32, [vp, f32p, u32, u32, u32p, u32, f32p]),
+        "rq_neighbours_of": (i32, [vp, u32p, u32, u32, u32, C.c_int, vp, f32p, u32p, u32p]),
+        "rq_neighbours_of_device": (i32, [vp, u32p, u32, u32, u32, C.c_int, vp, f32p, u32p, u32p]),
+        "rq_neighbours_of_exact": (i32, [vp, u32p, u32, u32, vp, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
+        "rq_neighbours_of_exact_device": (i32, [vp, u32p, u32, u32, vp, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
+        "rq_last_by_id_stats": (i32, [C.POINTER(ByIdStatsT)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the .so lacks a declared symbol

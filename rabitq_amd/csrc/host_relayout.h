@@ -266,6 +266,10 @@ static rq_status commit_layout(rq_index *idx, std::unique_ptr<rq_index> &nx, Pha
     idx->row_key_valid = true;
     delete idx->live;  // the pending removals went with the old layout (every relayout of a pending index drops them)
     idx->live = nullptr;
+    {  // the id directory names positions of the old layout (made again by the next by-id call: host_directory.h)
+        std::lock_guard<std::mutex> g(idx->dir_mu);
+        idx->dir.reset();
+    }
     {  // workspaces and tile tables describe the old layout (no query runs during a mutation; the learnt hints stay)
         std::lock_guard<std::mutex> g(idx->tt_mu);
         idx->tile_tables.clear();

@@ -244,6 +244,10 @@ struct Workspace {
     DevBuf<uint32_t> sh_flag;                 // handshake / status words of the step
     DevBuf<uint32_t> sh_pc, sh_id_b, sh_n_b;  // shared-threshold step: probe lists (whole | nearest | rest), second call's results
     DevBuf<float> sh_pd, sh_thr, sh_dist_b;
+    // by-id calls (host_directory.h): positions of the asked ids, the gathered query rows of rq_neighbours_of and its plain call's results
+    DevBuf<uint32_t> id_pos, id_res_id, id_res_n;
+    DevBuf<float> id_rows, id_rows_raw, id_res_dist;
+    DevBuf<unsigned long long> id_found;
     unsigned long long *h_totals = nullptr;  // pinned, 16
     Prof prof;
     ~Workspace() {
@@ -259,6 +263,20 @@ struct MetricSpec {
     uint32_t id = RQ_METRIC_L2;
     uint32_t d = 0;
     float S = 0.0f;
+};
+
+// The id directory of an index (host_directory.h, kernels_directory.h): id -> position, read-only, made on the first
+// by-id call of a generation.  One of its two buffers is set.
+struct IdDirectory {
+    uint64_t generation = 0;  // idx->generation it was made for
+    uint64_t top = 0;         // 1 + the largest stored id (0: an empty index)
+    uint32_t bits = 0;        // hash form: log2 of the table's capacity
+    DevBuf<uint32_t> dense;   // dense form: top entries
+    DevBuf<unsigned long long> slots;  // hash form: 2^bits slots
+    bool hashed = false;
+    uint64_t bytes = 0;       // of the buffer
+    float ms_build = 0.0f;    // wall time of the build, the scan for `top` included
+    uint32_t longest_chain = 0;  // hash form: slots the worst insertion looked at
 };
 
 struct rq_index {
@@ -321,6 +339,10 @@ struct rq_index {
     // entry that has a filtered form runs under it when the caller brings no filter of their own (live_or).  Updated in place by
     // rq_remove_lazy (its hints stay), dropped by every relayout (commit_layout).
     struct rq_filter *live = nullptr;
+    // rows by id (host_directory.h): null until the first by-id call of this generation; dropped by every relayout (commit_layout).
+    // No query path reads it.
+    std::mutex dir_mu;
+    std::unique_ptr<IdDirectory> dir;
     uint64_t removal_epoch = 0;   // bumped by every rq_remove_lazy that marks a row; a filter made under an older epoch is refused
     inline uint64_t pending() const;  // stored rows that are dead
 };

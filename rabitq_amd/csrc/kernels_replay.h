@@ -438,8 +438,10 @@ __device__ __forceinline__ void stage_finish_body(SurvRec *__restrict__ surv, Ru
                                                            const float *__restrict__ qpad, uint32_t dim, uint32_t topk,
                                                            const ReplayState &st, const uint32_t *__restrict__ probe_cluster,
                                                            uint32_t nprobe, uint32_t presorted) {
-    __shared__ int32_t hkey[HEURISTIC ? 1 : RQ_MAX_TOPK];
-    __shared__ uint32_t hid[HEURISTIC ? 1 : RQ_MAX_TOPK];
+    // (+ 1: replay_wave pushes before it pops, so a full heap holds topk + 1 elements for a moment -- at topk == RQ_MAX_TOPK the
+    // element one past the arrays landed in whatever LDS follows them)
+    __shared__ int32_t hkey[HEURISTIC ? 1 : RQ_MAX_TOPK + 1];
+    __shared__ uint32_t hid[HEURISTIC ? 1 : RQ_MAX_TOPK + 1];
     extern __shared__ __attribute__((aligned(16))) float fin_q[];  // dim floats: the padded query
     const uint32_t b = blockIdx.x;
     const StageCounts sc = stage_begin<true>(surv_cnt, seg, b, st);

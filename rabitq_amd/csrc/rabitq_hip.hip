@@ -34,6 +34,7 @@
 #include "kernels_small.h"
 #include "kernels_train.h"
 #include "kernels_relayout.h"
+#include "kernels_directory.h"
 
 #include "kernel_shapes.h"
 #include "host_state.h"
@@ -50,6 +51,7 @@
 #include "host_exact.h"
 #include "host_exact_range.h"
 #include "host_train.h"
+#include "host_directory.h"
 
 // ------------------------------------------------------------------------------------------------
 // extern "C"
@@ -1112,6 +1114,56 @@ rq_status rq_pending_removals(const rq_index *idx, uint64_t *out_dead) {
 rq_status rq_last_mutate_stats(rq_mutate_stats_t *out) {
     if (!out) return fail(RQ_ERR_INVALID, "null argument");
     return copy_out_sized(out, g_mutate_stats);
+}
+
+// ---- rows by id (host_directory.h): they read the index and write nothing of it ----
+static rq_status by_id_done(rq_status s) {
+    if (s != RQ_OK) (void)hipGetLastError();  // (a failed hipMalloc's sticky error must not fail the next call)
+    return s;
+}
+rq_status rq_locate(const rq_index *idx, const uint32_t *ids, uint64_t m, uint32_t *out_pos) { return by_id_done(locate_host(idx, ids, m, out_pos)); }
+rq_status rq_locate_device(const rq_index *idx, const uint32_t *d_ids, uint64_t m, uint32_t *d_out_pos) { return by_id_done(locate_device(idx, d_ids, m, d_out_pos)); }
+rq_status rq_fetch_rows(const rq_index *idx, const uint32_t *ids, uint64_t m, float *out_rows, uint32_t *out_found) {
+    return by_id_done(fetch_host(idx, ids, m, false, out_rows, out_found));
+}
+rq_status rq_fetch_rows_device(const rq_index *idx, const uint32_t *d_ids, uint64_t m, float *d_out_rows, uint32_t *d_out_found) {
+    return by_id_done(fetch_device(idx, d_ids, m, false, d_out_rows, d_out_found));
+}
+rq_status rq_fetch_stored(const rq_index *idx, const uint32_t *ids, uint64_t m, void *out_rows, uint32_t *out_found) {
+    return by_id_done(fetch_host(idx, ids, m, true, out_rows, out_found));
+}
+rq_status rq_fetch_stored_device(const rq_index *idx, const uint32_t *d_ids, uint64_t m, void *d_out_rows, uint32_t *d_out_found) {
+    return by_id_done(fetch_device(idx, d_ids, m, true, d_out_rows, d_out_found));
+}
+rq_status rq_pair_distances(const rq_index *idx, const float *queries, uint32_t nq, uint32_t length, const uint32_t *ids, uint32_t c,
+                            float *out_dist) {
+    return by_id_done(pair_distances_host(idx, queries, nq, length, ids, c, out_dist));
+}
+rq_status rq_pair_distances_device(const rq_index *idx, const float *d_queries, uint32_t nq, uint32_t length, const uint32_t *d_ids,
+                                   uint32_t c, float *d_out_dist) {
+    return by_id_done(pair_distances_device(idx, d_queries, nq, length, d_ids, c, d_out_dist));
+}
+rq_status rq_neighbours_of(const rq_index *idx, const uint32_t *ids, uint32_t m, uint32_t probe, uint32_t topk, int heuristic_rank,
+                           const rq_filter *filter, float *out_dist, uint32_t *out_ids, uint32_t *out_found) {
+    return by_id_done(neighbours_host(idx, ids, m, false, probe, topk, heuristic_rank, filter, nullptr, out_dist, out_ids, out_found));
+}
+rq_status rq_neighbours_of_device(const rq_index *idx, const uint32_t *d_ids, uint32_t m, uint32_t probe, uint32_t topk,
+                                  int heuristic_rank, const rq_filter *filter, float *d_out_dist, uint32_t *d_out_ids,
+                                  uint32_t *d_out_found) {
+    return by_id_done(neighbours_device(idx, d_ids, m, false, probe, topk, heuristic_rank, filter, nullptr, d_out_dist, d_out_ids, d_out_found));
+}
+rq_status rq_neighbours_of_exact(const rq_index *idx, const uint32_t *ids, uint32_t m, uint32_t topk, const rq_filter *filter,
+                                 const rq_exact_params_t *params, float *out_dist, uint32_t *out_ids, uint32_t *out_found) {
+    return by_id_done(neighbours_host(idx, ids, m, true, 1, topk, 0, filter, params, out_dist, out_ids, out_found));
+}
+rq_status rq_neighbours_of_exact_device(const rq_index *idx, const uint32_t *d_ids, uint32_t m, uint32_t topk, const rq_filter *filter,
+                                        const rq_exact_params_t *params, float *d_out_dist, uint32_t *d_out_ids,
+                                        uint32_t *d_out_found) {
+    return by_id_done(neighbours_device(idx, d_ids, m, true, 1, topk, 0, filter, params, d_out_dist, d_out_ids, d_out_found));
+}
+rq_status rq_last_by_id_stats(rq_by_id_stats_t *out) {
+    if (!out) return fail(RQ_ERR_INVALID, "null argument");
+    return copy_out_sized(out, g_by_id_stats);
 }
 
 rq_status rq_query(const rq_index *idx, const float *query, uint32_t len, uint32_t probe, uint32_t topk,

@@ -661,6 +661,116 @@ class RaBitQ:
                                            C.byref(prm) if prm is not None else None, C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr),
                                            C.c_void_p(out_n_ptr)))
 
+    # ---- rows by id: locate, fetch, exact distances to known ids, neighbours of stored rows (rq_locate ...) ----
+    @staticmethod
+    def _id_list(ids):
+        """ids of a by-id call -> contiguous u32 array (any shape; the result keeps it)."""
+        a = np.asarray(ids)
+        if a.dtype.kind not in "iu":
+            raise TypeError(f"ids must be integers, not {a.dtype}")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise ValueError("ids are u32: 0 <= id < 2^32")
+        return np.ascontiguousarray(a, dtype=np.uint32)
+
+    def locate(self, ids) -> np.ndarray:
+        """Cluster-order positions of `ids` (u32, the shape of ids): what rq_rerank takes and base / map_ids are ordered by;
+        0xFFFFFFFF for an id the index does not hold or whose row is dead.  Valid until the next relayout."""
+        a = self._id_list(ids)
+        out = np.empty(a.shape, dtype=np.uint32)
+        check(lib().rq_locate(self._h, _addr(a), a.size, _addr(out)))
+        return out
+
+    def contains(self, ids) -> np.ndarray:
+        """Boolean, the shape of ids: the index holds a live row with that id."""
+        return self.locate(ids) != np.uint32(_lib.POS_ABSENT)
+
+    def fetch(self, ids, stored: bool = False, raw: bool = True):
+        """The rows of `ids` (1-D) -> (rows, found): rows[i] is the row `base` holds for ids[i], bit for bit (f32, m x dim); with
+        stored=True the row as `base_rows` holds it, in the index's row type (an f32 index raises, as base_rows' array id does).
+        raw=True cuts the rows of an inner-product index to its d (the augmented coordinate and the padding off); the rows of
+        other indexes keep dim.  An absent id gives a row of zeros and found[i] == False."""
+        a = self._id_list(ids).reshape(-1)
+        found = np.zeros(a.size, dtype=np.uint32)
+        if stored:
+            rows = np.zeros((a.size, self.dim), dtype=_lib.ROW_TYPE_BY_NAME[self.row_type].returns)
+            check(lib().rq_fetch_stored(self._h, _addr(a), a.size, _addr(rows), _addr(found)))
+        else:
+            rows = np.zeros((a.size, self.dim), dtype=np.float32)
+            check(lib().rq_fetch_rows(self._h, _addr(a), a.size, _addr(rows), _addr(found)))
+        if raw and self._ip_d:
+            rows = np.ascontiguousarray(rows[:, :self._ip_d])
+        return rows, found.astype(bool)
+
+    def fetch_device(self, ids_ptr: int, m: int, out_rows_ptr: int, out_found_ptr: int = 0, stored: bool = False) -> None:
+        """fetch with ids and outputs in device memory (raw addresses; rows m x dim f32, or m x dim elements with stored=True;
+        16-byte aligned; found m x u32, 0 = not wanted)."""
+        fn = lib().rq_fetch_stored_device if stored else lib().rq_fetch_rows_device
+        check(fn(self._h, C.c_void_p(ids_ptr), m, C.c_void_p(out_rows_ptr), C.c_void_p(out_found_ptr)))
+
+    def locate_device(self, ids_ptr: int, m: int, out_pos_ptr: int) -> None:
+        """locate with ids and positions in device memory (raw addresses)."""
+        check(lib().rq_locate_device(self._h, C.c_void_p(ids_ptr), m, C.c_void_p(out_pos_ptr)))
+
+    def distances_to(self, queries, ids) -> np.ndarray:
+        """Exact distances from query i (B x d, raw: transformed and padded as in query_batch) to its own ids[i] (B x c) -> B x c
+        f32, bit for bit the rerank's value for that row; +inf for an absent id.  (An "ip" index: inner_product() converts.)"""
+        q = _f32(queries)
+        a = self._id_list(ids)
+        if q.ndim != 2 or a.ndim != 2 or a.shape[0] != q.shape[0]:
+            raise _lib.RabitqError(-1, "queries must be B x d and ids B x c")
+        out = np.empty(a.shape, dtype=np.float32)
+        check(lib().rq_pair_distances(self._h, _addr(q), q.shape[0], q.shape[1], _addr(a), a.shape[1], _addr(out)))
+        return out
+
+    def neighbours_of(self, ids, probe: int, topk: int, filter: Filter = None, heuristic_rank: bool = False, exact: bool = False):
+        """The neighbours of stored rows -> (dist m x topk, ids m x topk, found m): row i is what query_batch (exact=True:
+        exact_search; probe is not used) returns at topk + 1 for the stored row of ids[i] (fetch(ids)[0][i]) without the row
+        itself -- the first entry with id ids[i] is removed, or the last entry if the row is not among them (outside the
+        probed lists or the filter).  Short rows are padded with NaN / 0xFFFFFFFF; an absent id gives such a row and
+        found[i] == False.  One call on the GPU: lookup, gather, the query, the removal."""
+        a = self._id_list(ids).reshape(-1)
+        m = a.size
+        d = np.full((m, max(topk, 1)), np.nan, dtype=np.float32)
+        out = np.full((m, max(topk, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        found = np.zeros(m, dtype=np.uint32)
+        if exact:
+            st = lib().rq_neighbours_of_exact(self._h, _addr(a), m, topk, _fh(filter), None, _addr(d), _addr(out), _addr(found))
+        else:
+            st = lib().rq_neighbours_of(self._h, _addr(a), m, probe, topk, int(heuristic_rank), _fh(filter), _addr(d), _addr(out),
+                                        _addr(found))
+        if st != _lib.RQ_ERR_EMPTY:
+            check(st)
+        return d, out, found.astype(bool)
+
+    def neighbours_of_device(self, ids_ptr: int, m: int, probe: int, topk: int, out_dist_ptr: int, out_id_ptr: int, out_found_ptr: int,
+                             filter: Filter = None, heuristic_rank: bool = False, exact: bool = False) -> None:
+        """neighbours_of with ids and outputs in device memory (raw addresses)."""
+        if exact:
+            st = lib().rq_neighbours_of_exact_device(self._h, C.c_void_p(ids_ptr), m, topk, _fh(filter), None, C.c_void_p(out_dist_ptr),
+                                                     C.c_void_p(out_id_ptr), C.c_void_p(out_found_ptr))
+        else:
+            st = lib().rq_neighbours_of_device(self._h, C.c_void_p(ids_ptr), m, probe, topk, int(heuristic_rank), _fh(filter),
+                                               C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr), C.c_void_p(out_found_ptr))
+        if st != _lib.RQ_ERR_EMPTY:
+            check(st)
+
+    def knn_graph(self, probe: int, topk: int, exact: bool = False, chunk: int = 65536):
+        """The k-NN graph of the index -> (ids, neigh_dist, neigh_ids): every live id in ascending order and, through
+        neighbours_of in chunks of `chunk` ids, its topk neighbours (n_live x topk; padded as neighbours_of pads)."""
+        ids = np.sort(self.map_ids)
+        ids = ids[self.contains(ids)] if self.pending_removals else ids
+        nd = np.full((ids.size, max(topk, 1)), np.nan, dtype=np.float32)
+        ni = np.full((ids.size, max(topk, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        for i0 in range(0, ids.size, max(int(chunk), 1)):
+            sl = slice(i0, i0 + max(int(chunk), 1))
+            nd[sl], ni[sl], _ = self.neighbours_of(ids[sl], probe, topk, exact=exact)
+        return ids, nd, ni
+
+    @staticmethod
+    def last_by_id_stats() -> dict:
+        """The calling thread's last by-id call (include/rabitq_hip.h: rq_by_id_stats_t); form as "dense" / "hash"."""
+        return last_by_id_stats()
+
     @staticmethod
     def _recall_of(ids, cnt, exact_ids, exact_cnt) -> float:
         """mean over the queries with a non-empty exact answer of |query ids n exact ids| / exact count"""
@@ -1081,6 +1191,15 @@ def last_exact_stats() -> dict:
     st = _lib.ExactStatsT()
     check(lib().rq_last_exact_stats(C.byref(st)))
     return {name: getattr(st, name) for name, _ in _lib.ExactStatsT._fields_ if name not in ("struct_size", "reserved0")}
+
+
+def last_by_id_stats() -> dict:
+    """The calling thread's last by-id call (include/rabitq_hip.h: rq_last_by_id_stats)."""
+    st = _lib.ByIdStatsT()
+    check(lib().rq_last_by_id_stats(C.byref(st)))
+    out = {name: getattr(st, name) for name, _ in _lib.ByIdStatsT._fields_ if name not in ("struct_size", "reserved0")}
+    out["form"] = _lib.DIRECTORY_FORMS.get(out["form"], out["form"])
+    return out
 
 
 def calculate_recall(truth, res, topk: int) -> float:
