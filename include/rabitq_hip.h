@@ -96,7 +96,11 @@ typedef struct {
  * 0.13.0: lazy removal, additions only -- rq_remove_lazy, rq_compact, rq_pending_removals; an index with pending removals
  * refuses the entries that have no filtered form, and a filter made before a marking rq_remove_lazy is refused;
  * 0.14.0: rows by id, additions only -- rq_locate*, rq_fetch_rows*, rq_fetch_stored*, rq_pair_distances*, rq_neighbours_of*,
- * rq_neighbours_of_exact*, rq_by_id_stats_t, rq_last_by_id_stats; they read the index and change nothing of it).
+ * rq_neighbours_of_exact*, rq_by_id_stats_t, rq_last_by_id_stats; they read the index and change nothing of it;
+ * 0.15.0: attribute columns, additions only -- RQ_ATTR_*, rq_attr_value_t, rq_attr_info_t, rq_attr_create / _drop / _count / _info /
+ * _index / _set* / _get* / _get_array, RQ_WHERE_*, rq_where_term_t, rq_filter_create_where, rq_where_stats_t, rq_last_where_stats,
+ * RQ_FILTER_*, rq_filter_combine, rq_filter_id_bits, rq_filter_ids_device; an index without columns behaves, allocates and dumps
+ * exactly as before; rq_last_mutate_stats.gather_bytes counts the column bytes a relayout moves).
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -799,6 +803,131 @@ rq_status rq_neighbours_of_exact_device(const rq_index *idx, const uint32_t *d_i
                                         const rq_exact_params_t *params, float *d_out_dist, uint32_t *d_out_ids,
                                         uint32_t *d_out_found);
 rq_status rq_last_by_id_stats(rq_by_id_stats_t *out);
+
+/* ---- attribute columns: per-row values, and predicates over them as filters (0.15.0, additions only) ------------------------- */
+/* An index may carry up to RQ_ATTR_MAX_COLUMNS named columns of per-row values.  A name is 1-31 bytes of [A-Za-z0-9_], unique per
+ * index.  Types: RQ_ATTR_U32, _I32, _F32 (4 bytes), RQ_ATTR_U64, _I64 (8 bytes); rq_attr_value_t is the 8-byte union of the five (a
+ * 4-byte value lies in its low 4 bytes; the library ignores the others).  A column is one device array of n x elem bytes in
+ * POSITION order: element p belongs to the row at cluster-order position p, beside map_ids[p].  Every column has a fill value;
+ * a row holds it until it is set.  The reference has no counterpart.  An index without columns behaves, allocates and dumps
+ * exactly as before.
+ * rq_attr_create: a new column, every row holding `fill`.  rq_attr_drop: the column goes, the indexes (rq_attr_info order) of the
+ *   later columns move down by one.  rq_attr_count / rq_attr_info (a sized struct; bytes = n x elem) / rq_attr_index (name -> index).
+ * rq_attr_set[_device]: values[i] (m elements of the column's type) becomes the value of the row with id ids[i]: ids -> positions
+ *   through the id directory, as rq_locate, then a scatter.  An id the index does not hold, or a dead one (rq_remove_lazy), is
+ *   absent: counted in *out_absent (nullable), not an error.  When an id repeats in the request the LAST occurrence wins, and not
+ *   by store order: a first pass gives every asked position to the highest request index that names it (an integer atomic max on a
+ *   per-position owner word), a second pass stores only the values whose request index owns their position.  m < 2^32 - 1.
+ *   The call changes values, not positions: no generation is bumped, and existing filters stay valid -- a filter is the set its
+ *   predicate selected when it was made.
+ * rq_attr_get[_device]: out_values[i] = the value of ids[i], out_found[i] (nullable) = 1; an absent id gives the fill value and 0.
+ * rq_attr_get_array: the whole column in position order (dst_bytes = n x elem): the counterpart of rq_get_array(RQ_ARR_MAP_IDS).
+ * Host forms take host pointers; _device forms take device pointers and return with their outputs complete.  m == 0 succeeds.
+ * Columns do not depend on how the raw vectors are stored: these entries are accepted on every metric and row type, tiered and
+ * split-row indexes, shards of rq_shard_index, indexes with pending removals and with open tickets.  No query may run during
+ * rq_attr_set, rq_attr_create or rq_attr_drop.
+ * Refused with RQ_ERR_INVALID before a device is looked for: a null index, name, or (m > 0) ids / values / out_values; a malformed
+ * name; an unknown type.  RQ_ERR_INVALID: a name the index already has (create) or does not have; RQ_ERR_UNSUPPORTED: a 17th column.
+ *
+ * Columns follow their rows.  Every relayout (rq_add, rq_remove, rq_compact, rq_merge_from; rq_extract and so a copy) moves each
+ * column with one gather driven by the relayout's own destination-to-source map: a row keeps its value.  The rows of an rq_add
+ * hold the fill value.  rq_merge_from: rows of src bring src's value where src has a column of the same name and type, else they
+ * hold dst's fill; the same name with another type is refused with RQ_ERR_INVALID, both indexes untouched; columns that only src
+ * has are NOT taken (create them on dst first).  rq_extract gives the new index every column of src; rq_shard_index gives a shard
+ * every column (each owned list's slice).  rq_last_mutate_stats.gather_bytes counts each column element read once and written once.
+ * Persistence: an index with columns writes into rq_dump_dir one more text file `attrs`, one line "<name> <type id> <fill as 16
+ * hex digits>\n" per column in rq_attr_info order, and per column one raw little-endian file `attr.<name>` of n x elem bytes in
+ * position order; rq_load_dir restores the columns when `attrs` is there (a missing or wrongly sized data file, or a malformed
+ * line: RQ_ERR_IO).  An index without columns writes exactly the files it wrote before.  rq_dump_json of an index with columns is
+ * RQ_ERR_UNSUPPORTED (JSON is the debugging format). */
+#define RQ_ATTR_MAX_COLUMNS 16u
+enum { RQ_ATTR_U32 = 0, RQ_ATTR_I32 = 1, RQ_ATTR_F32 = 2, RQ_ATTR_U64 = 3, RQ_ATTR_I64 = 4 };
+typedef union {
+    uint32_t u32;
+    int32_t i32;
+    float f32;
+    uint64_t u64;
+    int64_t i64;
+} rq_attr_value_t;
+typedef struct {
+    uint32_t struct_size; /* set to sizeof(rq_attr_info_t) before the call */
+    uint32_t type;        /* RQ_ATTR_* */
+    char name[32];        /* zero-terminated */
+    rq_attr_value_t fill;
+    uint64_t bytes;       /* n x elem: the size of the column (and of rq_attr_get_array's dst) */
+} rq_attr_info_t;
+rq_status rq_attr_create(rq_index *idx, const char *name, uint32_t type, rq_attr_value_t fill);
+rq_status rq_attr_drop(rq_index *idx, const char *name);
+rq_status rq_attr_count(const rq_index *idx, uint32_t *out);
+rq_status rq_attr_info(const rq_index *idx, uint32_t i, rq_attr_info_t *out);
+rq_status rq_attr_index(const rq_index *idx, const char *name, uint32_t *out);
+rq_status rq_attr_set(rq_index *idx, const char *name, const uint32_t *ids, const void *values, uint64_t m, uint64_t *out_absent);
+rq_status rq_attr_set_device(rq_index *idx, const char *name, const uint32_t *d_ids, const void *d_values, uint64_t m, uint64_t *out_absent);
+rq_status rq_attr_get(const rq_index *idx, const char *name, const uint32_t *ids, uint64_t m, void *out_values, uint32_t *out_found);
+rq_status rq_attr_get_device(const rq_index *idx, const char *name, const uint32_t *d_ids, uint64_t m, void *d_out_values, uint32_t *d_out_found);
+rq_status rq_attr_get_array(const rq_index *idx, const char *name, void *dst, uint64_t dst_bytes);
+
+/* Predicates to filters.  rq_filter_create_where evaluates a boolean expression over the columns for every stored row, on the
+ * device, and returns an ordinary rq_filter of the rows it holds for (AND the live rows, where removals are pending): everything
+ * that takes a filter takes it, it carries the index's current generation and removal epoch, and it is freed by rq_filter_free.
+ * A term compares one column (its index in rq_attr_info order: rq_attr_index) with constants: RQ_WHERE_EQ, _NE, _LT, _LE, _GT, _GE
+ * against a; RQ_WHERE_BETWEEN: a <= v <= b; RQ_WHERE_IN: v == s for one of the set_count <= RQ_WHERE_MAX_SET values at `set` (host
+ * memory, elements of the column's type; the library sorts and uploads them; an empty set holds for no row); RQ_WHERE_ANY_BITS:
+ * (v & a) != 0; RQ_WHERE_ALL_BITS: (v & a) == a -- the two bit ops on integer columns only.  Comparisons are the column type's own:
+ * unsigned for U32 / U64, signed for I32 / I64, IEEE for F32 (a NaN value or constant fails everything but NE; -0 == +0).
+ * `program` is a postfix string of ntokens one-byte tokens: a value below RQ_WHERE_MAX_TERMS pushes that term's truth value,
+ * RQ_WHERE_AND / _OR pop two and push one, RQ_WHERE_NOT negates the top.  At most 32 terms, 64 tokens, stack depth 32; the program
+ * must end at depth 1.  program == NULL: the AND of all terms.  nterms == 0 (with program == NULL): every row holds.
+ * Refused with RQ_ERR_INVALID (before a device is looked for where no field of the index is needed): null arguments, nterms or
+ * ntokens past the limits, an unknown op or token, a program that underflows, overflows depth 32 or does not end at depth 1, an IN
+ * term with a null set and set_count > 0 or with more than RQ_WHERE_MAX_SET values; then an unknown column, an op the column's
+ * type does not have, a predicate that reads more than RQ_WHERE_MAX_COLUMNS distinct columns.
+ * On the device: one kernel streams the referenced columns (n x elem bytes each, coalesced) and writes the position bitmap, 64
+ * positions per wave ballot; then the steps of rq_filter_create.  No id bitmap, no upload, no read through map_ids.
+ * rq_last_where_stats: the calling thread's last rq_filter_create_where. */
+enum { RQ_WHERE_EQ = 0, RQ_WHERE_NE, RQ_WHERE_LT, RQ_WHERE_LE, RQ_WHERE_GT, RQ_WHERE_GE, RQ_WHERE_BETWEEN, RQ_WHERE_IN,
+       RQ_WHERE_ANY_BITS, RQ_WHERE_ALL_BITS };
+#define RQ_WHERE_MAX_TERMS   32u
+#define RQ_WHERE_MAX_TOKENS  64u
+#define RQ_WHERE_MAX_COLUMNS 8u
+#define RQ_WHERE_MAX_SET     4096u
+#define RQ_WHERE_AND 0x80u
+#define RQ_WHERE_OR  0x81u
+#define RQ_WHERE_NOT 0x82u
+typedef struct {
+    uint32_t column;       /* index of the column in rq_attr_info order */
+    uint32_t op;           /* RQ_WHERE_EQ .. RQ_WHERE_ALL_BITS */
+    rq_attr_value_t a, b;  /* the constants (b: RQ_WHERE_BETWEEN only) */
+    const void *set;       /* RQ_WHERE_IN: set_count elements of the column's type, host memory */
+    uint32_t set_count;
+    uint32_t reserved0;    /* 0 */
+} rq_where_term_t;
+typedef struct {
+    uint32_t struct_size;  /* set to sizeof(rq_where_stats_t) before the call */
+    uint32_t columns;      /* distinct columns the predicate read */
+    uint64_t rows;         /* stored rows evaluated */
+    uint64_t admitted;     /* rows of the filter */
+    uint64_t bytes_read;   /* column bytes the kernel streamed: rows x the elem sizes of the columns read */
+    float ms_eval;         /* device ms of the predicate kernel (HIP events) */
+    float ms_finish;       /* wall ms of everything behind it: live AND, per-list counts, the filter's derived state */
+} rq_where_stats_t;
+rq_status rq_filter_create_where(const rq_index *idx, const rq_where_term_t *terms, uint32_t nterms, const uint8_t *program,
+                                 uint32_t ntokens, rq_filter **out);
+rq_status rq_last_where_stats(rq_where_stats_t *out);
+/* rq_filter_combine: *out = a new filter of idx admitting a AND b, a OR b, a AND NOT b, or NOT a (b ignored, may be NULL) -- one
+ * word-wise pass over the two position bitmaps, ANDed with the live rows and cut at n (NOT never admits a dead row or a position
+ * past the last), then the steps of rq_filter_create.  This is how a predicate and an id allow-list meet.  A filter of another
+ * index, or a stale one (made before a relayout or a marking rq_remove_lazy), is RQ_ERR_INVALID, exactly as the queries refuse it.
+ * rq_filter_id_bits: the id bitmap of the admitted rows in the format rq_remove, rq_remove_lazy, rq_extract and rq_filter_create
+ * take -- (nbits + 31) / 32 words, zeroed first, ids at or past nbits left out; host or device memory (bits_on_device).  "Delete
+ * where" and "extract where" are rq_filter_create_where, this call and rq_remove / rq_extract.
+ * rq_filter_ids_device: the admitted ids in position order into d_out_ids (device memory, room for `cap` ids): the first
+ * min(cap, admitted) of them are written; *out_count (host) = the number admitted.  The two read the filter's own bitmap and the
+ * ids of its index: a stale filter is RQ_ERR_INVALID here too. */
+enum { RQ_FILTER_AND = 0, RQ_FILTER_OR = 1, RQ_FILTER_ANDNOT = 2, RQ_FILTER_NOT = 3 };
+rq_status rq_filter_combine(const rq_index *idx, const rq_filter *a, const rq_filter *b, uint32_t op, rq_filter **out);
+rq_status rq_filter_id_bits(const rq_filter *f, uint32_t *bits, uint64_t nbits, int bits_on_device);
+rq_status rq_filter_ids_device(const rq_filter *f, uint32_t *d_out_ids, uint64_t cap, uint64_t *out_count);
 
 /* ---- merge two indexes, extract a sub-index ------------------------------------------------------------------------------ */
 /* Both work on stored rows as they stand: nothing is rotated, assigned, quantised -- or, on a cosine or inner-product index,

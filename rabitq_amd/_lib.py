@@ -41,6 +41,9 @@ EXPORTS = [
     "rq_locate", "rq_locate_device", "rq_fetch_rows", "rq_fetch_rows_device", "rq_fetch_stored", "rq_fetch_stored_device",
     "rq_pair_distances", "rq_pair_distances_device", "rq_neighbours_of", "rq_neighbours_of_device", "rq_neighbours_of_exact",
     "rq_neighbours_of_exact_device", "rq_last_by_id_stats",
+    "rq_attr_create", "rq_attr_drop", "rq_attr_count", "rq_attr_info", "rq_attr_index", "rq_attr_set", "rq_attr_set_device",
+    "rq_attr_get", "rq_attr_get_device", "rq_attr_get_array", "rq_filter_create_where", "rq_last_where_stats",
+    "rq_filter_combine", "rq_filter_id_bits", "rq_filter_ids_device",
 ]
 
 
@@ -183,6 +186,45 @@ class ByIdStatsT(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("form", C.c_uint32), ("directory_bytes", C.c_uint64), ("ms_build", C.c_float),
                 ("longest_chain", C.c_uint32), ("found", C.c_uint64), ("absent", C.c_uint64), ("gather_bytes", C.c_uint64),
                 ("ms_gather", C.c_float), ("ms_lookup", C.c_float), ("built", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
+class AttrType(NamedTuple):
+    """One attribute column type (RQ_ATTR_* of include/rabitq_hip.h)."""
+    name: str        # the dtype= argument of create_attr
+    id: int
+    dtype: type      # numpy dtype of the column's values
+    elem_bytes: int
+
+
+ATTR_TABLE = (
+    AttrType("u32", 0, np.uint32, 4), AttrType("i32", 1, np.int32, 4), AttrType("f32", 2, np.float32, 4),
+    AttrType("u64", 3, np.uint64, 8), AttrType("i64", 4, np.int64, 8),
+)
+ATTR_BY_NAME = {t.name: t for t in ATTR_TABLE}
+ATTR_BY_ID = {t.id: t for t in ATTR_TABLE}
+ATTR_MAX_COLUMNS = 16                                    # RQ_ATTR_MAX_COLUMNS
+FILTER_AND, FILTER_OR, FILTER_ANDNOT, FILTER_NOT = range(4)   # RQ_FILTER_*
+
+
+class AttrValue(C.Union):
+    """rq_attr_value_t: 8 bytes, a 4-byte value in the low 4.  (ctypes passes no union by value: the entries that take one by value
+    are declared with its u64 image, which the x86-64 and aarch64 calling conventions pass the same way.)"""
+    _fields_ = [("u32", C.c_uint32), ("i32", C.c_int32), ("f32", C.c_float), ("u64", C.c_uint64), ("i64", C.c_int64)]
+
+
+class AttrInfoT(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("type", C.c_uint32), ("name", C.c_char * 32), ("fill", AttrValue), ("bytes", C.c_uint64)]
+
+
+class WhereTermT(C.Structure):
+    """rq_where_term_t: one comparison of a column (its index in rq_attr_info order) with constants; `set`: a host address."""
+    _fields_ = [("column", C.c_uint32), ("op", C.c_uint32), ("a", AttrValue), ("b", AttrValue), ("set", C.c_void_p),
+                ("set_count", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
+class WhereStatsT(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("columns", C.c_uint32), ("rows", C.c_uint64), ("admitted", C.c_uint64),
+                ("bytes_read", C.c_uint64), ("ms_eval", C.c_float), ("ms_finish", C.c_float)]
 
 
 def build(force: bool = False) -> str:
@@ -340,6 +382,21 @@ def lib():
         "rq_neighbours_of_exact": (i32, [vp, u32p, u32, u32, vp, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
         "rq_neighbours_of_exact_device": (i32, [vp, u32p, u32, u32, vp, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
         "rq_last_by_id_stats": (i32, [C.POINTER(ByIdStatsT)]),
+        "rq_attr_create": (i32, [vp, C.c_char_p, u32, u64]),   # (fill: the union's u64 image, see AttrValue)
+        "rq_attr_drop": (i32, [vp, C.c_char_p]),
+        "rq_attr_count": (i32, [vp, C.POINTER(u32)]),
+        "rq_attr_info": (i32, [vp, u32, C.POINTER(AttrInfoT)]),
+        "rq_attr_index": (i32, [vp, C.c_char_p, C.POINTER(u32)]),
+        "rq_attr_set": (i32, [vp, C.c_char_p, u32p, vp, u64, C.POINTER(u64)]),
+        "rq_attr_set_device": (i32, [vp, C.c_char_p, u32p, vp, u64, C.POINTER(u64)]),
+        "rq_attr_get": (i32, [vp, C.c_char_p, u32p, u64, vp, u32p]),
+        "rq_attr_get_device": (i32, [vp, C.c_char_p, u32p, u64, vp, u32p]),
+        "rq_attr_get_array": (i32, [vp, C.c_char_p, vp, u64]),
+        "rq_filter_create_where": (i32, [vp, C.POINTER(WhereTermT), u32, vp, u32, pp]),
+        "rq_last_where_stats": (i32, [C.POINTER(WhereStatsT)]),
+        "rq_filter_combine": (i32, [vp, vp, vp, u32, pp]),
+        "rq_filter_id_bits": (i32, [vp, u32p, u64, C.c_int]),
+        "rq_filter_ids_device": (i32, [vp, u32p, u64, C.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the .so lacks a declared symbol

@@ -234,6 +234,9 @@ static rq_status index_add(rq_index *idx, const float *rows, uint64_t m, uint32_
 }
 
 // ---- rq_merge_from / rq_extract --------------------------------------------------------------------------------------------------
+// (host_attr.h) a column of the same name in both indexes has the same type, else RQ_ERR_INVALID
+static rq_status attr_merge_check(const rq_index *dst, const rq_index *src);
+
 // `what` of the two indexes equal bit for bit (device arrays of `count` 32-bit words), else RQ_ERR_INVALID naming the first difference
 static rq_status same_bits_check(const char *what, const float *a, const float *b, uint64_t count) {
     DevBuf<unsigned long long> first;
@@ -288,6 +291,7 @@ static rq_status index_merge_from(rq_index *dst, rq_index *src, uint32_t id_mode
     if (dst->metric.id != src->metric.id) return fail(RQ_ERR_INVALID, "the two indexes differ in metric");
     if (dst->metric.d != src->metric.d) return fail(RQ_ERR_INVALID, "the two inner-product indexes differ in the row length d");
     if (memcmp(&dst->metric.S, &src->metric.S, 4) != 0) return fail(RQ_ERR_INVALID, "the two inner-product indexes differ in sq_bound (S)");
+    RQC(attr_merge_check(dst, src));
     RQC(same_bits_check("the rotation P", dst->P.p, src->P.p, (uint64_t)dst->dim * dst->dim));
     RQC(same_bits_check("the rotated centroids", dst->centroids.p, src->centroids.p, (uint64_t)dst->k * dst->dim));
     if (dst->n + src->n >= 0xFFFFFFFFull) return fail(RQ_ERR_UNSUPPORTED, "n must fit u32 ids (rabitq.rs:64-65)");

@@ -173,6 +173,9 @@ static rq_status filter_finish(const rq_index *idx, rq_filter *f) {
 }
 
 // ---- the core ------------------------------------------------------------------------------------------------------------------------
+// (host_attr.h) every attribute column of a follows the layout's destination-to-source map into nx; *bytes += what that moves
+static rq_status columns_follow(const rq_index *a, const rq_index *b, const uint32_t *src_of_dst, uint64_t n, rq_index *nx, uint64_t *bytes);
+
 static MergeSide merge_side(const rq_index *idx, bool keys) {
     if (!idx) return MergeSide{nullptr, nullptr, nullptr, nullptr, nullptr};
     return MergeSide{reinterpret_cast<const float4 *>(idx->base.p), idx->codes.p, idx->factors.p, idx->map_ids.p, keys ? idx->row_key.p : nullptr};
@@ -234,11 +237,13 @@ static rq_status build_layout(const rq_index *a, const rq_index *b, uint32_t shi
     HIPC(hipGetLastError());
     st.ms_merge = clk.lap();
     if (n) launch_merge_gather(src_of_dst.p, n, a, b, shift_b, keys, nx.get(), holes.p);
+    uint64_t column_bytes = 0;  // the attribute columns of a, by the same map (none: nothing is allocated or launched)
+    RQC(columns_follow(a, b, src_of_dst.p, n, nx.get(), &column_bytes));
     HIPC(hipDeviceSynchronize());
     HIPC(hipGetLastError());
     st.ms_gather = clk.lap();
     // bytes the gather moves: every destination row read once and written once (raw vector, codes, factors, id, key), and the map
-    st.gather_bytes = 2 * n * ((uint64_t)dim * 4 + (uint64_t)W * 8 + 16 + 4 + (keys ? 4 : 0)) + n * 4;
+    st.gather_bytes = 2 * n * ((uint64_t)dim * 4 + (uint64_t)W * 8 + 16 + 4 + (keys ? 4 : 0)) + n * 4 + column_bytes;
     unsigned int h_holes = 0;
     HIPC(hipMemcpy(&h_holes, holes.p, 4, hipMemcpyDeviceToHost));
     if (h_holes)  // (cannot happen on lists in the build's order with unique ids, which the caller checks; refused rather than committed)
@@ -259,6 +264,7 @@ static rq_status commit_layout(rq_index *idx, std::unique_ptr<rq_index> &nx, Pha
     swap_buf(idx->offsets, nx->offsets), swap_buf(idx->map_ids, nx->map_ids), swap_buf(idx->codes, nx->codes);
     swap_buf(idx->factors, nx->factors), swap_buf(idx->list_uref, nx->list_uref), swap_buf(idx->cent_bf, nx->cent_bf);
     swap_buf(idx->cent_sqnorm, nx->cent_sqnorm), swap_buf(idx->row_key, nx->row_key);
+    idx->attrs.swap(nx->attrs);
     idx->n = nx->n, idx->n_dev = nx->n_dev, idx->max_list_len = nx->max_list_len, idx->min_list_len = nx->min_list_len;
     idx->cent_norm_max = nx->cent_norm_max, idx->nonempty_lists = nx->nonempty_lists, idx->fstats = nx->fstats;
     idx->pass_budget = nx->pass_budget;

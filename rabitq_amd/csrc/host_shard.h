@@ -61,6 +61,7 @@ rq_status rq_shard_index(const rq_index *idx, const uint32_t *owner, uint32_t ra
         shard_gather_kernel<<<(uint32_t)std::min<uint64_t>(ceil_div(n_local, 4), 1u << 20), 256>>>(
             sh->offsets.p, idx->offsets.p, k, n_local, dim, idx->view(), idx->codes.p, idx->factors.p, idx->map_ids.p,
             sh->view(), sh->codes.p, sh->factors.p, sh->map_ids.p);
+    RQC(columns_shard(idx, sh.get(), off, noff, owner, rank));  // the attribute columns: each owned list's slice
     HIPC(hipDeviceSynchronize());
     HIPC(hipGetLastError());
     RQC(finish_index(sh.get()));

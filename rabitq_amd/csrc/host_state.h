@@ -279,6 +279,14 @@ struct IdDirectory {
     uint32_t longest_chain = 0;  // hash form: slots the worst insertion looked at
 };
 
+// One attribute column of an index (host_attr.h, kernels_attr.h): n elements of 4 or 8 bytes in position order.
+struct AttrColumn {
+    std::string name;
+    uint32_t type = 0;   // RQ_ATTR_*
+    uint64_t fill = 0;   // the u64 image of the fill value (a 4-byte type: the high word is zero)
+    DevBuf<uint8_t> data;
+};
+
 struct rq_index {
     uint32_t dim = 0, k = 0, W = 0, max_list_len = 0;
     uint32_t min_list_len = 0;  // 0 if some list is empty (then no slot bound can be derived from stream positions)
@@ -344,6 +352,8 @@ struct rq_index {
     std::mutex dir_mu;
     std::unique_ptr<IdDirectory> dir;
     uint64_t removal_epoch = 0;   // bumped by every rq_remove_lazy that marks a row; a filter made under an older epoch is refused
+    // attribute columns (host_attr.h), in rq_attr_info order; empty on an index that was given none.  Moved along by every relayout.
+    std::vector<std::unique_ptr<AttrColumn>> attrs;
     inline uint64_t pending() const;  // stored rows that are dead
 };
 

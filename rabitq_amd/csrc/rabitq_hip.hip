@@ -21,6 +21,7 @@
 #include <random>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include <sys/stat.h>
 #include <dlfcn.h>
@@ -35,6 +36,7 @@
 #include "kernels_train.h"
 #include "kernels_relayout.h"
 #include "kernels_directory.h"
+#include "kernels_attr.h"
 
 #include "kernel_shapes.h"
 #include "host_state.h"
@@ -52,6 +54,7 @@
 #include "host_exact_range.h"
 #include "host_train.h"
 #include "host_directory.h"
+#include "host_attr.h"
 
 // ------------------------------------------------------------------------------------------------
 // extern "C"
@@ -432,10 +435,16 @@ rq_status rq_load_dir(const char *dir, rq_index **out) {
         return fail(RQ_ERR_IO, "rows: an index of this metric has no rows of the announced type (" + d + ")");
     std::vector<uint8_t> typed;  // typed rows: every value of base.fvecs must be one of the type's
     if (rows.typed()) RQC(narrow_exact(reinterpret_cast<const float *>(base.data.data()), n * dim, rows, typed, d + "/base.fvecs"));
-    return from_arrays(dim, n, k, RowsIn::of(rows.typed() ? typed.data() : base.data.data(), rows),
-                       reinterpret_cast<const float *>(ortho.data.data()), c.data(), oip, oip + (total - last),
-                       reinterpret_cast<const uint64_t *>(bin.data.data()),
-                       reinterpret_cast<const rq_factor_t *>(fac.data.data()), metric, out);
+    RQC(from_arrays(dim, n, k, RowsIn::of(rows.typed() ? typed.data() : base.data.data(), rows),
+                    reinterpret_cast<const float *>(ortho.data.data()), c.data(), oip, oip + (total - last),
+                    reinterpret_cast<const uint64_t *>(bin.data.data()),
+                    reinterpret_cast<const rq_factor_t *>(fac.data.data()), metric, out));
+    const rq_status as = attr_load_dir(d, *out);  // the attribute columns of the dump, where it has an `attrs` file
+    if (as != RQ_OK) {
+        delete *out;
+        *out = nullptr;
+    }
+    return as;
 }
 
 rq_status rq_get_array(const rq_index *idx, int which, void *dst, uint64_t dst_bytes);
@@ -525,7 +534,7 @@ rq_status rq_dump_dir(const rq_index *idx, const char *dir) {
     } else {
         remove((d + "/rows").c_str());
     }
-    return RQ_OK;
+    return attr_dump_dir(idx, d);  // (an index without columns: nothing is written)
 }
 
 // ---- JSON persistence: load_from_json / dump_to_json, src/rabitq.rs:72-81 ------------------------------------
@@ -540,6 +549,7 @@ rq_status rq_dump_dir(const rq_index *idx, const char *dir) {
 rq_status rq_dump_json(const rq_index *idx, const char *path) {
     if (!idx || !path) return fail(RQ_ERR_INVALID, "null argument");
     if (idx->live) return fail(RQ_ERR_UNSUPPORTED, kPendingRefusal);
+    if (!idx->attrs.empty()) return fail(RQ_ERR_UNSUPPORTED, "the JSON image has no attribute columns (rq_dump_dir writes them)");
     const uint64_t n = idx->n, dim = idx->dim, k = idx->k;
     std::vector<float> base(n * dim), P(dim * dim), C(k * dim), fac(n * 4);
     std::vector<uint32_t> off(k + 1), ids(n);
@@ -1164,6 +1174,52 @@ rq_status rq_neighbours_of_exact_device(const rq_index *idx, const uint32_t *d_i
 rq_status rq_last_by_id_stats(rq_by_id_stats_t *out) {
     if (!out) return fail(RQ_ERR_INVALID, "null argument");
     return copy_out_sized(out, g_by_id_stats);
+}
+
+// ---- attribute columns and predicate filters (host_attr.h) ----
+rq_status rq_attr_create(rq_index *idx, const char *name, uint32_t type, rq_attr_value_t fill) { return by_id_done(attr_create(idx, name, type, fill)); }
+rq_status rq_attr_drop(rq_index *idx, const char *name) { return attr_drop(idx, name); }
+rq_status rq_attr_count(const rq_index *idx, uint32_t *out) {
+    if (!idx || !out) return fail(RQ_ERR_INVALID, "null argument");
+    *out = (uint32_t)idx->attrs.size();
+    return RQ_OK;
+}
+rq_status rq_attr_info(const rq_index *idx, uint32_t i, rq_attr_info_t *out) { return attr_info(idx, i, out); }
+rq_status rq_attr_index(const rq_index *idx, const char *name, uint32_t *out) {
+    AttrColumn *c = nullptr;
+    RQC(attr_named(idx, name, !out, &c));
+    *out = (uint32_t)attr_find(idx, name);
+    return RQ_OK;
+}
+rq_status rq_attr_set(rq_index *idx, const char *name, const uint32_t *ids, const void *values, uint64_t m, uint64_t *out_absent) {
+    return by_id_done(attr_set_host(idx, name, ids, values, m, out_absent));
+}
+rq_status rq_attr_set_device(rq_index *idx, const char *name, const uint32_t *d_ids, const void *d_values, uint64_t m, uint64_t *out_absent) {
+    return by_id_done(attr_set_device(idx, name, d_ids, d_values, m, out_absent));
+}
+rq_status rq_attr_get(const rq_index *idx, const char *name, const uint32_t *ids, uint64_t m, void *out_values, uint32_t *out_found) {
+    return by_id_done(attr_get_host(idx, name, ids, m, out_values, out_found));
+}
+rq_status rq_attr_get_device(const rq_index *idx, const char *name, const uint32_t *d_ids, uint64_t m, void *d_out_values, uint32_t *d_out_found) {
+    return by_id_done(attr_get_device(idx, name, d_ids, m, d_out_values, d_out_found));
+}
+rq_status rq_attr_get_array(const rq_index *idx, const char *name, void *dst, uint64_t dst_bytes) { return attr_get_array(idx, name, dst, dst_bytes); }
+rq_status rq_filter_create_where(const rq_index *idx, const rq_where_term_t *terms, uint32_t nterms, const uint8_t *program, uint32_t ntokens,
+                                 rq_filter **out) {
+    return by_id_done(filter_create_where(idx, terms, nterms, program, ntokens, out));
+}
+rq_status rq_last_where_stats(rq_where_stats_t *out) {
+    if (!out) return fail(RQ_ERR_INVALID, "null argument");
+    return copy_out_sized(out, g_where_stats);
+}
+rq_status rq_filter_combine(const rq_index *idx, const rq_filter *a, const rq_filter *b, uint32_t op, rq_filter **out) {
+    return by_id_done(filter_combine(idx, a, b, op, out));
+}
+rq_status rq_filter_id_bits(const rq_filter *f, uint32_t *bits, uint64_t nbits, int bits_on_device) {
+    return by_id_done(filter_id_bits(f, bits, nbits, bits_on_device));
+}
+rq_status rq_filter_ids_device(const rq_filter *f, uint32_t *d_out_ids, uint64_t cap, uint64_t *out_count) {
+    return by_id_done(filter_ids_device(f, d_out_ids, cap, out_count));
 }
 
 rq_status rq_query(const rq_index *idx, const float *query, uint32_t len, uint32_t probe, uint32_t topk,

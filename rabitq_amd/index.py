@@ -158,6 +158,63 @@ class Filter:
         except Exception:
             pass
 
+    # ---- set algebra (rq_filter_combine): new filters of the same index, made on the device ----
+    def _combine(self, other, op):
+        if op != _lib.FILTER_NOT:
+            if not isinstance(other, Filter):
+                return NotImplemented
+            if other.index is not self.index:
+                raise ValueError("the two filters belong to different indexes")
+        h = C.c_void_p()
+        check(lib().rq_filter_combine(self.index._h, self._h, _fh(other), op, C.byref(h)))
+        return Filter(self.index, h)
+
+    def __and__(self, other):
+        """Rows both filters admit."""
+        return self._combine(other, _lib.FILTER_AND)
+
+    def __or__(self, other):
+        """Rows either filter admits."""
+        return self._combine(other, _lib.FILTER_OR)
+
+    def __sub__(self, other):
+        """Rows this filter admits and `other` does not."""
+        return self._combine(other, _lib.FILTER_ANDNOT)
+
+    def __invert__(self):
+        """The live rows this filter does not admit."""
+        return self._combine(None, _lib.FILTER_NOT)
+
+    def ids_device(self, out_ptr: int, cap: int) -> int:
+        """The admitted ids in position order into device memory at out_ptr (room for cap u32); -> rows admitted (rq_filter_ids_device)."""
+        count = C.c_uint64()
+        check(lib().rq_filter_ids_device(self._h, C.c_void_p(out_ptr), cap, C.byref(count)))
+        return int(count.value)
+
+    def ids(self) -> np.ndarray:
+        """The admitted ids (u32) in position order, compacted on the device; the array travels through torch."""
+        if self.rows == 0:
+            return np.empty(0, dtype=np.uint32)
+        import torch
+        out = torch.empty(self.rows, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        got = self.ids_device(out.data_ptr(), self.rows)
+        return out[:got].cpu().numpy().view(np.uint32)
+
+    def id_bits(self, nbits=None) -> np.ndarray:
+        """The admitted ids as a boolean mask over ids (rq_filter_id_bits), the `mask=` remove(), extract() and make_filter() take:
+        `index.remove(mask=index.where(expr).id_bits())` is "delete where".  nbits: the mask's length, ids at or past it are left
+        out; default 1 + the largest admitted id."""
+        if nbits is None:
+            ids = self.ids()
+            nbits = int(ids.max()) + 1 if ids.size else 0
+        nbits = int(nbits)
+        if not 0 <= nbits <= (1 << 32):
+            raise ValueError("ids are u32: 0 <= nbits <= 2^32")
+        words = np.zeros((nbits + 31) // 32, dtype=np.uint32)
+        check(lib().rq_filter_id_bits(self._h, _addr(words), nbits, 0))
+        return np.unpackbits(words.view(np.uint8), bitorder="little")[:nbits].astype(bool)
+
 
 def _fh(filter):
     return filter._h if filter is not None else None
@@ -453,6 +510,121 @@ class RaBitQ:
         h = C.c_void_p()
         check(lib().rq_filter_create(self._h, C.c_void_p(bits_ptr), nbits, 1, C.byref(h)))
         return Filter(self, h)
+
+    # ---- attribute columns: per-row values in position order, predicates over them as filters -------
+    def create_attr(self, name: str, dtype, fill=0) -> None:
+        """A new column `name` of dtype "u32" / "i32" / "f32" / "u64" / "i64" (or the numpy dtype), every row holding `fill`
+        (rq_attr_create).  At most 16 columns; a name is 1-31 bytes of [A-Za-z0-9_]."""
+        t = self._attr_type(dtype)
+        image = int(np.array([fill]).astype(t.dtype).view(np.uint32 if t.elem_bytes == 4 else np.uint64)[0])
+        check(lib().rq_attr_create(self._h, name.encode(), t.id, image))
+
+    def drop_attr(self, name: str) -> None:
+        check(lib().rq_attr_drop(self._h, name.encode()))
+
+    @staticmethod
+    def _attr_type(dtype):
+        if isinstance(dtype, str) and dtype in _lib.ATTR_BY_NAME:
+            return _lib.ATTR_BY_NAME[dtype]
+        for t in _lib.ATTR_TABLE:
+            if not isinstance(dtype, str) and np.dtype(dtype) == np.dtype(t.dtype):
+                return t
+        raise ValueError(f"dtype must be one of {sorted(_lib.ATTR_BY_NAME)} or their numpy dtypes, not {dtype!r}")
+
+    def attrs(self) -> list:
+        """The columns in rq_attr_info order: [{"name", "dtype", "fill", "bytes"}]."""
+        cnt = C.c_uint32()
+        check(lib().rq_attr_count(self._h, C.byref(cnt)))
+        out = []
+        for i in range(cnt.value):
+            info = _lib.AttrInfoT()
+            check(lib().rq_attr_info(self._h, i, C.byref(info)))
+            t = _lib.ATTR_BY_ID[int(info.type)]
+            fill = np.array([info.fill.u64], dtype=np.uint64).view(t.dtype)[0]
+            out.append({"name": info.name.decode(), "dtype": t.name, "fill": fill.item(), "bytes": int(info.bytes)})
+        return out
+
+    def _attr(self, name):
+        for a in self.attrs():
+            if a["name"] == name:
+                return _lib.ATTR_BY_NAME[a["dtype"]]
+        raise _lib.RabitqError(-1, f"the index has no column named {name}")
+
+    def set_attr(self, name: str, ids, values) -> int:
+        """values[i] becomes the value of the row with id ids[i] (rq_attr_set); a scalar `values` goes to every id.  Ids the index
+        does not hold (or dead ones) are skipped -> how many were.  Where an id repeats, its last value wins.  Positions do not
+        change: existing filters stay valid and keep the rows they selected."""
+        t = self._attr(name)
+        idv = self._id_list(ids)
+        vals = np.asarray(values)
+        if vals.ndim == 0:
+            vals = np.full(idv.shape, vals)
+        vals = np.ascontiguousarray(vals.astype(t.dtype, copy=False))
+        if vals.shape != idv.shape:
+            raise ValueError(f"values must have one value per id ({idv.size}), not shape {vals.shape}")
+        absent = C.c_uint64()
+        check(lib().rq_attr_set(self._h, name.encode(), _addr(idv), _addr(vals), idv.size, C.byref(absent)))
+        return int(absent.value)
+
+    def get_attr(self, name: str, ids):
+        """-> (values in the column's dtype, found bool): the value of each id; an absent id gives the fill value and False."""
+        t = self._attr(name)
+        idv = self._id_list(ids)
+        vals = np.empty(idv.size, dtype=t.dtype)
+        found = np.zeros(idv.size, dtype=np.uint32)
+        check(lib().rq_attr_get(self._h, name.encode(), _addr(idv), idv.size, _addr(vals), _addr(found)))
+        return vals, found.astype(bool)
+
+    def attr_array(self, name: str) -> np.ndarray:
+        """The whole column in position order: element p belongs to the row whose id is map_ids[p] (rq_attr_get_array)."""
+        t = self._attr(name)
+        self._refresh()
+        out = np.empty(self.n, dtype=t.dtype)
+        check(lib().rq_attr_get_array(self._h, name.encode(), _addr(out), out.nbytes))
+        return out
+
+    def where(self, expr) -> Filter:
+        """A filter of the rows a predicate over the columns holds for, evaluated on the device (rq_filter_create_where):
+        `idx.where((col("tenant") == 7) & (col("ts") >= t0))`.  See rabitq_amd/where.py for the expression forms."""
+        from . import where as W
+        terms, program = W.compile_expr(expr)
+        cols = {a["name"]: (i, _lib.ATTR_BY_NAME[a["dtype"]]) for i, a in enumerate(self.attrs())}
+        arr = (_lib.WhereTermT * max(len(terms), 1))()
+        keep = []   # the sets' host arrays, alive until the call returns
+        for i, t in enumerate(terms):
+            if t.column not in cols:
+                raise _lib.RabitqError(-1, f"the index has no column named {t.column}")
+            ci, at = cols[t.column]
+            view = np.uint32 if at.elem_bytes == 4 else np.uint64
+            image = lambda v: int(self._attr_const(v, at).view(view)[0])
+            arr[i].column, arr[i].op = ci, t.op
+            arr[i].a.u64, arr[i].b.u64 = image(t.a), image(t.b)
+            if t.op == W.OP_IN:
+                vals = np.concatenate([self._attr_const(v, at) for v in t.values]) if t.values else np.empty(0, dtype=at.dtype)
+                keep.append(vals)
+                arr[i].set, arr[i].set_count = vals.ctypes.data, vals.size
+        prog = np.asarray(program, dtype=np.uint8)
+        h = C.c_void_p()
+        check(lib().rq_filter_create_where(self._h, arr, len(terms), _addr(prog), prog.size, C.byref(h)))
+        return Filter(self, h)
+
+    @staticmethod
+    def _attr_const(v, at):
+        """A predicate's constant in the column's type, as a 1-element array: exact, or ValueError (an integer the type cannot
+        hold, a fraction for an integer column)."""
+        if at.name == "f32":
+            return np.array([v], dtype=np.float32)
+        if isinstance(v, (float, np.floating)) and not float(v).is_integer():
+            raise ValueError(f"{v!r} is not a value of an integer ({at.name}) column")
+        iv = int(v)
+        info = np.iinfo(at.dtype)
+        if not info.min <= iv <= info.max:
+            raise ValueError(f"{iv} is not a value of a {at.name} column")
+        return np.array([iv], dtype=at.dtype)
+
+    @staticmethod
+    def last_where_stats() -> dict:
+        return last_where_stats()
 
     # ---- in-place mutation: the index afterwards equals a fresh build of its live rows -------------
     def _rows(self, vectors):
@@ -1200,6 +1372,13 @@ def last_by_id_stats() -> dict:
     out = {name: getattr(st, name) for name, _ in _lib.ByIdStatsT._fields_ if name not in ("struct_size", "reserved0")}
     out["form"] = _lib.DIRECTORY_FORMS.get(out["form"], out["form"])
     return out
+
+
+def last_where_stats() -> dict:
+    """The calling thread's last where() (include/rabitq_hip.h: rq_last_where_stats)."""
+    st = _lib.WhereStatsT()
+    check(lib().rq_last_where_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _lib.WhereStatsT._fields_ if name != "struct_size"}
 
 
 def calculate_recall(truth, res, topk: int) -> float:
