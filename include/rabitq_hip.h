@@ -100,7 +100,9 @@ typedef struct {
  * 0.15.0: attribute columns, additions only -- RQ_ATTR_*, rq_attr_value_t, rq_attr_info_t, rq_attr_create / _drop / _count / _info /
  * _index / _set* / _get* / _get_array, RQ_WHERE_*, rq_where_term_t, rq_filter_create_where, rq_where_stats_t, rq_last_where_stats,
  * RQ_FILTER_*, rq_filter_combine, rq_filter_id_bits, rq_filter_ids_device; an index without columns behaves, allocates and dumps
- * exactly as before; rq_last_mutate_stats.gather_bytes counts the column bytes a relayout moves).
+ * exactly as before; rq_last_mutate_stats.gather_bytes counts the column bytes a relayout moves);
+ * 0.16.0: grouped search, additions only -- rq_group_params_t, rq_group_stats_t, rq_query_batch_grouped*, rq_exact_search_grouped*,
+ * rq_group_results*, rq_last_group_stats; no existing call, refusal or output changes.
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -928,6 +930,83 @@ enum { RQ_FILTER_AND = 0, RQ_FILTER_OR = 1, RQ_FILTER_ANDNOT = 2, RQ_FILTER_NOT 
 rq_status rq_filter_combine(const rq_index *idx, const rq_filter *a, const rq_filter *b, uint32_t op, rq_filter **out);
 rq_status rq_filter_id_bits(const rq_filter *f, uint32_t *bits, uint64_t nbits, int bits_on_device);
 rq_status rq_filter_ids_device(const rq_filter *f, uint32_t *d_out_ids, uint64_t cap, uint64_t *out_count);
+
+/* ---- grouped search: at most group_size rows per value of a column, the topk nearest values (0.16.0, additions only) ------------ */
+/* "The topk nearest documents, at most group_size passages each" (group_by / collapse / dedup by field), on the device: the
+ * result rows of an existing call at topk = fetch are grouped by a column without travelling to the host.
+ * SOURCE.  For query b, the result row of the plain call at topk = fetch: cnt_b <= fetch pairs (dist, id).  rq_query_batch_grouped
+ *   runs rq_query_batch[_filtered](probe, fetch, heuristic_rank), rq_exact_search_grouped runs rq_exact_search(fetch, exact params),
+ *   both under `filter` (nullable; with removals pending and no filter: the live filter, as in the plain entries);
+ *   rq_group_results takes the rows from the caller (dist / id of stride fetch, cnt[b] valid entries, a larger cnt is cut at fetch):
+ *   the results of tickets, the adaptive call, rq_neighbours_of or the sharded step.  The order of the pairs inside a row is
+ *   arbitrary (the heap ranker returns its heap-internal order) and nothing depends on it.
+ * KEYS.  The group key of a candidate is the u64 image of its row's value in the named column: 4-byte types zero-extended (as
+ *   rq_attr_info's fill is), 8-byte types as stored.  Two rows are in one group iff the images are equal.  Integer columns only
+ *   (RQ_ATTR_U32 / _I32 / _U64 / _I64); an RQ_ATTR_F32 column is RQ_ERR_INVALID (-0 / +0 and NaNs have no agreed equality here).
+ * ABSENT IDS.  A candidate whose id has no live row (rq_locate would answer RQ_POS_ABSENT) is skipped and counted in
+ *   rq_group_stats_t.absent.  Only rq_group_results can meet one.
+ * SELECTION.  Sort the candidates ascending by the 64-bit key ord32_biased(dist) << 32 | id, the library's (distance, id) order.
+ *   ord(key) = the number of distinct keys whose first occurrence in that order precedes this key's first occurrence; rank(c) = the
+ *   number of earlier candidates with the same key as c.  c is kept iff ord(key_c) < topk and rank(c) < group_size.  This equals the
+ *   sequential walk "open a group while fewer than topk are open; take a row while its group holds fewer than group_size", and
+ *   does not depend on any processing order.
+ * OUTPUT, group-major: out_id / out_dist[b, ord * group_size + rank] (nq x topk x group_size), out_key[b, ord] (u64 images) and
+ *   out_group_n[b, ord] (rows kept of the group; nq x topk), out_n[b] = the number of groups.  Every slot without a row is written
+ *   on every call: id 0xFFFFFFFF, dist NaN (0x7FC00000, as rq_neighbours_of pads), key 0, group_n 0.  The same inputs give the same
+ *   bits on every run.
+ * COMPLETENESS.  The two query entries also write out_fetched[b] = cnt_b (nullable).  out_fetched[b] < fetch: the source had
+ *   nothing more to give -- behind the exact source the grouped answer is then the true one over all admitted rows.  Behind the
+ *   exact source with group_size == 1, out_n[b] == topk proves it too.  Otherwise the answer is "grouped top-fetch": raise fetch.
+ * LIMITS.  1 <= topk, 1 <= group_size, topk * group_size <= fetch <= 2048, else RQ_ERR_UNSUPPORTED.  Refused with RQ_ERR_INVALID
+ *   before a device is looked for: a null index, column name, params or output (out_fetched excepted), a null input with nq > 0,
+ *   params->struct_size != sizeof(rq_group_params_t), a set bit in flags, a malformed or unknown column name, an f32 column; the
+ *   limits likewise.  Then the source call's own refusals at topk = fetch (a stale or foreign filter; the exact form on tiered and
+ *   split-row indexes: RQ_ERR_UNSUPPORTED).  RQ_ERR_EMPTY from the source passes through with the outputs written, as in
+ *   rq_neighbours_of.  nq == 0 is RQ_OK.  Accepted wherever the source call and the by-id entries both are: every metric and row
+ *   type, shards of rq_shard_index, pending removals, after any relayout (the columns and a fresh directory follow).  rq_metrics
+ *   counts the source call.  _device forms: every pointer but column and params in device memory; they return with their outputs
+ *   complete.  No relayout and no rq_attr_set may run during a call.
+ * rq_last_group_stats: the calling thread's last grouped call. */
+typedef struct {
+    uint32_t struct_size; /* sizeof(rq_group_params_t) */
+    uint32_t topk;        /* groups per query */
+    uint32_t group_size;  /* rows per group */
+    uint32_t fetch;       /* candidates per query the source is asked for */
+    uint32_t flags;       /* 0 */
+} rq_group_params_t;
+typedef struct {
+    uint32_t struct_size;     /* set to sizeof(rq_group_stats_t) before the call */
+    uint32_t fetch;
+    float ms_source;          /* wall ms of the source call (0: rq_group_results) */
+    float ms_group;           /* device ms of the selection kernel (HIP events) */
+    uint64_t candidates;      /* sum of cnt_b */
+    uint64_t absent;          /* candidates without a live row */
+    uint64_t kept;            /* rows written */
+    uint64_t groups;          /* sum of out_n */
+    uint32_t directory_built; /* 1: this call made the id directory */
+    uint32_t reserved0;
+} rq_group_stats_t;
+rq_status rq_query_batch_grouped(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len, uint32_t probe,
+                                 int heuristic_rank, const char *column, const rq_group_params_t *params, float *out_dist, uint32_t *out_id,
+                                 uint64_t *out_key, uint32_t *out_group_n, uint32_t *out_n, uint32_t *out_fetched);
+rq_status rq_query_batch_grouped_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
+                                        uint32_t probe, int heuristic_rank, const char *column, const rq_group_params_t *params,
+                                        float *d_out_dist, uint32_t *d_out_id, uint64_t *d_out_key, uint32_t *d_out_group_n, uint32_t *d_out_n,
+                                        uint32_t *d_out_fetched);
+rq_status rq_exact_search_grouped(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len,
+                                  const rq_exact_params_t *exact, const char *column, const rq_group_params_t *params, float *out_dist,
+                                  uint32_t *out_id, uint64_t *out_key, uint32_t *out_group_n, uint32_t *out_n, uint32_t *out_fetched);
+rq_status rq_exact_search_grouped_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
+                                         const rq_exact_params_t *exact, const char *column, const rq_group_params_t *params,
+                                         float *d_out_dist, uint32_t *d_out_id, uint64_t *d_out_key, uint32_t *d_out_group_n,
+                                         uint32_t *d_out_n, uint32_t *d_out_fetched);
+rq_status rq_group_results(const rq_index *idx, const float *dist, const uint32_t *id, const uint32_t *cnt, uint32_t nq, const char *column,
+                           const rq_group_params_t *params, float *out_dist, uint32_t *out_id, uint64_t *out_key, uint32_t *out_group_n,
+                           uint32_t *out_n);
+rq_status rq_group_results_device(const rq_index *idx, const float *d_dist, const uint32_t *d_id, const uint32_t *d_cnt, uint32_t nq,
+                                  const char *column, const rq_group_params_t *params, float *d_out_dist, uint32_t *d_out_id,
+                                  uint64_t *d_out_key, uint32_t *d_out_group_n, uint32_t *d_out_n);
+rq_status rq_last_group_stats(rq_group_stats_t *out);
 
 /* ---- merge two indexes, extract a sub-index ------------------------------------------------------------------------------ */
 /* Both work on stored rows as they stand: nothing is rotated, assigned, quantised -- or, on a cosine or inner-product index,

@@ -44,6 +44,8 @@ EXPORTS = [
     "rq_attr_create", "rq_attr_drop", "rq_attr_count", "rq_attr_info", "rq_attr_index", "rq_attr_set", "rq_attr_set_device",
     "rq_attr_get", "rq_attr_get_device", "rq_attr_get_array", "rq_filter_create_where", "rq_last_where_stats",
     "rq_filter_combine", "rq_filter_id_bits", "rq_filter_ids_device",
+    "rq_query_batch_grouped", "rq_query_batch_grouped_device", "rq_exact_search_grouped", "rq_exact_search_grouped_device",
+    "rq_group_results", "rq_group_results_device", "rq_last_group_stats",
 ]
 
 
@@ -227,6 +229,26 @@ class WhereStatsT(_Sized):
                 ("bytes_read", C.c_uint64), ("ms_eval", C.c_float), ("ms_finish", C.c_float)]
 
 
+class GroupParamsT(_Sized):
+    """rq_group_params_t: topk groups of at most group_size rows, out of `fetch` candidates per query."""
+    _fields_ = [("struct_size", C.c_uint32), ("topk", C.c_uint32), ("group_size", C.c_uint32), ("fetch", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class GroupStatsT(_Sized):
+    """rq_group_stats_t: the calling thread's last grouped call."""
+    _fields_ = [("struct_size", C.c_uint32), ("fetch", C.c_uint32), ("ms_source", C.c_float), ("ms_group", C.c_float),
+                ("candidates", C.c_uint64), ("absent", C.c_uint64), ("kept", C.c_uint64), ("groups", C.c_uint64),
+                ("directory_built", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
+GROUP_MAX_FETCH = 2048   # RQ_MAX_TOPK: the most candidates per query a grouped call takes
+
+
+def default_group_fetch(topk: int, group_size: int) -> int:
+    """fetch=None of the grouped calls: min(2048, max(64, 4 * topk * group_size)) -- a default, not a guarantee."""
+    return min(GROUP_MAX_FETCH, max(64, 4 * int(topk) * int(group_size)))
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", CSRC] + (["-B"] if force else [])
@@ -397,6 +419,13 @@ def lib():
         "rq_filter_combine": (i32, [vp, vp, vp, u32, pp]),
         "rq_filter_id_bits": (i32, [vp, u32p, u64, C.c_int]),
         "rq_filter_ids_device": (i32, [vp, u32p, u64, C.POINTER(u64)]),
+        "rq_query_batch_grouped": (i32, [vp, vp, f32p, u32, u32, u32, C.c_int, C.c_char_p, C.POINTER(GroupParamsT), f32p, u32p, u64p, u32p, u32p, u32p]),
+        "rq_query_batch_grouped_device": (i32, [vp, vp, f32p, u32, u32, u32, C.c_int, C.c_char_p, C.POINTER(GroupParamsT), f32p, u32p, u64p, u32p, u32p, u32p]),
+        "rq_exact_search_grouped": (i32, [vp, vp, f32p, u32, u32, C.POINTER(ExactParamsT), C.c_char_p, C.POINTER(GroupParamsT), f32p, u32p, u64p, u32p, u32p, u32p]),
+        "rq_exact_search_grouped_device": (i32, [vp, vp, f32p, u32, u32, C.POINTER(ExactParamsT), C.c_char_p, C.POINTER(GroupParamsT), f32p, u32p, u64p, u32p, u32p, u32p]),
+        "rq_group_results": (i32, [vp, f32p, u32p, u32p, u32, C.c_char_p, C.POINTER(GroupParamsT), f32p, u32p, u64p, u32p, u32p]),
+        "rq_group_results_device": (i32, [vp, f32p, u32p, u32p, u32, C.c_char_p, C.POINTER(GroupParamsT), f32p, u32p, u64p, u32p, u32p]),
+        "rq_last_group_stats": (i32, [C.POINTER(GroupStatsT)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the .so lacks a declared symbol

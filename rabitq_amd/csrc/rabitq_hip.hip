@@ -37,6 +37,7 @@
 #include "kernels_relayout.h"
 #include "kernels_directory.h"
 #include "kernels_attr.h"
+#include "kernels_group.h"
 
 #include "kernel_shapes.h"
 #include "host_state.h"
@@ -55,6 +56,7 @@
 #include "host_train.h"
 #include "host_directory.h"
 #include "host_attr.h"
+#include "host_group.h"
 
 // ------------------------------------------------------------------------------------------------
 // extern "C"
@@ -1220,6 +1222,64 @@ rq_status rq_filter_id_bits(const rq_filter *f, uint32_t *bits, uint64_t nbits, 
 }
 rq_status rq_filter_ids_device(const rq_filter *f, uint32_t *d_out_ids, uint64_t cap, uint64_t *out_count) {
     return by_id_done(filter_ids_device(f, d_out_ids, cap, out_count));
+}
+
+// ---- grouped search (host_group.h): at most group_size rows per value of a column, the topk nearest values ----
+static GroupIn group_in_query(const rq_filter *filter, const float *q, uint32_t len, uint32_t probe, int heuristic_rank) {
+    GroupIn in;
+    in.src = GROUP_SRC_QUERY, in.filter = filter, in.q = q, in.len = len, in.probe = probe, in.heuristic = heuristic_rank;
+    return in;
+}
+static GroupIn group_in_exact(const rq_filter *filter, const float *q, uint32_t len, const rq_exact_params_t *exact) {
+    GroupIn in;
+    in.src = GROUP_SRC_EXACT, in.filter = filter, in.q = q, in.len = len, in.exact = exact;
+    return in;
+}
+static GroupIn group_in_results(const float *dist, const uint32_t *id, const uint32_t *cnt) {
+    GroupIn in;
+    in.src = GROUP_SRC_RESULTS, in.dist = dist, in.id = id, in.cnt = cnt;
+    return in;
+}
+rq_status rq_query_batch_grouped(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len, uint32_t probe,
+                                 int heuristic_rank, const char *column, const rq_group_params_t *params, float *out_dist, uint32_t *out_id,
+                                 uint64_t *out_key, uint32_t *out_group_n, uint32_t *out_n, uint32_t *out_fetched) {
+    return by_id_done(group_host(idx, group_in_query(filter, queries, len, probe, heuristic_rank), nq, column, params,
+                                 GroupOut{out_dist, out_id, out_key, out_group_n, out_n, out_fetched}));
+}
+rq_status rq_query_batch_grouped_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
+                                        uint32_t probe, int heuristic_rank, const char *column, const rq_group_params_t *params,
+                                        float *d_out_dist, uint32_t *d_out_id, uint64_t *d_out_key, uint32_t *d_out_group_n, uint32_t *d_out_n,
+                                        uint32_t *d_out_fetched) {
+    return by_id_done(group_device(idx, group_in_query(filter, d_queries, len, probe, heuristic_rank), nq, column, params,
+                                   GroupOut{d_out_dist, d_out_id, d_out_key, d_out_group_n, d_out_n, d_out_fetched}));
+}
+rq_status rq_exact_search_grouped(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len,
+                                  const rq_exact_params_t *exact, const char *column, const rq_group_params_t *params, float *out_dist,
+                                  uint32_t *out_id, uint64_t *out_key, uint32_t *out_group_n, uint32_t *out_n, uint32_t *out_fetched) {
+    return by_id_done(group_host(idx, group_in_exact(filter, queries, len, exact), nq, column, params,
+                                 GroupOut{out_dist, out_id, out_key, out_group_n, out_n, out_fetched}));
+}
+rq_status rq_exact_search_grouped_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
+                                         const rq_exact_params_t *exact, const char *column, const rq_group_params_t *params,
+                                         float *d_out_dist, uint32_t *d_out_id, uint64_t *d_out_key, uint32_t *d_out_group_n,
+                                         uint32_t *d_out_n, uint32_t *d_out_fetched) {
+    return by_id_done(group_device(idx, group_in_exact(filter, d_queries, len, exact), nq, column, params,
+                                   GroupOut{d_out_dist, d_out_id, d_out_key, d_out_group_n, d_out_n, d_out_fetched}));
+}
+rq_status rq_group_results(const rq_index *idx, const float *dist, const uint32_t *id, const uint32_t *cnt, uint32_t nq, const char *column,
+                           const rq_group_params_t *params, float *out_dist, uint32_t *out_id, uint64_t *out_key, uint32_t *out_group_n,
+                           uint32_t *out_n) {
+    return by_id_done(group_host(idx, group_in_results(dist, id, cnt), nq, column, params, GroupOut{out_dist, out_id, out_key, out_group_n, out_n, nullptr}));
+}
+rq_status rq_group_results_device(const rq_index *idx, const float *d_dist, const uint32_t *d_id, const uint32_t *d_cnt, uint32_t nq,
+                                  const char *column, const rq_group_params_t *params, float *d_out_dist, uint32_t *d_out_id,
+                                  uint64_t *d_out_key, uint32_t *d_out_group_n, uint32_t *d_out_n) {
+    return by_id_done(group_device(idx, group_in_results(d_dist, d_id, d_cnt), nq, column, params,
+                                   GroupOut{d_out_dist, d_out_id, d_out_key, d_out_group_n, d_out_n, nullptr}));
+}
+rq_status rq_last_group_stats(rq_group_stats_t *out) {
+    if (!out) return fail(RQ_ERR_INVALID, "null argument");
+    return copy_out_sized(out, g_group_stats);
 }
 
 rq_status rq_query(const rq_index *idx, const float *query, uint32_t len, uint32_t probe, uint32_t topk,

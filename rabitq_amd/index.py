@@ -264,6 +264,19 @@ class RangeResult:
             pass
 
 
+class GroupedResult:
+    """What a host-form grouped call returns.  dist / ids: B x topk x group_size, group-major, padded with NaN / 0xFFFFFFFF; keys
+    (the column's dtype) and group_counts (rows kept per group): B x topk, padded with 0; counts: groups per query; fetched:
+    candidates the source call gave per query (None from group_results)."""
+    __slots__ = ("dist", "ids", "keys", "group_counts", "counts", "fetched")
+
+    def __init__(self, dist, ids, keys, group_counts, counts, fetched):
+        self.dist, self.ids, self.keys, self.group_counts, self.counts, self.fetched = dist, ids, keys, group_counts, counts, fetched
+
+    def __repr__(self):
+        return f"GroupedResult(queries={self.counts.size}, topk={self.keys.shape[1]}, group_size={self.ids.shape[2]})"
+
+
 class RaBitQ:
     """Device-resident RaBitQ index.  Construct with `from_path`, `build`, `load_from_dir` or
     `from_arrays`; query with `query` (one vector, like the crate) or `query_batch`."""
@@ -943,6 +956,107 @@ class RaBitQ:
         """The calling thread's last by-id call (include/rabitq_hip.h: rq_by_id_stats_t); form as "dense" / "hash"."""
         return last_by_id_stats()
 
+    # ---- grouped search: at most group_size rows per value of a column, the topk nearest values (rq_*_grouped, rq_group_results) ----
+    @staticmethod
+    def _group_params(topk, group_size, fetch):
+        f = _lib.default_group_fetch(topk, group_size) if fetch is None else int(fetch)
+        return _lib.GroupParamsT(topk=int(topk), group_size=int(group_size), fetch=f, flags=0)
+
+    def _grouped_host(self, call, B, prm, group_by, with_fetched):
+        """The outputs of a host-form grouped call, made, filled by call(addresses...) and wrapped."""
+        t = self._attr(group_by)
+        cells = (B, max(prm.topk, 1), max(prm.group_size, 1))
+        d = np.full(cells, np.nan, dtype=np.float32)
+        ids = np.full(cells, 0xFFFFFFFF, dtype=np.uint32)
+        keys = np.zeros(cells[:2], dtype=np.uint64)
+        gn = np.zeros(cells[:2], dtype=np.uint32)
+        cnt = np.zeros(B, dtype=np.uint32)
+        fetched = np.zeros(B, dtype=np.uint32) if with_fetched else None
+        st = call(_addr(d), _addr(ids), _addr(keys), _addr(gn), _addr(cnt), *([_addr(fetched)] if with_fetched else []))
+        if st != _lib.RQ_ERR_EMPTY:
+            check(st)
+        if t.elem_bytes == 4:
+            keys = keys.astype(np.uint32)   # (the u64 image of a 4-byte value is zero-extended)
+        return GroupedResult(d, ids, keys.view(t.dtype), gn, cnt, fetched)
+
+    def query_batch_grouped(self, queries, probe: int, topk: int, group_by: str, group_size: int = 1, fetch=None,
+                            heuristic_rank: bool = False, filter: Filter = None) -> "GroupedResult":
+        """The topk nearest VALUES of the integer column `group_by`, at most group_size rows each, out of what query_batch returns
+        at topk = fetch -- grouped on the GPU, nothing travels to the host in between.  Groups come in order of their nearest row,
+        rows inside a group ascending by (distance, id).  fetch=None means min(2048, max(64, 4 * topk * group_size)): a default, not
+        a guarantee -- result.fetched[b] == fetch says query b may have more to give (raise fetch)."""
+        q = _f32(queries)
+        if q.ndim != 2:
+            raise _lib.RabitqError(-1, "queries must be 2-D")
+        prm = self._group_params(topk, group_size, fetch)
+        return self._grouped_host(lambda *out: lib().rq_query_batch_grouped(
+            self._h, _fh(filter), _addr(q), q.shape[0], q.shape[1], probe, int(heuristic_rank), group_by.encode(), C.byref(prm), *out),
+            q.shape[0], prm, group_by, True)
+
+    def exact_search_grouped(self, queries, topk: int, group_by: str, group_size: int = 1, fetch=None, filter: Filter = None,
+                             params=None) -> "GroupedResult":
+        """query_batch_grouped over exact_search at topk = fetch.  Where result.fetched[b] < fetch the answer is the true grouped
+        answer over all admitted rows; with group_size == 1, counts[b] == topk proves it too."""
+        q = _f32(queries)
+        if q.ndim != 2:
+            raise _lib.RabitqError(-1, "queries must be 2-D")
+        prm = self._group_params(topk, group_size, fetch)
+        ex = self._exact_params(params)
+        return self._grouped_host(lambda *out: lib().rq_exact_search_grouped(
+            self._h, _fh(filter), _addr(q), q.shape[0], q.shape[1], C.byref(ex) if ex is not None else None, group_by.encode(),
+            C.byref(prm), *out), q.shape[0], prm, group_by, True)
+
+    def group_results(self, dist, ids, counts, topk: int, group_by: str, group_size: int = 1) -> "GroupedResult":
+        """The selection alone over result rows the caller has (dist / ids B x fetch, counts B; fetch = their width): those of
+        tickets, the adaptive call, neighbours_of or the sharded step.  The order inside a row does not matter; an id without a
+        live row is skipped (last_group_stats()["absent"])."""
+        d = np.ascontiguousarray(dist, dtype=np.float32)
+        i = self._id_list(ids)
+        c = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        if d.ndim != 2 or i.shape != d.shape or c.size != d.shape[0]:
+            raise _lib.RabitqError(-1, "dist and ids must be B x fetch and counts B")
+        prm = self._group_params(topk, group_size, d.shape[1])
+        return self._grouped_host(lambda *out: lib().rq_group_results(
+            self._h, _addr(d), _addr(i), _addr(c), d.shape[0], group_by.encode(), C.byref(prm), *out), d.shape[0], prm, group_by, False)
+
+    def query_batch_grouped_device(self, q_ptr: int, nq: int, length: int, probe: int, topk: int, group_by: str, out_dist_ptr: int,
+                                   out_id_ptr: int, out_key_ptr: int, out_group_n_ptr: int, out_n_ptr: int, out_fetched_ptr: int = 0,
+                                   group_size: int = 1, fetch=None, heuristic_rank: bool = False, filter: Filter = None) -> None:
+        """query_batch_grouped with queries and outputs in device memory (raw addresses; dist / ids nq x topk x group_size, keys u64
+        and group counts nq x topk, counts and fetched nq; fetched 0 = not wanted)."""
+        prm = self._group_params(topk, group_size, fetch)
+        st = lib().rq_query_batch_grouped_device(self._h, _fh(filter), C.c_void_p(q_ptr), nq, length, probe, int(heuristic_rank),
+                                                 group_by.encode(), C.byref(prm), C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr),
+                                                 C.c_void_p(out_key_ptr), C.c_void_p(out_group_n_ptr), C.c_void_p(out_n_ptr),
+                                                 C.c_void_p(out_fetched_ptr))
+        if st != _lib.RQ_ERR_EMPTY:
+            check(st)
+
+    def exact_search_grouped_device(self, q_ptr: int, nq: int, length: int, topk: int, group_by: str, out_dist_ptr: int, out_id_ptr: int,
+                                    out_key_ptr: int, out_group_n_ptr: int, out_n_ptr: int, out_fetched_ptr: int = 0, group_size: int = 1,
+                                    fetch=None, filter: Filter = None, params=None) -> None:
+        """exact_search_grouped with queries and outputs in device memory (raw addresses, as query_batch_grouped_device)."""
+        prm = self._group_params(topk, group_size, fetch)
+        ex = self._exact_params(params)
+        check(lib().rq_exact_search_grouped_device(self._h, _fh(filter), C.c_void_p(q_ptr), nq, length,
+                                                   C.byref(ex) if ex is not None else None, group_by.encode(), C.byref(prm),
+                                                   C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr), C.c_void_p(out_key_ptr),
+                                                   C.c_void_p(out_group_n_ptr), C.c_void_p(out_n_ptr), C.c_void_p(out_fetched_ptr)))
+
+    def group_results_device(self, dist_ptr: int, id_ptr: int, cnt_ptr: int, nq: int, fetch: int, topk: int, group_by: str,
+                             out_dist_ptr: int, out_id_ptr: int, out_key_ptr: int, out_group_n_ptr: int, out_n_ptr: int,
+                             group_size: int = 1) -> None:
+        """group_results with the rows (stride fetch) and outputs in device memory (raw addresses)."""
+        prm = self._group_params(topk, group_size, fetch)
+        check(lib().rq_group_results_device(self._h, C.c_void_p(dist_ptr), C.c_void_p(id_ptr), C.c_void_p(cnt_ptr), nq, group_by.encode(),
+                                            C.byref(prm), C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr), C.c_void_p(out_key_ptr),
+                                            C.c_void_p(out_group_n_ptr), C.c_void_p(out_n_ptr)))
+
+    @staticmethod
+    def last_group_stats() -> dict:
+        """The calling thread's last grouped call (include/rabitq_hip.h: rq_group_stats_t)."""
+        return last_group_stats()
+
     @staticmethod
     def _recall_of(ids, cnt, exact_ids, exact_cnt) -> float:
         """mean over the queries with a non-empty exact answer of |query ids n exact ids| / exact count"""
@@ -1379,6 +1493,13 @@ def last_where_stats() -> dict:
     st = _lib.WhereStatsT()
     check(lib().rq_last_where_stats(C.byref(st)))
     return {name: getattr(st, name) for name, _ in _lib.WhereStatsT._fields_ if name != "struct_size"}
+
+
+def last_group_stats() -> dict:
+    """The calling thread's last grouped call (include/rabitq_hip.h: rq_last_group_stats)."""
+    st = _lib.GroupStatsT()
+    check(lib().rq_last_group_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _lib.GroupStatsT._fields_ if name not in ("struct_size", "reserved0")}
 
 
 def calculate_recall(truth, res, topk: int) -> float:
