@@ -53,7 +53,8 @@ def build(rq, n, seed=500, **kw):
 
 
 def values_by_id(n, seed=1):
-    """{column: (dtype, values by id 0 .. n - 1)}: small ranges so that every op selects something, and the edge values."""
+    """{column: (dtype, values by id 0 .. n - 1)}: small ranges so that every op selects something, and the edge values.  One column of
+    each type, and two more 4-byte ones (v, w) for a predicate over five columns none of which is 8 bytes wide."""
     rng = np.random.default_rng(seed)
     u = rng.integers(0, 50, size=n).astype(np.uint32)
     i = rng.integers(-20, 20, size=n).astype(np.int32)
@@ -64,7 +65,12 @@ def values_by_id(n, seed=1):
                       (U, [2**64 - 1, 2**63, 2**32, 1]), (I, [-1, -2**63, 2**63 - 1, 2**32 + 1])):
         at = rng.choice(n, size=min(n, 3 * len(edge)), replace=False)
         arr[at] = np.array(edge * 3, dtype=arr.dtype)[:at.size]
-    return {"u": ("u32", u), "i": ("i32", i), "f": ("f32", f), "U": ("u64", U), "I": ("i64", I)}
+    v = rng.integers(0, 100, size=n).astype(np.uint32)                       # (drawn last: the five columns above are what they were)
+    w = rng.integers(-3, 4, size=n).astype(np.int32)
+    for arr, edge in ((v, [0xFFFFFFFF, 0]), (w, [-2**31, 2**31 - 1])):
+        at = rng.choice(n, size=min(n, 3 * len(edge)), replace=False)
+        arr[at] = np.array(edge * 3, dtype=arr.dtype)[:at.size]
+    return {"u": ("u32", u), "i": ("i32", i), "f": ("f32", f), "U": ("u64", U), "I": ("i64", I), "v": ("u32", v), "w": ("i32", w)}
 
 
 def fill_columns(g, cols, ids):
@@ -108,7 +114,7 @@ def same_answers(g, f, y, queries, what):
 
 def predicates():
     from rabitq_amd import col
-    u, i, f, U, I = col("u"), col("i"), col("f"), col("U"), col("I")
+    u, i, f, U, I, v, w = col("u"), col("i"), col("f"), col("U"), col("I"), col("v"), col("w")
     nan = float("nan")
     return {
         "u_eq": u == 3, "u_ne": u != 3, "u_lt": u < 10, "u_le": u <= 10, "u_gt": u > 40, "u_ge": u >= 40, "u_between": u.between(5, 9),
@@ -125,6 +131,7 @@ def predicates():
         "I_le_min": I <= -2**63, "I_in": I.isin([-1, 2**63 - 1, 12345]),
         "and2": (u < 10) & (i < 0), "or_not": ~(u < 10) | (f >= 1.0), "nested": ((u == 3) | (i == -1)) & ~((f < 0.0) | (U >= 2**32)),
         "not_not": ~~(I < 0), "and3": (u < 25) & (i >= 0) & (f <= 1.0), "all5": (u < 40) & (i > -15) & (f < 3.0) & (U > 5) & (I != 0),
+        "all5_narrow": (u < 40) & (i > -15) & (f < 3.0) & (v != 3) & (w >= -2),         # where_kernel<8, false>: five 4-byte columns
         "xor": ((u < 25) & ~(i < 0)) | (~(u < 25) & (i < 0)), "none": (u < 5) & (u > 45), "every": (u < 5) | ~(u < 5),
     }
 
@@ -180,9 +187,10 @@ def test_where_stats_and_the_raw_entry(rq, big):
         assert np.array_equal(np.sort(f.ids()), np.nonzero(uv < 32)[0])
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 8191, 8192, 8193, 16385])
 def test_bitmap_tail_words(rq, n):
-    """n around the 64-position runs: the predicate's bitmap, its complement and the id list at the last words."""
+    """n around the 64-position runs: the predicate's bitmap, its complement and the id list at the last words; and around the 8192
+    positions of one block of ids(): the smallest sizes at which the id list is joined from two and from three blocks."""
     from rabitq_amd import col
     g = build(rq, n)
     g.create_attr("v", "u64", fill=2**40)
@@ -195,6 +203,8 @@ def test_bitmap_tail_words(rq, n):
             assert np.array_equal(np.sort(f.ids()), ids[keep]) and f.rows == keep.sum()
             assert np.array_equal(np.sort(nf.ids()), ids[~keep]) and nf.rows == n - keep.sum()
             assert both.rows == n and none.rows == 0 and none.ids().size == 0
+            mids = g.map_ids
+            assert np.array_equal(both.ids(), mids) and np.array_equal(f.ids(), mids[keep[mids]]) and np.array_equal(nf.ids(), mids[~keep[mids]])
             assert np.array_equal(f.id_bits(n + 3), np.concatenate([keep, [False] * 3]))
             assert np.array_equal(nf.id_bits(), (~keep)[:nf.id_bits().size]) and not (~keep)[nf.id_bits().size:].any()
     g.close()
