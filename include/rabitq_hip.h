@@ -102,7 +102,9 @@ typedef struct {
  * RQ_FILTER_*, rq_filter_combine, rq_filter_id_bits, rq_filter_ids_device; an index without columns behaves, allocates and dumps
  * exactly as before; rq_last_mutate_stats.gather_bytes counts the column bytes a relayout moves);
  * 0.16.0: grouped search, additions only -- rq_group_params_t, rq_group_stats_t, rq_query_batch_grouped*, rq_exact_search_grouped*,
- * rq_group_results*, rq_last_group_stats; no existing call, refusal or output changes.
+ * rq_group_results*, rq_last_group_stats; no existing call, refusal or output changes;
+ * 0.17.0: diverse search, additions only -- rq_diverse_params_t, rq_diverse_stats_t, rq_query_batch_diverse*, rq_exact_search_diverse*,
+ * rq_diversify_results*, rq_last_diverse_stats; no existing call, refusal or output changes.
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -1007,6 +1009,80 @@ rq_status rq_group_results_device(const rq_index *idx, const float *d_dist, cons
                                   const char *column, const rq_group_params_t *params, float *d_out_dist, uint32_t *d_out_id,
                                   uint64_t *d_out_key, uint32_t *d_out_group_n, uint32_t *d_out_n);
 rq_status rq_last_group_stats(rq_group_stats_t *out);
+
+/* ---- diverse search: the topk rows maximal marginal relevance takes out of `fetch` candidates (0.17.0, additions only) ---------- */
+/* "The topk nearest rows, but not topk copies of the same passage" (MMR), on the device: the result rows of an existing call at
+ * topk = fetch are re-selected greedily, trading a row's distance to the query against its distance to the rows already taken,
+ * without the rows travelling to the host.
+ * SOURCE.  As in grouped search: rq_query_batch_diverse runs rq_query_batch[_filtered](probe, fetch, heuristic_rank),
+ *   rq_exact_search_diverse runs rq_exact_search(fetch, exact params), both under `filter` (nullable; with removals pending and no
+ *   filter: the live filter); rq_diversify_results takes the rows from the caller (dist / id of stride fetch, cnt[b] valid entries,
+ *   a larger cnt is cut at fetch).  The order of the pairs inside a row is arbitrary and nothing depends on it.
+ * CANDIDATES.  Sort a row's cnt_b pairs ascending by the 64-bit key ord32_biased(dist) << 32 | id, the library's (distance, id)
+ *   order.  A pair whose id has no live row (rq_locate would answer RQ_POS_ABSENT) is skipped and counted in
+ *   rq_diverse_stats_t.absent; of the others, a pair whose distance is not finite is skipped and counted in .skipped.  The rest are
+ *   the candidates c_0 .. c_{m-1} in that order, place(c_j) = j.  Equal ids in a caller's row are separate candidates.
+ * PAIR DISTANCE.  D(c, s) = the engine's exact squared L2 between the STORED row of c and the row of s as rq_fetch_rows returns it
+ *   (f32, widened, dim long): bit for bit rq_rerank(prepared query = that row, position of c).  On a cosine index that is
+ *   2 - 2 cos of the two rows, on an inner-product index the distance in the augmented space -- not the metric's own score.
+ * SELECTION, greedy and sequential.  lambda = params->lambda, mu = 1.0f - lambda (f32, computed once).  Step 0 takes c_0; div(c) =
+ *   +inf for every candidate.  After taking s, every candidate not yet taken has div(c) = fminf(div(c), D(c, s)).  Step t >= 1:
+ *   score(c) = (lambda * rel(c)) - (mu * div(c)) with rel the source's distance -- two f32 multiplications and one f32 subtraction,
+ *   each rounded to nearest, never contracted; a NaN score is replaced by 0x7FC00000; the candidate not yet taken with the smallest
+ *   ord32_biased(score) << 32 | place is taken.  min(topk, m) steps.  lambda == 1 gives the source's first topk candidates in
+ *   (distance, id) order; topk == 1 gives c_0.
+ * OUTPUT, in selection order (nq x topk): out_id, out_dist (rel: the source's bits), out_div (div at the moment of selection; +inf
+ *   in slot 0); out_n[b] = rows taken.  Every slot without a row is written on every call: id 0xFFFFFFFF, dist and div NaN
+ *   (0x7FC00000).  The two query entries also write out_fetched[b] = cnt_b (nullable).  The same inputs give the same bits on every
+ *   run.
+ * LIMITS.  Refused with RQ_ERR_INVALID before a device is looked for: a null index, params or output (out_fetched excepted), a
+ *   null input with nq > 0, params->struct_size != sizeof(rq_diverse_params_t), a set bit in flags, lambda NaN or outside [0, 1].
+ *   RQ_ERR_UNSUPPORTED likewise: topk == 0, topk > fetch, fetch > 2048 (RQ_MAX_TOPK).  Then the source call's own refusals at
+ *   topk = fetch (a stale or foreign filter; the exact form on tiered and split-row indexes), and dim > 4096: the kernel holds the
+ *   taken row in LDS beside the state of 2048 candidates (16 KB + 38 KB of the 64 KB a block gets), RQ_ERR_UNSUPPORTED.
+ *   RQ_ERR_EMPTY from the source passes through with the outputs written.  nq == 0 is RQ_OK.  Accepted wherever the source call and
+ *   the by-id entries both are: every metric and row type, shards, pending removals, after any relayout, the hash directory, and
+ *   tiered and split-row indexes for the approximate source and rq_diversify_results.  rq_metrics counts the source call.  _device
+ *   forms: every pointer but params in device memory; they return with their outputs complete.  No relayout may run during a call.
+ * rq_last_diverse_stats: the calling thread's last diverse call. */
+typedef struct {
+    uint32_t struct_size; /* sizeof(rq_diverse_params_t) */
+    uint32_t topk;        /* rows per query */
+    uint32_t fetch;       /* candidates per query the source is asked for */
+    float lambda;         /* 1: relevance alone ... 0: diversity alone */
+    uint32_t flags;       /* 0 */
+} rq_diverse_params_t;
+typedef struct {
+    uint32_t struct_size;     /* set to sizeof(rq_diverse_stats_t) before the call */
+    uint32_t fetch;
+    float ms_source;          /* wall ms of the source call (0: rq_diversify_results) */
+    float ms_select;          /* device ms of the selection kernel (HIP events) */
+    uint64_t candidates;      /* sum of cnt_b */
+    uint64_t absent;          /* pairs without a live row */
+    uint64_t skipped;         /* pairs with a live row whose distance is not finite */
+    uint64_t taken;           /* sum of out_n */
+    uint64_t pair_distances;  /* evaluations of D */
+    uint32_t directory_built; /* 1: this call made the id directory */
+    uint32_t reserved0;
+} rq_diverse_stats_t;
+rq_status rq_query_batch_diverse(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len, uint32_t probe,
+                                 int heuristic_rank, const rq_diverse_params_t *params, float *out_dist, uint32_t *out_id, float *out_div,
+                                 uint32_t *out_n, uint32_t *out_fetched);
+rq_status rq_query_batch_diverse_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
+                                        uint32_t probe, int heuristic_rank, const rq_diverse_params_t *params, float *d_out_dist,
+                                        uint32_t *d_out_id, float *d_out_div, uint32_t *d_out_n, uint32_t *d_out_fetched);
+rq_status rq_exact_search_diverse(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len,
+                                  const rq_exact_params_t *exact, const rq_diverse_params_t *params, float *out_dist, uint32_t *out_id,
+                                  float *out_div, uint32_t *out_n, uint32_t *out_fetched);
+rq_status rq_exact_search_diverse_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
+                                         const rq_exact_params_t *exact, const rq_diverse_params_t *params, float *d_out_dist,
+                                         uint32_t *d_out_id, float *d_out_div, uint32_t *d_out_n, uint32_t *d_out_fetched);
+rq_status rq_diversify_results(const rq_index *idx, const float *dist, const uint32_t *id, const uint32_t *cnt, uint32_t nq,
+                               const rq_diverse_params_t *params, float *out_dist, uint32_t *out_id, float *out_div, uint32_t *out_n);
+rq_status rq_diversify_results_device(const rq_index *idx, const float *d_dist, const uint32_t *d_id, const uint32_t *d_cnt, uint32_t nq,
+                                      const rq_diverse_params_t *params, float *d_out_dist, uint32_t *d_out_id, float *d_out_div,
+                                      uint32_t *d_out_n);
+rq_status rq_last_diverse_stats(rq_diverse_stats_t *out);
 
 /* ---- merge two indexes, extract a sub-index ------------------------------------------------------------------------------ */
 /* Both work on stored rows as they stand: nothing is rotated, assigned, quantised -- or, on a cosine or inner-product index,

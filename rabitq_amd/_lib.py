@@ -46,6 +46,8 @@ EXPORTS = [
     "rq_filter_combine", "rq_filter_id_bits", "rq_filter_ids_device",
     "rq_query_batch_grouped", "rq_query_batch_grouped_device", "rq_exact_search_grouped", "rq_exact_search_grouped_device",
     "rq_group_results", "rq_group_results_device", "rq_last_group_stats",
+    "rq_query_batch_diverse", "rq_query_batch_diverse_device", "rq_exact_search_diverse", "rq_exact_search_diverse_device",
+    "rq_diversify_results", "rq_diversify_results_device", "rq_last_diverse_stats",
 ]
 
 
@@ -249,6 +251,23 @@ def default_group_fetch(topk: int, group_size: int) -> int:
     return min(GROUP_MAX_FETCH, max(64, 4 * int(topk) * int(group_size)))
 
 
+class DiverseParamsT(_Sized):
+    """rq_diverse_params_t: the topk rows maximal marginal relevance takes out of `fetch` candidates per query."""
+    _fields_ = [("struct_size", C.c_uint32), ("topk", C.c_uint32), ("fetch", C.c_uint32), ("lambda_", C.c_float), ("flags", C.c_uint32)]
+
+
+class DiverseStatsT(_Sized):
+    """rq_diverse_stats_t: the calling thread's last diverse call."""
+    _fields_ = [("struct_size", C.c_uint32), ("fetch", C.c_uint32), ("ms_source", C.c_float), ("ms_select", C.c_float),
+                ("candidates", C.c_uint64), ("absent", C.c_uint64), ("skipped", C.c_uint64), ("taken", C.c_uint64),
+                ("pair_distances", C.c_uint64), ("directory_built", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
+def default_diverse_fetch(topk: int) -> int:
+    """fetch=None of the diverse calls: min(2048, max(64, 4 * topk)) -- a default, not a guarantee."""
+    return min(GROUP_MAX_FETCH, max(64, 4 * int(topk)))
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", CSRC] + (["-B"] if force else [])
@@ -426,6 +445,13 @@ def lib():
         "rq_group_results": (i32, [vp, f32p, u32p, u32p, u32, C.c_char_p, C.POINTER(GroupParamsT), f32p, u32p, u64p, u32p, u32p]),
         "rq_group_results_device": (i32, [vp, f32p, u32p, u32p, u32, C.c_char_p, C.POINTER(GroupParamsT), f32p, u32p, u64p, u32p, u32p]),
         "rq_last_group_stats": (i32, [C.POINTER(GroupStatsT)]),
+        "rq_query_batch_diverse": (i32, [vp, vp, f32p, u32, u32, u32, C.c_int, C.POINTER(DiverseParamsT), f32p, u32p, f32p, u32p, u32p]),
+        "rq_query_batch_diverse_device": (i32, [vp, vp, f32p, u32, u32, u32, C.c_int, C.POINTER(DiverseParamsT), f32p, u32p, f32p, u32p, u32p]),
+        "rq_exact_search_diverse": (i32, [vp, vp, f32p, u32, u32, C.POINTER(ExactParamsT), C.POINTER(DiverseParamsT), f32p, u32p, f32p, u32p, u32p]),
+        "rq_exact_search_diverse_device": (i32, [vp, vp, f32p, u32, u32, C.POINTER(ExactParamsT), C.POINTER(DiverseParamsT), f32p, u32p, f32p, u32p, u32p]),
+        "rq_diversify_results": (i32, [vp, f32p, u32p, u32p, u32, C.POINTER(DiverseParamsT), f32p, u32p, f32p, u32p]),
+        "rq_diversify_results_device": (i32, [vp, f32p, u32p, u32p, u32, C.POINTER(DiverseParamsT), f32p, u32p, f32p, u32p]),
+        "rq_last_diverse_stats": (i32, [C.POINTER(DiverseStatsT)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the .so lacks a declared symbol

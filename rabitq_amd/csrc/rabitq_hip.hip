@@ -38,6 +38,7 @@
 #include "kernels_directory.h"
 #include "kernels_attr.h"
 #include "kernels_group.h"
+#include "kernels_diverse.h"
 
 #include "kernel_shapes.h"
 #include "host_state.h"
@@ -57,6 +58,7 @@
 #include "host_directory.h"
 #include "host_attr.h"
 #include "host_group.h"
+#include "host_diverse.h"
 
 // ------------------------------------------------------------------------------------------------
 // extern "C"
@@ -1280,6 +1282,44 @@ rq_status rq_group_results_device(const rq_index *idx, const float *d_dist, cons
 rq_status rq_last_group_stats(rq_group_stats_t *out) {
     if (!out) return fail(RQ_ERR_INVALID, "null argument");
     return copy_out_sized(out, g_group_stats);
+}
+
+// ---- diverse search (host_diverse.h): the topk rows maximal marginal relevance takes out of `fetch` candidates ----
+rq_status rq_query_batch_diverse(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len, uint32_t probe,
+                                 int heuristic_rank, const rq_diverse_params_t *params, float *out_dist, uint32_t *out_id, float *out_div,
+                                 uint32_t *out_n, uint32_t *out_fetched) {
+    return by_id_done(diverse_host(idx, group_in_query(filter, queries, len, probe, heuristic_rank), nq, params,
+                                   DiverseOut{out_dist, out_id, out_div, out_n, out_fetched}));
+}
+rq_status rq_query_batch_diverse_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
+                                        uint32_t probe, int heuristic_rank, const rq_diverse_params_t *params, float *d_out_dist,
+                                        uint32_t *d_out_id, float *d_out_div, uint32_t *d_out_n, uint32_t *d_out_fetched) {
+    return by_id_done(diverse_device(idx, group_in_query(filter, d_queries, len, probe, heuristic_rank), nq, params,
+                                     DiverseOut{d_out_dist, d_out_id, d_out_div, d_out_n, d_out_fetched}));
+}
+rq_status rq_exact_search_diverse(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len,
+                                  const rq_exact_params_t *exact, const rq_diverse_params_t *params, float *out_dist, uint32_t *out_id,
+                                  float *out_div, uint32_t *out_n, uint32_t *out_fetched) {
+    return by_id_done(diverse_host(idx, group_in_exact(filter, queries, len, exact), nq, params, DiverseOut{out_dist, out_id, out_div, out_n, out_fetched}));
+}
+rq_status rq_exact_search_diverse_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
+                                         const rq_exact_params_t *exact, const rq_diverse_params_t *params, float *d_out_dist,
+                                         uint32_t *d_out_id, float *d_out_div, uint32_t *d_out_n, uint32_t *d_out_fetched) {
+    return by_id_done(diverse_device(idx, group_in_exact(filter, d_queries, len, exact), nq, params,
+                                     DiverseOut{d_out_dist, d_out_id, d_out_div, d_out_n, d_out_fetched}));
+}
+rq_status rq_diversify_results(const rq_index *idx, const float *dist, const uint32_t *id, const uint32_t *cnt, uint32_t nq,
+                               const rq_diverse_params_t *params, float *out_dist, uint32_t *out_id, float *out_div, uint32_t *out_n) {
+    return by_id_done(diverse_host(idx, group_in_results(dist, id, cnt), nq, params, DiverseOut{out_dist, out_id, out_div, out_n, nullptr}));
+}
+rq_status rq_diversify_results_device(const rq_index *idx, const float *d_dist, const uint32_t *d_id, const uint32_t *d_cnt, uint32_t nq,
+                                      const rq_diverse_params_t *params, float *d_out_dist, uint32_t *d_out_id, float *d_out_div,
+                                      uint32_t *d_out_n) {
+    return by_id_done(diverse_device(idx, group_in_results(d_dist, d_id, d_cnt), nq, params, DiverseOut{d_out_dist, d_out_id, d_out_div, d_out_n, nullptr}));
+}
+rq_status rq_last_diverse_stats(rq_diverse_stats_t *out) {
+    if (!out) return fail(RQ_ERR_INVALID, "null argument");
+    return copy_out_sized(out, g_diverse_stats);
 }
 
 rq_status rq_query(const rq_index *idx, const float *query, uint32_t len, uint32_t probe, uint32_t topk,

@@ -264,6 +264,19 @@ class RangeResult:
             pass
 
 
+class DiverseResult:
+    """What a host-form diverse call returns.  dist / ids / div: B x topk in SELECTION order, padded with NaN / 0xFFFFFFFF / NaN
+    (dist: the source's distance; div: the smallest pair distance to the rows taken before, +inf for the first); counts: rows taken
+    per query; fetched: candidates the source call gave per query (None from diversify_results)."""
+    __slots__ = ("dist", "ids", "div", "counts", "fetched")
+
+    def __init__(self, dist, ids, div, counts, fetched):
+        self.dist, self.ids, self.div, self.counts, self.fetched = dist, ids, div, counts, fetched
+
+    def __repr__(self):
+        return f"DiverseResult(queries={self.counts.size}, topk={self.ids.shape[1]})"
+
+
 class GroupedResult:
     """What a host-form grouped call returns.  dist / ids: B x topk x group_size, group-major, padded with NaN / 0xFFFFFFFF; keys
     (the column's dtype) and group_counts (rows kept per group): B x topk, padded with 0; counts: groups per query; fetched:
@@ -1057,6 +1070,101 @@ class RaBitQ:
         """The calling thread's last grouped call (include/rabitq_hip.h: rq_group_stats_t)."""
         return last_group_stats()
 
+    # ---- diverse search: the topk rows MMR takes out of `fetch` candidates (rq_*_diverse, rq_diversify_results) ----
+    @staticmethod
+    def _diverse_params(topk, lam, fetch):
+        f = _lib.default_diverse_fetch(topk) if fetch is None else int(fetch)
+        return _lib.DiverseParamsT(topk=int(topk), fetch=f, lambda_=float(lam), flags=0)
+
+    @staticmethod
+    def _diverse_host(call, B, prm, with_fetched):
+        """The outputs of a host-form diverse call, made, filled by call(addresses...) and wrapped."""
+        cells = (B, max(prm.topk, 1))
+        d = np.full(cells, np.nan, dtype=np.float32)
+        ids = np.full(cells, 0xFFFFFFFF, dtype=np.uint32)
+        div = np.full(cells, np.nan, dtype=np.float32)
+        cnt = np.zeros(B, dtype=np.uint32)
+        fetched = np.zeros(B, dtype=np.uint32) if with_fetched else None
+        st = call(_addr(d), _addr(ids), _addr(div), _addr(cnt), *([_addr(fetched)] if with_fetched else []))
+        if st != _lib.RQ_ERR_EMPTY:
+            check(st)
+        return DiverseResult(d, ids, div, cnt, fetched)
+
+    def query_batch_diverse(self, queries, probe: int, topk: int, lam: float = 0.5, fetch=None, heuristic_rank: bool = False,
+                            filter: Filter = None) -> "DiverseResult":
+        """The topk rows that maximal marginal relevance takes, greedily, out of what query_batch returns at topk = fetch --
+        selected on the GPU, no row travels to the host.  Each step takes the candidate with the smallest
+        lam * distance - (1 - lam) * (smallest pair distance to the rows already taken); lam = 1 is the plain call's order, lam = 0
+        diversity alone.  The pair distance is the engine's squared L2 between STORED rows (2 - 2 cos on a cosine index, the
+        augmented space's distance on an inner-product index).  fetch=None means min(2048, max(64, 4 * topk)): a default, not a
+        guarantee -- the selection sees no row beyond the first `fetch`."""
+        q = _f32(queries)
+        if q.ndim != 2:
+            raise _lib.RabitqError(-1, "queries must be 2-D")
+        prm = self._diverse_params(topk, lam, fetch)
+        return self._diverse_host(lambda *out: lib().rq_query_batch_diverse(
+            self._h, _fh(filter), _addr(q), q.shape[0], q.shape[1], probe, int(heuristic_rank), C.byref(prm), *out), q.shape[0], prm, True)
+
+    def exact_search_diverse(self, queries, topk: int, lam: float = 0.5, fetch=None, filter: Filter = None, params=None) -> "DiverseResult":
+        """query_batch_diverse over exact_search at topk = fetch."""
+        q = _f32(queries)
+        if q.ndim != 2:
+            raise _lib.RabitqError(-1, "queries must be 2-D")
+        prm = self._diverse_params(topk, lam, fetch)
+        ex = self._exact_params(params)
+        return self._diverse_host(lambda *out: lib().rq_exact_search_diverse(
+            self._h, _fh(filter), _addr(q), q.shape[0], q.shape[1], C.byref(ex) if ex is not None else None, C.byref(prm), *out),
+            q.shape[0], prm, True)
+
+    def diversify_results(self, dist, ids, counts, topk: int, lam: float = 0.5) -> "DiverseResult":
+        """The selection alone over result rows the caller has (dist / ids B x fetch, counts B; fetch = their width).  The order
+        inside a row does not matter; an id without a live row is skipped (last_diverse_stats()["absent"]), and so is a distance
+        that is not finite (["skipped"])."""
+        d = np.ascontiguousarray(dist, dtype=np.float32)
+        i = self._id_list(ids)
+        c = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        if d.ndim != 2 or i.shape != d.shape or c.size != d.shape[0]:
+            raise _lib.RabitqError(-1, "dist and ids must be B x fetch and counts B")
+        prm = self._diverse_params(topk, lam, d.shape[1])
+        return self._diverse_host(lambda *out: lib().rq_diversify_results(
+            self._h, _addr(d), _addr(i), _addr(c), d.shape[0], C.byref(prm), *out), d.shape[0], prm, False)
+
+    def query_batch_diverse_device(self, q_ptr: int, nq: int, length: int, probe: int, topk: int, out_dist_ptr: int, out_id_ptr: int,
+                                   out_div_ptr: int, out_n_ptr: int, out_fetched_ptr: int = 0, lam: float = 0.5, fetch=None,
+                                   heuristic_rank: bool = False, filter: Filter = None) -> None:
+        """query_batch_diverse with queries and outputs in device memory (raw addresses; dist / ids / div nq x topk, counts and
+        fetched nq; fetched 0 = not wanted)."""
+        prm = self._diverse_params(topk, lam, fetch)
+        st = lib().rq_query_batch_diverse_device(self._h, _fh(filter), C.c_void_p(q_ptr), nq, length, probe, int(heuristic_rank),
+                                                 C.byref(prm), C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr), C.c_void_p(out_div_ptr),
+                                                 C.c_void_p(out_n_ptr), C.c_void_p(out_fetched_ptr))
+        if st != _lib.RQ_ERR_EMPTY:
+            check(st)
+
+    def exact_search_diverse_device(self, q_ptr: int, nq: int, length: int, topk: int, out_dist_ptr: int, out_id_ptr: int, out_div_ptr: int,
+                                    out_n_ptr: int, out_fetched_ptr: int = 0, lam: float = 0.5, fetch=None, filter: Filter = None,
+                                    params=None) -> None:
+        """exact_search_diverse with queries and outputs in device memory (raw addresses, as query_batch_diverse_device)."""
+        prm = self._diverse_params(topk, lam, fetch)
+        ex = self._exact_params(params)
+        check(lib().rq_exact_search_diverse_device(self._h, _fh(filter), C.c_void_p(q_ptr), nq, length,
+                                                   C.byref(ex) if ex is not None else None, C.byref(prm), C.c_void_p(out_dist_ptr),
+                                                   C.c_void_p(out_id_ptr), C.c_void_p(out_div_ptr), C.c_void_p(out_n_ptr),
+                                                   C.c_void_p(out_fetched_ptr)))
+
+    def diversify_results_device(self, dist_ptr: int, id_ptr: int, cnt_ptr: int, nq: int, fetch: int, topk: int, out_dist_ptr: int,
+                                 out_id_ptr: int, out_div_ptr: int, out_n_ptr: int, lam: float = 0.5) -> None:
+        """diversify_results with the rows (stride fetch) and outputs in device memory (raw addresses)."""
+        prm = self._diverse_params(topk, lam, fetch)
+        check(lib().rq_diversify_results_device(self._h, C.c_void_p(dist_ptr), C.c_void_p(id_ptr), C.c_void_p(cnt_ptr), nq, C.byref(prm),
+                                                C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr), C.c_void_p(out_div_ptr),
+                                                C.c_void_p(out_n_ptr)))
+
+    @staticmethod
+    def last_diverse_stats() -> dict:
+        """The calling thread's last diverse call (include/rabitq_hip.h: rq_diverse_stats_t)."""
+        return last_diverse_stats()
+
     @staticmethod
     def _recall_of(ids, cnt, exact_ids, exact_cnt) -> float:
         """mean over the queries with a non-empty exact answer of |query ids n exact ids| / exact count"""
@@ -1493,6 +1601,13 @@ def last_where_stats() -> dict:
     st = _lib.WhereStatsT()
     check(lib().rq_last_where_stats(C.byref(st)))
     return {name: getattr(st, name) for name, _ in _lib.WhereStatsT._fields_ if name != "struct_size"}
+
+
+def last_diverse_stats() -> dict:
+    """The calling thread's last diverse call (include/rabitq_hip.h: rq_last_diverse_stats)."""
+    st = _lib.DiverseStatsT()
+    check(lib().rq_last_diverse_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _lib.DiverseStatsT._fields_ if name not in ("struct_size", "reserved0")}
 
 
 def last_group_stats() -> dict:
