@@ -9,6 +9,9 @@
 static thread_local std::string g_err;
 static rq_status fail(rq_status s, const std::string &msg) {
     g_err = msg;
+    // a failed hipMalloc / hipHostMalloc leaves hipErrorOutOfMemory as the thread's last error (sticky on ROCm 7.2): it is reported
+    // here, once -- the hipGetLastError() check of the caller's next call must not pick it up
+    if (s == RQ_ERR_OOM) (void)hipGetLastError();
     return s;
 }
 #define HIPC(expr)                                                                                   \

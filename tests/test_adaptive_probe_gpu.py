@@ -32,12 +32,18 @@ def rq():
     from rabitq_amd import _lib
     assert os.path.exists(_lib.SO_PATH), "librabitq_hip.so must be built in-tree"
     _lib.check(_lib.lib().rq_init(0))
-    return rabitq_amd
+    yield rabitq_amd
+    # the worlds' indexes keep the workspaces of their largest calls (the 70 000-query call: tens of GB of HBM, sized by what was
+    # free): they go back with the module, not with the process -- a later module sizes an HBM tier by what is free then
+    for wd in _worlds.values():
+        wd["g"].close()
+        wd["o"].close()
+    _worlds.clear()
 
 
 def get_world(rq, oracle, name):
     """The world's GPU index, oracle index, queries (2048: the first 600 are the model test's), the oracle's coarse distances of the
-    first 600 -- built once, never changed."""
+    first 600 -- built once, never changed, closed with the module."""
     if name not in _worlds:
         x, centres, P, q, w = am.world(name, nq=2048)
         g = rq.RaBitQ.build(x, centres, P)

@@ -1688,6 +1688,21 @@ def test_streamed_builder_equals_one_shot_build(rq, oracle, d, budget):
     oidx.close()
 
 
+def test_a_failed_allocation_stays_with_its_call(rq):
+    """A builder whose pass-1 arrays cannot exist (4e9 x 1024: 512 GB of codes, more than the HBM) is refused with RQ_ERR_OOM.
+    The failed hipMalloc's error is reported by that call alone: the thread's next call -- a small normalisation, which ends
+    with a hipGetLastError() check -- succeeds and returns what it returned before."""
+    import torch
+    d = 1024
+    x = np.random.default_rng(3).standard_normal((37, d)).astype(np.float32)
+    want = rq.normalize(x)
+    cd = torch.zeros((1, d), device=torch.device("cuda", 0))
+    with pytest.raises(rq.RabitqError) as e:
+        rq.RaBitQ.builder(4_000_000_000, d, cd.data_ptr(), 1, orthogonal=np.eye(d, dtype=np.float32))
+    assert e.value.status == -8, e.value
+    assert_bits_equal(rq.normalize(x), want, "rq_normalize after a refused allocation")
+
+
 def test_fuzz_scale_slice(rq):
     """A bounded slice of tests/fuzz_scale.py (the engine against itself where the oracle cannot go): 10M vectors, hard
     distribution, batches up to 16 384 queries, 16 random knob sets against the default-knob answer, bit for bit."""
