@@ -104,7 +104,9 @@ typedef struct {
  * 0.16.0: grouped search, additions only -- rq_group_params_t, rq_group_stats_t, rq_query_batch_grouped*, rq_exact_search_grouped*,
  * rq_group_results*, rq_last_group_stats; no existing call, refusal or output changes;
  * 0.17.0: diverse search, additions only -- rq_diverse_params_t, rq_diverse_stats_t, rq_query_batch_diverse*, rq_exact_search_diverse*,
- * rq_diversify_results*, rq_last_diverse_stats; no existing call, refusal or output changes.
+ * rq_diversify_results*, rq_last_diverse_stats; no existing call, refusal or output changes;
+ * 0.18.0: multi-vector search, additions only -- RQ_MAXSIM_*, rq_maxsim_params_t, rq_maxsim_stats_t, rq_maxsim_scores*,
+ * rq_query_batch_maxsim*, rq_last_maxsim_stats; no existing call, refusal or output changes.
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -1083,6 +1085,84 @@ rq_status rq_diversify_results_device(const rq_index *idx, const float *d_dist, 
                                       const rq_diverse_params_t *params, float *d_out_dist, uint32_t *d_out_id, float *d_out_div,
                                       uint32_t *d_out_n);
 rq_status rq_last_diverse_stats(rq_diverse_stats_t *out);
+
+/* ---- multi-vector search: exact MaxSim (Chamfer) of token sets against documents of stored rows (0.18.0, additions only) -------- */
+/* Late-interaction retrieval (ColBERT, ColPali, XTR) on the device: a query is a SET of token vectors, a document a SET of stored
+ * rows, the score the sum over the query's tokens of the best match inside the document.
+ * DOCUMENTS.  S = params->doc_stride (1 .. 4096).  The document of id i is i / S; the rows of document D are the ids in
+ *   [D S, D S + S) that have a live row (rq_locate would answer a position) -- absent and lazily removed ids are simply not there.
+ *   A document without a live row is not a candidate.  No column and no postings: the id directory answers it.  S = 1 makes every
+ *   row its own document.
+ * TOKENS.  tokens: nq x params->tokens x len f32 (len as any query's raw length; params->tokens = T, 1 .. 256); n_tokens: nq u32,
+ *   or null = T everywhere; query b uses its first T_b = min(n_tokens[b], T) tokens.  Every token goes through the index's query
+ *   transform (cosine: normalised; inner product: zero-augmented), the one the plain query uses.
+ * SCORE.  d(t, x) = the engine's exact distance between the transformed token and the stored row: bit for bit rq_rerank.
+ *   chamfer(b, D) = sum over t < T_b of min over the rows x of D of d(t, x): the minimum is the value with the smallest
+ *   ord32_biased image (a total order of all f32 bit patterns), the sum runs in f32 from +0.0f in ascending t, one rounding per
+ *   addition.
+ * NaN.  A NaN distance counts as 0x7FC00000 whatever its sign and payload, and a NaN sum is written as 0x7FC00000 (out_rows > 0
+ *   tells it from a document without a row).  The reason: what a NaN operand leaves behind is the hardware's -- rq_rerank gives
+ *   0xFFC00000 on gfx950 where a CPU gives 0x7FC00000, the smallest and nearly the largest value of the order.  The consequence:
+ *   a NaN is always the LARGEST distance.  A stored row that holds a NaN never wins a token's minimum while the document has
+ *   another row (by rq_rerank's own bits its 0xFFC00000 would have won); a token that holds a NaN makes every distance, and so the
+ *   sum, 0x7FC00000.  Ascending chamfer is descending MaxSim: on a cosine index sum max cos = T_b - chamfer / 2, on an
+ *   inner-product index sum max <x, q> = (T_b S_norm + sum |q_t|^2 - chamfer) / 2 with S_norm the index's squared-norm bound.  The
+ *   same inputs give the same bits on every run; RQ_MAXSIM_NO_PREFILTER (every pair on the exact path) gives the same bits too.
+ * rq_maxsim_scores: the scoring alone.  cand: nq x ncand document numbers, cand_n[b] of them valid (null: ncand), any order,
+ *   duplicates scored independently, a number whose ids lie beyond the stored ones has no row.  out_score / out_rows: nq x ncand,
+ *   chamfer and the live rows seen; padding slots and documents without a live row are written as 0x7FC00000 / 0.  topk and fetch
+ *   of params are not read.
+ * rq_query_batch_maxsim: end to end, nothing travels to the host in between.  (1) rq_query_batch[_filtered](probe, fetch,
+ *   heuristic_rank) on the nq T token rows under `filter` (nullable; with removals pending and no filter: the live filter); (2) per
+ *   query the documents id / S of the results of its first T_b tokens, sorted and made unique; (3) their chamfer; (4) the topk
+ *   smallest (ord32_biased(chamfer), document).  out_dist / out_docs: nq x topk ascending, padded with 0x7FC00000 / 0xFFFFFFFF;
+ *   out_n[b] = documents returned; out_candidates[b] (nullable) = unique documents scored.
+ * LIMITS.  RQ_ERR_INVALID before a device is looked for: a null index, params or output, a null input with nq > 0,
+ *   params->struct_size != sizeof(rq_maxsim_params_t), an unknown bit in flags, doc_stride or tokens outside their ranges.
+ *   RQ_ERR_UNSUPPORTED before any work: tiered and split-row indexes (the scoring reads every row from HBM at its position, as the
+ *   exact search), shards (a shard holds part of every document), dim > 4096, and for the end-to-end entry tokens x fetch > 2048,
+ *   topk == 0 or topk > 2048; then the source call's own refusals at topk = fetch.  RQ_ERR_EMPTY from the source passes through
+ *   with the outputs written.  nq == 0 is RQ_OK.  Pending lazy removals and open tickets are fine (the calls read the index and
+ *   write nothing of it).  There is no exact-search source in this version.  _device forms: every pointer but params in device
+ *   memory; they return with their outputs complete.  No relayout may run during a call.
+ * rq_last_maxsim_stats: the calling thread's last multi-vector call. */
+#define RQ_MAXSIM_NO_PREFILTER 1u /* flags bit 0: no matrix-core pass, every (token, row) pair gets its exact distance */
+typedef struct {
+    uint32_t struct_size; /* sizeof(rq_maxsim_params_t) */
+    uint32_t tokens;      /* T: token rows per query in `tokens` */
+    uint32_t doc_stride;  /* S */
+    uint32_t topk;        /* documents per query (end to end) */
+    uint32_t fetch;       /* rows per token the source is asked for (end to end) */
+    uint32_t flags;       /* RQ_MAXSIM_* */
+} rq_maxsim_params_t;
+typedef struct {
+    uint32_t struct_size;     /* set to sizeof(rq_maxsim_stats_t) before the call */
+    uint32_t prefilter;       /* 1: the scoring launch ran its matrix-core pass */
+    float ms_source;          /* wall ms of the source call (0: rq_maxsim_scores) */
+    float ms_score;           /* device ms of the scoring launch (HIP events) */
+    uint64_t rows_gathered;   /* live document rows the scoring walked */
+    uint64_t pairs;           /* (token, row) pairs scored */
+    uint64_t exact_distances; /* pairs that got their exact distance */
+    uint64_t list_overflows;  /* (token, document) pairs that fell back to the exact distance of every row */
+    uint64_t candidates;      /* documents scored (end to end: the unique documents of all queries) */
+    uint32_t directory_built; /* 1: this call made the id directory */
+    uint32_t lds_bytes;       /* dynamic LDS of a scoring block */
+    uint32_t tokens_in_lds;   /* 1: a block staged its query's f32 tokens in LDS; 0: the exact step reads them from global memory */
+    uint32_t reserved0;
+} rq_maxsim_stats_t;
+rq_status rq_maxsim_scores(const rq_index *idx, const float *tokens, const uint32_t *n_tokens, uint32_t nq, uint32_t len,
+                           const uint32_t *cand, const uint32_t *cand_n, uint32_t ncand, const rq_maxsim_params_t *params,
+                           float *out_score, uint32_t *out_rows);
+rq_status rq_maxsim_scores_device(const rq_index *idx, const float *d_tokens, const uint32_t *d_n_tokens, uint32_t nq, uint32_t len,
+                                  const uint32_t *d_cand, const uint32_t *d_cand_n, uint32_t ncand, const rq_maxsim_params_t *params,
+                                  float *d_out_score, uint32_t *d_out_rows);
+rq_status rq_query_batch_maxsim(const rq_index *idx, const rq_filter *filter, const float *tokens, const uint32_t *n_tokens, uint32_t nq,
+                                uint32_t len, uint32_t probe, int heuristic_rank, const rq_maxsim_params_t *params, float *out_dist,
+                                uint32_t *out_docs, uint32_t *out_n, uint32_t *out_candidates);
+rq_status rq_query_batch_maxsim_device(const rq_index *idx, const rq_filter *filter, const float *d_tokens, const uint32_t *d_n_tokens,
+                                       uint32_t nq, uint32_t len, uint32_t probe, int heuristic_rank, const rq_maxsim_params_t *params,
+                                       float *d_out_dist, uint32_t *d_out_docs, uint32_t *d_out_n, uint32_t *d_out_candidates);
+rq_status rq_last_maxsim_stats(rq_maxsim_stats_t *out);
 
 /* ---- merge two indexes, extract a sub-index ------------------------------------------------------------------------------ */
 /* Both work on stored rows as they stand: nothing is rotated, assigned, quantised -- or, on a cosine or inner-product index,

@@ -48,6 +48,7 @@ EXPORTS = [
     "rq_group_results", "rq_group_results_device", "rq_last_group_stats",
     "rq_query_batch_diverse", "rq_query_batch_diverse_device", "rq_exact_search_diverse", "rq_exact_search_diverse_device",
     "rq_diversify_results", "rq_diversify_results_device", "rq_last_diverse_stats",
+    "rq_maxsim_scores", "rq_maxsim_scores_device", "rq_query_batch_maxsim", "rq_query_batch_maxsim_device", "rq_last_maxsim_stats",
 ]
 
 
@@ -268,6 +269,24 @@ def default_diverse_fetch(topk: int) -> int:
     return min(GROUP_MAX_FETCH, max(64, 4 * int(topk)))
 
 
+MAXSIM_NO_PREFILTER = 1   # RQ_MAXSIM_NO_PREFILTER
+MAXSIM_MAX_SOURCE = 2048  # tokens x fetch of query_batch_maxsim
+
+
+class MaxsimParamsT(_Sized):
+    """rq_maxsim_params_t: T tokens per query, documents of doc_stride ids; topk / fetch for the end-to-end entry."""
+    _fields_ = [("struct_size", C.c_uint32), ("tokens", C.c_uint32), ("doc_stride", C.c_uint32), ("topk", C.c_uint32), ("fetch", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class MaxsimStatsT(_Sized):
+    """rq_maxsim_stats_t: the calling thread's last multi-vector call."""
+    _fields_ = [("struct_size", C.c_uint32), ("prefilter", C.c_uint32), ("ms_source", C.c_float), ("ms_score", C.c_float),
+                ("rows_gathered", C.c_uint64), ("pairs", C.c_uint64), ("exact_distances", C.c_uint64), ("list_overflows", C.c_uint64),
+                ("candidates", C.c_uint64), ("directory_built", C.c_uint32), ("lds_bytes", C.c_uint32), ("tokens_in_lds", C.c_uint32),
+                ("reserved0", C.c_uint32)]
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", CSRC] + (["-B"] if force else [])
@@ -452,6 +471,11 @@ def lib():
         "rq_diversify_results": (i32, [vp, f32p, u32p, u32p, u32, C.POINTER(DiverseParamsT), f32p, u32p, f32p, u32p]),
         "rq_diversify_results_device": (i32, [vp, f32p, u32p, u32p, u32, C.POINTER(DiverseParamsT), f32p, u32p, f32p, u32p]),
         "rq_last_diverse_stats": (i32, [C.POINTER(DiverseStatsT)]),
+        "rq_maxsim_scores": (i32, [vp, f32p, u32p, u32, u32, u32p, u32p, u32, C.POINTER(MaxsimParamsT), f32p, u32p]),
+        "rq_maxsim_scores_device": (i32, [vp, f32p, u32p, u32, u32, u32p, u32p, u32, C.POINTER(MaxsimParamsT), f32p, u32p]),
+        "rq_query_batch_maxsim": (i32, [vp, vp, f32p, u32p, u32, u32, u32, C.c_int, C.POINTER(MaxsimParamsT), f32p, u32p, u32p, u32p]),
+        "rq_query_batch_maxsim_device": (i32, [vp, vp, f32p, u32p, u32, u32, u32, C.c_int, C.POINTER(MaxsimParamsT), f32p, u32p, u32p, u32p]),
+        "rq_last_maxsim_stats": (i32, [C.POINTER(MaxsimStatsT)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the .so lacks a declared symbol

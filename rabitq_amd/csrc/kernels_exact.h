@@ -99,17 +99,11 @@ void launch_exact_range_scatter(const ExactArgs &a, const ExactSegments &sg, uin
 
 #ifdef RQ_EXACT_KERNELS
 #include "kernels_rerank.h"
+#include "exact_margin.h"  // ex_bf16_pair, ex_margin_factor: shared with kernels_maxsim.h
 
 typedef __bf16 ex_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float ex_f32x16 __attribute__((ext_vector_type(16)));
 
-// two f32 -> packed bf16, round to nearest even (the rounding of asg_bf16_pair, kernels_coarse.h)
-__device__ __forceinline__ uint32_t ex_bf16_pair(float lo, float hi) {
-    uint32_t a = __builtin_bit_cast(uint32_t, lo), b = __builtin_bit_cast(uint32_t, hi);
-    a += 0x7FFFu + ((a >> 16) & 1u);
-    b += 0x7FFFu + ((b >> 16) & 1u);
-    return (a >> 16) | (b & 0xFFFF0000u);
-}
 // T + m for one (row, query) pair and the comparison's own rounding: prefilter_bound's arithmetic with the two roots taken once per
 // row and once per query (xs = sqrt(|x|^2) 1.000001, qs likewise) and one margin where the coarse ranking needs two.  inf / NaN in,
 // inf / NaN out.
@@ -118,7 +112,6 @@ __device__ __forceinline__ float ex_pair_bound(float T, float xs, float qs, floa
     const float thr = T + c * (rad * rad);
     return thr + fabsf(thr) * 1.0e-6f;
 }
-__device__ __forceinline__ float ex_margin_factor(uint32_t dim) { return (0.00390625f + (float)(2 * dim + 64) * 5.9604645e-8f) * 1.05f; }
 
 // One wave per query row of the launch (rows nq .. nq32 - 1 are padding: zeros): the bf16 image and the two norm terms.
 __global__ __launch_bounds__(256) void exact_prep_kernel(const ExactArgs a) {

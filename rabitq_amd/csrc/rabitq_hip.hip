@@ -59,6 +59,7 @@
 #include "host_attr.h"
 #include "host_group.h"
 #include "host_diverse.h"
+#include "host_maxsim.h"
 
 // ------------------------------------------------------------------------------------------------
 // extern "C"
@@ -1320,6 +1321,44 @@ rq_status rq_diversify_results_device(const rq_index *idx, const float *d_dist, 
 rq_status rq_last_diverse_stats(rq_diverse_stats_t *out) {
     if (!out) return fail(RQ_ERR_INVALID, "null argument");
     return copy_out_sized(out, g_diverse_stats);
+}
+
+// ---- multi-vector search (host_maxsim.h): the Chamfer sum of a query's tokens against documents of stored rows ----
+static MaxsimIn maxsim_in_scores(const float *tokens, const uint32_t *n_tokens, uint32_t len, const uint32_t *cand, const uint32_t *cand_n, uint32_t ncand) {
+    MaxsimIn in;
+    in.tokens = tokens, in.n_tokens = n_tokens, in.len = len, in.cand = cand, in.cand_n = cand_n, in.ncand = ncand;
+    return in;
+}
+static MaxsimIn maxsim_in_query(const rq_filter *filter, const float *tokens, const uint32_t *n_tokens, uint32_t len, uint32_t probe, int heuristic) {
+    MaxsimIn in;
+    in.query = true, in.filter = filter, in.tokens = tokens, in.n_tokens = n_tokens, in.len = len, in.probe = probe, in.heuristic = heuristic;
+    return in;
+}
+rq_status rq_maxsim_scores(const rq_index *idx, const float *tokens, const uint32_t *n_tokens, uint32_t nq, uint32_t len, const uint32_t *cand,
+                           const uint32_t *cand_n, uint32_t ncand, const rq_maxsim_params_t *params, float *out_score, uint32_t *out_rows) {
+    return by_id_done(maxsim_host(idx, maxsim_in_scores(tokens, n_tokens, len, cand, cand_n, ncand), nq, params, MaxsimOut{out_score, out_rows, nullptr, nullptr}));
+}
+rq_status rq_maxsim_scores_device(const rq_index *idx, const float *d_tokens, const uint32_t *d_n_tokens, uint32_t nq, uint32_t len,
+                                  const uint32_t *d_cand, const uint32_t *d_cand_n, uint32_t ncand, const rq_maxsim_params_t *params,
+                                  float *d_out_score, uint32_t *d_out_rows) {
+    return by_id_done(maxsim_device(idx, maxsim_in_scores(d_tokens, d_n_tokens, len, d_cand, d_cand_n, ncand), nq, params,
+                                    MaxsimOut{d_out_score, d_out_rows, nullptr, nullptr}));
+}
+rq_status rq_query_batch_maxsim(const rq_index *idx, const rq_filter *filter, const float *tokens, const uint32_t *n_tokens, uint32_t nq,
+                                uint32_t len, uint32_t probe, int heuristic_rank, const rq_maxsim_params_t *params, float *out_dist,
+                                uint32_t *out_docs, uint32_t *out_n, uint32_t *out_candidates) {
+    return by_id_done(maxsim_host(idx, maxsim_in_query(filter, tokens, n_tokens, len, probe, heuristic_rank), nq, params,
+                                  MaxsimOut{out_dist, out_docs, out_n, out_candidates}));
+}
+rq_status rq_query_batch_maxsim_device(const rq_index *idx, const rq_filter *filter, const float *d_tokens, const uint32_t *d_n_tokens,
+                                       uint32_t nq, uint32_t len, uint32_t probe, int heuristic_rank, const rq_maxsim_params_t *params,
+                                       float *d_out_dist, uint32_t *d_out_docs, uint32_t *d_out_n, uint32_t *d_out_candidates) {
+    return by_id_done(maxsim_device(idx, maxsim_in_query(filter, d_tokens, d_n_tokens, len, probe, heuristic_rank), nq, params,
+                                    MaxsimOut{d_out_dist, d_out_docs, d_out_n, d_out_candidates}));
+}
+rq_status rq_last_maxsim_stats(rq_maxsim_stats_t *out) {
+    if (!out) return fail(RQ_ERR_INVALID, "null argument");
+    return copy_out_sized(out, g_maxsim_stats);
 }
 
 rq_status rq_query(const rq_index *idx, const float *query, uint32_t len, uint32_t probe, uint32_t topk,

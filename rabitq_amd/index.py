@@ -277,6 +277,18 @@ class DiverseResult:
         return f"DiverseResult(queries={self.counts.size}, topk={self.ids.shape[1]})"
 
 
+class MaxSimResult:
+    """What query_batch_maxsim returns.  dist / docs: B x topk ascending by (Chamfer sum, document number), padded with NaN /
+    0xFFFFFFFF; counts: documents returned per query; candidates: unique documents scored per query."""
+    __slots__ = ("dist", "docs", "counts", "candidates")
+
+    def __init__(self, dist, docs, counts, candidates):
+        self.dist, self.docs, self.counts, self.candidates = dist, docs, counts, candidates
+
+    def __repr__(self):
+        return f"MaxSimResult(queries={self.counts.size}, topk={self.docs.shape[1]})"
+
+
 class GroupedResult:
     """What a host-form grouped call returns.  dist / ids: B x topk x group_size, group-major, padded with NaN / 0xFFFFFFFF; keys
     (the column's dtype) and group_counts (rows kept per group): B x topk, padded with 0; counts: groups per query; fetched:
@@ -1165,6 +1177,92 @@ class RaBitQ:
         """The calling thread's last diverse call (include/rabitq_hip.h: rq_diverse_stats_t)."""
         return last_diverse_stats()
 
+    # ---- multi-vector search: the Chamfer sum (MaxSim) of token sets against documents of stored rows (rq_maxsim_*) ----
+    @staticmethod
+    def _maxsim_tokens(tokens, n_tokens):
+        t = _f32(tokens)
+        if t.ndim != 3:
+            raise _lib.RabitqError(-1, "tokens must be B x T x d")
+        nt = None if n_tokens is None else np.ascontiguousarray(n_tokens, dtype=np.uint32).reshape(-1)
+        if nt is not None and nt.size != t.shape[0]:
+            raise _lib.RabitqError(-1, "n_tokens must hold one count per query")
+        return t, nt
+
+    def maxsim_scores(self, tokens, docs, doc_stride: int, n_tokens=None, counts=None, prefilter: bool = True):
+        """The Chamfer sum of every query's tokens (B x T x d; the first n_tokens[b] of them) against the documents docs[b]
+        (B x C document numbers, counts[b] valid) -> (score B x C f32, rows B x C u32).  The document of id i is i // doc_stride;
+        score = sum over the tokens of the smallest exact distance to a live row of the document, rows = its live rows; a slot
+        past counts[b] or a document without a live row gives NaN / 0.  Ascending score is descending MaxSim
+        (maxsim_similarity converts).  prefilter=False: every pair on the exact path (the same bits)."""
+        t, nt = self._maxsim_tokens(tokens, n_tokens)
+        d = self._id_list(docs)
+        cn = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        if d.ndim != 2 or d.shape[0] != t.shape[0] or (cn is not None and cn.size != t.shape[0]):
+            raise _lib.RabitqError(-1, "docs must be B x C and counts B")
+        prm = _lib.MaxsimParamsT(tokens=t.shape[1], doc_stride=int(doc_stride), topk=0, fetch=0, flags=0 if prefilter else _lib.MAXSIM_NO_PREFILTER)
+        score = np.full(d.shape, np.nan, dtype=np.float32)
+        rows = np.zeros(d.shape, dtype=np.uint32)
+        check(lib().rq_maxsim_scores(self._h, _addr(t), _addr(nt), t.shape[0], t.shape[2], _addr(d), _addr(cn), d.shape[1], C.byref(prm),
+                                     _addr(score), _addr(rows)))
+        return score, rows
+
+    def query_batch_maxsim(self, tokens, probe: int, topk: int, doc_stride: int, fetch=None, n_tokens=None, filter: Filter = None,
+                           heuristic_rank: bool = False, prefilter: bool = True) -> "MaxSimResult":
+        """Late-interaction search on the GPU: query_batch at topk = fetch for every token (B x T x d), the documents
+        id // doc_stride of the results, their Chamfer sums over ALL live rows of each document, and the topk documents with the
+        smallest sum (= the largest MaxSim) -- nothing travels to the host in between.  fetch=None means
+        min(64, 2048 // T): T * fetch <= 2048."""
+        t, nt = self._maxsim_tokens(tokens, n_tokens)
+        f = min(64, _lib.MAXSIM_MAX_SOURCE // max(t.shape[1], 1)) if fetch is None else int(fetch)
+        prm = _lib.MaxsimParamsT(tokens=t.shape[1], doc_stride=int(doc_stride), topk=int(topk), fetch=f, flags=0 if prefilter else _lib.MAXSIM_NO_PREFILTER)
+        B, cells = t.shape[0], (t.shape[0], max(int(topk), 1))
+        dist = np.full(cells, np.nan, dtype=np.float32)
+        docs = np.full(cells, 0xFFFFFFFF, dtype=np.uint32)
+        cnt, cand = np.zeros(B, dtype=np.uint32), np.zeros(B, dtype=np.uint32)
+        st = lib().rq_query_batch_maxsim(self._h, _fh(filter), _addr(t), _addr(nt), B, t.shape[2], probe, int(heuristic_rank), C.byref(prm),
+                                         _addr(dist), _addr(docs), _addr(cnt), _addr(cand))
+        if st != _lib.RQ_ERR_EMPTY:
+            check(st)
+        return MaxSimResult(dist, docs, cnt, cand)
+
+    def maxsim_scores_device(self, tokens_ptr: int, n_tokens_ptr: int, nq: int, T: int, length: int, docs_ptr: int, counts_ptr: int, ncand: int,
+                             doc_stride: int, out_score_ptr: int, out_rows_ptr: int, prefilter: bool = True) -> None:
+        """maxsim_scores with every array in device memory (raw addresses; n_tokens / counts 0 = none)."""
+        prm = _lib.MaxsimParamsT(tokens=T, doc_stride=int(doc_stride), topk=0, fetch=0, flags=0 if prefilter else _lib.MAXSIM_NO_PREFILTER)
+        check(lib().rq_maxsim_scores_device(self._h, C.c_void_p(tokens_ptr), C.c_void_p(n_tokens_ptr), nq, length, C.c_void_p(docs_ptr),
+                                            C.c_void_p(counts_ptr), ncand, C.byref(prm), C.c_void_p(out_score_ptr), C.c_void_p(out_rows_ptr)))
+
+    def query_batch_maxsim_device(self, tokens_ptr: int, n_tokens_ptr: int, nq: int, T: int, length: int, probe: int, topk: int, doc_stride: int,
+                                  fetch: int, out_dist_ptr: int, out_docs_ptr: int, out_n_ptr: int, out_candidates_ptr: int = 0,
+                                  heuristic_rank: bool = False, filter: Filter = None, prefilter: bool = True) -> None:
+        """query_batch_maxsim with tokens and outputs in device memory (raw addresses; candidates 0 = not wanted)."""
+        prm = _lib.MaxsimParamsT(tokens=T, doc_stride=int(doc_stride), topk=int(topk), fetch=int(fetch), flags=0 if prefilter else _lib.MAXSIM_NO_PREFILTER)
+        st = lib().rq_query_batch_maxsim_device(self._h, _fh(filter), C.c_void_p(tokens_ptr), C.c_void_p(n_tokens_ptr), nq, length, probe,
+                                                int(heuristic_rank), C.byref(prm), C.c_void_p(out_dist_ptr), C.c_void_p(out_docs_ptr),
+                                                C.c_void_p(out_n_ptr), C.c_void_p(out_candidates_ptr))
+        if st != _lib.RQ_ERR_EMPTY:
+            check(st)
+
+    def maxsim_similarity(self, score, tokens, n_tokens=None):
+        """The MaxSim a Chamfer sum stands for (score: B x C as maxsim_scores / query_batch_maxsim return it), in f64: on a
+        cosine index sum max cos = T_b - score / 2, on an "ip" index sum max <x, q> = (T_b * S + sum |q_t|^2 - score) / 2 with S
+        the index's squared-norm bound; on an l2 index the negated score (the larger the better)."""
+        t, nt = self._maxsim_tokens(tokens, n_tokens)
+        s = np.asarray(score, dtype=np.float64)
+        tb = np.full(t.shape[0], t.shape[1], dtype=np.int64) if nt is None else np.minimum(nt.astype(np.int64), t.shape[1])
+        if self.metric == "cosine":
+            return tb[:, None] - s / 2
+        if self.metric == "ip":
+            used = np.arange(t.shape[1])[None, :] < tb[:, None]
+            qn = ((t.astype(np.float64) ** 2).sum(axis=2) * used).sum(axis=1)
+            return (tb[:, None] * float(self.ip_params[1]) + qn[:, None] - s) / 2
+        return -s
+
+    @staticmethod
+    def last_maxsim_stats() -> dict:
+        """The calling thread's last multi-vector call (include/rabitq_hip.h: rq_maxsim_stats_t)."""
+        return last_maxsim_stats()
+
     @staticmethod
     def _recall_of(ids, cnt, exact_ids, exact_cnt) -> float:
         """mean over the queries with a non-empty exact answer of |query ids n exact ids| / exact count"""
@@ -1601,6 +1699,13 @@ def last_where_stats() -> dict:
     st = _lib.WhereStatsT()
     check(lib().rq_last_where_stats(C.byref(st)))
     return {name: getattr(st, name) for name, _ in _lib.WhereStatsT._fields_ if name != "struct_size"}
+
+
+def last_maxsim_stats() -> dict:
+    """The calling thread's last multi-vector call (include/rabitq_hip.h: rq_last_maxsim_stats)."""
+    st = _lib.MaxsimStatsT()
+    check(lib().rq_last_maxsim_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _lib.MaxsimStatsT._fields_ if name not in ("struct_size", "reserved0")}
 
 
 def last_diverse_stats() -> dict:
