@@ -106,7 +106,10 @@ typedef struct {
  * 0.17.0: diverse search, additions only -- rq_diverse_params_t, rq_diverse_stats_t, rq_query_batch_diverse*, rq_exact_search_diverse*,
  * rq_diversify_results*, rq_last_diverse_stats; no existing call, refusal or output changes;
  * 0.18.0: multi-vector search, additions only -- RQ_MAXSIM_*, rq_maxsim_params_t, rq_maxsim_stats_t, rq_maxsim_scores*,
- * rq_query_batch_maxsim*, rq_last_maxsim_stats; no existing call, refusal or output changes.
+ * rq_query_batch_maxsim*, rq_last_maxsim_stats; no existing call, refusal or output changes;
+ * 0.19.0: postings and keyed exact search, additions only -- rq_postings, rq_postings_info_t, rq_postings_create / _free / _info /
+ * _values / _counts / _positions_device, rq_keyed_stats_t, rq_exact_search_keyed*, rq_last_keyed_stats, rq_keyed_tuning; no existing call, refusal
+ * or output changes, and an index on which no postings are made behaves and allocates exactly as before.
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -1163,6 +1166,84 @@ rq_status rq_query_batch_maxsim_device(const rq_index *idx, const rq_filter *fil
                                        uint32_t nq, uint32_t len, uint32_t probe, int heuristic_rank, const rq_maxsim_params_t *params,
                                        float *d_out_dist, uint32_t *d_out_docs, uint32_t *d_out_n, uint32_t *d_out_candidates);
 rq_status rq_last_maxsim_stats(rq_maxsim_stats_t *out);
+
+/* ---- postings of a column, and the exact search keyed by them (0.19.0, additions only) --------------------------------------- */
+/* POSTINGS: the value -> positions directory of one integer column (RQ_ATTR_U32 / _I32 / _U64 / _I64; an RQ_ATTR_F32 column is
+ * RQ_ERR_INVALID), built on the device.  A postings object is a SNAPSHOT, as a filter is: it holds the distinct values of the rows
+ * live at creation in ascending order under the column type's own comparison, their row counts, and the live positions grouped by
+ * value.  Rows dead at creation are not in it.  It carries the index's generation and removal epoch: every entry that takes it
+ * refuses it with RQ_ERR_INVALID once the index has been relaid out (rq_add, rq_remove, rq_compact, rq_merge_from) or rows have been
+ * marked dead (a marking rq_remove_lazy) since -- exactly as a filter is refused.  A later rq_attr_set does NOT invalidate it: it
+ * keeps the values it saw, as a filter is the set its predicate selected when it was made.  The order of the positions inside one
+ * value is not part of the contract and no output of any search depends on it.  More than 2^22 distinct values: RQ_ERR_UNSUPPORTED
+ * with nothing left allocated.  Every 64-bit pattern is a legal value.  Postings read the column, the live bitmap and the row count
+ * only: every metric and row type, tiered and split-row indexes, shards and indexes with pending removals are accepted.  Free them
+ * with rq_postings_free before or after the index (they are never dereferenced by rq_free).
+ * rq_postings_info: distinct values, rows, column type, bytes held (device postings + host directory).
+ * rq_postings_values: the first min(cap, values) values, ascending, with their row counts (host arrays).
+ * rq_postings_counts: the rows of each of m keys, 0 for a key the postings do not hold (host arrays; a 4-byte type reads the
+ *   union's low 4 bytes).
+ * rq_postings_positions_device: a test and debug reader in the style of rq_filter_ids_device -- the first min(cap, count) positions
+ *   of `key` into d_out (device memory), in the postings' own (unspecified) order; *out_count = the key's rows.
+ *
+ * KEYED EXACT SEARCH: rq_exact_search_keyed*.  Query b carries keys[b] and is answered from that key's rows only: it gets exactly
+ * what rq_exact_search returns for it under a filter admitting {live rows whose column value (at postings creation) == keys[b]}
+ * intersected with `filter` (nullable) -- the topk smallest (Ord32(e), id) with e < f32::MAX, ascending, e the library's one
+ * exact-order distance (bit for bit rq_rerank); out_n[b] is written and slots past it are left untouched.  A key the postings do
+ * not hold gives out_n[b] = 0.  The result does not depend on params, on options, on the batch or on how the work is split.  The
+ * work follows the rows of the keys asked for, not queries x n.  keys: nq values in HOST memory in both forms (routing metadata: the
+ * work plan is made from them without waiting on the device).  Refusals as rq_exact_search: tiered or split-row index
+ * RQ_ERR_UNSUPPORTED with nothing allocated, topk in [1, 2048], dim <= 4096, a foreign or stale filter or postings RQ_ERR_INVALID
+ * (null arguments are refused before a device is looked for); nq == 0 is RQ_OK.  rq_metrics is not touched.  params: the exact
+ * search's test hooks -- RQ_EXACT_NO_SEED, RQ_EXACT_NO_PREFILTER and cand_per_query act as there; seed_probe likewise, per key.
+ * WIDE DIMENSIONS.  The matrix pass of the keyed scan holds a query tile and four row slabs in LDS and exists for dim <= 448 only
+ * (rq_exact_search pre-filters up to dim 2432).  From dim 512 on every (query, row of its key) pair gets its exact distance and a
+ * query takes as many candidate slots (12 bytes each) as its key has rows: correct, but on a large key slower and heavier on memory
+ * than the filtered rq_exact_search it stands in for -- prefer that one there.
+ * rq_keyed_tuning: developer knob for measurements, process-wide; results never depend on it.  chunk_rows = postings per work item,
+ * small_rows = the segment size below which a key takes neither bound nor matrix pass, slabs = 1: one LDS slab per wave everywhere,
+ * 2 (or 0): the double-buffered scan where it exists (dim 64); 0 = the default for each.
+ * rq_last_keyed_stats: the calling thread's last keyed search. */
+typedef struct rq_postings rq_postings;
+typedef struct {
+    uint32_t struct_size; /* in: sizeof(rq_postings_info_t) of the caller */
+    uint32_t type;        /* RQ_ATTR_* of the column */
+    uint64_t values;      /* distinct values */
+    uint64_t rows;        /* live rows at creation */
+    uint64_t bytes;       /* device postings + host directory */
+} rq_postings_info_t;
+rq_status rq_postings_create(const rq_index *idx, const char *column, rq_postings **out);
+void rq_postings_free(rq_postings *p);
+rq_status rq_postings_info(const rq_postings *p, rq_postings_info_t *out);
+rq_status rq_postings_values(const rq_postings *p, rq_attr_value_t *out_values, uint64_t *out_counts, uint64_t cap);
+rq_status rq_postings_counts(const rq_postings *p, const rq_attr_value_t *keys, uint64_t m, uint64_t *out_counts);
+rq_status rq_postings_positions_device(const rq_postings *p, rq_attr_value_t key, uint32_t *d_out, uint64_t cap, uint64_t *out_count);
+typedef struct {
+    uint32_t struct_size;    /* in: sizeof(rq_keyed_stats_t) of the caller */
+    uint32_t prefilter;      /* 1: the matrix pass ran (for at least one key) */
+    float ms_plan;           /* wall ms of the host plan */
+    float ms_seed;           /* device ms of the bounds: the sample's scan, exact distances and selection */
+    float ms_scan;           /* device ms of the scan launches (re-runs included) */
+    float ms_exact;          /* device ms of the exact distances */
+    float ms_select;         /* device ms of the selection */
+    uint32_t reruns;         /* scan launches repeated because a query's candidates did not fit its slots */
+    uint32_t keys_distinct;  /* distinct keys of the batch that the postings hold */
+    uint32_t queries_absent; /* queries whose key the postings do not hold */
+    uint64_t items;          /* work items (query tile x row chunk), the sample's included */
+    uint64_t rows_gathered;  /* rows the scan gathered for its matrix pass: per query tile, the rows of its key (keys with a matrix pass) */
+    uint64_t candidates;     /* (query, row) pairs the scan kept */
+    uint64_t exact;          /* exact distances computed, the sample's included */
+    uint64_t rows_listed;    /* postings the scan items covered, with or without a matrix pass: per query tile, the rows of its key */
+} rq_keyed_stats_t;
+rq_status rq_exact_search_keyed_device(const rq_index *idx, const rq_postings *postings, const rq_filter *filter /* nullable */,
+                                       const float *d_queries, uint32_t nq, uint32_t len, const rq_attr_value_t *keys /* host */,
+                                       uint32_t topk, const rq_exact_params_t *params /* nullable */, float *d_out_dist,
+                                       uint32_t *d_out_id, uint32_t *d_out_n);
+rq_status rq_exact_search_keyed(const rq_index *idx, const rq_postings *postings, const rq_filter *filter /* nullable */,
+                                const float *queries, uint32_t nq, uint32_t len, const rq_attr_value_t *keys, uint32_t topk,
+                                const rq_exact_params_t *params /* nullable */, float *out_dist, uint32_t *out_id, uint32_t *out_n);
+rq_status rq_last_keyed_stats(rq_keyed_stats_t *out);
+rq_status rq_keyed_tuning(uint32_t chunk_rows, uint32_t small_rows, uint32_t slabs);
 
 /* ---- merge two indexes, extract a sub-index ------------------------------------------------------------------------------ */
 /* Both work on stored rows as they stand: nothing is rotated, assigned, quantised -- or, on a cosine or inner-product index,

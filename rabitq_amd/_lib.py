@@ -49,6 +49,8 @@ EXPORTS = [
     "rq_query_batch_diverse", "rq_query_batch_diverse_device", "rq_exact_search_diverse", "rq_exact_search_diverse_device",
     "rq_diversify_results", "rq_diversify_results_device", "rq_last_diverse_stats",
     "rq_maxsim_scores", "rq_maxsim_scores_device", "rq_query_batch_maxsim", "rq_query_batch_maxsim_device", "rq_last_maxsim_stats",
+    "rq_postings_create", "rq_postings_free", "rq_postings_info", "rq_postings_values", "rq_postings_counts", "rq_postings_positions_device",
+    "rq_exact_search_keyed", "rq_exact_search_keyed_device", "rq_last_keyed_stats", "rq_keyed_tuning",
 ]
 
 
@@ -287,6 +289,20 @@ class MaxsimStatsT(_Sized):
                 ("reserved0", C.c_uint32)]
 
 
+class PostingsInfoT(_Sized):
+    """rq_postings_info_t: distinct values, live rows, column type and bytes of a postings object."""
+    _fields_ = [("struct_size", C.c_uint32), ("type", C.c_uint32), ("values", C.c_uint64), ("rows", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class KeyedStatsT(_Sized):
+    """rq_keyed_stats_t: the calling thread's last keyed exact search."""
+    _fields_ = [("struct_size", C.c_uint32), ("prefilter", C.c_uint32)] + [(n, C.c_float) for n in (
+        "ms_plan", "ms_seed", "ms_scan", "ms_exact", "ms_select")] + [
+        ("reruns", C.c_uint32), ("keys_distinct", C.c_uint32), ("queries_absent", C.c_uint32),
+        ("items", C.c_uint64), ("rows_gathered", C.c_uint64), ("candidates", C.c_uint64), ("exact", C.c_uint64),
+        ("rows_listed", C.c_uint64)]
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", CSRC] + (["-B"] if force else [])
@@ -476,6 +492,16 @@ def lib():
         "rq_query_batch_maxsim": (i32, [vp, vp, f32p, u32p, u32, u32, u32, C.c_int, C.POINTER(MaxsimParamsT), f32p, u32p, u32p, u32p]),
         "rq_query_batch_maxsim_device": (i32, [vp, vp, f32p, u32p, u32, u32, u32, C.c_int, C.POINTER(MaxsimParamsT), f32p, u32p, u32p, u32p]),
         "rq_last_maxsim_stats": (i32, [C.POINTER(MaxsimStatsT)]),
+        "rq_postings_create": (i32, [vp, C.c_char_p, pp]),
+        "rq_postings_free": (None, [vp]),
+        "rq_postings_info": (i32, [vp, C.POINTER(PostingsInfoT)]),
+        "rq_postings_values": (i32, [vp, vp, u64p, u64]),
+        "rq_postings_counts": (i32, [vp, vp, u64, u64p]),
+        "rq_postings_positions_device": (i32, [vp, u64, u32p, u64, C.POINTER(u64)]),   # (key: the union's u64 image, see AttrValue)
+        "rq_exact_search_keyed": (i32, [vp, vp, vp, f32p, u32, u32, vp, u32, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
+        "rq_exact_search_keyed_device": (i32, [vp, vp, vp, f32p, u32, u32, vp, u32, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
+        "rq_last_keyed_stats": (i32, [C.POINTER(KeyedStatsT)]),
+        "rq_keyed_tuning": (i32, [u32, u32, u32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the .so lacks a declared symbol

@@ -60,6 +60,7 @@
 #include "host_group.h"
 #include "host_diverse.h"
 #include "host_maxsim.h"
+#include "host_keyed.h"
 
 // ------------------------------------------------------------------------------------------------
 // extern "C"
@@ -1359,6 +1360,39 @@ rq_status rq_query_batch_maxsim_device(const rq_index *idx, const rq_filter *fil
 rq_status rq_last_maxsim_stats(rq_maxsim_stats_t *out) {
     if (!out) return fail(RQ_ERR_INVALID, "null argument");
     return copy_out_sized(out, g_maxsim_stats);
+}
+
+// ---- postings and the keyed exact search (host_keyed.h) ----
+rq_status rq_postings_create(const rq_index *idx, const char *column, rq_postings **out) { return by_id_done(postings_create(idx, column, out)); }
+void rq_postings_free(rq_postings *p) { delete p; }
+rq_status rq_postings_info(const rq_postings *p, rq_postings_info_t *out) { return postings_info(p, out); }
+rq_status rq_postings_values(const rq_postings *p, rq_attr_value_t *out_values, uint64_t *out_counts, uint64_t cap) {
+    return postings_values(p, out_values, out_counts, cap);
+}
+rq_status rq_postings_counts(const rq_postings *p, const rq_attr_value_t *keys, uint64_t m, uint64_t *out_counts) {
+    return postings_counts(p, keys, m, out_counts);
+}
+rq_status rq_postings_positions_device(const rq_postings *p, rq_attr_value_t key, uint32_t *d_out, uint64_t cap, uint64_t *out_count) {
+    return postings_positions_device(p, key, d_out, cap, out_count);
+}
+rq_status rq_exact_search_keyed_device(const rq_index *idx, const rq_postings *postings, const rq_filter *filter, const float *d_queries,
+                                       uint32_t nq, uint32_t len, const rq_attr_value_t *keys, uint32_t topk, const rq_exact_params_t *params,
+                                       float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n) {
+    return by_id_done(keyed_search_device(idx, postings, filter, d_queries, nq, len, keys, topk, params, d_out_dist, d_out_id, d_out_n));
+}
+rq_status rq_exact_search_keyed(const rq_index *idx, const rq_postings *postings, const rq_filter *filter, const float *queries, uint32_t nq,
+                                uint32_t len, const rq_attr_value_t *keys, uint32_t topk, const rq_exact_params_t *params, float *out_dist,
+                                uint32_t *out_id, uint32_t *out_n) {
+    return by_id_done(keyed_search_host(idx, postings, filter, queries, nq, len, keys, topk, params, out_dist, out_id, out_n));
+}
+rq_status rq_keyed_tuning(uint32_t chunk_rows, uint32_t small_rows, uint32_t slabs) {
+    if (slabs > 2 || (chunk_rows && chunk_rows < 32)) return fail(RQ_ERR_INVALID, "chunk_rows must be 0 or at least 32, slabs 0, 1 or 2");
+    g_keyed_chunk = chunk_rows, g_keyed_small = small_rows, g_keyed_slabs = slabs;
+    return RQ_OK;
+}
+rq_status rq_last_keyed_stats(rq_keyed_stats_t *out) {
+    if (!out) return fail(RQ_ERR_INVALID, "null argument");
+    return copy_out_sized(out, g_keyed_stats);
 }
 
 rq_status rq_query(const rq_index *idx, const float *query, uint32_t len, uint32_t probe, uint32_t topk,

@@ -216,6 +216,78 @@ class Filter:
         return np.unpackbits(words.view(np.uint8), bitorder="little")[:nbits].astype(bool)
 
 
+class Postings:
+    """The value -> positions directory of one integer column (rq_postings_create): a snapshot of the rows live when it was made,
+    passed as `by=` to exact_search_keyed.  Refused once the index has been relaid out or rows have been marked dead since; a
+    later set_attr does not change it.  Holds a reference to its index, so the index outlives it."""
+
+    def __init__(self, index: "RaBitQ", handle, column: str):
+        self.index, self._h, self.column = index, handle, column
+        try:
+            info = _lib.PostingsInfoT()
+            check(lib().rq_postings_info(self._h, C.byref(info)))
+            self.type = _lib.ATTR_BY_ID[int(info.type)]
+            self.rows, self.bytes = int(info.rows), int(info.bytes)
+            nv = int(info.values)
+            vals = np.zeros(nv, dtype=np.uint64)
+            self.counts = np.zeros(nv, dtype=np.uint64)   # rows per value, in the order of .values
+            check(lib().rq_postings_values(self._h, _addr(vals), _addr(self.counts), nv))
+        except Exception:
+            self.close()   # (the handle is ours already: a failed constructor must not leak it)
+            raise
+        # the distinct values, ascending in the column's own order
+        self.values = vals.astype(np.uint32).view(self.type.dtype) if self.type.elem_bytes == 4 else vals.view(self.type.dtype)
+
+    def _keys(self, keys) -> np.ndarray:
+        """keys in the column's type -> their 8-byte rq_attr_value_t images (a 4-byte value in the low 4 bytes)."""
+        k = np.asarray(keys)
+        if k.dtype.kind not in "iu":
+            raise ValueError("keys must be integers")
+        info = np.iinfo(self.type.dtype)
+        if k.size and (int(k.min()) < info.min or int(k.max()) > info.max):
+            raise ValueError(f"a key is not a value of a {self.type.name} column")
+        k = k.astype(self.type.dtype)
+        view = np.uint32 if self.type.elem_bytes == 4 else np.uint64
+        return np.ascontiguousarray(k.view(view).astype(np.uint64))
+
+    def count_of(self, keys) -> np.ndarray:
+        """Rows per key (u64), 0 for a key the postings do not hold (rq_postings_counts)."""
+        img = self._keys(keys)
+        out = np.zeros(img.shape, dtype=np.uint64)
+        check(lib().rq_postings_counts(self._h, _addr(img), img.size, _addr(out)))
+        return out
+
+    def positions(self, key) -> np.ndarray:
+        """The positions of one key's rows (u32), sorted on the host: a test and debug reader; the array travels through torch."""
+        img = int(self._keys([key])[0])
+        count = C.c_uint64()
+        check(lib().rq_postings_positions_device(self._h, img, None, 0, C.byref(count)))
+        if count.value == 0:
+            return np.empty(0, dtype=np.uint32)
+        import torch
+        out = torch.empty(count.value, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        check(lib().rq_postings_positions_device(self._h, img, C.c_void_p(out.data_ptr()), count.value, C.byref(count)))
+        return np.sort(out.cpu().numpy().view(np.uint32))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().rq_postings_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _fh(filter):
     return filter._h if filter is not None else None
 
@@ -870,6 +942,45 @@ class RaBitQ:
         check(lib().rq_exact_search_device(self._h, _fh(filter), C.c_void_p(q_ptr), nq, length, topk,
                                            C.byref(prm) if prm is not None else None, C.c_void_p(out_dist_ptr), C.c_void_p(out_id_ptr),
                                            C.c_void_p(out_n_ptr)))
+
+    # ---- postings and the keyed exact search: each query over the rows of its own key (rq_postings_*, rq_exact_search_keyed*) ----
+    def postings(self, column: str) -> Postings:
+        """The postings of an integer column, built on the device: `p = idx.postings("tenant")`."""
+        h = C.c_void_p()
+        check(lib().rq_postings_create(self._h, column.encode(), C.byref(h)))
+        return Postings(self, h, column)
+
+    def exact_search_keyed(self, queries, keys, topk: int, by: Postings, filter: Filter = None, params=None):
+        """exact_search where query b sees only the rows whose column value (when `by` was made) equals keys[b] -> (dist, ids,
+        counts) as exact_search gives them; a key the postings do not hold gives count 0.  The work follows the rows of the keys
+        asked for."""
+        q = _f32(queries)
+        if q.ndim != 2:
+            raise _lib.RabitqError(-1, "queries must be 2-D")
+        B = q.shape[0]
+        img = by._keys(keys)
+        if img.shape != (B,):
+            raise ValueError(f"keys must hold one key per query ({B}), not shape {img.shape}")
+        d = np.full((B, max(topk, 1)), np.nan, dtype=np.float32)
+        ids = np.full((B, max(topk, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        cnt = np.zeros(B, dtype=np.uint32)
+        prm = self._exact_params(params)
+        check(lib().rq_exact_search_keyed(self._h, by._h, _fh(filter), _addr(q), B, q.shape[1], _addr(img), topk,
+                                          C.byref(prm) if prm is not None else None, _addr(d), _addr(ids), _addr(cnt)))
+        return d, ids, cnt
+
+    def exact_search_keyed_device(self, q_ptr: int, nq: int, length: int, keys, topk: int, by: Postings, out_dist_ptr: int, out_id_ptr: int,
+                                  out_n_ptr: int, filter: Filter = None, params=None):
+        """exact_search_keyed with queries and outputs already in device memory (raw addresses); keys stay a host array."""
+        img = by._keys(keys)
+        prm = self._exact_params(params)
+        check(lib().rq_exact_search_keyed_device(self._h, by._h, _fh(filter), C.c_void_p(q_ptr), nq, length, _addr(img), topk,
+                                                 C.byref(prm) if prm is not None else None, C.c_void_p(out_dist_ptr),
+                                                 C.c_void_p(out_id_ptr), C.c_void_p(out_n_ptr)))
+
+    @staticmethod
+    def last_keyed_stats() -> dict:
+        return last_keyed_stats()
 
     # ---- rows by id: locate, fetch, exact distances to known ids, neighbours of stored rows (rq_locate ...) ----
     @staticmethod
@@ -1706,6 +1817,13 @@ def last_maxsim_stats() -> dict:
     st = _lib.MaxsimStatsT()
     check(lib().rq_last_maxsim_stats(C.byref(st)))
     return {name: getattr(st, name) for name, _ in _lib.MaxsimStatsT._fields_ if name not in ("struct_size", "reserved0")}
+
+
+def last_keyed_stats() -> dict:
+    """The calling thread's last keyed exact search (include/rabitq_hip.h: rq_last_keyed_stats)."""
+    st = _lib.KeyedStatsT()
+    check(lib().rq_last_keyed_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _lib.KeyedStatsT._fields_ if name != "struct_size"}
 
 
 def last_diverse_stats() -> dict:
