@@ -109,7 +109,9 @@ typedef struct {
  * rq_query_batch_maxsim*, rq_last_maxsim_stats; no existing call, refusal or output changes;
  * 0.19.0: postings and keyed exact search, additions only -- rq_postings, rq_postings_info_t, rq_postings_create / _free / _info /
  * _values / _counts / _positions_device, rq_keyed_stats_t, rq_exact_search_keyed*, rq_last_keyed_stats, rq_keyed_tuning; no existing call, refusal
- * or output changes, and an index on which no postings are made behaves and allocates exactly as before.
+ * or output changes, and an index on which no postings are made behaves and allocates exactly as before;
+ * 0.20.0: exact search on split-row and tiered indexes, additions only -- rq_exact_search_tiered*, rq_exact_range_search_tiered*; the
+ * plain entries refuse those layouts as before.
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -621,6 +623,38 @@ rq_status rq_exact_range_search_device(const rq_index *idx, const rq_filter *fil
 rq_status rq_exact_range_search(const rq_index *idx, const rq_filter *filter /* nullable */, const float *queries, uint32_t nq,
                                 uint32_t len, const float *radius, const rq_exact_params_t *params /* nullable */,
                                 rq_range_result **out);
+
+/* ---- exact search on split-row and tiered indexes (0.20.0, additions only) ---------------------------------------------- */
+/* rq_exact_search_tiered* / rq_exact_range_search_tiered*: the arguments, the contract and the stats of rq_exact_search* /
+ * rq_exact_range_search* on EVERY f32-row index -- plain, split rows, tiered (list tails in pinned host memory), tiered + split.
+ * The result of query b is the topk smallest by (Ord32(e), id) among the admitted rows with e < f32::MAX, e bit for bit what
+ * rq_rerank returns for the row's position; the range form returns every admitted row with e strictly below the radius.  The
+ * result does not depend on `params`, on options, on the batch size, on how the work was split or on which tier a row lives in.
+ * L2, cosine and inner-product indexes, filters, and pending lazy removals through the index's own live filter, as the plain
+ * entries handle them.  Indexes the plain entries accept (rows all in HBM as plain f32, f16 / bf16, u8 / i8) are forwarded to them.
+ * Refused: what the plain entries refuse for other reasons than the layout -- topk outside [1, 2048], dim > 4096
+ * (RQ_ERR_UNSUPPORTED), unknown flag bits, a foreign or stale filter (RQ_ERR_INVALID); a null pointer is RQ_ERR_INVALID before a
+ * device is looked for; nq == 0 is RQ_OK (the range form: as rq_exact_range_search).  The plain entries keep refusing split-row and
+ * tiered indexes, and so do the grouped, diverse and keyed exact forms and rq_neighbours_of_exact.
+ * Method: the phases of rq_exact_search.  The scan runs over the PHYSICAL rows of one tier per launch, the HBM array
+ * and the host array on two streams, and recovers a row's position from the tier records of its list.  On split rows it reads the
+ * FIRST PLANE alone -- already a bf16 image of the row: half the bytes, no conversion before the matrix pass -- with a margin
+ * re-derived for a norm taken from that plane; a NaN element whose bit pattern is at or above 0x7FFF8000 (it wraps to zero in the
+ * first plane) is not seen by the scan, and its row, whose e is NaN, is never returned anyway.  Exact distances read both planes.
+ * rq_last_exact_stats: as for the plain entries, with row_bytes_read = the bytes the scan launches read (n x 2 dim for split rows,
+ * n x 4 dim for plain rows; 0 for a scan without the pre-filter, which reads no row). */
+rq_status rq_exact_search_tiered_device(const rq_index *idx, const rq_filter *filter /* nullable */, const float *d_queries, uint32_t nq,
+                                        uint32_t len, uint32_t topk, const rq_exact_params_t *params /* nullable */, float *d_out_dist,
+                                        uint32_t *d_out_id, uint32_t *d_out_n);
+rq_status rq_exact_search_tiered(const rq_index *idx, const rq_filter *filter /* nullable */, const float *queries, uint32_t nq, uint32_t len,
+                                 uint32_t topk, const rq_exact_params_t *params /* nullable */, float *out_dist, uint32_t *out_id,
+                                 uint32_t *out_n);
+rq_status rq_exact_range_search_tiered_device(const rq_index *idx, const rq_filter *filter /* nullable */, const float *d_queries,
+                                              uint32_t nq, uint32_t len, const float *d_radius,
+                                              const rq_exact_params_t *params /* nullable */, rq_range_result **out);
+rq_status rq_exact_range_search_tiered(const rq_index *idx, const rq_filter *filter /* nullable */, const float *queries, uint32_t nq,
+                                       uint32_t len, const float *radius, const rq_exact_params_t *params /* nullable */,
+                                       rq_range_result **out);
 
 /* ---- adaptive probing: each query's probe list cut by centroid distance (later in 0.11, additions only) ----------------- */
 /* Every query of a plain call visits `probe` lists; these entries let each query stop where its centroids stop being near.

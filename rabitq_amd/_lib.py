@@ -34,6 +34,7 @@ EXPORTS = [
     "rq_from_arrays_rows", "rq_row_type", "rq_widen", "rq_widen_device",
     "rq_exact_search", "rq_exact_search_device", "rq_last_exact_stats",
     "rq_exact_range_search", "rq_exact_range_search_device",
+    "rq_exact_search_tiered", "rq_exact_search_tiered_device", "rq_exact_range_search_tiered", "rq_exact_range_search_tiered_device",
     "rq_query_batch_adaptive", "rq_query_batch_device_adaptive", "rq_probe_counts_device",
     "rq_train_centroids", "rq_train_centroids_device",
     "rq_merge_from", "rq_extract",
@@ -440,6 +441,10 @@ def lib():
         "rq_last_exact_stats": (i32, [C.POINTER(ExactStatsT)]),
         "rq_exact_range_search": (i32, [vp, vp, f32p, u32, u32, f32p, C.POINTER(ExactParamsT), pp]),
         "rq_exact_range_search_device": (i32, [vp, vp, f32p, u32, u32, f32p, C.POINTER(ExactParamsT), pp]),
+        "rq_exact_search_tiered": (i32, [vp, vp, f32p, u32, u32, u32, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
+        "rq_exact_search_tiered_device": (i32, [vp, vp, f32p, u32, u32, u32, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
+        "rq_exact_range_search_tiered": (i32, [vp, vp, f32p, u32, u32, f32p, C.POINTER(ExactParamsT), pp]),
+        "rq_exact_range_search_tiered_device": (i32, [vp, vp, f32p, u32, u32, f32p, C.POINTER(ExactParamsT), pp]),
         "rq_query_batch_adaptive": (i32, [vp, vp, f32p, u32, u32, u32, u32, C.c_int, C.POINTER(ProbeRuleT), f32p, u32p, u32p, u32p]),
         "rq_query_batch_device_adaptive": (i32, [vp, vp, f32p, u32, u32, u32, u32, C.c_int, C.POINTER(ProbeRuleT), f32p, u32p, u32p, u32p]),
         "rq_probe_counts_device": (i32, [vp, f32p, u32, u32, u32, C.POINTER(ProbeRuleT), u32p]),

@@ -81,8 +81,10 @@ def make_truth(index, queries, path, topk: int) -> bool:
     k = max(topk, 100)
     ids = np.zeros((0, k), np.uint32)
     cnt = np.zeros(0, np.uint32)
+    # (split-row and tiered indexes have an entry of their own; every other index keeps the plain one)
+    search = index.exact_search_tiered if index.split_rows or index.n_hbm < index.n else index.exact_search
     for s in range(0, len(queries), 4096):
-        _, i_, c_ = index.exact_search(np.stack(queries[s:s + 4096]), k)
+        _, i_, c_ = search(np.stack(queries[s:s + 4096]), k)
         ids, cnt = np.concatenate([ids, i_]), np.concatenate([cnt, c_])
     if len(cnt) and int(cnt.min()) == k:
         vecs.write_ivecs(path, ids)

@@ -54,6 +54,7 @@
 #include "host_mutate.h"
 #include "host_exact.h"
 #include "host_exact_range.h"
+#include "host_exact_tiered.h"
 #include "host_train.h"
 #include "host_directory.h"
 #include "host_attr.h"
@@ -1080,6 +1081,23 @@ rq_status rq_exact_range_search_device(const rq_index *idx, const rq_filter *fil
 rq_status rq_exact_range_search(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len,
                                 const float *radius, const rq_exact_params_t *params, rq_range_result **out) {
     return exact_range_host(idx, live_or(idx, filter), queries, nq, len, radius, params, out);
+}
+// ---- the same two on every f32-row index: split rows, tiered (host_exact_tiered.h) ----
+rq_status rq_exact_search_tiered_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len, uint32_t topk,
+                                        const rq_exact_params_t *params, float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n) {
+    return exact_tiered_search_device(idx, nq ? live_or(idx, filter) : filter, d_queries, nq, len, topk, params, d_out_dist, d_out_id, d_out_n);
+}
+rq_status rq_exact_search_tiered(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len, uint32_t topk,
+                                 const rq_exact_params_t *params, float *out_dist, uint32_t *out_id, uint32_t *out_n) {
+    return exact_tiered_search_host(idx, nq ? live_or(idx, filter) : filter, queries, nq, len, topk, params, out_dist, out_id, out_n);
+}
+rq_status rq_exact_range_search_tiered_device(const rq_index *idx, const rq_filter *filter, const float *d_queries, uint32_t nq, uint32_t len,
+                                              const float *d_radius, const rq_exact_params_t *params, rq_range_result **out) {
+    return exact_tiered_range_device(idx, nq ? live_or(idx, filter) : filter, d_queries, nq, len, d_radius, params, out);
+}
+rq_status rq_exact_range_search_tiered(const rq_index *idx, const rq_filter *filter, const float *queries, uint32_t nq, uint32_t len,
+                                       const float *radius, const rq_exact_params_t *params, rq_range_result **out) {
+    return exact_tiered_range_host(idx, nq ? live_or(idx, filter) : filter, queries, nq, len, radius, params, out);
 }
 rq_status rq_last_exact_stats(rq_exact_stats_t *out) {
     if (!out) return fail(RQ_ERR_INVALID, "null argument");

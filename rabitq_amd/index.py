@@ -923,6 +923,9 @@ class RaBitQ:
     def exact_search(self, queries, topk: int, filter: Filter = None, params=None):
         """The true topk nearest stored rows of every query, on the GPU -> (dist B x topk f32, ids B x topk u32, counts B u32),
         ascending by (distance, id); slots past a query's count hold NaN / 0xFFFFFFFF.  filter: only its rows can be returned."""
+        return self._exact_host(lib().rq_exact_search, queries, topk, filter, params)
+
+    def _exact_host(self, entry, queries, topk, filter, params):
         q = _f32(queries)
         if q.ndim != 2:
             raise _lib.RabitqError(-1, "queries must be 2-D")
@@ -931,9 +934,22 @@ class RaBitQ:
         ids = np.full((B, max(topk, 1)), 0xFFFFFFFF, dtype=np.uint32)
         cnt = np.zeros(B, dtype=np.uint32)
         prm = self._exact_params(params)
-        check(lib().rq_exact_search(self._h, _fh(filter), _addr(q), B, q.shape[1], topk, C.byref(prm) if prm is not None else None,
-                                    _addr(d), _addr(ids), _addr(cnt)))
+        check(entry(self._h, _fh(filter), _addr(q), B, q.shape[1], topk, C.byref(prm) if prm is not None else None,
+                    _addr(d), _addr(ids), _addr(cnt)))
         return d, ids, cnt
+
+    def exact_search_tiered(self, queries, topk: int, filter: Filter = None, params=None):
+        """exact_search on every f32-row index -- split rows, tiered, both -- with the same answer (rq_exact_search_tiered): the scan
+        reads each tier's rows linearly, and only the first plane of split rows."""
+        return self._exact_host(lib().rq_exact_search_tiered, queries, topk, filter, params)
+
+    def exact_search_tiered_device(self, q_ptr: int, nq: int, length: int, topk: int, out_dist_ptr: int, out_id_ptr: int, out_n_ptr: int,
+                                   filter: Filter = None, params=None):
+        """exact_search_tiered with queries and outputs already in device memory (raw addresses)."""
+        prm = self._exact_params(params)
+        check(lib().rq_exact_search_tiered_device(self._h, _fh(filter), C.c_void_p(q_ptr), nq, length, topk,
+                                                  C.byref(prm) if prm is not None else None, C.c_void_p(out_dist_ptr),
+                                                  C.c_void_p(out_id_ptr), C.c_void_p(out_n_ptr)))
 
     def exact_search_device(self, q_ptr: int, nq: int, length: int, topk: int, out_dist_ptr: int, out_id_ptr: int, out_n_ptr: int,
                             filter: Filter = None, params=None):
@@ -1381,18 +1397,19 @@ class RaBitQ:
                 for b in range(len(exact_cnt)) if exact_cnt[b]]
         return float(np.mean(vals)) if vals else 1.0
 
-    def recall(self, queries, probe: int, topk: int, filter: Filter = None, heuristic_rank: bool = False) -> float:
+    def recall(self, queries, probe: int, topk: int, filter: Filter = None, heuristic_rank: bool = False, tiered: bool = False) -> float:
         """What fraction of the true topk neighbours query_batch(queries, probe, topk) returns: the mean over the queries of
-        |query ids n exact ids| / exact count (queries whose exact answer is empty are left out; none left: 1.0)."""
-        _, eids, ecnt = self.exact_search(queries, topk, filter)
+        |query ids n exact ids| / exact count (queries whose exact answer is empty are left out; none left: 1.0).  tiered: the truth
+        comes from exact_search_tiered (split-row and tiered indexes, which exact_search refuses)."""
+        _, eids, ecnt = (self.exact_search_tiered if tiered else self.exact_search)(queries, topk, filter)
         _, ids, cnt = self.query_batch(queries, probe, topk, heuristic_rank, filter)
         return self._recall_of(ids, cnt, eids, ecnt)
 
-    def tune_nprobe(self, queries, topk: int, target_recall: float, filter: Filter = None):
+    def tune_nprobe(self, queries, topk: int, target_recall: float, filter: Filter = None, tiered: bool = False):
         """The smallest nprobe whose recall on these queries reaches target_recall -> (nprobe, recall); (k, recall at k) when the
         target is out of reach.  The exact answer is computed once; every probe value tried is one query_batch: doubling from 1
-        until the target is met, then bisection between the last miss and the first hit."""
-        _, eids, ecnt = self.exact_search(queries, topk, filter)
+        until the target is met, then bisection between the last miss and the first hit.  tiered: as in recall."""
+        _, eids, ecnt = (self.exact_search_tiered if tiered else self.exact_search)(queries, topk, filter)
         seen = {}
 
         def at(p):
@@ -1594,16 +1611,30 @@ class RaBitQ:
         below radius[b] (a scalar = the same radius for every query), at [lims[b], lims[b + 1]) ascending by (distance, id): what
         range_search is measured against.  filter: only its rows can be returned.  min_ip (an "ip" index, instead of radius): the rows
         whose inner product is above min_ip[b] (ip_radius).  params: the exact search's test hooks (result-neutral)."""
+        return self._exact_range_host(lib().rq_exact_range_search, queries, radius, filter, min_ip, params)
+
+    def _exact_range_host(self, entry, queries, radius, filter, min_ip, params):
         q = _f32(queries)
         if q.ndim != 2:
             raise _lib.RabitqError(-1, "queries must be 2-D")
         r = self._radii(q, radius, min_ip)
         prm = self._exact_params(params)
         h = C.c_void_p()
-        check(lib().rq_exact_range_search(self._h, _fh(filter), _addr(q), q.shape[0], q.shape[1], _addr(r),
-                                          C.byref(prm) if prm is not None else None, C.byref(h)))
+        check(entry(self._h, _fh(filter), _addr(q), q.shape[0], q.shape[1], _addr(r), C.byref(prm) if prm is not None else None, C.byref(h)))
         with RangeResult(self, h) as res:
             return res.to_host()
+
+    def exact_range_search_tiered(self, queries, radius=None, filter: Filter = None, min_ip=None, params=None):
+        """exact_range_search on every f32-row index -- split rows, tiered, both (rq_exact_range_search_tiered)."""
+        return self._exact_range_host(lib().rq_exact_range_search_tiered, queries, radius, filter, min_ip, params)
+
+    def exact_range_search_tiered_device(self, q_ptr: int, nq: int, length: int, radius_ptr: int, filter: Filter = None, params=None) -> RangeResult:
+        """exact_range_search_tiered with queries and radii already in device memory -> a RangeResult whose arrays stay on the device."""
+        prm = self._exact_params(params)
+        h = C.c_void_p()
+        check(lib().rq_exact_range_search_tiered_device(self._h, _fh(filter), C.c_void_p(q_ptr), nq, length, C.c_void_p(radius_ptr),
+                                                        C.byref(prm) if prm is not None else None, C.byref(h)))
+        return RangeResult(self, h)
 
     def exact_range_search_device(self, q_ptr: int, nq: int, length: int, radius_ptr: int, filter: Filter = None, params=None) -> RangeResult:
         """exact_range_search with queries (nq x length) and radii (nq f32) already in device memory (raw addresses) -> a
