@@ -111,7 +111,9 @@ typedef struct {
  * _values / _counts / _positions_device, rq_keyed_stats_t, rq_exact_search_keyed*, rq_last_keyed_stats, rq_keyed_tuning; no existing call, refusal
  * or output changes, and an index on which no postings are made behaves and allocates exactly as before;
  * 0.20.0: exact search on split-row and tiered indexes, additions only -- rq_exact_search_tiered*, rq_exact_range_search_tiered*; the
- * plain entries refuse those layouts as before.
+ * plain entries refuse those layouts as before;
+ * 0.21.0: multi-vector search over documents named by a column, additions only -- rq_maxsim_scores_keyed*,
+ * rq_query_batch_maxsim_keyed*; rq_maxsim_params_t, rq_maxsim_stats_t and every existing call, refusal and output are unchanged.
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -1278,6 +1280,54 @@ rq_status rq_exact_search_keyed(const rq_index *idx, const rq_postings *postings
                                 const rq_exact_params_t *params /* nullable */, float *out_dist, uint32_t *out_id, uint32_t *out_n);
 rq_status rq_last_keyed_stats(rq_keyed_stats_t *out);
 rq_status rq_keyed_tuning(uint32_t chunk_rows, uint32_t small_rows, uint32_t slabs);
+
+/* ---- multi-vector search over documents named by a column: MaxSim by postings (0.21.0, additions only) ------------------------ */
+/* The multi-vector entries above with a postings object in the place of the document stride: documents of any length, ids the
+ * caller does not get to choose.
+ * DOCUMENTS.  `postings`: a postings object of an integer column of this index; RQ_ERR_INVALID when it was made for another index
+ *   or is stale (its own check of generation and removal epoch, as rq_exact_search_keyed).  The document of key v is the set of
+ *   positions in v's segment: the rows that were live and held v when the postings were made.  The calls read no live bitmap and,
+ *   for the walk, no id directory: the epoch check is what guarantees that every posting is still a live row.  A key the postings do
+ *   not hold is a document without a row.  Documents have any length >= 1: there is no stride and no 4096 limit.
+ *   params->doc_stride must be 0 (RQ_ERR_INVALID otherwise).
+ * SCORE.  Exactly the one above, over the segment's rows: chamfer(b, v) = sum over t < T_b of min over the rows x of d(t, x), d the
+ *   engine's exact distance of the transformed token (bit for bit rq_rerank), the minimum by the smallest ord32_biased image, the sum
+ *   in f32 from +0.0f in ascending t; a NaN distance counts as 0x7FC00000 and a NaN sum is written as 0x7FC00000.
+ *   RQ_MAXSIM_NO_PREFILTER and every split of the work give the same bits; no output depends on the order of the positions inside a
+ *   segment, on the order threads run in or on an atomic's return value.  A document is scored wholly by one wave: a very long
+ *   document is that wave's serial work.
+ * rq_maxsim_scores_keyed: keys: nq x ncand rq_attr_value_t (a 4-byte type reads the low 4 bytes), cand_n[b] of them valid (null:
+ *   ncand), any order, duplicates scored independently; in HOST memory in the host form, in DEVICE memory in the _device form (they
+ *   are resolved to segments on the device; nothing waits on the host).  out_score / out_rows: nq x ncand, chamfer and the segment's
+ *   rows; padding slots and absent keys give 0x7FC00000 / 0.  topk and fetch of params are not read.
+ * rq_query_batch_maxsim_keyed: end to end, nothing travels to the host in between.  (1) rq_query_batch[_filtered](probe, fetch,
+ *   heuristic_rank) on the nq T token rows under `filter`, exactly step (1) above -- filter, probe and heuristic_rank apply here
+ *   only; (2) per query, for the result rows of its first T_b tokens: id -> position (the id directory) -> the column's value AS IT
+ *   IS NOW -> that value's segment in `postings`; a value the postings do not hold is no candidate; the segments sorted and made
+ *   unique; (3) their chamfer over the POSTINGS' rows; (4) the topk smallest (ord32_biased(chamfer), segment) -- ties go by the
+ *   column type's own ascending order of the keys.  out_dist / out_keys: nq x topk ascending, padded with 0x7FC00000 / value 0
+ *   (a 4-byte type: zero-extended); out_n[b] = documents returned; out_candidates[b] (nullable) = unique documents scored.
+ *   Step (2) reads the LIVE column while step (3) reads the SNAPSHOT: an rq_attr_set after the postings were made can route a row to
+ *   a document that no longer lists it (and the row still counts for the document that listed it).  The cure is fresh postings.
+ *   The postings' column must still exist in its type (RQ_ERR_INVALID).
+ * LIMITS.  Everything the entries above refuse stays refused: tiered, split-row, shard, dim > 4096, tokens x fetch > 2048, topk
+ *   outside [1, 2048] (RQ_ERR_UNSUPPORTED), tokens outside [1, 256], struct_size, unknown flags (RQ_ERR_INVALID).  Null arguments
+ *   and the parameter checks come before a device is looked for and before the index or the postings are read.  nq == 0 is RQ_OK.
+ * rq_last_maxsim_stats reports these calls through the same struct; rows_gathered = the postings walked. */
+rq_status rq_maxsim_scores_keyed(const rq_index *idx, const rq_postings *postings, const float *tokens, const uint32_t *n_tokens, uint32_t nq,
+                                 uint32_t len, const rq_attr_value_t *keys, const uint32_t *cand_n, uint32_t ncand,
+                                 const rq_maxsim_params_t *params, float *out_score, uint32_t *out_rows);
+rq_status rq_maxsim_scores_keyed_device(const rq_index *idx, const rq_postings *postings, const float *d_tokens, const uint32_t *d_n_tokens,
+                                        uint32_t nq, uint32_t len, const rq_attr_value_t *d_keys, const uint32_t *d_cand_n, uint32_t ncand,
+                                        const rq_maxsim_params_t *params, float *d_out_score, uint32_t *d_out_rows);
+rq_status rq_query_batch_maxsim_keyed(const rq_index *idx, const rq_postings *postings, const rq_filter *filter, const float *tokens,
+                                      const uint32_t *n_tokens, uint32_t nq, uint32_t len, uint32_t probe, int heuristic_rank,
+                                      const rq_maxsim_params_t *params, float *out_dist, rq_attr_value_t *out_keys, uint32_t *out_n,
+                                      uint32_t *out_candidates);
+rq_status rq_query_batch_maxsim_keyed_device(const rq_index *idx, const rq_postings *postings, const rq_filter *filter, const float *d_tokens,
+                                             const uint32_t *d_n_tokens, uint32_t nq, uint32_t len, uint32_t probe, int heuristic_rank,
+                                             const rq_maxsim_params_t *params, float *d_out_dist, rq_attr_value_t *d_out_keys,
+                                             uint32_t *d_out_n, uint32_t *d_out_candidates);
 
 /* ---- merge two indexes, extract a sub-index ------------------------------------------------------------------------------ */
 /* Both work on stored rows as they stand: nothing is rotated, assigned, quantised -- or, on a cosine or inner-product index,

@@ -52,6 +52,7 @@ EXPORTS = [
     "rq_maxsim_scores", "rq_maxsim_scores_device", "rq_query_batch_maxsim", "rq_query_batch_maxsim_device", "rq_last_maxsim_stats",
     "rq_postings_create", "rq_postings_free", "rq_postings_info", "rq_postings_values", "rq_postings_counts", "rq_postings_positions_device",
     "rq_exact_search_keyed", "rq_exact_search_keyed_device", "rq_last_keyed_stats", "rq_keyed_tuning",
+    "rq_maxsim_scores_keyed", "rq_maxsim_scores_keyed_device", "rq_query_batch_maxsim_keyed", "rq_query_batch_maxsim_keyed_device",
 ]
 
 
@@ -497,6 +498,10 @@ def lib():
         "rq_query_batch_maxsim": (i32, [vp, vp, f32p, u32p, u32, u32, u32, C.c_int, C.POINTER(MaxsimParamsT), f32p, u32p, u32p, u32p]),
         "rq_query_batch_maxsim_device": (i32, [vp, vp, f32p, u32p, u32, u32, u32, C.c_int, C.POINTER(MaxsimParamsT), f32p, u32p, u32p, u32p]),
         "rq_last_maxsim_stats": (i32, [C.POINTER(MaxsimStatsT)]),
+        "rq_maxsim_scores_keyed": (i32, [vp, vp, f32p, u32p, u32, u32, vp, u32p, u32, C.POINTER(MaxsimParamsT), f32p, u32p]),
+        "rq_maxsim_scores_keyed_device": (i32, [vp, vp, f32p, u32p, u32, u32, vp, u32p, u32, C.POINTER(MaxsimParamsT), f32p, u32p]),
+        "rq_query_batch_maxsim_keyed": (i32, [vp, vp, vp, f32p, u32p, u32, u32, u32, C.c_int, C.POINTER(MaxsimParamsT), f32p, vp, u32p, u32p]),
+        "rq_query_batch_maxsim_keyed_device": (i32, [vp, vp, vp, f32p, u32p, u32, u32, u32, C.c_int, C.POINTER(MaxsimParamsT), f32p, vp, u32p, u32p]),
         "rq_postings_create": (i32, [vp, C.c_char_p, pp]),
         "rq_postings_free": (None, [vp]),
         "rq_postings_info": (i32, [vp, C.POINTER(PostingsInfoT)]),

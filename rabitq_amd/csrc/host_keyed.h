@@ -21,6 +21,12 @@ struct rq_postings {
     std::vector<uint64_t> starts;                // values.size() + 1
     DevBuf<uint32_t> pos;                        // the live positions, grouped by value
     std::atomic<uint32_t> cap_hint{0};           // candidate slots per query the keyed search learnt on these postings
+    std::string column;                          // the column's name (multi-vector search by postings reads its values as they are now)
+    // the device copy of values / starts, made by the first multi-vector call by these postings and kept (host_maxsim_keyed.h)
+    std::mutex dev_mu;
+    bool dev_ready = false;
+    DevBuf<uint64_t> d_values;
+    DevBuf<uint32_t> d_starts;
     bool is_signed() const { return type == RQ_ATTR_I32 || type == RQ_ATTR_I64; }
     bool wide() const { return type >= RQ_ATTR_U64; }
 };
@@ -51,6 +57,7 @@ static rq_status postings_create(const rq_index *idx, const char *column, rq_pos
     RQC(ensure_device());
     std::unique_ptr<rq_postings> p(new rq_postings());
     p->idx = idx, p->generation = idx->generation, p->removal_epoch = idx->removal_epoch, p->type = c->type;
+    p->column = c->name;
     p->starts.assign(1, 0);
     if (idx->n == 0) {
         *out = p.release();

@@ -51,6 +51,15 @@ static inline uint32_t keyed_find(const uint64_t *values, uint32_t nv, uint64_t 
     return lo < nv && values[lo] == key ? lo : nv;
 }
 
+// m keys as the caller holds them (8-byte rq_attr_value_t images; a 4-byte type reads the low 4 bytes) -> their segments, or
+// RQ_KEYED_PAD for a key the values do not hold (multi-vector search by postings, host form: DESIGN §4.26)
+static inline void keyed_segments(const uint64_t *values, uint32_t nv, bool is_signed, bool wide, const uint64_t *keys, uint64_t m, uint32_t *out) {
+    for (uint64_t i = 0; i < m; ++i) {
+        const uint32_t s = keyed_find(values, nv, wide ? keys[i] : keys[i] & 0xFFFFFFFFull, is_signed, wide);
+        out[i] = s < nv ? s : RQ_KEYED_PAD;
+    }
+}
+
 // values[nv] ascending in the column's order, starts[nv + 1]; keys[nq]: the u64 images of the queries' keys.  matrix: the call runs
 // the matrix pass at all; seeded: it makes bounds.  Segments below small_rows postings take neither.
 static inline void keyed_plan(const uint64_t *values, const uint64_t *starts, uint32_t nv, bool is_signed, bool wide, const uint64_t *keys,

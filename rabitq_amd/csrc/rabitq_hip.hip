@@ -62,6 +62,7 @@
 #include "host_diverse.h"
 #include "host_maxsim.h"
 #include "host_keyed.h"
+#include "host_maxsim_keyed.h"
 
 // ------------------------------------------------------------------------------------------------
 // extern "C"
@@ -1402,6 +1403,38 @@ rq_status rq_exact_search_keyed(const rq_index *idx, const rq_postings *postings
                                 uint32_t len, const rq_attr_value_t *keys, uint32_t topk, const rq_exact_params_t *params, float *out_dist,
                                 uint32_t *out_id, uint32_t *out_n) {
     return by_id_done(keyed_search_host(idx, postings, filter, queries, nq, len, keys, topk, params, out_dist, out_id, out_n));
+}
+// ---- multi-vector search over documents named by a column (host_maxsim_keyed.h) ----
+static MaxsimKeyedIn maxsim_keyed_in(const rq_postings *postings, const rq_attr_value_t *keys, rq_attr_value_t *out_keys) {
+    MaxsimKeyedIn kin;
+    kin.post = postings, kin.keys = keys, kin.out_keys = out_keys;
+    return kin;
+}
+rq_status rq_maxsim_scores_keyed(const rq_index *idx, const rq_postings *postings, const float *tokens, const uint32_t *n_tokens, uint32_t nq,
+                                 uint32_t len, const rq_attr_value_t *keys, const uint32_t *cand_n, uint32_t ncand, const rq_maxsim_params_t *params,
+                                 float *out_score, uint32_t *out_rows) {
+    return by_id_done(maxsim_keyed_host(idx, maxsim_in_scores(tokens, n_tokens, len, nullptr, cand_n, ncand), maxsim_keyed_in(postings, keys, nullptr), nq,
+                                        params, MaxsimOut{out_score, out_rows, nullptr, nullptr}));
+}
+rq_status rq_maxsim_scores_keyed_device(const rq_index *idx, const rq_postings *postings, const float *d_tokens, const uint32_t *d_n_tokens,
+                                        uint32_t nq, uint32_t len, const rq_attr_value_t *d_keys, const uint32_t *d_cand_n, uint32_t ncand,
+                                        const rq_maxsim_params_t *params, float *d_out_score, uint32_t *d_out_rows) {
+    return by_id_done(maxsim_keyed_device(idx, maxsim_in_scores(d_tokens, d_n_tokens, len, nullptr, d_cand_n, ncand),
+                                          maxsim_keyed_in(postings, d_keys, nullptr), nq, params, MaxsimOut{d_out_score, d_out_rows, nullptr, nullptr}));
+}
+rq_status rq_query_batch_maxsim_keyed(const rq_index *idx, const rq_postings *postings, const rq_filter *filter, const float *tokens,
+                                      const uint32_t *n_tokens, uint32_t nq, uint32_t len, uint32_t probe, int heuristic_rank,
+                                      const rq_maxsim_params_t *params, float *out_dist, rq_attr_value_t *out_keys, uint32_t *out_n,
+                                      uint32_t *out_candidates) {
+    return by_id_done(maxsim_keyed_host(idx, maxsim_in_query(filter, tokens, n_tokens, len, probe, heuristic_rank), maxsim_keyed_in(postings, nullptr, out_keys),
+                                        nq, params, MaxsimOut{out_dist, nullptr, out_n, out_candidates}));
+}
+rq_status rq_query_batch_maxsim_keyed_device(const rq_index *idx, const rq_postings *postings, const rq_filter *filter, const float *d_tokens,
+                                             const uint32_t *d_n_tokens, uint32_t nq, uint32_t len, uint32_t probe, int heuristic_rank,
+                                             const rq_maxsim_params_t *params, float *d_out_dist, rq_attr_value_t *d_out_keys, uint32_t *d_out_n,
+                                             uint32_t *d_out_candidates) {
+    return by_id_done(maxsim_keyed_device(idx, maxsim_in_query(filter, d_tokens, d_n_tokens, len, probe, heuristic_rank),
+                                          maxsim_keyed_in(postings, nullptr, d_out_keys), nq, params, MaxsimOut{d_out_dist, nullptr, d_out_n, d_out_candidates}));
 }
 rq_status rq_keyed_tuning(uint32_t chunk_rows, uint32_t small_rows, uint32_t slabs) {
     if (slabs > 2 || (chunk_rows && chunk_rows < 32)) return fail(RQ_ERR_INVALID, "chunk_rows must be 0 or at least 32, slabs 0, 1 or 2");

@@ -250,6 +250,11 @@ class Postings:
         view = np.uint32 if self.type.elem_bytes == 4 else np.uint64
         return np.ascontiguousarray(k.view(view).astype(np.uint64))
 
+    def _values_of(self, images) -> np.ndarray:
+        """8-byte rq_attr_value_t images -> values in the column's dtype (the inverse of _keys)."""
+        img = np.ascontiguousarray(images, dtype=np.uint64)
+        return img.astype(np.uint32).view(self.type.dtype) if self.type.elem_bytes == 4 else img.view(self.type.dtype)
+
     def count_of(self, keys) -> np.ndarray:
         """Rows per key (u64), 0 for a key the postings do not hold (rq_postings_counts)."""
         img = self._keys(keys)
@@ -351,7 +356,8 @@ class DiverseResult:
 
 class MaxSimResult:
     """What query_batch_maxsim returns.  dist / docs: B x topk ascending by (Chamfer sum, document number), padded with NaN /
-    0xFFFFFFFF; counts: documents returned per query; candidates: unique documents scored per query."""
+    0xFFFFFFFF; counts: documents returned per query; candidates: unique documents scored per query.  With by=postings, docs
+    holds the documents' keys in the column's dtype, ties ascending in that type's order, padded with 0."""
     __slots__ = ("dist", "docs", "counts", "candidates")
 
     def __init__(self, dist, docs, counts, candidates):
@@ -1315,58 +1321,93 @@ class RaBitQ:
             raise _lib.RabitqError(-1, "n_tokens must hold one count per query")
         return t, nt
 
-    def maxsim_scores(self, tokens, docs, doc_stride: int, n_tokens=None, counts=None, prefilter: bool = True):
+    @staticmethod
+    def _maxsim_params(T, doc_stride, by, topk, fetch, prefilter):
+        """exactly one of doc_stride / by names the documents -> rq_maxsim_params_t (doc_stride 0 with by)"""
+        if (doc_stride is None) == (by is None):
+            raise ValueError("give exactly one of doc_stride= (documents by id arithmetic) and by= (documents by a column's postings)")
+        return _lib.MaxsimParamsT(tokens=T, doc_stride=0 if by is not None else int(doc_stride), topk=int(topk), fetch=int(fetch),
+                                  flags=0 if prefilter else _lib.MAXSIM_NO_PREFILTER)
+
+    def maxsim_scores(self, tokens, docs, doc_stride: int = None, n_tokens=None, counts=None, prefilter: bool = True, by: Postings = None):
         """The Chamfer sum of every query's tokens (B x T x d; the first n_tokens[b] of them) against the documents docs[b]
         (B x C document numbers, counts[b] valid) -> (score B x C f32, rows B x C u32).  The document of id i is i // doc_stride;
         score = sum over the tokens of the smallest exact distance to a live row of the document, rows = its live rows; a slot
         past counts[b] or a document without a live row gives NaN / 0.  Ascending score is descending MaxSim
-        (maxsim_similarity converts).  prefilter=False: every pair on the exact path (the same bits)."""
+        (maxsim_similarity converts).  prefilter=False: every pair on the exact path (the same bits).
+        by=postings instead of doc_stride: docs are keys of the postings' column and the document of a key is its rows in the
+        postings -- any length, any ids; a key the postings do not hold gives NaN / 0."""
         t, nt = self._maxsim_tokens(tokens, n_tokens)
-        d = self._id_list(docs)
+        prm = self._maxsim_params(t.shape[1], doc_stride, by, 0, 0, prefilter)
+        d = self._id_list(docs) if by is None else by._keys(docs)
         cn = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
         if d.ndim != 2 or d.shape[0] != t.shape[0] or (cn is not None and cn.size != t.shape[0]):
             raise _lib.RabitqError(-1, "docs must be B x C and counts B")
-        prm = _lib.MaxsimParamsT(tokens=t.shape[1], doc_stride=int(doc_stride), topk=0, fetch=0, flags=0 if prefilter else _lib.MAXSIM_NO_PREFILTER)
         score = np.full(d.shape, np.nan, dtype=np.float32)
         rows = np.zeros(d.shape, dtype=np.uint32)
-        check(lib().rq_maxsim_scores(self._h, _addr(t), _addr(nt), t.shape[0], t.shape[2], _addr(d), _addr(cn), d.shape[1], C.byref(prm),
-                                     _addr(score), _addr(rows)))
+        if by is None:
+            check(lib().rq_maxsim_scores(self._h, _addr(t), _addr(nt), t.shape[0], t.shape[2], _addr(d), _addr(cn), d.shape[1], C.byref(prm),
+                                         _addr(score), _addr(rows)))
+        else:
+            check(lib().rq_maxsim_scores_keyed(self._h, by._h, _addr(t), _addr(nt), t.shape[0], t.shape[2], _addr(d), _addr(cn), d.shape[1],
+                                               C.byref(prm), _addr(score), _addr(rows)))
         return score, rows
 
-    def query_batch_maxsim(self, tokens, probe: int, topk: int, doc_stride: int, fetch=None, n_tokens=None, filter: Filter = None,
-                           heuristic_rank: bool = False, prefilter: bool = True) -> "MaxSimResult":
+    def query_batch_maxsim(self, tokens, probe: int, topk: int, doc_stride: int = None, fetch=None, n_tokens=None, filter: Filter = None,
+                           heuristic_rank: bool = False, prefilter: bool = True, by: Postings = None) -> "MaxSimResult":
         """Late-interaction search on the GPU: query_batch at topk = fetch for every token (B x T x d), the documents
         id // doc_stride of the results, their Chamfer sums over ALL live rows of each document, and the topk documents with the
         smallest sum (= the largest MaxSim) -- nothing travels to the host in between.  fetch=None means
-        min(64, 2048 // T): T * fetch <= 2048."""
+        min(64, 2048 // T): T * fetch <= 2048.
+        by=postings instead of doc_stride: the document of a result row is its value in the postings' column as it is now, its
+        rows the postings' (a snapshot: after set_attr make fresh postings); MaxSimResult.docs holds keys in the column's dtype."""
         t, nt = self._maxsim_tokens(tokens, n_tokens)
         f = min(64, _lib.MAXSIM_MAX_SOURCE // max(t.shape[1], 1)) if fetch is None else int(fetch)
-        prm = _lib.MaxsimParamsT(tokens=t.shape[1], doc_stride=int(doc_stride), topk=int(topk), fetch=f, flags=0 if prefilter else _lib.MAXSIM_NO_PREFILTER)
+        prm = self._maxsim_params(t.shape[1], doc_stride, by, topk, f, prefilter)
         B, cells = t.shape[0], (t.shape[0], max(int(topk), 1))
         dist = np.full(cells, np.nan, dtype=np.float32)
-        docs = np.full(cells, 0xFFFFFFFF, dtype=np.uint32)
         cnt, cand = np.zeros(B, dtype=np.uint32), np.zeros(B, dtype=np.uint32)
-        st = lib().rq_query_batch_maxsim(self._h, _fh(filter), _addr(t), _addr(nt), B, t.shape[2], probe, int(heuristic_rank), C.byref(prm),
-                                         _addr(dist), _addr(docs), _addr(cnt), _addr(cand))
+        if by is None:
+            docs = np.full(cells, 0xFFFFFFFF, dtype=np.uint32)
+            st = lib().rq_query_batch_maxsim(self._h, _fh(filter), _addr(t), _addr(nt), B, t.shape[2], probe, int(heuristic_rank), C.byref(prm),
+                                             _addr(dist), _addr(docs), _addr(cnt), _addr(cand))
+        else:
+            img = np.zeros(cells, dtype=np.uint64)
+            st = lib().rq_query_batch_maxsim_keyed(self._h, by._h, _fh(filter), _addr(t), _addr(nt), B, t.shape[2], probe, int(heuristic_rank),
+                                                   C.byref(prm), _addr(dist), _addr(img), _addr(cnt), _addr(cand))
+            docs = by._values_of(img)
         if st != _lib.RQ_ERR_EMPTY:
             check(st)
         return MaxSimResult(dist, docs, cnt, cand)
 
     def maxsim_scores_device(self, tokens_ptr: int, n_tokens_ptr: int, nq: int, T: int, length: int, docs_ptr: int, counts_ptr: int, ncand: int,
-                             doc_stride: int, out_score_ptr: int, out_rows_ptr: int, prefilter: bool = True) -> None:
-        """maxsim_scores with every array in device memory (raw addresses; n_tokens / counts 0 = none)."""
-        prm = _lib.MaxsimParamsT(tokens=T, doc_stride=int(doc_stride), topk=0, fetch=0, flags=0 if prefilter else _lib.MAXSIM_NO_PREFILTER)
-        check(lib().rq_maxsim_scores_device(self._h, C.c_void_p(tokens_ptr), C.c_void_p(n_tokens_ptr), nq, length, C.c_void_p(docs_ptr),
-                                            C.c_void_p(counts_ptr), ncand, C.byref(prm), C.c_void_p(out_score_ptr), C.c_void_p(out_rows_ptr)))
+                             doc_stride: int = None, out_score_ptr: int = 0, out_rows_ptr: int = 0, prefilter: bool = True, by: Postings = None) -> None:
+        """maxsim_scores with every array in device memory (raw addresses; n_tokens / counts 0 = none).  by=postings: docs_ptr
+        holds nq x ncand 8-byte keys (rq_attr_value_t images, a 4-byte value zero-extended) in device memory."""
+        prm = self._maxsim_params(T, doc_stride, by, 0, 0, prefilter)
+        if by is None:
+            check(lib().rq_maxsim_scores_device(self._h, C.c_void_p(tokens_ptr), C.c_void_p(n_tokens_ptr), nq, length, C.c_void_p(docs_ptr),
+                                                C.c_void_p(counts_ptr), ncand, C.byref(prm), C.c_void_p(out_score_ptr), C.c_void_p(out_rows_ptr)))
+        else:
+            check(lib().rq_maxsim_scores_keyed_device(self._h, by._h, C.c_void_p(tokens_ptr), C.c_void_p(n_tokens_ptr), nq, length,
+                                                      C.c_void_p(docs_ptr), C.c_void_p(counts_ptr), ncand, C.byref(prm),
+                                                      C.c_void_p(out_score_ptr), C.c_void_p(out_rows_ptr)))
 
-    def query_batch_maxsim_device(self, tokens_ptr: int, n_tokens_ptr: int, nq: int, T: int, length: int, probe: int, topk: int, doc_stride: int,
-                                  fetch: int, out_dist_ptr: int, out_docs_ptr: int, out_n_ptr: int, out_candidates_ptr: int = 0,
-                                  heuristic_rank: bool = False, filter: Filter = None, prefilter: bool = True) -> None:
-        """query_batch_maxsim with tokens and outputs in device memory (raw addresses; candidates 0 = not wanted)."""
-        prm = _lib.MaxsimParamsT(tokens=T, doc_stride=int(doc_stride), topk=int(topk), fetch=int(fetch), flags=0 if prefilter else _lib.MAXSIM_NO_PREFILTER)
-        st = lib().rq_query_batch_maxsim_device(self._h, _fh(filter), C.c_void_p(tokens_ptr), C.c_void_p(n_tokens_ptr), nq, length, probe,
-                                                int(heuristic_rank), C.byref(prm), C.c_void_p(out_dist_ptr), C.c_void_p(out_docs_ptr),
-                                                C.c_void_p(out_n_ptr), C.c_void_p(out_candidates_ptr))
+    def query_batch_maxsim_device(self, tokens_ptr: int, n_tokens_ptr: int, nq: int, T: int, length: int, probe: int, topk: int,
+                                  doc_stride: int = None, fetch: int = 0, out_dist_ptr: int = 0, out_docs_ptr: int = 0, out_n_ptr: int = 0,
+                                  out_candidates_ptr: int = 0, heuristic_rank: bool = False, filter: Filter = None, prefilter: bool = True,
+                                  by: Postings = None) -> None:
+        """query_batch_maxsim with tokens and outputs in device memory (raw addresses; candidates 0 = not wanted).  by=postings:
+        out_docs_ptr receives nq x topk 8-byte keys."""
+        prm = self._maxsim_params(T, doc_stride, by, topk, fetch, prefilter)
+        if by is None:
+            st = lib().rq_query_batch_maxsim_device(self._h, _fh(filter), C.c_void_p(tokens_ptr), C.c_void_p(n_tokens_ptr), nq, length, probe,
+                                                    int(heuristic_rank), C.byref(prm), C.c_void_p(out_dist_ptr), C.c_void_p(out_docs_ptr),
+                                                    C.c_void_p(out_n_ptr), C.c_void_p(out_candidates_ptr))
+        else:
+            st = lib().rq_query_batch_maxsim_keyed_device(self._h, by._h, _fh(filter), C.c_void_p(tokens_ptr), C.c_void_p(n_tokens_ptr), nq, length,
+                                                          probe, int(heuristic_rank), C.byref(prm), C.c_void_p(out_dist_ptr),
+                                                          C.c_void_p(out_docs_ptr), C.c_void_p(out_n_ptr), C.c_void_p(out_candidates_ptr))
         if st != _lib.RQ_ERR_EMPTY:
             check(st)
 
