@@ -113,7 +113,9 @@ typedef struct {
  * 0.20.0: exact search on split-row and tiered indexes, additions only -- rq_exact_search_tiered*, rq_exact_range_search_tiered*; the
  * plain entries refuse those layouts as before;
  * 0.21.0: multi-vector search over documents named by a column, additions only -- rq_maxsim_scores_keyed*,
- * rq_query_batch_maxsim_keyed*; rq_maxsim_params_t, rq_maxsim_stats_t and every existing call, refusal and output are unchanged.
+ * rq_query_batch_maxsim_keyed*; rq_maxsim_params_t, rq_maxsim_stats_t and every existing call, refusal and output are unchanged;
+ * 0.22.0: the complete exact grouped search, additions only -- rq_exact_search_grouped_full*, rq_group_full_stats_t,
+ * rq_last_group_full_stats; no existing call, refusal or output changes, and postings on which it is never called allocate as before.
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -1328,6 +1330,59 @@ rq_status rq_query_batch_maxsim_keyed_device(const rq_index *idx, const rq_posti
                                              const uint32_t *d_n_tokens, uint32_t nq, uint32_t len, uint32_t probe, int heuristic_rank,
                                              const rq_maxsim_params_t *params, float *d_out_dist, rq_attr_value_t *d_out_keys,
                                              uint32_t *d_out_n, uint32_t *d_out_candidates);
+
+/* ---- the complete exact grouped search: the true topk groups from one pass over all rows (0.22.0, additions only) ------------- */
+/* rq_exact_search_grouped answers "grouped top-fetch" (fetch <= 2048): when a query's nearest 3 000 rows share one value it returns
+ * that one group at every legal fetch.  These entries return the answer over ALL rows, at any group count and density.
+ * ROWS.  Query b sees the rows rq_exact_search_keyed would see over all of the postings' values: the rows live when `postings` was
+ *   made (a stale or foreign postings object is RQ_ERR_INVALID, exactly as there), intersected with `filter` (nullable), with exact
+ *   distance e < f32::MAX (NaN excluded), e the library's one exact-order distance (bit for bit rq_rerank).
+ * KEYS.  A row's group is its segment of the postings: its column value when they were made (a later rq_attr_set does not move it,
+ *   as for the keyed search).  out_key is the u64 image of that value (grouped search's image).
+ * SELECTION.  Grouped search's, word for word, applied to the COMPLETE sequence of those rows sorted by ord32_biased(e) << 32 | id:
+ *   a row is kept iff ord(its key) < topk and rank(row) < group_size.  So the groups are the topk values with the smallest minimum
+ *   distance, ascending by (that minimum, its id), each with its group_size nearest rows.
+ * OUTPUT.  Grouped search's layout and padding: group-major out_id / out_dist[b, ord * group_size + rank], out_key / out_group_n
+ *   [b, ord], out_n[b]; every slot without a row holds id 0xFFFFFFFF, dist 0x7FC00000, key 0, group_n 0 and every slot is written
+ *   on every call.  out_fetched[b] (nullable): the rows the query's selection looked at -- informational, it depends on the bound.
+ *   The same inputs give the same bits on every run; nothing depends on `exact` (the exact search's test hooks), on options, on how
+ *   the batch is split or on tuning numbers.
+ * LIMITS.  1 <= topk, 1 <= group_size, topk * group_size <= 2048 (RQ_ERR_UNSUPPORTED); params->fetch must be 0, params->flags 0,
+ *   params->struct_size == sizeof(rq_group_params_t), no null argument but filter, exact and out_fetched (RQ_ERR_INVALID): all of
+ *   these are refused before a device is looked for.  Then: postings of another index or stale ones, a stale or foreign filter
+ *   (RQ_ERR_INVALID), and the layouts rq_exact_search refuses -- tiered and split-row indexes (RQ_ERR_UNSUPPORTED).  nq == 0 is
+ *   RQ_OK.  No source call here can answer RQ_ERR_EMPTY.  rq_metrics is not touched.  _device form: every pointer but params and
+ *   exact in device memory; it returns with its outputs complete.  No relayout may run during a call.
+ * MEMORY.  The first call by a postings object makes its position -> segment array (4 bytes per stored row, kept until
+ *   rq_postings_free; rq_group_full_stats_t.inverse_bytes).  Work memory follows the (query, row) pairs the scan keeps.
+ * rq_last_group_full_stats: the calling thread's last call of these entries. */
+typedef struct {
+    uint32_t struct_size;   /* in: sizeof(rq_group_full_stats_t) of the caller */
+    uint32_t scan_reruns;   /* scan launches repeated because the records did not fit the arena */
+    float ms_inverse;       /* wall ms of the position -> segment array (0 unless inverse_built) */
+    float ms_bound;         /* device ms of the bounds: the sample's scan, exact distances and distinct-minimum selection */
+    float ms_scan;          /* device ms of the scan launches (re-runs included) */
+    float ms_exact;         /* device ms of the records' exact distances and segments */
+    float ms_scatter;       /* device ms of the offsets and of the hits' scatter into per-query segments */
+    float ms_select;        /* device ms of the distinct-minimum selection */
+    float ms_rows;          /* wall ms of the second phase: the read-back, the plan and the keyed search (group_size > 1) */
+    uint32_t inverse_built; /* 1: this call made the postings' position -> segment array */
+    uint64_t inverse_bytes; /* bytes of that array */
+    uint64_t records;       /* (query, row) pairs the scan kept */
+    uint64_t hits;          /* of them, pairs with e <= T_q in a segment: what the selection read */
+    uint64_t plan_queries;  /* second phase: plan-queries of the keyed search (nq x topk) */
+    uint64_t rows_listed;   /* second phase: postings its scan items covered */
+} rq_group_full_stats_t;
+rq_status rq_exact_search_grouped_full(const rq_index *idx, const rq_postings *postings, const rq_filter *filter /* nullable */,
+                                       const float *queries, uint32_t nq, uint32_t len, const rq_exact_params_t *exact /* nullable */,
+                                       const rq_group_params_t *params, float *out_dist, uint32_t *out_id, uint64_t *out_key,
+                                       uint32_t *out_group_n, uint32_t *out_n, uint32_t *out_fetched /* nullable */);
+rq_status rq_exact_search_grouped_full_device(const rq_index *idx, const rq_postings *postings, const rq_filter *filter /* nullable */,
+                                              const float *d_queries, uint32_t nq, uint32_t len, const rq_exact_params_t *exact /* nullable */,
+                                              const rq_group_params_t *params, float *d_out_dist, uint32_t *d_out_id,
+                                              uint64_t *d_out_key, uint32_t *d_out_group_n, uint32_t *d_out_n,
+                                              uint32_t *d_out_fetched /* nullable */);
+rq_status rq_last_group_full_stats(rq_group_full_stats_t *out);
 
 /* ---- merge two indexes, extract a sub-index ------------------------------------------------------------------------------ */
 /* Both work on stored rows as they stand: nothing is rotated, assigned, quantised -- or, on a cosine or inner-product index,

@@ -53,6 +53,7 @@ EXPORTS = [
     "rq_postings_create", "rq_postings_free", "rq_postings_info", "rq_postings_values", "rq_postings_counts", "rq_postings_positions_device",
     "rq_exact_search_keyed", "rq_exact_search_keyed_device", "rq_last_keyed_stats", "rq_keyed_tuning",
     "rq_maxsim_scores_keyed", "rq_maxsim_scores_keyed_device", "rq_query_batch_maxsim_keyed", "rq_query_batch_maxsim_keyed_device",
+    "rq_exact_search_grouped_full", "rq_exact_search_grouped_full_device", "rq_last_group_full_stats",
 ]
 
 
@@ -305,6 +306,14 @@ class KeyedStatsT(_Sized):
         ("rows_listed", C.c_uint64)]
 
 
+class GroupFullStatsT(_Sized):
+    """rq_group_full_stats_t: the calling thread's last complete exact grouped search."""
+    _fields_ = [("struct_size", C.c_uint32), ("scan_reruns", C.c_uint32)] + [(n, C.c_float) for n in (
+        "ms_inverse", "ms_bound", "ms_scan", "ms_exact", "ms_scatter", "ms_select", "ms_rows")] + [
+        ("inverse_built", C.c_uint32), ("inverse_bytes", C.c_uint64), ("records", C.c_uint64), ("hits", C.c_uint64),
+        ("plan_queries", C.c_uint64), ("rows_listed", C.c_uint64)]
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP library for gfx950 (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", CSRC] + (["-B"] if force else [])
@@ -512,6 +521,9 @@ def lib():
         "rq_exact_search_keyed_device": (i32, [vp, vp, vp, f32p, u32, u32, vp, u32, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
         "rq_last_keyed_stats": (i32, [C.POINTER(KeyedStatsT)]),
         "rq_keyed_tuning": (i32, [u32, u32, u32]),
+        "rq_exact_search_grouped_full": (i32, [vp, vp, vp, f32p, u32, u32, C.POINTER(ExactParamsT), C.POINTER(GroupParamsT), f32p, u32p, u64p, u32p, u32p, u32p]),
+        "rq_exact_search_grouped_full_device": (i32, [vp, vp, vp, f32p, u32, u32, C.POINTER(ExactParamsT), C.POINTER(GroupParamsT), f32p, u32p, u64p, u32p, u32p, u32p]),
+        "rq_last_group_full_stats": (i32, [C.POINTER(GroupFullStatsT)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError if the .so lacks a declared symbol

@@ -27,6 +27,10 @@ struct rq_postings {
     bool dev_ready = false;
     DevBuf<uint64_t> d_values;
     DevBuf<uint32_t> d_starts;
+    // position -> segment, made by the first complete grouped call by these postings and kept (host_group_full.h; under dev_mu too)
+    bool inverse_ready = false;
+    DevBuf<uint32_t> inverse;
+    std::atomic<uint32_t> full_cap_hint{0};      // arena records per query the complete grouped search learnt on these postings
     bool is_signed() const { return type == RQ_ATTR_I32 || type == RQ_ATTR_I64; }
     bool wide() const { return type >= RQ_ATTR_U64; }
 };

@@ -63,6 +63,7 @@
 #include "host_maxsim.h"
 #include "host_keyed.h"
 #include "host_maxsim_keyed.h"
+#include "host_group_full.h"
 
 // ------------------------------------------------------------------------------------------------
 // extern "C"
@@ -1403,6 +1404,23 @@ rq_status rq_exact_search_keyed(const rq_index *idx, const rq_postings *postings
                                 uint32_t len, const rq_attr_value_t *keys, uint32_t topk, const rq_exact_params_t *params, float *out_dist,
                                 uint32_t *out_id, uint32_t *out_n) {
     return by_id_done(keyed_search_host(idx, postings, filter, queries, nq, len, keys, topk, params, out_dist, out_id, out_n));
+}
+// ---- the complete exact grouped search (host_group_full.h): the true topk groups from one pass over all rows ----
+rq_status rq_exact_search_grouped_full(const rq_index *idx, const rq_postings *postings, const rq_filter *filter, const float *queries, uint32_t nq,
+                                       uint32_t len, const rq_exact_params_t *exact, const rq_group_params_t *params, float *out_dist,
+                                       uint32_t *out_id, uint64_t *out_key, uint32_t *out_group_n, uint32_t *out_n, uint32_t *out_fetched) {
+    return by_id_done(group_full_host(idx, postings, filter, queries, nq, len, exact, params, GroupOut{out_dist, out_id, out_key, out_group_n, out_n, out_fetched}));
+}
+rq_status rq_exact_search_grouped_full_device(const rq_index *idx, const rq_postings *postings, const rq_filter *filter, const float *d_queries,
+                                              uint32_t nq, uint32_t len, const rq_exact_params_t *exact, const rq_group_params_t *params,
+                                              float *d_out_dist, uint32_t *d_out_id, uint64_t *d_out_key, uint32_t *d_out_group_n,
+                                              uint32_t *d_out_n, uint32_t *d_out_fetched) {
+    return by_id_done(group_full_device(idx, postings, filter, d_queries, nq, len, exact, params,
+                                        GroupOut{d_out_dist, d_out_id, d_out_key, d_out_group_n, d_out_n, d_out_fetched}));
+}
+rq_status rq_last_group_full_stats(rq_group_full_stats_t *out) {
+    if (!out) return fail(RQ_ERR_INVALID, "null argument");
+    return copy_out_sized(out, g_group_full_stats);
 }
 // ---- multi-vector search over documents named by a column (host_maxsim_keyed.h) ----
 static MaxsimKeyedIn maxsim_keyed_in(const rq_postings *postings, const rq_attr_value_t *keys, rq_attr_value_t *out_keys) {

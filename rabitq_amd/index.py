@@ -370,14 +370,22 @@ class MaxSimResult:
 class GroupedResult:
     """What a host-form grouped call returns.  dist / ids: B x topk x group_size, group-major, padded with NaN / 0xFFFFFFFF; keys
     (the column's dtype) and group_counts (rows kept per group): B x topk, padded with 0; counts: groups per query; fetched:
-    candidates the source call gave per query (None from group_results)."""
+    candidates the source call gave per query (None from group_results).  complete: False -- the answer is "grouped top-fetch"."""
     __slots__ = ("dist", "ids", "keys", "group_counts", "counts", "fetched")
+    complete = False
 
     def __init__(self, dist, ids, keys, group_counts, counts, fetched):
         self.dist, self.ids, self.keys, self.group_counts, self.counts, self.fetched = dist, ids, keys, group_counts, counts, fetched
 
     def __repr__(self):
         return f"GroupedResult(queries={self.counts.size}, topk={self.keys.shape[1]}, group_size={self.ids.shape[2]})"
+
+
+class CompleteGroupedResult(GroupedResult):
+    """What exact_search_grouped returns when it groups by postings: the true answer over all rows (complete is True); fetched is
+    the rows each query's selection looked at, informational only."""
+    __slots__ = ()
+    complete = True
 
 
 class RaBitQ:
@@ -1120,7 +1128,7 @@ class RaBitQ:
         f = _lib.default_group_fetch(topk, group_size) if fetch is None else int(fetch)
         return _lib.GroupParamsT(topk=int(topk), group_size=int(group_size), fetch=f, flags=0)
 
-    def _grouped_host(self, call, B, prm, group_by, with_fetched):
+    def _grouped_host(self, call, B, prm, group_by, with_fetched, result=None):
         """The outputs of a host-form grouped call, made, filled by call(addresses...) and wrapped."""
         t = self._attr(group_by)
         cells = (B, max(prm.topk, 1), max(prm.group_size, 1))
@@ -1135,7 +1143,7 @@ class RaBitQ:
             check(st)
         if t.elem_bytes == 4:
             keys = keys.astype(np.uint32)   # (the u64 image of a 4-byte value is zero-extended)
-        return GroupedResult(d, ids, keys.view(t.dtype), gn, cnt, fetched)
+        return (result or GroupedResult)(d, ids, keys.view(t.dtype), gn, cnt, fetched)
 
     def query_batch_grouped(self, queries, probe: int, topk: int, group_by: str, group_size: int = 1, fetch=None,
                             heuristic_rank: bool = False, filter: Filter = None) -> "GroupedResult":
@@ -1151,18 +1159,48 @@ class RaBitQ:
             self._h, _fh(filter), _addr(q), q.shape[0], q.shape[1], probe, int(heuristic_rank), group_by.encode(), C.byref(prm), *out),
             q.shape[0], prm, group_by, True)
 
-    def exact_search_grouped(self, queries, topk: int, group_by: str, group_size: int = 1, fetch=None, filter: Filter = None,
+    def exact_search_grouped(self, queries, topk: int, group_by, group_size: int = 1, fetch=None, filter: Filter = None,
                              params=None) -> "GroupedResult":
         """query_batch_grouped over exact_search at topk = fetch.  Where result.fetched[b] < fetch the answer is the true grouped
-        answer over all admitted rows; with group_size == 1, counts[b] == topk proves it too."""
+        answer over all admitted rows; with group_size == 1, counts[b] == topk proves it too.
+        group_by=self.postings(column) -- a Postings object in the place of the column's name -- selects the COMPLETE form
+        (rq_exact_search_grouped_full): the true topk groups over all rows of the postings (under `filter`), however many rows a
+        group holds: one scan of all rows, a distinct-minimum selection per query and, for group_size > 1, the keyed search over
+        the chosen values.  fetch must then be None; a row's key is its value when the postings were made; result.complete is
+        True and result.fetched the rows each selection looked at (informational)."""
         q = _f32(queries)
         if q.ndim != 2:
             raise _lib.RabitqError(-1, "queries must be 2-D")
+        if isinstance(group_by, Postings):
+            if fetch is not None:
+                raise _lib.RabitqError(-1, "fetch must be None when grouping by postings: the complete form sees every row")
+            prm = _lib.GroupParamsT(topk=int(topk), group_size=int(group_size), fetch=0, flags=0)
+            ex = self._exact_params(params)
+            return self._grouped_host(lambda *out: lib().rq_exact_search_grouped_full(
+                self._h, group_by._h, _fh(filter), _addr(q), q.shape[0], q.shape[1], C.byref(ex) if ex is not None else None, C.byref(prm),
+                *out), q.shape[0], prm, group_by.column, True, CompleteGroupedResult)
         prm = self._group_params(topk, group_size, fetch)
         ex = self._exact_params(params)
         return self._grouped_host(lambda *out: lib().rq_exact_search_grouped(
             self._h, _fh(filter), _addr(q), q.shape[0], q.shape[1], C.byref(ex) if ex is not None else None, group_by.encode(),
             C.byref(prm), *out), q.shape[0], prm, group_by, True)
+
+    def exact_search_grouped_full_device(self, q_ptr: int, nq: int, length: int, topk: int, by: Postings, out_dist_ptr: int, out_id_ptr: int,
+                                         out_key_ptr: int, out_group_n_ptr: int, out_n_ptr: int, out_fetched_ptr: int = 0,
+                                         group_size: int = 1, filter: Filter = None, params=None) -> None:
+        """The complete form of exact_search_grouped (group_by = postings) with queries and outputs in device memory (raw addresses, as
+        query_batch_grouped_device)."""
+        prm = _lib.GroupParamsT(topk=int(topk), group_size=int(group_size), fetch=0, flags=0)
+        ex = self._exact_params(params)
+        check(lib().rq_exact_search_grouped_full_device(self._h, by._h, _fh(filter), C.c_void_p(q_ptr), nq, length,
+                                                        C.byref(ex) if ex is not None else None, C.byref(prm), C.c_void_p(out_dist_ptr),
+                                                        C.c_void_p(out_id_ptr), C.c_void_p(out_key_ptr), C.c_void_p(out_group_n_ptr),
+                                                        C.c_void_p(out_n_ptr), C.c_void_p(out_fetched_ptr)))
+
+    @staticmethod
+    def last_group_full_stats() -> dict:
+        """The calling thread's last complete exact grouped search (include/rabitq_hip.h: rq_group_full_stats_t)."""
+        return last_group_full_stats()
 
     def group_results(self, dist, ids, counts, topk: int, group_by: str, group_size: int = 1) -> "GroupedResult":
         """The selection alone over result rows the caller has (dist / ids B x fetch, counts B; fetch = their width): those of
@@ -1903,6 +1941,13 @@ def last_diverse_stats() -> dict:
     st = _lib.DiverseStatsT()
     check(lib().rq_last_diverse_stats(C.byref(st)))
     return {name: getattr(st, name) for name, _ in _lib.DiverseStatsT._fields_ if name not in ("struct_size", "reserved0")}
+
+
+def last_group_full_stats() -> dict:
+    """The calling thread's last complete exact grouped search (include/rabitq_hip.h: rq_last_group_full_stats)."""
+    st = _lib.GroupFullStatsT()
+    check(lib().rq_last_group_full_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _lib.GroupFullStatsT._fields_ if name != "struct_size"}
 
 
 def last_group_stats() -> dict:
