@@ -115,7 +115,9 @@ typedef struct {
  * 0.21.0: multi-vector search over documents named by a column, additions only -- rq_maxsim_scores_keyed*,
  * rq_query_batch_maxsim_keyed*; rq_maxsim_params_t, rq_maxsim_stats_t and every existing call, refusal and output are unchanged;
  * 0.22.0: the complete exact grouped search, additions only -- rq_exact_search_grouped_full*, rq_group_full_stats_t,
- * rq_last_group_full_stats; no existing call, refusal or output changes, and postings on which it is never called allocate as before.
+ * rq_last_group_full_stats; no existing call, refusal or output changes, and postings on which it is never called allocate as before;
+ * 0.23.0: exact multi-vector search, additions only -- rq_exact_search_maxsim*, rq_maxsim_exact_stats_t, rq_last_maxsim_exact_stats;
+ * rq_maxsim_params_t and every existing call, refusal and output are unchanged.
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -1330,6 +1332,53 @@ rq_status rq_query_batch_maxsim_keyed_device(const rq_index *idx, const rq_posti
                                              const uint32_t *d_n_tokens, uint32_t nq, uint32_t len, uint32_t probe, int heuristic_rank,
                                              const rq_maxsim_params_t *params, float *d_out_dist, rq_attr_value_t *d_out_keys,
                                              uint32_t *d_out_n, uint32_t *d_out_candidates);
+
+/* ---- exact multi-vector search: the true topk documents over all postings (0.23.0, additions only) --------------------------- */
+/* rq_query_batch_maxsim_keyed scores the documents that the per-token plain queries surface.  These entries return the ground truth
+ * it is measured against: the best documents over ALL segments of the postings.
+ * DOCUMENTS.  Exactly those of the section above: a document is a segment of `postings` (foreign or stale postings: RQ_ERR_INVALID).
+ * SCORE.  chamfer of the multi-vector sections, word for word: d(t, x) the engine's exact distance (exact_l2_row, bit for bit
+ *   rq_rerank), a token's minimum by the smallest ord32_biased image, the sum in f32 from +0.0f in ascending t, a NaN distance
+ *   counted as 0x7FC00000 and a NaN sum written as 0x7FC00000.
+ * RESULT.  Per query the topk segments with the smallest (ord32_biased(chamfer), segment number) over all segments -- ties go by
+ *   the column type's own ascending order of the keys.  out_dist / out_keys: nq x topk ascending, padded with 0x7FC00000 / value 0
+ *   (a 4-byte type: zero-extended), out_n[b] = documents returned = min(topk, segments): the shape of rq_query_batch_maxsim_keyed's
+ *   outputs.  The result is bit-identical to rq_maxsim_scores_keyed over every key of the postings followed by a sort.  The same
+ *   inputs give the same bits on every run, with RQ_MAXSIM_NO_PREFILTER (every document scored on the exact path) and for every
+ *   split of the work: the bound pass that runs otherwise only decides which documents are scored, never a score.
+ * params: rq_maxsim_params_t as it is.  doc_stride must be 0 and fetch must be 0 (RQ_ERR_INVALID), tokens in [1, 256]
+ *   (RQ_ERR_INVALID), topk in [1, 2048] (RQ_ERR_UNSUPPORTED).  THERE IS NO FILTER ARGUMENT in this revision: every posting counts.
+ * LIMITS.  Those of the section above: tiered and split-row indexes, shards, dim > 4096 (RQ_ERR_UNSUPPORTED).  Null arguments and
+ *   the parameter checks come before a device is looked for and before the index or the postings are read.  nq == 0 is RQ_OK.
+ *   _device form: tokens, n_tokens and the outputs in device memory; it returns with its outputs complete.
+ * MEMORY.  Work memory is 12 bytes per (query, segment) for the queries of one pass, at most 256 MiB unless one query needs more;
+ *   larger batches run in passes.
+ * rq_last_maxsim_exact_stats: the calling thread's last call of these entries. */
+typedef struct {
+    uint32_t struct_size;    /* set to sizeof(rq_maxsim_exact_stats_t) before the call */
+    uint32_t prefilter;      /* 1: the bound pass ran; 0: every document was scored (RQ_MAXSIM_NO_PREFILTER, or the shape does not fit) */
+    float ms_bound;          /* device ms of the bound pass, the thresholds and the survivors' compaction */
+    float ms_score;          /* device ms of the scoring rounds and their merges */
+    float ms_total;          /* wall ms of the call */
+    uint32_t chunk_queries;  /* queries that share one gathered row tile in the bound pass (Bc) */
+    uint32_t query_chunks;   /* chunks of Bc queries the bound pass ran (over all passes) */
+    uint32_t rounds;         /* scoring rounds */
+    uint32_t passes;         /* passes over the postings (work memory bounds the queries of one) */
+    uint32_t lds_bytes;      /* LDS of a block of the bound pass */
+    uint32_t image_in_lds;   /* 1: a chunk's token image is staged in LDS; 0: read through the L2 */
+    uint32_t reserved0;
+    uint64_t documents;      /* segments of the postings */
+    uint64_t postings_walked;/* postings gathered by the bound pass (every chunk walks all of them) */
+    uint64_t survivors;      /* (query, document) pairs scored exactly */
+    uint64_t pairs;          /* (token, row) pairs of the exact scoring */
+} rq_maxsim_exact_stats_t;
+rq_status rq_exact_search_maxsim(const rq_index *idx, const rq_postings *postings, const float *tokens, const uint32_t *n_tokens /* nullable */,
+                                 uint32_t nq, uint32_t len, const rq_maxsim_params_t *params, float *out_dist, rq_attr_value_t *out_keys,
+                                 uint32_t *out_n);
+rq_status rq_exact_search_maxsim_device(const rq_index *idx, const rq_postings *postings, const float *d_tokens,
+                                        const uint32_t *d_n_tokens /* nullable */, uint32_t nq, uint32_t len, const rq_maxsim_params_t *params,
+                                        float *d_out_dist, rq_attr_value_t *d_out_keys, uint32_t *d_out_n);
+rq_status rq_last_maxsim_exact_stats(rq_maxsim_exact_stats_t *out);
 
 /* ---- the complete exact grouped search: the true topk groups from one pass over all rows (0.22.0, additions only) ------------- */
 /* rq_exact_search_grouped answers "grouped top-fetch" (fetch <= 2048): when a query's nearest 3 000 rows share one value it returns

@@ -53,6 +53,7 @@ EXPORTS = [
     "rq_postings_create", "rq_postings_free", "rq_postings_info", "rq_postings_values", "rq_postings_counts", "rq_postings_positions_device",
     "rq_exact_search_keyed", "rq_exact_search_keyed_device", "rq_last_keyed_stats", "rq_keyed_tuning",
     "rq_maxsim_scores_keyed", "rq_maxsim_scores_keyed_device", "rq_query_batch_maxsim_keyed", "rq_query_batch_maxsim_keyed_device",
+    "rq_exact_search_maxsim", "rq_exact_search_maxsim_device", "rq_last_maxsim_exact_stats",
     "rq_exact_search_grouped_full", "rq_exact_search_grouped_full_device", "rq_last_group_full_stats",
 ]
 
@@ -292,6 +293,13 @@ class MaxsimStatsT(_Sized):
                 ("reserved0", C.c_uint32)]
 
 
+class MaxsimExactStatsT(_Sized):
+    """rq_maxsim_exact_stats_t: the calling thread's last exact multi-vector search."""
+    _fields_ = [("struct_size", C.c_uint32), ("prefilter", C.c_uint32), ("ms_bound", C.c_float), ("ms_score", C.c_float), ("ms_total", C.c_float)] + [
+        (n, C.c_uint32) for n in ("chunk_queries", "query_chunks", "rounds", "passes", "lds_bytes", "image_in_lds", "reserved0")] + [
+        (n, C.c_uint64) for n in ("documents", "postings_walked", "survivors", "pairs")]
+
+
 class PostingsInfoT(_Sized):
     """rq_postings_info_t: distinct values, live rows, column type and bytes of a postings object."""
     _fields_ = [("struct_size", C.c_uint32), ("type", C.c_uint32), ("values", C.c_uint64), ("rows", C.c_uint64), ("bytes", C.c_uint64)]
@@ -511,6 +519,9 @@ def lib():
         "rq_maxsim_scores_keyed_device": (i32, [vp, vp, f32p, u32p, u32, u32, vp, u32p, u32, C.POINTER(MaxsimParamsT), f32p, u32p]),
         "rq_query_batch_maxsim_keyed": (i32, [vp, vp, vp, f32p, u32p, u32, u32, u32, C.c_int, C.POINTER(MaxsimParamsT), f32p, vp, u32p, u32p]),
         "rq_query_batch_maxsim_keyed_device": (i32, [vp, vp, vp, f32p, u32p, u32, u32, u32, C.c_int, C.POINTER(MaxsimParamsT), f32p, vp, u32p, u32p]),
+        "rq_exact_search_maxsim": (i32, [vp, vp, f32p, u32p, u32, u32, C.POINTER(MaxsimParamsT), f32p, vp, u32p]),
+        "rq_exact_search_maxsim_device": (i32, [vp, vp, f32p, u32p, u32, u32, C.POINTER(MaxsimParamsT), f32p, vp, u32p]),
+        "rq_last_maxsim_exact_stats": (i32, [C.POINTER(MaxsimExactStatsT)]),
         "rq_postings_create": (i32, [vp, C.c_char_p, pp]),
         "rq_postings_free": (None, [vp]),
         "rq_postings_info": (i32, [vp, C.POINTER(PostingsInfoT)]),

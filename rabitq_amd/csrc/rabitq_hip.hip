@@ -63,6 +63,7 @@
 #include "host_maxsim.h"
 #include "host_keyed.h"
 #include "host_maxsim_keyed.h"
+#include "host_maxsim_exact.h"
 #include "host_group_full.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1422,6 +1423,21 @@ rq_status rq_last_group_full_stats(rq_group_full_stats_t *out) {
     if (!out) return fail(RQ_ERR_INVALID, "null argument");
     return copy_out_sized(out, g_group_full_stats);
 }
+// ---- exact multi-vector search: the true topk documents over all postings (host_maxsim_exact.h) ----
+rq_status rq_exact_search_maxsim(const rq_index *idx, const rq_postings *postings, const float *tokens, const uint32_t *n_tokens, uint32_t nq,
+                                 uint32_t len, const rq_maxsim_params_t *params, float *out_dist, rq_attr_value_t *out_keys, uint32_t *out_n) {
+    return by_id_done(maxsim_exact_host(idx, MaxsimExactIO{postings, tokens, n_tokens, len, out_dist, out_keys, out_n}, nq, params));
+}
+rq_status rq_exact_search_maxsim_device(const rq_index *idx, const rq_postings *postings, const float *d_tokens, const uint32_t *d_n_tokens,
+                                        uint32_t nq, uint32_t len, const rq_maxsim_params_t *params, float *d_out_dist,
+                                        rq_attr_value_t *d_out_keys, uint32_t *d_out_n) {
+    return by_id_done(maxsim_exact_device(idx, MaxsimExactIO{postings, d_tokens, d_n_tokens, len, d_out_dist, d_out_keys, d_out_n}, nq, params));
+}
+rq_status rq_last_maxsim_exact_stats(rq_maxsim_exact_stats_t *out) {
+    if (!out) return fail(RQ_ERR_INVALID, "null argument");
+    return copy_out_sized(out, g_maxsim_exact_stats);
+}
+
 // ---- multi-vector search over documents named by a column (host_maxsim_keyed.h) ----
 static MaxsimKeyedIn maxsim_keyed_in(const rq_postings *postings, const rq_attr_value_t *keys, rq_attr_value_t *out_keys) {
     MaxsimKeyedIn kin;

@@ -1469,6 +1469,44 @@ class RaBitQ:
         """The calling thread's last multi-vector call (include/rabitq_hip.h: rq_maxsim_stats_t)."""
         return last_maxsim_stats()
 
+    def exact_search_maxsim(self, tokens, topk: int, by: Postings = None, n_tokens=None, prefilter: bool = True) -> "MaxSimResult":
+        """The true topk documents of the postings `by` for every query's tokens (B x T x d): the Chamfer sum of maxsim_scores over
+        EVERY document, the topk smallest (sum, key) -- the ground truth query_batch_maxsim(..., by=by) is measured against.  A
+        bound pass on the matrix cores leaves only the documents that can still be among the best to the exact scoring;
+        prefilter=False scores every document (the same bits).  MaxSimResult.candidates = the documents of the postings."""
+        if by is None:
+            raise ValueError("by= (the postings that name the documents) is required")
+        t, nt = self._maxsim_tokens(tokens, n_tokens)
+        prm = self._maxsim_params(t.shape[1], None, by, topk, 0, prefilter)
+        B, cells = t.shape[0], (t.shape[0], max(int(topk), 1))
+        dist = np.full(cells, np.nan, dtype=np.float32)
+        img, cnt = np.zeros(cells, dtype=np.uint64), np.zeros(B, dtype=np.uint32)
+        check(lib().rq_exact_search_maxsim(self._h, by._h, _addr(t), _addr(nt), B, t.shape[2], C.byref(prm), _addr(dist), _addr(img), _addr(cnt)))
+        return MaxSimResult(dist, by._values_of(img), cnt, np.full(B, last_maxsim_exact_stats()["documents"], dtype=np.uint32))
+
+    def exact_search_maxsim_device(self, tokens_ptr: int, n_tokens_ptr: int, nq: int, T: int, length: int, topk: int, by: Postings,
+                                   out_dist_ptr: int = 0, out_docs_ptr: int = 0, out_n_ptr: int = 0, prefilter: bool = True) -> None:
+        """exact_search_maxsim with tokens and outputs in device memory (raw addresses; n_tokens 0 = none); out_docs_ptr receives
+        nq x topk 8-byte keys."""
+        prm = self._maxsim_params(T, None, by, topk, 0, prefilter)
+        check(lib().rq_exact_search_maxsim_device(self._h, by._h, C.c_void_p(tokens_ptr), C.c_void_p(n_tokens_ptr), nq, length, C.byref(prm),
+                                                  C.c_void_p(out_dist_ptr), C.c_void_p(out_docs_ptr), C.c_void_p(out_n_ptr)))
+
+    def maxsim_recall(self, tokens, probe: int, topk: int, by: Postings = None, fetch=None, n_tokens=None, filter: Filter = None) -> float:
+        """What fraction of the true topk documents query_batch_maxsim(tokens, probe, topk, fetch=fetch, by=by) returns: pooled over
+        the queries, |returned n exact| / |exact| (no exact document at all: 1.0).  Refused with a filter: the exact form takes none."""
+        if filter is not None:
+            raise _lib.RabitqError(-6, "maxsim_recall with a filter: exact_search_maxsim takes no filter")
+        truth = self.exact_search_maxsim(tokens, topk, by=by, n_tokens=n_tokens)
+        got = self.query_batch_maxsim(tokens, probe, topk, fetch=fetch, n_tokens=n_tokens, by=by)
+        hit = sum(len(np.intersect1d(got.docs[b, :got.counts[b]], truth.docs[b, :truth.counts[b]])) for b in range(truth.counts.size))
+        return hit / int(truth.counts.sum()) if truth.counts.sum() else 1.0
+
+    @staticmethod
+    def last_maxsim_exact_stats() -> dict:
+        """The calling thread's last exact multi-vector search (include/rabitq_hip.h: rq_maxsim_exact_stats_t)."""
+        return last_maxsim_exact_stats()
+
     @staticmethod
     def _recall_of(ids, cnt, exact_ids, exact_cnt) -> float:
         """mean over the queries with a non-empty exact answer of |query ids n exact ids| / exact count"""
@@ -1927,6 +1965,13 @@ def last_maxsim_stats() -> dict:
     st = _lib.MaxsimStatsT()
     check(lib().rq_last_maxsim_stats(C.byref(st)))
     return {name: getattr(st, name) for name, _ in _lib.MaxsimStatsT._fields_ if name not in ("struct_size", "reserved0")}
+
+
+def last_maxsim_exact_stats() -> dict:
+    """The calling thread's last exact multi-vector search (include/rabitq_hip.h: rq_last_maxsim_exact_stats)."""
+    st = _lib.MaxsimExactStatsT()
+    check(lib().rq_last_maxsim_exact_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _lib.MaxsimExactStatsT._fields_ if name not in ("struct_size", "reserved0")}
 
 
 def last_keyed_stats() -> dict:
