@@ -117,7 +117,9 @@ typedef struct {
  * 0.22.0: the complete exact grouped search, additions only -- rq_exact_search_grouped_full*, rq_group_full_stats_t,
  * rq_last_group_full_stats; no existing call, refusal or output changes, and postings on which it is never called allocate as before;
  * 0.23.0: exact multi-vector search, additions only -- rq_exact_search_maxsim*, rq_maxsim_exact_stats_t, rq_last_maxsim_exact_stats;
- * rq_maxsim_params_t and every existing call, refusal and output are unchanged.
+ * rq_maxsim_params_t and every existing call, refusal and output are unchanged;
+ * 0.24.0: additions only: restricted postings and the filtered exact multi-vector search -- rq_postings_restrict,
+ * rq_exact_search_maxsim_filtered*; no existing call, refusal or output changes.
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -1347,7 +1349,8 @@ rq_status rq_query_batch_maxsim_keyed_device(const rq_index *idx, const rq_posti
  *   inputs give the same bits on every run, with RQ_MAXSIM_NO_PREFILTER (every document scored on the exact path) and for every
  *   split of the work: the bound pass that runs otherwise only decides which documents are scored, never a score.
  * params: rq_maxsim_params_t as it is.  doc_stride must be 0 and fetch must be 0 (RQ_ERR_INVALID), tokens in [1, 256]
- *   (RQ_ERR_INVALID), topk in [1, 2048] (RQ_ERR_UNSUPPORTED).  THERE IS NO FILTER ARGUMENT in this revision: every posting counts.
+ *   (RQ_ERR_INVALID), topk in [1, 2048] (RQ_ERR_UNSUPPORTED).  These entries take no filter: every posting counts
+ *   (under a filter: rq_exact_search_maxsim_filtered, below).
  * LIMITS.  Those of the section above: tiered and split-row indexes, shards, dim > 4096 (RQ_ERR_UNSUPPORTED).  Null arguments and
  *   the parameter checks come before a device is looked for and before the index or the postings are read.  nq == 0 is RQ_OK.
  *   _device form: tokens, n_tokens and the outputs in device memory; it returns with its outputs complete.
@@ -1379,6 +1382,34 @@ rq_status rq_exact_search_maxsim_device(const rq_index *idx, const rq_postings *
                                         const uint32_t *d_n_tokens /* nullable */, uint32_t nq, uint32_t len, const rq_maxsim_params_t *params,
                                         float *d_out_dist, rq_attr_value_t *d_out_keys, uint32_t *d_out_n);
 rq_status rq_last_maxsim_exact_stats(rq_maxsim_exact_stats_t *out);
+
+/* ---- restricted postings, and the exact multi-vector search under a filter (0.24.0, additions only) ---------------------------- */
+/* rq_postings_restrict: *out = the intersection of the postings p with the filter f (both of the same index), made on the device,
+ *   as a postings object of its own over p's column and type.  The segment of a value holds the positions of p's segment that f
+ *   admits, in p's order; a value whose segment becomes empty is dropped; the values stay ascending in the column type's order.
+ *   An all-admitting filter gives p's arrays again, a filter that admits nothing a valid object without a value.  *out carries p's
+ *   generation and removal epoch: it is refused as stale exactly when p would be, and rq_postings_info / _values / _counts /
+ *   _positions_device / _free and EVERY entry that takes postings treat it as any other -- rq_exact_search_keyed*,
+ *   rq_exact_search_grouped_full*, rq_maxsim_scores_keyed*, rq_query_batch_maxsim_keyed*, rq_exact_search_maxsim* all have a
+ *   filtered form through it.  Nothing of the index, of p's arrays or of f is written.
+ *   Refusals, in this order: a null argument (RQ_ERR_INVALID, before a device is looked for); f made for another index than p;
+ *   p stale; f stale (the filter's own checks).  Cost: one streaming pass, about 4 bytes read and at most 8 written and read
+ *   again per posting plus the filter words, and work memory of about 4.2 bytes per posting of p for the call.
+ * rq_exact_search_maxsim_filtered*: rq_exact_search_maxsim* with `filter` after the postings, bit for bit that entry over
+ *   rq_postings_restrict(postings, filter): a document is its ADMITTED rows, a document without one does not exist, and
+ *   rq_maxsim_exact_stats_t.documents is the restricted count.  The restricted object is made for the call and freed after it: a
+ *   caller with many batches under one filter holds rq_postings_restrict's result and calls the unfiltered entry.  A null filter
+ *   is the unfiltered entry.  Refusals: the unfiltered entry's, in its order, then rq_postings_restrict's.
+ *   (rq_query_batch_maxsim_keyed's filter restricts only its source query and scores a found document over ALL its rows; the two
+ *   agree for filters that admit whole documents.) */
+rq_status rq_postings_restrict(const rq_postings *p, const rq_filter *f, rq_postings **out);
+rq_status rq_exact_search_maxsim_filtered(const rq_index *idx, const rq_postings *postings, const rq_filter *filter /* nullable */,
+                                          const float *tokens, const uint32_t *n_tokens /* nullable */, uint32_t nq, uint32_t len,
+                                          const rq_maxsim_params_t *params, float *out_dist, rq_attr_value_t *out_keys, uint32_t *out_n);
+rq_status rq_exact_search_maxsim_filtered_device(const rq_index *idx, const rq_postings *postings, const rq_filter *filter /* nullable */,
+                                                 const float *d_tokens, const uint32_t *d_n_tokens /* nullable */, uint32_t nq, uint32_t len,
+                                                 const rq_maxsim_params_t *params, float *d_out_dist, rq_attr_value_t *d_out_keys,
+                                                 uint32_t *d_out_n);
 
 /* ---- the complete exact grouped search: the true topk groups from one pass over all rows (0.22.0, additions only) ------------- */
 /* rq_exact_search_grouped answers "grouped top-fetch" (fetch <= 2048): when a query's nearest 3 000 rows share one value it returns

@@ -54,6 +54,7 @@ EXPORTS = [
     "rq_exact_search_keyed", "rq_exact_search_keyed_device", "rq_last_keyed_stats", "rq_keyed_tuning",
     "rq_maxsim_scores_keyed", "rq_maxsim_scores_keyed_device", "rq_query_batch_maxsim_keyed", "rq_query_batch_maxsim_keyed_device",
     "rq_exact_search_maxsim", "rq_exact_search_maxsim_device", "rq_last_maxsim_exact_stats",
+    "rq_postings_restrict", "rq_exact_search_maxsim_filtered", "rq_exact_search_maxsim_filtered_device",
     "rq_exact_search_grouped_full", "rq_exact_search_grouped_full_device", "rq_last_group_full_stats",
 ]
 
@@ -522,6 +523,9 @@ def lib():
         "rq_exact_search_maxsim": (i32, [vp, vp, f32p, u32p, u32, u32, C.POINTER(MaxsimParamsT), f32p, vp, u32p]),
         "rq_exact_search_maxsim_device": (i32, [vp, vp, f32p, u32p, u32, u32, C.POINTER(MaxsimParamsT), f32p, vp, u32p]),
         "rq_last_maxsim_exact_stats": (i32, [C.POINTER(MaxsimExactStatsT)]),
+        "rq_postings_restrict": (i32, [vp, vp, pp]),
+        "rq_exact_search_maxsim_filtered": (i32, [vp, vp, vp, f32p, u32p, u32, u32, C.POINTER(MaxsimParamsT), f32p, vp, u32p]),
+        "rq_exact_search_maxsim_filtered_device": (i32, [vp, vp, vp, f32p, u32p, u32, u32, C.POINTER(MaxsimParamsT), f32p, vp, u32p]),
         "rq_postings_create": (i32, [vp, C.c_char_p, pp]),
         "rq_postings_free": (None, [vp]),
         "rq_postings_info": (i32, [vp, C.POINTER(PostingsInfoT)]),

@@ -64,6 +64,7 @@
 #include "host_keyed.h"
 #include "host_maxsim_keyed.h"
 #include "host_maxsim_exact.h"
+#include "host_postings_restrict.h"
 #include "host_group_full.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1436,6 +1437,18 @@ rq_status rq_exact_search_maxsim_device(const rq_index *idx, const rq_postings *
 rq_status rq_last_maxsim_exact_stats(rq_maxsim_exact_stats_t *out) {
     if (!out) return fail(RQ_ERR_INVALID, "null argument");
     return copy_out_sized(out, g_maxsim_exact_stats);
+}
+// ---- restricted postings and the filtered exact multi-vector search (host_postings_restrict.h) ----
+rq_status rq_postings_restrict(const rq_postings *p, const rq_filter *f, rq_postings **out) { return by_id_done(postings_restrict(p, f, out)); }
+rq_status rq_exact_search_maxsim_filtered(const rq_index *idx, const rq_postings *postings, const rq_filter *filter, const float *tokens,
+                                          const uint32_t *n_tokens, uint32_t nq, uint32_t len, const rq_maxsim_params_t *params, float *out_dist,
+                                          rq_attr_value_t *out_keys, uint32_t *out_n) {
+    return by_id_done(maxsim_exact_filtered(idx, MaxsimExactIO{postings, tokens, n_tokens, len, out_dist, out_keys, out_n}, filter, nq, params, false));
+}
+rq_status rq_exact_search_maxsim_filtered_device(const rq_index *idx, const rq_postings *postings, const rq_filter *filter, const float *d_tokens,
+                                                 const uint32_t *d_n_tokens, uint32_t nq, uint32_t len, const rq_maxsim_params_t *params,
+                                                 float *d_out_dist, rq_attr_value_t *d_out_keys, uint32_t *d_out_n) {
+    return by_id_done(maxsim_exact_filtered(idx, MaxsimExactIO{postings, d_tokens, d_n_tokens, len, d_out_dist, d_out_keys, d_out_n}, filter, nq, params, true));
 }
 
 // ---- multi-vector search over documents named by a column (host_maxsim_keyed.h) ----

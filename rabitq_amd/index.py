@@ -275,6 +275,15 @@ class Postings:
         check(lib().rq_postings_positions_device(self._h, img, C.c_void_p(out.data_ptr()), count.value, C.byref(count)))
         return np.sort(out.cpu().numpy().view(np.uint32))
 
+    def restrict(self, filter: "Filter") -> "Postings":
+        """These postings under a filter of the same index, made on the device (rq_postings_restrict): every value keeps the
+        positions the filter admits, in order; a value left without one is dropped.  The result is a Postings like any other --
+        `by=p.restrict(f)` gives exact_search_keyed, exact_search_grouped, maxsim_scores, query_batch_maxsim and
+        exact_search_maxsim their filtered form -- and is stale exactly when these postings are."""
+        h = C.c_void_p()
+        check(lib().rq_postings_restrict(self._h, _fh(filter), C.byref(h)))
+        return Postings(self.index, h, self.column)
+
     def close(self):
         if getattr(self, "_h", None):
             lib().rq_postings_free(self._h)
@@ -1469,11 +1478,16 @@ class RaBitQ:
         """The calling thread's last multi-vector call (include/rabitq_hip.h: rq_maxsim_stats_t)."""
         return last_maxsim_stats()
 
-    def exact_search_maxsim(self, tokens, topk: int, by: Postings = None, n_tokens=None, prefilter: bool = True) -> "MaxSimResult":
+    def exact_search_maxsim(self, tokens, topk: int, by: Postings = None, n_tokens=None, prefilter: bool = True,
+                            filter: Filter = None) -> "MaxSimResult":
         """The true topk documents of the postings `by` for every query's tokens (B x T x d): the Chamfer sum of maxsim_scores over
         EVERY document, the topk smallest (sum, key) -- the ground truth query_batch_maxsim(..., by=by) is measured against.  A
         bound pass on the matrix cores leaves only the documents that can still be among the best to the exact scoring;
-        prefilter=False scores every document (the same bits).  MaxSimResult.candidates = the documents of the postings."""
+        prefilter=False scores every document (the same bits).  MaxSimResult.candidates = the documents of the postings.
+        filter: the same search over by.restrict(filter), bit for bit -- a document is its ADMITTED rows, one without an admitted
+        row does not exist.  (query_batch_maxsim(..., filter=) restricts only its source query and scores a found document over
+        ALL its rows: the two agree for filters that admit whole documents, the usual case since attributes are per document.)
+        The restricted postings are made for the call; with many batches under one filter hold by.restrict(filter) and pass it."""
         if by is None:
             raise ValueError("by= (the postings that name the documents) is required")
         t, nt = self._maxsim_tokens(tokens, n_tokens)
@@ -1481,22 +1495,26 @@ class RaBitQ:
         B, cells = t.shape[0], (t.shape[0], max(int(topk), 1))
         dist = np.full(cells, np.nan, dtype=np.float32)
         img, cnt = np.zeros(cells, dtype=np.uint64), np.zeros(B, dtype=np.uint32)
-        check(lib().rq_exact_search_maxsim(self._h, by._h, _addr(t), _addr(nt), B, t.shape[2], C.byref(prm), _addr(dist), _addr(img), _addr(cnt)))
+        check(lib().rq_exact_search_maxsim_filtered(self._h, by._h, _fh(filter), _addr(t), _addr(nt), B, t.shape[2], C.byref(prm), _addr(dist),
+                                                    _addr(img), _addr(cnt)))
         return MaxSimResult(dist, by._values_of(img), cnt, np.full(B, last_maxsim_exact_stats()["documents"], dtype=np.uint32))
 
     def exact_search_maxsim_device(self, tokens_ptr: int, n_tokens_ptr: int, nq: int, T: int, length: int, topk: int, by: Postings,
-                                   out_dist_ptr: int = 0, out_docs_ptr: int = 0, out_n_ptr: int = 0, prefilter: bool = True) -> None:
+                                   out_dist_ptr: int = 0, out_docs_ptr: int = 0, out_n_ptr: int = 0, prefilter: bool = True,
+                                   filter: Filter = None) -> None:
         """exact_search_maxsim with tokens and outputs in device memory (raw addresses; n_tokens 0 = none); out_docs_ptr receives
         nq x topk 8-byte keys."""
         prm = self._maxsim_params(T, None, by, topk, 0, prefilter)
-        check(lib().rq_exact_search_maxsim_device(self._h, by._h, C.c_void_p(tokens_ptr), C.c_void_p(n_tokens_ptr), nq, length, C.byref(prm),
-                                                  C.c_void_p(out_dist_ptr), C.c_void_p(out_docs_ptr), C.c_void_p(out_n_ptr)))
+        check(lib().rq_exact_search_maxsim_filtered_device(self._h, by._h, _fh(filter), C.c_void_p(tokens_ptr), C.c_void_p(n_tokens_ptr), nq,
+                                                           length, C.byref(prm), C.c_void_p(out_dist_ptr), C.c_void_p(out_docs_ptr),
+                                                           C.c_void_p(out_n_ptr)))
 
     def maxsim_recall(self, tokens, probe: int, topk: int, by: Postings = None, fetch=None, n_tokens=None, filter: Filter = None) -> float:
         """What fraction of the true topk documents query_batch_maxsim(tokens, probe, topk, fetch=fetch, by=by) returns: pooled over
-        the queries, |returned n exact| / |exact| (no exact document at all: 1.0).  Refused with a filter: the exact form takes none."""
+        the queries, |returned n exact| / |exact| (no exact document at all: 1.0).  Refused with a filter: the two searches read a
+        filter differently (exact_search_maxsim scores admitted rows only, query_batch_maxsim whole documents)."""
         if filter is not None:
-            raise _lib.RabitqError(-6, "maxsim_recall with a filter: exact_search_maxsim takes no filter")
+            raise _lib.RabitqError(-6, "maxsim_recall with a filter: not supported (compare exact_search_maxsim(filter=) yourself)")
         truth = self.exact_search_maxsim(tokens, topk, by=by, n_tokens=n_tokens)
         got = self.query_batch_maxsim(tokens, probe, topk, fetch=fetch, n_tokens=n_tokens, by=by)
         hit = sum(len(np.intersect1d(got.docs[b, :got.counts[b]], truth.docs[b, :truth.counts[b]])) for b in range(truth.counts.size))
