@@ -119,7 +119,9 @@ typedef struct {
  * 0.23.0: exact multi-vector search, additions only -- rq_exact_search_maxsim*, rq_maxsim_exact_stats_t, rq_last_maxsim_exact_stats;
  * rq_maxsim_params_t and every existing call, refusal and output are unchanged;
  * 0.24.0: additions only: restricted postings and the filtered exact multi-vector search -- rq_postings_restrict,
- * rq_exact_search_maxsim_filtered*; no existing call, refusal or output changes.
+ * rq_exact_search_maxsim_filtered*; no existing call, refusal or output changes;
+ * 0.25.0: additions only: keyed exact search on wide, split-row and tiered indexes -- rq_exact_search_keyed_tiered*; rq_keyed_stats_t
+ * and every existing call, refusal and output are unchanged.
  * A host checks rq_abi_version() == RQ_ABI_VERSION once after loading the library. */
 #define RQ_ABI_VERSION 4
 uint32_t rq_abi_version(void);
@@ -643,7 +645,8 @@ rq_status rq_exact_range_search(const rq_index *idx, const rq_filter *filter /* 
  * Refused: what the plain entries refuse for other reasons than the layout -- topk outside [1, 2048], dim > 4096
  * (RQ_ERR_UNSUPPORTED), unknown flag bits, a foreign or stale filter (RQ_ERR_INVALID); a null pointer is RQ_ERR_INVALID before a
  * device is looked for; nq == 0 is RQ_OK (the range form: as rq_exact_range_search).  The plain entries keep refusing split-row and
- * tiered indexes, and so do the grouped, diverse and keyed exact forms and rq_neighbours_of_exact.
+ * tiered indexes, and so do the grouped, diverse and keyed exact forms and rq_neighbours_of_exact (the keyed form has an entry of
+ * its own for these layouts since 0.25.0: rq_exact_search_keyed_tiered).
  * Method: the phases of rq_exact_search.  The scan runs over the PHYSICAL rows of one tier per launch, the HBM array
  * and the host array on two streams, and recovers a row's position from the tier records of its list.  On split rows it reads the
  * FIRST PLANE alone -- already a bf16 image of the row: half the bytes, no conversion before the matrix pass -- with a margin
@@ -1241,7 +1244,8 @@ rq_status rq_last_maxsim_stats(rq_maxsim_stats_t *out);
  * WIDE DIMENSIONS.  The matrix pass of the keyed scan holds a query tile and four row slabs in LDS and exists for dim <= 448 only
  * (rq_exact_search pre-filters up to dim 2432).  From dim 512 on every (query, row of its key) pair gets its exact distance and a
  * query takes as many candidate slots (12 bytes each) as its key has rows: correct, but on a large key slower and heavier on memory
- * than the filtered rq_exact_search it stands in for -- prefer that one there.
+ * than the filtered rq_exact_search it stands in for -- prefer that one there.  rq_exact_search_keyed_tiered (below) has a matrix
+ * pass up to dim 2048.
  * rq_keyed_tuning: developer knob for measurements, process-wide; results never depend on it.  chunk_rows = postings per work item,
  * small_rows = the segment size below which a key takes neither bound nor matrix pass, slabs = 1: one LDS slab per wave everywhere,
  * 2 (or 0): the double-buffered scan where it exists (dim 64); 0 = the default for each.
@@ -1286,6 +1290,30 @@ rq_status rq_exact_search_keyed(const rq_index *idx, const rq_postings *postings
                                 const rq_exact_params_t *params /* nullable */, float *out_dist, uint32_t *out_id, uint32_t *out_n);
 rq_status rq_last_keyed_stats(rq_keyed_stats_t *out);
 rq_status rq_keyed_tuning(uint32_t chunk_rows, uint32_t small_rows, uint32_t slabs);
+
+/* ---- the keyed exact search on wide, split-row and tiered indexes (0.25.0, additions only) ------------------------------------ */
+/* rq_exact_search_keyed_tiered*: rq_exact_search_keyed*'s arguments, contract and statistics (rq_last_keyed_stats) on EVERY f32-row
+ * index at every dim <= 4096: plain, split rows, tiered, tiered + split, tiered + plain.  Query b gets bit for bit what the exact
+ * search returns under a filter admitting {rows live and holding keys[b] when the postings were made} intersected with `filter` --
+ * the topk smallest (Ord32(e), id) with e < f32::MAX, e the library's one exact-order distance (both planes of a split row);
+ * out_n[b] is written and slots past it are left untouched; an absent key gives 0.  The result does not depend on params, options,
+ * the batch, how the work is split or the tier a row lives in; lazy removals and stale postings or filters are handled exactly as
+ * by rq_exact_search_keyed.  topk limits, the order of the null-argument checks and the refusals without a device are that entry's.
+ * WHICH PATH AN INDEX TAKES.
+ *   forwarded to rq_exact_search_keyed as it is: half-precision and byte rows at any dim, and plain f32 rows all in HBM at
+ *     dim <= 448 (where that entry has its own matrix pass);
+ *   the dimension-sliced scan (matrix pass, prefilter = 1): plain f32 rows at 512 <= dim <= 2048, and split-row and tiered indexes
+ *     at every dim <= 2048 -- of a split row only the first plane (2 dim bytes) is gathered, as it stands;
+ *   dim > 2048 (the query tile no longer fits in LDS): the exact-only form, every (query, row of its key) pair gets its exact
+ *     distance, prefilter = 0.
+ * rq_keyed_tuning's chunk_rows and small_rows act here as there; slabs is not read. */
+rq_status rq_exact_search_keyed_tiered_device(const rq_index *idx, const rq_postings *postings, const rq_filter *filter /* nullable */,
+                                              const float *d_queries, uint32_t nq, uint32_t len, const rq_attr_value_t *keys /* host */,
+                                              uint32_t topk, const rq_exact_params_t *params /* nullable */, float *d_out_dist,
+                                              uint32_t *d_out_id, uint32_t *d_out_n);
+rq_status rq_exact_search_keyed_tiered(const rq_index *idx, const rq_postings *postings, const rq_filter *filter /* nullable */,
+                                       const float *queries, uint32_t nq, uint32_t len, const rq_attr_value_t *keys, uint32_t topk,
+                                       const rq_exact_params_t *params /* nullable */, float *out_dist, uint32_t *out_id, uint32_t *out_n);
 
 /* ---- multi-vector search over documents named by a column: MaxSim by postings (0.21.0, additions only) ------------------------ */
 /* The multi-vector entries above with a postings object in the place of the document stride: documents of any length, ids the

@@ -52,6 +52,7 @@ EXPORTS = [
     "rq_maxsim_scores", "rq_maxsim_scores_device", "rq_query_batch_maxsim", "rq_query_batch_maxsim_device", "rq_last_maxsim_stats",
     "rq_postings_create", "rq_postings_free", "rq_postings_info", "rq_postings_values", "rq_postings_counts", "rq_postings_positions_device",
     "rq_exact_search_keyed", "rq_exact_search_keyed_device", "rq_last_keyed_stats", "rq_keyed_tuning",
+    "rq_exact_search_keyed_tiered", "rq_exact_search_keyed_tiered_device",
     "rq_maxsim_scores_keyed", "rq_maxsim_scores_keyed_device", "rq_query_batch_maxsim_keyed", "rq_query_batch_maxsim_keyed_device",
     "rq_exact_search_maxsim", "rq_exact_search_maxsim_device", "rq_last_maxsim_exact_stats",
     "rq_postings_restrict", "rq_exact_search_maxsim_filtered", "rq_exact_search_maxsim_filtered_device",
@@ -534,6 +535,8 @@ def lib():
         "rq_postings_positions_device": (i32, [vp, u64, u32p, u64, C.POINTER(u64)]),   # (key: the union's u64 image, see AttrValue)
         "rq_exact_search_keyed": (i32, [vp, vp, vp, f32p, u32, u32, vp, u32, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
         "rq_exact_search_keyed_device": (i32, [vp, vp, vp, f32p, u32, u32, vp, u32, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
+        "rq_exact_search_keyed_tiered": (i32, [vp, vp, vp, f32p, u32, u32, vp, u32, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
+        "rq_exact_search_keyed_tiered_device": (i32, [vp, vp, vp, f32p, u32, u32, vp, u32, C.POINTER(ExactParamsT), f32p, u32p, u32p]),
         "rq_last_keyed_stats": (i32, [C.POINTER(KeyedStatsT)]),
         "rq_keyed_tuning": (i32, [u32, u32, u32]),
         "rq_exact_search_grouped_full": (i32, [vp, vp, vp, f32p, u32, u32, C.POINTER(ExactParamsT), C.POINTER(GroupParamsT), f32p, u32p, u64p, u32p, u32p, u32p]),

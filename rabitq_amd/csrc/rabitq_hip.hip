@@ -62,6 +62,7 @@
 #include "host_diverse.h"
 #include "host_maxsim.h"
 #include "host_keyed.h"
+#include "host_keyed_tiered.h"
 #include "host_maxsim_keyed.h"
 #include "host_maxsim_exact.h"
 #include "host_postings_restrict.h"
@@ -1406,6 +1407,17 @@ rq_status rq_exact_search_keyed(const rq_index *idx, const rq_postings *postings
                                 uint32_t len, const rq_attr_value_t *keys, uint32_t topk, const rq_exact_params_t *params, float *out_dist,
                                 uint32_t *out_id, uint32_t *out_n) {
     return by_id_done(keyed_search_host(idx, postings, filter, queries, nq, len, keys, topk, params, out_dist, out_id, out_n));
+}
+// ---- the same two on every f32-row index at every dimension: wide, split rows, tiered (host_keyed_tiered.h) ----
+rq_status rq_exact_search_keyed_tiered_device(const rq_index *idx, const rq_postings *postings, const rq_filter *filter, const float *d_queries,
+                                              uint32_t nq, uint32_t len, const rq_attr_value_t *keys, uint32_t topk,
+                                              const rq_exact_params_t *params, float *d_out_dist, uint32_t *d_out_id, uint32_t *d_out_n) {
+    return by_id_done(keyed_tiered_search_device(idx, postings, filter, d_queries, nq, len, keys, topk, params, d_out_dist, d_out_id, d_out_n));
+}
+rq_status rq_exact_search_keyed_tiered(const rq_index *idx, const rq_postings *postings, const rq_filter *filter, const float *queries,
+                                       uint32_t nq, uint32_t len, const rq_attr_value_t *keys, uint32_t topk, const rq_exact_params_t *params,
+                                       float *out_dist, uint32_t *out_id, uint32_t *out_n) {
+    return by_id_done(keyed_tiered_search_host(idx, postings, filter, queries, nq, len, keys, topk, params, out_dist, out_id, out_n));
 }
 // ---- the complete exact grouped search (host_group_full.h): the true topk groups from one pass over all rows ----
 rq_status rq_exact_search_grouped_full(const rq_index *idx, const rq_postings *postings, const rq_filter *filter, const float *queries, uint32_t nq,

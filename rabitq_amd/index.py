@@ -1017,6 +1017,34 @@ class RaBitQ:
                                                  C.byref(prm) if prm is not None else None, C.c_void_p(out_dist_ptr),
                                                  C.c_void_p(out_id_ptr), C.c_void_p(out_n_ptr)))
 
+    def exact_search_keyed_tiered(self, queries, keys, topk: int, by: Postings, filter: Filter = None, params=None):
+        """exact_search_keyed on every f32-row index at every dimension -- wide (512 and above), split rows, tiered -- with the same
+        answer and the same statistics (last_keyed_stats): a matrix pass up to dim 2048, of a split row over its first plane alone.
+        Indexes exact_search_keyed serves with its own matrix pass are forwarded to it."""
+        q = _f32(queries)
+        if q.ndim != 2:
+            raise _lib.RabitqError(-1, "queries must be 2-D")
+        B = q.shape[0]
+        img = by._keys(keys)
+        if img.shape != (B,):
+            raise ValueError(f"keys must hold one key per query ({B}), not shape {img.shape}")
+        d = np.full((B, max(topk, 1)), np.nan, dtype=np.float32)
+        ids = np.full((B, max(topk, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        cnt = np.zeros(B, dtype=np.uint32)
+        prm = self._exact_params(params)
+        check(lib().rq_exact_search_keyed_tiered(self._h, by._h, _fh(filter), _addr(q), B, q.shape[1], _addr(img), topk,
+                                                 C.byref(prm) if prm is not None else None, _addr(d), _addr(ids), _addr(cnt)))
+        return d, ids, cnt
+
+    def exact_search_keyed_tiered_device(self, q_ptr: int, nq: int, length: int, keys, topk: int, by: Postings, out_dist_ptr: int,
+                                         out_id_ptr: int, out_n_ptr: int, filter: Filter = None, params=None):
+        """exact_search_keyed_tiered with queries and outputs already in device memory (raw addresses); keys stay a host array."""
+        img = by._keys(keys)
+        prm = self._exact_params(params)
+        check(lib().rq_exact_search_keyed_tiered_device(self._h, by._h, _fh(filter), C.c_void_p(q_ptr), nq, length, _addr(img), topk,
+                                                        C.byref(prm) if prm is not None else None, C.c_void_p(out_dist_ptr),
+                                                        C.c_void_p(out_id_ptr), C.c_void_p(out_n_ptr)))
+
     @staticmethod
     def last_keyed_stats() -> dict:
         return last_keyed_stats()
